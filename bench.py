@@ -35,6 +35,7 @@ SETUP_STEPS = 30
 SETUP_MS = 40.0         # untimed steady work in front of the warm-up steps (see main)
 MFMA_F16_PEAK_TFLOPS = 2500.0   # dense bf16/f16 MFMA
 VALU_LANE_OPS_PEAK = 256 * 4 * 32 * 2.4e9   # 256 CU x 4 SIMD32 x 2.4 GHz = 78.6e12 lane-ops/s
+DUMP_MAX_QUERIES = 1 << 22    # --dump-outputs: queries written at most (12 B each)
 
 
 def parse_args():
@@ -76,6 +77,9 @@ def parse_args():
                          "per-wave wall-clock stamps of the last pruned-scan launch, pipelined and one batch at a time")
     ap.add_argument("--cpu-queries", type=int, default=-1,
                     help="queries in the cpu_baseline sample (-1: sized for ~15 s, 0: skip)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/*.npy: "
+                         "indices.npy (the nearest index per query, float64) and dist2.npy (its squared distance, float32)")
     ap.add_argument("--selftest-launcher", action="store_true",
                     help="launcher rehearsal without GPUs: the ranks only form a gloo group, min-reduce packed keys "
                          "and rank 0 prints one JSON line (tests/test_host_logic.py)")
@@ -140,10 +144,8 @@ def selftest_launcher():
 
 def main():
     args = parse_args()
-    # Batches in flight run on streams of their own; the HIP runtime maps streams onto 4 hardware queues by default, and
-    # with four batch streams plus the default stream two of them then share a queue and serialise (4 in flight: 0.053 ms
-    # per step at n_local 2^21 against 0.044 for 3).  Eight queues: 4 in flight 0.042.  Must be set before HIP starts.
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+    # Batches in flight run on streams of their own, which the HIP runtime maps onto the hardware queues the environment
+    # gives the process; streams that share a queue serialise.  The process takes the environment's setting as it is.
     # (ranks started by an outside torchrun: the host driver only supports dmabuf IPC, RCCL fails without this)
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -538,6 +540,11 @@ def main():
     fence()
     elapsed = time.perf_counter() - t0
     launches, kern_ms = index.timing_read()
+    dumped = None
+    if args.dump_outputs:
+        # the last timed step's packed keys and indices, before anything after the timed region reuses their buffers
+        g_last, b_last = state["last"]
+        dumped = (keys_all[g_last, b_last].cpu().numpy(), outs_all[g_last, b_last].cpu().numpy())
     # outside the timed region: the dominant kernel alone on the GPU (one batch in flight), so the
     # roofline block can show both the pipelined-phase duration and the kernel's own
     torch.cuda.synchronize()
@@ -653,6 +660,8 @@ def main():
             line["cpu_baseline_16_threads"] = cpu_all
         if parity:
             line["parity_spot_check"] = parity
+        if dumped is not None:
+            dump_outputs(args.dump_outputs, *dumped)
         sys.stdout.flush()
         os.dup2(saved_stdout_fd, 1)
         print(json.dumps(line), flush=True)
@@ -678,6 +687,18 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, keys, indices):
+    """One step's answers as .npy files: indices (int32 -> float64, exact) and the squared distances carried in the high
+    word of the packed keys (float32 bits, exact).  12 B per query: beyond 2^22 queries only the first 2^22 are written
+    (48 MB), to stay under 64 MB in all."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    keys, indices = keys[:DUMP_MAX_QUERIES], indices[:DUMP_MAX_QUERIES]
+    dist2 = (keys.view(np.uint64) >> np.uint64(32)).astype(np.uint32).view(np.float32)
+    np.save(os.path.join(out_dir, "indices.npy"), indices.astype(np.float64))
+    np.save(os.path.join(out_dir, "dist2.npy"), dist2)
 
 
 def pmc_workload_key(k, m, n_local, shard_mode, emu_n, emu_r, world):

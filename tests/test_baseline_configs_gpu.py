@@ -179,3 +179,27 @@ def test_two_rank_flow_falls_back_to_index_ranges_when_one_rank_fails_before_the
     assert "index ranges" in doc["config"]["shards"] and doc["config"]["n_per_gpu"] == 1 << 20
     assert "index-range shards instead" in r.stderr
     assert doc["parity_spot_check"].startswith("8/8 sampled queries identical")
+
+
+def test_bench_dump_outputs_are_the_oracle_answers(oracle, tmp_path):
+    """bench.py --dump-outputs on the cell-pruned path: the last timed step's indices and squared distances, every query,
+    bit-exact against the oracle over the same synthetic set."""
+    k, m, n = 16, 1024, 1 << 21
+    env = dict(os.environ)
+    for name in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "KNN_BENCH_FORCE_DIST", "KNN_BENCH_REHEARSE_ON_ONE_GPU"):
+        env.pop(name, None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "%d,%d,%d" % (k, m, n), "--steps", "5",
+                        "--warmup", "1", "--cpu-queries", "0", "--dump-outputs", str(tmp_path)], capture_output=True, text=True,
+                       env=env, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    doc = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert doc["steps"] == 5
+    idx = np.load(tmp_path / "indices.npy")
+    d2 = np.load(tmp_path / "dist2.npy")
+    assert idx.dtype == np.float64 and d2.dtype == np.float32 and idx.shape == d2.shape == (m,)
+    Q, R = oracle.synth(m * k, 1000), oracle.synth(n * k, 1001)
+    want = oracle.v0(k, Q, R, threads=THREADS)
+    np.testing.assert_array_equal(idx, want.astype(np.float64))
+    Qm, Rm = Q.reshape(m, k), R.reshape(n, k)
+    want_d2 = np.array([oracle.dist2(Qm[j], Rm[want[j]]) for j in range(m)], dtype=np.float32)
+    np.testing.assert_array_equal(d2, want_d2)

@@ -591,3 +591,23 @@ def test_one_shot_cost_model_picks_the_pruned_scan_only_when_the_batch_repays_th
             pkg.set_option(name, 0)
     with pytest.raises(pkg.KnnError):
         pkg.debug_plan_shard(0, 1, 1)
+
+
+def test_bench_dump_outputs_writes_indices_and_distances_exactly(tmp_path):
+    """--dump-outputs: the packed keys' high word is the float32 squared distance, the indices go out as float64."""
+    b = _bench_module()
+    dist2 = np.array([0.0, 1.5, 3e-7, np.inf], dtype=np.float32)
+    idx = np.array([0, 7, 2147483646, 123456789], dtype=np.int32)
+    keys = ((dist2.view(np.uint32).astype(np.uint64) << np.uint64(32)) | idx.astype(np.uint64)).view(np.int64)
+    b.dump_outputs(str(tmp_path / "out"), keys, idx)
+    got_i = np.load(tmp_path / "out" / "indices.npy")
+    got_d = np.load(tmp_path / "out" / "dist2.npy")
+    assert got_i.dtype == np.float64 and got_d.dtype == np.float32
+    np.testing.assert_array_equal(got_i, idx.astype(np.float64))
+    np.testing.assert_array_equal(got_d.view(np.uint32), dist2.view(np.uint32))
+    # a larger answer: the first DUMP_MAX_QUERIES queries only (under 64 MB in all)
+    big = b.DUMP_MAX_QUERIES + 5
+    b.dump_outputs(str(tmp_path / "big"), np.zeros(big, dtype=np.int64), np.arange(big, dtype=np.int32))
+    got_i = np.load(tmp_path / "big" / "indices.npy")
+    assert got_i.shape == (b.DUMP_MAX_QUERIES,) and got_i[-1] == b.DUMP_MAX_QUERIES - 1
+    assert (tmp_path / "big" / "indices.npy").stat().st_size + (tmp_path / "big" / "dist2.npy").stat().st_size <= 64 << 20

@@ -3,8 +3,6 @@
 short timed region cost on top of K steady-state steps.  usage: fill_drain.py [n]"""
 import sys, time
 sys.path.insert(0, ".")
-import os
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch
 import multicore_hw2_amd as pkg
 k, m = 16, 1024
