@@ -252,6 +252,11 @@ int knn_index_query_host(knn_index *idx, int m, const float *queries_host, int *
  *             box); 1 = every cell-sorted layout; 2 = never.  Read when an index is built.  Costs one more pass over the rows at
  *             build time and ~100 instructions per (cell, 32 queries) at query time; results are identical either way.
  *             knn_get_option("cells_centred_builds") counts the layouts built so (read-only).
+ *   "cells_rows" the rows the cell-pruned scan reads (k <= 16, not for cell-range shards): 1 = the fp16 fragments (32 bytes
+ *             per row + a 4-byte norm); 2 = 8-bit codes in per-cell frames (8 bytes per half row: 16 bytes + the 4-byte norm),
+ *             which brings per-cell frames with it; 0 = library policy (8-bit rows for shards of >= 2^24 rows whose build
+ *             sample is uniform-like and not clustered).  Read when an index is built; results are identical either way.
+ *             knn_get_option("cells_u8_builds") counts the layouts built with 8-bit rows (read-only).
  *   "cells_lists" who makes a cell's list of queries (those of the batch that cannot rule the cell out) on the pruned path:
  *             1 = knn_cells_match_kernel in a launch of its own between the preparation and the scan (lists in memory),
  *             2 = the scan's waves for the items they take (same test, same arithmetic, lists in LDS: one launch and one
@@ -302,6 +307,10 @@ int knn_debug_shard_policy(int k, int m, long long n, int ndev);
  * current options: out = {filter layouts (0 none: exact kernels, 1 plain, 2 cell-sorted: the pruned scan), 1 if the exact scan
  * runs chunk by chunk under the copy, 1 if the grid index (k <= 4) serves it, copy calls of the streamed form}. */
 int knn_debug_plan_shard(int k, int m, long long rows, long long out[4]);
+/* Test hook (host arithmetic, no GPU): one row of k <= 16 coordinates through the 8-bit rows' quantiser (option "cells_rows"),
+ * v = (row - centre) x scale in fp32: codes[k] = its bytes, out[0] = the largest per-coordinate error bound, out[1] = eta for a
+ * query of largest |coordinate| amax.  0 on success. */
+int knn_debug_u8_row(int k, const float *row, const float *centre, float scale, double amax, unsigned char *codes, double out[2]);
 
 /* Test hook (host arithmetic only, no GPU needed): every size one scan launch of the cell-pruned path and the re-rank behind
  * it index with, for an index of `nitems` work items on a device of num_cu CUs and a batch of m <= 1024 queries:

@@ -375,6 +375,12 @@ int knn_set_option(const char *name, long long value)
         g_knn_cells_centre = (int)value;
         return KNN_OK;
     }
+    if (!strcmp(name, "cells_rows")) {
+        if (value < 0 || value > 2)
+            return fail(KNN_EINVAL, "knn_set_option: cells_rows must be 0 (auto), 1 (fp16 fragments) or 2 (8-bit rows in per-cell frames)");
+        g_knn_cells_rows = (int)value;
+        return KNN_OK;
+    }
     if (!strcmp(name, "cells_lists")) {
         if (value < 0 || value > 2)
             return fail(KNN_EINVAL, "knn_set_option: cells_lists must be 0 (auto), 1 (match launch) or 2 (the scan lists its own items)");
@@ -444,6 +450,10 @@ long long knn_get_option(const char *name)
         return (long long)g_knn_cells_centre.load();
     if (name && !strcmp(name, "cells_centred_builds"))   // read-only: cell-sorted layouts moved into per-cell frames so far
         return g_knn_cells_centred_builds.load();
+    if (name && !strcmp(name, "cells_rows"))
+        return (long long)g_knn_cells_rows.load();
+    if (name && !strcmp(name, "cells_u8_builds"))   // read-only: cell-sorted layouts given 8-bit rows so far
+        return g_knn_cells_u8_builds.load();
     if (name && !strcmp(name, "run_thresholds"))
         return g_opt_run_thresholds;
     if (name && !strcmp(name, "sample_stride"))
@@ -1632,3 +1642,4 @@ extern "C" void cudaCallback(int k, int m, int n, float *searchPoints, float *re
     }
     *results = out;
 }
+

@@ -139,6 +139,7 @@ __device__ __forceinline__ unsigned cell_bin(const float *__restrict__ bnd, int 
 // absolute where the scaled remainder falls into fp16's subnormal range (< 2^-14) and the matrix core flushes it.
 // knn_bound_consts carries both in rho.  +INF (padding, rows outside the box) -> (+INF, 0).
 typedef unsigned u4v __attribute__((ext_vector_type(4)));
+typedef unsigned u2v __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ unsigned pack_norm22(float n)
 {
@@ -1009,6 +1010,24 @@ __global__ __launch_bounds__(64 * CELL_MATCH_WAVES) void knn_cells_match_kernel(
 #define CELL_BATCH_RECORD_LIMIT (1u << 19)   // records of a batch beyond which it goes to the exact evaluation of its listed pairs
 #define CELL_SCAN_RUN 16      // DYN: consecutive items a block takes at a time; its next run lies gridDim.x runs further on
 
+// An 8-bit row tile's lane (8 codes, byte j = K-slot j) as the fp16 A operand (code - 128) / 128: v_perm_b32 puts each code under
+// the high byte 0x48 — the fp16 number 8 + code / 128, exact (8 <= x < 16: steps of 2^-7) — and one packed add of -9 per pair
+// leaves (code - 128) / 128, exact.  (perm selector byte i: 0-3 = bytes of the second source, 4-7 = bytes of the first.)
+typedef _Float16 h2v __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ h8 cell_widen_u8(u2v w)
+{
+    const h2v nine = {(_Float16)9.0f, (_Float16)9.0f};
+    h8 r;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const unsigned x = __builtin_amdgcn_perm(0x48484848u, w[i >> 1], (i & 1) ? 0x04030402u : 0x04010400u);
+        const h2v p = __builtin_bit_cast(h2v, x) - nine;
+        r[2 * i] = p[0];
+        r[2 * i + 1] = p[1];
+    }
+    return r;
+}
+
 // One (tile, block of 32 listed queries) step: scores + min tree + threshold test -> hit mask.
 template <int KT>
 __device__ __forceinline__ u64 cell_tile_step(const h8 (&a)[KT], const f4v *__restrict__ my_nrm, int p, int half, const h8 (&b)[KT], float th)
@@ -1059,8 +1078,11 @@ __device__ __forceinline__ u64 cell_tile_step_nif(const h8 (&a)[KT], const h8 (&
 // 10^-5 larger; mq x 0.999996 <= mq (1 - gamma)(1 - 10^-6)(1 - 2^-22) (gamma = 18 x 2^-24 = 1.07 x 10^-6; the 10^-6 is the slack
 // knn_threshold gives its own double arithmetic: the fp32 value is never below the double one — tests/test_cells_logic.py checks
 // 200 000 random pairs); the last subtraction rounds by at most 2^-24 (P + mq), 2.4 x 10^-7 (P + mq) is added.  A pair whose query does not fit the cell's frame: see the end.
+// U8 (8-bit rows): the constants of knn_bound_consts_u8(k, 1, scale_c, amax, er_c, nmax8_c) instead — emax = thp amax + er_c + 2 nu0,
+// er_c = the cell's cell_u8 word 0 taken 10^-6 larger (`er`), nmaxc = the cell's largest norm of the dequantised rows.
+template <bool U8 = false>
 __device__ __forceinline__ void cell_centred_operand(const float *__restrict__ s_q32, int k, unsigned qid, int half, bool valid,
-                                                     const float (&cc)[8], float scale, float ratio, float bmaxc, float nmaxc,
+                                                     const float (&cc)[8], float scale, float ratio, float bmaxc, float nmaxc, float er,
                                                      float dupq, float sqdq, h8 &b, float &th)
 {
 #pragma clang fp contract(off)
@@ -1081,7 +1103,8 @@ __device__ __forceinline__ void cell_centred_operand(const float *__restrict__ s
     mq = mq + __shfl_xor(mq, 32, KNN_WAVE);
     b = hv * (_Float16)-2.0f;   // exact: |coordinate| <= CELL_FRAME_AMAX = 2^14 below
     const float kf = (float)k;
-    const float emax = 4.8865e-4f * (a + bmaxc) + 1.2220e-4f;          // theta' (amax + bmax) + 2 nu0
+    const float emax = U8 ? 4.8865e-4f * a + er * 1.000001f + 1.2220e-4f   // theta' amax + er + 2 nu0
+                          : 4.8865e-4f * (a + bmaxc) + 1.2220e-4f;           // theta' (amax + bmax) + 2 nu0
     const float sqk = k <= 1 ? 1.0f : k <= 4 ? 2.0f : k <= 9 ? 3.0f : 4.0f;   // >= sqrt(k), k <= 16 (no square root here: the exact kernels' ISA is checked for FMAs)
     const float eta = sqk * emax, eta2 = kf * emax * emax;
     const float rho = 1.1921e-5f * (nmaxc + 16.0f * a * a) + 1.79e-7f + 4.77e-7f * nmaxc;
@@ -1692,7 +1715,9 @@ extern "C" int knn_debug_scan_stamps(unsigned long long *out)
 //       cell) pair are made here, from the fp32 query, the cell's frame and Dup_q (cell_centred_operand) — s_thr holds the
 //       batch's sqrt(Dup) bounds, s_dup the Dup values, the B operands' room in LDS stays unused
 // NIF:  16 < k <= 30: the norms ride in the fragments' K-slots 30, 31 (cell_tile_step_nif): no norm window
-template <bool DYN, int K, bool SELF, int KT = 1, bool CTR = false, bool NIF = false>
+// U8:   with CTR: `rf` / `rn` are the 8-bit rows and their norms (knn_cells_recentre_kernel) — 512-byte tiles, widened to fp16 in
+//       registers (cell_widen_u8) at every step; the pair's threshold from knn_bound_consts_u8's constants
+template <bool DYN, int K, bool SELF, int KT = 1, bool CTR = false, bool NIF = false, bool U8 = false>
 __global__ __launch_bounds__(64 * (KT == 1 && !CTR ? CELL_SCAN_WAVES : CELL_SCAN_WAVES_KT2), CTR ? 4 : KT == 1 ? 6 : 4) void knn_cells_scan_kernel(
     const h8 *__restrict__ rf, const float *__restrict__ rn, const u64 *__restrict__ items, unsigned nitems,
     const h8 *__restrict__ qfg, const float *__restrict__ thrg, int m, int m_padded,
@@ -1885,7 +1910,7 @@ __global__ __launch_bounds__(64 * (KT == 1 && !CTR ? CELL_SCAN_WAVES : CELL_SCAN
             // (round 3: blocks three and four of the list too — lists average 120 entries on the 2^21-row shards of an
             // 8-GPU run, and every block beyond the second was a dependent read from memory)
             const unsigned l1 = SELF ? 0u : dense ? 64u + (unsigned)lane : (unsigned)list[min(64u + (unsigned)lane, nq - 1u)];
-            float ccv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, c_scale = 0.f, c_ratio = 0.f, c_bmax = 0.f, c_nmax = 0.f, th_kept = 0.f;
+            float ccv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, c_scale = 0.f, c_ratio = 0.f, c_bmax = 0.f, c_nmax = 0.f, c_er = 0.f, th_kept = 0.f;
             h8 b_kept = {0, 0, 0, 0, 0, 0, 0, 0};
             if constexpr (CTR) {   // the cell's frame: this lane's half of the centre, the scale, the cell's bounds
                 const float *__restrict__ fr = self.frame + (size_t)cellj * KNN_CELL_FRAME_WORDS;
@@ -1896,16 +1921,25 @@ __global__ __launch_bounds__(64 * (KT == 1 && !CTR ? CELL_SCAN_WAVES : CELL_SCAN
                 c_ratio = fr[17];
                 c_bmax = fr[18];
                 c_nmax = fr[19];
+                if constexpr (U8) {   // the 8-bit rows' error and norm bounds
+                    c_er = self.cell_u8[(size_t)cellj * 2];
+                    c_nmax = self.cell_u8[(size_t)cellj * 2 + 1];
+                }
             }
             for (unsigned t0 = tb; t0 < te && !dead; t0 += TPP) {
                 const int nt = (int)min((unsigned)TPP, te - t0);   // wave-uniform
-                h8 ar[TPP][KT];
+                h8 ar[U8 ? 1 : TPP][KT];
+                u2v a8[U8 ? TPP : 1];   // (U8: widened at every step — two registers per tile held instead of four)
 #pragma unroll
                 for (int p = 0; p < TPP; ++p)
                     if (p < nt) {
+                        if constexpr (U8) {
+                            a8[p] = __builtin_nontemporal_load(&((const u2v *)rf)[(size_t)(t0 + (unsigned)p) * 64 + lane]);
+                        } else {
 #pragma unroll
-                        for (int kk = 0; kk < KT; ++kk)
-                            ar[p][kk] = __builtin_nontemporal_load(&rf[((size_t)(t0 + (unsigned)p) * KT + kk) * 64 + lane]);
+                            for (int kk = 0; kk < KT; ++kk)
+                                ar[U8 ? 0 : p][kk] = __builtin_nontemporal_load(&rf[((size_t)(t0 + (unsigned)p) * KT + kk) * 64 + lane]);
+                        }
                     }
                 if constexpr (!NIF) {
                     const f4v *__restrict__ rn4 = (const f4v *)rn + (size_t)t0 * 8;
@@ -1942,7 +1976,7 @@ __global__ __launch_bounds__(64 * (KT == 1 && !CTR ? CELL_SCAN_WAVES : CELL_SCAN
                         // (an item of several passes whose list is one block of queries — 16 queries per cluster cell on 64 tight
                         // clusters — keeps the block's operand from its first pass)
                         if (t0 == tb || nq > 32u)
-                            cell_centred_operand((const float *)s_dyn, K > 0 ? K : krt, qid, half, valid, ccv, c_scale, c_ratio, c_bmax, c_nmax,
+                            cell_centred_operand<U8>((const float *)s_dyn, K > 0 ? K : krt, qid, half, valid, ccv, c_scale, c_ratio, c_bmax, c_nmax, c_er,
                                                  s_dup[qid], s_thr[qid], b_kept, th_kept);
                         b[0] = b_kept;
                         th = th_kept;
@@ -1957,7 +1991,13 @@ __global__ __launch_bounds__(64 * (KT == 1 && !CTR ? CELL_SCAN_WAVES : CELL_SCAN
 #pragma unroll
                     for (int p = 0; p < TPP; ++p) {
                         if (p < nt) {
-                            const u64 mask = NIF ? cell_tile_step_nif<KT>(ar[p], b, th) : cell_tile_step<KT>(ar[p], my_nrm, p, half, b, th);
+                            u64 mask;
+                            if constexpr (U8) {
+                                const h8 a1[1] = {cell_widen_u8(a8[p])};
+                                mask = cell_tile_step<1>(a1, my_nrm, p, half, b, th);
+                            } else {
+                                mask = NIF ? cell_tile_step_nif<KT>(ar[p], b, th) : cell_tile_step<KT>(ar[p], my_nrm, p, half, b, th);
+                            }
                             if (__builtin_expect(mask != 0ull, 0)) {
                                 const bool hit = (mask >> lane) & 1ull;
                                 const unsigned pos = cnt + __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32),
@@ -2490,13 +2530,22 @@ __global__ __launch_bounds__(256) void knn_cells_frame_kernel(const unsigned *__
     f[19] = 0.0f;
 }
 
+// With rows8 (option `cells_rows`): every row also as one byte per coordinate in its cell's frame, for the scan alone (the prep
+// kernel's seeds keep reading the fp16 fragments).  v = (row - centre_c) x scale_c is the fp32 value the fragment rounds to fp16 (fp32 subtract, exact power-of-two scale: |v - v_exact| <= 2^-24 |v_exact|), and it
+// is rounded ONCE: code = 128 + clamp(rint(128 v), -128, 127), so the row the scan scores is r^ = (code - 128) / 128 — a
+// multiple of 2^-7 in [-1, 127/128], exact in fp16.  Per coordinate |v_exact - r^| <= |v - r^| + 2^-23 |v|, at most 2^-8 + 2^-23
+// inside the cell's box (|v| <= 1), 2^-7 where the clamp bites; cell_u8[c][0] holds the cell's largest err of knn_u8_code
+// (|v - r^| + 2^-22 |v| + 2^-100, rounded: the scan takes it 10^-6 larger), the row error knn_bound_consts_u8 starts from.  norms8 =
+// |r^|^2, exact in fp32 (16 multiples of 2^-14 below 1); cell_u8[c][1] its largest value in the cell.  Padding rows and rows
+// outside the shard's robust box: code 128 (r^ = 0) and norm +INF, as in the fp16 layout.  Lane order: the fragments'.
 // The fragments, norms and norm halves of every tile again, in its cell's frame; frame[c][18] / [19] = the cell's largest
 // |coordinate| and norm.  Same arithmetic as the placement (fp32 subtract, exact power-of-two scale, round to nearest even,
 // exact products summed in fp32), same rule for rows outside the shard's robust box (they stay out: zero fragment, +INF norm).
 __global__ __launch_bounds__(256) void knn_cells_recentre_kernel(const float *__restrict__ R, int k, const unsigned *__restrict__ perm,
                                                                  unsigned ntiles, const unsigned *__restrict__ tile_cell,
                                                                  float *__restrict__ frame, h8 *__restrict__ frag,
-                                                                 float *__restrict__ norms, unsigned *__restrict__ norms2)
+                                                                 float *__restrict__ norms, unsigned *__restrict__ norms2,
+                                                                 u2v *__restrict__ rows8, float *__restrict__ norms8, float *__restrict__ cell_u8)
 {
     const unsigned t = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int lane = threadIdx.x & 63, half = lane >> 5;
@@ -2509,7 +2558,10 @@ __global__ __launch_bounds__(256) void knn_cells_recentre_kernel(const float *__
     const float scale = f[16];
     h8 v = {0, 0, 0, 0, 0, 0, 0, 0};
     float vmax = 0.0f, part = 0.0f;
+    u2v code = {0x80808080u, 0x80808080u};   // 8-bit rows (rows8 != null): see above — the same v, rounded once more
+    float err8 = 0.0f, part8 = 0.0f;
     if (real) {
+        code = (u2v){0u, 0u};
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int d = 8 * half + j;
@@ -2519,6 +2571,24 @@ __global__ __launch_bounds__(256) void knn_cells_recentre_kernel(const float *__
             vmax = fmaxf(vmax, fabsf(back));
             part = part + back * back;
             v[j] = hval;
+            float rh, e;
+            const unsigned b = knn_u8_code(sc, rh, e);
+            err8 = fmaxf(err8, e);
+            part8 = part8 + rh * rh;   // exact
+            code[j >> 2] |= b << (8 * (j & 3));
+        }
+    }
+    if (rows8) {   // (kernel-uniform) the 8-bit rows from the same gather of the rows
+        const float other8 = __shfl_xor(part8, 32, KNN_WAVE);
+        const float nrm8 = half == 0 ? part8 + other8 : other8 + part8;
+        rows8[(size_t)t * 64 + lane] = code;
+        if (half == 0)
+            norms8[pos] = real ? nrm8 : INFINITY;
+        err8 = wave_max_f(err8);
+        const float nmax8 = wave_max_f(real ? nrm8 : 0.0f);
+        if (lane == 0) {
+            guarded_atomic_max((unsigned *)&cell_u8[(size_t)tile_cell[t] * 2], __float_as_uint(err8));
+            guarded_atomic_max((unsigned *)&cell_u8[(size_t)tile_cell[t] * 2 + 1], __float_as_uint(nmax8));
         }
     }
     const float other = __shfl_xor(part, 32, KNN_WAVE);
@@ -2552,22 +2622,46 @@ void knn_cells_free(CellIndex *&c)
     (void)KNN_DEV_FREE(c->bucket_start);
     (void)KNN_DEV_FREE(c->cell_frame);
     (void)KNN_DEV_FREE(c->tile_cell);
+    (void)KNN_DEV_FREE(c->rows8);
+    (void)KNN_DEV_FREE(c->norms8);
+    (void)KNN_DEV_FREE(c->cell_u8);
     delete c;
     c = nullptr;
 }
 
 std::atomic<int> g_knn_cells_centre{0};                 // option `cells_centre`
 std::atomic<long long> g_knn_cells_centred_builds{0};   // read-only option `cells_centred_builds`
+std::atomic<int> g_knn_cells_rows{0};                   // option `cells_rows`
+std::atomic<long long> g_knn_cells_u8_builds{0};        // read-only option `cells_u8_builds`
 
 // Moves a finished cell-sorted layout (k <= 16, no shard geometry) into per-cell frames — see the kernels.  Enqueues on `s`;
 // the caller's next synchronisation covers it.
-hipError_t knn_cells_recentre(FilterState &st, const float *r, hipStream_t s)
+hipError_t knn_cells_recentre(FilterState &st, const float *r, hipStream_t s, bool rows_u8, bool frames_wanted)
 {
     if (!st.cells || st.kt != 1 || st.cells->geom || st.cells->centred)
         return hipSuccess;
     CellIndex &c = *st.cells;
     const unsigned ntiles = (unsigned)st.ntiles;
     unsigned *box = nullptr;
+    if (rows_u8 && ntiles != 0u) {   // 8-bit rows for the scan (the fp16 fragments stay: the prep kernel's seeds)
+        hipError_t e8 = KNN_DEV_ALLOC((void **)&c.rows8, (size_t)ntiles * 64 * 8);
+        if (e8 == hipSuccess)
+            e8 = KNN_DEV_ALLOC((void **)&c.norms8, (size_t)ntiles * 32 * sizeof(float));
+        if (e8 == hipSuccess)
+            e8 = KNN_DEV_ALLOC((void **)&c.cell_u8, (size_t)c.ncells * 2 * sizeof(float));
+        if (e8 == hipSuccess)
+            e8 = hipMemsetAsync(c.cell_u8, 0, (size_t)c.ncells * 2 * sizeof(float), s);
+        if (e8 != hipSuccess) {   // no room: per-cell frames only if they were asked for on their own, else the shard's one frame
+            (void)KNN_DEV_FREE(c.rows8);
+            (void)KNN_DEV_FREE(c.norms8);
+            (void)KNN_DEV_FREE(c.cell_u8);
+            c.rows8 = nullptr;
+            c.norms8 = c.cell_u8 = nullptr;
+            (void)hipGetLastError();
+            if (!frames_wanted)
+                return hipSuccess;
+        }
+    }
     FTRY(KNN_DEV_ALLOC((void **)&c.cell_frame, (size_t)c.ncells * KNN_CELL_FRAME_WORDS * sizeof(float)));
     FTRY(KNN_DEV_ALLOC((void **)&c.tile_cell, (size_t)std::max(1u, ntiles) * sizeof(unsigned)));
     FTRY(KNN_DEV_ALLOC((void **)&box, (size_t)c.ncells * 32 * sizeof(unsigned)));
@@ -2580,7 +2674,7 @@ hipError_t knn_cells_recentre(FilterState &st, const float *r, hipStream_t s)
                            ntiles, c.tile_cell, box);
         hipLaunchKernelGGL(knn_cells_frame_kernel, dim3((c.ncells + 255u) / 256u), dim3(256), 0, s, box, c.ncells, st.k, st.sigma, c.cell_frame);
         hipLaunchKernelGGL(knn_cells_recentre_kernel, dim3((ntiles + 3u) / 4u), dim3(256), 0, s, r, st.k, c.perm, ntiles, c.tile_cell,
-                           c.cell_frame, (h8 *)st.ref_frags, st.ref_norms, st.ref_norms2);
+                           c.cell_frame, (h8 *)st.ref_frags, st.ref_norms, st.ref_norms2, (u2v *)c.rows8, c.norms8, c.cell_u8);
         e = hipGetLastError();
     }
     if (e == hipSuccess)
@@ -2589,6 +2683,10 @@ hipError_t knn_cells_recentre(FilterState &st, const float *r, hipStream_t s)
     FTRY(e);
     c.centred = true;
     ++g_knn_cells_centred_builds;
+    if (c.rows8) {
+        c.rows_u8 = true;
+        ++g_knn_cells_u8_builds;
+    }
     return hipSuccess;
 }
 
@@ -2598,10 +2696,43 @@ hipError_t knn_cells_maybe_recentre(FilterState &st, const float *r, const float
 {
     if (!st.usable || !st.cells || st.kt != 1 || st.cells->geom)
         return hipSuccess;
-    const int opt = g_knn_cells_centre;
-    if (opt == 2 || (opt == 0 && !(samp && knn_cells_sample_is_clustered(samp, samples, st.k, st.sigma))))
+    const int opt = g_knn_cells_centre, rows = g_knn_cells_rows;
+    const bool clustered = samp && knn_cells_sample_is_clustered(samp, samples, st.k, st.sigma);
+    // 8-bit rows (they need per-cell frames): on request, or — library policy — for shards of >= 2^24 rows whose sample is
+    // uniform-like (profiles/r06_u8_rows.txt, one batch at a time, fp16 -> u8 ms: uniform 2^24 0.153 -> 0.149 (C3 pipelined -6 %,
+    // C4 -25 %); uniform 2^22 0.080 -> 0.094, gaussian 2^24 0.187 -> 0.219, unit sphere 0.166 -> 0.199, heavy tails 0.365 ->
+    // 0.368: where the lists are long the per-pair operand work of the per-cell-frame scan costs more than the bytes save)
+    const bool rows_u8 = rows == 2 || (rows == 0 && opt != 2 && !clustered && st.n >= (1ll << 24) && samp &&
+                                       knn_cells_sample_is_uniform_like(samp, samples, st.k));
+    const bool frames = opt == 1 || (opt == 0 && clustered);
+    if (!rows_u8 && !frames)
         return hipSuccess;
-    return knn_cells_recentre(st, r, s);
+    return knn_cells_recentre(st, r, s, rows_u8, frames);
+}
+
+// Is the build's host sample uniform-like?  Per dimension, the inter-quartile range against the 1st..99th percentile range:
+// 0.5 for uniform rows (and for uniform integer codes), 0.29 for gaussian, less for heavy tails; the mean over the dimensions
+// must reach 0.4.  Where the rows are spread evenly the cells' lists are short and the 8-bit rows' bytes are what counts.
+bool knn_cells_sample_is_uniform_like(const float *samp, long long samples, int k)
+{
+    if (samples < 256 || k < 1)
+        return false;
+    std::vector<float> col((size_t)samples);
+    double sum = 0.0;
+    for (int d = 0; d < k; ++d) {
+        for (long long i = 0; i < samples; ++i)
+            col[(size_t)i] = samp[(size_t)i * k + d];
+        auto at = [&](double f) {
+            const size_t j = (size_t)(f * (double)(samples - 1));
+            std::nth_element(col.begin(), col.begin() + j, col.end());
+            return (double)col[j];
+        };
+        const double p01 = at(0.01), p25 = at(0.25), p75 = at(0.75), p99 = at(0.99);
+        if (!(p99 > p01))
+            return false;
+        sum += (p75 - p25) / (p99 - p01);
+    }
+    return sum / k >= 0.4;
 }
 
 // Does the build's host sample look clustered?  Median, over 64 sample rows, of the distance (largest coordinate difference)
@@ -3176,6 +3307,7 @@ hipError_t knn_cells_query(FilterState &st, FilterWorkspace &w, int m, const flo
     if (centred) {
         self.dup = w.dup;
         self.frame = c.cell_frame;
+        self.cell_u8 = c.rows_u8 ? c.cell_u8 : nullptr;
     }
     const unsigned list_cap = self_lists ? CELL_SELF_CAP : c.cap;
     static const bool trace_cells = getenv("KNN_MI355X_TRACE_CELLS") != nullptr;   // (read once: a query may run beside a thread that changes the environment)
@@ -3233,6 +3365,16 @@ hipError_t knn_cells_query(FilterState &st, FilterWorkspace &w, int m, const flo
         else                                                                                                               \
             KNN_SCAN_LAUNCH(DYNV, 0, SELFV);                                                                               \
     } while (0)
+#define KNN_SCAN_LAUNCH_U8(DYNV, KV)   /* 8-bit rows in per-cell frames: the same LDS as KNN_SCAN_LAUNCH_K5 */                \
+    do {                                                                                                                   \
+        if (lds > (size_t)(64u << 10))                                                                                     \
+            FTRY(hipFuncSetAttribute((const void *)knn_cells_scan_kernel<DYNV, KV, false, 1, true, false, true>,           \
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                              \
+        hipLaunchKernelGGL((knn_cells_scan_kernel<DYNV, KV, false, 1, true, false, true>), dim3(gx), dim3(64 * plan.waves), lds, s, \
+                           (const h8 *)c.rows8, c.norms8, c.items, c.nitems, (const h8 *)w.qry_frags, w.thr, m, m_padded,  \
+                           w.cell_counts, w.cell_lists, list_cap, w.records, w.counts, w.ctl_cur, w.slice, w.ovf_base,    \
+                           w.ovf_cap, q, r, st.k, c.perm, npos, base, keys, fin, self);                                    \
+    } while (0)
 #define KNN_SCAN_LAUNCH_K5(DYNV)   /* per-cell frames: 92 KiB of dynamic LDS for 1024 queries (their fp32 rows) */                  \
     do {                                                                                                                   \
         if (st.k == 16) {                                                                                                  \
@@ -3247,7 +3389,13 @@ hipError_t knn_cells_query(FilterState &st, FilterWorkspace &w, int m, const flo
             KNN_SCAN_LAUNCH(DYNV, 0, false, 1, true);                                                                      \
         }                                                                                                                  \
     } while (0)
-    if (centred) {   // per-cell frames: lists from the match launch
+    if (centred && c.rows_u8) {   // 8-bit rows in per-cell frames: items from the block's counter only (the fixed deal's form
+                                  // of this kernel needs 8 bytes of scratch under the 128-register cap)
+        if (st.k == 16)
+            KNN_SCAN_LAUNCH_U8(true, 16);
+        else
+            KNN_SCAN_LAUNCH_U8(true, 0);
+    } else if (centred) {   // per-cell frames: lists from the match launch
         if (dyn)
             KNN_SCAN_LAUNCH_K5(true);
         else
@@ -3315,4 +3463,26 @@ hipError_t knn_cells_query(FilterState &st, FilterWorkspace &w, int m, const flo
 #undef KNN_TAIL_LAUNCH
     }
     return hipGetLastError();
+}
+
+// Test hook (host arithmetic, no GPU): one row through the 8-bit rows' quantiser (knn_u8_code — what knn_cells_recentre_kernel
+// does per coordinate, v = (row - centre) x scale in fp32) -> its codes, the largest per-coordinate err and the eta of
+// knn_bound_consts_u8(k, 1, scale, amax, err, nmax) for a query of largest |coordinate| amax.
+extern "C" int knn_debug_u8_row(int k, const float *row, const float *centre, float scale, double amax, unsigned char *codes,
+                                double out[2])
+{
+#pragma clang fp contract(off)
+    if (k < 1 || k > 16 || !row || !centre || !codes || !out)
+        return -1;   // KNN_EINVAL
+    float er = 0.0f, nmax = 0.0f;
+    for (int d = 0; d < k; ++d) {
+        const float v = (row[d] - centre[d]) * scale;
+        float rh, e;
+        codes[d] = (unsigned char)knn_u8_code(v, rh, e);
+        er = std::max(er, e);
+        nmax = nmax + rh * rh;
+    }
+    out[0] = er;
+    out[1] = knn_bound_consts_u8(k, 1, scale, amax, er, nmax).eta;
+    return 0;
 }

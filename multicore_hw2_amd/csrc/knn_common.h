@@ -204,6 +204,15 @@ struct CellIndex {
     bool centred = false;
     float *cell_frame = nullptr;          // device [ncells][KNN_CELL_FRAME_WORDS]
     unsigned *tile_cell = nullptr;        // device [ntiles]
+    // 8-bit rows (option `cells_rows`; needs per-cell frames): the scan reads these instead of the fp16 fragments and their
+    // norms — rows8 u8 [tile][64 lanes][8], byte j of a lane = 128 + round(128 v) of the lane's K-slot j, v the row in its
+    // cell's frame, so the row the scan scores is (code - 128) / 128; norms8 fp32 [tiles * 32] = that row's squared norm
+    // (+INF on padding rows and rows outside the robust box); cell_u8[c] = { max over the cell's coordinates of
+    // knn_u8_code's err, max norms8 of the cell }.  The fp16 fragments stay: the prep kernel's seeds.
+    bool rows_u8 = false;
+    unsigned char *rows8 = nullptr;       // device [ntiles][64][8]
+    float *norms8 = nullptr;              // device [ntiles * 32]
+    float *cell_u8 = nullptr;             // device [ncells][2]
 };
 #define KNN_CELL_FRAME_WORDS 20
 #define KNN_NIF_MAX_K 30   // 16 < k <= 30: the cell-sorted fragments carry the rows' norms in K-slots 30, 31 (knn_cells.hip: cell_tile_step_nif)
@@ -270,11 +279,16 @@ bool knn_cells_lists_policy(unsigned ncells, bool several_slots);
 hipError_t knn_cells_place_rows(FilterState &st, const float *r_dev, const unsigned *code, unsigned *fill, unsigned *out,
                                 unsigned ocap, hipStream_t s);
 void knn_cells_free(CellIndex *&c);
-hipError_t knn_cells_recentre(FilterState &st, const float *r, hipStream_t s);
+// rows_u8: also the 8-bit rows; frames_wanted: per-cell frames are wanted on their own (else, without room for the 8-bit rows,
+// the layout stays in the shard's one frame)
+hipError_t knn_cells_recentre(FilterState &st, const float *r, hipStream_t s, bool rows_u8 = false, bool frames_wanted = true);
 bool knn_cells_sample_is_clustered(const float *samp, long long samples, int k, float sigma);
+bool knn_cells_sample_is_uniform_like(const float *samp, long long samples, int k);
 hipError_t knn_cells_maybe_recentre(FilterState &st, const float *r, const float *samp, long long samples, hipStream_t s);
 extern std::atomic<int> g_knn_cells_centre;
 extern std::atomic<long long> g_knn_cells_centred_builds;
+extern std::atomic<int> g_knn_cells_rows;
+extern std::atomic<long long> g_knn_cells_u8_builds;
 void knn_cells_workspace_free(FilterWorkspace &w);
 // One batch of <= KNN_CELL_BATCH queries already prepared by the filter's query-fragment kernel: seed, thresholds,
 // match, scan (records in w, as the full scan leaves them).  Asynchronous.

@@ -217,6 +217,7 @@ struct CellSelf {
     const float *dup;    // device [m_padded]
     int sa, m_padded;
     const float *frame;  // per-cell frames (the centred scan): device [cells][KNN_CELL_FRAME_WORDS]; null otherwise
+    const float *cell_u8;   // 8-bit rows (the centred scan's U8 form): device [cells][2]; null otherwise
 };
 
 // -> the list's length; entries beyond CELL_SELF_CAP are counted, not stored.  `dupv`: the batch's Dup values (LDS in the

@@ -112,6 +112,36 @@ __host__ __device__ inline BoundConsts knn_bound_consts(int k, int kt, double si
     return c;
 }
 
+// 8-bit rows in a cell's frame (option `cells_rows`, knn_cells_recentre_kernel): one rounding of the fp32 value v of a coordinate
+// in the cell's frame to a multiple of 2^-7 in [-1, 127/128] — rh, exact in fp16 and fp32 — and its byte, 128 + 128 rh.
+// err = |v - rh| + 2^-22 |v| + 2^-100 (each term exact, the sums rounded once each) bounds, taken 10^-6 larger, the coordinate's
+// distance from the row's exact value in the frame, v_exact: the centring made v with |v - v_exact| <= 2^-24 |v_exact| (fp32
+// subtract, exact power-of-two scale) — or, where the product falls below fp32's normal range (or is flushed), within 2^-126.  Inside the cell's box (|v| <= 1) err <= 2^-8 + 2^-22; the clamp at 127/128 makes it at most 2^-7 + 2^-22.
+__host__ __device__ inline unsigned knn_u8_code(float v, float &rh, float &err)
+{
+#pragma clang fp contract(off)
+    const float q = fminf(fmaxf(rintf(v * 128.0f), -128.0f), 127.0f);   // (v * 128: exact)
+    rh = q * 0.0078125f;
+    err = fabsf(v - rh) + 0x1p-22f * fabsf(v) + 0x1p-100f;
+    return (unsigned)((int)q + 128);
+}
+
+// knn_bound_consts for 8-bit rows: the row's part of the per-coordinate error is ABSOLUTE — er, the cell's largest knn_u8_code
+// err (10^-6 added) — instead of the fp16 rounding thp bmax; the query's fp16 rounding thp amax, the subnormal allowance 2 nu0
+// and every other constant (omega, gamma, rho, g2, tau) are knn_bound_consts' own:
+//     emax = thp amax + er + 2 nu0,  eta = sqrt(k) emax
+// (a coordinate of (q~ - r^) - (q - r) is off by at most the query's rounding plus the row's quantisation).  nmax is the
+// largest norm of the DEQUANTISED rows, |r^|^2, which is what the C operand holds — exactly (knn_cells_recentre_kernel).
+__host__ __device__ inline BoundConsts knn_bound_consts_u8(int k, int kt, double sigma, double amax, double er, double nmax)
+{
+    BoundConsts c = knn_bound_consts(k, kt, sigma, amax, 0.0, nmax);
+    const double theta = 0x1p-11 + 0x1p-23;
+    const double emax = theta / (1.0 - theta) * amax + er * (1.0 + 1e-6) + 2.0 * (0x1p-14 * 1.001);
+    c.eta2 = k * emax * emax;
+    c.eta = sqrt(c.eta2);
+    return c;
+}
+
 // Threshold implied by a filter score `u` = S of SOME real reference j0 of the shard (the minimum
 // over the sample pass), for a query whose fp16 row has computed squared norm mq:
 //   D~_j0 <= u + mq(1+g) + rho;  (sqrt(D_j0) - eta)^2 <= D~_j0 + 2 eta^2  =>  D_j0 <= D0up
