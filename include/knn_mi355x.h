@@ -193,6 +193,40 @@ int knn_keys_to_indices(int device, const unsigned long long *keys_dev, int m, i
 /* Convenience: host queries in, host indices out, synchronous. */
 int knn_index_query_host(knn_index *idx, int m, const float *queries_host, int *out_host);
 
+/* ------------------------------------------------------------------------
+ * 2c. k-nearest neighbours (top-K), 1 <= K <= 64.
+ *
+ * For query j, keys_dev[j*K + t], t = 0 .. K-1, holds the K smallest packed keys of the shard's rows whose v0 distance is
+ * finite (v0's strict `<` against +INF admits only these), in ascending order: distance first, then the lowest global
+ * number.  A query with fewer than K such rows gets KNN_KEY_INIT (+INF, index 0) in the remaining slots.  Column 0 is the
+ * 1-NN key for every input (NaN and overflowing rows included), and K = 1 equals knn_index_query bit for bit.  The keys
+ * carry the same global numbers as the 1-NN keys: base_index + row for index-range shards, gids for cell-range shards.
+ *
+ * Folding shards: without KNN_QUERY_INIT_KEYS the call folds into what keys_dev holds (K sorted keys per query, e.g. the
+ * answer of another shard): the result is the K smallest of (those keys and this shard's).  With the flag it writes the
+ * keys fresh.  Global numbers are distinct across shards, so a fold never holds a row twice.  Cell-range shards fold too.
+ * knn_keys_init and knn_keys_to_indices work on top-K keys as they are: pass m*K as their count.
+ *
+ * Paths (knn_index_last_stats [0]; options "path" and "cells" as for 1-NN): 2 = the MFMA filter, for the dense filter layouts
+ * and for cell-sorted layouts in the shard's frame (scanned in full) — the threshold comes from the K-th smallest per-block
+ * sample minimum, the survivors are evaluated with v0's arithmetic and the K smallest kept; a batch the filter cannot serve
+ * (a query nothing bounds, fewer than K sampled blocks with a real row, more candidates than the buffers hold) raises [2] = 1
+ * and is answered by the exact top-K scan; [1] = records re-ranked.  1 = the exact top-K scan (v0 arithmetic over every
+ * row): per-cell frames (centred or 8-bit rows), grid indexes, cell-range shards, shards or batches below the filter's sizes.
+ * Results are bit-exact either way.
+ * Any K outside 1 .. 64, or m < 1, is KNN_EINVAL (knn_last_error says why) and launches nothing.
+ * ---------------------------------------------------------------------- */
+/* keys_dev [m][K]; indices_dev [m][K] or NULL: the int32 indices, unpacked after the fold.  Slot rules as knn_index_query:
+ * eight workspaces, calls sharing one must be stream-ordered; asynchronous on `stream`. */
+int knn_index_query_topk(knn_index *idx, int slot, int m, int K, const float *queries_dev, unsigned long long *keys_dev,
+                         int *indices_dev, void *stream, unsigned flags);
+/* b_dev[j] <- the K smallest of a_dev[j] and b_dev[j], sorted; both hold m sorted lists of K keys (device arrays on
+ * `device`).  Merges shards, or GPUs after the caller has gathered their keys.  Asynchronous on `stream`. */
+int knn_keys_topk_merge(int device, int m, int K, const unsigned long long *a_dev, unsigned long long *b_dev, void *stream);
+/* Synchronous: host queries [m][k] in, indices_host [m][K] out; dist2_host [m][K] (may be NULL) receives the float of each
+ * key's high word (+INF in padding slots). */
+int knn_index_query_topk_host(knn_index *idx, int m, int K, const float *queries_host, int *indices_host, float *dist2_host);
+
 /* Tuning / test hooks.  Known names:
  *   "path"    0 = auto, 1 = exact VALU kernels only, 2 = force the MFMA filter
  *             (+ exact re-rank) where its preconditions hold, 3 = the uniform-grid spatial index
@@ -283,7 +317,7 @@ int knn_index_query_host(knn_index *idx, int m, const float *queries_host, int *
 int knn_set_option(const char *name, long long value);
 long long knn_get_option(const char *name);
 
-/* Statistics of the most recent knn_index_query_keys on this index (filled
+/* Statistics of the most recent knn_index_query_keys or knn_index_query_topk on this index (filled
  * when the stream has completed; call after synchronising):
  *   [0] path taken (1 exact, 2 filter, 3 grid index, 4 filter in its cell-pruned form)
  *   [1] candidates re-ranked exactly

@@ -17,7 +17,7 @@ import sys
 import numpy as np
 
 __all__ = ["lib", "lib_path", "cudaCallback", "KnnIndex", "KnnGeom", "KnnError", "KEY_INIT", "set_option",
-           "get_option", "trim", "device_count", "EXPORTED_SYMBOLS", "shard_bounds"]
+           "get_option", "trim", "device_count", "EXPORTED_SYMBOLS", "shard_bounds", "keys_topk_merge"]
 
 KEY_INIT = 0x7F80000000000000
 
@@ -31,6 +31,7 @@ EXPORTED_SYMBOLS = [
     "knn_index_query_keys_ex", "knn_index_debug_counters", "knn_debug_scan_plan", "knn_debug_scan_plan_ex", "knn_debug_shard_policy", "knn_debug_plan_shard", "knn_debug_u8_row", "knn_index_query",
     "knn_geom_create", "knn_geom_destroy", "knn_geom_info", "knn_geom_assign", "knn_index_create_sharded",
     "knn_index_seed_export", "knn_index_seed_attach", "knn_geom_first_cell",
+    "knn_index_query_topk", "knn_keys_topk_merge", "knn_index_query_topk_host",
 ]
 QUERY_INIT_KEYS = 1   # KNN_QUERY_INIT_KEYS
 
@@ -94,6 +95,9 @@ def lib():
     L.knn_index_create_sharded.argtypes = [ctypes.POINTER(c_vp), c_int, c_vp, c_int, c_ll, c_vp, c_vp, c_vp]
     L.knn_index_seed_export.argtypes = [c_vp, c_vp, c_vp]
     L.knn_index_seed_attach.argtypes = [c_vp, c_vp]
+    L.knn_index_query_topk.argtypes = [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, ctypes.c_uint]
+    L.knn_keys_topk_merge.argtypes = [c_int, c_int, c_int, c_vp, c_vp, c_vp]
+    L.knn_index_query_topk_host.argtypes = [c_vp, c_int, c_int, c_vp, c_vp, c_vp]
     _lib = L
     return L
 
@@ -295,6 +299,25 @@ class KnnIndex:
                                           out.ctypes.data_as(ctypes.c_void_p)))
         return out
 
+    def query_topk(self, m, K, queries_dev, keys_dev, stream=0, slot=0, init_keys=False, indices_dev=None):
+        """Async (knn_index_query_topk): keys_dev[m][K] <- the K smallest (distance, global index) keys of (this shard's rows
+        and, unless init_keys, the K sorted keys per query keys_dev already holds), sorted.  indices_dev: also the int32
+        indices [m][K]."""
+        _check(lib().knn_index_query_topk(self._h, int(slot), int(m), int(K), ctypes.c_void_p(int(queries_dev)),
+                                          ctypes.c_void_p(int(keys_dev)),
+                                          ctypes.c_void_p(int(indices_dev)) if indices_dev is not None else None,
+                                          ctypes.c_void_p(stream), QUERY_INIT_KEYS if init_keys else 0))
+
+    def query_topk_host(self, queries, K):
+        """Synchronous top-K of this shard alone: (indices int32 [m][K], dist2 float32 [m][K])."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1)
+        m = q.size // self.k
+        idx = np.empty((m, int(K)), dtype=np.int32)
+        d2 = np.empty((m, int(K)), dtype=np.float32)
+        _check(lib().knn_index_query_topk_host(self._h, m, int(K), q.ctypes.data_as(ctypes.c_void_p),
+                                               idx.ctypes.data_as(ctypes.c_void_p), d2.ctypes.data_as(ctypes.c_void_p)))
+        return idx, d2
+
     def last_stats(self):
         st = (ctypes.c_longlong * 4)()
         _check(lib().knn_index_last_stats(self._h, st))
@@ -346,6 +369,12 @@ def keys_init(keys_dev, m, device=0, stream=0):
 def keys_to_indices(keys_dev, m, out_dev, device=0, stream=0):
     _check(lib().knn_keys_to_indices(int(device), ctypes.c_void_p(int(keys_dev)), int(m),
                                      ctypes.c_void_p(int(out_dev)), ctypes.c_void_p(stream)))
+
+
+def keys_topk_merge(a_dev, b_dev, m, K, device=0, stream=0):
+    """b[j] <- the K smallest of a[j] and b[j] (device arrays of m sorted lists of K keys; knn_keys_topk_merge)."""
+    _check(lib().knn_keys_topk_merge(int(device), int(m), int(K), ctypes.c_void_p(int(a_dev)), ctypes.c_void_p(int(b_dev)),
+                                     ctypes.c_void_p(stream)))
 
 
 def keys_allreduce_min(devices, keys_dev, m, streams=None):

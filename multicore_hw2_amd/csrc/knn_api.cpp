@@ -9,6 +9,7 @@
 #include "../../include/knn_mi355x.h"
 #include "knn_common.h"
 
+#include <limits.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -268,6 +269,10 @@ struct knn_index {
     bool sharded = false;        // a cell-range shard (knn_index_create_sharded): always served by the cell-pruned path
     ShardGeom geom;              // its copy of the global grid (filter.cells->geom points here)
     int rank = 0;
+    u64 *topk_part[KNN_SLOTS] = {};      // per slot: the exact top-K scan's per-slice lists (grown on first use)
+    size_t topk_bytes[KNN_SLOTS] = {};
+    u64 *topk_cand[KNN_SLOTS] = {};      // per slot: the filter top-K's candidate lists [m][cap] + counts [m] (grown on first use)
+    size_t topk_cand_bytes[KNN_SLOTS] = {};
     // Calls on one index from several host threads are serialised (enqueueing a batch is ~20 us of host work; the GPU
     // work of different slots still overlaps): the workspaces' lazily grown buffers, the event list, the statistics and
     // the chain events are plain members.  Recursive: knn_index_query_host calls the keyed entry points.
@@ -807,6 +812,10 @@ void knn_index_destroy(knn_index *idx)
             pool_put(idx->device, idx->owned_refs, idx->owned_bytes);
         knn_filter_free(idx->filter);
         knn_grid_free(idx->grid);
+        for (int i = 0; i < KNN_SLOTS; ++i) {
+            (void)knn_dev_free(idx->topk_part[i]);
+            (void)knn_dev_free(idx->topk_cand[i]);
+        }
         knn_dev_free_end_synced();
         for (auto &ev : idx->events) {
             (void)hipEventDestroy(ev.first);
@@ -947,6 +956,95 @@ int knn_index_query(knn_index *idx, int slot, int m, const float *queries_dev, u
         HIP_TRY(hipEventRecord(ev->second, s));
     if (indices_dev)
         HIP_TRY(knn_keys_unpack_launch((const u64 *)keys_dev, m, indices_dev, s));
+    return KNN_OK;
+}
+
+int knn_index_query_topk(knn_index *idx, int slot, int m, int K, const float *queries_dev, unsigned long long *keys_dev,
+                         int *indices_dev, void *stream, unsigned flags)
+{
+    if (!idx || m < 1 || K < 1 || K > KNN_TOPK_MAX || (long long)m * K > INT_MAX || slot < 0 || slot >= KNN_SLOTS ||
+        !queries_dev || !keys_dev || (flags & ~(unsigned)KNN_QUERY_INIT_KEYS) != 0u)
+        return fail(KNN_EINVAL, "knn_index_query_topk: bad arguments (1 <= K <= 64, m >= 1, slot 0 .. 7)");
+    std::lock_guard<std::recursive_mutex> lock(idx->mu);
+    DeviceGuard guard(idx->device);
+    if (!guard.ok)
+        return fail(KNN_EHIP, "knn_index_query_topk: hipSetDevice failed");
+    const int init = (flags & KNN_QUERY_INIT_KEYS) != 0u;
+    hipStream_t s = (hipStream_t)stream;
+    idx->stats[0] = 1;
+    idx->stats[1] = 0;
+    idx->stats[2] = 0;
+    idx->last_slot = slot;
+    const int mk = m * K;
+    if (idx->n == 0) {   // an empty shard adds nothing
+        if (init)
+            HIP_TRY(knn_keys_fill_launch((u64 *)keys_dev, mk, s));
+    } else {
+        // Which path: the MFMA filter for the dense layouts and for a cell-sorted layout in the shard's frame
+        // (scanned in full), under the 1-NN rule's options and sizes; exact top-K for per-cell frames (centred, u8), grid
+        // indexes, cell-range shards (their keys need gids), tiny shards, few queries, and outlier lists longer than half a
+        // query's candidate room.
+        const long long path = g_opt_path;
+        const unsigned ccap = (unsigned)std::min<long long>(4096 + 128 * (long long)K, ((long long)32 << 20) / m);
+        const bool use_filter = !idx->sharded && idx->filter.usable && !(idx->grid && (path == 0 || path == 3)) &&
+                                !(idx->filter.cells && idx->filter.cells->centred) && idx->filter.n_outliers <= ccap / 2 &&
+                                ccap >= 64 &&
+                                (path == 2 || (path == 0 && m >= 5 && (idx->n >= 65536 || idx->filter_wanted)));
+        const size_t need = knn_topk_part_bytes(m, K, idx->n, idx->num_cu);
+        if (idx->topk_bytes[slot] < need) {
+            HIP_TRY(knn_dev_free(idx->topk_part[slot]));   // (waits for the device: the old buffer may be in use)
+            idx->topk_part[slot] = nullptr;
+            idx->topk_bytes[slot] = 0;
+            HIP_TRY(knn_dev_alloc((void **)&idx->topk_part[slot], need));
+            idx->topk_bytes[slot] = need;
+        }
+        std::pair<hipEvent_t, hipEvent_t> *ev = nullptr;
+        if (idx->timing > 0 && idx->timing_seq++ % (unsigned long long)idx->timing == 0 && idx->events_used < idx->events.size())
+            ev = &idx->events[idx->events_used++];
+        if (use_filter) {
+            const size_t cbytes = (size_t)m * ccap * sizeof(u64) + (size_t)m * sizeof(unsigned);
+            if (idx->topk_cand_bytes[slot] < cbytes) {
+                HIP_TRY(knn_dev_free(idx->topk_cand[slot]));
+                idx->topk_cand[slot] = nullptr;
+                idx->topk_cand_bytes[slot] = 0;
+                HIP_TRY(knn_dev_alloc((void **)&idx->topk_cand[slot], cbytes));
+                idx->topk_cand_bytes[slot] = cbytes;
+            }
+            idx->stats[0] = 2;
+            idx->filter.force_qt = (int)g_opt_filter_qt;
+            idx->filter.force_rounds = (int)g_opt_filter_rounds;
+            idx->filter.chain_policy = (int)g_opt_filter_chain;
+            idx->filter.run_thresholds = 2;   // running thresholds are a 1-NN argument; the non-running sample stride with them
+            idx->filter.sample_stride = 0;
+            u64 *cand = idx->topk_cand[slot];
+            unsigned *ccount = (unsigned *)(cand + (size_t)m * ccap);
+            HIP_TRY(knn_filter_query_topk(idx->filter, slot, m, K, queries_dev, idx->refs, idx->base, (u64 *)keys_dev, init != 0,
+                                          cand, ccount, ccap, idx->topk_part[slot], idx->topk_bytes[slot], idx->num_cu, s,
+                                          ev ? ev->first : nullptr, ev ? ev->second : nullptr));
+        } else {
+            // a cell-range shard's keys carry its rows' global numbers (gids); an index-range shard's base + row
+            const unsigned *gids = idx->sharded && idx->filter.cells ? idx->filter.cells->gids : nullptr;
+            if (ev)
+                HIP_TRY(hipEventRecord(ev->first, s));
+            HIP_TRY(knn_exact_topk_launch(idx->k, m, K, idx->n, idx->base, gids, queries_dev, idx->refs, (u64 *)keys_dev, init,
+                                          idx->topk_part[slot], idx->topk_bytes[slot], idx->num_cu, s));
+            if (ev)
+                HIP_TRY(hipEventRecord(ev->second, s));
+        }
+    }
+    if (indices_dev)
+        HIP_TRY(knn_keys_unpack_launch((const u64 *)keys_dev, mk, indices_dev, s));
+    return KNN_OK;
+}
+
+int knn_keys_topk_merge(int device, int m, int K, const unsigned long long *a_dev, unsigned long long *b_dev, void *stream)
+{
+    if (m < 1 || K < 1 || K > KNN_TOPK_MAX || !a_dev || !b_dev)
+        return fail(KNN_EINVAL, "knn_keys_topk_merge: bad arguments (1 <= K <= 64, m >= 1)");
+    DeviceGuard guard(device);
+    if (!guard.ok)
+        return fail(KNN_EHIP, "knn_keys_topk_merge: hipSetDevice failed");
+    HIP_TRY(knn_topk_merge_launch(m, K, (const u64 *)a_dev, (u64 *)b_dev, (hipStream_t)stream));
     return KNN_OK;
 }
 
@@ -1182,6 +1280,50 @@ extern "C" int knn_index_query_host(knn_index *idx, int m, const float *queries_
     }
     for (int j = 0; j < m; ++j)
         out_host[j] = (int)(unsigned)(keys[(size_t)j] & 0xFFFFFFFFull);
+    return KNN_OK;
+}
+
+extern "C" int knn_index_query_topk_host(knn_index *idx, int m, int K, const float *queries_host, int *indices_host,
+                                         float *dist2_host)
+{
+    if (!idx || m < 1 || K < 1 || K > KNN_TOPK_MAX || (long long)m * K > INT_MAX || !queries_host || !indices_host)
+        return fail(KNN_EINVAL, "knn_index_query_topk_host: bad arguments (1 <= K <= 64, m >= 1)");
+    std::lock_guard<std::recursive_mutex> lock(idx->mu);
+    DeviceGuard guard(idx->device);
+    if (!guard.ok)
+        return fail(KNN_EHIP, "knn_index_query_topk_host: hipSetDevice failed");
+    const size_t mk = (size_t)m * (size_t)K;
+    const size_t qbytes = (size_t)m * (size_t)idx->k * sizeof(float), kbytes = mk * sizeof(u64);
+    float *q_dev = nullptr;
+    u64 *keys_dev = nullptr;
+    std::vector<u64> keys(mk);
+    int rc = KNN_OK;
+    hipError_t e = pool_get(idx->device, qbytes, (void **)&q_dev);
+    if (e == hipSuccess)
+        e = pool_get(idx->device, kbytes, (void **)&keys_dev);
+    if (e == hipSuccess)
+        e = hipMemcpy(q_dev, queries_host, qbytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess)
+        rc = fail(KNN_EHIP, "knn_index_query_topk_host: staging queries", hipGetErrorString(e));
+    if (rc == KNN_OK)
+        rc = knn_index_query_topk(idx, 0, m, K, q_dev, keys_dev, nullptr, nullptr, KNN_QUERY_INIT_KEYS);
+    if (rc == KNN_OK) {
+        e = hipMemcpy(keys.data(), keys_dev, kbytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess)
+            rc = fail(KNN_EHIP, "knn_index_query_topk_host: D2H keys", hipGetErrorString(e));
+    }
+    (void)hipDeviceSynchronize();   // nothing in flight may still use the buffers going back to the pool
+    pool_put(idx->device, q_dev, qbytes);
+    pool_put(idx->device, keys_dev, kbytes);
+    if (rc != KNN_OK)
+        return rc;
+    for (size_t i = 0; i < mk; ++i) {
+        indices_host[i] = (int)(unsigned)(keys[i] & 0xFFFFFFFFull);
+        if (dist2_host) {
+            const unsigned hi = (unsigned)(keys[i] >> 32);
+            memcpy(&dist2_host[i], &hi, sizeof hi);
+        }
+    }
     return KNN_OK;
 }
 

@@ -51,6 +51,29 @@ hipError_t knn_keys_unpack_launch(const u64 *keys_dev, int m, int *out_dev, hipS
 hipError_t knn_synth_fill_launch(float *dst, long long count, u64 seed, long long first,
                                  hipStream_t stream);
 
+// ---- top-K (knn_exact.hip) ---------------------------------------------------
+#define KNN_TOPK_MAX 64        // largest K of knn_index_query_topk
+#define KNN_TOPK_CHUNK 65536   // queries per scan launch of the exact top-K (bounds the per-slice lists)
+// Bytes of the per-slice list buffer the exact top-K scan of m queries, K neighbours, n rows uses (part of a workspace slot).
+size_t knn_topk_part_bytes(int m, int K, long long n, int num_cu);
+// keys[m][K] <- the K smallest of (keys unless init, this shard's finite-distance rows), sorted; v0 arithmetic.  Global
+// numbers: gids[row] when gids != nullptr, else base + row.  part: part_bytes of scratch (knn_topk_part_bytes), stream-ordered.
+// gate != nullptr: the launches do nothing unless *gate != 0 (the filter top-K's FALLBACK word).
+hipError_t knn_exact_topk_launch(int k, int m, int K, long long n, long long base, const unsigned *gids, const float *q,
+                                 const float *r, u64 *keys, int init, u64 *part, size_t part_bytes, int num_cu,
+                                 hipStream_t stream, const unsigned *gate = nullptr);
+// Filter top-K: umin[0][q] <- K-th smallest finite per-block minimum (one row for knn_thr_kernel).
+hipError_t knn_topk_umin_launch(float *umin, int nb, int m_padded, int K, hipStream_t stream);
+// Filter top-K after the scan: records + outlier rows -> per-query candidate lists (overflow -> FALLBACK), then, unless
+// FALLBACK, keys <- K smallest of (keys unless init, candidates).
+hipError_t knn_topk_filter_finish(int k, int m, int K, long long positions, long long base, const float *q, const float *r,
+                                  const u64 *rec, const unsigned short *rec_rows, const unsigned *counts, unsigned nlists,
+                                  unsigned slice, unsigned *ctl, RerankPieces pieces, const unsigned *perm,
+                                  unsigned n_outliers, const unsigned *outliers, u64 *cand, unsigned *ccount, unsigned ccap,
+                                  u64 *keys, int init, hipStream_t stream);
+// b[j] <- the K smallest of a[j] and b[j] (both sorted lists of K keys), sorted.
+hipError_t knn_topk_merge_launch(int m, int K, const u64 *a, u64 *b, hipStream_t stream);
+
 // ---- MFMA filter + exact re-rank (knn_filter.hip) ---------------------------
 // Device-side control words of one filter query (FilterState::ctl).
 enum {
@@ -242,6 +265,8 @@ struct FilterState {
     int scan_deal = 0;            // pruned scan: 0 auto (block counter unless several_slots), 1 fixed deal, 2 items from a block counter
     int scan_blocks = 0;          // pruned scan, blocks per CU: 0 auto (one for small shards when several_slots, else two), 1, 2
     int sample_stride = 0;        // deep-K scans (k > 32): tiles the sample pass skips between two it scores; 0 = library policy
+    int topk = 0;                 // K of the top-K call in progress (knn_filter_query_topk): the threshold comes from the K-th
+                                  // smallest per-block sample minimum; 0 = 1-NN
     int run_thresholds = 0;       // deep-K scan (64 < k <= 128): 0 / 1 thresholds tighten during the launch, 2 they stay as the sample pass left them
     int cells_lists = 0;          // pruned scan, who lists a cell's queries: 0 auto, 1 knn_cells_match_kernel, 2 the scan's own waves
     FilterWorkspace ws[KNN_SLOTS];
@@ -355,6 +380,9 @@ void knn_filter_free(FilterState &st);
 hipError_t knn_filter_query(FilterState &st, int slot, int m, const float *q_dev, const float *r_dev,
                             long long base, u64 *keys_dev, int num_cu, hipStream_t stream,
                             hipEvent_t ev_begin, hipEvent_t ev_end, bool init_keys = false, int *out_idx = nullptr);
+hipError_t knn_filter_query_topk(FilterState &st, int slot, int m, int K, const float *q, const float *r, long long base,
+                                 u64 *keys, bool init_keys, u64 *cand, unsigned *ccount, unsigned ccap, u64 *part,
+                                 size_t part_bytes, int num_cu, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end);
 // Test hook: raw filter scores S[m][n] (row-major) and the per-query thresholds for a query
 // batch, plus {sigma, eta, rho, amax, bmax}.  Synchronous.
 hipError_t knn_filter_debug(FilterState &st, int m, const float *q_dev, const float *r_dev,

@@ -861,3 +861,426 @@ hipError_t knn_synth_fill_launch(float *dst, long long count, u64 seed, long lon
                        first);
     return hipGetLastError();
 }
+
+// ------------------------------------------------------------------------------------------
+// Top-K (knn_index_query_topk): the K smallest packed keys per query, sorted ascending.
+//
+// knn_exact_topk_kernel<KC> — the exact scan with v0's arithmetic.  One wave per block, lanes = queries (coordinates in
+// VGPRs), rows streamed as wave-uniform scalar loads over the block's slice of the shard: the qregn scheme unpacked.  Each
+// lane keeps its query's K best (distance, LOCAL row) keys as a sorted column of LDS ([K][64] u64: 32 KiB at K = 64) and
+// its K-th key in a register; a row costs the 1-NN loop plus one 64-bit compare, and the rare accepted row is inserted
+// by shifting the larger keys down one place.  Rows whose distance is not finite never get in: their key is >= (+INF, 0),
+// the K-th key never exceeds it.  At the end the column goes to part[slice][query][K] with the global row numbers (base +
+// row, or gids[row]: both ascending in the local row, so the order the scan decided is kept).
+// KC = chunks of 16 dimensions held in VGPRs (k <= 128); KC = 0: any k, the query's coordinates re-read from memory.
+// ------------------------------------------------------------------------------------------
+template <int KC>
+__global__ __launch_bounds__(KNN_WAVE) void knn_exact_topk_kernel(const float *__restrict__ Q, const float *__restrict__ R,
+                                                                 int k, int m, long long n, int K, long long rows_per_slice,
+                                                                 long long base, const unsigned *__restrict__ gids,
+                                                                 u64 *__restrict__ part, const unsigned *__restrict__ gate)
+{
+#pragma clang fp contract(off)
+    extern __shared__ u64 topk_lst[];   // [K][KNN_WAVE]
+    if (gate && *gate == 0u)   // gated form: the filter top-K's fallback (runs only when the batch raised FALLBACK)
+        return;
+    constexpr int KM = KC > 0 ? 16 * KC : 1;
+    const int lane = threadIdx.x;
+    const int q = blockIdx.y * KNN_WAVE + lane;
+    const int qa = min(q, m - 1);
+    float qv[KM];
+#pragma unroll
+    for (int d = 0; d < KM; ++d)
+        qv[d] = KC > 0 && d < k ? Q[(size_t)qa * k + d] : 0.0f;
+    for (int t = 0; t < K; ++t)
+        topk_lst[t * KNN_WAVE + lane] = kKeyInit;
+    u64 kth = kKeyInit;
+    const long long i0 = (long long)blockIdx.x * rows_per_slice;
+    const long long i1 = min(n, i0 + rows_per_slice);
+    const float *__restrict__ r = R + (size_t)i0 * k;
+    const float *__restrict__ qp = Q + (size_t)qa * k;
+    for (long long i = i0; i < i1; ++i, r += k) {
+        float acc = 0.0f;
+        if (KC > 0) {
+#pragma unroll
+            for (int c = 0; c < (KC > 0 ? KC : 1); ++c) {
+                const int rem = k - 16 * c;   // wave-uniform
+                if (rem >= 16) {
+                    float rv[16];
+#pragma unroll
+                    for (int j = 0; j < 16; ++j)
+                        rv[j] = r[16 * c + j];   // wave-uniform address -> scalar loads
+#pragma unroll
+                    for (int j = 0; j < 16; ++j) {
+                        const float diff = qv[16 * c + j] - rv[j];
+                        const float sq = diff * diff;
+                        acc = acc + sq;
+                    }
+                } else if (rem > 0) {
+#pragma unroll
+                    for (int j = 0; j < 15; ++j)
+                        if (j < rem) {
+                            const float diff = qv[16 * c + j] - r[16 * c + j];
+                            const float sq = diff * diff;
+                            acc = acc + sq;
+                        }
+                }
+            }
+        } else {
+            for (int d = 0; d < k; ++d) {
+                const float diff = qp[d] - r[d];
+                const float sq = diff * diff;
+                acc = acc + sq;
+            }
+        }
+        const u64 key = pack_key(acc, (unsigned)i);
+        if (key < kth) {
+            int p = K - 1;
+            while (p > 0) {
+                const u64 prev = topk_lst[(p - 1) * KNN_WAVE + lane];
+                if (prev < key)
+                    break;
+                topk_lst[p * KNN_WAVE + lane] = prev;
+                --p;
+            }
+            topk_lst[p * KNN_WAVE + lane] = key;
+            kth = topk_lst[(K - 1) * KNN_WAVE + lane];
+        }
+    }
+    if (q >= m)
+        return;
+    u64 *__restrict__ out = part + ((size_t)blockIdx.x * m + q) * K;
+    for (int t = 0; t < K; ++t) {
+        const u64 key = topk_lst[t * KNN_WAVE + lane];
+        const unsigned row = (unsigned)key;
+        const bool real = (key >> 32) < 0x7F800000ull;
+        const unsigned g = gids ? (real ? gids[row] : 0u) : (unsigned)(base + (long long)row);
+        out[t] = real ? ((key & 0xFFFFFFFF00000000ull) | (u64)g) : kKeyInit;
+    }
+}
+
+// One wave: a (its lane t < K holds a[t], the others ~0) <- the K smallest of a and b (same form), both sorted.  The
+// output place of a[t] is t + #{b < a[t]}, of b[t] is t + #{a <= b[t]}: distinct places, a stable merge.  sa / sb / so:
+// the wave's three 64-key LDS rows.
+__device__ __forceinline__ u64 topk_wave_merge(u64 a, u64 b, int K, int lane, u64 *sa, u64 *sb, u64 *so)
+{
+    const u64 b0 = __shfl(b, 0, KNN_WAVE);
+    const u64 alast = __shfl(a, K - 1, KNN_WAVE);
+    if (b0 >= alast)   // nothing of b gets in (wave-uniform)
+        return a;
+    sa[lane] = a;
+    sb[lane] = b;
+    __syncthreads();
+    if (lane < K) {
+        int lo = 0, hi = K;   // #{b < a[lane]}
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (sb[mid] < a)
+                lo = mid + 1;
+            else
+                hi = mid;
+        }
+        if (lane + lo < K)
+            so[lane + lo] = a;
+        lo = 0;
+        hi = K;   // #{a <= b[lane]}
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (sa[mid] <= b)
+                lo = mid + 1;
+            else
+                hi = mid;
+        }
+        if (lane + lo < K)
+            so[lane + lo] = b;
+    }
+    __syncthreads();
+    const u64 r = lane < K ? so[lane] : ~0ull;
+    __syncthreads();
+    return r;
+}
+
+// One wave (block) per query: keys[q][0..K) <- the K smallest of (keys[q] unless init, lists[0][q], ..., lists[nl-1][q]),
+// sorted.  lists = [nl][m][K], every list sorted.  The fold of the scan's slices and knn_keys_topk_merge.
+__global__ __launch_bounds__(KNN_WAVE) void knn_topk_select_kernel(const u64 *__restrict__ lists, int nl, int m, int K,
+                                                                  u64 *__restrict__ keys, int init,
+                                                                  const unsigned *__restrict__ gate)
+{
+    __shared__ u64 sa[KNN_WAVE], sb[KNN_WAVE], so[KNN_WAVE];
+    if (gate && *gate == 0u)
+        return;
+    const int q = blockIdx.x;
+    const int lane = threadIdx.x;
+    u64 cur = lane < K ? (init ? kKeyInit : keys[(size_t)q * K + lane]) : ~0ull;
+    for (int l = 0; l < nl; ++l) {
+        const u64 b = lane < K ? lists[((size_t)l * m + q) * K + lane] : ~0ull;
+        cur = topk_wave_merge(cur, b, K, lane, sa, sb, so);
+    }
+    if (lane < K)
+        keys[(size_t)q * K + lane] = cur;
+}
+
+namespace {
+constexpr size_t kTopkPartBytes = (size_t)128 << 20;   // most bytes of the scan's per-slice lists of one query chunk
+
+// Slices of the shard the exact top-K scan splits one chunk of mc queries into: >= 1024 rows each, lists within
+// kTopkPartBytes (at least one), and ~32 waves per CU for K <= 16 (the scalar row loads need the occupancy: K 8 at C3's shape
+// 68 -> 22 ms) but ~8 for larger K (every slice fills its K-list from scratch and the fold reads every slice's list: K 64
+// 241 ms at 8, 334 at 32).
+long long topk_slices(int mc, int K, long long n, int num_cu)
+{
+    const unsigned qg = (unsigned)knn_divup(mc, KNN_WAVE);
+    long long slices = (long long)num_cu * (K <= 16 ? 32 : 8) / qg;
+    const long long by_rows = (n + 1023) / 1024;
+    const long long by_room = (long long)(kTopkPartBytes / ((size_t)mc * (size_t)K * sizeof(u64)));
+    if (slices > by_rows)
+        slices = by_rows;
+    if (slices > by_room)
+        slices = by_room;
+    if (slices > 65535)
+        slices = 65535;
+    if (slices < 1)
+        slices = 1;
+    const long long per = (n + slices - 1) / slices;
+    return (n + per - 1) / per;
+}
+}  // namespace
+
+size_t knn_topk_part_bytes(int m, int K, long long n, int num_cu)
+{
+    if (n <= 0 || m <= 0)
+        return 0;
+    const int mc = m < KNN_TOPK_CHUNK ? m : KNN_TOPK_CHUNK;
+    return (size_t)topk_slices(mc, K, n, num_cu) * (size_t)mc * (size_t)K * sizeof(u64);
+}
+
+hipError_t knn_exact_topk_launch(int k, int m, int K, long long n, long long base, const unsigned *gids, const float *q,
+                                 const float *r, u64 *keys, int init, u64 *part, size_t part_bytes, int num_cu,
+                                 hipStream_t s, const unsigned *gate)
+{
+    if (m <= 0 || K < 1 || K > KNN_TOPK_MAX)
+        return m <= 0 ? hipSuccess : hipErrorInvalidValue;
+    if (n <= 0) {   // nothing to add: the keys stay (or start at (+INF, 0))
+        if (init && !gate)
+            return knn_keys_fill_launch(keys, (int)((long long)m * K), s);
+        return hipSuccess;
+    }
+    for (int c0 = 0; c0 < m; c0 += KNN_TOPK_CHUNK) {
+        const int mc = m - c0 < KNN_TOPK_CHUNK ? m - c0 : KNN_TOPK_CHUNK;
+        const unsigned qg = (unsigned)knn_divup(mc, KNN_WAVE);
+        const long long slices = topk_slices(mc, K, n, num_cu);
+        if ((size_t)slices * (size_t)mc * (size_t)K * sizeof(u64) > part_bytes)
+            return hipErrorInvalidValue;
+        const long long per = (n + slices - 1) / slices;
+        const dim3 grid((unsigned)slices, qg), block(KNN_WAVE);
+        const size_t lds = (size_t)K * KNN_WAVE * sizeof(u64);
+        const float *qc = q + (size_t)c0 * k;
+#define KNN_TOPK_SCAN(KCV)                                                                                         \
+    hipLaunchKernelGGL((knn_exact_topk_kernel<KCV>), grid, block, lds, s, qc, r, k, mc, n, K, per, base, gids, part, gate)
+        switch ((k + 15) / 16) {
+        case 1: KNN_TOPK_SCAN(1); break;
+        case 2: KNN_TOPK_SCAN(2); break;
+        case 3: KNN_TOPK_SCAN(3); break;
+        case 4: KNN_TOPK_SCAN(4); break;
+        case 5: KNN_TOPK_SCAN(5); break;
+        case 6: KNN_TOPK_SCAN(6); break;
+        case 7: KNN_TOPK_SCAN(7); break;
+        case 8: KNN_TOPK_SCAN(8); break;
+        default: KNN_TOPK_SCAN(0); break;
+        }
+#undef KNN_TOPK_SCAN
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess)
+            return e;
+        hipLaunchKernelGGL(knn_topk_select_kernel, dim3((unsigned)mc), dim3(KNN_WAVE), 0, s, (const u64 *)part, (int)slices, mc,
+                           K, keys + (size_t)c0 * K, init, gate);
+        e = hipGetLastError();
+        if (e != hipSuccess)
+            return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t knn_topk_merge_launch(int m, int K, const u64 *a, u64 *b, hipStream_t s)
+{
+    if (m <= 0)
+        return hipSuccess;
+    if (K < 1 || K > KNN_TOPK_MAX)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(knn_topk_select_kernel, dim3((unsigned)m), dim3(KNN_WAVE), 0, s, a, 1, m, K, b, 0, (const unsigned *)nullptr);
+    return hipGetLastError();
+}
+
+// ---- top-K on the MFMA filter (knn_filter_query_topk) --------------------------------------------------------------------
+
+// Bitonic sort of one key per lane across the wave, ascending.
+__device__ __forceinline__ u64 topk_wave_sort(u64 v, int lane)
+{
+#pragma unroll
+    for (int kk = 2; kk <= KNN_WAVE; kk <<= 1) {
+#pragma unroll
+        for (int j = kk >> 1; j > 0; j >>= 1) {
+            const u64 o = __shfl_xor(v, j, KNN_WAVE);
+            const bool up = (lane & kk) == 0;
+            const bool lower = (lane & j) == 0;
+            const u64 lo = o < v ? o : v, hi = o < v ? v : o;
+            v = lower == up ? lo : hi;
+        }
+    }
+    return v;
+}
+
+__device__ __forceinline__ unsigned topk_f2ord(float f)
+{
+    const unsigned b = __float_as_uint(f);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float topk_ord2f(unsigned o)
+{
+    return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
+}
+
+// One wave per query: umin[0][q] <- the K-th smallest FINITE per-block minimum of umin[0 .. nb)[q] (+INF when fewer than K
+// blocks hold one).  The sample pass's blocks score disjoint tiles, and a padding position's or an out-of-box row's score is
+// +INF (norm +INF), so K finite minima are the scores of K distinct real rows.  knn_thr_kernel then reads this one row.
+__global__ __launch_bounds__(KNN_WAVE) void knn_topk_umin_kernel(float *__restrict__ umin, int nb, int m_padded, int K)
+{
+    __shared__ u64 sa[KNN_WAVE], sb[KNN_WAVE], so[KNN_WAVE];
+    const int q = blockIdx.x, lane = threadIdx.x;
+    u64 cur = ~0ull;
+    for (int b0 = 0; b0 < nb; b0 += KNN_WAVE) {
+        const int b = b0 + lane;
+        const float u = b < nb ? umin[(size_t)b * m_padded + q] : INFINITY;
+        u64 key = (u < INFINITY && u > -INFINITY) ? (((u64)topk_f2ord(u) << 32) | (u64)(unsigned)b) : ~0ull;
+        key = topk_wave_sort(key, lane);
+        cur = topk_wave_merge(cur, lane < K ? key : ~0ull, K, lane, sa, sb, so);
+    }
+    const u64 kth = __shfl(cur, K - 1, KNN_WAVE);
+    __syncthreads();
+    if (lane == 0)
+        umin[q] = kth == ~0ull ? INFINITY : topk_ord2f((unsigned)(kth >> 32));
+}
+
+__device__ __forceinline__ void topk_cand_push(u64 key, unsigned q, u64 *__restrict__ cand, unsigned *__restrict__ ccount,
+                                               unsigned ccap, unsigned *__restrict__ ctl)
+{
+    const unsigned slot = atomicAdd(&ccount[q], 1u);
+    if (slot < ccap)
+        cand[(size_t)q * ccap + slot] = key;
+    else
+        ctl[KNN_CTL_FALLBACK] = 1u;   // candidates dropped: the gated exact top-K answers the batch
+}
+
+// The filter's records, every row of every record with v0 arithmetic (through perm on a cell-sorted layout): each finite key
+// goes to its query's candidate list.  One block per record list (= filter wave), as knn_rerank_kernel.
+__global__ __launch_bounds__(KNN_BLOCK) void knn_topk_rerank_kernel(const float *__restrict__ Q, const float *__restrict__ R,
+                                                                   int k, long long n, long long base,
+                                                                   const u64 *__restrict__ rec,
+                                                                   const unsigned short *__restrict__ rec_rows,
+                                                                   const unsigned *__restrict__ counts, unsigned nlists,
+                                                                   unsigned slice, unsigned *__restrict__ ctl,
+                                                                   RerankPieces pieces, const unsigned *__restrict__ perm,
+                                                                   u64 *__restrict__ cand, unsigned *__restrict__ ccount,
+                                                                   unsigned ccap)
+{
+    const unsigned list_id = blockIdx.x;
+    unsigned qrow_base = pieces.qrow_base[0];
+#pragma unroll
+    for (int i = 1; i < 4; ++i)
+        if (list_id >= pieces.list_base[i])
+            qrow_base = pieces.qrow_base[i];
+    if (ctl[KNN_CTL_FALLBACK] != 0u || list_id >= nlists)
+        return;
+    const unsigned want = counts[list_id];
+    const unsigned nrec = min(want, slice);
+    if (threadIdx.x == 0 && want > slice)
+        ctl[KNN_CTL_FALLBACK] = 1u;
+    const u64 *__restrict__ list = rec + (size_t)list_id * slice;
+    for (unsigned c = threadIdx.x; c < nrec * 16u; c += KNN_BLOCK) {
+        const unsigned rmask = rec_rows ? rec_rows[(size_t)list_id * slice + (c >> 4)] : 0xFFFFu;
+        unsigned qi = 0u;
+        const u64 key = rerank_pair<0>(Q, R, k, n, base, list[c >> 4], c & 15u, rmask, qrow_base, perm, qi);
+        if (key != ~0ull)
+            topk_cand_push(key, qi, cand, ccount, ccap, ctl);
+    }
+}
+
+// Rows outside the filter's robust box never enter the scan: every (query, listed row) pair with v0 arithmetic, each finite
+// key to the query's candidate list.  grid (row blocks, queries).
+__global__ __launch_bounds__(KNN_BLOCK) void knn_topk_outlier_kernel(const float *__restrict__ Q, const float *__restrict__ R,
+                                                                    int k, unsigned count, long long base,
+                                                                    const unsigned *__restrict__ list, unsigned *__restrict__ ctl,
+                                                                    u64 *__restrict__ cand, unsigned *__restrict__ ccount,
+                                                                    unsigned ccap)
+{
+#pragma clang fp contract(off)
+    if (ctl[KNN_CTL_FALLBACK] != 0u)
+        return;
+    const unsigned q = blockIdx.y;
+    const float *__restrict__ qp = Q + (size_t)q * k;
+    for (unsigned j = blockIdx.x * KNN_BLOCK + threadIdx.x; j < count; j += gridDim.x * KNN_BLOCK) {
+        const unsigned row = list[j];
+        const float *__restrict__ r = R + (size_t)row * k;
+        float acc = 0.0f;
+        for (int d = 0; d < k; ++d) {
+            const float diff = qp[d] - r[d];
+            const float sq = diff * diff;
+            acc = acc + sq;
+        }
+        if (acc < INFINITY)
+            topk_cand_push(pack_key(acc, (unsigned)(base + (long long)row)), q, cand, ccount, ccap, ctl);
+    }
+}
+
+// One wave per query, gated on NO fallback: keys[q] <- the K smallest of (keys[q] unless init, the query's candidates), sorted.
+__global__ __launch_bounds__(KNN_WAVE) void knn_topk_select_cand_kernel(const u64 *__restrict__ cand,
+                                                                       const unsigned *__restrict__ ccount, unsigned ccap,
+                                                                       int K, u64 *__restrict__ keys, int init,
+                                                                       const unsigned *__restrict__ fallback)
+{
+    __shared__ u64 sa[KNN_WAVE], sb[KNN_WAVE], so[KNN_WAVE];
+    if (*fallback != 0u)
+        return;
+    const int q = blockIdx.x, lane = threadIdx.x;
+    const unsigned c = min(ccount[q], ccap);
+    u64 cur = lane < K ? (init ? kKeyInit : keys[(size_t)q * K + lane]) : ~0ull;
+    for (unsigned i0 = 0; i0 < c; i0 += KNN_WAVE) {
+        u64 v = i0 + lane < c ? cand[(size_t)q * ccap + i0 + lane] : ~0ull;
+        v = topk_wave_sort(v, lane);
+        cur = topk_wave_merge(cur, lane < K ? v : ~0ull, K, lane, sa, sb, so);
+    }
+    if (lane < K)
+        keys[(size_t)q * K + lane] = cur;
+}
+
+hipError_t knn_topk_umin_launch(float *umin, int nb, int m_padded, int K, hipStream_t s)
+{
+    hipLaunchKernelGGL(knn_topk_umin_kernel, dim3((unsigned)m_padded), dim3(KNN_WAVE), 0, s, umin, nb, m_padded, K);
+    return hipGetLastError();
+}
+
+hipError_t knn_topk_filter_finish(int k, int m, int K, long long positions, long long base, const float *q, const float *r,
+                                  const u64 *rec, const unsigned short *rec_rows, const unsigned *counts, unsigned nlists,
+                                  unsigned slice, unsigned *ctl, RerankPieces pieces, const unsigned *perm,
+                                  unsigned n_outliers, const unsigned *outliers, u64 *cand, unsigned *ccount, unsigned ccap,
+                                  u64 *keys, int init, hipStream_t s)
+{
+    if (nlists) {
+        hipLaunchKernelGGL(knn_topk_rerank_kernel, dim3(nlists), dim3(KNN_BLOCK), 0, s, q, r, k, positions, base, rec, rec_rows,
+                           counts, nlists, slice, ctl, pieces, perm, cand, ccount, ccap);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess)
+            return e;
+    }
+    if (n_outliers) {
+        const unsigned gx = (n_outliers + KNN_BLOCK - 1) / KNN_BLOCK < 64u ? (n_outliers + KNN_BLOCK - 1) / KNN_BLOCK : 64u;
+        hipLaunchKernelGGL(knn_topk_outlier_kernel, dim3(gx, (unsigned)m), dim3(KNN_BLOCK), 0, s, q, r, k, n_outliers, base,
+                           outliers, ctl, cand, ccount, ccap);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess)
+            return e;
+    }
+    hipLaunchKernelGGL(knn_topk_select_cand_kernel, dim3((unsigned)m), dim3(KNN_WAVE), 0, s, (const u64 *)cand,
+                       (const unsigned *)ccount, ccap, K, keys, init, (const unsigned *)(ctl + KNN_CTL_FALLBACK));
+    return hipGetLastError();
+}

@@ -2489,6 +2489,8 @@ static hipError_t launch_filter(FilterState &st, FilterWorkspace &w, int m, int 
         stride = 1;
     if (stride > 16)   // (32 / 64 / 8 A/B'd at C3 in round 2: 0.547 / 0.555 / 0.585 ms per step against 0.5505: flat)
         stride = 16;
+    if (st.topk > 0)   // top-K: a threshold from the K-th block minimum passes ~ n K / (sampled rows) rows: sample K times denser
+        stride = std::max<long long>(1, stride / st.topk);
     const long long ns = (st.ntiles + stride - 1) / stride;
     unsigned sb = (unsigned)num_cu * 2;  // 2 waves per SIMD, like the main pass
     if (sb > kSampleBlocks)
@@ -2501,6 +2503,13 @@ static hipError_t launch_filter(FilterState &st, FilterWorkspace &w, int m, int 
         sb = (unsigned)((ns + 31) / 32);
     if (sb < 1)
         sb = 1;
+    if (st.topk > 0) {
+        // top-K: the threshold is the K-th smallest per-block minimum, so the pass needs well over K blocks (fewer than K
+        // blocks with a real row raises FALLBACK): at least 4K of them, as far as the sampled tiles go
+        const long long want = std::min<long long>(std::min<long long>(ns, kSampleBlocks), 4ll * st.topk);
+        if ((long long)sb < want)
+            sb = (unsigned)want;
+    }
     {   // per-block minima buffer, grown on demand
         const size_t need = (size_t)sb * (size_t)m_padded;
         if (need > w.umin_cap) {
@@ -2534,8 +2543,13 @@ static hipError_t launch_filter(FilterState &st, FilterWorkspace &w, int m, int 
     }
 
     // 2. thresholds
+    int thr_nb = (int)sb;
+    if (st.topk > 0) {   // top-K: the K-th smallest real per-block minimum instead of the smallest (knn_topk_umin_kernel)
+        FTRY(knn_topk_umin_launch(w.umin, thr_nb, m_padded, st.topk, s));
+        thr_nb = 1;
+    }
     hipLaunchKernelGGL(knn_thr_kernel, dim3((unsigned)(m_padded / 32)), dim3(32 * THR_PARTS), 0, s, w.umin,
-                       (int)sb, w.qry_norms, w.qry_amax, m, m_padded, st.k, st.kt, st.sigma, st.bmax, st.nmax, kAmaxLimit,
+                       thr_nb, w.qry_norms, w.qry_amax, m, m_padded, st.k, st.kt, st.sigma, st.bmax, st.nmax, kAmaxLimit,
                        w.thr, w.ctl, w.qpart, (m_padded + 255) / 256, w.counts, w.nlists);
     FTRY(hipGetLastError());
 
@@ -2612,6 +2626,8 @@ static hipError_t launch_filter_tiled(FilterState &st, FilterWorkspace &w, int m
         stride = std::min<long long>(32, std::max<long long>(1, st.ntiles / 64));
     if (st.sample_stride > 0)   // option `sample_stride` (the sweep's knob, and the tests' like-for-like comparison)
         stride = std::min<long long>(st.sample_stride, std::max<long long>(1, st.ntiles / 16));
+    if (st.topk > 0)   // top-K: a threshold from the K-th block minimum passes ~ n K / (sampled rows) rows: sample K times denser
+        stride = std::max<long long>(1, stride / st.topk);
     const long long ns = (st.ntiles + stride - 1) / stride;
     unsigned sb = gx;
     if ((long long)sb > ns)
@@ -2633,8 +2649,13 @@ static hipError_t launch_filter_tiled(FilterState &st, FilterWorkspace &w, int m
                        stride, w.umin, m_padded, w.records, w.counts, w.ctl, w.slice,
                        (unsigned short *)(w.records + w.rec_cap));
     FTRY(hipGetLastError());
+    int thr_nb = (int)sb;
+    if (st.topk > 0) {   // top-K: the K-th smallest real per-block minimum instead of the smallest (knn_topk_umin_kernel)
+        FTRY(knn_topk_umin_launch(w.umin, thr_nb, m_padded, st.topk, s));
+        thr_nb = 1;
+    }
     hipLaunchKernelGGL(knn_thr_kernel, dim3((unsigned)(m_padded / 32)), dim3(32 * THR_PARTS), 0, s, w.umin,
-                       (int)sb, w.qry_norms, w.qry_amax, m, m_padded, st.k, st.kt, st.sigma, st.bmax, st.nmax, kAmaxLimit,
+                       thr_nb, w.qry_norms, w.qry_amax, m, m_padded, st.k, st.kt, st.sigma, st.bmax, st.nmax, kAmaxLimit,
                        w.thr, w.ctl, w.qpart, (m_padded + 255) / 256, w.counts, w.nlists, nullptr,
                        w.thr + (size_t)w.m_cap, w.thr + 2 * (size_t)w.m_cap, (unsigned *)(w.thr + 3 * (size_t)w.m_cap));
     FTRY(hipGetLastError());
@@ -2705,6 +2726,8 @@ static hipError_t launch_filter_chunked(FilterState &st, FilterWorkspace &w, int
         stride = 1;
     if (stride > 16)
         stride = 16;
+    if (st.topk > 0)   // top-K: a threshold from the K-th block minimum passes ~ n K / (sampled rows) rows: sample K times denser
+        stride = std::max<long long>(1, stride / st.topk);
     const long long sgroups = ((st.ntiles + stride - 1) / stride + CHK_T - 1) / CHK_T;
     unsigned sb = gx;
     if ((long long)sb > sgroups)
@@ -2723,8 +2746,13 @@ static hipError_t launch_filter_chunked(FilterState &st, FilterWorkspace &w, int
                        st.ref_norms, (const h8 *)w.qry_frags, w.thr, st.kt, qtiles, st.ntiles, stride, w.umin, m_padded, w.records,
                        w.counts, w.ctl, w.slice, (unsigned short *)(w.records + w.rec_cap), 0u, gy);
     FTRY(hipGetLastError());
+    int thr_nb = (int)sb;
+    if (st.topk > 0) {   // top-K: the K-th smallest real per-block minimum instead of the smallest (knn_topk_umin_kernel)
+        FTRY(knn_topk_umin_launch(w.umin, thr_nb, m_padded, st.topk, s));
+        thr_nb = 1;
+    }
     hipLaunchKernelGGL(knn_thr_kernel, dim3((unsigned)(m_padded / 32)), dim3(32 * THR_PARTS), 0, s, w.umin,
-                       (int)sb, w.qry_norms, w.qry_amax, m, m_padded, st.k, st.kt, st.sigma, st.bmax, st.nmax, kAmaxLimit,
+                       thr_nb, w.qry_norms, w.qry_amax, m, m_padded, st.k, st.kt, st.sigma, st.bmax, st.nmax, kAmaxLimit,
                        w.thr, w.ctl, w.qpart, (m_padded + 255) / 256, w.counts, w.nlists);
     FTRY(hipGetLastError());
     if (w.ev_begin)
@@ -2737,6 +2765,38 @@ static hipError_t launch_filter_chunked(FilterState &st, FilterWorkspace &w, int
     FTRY(hipGetLastError());
     if (w.ev_end)
         FTRY(hipEventRecord(w.ev_end, s));
+    return hipSuccess;
+}
+
+// The sample pass, thresholds and scan for the index's K-steps (kt): records in w's lists.
+static hipError_t launch_scan_for_kt(FilterState &st, FilterWorkspace &w, int m, int num_cu, hipStream_t s)
+{
+    const int qtiles = (m + 31) / 32;
+    switch (st.kt) {
+    case 1: FTRY(launch_filter<1>(st, w, m, num_cu, s)); break;
+    case 2: FTRY(launch_filter<2>(st, w, m, num_cu, s)); break;
+    case 4:
+        if (qtiles >= 16)
+            FTRY((launch_filter_tiled<4, 4>(st, w, m, num_cu, s)));
+        else
+            FTRY(launch_filter<4>(st, w, m, num_cu, s));
+        break;
+    case 8:
+        if (qtiles >= 16)
+            FTRY((launch_filter_tiled<8, 4>(st, w, m, num_cu, s)));
+        else
+            FTRY(launch_filter<8>(st, w, m, num_cu, s));
+        break;
+    // 128 < k <= 512: always the LDS-tiled scan (a reference tile is 16 / 32 KiB: no wave can hold one in registers beside its
+    // queries); the B operands of 2 / 1 blocks of 32 queries are the wave's 128 operand registers
+    case 16: FTRY((launch_filter_tiled<16, 2>(st, w, m, num_cu, s))); break;
+    case 32: FTRY((launch_filter_tiled<32, 1>(st, w, m, num_cu, s))); break;
+    default:   // k > 512: K in chunks of 128 dimensions
+        if (st.kt % CHK_KC != 0)
+            return hipErrorInvalidValue;
+        FTRY(launch_filter_chunked(st, w, m, num_cu, s));
+        break;
+    }
     return hipSuccess;
 }
 
@@ -2772,32 +2832,7 @@ hipError_t knn_filter_query(FilterState &st, int slot, int m, const float *q, co
     if (init_keys)
         FTRY(knn_keys_fill_launch(keys, m, s));
     FTRY(prep_queries(st, w, m, q, s));
-    const int qtiles = (m + 31) / 32;
-    switch (st.kt) {
-    case 1: FTRY(launch_filter<1>(st, w, m, num_cu, s)); break;
-    case 2: FTRY(launch_filter<2>(st, w, m, num_cu, s)); break;
-    case 4:
-        if (qtiles >= 16)
-            FTRY((launch_filter_tiled<4, 4>(st, w, m, num_cu, s)));
-        else
-            FTRY(launch_filter<4>(st, w, m, num_cu, s));
-        break;
-    case 8:
-        if (qtiles >= 16)
-            FTRY((launch_filter_tiled<8, 4>(st, w, m, num_cu, s)));
-        else
-            FTRY(launch_filter<8>(st, w, m, num_cu, s));
-        break;
-    // 128 < k <= 512: always the LDS-tiled scan (a reference tile is 16 / 32 KiB: no wave can hold one in registers beside its
-    // queries); the B operands of 2 / 1 blocks of 32 queries are the wave's 128 operand registers
-    case 16: FTRY((launch_filter_tiled<16, 2>(st, w, m, num_cu, s))); break;
-    case 32: FTRY((launch_filter_tiled<32, 1>(st, w, m, num_cu, s))); break;
-    default:   // k > 512: K in chunks of 128 dimensions
-        if (st.kt % CHK_KC != 0)
-            return hipErrorInvalidValue;
-        FTRY(launch_filter_chunked(st, w, m, num_cu, s));
-        break;
-    }
+    FTRY(launch_scan_for_kt(st, w, m, num_cu, s));
     // exact re-rank of the survivors; a list that overflowed its slice raises the fallback flag
     FTRY(knn_rerank_launch(st.k, positions, q, r, base, w.records,
                            w.has_rows ? (const unsigned short *)(w.records + w.rec_cap) : nullptr, w.counts, w.nlists,
@@ -2808,6 +2843,42 @@ hipError_t knn_filter_query(FilterState &st, int slot, int m, const float *q, co
     FTRY(knn_exact_launch(st.k, m, st.n, base, q, r, keys, num_cu, w.ctl + KNN_CTL_FALLBACK, s));
     if (out_idx)
         FTRY(knn_keys_unpack_launch(keys, m, out_idx, s));
+    return hipSuccess;
+}
+
+// Top-K on the filter (include/knn_mi355x.h §2c): the dense layouts, or a cell-sorted layout in the shard's frame
+// scanned in full through perm.  The scan is the 1-NN one; its threshold comes from the K-th smallest real per-block sample
+// minimum (st.topk), running thresholds are off (the caller sets them so).  Records and outlier rows go to per-query candidate
+// lists, a select kernel keeps the K smallest; a batch that raised FALLBACK (a query nothing bounds, fewer than K sampled
+// blocks with a real row, records or candidates overflowing) is answered by the gated exact top-K instead.
+hipError_t knn_filter_query_topk(FilterState &st, int slot, int m, int K, const float *q, const float *r, long long base,
+                                 u64 *keys, bool init_keys, u64 *cand, unsigned *ccount, unsigned ccap, u64 *part,
+                                 size_t part_bytes, int num_cu, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end)
+{
+    if (st.cells && st.cells->centred)
+        return hipErrorInvalidValue;   // per-cell frames: the full scan cannot read them (the caller sends these to exact top-K)
+    FilterWorkspace &w = st.ws[slot];
+    w.last_used_cells = false;
+    w.ev_begin = ev_begin;
+    w.ev_end = ev_end;
+    FTRY(ensure_workspace(st, w, m));
+    w.ctl_cur = w.ctl;
+    w.ovf_base = w.ovf_cap = 0u;
+    FTRY(prep_queries(st, w, m, q, s));
+    FTRY(hipMemsetAsync(ccount, 0, (size_t)m * sizeof(unsigned), s));
+    st.topk = K;
+    const hipError_t e = launch_scan_for_kt(st, w, m, num_cu, s);
+    st.topk = 0;
+    FTRY(e);
+    const unsigned *perm = st.cells ? st.cells->perm : nullptr;
+    const long long positions = st.cells ? st.ntiles * 32 : st.n;
+    FTRY(knn_topk_filter_finish(st.k, m, K, positions, base, q, r, w.records,
+                                w.has_rows ? (const unsigned short *)(w.records + w.rec_cap) : nullptr, w.counts, w.nlists,
+                                w.slice, w.ctl, w.pieces, perm, st.n_outliers, st.outliers, cand, ccount, ccap, keys,
+                                init_keys ? 1 : 0, s));
+    // gated: runs only if the batch raised FALLBACK; folds into the keys the select left alone
+    FTRY(knn_exact_topk_launch(st.k, m, K, st.n, base, nullptr, q, r, keys, init_keys ? 1 : 0, part, part_bytes, num_cu, s,
+                               w.ctl + KNN_CTL_FALLBACK));
     return hipSuccess;
 }
 
