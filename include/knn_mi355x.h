@@ -291,6 +291,11 @@ int knn_index_query_topk_host(knn_index *idx, int m, int K, const float *queries
  *             which brings per-cell frames with it; 0 = library policy (8-bit rows for shards of >= 2^24 rows whose build
  *             sample is uniform-like and not clustered).  Read when an index is built; results are identical either way.
  *             knn_get_option("cells_u8_builds") counts the layouts built with 8-bit rows (read-only).
+ *   "cells_u8_frame" the frame of the 8-bit rows: 2 = per-dimension bins (one shard-wide scale, an offset per bin of every
+ *             dimension: the layout stays in the shard's one frame and the scan takes a per-query operand), 1 = each cell's own
+ *             frame, 0 = auto (bins where they fit the cells — uniform-like rows —, per-cell frames on clustered data).  Read when
+ *             an index is built; results are identical either way.  knn_get_option("cells_u8_bin_builds") counts the layouts built
+ *             with bin frames (read-only).  Either way the top-K queries of an index with 8-bit rows take the exact top-K scan.
  *   "cells_lists" who makes a cell's list of queries (those of the batch that cannot rule the cell out) on the pruned path:
  *             1 = knn_cells_match_kernel in a launch of its own between the preparation and the scan (lists in memory),
  *             2 = the scan's waves for the items they take (same test, same arithmetic, lists in LDS: one launch and one
@@ -345,6 +350,12 @@ int knn_debug_plan_shard(int k, int m, long long rows, long long out[4]);
  * v = (row - centre) x scale in fp32: codes[k] = its bytes, out[0] = the largest per-coordinate error bound, out[1] = eta for a
  * query of largest |coordinate| amax.  0 on success. */
 int knn_debug_u8_row(int k, const float *row, const float *centre, float scale, double amax, unsigned char *codes, double out[2]);
+/* Test hooks (host arithmetic, no GPU) for the 8-bit rows in bin frames (option "cells_u8_frame"): knn_debug_u8_bin_row codes
+ * one row, u = (row - centre) x scale, v = u - w in fp32 -> codes[k], *err = the largest per-coordinate error bound;
+ * knn_debug_u8_bin_threshold -> *thr, the scan's threshold for a query whose fp16 B operand in the bins' units has the bits
+ * b_bits[16], with Dup dup (shard units), 2^e ratio and the shard's largest err, N'' and sum |w|.  0 on success. */
+int knn_debug_u8_bin_row(int k, const float *row, const float *centre, float scale, const float *w, unsigned char *codes, double *err);
+int knn_debug_u8_bin_threshold(int k, const unsigned short *b_bits, float dup, float ratio, float er, float nmax, float w1, float *thr);
 
 /* Test hook (host arithmetic only, no GPU needed): every size one scan launch of the cell-pruned path and the re-rank behind
  * it index with, for an index of `nitems` work items on a device of num_cu CUs and a batch of m <= 1024 queries:

@@ -386,6 +386,12 @@ int knn_set_option(const char *name, long long value)
         g_knn_cells_rows = (int)value;
         return KNN_OK;
     }
+    if (!strcmp(name, "cells_u8_frame")) {
+        if (value < 0 || value > 2)
+            return fail(KNN_EINVAL, "knn_set_option: cells_u8_frame must be 0 (auto), 1 (per-cell frames) or 2 (per-dimension bin frames)");
+        g_knn_cells_u8_frame = (int)value;
+        return KNN_OK;
+    }
     if (!strcmp(name, "cells_lists")) {
         if (value < 0 || value > 2)
             return fail(KNN_EINVAL, "knn_set_option: cells_lists must be 0 (auto), 1 (match launch) or 2 (the scan lists its own items)");
@@ -455,6 +461,10 @@ long long knn_get_option(const char *name)
         return (long long)g_knn_cells_centre.load();
     if (name && !strcmp(name, "cells_centred_builds"))   // read-only: cell-sorted layouts moved into per-cell frames so far
         return g_knn_cells_centred_builds.load();
+    if (name && !strcmp(name, "cells_u8_frame"))
+        return (long long)g_knn_cells_u8_frame.load();
+    if (name && !strcmp(name, "cells_u8_bin_builds"))   // read-only: 8-bit-row layouts built in bin frames so far
+        return g_knn_cells_u8_bin_builds.load();
     if (name && !strcmp(name, "cells_rows"))
         return (long long)g_knn_cells_rows.load();
     if (name && !strcmp(name, "cells_u8_builds"))   // read-only: cell-sorted layouts given 8-bit rows so far
@@ -981,13 +991,14 @@ int knn_index_query_topk(knn_index *idx, int slot, int m, int K, const float *qu
             HIP_TRY(knn_keys_fill_launch((u64 *)keys_dev, mk, s));
     } else {
         // Which path: the MFMA filter for the dense layouts and for a cell-sorted layout in the shard's frame
-        // (scanned in full), under the 1-NN rule's options and sizes; exact top-K for per-cell frames (centred, u8), grid
+        // (scanned in full), under the 1-NN rule's options and sizes; exact top-K for per-cell frames (centred), 8-bit rows, grid
         // indexes, cell-range shards (their keys need gids), tiny shards, few queries, and outlier lists longer than half a
         // query's candidate room.
         const long long path = g_opt_path;
         const unsigned ccap = (unsigned)std::min<long long>(4096 + 128 * (long long)K, ((long long)32 << 20) / m);
         const bool use_filter = !idx->sharded && idx->filter.usable && !(idx->grid && (path == 0 || path == 3)) &&
-                                !(idx->filter.cells && idx->filter.cells->centred) && idx->filter.n_outliers <= ccap / 2 &&
+                                !(idx->filter.cells && (idx->filter.cells->centred || idx->filter.cells->rows_u8)) &&
+                                idx->filter.n_outliers <= ccap / 2 &&
                                 ccap >= 64 &&
                                 (path == 2 || (path == 0 && m >= 5 && (idx->n >= 65536 || idx->filter_wanted)));
         const size_t need = knn_topk_part_bytes(m, K, idx->n, idx->num_cu);

@@ -1717,6 +1717,9 @@ extern "C" int knn_debug_scan_stamps(unsigned long long *out)
 // NIF:  16 < k <= 30: the norms ride in the fragments' K-slots 30, 31 (cell_tile_step_nif): no norm window
 // U8:   with CTR: `rf` / `rn` are the 8-bit rows and their norms (knn_cells_recentre_kernel) — 512-byte tiles, widened to fp16 in
 //       registers (cell_widen_u8) at every step; the pair's threshold from knn_bound_consts_u8's constants
+//       without CTR (bin frames, knn_cells_bin_rows_kernel): the same tiles, rn = N''; the 12-wave one-frame scan with the B operands
+//       of `qfg` times 2^e, s_thr = knn_u8_bin_threshold of every query (made in the fill), and per (cell, block of 32 queries)
+//       the pair term B.w_c — eight exact fp32 products, fp32 sums, one swap of halves — taken off the threshold (knn_filter_dev.h)
 template <bool DYN, int K, bool SELF, int KT = 1, bool CTR = false, bool NIF = false, bool U8 = false>
 __global__ __launch_bounds__(64 * (KT == 1 && !CTR ? CELL_SCAN_WAVES : CELL_SCAN_WAVES_KT2), CTR ? 4 : KT == 1 ? 6 : 4) void knn_cells_scan_kernel(
     const h8 *__restrict__ rf, const float *__restrict__ rn, const u64 *__restrict__ items, unsigned nitems,
@@ -1803,12 +1806,23 @@ __global__ __launch_bounds__(64 * (KT == 1 && !CTR ? CELL_SCAN_WAVES : CELL_SCAN
         const int kq = K > 0 ? K : krt;
         for (int i = threadIdx.x; i < m_padded * 16; i += 64 * SW)
             ((float *)s_dyn)[i] = (i >> 4) < m && (i & 15) < kq ? Q[(size_t)(i >> 4) * kq + (i & 15)] : 0.0f;
+    } else if constexpr (U8) {   // bin frames: the B operands at the bins' scale (x 2^e: exact) and every query's threshold
+        const _Float16 rt = (_Float16)self.bin_ratio;
+        for (int i = threadIdx.x; i < m_padded * 2; i += 64 * SW)
+            s_qf[i] = qfg[i] * rt;
+        const int kq = K > 0 ? K : krt;
+        for (int i = threadIdx.x; i < m_padded; i += 64 * SW) {
+            const size_t at = (size_t)(i >> 5) * 64 + (size_t)(i & 31);
+            s_thr[i] = knn_u8_bin_threshold(kq, qfg[at] * rt, qfg[at + 32] * rt, self.dup[i], self.bin_ratio, self.bin_er,
+                                            self.bin_nmax, self.bin_w1);
+        }
     } else {
         for (int i = threadIdx.x; i < m_padded * 2 * KT; i += 64 * SW)
             s_qf[i] = qfg[i];
     }
-    for (int i = threadIdx.x; i < m_padded; i += 64 * SW)
-        s_thr[i] = thrg[i];
+    if constexpr (CTR || !U8)
+        for (int i = threadIdx.x; i < m_padded; i += 64 * SW)
+            s_thr[i] = thrg[i];
     if constexpr (SELF || CTR)
         for (int i = threadIdx.x; i < m_padded; i += 64 * SW)
             s_dup[i] = self.dup[i];
@@ -1912,6 +1926,9 @@ __global__ __launch_bounds__(64 * (KT == 1 && !CTR ? CELL_SCAN_WAVES : CELL_SCAN
             const unsigned l1 = SELF ? 0u : dense ? 64u + (unsigned)lane : (unsigned)list[min(64u + (unsigned)lane, nq - 1u)];
             float ccv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, c_scale = 0.f, c_ratio = 0.f, c_bmax = 0.f, c_nmax = 0.f, c_er = 0.f, th_kept = 0.f;
             h8 b_kept = {0, 0, 0, 0, 0, 0, 0, 0};
+            h8 wc = {0, 0, 0, 0, 0, 0, 0, 0};   // bin frames: this lane's half of the cell's offset w_c
+            if constexpr (U8 && !CTR)
+                wc = ((const h8 *)self.binw)[(size_t)cellj * 2 + half];
             if constexpr (CTR) {   // the cell's frame: this lane's half of the centre, the scale, the cell's bounds
                 const float *__restrict__ fr = self.frame + (size_t)cellj * KNN_CELL_FRAME_WORDS;
 #pragma unroll
@@ -1985,6 +2002,15 @@ __global__ __launch_bounds__(64 * (KT == 1 && !CTR ? CELL_SCAN_WAVES : CELL_SCAN
                         for (int kk = 0; kk < KT; ++kk)
                             b[kk] = s_qf[((qid >> 5) * KT + (unsigned)kk) * 64u + (unsigned)half * 32u + (qid & 31u)];
                         th = valid ? s_thr[qid] : -INFINITY;
+                        if constexpr (U8) {   // bin frames: the pair term B.w_c (exact fp32 products, fp32 sums in dimension order —
+                                              // no FMA or dot instruction in this kernel; the rounding is in s_thr)
+                            float dw = (float)b[0][0] * (float)wc[0];
+#pragma unroll
+                            for (int i = 1; i < 8; ++i)
+                                dw = dw + (float)b[0][i] * (float)wc[i];
+                            dw = dw + __shfl_xor(dw, 32, KNN_WAVE);
+                            th = th - dw;
+                        }
                     }
                     // (a hit is recorded right behind its tile: parking the nine masks of a pass until its end, as round 2
                     // did, kept 18 registers busy with them — the allocator put the mask pairs in VGPRs)
@@ -1993,6 +2019,8 @@ __global__ __launch_bounds__(64 * (KT == 1 && !CTR ? CELL_SCAN_WAVES : CELL_SCAN
                         if (p < nt) {
                             u64 mask;
                             if constexpr (U8) {
+                                if constexpr (!CTR)   // (else the widened tiles, invariant over the blocks of queries, are hoisted
+                                    __asm__ volatile("" : "+v"(a8[p]));   //  out of that loop: 36 registers under the 80-register cap)
                                 const h8 a1[1] = {cell_widen_u8(a8[p])};
                                 mask = cell_tile_step<1>(a1, my_nrm, p, half, b, th);
                             } else {
@@ -2002,7 +2030,10 @@ __global__ __launch_bounds__(64 * (KT == 1 && !CTR ? CELL_SCAN_WAVES : CELL_SCAN
                                 const bool hit = (mask >> lane) & 1ull;
                                 const unsigned pos = cnt + __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32),
                                                                                      __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-                                const u64 r = ((u64)qid << 32) | ((u64)(t0 + (unsigned)p) << 1) | (u64)half;
+                                unsigned hh = (unsigned)half;
+                                if constexpr (U8 && !CTR)   // (else the nine tiles' record words are made ahead of the query loop:
+                                    __asm__ volatile("" : "+v"(hh));   //  18 registers, spilled under the 80-register cap)
+                                const u64 r = ((u64)qid << 32) | ((u64)(t0 + (unsigned)p) << 1) | (u64)hh;
                                 if (hit && pos < slice)
                                     my_rec[pos] = r;
                                 const unsigned total = cnt + (unsigned)__popcll(mask);
@@ -2606,6 +2637,56 @@ __global__ __launch_bounds__(256) void knn_cells_recentre_kernel(const float *__
     }
 }
 
+// With bin frames (option `cells_u8_frame`): every row as one byte per coordinate, the offset from its cell's w_c at the shard's
+// scale sigma 2^e (knn_u8_bin_code; the derivation is beside it in knn_filter_dev.h).  The fp16 fragments, norms and norm halves
+// are not touched: they stay in the shard's one frame for the prep kernel's seeds.  norms8 = N'' = |w_c + r^|^2, summed in
+// double (every term exact) and rounded once; cell_u8[0] / [1] = the shard's largest err / N''.  Padding rows and rows outside
+// the shard's robust box: code 128 and norm +INF, as in the fp16 layout.  Lane order: the fragments'.
+__global__ __launch_bounds__(256) void knn_cells_bin_rows_kernel(const float *__restrict__ R, int k, const unsigned *__restrict__ perm,
+                                                                 const float *__restrict__ norms, unsigned ntiles,
+                                                                 const unsigned *__restrict__ tile_cell, const float *__restrict__ center,
+                                                                 float scale, const h8 *__restrict__ binw, u2v *__restrict__ rows8,
+                                                                 float *__restrict__ norms8, float *__restrict__ cell_u8)
+{
+    const unsigned t = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int lane = threadIdx.x & 63, half = lane >> 5;
+    if (t >= ntiles)
+        return;
+    const size_t pos = (size_t)t * 32 + (lane & 31);
+    const unsigned row = perm[pos];
+    const bool real = row != 0xFFFFFFFFu && norms[pos] < INFINITY;
+    const h8 w = binw[(size_t)tile_cell[t] * 2 + half];
+    u2v code = {0x80808080u, 0x80808080u};
+    float err8 = 0.0f;
+    double part = 0.0;
+    if (real) {
+        code = (u2v){0u, 0u};
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int d = 8 * half + j;
+            float rh = 0.0f, e = 0.0f;
+            unsigned b = 128u;
+            if (d < k)
+                b = knn_u8_bin_code(R[(size_t)row * k + d], center[d], scale, (float)w[j], rh, e);
+            err8 = fmaxf(err8, e);
+            const double f = (double)w[j] + (double)rh;   // (0 beyond k: w and r^ are)
+            part = part + f * f;
+            code[j >> 2] |= b << (8 * (j & 3));
+        }
+    }
+    const double other = __shfl_xor(part, 32, KNN_WAVE);
+    const float nrm = (float)(part + other);   // (the same sum on both lanes of a row)
+    rows8[(size_t)t * 64 + lane] = code;
+    if (half == 0)
+        norms8[pos] = real ? nrm : INFINITY;
+    err8 = wave_max_f(err8);
+    const float nmax8 = wave_max_f(real ? nrm : 0.0f);
+    if (lane == 0) {
+        guarded_atomic_max((unsigned *)&cell_u8[0], __float_as_uint(err8));
+        guarded_atomic_max((unsigned *)&cell_u8[1], __float_as_uint(nmax8));
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // Host side.
 // ------------------------------------------------------------------------------------------
@@ -2625,6 +2706,7 @@ void knn_cells_free(CellIndex *&c)
     (void)KNN_DEV_FREE(c->rows8);
     (void)KNN_DEV_FREE(c->norms8);
     (void)KNN_DEV_FREE(c->cell_u8);
+    (void)KNN_DEV_FREE(c->binw);
     delete c;
     c = nullptr;
 }
@@ -2633,12 +2715,107 @@ std::atomic<int> g_knn_cells_centre{0};                 // option `cells_centre`
 std::atomic<long long> g_knn_cells_centred_builds{0};   // read-only option `cells_centred_builds`
 std::atomic<int> g_knn_cells_rows{0};                   // option `cells_rows`
 std::atomic<long long> g_knn_cells_u8_builds{0};        // read-only option `cells_u8_builds`
+std::atomic<int> g_knn_cells_u8_frame{0};               // option `cells_u8_frame`
+std::atomic<long long> g_knn_cells_u8_bin_builds{0};    // read-only option `cells_u8_bin_builds`
 
-// Moves a finished cell-sorted layout (k <= 16, no shard geometry) into per-cell frames — see the kernels.  Enqueues on `s`;
-// the caller's next synchronisation covers it.
+// The 8-bit rows in per-dimension bin frames (knn_filter_dev.h, knn_u8_bin_code), from the finished cells' boxes (`box`, host
+// copy `hb`).  Auto (forced = false) takes them where the bins fit the cells: for >= 95 % of the (non-empty cell, cut dimension)
+// pairs the bin's extent is at most twice the cell's own — uniform-like rows (a cell fills its orthant); clustered rows, whose
+// cells hold a sliver of their bins, keep per-cell frames.  -> *done: the layout has them.  Enqueues on `s` and synchronises.
+static hipError_t knn_cells_bin_frame(FilterState &st, const float *r, const std::vector<unsigned> &hb, hipStream_t s, bool forced, bool *done)
+{
+    *done = false;
+    CellIndex &c = *st.cells;
+    const int k = st.k;
+    float ctr[16] = {0};
+    FTRY(hipMemcpyAsync(ctr, st.center, (size_t)k * sizeof(float), hipMemcpyDeviceToHost, s));
+    FTRY(hipStreamSynchronize(s));
+    auto bin_of = [&](unsigned cell, int d) { return c.nb[d] ? (cell >> c.shift[d]) & ((1u << c.nb[d]) - 1u) : 0u; };
+    auto filled = [&](unsigned cell, int d) { return hb[(size_t)cell * 32 + d] <= hb[(size_t)cell * 32 + 16 + d]; };
+    double blo[16][CELL_MAX_BINS], bhi[16][CELL_MAX_BINS];
+    for (int d = 0; d < 16; ++d)
+        for (int b = 0; b < CELL_MAX_BINS; ++b) {
+            blo[d][b] = INFINITY;
+            bhi[d][b] = -INFINITY;
+        }
+    for (unsigned cell = 0; cell < c.ncells; ++cell)
+        for (int d = 0; d < k; ++d)
+            if (filled(cell, d)) {
+                const unsigned b = bin_of(cell, d);
+                blo[d][b] = std::min(blo[d][b], (double)ord2f_host(hb[(size_t)cell * 32 + d]));
+                bhi[d][b] = std::max(bhi[d][b], (double)ord2f_host(hb[(size_t)cell * 32 + 16 + d]));
+            }
+    if (!forced) {
+        size_t pairs = 0, fit = 0;
+        for (unsigned cell = 0; cell < c.ncells; ++cell)
+            for (int d = 0; d < k; ++d)
+                if (c.nb[d] && filled(cell, d)) {
+                    const unsigned b = bin_of(cell, d);
+                    const double cw = (double)ord2f_host(hb[(size_t)cell * 32 + 16 + d]) - (double)ord2f_host(hb[(size_t)cell * 32 + d]);
+                    ++pairs;
+                    fit += bhi[d][b] - blo[d][b] <= 2.0 * cw ? 1u : 0u;
+                }
+        if (pairs == 0 || (double)fit < 0.95 * (double)pairs)
+            return hipSuccess;
+    }
+    // the scale: the widest bin's half-extent, in sigma units, fills [-1, 1] up to the 2^-7 the offsets' rounding moves a centre
+    double hw = 0.0;
+    for (int d = 0; d < k; ++d)
+        for (int b = 0; b < CELL_MAX_BINS; ++b)
+            if (blo[d][b] <= bhi[d][b])
+                hw = std::max(hw, 0.5 * (bhi[d][b] - blo[d][b]) * (double)st.sigma);
+    int e = 0;
+    while (e < 4 && hw * std::ldexp(1.0, e + 1) + 0x1p-7 <= 1.0)
+        ++e;
+    const float ratio = std::ldexp(1.0f, e), scale = st.sigma * ratio;
+    float wt[16][CELL_MAX_BINS];
+    for (int d = 0; d < 16; ++d)
+        for (int b = 0; b < CELL_MAX_BINS; ++b) {
+            wt[d][b] = 0.0f;
+            if (d < k && blo[d][b] <= bhi[d][b]) {
+                const double o = 0.5 * (blo[d][b] + bhi[d][b]);
+                const double w = std::rint((o - (double)ctr[d]) * (double)scale * 64.0) / 64.0;
+                if (!(std::fabs(w) < 32.0))
+                    return hipSuccess;   // (not an fp16 number of <= 11 bits: keep per-cell frames)
+                wt[d][b] = (float)w;
+            }
+        }
+    std::vector<_Float16> hw16((size_t)c.ncells * 16);
+    double w1 = 0.0;
+    for (unsigned cell = 0; cell < c.ncells; ++cell) {
+        double sum = 0.0;
+        for (int d = 0; d < 16; ++d) {
+            const float w = d < k ? wt[d][bin_of(cell, d)] : 0.0f;
+            hw16[(size_t)cell * 16 + d] = (_Float16)w;   // exact
+            sum += std::fabs((double)w);
+        }
+        w1 = std::max(w1, sum);
+    }
+    FTRY(KNN_DEV_ALLOC(&c.binw, hw16.size() * sizeof(_Float16)));
+    FTRY(hipMemcpyAsync(c.binw, hw16.data(), hw16.size() * sizeof(_Float16), hipMemcpyHostToDevice, s));
+    FTRY(hipMemsetAsync(c.cell_u8, 0, 2 * sizeof(float), s));
+    const unsigned ntiles = (unsigned)st.ntiles;
+    hipLaunchKernelGGL(knn_cells_bin_rows_kernel, dim3((ntiles + 3u) / 4u), dim3(256), 0, s, r, k, c.perm, st.ref_norms, ntiles, c.tile_cell,
+                       st.center, scale, (const h8 *)c.binw, (u2v *)c.rows8, c.norms8, c.cell_u8);
+    FTRY(hipGetLastError());
+    float mx[2];
+    FTRY(hipMemcpyAsync(mx, c.cell_u8, sizeof mx, hipMemcpyDeviceToHost, s));
+    FTRY(hipStreamSynchronize(s));   // (hw16 and mx are on this stack)
+    c.bin_ratio = ratio;
+    c.bin_er = mx[0];
+    c.bin_nmax = mx[1];
+    c.bin_w1 = (float)(w1 * (1.0 + 1e-6));
+    c.bins = true;
+    *done = true;
+    return hipSuccess;
+}
+
+// Moves a finished cell-sorted layout (k <= 16, no shard geometry) into per-cell frames — see the kernels — or, for 8-bit rows
+// in bin frames, leaves it in the shard's frame and adds the rows (knn_cells_bin_frame).  Enqueues on `s`; the caller's next
+// synchronisation covers it.
 hipError_t knn_cells_recentre(FilterState &st, const float *r, hipStream_t s, bool rows_u8, bool frames_wanted)
 {
-    if (!st.cells || st.kt != 1 || st.cells->geom || st.cells->centred)
+    if (!st.cells || st.kt != 1 || st.cells->geom || st.cells->centred || st.cells->rows_u8)
         return hipSuccess;
     CellIndex &c = *st.cells;
     const unsigned ntiles = (unsigned)st.ntiles;
@@ -2662,7 +2839,6 @@ hipError_t knn_cells_recentre(FilterState &st, const float *r, hipStream_t s, bo
                 return hipSuccess;
         }
     }
-    FTRY(KNN_DEV_ALLOC((void **)&c.cell_frame, (size_t)c.ncells * KNN_CELL_FRAME_WORDS * sizeof(float)));
     FTRY(KNN_DEV_ALLOC((void **)&c.tile_cell, (size_t)std::max(1u, ntiles) * sizeof(unsigned)));
     FTRY(KNN_DEV_ALLOC((void **)&box, (size_t)c.ncells * 32 * sizeof(unsigned)));
     hipError_t e = hipMemsetAsync(box, 0xFF, (size_t)c.ncells * 32 * sizeof(unsigned), s);   // min = ~0; max: cleared below
@@ -2672,6 +2848,30 @@ hipError_t knn_cells_recentre(FilterState &st, const float *r, hipStream_t s, bo
         hipLaunchKernelGGL(knn_cells_tile_cell_kernel, dim3((c.ncells * 32u + 255u) / 256u), dim3(256), 0, s, c.tile_start, c.ncells, c.tile_cell);
         hipLaunchKernelGGL(knn_cells_box_kernel, dim3(((ntiles + CELL_BOX_RUN - 1u) / CELL_BOX_RUN + 3u) / 4u), dim3(256), 0, s, r, st.k, c.perm, st.ref_norms,
                            ntiles, c.tile_cell, box);
+        e = hipGetLastError();
+    }
+    // Which frame the 8-bit rows get (option `cells_u8_frame`: 0 auto, 1 per-cell, 2 per-bin): per-bin where asked for, or — auto,
+    // unless per-cell frames are wanted on their own (clustered data) — where the bins fit the cells (knn_cells_bin_frame)
+    const int fopt = g_knn_cells_u8_frame;
+    if (e == hipSuccess && c.rows8 && ntiles != 0u && (fopt == 2 || (fopt == 0 && !frames_wanted))) {
+        std::vector<unsigned> hb((size_t)c.ncells * 32);
+        e = hipMemcpyAsync(hb.data(), box, hb.size() * sizeof(unsigned), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess)
+            e = hipStreamSynchronize(s);
+        bool done = false;
+        if (e == hipSuccess)
+            e = knn_cells_bin_frame(st, r, hb, s, fopt == 2, &done);
+        if (e == hipSuccess && done) {
+            (void)KNN_DEV_FREE(box);
+            c.rows_u8 = true;
+            ++g_knn_cells_u8_builds;
+            ++g_knn_cells_u8_bin_builds;
+            return hipSuccess;
+        }
+    }
+    if (e == hipSuccess)
+        e = KNN_DEV_ALLOC((void **)&c.cell_frame, (size_t)c.ncells * KNN_CELL_FRAME_WORDS * sizeof(float));
+    if (e == hipSuccess && ntiles != 0u) {
         hipLaunchKernelGGL(knn_cells_frame_kernel, dim3((c.ncells + 255u) / 256u), dim3(256), 0, s, box, c.ncells, st.k, st.sigma, c.cell_frame);
         hipLaunchKernelGGL(knn_cells_recentre_kernel, dim3((ntiles + 3u) / 4u), dim3(256), 0, s, r, st.k, c.perm, ntiles, c.tile_cell,
                            c.cell_frame, (h8 *)st.ref_frags, st.ref_norms, st.ref_norms2, (u2v *)c.rows8, c.norms8, c.cell_u8);
@@ -3222,7 +3422,7 @@ hipError_t knn_cells_query(FilterState &st, FilterWorkspace &w, int m, const flo
     // Who makes the cells' lists of queries: knn_cells_match_kernel in a launch of its own (rounds 2-4), or the scan's waves
     // for the items they take (round 5, cell_self_list).  Policy in knn_cells_lists_policy.
     const bool centred = c.centred;   // per-cell frames (knn_cells_recentre): the centred prep and scan, lists from the match launch
-    const bool self_lists = st.kt == 1 && !centred && (st.cells_lists == 2 || (st.cells_lists == 0 && knn_cells_lists_policy(c.ncells, st.several_slots)));
+    const bool self_lists = st.kt == 1 && !centred && !c.rows_u8 && (st.cells_lists == 2 || (st.cells_lists == 0 && knn_cells_lists_policy(c.ncells, st.several_slots)));
     const CellScanPlan plan = knn_cells_scan_plan(num_cu, one_block ? 1 : 2, c.nitems, w.rec_cap, m_padded, self_lists, st.kt, centred);
     const unsigned gx = plan.blocks;
     w.nlists = plan.nlists;
@@ -3308,6 +3508,13 @@ hipError_t knn_cells_query(FilterState &st, FilterWorkspace &w, int m, const flo
         self.dup = w.dup;
         self.frame = c.cell_frame;
         self.cell_u8 = c.rows_u8 ? c.cell_u8 : nullptr;
+    } else if (c.rows_u8) {   // 8-bit rows in bin frames
+        self.dup = w.dup;
+        self.binw = c.binw;
+        self.bin_ratio = c.bin_ratio;
+        self.bin_er = c.bin_er;
+        self.bin_nmax = c.bin_nmax;
+        self.bin_w1 = c.bin_w1;
     }
     const unsigned list_cap = self_lists ? CELL_SELF_CAP : c.cap;
     static const bool trace_cells = getenv("KNN_MI355X_TRACE_CELLS") != nullptr;   // (read once: a query may run beside a thread that changes the environment)
@@ -3375,6 +3582,11 @@ hipError_t knn_cells_query(FilterState &st, FilterWorkspace &w, int m, const flo
                            w.cell_counts, w.cell_lists, list_cap, w.records, w.counts, w.ctl_cur, w.slice, w.ovf_base,    \
                            w.ovf_cap, q, r, st.k, c.perm, npos, base, keys, fin, self);                                    \
     } while (0)
+#define KNN_SCAN_LAUNCH_U8B(DYNV, KV)   /* 8-bit rows in bin frames: the one-frame scan's LDS */                            \
+    hipLaunchKernelGGL((knn_cells_scan_kernel<DYNV, KV, false, 1, false, false, true>), dim3(gx), dim3(64 * plan.waves), lds, s, \
+                       (const h8 *)c.rows8, c.norms8, c.items, c.nitems, (const h8 *)w.qry_frags, w.thr, m, m_padded,      \
+                       w.cell_counts, w.cell_lists, list_cap, w.records, w.counts, w.ctl_cur, w.slice, w.ovf_base,        \
+                       w.ovf_cap, q, r, st.k, c.perm, npos, base, keys, fin, self)
 #define KNN_SCAN_LAUNCH_K5(DYNV)   /* per-cell frames: 92 KiB of dynamic LDS for 1024 queries (their fp32 rows) */                  \
     do {                                                                                                                   \
         if (st.k == 16) {                                                                                                  \
@@ -3395,6 +3607,12 @@ hipError_t knn_cells_query(FilterState &st, FilterWorkspace &w, int m, const flo
             KNN_SCAN_LAUNCH_U8(true, 16);
         else
             KNN_SCAN_LAUNCH_U8(true, 0);
+    } else if (c.rows_u8) {   // 8-bit rows in bin frames: the one-frame scan's two blocks of 12 waves per CU, items from the
+                              // block's counter (the fixed deal's form holds 8 bytes of scratch under the 80-register cap)
+        if (st.k == 16)
+            KNN_SCAN_LAUNCH_U8B(true, 16);
+        else
+            KNN_SCAN_LAUNCH_U8B(true, 0);
     } else if (centred) {   // per-cell frames: lists from the match launch
         if (dyn)
             KNN_SCAN_LAUNCH_K5(true);
@@ -3433,6 +3651,7 @@ hipError_t knn_cells_query(FilterState &st, FilterWorkspace &w, int m, const flo
         else
             KNN_SCAN_LAUNCH_K(false, false);
     }
+#undef KNN_SCAN_LAUNCH_U8B
 #undef KNN_SCAN_LAUNCH_K5
 #undef KNN_SCAN_LAUNCH_K
 #undef KNN_SCAN_LAUNCH
@@ -3484,5 +3703,38 @@ extern "C" int knn_debug_u8_row(int k, const float *row, const float *centre, fl
     }
     out[0] = er;
     out[1] = knn_bound_consts_u8(k, 1, scale, amax, er, nmax).eta;
+    return 0;
+}
+
+// Test hooks (host arithmetic, no GPU) for the 8-bit rows in bin frames.  knn_debug_u8_bin_row: one row through knn_u8_bin_code
+// (what knn_cells_bin_rows_kernel does per coordinate) with the centre of the shard's frame, the scale sigma 2^e and the cell's
+// offsets w -> its codes and the largest err.  knn_debug_u8_bin_threshold: knn_u8_bin_threshold of one query given its fp16 B
+// operand in the bins' units (16 values, as bits).
+extern "C" int knn_debug_u8_bin_row(int k, const float *row, const float *centre, float scale, const float *w, unsigned char *codes,
+                                    double *err)
+{
+    if (k < 1 || k > 16 || !row || !centre || !w || !codes || !err)
+        return -1;   // KNN_EINVAL
+    float er = 0.0f;
+    for (int d = 0; d < k; ++d) {
+        float rh, e;
+        codes[d] = (unsigned char)knn_u8_bin_code(row[d], centre[d], scale, w[d], rh, e);
+        er = std::max(er, e);
+    }
+    *err = er;
+    return 0;
+}
+
+extern "C" int knn_debug_u8_bin_threshold(int k, const unsigned short *b_bits, float dup, float ratio, float er, float nmax, float w1,
+                                          float *thr)
+{
+    if (k < 1 || k > 16 || !b_bits || !thr)
+        return -1;   // KNN_EINVAL
+    h8 b0, b1;
+    for (int j = 0; j < 8; ++j) {
+        b0[j] = __builtin_bit_cast(_Float16, b_bits[j]);
+        b1[j] = __builtin_bit_cast(_Float16, b_bits[8 + j]);
+    }
+    *thr = knn_u8_bin_threshold(k, b0, b1, dup, ratio, er, nmax, w1);
     return 0;
 }

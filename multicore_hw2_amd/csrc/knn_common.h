@@ -235,7 +235,13 @@ struct CellIndex {
     bool rows_u8 = false;
     unsigned char *rows8 = nullptr;       // device [ntiles][64][8]
     float *norms8 = nullptr;              // device [ntiles * 32]
-    float *cell_u8 = nullptr;             // device [ncells][2]
+    float *cell_u8 = nullptr;             // device [ncells][2] (bin frames: [2], the shard's largest err and N'')
+    // 8-bit rows in per-dimension bin frames (option `cells_u8_frame`, knn_filter_dev.h knn_u8_bin_code): the layout stays in the
+    // shard's one frame (centred = false: the fp16 fragments are the prep kernel's, untouched); rows8 hold the rows' offsets
+    // from their cell's w_c at scale sigma 2^e, norms8 = N'' = |w_c + r^|^2; binw fp16 [ncells][16] = w_c (0 beyond k)
+    bool bins = false;
+    void *binw = nullptr;                 // device [ncells][16] fp16
+    float bin_ratio = 1.0f, bin_er = 0.0f, bin_nmax = 0.0f, bin_w1 = 0.0f;
 };
 #define KNN_CELL_FRAME_WORDS 20
 #define KNN_NIF_MAX_K 30   // 16 < k <= 30: the cell-sorted fragments carry the rows' norms in K-slots 30, 31 (knn_cells.hip: cell_tile_step_nif)
@@ -314,6 +320,8 @@ extern std::atomic<int> g_knn_cells_centre;
 extern std::atomic<long long> g_knn_cells_centred_builds;
 extern std::atomic<int> g_knn_cells_rows;
 extern std::atomic<long long> g_knn_cells_u8_builds;
+extern std::atomic<int> g_knn_cells_u8_frame;
+extern std::atomic<long long> g_knn_cells_u8_bin_builds;
 void knn_cells_workspace_free(FilterWorkspace &w);
 // One batch of <= KNN_CELL_BATCH queries already prepared by the filter's query-fragment kernel: seed, thresholds,
 // match, scan (records in w, as the full scan leaves them).  Asynchronous.

@@ -218,6 +218,8 @@ struct CellSelf {
     int sa, m_padded;
     const float *frame;  // per-cell frames (the centred scan): device [cells][KNN_CELL_FRAME_WORDS]; null otherwise
     const float *cell_u8;   // 8-bit rows (the centred scan's U8 form): device [cells][2]; null otherwise
+    const void *binw;       // 8-bit rows in bin frames (the one-frame scan's U8 form): device fp16 [cells][16]; null otherwise
+    float bin_ratio, bin_er, bin_nmax, bin_w1;
 };
 
 // -> the list's length; entries beyond CELL_SELF_CAP are counted, not stored.  `dupv`: the batch's Dup values (LDS in the

@@ -142,6 +142,70 @@ __host__ __device__ inline BoundConsts knn_bound_consts_u8(int k, int kt, double
     return c;
 }
 
+// 8-bit rows in per-dimension BIN frames (option `cells_u8_frame`, knn_cells_bin_rows_kernel).  One shard-wide scale s = sigma 2^e
+// (power of two, the shard's fp16 frame times 2^e, e <= 4), and per (dimension d, bin b) an offset w[d][b], a multiple of 2^-6
+// below 32 in s units — exact in fp16.  A row x of cell c (bin b_d of every dimension) is stored as the code of
+//     u = fl(x_d - centre_d) s,   v = fl(u - w_c,d),   r^ = knn_u8_code(v)      (w_c,d = w[d][b_d])
+// so the row in the shard's frame at scale s is w_c + r, r its exact offset; r^ within err of r per coordinate, err = knn_u8_code's
+// (|v - r^| + 2^-22 |v| + 2^-100: covers the rounding of v) + 2^-22 |u| (the fp32 centring of u, <= 2^-24 |u| (1 + 2^-24)).
+// The scan scores  S = N'' + B.r^  with  N'' = |w_c + r^|^2 (double sum, rounded once to fp32: 2^-24 N'') and B = -2 p~, the
+// prep kernel's fp16 B operand times 2^e (exact): p~ is the query in the shard's frame, rounded.  Then
+//     S + B.w_c = |w_c + r^|^2 - 2 p~.(w_c + r^) = |p~ - (w_c + r^)|^2 - |p~|^2
+// is the ONE-FRAME score of the row w_c + r^ against p~: knn_threshold's derivation holds word for word with
+//     emax = thp amax + er + 2 nu0 2^e      (amax = max |p~_d| in s units — the query's rounding is relative to |p~|, made in
+//                                           sigma units where nu0 is absolute; er = the shard's largest err, 10^-6 larger)
+//     eta = sqrt(k) emax,  Dup (s units) = Dup_q (sigma units) 4^e,  mq = the computed |p~|^2 (exact products, fp32 sum)
+//     rho: the matrix core's accumulation of S relative to |N''| + sum |B_d r^_d| <= nmax + 2 k amax (|r^_d| <= 1), and
+//          nmax + 2k + 16 amax^2 >= that for k <= 16 — knn_bound_consts' (omega + 2 gamma) 2 (...) with nmax + 2k for nmax —,
+//          plus 2^-21 nmax for N''s rounding and kp 2^-27 + 2^-24 as there.
+// knn_u8_bin_threshold is that line, thr = Dup + 2 eta sqrt(Dup) + eta^2 + rho - mq (1 - gamma), in fp32 rounded towards "pass"
+// exactly as cell_centred_operand evaluates it (P within 2^-20 of exact, taken 10^-5 larger; the square root of max(Dup, 2^-100)
+// taken 10^-6 larger: a few ulp).
+// The pair term B.w_c is per (query, cell): the scan computes it in fp32 (products of two fp16 numbers of <= 11 significant
+// bits: exact; eight additions of magnitude <= A = sum |B_d w_c,d| <= 2 amax W1, W1 = the shard's largest sum |w_c,d|:
+// <= 2^-21 A; an fp16 subnormal B flushed: <= 2^-14 W1) and passes S < thr - B.w_c.  That subtraction rounds by
+// 2^-24 (|thr| + A); all of it is covered by adding  2^-18 (|thr| + 2 amax W1) + 2^-14 W1  to thr here, once per query.
+__host__ __device__ inline unsigned knn_u8_bin_code(float x, float centre, float scale, float w, float &rh, float &err)
+{
+#pragma clang fp contract(off)
+    const float u = (x - centre) * scale;   // fp32 subtract, exact power-of-two scale
+    const float v = u - w;
+    float e;
+    const unsigned b = knn_u8_code(v, rh, e);
+    err = e + 0x1p-22f * fabsf(u);
+    return b;
+}
+
+// b0, b1: the query's B operand in s units (dimensions 0-7, 8-15); dup: Dup_q in sigma units (-INF: a query the batch cannot
+// bound — nothing passes); ratio = 2^e; er, nmax, w1: the shard's largest err, N'' and sum |w_c,d|.
+__host__ __device__ inline float knn_u8_bin_threshold(int k, const h8 &b0, const h8 &b1, float dup, float ratio, float er, float nmax, float w1)
+{
+#pragma clang fp contract(off)
+    float a = 0.0f, mq = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const float h = (float)(j < 8 ? b0[j & 7] : b1[j & 7]) * -0.5f;   // p~_d, exact
+        a = fmaxf(a, fabsf(h));
+        mq = mq + h * h;
+    }
+    if (!(dup > -INFINITY))
+        return -INFINITY;
+    const float kf = (float)k;
+    const float emax = 4.8865e-4f * a + er * 1.000001f + 1.2220e-4f * ratio;   // theta' amax + er + 2 nu0 2^e
+    const float sqk = k <= 1 ? 1.0f : k <= 4 ? 2.0f : k <= 9 ? 3.0f : 4.0f;   // >= sqrt(k), k <= 16
+    const float eta = sqk * emax, eta2 = kf * emax * emax;
+    const float rho = 1.1921e-5f * (nmax + 2.0f * kf + 16.0f * a * a) + 1.79e-7f + 4.77e-7f * nmax;
+    const float dupc = dup * ratio * ratio;
+#ifdef __HIP_DEVICE_COMPILE__
+    const float sqdc = __builtin_amdgcn_sqrtf(fmaxf(dupc, 0x1p-100f)) * 1.000001f;   // (v_sqrt_f32: 1 ulp, no FMA; a normal argument)
+#else
+    const float sqdc = sqrtf(fmaxf(dupc, 0x1p-100f)) * 1.000001f;
+#endif
+    const float P = dupc + 2.0f * eta * sqdc + eta2 + rho;
+    const float th = (P * 1.00001f + (P + mq) * 2.4e-7f + 1e-30f) - mq * 0.999996f;
+    return th + (0x1p-18f * (fabsf(th) + 2.0f * a * w1) + 0x1p-14f * w1);
+}
+
 // Threshold implied by a filter score `u` = S of SOME real reference j0 of the shard (the minimum
 // over the sample pass), for a query whose fp16 row has computed squared norm mq:
 //   D~_j0 <= u + mq(1+g) + rho;  (sqrt(D_j0) - eta)^2 <= D~_j0 + 2 eta^2  =>  D_j0 <= D0up
