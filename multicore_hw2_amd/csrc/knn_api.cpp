@@ -618,7 +618,7 @@ int index_create_impl(knn_index **out, int device, int k, long long n_local, con
             want_layouts = false;
     }
     if (want_layouts && !layouts_done) {
-        hipError_t e = knn_filter_build(idx->filter, k, n_local, idx->refs, s, want_cells ? (g_opt_cells_build == 1 ? 2 : g_opt_cells_build == 2 ? 3 : 1) : 0);
+        hipError_t e = knn_filter_build(idx->filter, k, n_local, idx->refs, s, want_cells, (int)g_opt_cells_build);
         if (e == hipErrorOutOfMemory) {
             // no room for the fp16 layouts beside the rows: the index still works, exact kernels only
             (void)hipGetLastError();
@@ -743,8 +743,8 @@ int knn_index_create_sharded(knn_index **out, int device, const knn_geom *g, int
         idx->num_cu = prop.multiProcessorCount;
     if (n_local > 0) {
         unsigned bad_rows = 0u;
-        const hipError_t e = knn_filter_build(idx->filter, idx->k, n_local, refs_dev, s, g_opt_cells_build == 1 ? 2 : g_opt_cells_build == 2 ? 3 : 1, &idx->geom,
-                                              rank, &bad_rows);
+        const hipError_t e = knn_filter_build(idx->filter, idx->k, n_local, refs_dev, s, true, (int)g_opt_cells_build, &idx->geom, rank,
+                                              &bad_rows);
         if (e != hipSuccess || !idx->filter.usable || !idx->filter.cells) {
             char why[160];
             if (bad_rows != 0u)

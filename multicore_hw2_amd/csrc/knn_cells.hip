@@ -2698,9 +2698,7 @@ void knn_cells_free(CellIndex *&c)
     (void)KNN_DEV_FREE(c->tile_start);
     (void)KNN_DEV_FREE(c->perm);
     (void)KNN_DEV_FREE(c->items);
-    (void)KNN_DEV_FREE(c->tmp_rows);
-    (void)KNN_DEV_FREE(c->tmp_meta);
-    (void)KNN_DEV_FREE(c->bucket_start);
+    knn_cells_release_build_scratch(*c);
     (void)KNN_DEV_FREE(c->cell_frame);
     (void)KNN_DEV_FREE(c->tile_cell);
     (void)KNN_DEV_FREE(c->rows8);
@@ -2964,6 +2962,107 @@ bool knn_cells_sample_is_clustered(const float *samp, long long samples, int k, 
     return nn[(size_t)(probes / 2)] * sigma < 1.0f / 16.0f;
 }
 
+// ---- the build --------------------------------------------------------------------------------
+// A cell-sorted layout is built in four steps: the grid (knn_cells_plan: host arithmetic), the strategy
+// (knn_cells_first_build, then knn_cells_next_build), the staging of the rows into cells (knn_cells_stage: codes, counts or
+// buckets, tile ranges, items) and the finish (knn_filter.hip: layouts, placement, ONE synchronisation, accept or reject).
+
+// The grid of the shard's cell-sorted layout (see the head of this file): shape, cuts (h_bounds), list capacity and lbits.
+// geom != null: the cell-range shard `rank` of that global grid (no cuts of its own).  samp: the strided host sample of the
+// build (samples x k).  False when the shard is too small, the dimension does not suit, or the grid would be too coarse.
+bool knn_cells_plan(CellIndex &c, int k, long long n, const float *samp, long long samples, const ShardGeom *geom, int rank)
+{
+    c = CellIndex();
+    // (16 < k <= 32, round 5: the cells cut the first 16 dimensions — a lower bound over some dimensions is one over all —
+    // and the layout has two K-steps per tile; one-pass placement, no shard geometry)
+    if (k > 32 || (k > 16 && geom) || n > 0x7FFFFFFFll || (!geom && (n < (1ll << 17) || samples < 64)))
+        return false;
+    static_assert(sizeof c.h_bounds == 16 * (CELL_MAX_BINS - 1) * sizeof(float) && sizeof c.h_bounds == sizeof geom->bounds, "cuts");
+    if (geom) {
+        // cell-range shard: the global grid's shape and cuts, this rank's range of its codes
+        c.bits = geom->bits;
+        c.sa = geom->sa;
+        memcpy(c.nb, geom->nb, 16);
+        memcpy(c.shift, geom->shift, 16);
+        c.cell_base = geom->first_cell(rank);
+        c.ncells = geom->cells_of(rank);
+        c.geom = geom;
+        memcpy(c.h_bounds, geom->bounds, sizeof c.h_bounds);
+        if (c.ncells < 512u || c.ncells % 64u != 0u || c.ncells > 65536u)   // (knn_geom_from_sample sizes the ranges so)
+            return false;
+    } else {
+        const int kc = std::min(k, 16);   // dimensions the cells may cut
+        const int bits = std::min(cell_bits_for_rows(n), std::min(16, 4 * kc));
+        if (bits < 9)
+            return false;
+        c.bits = bits;
+        c.ncells = 1u << bits;
+        cell_grid_shape(kc, bits, c.nb, c.shift, &c.sa);
+        if (c.sa < 6)   // a wave of the match pass covers 64 consecutive low-table entries
+            return false;
+        cell_quantile_cuts(k, c.nb, samp, samples, c.h_bounds);
+    }
+    // list capacity per cell and batch: 384 queries per cell at >= 2^15 cells (48 MiB of lists per slot at 2^16 cells; uniform
+    // data in 16 dimensions keeps 25 of 1024 on average, 53 at most), every query of a batch at <= 2^13 cells
+    // (round 5: 384 entries at >= 2^15 cells, was 128 — heavy-tailed rows with gaussian queries, n 2^24: lists of 121 .. 213
+    // queries, nearly every cell `dense` (scored against all 1024), 1.16 ms per step; 0.36 with room for the lists.  The match
+    // kernel assembles the first 128 entries of a list in LDS as before and writes the rest straight to memory)
+    c.cap = std::min(1024u, std::max(384u, (1u << 23) / c.ncells));
+    if (k > 16)   // (more dimensions, fewer cells ruled out: lists of ~100-200 of 1024 queries at k = 20 — 128 entries made most cells dense)
+        c.cap = std::min(1024u, std::max(k > 20 ? 640u : 384u, (1u << 24) / c.ncells));
+    // (k = 24, n 2^24: lists of 384 left most cells dense, 1.19 ms per step; 640 or 1024 entries 0.75 — the full scan takes 0.97)
+    while ((1u << c.lbits) < c.ncells)   // bits of a LOCAL cell number (= bits without a shard geometry)
+        ++c.lbits;
+    return true;
+}
+
+// The first strategy to try.  The fast build (round 5) is taken for whole indexes (no shard geometry: their rows' codes are
+// local = global and fit 16 bits) of >= 512 cells whose scratch (n x 96 bytes) fits; the counted two-pass build needs n x 64
+// bytes of scratch (shards of up to 2^25 rows: beyond, the scratch is gigabytes that the buffer pool does not keep between
+// builds, and one hipMalloc / hipFree pair of that size in eight took 2.2 SECONDS on a 2^27-row shard — tools/build_repeat.py:
+// 30 20 19 19 19 19 2208 21 ms — where the one-pass placement's 33 ms are steady); the one-pass placement serves k > 16 and
+// everything else.  cells_build: option `cells_build` (0 auto, 1 one-pass, 2 counted: A/B timing and tests).  An ingest
+// (CellRows::Host) has no rows on the device to count: the fast build under the copy, or nothing.
+CellBuild knn_cells_first_build(const CellIndex &plan, int k, long long n, int cells_build, CellRows rows)
+{
+    const bool fast_fits = !plan.geom && (size_t)n * 96 <= ((size_t)2 << 30) && plan.ncells >= 512u;
+    if (rows == CellRows::Host)
+        return k <= 16 && fast_fits ? CellBuild::Fast : CellBuild::None;
+    if (k > 16 || cells_build == 1 || (size_t)n * 64 > ((size_t)2 << 30))
+        return CellBuild::OnePass;
+    return cells_build == 0 && rows == CellRows::Sample && fast_fits ? CellBuild::Fast : CellBuild::Counted;
+}
+
+// What follows a strategy that could not finish: Fast -> Counted (a bucket outgrew its fixed room — data the quantile cuts do
+// not spread evenly over the 256 buckets — or no room for its scratch), Counted -> OnePass (no room for its scratch).  An
+// ingest gives up instead: its rows are not on the device yet, the caller copies them, then builds.
+CellBuild knn_cells_next_build(CellBuild how, CellRows rows)
+{
+    if (how == CellBuild::Fast && rows != CellRows::Host)
+        return CellBuild::Counted;
+    return how == CellBuild::Counted ? CellBuild::OnePass : CellBuild::None;
+}
+
+// The build's scratch (buckets, codes, fill counters): the layout keeps the rest.  The only place that frees it.
+void knn_cells_release_build_scratch(CellIndex &c)
+{
+    (void)KNN_DEV_FREE(c.tmp_rows);
+    (void)KNN_DEV_FREE(c.tmp_meta);
+    (void)KNN_DEV_FREE(c.bucket_start);
+    c.tmp_rows = nullptr;
+    c.tmp_meta = nullptr;
+    c.bucket_start = c.bucket_fill = c.build_res = nullptr;
+}
+
+void CellStaging::release()
+{
+    (void)KNN_DEV_FREE(code);
+    (void)KNN_DEV_FREE(fill);
+    code = fill = nullptr;
+    if (c)
+        knn_cells_release_build_scratch(*c);
+}
+
 // The fast build in stages (an ingest runs the scatter chunk by chunk under the copy): rows [row0, row1) of the shard, at `r`
 // = the shard's first row on the device.
 hipError_t knn_cells_fast_scatter(CellIndex &c, int k, const float *r, long long row0, long long row1, hipStream_t s)
@@ -2989,153 +3088,84 @@ hipError_t knn_cells_fast_finish(CellIndex &c, unsigned *counts, hipStream_t s)
     return hipMemsetAsync(counts, 0, (size_t)c.ncells * sizeof(unsigned), s);   // the counts become the placement's fill counters
 }
 
-// Sorts the shard into cells (see the head of this file).  *out stays null when the shard is too small, the
-// dimension does not suit, or the cuts leave the cells badly unbalanced.  samp: the strided host sample
-// of the build (samples x k).  Synchronous.
-hipError_t knn_cells_build(CellIndex **out, int k, long long n, const float *r, const std::vector<float> &samp,
-                           long long samples, hipStream_t s, long long *ntiles_out, unsigned **code_out,
-                           unsigned **fill_out, bool one_pass, const ShardGeom *geom, int rank, unsigned *bad_rows_out, bool fast,
-                           bool defer_scatter)
+// The fast build (round 5): no counting pass over the rows, no host round trip (see the kernels).  Everything it launches is
+// asynchronous — the finish reads c->build_res behind the placement and, if a bucket outgrew its fixed room, the build starts
+// over with the counted one.  scatter = false (an ingest): everything allocated and uploaded, nothing scattered yet.
+// False: no room (or a launch failed).
+static bool cells_stage_fast(CellStaging &stg, const CellIndex &plan, int k, long long n, const float *r, hipStream_t s, bool scatter)
 {
-    *out = nullptr;
-    *code_out = nullptr;
-    *fill_out = nullptr;
-    if (bad_rows_out)
-        *bad_rows_out = 0u;
-    // (16 < k <= 32, round 5: the cells cut the first 16 dimensions — a lower bound over some dimensions is one over all —
-    // and the layout has two K-steps per tile; one-pass placement, no shard geometry)
-    if (k > 32 || (k > 16 && geom) || n > 0x7FFFFFFFll || (!geom && (n < (1ll << 17) || samples < 64)))
-        return hipSuccess;
-    const int kc = std::min(k, 16);   // dimensions the cells may cut
-    if (k > 16) {
-        one_pass = true;
-        fast = false;
-    }
-    CellIndex *c = new CellIndex();
-    std::vector<float> bounds((size_t)16 * (CELL_MAX_BINS - 1), INFINITY);
-    if (geom) {
-        // cell-range shard: the global grid's shape and cuts, this rank's range of its codes
-        c->bits = geom->bits;
-        c->sa = geom->sa;
-        memcpy(c->nb, geom->nb, 16);
-        memcpy(c->shift, geom->shift, 16);
-        c->cell_base = geom->first_cell(rank);
-        c->ncells = geom->cells_of(rank);
-        c->geom = geom;
-        memcpy(bounds.data(), geom->bounds, sizeof geom->bounds);
-        if (c->ncells < 512u || c->ncells % 64u != 0u || c->ncells > 65536u) {   // (knn_geom_from_sample sizes the ranges so)
-            delete c;
-            return hipSuccess;
-        }
-    } else {
-        const int bits = std::min(cell_bits_for_rows(n), std::min(16, 4 * kc));
-        if (bits < 9) {
-            delete c;
-            return hipSuccess;
-        }
-        c->bits = bits;
-        c->ncells = 1u << bits;
-        cell_grid_shape(kc, bits, c->nb, c->shift, &c->sa);
-        if (c->sa < 6) {   // a wave of the match pass covers 64 consecutive low-table entries
-            delete c;
-            return hipSuccess;
-        }
-        cell_quantile_cuts(k, c->nb, samp.data(), samples, bounds.data());
-    }
-    // list capacity per cell and batch: 384 queries per cell at >= 2^15 cells (48 MiB of lists per slot at 2^16 cells; uniform
-    // data in 16 dimensions keeps 25 of 1024 on average, 53 at most), every query of a batch at <= 2^13 cells
-    // (round 5: 384 entries at >= 2^15 cells, was 128 — heavy-tailed rows with gaussian queries, n 2^24: lists of 121 .. 213
-    // queries, nearly every cell `dense` (scored against all 1024), 1.16 ms per step; 0.36 with room for the lists.  The match
-    // kernel assembles the first 128 entries of a list in LDS as before and writes the rest straight to memory)
-    c->cap = std::min(1024u, std::max(384u, (1u << 23) / c->ncells));
-    if (k > 16)   // (more dimensions, fewer cells ruled out: lists of ~100-200 of 1024 queries at k = 20 — 128 entries made most cells dense)
-        c->cap = std::min(1024u, std::max(k > 20 ? 640u : 384u, (1u << 24) / c->ncells));
-    // (k = 24, n 2^24: lists of 384 left most cells dense, 1.19 ms per step; 640 or 1024 entries 0.75 — the full scan takes 0.97)
-    const CellGeom g = cell_geom_of(*c, k);
-    int lbits = 0;   // bits of a LOCAL cell number (= bits without a shard geometry)
-    while ((1u << lbits) < c->ncells)
-        ++lbits;
-
-    // ---- the fast build (round 5): no counting pass over the rows, no host round trip (see the kernels).  Taken for whole
-    // indexes (no shard geometry: their rows' codes are local = global and fit 16 bits) whose scratch fits; everything it
-    // launches is asynchronous — the caller reads c->build_res behind the placement and, if a bucket outgrew its fixed room
-    // (data the quantile cuts do not spread evenly over the 256 buckets), builds again with fast = false.
-    if (defer_scatter && !(fast && !geom && !one_pass && (size_t)n * 96 <= ((size_t)2 << 30) && c->ncells >= 512u)) {
-        delete c;
-        return hipSuccess;
-    }
-    if (fast && !geom && !one_pass && (size_t)n * 96 <= ((size_t)2 << 30) && c->ncells >= 512u) {
-        // room per bucket: an even spread + 1/2.  The cuts are medians of a 1024-row sample: each is off by ~1.6 % of the rows
-        // (1 sigma), a bucket is the product of 8 such halves — 1 sigma 9 %, the fullest of 256 buckets ~27 % over the mean on
-        // uniform data (measured: + 1/8 overflowed at C3)
-        const unsigned cap_rows = (unsigned)((n / CELL_BUCKETS) + (n / CELL_BUCKETS) / 2 + CELL_BUILD_ROWS);
-        const size_t recs = (size_t)cap_rows * CELL_BUCKETS;
-        const long long tiles_ub = n / 32 + (long long)c->ncells;                         // every cell wastes less than a tile
-        const size_t items_ub = (size_t)c->ncells + (size_t)(tiles_ub / KNN_CELL_ITEM_TILES) + 1u;
-        unsigned *counts_f = nullptr;
-        hipError_t a = KNN_DEV_ALLOC((void **)&c->bounds, (bounds.size() + 1) * sizeof(float));
+    CellIndex *c = new CellIndex(plan);
+    // room per bucket: an even spread + 1/2.  The cuts are medians of a 1024-row sample: each is off by ~1.6 % of the rows
+    // (1 sigma), a bucket is the product of 8 such halves — 1 sigma 9 %, the fullest of 256 buckets ~27 % over the mean on
+    // uniform data (measured: + 1/8 overflowed at C3)
+    const unsigned cap_rows = (unsigned)((n / CELL_BUCKETS) + (n / CELL_BUCKETS) / 2 + CELL_BUILD_ROWS);
+    const size_t recs = (size_t)cap_rows * CELL_BUCKETS;
+    const long long tiles_ub = n / 32 + (long long)c->ncells;                         // every cell wastes less than a tile
+    const size_t items_ub = (size_t)c->ncells + (size_t)(tiles_ub / KNN_CELL_ITEM_TILES) + 1u;
+    unsigned *counts = nullptr;
+    hipError_t a = KNN_DEV_ALLOC((void **)&c->bounds, sizeof c->h_bounds + sizeof(float));
+    if (a == hipSuccess)
+        a = KNN_DEV_ALLOC((void **)&c->tile_start, ((size_t)c->ncells + 1) * sizeof(unsigned));
+    if (a == hipSuccess)
+        a = KNN_DEV_ALLOC((void **)&counts, (size_t)c->ncells * sizeof(unsigned));
+    if (a == hipSuccess)
+        a = KNN_DEV_ALLOC((void **)&c->tmp_rows, recs * 16 * sizeof(float));
+    if (a == hipSuccess)
+        a = KNN_DEV_ALLOC((void **)&c->tmp_meta, recs * sizeof(u64));
+    if (a == hipSuccess)   // [257] bucket starts | [256] fills | [4] results
+        a = KNN_DEV_ALLOC((void **)&c->bucket_start, (CELL_BUCKETS + 1 + CELL_BUCKETS + 4) * sizeof(unsigned));
+    if (a == hipSuccess)
+        a = KNN_DEV_ALLOC((void **)&c->items, items_ub * sizeof(u64));
+    if (a == hipSuccess)
+        a = KNN_DEV_ALLOC((void **)&c->perm, (size_t)tiles_ub * 32 * sizeof(unsigned));
+    if (a == hipSuccess) {
+        c->bucket_fill = c->bucket_start + CELL_BUCKETS + 1;
+        c->build_res = c->bucket_fill + CELL_BUCKETS;
+        for (int b = 0; b <= CELL_BUCKETS; ++b)
+            c->h_bucket_start[b] = (unsigned)b * cap_rows;
+        a = hipMemcpyAsync(c->bounds, c->h_bounds, sizeof c->h_bounds, hipMemcpyHostToDevice, s);
         if (a == hipSuccess)
-            a = KNN_DEV_ALLOC((void **)&c->tile_start, ((size_t)c->ncells + 1) * sizeof(unsigned));
+            a = hipMemcpyAsync(c->bucket_start, c->h_bucket_start, sizeof c->h_bucket_start, hipMemcpyHostToDevice, s);
         if (a == hipSuccess)
-            a = KNN_DEV_ALLOC((void **)&counts_f, (size_t)c->ncells * sizeof(unsigned));
+            a = hipMemsetAsync(c->bucket_fill, 0, (CELL_BUCKETS + 4) * sizeof(unsigned), s);
         if (a == hipSuccess)
-            a = KNN_DEV_ALLOC((void **)&c->tmp_rows, recs * 16 * sizeof(float));
-        if (a == hipSuccess)
-            a = KNN_DEV_ALLOC((void **)&c->tmp_meta, recs * sizeof(u64));
-        if (a == hipSuccess)   // [257] bucket starts | [256] fills | [4] results
-            a = KNN_DEV_ALLOC((void **)&c->bucket_start, (CELL_BUCKETS + 1 + CELL_BUCKETS + 4) * sizeof(unsigned));
-        if (a == hipSuccess)
-            a = KNN_DEV_ALLOC((void **)&c->items, items_ub * sizeof(u64));
-        if (a == hipSuccess)
-            a = KNN_DEV_ALLOC((void **)&c->perm, (size_t)tiles_ub * 32 * sizeof(unsigned));
-        if (a == hipSuccess) {
-            c->bucket_fill = c->bucket_start + CELL_BUCKETS + 1;
-            c->build_res = c->bucket_fill + CELL_BUCKETS;
-            static_assert(sizeof c->h_bounds == 16 * (CELL_MAX_BINS - 1) * sizeof(float), "cuts");
-            for (int b = 0; b <= CELL_BUCKETS; ++b)
-                c->h_bucket_start[b] = (unsigned)b * cap_rows;
-            memcpy(c->h_bounds, bounds.data(), sizeof c->h_bounds);
-            a = hipMemcpyAsync(c->bounds, c->h_bounds, sizeof c->h_bounds, hipMemcpyHostToDevice, s);
+            a = hipMemsetAsync(counts, 0, (size_t)c->ncells * sizeof(unsigned), s);
+        c->bucket_cap = cap_rows;
+        if (a == hipSuccess && scatter) {
+            a = knn_cells_fast_scatter(*c, k, r, 0, n, s);
             if (a == hipSuccess)
-                a = hipMemcpyAsync(c->bucket_start, c->h_bucket_start, sizeof c->h_bucket_start, hipMemcpyHostToDevice, s);
-            if (a == hipSuccess)
-                a = hipMemsetAsync(c->bucket_fill, 0, (CELL_BUCKETS + 4) * sizeof(unsigned), s);
-            if (a == hipSuccess)
-                a = hipMemsetAsync(counts_f, 0, (size_t)c->ncells * sizeof(unsigned), s);
-            c->lbits = lbits;
-            c->bucket_cap = cap_rows;
-            if (a == hipSuccess && !defer_scatter) {   // (an ingest scatters chunk by chunk as the rows land, then finishes)
-                a = knn_cells_fast_scatter(*c, k, r, 0, n, s);
-                if (a == hipSuccess)
-                    a = knn_cells_fast_finish(*c, counts_f, s);
-            }
+                a = knn_cells_fast_finish(*c, counts, s);
         }
-        if (a == hipSuccess) {
-            c->nitems = 0u;   // (the caller fills nitems / max_cell_rows in from build_res)
-            *code_out = nullptr;
-            *fill_out = counts_f;
-            *ntiles_out = tiles_ub;
-            *out = c;
-            return hipSuccess;
-        }
-        // no room (or a launch failed): the counted build below starts from scratch
+    }
+    if (a != hipSuccess) {
         (void)hipGetLastError();
-        (void)KNN_DEV_FREE(counts_f);
+        (void)KNN_DEV_FREE(counts);
         knn_cells_free(c);
-        if (defer_scatter)   // (an ingest has no rows on the device yet: nothing to count — the caller copies, then builds)
-            return hipSuccess;
-        c = new CellIndex();
-        c->bits = lbits;
-        c->ncells = 1u << lbits;
-        cell_grid_shape(kc, lbits, c->nb, c->shift, &c->sa);
-        c->cap = std::min(1024u, std::max(384u, (1u << 23) / c->ncells));
+        return false;
     }
+    c->nitems = 0u;   // (the finish fills nitems / max_cell_rows in from build_res)
+    stg.c = c;
+    stg.fill = counts;
+    stg.ntiles = tiles_ub;
+    return true;
+}
+
+// The counted build (how = Counted: rows to buckets, bucket counts to the host, rows to cells in buckets; see the kernels) or
+// the one-pass placement (how = OnePass: cell codes and counts in one pass, the rows placed straight from the shard).  Both
+// end in the host prefix of the cells' counts and hand the codes and zeroed fill counters to the placement.  stg.c stays null
+// when the layout is declined: no room for it, no items, or (geom) rows outside this rank's cell range — *bad_rows_out says
+// how many.  Synchronous.
+static hipError_t cells_stage_counted(CellStaging &stg, const CellIndex &plan, CellBuild how, int k, long long n, const float *r, hipStream_t s,
+                                      unsigned *bad_rows_out)
+{
+    CellIndex *c = new CellIndex(plan);
+    const CellGeom g = cell_geom_of(*c, k);
     unsigned *code = nullptr, *counts = nullptr;
     std::vector<unsigned> hcounts((size_t)c->ncells), hstart((size_t)c->ncells + 1);
     std::vector<u64> hitems;
     // (one word behind the cuts counts rows outside the index's cell range)
-    hipError_t e = KNN_DEV_ALLOC((void **)&c->bounds, (bounds.size() + 1) * sizeof(float));
-    unsigned *bad_dev = (unsigned *)(c->bounds + bounds.size());
+    hipError_t e = KNN_DEV_ALLOC((void **)&c->bounds, sizeof c->h_bounds + sizeof(float));
+    unsigned *bad_dev = (unsigned *)(c->bounds + sizeof c->h_bounds / sizeof(float));
     if (e == hipSuccess)
         e = hipMemsetAsync(bad_dev, 0, sizeof(unsigned), s);
     if (e == hipSuccess)
@@ -3145,21 +3175,13 @@ hipError_t knn_cells_build(CellIndex **out, int k, long long n, const float *r, 
     if (e == hipSuccess)
         e = KNN_DEV_ALLOC((void **)&counts, hcounts.size() * sizeof(unsigned));
     if (e == hipSuccess)
-        e = hipMemcpyAsync(c->bounds, bounds.data(), bounds.size() * sizeof(float), hipMemcpyHostToDevice, s);
+        e = hipMemcpyAsync(c->bounds, c->h_bounds, sizeof c->h_bounds, hipMemcpyHostToDevice, s);
     if (e == hipSuccess)
         e = hipMemsetAsync(counts, 0, hcounts.size() * sizeof(unsigned), s);
-    const unsigned blocks = (unsigned)((n + 255) / 256);
-    // Two-pass build (see the kernels): needs n x 72 bytes of scratch; without it (or with option `cells_build` = 1, for A/B
-    // timing and tests) the one-pass placement serves.
-    const bool one_pass_env = one_pass;
-    const int bshift = lbits - 8;   // >= 512 cells: a bucket = 2^bshift consecutive (local) cells
+    const int bshift = c->lbits - 8;   // >= 512 cells: a bucket = 2^bshift consecutive (local) cells
     const unsigned bblocks = (unsigned)((n + CELL_BUILD_ROWS - 1) / CELL_BUILD_ROWS);
-    unsigned *bucket_counts = nullptr, *bucket_fill = nullptr;
-    // (shards of up to 2^25 rows: beyond, the scratch is gigabytes that the buffer pool does not keep between builds, and one
-    // hipMalloc / hipFree pair of that size in eight took 2.2 SECONDS on a 2^27-row shard — tools/build_repeat.py: 30 20 19 19
-    // 19 19 2208 21 ms — where the one-pass placement's 33 ms are steady)
-    bool two_pass = e == hipSuccess && !one_pass_env && (size_t)n * 64 <= ((size_t)2 << 30);
-    if (two_pass) {
+    unsigned *bucket_counts = nullptr, hb[CELL_BUCKETS], hbs[CELL_BUCKETS + 1];   // (hbs: the source of a copy the sync below waits for)
+    if (e == hipSuccess && how == CellBuild::Counted) {   // the scratch: n x 72 bytes
         hipError_t a = KNN_DEV_ALLOC((void **)&c->tmp_rows, (size_t)n * 16 * sizeof(float));
         if (a == hipSuccess)
             a = KNN_DEV_ALLOC((void **)&c->tmp_meta, (size_t)n * sizeof(u64));
@@ -3167,22 +3189,16 @@ hipError_t knn_cells_build(CellIndex **out, int k, long long n, const float *r, 
             a = KNN_DEV_ALLOC((void **)&c->bucket_start, (CELL_BUCKETS + 1) * sizeof(unsigned));
         if (a == hipSuccess)
             a = KNN_DEV_ALLOC((void **)&bucket_counts, 2 * CELL_BUCKETS * sizeof(unsigned));
-        if (a != hipSuccess) {   // no room for the scratch: one pass
+        if (a != hipSuccess) {
             (void)hipGetLastError();
-            (void)KNN_DEV_FREE(c->tmp_rows);
-            (void)KNN_DEV_FREE(c->tmp_meta);
-            (void)KNN_DEV_FREE(c->bucket_start);
+            knn_cells_release_build_scratch(*c);
             (void)KNN_DEV_FREE(bucket_counts);
-            c->tmp_rows = nullptr;
-            c->tmp_meta = nullptr;
-            c->bucket_start = nullptr;
             bucket_counts = nullptr;
-            two_pass = false;
-        } else
-            bucket_fill = bucket_counts + CELL_BUCKETS;
+            how = knn_cells_next_build(how, CellRows::Sample);
+        }
     }
-    if (two_pass) {
-        unsigned hb[CELL_BUCKETS], hbs[CELL_BUCKETS + 1];
+    if (e == hipSuccess && how == CellBuild::Counted) {
+        unsigned *bucket_fill = bucket_counts + CELL_BUCKETS;
         e = hipMemsetAsync(bucket_counts, 0, 2 * CELL_BUCKETS * sizeof(unsigned), s);
         if (e == hipSuccess) {
             hipLaunchKernelGGL(knn_cells_bucket_count_kernel, dim3(bblocks), dim3(256), 0, s, r, n, g, c->bounds, bshift, code,
@@ -3209,23 +3225,17 @@ hipError_t knn_cells_build(CellIndex **out, int k, long long n, const float *r, 
                                c->bucket_start, bshift, counts, (const unsigned *)nullptr);
             e = hipGetLastError();
         }
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(hcounts.data(), counts, hcounts.size() * sizeof(unsigned), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess)
-            e = hipStreamSynchronize(s);   // (hbs has been copied; also keeps `bounds` alive until its copy is done)
-        (void)KNN_DEV_FREE(bucket_counts);
-    } else {
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(knn_cells_code_kernel, dim3(blocks), dim3(256), 0, s, r, n, g, c->bounds, code, counts, bad_dev);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(hcounts.data(), counts, hcounts.size() * sizeof(unsigned), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess)
-            e = hipStreamSynchronize(s);   // (also keeps `bounds` alive until its copy is done)
+    } else if (e == hipSuccess) {
+        hipLaunchKernelGGL(knn_cells_code_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, r, n, g, c->bounds, code, counts, bad_dev);
+        e = hipGetLastError();
     }
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(hcounts.data(), counts, hcounts.size() * sizeof(unsigned), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(s);
+    (void)KNN_DEV_FREE(bucket_counts);
     bool keep = e == hipSuccess;
-    if (keep && geom) {   // rows outside this rank's cell range: the caller partitioned with another geometry
+    if (keep && c->geom) {   // rows outside this rank's cell range: the caller partitioned with another geometry
         unsigned hbad = 0u;
         e = hipMemcpy(&hbad, bad_dev, sizeof hbad, hipMemcpyDeviceToHost);
         if (e == hipSuccess && hbad != 0u) {
@@ -3235,7 +3245,6 @@ hipError_t knn_cells_build(CellIndex **out, int k, long long n, const float *r, 
         }
         keep = keep && e == hipSuccess;
     }
-    c->lbits = lbits;
     long long tiles = 0;
     if (keep) {
         unsigned biggest = 0u;
@@ -3257,7 +3266,7 @@ hipError_t knn_cells_build(CellIndex **out, int k, long long n, const float *r, 
     }
     if (keep) {
         // the rows are placed (and turned into fragments) by knn_cells_scatter_frag_kernel once the layout buffers
-        // exist: `code` and the zeroed fill counters go back to the caller
+        // exist: `code` and the zeroed fill counters go to the finish
         e = hipMemcpyAsync(c->tile_start, hstart.data(), hstart.size() * sizeof(unsigned), hipMemcpyHostToDevice, s);
         if (e == hipSuccess)
             e = hipMemsetAsync(counts, 0, hcounts.size() * sizeof(unsigned), s);
@@ -3281,15 +3290,32 @@ hipError_t knn_cells_build(CellIndex **out, int k, long long n, const float *r, 
         knn_cells_free(c);
         return e;
     }
-    *code_out = code;
-    *fill_out = counts;
-    *ntiles_out = tiles;
-    *out = c;
+    stg.c = c;
+    stg.code = code;
+    stg.fill = counts;
+    stg.ntiles = tiles;
     return hipSuccess;
 }
 
+// Stages `how` (Fast, Counted or OnePass): the rows' cells counted, the cells' tile ranges and items made (the fast build:
+// enqueued), the layout's perm allocated.  A fast build without room for its scratch falls back (knn_cells_next_build) here.
+// stg.c stays null when the shard does not suit the cells.
+hipError_t knn_cells_stage(CellStaging &stg, const CellIndex &plan, CellBuild how, CellRows rows, int k, long long n, const float *r,
+                           hipStream_t s, unsigned *bad_rows_out)
+{
+    stg = CellStaging();
+    if (how == CellBuild::Fast) {
+        if (cells_stage_fast(stg, plan, k, n, r, s, rows != CellRows::Host))
+            return hipSuccess;
+        how = knn_cells_next_build(how, rows);
+    }
+    if (how == CellBuild::None)
+        return hipSuccess;
+    return cells_stage_counted(stg, plan, how, k, n, r, s, bad_rows_out);
+}
+
 // Every row to its cell (knn_cells_place_kernel / knn_cells_scatter_frag_kernel), then the padding of the cells' last tiles.
-// code / fill: what knn_cells_build handed back; out: the 4 words of knn_frag_kernel's statistics.
+// code / fill: what knn_cells_stage handed back; out: the 4 words of knn_frag_kernel's statistics.
 hipError_t knn_cells_place_rows(FilterState &st, const float *r, const unsigned *code, unsigned *fill, unsigned *out,
                                 unsigned ocap, hipStream_t s)
 {

@@ -206,7 +206,7 @@ struct CellIndex {
     float *tmp_rows = nullptr;
     unsigned long long *tmp_meta = nullptr;
     unsigned *bucket_start = nullptr;   // device [257]: first record of each bucket
-    // the FAST build (round 5; knn_cells_build with fast = true): buckets of fixed room, filled to bucket_fill[b]; the cells' tile
+    // the FAST build (round 5; CellBuild::Fast): buckets of fixed room, filled to bucket_fill[b]; the cells' tile
     // ranges and the items come from a device prefix — build_res = {tiles, items, rows of the largest cell, bucket overflow}
     // is read by the caller together with the placement's statistics, ONE synchronisation for the whole build
     float h_bounds[16 * 15];            // (host sources of the fast build's asynchronous copies: they must outlive the call)
@@ -287,15 +287,27 @@ struct FilterState {
 #define KNN_CELL_BATCH 1024   // queries per pass: their B operands + thresholds sit in 36 KiB of LDS (68 KiB for 16 < k <= 32)
 #ifdef __cplusplus
 #include <vector>
-// Cell codes + counts of the shard (cuts from the strided host sample of the build).  *out stays null when the
-// shard does not suit; else *code_out / *fill_out (device; the caller frees them) feed knn_cells_place_rows.
-// geom != null: the cell-range shard `rank` of that global grid (no cuts of its own; *out stays null — with *bad_rows_out
-// set — when rows fall outside the rank's cell range).
-hipError_t knn_cells_build(CellIndex **out, int k, long long n, const float *r_dev, const std::vector<float> &samp,
-                           long long samples, hipStream_t s, long long *ntiles_out, unsigned **code_out,
-                           unsigned **fill_out, bool one_pass = false, const ShardGeom *geom = nullptr, int rank = 0,
-                           unsigned *bad_rows_out = nullptr, bool fast = false, bool defer_scatter = false);
-// The fast build in stages (knn_cells_build with defer_scatter: everything allocated and uploaded, nothing scattered yet).
+// The build of a cell-sorted layout (knn_cells.hip, "the build"): plan, strategy, staging; the finish is knn_filter.hip's.
+enum class CellBuild { Fast, Counted, OnePass, None };   // None: no cell-sorted layout from this build
+// Where the build's frame and rows come from: the strided sample of resident rows (and cell-range shards), the full-range
+// statistics of resident rows (after the sampled frame was declined), or host rows that an ingest is still copying.
+enum class CellRows { Sample, FullRange, Host };
+bool knn_cells_plan(CellIndex &plan, int k, long long n, const float *samp, long long samples, const ShardGeom *geom, int rank);
+CellBuild knn_cells_first_build(const CellIndex &plan, int k, long long n, int cells_build, CellRows rows);
+CellBuild knn_cells_next_build(CellBuild how, CellRows rows);
+// A staged layout: what the placement (knn_cells_place_rows) needs besides the CellIndex.
+struct CellStaging {
+    CellIndex *c = nullptr;      // null: the shard does not suit the cells
+    long long ntiles = 0;        // the layout's tiles (the fast build: room for them — its build_res holds the count)
+    unsigned *code = nullptr;    // device [n]: every row's cell (counted build, one-pass placement)
+    unsigned *fill = nullptr;    // device [ncells]: the placement's fill counters, zeroed
+    void release();              // frees the build scratch (code, fill, the CellIndex's buckets); the layout stays
+};
+void knn_cells_release_build_scratch(CellIndex &c);
+// rows = CellRows::Host: the scatter is left to the ingest (knn_cells_fast_scatter).  *bad_rows_out: see cells_stage_counted.
+hipError_t knn_cells_stage(CellStaging &stg, const CellIndex &plan, CellBuild how, CellRows rows, int k, long long n, const float *r_dev,
+                           hipStream_t s, unsigned *bad_rows_out = nullptr);
+// The fast build in stages (knn_cells_stage for CellRows::Host: everything allocated and uploaded, nothing scattered yet).
 hipError_t knn_cells_fast_scatter(CellIndex &c, int k, const float *r_dev, long long row0, long long row1, hipStream_t s);
 hipError_t knn_cells_fast_finish(CellIndex &c, unsigned *counts, hipStream_t s);
 #endif
@@ -359,10 +371,10 @@ int knn_rccl_allreduce_min(int ndev, const int *devices, u64 *const *keys, int m
                            std::string &err, u64 *const *recv = nullptr);
 #endif
 
-// want_cells != 0: also sort the layout into cells (k <= 16, large shards; see CellIndex).
+// want_cells: also sort the layout into cells (k <= 32, large shards; see CellIndex); cells_build: option `cells_build`.
 // geom != null (cell-range shard `rank`): centre, scale and cuts are the global grid's; the layout is always cell-sorted.
-hipError_t knn_filter_build(FilterState &st, int k, long long n, const float *r_dev, hipStream_t stream,
-                            int want_cells = 0, const ShardGeom *geom = nullptr, int rank = 0, unsigned *bad_rows_out = nullptr);
+hipError_t knn_filter_build(FilterState &st, int k, long long n, const float *r_dev, hipStream_t stream, bool want_cells = false,
+                            int cells_build = 0, const ShardGeom *geom = nullptr, int rank = 0, unsigned *bad_rows_out = nullptr);
 // The global grid of a cell-range sharded set from a sample of it (host rows, samples x k): false when the set does not suit
 // (k > 16, too few rows per rank for a cell-sorted layout, a degenerate or non-finite sample).
 bool knn_geom_cells(ShardGeom &g, int k, long long n_global, int nranks, const float *sample, long long samples, int seed_tiles);   // (the grid part of it)

@@ -36,8 +36,8 @@
 // shards: the cell-pruned form, knn_cells.hip.
 #include "knn_filter_dev.h"
 
-#include <functional>
-#include <thread>
+#include <chrono>
+#include <future>
 
 // ------------------------------------------------------------------------------------------
 // Per-dimension min / max of the reference coordinates (+ count of non-finite values).
@@ -1557,8 +1557,8 @@ static double robust_box(const std::vector<float> &samp, long long samples, int 
     return h;
 }
 
-// Centre and power-of-two scale of a sample's robust box (what knn_filter_build_from_host derives from its host sample):
-// false when the sample holds non-finite values or its box is degenerate.
+// Centre (kp entries, 0 beyond k) and power-of-two scale of a sample's robust box — the frame of the builds that start from a
+// sample of 4096 rows (or fewer): false when the sample holds non-finite values or its box is degenerate.
 static bool box_from_sample(const float *sample, long long samples, int k, int kp, std::vector<float> &center, float *sigma_out)
 {
     const long long sub = samples >= 4096 ? 4 : 1, nsub = samples / sub;
@@ -1610,191 +1610,203 @@ bool knn_geom_from_sample(ShardGeom &g, int k, long long n_global, int nranks, c
     return true;
 }
 
-hipError_t knn_filter_build(FilterState &st, int k, long long n, const float *r, hipStream_t s, int want_cells,
+// Per-stage wall-clock laps of a build on stderr (KNN_MI355X_TRACE_BUILD set).
+struct BuildTrace {
+    const char *tag;
+    const bool on = getenv("KNN_MI355X_TRACE_BUILD") != nullptr;
+    std::chrono::steady_clock::time_point last = std::chrono::steady_clock::now();
+    void lap(const char *what)
+    {
+        if (!on)
+            return;
+        const auto now = std::chrono::steady_clock::now();
+        fprintf(stderr, "[%s] %-36s %8.3f ms\n", tag, what, std::chrono::duration<double, std::milli>(now - last).count());
+        last = now;
+    }
+};
+
+static unsigned outlier_cap(long long n) { return (unsigned)(n / 32 > 4096 ? n / 32 : 4096); }   // more outliers than this: no filter
+
+// `samples` strided rows (row i x (n / samples)) of the shard's device rows, on the host.  Synchronous.
+static hipError_t device_sample(const float *r, long long n, int k, long long samples, hipStream_t s, std::vector<float> &samp)
+{
+    samp.resize((size_t)samples * k);
+    float *dsamp = nullptr;
+    FTRY(KNN_DEV_ALLOC((void **)&dsamp, samp.size() * sizeof(float)));
+    hipLaunchKernelGGL(knn_sample_rows_kernel, dim3((unsigned)((samples * k + 255) / 256)), dim3(256), 0, s, r, k, n / samples, samples,
+                       dsamp);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(samp.data(), dsamp, samp.size() * sizeof(float), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(s);
+    (void)KNN_DEV_FREE(dsamp);
+    return e;
+}
+
+// The same sample of host rows
+static std::vector<float> host_sample(const float *r_host, long long n, int k, long long samples)
+{
+    std::vector<float> samp((size_t)samples * k);
+    for (long long i = 0; i < samples; ++i)
+        memcpy(&samp[(size_t)i * k], r_host + (size_t)(i * (n / samples)) * k, (size_t)k * sizeof(float));
+    return samp;
+}
+
+// The cuts' sample: every fourth row of a build's 4096-row sample (1024 rows, as the cuts had before the sample grew)
+static std::vector<float> cut_sample(const std::vector<float> &samp, int k)
+{
+    std::vector<float> cuts(samp.size() / 4 / k * k);
+    for (size_t i = 0; i < cuts.size() / k; ++i)
+        memcpy(&cuts[i * k], &samp[4 * i * k], (size_t)k * sizeof(float));
+    return cuts;
+}
+
+// st's shape and the buffers of its layouts: `ntiles` tiles (cells: + the split norms of a cell-sorted layout), the outlier
+// list, the fragment kernels' 4 statistics words (*dout, zeroed) and the centre (16 kt floats, uploaded from `center`, which
+// must outlive the next synchronisation).  Enqueues on `s`.
+static hipError_t layouts_alloc(FilterState &st, int k, long long n, long long ntiles, const float *center, float sigma, bool cells,
+                                unsigned **dout, hipStream_t s)
+{
+    st.k = k;
+    st.kt = knn_kt_of(k);
+    st.n = n;
+    st.ntiles = ntiles;
+    st.sigma = sigma;
+    FTRY(KNN_DEV_ALLOC((void **)&st.center, (size_t)16 * st.kt * sizeof(float)));
+    FTRY(KNN_DEV_ALLOC(&st.ref_frags, (size_t)ntiles * st.kt * 64 * 16));
+    FTRY(KNN_DEV_ALLOC((void **)&st.ref_norms, (size_t)ntiles * 32 * sizeof(float)));
+    if (cells)
+        FTRY(KNN_DEV_ALLOC((void **)&st.ref_norms2, (size_t)ntiles * 32 * sizeof(unsigned)));
+    FTRY(KNN_DEV_ALLOC((void **)&st.outliers, (size_t)outlier_cap(n) * sizeof(unsigned)));
+    FTRY(KNN_DEV_ALLOC((void **)dout, 4 * sizeof(unsigned)));
+    FTRY(hipMemsetAsync(*dout, 0, 4 * sizeof(unsigned), s));
+    return hipMemcpyAsync(st.center, center, (size_t)16 * st.kt * sizeof(float), hipMemcpyHostToDevice, s);
+}
+
+static const char *staged(const CellStaging &stg)
+{
+    return !stg.c ? "cell codes (not kept)" : stg.c->build_res ? "buckets + cell prefix (enqueued)" : "cell codes + counts";
+}
+
+// The end of every cell-sorted build, once the layout is staged (st.cells = stg.c) and its buffers are allocated (layouts_alloc,
+// whose error is `e`): the rows placed, the statistics — and the fast build's build_res — read behind ONE synchronisation (of
+// `s`, and of an ingest's `copy` stream), the build scratch released, then the layout accepted or rejected: fp16 range
+// trouble, too many rows outside the box (no layouts from this frame), or *overflow — a bucket of the fast build outgrew its
+// fixed room.  An accepted layout gets per-cell frames or 8-bit rows where knn_cells_maybe_recentre wants them (samp: the
+// build's host sample, null when there is none).  Leaves st reset unless the layout stands.
+static hipError_t cells_finish(FilterState &st, CellStaging &stg, hipError_t e, const float *r, unsigned *dout, const float *samp,
+                               long long samples, hipStream_t s, BuildTrace &tr, bool *overflow, hipStream_t copy = nullptr)
+{
+    *overflow = false;
+    const unsigned ocap = outlier_cap(st.n);
+    const bool fast = stg.c->build_res != nullptr;
+    unsigned hout[4] = {0, 0, 0, 0}, hres[4] = {0, 0, 0, 0};
+    if (e == hipSuccess)
+        e = knn_cells_place_rows(st, r, stg.code, stg.fill, dout, ocap, s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(hout, dout, sizeof hout, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && fast)
+        e = hipMemcpyAsync(hres, stg.c->build_res, sizeof hres, hipMemcpyDeviceToHost, s);
+    const hipError_t e1 = copy ? hipStreamSynchronize(copy) : hipSuccess, e2 = hipStreamSynchronize(s);
+    if (e == hipSuccess)
+        e = e1 != hipSuccess ? e1 : e2;
+    tr.lap(fast ? "build kernels + placement + sync" : "placement + sync");
+    if (e == hipSuccess && fast) {
+        // the fast build's verdict: tiles, items, the largest cell — or a bucket that outgrew its fixed room
+        st.ntiles = hres[0];
+        st.cells->nitems = hres[1];
+        st.cells->max_cell_rows = hres[2];
+        *overflow = hres[3] != 0u || hres[1] == 0u;
+        if (tr.on)
+            fprintf(stderr, "[%s] fast build: %u tiles (room for %lld), %u items, largest cell %u rows, overflow %u, outside the box %u\n",
+                    tr.tag, hres[0], stg.ntiles, hres[1], hres[2], hres[3], hout[3]);
+    }
+    stg.release();
+    (void)KNN_DEV_FREE(dout);
+    if (e != hipSuccess || *overflow || hout[2] != 0u || hout[3] > ocap) {
+        knn_filter_free(st);
+        return e;
+    }
+    st.n_outliers = hout[3];
+    memcpy(&st.bmax, &hout[0], 4);
+    memcpy(&st.nmax, &hout[1], 4);
+    st.usable = true;
+    e = knn_cells_maybe_recentre(st, r, samp, samples, s);   // clustered data (or on request): each cell in its own frame
+    tr.lap("per-cell frames (if any)");
+    if (e != hipSuccess)
+        knn_filter_free(st);
+    return e;
+}
+
+hipError_t knn_filter_build(FilterState &st, int k, long long n, const float *r, hipStream_t s, bool want_cells, int cells_build,
                             const ShardGeom *geom, int rank, unsigned *bad_rows_out)
 {
     st = FilterState();
     const int kt = knn_kt_of(k);
-    if (n <= 0 || kt == 0)
+    if (n <= 0 || kt == 0 || (geom && (kt != 1 || geom->k != k)))
         return hipSuccess;
-    const bool trace = getenv("KNN_MI355X_TRACE_BUILD") != nullptr;
-    auto t_last = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
-        if (!trace)
-            return;
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[knn build] %-24s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
-        t_last = now;
-    };
-    // want_cells: 1 = the fast two-pass build, counted build if a bucket overflows; 2 = one-pass placement; 3 = the counted two-pass build
-    bool fast_build = want_cells == 1, fast_overflow = false;
-    // The cell-sorted layout from a GIVEN frame (centre, scale) and either a shard geometry's cuts or cuts taken from `samp`.
-    // Returns with st.usable set when the layout stands; st.cells null (and st reset) when the shard does not suit the cells.
-    // late_frame (nullable): called once the cells are counted; fills centre and scale then (false: no frame — give up)
-    auto sorted_layout = [&](float *center16, float sigma, const std::vector<float> &samp, long long samples,
-                             const std::function<bool(float *, float *)> &late_frame) -> hipError_t {
-        long long ntiles = 0;
-        unsigned *cell_code = nullptr, *cell_fill = nullptr;
-        FTRY(knn_cells_build(&st.cells, k, n, r, samp, samples, s, &ntiles, &cell_code, &cell_fill, want_cells == 2 || kt == 2, geom, rank,
-                             bad_rows_out, fast_build && kt == 1));
-        lap(st.cells ? (st.cells->build_res ? "buckets + cell prefix (enqueued)" : "cell codes + counts") : "cell codes (not kept)");
-        if (!st.cells)
-            return hipSuccess;
-        if (late_frame && !late_frame(center16, &sigma)) {
-            (void)KNN_DEV_FREE(cell_code);
-            (void)KNN_DEV_FREE(cell_fill);
-            knn_filter_free(st);
-            return hipSuccess;
-        }
-        st.k = k;
-        st.kt = kt;   // (1, or 2 for 16 < k <= 32)
-        st.n = n;
-        st.ntiles = ntiles;
-        st.sigma = sigma;
-        unsigned *dout = nullptr;
-        hipError_t e = KNN_DEV_ALLOC((void **)&st.center, (size_t)16 * kt * sizeof(float));
-        if (e == hipSuccess)
-            e = KNN_DEV_ALLOC(&st.ref_frags, (size_t)ntiles * kt * 64 * 16);
-        if (e == hipSuccess)
-            e = KNN_DEV_ALLOC((void **)&st.ref_norms, (size_t)ntiles * 32 * sizeof(float));
-        if (e == hipSuccess)
-            e = KNN_DEV_ALLOC((void **)&st.ref_norms2, (size_t)ntiles * 32 * sizeof(unsigned));
-        const unsigned ocap = (unsigned)(n / 32 > 4096 ? n / 32 : 4096);
-        if (e == hipSuccess)
-            e = KNN_DEV_ALLOC((void **)&st.outliers, (size_t)ocap * sizeof(unsigned));
-        if (e == hipSuccess)
-            e = KNN_DEV_ALLOC((void **)&dout, 4 * sizeof(unsigned));
-        if (e == hipSuccess)
-            e = hipMemsetAsync(dout, 0, 4 * sizeof(unsigned), s);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(st.center, center16, (size_t)16 * kt * sizeof(float), hipMemcpyHostToDevice, s);
-        lap("allocations");
-        unsigned hout[4] = {0, 0, 0, 0}, hres[4] = {0, 0, 0, 0};
-        const bool fast_built = st.cells->build_res != nullptr;
-        if (e == hipSuccess)
-            e = knn_cells_place_rows(st, r, cell_code, cell_fill, dout, ocap, s);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(hout, dout, sizeof hout, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess && fast_built)
-            e = hipMemcpyAsync(hres, st.cells->build_res, sizeof hres, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess)
-            e = hipStreamSynchronize(s);   // (also keeps `center16` alive until the copy is done)
-        lap(fast_built ? "build kernels + placement + sync" : "placement + sync");
-        if (e == hipSuccess && fast_built) {
-            // the fast build's verdict: tiles, items, the largest cell — or a bucket that outgrew its fixed room
-            st.ntiles = hres[0];
-            st.cells->nitems = hres[1];
-            st.cells->max_cell_rows = hres[2];
-            if (hres[3] != 0u || hres[1] == 0u)
-                fast_overflow = true;
-            if (trace)
-                fprintf(stderr, "[knn build] fast build: %u tiles (room for %lld), %u items, largest cell %u rows, overflow %u\n", hres[0], ntiles,
-                        hres[1], hres[2], hres[3]);
-        }
-        (void)KNN_DEV_FREE(cell_code);
-        (void)KNN_DEV_FREE(cell_fill);
-        (void)KNN_DEV_FREE(st.cells->tmp_rows);
-        (void)KNN_DEV_FREE(st.cells->tmp_meta);
-        (void)KNN_DEV_FREE(st.cells->bucket_start);
-        st.cells->tmp_rows = nullptr;
-        st.cells->tmp_meta = nullptr;
-        st.cells->bucket_start = nullptr;
-        (void)KNN_DEV_FREE(dout);
-        st.cells->bucket_fill = nullptr;
-        st.cells->build_res = nullptr;
-        if (e != hipSuccess || fast_overflow || hout[2] != 0u || hout[3] > ocap) {   // (too many rows outside the box: no layouts from this frame)
-            knn_filter_free(st);
-            return e;
-        }
-        st.n_outliers = hout[3];
-        memcpy(&st.bmax, &hout[0], 4);
-        memcpy(&st.nmax, &hout[1], 4);
-        st.usable = true;
-        if (!geom) {   // clustered data (or on request): the fragments again, each cell in its own frame
-            e = knn_cells_maybe_recentre(st, r, samples > 0 ? samp.data() : nullptr, samples, s);
-            lap("per-cell frames (if any)");
-            if (e != hipSuccess)
-                knn_filter_free(st);
-        }
-        return e;
-    };
-    if (geom) {
+    BuildTrace tr{"knn build"};
+    if (geom || (want_cells && kt <= 2 && n >= (1ll << 17))) {
+        // The cell-sorted layout from a GIVEN frame (centre, scale) and either a shard geometry's cuts or cuts taken from a sample.
         // Cell-range shard of a global grid: centre, scale and cuts are the grid's (identical on every rank: the ranks' fp16
         // fragments — the seed layer — must live in one frame), the layout is this rank's cells of it.
-        if (kt != 1 || geom->k != k)
-            return hipSuccess;
-        std::vector<float> none;
-        float center16[16];
-        memcpy(center16, geom->center, sizeof center16);
-        return sorted_layout(center16, geom->sigma, none, 0, nullptr);
-    }
-    if (want_cells && kt <= 2 && n >= (1ll << 17)) {
-        // Round 4: the frame of a cell-sorted layout from a strided SAMPLE of the rows (4096 of them: range widened by 1 / 32,
-        // median / MAD box inside it — what knn_filter_build_from_host does for host rows), not from a pass over the whole
-        // shard: the full-range statistics kernel read 1 GiB for a box that any representative sample gives, and its round
-        // trip to the host stood in front of everything else (0.25 of the build's 3.4 ms at C3).  ANY box is correct: rows
-        // outside it go to the exact list; if the sample was not representative (more than n / 32 rows outside, or values that
-        // are not finite in the sample) the classic build below starts over with full-range statistics.
-        const long long samples = 4096, row_stride = n / samples;
-        std::vector<float> samp((size_t)samples * k);
-        float *dsamp = nullptr;
-        FTRY(KNN_DEV_ALLOC((void **)&dsamp, samp.size() * sizeof(float)));
-        hipLaunchKernelGGL(knn_sample_rows_kernel, dim3((unsigned)((samples * k + 255) / 256)), dim3(256), 0, s, r, k, row_stride,
-                           samples, dsamp);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(samp.data(), dsamp, samp.size() * sizeof(float), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess)
-            e = hipStreamSynchronize(s);
-        (void)KNN_DEV_FREE(dsamp);
-        FTRY(e);
-        lap("sample rows + copy");
-        // (the frame is host arithmetic on the sample — 0.25 ms — and only the placement needs it: it is worked out on a thread
-        // of its own while the cell codes and buckets are made on the GPU)
-        std::vector<float> center;
+        // Round 4: else the frame from a strided SAMPLE of the rows (4096 of them: range widened by 1 / 32, median / MAD box
+        // inside it — what knn_filter_build_from_host does for host rows), not from a pass over the whole shard: the
+        // full-range statistics kernel read 1 GiB for a box that any representative sample gives, and its round trip to the
+        // host stood in front of everything else (0.25 of the build's 3.4 ms at C3).  ANY box is correct: rows outside it go
+        // to the exact list; if the sample was not representative (more than n / 32 rows outside, or values that are not
+        // finite in the sample) the classic build below starts over with full-range statistics.
+        std::vector<float> samp, cuts, center;
         float sigma = 1.0f;
-        bool box_ok = false;
-        std::thread boxer([&] { box_ok = box_from_sample(samp.data(), samples, k, 16 * kt, center, &sigma); });
-        std::vector<float> cut_samp((size_t)(samples / 4) * k);   // (the cuts from every fourth sample row, 1024 as before)
-        for (long long i = 0; i < samples / 4; ++i)
-            memcpy(&cut_samp[(size_t)i * k], &samp[(size_t)(4 * i) * k], (size_t)k * sizeof(float));
-        float center16[32] = {0};   // (16 kt entries used)
-        struct Joiner {   // (every way out of this block waits for the thread)
-            std::thread &t;
-            ~Joiner()
-            {
-                if (t.joinable())
-                    t.join();
-            }
-        } joiner{boxer};
-        auto frame = [&](float *c16, float *sg) -> bool {
-            if (boxer.joinable())
-                boxer.join();
-            if (!box_ok)
-                return false;
-            for (int d = 0; d < 16 * kt; ++d)
-                c16[d] = d < k ? center[(size_t)d] : 0.0f;
-            *sg = sigma;
-            return true;
-        };
-        {
-            FTRY(sorted_layout(center16, sigma, cut_samp, samples / 4, frame));
-            if (st.usable)
-                return hipSuccess;
-            if (fast_overflow) {   // a bucket outgrew its fixed room (rows the cuts do not spread evenly): the counted build
-                lap("fast build: bucket overflow");
-                fast_overflow = false;
-                fast_build = false;
-                st = FilterState();
-                FTRY(sorted_layout(center16, sigma, cut_samp, samples / 4, frame));
-                if (st.usable)
-                    return hipSuccess;
-            }
-            st = FilterState();   // (declined, or the sampled frame left too many rows out: the classic build decides)
+        bool box_ok = true;
+        std::future<bool> frame;   // (every way out of this block waits for its thread)
+        if (geom) {
+            center.assign(geom->center, geom->center + 16);
+            sigma = geom->sigma;
+        } else {
+            const long long samples = 4096;
+            FTRY(device_sample(r, n, k, samples, s, samp));
+            tr.lap("sample rows + copy");
+            // (the frame is host arithmetic on the sample — 0.25 ms — and only the placement needs it: it is worked out on a
+            // thread of its own while the cell codes and buckets are made on the GPU)
+            frame = std::async(std::launch::async, [&] { return box_from_sample(samp.data(), samples, k, 16 * kt, center, &sigma); });
+            cuts = cut_sample(samp, k);
         }
+        const long long ncuts = (long long)cuts.size() / k;
+        CellIndex plan;
+        if (knn_cells_plan(plan, k, n, cuts.data(), ncuts, geom, rank)) {
+            CellBuild how = knn_cells_first_build(plan, k, n, cells_build, CellRows::Sample);
+            for (;;) {
+                CellStaging stg;
+                FTRY(knn_cells_stage(stg, plan, how, CellRows::Sample, k, n, r, s, bad_rows_out));
+                tr.lap(staged(stg));
+                if (!(st.cells = stg.c))
+                    break;
+                if (frame.valid())
+                    box_ok = frame.get();
+                if (!box_ok) {   // (the sample is not finite, or its box degenerate)
+                    stg.release();
+                    knn_filter_free(st);
+                    break;
+                }
+                unsigned *dout = nullptr;
+                const hipError_t e = layouts_alloc(st, k, n, stg.ntiles, center.data(), sigma, true, &dout, s);
+                tr.lap("allocations");
+                bool overflow = false;
+                FTRY(cells_finish(st, stg, e, r, dout, ncuts > 0 ? cuts.data() : nullptr, ncuts, s, tr, &overflow));
+                if (st.usable || !overflow)
+                    break;
+                tr.lap("fast build: bucket overflow");   // (rows the cuts do not spread evenly)
+                how = knn_cells_next_build(how, CellRows::Sample);
+            }
+        }
+        if (st.usable || geom)
+            return hipSuccess;
+        st = FilterState();   // (declined, or the sampled frame left too many rows out: the classic build decides)
     }
     const int kp = 16 * kt;
-    long long ntiles = (n + 31) / 32;
+    const long long ntiles = (n + 31) / 32;
 
     // 1. per-dimension range
     std::vector<unsigned> hstats((size_t)2 * k + 1);
@@ -1821,7 +1833,7 @@ hipError_t knn_filter_build(FilterState &st, int k, long long n, const float *r,
         e = hipStreamSynchronize(s);
     (void)KNN_DEV_FREE(dstats);
     FTRY(e);
-    lap("range kernel + sync");
+    tr.lap("range kernel + sync");
     // NaN / Inf among the references: those rows are outside any box and go to the exact list like every other
     // outlier (the fragment kernels test for them); only a shard that is mostly such rows gets no layouts
     const bool has_nonfinite = hstats[(size_t)2 * k] != 0u;
@@ -1831,31 +1843,12 @@ hipError_t knn_filter_build(FilterState &st, int k, long long n, const float *r,
         if (hstats[(size_t)d] == 0xFFFFFFFFu || hstats[(size_t)k + d] == 0u)
             return hipSuccess;  // a dimension without a single finite value
 
-    // 1b. robust box: per dimension [median - w s, median + w s] clipped to [min, max], with
-    // s = 1.4826 * MAD from a strided sample of up to 1024 rows (median/MAD do not move when a few rows sit
-    // 300 sigma out; mean/std do).  A few far-out rows would otherwise stretch the box, and with it
-    // the fp16 step, for everybody.  ANY box is correct: rows outside it leave the filter and are
-    // scanned exactly on every query, so the box is only worth it if it leaves out a handful of
-    // rows — w doubles from 12 until at most 1 % of the sample falls outside (heavy tails), and a
-    // second mode further out than 96 s (more than 1 % of the rows) keeps the plain [min, max].
+    // 1b. robust box (robust_box) clipped to [min, max], from a strided sample of up to 1024 rows
     const long long want = k <= 16 ? 1024 : (16384 / k > 256 ? 16384 / k : 256);  // host work ~0.2 ms at any k
     const long long samples = n < want ? n : want;
-    const long long row_stride = n / samples;
-    std::vector<float> samp((size_t)samples * k);
-    {
-        float *dsamp = nullptr;
-        FTRY(KNN_DEV_ALLOC((void **)&dsamp, samp.size() * sizeof(float)));
-        hipLaunchKernelGGL(knn_sample_rows_kernel, dim3((unsigned)((samples * k + 255) / 256)), dim3(256), 0, s, r, k,
-                           row_stride, samples, dsamp);
-        e = hipGetLastError();
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(samp.data(), dsamp, samp.size() * sizeof(float), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess)
-            e = hipStreamSynchronize(s);
-        (void)KNN_DEV_FREE(dsamp);
-        FTRY(e);
-        lap("sample rows + copy");
-    }
+    std::vector<float> samp;
+    FTRY(device_sample(r, n, k, samples, s, samp));
+    tr.lap("sample rows + copy");
     long long samples_used = samples;
     if (has_nonfinite) {   // the statistics below want finite rows only
         samples_used = 0;
@@ -1878,7 +1871,7 @@ hipError_t knn_filter_build(FilterState &st, int k, long long n, const float *r,
         dhi[(size_t)d] = ord2f_host(hstats[(size_t)k + d]);
     }
     const double h = robust_box(samp, samples_used, k, kp, dlo, dhi, center);
-    lap("median / MAD box (host)");
+    tr.lap("median / MAD box (host)");
     if (!(h <= 1e15) || (h != 0.0 && h < 1e-15))
         return hipSuccess;
     float sigma = 1.0f;
@@ -1888,43 +1881,32 @@ hipError_t knn_filter_build(FilterState &st, int k, long long n, const float *r,
         sigma = (float)ldexp(1.0, -ex);
     }
 
-    // 1c. cell-sorted layout (k <= 16, resident indexes): ntiles becomes the padded tile count
-    unsigned *cell_code = nullptr, *cell_fill = nullptr;
+    // 1c. cell-sorted layout (k <= 16, resident indexes): the counted build, or the one-pass placement
     if (want_cells && kt == 1) {
-        FTRY(knn_cells_build(&st.cells, k, n, r, samp, samples_used, s, &ntiles, &cell_code, &cell_fill, want_cells == 2));
-        lap(st.cells ? "cell codes + counts" : "cell codes (not kept)");
+        CellIndex plan;
+        CellStaging stg;
+        if (knn_cells_plan(plan, k, n, samp.data(), samples_used, nullptr, 0))
+            FTRY(knn_cells_stage(stg, plan, knn_cells_first_build(plan, k, n, cells_build, CellRows::FullRange), CellRows::FullRange, k, n,
+                                 r, s));
+        tr.lap(staged(stg));
+        if ((st.cells = stg.c)) {
+            unsigned *dout = nullptr;
+            e = layouts_alloc(st, k, n, stg.ntiles, center.data(), sigma, true, &dout, s);
+            tr.lap("allocations");
+            bool overflow = false;
+            return cells_finish(st, stg, e, r, dout, samp.data(), samples_used, s, tr, &overflow);
+        }
     }
 
     // 2. fragments + norms
-    st.k = k;
-    st.kt = kt;
-    st.n = n;
-    st.ntiles = ntiles;
-    st.sigma = sigma;
     unsigned *dout = nullptr;
-    e = KNN_DEV_ALLOC((void **)&st.center, (size_t)kp * sizeof(float));
-    if (e == hipSuccess)
-        e = KNN_DEV_ALLOC(&st.ref_frags, (size_t)ntiles * kt * 64 * 16);
-    if (e == hipSuccess)
-        e = KNN_DEV_ALLOC((void **)&st.ref_norms, (size_t)ntiles * 32 * sizeof(float));
-    if (e == hipSuccess && st.cells)
-        e = KNN_DEV_ALLOC((void **)&st.ref_norms2, (size_t)ntiles * 32 * sizeof(unsigned));
-    const unsigned ocap = (unsigned)(n / 32 > 4096 ? n / 32 : 4096);  // more outliers than this: no filter
-    if (e == hipSuccess)
-        e = KNN_DEV_ALLOC((void **)&st.outliers, (size_t)ocap * sizeof(unsigned));
-    if (e == hipSuccess)
-        e = KNN_DEV_ALLOC((void **)&dout, 4 * sizeof(unsigned));
-    if (e == hipSuccess)
-        e = hipMemsetAsync(dout, 0, 4 * sizeof(unsigned), s);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(st.center, center.data(), (size_t)kp * sizeof(float), hipMemcpyHostToDevice, s);
+    const unsigned ocap = outlier_cap(n);
+    e = layouts_alloc(st, k, n, ntiles, center.data(), sigma, false, &dout, s);
     unsigned hout[4] = {0, 0, 0, 0};
-    lap("allocations");
+    tr.lap("allocations");
     if (e == hipSuccess) {
         const long long rows_padded = ntiles * 32;
-        if (st.cells) {
-            e = knn_cells_place_rows(st, r, cell_code, cell_fill, dout, ocap, s);
-        } else if (k == 16 && ((uintptr_t)r & 15u) == 0)
+        if (k == 16 && ((uintptr_t)r & 15u) == 0)
             hipLaunchKernelGGL(knn_frag16_kernel, dim3((unsigned)((rows_padded + 255) / 256)), dim3(256), 0, s,
                                (const f4v *)r, n, rows_padded, st.center, sigma, (h8 *)st.ref_frags,
                                st.ref_norms, dout, st.outliers, ocap);
@@ -1938,17 +1920,7 @@ hipError_t knn_filter_build(FilterState &st, int k, long long n, const float *r,
         e = hipMemcpyAsync(hout, dout, sizeof hout, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess)
         e = hipStreamSynchronize(s);  // also keeps `center` alive until the copy is done
-    lap("fragment kernel + sync");
-    (void)KNN_DEV_FREE(cell_code);
-    (void)KNN_DEV_FREE(cell_fill);
-    if (st.cells) {   // the two-pass build's scratch (the stream has been synchronised: the placement kernel is done)
-        (void)KNN_DEV_FREE(st.cells->tmp_rows);
-        (void)KNN_DEV_FREE(st.cells->tmp_meta);
-        (void)KNN_DEV_FREE(st.cells->bucket_start);
-        st.cells->tmp_rows = nullptr;
-        st.cells->tmp_meta = nullptr;
-        st.cells->bucket_start = nullptr;
-    }
+    tr.lap("fragment kernel + sync");
     (void)KNN_DEV_FREE(dout);
     if (e != hipSuccess) {
         knn_filter_free(st);
@@ -1962,12 +1934,7 @@ hipError_t knn_filter_build(FilterState &st, int k, long long n, const float *r,
     memcpy(&st.bmax, &hout[0], 4);
     memcpy(&st.nmax, &hout[1], 4);
     st.usable = true;
-    if (st.cells) {
-        e = knn_cells_maybe_recentre(st, r, samp.data(), samples_used, s);
-        if (e != hipSuccess)
-            knn_filter_free(st);
-    }
-    return e;
+    return hipSuccess;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1990,65 +1957,28 @@ hipError_t knn_filter_build_from_host(FilterState &st, int k, long long n, float
                                       hipStream_t copy, hipStream_t compute)
 {
     st = FilterState();
-    const bool trace = getenv("KNN_MI355X_TRACE_BUILD") != nullptr;
-    auto t_last = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
-        if (!trace)
-            return;
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[knn ingest] %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
-        t_last = now;
-    };
+    BuildTrace tr{"knn ingest"};
     const size_t row_bytes = (size_t)k * sizeof(float);
     const bool layouts = n > 0 && knn_kt_of(k) != 0;
     const int kt = layouts ? knn_kt_of(k) : 1;
     const int kp = 16 * kt;
     const long long ntiles = (n + 31) / 32;
 
-    // 1. box from a host sample
+    // 1. box from a host sample: 4096 strided rows give the range (every read is a cache + TLB miss: 16384 rows cost 3.6 ms,
+    // more than the layouts), every 4th of them — 1024 rows, as in knn_filter_build — the median / MAD (box_from_sample;
+    // non-finite rows in the sample: leave it to the classic build)
     bool usable = layouts;
     std::vector<float> center;
     float sigma = 1.0f;
     if (usable) {
-        // 4096 strided rows give the range (every read is a cache + TLB miss: 16384 rows cost 3.6 ms, more than
-        // the layouts), every 4th of them — 1024 rows, as in knn_filter_build — the median / MAD
         const long long samples = n < 4096 ? n : 4096;
-        const long long row_stride = n / samples;
-        const long long sub = samples >= 4096 ? 4 : 1, nsub = samples / sub;
-        std::vector<float> samp((size_t)nsub * k), dlo((size_t)k, INFINITY), dhi((size_t)k, -INFINITY);
-        for (long long i = 0; i < samples && usable; ++i) {
-            const float *x = r_host + (size_t)(i * row_stride) * k;
-            for (int d = 0; d < k; ++d) {
-                const float v = x[d];
-                if (!(fabsf(v) < INFINITY))
-                    usable = false;   // non-finite rows in the sample: leave it to the classic build
-                if (i % sub == 0 && i / sub < nsub)
-                    samp[(size_t)(i / sub) * k + d] = v;
-                dlo[(size_t)d] = fminf(dlo[(size_t)d], v);
-                dhi[(size_t)d] = fmaxf(dhi[(size_t)d], v);
-            }
-        }
-        if (usable) {
-            for (int d = 0; d < k; ++d) {
-                const float pad = (dhi[(size_t)d] - dlo[(size_t)d]) * (1.0f / 32.0f);
-                dlo[(size_t)d] -= pad;
-                dhi[(size_t)d] += pad;
-            }
-            const double h = robust_box(samp, nsub, k, kp, dlo, dhi, center);
-            if (!(h <= 1e15) || (h != 0.0 && h < 1e-15))
-                usable = false;
-            else if (h > 0.0) {
-                int ex;
-                (void)frexp(h, &ex);
-                sigma = (float)ldexp(1.0, -ex);
-            }
-        }
+        usable = box_from_sample(host_sample(r_host, n, k, samples).data(), samples, k, kp, center, &sigma);
     }
 
-    lap("host sample + box");
+    tr.lap("host sample + box");
     // 2. buffers
     unsigned *dout = nullptr;
-    const unsigned ocap = (unsigned)(n / 32 > 4096 ? n / 32 : 4096);
+    const unsigned ocap = outlier_cap(n);
     hipError_t e = hipSuccess;
     if (usable) {
         st.k = k;
@@ -2084,7 +2014,7 @@ hipError_t knn_filter_build_from_host(FilterState &st, int k, long long n, float
         }
     }
 
-    lap("allocations");
+    tr.lap("allocations");
     // 3. Two chunks: everything but the last 64 MiB in ONE pageable copy, then the tail.  A pageable
     // hipMemcpy runs at the link rate (55 GB/s: the runtime pins the caller's pages as it goes) but every
     // call costs ~0.25 ms of pipeline fill, so sixteen 64 MiB chunks lost 4 ms against one 1 GiB copy
@@ -2101,7 +2031,7 @@ hipError_t knn_filter_build_from_host(FilterState &st, int k, long long n, float
                            hipMemcpyHostToDevice, copy);
         const long long r0_this = r0;
         r0 = r1;
-        lap("copy call returned");
+        tr.lap("copy call returned");
         if (!usable || e != hipSuccess)
             continue;
         hipEvent_t ev = nullptr;
@@ -2134,13 +2064,13 @@ hipError_t knn_filter_build_from_host(FilterState &st, int k, long long n, float
     if (usable && e == hipSuccess)
         e = hipMemcpyAsync(hout, dout, sizeof hout, hipMemcpyDeviceToHost, compute);
     const hipError_t e1 = hipStreamSynchronize(copy), e2 = hipStreamSynchronize(compute);
-    lap("streams drained");
+    tr.lap("streams drained");
     if (e == hipSuccess)
         e = e1 != hipSuccess ? e1 : e2;
     for (hipEvent_t ev : events)
         (void)hipEventDestroy(ev);
     (void)KNN_DEV_FREE(dout);
-    lap("events + scratch released");
+    tr.lap("events + scratch released");
     if (e != hipSuccess) {
         knn_filter_free(st);
         return e;
@@ -2175,15 +2105,7 @@ hipError_t knn_filter_build_cells_from_host(FilterState &st, int k, long long n,
                                             hipStream_t copy, hipStream_t compute)
 {
     st = FilterState();
-    const bool trace = getenv("KNN_MI355X_TRACE_BUILD") != nullptr;
-    auto t_last = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
-        if (!trace)
-            return;
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[knn ingest] %-36s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
-        t_last = now;
-    };
+    BuildTrace tr{"knn ingest"};
     const size_t row_bytes = (size_t)k * sizeof(float);
     auto plain_copy = [&]() -> hipError_t {
         FTRY(hipMemcpyAsync(r_dev, r_host, (size_t)n * row_bytes, hipMemcpyHostToDevice, copy));
@@ -2192,59 +2114,32 @@ hipError_t knn_filter_build_cells_from_host(FilterState &st, int k, long long n,
     if (k > 16 || n < (1ll << 17))
         return plain_copy();
     // 1. frame and cuts from a host sample
-    const long long samples = 4096, row_stride = n / samples;
-    std::vector<float> samp((size_t)samples * k);
-    for (long long i = 0; i < samples; ++i)
-        memcpy(&samp[(size_t)i * k], r_host + (size_t)(i * row_stride) * k, row_bytes);
+    const long long samples = 4096;
+    const std::vector<float> samp = host_sample(r_host, n, k, samples);
     std::vector<float> center;
     float sigma = 1.0f;
     if (!box_from_sample(samp.data(), samples, k, 16, center, &sigma))
         return plain_copy();
-    std::vector<float> cut_samp((size_t)(samples / 4) * k);
-    for (long long i = 0; i < samples / 4; ++i)
-        memcpy(&cut_samp[(size_t)i * k], &samp[(size_t)(4 * i) * k], row_bytes);
-    lap("host sample, box, cuts");
+    const std::vector<float> cuts = cut_sample(samp, k);
+    tr.lap("host sample, box, cuts");
     // 2. the fast build, everything but its scatter
-    long long ntiles = 0;
-    unsigned *cell_code = nullptr, *cell_fill = nullptr;
-    FTRY(knn_cells_build(&st.cells, k, n, r_dev, cut_samp, samples / 4, compute, &ntiles, &cell_code, &cell_fill, false, nullptr, 0, nullptr,
-                         true, true));
-    if (!st.cells)
+    CellIndex plan;
+    CellStaging stg;
+    if (knn_cells_plan(plan, k, n, cuts.data(), samples / 4, nullptr, 0))
+        FTRY(knn_cells_stage(stg, plan, knn_cells_first_build(plan, k, n, 0, CellRows::Host), CellRows::Host, k, n, r_dev, compute));
+    if (!(st.cells = stg.c))
         return plain_copy();
-    st.k = k;
-    st.kt = 1;
-    st.n = n;
-    st.ntiles = ntiles;   // (room; the build's own count replaces it below)
-    st.sigma = sigma;
-    float center16[16];
-    for (int d = 0; d < 16; ++d)
-        center16[d] = d < k ? center[(size_t)d] : 0.0f;
     unsigned *dout = nullptr;
-    const unsigned ocap = (unsigned)(n / 32 > 4096 ? n / 32 : 4096);
-    hipError_t e = KNN_DEV_ALLOC((void **)&st.center, 16 * sizeof(float));
-    if (e == hipSuccess)
-        e = KNN_DEV_ALLOC(&st.ref_frags, (size_t)ntiles * 64 * 16);
-    if (e == hipSuccess)
-        e = KNN_DEV_ALLOC((void **)&st.ref_norms, (size_t)ntiles * 32 * sizeof(float));
-    if (e == hipSuccess)
-        e = KNN_DEV_ALLOC((void **)&st.ref_norms2, (size_t)ntiles * 32 * sizeof(unsigned));
-    if (e == hipSuccess)
-        e = KNN_DEV_ALLOC((void **)&st.outliers, (size_t)ocap * sizeof(unsigned));
-    if (e == hipSuccess)
-        e = KNN_DEV_ALLOC((void **)&dout, 4 * sizeof(unsigned));
-    if (e == hipSuccess)
-        e = hipMemsetAsync(dout, 0, 4 * sizeof(unsigned), compute);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(st.center, center16, sizeof center16, hipMemcpyHostToDevice, compute);
+    hipError_t e = layouts_alloc(st, k, n, stg.ntiles, center.data(), sigma, true, &dout, compute);
     if (e != hipSuccess) {   // no room for the layouts: rows only (the caller's build will find the same and say so)
         (void)hipGetLastError();
         (void)hipStreamSynchronize(compute);
         (void)KNN_DEV_FREE(dout);
-        (void)KNN_DEV_FREE(cell_fill);
+        stg.release();
         knn_filter_free(st);
         return plain_copy();
     }
-    lap("allocations");
+    tr.lap("allocations");
     // 3. two chunks (see knn_filter_build_from_host: a pageable copy runs at the link rate but every call costs ~0.25 ms of
     // pipeline fill): everything but the last 64 MiB, then the tail; each is scattered into the buckets as soon as it is there
     const long long tail_rows = ((long long)((64u << 20) / row_bytes) + 4095) / 4096 * 4096;
@@ -2253,7 +2148,7 @@ hipError_t knn_filter_build_cells_from_host(FilterState &st, int k, long long n,
     for (long long r0 = 0; r0 < n && e == hipSuccess;) {
         const long long r1 = r0 == 0 ? head_rows : n;
         e = hipMemcpyAsync(r_dev + (size_t)r0 * k, r_host + (size_t)r0 * k, (size_t)(r1 - r0) * row_bytes, hipMemcpyHostToDevice, copy);
-        lap("copy call returned");
+        tr.lap("copy call returned");
         hipEvent_t ev = nullptr;
         if (e == hipSuccess)
             e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
@@ -2267,53 +2162,14 @@ hipError_t knn_filter_build_cells_from_host(FilterState &st, int k, long long n,
             e = knn_cells_fast_scatter(*st.cells, k, r_dev, r0, r1, compute);
         r0 = r1;
     }
-    // 4. cell prefix, placement, padding — and ONE synchronisation
-    unsigned hout[4] = {0, 0, 0, 0}, hres[4] = {0, 0, 0, 0};
+    // 4. cell prefix, placement, padding — and ONE synchronisation of both streams.  Not usable (a bucket overflowed, the
+    // sample was not representative): the caller builds from the resident rows.
     if (e == hipSuccess)
-        e = knn_cells_fast_finish(*st.cells, cell_fill, compute);
-    if (e == hipSuccess)
-        e = knn_cells_place_rows(st, r_dev, nullptr, cell_fill, dout, ocap, compute);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(hout, dout, sizeof hout, hipMemcpyDeviceToHost, compute);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(hres, st.cells->build_res, sizeof hres, hipMemcpyDeviceToHost, compute);
-    const hipError_t e1 = hipStreamSynchronize(copy), e2 = hipStreamSynchronize(compute);
-    lap("streams drained");
-    if (e == hipSuccess)
-        e = e1 != hipSuccess ? e1 : e2;
+        e = knn_cells_fast_finish(*st.cells, stg.fill, compute);
+    bool overflow = false;
+    e = cells_finish(st, stg, e, r_dev, dout, cuts.data(), samples / 4, compute, tr, &overflow, copy);
     for (hipEvent_t ev : events)
         (void)hipEventDestroy(ev);
-    (void)KNN_DEV_FREE(cell_fill);
-    (void)KNN_DEV_FREE(st.cells->tmp_rows);
-    (void)KNN_DEV_FREE(st.cells->tmp_meta);
-    (void)KNN_DEV_FREE(st.cells->bucket_start);
-    st.cells->tmp_rows = nullptr;
-    st.cells->tmp_meta = nullptr;
-    st.cells->bucket_start = nullptr;
-    st.cells->bucket_fill = nullptr;
-    st.cells->build_res = nullptr;
-    (void)KNN_DEV_FREE(dout);
-    if (trace)
-        fprintf(stderr, "[knn ingest] fast build under the copy: %u tiles (room for %lld), %u items, largest cell %u rows, overflow %u, outside the box %u\n",
-                hres[0], ntiles, hres[1], hres[2], hres[3], hout[3]);
-    if (e != hipSuccess) {
-        knn_filter_free(st);
-        return e;
-    }
-    if (hres[3] != 0u || hres[1] == 0u || hout[2] != 0u || hout[3] > ocap) {   // the caller builds from the resident rows
-        knn_filter_free(st);
-        return hipSuccess;
-    }
-    st.ntiles = hres[0];
-    st.cells->nitems = hres[1];
-    st.cells->max_cell_rows = hres[2];
-    st.n_outliers = hout[3];
-    memcpy(&st.bmax, &hout[0], 4);
-    memcpy(&st.nmax, &hout[1], 4);
-    st.usable = true;
-    e = knn_cells_maybe_recentre(st, r_dev, cut_samp.data(), samples / 4, compute);
-    if (e != hipSuccess)
-        knn_filter_free(st);
     return e;
 }
 

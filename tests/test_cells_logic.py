@@ -65,7 +65,7 @@ def test_cell_lower_bound_never_exceeds_the_distance(kind, k, bins):
 
 def test_cell_code_layout_matches_the_build_rules():
     """bits per dimension = B / k rounded up for the first B % k dimensions; the low pruning table ends at the last
-    dimension boundary at or below bit 8 and must cover >= 64 entries (knn_cells_build)."""
+    dimension boundary at or below bit 8 and must cover >= 64 entries (knn_cells_plan)."""
     def plan(k, bits):
         nb = [bits // k + (1 if d < bits % k else 0) for d in range(k)]
         pos, sa, shift = 0, 0, []

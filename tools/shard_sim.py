@@ -25,7 +25,7 @@ import time
 import numpy as np
 
 K = 16
-ROWS_MIN = 144          # knn_cells_build: cells of 144 .. 288 rows
+ROWS_MIN = 144          # knn_cells_plan: cells of 144 .. 288 rows
 DUP_SLACK = 1.012       # what the fp16 error band adds to the seed's squared distance (~1 %)
 
 
