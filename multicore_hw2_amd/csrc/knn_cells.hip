@@ -1736,6 +1736,9 @@ __global__ __launch_bounds__(64 * (KT == 1 && !CTR ? CELL_SCAN_WAVES : CELL_SCAN
     constexpr int TPP = CELL_TILES_PER_PASS;                         // reference tiles a wave holds in registers at a time
     constexpr int SW = KT == 1 && !CTR ? CELL_SCAN_WAVES : CELL_SCAN_WAVES_KT2;   // waves of a block
     constexpr int QB = CTR ? 64 : 32 * KT;                              // bytes of a query in LDS (CTR: its fp32 row, 16 dimensions)
+    // the bin-frame 8-bit scan with the counter deal: an item's list words and w_c are requested with its tiles and first
+    // waited for behind them — one round trip per item (see l0 below)
+    constexpr bool ONE_TRIP = DYN && U8 && !CTR && !SELF && KT == 1;
     h8 *s_qf = (h8 *)s_dyn;                                             // [m_padded / 32][KT][64]; CTR: float s_q32[m_padded][16]
     float *s_thr = (float *)(s_dyn + (size_t)m_padded * QB);            // [m_padded]
     f4v *s_nrm = (f4v *)(s_dyn + (size_t)m_padded * (QB + 4));          // [waves][TPP * 8]
@@ -1912,6 +1915,7 @@ __global__ __launch_bounds__(64 * (KT == 1 && !CTR ? CELL_SCAN_WAVES : CELL_SCAN
             // match kernel: the cell is then scored `dense`, against every query of the batch — what a list that long
             // asks for anyway — instead of sending the batch to the exact scan as round 2 did
             const bool dense = nq > cap;
+            const unsigned nq_room = min(nq, cap);   // entries of the list's room that hold queries (>= 1)
             if (dense) {
                 nq = (unsigned)m;
                 if (lane == 0)
@@ -1920,10 +1924,12 @@ __global__ __launch_bounds__(64 * (KT == 1 && !CTR ? CELL_SCAN_WAVES : CELL_SCAN
             const unsigned short *__restrict__ list = SELF ? my_list : lists + (size_t)cellj * cap;
             // the first two blocks of the list travel with the tiles (one round trip per cell)
             // (SELF: the list is in LDS — every block of 32 is read from there)
-            const unsigned l0 = SELF ? 0u : dense ? (unsigned)lane : (unsigned)list[min((unsigned)lane, nq - 1u)];
+            // (ONE_TRIP: read whether dense or not, inside the room, and the dense case taken where the words are used: a select
+            // here made the wave wait for l0 before it asked for l1, w_c and the tiles — three round trips per item, not one)
+            unsigned l0 = SELF ? 0u : ONE_TRIP ? (unsigned)list[min((unsigned)lane, nq_room - 1u)] : dense ? (unsigned)lane : (unsigned)list[min((unsigned)lane, nq - 1u)];
             // (round 3: blocks three and four of the list too — lists average 120 entries on the 2^21-row shards of an
             // 8-GPU run, and every block beyond the second was a dependent read from memory)
-            const unsigned l1 = SELF ? 0u : dense ? 64u + (unsigned)lane : (unsigned)list[min(64u + (unsigned)lane, nq - 1u)];
+            unsigned l1 = SELF ? 0u : ONE_TRIP ? (unsigned)list[min(64u + (unsigned)lane, nq_room - 1u)] : dense ? 64u + (unsigned)lane : (unsigned)list[min(64u + (unsigned)lane, nq - 1u)];
             float ccv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, c_scale = 0.f, c_ratio = 0.f, c_bmax = 0.f, c_nmax = 0.f, c_er = 0.f, th_kept = 0.f;
             h8 b_kept = {0, 0, 0, 0, 0, 0, 0, 0};
             h8 wc = {0, 0, 0, 0, 0, 0, 0, 0};   // bin frames: this lane's half of the cell's offset w_c
@@ -1964,6 +1970,8 @@ __global__ __launch_bounds__(64 * (KT == 1 && !CTR ? CELL_SCAN_WAVES : CELL_SCAN
                     f4v n1 = {0.f, 0.f, 0.f, 0.f};
                     if constexpr (TPP * 8 > 64)
                         n1 = 64 + lane < nt * 8 ? __builtin_nontemporal_load(&rn4[64 + lane]) : (f4v){0.f, 0.f, 0.f, 0.f};
+                    if constexpr (ONE_TRIP)   // first used here, behind the pass's loads: nothing hoists a use (the w_c widening,
+                        __asm__ volatile("" : "+v"(l0), "+v"(l1), "+v"(wc));   // a lane select) in front of them
                     __builtin_amdgcn_wave_barrier();   // the previous pass's reads of the window are done
                     if (TPP * 8 >= 64 || lane < TPP * 8)
                         my_nrm[lane] = n0;
@@ -1987,6 +1995,8 @@ __global__ __launch_bounds__(64 * (KT == 1 && !CTR ? CELL_SCAN_WAVES : CELL_SCAN
                     } else {
                         qid = dense ? (valid ? idx : 0u) : (unsigned)list[valid ? idx : 0u];
                     }
+                    if constexpr (ONE_TRIP)   // (l0 / l1 are list words even for a dense cell)
+                        qid = dense ? (valid ? idx : 0u) : qid;
                     h8 b[KT];
                     float th;
                     if constexpr (CTR) {
