@@ -365,6 +365,13 @@ int knn_debug_scan_plan(int num_cu, int blocks_per_cu, unsigned nitems, int m, l
 /* The same with the list maker named: self_lists != 0 = the scan's waves list their own items (option "cells_lists" 2): the
  * dynamic LDS then also holds the batch's Dup values and one list room per wave. */
 int knn_debug_scan_plan_ex(int num_cu, int blocks_per_cu, unsigned nitems, int m, int self_lists, long long out[8]);
+/* Test hook (host arithmetic only, no GPU needed): every choice and size one batch of the cell-pruned query launches with.
+ * in = {k, kt, centred, rows_u8, ncells, nitems, cap, several_slots, scan_blocks, scan_deal, cells_lists, m, num_cu, rec_cap};
+ * out = {prep: PW, KT, CTR; self_lists; match: waves (0 none), stage, dynamic LDS; the scan's form: DYN, K, SELF, KT, CTR,
+ * NIF, U8; its grid: blocks, waves, record lists, records per list, overflow base, overflow capacity, dynamic LDS; list_cap;
+ * tail: K, KT, blocks; 1 if the gated exact scan is a launch of its own; the LDS limits of the scan and the match kernel
+ * (0: the default)}. */
+int knn_debug_cells_query_plan(const long long in[14], long long out[28]);
 
 /* Test hook for the filter's error bound: raw MFMA filter scores S[m][n_local] (row-major,
  * device) for a query batch, the fp32 squared norms M[m] of the fp16 query rows (device), and

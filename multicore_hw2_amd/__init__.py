@@ -28,7 +28,7 @@ EXPORTED_SYMBOLS = [
     "knn_index_query_host", "knn_set_option", "knn_get_option", "knn_index_last_stats",
     "knn_synth_fill_device", "knn_index_timing", "knn_index_timing_read",
     "knn_debug_filter_scores", "knn_index_query_keys_slot", "knn_trim", "knn_keys_allreduce_min",
-    "knn_index_query_keys_ex", "knn_index_debug_counters", "knn_debug_scan_plan", "knn_debug_scan_plan_ex", "knn_debug_shard_policy", "knn_debug_plan_shard", "knn_debug_u8_row", "knn_debug_u8_bin_row", "knn_debug_u8_bin_threshold", "knn_index_query",
+    "knn_index_query_keys_ex", "knn_index_debug_counters", "knn_debug_scan_plan", "knn_debug_scan_plan_ex", "knn_debug_cells_query_plan", "knn_debug_shard_policy", "knn_debug_plan_shard", "knn_debug_u8_row", "knn_debug_u8_bin_row", "knn_debug_u8_bin_threshold", "knn_index_query",
     "knn_geom_create", "knn_geom_destroy", "knn_geom_info", "knn_geom_assign", "knn_index_create_sharded",
     "knn_index_seed_export", "knn_index_seed_attach", "knn_geom_first_cell",
     "knn_index_query_topk", "knn_keys_topk_merge", "knn_index_query_topk_host",
@@ -143,6 +143,25 @@ def debug_scan_plan(num_cu, blocks_per_cu, nitems, m, self_lists=False):
     f.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_longlong)]
     _check(f(int(num_cu), int(blocks_per_cu), int(nitems), int(m), 1 if self_lists else 0, out))
     return dict(zip(("blocks", "nlists", "slice", "ovf_base", "ovf_cap", "lds_bytes", "rec_cap", "max_lists"), list(out)))
+
+
+CELLS_QUERY_INPUTS = ("k", "kt", "centred", "rows_u8", "ncells", "nitems", "cap", "several_slots", "scan_blocks", "scan_deal",
+                      "cells_lists", "m", "num_cu", "rec_cap")
+CELLS_QUERY_PLAN = ("prep_pw", "prep_kt", "prep_ctr", "self_lists", "match_waves", "stage", "match_lds",
+                    "scan_dyn", "scan_k", "scan_self", "scan_kt", "scan_ctr", "scan_nif", "scan_u8",
+                    "blocks", "waves", "nlists", "slice", "ovf_base", "ovf_cap", "lds_bytes", "list_cap",
+                    "tail_k", "tail_kt", "tail_blocks", "exact_launch", "scan_lds_limit", "match_lds_limit")
+
+
+def debug_cells_query_plan(**inputs):
+    """knn_debug_cells_query_plan: every choice and size one batch of the cell-pruned query launches with, for the inputs
+    named in CELLS_QUERY_INPUTS (host arithmetic; works without a GPU)."""
+    vin = (ctypes.c_longlong * len(CELLS_QUERY_INPUTS))(*[int(inputs[n]) for n in CELLS_QUERY_INPUTS])
+    out = (ctypes.c_longlong * len(CELLS_QUERY_PLAN))()
+    f = lib().knn_debug_cells_query_plan
+    f.argtypes = [ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)]
+    _check(f(vin, out))
+    return dict(zip(CELLS_QUERY_PLAN, list(out)))
 
 
 def debug_plan_shard(k, m, rows):

@@ -1186,6 +1186,37 @@ int knn_debug_scan_plan_ex(int num_cu, int blocks_per_cu, unsigned nitems, int m
     return KNN_OK;
 }
 
+int knn_debug_cells_query_plan(const long long in[14], long long out[28])
+{
+    if (!in || !out || in[0] < 1 || in[0] > 32 || in[1] < 1 || in[1] > 2 || in[4] < 1 || in[11] < 1 || in[11] > KNN_CELL_BATCH ||
+        in[12] < 1)
+        return fail(KNN_EINVAL, "knn_debug_cells_query_plan: bad arguments");
+    CellQueryInputs ci;
+    ci.k = (int)in[0];
+    ci.kt = (int)in[1];
+    ci.centred = in[2] != 0;
+    ci.rows_u8 = in[3] != 0;
+    ci.ncells = (unsigned)in[4];
+    ci.nitems = (unsigned)in[5];
+    ci.cap = (unsigned)in[6];
+    ci.several_slots = in[7] != 0;
+    ci.scan_blocks = (int)in[8];
+    ci.scan_deal = (int)in[9];
+    ci.cells_lists = (int)in[10];
+    ci.m = (int)in[11];
+    ci.num_cu = (int)in[12];
+    ci.rec_cap = (unsigned)in[13];
+    const CellQueryPlan p = knn_cells_query_plan(ci);
+    const CellScanForm &f = p.scan;
+    const long long v[28] = {p.prep_pw, p.prep_kt, p.prep_ctr, p.self_lists, p.match_waves, p.stage, (long long)p.match_lds,
+                             f.dyn, f.k, f.self, f.kt, f.ctr, f.nif, f.u8,
+                             p.grid.blocks, p.grid.waves, p.grid.nlists, p.grid.slice, p.grid.ovf_base, p.grid.ovf_cap,
+                             (long long)p.grid.lds_bytes, p.list_cap, p.tail_k, p.tail_kt, p.tail_blocks, p.exact_launch,
+                             (long long)p.scan_lds_limit, (long long)p.match_lds_limit};
+    memcpy(out, v, sizeof v);
+    return KNN_OK;
+}
+
 int knn_keys_to_indices(int device, const unsigned long long *keys_dev, int m, int *out_dev,
                         void *stream)
 {

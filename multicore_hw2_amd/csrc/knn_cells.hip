@@ -9,6 +9,8 @@
 #include <stdlib.h>
 #include <algorithm>
 #include <atomic>
+#include <mutex>
+#include <set>
 #include <type_traits>
 #include <vector>
 
@@ -3364,7 +3366,136 @@ void knn_cells_workspace_free(FilterWorkspace &w)
 
 // ---- per batch ---------------------------------------------------------------------------------
 
-static hipError_t ensure_cells_workspace(FilterState &st, FilterWorkspace &w, int m)
+// The dynamic-LDS limit is an attribute of the function on the device, not of a launch: a variant that may ask for more than the
+// default gets the most it can ask for (the plan's limit) once per device, before its first launch there.  (Set per launch to the
+// batch's own size, another thread's set could lower it between that set and that launch.)
+static hipError_t cells_lds_limit(const void *fn, size_t limit)
+{
+    if (!limit)
+        return hipSuccess;
+    int dev = 0;
+    FTRY(hipGetDevice(&dev));
+    static std::mutex mu;
+    static std::set<std::pair<int, const void *>> done;
+    std::lock_guard<std::mutex> lock(mu);
+    if (!done.count({dev, fn})) {
+        FTRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)limit));
+        done.insert({dev, fn});
+    }
+    return hipSuccess;
+}
+
+// What the launches of one batch read: the index, the slot's workspace, the plan and the call's arguments.
+struct CellBatch {
+    const FilterState &st;
+    const CellIndex &c;
+    const FilterWorkspace &w;
+    const CellQueryPlan &p;
+    int m, m_padded;
+    const float *q, *r;
+    long long base;
+    u64 *keys, *keys_init;
+    CellFinal fin;
+    CellSelf self;
+    SeedLayer layer;
+    unsigned *ctl_next;
+    hipStream_t s;
+};
+
+struct CellKernel {   // a kernel the plan picked: its launch for a batch, and the kernel itself (for its attributes)
+    void (*launch)(const CellBatch &);
+    const void *fn;
+};
+
+// (SD = 2, four seed cells; cell-range shards take the same four — those of another rank through the seed layer.  Sixteen seed
+// cells (SD = 4) leave 20 % fewer candidates, as the simulation said, and cost more than they save: the prep kernel is a chain
+// of dependent round trips, and at a rank's size the step is made of those — emulated rank of N = 8, ms per step / one
+// batch at a time: 16 cells x 2 tiles 0.0302 / 0.0526, 8 x 2 0.0279 / 0.0493, 4 x 2 0.0275 / 0.0471, 4 x 4 0.0271 / 0.0473;
+// N = 4: 0.0432 / 0.0423 / 0.0414 / 0.0408.  profiles/r04_seed_sweep.txt)
+template <int PW, int KT, bool CTR>
+static void cells_prep_as(const CellBatch &b)
+{
+    const FilterState &st = b.st;
+    hipLaunchKernelGGL((knn_cells_prep_kernel<PW, 2, KT, CTR>), dim3((unsigned)b.m_padded), dim3(64 * PW), 0, b.s, b.q, b.m, b.m_padded,
+                       cell_geom_of(b.c, st.k), b.c.bounds, (double)st.sigma * (double)st.sigma, st.center, st.sigma, b.c.tile_start,
+                       st.ntiles, (const h8 *)st.ref_frags, st.ref_norms2, b.layer, (h8 *)b.w.qry_frags, b.w.lo_tab, b.w.hi_tab, st.bmax,
+                       st.nmax, kAmaxLimit, b.w.thr, b.w.dup, b.w.ctl_cur, b.ctl_next, b.w.counts, b.w.nlists, b.keys_init,
+                       b.p.self_lists ? 1 : 0, b.c.cell_frame, b.c.tile_cell);
+}
+static void cells_prep_launch(const CellBatch &b)
+{
+    const bool two = b.p.prep_pw == 2;
+    if (b.p.prep_ctr)
+        (two ? cells_prep_as<2, 1, true> : cells_prep_as<4, 1, true>)(b);
+    else if (b.p.prep_kt == 2)
+        (two ? cells_prep_as<2, 2, false> : cells_prep_as<4, 2, false>)(b);
+    else
+        (two ? cells_prep_as<2, 1, false> : cells_prep_as<4, 1, false>)(b);
+}
+
+template <int WAVES>
+static CellKernel cells_match_of()
+{
+    return {[](const CellBatch &b) {
+                hipLaunchKernelGGL(knn_cells_match_kernel<WAVES>, dim3(b.c.ncells / 64u), dim3(64 * WAVES), b.p.match_lds, b.s, b.w.lo_tab,
+                                   b.w.hi_tab, b.w.dup, b.m, b.m_padded, cell_geom_of(b.c, b.st.k), b.c.ncells, b.c.cap, b.w.cell_lists,
+                                   b.w.cell_counts, b.w.ctl_cur, b.p.stage);
+            },
+            (const void *)knn_cells_match_kernel<WAVES>};
+}
+static CellKernel cells_match_kernel(int waves)
+{
+    return waves == 16 ? cells_match_of<16>() : cells_match_of<8>();
+}
+
+template <bool DYN, int K, bool SELF, int KT = 1, bool CTR = false, bool NIF = false, bool U8 = false>
+static CellKernel cells_scan_of()
+{
+    return {[](const CellBatch &b) {
+                const CellIndex &c = b.c;
+                const FilterWorkspace &w = b.w;
+                hipLaunchKernelGGL((knn_cells_scan_kernel<DYN, K, SELF, KT, CTR, NIF, U8>), dim3(b.p.grid.blocks), dim3(64 * b.p.grid.waves),
+                                   b.p.grid.lds_bytes, b.s, U8 ? (const h8 *)c.rows8 : (const h8 *)b.st.ref_frags, U8 ? c.norms8 : b.st.ref_norms,
+                                   c.items, c.nitems, (const h8 *)w.qry_frags, w.thr, b.m, b.m_padded, w.cell_counts, w.cell_lists,
+                                   b.p.list_cap, w.records, w.counts, w.ctl_cur, w.slice, w.ovf_base, w.ovf_cap, b.q, b.r, b.st.k, c.perm,
+                                   b.st.ntiles * 32, b.base, b.keys, b.fin, b.self);
+            },
+            (const void *)knn_cells_scan_kernel<DYN, K, SELF, KT, CTR, NIF, U8>};
+}
+// The scan's forms (knn_cells_query_plan picks one): the 20 instantiations of knn_cells_scan_kernel.
+static CellKernel cells_scan_kernel(const CellScanForm &f)
+{
+    const bool k16 = f.k == 16;
+    if (f.u8)
+        return f.ctr ? (k16 ? cells_scan_of<true, 16, false, 1, true, false, true>() : cells_scan_of<true, 0, false, 1, true, false, true>())
+                     : (k16 ? cells_scan_of<true, 16, false, 1, false, false, true>() : cells_scan_of<true, 0, false, 1, false, false, true>());
+    if (f.ctr)
+        return f.dyn ? (k16 ? cells_scan_of<true, 16, false, 1, true>() : cells_scan_of<true, 0, false, 1, true>())
+                     : (k16 ? cells_scan_of<false, 16, false, 1, true>() : cells_scan_of<false, 0, false, 1, true>());
+    if (f.kt == 2)
+        return f.nif ? (f.dyn ? cells_scan_of<true, 0, false, 2, false, true>() : cells_scan_of<false, 0, false, 2, false, true>())
+                     : (f.dyn ? cells_scan_of<true, 0, false, 2>() : cells_scan_of<false, 0, false, 2>());
+    if (f.self)
+        return f.dyn ? (k16 ? cells_scan_of<true, 16, true>() : cells_scan_of<true, 0, true>())
+                     : (k16 ? cells_scan_of<false, 16, true>() : cells_scan_of<false, 0, true>());
+    return f.dyn ? (k16 ? cells_scan_of<true, 16, false>() : cells_scan_of<true, 0, false>())
+                 : (k16 ? cells_scan_of<false, 16, false>() : cells_scan_of<false, 0, false>());
+}
+
+template <int K, int KT = 1>
+static void cells_tail_as(const CellBatch &b)
+{
+    const FilterWorkspace &w = b.w;
+    hipLaunchKernelGGL((knn_cells_tail_kernel<K, KT>), dim3(b.p.tail_blocks), dim3(KNN_BLOCK), 0, b.s, b.q, b.r, b.st.k, b.m, b.st.n,
+                       b.st.ntiles * 32, b.base, b.c.items, b.c.nitems, w.cell_counts, w.cell_lists, b.p.list_cap, b.c.perm, w.records, w.ovf_base, w.ovf_cap,
+                       w.ctl_cur, b.keys, b.fin, w.counts, w.nlists, w.slice, b.self);
+}
+static void cells_tail_launch(const CellBatch &b)
+{
+    (b.p.tail_kt == 2 ? cells_tail_as<0, 2> : b.p.tail_k == 16 ? cells_tail_as<16> : b.p.tail_k == 8 ? cells_tail_as<8> : cells_tail_as<0>)(b);
+}
+
+static hipError_t ensure_cells_workspace(FilterState &st, FilterWorkspace &w, int m, const CellQueryPlan &p)
 {
     const CellIndex &c = *st.cells;
     if (!w.cell_counts)
@@ -3383,6 +3514,9 @@ static hipError_t ensure_cells_workspace(FilterState &st, FilterWorkspace &w, in
         FTRY(KNN_DEV_ALLOC((void **)&w.hi_tab, (size_t)m_padded * (size_t)((c.ncells + (1u << c.sa) - 1u) >> c.sa) * sizeof(float)));
         w.cell_m_cap = m_padded;
     }
+    FTRY(cells_lds_limit(cells_scan_kernel(p.scan).fn, p.scan_lds_limit));
+    if (p.match_waves)
+        FTRY(cells_lds_limit(cells_match_kernel(p.match_waves).fn, p.match_lds_limit));
     return hipSuccess;
 }
 
@@ -3411,8 +3545,8 @@ CellScanPlan knn_cells_scan_plan(int num_cu, int blocks_per_cu, unsigned nitems,
     p.ovf_base = rec_cap - p.ovf_cap;
     p.slice = p.ovf_base / p.nlists;
     // (16 < k <= 32: 64-byte B operands, 74 KiB for 1024 queries: with windows of nine 2-KiB tiles in registers (126 VGPRs) a CU
-    // holds ONE block, so that block has sixteen waves — four per SIMD; the launch raises the kernel's dynamic-LDS limit above
-    // the default 64 KiB.  Round 5, one box, ms per step at k 17 / 18 / 20, n 2^24: four tiles per pass, 12 waves, 96
+    // holds ONE block, so that block has sixteen waves — four per SIMD; the kernel's dynamic-LDS limit is raised above the
+    // default 64 KiB (cells_lds_limit).  Round 5, one box, ms per step at k 17 / 18 / 20, n 2^24: four tiles per pass, 12 waves, 96
     // registers 0.282 / 0.315 / 0.428; five 0.269 / 0.303 / 0.399; nine, 12 waves (3 per SIMD) 0.237 / 0.242 / 0.352)
     p.lds_bytes = (size_t)m_padded * ((centred ? 64 : 32 * kt) + 4) + (size_t)sw * CELL_TILES_PER_PASS * 8 * sizeof(f4v);   // (per-cell frames: the queries' fp32 rows)
     if (self_lists)   // the self-listing scan: the batch's Dup values + one list room per wave
@@ -3433,151 +3567,43 @@ bool knn_cells_lists_policy(unsigned ncells, bool several_slots)
     return !several_slots && ncells <= 8192u;
 }
 
-// One batch of <= KNN_CELL_BATCH queries, the whole chain: prep -> match -> scan (its waves re-rank their own records) ->
-// [rows outside the robust box, exactly] -> the exact scan of the shard, gated on FALLBACK -> the tail kernel (gated: records
-// in the shared area, the listed pairs exactly when that area is over-full, the finalisation when the scan could not do it).
-// Four launches on clean data at k = 16 (the exact scan of the shard is a branch of the tail kernel there), five otherwise.  out_idx (nullable): int32 indices of the batch, written by whichever block ends it.
-hipError_t knn_cells_query(FilterState &st, FilterWorkspace &w, int m, const float *q, const float *r, long long base,
-                           u64 *keys, int num_cu, bool timed, hipStream_t s, bool init_keys, int *out_idx)
+// What one batch launches and with which sizes, decided in one place (host arithmetic: nothing allocated or launched;
+// tests/test_cells_logic.py checks it on the CPU through knn_debug_cells_query_plan).
+CellQueryPlan knn_cells_query_plan(const CellQueryInputs &in)
 {
-    u64 *keys_init = init_keys ? keys : nullptr;
-    FTRY(ensure_cells_workspace(st, w, m));
-    const CellIndex &c = *st.cells;
-    const int m_padded = (m + 31) / 32 * 32;
-    const CellGeom g = cell_geom_of(c, st.k);
-    w.has_rows = false;
-    w.pieces = RerankPieces();
-    const double sigma2 = (double)st.sigma * (double)st.sigma;
+    CellQueryPlan p;
+    const int m_padded = (in.m + 31) / 32 * 32;
+    // prep: batches in flight side by side: two waves per query (two seed cells each) — half the registers the launch holds,
+    // 0.0421 -> 0.0408 ms per step at n_local 2^21 for 2 us more when a batch runs alone; else four waves per query
+    p.prep_pw = in.several_slots ? 2 : 4;
+    p.prep_kt = in.centred ? 1 : in.kt;
+    p.prep_ctr = in.centred;
     // scan grid: two blocks of CELL_SCAN_WAVES waves per CU fill every SIMD's registers (6 waves x 80) and give the shortest
     // launch — and leave nothing for the kernels of the next batch, so with batches in flight side by side the step was the
     // SUM of the kernels' durations.  One block per CU: the scan alone takes 10-20 % longer, the step of a shard of up to 2^14
     // cells 5-7 % less (0.0465 -> 0.0444 ms at 2^21 rows; at C3 the two are within 1 %: it keeps two).
     // (2^15 cells, n = 2^23: step 0.0795 -> 0.0777 with one, three runs each on one box; 2^16 cells, C3: 0.1237 -> 0.1223, not
     // worth the 8 % the launch itself gets longer)
-    const bool one_block = st.scan_blocks == 1 || (st.scan_blocks == 0 && st.several_slots && c.ncells <= 32768u);
+    const bool one_block = in.scan_blocks == 1 || (in.scan_blocks == 0 && in.several_slots && in.ncells <= 32768u);
     // Who makes the cells' lists of queries: knn_cells_match_kernel in a launch of its own (rounds 2-4), or the scan's waves
-    // for the items they take (round 5, cell_self_list).  Policy in knn_cells_lists_policy.
-    const bool centred = c.centred;   // per-cell frames (knn_cells_recentre): the centred prep and scan, lists from the match launch
-    const bool self_lists = st.kt == 1 && !centred && !c.rows_u8 && (st.cells_lists == 2 || (st.cells_lists == 0 && knn_cells_lists_policy(c.ncells, st.several_slots)));
-    const CellScanPlan plan = knn_cells_scan_plan(num_cu, one_block ? 1 : 2, c.nitems, w.rec_cap, m_padded, self_lists, st.kt, centred);
-    const unsigned gx = plan.blocks;
-    w.nlists = plan.nlists;
-    w.ovf_cap = plan.ovf_cap;
-    w.ovf_base = plan.ovf_base;
-    w.slice = plan.slice;
-
-    // the control words of this batch were cleared by the previous batch on this slot (or at allocation)
-    const unsigned parity = w.cell_batches++ & 1u;
-    w.ctl_cur = w.ctl + KNN_CTL_WORDS * (1u + parity);
-    unsigned *ctl_next = w.ctl + KNN_CTL_WORDS * (2u - parity);
-    // batches in flight side by side: two waves per query (two seed cells each) — half the registers the launch holds,
-    // 0.0421 -> 0.0408 ms per step at n_local 2^21 for 2 us more when a batch runs alone; else four waves per query
-    SeedLayer layer;
-    memset(&layer, 0, sizeof layer);
-    if (c.geom && c.seed_layer) {
-        layer.base = c.seed_layer;
-        layer.cpr = c.geom->cells_per_rank;
-        layer.tiles = (unsigned)c.geom->seed_tiles;
-        layer.nranks = (unsigned)c.geom->nranks;
-        for (int r_ = 0; r_ <= c.geom->nranks && r_ <= KNN_MAX_RANKS; ++r_)
-            layer.first[r_] = c.geom->first_cell(r_);
-        layer.part_bytes = c.geom->part_bytes();
-    }
-#define KNN_PREP_LAUNCH(PWV, SDV, ...)                                                                                     \
-    hipLaunchKernelGGL((knn_cells_prep_kernel<PWV, SDV, ##__VA_ARGS__>), dim3((unsigned)m_padded), dim3(64 * PWV), 0, s, q, m, m_padded, g, \
-                       c.bounds, sigma2, st.center, st.sigma, c.tile_start, st.ntiles, (const h8 *)st.ref_frags,            \
-                       st.ref_norms2, layer, (h8 *)w.qry_frags, w.lo_tab, w.hi_tab, st.bmax, st.nmax, kAmaxLimit, w.thr,    \
-                       w.dup, w.ctl_cur, ctl_next, w.counts, w.nlists, keys_init, self_lists ? 1 : 0, c.cell_frame, c.tile_cell)
-    // (cell-range shards take the same four seed cells — those of another rank through the seed layer.  Sixteen seed cells
-    // (SD = 4) leave 20 % fewer candidates, as the simulation said, and cost more than they save: the prep kernel is a chain
-    // of dependent round trips, and at a rank's size the step is made of those — emulated rank of N = 8, ms per step / one
-    // batch at a time: 16 cells x 2 tiles 0.0302 / 0.0526, 8 x 2 0.0279 / 0.0493, 4 x 2 0.0275 / 0.0471, 4 x 4 0.0271 / 0.0473;
-    // N = 4: 0.0432 / 0.0423 / 0.0414 / 0.0408.  profiles/r04_seed_sweep.txt)
-    if (centred) {
-        if (st.several_slots)
-            KNN_PREP_LAUNCH(2, 2, 1, true);
-        else
-            KNN_PREP_LAUNCH(4, 2, 1, true);
-    } else if (st.kt == 2) {
-        if (st.several_slots)
-            KNN_PREP_LAUNCH(2, 2, 2);
-        else
-            KNN_PREP_LAUNCH(4, 2, 2);
-    } else if (st.several_slots)
-        KNN_PREP_LAUNCH(2, 2, 1);
-    else
-        KNN_PREP_LAUNCH(4, 2, 1);
-#undef KNN_PREP_LAUNCH
-    FTRY(hipGetLastError());
-    if (self_lists) {
-        // no match launch: the scan's waves list their own items
-    } else {
+    // for the items they take (round 5, cell_self_list).  Policy in knn_cells_lists_policy.  Per-cell frames and 8-bit rows:
+    // lists from the match launch.
+    p.self_lists = in.kt == 1 && !in.centred && !in.rows_u8 &&
+                   (in.cells_lists == 2 || (in.cells_lists == 0 && knn_cells_lists_policy(in.ncells, in.several_slots)));
+    p.grid = knn_cells_scan_plan(in.num_cu, one_block ? 1 : 2, in.nitems, in.rec_cap, m_padded, p.self_lists, in.kt, in.centred);
+    p.list_cap = p.self_lists ? CELL_SELF_CAP : in.cap;
+    if (!p.self_lists) {
         // entries of a list assembled in LDS: k <= 16 the first 128 (16.6 KiB: four or five blocks per CU), 16 < k <= 32 the whole
         // list up to 640 entries (lists of 150-400 are the rule there)
         // (a rank of 8 of C3 — 2^13 cells, room for 1024 entries, lists of ~25 — on one box, ms per pipelined step: nothing staged (rounds
         // 2-5) 0.0290 / 0.0301, 128 entries 0.0266 / 0.0269, 256 entries 0.0274 / 0.0280)
-        const unsigned stage = st.kt == 1 ? std::min(c.cap, 128u) : c.cap <= CELL_MATCH_STAGED_CAP ? c.cap : 0u;
-        const size_t mlds = stage ? (size_t)64 * (stage + 2u) * sizeof(unsigned short) : 0;
-        if (c.ncells <= 16384u) {
-            if (mlds > (size_t)(48u << 10))   // (12-20 KiB of static LDS in front of it; the attribute is per device, so per launch)
-                FTRY(hipFuncSetAttribute((const void *)knn_cells_match_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlds));
-            hipLaunchKernelGGL(knn_cells_match_kernel<16>, dim3(c.ncells / 64u), dim3(64 * 16), mlds, s, w.lo_tab, w.hi_tab, w.dup, m,
-                               m_padded, g, c.ncells, c.cap, w.cell_lists, w.cell_counts, w.ctl_cur, stage);
-        } else {
-            if (mlds > (size_t)(48u << 10))
-                FTRY(hipFuncSetAttribute((const void *)knn_cells_match_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlds));
-            hipLaunchKernelGGL(knn_cells_match_kernel<8>, dim3(c.ncells / 64u), dim3(64 * 8), mlds, s, w.lo_tab, w.hi_tab, w.dup, m,
-                               m_padded, g, c.ncells, c.cap, w.cell_lists, w.cell_counts, w.ctl_cur, stage);
-        }
+        p.match_waves = in.ncells <= 16384u ? 16 : 8;
+        p.stage = in.kt == 1 ? std::min(in.cap, 128u) : in.cap <= CELL_MATCH_STAGED_CAP ? in.cap : 0u;
+        p.match_lds = p.stage ? (size_t)64 * (p.stage + 2u) * sizeof(unsigned short) : 0;
+        // (12-20 KiB of static LDS in front of it: a staged list of 16 < k <= 32 may ask for more than the default 48 KiB)
+        if (in.kt == 2)
+            p.match_lds_limit = (size_t)64 * (CELL_MATCH_STAGED_CAP + 2u) * sizeof(unsigned short);
     }
-    FTRY(hipGetLastError());
-    CellSelf self;
-    memset(&self, 0, sizeof self);
-    if (self_lists) {
-        self.lo_t = w.lo_tab;
-        self.hi = w.hi_tab;
-        self.dup = w.dup;
-        self.sa = c.sa;
-        self.m_padded = m_padded;
-    }
-    if (centred) {
-        self.dup = w.dup;
-        self.frame = c.cell_frame;
-        self.cell_u8 = c.rows_u8 ? c.cell_u8 : nullptr;
-    } else if (c.rows_u8) {   // 8-bit rows in bin frames
-        self.dup = w.dup;
-        self.binw = c.binw;
-        self.bin_ratio = c.bin_ratio;
-        self.bin_er = c.bin_er;
-        self.bin_nmax = c.bin_nmax;
-        self.bin_w1 = c.bin_w1;
-    }
-    const unsigned list_cap = self_lists ? CELL_SELF_CAP : c.cap;
-    static const bool trace_cells = getenv("KNN_MI355X_TRACE_CELLS") != nullptr;   // (read once: a query may run beside a thread that changes the environment)
-    if (trace_cells && !self_lists) {   // development aid: the lists of this batch and how evenly the scan's waves are loaded (synchronises)
-        std::vector<unsigned> hc((size_t)c.ncells), ht((size_t)c.ncells + 1);
-        FTRY(hipStreamSynchronize(s));
-        FTRY(hipMemcpy(hc.data(), w.cell_counts, hc.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
-        FTRY(hipMemcpy(ht.data(), c.tile_start, ht.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
-        std::vector<unsigned> sorted(hc);
-        std::sort(sorted.begin(), sorted.end());
-        const unsigned nwaves = w.nlists;
-        std::vector<double> wl((size_t)nwaves, 0.0);
-        double total = 0, biggest = 0;
-        for (unsigned cell = 0; cell < c.ncells; ++cell) {
-            const double steps = (double)((std::min(hc[cell], c.cap + 1u) + 31u) / 32u) * (double)(ht[cell + 1] - ht[cell]);
-            wl[cell % nwaves] += steps;   // (plain order: wave w takes cells w, w + nwaves, ...; the scan's scatter spreads them)
-            total += steps;
-            biggest = std::max(biggest, steps);
-        }
-        const double wmax = *std::max_element(wl.begin(), wl.end());
-        fprintf(stderr, "[knn cells] m %d: %u cells; list length min %u  p10 %u  median %u  p90 %u  max %u; tile steps %.0f in all, %.0f in the largest "
-                        "cell; %u waves: %.1f steps each on average, %.0f on the busiest\n", m, c.ncells, sorted.front(), sorted[sorted.size() / 10],
-                sorted[sorted.size() / 2], sorted[sorted.size() * 9 / 10], sorted.back(), total, biggest, nwaves, total / nwaves, wmax);
-    }
-    if (timed && w.ev_begin)
-        FTRY(hipEventRecord(w.ev_begin, s));
-    const size_t lds = plan.lds_bytes;
     // Items handed out inside the block (LDS counter, see the kernel) when batches come one at a time: the launch is as long as
     // its busiest wave, and evening the waves out takes 6-8 % off it (alone, ms: 0.0433 -> 0.0408 at 2^21 rows, 0.060 -> 0.055 at
     // 2^22, 0.1176 -> 0.1094 at C3; one batch at a time 0.0855 -> 0.0828, 0.102 -> 0.097, 0.1677 -> 0.160).  With batches in
@@ -3589,134 +3615,126 @@ hipError_t knn_cells_query(FilterState &st, FilterWorkspace &w, int m, const flo
     // shorter alone at C3, 0.1127 against 0.1169 ms between events — and with that it also gives the shorter PIPELINED step on
     // the large shards that keep two blocks per CU, 0.1188-0.1202 against 0.1197-0.1214; a rank of eight stays with the fixed
     // deal, 0.0258-0.0265 against 0.0266-0.0293)
-    const bool dyn = st.scan_deal == 2 ||
-                     (st.scan_deal == 0 && c.nitems >= 2u * w.nlists && (!st.several_slots || c.ncells > 32768u));
-    CellFinal fin;
-    fin.gids = c.gids;
-    fin.out_idx = out_idx;
-    fin.defer = st.n_outliers != 0u ? 1 : 0;
-    const long long npos = st.ntiles * 32;
-#define KNN_SCAN_LAUNCH(DYNV, KV, SELFV, ...)                                                                              \
-    hipLaunchKernelGGL((knn_cells_scan_kernel<DYNV, KV, SELFV, ##__VA_ARGS__>), dim3(gx), dim3(64 * plan.waves), lds, s, (const h8 *)st.ref_frags, \
-                       st.ref_norms, c.items, c.nitems, (const h8 *)w.qry_frags, w.thr, m, m_padded, w.cell_counts,        \
-                       w.cell_lists, list_cap, w.records, w.counts, w.ctl_cur, w.slice, w.ovf_base, w.ovf_cap, q, r, st.k, \
-                       c.perm, npos, base, keys, fin, self)
-#define KNN_SCAN_LAUNCH_K(DYNV, SELFV)                                                                                     \
-    do {                                                                                                                   \
-        if (st.k == 16)                                                                                                    \
-            KNN_SCAN_LAUNCH(DYNV, 16, SELFV);                                                                              \
-        else                                                                                                               \
-            KNN_SCAN_LAUNCH(DYNV, 0, SELFV);                                                                               \
-    } while (0)
-#define KNN_SCAN_LAUNCH_U8(DYNV, KV)   /* 8-bit rows in per-cell frames: the same LDS as KNN_SCAN_LAUNCH_K5 */                \
-    do {                                                                                                                   \
-        if (lds > (size_t)(64u << 10))                                                                                     \
-            FTRY(hipFuncSetAttribute((const void *)knn_cells_scan_kernel<DYNV, KV, false, 1, true, false, true>,           \
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                              \
-        hipLaunchKernelGGL((knn_cells_scan_kernel<DYNV, KV, false, 1, true, false, true>), dim3(gx), dim3(64 * plan.waves), lds, s, \
-                           (const h8 *)c.rows8, c.norms8, c.items, c.nitems, (const h8 *)w.qry_frags, w.thr, m, m_padded,  \
-                           w.cell_counts, w.cell_lists, list_cap, w.records, w.counts, w.ctl_cur, w.slice, w.ovf_base,    \
-                           w.ovf_cap, q, r, st.k, c.perm, npos, base, keys, fin, self);                                    \
-    } while (0)
-#define KNN_SCAN_LAUNCH_U8B(DYNV, KV)   /* 8-bit rows in bin frames: the one-frame scan's LDS */                            \
-    hipLaunchKernelGGL((knn_cells_scan_kernel<DYNV, KV, false, 1, false, false, true>), dim3(gx), dim3(64 * plan.waves), lds, s, \
-                       (const h8 *)c.rows8, c.norms8, c.items, c.nitems, (const h8 *)w.qry_frags, w.thr, m, m_padded,      \
-                       w.cell_counts, w.cell_lists, list_cap, w.records, w.counts, w.ctl_cur, w.slice, w.ovf_base,        \
-                       w.ovf_cap, q, r, st.k, c.perm, npos, base, keys, fin, self)
-#define KNN_SCAN_LAUNCH_K5(DYNV)   /* per-cell frames: 92 KiB of dynamic LDS for 1024 queries (their fp32 rows) */                  \
-    do {                                                                                                                   \
-        if (st.k == 16) {                                                                                                  \
-            if (lds > (size_t)(64u << 10))                                                                                 \
-                FTRY(hipFuncSetAttribute((const void *)knn_cells_scan_kernel<DYNV, 16, false, 1, true>,                    \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                          \
-            KNN_SCAN_LAUNCH(DYNV, 16, false, 1, true);                                                                     \
-        } else {                                                                                                           \
-            if (lds > (size_t)(64u << 10))                                                                                 \
-                FTRY(hipFuncSetAttribute((const void *)knn_cells_scan_kernel<DYNV, 0, false, 1, true>,                     \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                          \
-            KNN_SCAN_LAUNCH(DYNV, 0, false, 1, true);                                                                      \
-        }                                                                                                                  \
-    } while (0)
-    if (centred && c.rows_u8) {   // 8-bit rows in per-cell frames: items from the block's counter only (the fixed deal's form
-                                  // of this kernel needs 8 bytes of scratch under the 128-register cap)
-        if (st.k == 16)
-            KNN_SCAN_LAUNCH_U8(true, 16);
-        else
-            KNN_SCAN_LAUNCH_U8(true, 0);
-    } else if (c.rows_u8) {   // 8-bit rows in bin frames: the one-frame scan's two blocks of 12 waves per CU, items from the
-                              // block's counter (the fixed deal's form holds 8 bytes of scratch under the 80-register cap)
-        if (st.k == 16)
-            KNN_SCAN_LAUNCH_U8B(true, 16);
-        else
-            KNN_SCAN_LAUNCH_U8B(true, 0);
-    } else if (centred) {   // per-cell frames: lists from the match launch
-        if (dyn)
-            KNN_SCAN_LAUNCH_K5(true);
-        else
-            KNN_SCAN_LAUNCH_K5(false);
-    } else if (st.kt == 2 && st.k <= KNN_NIF_MAX_K) {   // 16 < k <= 30: run-time k, lists from the match launch, norms in the fragments
-        if (lds > (size_t)(64u << 10)) {   // (more than the default limit of dynamic LDS: say so, per launch — the attribute is per device)
-            if (dyn)
-                FTRY(hipFuncSetAttribute((const void *)knn_cells_scan_kernel<true, 0, false, 2, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            else
-                FTRY(hipFuncSetAttribute((const void *)knn_cells_scan_kernel<false, 0, false, 2, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        }
-        if (dyn)
-            KNN_SCAN_LAUNCH(true, 0, false, 2, false, true);
-        else
-            KNN_SCAN_LAUNCH(false, 0, false, 2, false, true);
-    } else if (st.kt == 2) {   // k 31, 32: no free K-slots — the norm window
-        if (lds > (size_t)(64u << 10)) {   // (more than the default limit of dynamic LDS: say so, per launch — the attribute is per device)
-            if (dyn)
-                FTRY(hipFuncSetAttribute((const void *)knn_cells_scan_kernel<true, 0, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            else
-                FTRY(hipFuncSetAttribute((const void *)knn_cells_scan_kernel<false, 0, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        }
-        if (dyn)
-            KNN_SCAN_LAUNCH(true, 0, false, 2);
-        else
-            KNN_SCAN_LAUNCH(false, 0, false, 2);
-    } else if (dyn) {
-        if (self_lists)
-            KNN_SCAN_LAUNCH_K(true, true);
-        else
-            KNN_SCAN_LAUNCH_K(true, false);
-    } else {
-        if (self_lists)
-            KNN_SCAN_LAUNCH_K(false, true);
-        else
-            KNN_SCAN_LAUNCH_K(false, false);
+    const bool dyn = in.scan_deal == 2 ||
+                     (in.scan_deal == 0 && in.nitems >= 2u * p.grid.nlists && (!in.several_slots || in.ncells > 32768u));
+    const int k16 = in.k == 16 ? 16 : 0;
+    if (in.rows_u8)   // 8-bit rows (per-cell or bin frames): items from the block's counter only — the fixed deal's form of this
+                      // kernel holds 8 bytes of scratch under the register cap (128 in per-cell frames; 80 for the one-frame
+                      // scan's two blocks of 12 waves per CU in bin frames)
+        p.scan = {true, k16, false, 1, in.centred, false, true};
+    else if (in.centred)   // per-cell frames: lists from the match launch
+        p.scan = {dyn, k16, false, 1, true, false, false};
+    else if (in.kt == 2)   // 16 < k <= 30: run-time k, norms in the fragments (NIF); k 31, 32: no free K-slots — the norm window
+        p.scan = {dyn, 0, false, 2, false, in.k <= KNN_NIF_MAX_K, false};
+    else
+        p.scan = {dyn, k16, p.self_lists, 1, false, false, false};
+    // the scan's LDS limit: what its form asks for at a full batch, when that is more than the default 64 KiB (per-cell frames,
+    // 16 < k <= 32)
+    const size_t full = knn_cells_scan_plan(in.num_cu, 1, in.nitems, in.rec_cap, KNN_CELL_BATCH, p.self_lists, in.kt, in.centred).lds_bytes;
+    p.scan_lds_limit = full > (size_t)(64u << 10) ? full : 0;
+    // gated on the device: the whole shard exactly when the batch has a query nothing bounds (k = 16: inside the tail kernel)
+    p.exact_launch = in.k != 16;
+    p.tail_k = in.kt == 1 && (in.k == 16 || in.k == 8) ? in.k : 0;
+    p.tail_kt = in.kt;
+    p.tail_blocks = (unsigned)in.num_cu * 8u;
+    if (p.tail_blocks * KNN_WAVES > in.nitems)
+        p.tail_blocks = std::max(2u, (in.nitems + KNN_WAVES - 1u) / KNN_WAVES);
+    return p;
+}
+
+// The scan's and the tail's CellSelf, according to the scan's form: the self-listing scan, per-cell frames, 8-bit rows in bin frames.
+static CellSelf cells_self(const CellQueryPlan &p, const CellIndex &c, const FilterWorkspace &w, int m_padded)
+{
+    if (p.self_lists)
+        return CellSelf{w.lo_tab, w.hi_tab, w.dup, c.sa, m_padded, nullptr, nullptr, nullptr, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (p.scan.ctr)
+        return CellSelf{nullptr, nullptr, w.dup, 0, 0, c.cell_frame, p.scan.u8 ? c.cell_u8 : nullptr, nullptr, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (p.scan.u8)
+        return CellSelf{nullptr, nullptr, w.dup, 0, 0, nullptr, nullptr, c.binw, c.bin_ratio, c.bin_er, c.bin_nmax, c.bin_w1};
+    return CellSelf{};
+}
+
+// Development aid (KNN_MI355X_TRACE_CELLS, read by tools/cells_trace.py): the lists of this batch and how evenly the scan's
+// waves are loaded.  Synchronises.
+static hipError_t cells_trace_lists(const CellIndex &c, const FilterWorkspace &w, int m, hipStream_t s)
+{
+    std::vector<unsigned> hc((size_t)c.ncells), ht((size_t)c.ncells + 1);
+    FTRY(hipStreamSynchronize(s));
+    FTRY(hipMemcpy(hc.data(), w.cell_counts, hc.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+    FTRY(hipMemcpy(ht.data(), c.tile_start, ht.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+    std::vector<unsigned> sorted(hc);
+    std::sort(sorted.begin(), sorted.end());
+    const unsigned nwaves = w.nlists;
+    std::vector<double> wl((size_t)nwaves, 0.0);
+    double total = 0, biggest = 0;
+    for (unsigned cell = 0; cell < c.ncells; ++cell) {
+        const double steps = (double)((std::min(hc[cell], c.cap + 1u) + 31u) / 32u) * (double)(ht[cell + 1] - ht[cell]);
+        wl[cell % nwaves] += steps;   // (plain order: wave w takes cells w, w + nwaves, ...; the scan's scatter spreads them)
+        total += steps;
+        biggest = std::max(biggest, steps);
     }
-#undef KNN_SCAN_LAUNCH_U8B
-#undef KNN_SCAN_LAUNCH_K5
-#undef KNN_SCAN_LAUNCH_K
-#undef KNN_SCAN_LAUNCH
+    const double wmax = *std::max_element(wl.begin(), wl.end());
+    fprintf(stderr, "[knn cells] m %d: %u cells; list length min %u  p10 %u  median %u  p90 %u  max %u; tile steps %.0f in all, %.0f in the largest "
+                    "cell; %u waves: %.1f steps each on average, %.0f on the busiest\n", m, c.ncells, sorted.front(), sorted[sorted.size() / 10],
+            sorted[sorted.size() / 2], sorted[sorted.size() * 9 / 10], sorted.back(), total, biggest, nwaves, total / nwaves, wmax);
+    return hipSuccess;
+}
+
+// One batch of <= KNN_CELL_BATCH queries, the whole chain: prep -> match -> scan (its waves re-rank their own records) ->
+// [rows outside the robust box, exactly] -> the exact scan of the shard, gated on FALLBACK -> the tail kernel (gated: records
+// in the shared area, the listed pairs exactly when that area is over-full, the finalisation when the scan could not do it).
+// Four launches on clean data at k = 16 (the exact scan of the shard is a branch of the tail kernel there), five otherwise.  out_idx (nullable): int32 indices of the batch, written by whichever block ends it.
+hipError_t knn_cells_query(FilterState &st, FilterWorkspace &w, int m, const float *q, const float *r, long long base,
+                           u64 *keys, int num_cu, bool timed, hipStream_t s, bool init_keys, int *out_idx)
+{
+    const CellIndex &c = *st.cells;
+    const CellQueryPlan p = knn_cells_query_plan({st.k, st.kt, c.centred, c.rows_u8, c.ncells, c.nitems, c.cap, st.several_slots,
+                                                  st.scan_blocks, st.scan_deal, st.cells_lists, m, num_cu, w.rec_cap});
+    FTRY(ensure_cells_workspace(st, w, m, p));
+    const int m_padded = (m + 31) / 32 * 32;
+    w.has_rows = false;
+    w.pieces = RerankPieces();
+    w.nlists = p.grid.nlists;
+    w.ovf_cap = p.grid.ovf_cap;
+    w.ovf_base = p.grid.ovf_base;
+    w.slice = p.grid.slice;
+
+    // the control words of this batch were cleared by the previous batch on this slot (or at allocation)
+    const unsigned parity = w.cell_batches++ & 1u;
+    w.ctl_cur = w.ctl + KNN_CTL_WORDS * (1u + parity);
+    unsigned *ctl_next = w.ctl + KNN_CTL_WORDS * (2u - parity);
+    SeedLayer layer;
+    memset(&layer, 0, sizeof layer);
+    if (c.geom && c.seed_layer) {
+        layer.base = c.seed_layer;
+        layer.cpr = c.geom->cells_per_rank;
+        layer.tiles = (unsigned)c.geom->seed_tiles;
+        layer.nranks = (unsigned)c.geom->nranks;
+        for (int r_ = 0; r_ <= c.geom->nranks && r_ <= KNN_MAX_RANKS; ++r_)
+            layer.first[r_] = c.geom->first_cell(r_);
+        layer.part_bytes = c.geom->part_bytes();
+    }
+    const CellBatch b{st, c, w, p, m, m_padded, q, r, base, keys, init_keys ? keys : nullptr,
+                      CellFinal{c.gids, out_idx, st.n_outliers != 0u ? 1 : 0}, cells_self(p, c, w, m_padded), layer, ctl_next, s};
+    cells_prep_launch(b);
+    FTRY(hipGetLastError());
+    if (p.match_waves)
+        cells_match_kernel(p.match_waves).launch(b);
+    FTRY(hipGetLastError());
+    static const bool trace_cells = getenv("KNN_MI355X_TRACE_CELLS") != nullptr;   // (read once: a query may run beside a thread that changes the environment)
+    if (trace_cells && !p.self_lists)
+        FTRY(cells_trace_lists(c, w, m, s));
+    if (timed && w.ev_begin)
+        FTRY(hipEventRecord(w.ev_begin, s));
+    cells_scan_kernel(p.scan).launch(b);
     FTRY(hipGetLastError());
     if (timed && w.ev_end)
         FTRY(hipEventRecord(w.ev_end, s));
     // rows outside the robust box never entered the layouts: exact scan of that (short) list
     FTRY(knn_exact_gather_launch(st.k, m, st.n_outliers, base, q, r, st.outliers, keys, num_cu, nullptr, s));
-    // gated on the device: the whole shard exactly when the batch has a query nothing bounds (k = 16: inside the tail kernel)
-    if (st.k != 16)
+    if (p.exact_launch)
         FTRY(knn_exact_launch(st.k, m, st.n, base, q, r, keys, num_cu, w.ctl_cur + KNN_CTL_FALLBACK, s));
-    {
-        unsigned blocks = (unsigned)num_cu * 8u;
-        if (blocks * KNN_WAVES > c.nitems)
-            blocks = std::max(2u, (c.nitems + KNN_WAVES - 1u) / KNN_WAVES);
-#define KNN_TAIL_LAUNCH(...)                                                                                               \
-    hipLaunchKernelGGL((knn_cells_tail_kernel<__VA_ARGS__>), dim3(blocks), dim3(KNN_BLOCK), 0, s, q, r, st.k, m, st.n, npos, base, c.items,  \
-                       c.nitems, w.cell_counts, w.cell_lists, list_cap, c.perm, w.records, w.ovf_base, w.ovf_cap, w.ctl_cur, \
-                       keys, fin, w.counts, w.nlists, w.slice, self)
-        if (st.kt == 2)
-            KNN_TAIL_LAUNCH(0, 2);
-        else
-            switch (st.k) {
-            case 16: KNN_TAIL_LAUNCH(16); break;
-            case 8: KNN_TAIL_LAUNCH(8); break;
-            default: KNN_TAIL_LAUNCH(0); break;
-            }
-#undef KNN_TAIL_LAUNCH
-    }
+    cells_tail_launch(b);
     return hipGetLastError();
 }
 

@@ -319,6 +319,39 @@ struct CellScanPlan {
 CellScanPlan knn_cells_scan_plan(int num_cu, int blocks_per_cu, unsigned nitems, unsigned rec_cap, int m_padded,
                                  bool self_lists = false, int kt = 1, bool centred = false);
 bool knn_cells_lists_policy(unsigned ncells, bool several_slots);
+// Every choice and size one batch of the cell-pruned query launches with (knn_cells_query_plan; host arithmetic only).
+struct CellQueryInputs {
+    int k = 0, kt = 1;
+    bool centred = false, rows_u8 = false;      // per-cell frames; 8-bit rows (in bin frames when not centred)
+    unsigned ncells = 0, nitems = 0, cap = 0;   // the index's cells, work items and room per list of queries
+    bool several_slots = false;
+    int scan_blocks = 0, scan_deal = 0, cells_lists = 0;   // the options (FilterState)
+    int m = 0, num_cu = 0;
+    unsigned rec_cap = 0;
+};
+struct CellScanForm {   // knn_cells_scan_kernel<dyn, k, self, kt, ctr, nif, u8>; u8: it reads the 8-bit rows
+    bool dyn = false;
+    int k = 0;
+    bool self = false;
+    int kt = 1;
+    bool ctr = false, nif = false, u8 = false;
+};
+struct CellQueryPlan {
+    int prep_pw = 4, prep_kt = 1;   // knn_cells_prep_kernel<pw, 2, kt, ctr>
+    bool prep_ctr = false;
+    bool self_lists = false;        // the scan's waves list their own items: no match launch
+    int match_waves = 0;            // knn_cells_match_kernel<16> or <8>; 0 with self_lists
+    unsigned stage = 0;             // entries of a list the match kernel assembles in LDS
+    size_t match_lds = 0;
+    CellScanForm scan;
+    CellScanPlan grid;              // the scan's grid, record lists and LDS
+    unsigned list_cap = 0;
+    int tail_k = 0, tail_kt = 1;    // knn_cells_tail_kernel<k, kt>
+    unsigned tail_blocks = 0;
+    bool exact_launch = false;      // the gated exact scan of the shard is a launch of its own (k != 16)
+    size_t scan_lds_limit = 0, match_lds_limit = 0;   // the variants' dynamic-LDS attribute (0: the default)
+};
+CellQueryPlan knn_cells_query_plan(const CellQueryInputs &in);
 hipError_t knn_cells_place_rows(FilterState &st, const float *r_dev, const unsigned *code, unsigned *fill, unsigned *out,
                                 unsigned ocap, hipStream_t s);
 void knn_cells_free(CellIndex *&c);

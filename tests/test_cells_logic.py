@@ -153,6 +153,154 @@ def test_scan_plan_refuses_batches_longer_than_one_pass():
             pkg.debug_scan_plan(*bad)
 
 
+# ---- the query plan (knn_cells_query_plan: every choice and size one batch of the pruned query launches with) ------------
+CELL_SCAN_WAVES_KT2, CELL_SELF_CAP, CELL_MATCH_STAGED_CAP, KNN_WAVES, KNN_CELL_BATCH = 16, 256, 640, 4, 1024
+SCAN_STATIC_LDS, MATCH_STATIC_LDS = 3200, 14352      # the kernels' largest static LDS as compiled (the counter deal's tables; match<16>)
+LDS_PER_CU = 160 * 1024
+# the instantiations the code object holds: knn_cells_scan_kernel<DYN, K, SELF, KT, CTR, NIF, U8>, knn_cells_prep_kernel<PW, 2, KT,
+# CTR>, knn_cells_match_kernel<WAVES>, knn_cells_tail_kernel<K, KT>
+SCAN_FORMS = ({(d, kk, s, 1, 0, 0, 0) for d in (0, 1) for kk in (0, 16) for s in (0, 1)} |
+              {(d, kk, 0, 1, 1, 0, 0) for d in (0, 1) for kk in (0, 16)} |
+              {(d, 0, 0, 2, 0, nif, 0) for d in (0, 1) for nif in (0, 1)} |
+              {(1, kk, 0, 1, ctr, 0, 1) for kk in (0, 16) for ctr in (0, 1)})
+PREP_FORMS = {(pw, kt, ctr) for pw in (2, 4) for kt, ctr in ((1, 0), (2, 0), (1, 1))}
+MATCH_FORMS = {16, 8}
+TAIL_FORMS = {(16, 1), (8, 1), (0, 1), (0, 2)}
+
+
+def scan_grid(num_cu, blocks_per_cu, nitems, rec_cap, m_padded, self_lists, kt, centred):
+    """knn_cells_scan_plan restated."""
+    sw = CELL_SCAN_WAVES if kt == 1 and not centred else CELL_SCAN_WAVES_KT2
+    blocks = num_cu * (blocks_per_cu if kt == 1 and not centred else 1)
+    if blocks * sw > nitems:
+        blocks = max(1, nitems // sw)
+    ovf_cap = min(rec_cap // 4, 1 << 16)
+    lds = m_padded * ((64 if centred else 32 * kt) + 4) + sw * CELL_TILES_PER_PASS * 8 * 16
+    if self_lists:
+        lds += m_padded * 4 + sw * CELL_SELF_CAP * 2
+    elif centred:
+        lds += m_padded * 4
+    return dict(blocks=blocks, waves=sw, nlists=blocks * sw, slice=(rec_cap - ovf_cap) // (blocks * sw), ovf_base=rec_cap - ovf_cap,
+                ovf_cap=ovf_cap, lds_bytes=lds)
+
+
+def parent_query_plan(k, kt, centred, rows_u8, ncells, nitems, cap, several_slots, scan_blocks, scan_deal, cells_lists, m, num_cu,
+                      rec_cap):
+    """The rules knn_cells_query applied inline before the plan had a function of its own (everything but the LDS limits)."""
+    m_padded = (m + 31) // 32 * 32
+    one_block = scan_blocks == 1 or (scan_blocks == 0 and several_slots and ncells <= 32768)
+    self_lists = kt == 1 and not centred and not rows_u8 and (
+        cells_lists == 2 or (cells_lists == 0 and not several_slots and ncells <= 8192))
+    grid = scan_grid(num_cu, 1 if one_block else 2, nitems, rec_cap, m_padded, self_lists, kt, centred)
+    dyn = scan_deal == 2 or (scan_deal == 0 and nitems >= 2 * grid["nlists"] and (not several_slots or ncells > 32768))
+    k16 = 16 if k == 16 else 0
+    if centred and rows_u8:
+        form = (1, k16, 0, 1, 1, 0, 1)
+    elif rows_u8:
+        form = (1, k16, 0, 1, 0, 0, 1)
+    elif centred:
+        form = (dyn, k16, 0, 1, 1, 0, 0)
+    elif kt == 2 and k <= 30:
+        form = (dyn, 0, 0, 2, 0, 1, 0)
+    elif kt == 2:
+        form = (dyn, 0, 0, 2, 0, 0, 0)
+    else:
+        form = (dyn, k16, self_lists, 1, 0, 0, 0)
+    match_waves = 0 if self_lists else 16 if ncells <= 16384 else 8
+    stage = 0 if self_lists else min(cap, 128) if kt == 1 else cap if cap <= CELL_MATCH_STAGED_CAP else 0
+    tail_blocks = num_cu * 8
+    if tail_blocks * KNN_WAVES > nitems:
+        tail_blocks = max(2, (nitems + KNN_WAVES - 1) // KNN_WAVES)
+    want = dict(prep_pw=2 if several_slots else 4, prep_kt=1 if centred else kt, prep_ctr=int(centred), self_lists=int(self_lists),
+                match_waves=match_waves, stage=stage, match_lds=64 * (stage + 2) * 2 if stage else 0,
+                list_cap=CELL_SELF_CAP if self_lists else cap, tail_k=0 if kt == 2 else k if k in (16, 8) else 0, tail_kt=kt,
+                tail_blocks=tail_blocks, exact_launch=int(k != 16), **grid)
+    want.update(zip(("scan_dyn", "scan_k", "scan_self", "scan_kt", "scan_ctr", "scan_nif", "scan_u8"), map(int, form)))
+    return want
+
+
+@pytest.mark.parametrize("k", [3, 8, 15, 16, 17, 20, 30, 31, 32])
+def test_query_plan_reproduces_the_rules_the_query_applied(k):
+    """knn_cells_query_plan against the rules restated, over every value of the options and the sizes that move them; the LDS
+    limits the variants' attributes are raised to (once per device) cover every launch above the defaults, are the same for
+    every launch of a variant, and fit a CU beside the kernel's static LDS."""
+    import itertools
+    import multicore_hw2_amd as pkg
+    kt = 1 if k <= 16 else 2
+    rec_cap = pkg.debug_scan_plan(256, 2, 100, 1)["rec_cap"]
+    frames = ((0, 0), (1, 0), (1, 1), (0, 1)) if kt == 1 else ((0, 0),)
+    limits = {}
+    for i, ((centred, rows_u8), cells_log2, nitems_of, several, sb, sd, cl, m, num_cu) in enumerate(itertools.product(
+            frames, (9, 13, 14, 15, 16), (lambda c: 1, lambda c: 5, lambda c: c, lambda c: 3 * c + 7), (0, 1), (0, 1, 2), (0, 1, 2),
+            (0, 1, 2), (1, 31, 1000, 1024), (8, 256, 304))):
+        ncells = 1 << cells_log2
+        inputs = dict(k=k, kt=kt, centred=centred, rows_u8=rows_u8, ncells=ncells, nitems=nitems_of(ncells),
+                      cap=(100, 640, 1024)[i % 3], several_slots=several, scan_blocks=sb, scan_deal=sd, cells_lists=cl, m=m,
+                      num_cu=num_cu, rec_cap=rec_cap)
+        got = pkg.debug_cells_query_plan(**inputs)
+        want = parent_query_plan(**inputs)
+        assert {n: got[n] for n in want} == want, inputs
+        form = tuple(got[n] for n in ("scan_dyn", "scan_k", "scan_self", "scan_kt", "scan_ctr", "scan_nif", "scan_u8"))
+        assert form in SCAN_FORMS and (got["prep_pw"], got["prep_kt"], got["prep_ctr"]) in PREP_FORMS, inputs
+        assert (got["tail_k"], got["tail_kt"]) in TAIL_FORMS and got["match_waves"] in MATCH_FORMS | {0}, inputs
+        # the scan grid: the buffers the kernels index
+        bpc = 2 if kt == 1 and not centred else 1
+        assert 1 <= got["blocks"] <= num_cu * bpc and got["nlists"] <= 1 << 16, inputs
+        assert got["nlists"] <= max(inputs["nitems"], got["waves"]), inputs
+        assert got["slice"] >= 1 and got["nlists"] * got["slice"] <= got["ovf_base"], inputs
+        assert got["ovf_base"] + got["ovf_cap"] == rec_cap and got["ovf_cap"] * 16 < 1 << 32, inputs
+        assert got["lds_bytes"] % 16 == 0, inputs
+        # LDS: above the default a launch needs its variant's limit, and a variant has one limit
+        if got["scan_lds_limit"]:
+            assert got["lds_bytes"] <= got["scan_lds_limit"], inputs
+        else:
+            assert got["lds_bytes"] + SCAN_STATIC_LDS <= DEFAULT_DYNAMIC_LDS_LIMIT, inputs
+        assert got["match_lds"] <= (got["match_lds_limit"] or 48 * 1024), inputs
+        assert got["scan_lds_limit"] + SCAN_STATIC_LDS <= LDS_PER_CU and got["match_lds_limit"] + MATCH_STATIC_LDS <= LDS_PER_CU
+        for variant, limit in ((form, got["scan_lds_limit"]), (got["match_waves"], got["match_lds_limit"])):
+            if limit:
+                assert limits.setdefault(variant, limit) == limit, (variant, inputs)
+
+
+def test_query_plan_reaches_exactly_the_instantiations_the_code_object_holds():
+    import itertools
+    import multicore_hw2_amd as pkg
+    rec_cap = pkg.debug_scan_plan(256, 2, 100, 1)["rec_cap"]
+    scan, prep, match, tail = set(), set(), set(), set()
+    for k in (3, 8, 15, 16, 17, 20, 30, 31, 32):
+        kt = 1 if k <= 16 else 2
+        for (centred, rows_u8), ncells, several, sd, cl in itertools.product(
+                ((0, 0), (1, 0), (1, 1), (0, 1)) if kt == 1 else ((0, 0),), (1 << 13, 1 << 16), (0, 1), (0, 1, 2), (0, 1, 2)):
+            p = pkg.debug_cells_query_plan(k=k, kt=kt, centred=centred, rows_u8=rows_u8, ncells=ncells, nitems=3 * ncells, cap=640,
+                                           several_slots=several, scan_blocks=0, scan_deal=sd, cells_lists=cl, m=1024, num_cu=256,
+                                           rec_cap=rec_cap)
+            scan.add(tuple(p[n] for n in ("scan_dyn", "scan_k", "scan_self", "scan_kt", "scan_ctr", "scan_nif", "scan_u8")))
+            prep.add((p["prep_pw"], p["prep_kt"], p["prep_ctr"]))
+            match.add(p["match_waves"])
+            tail.add((p["tail_k"], p["tail_kt"]))
+    assert scan == SCAN_FORMS and len(scan) == 20
+    assert prep == PREP_FORMS and len(prep) == 6
+    assert match - {0} == MATCH_FORMS and tail == TAIL_FORMS
+
+
+def test_query_plan_raises_the_lds_limits_of_the_variants_that_need_it():
+    """A full batch of the centred, centred-u8, NIF and window scans asks for more than the default 64 KiB, and so does a
+    staged match list of 16 < k <= 32: those variants get a limit; the k <= 16 one-frame scans and the match at k <= 16 do not."""
+    import multicore_hw2_amd as pkg
+    rec_cap = pkg.debug_scan_plan(256, 2, 100, 1)["rec_cap"]
+
+    def plan(k, centred=0, rows_u8=0, cells_lists=0):
+        return pkg.debug_cells_query_plan(k=k, kt=1 if k <= 16 else 2, centred=centred, rows_u8=rows_u8, ncells=1 << 16,
+                                          nitems=3 << 16, cap=640, several_slots=0, scan_blocks=0, scan_deal=0,
+                                          cells_lists=cells_lists, m=1, num_cu=256, rec_cap=rec_cap)
+    for p in (plan(16, 1), plan(16, 1, 1), plan(20), plan(32)):
+        assert p["scan_lds_limit"] > DEFAULT_DYNAMIC_LDS_LIMIT and p["lds_bytes"] < p["scan_lds_limit"]
+    for p in (plan(20), plan(32)):
+        assert p["match_lds_limit"] == 64 * (CELL_MATCH_STAGED_CAP + 2) * 2
+    for p in (plan(16), plan(16, 0, 1), plan(3, cells_lists=2)):
+        assert p["scan_lds_limit"] == 0 and p["match_lds_limit"] == 0
+
+
 @pytest.mark.parametrize("nitems", [1, 15, 16, 17, 8192, 65536, 65536 * 3 + 7])
 @pytest.mark.parametrize("blocks", [1, 2, 256, 512, 304])
 def test_block_counter_deal_hands_every_item_to_exactly_one_block(nitems, blocks):

@@ -1092,27 +1092,32 @@ def test_grid_index_give_up_flag_is_reset_between_batches_on_a_slot(oracle):
         np.testing.assert_array_equal(outs[j][0].cpu().numpy(), oracle.v0(k, Q, R), err_msg=f"batch {j}")
 
 
-def test_one_index_driven_from_several_host_threads(oracle):
+@pytest.mark.parametrize("k,nindexes", [(16, 1), (20, 2)], ids=["one_index", "two_indexes_k20"])
+def test_one_index_driven_from_several_host_threads(oracle, k, nindexes):
     """Round 2 documented "one index, one host thread"; the index now serialises its callers.  Four threads, each with
     its own slot, stream and batch, 20 calls each on ONE index (ctypes drops the GIL inside the library): every answer is
-    v0's."""
+    v0's.  two_indexes_k20: thread t queries index t % 2 with batches of 1024 (even t) or 800 (odd t) queries — the NIF scan
+    of both asks for more than the default 64 KiB of LDS, a different amount each, and the kernel's limit is the device's:
+    it must never drop under a launch of the other index (one index's mutex covers only its own calls)."""
     import threading
-    k, m, n = 16, 512, 1 << 18
+    n = 1 << 18
     R = oracle.synth(n * k, 77)
     dev = torch.device("cuda:0")
     r_d = torch.from_numpy(R).to(dev)
     pkg.set_option("cells", 1)
     try:
-        ix = pkg.KnnIndex(k, r_d.data_ptr(), n_local=n, refs_on_device=True)
+        ixs = [pkg.KnnIndex(k, r_d.data_ptr(), n_local=n, refs_on_device=True) for _ in range(nindexes)]
     finally:
         pkg.set_option("cells", 0)
     nthreads, rounds = 4, 20
-    Qs = [oracle.synth(m * k, 300 + t).reshape(m, k) for t in range(nthreads)]
+    ms = [512] * nthreads if nindexes == 1 else [1024 if t % 2 == 0 else 800 for t in range(nthreads)]
+    Qs = [oracle.synth(ms[t] * k, 300 + t).reshape(ms[t], k) for t in range(nthreads)]
     wants = [oracle.v0(k, Q, R, threads=THREADS) for Q in Qs]
     errors = []
 
     def worker(t):
         try:
+            m, ix = ms[t], ixs[t % nindexes]
             st = torch.cuda.Stream(device=dev)
             q_d = torch.from_numpy(Qs[t]).to(dev)
             keys = torch.empty(m, dtype=torch.int64, device=dev)
@@ -1125,7 +1130,9 @@ def test_one_index_driven_from_several_host_threads(oracle):
                 if not (out.cpu().numpy() == wants[t]).all():
                     errors.append((t, "mismatch"))
                     return
-                ix.last_stats()
+                if ix.last_stats()[0] != 4:
+                    errors.append((t, "not the pruned scan", ix.last_stats()))
+                    return
         except Exception as e:  # noqa: BLE001
             errors.append((t, repr(e)))
 
@@ -1134,7 +1141,8 @@ def test_one_index_driven_from_several_host_threads(oracle):
         th.start()
     for th in threads:
         th.join()
-    ix.close()
+    for ix in ixs:
+        ix.close()
     assert not errors, errors
 
 
