@@ -274,10 +274,13 @@ int knn_index_query_topk_host(knn_index *idx, int m, int K, const float *queries
  *   "scan_blocks" the pruned scan's blocks per CU: 0 = auto (two; one for shards of up to 2^15 cells while the index's last
  *             eight calls named more than one workspace slot — batches in flight side by side: the scan alone gets 10-20 %
  *             longer and the next batch's preparation kernels find room beside it, 5-7 % per step), 1, 2
- *   "run_thresholds" the deep-K scans (64 < k <= 512): 0 / 1 = every score below a query's threshold lowers that threshold for
- *             the rest of the launch (threshold' = max(floor, score + margin), shared between blocks through an atomic minimum
- *             per query; the sample pass then only visits every 32nd tile), 2 = thresholds stay what the sample pass made them
- *   "sample_stride" deep-K scans: tiles the sample pass skips between two it scores (0 = library policy)
+ *   "run_thresholds" the LDS-tiled filter scan at 64 < k <= 512 (at k <= 128 for batches of at least 16 query tiles, m > 480;
+ *             smaller batches there take the register scan): 0 / 1 = every score below a query's threshold lowers that
+ *             threshold for the rest of the launch (threshold' = max(floor, score + margin), shared between blocks through an
+ *             atomic minimum per query; the sample pass then only visits every 32nd tile), 2 = thresholds stay what the sample
+ *             pass made them.  1-NN queries only: top-K runs with 2
+ *   "sample_stride" the LDS-tiled filter scan (32 < k <= 512; at k <= 128 for batches of at least 16 query tiles): tiles the
+ *             sample pass skips between two it scores (0 = library policy).  1-NN queries only; the other scans keep the policy
  *   "cells_centre" per-cell frames of the cell-sorted layout (k <= 16, not for cell-range shards): the fp16 fragments of a cell are
  *             taken about the middle of the cell's own box and scaled (by up to 2^8 more) to fill the fp16 range the rows of the
  *             whole shard share otherwise — the filter's rounding error shrinks from 2^-12 of the shard's box to 2^-12 of the
@@ -372,6 +375,15 @@ int knn_debug_scan_plan_ex(int num_cu, int blocks_per_cu, unsigned nitems, int m
  * tail: K, KT, blocks; 1 if the gated exact scan is a launch of its own; the LDS limits of the scan and the match kernel
  * (0: the default)}. */
 int knn_debug_cells_query_plan(const long long in[14], long long out[28]);
+/* Test hook (host arithmetic only, no GPU needed): every choice and size one batch of the dense filter query launches with.
+ * in = {kt, ntiles, m, num_cu, rec_cap, K (0 = 1-NN), and the options filter_qt, filter_rounds, filter_chain, run_thresholds,
+ * sample_stride};
+ * out = {ok, form (0 register pieces, 1 LDS-tiled, 2 chunked-K), KT, pieces, record lists, records per list, sample stride,
+ * sample blocks, sample minima (floats), K of the K-th-minimum launch (0 none), sample rows of the thresholds kernel, 1 if it
+ * writes running thresholds, 1 if the scan reads them, 1 if the scan is in the slots' chain, 1 if it waits and records there,
+ * 1 if records carry row masks; per piece (four) {QT, first tile, tiles, grid x, grid y, first list}; the re-rank's pieces,
+ * first lists [4] and first query rows [4]}. */
+int knn_debug_filter_query_plan(const long long in[11], long long out[49]);
 
 /* Test hook for the filter's error bound: raw MFMA filter scores S[m][n_local] (row-major,
  * device) for a query batch, the fp32 squared norms M[m] of the fp16 query rows (device), and

@@ -28,7 +28,7 @@ EXPORTED_SYMBOLS = [
     "knn_index_query_host", "knn_set_option", "knn_get_option", "knn_index_last_stats",
     "knn_synth_fill_device", "knn_index_timing", "knn_index_timing_read",
     "knn_debug_filter_scores", "knn_index_query_keys_slot", "knn_trim", "knn_keys_allreduce_min",
-    "knn_index_query_keys_ex", "knn_index_debug_counters", "knn_debug_scan_plan", "knn_debug_scan_plan_ex", "knn_debug_cells_query_plan", "knn_debug_shard_policy", "knn_debug_plan_shard", "knn_debug_u8_row", "knn_debug_u8_bin_row", "knn_debug_u8_bin_threshold", "knn_index_query",
+    "knn_index_query_keys_ex", "knn_index_debug_counters", "knn_debug_scan_plan", "knn_debug_scan_plan_ex", "knn_debug_cells_query_plan", "knn_debug_filter_query_plan", "knn_debug_shard_policy", "knn_debug_plan_shard", "knn_debug_u8_row", "knn_debug_u8_bin_row", "knn_debug_u8_bin_threshold", "knn_index_query",
     "knn_geom_create", "knn_geom_destroy", "knn_geom_info", "knn_geom_assign", "knn_index_create_sharded",
     "knn_index_seed_export", "knn_index_seed_attach", "knn_geom_first_cell",
     "knn_index_query_topk", "knn_keys_topk_merge", "knn_index_query_topk_host",
@@ -162,6 +162,29 @@ def debug_cells_query_plan(**inputs):
     f.argtypes = [ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)]
     _check(f(vin, out))
     return dict(zip(CELLS_QUERY_PLAN, list(out)))
+
+
+FILTER_QUERY_INPUTS = ("kt", "ntiles", "m", "num_cu", "rec_cap", "topk", "filter_qt", "filter_rounds", "filter_chain",
+                       "run_thresholds", "sample_stride")
+FILTER_QUERY_PLAN = ("ok", "form", "kt", "npieces", "nlists", "slice", "stride", "sample_blocks", "umin_floats", "topk", "thr_nb",
+                     "thr_running", "scan_running", "in_chain", "chained", "has_rows")
+FILTER_PIECE = ("qt", "begin", "count", "gx", "gy", "list_base")
+
+
+def debug_filter_query_plan(**inputs):
+    """knn_debug_filter_query_plan: every choice and size one batch of the dense filter query launches with, for the inputs
+    named in FILTER_QUERY_INPUTS (host arithmetic; works without a GPU).  form: 0 register pieces, 1 LDS-tiled, 2 chunked-K;
+    "pieces": the npieces launches; "rerank": the re-rank's (n, list_base[4], qrow_base[4])."""
+    vin = (ctypes.c_longlong * len(FILTER_QUERY_INPUTS))(*[int(inputs[n]) for n in FILTER_QUERY_INPUTS])
+    out = (ctypes.c_longlong * 49)()
+    f = lib().knn_debug_filter_query_plan
+    f.argtypes = [ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)]
+    _check(f(vin, out))
+    v = list(out)
+    p = dict(zip(FILTER_QUERY_PLAN, v))
+    p["pieces"] = [dict(zip(FILTER_PIECE, v[16 + 6 * i:22 + 6 * i])) for i in range(p["npieces"])]
+    p["rerank"] = (v[40], tuple(v[41:45]), tuple(v[45:49]))
+    return p
 
 
 def debug_plan_shard(k, m, rows):

@@ -929,10 +929,13 @@ int knn_index_query(knn_index *idx, int slot, int m, const float *queries_dev, u
     if (use_filter) {
         // the event pair brackets the MFMA filter kernel alone (the dominant kernel)
         idx->stats[0] = 2;
-        idx->filter.force_qt = (int)g_opt_filter_qt;
-        idx->filter.force_rounds = (int)g_opt_filter_rounds;
-        idx->filter.chain_policy = (int)g_opt_filter_chain;
-        idx->filter.cells_policy = idx->sharded ? 0 : (int)g_opt_cells;   // (a cell-range shard has no other layout)
+        FilterCallOptions opt;
+        opt.force_qt = (int)g_opt_filter_qt;
+        opt.force_rounds = (int)g_opt_filter_rounds;
+        opt.chain_policy = (int)g_opt_filter_chain;
+        opt.run_thresholds = (int)g_opt_run_thresholds;
+        opt.sample_stride = (int)g_opt_sample_stride;
+        opt.cells_policy = idx->sharded ? 0 : (int)g_opt_cells;   // (a cell-range shard has no other layout)
         // batches in flight on several workspace slots = a caller after throughput: the pruned scan of a small shard then
         // takes ONE block per CU, so that the next batch's preparation kernels find registers beside it (knn_cells_query).
         // Derived from the last eight calls (the flag used to stick for the life of the index once any call
@@ -944,15 +947,13 @@ int knn_index_query(knn_index *idx, int slot, int m, const float *queries_dev, u
             bool several = false;
             for (int i = 1; i < idx->recent_calls; ++i)
                 several = several || ((idx->recent_slots >> (8 * i)) & 0xFFull) != (unsigned long long)(unsigned)slot;
-            idx->filter.several_slots = several;
+            opt.several_slots = several;
         }
-        idx->filter.scan_blocks = (int)g_opt_scan_blocks;
-        idx->filter.scan_deal = (int)g_opt_scan_deal;
-        idx->filter.cells_lists = (int)g_opt_cells_lists;
-        idx->filter.run_thresholds = (int)g_opt_run_thresholds;
-        idx->filter.sample_stride = (int)g_opt_sample_stride;
+        opt.scan_blocks = (int)g_opt_scan_blocks;
+        opt.scan_deal = (int)g_opt_scan_deal;
+        opt.cells_lists = (int)g_opt_cells_lists;
         idx->last_slot = slot;
-        HIP_TRY(knn_filter_query(idx->filter, slot, m, queries_dev, idx->refs, idx->base, (u64 *)keys_dev,
+        HIP_TRY(knn_filter_query(idx->filter, opt, slot, m, queries_dev, idx->refs, idx->base, (u64 *)keys_dev,
                                  idx->num_cu, s, ev ? ev->first : nullptr, ev ? ev->second : nullptr, init_keys, indices_dev));
         if (idx->filter.ws[slot].last_used_cells)
             idx->stats[0] = 4;
@@ -1022,14 +1023,16 @@ int knn_index_query_topk(knn_index *idx, int slot, int m, int K, const float *qu
                 idx->topk_cand_bytes[slot] = cbytes;
             }
             idx->stats[0] = 2;
-            idx->filter.force_qt = (int)g_opt_filter_qt;
-            idx->filter.force_rounds = (int)g_opt_filter_rounds;
-            idx->filter.chain_policy = (int)g_opt_filter_chain;
-            idx->filter.run_thresholds = 2;   // running thresholds are a 1-NN argument; the non-running sample stride with them
-            idx->filter.sample_stride = 0;
+            FilterCallOptions opt;
+            opt.force_qt = (int)g_opt_filter_qt;
+            opt.force_rounds = (int)g_opt_filter_rounds;
+            opt.chain_policy = (int)g_opt_filter_chain;
+            opt.run_thresholds = 2;   // running thresholds are a 1-NN argument; the non-running sample stride with them
+            opt.sample_stride = 0;
+            opt.topk = K;
             u64 *cand = idx->topk_cand[slot];
             unsigned *ccount = (unsigned *)(cand + (size_t)m * ccap);
-            HIP_TRY(knn_filter_query_topk(idx->filter, slot, m, K, queries_dev, idx->refs, idx->base, (u64 *)keys_dev, init != 0,
+            HIP_TRY(knn_filter_query_topk(idx->filter, opt, slot, m, queries_dev, idx->refs, idx->base, (u64 *)keys_dev, init != 0,
                                           cand, ccount, ccap, idx->topk_part[slot], idx->topk_bytes[slot], idx->num_cu, s,
                                           ev ? ev->first : nullptr, ev ? ev->second : nullptr));
         } else {
@@ -1213,6 +1216,40 @@ int knn_debug_cells_query_plan(const long long in[14], long long out[28])
                              p.grid.blocks, p.grid.waves, p.grid.nlists, p.grid.slice, p.grid.ovf_base, p.grid.ovf_cap,
                              (long long)p.grid.lds_bytes, p.list_cap, p.tail_k, p.tail_kt, p.tail_blocks, p.exact_launch,
                              (long long)p.scan_lds_limit, (long long)p.match_lds_limit};
+    memcpy(out, v, sizeof v);
+    return KNN_OK;
+}
+
+int knn_debug_filter_query_plan(const long long in[11], long long out[49])
+{
+    if (!in || !out || in[0] < 1 || in[0] > KNN_FILTER_MAX_K / 16 || in[1] < 1 || in[2] < 1 || in[2] > INT_MAX || in[3] < 1 ||
+        in[3] > 4096 || in[4] < 1 || in[4] > UINT_MAX || in[5] < 0 || in[5] > KNN_TOPK_MAX ||
+        (in[6] != 0 && in[6] != 2 && in[6] != 8 && in[6] != 16 && in[6] != 32) || in[7] < 0 || in[7] > 64 || in[8] < 0 ||
+        in[8] > 2 || in[9] < 0 || in[9] > 2 || in[10] < 0 || in[10] > 1024)
+        return fail(KNN_EINVAL, "knn_debug_filter_query_plan: bad arguments");
+    FilterQueryInputs fi;
+    fi.kt = (int)in[0];
+    fi.ntiles = in[1];
+    fi.m = (int)in[2];
+    fi.num_cu = (int)in[3];
+    fi.rec_cap = (unsigned)in[4];
+    fi.opt.topk = (int)in[5];
+    fi.opt.force_qt = (int)in[6];
+    fi.opt.force_rounds = (int)in[7];
+    fi.opt.chain_policy = (int)in[8];
+    fi.opt.run_thresholds = (int)in[9];
+    fi.opt.sample_stride = (int)in[10];
+    const FilterQueryPlan p = knn_filter_query_plan(fi);
+    long long v[49] = {p.ok, (long long)p.form, p.kt, p.npieces, p.nlists, p.slice, p.stride, p.sample_blocks, (long long)p.umin_floats,
+                       p.topk, p.thr_nb, p.thr_running, p.scan_running, p.in_chain, p.chained, p.has_rows};
+    for (int i = 0; i < 4; ++i) {
+        const FilterPiece &pc = p.pieces[i];
+        const long long f[6] = {pc.qt, pc.begin, pc.count, pc.gx, pc.gy, pc.list_base};
+        memcpy(v + 16 + 6 * i, f, sizeof f);
+        v[41 + i] = p.rerank.list_base[i];
+        v[45 + i] = p.rerank.qrow_base[i];
+    }
+    v[40] = p.rerank.n;
     memcpy(out, v, sizeof v);
     return KNN_OK;
 }

@@ -3684,12 +3684,12 @@ static hipError_t cells_trace_lists(const CellIndex &c, const FilterWorkspace &w
 // [rows outside the robust box, exactly] -> the exact scan of the shard, gated on FALLBACK -> the tail kernel (gated: records
 // in the shared area, the listed pairs exactly when that area is over-full, the finalisation when the scan could not do it).
 // Four launches on clean data at k = 16 (the exact scan of the shard is a branch of the tail kernel there), five otherwise.  out_idx (nullable): int32 indices of the batch, written by whichever block ends it.
-hipError_t knn_cells_query(FilterState &st, FilterWorkspace &w, int m, const float *q, const float *r, long long base,
-                           u64 *keys, int num_cu, bool timed, hipStream_t s, bool init_keys, int *out_idx)
+hipError_t knn_cells_query(FilterState &st, FilterWorkspace &w, FilterCallOptions opt, int m, const float *q, const float *r,
+                           long long base, u64 *keys, int num_cu, bool timed, hipStream_t s, bool init_keys, int *out_idx)
 {
     const CellIndex &c = *st.cells;
-    const CellQueryPlan p = knn_cells_query_plan({st.k, st.kt, c.centred, c.rows_u8, c.ncells, c.nitems, c.cap, st.several_slots,
-                                                  st.scan_blocks, st.scan_deal, st.cells_lists, m, num_cu, w.rec_cap});
+    const CellQueryPlan p = knn_cells_query_plan({st.k, st.kt, c.centred, c.rows_u8, c.ncells, c.nitems, c.cap, opt.several_slots,
+                                                  opt.scan_blocks, opt.scan_deal, opt.cells_lists, m, num_cu, w.rec_cap});
     FTRY(ensure_cells_workspace(st, w, m, p));
     const int m_padded = (m + 31) / 32 * 32;
     w.has_rows = false;

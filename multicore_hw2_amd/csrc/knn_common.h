@@ -30,7 +30,7 @@ hipError_t knn_exact_gather_launch(int k, int m, unsigned count, long long base,
 
 // Exact re-rank of the filter's candidate records (see knn_rerank_kernel).
 // Record lists [list_base[i], list_base[i+1]) belong to piece i of the batch, whose records number their
-// queries from qrow_base[i] (see plan_pieces in knn_filter.hip); unused entries have list_base = ~0.
+// queries from qrow_base[i] (see knn_filter_query_plan); unused entries have list_base = ~0.
 struct RerankPieces {
     unsigned list_base[4] = {0u, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
     unsigned qrow_base[4] = {0u, 0u, 0u, 0u};
@@ -246,6 +246,28 @@ struct CellIndex {
 #define KNN_CELL_FRAME_WORDS 20
 #define KNN_NIF_MAX_K 30   // 16 < k <= 30: the cell-sorted fragments carry the rows' norms in K-slots 30, 31 (knn_cells.hip: cell_tile_step_nif)
 
+// The options of one filter query, filled from the global options by knn_index_query / knn_index_query_topk and passed by value:
+// nothing of a call stays in the index.
+struct FilterCallOptions {
+    // the dense scan (knn_filter_query_plan)
+    int force_qt = 0;          // "filter_qt": query tiles per wave of the register scan at k <= 16 (0 = pick by m)
+    int force_rounds = 0;      // "filter_rounds": blocks per resident slot of the register scan (k <= 32; k 33 .. 128 below 16
+                               // query tiles); 0 = one
+    int chain_policy = 0;      // "filter_chain": scans of different slots (k <= 512; k > 512 never chains): 0 auto (chained from
+                               // 2^19 tiles), 1 always chained, 2 never
+    int run_thresholds = 0;    // LDS-tiled scan at k 65 .. 512 (at k <= 128 from 16 query tiles): 0 / 1 thresholds tighten during
+                               // the launch and the sample pass thins out, 2 they stay as the sample pass left them
+    int sample_stride = 0;     // LDS-tiled scan (k 33 .. 512; at k <= 128 from 16 query tiles): tiles the sample pass skips between
+                               // two it scores; 0 = library policy
+    int topk = 0;              // K of a top-K call (the threshold comes from the K-th smallest per-block sample minimum); 0 = 1-NN
+    // the cell-pruned scan (knn_cells_query_plan)
+    int cells_policy = 0;      // 0 use the cells when present, 2 full scan
+    bool several_slots = false;// the index's recent calls named more than one workspace slot: batches are in flight side by side
+    int scan_blocks = 0;       // blocks per CU: 0 auto (one for small shards when several_slots, else two), 1, 2
+    int scan_deal = 0;         // 0 auto (block counter unless several_slots), 1 fixed deal, 2 items from a block counter
+    int cells_lists = 0;       // who lists a cell's queries: 0 auto, 1 knn_cells_match_kernel, 2 the scan's own waves
+};
+
 struct FilterState {
     bool usable = false;       // references finite and in a sane range: filter layouts exist
     int k = 0, kt = 0;         // real dimension; 16-wide K steps (padded k = 16 * kt)
@@ -260,21 +282,9 @@ struct FilterState {
     unsigned *ref_norms2 = nullptr; // cell-sorted layouts only, device [ntiles*32]: the same norms as two fp16 halves
                                // (hi | mid * 2^11 << 16) — the prep kernel rebuilds the C tile of its seed scores from
                                // them with one extra MFMA: one register per tile in flight instead of 16 (knn_cells.hip)
-    int force_qt = 0;          // tuning hook: query tiles per wave (0 = pick by m)
-    int force_rounds = 0;      // tuning hook: filter blocks per resident slot (0 = default)
-    int chain_policy = 0;      // scans of different slots: 0 auto (chained when long), 1 always chained, 2 never
     unsigned *outliers = nullptr; // device: rows outside the robust box (excluded from the filter, scanned exactly)
     unsigned n_outliers = 0;
     CellIndex *cells = nullptr;   // non-null: the layout is cell-sorted (ntiles counts its padded tiles)
-    int cells_policy = 0;         // per call: 0 use the cells when present, 2 full scan
-    bool several_slots = false;   // a query has used a workspace slot other than 0: batches are in flight side by side
-    int scan_deal = 0;            // pruned scan: 0 auto (block counter unless several_slots), 1 fixed deal, 2 items from a block counter
-    int scan_blocks = 0;          // pruned scan, blocks per CU: 0 auto (one for small shards when several_slots, else two), 1, 2
-    int sample_stride = 0;        // deep-K scans (k > 32): tiles the sample pass skips between two it scores; 0 = library policy
-    int topk = 0;                 // K of the top-K call in progress (knn_filter_query_topk): the threshold comes from the K-th
-                                  // smallest per-block sample minimum; 0 = 1-NN
-    int run_thresholds = 0;       // deep-K scan (64 < k <= 128): 0 / 1 thresholds tighten during the launch, 2 they stay as the sample pass left them
-    int cells_lists = 0;          // pruned scan, who lists a cell's queries: 0 auto, 1 knn_cells_match_kernel, 2 the scan's own waves
     FilterWorkspace ws[KNN_SLOTS];
     // The slots' big scan kernels are chained through this event: two of them sharing the CUs run
     // 15 % slower than back to back; only the small preparation kernels are meant to overlap.
@@ -325,7 +335,7 @@ struct CellQueryInputs {
     bool centred = false, rows_u8 = false;      // per-cell frames; 8-bit rows (in bin frames when not centred)
     unsigned ncells = 0, nitems = 0, cap = 0;   // the index's cells, work items and room per list of queries
     bool several_slots = false;
-    int scan_blocks = 0, scan_deal = 0, cells_lists = 0;   // the options (FilterState)
+    int scan_blocks = 0, scan_deal = 0, cells_lists = 0;   // the options (FilterCallOptions)
     int m = 0, num_cu = 0;
     unsigned rec_cap = 0;
 };
@@ -352,6 +362,43 @@ struct CellQueryPlan {
     size_t scan_lds_limit = 0, match_lds_limit = 0;   // the variants' dynamic-LDS attribute (0: the default)
 };
 CellQueryPlan knn_cells_query_plan(const CellQueryInputs &in);
+// Every choice and size one batch of the dense filter query launches with (knn_filter_query_plan in knn_filter.hip; host
+// arithmetic only).  The scan comes in three forms: pieces of the batch on the register scan (knn_filter_kernel, k <= 32, and
+// k <= 128 below 16 query tiles), the LDS-tiled scan (knn_filter_tiled_kernel, k <= 512) and the chunked-K scan
+// (knn_filter_chunked_kernel, k > 512).
+struct FilterQueryInputs {
+    int kt = 1;                // the index's K-steps (knn_kt_of)
+    long long ntiles = 0;
+    int m = 0, num_cu = 0;
+    unsigned rec_cap = 0;      // records a workspace holds
+    FilterCallOptions opt;     // (its topk: K, 0 = 1-NN)
+};
+enum class FilterForm { Pieces, Tiled, Chunked };
+struct FilterPiece {           // query tiles [begin, begin + count), scanned by one launch whose waves keep qt tiles
+    int qt = 0, begin = 0, count = 0;
+    unsigned gx = 0, gy = 0;   // the scan's grid (the chunked form: ranges x query groups, launched as one dimension)
+    unsigned list_base = 0;    // its first record list
+};
+struct FilterQueryPlan {
+    bool ok = false;           // false: nothing to launch with (no record lists, too many, kt not a multiple of CHK_KC)
+    FilterForm form = FilterForm::Pieces;
+    int kt = 1;                // KT of the form (the chunked form: the run-time kt)
+    int npieces = 0;           // the pieces form: up to four; the others: one, the whole batch
+    FilterPiece pieces[4];
+    unsigned nlists = 0, slice = 0;
+    long long stride = 1;      // the sample pass scores every stride-th tile
+    unsigned sample_blocks = 0;// the sample grid's x (its y: the piece's gy)
+    size_t umin_floats = 0;    // per-block minima the sample pass writes
+    int topk = 0;              // > 0: the K-th smallest per-block minimum (knn_topk_umin_kernel) feeds the thresholds
+    int thr_nb = 0;            // sample rows knn_thr_kernel folds
+    bool thr_running = false;  // knn_thr_kernel also writes margins, floors and running thresholds
+    bool scan_running = false; // the scan is handed the running thresholds
+    bool in_chain = false;     // the scan takes part in the slots' chain (FilterState::scan_done)
+    bool chained = false;      // ... and waits on the last recorded scan and records its own
+    bool has_rows = false;     // the scan writes a row mask next to every record
+    RerankPieces rerank;
+};
+FilterQueryPlan knn_filter_query_plan(const FilterQueryInputs &in);
 hipError_t knn_cells_place_rows(FilterState &st, const float *r_dev, const unsigned *code, unsigned *fill, unsigned *out,
                                 unsigned ocap, hipStream_t s);
 void knn_cells_free(CellIndex *&c);
@@ -371,8 +418,8 @@ void knn_cells_workspace_free(FilterWorkspace &w);
 // One batch of <= KNN_CELL_BATCH queries already prepared by the filter's query-fragment kernel: seed, thresholds,
 // match, scan (records in w, as the full scan leaves them).  Asynchronous.
 // init_keys: the batch's keys are set to (+INF, 0) by the first kernel of the chain.
-hipError_t knn_cells_query(FilterState &st, FilterWorkspace &w, int m, const float *q_dev, const float *r_dev, long long base,
-                           u64 *keys, int num_cu, bool timed, hipStream_t s, bool init_keys, int *out_idx = nullptr);
+hipError_t knn_cells_query(FilterState &st, FilterWorkspace &w, FilterCallOptions opt, int m, const float *q_dev, const float *r_dev,
+                           long long base, u64 *keys, int num_cu, bool timed, hipStream_t s, bool init_keys, int *out_idx = nullptr);
 
 // Builds the filter layouts for refs[0..n) (device, AoS).  Synchronous.  Leaves st.usable false
 // (and returns hipSuccess) when the data rules the filter out.
@@ -430,10 +477,11 @@ void knn_filter_free(FilterState &st);
 // Asynchronous on `stream`: sample pre-pass + MFMA filter + exact re-rank + gated exact fallback.
 // init_keys: the keys are written from scratch ((+INF, 0) first) instead of min-folded into what they hold.
 // out_idx (nullable): the int32 indices of the batch as well (no separate unpack launch on the cell-pruned path).
-hipError_t knn_filter_query(FilterState &st, int slot, int m, const float *q_dev, const float *r_dev,
+hipError_t knn_filter_query(FilterState &st, FilterCallOptions opt, int slot, int m, const float *q_dev, const float *r_dev,
                             long long base, u64 *keys_dev, int num_cu, hipStream_t stream,
                             hipEvent_t ev_begin, hipEvent_t ev_end, bool init_keys = false, int *out_idx = nullptr);
-hipError_t knn_filter_query_topk(FilterState &st, int slot, int m, int K, const float *q, const float *r, long long base,
+// opt.topk = K (1 .. KNN_TOPK_MAX).
+hipError_t knn_filter_query_topk(FilterState &st, FilterCallOptions opt, int slot, int m, const float *q, const float *r, long long base,
                                  u64 *keys, bool init_keys, u64 *cand, unsigned *ccount, unsigned ccap, u64 *part,
                                  size_t part_bytes, int num_cu, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end);
 // Test hook: raw filter scores S[m][n] (row-major) and the per-query thresholds for a query

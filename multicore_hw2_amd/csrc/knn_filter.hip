@@ -2222,17 +2222,12 @@ static hipError_t prep_queries(FilterState &st, FilterWorkspace &w, int m, const
     return hipGetLastError();
 }
 
+// ---- the dense query: one plan (knn_filter_query_plan), typed launches, one sequence (filter_scan) --------------------------
+
 // A batch's query tiles are cut into pieces, each scanned by a launch whose waves keep QT tiles in
 // registers.  A ragged tail no longer pays for a full group: m = 1100 (35 tiles) used to run two
 // groups of 32 (1.09 ms at C3's n), now 32 + a piece of 8 (0.76 ms).  Costs per piece measured at
 // n = 2^24: QT 32: 0.54 ms, 16: 0.31, 8: 0.22, 2: 0.11.
-struct FilterPiece {
-    int qt;       // query tiles per wave
-    int begin;    // first query tile
-    int count;    // query tiles in the piece
-    unsigned gx, gy, list_base;
-};
-
 static int plan_pieces(int kt, int qtiles, int force_qt, FilterPiece out[4])
 {
     int np = 0, pos = 0, rem = qtiles;
@@ -2277,386 +2272,322 @@ static int plan_pieces(int kt, int qtiles, int force_qt, FilterPiece out[4])
     return np;
 }
 
-template <int KT, int QT>
-static void launch_sample_piece(const FilterState &st, const FilterWorkspace &w, const FilterPiece &p, unsigned sb,
-                                long long stride, int m_padded, hipStream_t s)
+// What one batch on the dense layouts launches and with which sizes, decided in one place (host arithmetic: nothing allocated
+// or launched; tests/test_filter_logic.py checks it on the CPU through knn_debug_filter_query_plan).
+FilterQueryPlan knn_filter_query_plan(const FilterQueryInputs &in)
 {
-    hipLaunchKernelGGL((knn_filter_sample_kernel<KT, QT>), dim3(sb, p.gy), dim3(FILTER_BLOCK), 0, s,
-                       (const h8 *)st.ref_frags, st.ref_norms, (const h8 *)w.qry_frags, p.begin + p.count, st.ntiles,
-                       stride, w.umin, m_padded, w.ctl, p.begin);
-}
+    FilterQueryPlan p;
+    const FilterCallOptions &o = in.opt;
+    const int qtiles = (in.m + 31) / 32;
+    const unsigned target_blocks = (unsigned)in.num_cu * 8;
+    p.kt = in.kt;
+    int qt = 0;   // query tiles per wave of the LDS-tiled and the chunked scan
+    switch (in.kt) {
+    case 1:
+    case 2: p.form = FilterForm::Pieces; break;
+    case 4:
+    case 8:
+        p.form = qtiles >= 16 ? FilterForm::Tiled : FilterForm::Pieces;
+        qt = 4;
+        break;
+    // 128 < k <= 512: always the LDS-tiled scan (a reference tile is 16 / 32 KiB: no wave can hold one in registers beside its
+    // queries); the B operands of 2 / 1 blocks of 32 queries are the wave's 128 operand registers
+    case 16: p.form = FilterForm::Tiled; qt = 2; break;
+    case 32: p.form = FilterForm::Tiled; qt = 1; break;
+    default:   // k > 512: K in chunks of 128 dimensions
+        p.form = FilterForm::Chunked;
+        qt = CHK_QT;
+        if (in.kt % CHK_KC != 0)
+            return p;
+    }
 
-template <int KT, int QT>
-static void launch_scan_piece(const FilterState &st, const FilterWorkspace &w, const FilterPiece &p, hipStream_t s)
-{
-    hipLaunchKernelGGL((knn_filter_kernel<KT, QT>), dim3(p.gx, p.gy), dim3(FILTER_BLOCK), 0, s,
-                       (const h8 *)st.ref_frags, st.ref_norms, (const h8 *)w.qry_frags + (size_t)p.begin * KT * 64,
-                       w.thr + (size_t)p.begin * 32, p.count, st.ntiles, w.records + (size_t)p.list_base * w.slice,
-                       w.counts + p.list_base, w.ctl, w.slice);
-}
-
-template <int KT>
-static hipError_t launch_filter(FilterState &st, FilterWorkspace &w, int m, int num_cu, hipStream_t s)
-{
-    const int qtiles = (m + 31) / 32;
-    const int m_padded = qtiles * 32;
-    FilterPiece pc[4];
-    const int np = plan_pieces(KT, qtiles, st.force_qt, pc);
-    const unsigned target_blocks = (unsigned)num_cu * 8;
-
-    // grids: 2 waves per SIMD when the wave's registers are full of query fragments, more when they
-    // are not (small batches are HBM-latency-bound; 5 waves per SIMD measured best at m = 8..64)
-    unsigned gy_sum = 0, nlists = 0;
-    for (int i = 0; i < np; ++i) {
-        FilterPiece &p = pc[i];
-        const int qk = p.qt * KT;
-        p.gy = (unsigned)((p.count + p.qt - 1) / p.qt);
-        long long waves = (long long)num_cu * (qk > 16 ? 8 : qk == 16 ? 12 : qk <= 2 ? 20 : 16);
-        waves *= st.force_rounds > 0 ? st.force_rounds : 1;
-        if (waves > st.ntiles)
-            waves = st.ntiles;
-        p.gx = (unsigned)((waves + 3) / 4);
-        // many query groups (large m): split the references over fewer waves so every wave still
-        // streams a long run of tiles per load of its query fragments
-        if (p.gy > 1 && (size_t)p.gx * p.gy > target_blocks)
-            p.gx = (target_blocks + p.gy - 1) / p.gy;
-        if (p.gx < 1)
-            p.gx = 1;
-        while ((size_t)p.gx * 4 * p.gy > kMaxLists / 4 && p.gx > 1)
-            p.gx = (p.gx + 1) / 2;
-        p.list_base = nlists;
-        nlists += p.gx * 4 * p.gy;
-        gy_sum += p.gy;
+    // the scan's grids and record lists (one list per wave)
+    size_t nlists = 0;
+    unsigned gy_sum = 0;
+    if (p.form == FilterForm::Pieces) {
+        p.npieces = plan_pieces(in.kt, qtiles, o.force_qt, p.pieces);
+        for (int i = 0; i < p.npieces; ++i) {
+            FilterPiece &pc = p.pieces[i];
+            // grids: 2 waves per SIMD when the wave's registers are full of query fragments, more when they
+            // are not (small batches are HBM-latency-bound; 5 waves per SIMD measured best at m = 8..64)
+            const int qk = pc.qt * in.kt;
+            pc.gy = (unsigned)((pc.count + pc.qt - 1) / pc.qt);
+            long long waves = (long long)in.num_cu * (qk > 16 ? 8 : qk == 16 ? 12 : qk <= 2 ? 20 : 16);
+            waves *= o.force_rounds > 0 ? o.force_rounds : 1;
+            if (waves > in.ntiles)
+                waves = in.ntiles;
+            pc.gx = (unsigned)((waves + 3) / 4);
+            // many query groups (large m): split the references over fewer waves so every wave still
+            // streams a long run of tiles per load of its query fragments
+            if (pc.gy > 1 && (size_t)pc.gx * pc.gy > target_blocks)
+                pc.gx = (target_blocks + pc.gy - 1) / pc.gy;
+            if (pc.gx < 1)
+                pc.gx = 1;
+            while ((size_t)pc.gx * 4 * pc.gy > kMaxLists / 4 && pc.gx > 1)
+                pc.gx = (pc.gx + 1) / 2;
+            pc.list_base = (unsigned)nlists;
+            nlists += (size_t)pc.gx * 4 * pc.gy;
+            gy_sum += pc.gy;
+        }
+    } else {
+        FilterPiece &pc = p.pieces[0];
+        p.npieces = 1;
+        pc.qt = qt;
+        pc.count = qtiles;
+        pc.gy = (unsigned)((qtiles + 4 * qt - 1) / (4 * qt));
+        if (p.form == FilterForm::Tiled) {
+            pc.gx = (target_blocks + pc.gy - 1) / pc.gy;
+            if ((long long)pc.gx > in.ntiles)
+                pc.gx = (unsigned)in.ntiles;
+        } else {
+            // ranges of reference tiles: enough blocks for the chip, and at least 16 so that an XCD's 64 resident blocks are FEW
+            // query groups (see the kernel: their B fragments have to fit its L2)
+            // (measured: 8 / 16 / 32 / 64 ranges within 2 % of each other at (1024, 65536, 65536); four blocks per CU in all instead of
+            // eight: the mid-size shapes' step 2-9 % shorter — profiles/r04_deepk.txt)
+            const long long groups = (in.ntiles + CHK_T - 1) / CHK_T;
+            pc.gx = std::max(16u, ((unsigned)in.num_cu * 4u + pc.gy - 1) / pc.gy);
+            if ((long long)pc.gx > groups)
+                pc.gx = (unsigned)groups;
+        }
+        if (pc.gx < 1)
+            pc.gx = 1;
+        while ((size_t)pc.gx * 4 * pc.gy > kMaxLists && pc.gx > 1)
+            pc.gx = (pc.gx + 1) / 2;
+        nlists = (size_t)pc.gx * 4 * pc.gy;
     }
     if (nlists == 0 || nlists > kMaxLists)
-        return hipErrorInvalidValue;
-    w.nlists = nlists;
-    w.slice = w.rec_cap / w.nlists;
-    w.has_rows = false;
-    w.pieces.n = np;
-    for (int i = 0; i < 4; ++i) {
-        w.pieces.list_base[i] = i < np ? pc[i].list_base : 0xFFFFFFFFu;
-        w.pieces.qrow_base[i] = i < np ? (unsigned)pc[i].begin * 32u : 0u;
-    }
+        return p;
+    p.nlists = (unsigned)nlists;
+    p.slice = in.rec_cap / p.nlists;
 
-    // 1. sample pass over every stride-th tile (about 1/16 of the shard) -> per-query minima
-    long long stride = st.ntiles / 256;
-    if (stride < 1)
-        stride = 1;
-    if (stride > 16)   // (32 / 64 / 8 A/B'd at C3 in round 2: 0.547 / 0.555 / 0.585 ms per step against 0.5505: flat)
-        stride = 16;
-    if (st.topk > 0)   // top-K: a threshold from the K-th block minimum passes ~ n K / (sampled rows) rows: sample K times denser
-        stride = std::max<long long>(1, stride / st.topk);
-    const long long ns = (st.ntiles + stride - 1) / stride;
-    unsigned sb = (unsigned)num_cu * 2;  // 2 waves per SIMD, like the main pass
-    if (sb > kSampleBlocks)
-        sb = kSampleBlocks;
-    if (gy_sum > 1 && (size_t)sb * gy_sum > target_blocks)
-        sb = (target_blocks + gy_sum - 1) / gy_sum;
-    // at least 8 sampled tiles per wave: a wave's prologue (its query fragments, QT KiB) is not
-    // worth fewer, and the threshold kernel folds one partial row per block
-    if ((long long)sb * 32 > ns)
-        sb = (unsigned)((ns + 31) / 32);
-    if (sb < 1)
-        sb = 1;
-    if (st.topk > 0) {
-        // top-K: the threshold is the K-th smallest per-block minimum, so the pass needs well over K blocks (fewer than K
-        // blocks with a real row raises FALLBACK): at least 4K of them, as far as the sampled tiles go
-        const long long want = std::min<long long>(std::min<long long>(ns, kSampleBlocks), 4ll * st.topk);
-        if ((long long)sb < want)
-            sb = (unsigned)want;
+    // 1. the sample pass over every stride-th tile (about 1/16 of the shard) -> per-query minima
+    // (16: 32 / 64 / 8 A/B'd at C3 in round 2: 0.547 / 0.555 / 0.585 ms per step against 0.5505: flat)
+    p.stride = std::min<long long>(16, std::max<long long>(1, in.ntiles / 256));
+    if (p.form == FilterForm::Tiled) {
+        // Running thresholds (KT = 8, round 5): the scan tightens every query's threshold as it goes, so the sample pass only has
+        // to give it a start — every 32nd tile instead of every 8th at C5 (2048 tiles): the pass shrinks 4x, the candidates grow
+        // from 210k to 355k of the 642k a fixed threshold left, ms per step 0.9155 (stride 8) / 0.8909 (16) / 0.8829 (32) / 0.9091
+        // (64) / 0.9378 (128) on one box (profiles/r05_c5_running_thresholds.txt).  KNN_MI355X_SAMPLE_STRIDE: the sweep's knob.
+        if (in.kt >= 8 && o.run_thresholds != 2)   // (KT = 16, 32: k 129 .. 512, the same scheme since the end of round 5)
+            p.stride = std::min<long long>(32, std::max<long long>(1, in.ntiles / 64));
+        if (o.sample_stride > 0)   // option `sample_stride` (the sweep's knob, and the tests' like-for-like comparison)
+            p.stride = std::min<long long>(o.sample_stride, std::max<long long>(1, in.ntiles / 16));
     }
-    {   // per-block minima buffer, grown on demand
-        const size_t need = (size_t)sb * (size_t)m_padded;
-        if (need > w.umin_cap) {
-            (void)KNN_DEV_FREE(w.umin);
-            w.umin = nullptr;
-            w.umin_cap = 0;
-            FTRY(KNN_DEV_ALLOC((void **)&w.umin, need * sizeof(float)));
-            w.umin_cap = need;
+    if (o.topk > 0)   // top-K: a threshold from the K-th block minimum passes ~ n K / (sampled rows) rows: sample K times denser
+        p.stride = std::max<long long>(1, p.stride / o.topk);
+    const long long ns = (in.ntiles + p.stride - 1) / p.stride;   // tiles the sample pass scores
+    if (p.form == FilterForm::Pieces) {
+        unsigned sb = (unsigned)in.num_cu * 2;  // 2 waves per SIMD, like the main pass
+        if (sb > kSampleBlocks)
+            sb = kSampleBlocks;
+        if (gy_sum > 1 && (size_t)sb * gy_sum > target_blocks)
+            sb = (target_blocks + gy_sum - 1) / gy_sum;
+        // at least 8 sampled tiles per wave: a wave's prologue (its query fragments, QT KiB) is not
+        // worth fewer, and the threshold kernel folds one partial row per block
+        if ((long long)sb * 32 > ns)
+            sb = (unsigned)((ns + 31) / 32);
+        if (sb < 1)
+            sb = 1;
+        if (o.topk > 0) {
+            // top-K: the threshold is the K-th smallest per-block minimum, so the pass needs well over K blocks (fewer than K
+            // blocks with a real row raises FALLBACK): at least 4K of them, as far as the sampled tiles go
+            const long long want = std::min<long long>(std::min<long long>(ns, kSampleBlocks), 4ll * o.topk);
+            if ((long long)sb < want)
+                sb = (unsigned)want;
         }
+        p.sample_blocks = sb;
+    } else {
+        // one sample block per range of the scan, as far as the sampled tiles (the chunked form: groups of CHK_T) go.  (The
+        // LDS-tiled sample pass — running minima only — keeps the 32 x 32 shape: with eight running minima the 16 x 16 form of
+        // it spilled.)
+        const long long units = p.form == FilterForm::Tiled ? ns : (ns + CHK_T - 1) / CHK_T;
+        p.sample_blocks = (unsigned)std::min<long long>(p.pieces[0].gx, units);
     }
-    for (int i = 0; i < np; ++i) {
-        const FilterPiece &p = pc[i];
-        if constexpr (KT == 1) {
-            switch (p.qt) {
-            case 2: launch_sample_piece<1, 2>(st, w, p, sb, stride, m_padded, s); break;
-            case 8: launch_sample_piece<1, 8>(st, w, p, sb, stride, m_padded, s); break;
-            case 16: launch_sample_piece<1, 16>(st, w, p, sb, stride, m_padded, s); break;
-            default: launch_sample_piece<1, 32>(st, w, p, sb, stride, m_padded, s); break;
-            }
-        } else if constexpr (KT == 2) {
-            if (p.qt == 8)
-                launch_sample_piece<2, 8>(st, w, p, sb, stride, m_padded, s);
-            else
-                launch_sample_piece<2, 16>(st, w, p, sb, stride, m_padded, s);
-        } else if constexpr (KT == 4) {
-            launch_sample_piece<4, 4>(st, w, p, sb, stride, m_padded, s);
-        } else {
-            launch_sample_piece<8, 2>(st, w, p, sb, stride, m_padded, s);
-        }
-        FTRY(hipGetLastError());
-    }
+    p.umin_floats = (size_t)p.sample_blocks * (size_t)qtiles * 32;
 
-    // 2. thresholds
-    int thr_nb = (int)sb;
-    if (st.topk > 0) {   // top-K: the K-th smallest real per-block minimum instead of the smallest (knn_topk_umin_kernel)
-        FTRY(knn_topk_umin_launch(w.umin, thr_nb, m_padded, st.topk, s));
-        thr_nb = 1;
-    }
-    hipLaunchKernelGGL(knn_thr_kernel, dim3((unsigned)(m_padded / 32)), dim3(32 * THR_PARTS), 0, s, w.umin,
-                       thr_nb, w.qry_norms, w.qry_amax, m, m_padded, st.k, st.kt, st.sigma, st.bmax, st.nmax, kAmaxLimit,
-                       w.thr, w.ctl, w.qpart, (m_padded + 255) / 256, w.counts, w.nlists);
-    FTRY(hipGetLastError());
+    // 2. thresholds: top-K takes the K-th smallest real per-block minimum instead of the smallest (knn_topk_umin_kernel)
+    p.topk = o.topk;
+    p.thr_nb = o.topk > 0 ? 1 : (int)p.sample_blocks;
+    p.thr_running = p.form == FilterForm::Tiled;
+    p.scan_running = p.thr_running && o.run_thresholds != 2;   // (read by the 16 x 16 scans only, KT >= 8)
 
-    // 3. the filter proper (timed: the dominant kernel).  Ordered after the other slot's scan.
-    if (!st.scan_done)
-        FTRY(hipEventCreateWithFlags(&st.scan_done, hipEventDisableTiming));
+    // 3. the scan (timed: the dominant kernel).
     // Scans of different slots: free to overlap (heads fill the other's tail, no event round trip:
     // -17 % per step at n = 2M, -5 % at 8M, -2.5 % at 16M with three batches in flight) unless the
     // shard is >= 16M rows, where they are chained so that a launch's duration stays that of the kernel
     // itself (the roofline is quoted from it; two 256-VGPR scans sharing the SIMDs take ~1.7x as long each).
-    const bool no_chain = st.chain_policy == 2 || (st.chain_policy == 0 && st.ntiles < (1ll << 19));
-    if (st.scan_recorded && !no_chain)
-        FTRY(hipStreamWaitEvent(s, st.scan_done, 0));
-    if (w.ev_begin)
-        FTRY(hipEventRecord(w.ev_begin, s));
-    for (int i = 0; i < np; ++i) {
-        const FilterPiece &p = pc[i];
-        if constexpr (KT == 1) {
-            switch (p.qt) {
-            case 2: launch_scan_piece<1, 2>(st, w, p, s); break;
-            case 8: launch_scan_piece<1, 8>(st, w, p, s); break;
-            case 16: launch_scan_piece<1, 16>(st, w, p, s); break;
-            default: launch_scan_piece<1, 32>(st, w, p, s); break;
-            }
-        } else if constexpr (KT == 2) {
-            if (p.qt == 8)
-                launch_scan_piece<2, 8>(st, w, p, s);
-            else
-                launch_scan_piece<2, 16>(st, w, p, s);
-        } else if constexpr (KT == 4) {
-            launch_scan_piece<4, 4>(st, w, p, s);
-        } else {
-            launch_scan_piece<8, 2>(st, w, p, s);
-        }
-        FTRY(hipGetLastError());
-    }
-    if (w.ev_end)
-        FTRY(hipEventRecord(w.ev_end, s));
-    if (!no_chain)
-        FTRY(hipEventRecord(st.scan_done, s));
-    st.scan_recorded = true;
-    return hipSuccess;
-}
-
-template <int KT, int QT>
-static hipError_t launch_filter_tiled(FilterState &st, FilterWorkspace &w, int m, int num_cu, hipStream_t s)
-{
-    const int qtiles = (m + 31) / 32;
-    const int m_padded = qtiles * 32;
-    const unsigned gy = (unsigned)((qtiles + 4 * QT - 1) / (4 * QT));
-    const unsigned target_blocks = (unsigned)num_cu * 8;
-    unsigned gx = (target_blocks + gy - 1) / gy;
-    if ((long long)gx > st.ntiles)
-        gx = (unsigned)st.ntiles;
-    if (gx < 1)
-        gx = 1;
-    while ((size_t)gx * 4 * gy > kMaxLists && gx > 1)
-        gx = (gx + 1) / 2;
-    if ((size_t)gx * 4 * gy > kMaxLists)
-        return hipErrorInvalidValue;
-    w.nlists = gx * 4 * gy;
-    w.slice = w.rec_cap / w.nlists;
-
-    long long stride = st.ntiles / 256;
-    if (stride < 1)
-        stride = 1;
-    if (stride > 16)
-        stride = 16;
-    // Running thresholds (KT = 8, round 5): the scan tightens every query's threshold as it goes, so the sample pass only has
-    // to give it a start — every 32nd tile instead of every 8th at C5 (2048 tiles): the pass shrinks 4x, the candidates grow
-    // from 210k to 355k of the 642k a fixed threshold left, ms per step 0.9155 (stride 8) / 0.8909 (16) / 0.8829 (32) / 0.9091
-    // (64) / 0.9378 (128) on one box (profiles/r05_c5_running_thresholds.txt).  KNN_MI355X_SAMPLE_STRIDE: the sweep's knob.
-    if (KT >= 8 && st.run_thresholds != 2)   // (KT = 16, 32: k 129 .. 512, the same scheme since the end of round 5)
-        stride = std::min<long long>(32, std::max<long long>(1, st.ntiles / 64));
-    if (st.sample_stride > 0)   // option `sample_stride` (the sweep's knob, and the tests' like-for-like comparison)
-        stride = std::min<long long>(st.sample_stride, std::max<long long>(1, st.ntiles / 16));
-    if (st.topk > 0)   // top-K: a threshold from the K-th block minimum passes ~ n K / (sampled rows) rows: sample K times denser
-        stride = std::max<long long>(1, stride / st.topk);
-    const long long ns = (st.ntiles + stride - 1) / stride;
-    unsigned sb = gx;
-    if ((long long)sb > ns)
-        sb = (unsigned)ns;
-    {
-        const size_t need = (size_t)sb * (size_t)m_padded;
-        if (need > w.umin_cap) {
-            (void)KNN_DEV_FREE(w.umin);
-            w.umin = nullptr;
-            w.umin_cap = 0;
-            FTRY(KNN_DEV_ALLOC((void **)&w.umin, need * sizeof(float)));
-            w.umin_cap = need;
-        }
-    }
-    // (the sample pass — 1 / 16 of the tiles, running minima only — keeps the 32 x 32 shape: with eight running minima the
-    // 16 x 16 form of it spilled)
-    hipLaunchKernelGGL((knn_filter_tiled_kernel<KT, QT, true>), dim3(sb, gy), dim3(FILTER_BLOCK), 0, s,
-                       (const h8 *)st.ref_frags, st.ref_norms, (const h8 *)w.qry_frags, w.thr, qtiles, st.ntiles,
-                       stride, w.umin, m_padded, w.records, w.counts, w.ctl, w.slice,
-                       (unsigned short *)(w.records + w.rec_cap));
-    FTRY(hipGetLastError());
-    int thr_nb = (int)sb;
-    if (st.topk > 0) {   // top-K: the K-th smallest real per-block minimum instead of the smallest (knn_topk_umin_kernel)
-        FTRY(knn_topk_umin_launch(w.umin, thr_nb, m_padded, st.topk, s));
-        thr_nb = 1;
-    }
-    hipLaunchKernelGGL(knn_thr_kernel, dim3((unsigned)(m_padded / 32)), dim3(32 * THR_PARTS), 0, s, w.umin,
-                       thr_nb, w.qry_norms, w.qry_amax, m, m_padded, st.k, st.kt, st.sigma, st.bmax, st.nmax, kAmaxLimit,
-                       w.thr, w.ctl, w.qpart, (m_padded + 255) / 256, w.counts, w.nlists, nullptr,
-                       w.thr + (size_t)w.m_cap, w.thr + 2 * (size_t)w.m_cap, (unsigned *)(w.thr + 3 * (size_t)w.m_cap));
-    FTRY(hipGetLastError());
-    if (!st.scan_done)
-        FTRY(hipEventCreateWithFlags(&st.scan_done, hipEventDisableTiming));
-    // Scans of different slots: free to overlap unless the shard is >= 16M rows (as in launch_filter).
     // Chaining the deep-K scans was measured at C5 (k 128, m = n = 65536; profiles/r02_c5_chain_ab.txt): a
     // launch's duration drops from 1.64 to 1.00 ms (0.84 with the GPU to itself) but the step goes UP, 1.043 ->
     // 1.081 ms: the other batch's sample pass, re-rank (640k records) and fragment kernels are ~0.25 ms of real
     // work that overlapping scans were absorbing in each other's tails.
-    const bool no_chain = st.chain_policy == 2 || (st.chain_policy == 0 && st.ntiles < (1ll << 19));
-    if (st.scan_recorded && !no_chain)
+    // The chunked scan (k > 512) has always stayed outside the chain: it neither waits on nor records scan_done, and does not
+    // count as a recorded scan.  Nothing on record says whether that was meant; it is kept as it was.
+    p.in_chain = p.form != FilterForm::Chunked;
+    p.chained = p.in_chain && !(o.chain_policy == 2 || (o.chain_policy == 0 && in.ntiles < (1ll << 19)));
+    p.has_rows = p.form != FilterForm::Pieces;
+    if (p.form == FilterForm::Pieces) {
+        p.rerank.n = p.npieces;
+        for (int i = 0; i < 4; ++i) {
+            p.rerank.list_base[i] = i < p.npieces ? p.pieces[i].list_base : 0xFFFFFFFFu;
+            p.rerank.qrow_base[i] = i < p.npieces ? (unsigned)p.pieces[i].begin * 32u : 0u;
+        }
+    }
+    p.ok = true;
+    return p;
+}
+
+// The launches of one batch, each kernel instantiation named once: a form's sample pass and scan for one piece.
+struct FilterBatch {
+    const FilterState &st;
+    const FilterWorkspace &w;
+    const FilterQueryPlan &p;
+    int qtiles, m_padded;
+    hipStream_t s;
+};
+typedef void (*FilterLaunch)(const FilterBatch &, const FilterPiece &);
+struct FilterKernels {
+    FilterLaunch sample, scan;
+};
+
+template <int KT, int QT>
+static FilterKernels filter_pieces_of()
+{
+    return {[](const FilterBatch &b, const FilterPiece &pc) {
+                hipLaunchKernelGGL((knn_filter_sample_kernel<KT, QT>), dim3(b.p.sample_blocks, pc.gy), dim3(FILTER_BLOCK), 0, b.s,
+                                   (const h8 *)b.st.ref_frags, b.st.ref_norms, (const h8 *)b.w.qry_frags, pc.begin + pc.count, b.st.ntiles,
+                                   b.p.stride, b.w.umin, b.m_padded, b.w.ctl, pc.begin);
+            },
+            [](const FilterBatch &b, const FilterPiece &pc) {
+                const FilterWorkspace &w = b.w;
+                hipLaunchKernelGGL((knn_filter_kernel<KT, QT>), dim3(pc.gx, pc.gy), dim3(FILTER_BLOCK), 0, b.s,
+                                   (const h8 *)b.st.ref_frags, b.st.ref_norms, (const h8 *)w.qry_frags + (size_t)pc.begin * KT * 64,
+                                   w.thr + (size_t)pc.begin * 32, pc.count, b.st.ntiles, w.records + (size_t)pc.list_base * w.slice,
+                                   w.counts + pc.list_base, w.ctl, w.slice);
+            }};
+}
+
+// The scan: k > 64 (KT = 8): four reference tiles per barrier staged by LDS-DMA (-2.4 % at C5 against one tile per barrier
+// through registers); k > 128: one tile per barrier — a tile is 16 or 32 KiB there, four of them twice over do not fit the LDS.
+// (8 waves per block and two tiles per barrier were measured too: profiles/r02_c5_variants.txt, r03_deepk.txt.)
+// 16 x 16 shape (X16) from k = 65 up: measured -8 % at k 128, -6 % at k 256 and 512, +7 % at k 64 where a tile is only 16 MFMAs.
+template <int KT, int QT>
+static FilterKernels filter_tiled_of()
+{
+    return {[](const FilterBatch &b, const FilterPiece &pc) {
+                const FilterWorkspace &w = b.w;
+                hipLaunchKernelGGL((knn_filter_tiled_kernel<KT, QT, true>), dim3(b.p.sample_blocks, pc.gy), dim3(FILTER_BLOCK), 0, b.s,
+                                   (const h8 *)b.st.ref_frags, b.st.ref_norms, (const h8 *)w.qry_frags, w.thr, b.qtiles, b.st.ntiles,
+                                   b.p.stride, w.umin, b.m_padded, w.records, w.counts, w.ctl, w.slice,
+                                   (unsigned short *)(w.records + w.rec_cap));
+            },
+            [](const FilterBatch &b, const FilterPiece &pc) {
+                const FilterWorkspace &w = b.w;
+                const size_t mc = (size_t)w.m_cap;
+                hipLaunchKernelGGL((knn_filter_tiled_kernel<KT, QT, false, FILTER_BLOCK, KT == 8 ? 4 : 1, (KT > 4)>), dim3(pc.gx, pc.gy),
+                                   dim3(FILTER_BLOCK), 0, b.s, (const h8 *)b.st.ref_frags, b.st.ref_norms, (const h8 *)w.qry_frags, w.thr,
+                                   b.qtiles, b.st.ntiles, 1ll, w.umin, b.m_padded, w.records, w.counts, w.ctl, w.slice,
+                                   (unsigned short *)(w.records + w.rec_cap), b.p.scan_running ? w.thr + mc : nullptr, w.thr + 2 * mc,
+                                   b.p.scan_running ? (unsigned *)(w.thr + 3 * mc) : nullptr);
+            }};
+}
+
+// (the scan's grid is one-dimensional: gx ranges x gy query groups rounded up to eight, see the kernel)
+static FilterKernels filter_chunked()
+{
+    return {[](const FilterBatch &b, const FilterPiece &pc) {
+                const FilterWorkspace &w = b.w;
+                hipLaunchKernelGGL(knn_filter_chunked_kernel<true>, dim3(b.p.sample_blocks, pc.gy), dim3(FILTER_BLOCK), 0, b.s,
+                                   (const h8 *)b.st.ref_frags, b.st.ref_norms, (const h8 *)w.qry_frags, w.thr, b.st.kt, b.qtiles,
+                                   b.st.ntiles, b.p.stride, w.umin, b.m_padded, w.records, w.counts, w.ctl, w.slice,
+                                   (unsigned short *)(w.records + w.rec_cap), 0u, pc.gy);
+            },
+            [](const FilterBatch &b, const FilterPiece &pc) {
+                const FilterWorkspace &w = b.w;
+                hipLaunchKernelGGL(knn_filter_chunked_kernel<false>, dim3(pc.gx * ((pc.gy + 7u) / 8u) * 8u), dim3(FILTER_BLOCK), 0, b.s,
+                                   (const h8 *)b.st.ref_frags, b.st.ref_norms, (const h8 *)w.qry_frags, w.thr, b.st.kt, b.qtiles,
+                                   b.st.ntiles, 1ll, w.umin, b.m_padded, w.records, w.counts, w.ctl, w.slice,
+                                   (unsigned short *)(w.records + w.rec_cap), pc.gx, pc.gy);
+            }};
+}
+
+// The plan's (form, KT, QT) -> its launches: the instantiations the code object holds.
+static FilterKernels filter_kernels(FilterForm form, int kt, int qt)
+{
+    if (form == FilterForm::Chunked)
+        return filter_chunked();
+    if (form == FilterForm::Tiled)
+        return kt == 4 ? filter_tiled_of<4, 4>() : kt == 8 ? filter_tiled_of<8, 4>() : kt == 16 ? filter_tiled_of<16, 2>() : filter_tiled_of<32, 1>();
+    if (kt == 1)
+        return qt == 2 ? filter_pieces_of<1, 2>() : qt == 8 ? filter_pieces_of<1, 8>() : qt == 16 ? filter_pieces_of<1, 16>() : filter_pieces_of<1, 32>();
+    if (kt == 2)
+        return qt == 8 ? filter_pieces_of<2, 8>() : filter_pieces_of<2, 16>();
+    return kt == 4 ? filter_pieces_of<4, 4>() : filter_pieces_of<8, 2>();
+}
+
+// The start of a batch on the dense layouts (1-NN and top-K): workspace, control block 0, [fill_keys set to (+INF, 0)], the
+// query fragments.
+static hipError_t filter_prelude(FilterState &st, FilterWorkspace &w, int m, const float *q, u64 *fill_keys, hipStream_t s)
+{
+    FTRY(ensure_workspace(st, w, m));
+    w.ctl_cur = w.ctl;
+    w.ovf_base = w.ovf_cap = 0u;
+    if (fill_keys)
+        FTRY(knn_keys_fill_launch(fill_keys, m, s));
+    return prep_queries(st, w, m, q, s);
+}
+
+// One batch as its plan says: sample pass -> [top-K: the K-th minimum] -> thresholds -> [the slots' chain] -> scan, records
+// in w's lists.
+static hipError_t filter_scan(FilterState &st, FilterWorkspace &w, const FilterQueryPlan &p, int m, hipStream_t s)
+{
+    if (!p.ok)
+        return hipErrorInvalidValue;
+    const int qtiles = (m + 31) / 32;
+    const int m_padded = qtiles * 32;
+    w.nlists = p.nlists;
+    w.slice = p.slice;
+    w.has_rows = p.has_rows;
+    w.pieces = p.rerank;
+    if (p.umin_floats > w.umin_cap) {   // per-block minima buffer, grown on demand
+        (void)KNN_DEV_FREE(w.umin);
+        w.umin = nullptr;
+        w.umin_cap = 0;
+        FTRY(KNN_DEV_ALLOC((void **)&w.umin, p.umin_floats * sizeof(float)));
+        w.umin_cap = p.umin_floats;
+    }
+    const FilterBatch b{st, w, p, qtiles, m_padded, s};
+    for (int i = 0; i < p.npieces; ++i) {
+        filter_kernels(p.form, p.kt, p.pieces[i].qt).sample(b, p.pieces[i]);
+        FTRY(hipGetLastError());
+    }
+    if (p.topk > 0)
+        FTRY(knn_topk_umin_launch(w.umin, (int)p.sample_blocks, m_padded, p.topk, s));
+    const size_t mc = (size_t)w.m_cap;
+    hipLaunchKernelGGL(knn_thr_kernel, dim3((unsigned)(m_padded / 32)), dim3(32 * THR_PARTS), 0, s, w.umin, p.thr_nb, w.qry_norms,
+                       w.qry_amax, m, m_padded, st.k, st.kt, st.sigma, st.bmax, st.nmax, kAmaxLimit, w.thr, w.ctl, w.qpart,
+                       (m_padded + 255) / 256, w.counts, w.nlists, nullptr, p.thr_running ? w.thr + mc : nullptr,
+                       p.thr_running ? w.thr + 2 * mc : nullptr, p.thr_running ? (unsigned *)(w.thr + 3 * mc) : nullptr);
+    FTRY(hipGetLastError());
+    if (p.in_chain && !st.scan_done)
+        FTRY(hipEventCreateWithFlags(&st.scan_done, hipEventDisableTiming));
+    if (p.chained && st.scan_recorded)   // ordered after the other slot's scan
         FTRY(hipStreamWaitEvent(s, st.scan_done, 0));
     if (w.ev_begin)
         FTRY(hipEventRecord(w.ev_begin, s));
-    // k > 64 (KT = 8): four reference tiles per barrier staged by LDS-DMA (-2.4 % at C5 against one tile per barrier through
-    // registers); k > 128: one tile per barrier — a tile is 16 or 32 KiB there, four of them twice over do not fit the LDS.
-    // (8 waves per block and two tiles per barrier were measured too: profiles/r02_c5_variants.txt, r03_deepk.txt.)
-    if constexpr (KT == 8)
-        hipLaunchKernelGGL((knn_filter_tiled_kernel<KT, QT, false, FILTER_BLOCK, 4, true>), dim3(gx, gy), dim3(FILTER_BLOCK), 0, s,
-                           (const h8 *)st.ref_frags, st.ref_norms, (const h8 *)w.qry_frags, w.thr, qtiles, st.ntiles,
-                           1ll, w.umin, m_padded, w.records, w.counts, w.ctl, w.slice,
-                           (unsigned short *)(w.records + w.rec_cap),
-                           st.run_thresholds != 2 ? w.thr + (size_t)w.m_cap : nullptr, w.thr + 2 * (size_t)w.m_cap,
-                           st.run_thresholds != 2 ? (unsigned *)(w.thr + 3 * (size_t)w.m_cap) : nullptr);
-    else   // (16 x 16 shape from k = 65 up: measured -8 % at k 128, -6 % at k 256 and 512, +7 % at k 64 where a tile is only 16 MFMAs)
-        hipLaunchKernelGGL((knn_filter_tiled_kernel<KT, QT, false, FILTER_BLOCK, 1, (KT > 4)>), dim3(gx, gy), dim3(FILTER_BLOCK), 0, s,
-                           (const h8 *)st.ref_frags, st.ref_norms, (const h8 *)w.qry_frags, w.thr, qtiles, st.ntiles,
-                           1ll, w.umin, m_padded, w.records, w.counts, w.ctl, w.slice,
-                           (unsigned short *)(w.records + w.rec_cap),
-                           st.run_thresholds != 2 ? w.thr + (size_t)w.m_cap : nullptr, w.thr + 2 * (size_t)w.m_cap,
-                           st.run_thresholds != 2 ? (unsigned *)(w.thr + 3 * (size_t)w.m_cap) : nullptr);
-    w.has_rows = true;
-    w.pieces = RerankPieces();
-    FTRY(hipGetLastError());
+    for (int i = 0; i < p.npieces; ++i) {
+        filter_kernels(p.form, p.kt, p.pieces[i].qt).scan(b, p.pieces[i]);
+        FTRY(hipGetLastError());
+    }
     if (w.ev_end)
         FTRY(hipEventRecord(w.ev_end, s));
-    if (!no_chain)
+    if (p.chained)
         FTRY(hipEventRecord(st.scan_done, s));
-    st.scan_recorded = true;
+    if (p.in_chain)
+        st.scan_recorded = true;
     return hipSuccess;
 }
 
-// k > 512: the chunked-K scan (knn_filter_chunked_kernel), sample pass -> thresholds -> scan, as launch_filter_tiled.
-static hipError_t launch_filter_chunked(FilterState &st, FilterWorkspace &w, int m, int num_cu, hipStream_t s)
-{
-    const int qtiles = (m + 31) / 32;
-    const int m_padded = qtiles * 32;
-    const unsigned gy = (unsigned)((qtiles + 4 * CHK_QT - 1) / (4 * CHK_QT));
-    const long long groups = (st.ntiles + CHK_T - 1) / CHK_T;
-    // ranges of reference tiles: enough blocks for the chip, and at least 16 so that an XCD's 64 resident blocks are FEW
-    // query groups (see the kernel: their B fragments have to fit its L2)
-    // (measured: 8 / 16 / 32 / 64 ranges within 2 % of each other at (1024, 65536, 65536); four blocks per CU in all instead of
-    // eight: the mid-size shapes' step 2-9 % shorter — profiles/r04_deepk.txt)
-    unsigned gx = std::max(16u, ((unsigned)num_cu * 4u + gy - 1) / gy);
-    if ((long long)gx > groups)
-        gx = (unsigned)groups;
-    if (gx < 1)
-        gx = 1;
-    while ((size_t)gx * 4 * gy > kMaxLists && gx > 1)
-        gx = (gx + 1) / 2;
-    if ((size_t)gx * 4 * gy > kMaxLists)
-        return hipErrorInvalidValue;
-    w.nlists = gx * 4 * gy;
-    w.slice = w.rec_cap / w.nlists;
-    long long stride = st.ntiles / 256;
-    if (stride < 1)
-        stride = 1;
-    if (stride > 16)
-        stride = 16;
-    if (st.topk > 0)   // top-K: a threshold from the K-th block minimum passes ~ n K / (sampled rows) rows: sample K times denser
-        stride = std::max<long long>(1, stride / st.topk);
-    const long long sgroups = ((st.ntiles + stride - 1) / stride + CHK_T - 1) / CHK_T;
-    unsigned sb = gx;
-    if ((long long)sb > sgroups)
-        sb = (unsigned)sgroups;
-    {
-        const size_t need = (size_t)sb * (size_t)m_padded;
-        if (need > w.umin_cap) {
-            (void)KNN_DEV_FREE(w.umin);
-            w.umin = nullptr;
-            w.umin_cap = 0;
-            FTRY(KNN_DEV_ALLOC((void **)&w.umin, need * sizeof(float)));
-            w.umin_cap = need;
-        }
-    }
-    hipLaunchKernelGGL(knn_filter_chunked_kernel<true>, dim3(sb, gy), dim3(FILTER_BLOCK), 0, s, (const h8 *)st.ref_frags,
-                       st.ref_norms, (const h8 *)w.qry_frags, w.thr, st.kt, qtiles, st.ntiles, stride, w.umin, m_padded, w.records,
-                       w.counts, w.ctl, w.slice, (unsigned short *)(w.records + w.rec_cap), 0u, gy);
-    FTRY(hipGetLastError());
-    int thr_nb = (int)sb;
-    if (st.topk > 0) {   // top-K: the K-th smallest real per-block minimum instead of the smallest (knn_topk_umin_kernel)
-        FTRY(knn_topk_umin_launch(w.umin, thr_nb, m_padded, st.topk, s));
-        thr_nb = 1;
-    }
-    hipLaunchKernelGGL(knn_thr_kernel, dim3((unsigned)(m_padded / 32)), dim3(32 * THR_PARTS), 0, s, w.umin,
-                       thr_nb, w.qry_norms, w.qry_amax, m, m_padded, st.k, st.kt, st.sigma, st.bmax, st.nmax, kAmaxLimit,
-                       w.thr, w.ctl, w.qpart, (m_padded + 255) / 256, w.counts, w.nlists);
-    FTRY(hipGetLastError());
-    if (w.ev_begin)
-        FTRY(hipEventRecord(w.ev_begin, s));
-    hipLaunchKernelGGL(knn_filter_chunked_kernel<false>, dim3(gx * ((gy + 7u) / 8u) * 8u), dim3(FILTER_BLOCK), 0, s,
-                       (const h8 *)st.ref_frags, st.ref_norms, (const h8 *)w.qry_frags, w.thr, st.kt, qtiles, st.ntiles, 1ll, w.umin,
-                       m_padded, w.records, w.counts, w.ctl, w.slice, (unsigned short *)(w.records + w.rec_cap), gx, gy);
-    w.has_rows = true;
-    w.pieces = RerankPieces();
-    FTRY(hipGetLastError());
-    if (w.ev_end)
-        FTRY(hipEventRecord(w.ev_end, s));
-    return hipSuccess;
-}
-
-// The sample pass, thresholds and scan for the index's K-steps (kt): records in w's lists.
-static hipError_t launch_scan_for_kt(FilterState &st, FilterWorkspace &w, int m, int num_cu, hipStream_t s)
-{
-    const int qtiles = (m + 31) / 32;
-    switch (st.kt) {
-    case 1: FTRY(launch_filter<1>(st, w, m, num_cu, s)); break;
-    case 2: FTRY(launch_filter<2>(st, w, m, num_cu, s)); break;
-    case 4:
-        if (qtiles >= 16)
-            FTRY((launch_filter_tiled<4, 4>(st, w, m, num_cu, s)));
-        else
-            FTRY(launch_filter<4>(st, w, m, num_cu, s));
-        break;
-    case 8:
-        if (qtiles >= 16)
-            FTRY((launch_filter_tiled<8, 4>(st, w, m, num_cu, s)));
-        else
-            FTRY(launch_filter<8>(st, w, m, num_cu, s));
-        break;
-    // 128 < k <= 512: always the LDS-tiled scan (a reference tile is 16 / 32 KiB: no wave can hold one in registers beside its
-    // queries); the B operands of 2 / 1 blocks of 32 queries are the wave's 128 operand registers
-    case 16: FTRY((launch_filter_tiled<16, 2>(st, w, m, num_cu, s))); break;
-    case 32: FTRY((launch_filter_tiled<32, 1>(st, w, m, num_cu, s))); break;
-    default:   // k > 512: K in chunks of 128 dimensions
-        if (st.kt % CHK_KC != 0)
-            return hipErrorInvalidValue;
-        FTRY(launch_filter_chunked(st, w, m, num_cu, s));
-        break;
-    }
-    return hipSuccess;
-}
-
-hipError_t knn_filter_query(FilterState &st, int slot, int m, const float *q, const float *r, long long base,
+hipError_t knn_filter_query(FilterState &st, FilterCallOptions opt, int slot, int m, const float *q, const float *r, long long base,
                             u64 *keys, int num_cu, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end, bool init_keys,
                             int *out_idx)
 {
@@ -2667,7 +2598,7 @@ hipError_t knn_filter_query(FilterState &st, int slot, int m, const float *q, co
     // raises its own FALLBACK flag on the device and is answered by the gated exact scan; the next batch is back on
     // the pruned path.  (Round 2 sent the whole index to full scans for 256 calls after such a batch, on a pinned
     // host word read here whenever the host happened to get to it.)
-    const bool cells = st.cells && (st.cells_policy != 2 || st.cells->centred) && st.kt <= 2;   // (per-cell frames: the full scan cannot read them)
+    const bool cells = st.cells && (opt.cells_policy != 2 || st.cells->centred) && st.kt <= 2;   // (per-cell frames: the full scan cannot read them)
     w.last_used_cells = cells;
     w.ev_begin = ev_begin;
     w.ev_end = ev_end;
@@ -2678,17 +2609,12 @@ hipError_t knn_filter_query(FilterState &st, int slot, int m, const float *q, co
             const int mb = std::min(cell_batch, m - q0);
             const float *qb = q + (size_t)q0 * st.k;
             u64 *kb = keys + q0;
-            FTRY(knn_cells_query(st, w, mb, qb, r, base, kb, num_cu, q0 == 0, s, init_keys, out_idx ? out_idx + q0 : nullptr));
+            FTRY(knn_cells_query(st, w, opt, mb, qb, r, base, kb, num_cu, q0 == 0, s, init_keys, out_idx ? out_idx + q0 : nullptr));
         }
         return hipSuccess;
     }
-    FTRY(ensure_workspace(st, w, m));
-    w.ctl_cur = w.ctl;
-    w.ovf_base = w.ovf_cap = 0u;
-    if (init_keys)
-        FTRY(knn_keys_fill_launch(keys, m, s));
-    FTRY(prep_queries(st, w, m, q, s));
-    FTRY(launch_scan_for_kt(st, w, m, num_cu, s));
+    FTRY(filter_prelude(st, w, m, q, init_keys ? keys : nullptr, s));
+    FTRY(filter_scan(st, w, knn_filter_query_plan({st.kt, st.ntiles, m, num_cu, w.rec_cap, opt}), m, s));
     // exact re-rank of the survivors; a list that overflowed its slice raises the fallback flag
     FTRY(knn_rerank_launch(st.k, positions, q, r, base, w.records,
                            w.has_rows ? (const unsigned short *)(w.records + w.rec_cap) : nullptr, w.counts, w.nlists,
@@ -2704,10 +2630,10 @@ hipError_t knn_filter_query(FilterState &st, int slot, int m, const float *q, co
 
 // Top-K on the filter (include/knn_mi355x.h §2c): the dense layouts, or a cell-sorted layout in the shard's frame
 // scanned in full through perm.  The scan is the 1-NN one; its threshold comes from the K-th smallest real per-block sample
-// minimum (st.topk), running thresholds are off (the caller sets them so).  Records and outlier rows go to per-query candidate
-// lists, a select kernel keeps the K smallest; a batch that raised FALLBACK (a query nothing bounds, fewer than K sampled
-// blocks with a real row, records or candidates overflowing) is answered by the gated exact top-K instead.
-hipError_t knn_filter_query_topk(FilterState &st, int slot, int m, int K, const float *q, const float *r, long long base,
+// minimum (opt.topk = K), running thresholds are off (the caller's options say so).  Records and outlier rows go to per-query
+// candidate lists, a select kernel keeps the K smallest; a batch that raised FALLBACK (a query nothing bounds, fewer than K
+// sampled blocks with a real row, records or candidates overflowing) is answered by the gated exact top-K instead.
+hipError_t knn_filter_query_topk(FilterState &st, FilterCallOptions opt, int slot, int m, const float *q, const float *r, long long base,
                                  u64 *keys, bool init_keys, u64 *cand, unsigned *ccount, unsigned ccap, u64 *part,
                                  size_t part_bytes, int num_cu, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end)
 {
@@ -2717,15 +2643,10 @@ hipError_t knn_filter_query_topk(FilterState &st, int slot, int m, int K, const 
     w.last_used_cells = false;
     w.ev_begin = ev_begin;
     w.ev_end = ev_end;
-    FTRY(ensure_workspace(st, w, m));
-    w.ctl_cur = w.ctl;
-    w.ovf_base = w.ovf_cap = 0u;
-    FTRY(prep_queries(st, w, m, q, s));
+    const int K = opt.topk;
+    FTRY(filter_prelude(st, w, m, q, nullptr, s));
     FTRY(hipMemsetAsync(ccount, 0, (size_t)m * sizeof(unsigned), s));
-    st.topk = K;
-    const hipError_t e = launch_scan_for_kt(st, w, m, num_cu, s);
-    st.topk = 0;
-    FTRY(e);
+    FTRY(filter_scan(st, w, knn_filter_query_plan({st.kt, st.ntiles, m, num_cu, w.rec_cap, opt}), m, s));
     const unsigned *perm = st.cells ? st.cells->perm : nullptr;
     const long long positions = st.cells ? st.ntiles * 32 : st.n;
     FTRY(knn_topk_filter_finish(st.k, m, K, positions, base, q, r, w.records,
@@ -2738,6 +2659,19 @@ hipError_t knn_filter_query_topk(FilterState &st, int slot, int m, int K, const 
     return hipSuccess;
 }
 
+// knn_filter_debug's scores: knn_filter_scores_kernel<KT>, KT = 0: knn_filter_scores_rt_kernel (run-time kt, k > 512).
+template <int KT>
+static void filter_scores_as(const FilterState &st, const FilterWorkspace &w, int m, float *scores, hipStream_t s)
+{
+    const dim3 grid((unsigned)st.ntiles, (unsigned)((m + 31) / 32));
+    if constexpr (KT == 0)
+        hipLaunchKernelGGL(knn_filter_scores_rt_kernel, grid, dim3(64), 0, s, (const h8 *)st.ref_frags, st.ref_norms,
+                           (const h8 *)w.qry_frags, st.kt, m, st.n, scores);
+    else
+        hipLaunchKernelGGL(knn_filter_scores_kernel<KT>, grid, dim3(64), 0, s, (const h8 *)st.ref_frags, st.ref_norms,
+                           (const h8 *)w.qry_frags, m, st.n, scores);
+}
+
 hipError_t knn_filter_debug(FilterState &st, int m, const float *q, const float *r, float *scores,
                             float *thr_out, float *qnorm_out, double consts[8], hipStream_t s)
 {
@@ -2746,17 +2680,8 @@ hipError_t knn_filter_debug(FilterState &st, int m, const float *q, const float 
         return hipErrorInvalidValue;  // scores[q][row] assumes the layout is in row order
     FTRY(ensure_workspace(st, w, m));
     FTRY(prep_queries(st, w, m, q, s));
-    const int qtiles = (m + 31) / 32;
-    const dim3 grid((unsigned)st.ntiles, (unsigned)qtiles);
-    switch (st.kt) {
-    case 1: hipLaunchKernelGGL(knn_filter_scores_kernel<1>, grid, dim3(64), 0, s, (const h8 *)st.ref_frags, st.ref_norms, (const h8 *)w.qry_frags, m, st.n, scores); break;
-    case 2: hipLaunchKernelGGL(knn_filter_scores_kernel<2>, grid, dim3(64), 0, s, (const h8 *)st.ref_frags, st.ref_norms, (const h8 *)w.qry_frags, m, st.n, scores); break;
-    case 4: hipLaunchKernelGGL(knn_filter_scores_kernel<4>, grid, dim3(64), 0, s, (const h8 *)st.ref_frags, st.ref_norms, (const h8 *)w.qry_frags, m, st.n, scores); break;
-    case 8: hipLaunchKernelGGL(knn_filter_scores_kernel<8>, grid, dim3(64), 0, s, (const h8 *)st.ref_frags, st.ref_norms, (const h8 *)w.qry_frags, m, st.n, scores); break;
-    case 16: hipLaunchKernelGGL(knn_filter_scores_kernel<16>, grid, dim3(64), 0, s, (const h8 *)st.ref_frags, st.ref_norms, (const h8 *)w.qry_frags, m, st.n, scores); break;
-    case 32: hipLaunchKernelGGL(knn_filter_scores_kernel<32>, grid, dim3(64), 0, s, (const h8 *)st.ref_frags, st.ref_norms, (const h8 *)w.qry_frags, m, st.n, scores); break;
-    default: hipLaunchKernelGGL(knn_filter_scores_rt_kernel, grid, dim3(64), 0, s, (const h8 *)st.ref_frags, st.ref_norms, (const h8 *)w.qry_frags, st.kt, m, st.n, scores); break;
-    }
+    (st.kt == 1 ? filter_scores_as<1> : st.kt == 2 ? filter_scores_as<2> : st.kt == 4 ? filter_scores_as<4> : st.kt == 8 ? filter_scores_as<8>
+     : st.kt == 16 ? filter_scores_as<16> : st.kt == 32 ? filter_scores_as<32> : filter_scores_as<0>)(st, w, m, scores, s);
     FTRY(hipGetLastError());
     FTRY(hipMemcpyAsync(qnorm_out, w.qry_norms, (size_t)m * sizeof(float), hipMemcpyDeviceToDevice, s));
     const int qblocks = ((m + 31) / 32 * 32 + 255) / 256;
