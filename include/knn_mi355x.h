@@ -298,7 +298,15 @@ int knn_index_query_topk_host(knn_index *idx, int m, int K, const float *queries
  *             dimension: the layout stays in the shard's one frame and the scan takes a per-query operand), 1 = each cell's own
  *             frame, 0 = auto (bins where they fit the cells — uniform-like rows —, per-cell frames on clustered data).  Read when
  *             an index is built; results are identical either way.  knn_get_option("cells_u8_bin_builds") counts the layouts built
- *             with bin frames (read-only).  Either way the top-K queries of an index with 8-bit rows take the exact top-K scan.
+ *             with bin frames (read-only).  Top-K queries: bin frames can take the cell-pruned scan ("topk_cells"), per-cell
+ *             frames take the exact top-K scan.
+ *   "topk_cells" top-K queries (knn_index_query_topk) on the cell-pruned scan, for cell-sorted layouts in the shard's one frame
+ *             (fp16 rows without per-cell frames, 8-bit rows in bin frames; k <= 32, m >= 5, not a cell-range shard):
+ *             0 = library policy: for now the same as 2 — the policy sends a call to this path only where it is measured faster
+ *             than the path it replaces, and those measurements are not taken yet (it will start at the row count from which the
+ *             library builds the cell-sorted layout on its own for that k);
+ *             1 = wherever the layout allows it; 2 = never (the MFMA filter's full scan or the exact top-K scan, as before).
+ *             Read at every call; results are identical either way.
  *   "cells_lists" who makes a cell's list of queries (those of the batch that cannot rule the cell out) on the pruned path:
  *             1 = knn_cells_match_kernel in a launch of its own between the preparation and the scan (lists in memory),
  *             2 = the scan's waves for the items they take (same test, same arithmetic, lists in LDS: one launch and one
@@ -333,7 +341,8 @@ long long knn_get_option(const char *name);
  *       nothing bounds: not finite, far outside the references' box); 2 = cell-pruned path only: more candidates than the
  *       record buffers hold (rows of a cluster tighter than the fp16 step), the batch's listed (cell, query) pairs were
  *       evaluated with the exact arithmetic — the cells the geometry ruled out stay ruled out
- *   [3] reference rows outside the filter's robust box (scanned exactly on every query) */
+ *   [3] reference rows outside the filter's robust box (scanned exactly on every query)
+ * A call of more than 1024 queries on the cell-pruned paths runs in passes of 1024: [1] and [2] are those of the LAST pass. */
 int knn_index_last_stats(knn_index *idx, long long stats[4]);
 
 /* Test / development hook: counters of the most recent batch on the cell-pruned path (call after synchronising; all 0
@@ -375,6 +384,24 @@ int knn_debug_scan_plan_ex(int num_cu, int blocks_per_cu, unsigned nitems, int m
  * tail: K, KT, blocks; 1 if the gated exact scan is a launch of its own; the LDS limits of the scan and the match kernel
  * (0: the default)}. */
 int knn_debug_cells_query_plan(const long long in[14], long long out[28]);
+/* Test hook (host arithmetic only, no GPU needed): whether a top-K call takes the cell-pruned scan and what one of its passes
+ * launches with.  in = {k, K, m (the call's queries), rows of the shard, option topk_cells, 1 if a cell-sorted layout exists,
+ * centred, rows_u8, 1 if the 8-bit rows are in bin frames, 1 for a cell-range shard, out-of-box rows, ncells, nitems, cap,
+ * several_slots, scan_blocks, scan_deal, num_cu, rec_cap, option cells};
+ * out = {1 if pruned; prep: PW, KT, CTR; match: waves, stage; the record-only scan's form: DYN, KT, NIF, U8, SELF, CTR; its grid:
+ * blocks, waves, record lists, records per list, overflow base, overflow capacity, dynamic LDS; list_cap; candidate keys per
+ * query; passes; the LDS limits of the scan and the match kernel; queries of the first pass}.  Everything after out[0] but the
+ * candidate keys is 0 when the call is not pruned. */
+int knn_debug_cells_topk_plan(const long long in[20], long long out[25]);
+/* Test hook (host arithmetic, no GPU): the value the top-K form of the cell-pruned path's preparation kernel hands to the
+ * threshold — the K-th smallest finite score among nseed seed scores as a block of pw (2 or 4) waves selects it, the nwide
+ * scores of the strided sample merged in when fewer than K are finite; +INF when still fewer.  0 on success. */
+int knn_debug_seed_kth(const float *seed, int nseed, const float *wide, int nwide, int K, int pw, float *out);
+/* Test hook (host arithmetic, no GPU): the threshold of a query of the cell-pruned path from a seed score u (filter units), for a
+ * shard of scale sigma, largest |fp16 query coordinate| amax, |fp16 row coordinate| bmax, row norm nmax, and the query's computed
+ * norm mq: out = {the score threshold, Dup (the largest scaled squared distance a candidate can have, fp32 rounded up), the
+ * distance gate of the top-K re-rank: the largest v0 distance (rows' own units) a row of the top-K can have}.  0 on success. */
+int knn_debug_topk_gate(int k, float sigma, double amax, double bmax, double nmax, double u, double mq, double out[3]);
 /* Test hook (host arithmetic only, no GPU needed): every choice and size one batch of the dense filter query launches with.
  * in = {kt, ntiles, m, num_cu, rec_cap, K (0 = 1-NN), and the options filter_qt, filter_rounds, filter_chain, run_thresholds,
  * sample_stride};

@@ -28,7 +28,7 @@ EXPORTED_SYMBOLS = [
     "knn_index_query_host", "knn_set_option", "knn_get_option", "knn_index_last_stats",
     "knn_synth_fill_device", "knn_index_timing", "knn_index_timing_read",
     "knn_debug_filter_scores", "knn_index_query_keys_slot", "knn_trim", "knn_keys_allreduce_min",
-    "knn_index_query_keys_ex", "knn_index_debug_counters", "knn_debug_scan_plan", "knn_debug_scan_plan_ex", "knn_debug_cells_query_plan", "knn_debug_filter_query_plan", "knn_debug_shard_policy", "knn_debug_plan_shard", "knn_debug_u8_row", "knn_debug_u8_bin_row", "knn_debug_u8_bin_threshold", "knn_index_query",
+    "knn_index_query_keys_ex", "knn_index_debug_counters", "knn_debug_scan_plan", "knn_debug_scan_plan_ex", "knn_debug_cells_query_plan", "knn_debug_cells_topk_plan", "knn_debug_seed_kth", "knn_debug_topk_gate", "knn_debug_filter_query_plan", "knn_debug_shard_policy", "knn_debug_plan_shard", "knn_debug_u8_row", "knn_debug_u8_bin_row", "knn_debug_u8_bin_threshold", "knn_index_query",
     "knn_geom_create", "knn_geom_destroy", "knn_geom_info", "knn_geom_assign", "knn_index_create_sharded",
     "knn_index_seed_export", "knn_index_seed_attach", "knn_geom_first_cell",
     "knn_index_query_topk", "knn_keys_topk_merge", "knn_index_query_topk_host",
@@ -162,6 +162,46 @@ def debug_cells_query_plan(**inputs):
     f.argtypes = [ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)]
     _check(f(vin, out))
     return dict(zip(CELLS_QUERY_PLAN, list(out)))
+
+
+CELLS_TOPK_INPUTS = ("k", "K", "m", "n", "topk_cells", "has_cells", "centred", "rows_u8", "bins", "sharded", "n_outliers", "ncells",
+                     "nitems", "cap", "several_slots", "scan_blocks", "scan_deal", "num_cu", "rec_cap", "cells")
+CELLS_TOPK_PLAN = ("use", "prep_pw", "prep_kt", "prep_ctr", "match_waves", "stage", "scan_dyn", "scan_kt", "scan_nif",
+                   "scan_u8", "scan_self", "scan_ctr", "blocks", "waves", "nlists", "slice", "ovf_base", "ovf_cap", "lds_bytes",
+                   "list_cap", "ccap", "passes", "scan_lds_limit", "match_lds_limit", "pass_m")
+
+
+def debug_cells_topk_plan(**inputs):
+    """knn_debug_cells_topk_plan: whether a top-K call takes the cell-pruned scan, and every choice and size of one of its
+    passes, for the inputs named in CELLS_TOPK_INPUTS (host arithmetic; works without a GPU)."""
+    vin = (ctypes.c_longlong * len(CELLS_TOPK_INPUTS))(*[int(inputs[n]) for n in CELLS_TOPK_INPUTS])
+    out = (ctypes.c_longlong * len(CELLS_TOPK_PLAN))()
+    f = lib().knn_debug_cells_topk_plan
+    f.argtypes = [ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)]
+    _check(f(vin, out))
+    return dict(zip(CELLS_TOPK_PLAN, list(out)))
+
+
+def debug_seed_kth(seed, wide, K, pw=4):
+    """knn_debug_seed_kth: the K-th smallest finite seed score as the top-K preparation kernel selects it (+inf: fewer than K
+    finite even with the wide sample).  Host arithmetic; works without a GPU."""
+    a = np.ascontiguousarray(seed, dtype=np.float32).reshape(-1)
+    b = np.ascontiguousarray(wide, dtype=np.float32).reshape(-1)
+    out = ctypes.c_float()
+    f = lib().knn_debug_seed_kth
+    f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                  ctypes.POINTER(ctypes.c_float)]
+    _check(f(a.ctypes.data if a.size else None, a.size, b.ctypes.data if b.size else None, b.size, int(K), int(pw), out))
+    return float(out.value)
+
+
+def debug_topk_gate(k, sigma, amax, bmax, nmax, u, mq):
+    """knn_debug_topk_gate: (score threshold, Dup, the top-K re-rank's distance gate) for a seed score u.  Host arithmetic."""
+    out = (ctypes.c_double * 3)()
+    f = lib().knn_debug_topk_gate
+    f.argtypes = [ctypes.c_int, ctypes.c_float] + [ctypes.c_double] * 5 + [ctypes.POINTER(ctypes.c_double)]
+    _check(f(int(k), float(sigma), float(amax), float(bmax), float(nmax), float(u), float(mq), out))
+    return tuple(out)
 
 
 FILTER_QUERY_INPUTS = ("kt", "ntiles", "m", "num_cu", "rec_cap", "topk", "filter_qt", "filter_rounds", "filter_chain",

@@ -77,6 +77,7 @@ std::atomic<long long> g_opt_run_thresholds{0};  // deep-K scan: 0 / 1 running t
 std::atomic<long long> g_opt_cells_lists{0};     // pruned scan, who lists a cell's queries: 0 auto, 1 the match launch, 2 the scan's own waves
 std::atomic<long long> g_opt_scan_deal{0};       // pruned scan, how waves get their items: 0 auto, 1 fixed deal, 2 block counter
 std::atomic<long long> g_opt_cells_build{0};     // cell-sorted layout: 0 fast two-pass build (counted one if a bucket overflows), 1 the one-pass placement, 2 the counted two-pass build (A/B, tests)
+std::atomic<long long> g_opt_topk_cells{0};      // top-K on the pruned scan: 0 policy (knn_cells_topk_plan), 1 wherever the layout allows it, 2 never
 std::atomic<long long> g_opt_cells{0};       // cell-sorted layouts (k <= 16): 0 resident indexes large enough to prune (index_create_impl), 1 from 2^17 rows, 2 never
 std::atomic<long long> g_opt_ingest{0};      // indexes created from host rows: 0 layouts built under the copy, 1 copy then build
 std::atomic<long long> g_opt_rccl{0};        // 0 auto (several GPUs, one shard each), 1 always, 2 never
@@ -392,6 +393,12 @@ int knn_set_option(const char *name, long long value)
         g_knn_cells_u8_frame = (int)value;
         return KNN_OK;
     }
+    if (!strcmp(name, "topk_cells")) {
+        if (value < 0 || value > 2)
+            return fail(KNN_EINVAL, "knn_set_option: topk_cells must be 0 (policy), 1 (pruned top-K wherever the layout allows it) or 2 (never)");
+        g_opt_topk_cells = value;
+        return KNN_OK;
+    }
     if (!strcmp(name, "cells_lists")) {
         if (value < 0 || value > 2)
             return fail(KNN_EINVAL, "knn_set_option: cells_lists must be 0 (auto), 1 (match launch) or 2 (the scan lists its own items)");
@@ -457,6 +464,8 @@ long long knn_get_option(const char *name)
         return g_opt_scan_deal;
     if (name && !strcmp(name, "cells_lists"))
         return g_opt_cells_lists;
+    if (name && !strcmp(name, "topk_cells"))
+        return g_opt_topk_cells;
     if (name && !strcmp(name, "cells_centre"))
         return (long long)g_knn_cells_centre.load();
     if (name && !strcmp(name, "cells_centred_builds"))   // read-only: cell-sorted layouts moved into per-cell frames so far
@@ -550,8 +559,7 @@ int index_create_impl(knn_index **out, int device, int k, long long n_local, con
     // uniform data, m = 1024, ms per step pruned / full scan on one box — n = 2^24: k 17 0.211 / 0.94, 20 0.265 / 0.96, 22 0.424 / 0.962,
     // 24 0.625 / 0.976, 25 0.716 / 0.980, 26 1.06 / 0.99 (loses); n = 2^23: k 21 0.238 / 0.465, 23 0.354 / 0.476, 24 0.445 / 0.477 (a wash),
     // 25 0.579 / 0.480 (loses); n = 2^22: k 20 0.143 / 0.25, 21 0.174 / 0.236, 22 0.220 / 0.240 and 23 0.219 / 0.243 (a wash), 24 loses)
-    const long long cells_from = k <= 12 ? (1ll << 19) : k <= 16 ? (1ll << 20) : k <= 21 ? (1ll << 22) : k <= 23 ? (1ll << 23)
-                                 : k <= KNN_CELLS_AUTO_MAX_K ? (1ll << 24) : (1ll << 62);
+    const long long cells_from = knn_cells_size_rule(k);
     const bool want_cells = k <= 32 && n_local >= (1ll << 17) &&
                             (g_opt_cells == 1 || (g_opt_cells == 0 && build_filter == 2) ||
                              (g_opt_cells == 0 && build_filter < 0 && n_local >= cells_from));
@@ -991,8 +999,9 @@ int knn_index_query_topk(knn_index *idx, int slot, int m, int K, const float *qu
         if (init)
             HIP_TRY(knn_keys_fill_launch((u64 *)keys_dev, mk, s));
     } else {
-        // Which path: the MFMA filter for the dense layouts and for a cell-sorted layout in the shard's frame
-        // (scanned in full), under the 1-NN rule's options and sizes; exact top-K for per-cell frames (centred), 8-bit rows, grid
+        // Which path: the cell-pruned top-K where knn_cells_topk_plan takes the call (below); else the MFMA filter for
+        // the dense layouts and for a cell-sorted fp16 layout in the shard's frame (scanned in full), under the 1-NN rule's options
+        // and sizes; exact top-K for per-cell frames (centred), 8-bit rows the plan declines, grid
         // indexes, cell-range shards (their keys need gids), tiny shards, few queries, and outlier lists longer than half a
         // query's candidate room.
         const long long path = g_opt_path;
@@ -1002,7 +1011,34 @@ int knn_index_query_topk(knn_index *idx, int slot, int m, int K, const float *qu
                                 idx->filter.n_outliers <= ccap / 2 &&
                                 ccap >= 64 &&
                                 (path == 2 || (path == 0 && m >= 5 && (idx->n >= 65536 || idx->filter_wanted)));
-        const size_t need = knn_topk_part_bytes(m, K, idx->n, idx->num_cu);
+        // Top-K on the cell-pruned scan (knn_cells_topk_plan decides; option `topk_cells`): layouts in the shard's frame, in passes
+        // of KNN_CELL_BATCH queries.
+        CellTopkInputs ti;
+        if (idx->filter.usable && idx->filter.cells) {
+            const CellIndex &c = *idx->filter.cells;
+            // (several_slots false: a top-K call does not feed the index's record of recent slots; one batch at a time shapes)
+            ti.q = CellQueryInputs{idx->filter.k, idx->filter.kt, c.centred, c.rows_u8, c.ncells, c.nitems, c.cap, false,
+                                   (int)g_opt_scan_blocks, (int)g_opt_scan_deal, 1, m, idx->num_cu, KNN_RECORD_CAPACITY};
+            ti.has_cells = true;
+            ti.bins = c.bins;
+        } else {
+            ti.q.m = m;
+        }
+        ti.K = K;
+        ti.n = idx->n;
+        ti.topk_cells = (int)g_opt_topk_cells;
+        ti.cells_option = (int)g_opt_cells;
+        ti.sharded = idx->sharded;
+        ti.other_path = (idx->grid && (path == 0 || path == 3)) || path == 1 || path == 3;
+        ti.n_outliers = idx->filter.n_outliers;
+        const CellTopkPlan tp = knn_cells_topk_plan(ti);
+        // (the gated exact top-K of a pass sizes its lists by the pass's queries)
+        size_t need = knn_topk_part_bytes(m, K, idx->n, idx->num_cu);
+        if (tp.use) {
+            need = std::max(need, knn_topk_part_bytes(tp.pass_m, K, idx->n, idx->num_cu));
+            if (m % KNN_CELL_BATCH)
+                need = std::max(need, knn_topk_part_bytes(m % KNN_CELL_BATCH, K, idx->n, idx->num_cu));
+        }
         if (idx->topk_bytes[slot] < need) {
             HIP_TRY(knn_dev_free(idx->topk_part[slot]));   // (waits for the device: the old buffer may be in use)
             idx->topk_part[slot] = nullptr;
@@ -1013,7 +1049,22 @@ int knn_index_query_topk(knn_index *idx, int slot, int m, int K, const float *qu
         std::pair<hipEvent_t, hipEvent_t> *ev = nullptr;
         if (idx->timing > 0 && idx->timing_seq++ % (unsigned long long)idx->timing == 0 && idx->events_used < idx->events.size())
             ev = &idx->events[idx->events_used++];
-        if (use_filter) {
+        if (tp.use) {
+            const size_t cbytes = (size_t)m * tp.ccap * sizeof(u64) + (size_t)m * sizeof(unsigned);
+            if (idx->topk_cand_bytes[slot] < cbytes) {
+                HIP_TRY(knn_dev_free(idx->topk_cand[slot]));
+                idx->topk_cand[slot] = nullptr;
+                idx->topk_cand_bytes[slot] = 0;
+                HIP_TRY(knn_dev_alloc((void **)&idx->topk_cand[slot], cbytes));
+                idx->topk_cand_bytes[slot] = cbytes;
+            }
+            idx->stats[0] = 4;
+            u64 *cand = idx->topk_cand[slot];
+            unsigned *ccount = (unsigned *)(cand + (size_t)m * tp.ccap);
+            HIP_TRY(knn_filter_query_topk_cells(idx->filter, tp, slot, m, K, queries_dev, idx->refs, idx->base, (u64 *)keys_dev,
+                                                init != 0, cand, ccount, idx->topk_part[slot], idx->topk_bytes[slot], idx->num_cu, s,
+                                                ev ? ev->first : nullptr, ev ? ev->second : nullptr));
+        } else if (use_filter) {
             const size_t cbytes = (size_t)m * ccap * sizeof(u64) + (size_t)m * sizeof(unsigned);
             if (idx->topk_cand_bytes[slot] < cbytes) {
                 HIP_TRY(knn_dev_free(idx->topk_cand[slot]));
@@ -1216,6 +1267,44 @@ int knn_debug_cells_query_plan(const long long in[14], long long out[28])
                              p.grid.blocks, p.grid.waves, p.grid.nlists, p.grid.slice, p.grid.ovf_base, p.grid.ovf_cap,
                              (long long)p.grid.lds_bytes, p.list_cap, p.tail_k, p.tail_kt, p.tail_blocks, p.exact_launch,
                              (long long)p.scan_lds_limit, (long long)p.match_lds_limit};
+    memcpy(out, v, sizeof v);
+    return KNN_OK;
+}
+
+int knn_debug_cells_topk_plan(const long long in[20], long long out[25])
+{
+    if (!in || !out || in[0] < 1 || in[0] > 4096 || in[2] < 1 || in[2] > INT_MAX || in[17] < 1 || in[3] < 0)
+        return fail(KNN_EINVAL, "knn_debug_cells_topk_plan: bad arguments");
+    CellTopkInputs ti;
+    ti.q.k = (int)in[0];
+    ti.q.kt = knn_kt_of(ti.q.k);
+    ti.K = (int)in[1];
+    ti.q.m = (int)in[2];
+    ti.n = in[3];
+    ti.topk_cells = (int)in[4];
+    ti.has_cells = in[5] != 0;
+    ti.q.centred = in[6] != 0;
+    ti.q.rows_u8 = in[7] != 0;
+    ti.bins = in[8] != 0;
+    ti.sharded = in[9] != 0;
+    ti.n_outliers = (unsigned)in[10];
+    ti.q.ncells = (unsigned)in[11];
+    ti.q.nitems = (unsigned)in[12];
+    ti.q.cap = (unsigned)in[13];
+    ti.q.several_slots = in[14] != 0;
+    ti.q.scan_blocks = (int)in[15];
+    ti.q.scan_deal = (int)in[16];
+    ti.q.num_cu = (int)in[17];
+    ti.q.rec_cap = (unsigned)in[18];
+    ti.cells_option = (int)in[19];
+    ti.q.cells_lists = 1;
+    const CellTopkPlan t = knn_cells_topk_plan(ti);
+    const CellQueryPlan &p = t.batch;
+    const long long v[25] = {t.use, p.prep_pw, p.prep_kt, p.prep_ctr, p.match_waves, p.stage,
+                             t.scan.dyn, t.scan.kt, t.scan.nif, t.scan.u8, t.scan.self, t.scan.ctr,
+                             p.grid.blocks, p.grid.waves, p.grid.nlists, p.grid.slice, p.grid.ovf_base, p.grid.ovf_cap,
+                             (long long)p.grid.lds_bytes, p.list_cap, t.ccap, t.passes, (long long)p.scan_lds_limit,
+                             (long long)p.match_lds_limit, t.pass_m};
     memcpy(out, v, sizeof v);
     return KNN_OK;
 }

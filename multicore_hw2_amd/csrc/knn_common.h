@@ -70,7 +70,15 @@ hipError_t knn_topk_filter_finish(int k, int m, int K, long long positions, long
                                   const u64 *rec, const unsigned short *rec_rows, const unsigned *counts, unsigned nlists,
                                   unsigned slice, unsigned *ctl, RerankPieces pieces, const unsigned *perm,
                                   unsigned n_outliers, const unsigned *outliers, u64 *cand, unsigned *ccount, unsigned ccap,
-                                  u64 *keys, int init, hipStream_t stream);
+                                  u64 *keys, int init, hipStream_t stream,
+                                  // the cell-pruned scan's shared overflow area, re-ranked as a list of one: ovf_count records
+                                  // (a device word) at ovf_rec, room ovf_slice — more than that raises FALLBACK
+                                  const u64 *ovf_rec = nullptr, const unsigned *ovf_count = nullptr, unsigned ovf_slice = 0u,
+                                  // the cell-pruned top-K's distance gate: the pass's Dup_q values and sigma^-2 (knn_topk_gate);
+                                  // null: every finite key is a candidate (the filter top-K)
+                                  const float *gate_dup = nullptr, float inv_sigma2 = 0.0f,
+                                  // with the gate: the layout's norms by position (+INF: padding, out-of-box rows — not re-ranked)
+                                  const float *pos_norms = nullptr);
 // b[j] <- the K smallest of a[j] and b[j] (both sorted lists of K keys), sorted.
 hipError_t knn_topk_merge_launch(int m, int K, const u64 *a, u64 *b, hipStream_t stream);
 
@@ -362,6 +370,35 @@ struct CellQueryPlan {
     size_t scan_lds_limit = 0, match_lds_limit = 0;   // the variants' dynamic-LDS attribute (0: the default)
 };
 CellQueryPlan knn_cells_query_plan(const CellQueryInputs &in);
+// Top-K on the cell-pruned scan (knn_cells_topk_plan; host arithmetic only): whether a call takes it, and every choice and size
+// of one of its passes.  DESIGN §4.6.
+struct CellTopkInputs {
+    CellQueryInputs q;             // the index and the options as for a 1-NN batch; q.m = the CALL's queries (passes of KNN_CELL_BATCH)
+    int K = 1;
+    long long n = 0;               // rows of the shard
+    int topk_cells = 0;            // option: 0 policy, 1 wherever the layout allows it, 2 never
+    int cells_option = 0;          // option `cells` (2: the caller asked for full scans)
+    bool has_cells = false;        // a cell-sorted layout exists
+    bool bins = false;             // its 8-bit rows are in per-dimension bin frames (with q.rows_u8)
+    bool sharded = false;          // cell-range shard
+    bool other_path = false;       // the grid index or a forced exact path answers this index
+    unsigned n_outliers = 0;
+};
+struct CellTopkPlan {
+    bool use = false;              // false: the call stays on the path it had (filter top-K or exact top-K)
+    int passes = 0, pass_m = 0;    // passes of <= KNN_CELL_BATCH queries; the first pass's queries
+    CellQueryPlan batch;           // prep_pw / prep_kt, the match launch, the scan's grid and record lists, list_cap, LDS limits
+    CellScanForm scan;             // knn_cells_records_kernel<dyn, kt, nif, u8> (self, ctr: never)
+    unsigned ccap = 0;             // candidate keys a query has room for
+    // (the launches behind the scan are knn_cells_query_topk's fixed sequence: nothing of them is a choice)
+};
+// rows from which the library builds a cell-sorted layout by policy (1-NN: the pruned scan wins from there; knn_api.cpp)
+static inline long long knn_cells_size_rule(int k)
+{
+    return k <= 12 ? (1ll << 19) : k <= 16 ? (1ll << 20) : k <= 21 ? (1ll << 22) : k <= 23 ? (1ll << 23)
+         : k <= KNN_CELLS_AUTO_MAX_K ? (1ll << 24) : (1ll << 62);
+}
+CellTopkPlan knn_cells_topk_plan(const CellTopkInputs &in);
 // Every choice and size one batch of the dense filter query launches with (knn_filter_query_plan in knn_filter.hip; host
 // arithmetic only).  The scan comes in three forms: pieces of the batch on the register scan (knn_filter_kernel, k <= 32, and
 // k <= 128 below 16 query tiles), the LDS-tiled scan (knn_filter_tiled_kernel, k <= 512) and the chunked-K scan
@@ -420,6 +457,12 @@ void knn_cells_workspace_free(FilterWorkspace &w);
 // init_keys: the batch's keys are set to (+INF, 0) by the first kernel of the chain.
 hipError_t knn_cells_query(FilterState &st, FilterWorkspace &w, FilterCallOptions opt, int m, const float *q_dev, const float *r_dev,
                            long long base, u64 *keys, int num_cu, bool timed, hipStream_t s, bool init_keys, int *out_idx = nullptr);
+// One pass of <= KNN_CELL_BATCH queries of a top-K call: prep (K-th seed bound) -> match -> record-only scan -> re-rank of the
+// slices and of the shared overflow area -> out-of-box rows -> select -> the exact top-K, gated on FALLBACK.  keys: the pass's
+// [m][K]; cand / ccount: the pass's candidate lists [m][tp.ccap] and counters [m].
+hipError_t knn_cells_query_topk(FilterState &st, FilterWorkspace &w, const CellTopkPlan &tp, int m, int K, const float *q_dev,
+                                const float *r_dev, long long base, u64 *keys, bool init_keys, u64 *cand, unsigned *ccount, u64 *part,
+                                size_t part_bytes, int num_cu, bool timed, hipStream_t s);
 
 // Builds the filter layouts for refs[0..n) (device, AoS).  Synchronous.  Leaves st.usable false
 // (and returns hipSuccess) when the data rules the filter out.
@@ -484,6 +527,10 @@ hipError_t knn_filter_query(FilterState &st, FilterCallOptions opt, int slot, in
 hipError_t knn_filter_query_topk(FilterState &st, FilterCallOptions opt, int slot, int m, const float *q, const float *r, long long base,
                                  u64 *keys, bool init_keys, u64 *cand, unsigned *ccount, unsigned ccap, u64 *part,
                                  size_t part_bytes, int num_cu, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end);
+// Top-K on the cell-pruned scan, the whole call in passes of KNN_CELL_BATCH queries (knn_cells_query_topk); cand / ccount: [m][tp.ccap], [m].
+hipError_t knn_filter_query_topk_cells(FilterState &st, const CellTopkPlan &tp, int slot, int m, int K, const float *q, const float *r,
+                                       long long base, u64 *keys, bool init_keys, u64 *cand, unsigned *ccount, u64 *part,
+                                       size_t part_bytes, int num_cu, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end);
 // Test hook: raw filter scores S[m][n] (row-major) and the per-query thresholds for a query
 // batch, plus {sigma, eta, rho, amax, bmax}.  Synchronous.
 hipError_t knn_filter_debug(FilterState &st, int m, const float *q_dev, const float *r_dev,

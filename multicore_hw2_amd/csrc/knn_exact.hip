@@ -1205,6 +1205,42 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_topk_rerank_kernel(const float 
     }
 }
 
+// The same for the cell-pruned top-K (knn_cells_query_topk): a key enters its query's candidate list only when its v0 distance
+// is at most gate[q] = knn_topk_gate(Dup_q) — no row of the query's top-K lies beyond it (knn_exact_dev.h) —, which turns
+// "16 keys per record" into about one.  One block per list; records through perm, all 16 rows — except positions whose layout
+// norm is +INF: padding, and rows outside the robust box, which sit in the layout beside rows that pass and are pushed by
+// knn_topk_outlier_kernel (pushed here as well such a row stood in the list twice and the select dropped the query's K-th key).
+__global__ __launch_bounds__(KNN_BLOCK) void knn_topk_rerank_gated_kernel(const float *__restrict__ Q, const float *__restrict__ R,
+                                                                         int k, long long n, long long base,
+                                                                         const u64 *__restrict__ rec,
+                                                                         const unsigned *__restrict__ counts, unsigned nlists,
+                                                                         unsigned slice, unsigned *__restrict__ ctl,
+                                                                         const unsigned *__restrict__ perm,
+                                                                         const float *__restrict__ norms,
+                                                                         const float *__restrict__ dup, float inv_sigma2,
+                                                                         u64 *__restrict__ cand, unsigned *__restrict__ ccount,
+                                                                         unsigned ccap)
+{
+    const unsigned list_id = blockIdx.x;
+    if (ctl[KNN_CTL_FALLBACK] != 0u || list_id >= nlists)
+        return;
+    const unsigned want = counts[list_id];
+    const unsigned nrec = min(want, slice);
+    if (threadIdx.x == 0 && want > slice)
+        ctl[KNN_CTL_FALLBACK] = 1u;
+    const u64 *__restrict__ list = rec + (size_t)list_id * slice;
+    for (unsigned c = threadIdx.x; c < nrec * 16u; c += KNN_BLOCK) {
+        unsigned qi = 0u;
+        const u64 e = list[c >> 4];
+        const unsigned lo = (unsigned)e, reg = c & 15u;
+        const long long pos = (long long)(lo >> 1) * 32 + 8 * (reg >> 2) + 4 * (lo & 1u) + (reg & 3u);   // (rerank_pair's)
+        const unsigned rmask = pos < n && norms[pos] < INFINITY ? 0xFFFFu : 0u;
+        const u64 key = rerank_pair<0>(Q, R, k, n, base, e, reg, rmask, 0u, perm, qi);
+        if (key != ~0ull && __uint_as_float((unsigned)(key >> 32)) <= knn_topk_gate(dup[qi], inv_sigma2))
+            topk_cand_push(key, qi, cand, ccount, ccap, ctl);
+    }
+}
+
 // Rows outside the filter's robust box never enter the scan: every (query, listed row) pair with v0 arithmetic, each finite
 // key to the query's candidate list.  grid (row blocks, queries).
 __global__ __launch_bounds__(KNN_BLOCK) void knn_topk_outlier_kernel(const float *__restrict__ Q, const float *__restrict__ R,
@@ -1263,9 +1299,22 @@ hipError_t knn_topk_filter_finish(int k, int m, int K, long long positions, long
                                   const u64 *rec, const unsigned short *rec_rows, const unsigned *counts, unsigned nlists,
                                   unsigned slice, unsigned *ctl, RerankPieces pieces, const unsigned *perm,
                                   unsigned n_outliers, const unsigned *outliers, u64 *cand, unsigned *ccount, unsigned ccap,
-                                  u64 *keys, int init, hipStream_t s)
+                                  u64 *keys, int init, hipStream_t s, const u64 *ovf_rec, const unsigned *ovf_count,
+                                  unsigned ovf_slice, const float *gate_dup, float inv_sigma2, const float *pos_norms)
 {
-    if (nlists) {
+    if (gate_dup) {   // the cell-pruned top-K: the gated re-rank over the waves' slices and over the shared overflow area
+        if (rec_rows || !perm || !pos_norms)
+            return hipErrorInvalidValue;
+        if (nlists)
+            hipLaunchKernelGGL(knn_topk_rerank_gated_kernel, dim3(nlists), dim3(KNN_BLOCK), 0, s, q, r, k, positions, base, rec, counts,
+                               nlists, slice, ctl, perm, pos_norms, gate_dup, inv_sigma2, cand, ccount, ccap);
+        if (ovf_rec && ovf_count)   // (its `want > slice` rule raises FALLBACK for an over-full area)
+            hipLaunchKernelGGL(knn_topk_rerank_gated_kernel, dim3(1), dim3(KNN_BLOCK), 0, s, q, r, k, positions, base, ovf_rec, ovf_count,
+                               1u, ovf_slice, ctl, perm, pos_norms, gate_dup, inv_sigma2, cand, ccount, ccap);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess)
+            return e;
+    } else if (nlists) {
         hipLaunchKernelGGL(knn_topk_rerank_kernel, dim3(nlists), dim3(KNN_BLOCK), 0, s, q, r, k, positions, base, rec, rec_rows,
                            counts, nlists, slice, ctl, pieces, perm, cand, ccount, ccap);
         hipError_t e = hipGetLastError();

@@ -360,3 +360,21 @@ __device__ __forceinline__ void cells_exact_items(
         }
     }
 }
+
+// The distance gate of the cell-pruned top-K's re-rank (knn_topk_rerank_kernel's gated twin): the largest v0 value E — the fp32
+// squared distance in the rows' own units, as the reference computes it — a row of the query's top-K can have, from Dup_q.
+// knn_threshold (knn_filter_dev.h): the K seed rows j0 behind u_(K) have real scaled distances D_j0 <= D0up, and Dup = D0up (1+g2)^2 + sigma^2 tau.
+// v0's own rounding, the line the threshold's derivation already rests on (knn_filter.hip's head: D <= sigma^2 (E (1+g2) + tau)),
+// read the other way — every term of E is (q-r)^2 (1+d)^3, the k-1 additions (1+d) each, an underflowing term off by < 2^-149:
+//     E_j0 <= (D_j0 / sigma^2) (1+g2) + tau <= (D0up (1+g2) + sigma^2 tau) / sigma^2 <= Dup / sigma^2.
+// A row of the true top-K has E <= E_(K) <= max E_j0 (the K-th smallest v0 value of the shard is at most the largest among ANY K
+// distinct rows), so E > Dup / sigma^2 rules a row out of the K smallest keys, ties at E_(K) included (they have E = E_(K)).
+// dup: the prep kernel's Dup_q as stored (fp32, rounded up); inv_sigma2 = sigma^-2, a power of two: the product is exact unless it
+// leaves fp32's normal range — +INF passes everything, and 2^-120 on top covers a denormal's rounding; the factor 1 + 2^-20 is slack.
+// dup = -INF (a query nothing bounds: the pass falls back) gives -INF: nothing passes.
+__host__ __device__ inline float knn_topk_gate(float dup, float inv_sigma2)
+{
+#pragma clang fp contract(off)
+    const float g = dup * inv_sigma2;
+    return g + (g * 0x1p-20f + 0x1p-120f);
+}

@@ -2659,6 +2659,29 @@ hipError_t knn_filter_query_topk(FilterState &st, FilterCallOptions opt, int slo
     return hipSuccess;
 }
 
+// Top-K on the cell-pruned scan: passes of KNN_CELL_BATCH queries, each its own prep -> match -> record-only scan ->
+// re-rank -> select -> gated exact top-K (knn_cells_query_topk).  Every pass decides for itself: one that raised FALLBACK is
+// answered exactly, the next is pruned again.
+hipError_t knn_filter_query_topk_cells(FilterState &st, const CellTopkPlan &tp, int slot, int m, int K, const float *q, const float *r,
+                                       long long base, u64 *keys, bool init_keys, u64 *cand, unsigned *ccount, u64 *part,
+                                       size_t part_bytes, int num_cu, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end)
+{
+    if (!st.cells || !tp.use)
+        return hipErrorInvalidValue;
+    FilterWorkspace &w = st.ws[slot];
+    w.last_used_cells = true;
+    w.ev_begin = ev_begin;
+    w.ev_end = ev_end;
+    const int cell_batch = KNN_CELL_BATCH;
+    FTRY(ensure_workspace(st, w, std::min(m, cell_batch)));
+    for (int q0 = 0; q0 < m; q0 += cell_batch) {
+        const int mb = std::min(cell_batch, m - q0);
+        FTRY(knn_cells_query_topk(st, w, tp, mb, K, q + (size_t)q0 * st.k, r, base, keys + (size_t)q0 * K, init_keys,
+                                  cand + (size_t)q0 * tp.ccap, ccount + q0, part, part_bytes, num_cu, q0 == 0, s));
+    }
+    return hipSuccess;
+}
+
 // knn_filter_debug's scores: knn_filter_scores_kernel<KT>, KT = 0: knn_filter_scores_rt_kernel (run-time kt, k > 512).
 template <int KT>
 static void filter_scores_as(const FilterState &st, const FilterWorkspace &w, int m, float *scores, hipStream_t s)

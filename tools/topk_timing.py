@@ -6,9 +6,13 @@ Workloads (fp32 rows from knn_synth_fill_device, seeds 1001 / 1000 as bench.py):
   c3_default   the same shape, library policy (1-NN: the cell-pruned scan over 8-bit rows)
   c5           k 128, m = n = 65536 (1-NN: the deep-K filter)
   c3_exact     the C3 shape with option path = 1 (1-NN: the exact kernels)
-A top-K call takes the MFMA filter (path 2) on the dense layouts and fp16 cell-sorted ones, the exact top-K scan (path 1) on
-per-cell frames (the default u8 index); "rec/q" is knn_index_last_stats()[1] / m (records of 16 rows re-ranked), "fb" its
-[2] (1: the batch fell back to the exact top-K).  usage: topk_timing.py [--reps R] [--only NAME ...]"""
+  c3_fp16      the C3 shape with option cells_rows = 1 (the fp16 cell-sorted layout)
+  k20          k 20, m 1024, n 2^24, library policy
+A top-K call takes the cell-pruned scan (path 4) on cell-sorted layouts in the shard's frame when option topk_cells allows it,
+the MFMA filter (path 2) on the dense layouts and on fp16 cell-sorted ones otherwise, the exact top-K scan (path 1) on per-cell
+frames; "rec/q" is knn_index_last_stats()[1] / m (records of 16 rows re-ranked), "fb" its [2] (1: the batch fell back to the
+exact top-K).  --topk-cells V sets that option (a library without it — KNN_MI355X_LIB naming an older build — is left alone).
+usage: topk_timing.py [--reps R] [--only NAME ...] [--topk-cells V] [--ks K ...]"""
 import argparse
 import json
 import sys
@@ -23,6 +27,8 @@ WORKLOADS = {
     "c3_default": (16, 1024, 1 << 24, {}),
     "c5": (128, 65536, 65536, {}),
     "c3_exact": (16, 1024, 1 << 24, {"path": 1}),
+    "c3_fp16": (16, 1024, 1 << 24, {"cells_rows": 1}),
+    "k20": (20, 1024, 1 << 24, {}),
 }
 KS = (1, 8, 32, 64)
 
@@ -43,9 +49,9 @@ def _time(fn, reps):
     return ts[len(ts) // 2], ts[0]
 
 
-def run(name, reps):
+def run(name, reps, ks=KS):
     k, m, n, opts = WORKLOADS[name]
-    for o in ("path", "cells"):
+    for o in ("path", "cells", "cells_rows"):
         pkg.set_option(o, 0)
     for o, v in opts.items():
         pkg.set_option(o, v)
@@ -62,7 +68,7 @@ def run(name, reps):
         keys1 = torch.empty(m, dtype=torch.int64, device=dev)
         one_med, one_min = _time(lambda: ix.query_keys(m, Q.data_ptr(), keys1.data_ptr(), stream=stream, init_keys=True), reps)
         one_stats = ix.last_stats()
-        for K in KS:
+        for K in ks:
             keys = torch.empty(m * K, dtype=torch.int64, device=dev)
             med, mn = _time(lambda: ix.query_topk(m, K, Q.data_ptr(), keys.data_ptr(), stream=stream, init_keys=True), reps)
             st = ix.last_stats()
@@ -75,7 +81,7 @@ def run(name, reps):
             print(json.dumps(rows[-1]), flush=True)
     finally:
         ix.close()
-        for o in ("path", "cells"):
+        for o in ("path", "cells", "cells_rows"):
             pkg.set_option(o, 0)
     return rows
 
@@ -84,10 +90,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--only", nargs="*", default=None)
+    ap.add_argument("--topk-cells", type=int, default=None)
+    ap.add_argument("--ks", type=int, nargs="*", default=None)
     a = ap.parse_args()
+    if a.topk_cells is not None and pkg.get_option("topk_cells") >= 0:
+        pkg.set_option("topk_cells", a.topk_cells)
     out = []
     for name in (a.only or list(WORKLOADS)):
-        out += run(name, a.reps)
+        out += run(name, a.reps, tuple(a.ks) if a.ks else KS)
     print("%-12s %4s %10s %5s %9s %3s %10s %6s %5s %9s" % ("workload", "K", "top-K ms", "path", "rec/q", "fb", "1-NN ms",
                                                          "x1-NN", "path", "rec/q"))
     for r in out:
