@@ -215,7 +215,24 @@ int knn_index_query_host(knn_index *idx, int m, const float *queries_host, int *
  * row): per-cell frames (centred or 8-bit rows), grid indexes, cell-range shards, shards or batches below the filter's sizes.
  * Results are bit-exact either way.
  * Any K outside 1 .. 64, or m < 1, is KNN_EINVAL (knn_last_error says why) and launches nothing.
+ *
+ * KNN_QUERY_TOPK_PARTIAL (knn_index_query_topk only; the 1-NN entry points reject it): the caller will MERGE this shard's lists
+ * with those of every other shard of the set (knn_keys_topk_merge, or a fold), so a shard need only report the rows that can
+ * belong to the GLOBAL top-K.  With the flag the call guarantees, for query j:
+ *   - every row of the shard whose packed key is <= the K-th smallest key over ALL ranks' rows — the global set the geometry
+ *     and the attached seed layer describe — is in the list (ties at the K-th distance included);
+ *   - every other entry that is not padding is a real row of this shard with its bit-exact v0 key;
+ *   - the list is strictly ascending, padding is KNN_KEY_INIT.
+ * It does NOT guarantee a prefix of the shard's own top-K: a row between the global bound and the path's distance gate may be
+ * present while a nearer one is absent (both are then beyond the global K-th key, so no merge can tell).  Merging every
+ * rank's list gives the global top-K bit for bit, and so does folding (no KNN_QUERY_INIT_KEYS) one rank after the other: the
+ * keys carry gids from the moment they are candidates.  What the flag buys: a cell-range shard (knn_index_create_sharded) with
+ * option "topk_cells" = 1 takes the cell-pruned top-K ([0] = 4), its bound the K-th smallest seed score over K distinct rows
+ * of the global set, those of other ranks scored from the seed layer.  Without a layer attached the bound comes from the rank's
+ * own rows and the list is the shard's complete top-K.  On any other index, or under "topk_cells" 0 or 2, the flag is accepted
+ * and changes nothing: full lists satisfy the contract.
  * ---------------------------------------------------------------------- */
+#define KNN_QUERY_TOPK_PARTIAL 2u
 /* keys_dev [m][K]; indices_dev [m][K] or NULL: the int32 indices, unpacked after the fold.  Slot rules as knn_index_query:
  * eight workspaces, calls sharing one must be stream-ordered; asynchronous on `stream`. */
 int knn_index_query_topk(knn_index *idx, int slot, int m, int K, const float *queries_dev, unsigned long long *keys_dev,
@@ -301,7 +318,8 @@ int knn_index_query_topk_host(knn_index *idx, int m, int K, const float *queries
  *             with bin frames (read-only).  Top-K queries: bin frames can take the cell-pruned scan ("topk_cells"), per-cell
  *             frames take the exact top-K scan.
  *   "topk_cells" top-K queries (knn_index_query_topk) on the cell-pruned scan, for cell-sorted layouts in the shard's one frame
- *             (fp16 rows without per-cell frames, 8-bit rows in bin frames; k <= 32, m >= 5, not a cell-range shard):
+ *             (fp16 rows without per-cell frames, 8-bit rows in bin frames; k <= 32, m >= 5; a cell-range shard only for calls
+ *             that carry KNN_QUERY_TOPK_PARTIAL, and only under 1):
  *             0 = library policy: for now the same as 2 — the policy sends a call to this path only where it is measured faster
  *             than the path it replaces, and those measurements are not taken yet (it will start at the row count from which the
  *             library builds the cell-sorted layout on its own for that k);
@@ -386,7 +404,8 @@ int knn_debug_scan_plan_ex(int num_cu, int blocks_per_cu, unsigned nitems, int m
 int knn_debug_cells_query_plan(const long long in[14], long long out[28]);
 /* Test hook (host arithmetic only, no GPU needed): whether a top-K call takes the cell-pruned scan and what one of its passes
  * launches with.  in = {k, K, m (the call's queries), rows of the shard, option topk_cells, 1 if a cell-sorted layout exists,
- * centred, rows_u8, 1 if the 8-bit rows are in bin frames, 1 for a cell-range shard, out-of-box rows, ncells, nitems, cap,
+ * centred, rows_u8, 1 if the 8-bit rows are in bin frames, 1 for a cell-range shard (2: and the call carries
+ * KNN_QUERY_TOPK_PARTIAL), out-of-box rows, ncells, nitems, cap,
  * several_slots, scan_blocks, scan_deal, num_cu, rec_cap, option cells};
  * out = {1 if pruned; prep: PW, KT, CTR; match: waves, stage; the record-only scan's form: DYN, KT, NIF, U8, SELF, CTR; its grid:
  * blocks, waves, record lists, records per list, overflow base, overflow capacity, dynamic LDS; list_cap; candidate keys per

@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = [
     "knn_index_query_topk", "knn_keys_topk_merge", "knn_index_query_topk_host",
 ]
 QUERY_INIT_KEYS = 1   # KNN_QUERY_INIT_KEYS
+QUERY_TOPK_PARTIAL = 2   # KNN_QUERY_TOPK_PARTIAL
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # KNN_MI355X_LIB: A/B hook — load another build of the same C-ABI (e.g. a previous commit's .so)
@@ -381,14 +382,17 @@ class KnnIndex:
                                           out.ctypes.data_as(ctypes.c_void_p)))
         return out
 
-    def query_topk(self, m, K, queries_dev, keys_dev, stream=0, slot=0, init_keys=False, indices_dev=None):
+    def query_topk(self, m, K, queries_dev, keys_dev, stream=0, slot=0, init_keys=False, indices_dev=None, partial=False):
         """Async (knn_index_query_topk): keys_dev[m][K] <- the K smallest (distance, global index) keys of (this shard's rows
         and, unless init_keys, the K sorted keys per query keys_dev already holds), sorted.  indices_dev: also the int32
-        indices [m][K]."""
+        indices [m][K].  partial (KNN_QUERY_TOPK_PARTIAL): the caller merges every shard's lists, so this shard need only
+        report the rows that can belong to the global top-K — what lets a cell-range shard take the cell-pruned scan
+        (option topk_cells = 1); see include/knn_mi355x.h, 2c, for the contract."""
         _check(lib().knn_index_query_topk(self._h, int(slot), int(m), int(K), ctypes.c_void_p(int(queries_dev)),
                                           ctypes.c_void_p(int(keys_dev)),
                                           ctypes.c_void_p(int(indices_dev)) if indices_dev is not None else None,
-                                          ctypes.c_void_p(stream), QUERY_INIT_KEYS if init_keys else 0))
+                                          ctypes.c_void_p(stream),
+                                          (QUERY_INIT_KEYS if init_keys else 0) | (QUERY_TOPK_PARTIAL if partial else 0)))
 
     def query_topk_host(self, queries, K):
         """Synchronous top-K of this shard alone: (indices int32 [m][K], dist2 float32 [m][K])."""

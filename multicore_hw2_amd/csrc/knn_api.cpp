@@ -982,7 +982,7 @@ int knn_index_query_topk(knn_index *idx, int slot, int m, int K, const float *qu
                          int *indices_dev, void *stream, unsigned flags)
 {
     if (!idx || m < 1 || K < 1 || K > KNN_TOPK_MAX || (long long)m * K > INT_MAX || slot < 0 || slot >= KNN_SLOTS ||
-        !queries_dev || !keys_dev || (flags & ~(unsigned)KNN_QUERY_INIT_KEYS) != 0u)
+        !queries_dev || !keys_dev || (flags & ~(unsigned)(KNN_QUERY_INIT_KEYS | KNN_QUERY_TOPK_PARTIAL)) != 0u)
         return fail(KNN_EINVAL, "knn_index_query_topk: bad arguments (1 <= K <= 64, m >= 1, slot 0 .. 7)");
     std::lock_guard<std::recursive_mutex> lock(idx->mu);
     DeviceGuard guard(idx->device);
@@ -1002,8 +1002,9 @@ int knn_index_query_topk(knn_index *idx, int slot, int m, int K, const float *qu
         // Which path: the cell-pruned top-K where knn_cells_topk_plan takes the call (below); else the MFMA filter for
         // the dense layouts and for a cell-sorted fp16 layout in the shard's frame (scanned in full), under the 1-NN rule's options
         // and sizes; exact top-K for per-cell frames (centred), 8-bit rows the plan declines, grid
-        // indexes, cell-range shards (their keys need gids), tiny shards, few queries, and outlier lists longer than half a
-        // query's candidate room.
+        // indexes, cell-range shards whose call does not carry KNN_QUERY_TOPK_PARTIAL (the pruned form's lists are not the
+        // shard's own top-K: include/knn_mi355x.h §2c), tiny shards, few queries, and outlier lists longer than half a query's
+        // candidate room.
         const long long path = g_opt_path;
         const unsigned ccap = (unsigned)std::min<long long>(4096 + 128 * (long long)K, ((long long)32 << 20) / m);
         const bool use_filter = !idx->sharded && idx->filter.usable && !(idx->grid && (path == 0 || path == 3)) &&
@@ -1029,6 +1030,7 @@ int knn_index_query_topk(knn_index *idx, int slot, int m, int K, const float *qu
         ti.topk_cells = (int)g_opt_topk_cells;
         ti.cells_option = (int)g_opt_cells;
         ti.sharded = idx->sharded;
+        ti.shard_partial = idx->sharded && (flags & KNN_QUERY_TOPK_PARTIAL) != 0u;
         ti.other_path = (idx->grid && (path == 0 || path == 3)) || path == 1 || path == 3;
         ti.n_outliers = idx->filter.n_outliers;
         const CellTopkPlan tp = knn_cells_topk_plan(ti);
@@ -1287,6 +1289,7 @@ int knn_debug_cells_topk_plan(const long long in[20], long long out[25])
     ti.q.rows_u8 = in[7] != 0;
     ti.bins = in[8] != 0;
     ti.sharded = in[9] != 0;
+    ti.shard_partial = in[9] == 2;
     ti.n_outliers = (unsigned)in[10];
     ti.q.ncells = (unsigned)in[11];
     ti.q.nitems = (unsigned)in[12];

@@ -1175,7 +1175,9 @@ struct SeedLayer {
 //     bound of sqrt(Dup_q) — what the centred scan's per-pair thresholds start from — instead of a score threshold
 // TK: a top-K batch (knn_cells_query_topk; not with CTR): u = the K-th smallest (K arrives in lo_by_entry) finite score among the scored
 //     rows instead of the smallest — knn_seed_kth.h has the rule, the argument and the mechanism; thr_q and Dup_q come from it
-//     through the same lines below.  keys_init is null there (the select kernel starts or folds the m x K keys).
+//     through the same lines below.  keys_init is null there (the select kernel starts or folds the m x K keys).  On a cell-range
+//     shard (KNN_QUERY_TOPK_PARTIAL) the scored rows include other ranks' rows from the seed layer: u is then a bound over the GLOBAL
+//     set, under bmax / nmax taken over all ranks' parts (knn_index_seed_attach) exactly as the 1-NN form's — DESIGN §6.1.
 template <int PW, int SD, int KT = 1, bool CTR = false, bool TK = false>
 __global__ __launch_bounds__(64 * PW, KT == 1 && !CTR ? 4 : 3) void knn_cells_prep_kernel(   // (4 waves per SIMD: a batch of 1024 queries is resident at once)
     const float *__restrict__ Q, int m, int m_padded, CellGeom g, const float *__restrict__ bounds, double sigma2,
@@ -1360,6 +1362,14 @@ __global__ __launch_bounds__(64 * PW, KT == 1 && !CTR ? 4 : 3) void knn_cells_pr
             v_fa = (unsigned long long)(rf + (size_t)tb * 64 * KT);
             v_na = (unsigned long long)(rn2 + (size_t)tb * 32);
         } else if (KT == 1 && layer.base) {
+            // (TK, a top-K pass of a cell-range shard: these positions enter the K-th seed selection beside the own cells'.  What
+            // knn_seed_kth.h asks of them — K finite scores are K distinct real rows — holds: a code outside this index's range
+            // belongs to ANOTHER rank's part, so layer positions and positions of the own layout never name the same row, and the
+            // four seed codes differ, so no layer position is read twice.  A finite norm is a real in-box row: the export
+            // (knn_cells_seed_export_kernel) copies the owner's split norms word for word for the tiles the cell has and writes
+            // 0x00007C00 = (+INF, 0) for the rest of its depth and for cells beyond the owner's range; the owner's placement kernels
+            // write pack_norm22(+INF) = the same word on padding positions and on rows outside the robust box; a rank without rows
+            // exports that word everywhere (knn_index_seed_export).  Checked by reading those three writers.)
             unsigned part = 0u;   // the rank whose range holds the cell (a table walk: no 64-bit divisions in here)
             for (unsigned r = 1u; r < layer.nranks; ++r)
                 part += code >= layer.first[r] ? 1u : 0u;
@@ -1593,11 +1603,16 @@ __global__ __launch_bounds__(64 * PW, KT == 1 && !CTR ? 4 : 3) void knn_cells_pr
         const int topk = lo_by_entry;
         unsigned cur = KNN_SEED_NONE;   // the wave's 64 smallest score keys so far, ascending over the lanes
         unsigned wide_first = 0xFFFFFFFFu, wide_stride = 0u;   // the wide sample: list position v is tile (wide_first + v) wide_stride
-        unsigned v_tb = 0u;   // the first tile of seed cell `lane` (the wide sample leaves the seed cells' tiles out)
+        // the tiles [v_tb, v_tb + v_own) of the layout that seed cell `lane` has put into the selection (the wide sample leaves them
+        // out).  Cells of THIS index only: a seed of another rank came out of the seed layer (v_nt = its depth there), no tile of
+        // this layout stands for it — taken for tiles 0 .. depth - 1 it cost the wide sample its first tiles (safe, a looser bound)
+        unsigned v_tb = 0u, v_own = 0u;
         {
             const unsigned l = code - g.cell_base;
-            if (ok && code >= g.cell_base && l < g.ncells)
+            if (ok && code >= g.cell_base && l < g.ncells) {
                 v_tb = tile_start[l];
+                v_own = v_nt;
+            }
         }
         // score_runs' walk over the wave's list of tiles, with the selection of knn_seed_kth.h in place of the minimum.  (A lambda of
         // its own inside the TK branch: with the selection as a branch of score_runs, or this lambda where the other forms see it, what
@@ -1649,7 +1664,7 @@ __global__ __launch_bounds__(64 * PW, KT == 1 && !CTR ? 4 : 3) void knn_cells_pr
                         bool skip = false;
                         if (wide_first != 0xFFFFFFFFu) {   // wave-uniform
                             const unsigned t = (wide_first + v0 + (unsigned)p) * wide_stride;
-                            skip = __ballot(lane < SEEDS && v_nt != 0u && t >= v_tb && t - v_tb < v_nt) != 0ull;
+                            skip = __ballot(lane < SEEDS && v_own != 0u && t >= v_tb && t - v_tb < v_own) != 0ull;
                         }
                         float sc = d[0];
 #pragma unroll
@@ -3432,6 +3447,24 @@ static hipError_t cells_trace_lists(const CellIndex &c, const FilterWorkspace &w
     return hipSuccess;
 }
 
+// Where the prep kernel finds the seed tiles of other ranks' cells: the attached seed layer of a cell-range shard; all zero for
+// every other index and for a shard nothing is attached to (its bounds then come from its own rows).
+static SeedLayer cells_seed_layer(const CellIndex &c)
+{
+    SeedLayer layer;
+    memset(&layer, 0, sizeof layer);
+    if (c.geom && c.seed_layer) {
+        layer.base = c.seed_layer;
+        layer.cpr = c.geom->cells_per_rank;
+        layer.tiles = (unsigned)c.geom->seed_tiles;
+        layer.nranks = (unsigned)c.geom->nranks;
+        for (int r_ = 0; r_ <= c.geom->nranks && r_ <= KNN_MAX_RANKS; ++r_)
+            layer.first[r_] = c.geom->first_cell(r_);
+        layer.part_bytes = c.geom->part_bytes();
+    }
+    return layer;
+}
+
 // One batch of <= KNN_CELL_BATCH queries, the whole chain: prep -> match -> scan (its waves re-rank their own records) ->
 // [rows outside the robust box, exactly] -> the exact scan of the shard, gated on FALLBACK -> the tail kernel (gated: records
 // in the shared area, the listed pairs exactly when that area is over-full, the finalisation when the scan could not do it).
@@ -3455,19 +3488,8 @@ hipError_t knn_cells_query(FilterState &st, FilterWorkspace &w, FilterCallOption
     const unsigned parity = w.cell_batches++ & 1u;
     w.ctl_cur = w.ctl + KNN_CTL_WORDS * (1u + parity);
     unsigned *ctl_next = w.ctl + KNN_CTL_WORDS * (2u - parity);
-    SeedLayer layer;
-    memset(&layer, 0, sizeof layer);
-    if (c.geom && c.seed_layer) {
-        layer.base = c.seed_layer;
-        layer.cpr = c.geom->cells_per_rank;
-        layer.tiles = (unsigned)c.geom->seed_tiles;
-        layer.nranks = (unsigned)c.geom->nranks;
-        for (int r_ = 0; r_ <= c.geom->nranks && r_ <= KNN_MAX_RANKS; ++r_)
-            layer.first[r_] = c.geom->first_cell(r_);
-        layer.part_bytes = c.geom->part_bytes();
-    }
     const CellBatch b{st, c, w, p, m, m_padded, q, r, base, keys, init_keys ? keys : nullptr,
-                      CellFinal{c.gids, out_idx, st.n_outliers != 0u ? 1 : 0}, cells_self(p, c, w, m_padded), layer, ctl_next, s};
+                      CellFinal{c.gids, out_idx, st.n_outliers != 0u ? 1 : 0}, cells_self(p, c, w, m_padded), cells_seed_layer(c), ctl_next, s};
     cells_prep_launch(b);
     FTRY(hipGetLastError());
     if (p.match_waves)
@@ -3493,8 +3515,10 @@ hipError_t knn_cells_query(FilterState &st, FilterWorkspace &w, FilterCallOption
 // Top-K on the cell-pruned scan: whether a call takes it and everything one of its passes launches with (host arithmetic:
 // nothing allocated or launched; tests/test_cells_topk_logic.py checks it on the CPU through knn_debug_cells_topk_plan).
 // Served: a resident, non-sharded index whose cell-sorted layout is in the shard's frame — fp16 rows not centred, or 8-bit rows in
-// bin frames —, k <= 32, m >= 5, out-of-box rows at most half a query's candidate room.  Not served (they keep the exact top-K):
-// per-cell frames (the bound is per (query, cell) there), cell-range shards, grid indexes, m < 5.
+// bin frames —, k <= 32, m >= 5, out-of-box rows at most half a query's candidate room; and a cell-range shard (always fp16, not
+// centred, KT 1) under the same conditions when the call carries KNN_QUERY_TOPK_PARTIAL (shard_partial: the lists are then what
+// the global top-K needs of this rank, not the rank's own top-K) and topk_cells is 1.  Not served (they keep the exact top-K):
+// per-cell frames (the bound is per (query, cell) there), cell-range shards without the flag, grid indexes, m < 5.
 // Policy (topk_cells = 0): declines for now (see below); topk_cells = 1 serves every such call.
 CellTopkPlan knn_cells_topk_plan(const CellTopkInputs &in)
 {
@@ -3505,7 +3529,7 @@ CellTopkPlan knn_cells_topk_plan(const CellTopkInputs &in)
     // candidate room: the filter top-K's rule.  The K-th seed bound admits about K times the 1-NN bound's rows, nearly each its own
     // record, but the re-rank's distance gate (knn_topk_gate) lets about one key of a record's sixteen through
     t.ccap = (unsigned)std::min<long long>(4096 + 128 * (long long)in.K, ((long long)32 << 20) / qi.m);
-    const bool layout = in.has_cells && !in.sharded && !in.other_path && !qi.centred && (!qi.rows_u8 || in.bins) && qi.kt >= 1 &&
+    const bool layout = in.has_cells && (!in.sharded || in.shard_partial) && !in.other_path && !qi.centred && (!qi.rows_u8 || in.bins) && qi.kt >= 1 &&
                         qi.kt <= 2 && qi.k <= 32;
     const bool call = qi.m >= 5 && t.ccap >= 64u && in.n_outliers <= t.ccap / 2u;
     // Policy (0) declines every call for now: the issue's condition for sending a (shape, K) to this path by default is a measured
@@ -3513,7 +3537,8 @@ CellTopkPlan knn_cells_topk_plan(const CellTopkInputs &in)
     // once they are: `policy_from`, the 1-NN size rule of k, and never under `cells` = 2.
     const bool policy_measured = false;
     const bool policy_from = in.cells_option != 2 && in.n >= knn_cells_size_rule(qi.k);
-    const bool policy = in.topk_cells == 1 || (in.topk_cells == 0 && policy_measured && policy_from);
+    // (a cell-range shard: on request only — nobody has measured either side there, profiles/shard_topk_timing.txt will)
+    const bool policy = in.topk_cells == 1 || (in.topk_cells == 0 && !in.sharded && policy_measured && policy_from);
     t.use = layout && call && policy && in.topk_cells != 2;
     if (!t.use)
         return t;
@@ -3536,7 +3561,7 @@ hipError_t knn_cells_query_topk(FilterState &st, FilterWorkspace &w, const CellT
 {
     const CellIndex &c = *st.cells;
     const CellQueryPlan &p = tp.batch;
-    if (!tp.use || m > tp.pass_m || tp.scan.self || tp.scan.ctr || c.centred || c.geom)
+    if (!tp.use || m > tp.pass_m || tp.scan.self || tp.scan.ctr || c.centred || (c.geom && (!c.gids || base != 0)))
         return hipErrorInvalidValue;
     const CellKernel scan = cells_records_kernel(tp.scan);
     FTRY(ensure_cells_workspace(st, w, m, p, scan));
@@ -3552,10 +3577,12 @@ hipError_t knn_cells_query_topk(FilterState &st, FilterWorkspace &w, const CellT
     const unsigned parity = w.cell_batches++ & 1u;
     w.ctl_cur = w.ctl + KNN_CTL_WORDS * (1u + parity);
     unsigned *ctl_next = w.ctl + KNN_CTL_WORDS * (2u - parity);
-    SeedLayer layer;
-    memset(&layer, 0, sizeof layer);
+    // A cell-range shard (KNN_QUERY_TOPK_PARTIAL): the K-th seed bound over the rows of the GLOBAL set the seed layer reaches — the
+    // prep kernel scores a seed cell of another rank from the layer's tiles, as the 1-NN form does —, and gids on the keys from the
+    // moment they are candidates (the select sorts them, a fold compares them with other ranks'): CellFinal stays empty, nothing is
+    // translated behind the select, while a 1-NN batch on the same slot keeps translating in its own last kernel.
     const CellBatch b{st, c, w, p, m, m_padded, q, r, base, keys, nullptr, CellFinal{nullptr, nullptr, 0}, cells_self(p, c, w, m_padded),
-                      layer, ctl_next, s, K};
+                      cells_seed_layer(c), ctl_next, s, K};
     FTRY(hipMemsetAsync(ccount, 0, (size_t)m * sizeof(unsigned), s));
     cells_prep_topk_launch(b);
     FTRY(hipGetLastError());
@@ -3573,9 +3600,9 @@ hipError_t knn_cells_query_topk(FilterState &st, FilterWorkspace &w, const CellT
     FTRY(knn_topk_filter_finish(st.k, m, K, st.ntiles * 32, base, q, r, w.records, nullptr, w.counts, w.nlists, w.slice, w.ctl_cur,
                                 RerankPieces(), c.perm, st.n_outliers, st.outliers, cand, ccount, tp.ccap, keys, init_keys ? 1 : 0, s,
                                 w.records + w.ovf_base, w.ctl_cur + KNN_CTL_RECORDS, w.ovf_cap, w.dup,
-                                (float)(1.0 / ((double)st.sigma * (double)st.sigma)), st.ref_norms));
+                                (float)(1.0 / ((double)st.sigma * (double)st.sigma)), st.ref_norms, c.gids));
     // gated: the exact top-K answers a pass that raised FALLBACK; it folds into the keys the select left alone
-    return knn_exact_topk_launch(st.k, m, K, st.n, base, nullptr, q, r, keys, init_keys ? 1 : 0, part, part_bytes, num_cu, s,
+    return knn_exact_topk_launch(st.k, m, K, st.n, base, c.gids, q, r, keys, init_keys ? 1 : 0, part, part_bytes, num_cu, s,
                                  w.ctl_cur + KNN_CTL_FALLBACK);
 }
 

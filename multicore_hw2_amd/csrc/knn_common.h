@@ -78,7 +78,9 @@ hipError_t knn_topk_filter_finish(int k, int m, int K, long long positions, long
                                   // null: every finite key is a candidate (the filter top-K)
                                   const float *gate_dup = nullptr, float inv_sigma2 = 0.0f,
                                   // with the gate: the layout's norms by position (+INF: padding, out-of-box rows — not re-ranked)
-                                  const float *pos_norms = nullptr);
+                                  const float *pos_norms = nullptr,
+                                  // with the gate, cell-range shards (base 0): the candidates' index half is gids[row]
+                                  const unsigned *gids = nullptr);
 // b[j] <- the K smallest of a[j] and b[j] (both sorted lists of K keys), sorted.
 hipError_t knn_topk_merge_launch(int m, int K, const u64 *a, u64 *b, hipStream_t stream);
 
@@ -381,6 +383,7 @@ struct CellTopkInputs {
     bool has_cells = false;        // a cell-sorted layout exists
     bool bins = false;             // its 8-bit rows are in per-dimension bin frames (with q.rows_u8)
     bool sharded = false;          // cell-range shard
+    bool shard_partial = false;    // ... whose call carries KNN_QUERY_TOPK_PARTIAL (the only top-K a cell-range shard prunes)
     bool other_path = false;       // the grid index or a forced exact path answers this index
     unsigned n_outliers = 0;
 };

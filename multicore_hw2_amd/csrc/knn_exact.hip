@@ -1210,6 +1210,8 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_topk_rerank_kernel(const float 
 // "16 keys per record" into about one.  One block per list; records through perm, all 16 rows — except positions whose layout
 // norm is +INF: padding, and rows outside the robust box, which sit in the layout beside rows that pass and are pushed by
 // knn_topk_outlier_kernel (pushed here as well such a row stood in the list twice and the select dropped the query's K-th key).
+// gids (nullable; cell-range shards, where base is 0): the key's index half becomes gids[row] BEFORE it enters the candidate list —
+// the select sorts keys and a fold compares them with other ranks' —; gids ascend with the row, so v0's lowest-index tie-break stands.
 __global__ __launch_bounds__(KNN_BLOCK) void knn_topk_rerank_gated_kernel(const float *__restrict__ Q, const float *__restrict__ R,
                                                                          int k, long long n, long long base,
                                                                          const u64 *__restrict__ rec,
@@ -1219,7 +1221,7 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_topk_rerank_gated_kernel(const 
                                                                          const float *__restrict__ norms,
                                                                          const float *__restrict__ dup, float inv_sigma2,
                                                                          u64 *__restrict__ cand, unsigned *__restrict__ ccount,
-                                                                         unsigned ccap)
+                                                                         unsigned ccap, const unsigned *__restrict__ gids)
 {
     const unsigned list_id = blockIdx.x;
     if (ctl[KNN_CTL_FALLBACK] != 0u || list_id >= nlists)
@@ -1237,17 +1239,17 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_topk_rerank_gated_kernel(const 
         const unsigned rmask = pos < n && norms[pos] < INFINITY ? 0xFFFFu : 0u;
         const u64 key = rerank_pair<0>(Q, R, k, n, base, e, reg, rmask, 0u, perm, qi);
         if (key != ~0ull && __uint_as_float((unsigned)(key >> 32)) <= knn_topk_gate(dup[qi], inv_sigma2))
-            topk_cand_push(key, qi, cand, ccount, ccap, ctl);
+            topk_cand_push(gids ? (key & 0xFFFFFFFF00000000ull) | (u64)gids[(unsigned)key] : key, qi, cand, ccount, ccap, ctl);
     }
 }
 
 // Rows outside the filter's robust box never enter the scan: every (query, listed row) pair with v0 arithmetic, each finite
-// key to the query's candidate list.  grid (row blocks, queries).
+// key to the query's candidate list.  grid (row blocks, queries).  gids (nullable): as in the gated re-rank.
 __global__ __launch_bounds__(KNN_BLOCK) void knn_topk_outlier_kernel(const float *__restrict__ Q, const float *__restrict__ R,
                                                                     int k, unsigned count, long long base,
                                                                     const unsigned *__restrict__ list, unsigned *__restrict__ ctl,
                                                                     u64 *__restrict__ cand, unsigned *__restrict__ ccount,
-                                                                    unsigned ccap)
+                                                                    unsigned ccap, const unsigned *__restrict__ gids)
 {
 #pragma clang fp contract(off)
     if (ctl[KNN_CTL_FALLBACK] != 0u)
@@ -1264,7 +1266,7 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_topk_outlier_kernel(const float
             acc = acc + sq;
         }
         if (acc < INFINITY)
-            topk_cand_push(pack_key(acc, (unsigned)(base + (long long)row)), q, cand, ccount, ccap, ctl);
+            topk_cand_push(pack_key(acc, gids ? gids[row] : (unsigned)(base + (long long)row)), q, cand, ccount, ccap, ctl);
     }
 }
 
@@ -1300,20 +1302,23 @@ hipError_t knn_topk_filter_finish(int k, int m, int K, long long positions, long
                                   unsigned slice, unsigned *ctl, RerankPieces pieces, const unsigned *perm,
                                   unsigned n_outliers, const unsigned *outliers, u64 *cand, unsigned *ccount, unsigned ccap,
                                   u64 *keys, int init, hipStream_t s, const u64 *ovf_rec, const unsigned *ovf_count,
-                                  unsigned ovf_slice, const float *gate_dup, float inv_sigma2, const float *pos_norms)
+                                  unsigned ovf_slice, const float *gate_dup, float inv_sigma2, const float *pos_norms,
+                                  const unsigned *gids)
 {
     if (gate_dup) {   // the cell-pruned top-K: the gated re-rank over the waves' slices and over the shared overflow area
-        if (rec_rows || !perm || !pos_norms)
+        if (rec_rows || !perm || !pos_norms || (gids && base != 0))
             return hipErrorInvalidValue;
         if (nlists)
             hipLaunchKernelGGL(knn_topk_rerank_gated_kernel, dim3(nlists), dim3(KNN_BLOCK), 0, s, q, r, k, positions, base, rec, counts,
-                               nlists, slice, ctl, perm, pos_norms, gate_dup, inv_sigma2, cand, ccount, ccap);
+                               nlists, slice, ctl, perm, pos_norms, gate_dup, inv_sigma2, cand, ccount, ccap, gids);
         if (ovf_rec && ovf_count)   // (its `want > slice` rule raises FALLBACK for an over-full area)
             hipLaunchKernelGGL(knn_topk_rerank_gated_kernel, dim3(1), dim3(KNN_BLOCK), 0, s, q, r, k, positions, base, ovf_rec, ovf_count,
-                               1u, ovf_slice, ctl, perm, pos_norms, gate_dup, inv_sigma2, cand, ccount, ccap);
+                               1u, ovf_slice, ctl, perm, pos_norms, gate_dup, inv_sigma2, cand, ccount, ccap, gids);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess)
             return e;
+    } else if (gids) {   // (the ungated re-rank of the filter's full scan pushes base + row: not for cell-range shards)
+        return hipErrorInvalidValue;
     } else if (nlists) {
         hipLaunchKernelGGL(knn_topk_rerank_kernel, dim3(nlists), dim3(KNN_BLOCK), 0, s, q, r, k, positions, base, rec, rec_rows,
                            counts, nlists, slice, ctl, pieces, perm, cand, ccount, ccap);
@@ -1324,7 +1329,7 @@ hipError_t knn_topk_filter_finish(int k, int m, int K, long long positions, long
     if (n_outliers) {
         const unsigned gx = (n_outliers + KNN_BLOCK - 1) / KNN_BLOCK < 64u ? (n_outliers + KNN_BLOCK - 1) / KNN_BLOCK : 64u;
         hipLaunchKernelGGL(knn_topk_outlier_kernel, dim3(gx, (unsigned)m), dim3(KNN_BLOCK), 0, s, q, r, k, n_outliers, base,
-                           outliers, ctl, cand, ccount, ccap);
+                           outliers, ctl, cand, ccount, ccap, gids);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess)
             return e;
