@@ -430,6 +430,22 @@ int knn_debug_topk_gate(int k, float sigma, double amax, double bmax, double nma
  * 1 if records carry row masks; per piece (four) {QT, first tile, tiles, grid x, grid y, first list}; the re-rank's pieces,
  * first lists [4] and first query rows [4]}. */
 int knn_debug_filter_query_plan(const long long in[11], long long out[49]);
+/* Test hook (host arithmetic only, no GPU needed): which path answers a call on a shard of n > 0 rows (the value
+ * knn_index_last_stats reports in [0]), under the options given as inputs.  in = {the twenty inputs of
+ * knn_debug_cells_topk_plan — K = 0: a 1-NN call; "1 if a cell-sorted layout exists": filter layouts exist and are cell-sorted —,
+ * option path, 1 if the index has filter layouts, 1 if it has a grid index (never together with a cell-range shard), 1 if the
+ * creator asked for the filter layouts, 1 if the call carries KNN_QUERY_INIT_KEYS};
+ * out = {the way: 1 exact, 2 filter, 3 grid index, 4 cell-pruned; 1 if the keys are set to (+INF, 0) by a launch of their own
+ * first (1-NN); top-K: candidate keys per query, 1 if knn_debug_cells_topk_plan takes the call, its passes and the first pass's
+ * queries}. */
+int knn_debug_query_route(const long long in[25], long long out[6]);
+/* Test hook (host arithmetic only, no GPU needed): what an index is built with.  in = {k, n_local, 1 if the rows are on the
+ * device, build_filter (-1 library policy: knn_index_create; 0 none, 1 the MFMA filter layouts, 2 cell-sorted), build_grid (-1
+ * library policy, 0, 1), and the options path, cells, ingest, cells_build};
+ * out = {1 if the creator asked for the layouts below the size rule, 1 if the layouts are cell-sorted, the resolved build_filter,
+ * 1 if the grid index is tried first, 1 if the layouts are built (unless the grid index serves the shard), how host rows reach
+ * the device: 0 copy then build, 1 layouts under the copy, 2 cell sort under the copy}. */
+int knn_debug_index_build_plan(const long long in[9], long long out[6]);
 
 /* Test hook for the filter's error bound: raw MFMA filter scores S[m][n_local] (row-major,
  * device) for a query batch, the fp32 squared norms M[m] of the fp16 query rows (device), and

@@ -28,7 +28,7 @@ EXPORTED_SYMBOLS = [
     "knn_index_query_host", "knn_set_option", "knn_get_option", "knn_index_last_stats",
     "knn_synth_fill_device", "knn_index_timing", "knn_index_timing_read",
     "knn_debug_filter_scores", "knn_index_query_keys_slot", "knn_trim", "knn_keys_allreduce_min",
-    "knn_index_query_keys_ex", "knn_index_debug_counters", "knn_debug_scan_plan", "knn_debug_scan_plan_ex", "knn_debug_cells_query_plan", "knn_debug_cells_topk_plan", "knn_debug_seed_kth", "knn_debug_topk_gate", "knn_debug_filter_query_plan", "knn_debug_shard_policy", "knn_debug_plan_shard", "knn_debug_u8_row", "knn_debug_u8_bin_row", "knn_debug_u8_bin_threshold", "knn_index_query",
+    "knn_index_query_keys_ex", "knn_index_debug_counters", "knn_debug_scan_plan", "knn_debug_scan_plan_ex", "knn_debug_cells_query_plan", "knn_debug_cells_topk_plan", "knn_debug_seed_kth", "knn_debug_topk_gate", "knn_debug_filter_query_plan", "knn_debug_query_route", "knn_debug_index_build_plan", "knn_debug_shard_policy", "knn_debug_plan_shard", "knn_debug_u8_row", "knn_debug_u8_bin_row", "knn_debug_u8_bin_threshold", "knn_index_query",
     "knn_geom_create", "knn_geom_destroy", "knn_geom_info", "knn_geom_assign", "knn_index_create_sharded",
     "knn_index_seed_export", "knn_index_seed_attach", "knn_geom_first_cell",
     "knn_index_query_topk", "knn_keys_topk_merge", "knn_index_query_topk_host",
@@ -226,6 +226,38 @@ def debug_filter_query_plan(**inputs):
     p["pieces"] = [dict(zip(FILTER_PIECE, v[16 + 6 * i:22 + 6 * i])) for i in range(p["npieces"])]
     p["rerank"] = (v[40], tuple(v[41:45]), tuple(v[45:49]))
     return p
+
+
+QUERY_ROUTE_INPUTS = CELLS_TOPK_INPUTS + ("path", "filter_usable", "has_grid", "filter_wanted", "init_keys")
+QUERY_ROUTE = ("way", "fill_keys_first", "ccap", "topk_use", "passes", "pass_m")
+WAY_EXACT, WAY_FILTER, WAY_GRID, WAY_CELLS = 1, 2, 3, 4   # last_stats()[0]
+
+
+def debug_query_route(**inputs):
+    """knn_debug_query_route: which path answers a call (last_stats()[0]) for the inputs named in QUERY_ROUTE_INPUTS — K = 0: a
+    1-NN call; sharded: 0, 1, or 2 (a cell-range shard whose call carries KNN_QUERY_TOPK_PARTIAL).  Host arithmetic; works
+    without a GPU."""
+    vin = (ctypes.c_longlong * len(QUERY_ROUTE_INPUTS))(*[int(inputs[n]) for n in QUERY_ROUTE_INPUTS])
+    out = (ctypes.c_longlong * len(QUERY_ROUTE))()
+    f = lib().knn_debug_query_route
+    f.argtypes = [ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)]
+    _check(f(vin, out))
+    return dict(zip(QUERY_ROUTE, list(out)))
+
+
+INDEX_BUILD_INPUTS = ("k", "n_local", "refs_on_device", "build_filter", "build_grid", "path", "cells", "ingest", "cells_build")
+INDEX_BUILD_PLAN = ("filter_wanted", "want_cells", "build_filter", "grid_planned", "want_layouts", "ingest")
+
+
+def debug_index_build_plan(**inputs):
+    """knn_debug_index_build_plan: what an index is built with, for the inputs named in INDEX_BUILD_INPUTS (ingest out: 0 copy
+    then build, 1 layouts under the copy, 2 cell sort under the copy).  Host arithmetic; works without a GPU."""
+    vin = (ctypes.c_longlong * len(INDEX_BUILD_INPUTS))(*[int(inputs[n]) for n in INDEX_BUILD_INPUTS])
+    out = (ctypes.c_longlong * len(INDEX_BUILD_PLAN))()
+    f = lib().knn_debug_index_build_plan
+    f.argtypes = [ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)]
+    _check(f(vin, out))
+    return dict(zip(INDEX_BUILD_PLAN, list(out)))
 
 
 def debug_plan_shard(k, m, rows):

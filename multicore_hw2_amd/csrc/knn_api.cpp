@@ -78,7 +78,7 @@ std::atomic<long long> g_opt_cells_lists{0};     // pruned scan, who lists a cel
 std::atomic<long long> g_opt_scan_deal{0};       // pruned scan, how waves get their items: 0 auto, 1 fixed deal, 2 block counter
 std::atomic<long long> g_opt_cells_build{0};     // cell-sorted layout: 0 fast two-pass build (counted one if a bucket overflows), 1 the one-pass placement, 2 the counted two-pass build (A/B, tests)
 std::atomic<long long> g_opt_topk_cells{0};      // top-K on the pruned scan: 0 policy (knn_cells_topk_plan), 1 wherever the layout allows it, 2 never
-std::atomic<long long> g_opt_cells{0};       // cell-sorted layouts (k <= 16): 0 resident indexes large enough to prune (index_create_impl), 1 from 2^17 rows, 2 never
+std::atomic<long long> g_opt_cells{0};       // cell-sorted layouts (k <= 16): 0 resident indexes large enough to prune (knn_index_build_plan), 1 from 2^17 rows, 2 never
 std::atomic<long long> g_opt_ingest{0};      // indexes created from host rows: 0 layouts built under the copy, 1 copy then build
 std::atomic<long long> g_opt_rccl{0};        // 0 auto (several GPUs, one shard each), 1 always, 2 never
 std::atomic<long long> g_rccl_reductions{0}; // cudaCallback merges done by the RCCL all-reduce
@@ -317,122 +317,74 @@ int knn_device_count(void)
     return n;
 }
 
+}  // extern "C"
+
+namespace {
+
+// The options, one row each: name, range (and, where the range has holes, the set of values as a bit mask), where the value
+// lives, and the message a value outside gets.  knn_set_option and knn_get_option both walk this table.
+struct OptionRow {
+    const char *name;
+    long long lo, hi;
+    unsigned long long allowed;          // 0: every value in [lo, hi]; else bit v set = v allowed
+    std::atomic<long long> *wide;        // the value's home: one of the two
+    std::atomic<int> *narrow;
+    const char *message;
+};
+const OptionRow kOptions[] = {
+    {"path", 0, 3, 0, &g_opt_path, nullptr, "knn_set_option: path must be 0, 1, 2 or 3"},
+    {"shards", 0, 1024, 0, &g_opt_shards, nullptr, "knn_set_option: shards must be in [0, 1024]"},
+    {"filter_qt", 0, 32, 1ull | 1ull << 2 | 1ull << 8 | 1ull << 16 | 1ull << 32, &g_opt_filter_qt, nullptr, "knn_set_option: filter_qt must be 0, 2, 8, 16 or 32"},
+    {"filter_chain", 0, 2, 0, &g_opt_filter_chain, nullptr, "knn_set_option: filter_chain must be 0 (auto), 1 (chained) or 2 (free)"},
+    {"stream", 0, 2, 0, &g_opt_stream, nullptr, "knn_set_option: stream must be 0 (auto), 1 (never) or 2 (whenever the shard is >= 32 MiB)"},
+    {"scan_blocks", 0, 2, 0, &g_opt_scan_blocks, nullptr, "knn_set_option: scan_blocks must be 0 (auto), 1 or 2"},
+    {"cells_build", 0, 2, 0, &g_opt_cells_build, nullptr, "knn_set_option: cells_build must be 0 (fast two-pass), 1 (one-pass placement) or 2 (counted two-pass)"},
+    {"sample_stride", 0, 1024, 0, &g_opt_sample_stride, nullptr, "knn_set_option: sample_stride must be in [0, 1024]"},
+    {"run_thresholds", 0, 2, 0, &g_opt_run_thresholds, nullptr, "knn_set_option: run_thresholds must be 0 (auto), 1 (on) or 2 (off)"},
+    {"cells_centre", 0, 2, 0, nullptr, &g_knn_cells_centre, "knn_set_option: cells_centre must be 0 (auto: per-cell frames for clustered data), 1 (always) or 2 (never)"},
+    {"cells_rows", 0, 2, 0, nullptr, &g_knn_cells_rows, "knn_set_option: cells_rows must be 0 (auto), 1 (fp16 fragments) or 2 (8-bit rows in per-cell frames)"},
+    {"cells_u8_frame", 0, 2, 0, nullptr, &g_knn_cells_u8_frame, "knn_set_option: cells_u8_frame must be 0 (auto), 1 (per-cell frames) or 2 (per-dimension bin frames)"},
+    {"topk_cells", 0, 2, 0, &g_opt_topk_cells, nullptr, "knn_set_option: topk_cells must be 0 (policy), 1 (pruned top-K wherever the layout allows it) or 2 (never)"},
+    {"cells_lists", 0, 2, 0, &g_opt_cells_lists, nullptr, "knn_set_option: cells_lists must be 0 (auto), 1 (match launch) or 2 (the scan lists its own items)"},
+    {"scan_deal", 0, 2, 0, &g_opt_scan_deal, nullptr, "knn_set_option: scan_deal must be 0 (auto), 1 (fixed deal) or 2 (block counter)"},
+    {"cells", 0, 2, 0, &g_opt_cells, nullptr, "knn_set_option: cells must be 0 (library policy), 1 (always) or 2 (never)"},
+    {"ingest", 0, 1, 0, &g_opt_ingest, nullptr, "knn_set_option: ingest must be 0 (layouts built under the copy) or 1 (copy, then build)"},
+    {"rccl", 0, 2, 0, &g_opt_rccl, nullptr, "knn_set_option: rccl must be 0 (auto), 1 (always) or 2 (never: host merge)"},
+    {"filter_rounds", 0, 64, 0, &g_opt_filter_rounds, nullptr, "knn_set_option: filter_rounds must be in [0, 64]"},
+};
+// What knn_get_option reads besides: counters nobody sets.
+struct CounterRow {
+    const char *name;
+    long long (*read)();
+};
+const CounterRow kCounters[] = {
+    {"cells_centred_builds", [] { return g_knn_cells_centred_builds.load(); }},   // cell-sorted layouts moved into per-cell frames so far
+    {"cells_u8_bin_builds", [] { return g_knn_cells_u8_bin_builds.load(); }},     // 8-bit-row layouts built in bin frames so far
+    {"cells_u8_builds", [] { return g_knn_cells_u8_builds.load(); }},             // cell-sorted layouts given 8-bit rows so far
+    {"rccl_reductions", [] { return g_rccl_reductions.load(); }},                 // cudaCallback merges done by RCCL so far
+    {"rccl_comm_sets", [] { return (long long)knn_rccl_comm_sets(); }},           // RCCL communicator sets created by this process (at most one)
+    {"last_shards", [] { return g_last_shards.load(); }},                         // GPUs / shards the most recent cudaCallback was split over
+    {"last_cells", [] { return g_last_cells.load(); }},                           // how many of them the pruned scan served
+    {"rccl_version", [] { return (long long)knn_rccl_version(); }},               // NCCL_VERSION_CODE of the loaded RCCL, 0 if none
+};
+
+}  // namespace
+
+extern "C" {
+
 int knn_set_option(const char *name, long long value)
 {
     if (!name)
         return fail(KNN_EINVAL, "knn_set_option: null name");
-    if (!strcmp(name, "path")) {
-        if (value < 0 || value > 3)
-            return fail(KNN_EINVAL, "knn_set_option: path must be 0, 1, 2 or 3");
-        g_opt_path = value;
-        return KNN_OK;
-    }
-    if (!strcmp(name, "shards")) {
-        if (value < 0 || value > 1024)
-            return fail(KNN_EINVAL, "knn_set_option: shards must be in [0, 1024]");
-        g_opt_shards = value;
-        return KNN_OK;
-    }
-    if (!strcmp(name, "filter_qt")) {
-        if (value != 0 && value != 2 && value != 8 && value != 16 && value != 32)
-            return fail(KNN_EINVAL, "knn_set_option: filter_qt must be 0, 2, 8, 16 or 32");
-        g_opt_filter_qt = value;
-        return KNN_OK;
-    }
-    if (!strcmp(name, "filter_chain")) {
-        if (value < 0 || value > 2)
-            return fail(KNN_EINVAL, "knn_set_option: filter_chain must be 0 (auto), 1 (chained) or 2 (free)");
-        g_opt_filter_chain = value;
-        return KNN_OK;
-    }
-    if (!strcmp(name, "stream")) {
-        if (value < 0 || value > 2)
-            return fail(KNN_EINVAL, "knn_set_option: stream must be 0 (auto), 1 (never) or 2 (whenever the shard is >= 32 MiB)");
-        g_opt_stream = value;
-        return KNN_OK;
-    }
-    if (!strcmp(name, "scan_blocks")) {
-        if (value < 0 || value > 2)
-            return fail(KNN_EINVAL, "knn_set_option: scan_blocks must be 0 (auto), 1 or 2");
-        g_opt_scan_blocks = value;
-        return KNN_OK;
-    }
-    if (!strcmp(name, "cells_build")) {
-        if (value < 0 || value > 2)
-            return fail(KNN_EINVAL, "knn_set_option: cells_build must be 0 (fast two-pass), 1 (one-pass placement) or 2 (counted two-pass)");
-        g_opt_cells_build = value;
-        return KNN_OK;
-    }
-    if (!strcmp(name, "sample_stride")) {
-        if (value < 0 || value > 1024)
-            return fail(KNN_EINVAL, "knn_set_option: sample_stride must be in [0, 1024]");
-        g_opt_sample_stride = value;
-        return KNN_OK;
-    }
-    if (!strcmp(name, "run_thresholds")) {
-        if (value < 0 || value > 2)
-            return fail(KNN_EINVAL, "knn_set_option: run_thresholds must be 0 (auto), 1 (on) or 2 (off)");
-        g_opt_run_thresholds = value;
-        return KNN_OK;
-    }
-    if (!strcmp(name, "cells_centre")) {
-        if (value < 0 || value > 2)
-            return fail(KNN_EINVAL, "knn_set_option: cells_centre must be 0 (auto: per-cell frames for clustered data), 1 (always) or 2 (never)");
-        g_knn_cells_centre = (int)value;
-        return KNN_OK;
-    }
-    if (!strcmp(name, "cells_rows")) {
-        if (value < 0 || value > 2)
-            return fail(KNN_EINVAL, "knn_set_option: cells_rows must be 0 (auto), 1 (fp16 fragments) or 2 (8-bit rows in per-cell frames)");
-        g_knn_cells_rows = (int)value;
-        return KNN_OK;
-    }
-    if (!strcmp(name, "cells_u8_frame")) {
-        if (value < 0 || value > 2)
-            return fail(KNN_EINVAL, "knn_set_option: cells_u8_frame must be 0 (auto), 1 (per-cell frames) or 2 (per-dimension bin frames)");
-        g_knn_cells_u8_frame = (int)value;
-        return KNN_OK;
-    }
-    if (!strcmp(name, "topk_cells")) {
-        if (value < 0 || value > 2)
-            return fail(KNN_EINVAL, "knn_set_option: topk_cells must be 0 (policy), 1 (pruned top-K wherever the layout allows it) or 2 (never)");
-        g_opt_topk_cells = value;
-        return KNN_OK;
-    }
-    if (!strcmp(name, "cells_lists")) {
-        if (value < 0 || value > 2)
-            return fail(KNN_EINVAL, "knn_set_option: cells_lists must be 0 (auto), 1 (match launch) or 2 (the scan lists its own items)");
-        g_opt_cells_lists = value;
-        return KNN_OK;
-    }
-    if (!strcmp(name, "scan_deal")) {
-        if (value < 0 || value > 2)
-            return fail(KNN_EINVAL, "knn_set_option: scan_deal must be 0 (auto), 1 (fixed deal) or 2 (block counter)");
-        g_opt_scan_deal = value;
-        return KNN_OK;
-    }
-    if (!strcmp(name, "cells")) {
-        if (value < 0 || value > 2)
-            return fail(KNN_EINVAL, "knn_set_option: cells must be 0 (library policy), 1 (always) or 2 (never)");
-        g_opt_cells = value;
-        return KNN_OK;
-    }
-    if (!strcmp(name, "ingest")) {
-        if (value < 0 || value > 1)
-            return fail(KNN_EINVAL, "knn_set_option: ingest must be 0 (layouts built under the copy) or 1 (copy, then build)");
-        g_opt_ingest = value;
-        return KNN_OK;
-    }
-    if (!strcmp(name, "rccl")) {
-        if (value < 0 || value > 2)
-            return fail(KNN_EINVAL, "knn_set_option: rccl must be 0 (auto), 1 (always) or 2 (never: host merge)");
-        g_opt_rccl = value;
-        return KNN_OK;
-    }
-    if (!strcmp(name, "filter_rounds")) {
-        if (value < 0 || value > 64)
-            return fail(KNN_EINVAL, "knn_set_option: filter_rounds must be in [0, 64]");
-        g_opt_filter_rounds = value;
+    for (const OptionRow &o : kOptions) {
+        if (strcmp(name, o.name))
+            continue;
+        if (value < o.lo || value > o.hi || (o.allowed && !(o.allowed >> value & 1ull)))
+            return fail(KNN_EINVAL, o.message);
+        if (o.wide)
+            *o.wide = value;
+        else
+            *o.narrow = (int)value;
         return KNN_OK;
     }
     return fail(KNN_EINVAL, "knn_set_option: unknown option", name);
@@ -440,85 +392,66 @@ int knn_set_option(const char *name, long long value)
 
 long long knn_get_option(const char *name)
 {
-    if (name && !strcmp(name, "path"))
-        return g_opt_path;
-    if (name && !strcmp(name, "shards"))
-        return g_opt_shards;
-    if (name && !strcmp(name, "filter_qt"))
-        return g_opt_filter_qt;
-    if (name && !strcmp(name, "filter_rounds"))
-        return g_opt_filter_rounds;
-    if (name && !strcmp(name, "filter_chain"))
-        return g_opt_filter_chain;
-    if (name && !strcmp(name, "stream"))
-        return g_opt_stream;
-    if (name && !strcmp(name, "rccl"))
-        return g_opt_rccl;
-    if (name && !strcmp(name, "ingest"))
-        return g_opt_ingest;
-    if (name && !strcmp(name, "cells"))
-        return g_opt_cells;
-    if (name && !strcmp(name, "scan_blocks"))
-        return g_opt_scan_blocks;
-    if (name && !strcmp(name, "scan_deal"))
-        return g_opt_scan_deal;
-    if (name && !strcmp(name, "cells_lists"))
-        return g_opt_cells_lists;
-    if (name && !strcmp(name, "topk_cells"))
-        return g_opt_topk_cells;
-    if (name && !strcmp(name, "cells_centre"))
-        return (long long)g_knn_cells_centre.load();
-    if (name && !strcmp(name, "cells_centred_builds"))   // read-only: cell-sorted layouts moved into per-cell frames so far
-        return g_knn_cells_centred_builds.load();
-    if (name && !strcmp(name, "cells_u8_frame"))
-        return (long long)g_knn_cells_u8_frame.load();
-    if (name && !strcmp(name, "cells_u8_bin_builds"))   // read-only: 8-bit-row layouts built in bin frames so far
-        return g_knn_cells_u8_bin_builds.load();
-    if (name && !strcmp(name, "cells_rows"))
-        return (long long)g_knn_cells_rows.load();
-    if (name && !strcmp(name, "cells_u8_builds"))   // read-only: cell-sorted layouts given 8-bit rows so far
-        return g_knn_cells_u8_builds.load();
-    if (name && !strcmp(name, "run_thresholds"))
-        return g_opt_run_thresholds;
-    if (name && !strcmp(name, "sample_stride"))
-        return g_opt_sample_stride;
-    if (name && !strcmp(name, "cells_build"))
-        return g_opt_cells_build;
-    if (name && !strcmp(name, "rccl_reductions"))   // read-only: cudaCallback merges done by RCCL so far
-        return g_rccl_reductions;
-    if (name && !strcmp(name, "rccl_comm_sets"))    // read-only: RCCL communicator sets created by this process (at most one)
-        return knn_rccl_comm_sets();
-    if (name && !strcmp(name, "last_shards"))       // read-only: GPUs / shards the most recent cudaCallback was split over
-        return g_last_shards;
-    if (name && !strcmp(name, "last_cells"))        // read-only: how many of them the pruned scan served
-        return g_last_cells;
-    if (name && !strcmp(name, "rccl_version"))      // read-only: NCCL_VERSION_CODE of the loaded RCCL, 0 if none
-        return knn_rccl_version();
+    if (!name)
+        return -1;
+    for (const OptionRow &o : kOptions)
+        if (!strcmp(name, o.name))
+            return o.wide ? o.wide->load() : (long long)o.narrow->load();
+    for (const CounterRow &c : kCounters)
+        if (!strcmp(name, c.name))
+            return c.read();
     return -1;
 }
 
 }  // extern "C"
 
+// What an index is built with (knn_common.h; tests/test_route_logic.py restates it through knn_debug_index_build_plan).
+IndexBuildPlan knn_index_build_plan(const IndexBuildInputs &in)
+{
+    IndexBuildPlan p;
+    const int k = in.k;
+    const long long n = in.n_local;
+    // MFMA filter layouts (skipped for small shards and when the exact path is forced)
+    p.filter_wanted = in.build_filter > 0;
+    // cell-sorted layout for the pruned scan: indexes the caller keeps (library policy) or on request; the
+    // one-shot cudaCallback asks for explicit layouts and answers one batch, which does not repay the sort.
+    // Pruning needs enough cells for the dimension: measured on uniform data at m = 1024 (profiles/r02_cells_policy.txt)
+    // the pruned scan wins from 2^19 rows for k <= 12 and from 2^20 rows for k = 13..16; below that the lists
+    // hold most of the batch and the full scan's register-resident loop is the faster way to score them.
+    // (16 < k <= 32, round 5: the cells cut the first 16 dimensions; policy from the measurements in profiles/r05_cells_k17_32.txt:
+    // uniform data, m = 1024, ms per step pruned / full scan on one box — n = 2^24: k 17 0.211 / 0.94, 20 0.265 / 0.96, 22 0.424 / 0.962,
+    // 24 0.625 / 0.976, 25 0.716 / 0.980, 26 1.06 / 0.99 (loses); n = 2^23: k 21 0.238 / 0.465, 23 0.354 / 0.476, 24 0.445 / 0.477 (a wash),
+    // 25 0.579 / 0.480 (loses); n = 2^22: k 20 0.143 / 0.25, 21 0.174 / 0.236, 22 0.220 / 0.240 and 23 0.219 / 0.243 (a wash), 24 loses)
+    p.want_cells = k <= 32 && n >= (1ll << 17) &&
+                   (in.cells == 1 || (in.cells == 0 && in.build_filter == 2) ||
+                    (in.cells == 0 && in.build_filter < 0 && n >= knn_cells_size_rule(k)));
+    p.build_filter = in.build_filter;
+    if (in.build_filter < 0) {
+        // library policy: shards of >= 65536 rows; for 32 < k <= 4096 (3k+3 exact lane-ops per pair,
+        // one query per lane above k = 64, row-per-lane kernels above 128) the MFMA filter pays off from 4096 rows already
+        p.build_filter = in.path == 2 || n >= 65536 || (k > 32 && k <= KNN_FILTER_MAX_K && n >= 4096);
+        p.filter_wanted = p.build_filter && n < 65536 && in.path != 2;
+    }
+    // k <= 4: the uniform-grid index (SURVEY §8 f4) — resident shards of >= 16384 rows, or whenever forced
+    p.grid_planned = k <= 4 && (in.path == 3 || (in.path == 0 && in.build_grid != 0 && (in.build_grid > 0 || n >= 16384)));
+    // (a shard the grid index will serve gets no MFMA layouts unless the grid turns out to be ruled out)
+    p.want_layouts = n > 0 && in.path != 1 && in.path != 3 && p.build_filter;
+    // host rows: the layouts are built under the copy (the cell sort: its fast build's bucket pass) unless option `ingest` says
+    // copy first or the grid index comes first
+    if (n > 0 && !in.refs_on_device && p.want_layouts && !p.grid_planned && in.ingest != 1) {
+        if (!p.want_cells)
+            p.ingest = IngestForm::LayoutsUnderCopy;
+        else if (in.cells_build == 0)
+            p.ingest = IngestForm::CellsUnderCopy;
+    }
+    return p;
+}
+
 namespace {
 // build_filter: 1 build the MFMA filter layouts, 2 build them cell-sorted (the pruned scan), 0 do not, -1 library policy
 // build_grid (k <= 4): 1 build the grid index, 0 do not, -1 library policy
 int index_create_impl(knn_index **out, int device, int k, long long n_local, const float *refs,
-                      int refs_on_device, long long base_index, void *stream, int build_filter, int build_grid = -1);
-}
-
-extern "C" {
-
-int knn_index_create(knn_index **out, int device, int k, long long n_local, const float *refs,
-                     int refs_on_device, long long base_index, void *stream)
-{
-    return index_create_impl(out, device, k, n_local, refs, refs_on_device, base_index, stream, -1);
-}
-
-}  // extern "C"
-
-namespace {
-int index_create_impl(knn_index **out, int device, int k, long long n_local, const float *refs,
-                      int refs_on_device, long long base_index, void *stream, int build_filter, int build_grid)
+                      int refs_on_device, long long base_index, void *stream, int build_filter, int build_grid = -1)
 {
     if (!out)
         return fail(KNN_EINVAL, "knn_index_create: null out");
@@ -548,30 +481,11 @@ int index_create_impl(knn_index **out, int device, int k, long long n_local, con
         idx->num_cu = prop.multiProcessorCount;
 
     hipStream_t s = (hipStream_t)stream;
-    // MFMA filter layouts (skipped for small shards and when the exact path is forced)
-    idx->filter_wanted = build_filter > 0;
-    // cell-sorted layout for the pruned scan: indexes the caller keeps (library policy) or on request; the
-    // one-shot cudaCallback asks for explicit layouts and answers one batch, which does not repay the sort.
-    // Pruning needs enough cells for the dimension: measured on uniform data at m = 1024 (profiles/r02_cells_policy.txt)
-    // the pruned scan wins from 2^19 rows for k <= 12 and from 2^20 rows for k = 13..16; below that the lists
-    // hold most of the batch and the full scan's register-resident loop is the faster way to score them.
-    // (16 < k <= 32, round 5: the cells cut the first 16 dimensions; policy from the measurements in profiles/r05_cells_k17_32.txt:
-    // uniform data, m = 1024, ms per step pruned / full scan on one box — n = 2^24: k 17 0.211 / 0.94, 20 0.265 / 0.96, 22 0.424 / 0.962,
-    // 24 0.625 / 0.976, 25 0.716 / 0.980, 26 1.06 / 0.99 (loses); n = 2^23: k 21 0.238 / 0.465, 23 0.354 / 0.476, 24 0.445 / 0.477 (a wash),
-    // 25 0.579 / 0.480 (loses); n = 2^22: k 20 0.143 / 0.25, 21 0.174 / 0.236, 22 0.220 / 0.240 and 23 0.219 / 0.243 (a wash), 24 loses)
-    const long long cells_from = knn_cells_size_rule(k);
-    const bool want_cells = k <= 32 && n_local >= (1ll << 17) &&
-                            (g_opt_cells == 1 || (g_opt_cells == 0 && build_filter == 2) ||
-                             (g_opt_cells == 0 && build_filter < 0 && n_local >= cells_from));
-    if (build_filter < 0) {
-        // library policy: shards of >= 65536 rows; for 32 < k <= 4096 (3k+3 exact lane-ops per pair,
-        // one query per lane above k = 64, row-per-lane kernels above 128) the MFMA filter pays off from 4096 rows already
-        build_filter = g_opt_path == 2 || n_local >= 65536 || (k > 32 && k <= KNN_FILTER_MAX_K && n_local >= 4096);
-        idx->filter_wanted = build_filter && n_local < 65536 && g_opt_path != 2;
-    }
-    const bool grid_planned = k <= 4 && (g_opt_path == 3 || (g_opt_path == 0 && build_grid != 0 && (build_grid > 0 || n_local >= 16384)));
-    // (a shard the grid index will serve gets no MFMA layouts unless the grid turns out to be ruled out)
-    bool want_layouts = n_local > 0 && g_opt_path != 1 && g_opt_path != 3 && build_filter;
+    const IndexBuildPlan plan = knn_index_build_plan({k, n_local, refs_on_device != 0, build_filter, build_grid, (int)g_opt_path,
+                                                      (int)g_opt_cells, (int)g_opt_ingest, (int)g_opt_cells_build});
+    idx->filter_wanted = plan.filter_wanted;
+    const bool want_cells = plan.want_cells;
+    bool want_layouts = plan.want_layouts;   // (until the grid index turns out to serve the shard)
     bool layouts_done = false;
     if (n_local > 0) {
         if (refs_on_device) {
@@ -585,14 +499,16 @@ int index_create_impl(knn_index **out, int device, int k, long long n_local, con
                 return fail(KNN_ENOMEM, "knn_index_create: hipMalloc(refs)", hipGetErrorString(e));
             }
             DeviceStreams ds;
-            if (want_layouts && !grid_planned && !want_cells && g_opt_ingest != 1 && streams_get(device, &ds) == hipSuccess) {
+            // (an ingest without its two streams: copy, then build)
+            const IngestForm ingest = plan.ingest != IngestForm::CopyThenBuild && streams_get(device, &ds) == hipSuccess
+                                          ? plan.ingest : IngestForm::CopyThenBuild;
+            if (ingest == IngestForm::LayoutsUnderCopy) {
                 // ingest: rows and filter layouts in one pass over PCIe (knn_filter_build_from_host)
                 e = hipStreamSynchronize(s);   // work the caller queued ahead of this call
                 if (e == hipSuccess)
                     e = knn_filter_build_from_host(idx->filter, k, n_local, idx->owned_refs, refs, ds.copy, ds.compute);
                 layouts_done = e == hipSuccess;
-            } else if (want_layouts && !grid_planned && want_cells && g_opt_ingest != 1 && g_opt_cells_build == 0 &&
-                       streams_get(device, &ds) == hipSuccess) {
+            } else if (ingest == IngestForm::CellsUnderCopy) {
                 // ingest into a cell-sorted index: the fast build's bucket pass under the copy (round 5)
                 e = hipStreamSynchronize(s);   // work the caller queued ahead of this call
                 if (e == hipSuccess)
@@ -615,8 +531,7 @@ int index_create_impl(knn_index **out, int device, int k, long long n_local, con
             idx->refs = idx->owned_refs;
         }
     }
-    // k <= 4: the uniform-grid index (SURVEY §8 f4) — resident shards of >= 16384 rows, or whenever forced
-    if (n_local > 0 && grid_planned) {
+    if (n_local > 0 && plan.grid_planned) {
         const hipError_t e = knn_grid_build(&idx->grid, k, n_local, idx->refs, s);
         if (e != hipSuccess) {
             knn_index_destroy(idx);
@@ -642,6 +557,12 @@ int index_create_impl(knn_index **out, int device, int k, long long n_local, con
     return KNN_OK;
 }
 }  // namespace
+
+extern "C" int knn_index_create(knn_index **out, int device, int k, long long n_local, const float *refs,
+                                int refs_on_device, long long base_index, void *stream)
+{
+    return index_create_impl(out, device, k, n_local, refs, refs_on_device, base_index, stream, -1);
+}
 
 // ---------------------------------------------------------------------------------------------
 // Cell-range shards (round 4): one global grid, every rank holds a contiguous range of its cell codes.
@@ -872,6 +793,156 @@ int knn_index_query_keys_ex(knn_index *idx, int slot, int m, const float *querie
     return knn_index_query(idx, slot, m, queries_dev, keys_dev, nullptr, stream, flags);
 }
 
+}  // extern "C"
+
+// Which path answers a call: the one place it is chosen (DESIGN, "which path answers a call").  n > 0 here: the entry points
+// answer an empty shard before they ask.
+// A cell-range shard is always served by its cell-sorted layout (it has no other, and never a grid index).
+// A known oddity, kept: under option `cells` = 2 a layout in per-cell frames (centred) has no full scan to go to, so a 1-NN call
+// that reaches the filter stays on the pruned scan — but `cells_live` is then false, so the filter is reached from m >= 5 only:
+// m < 5 takes the exact scan, m >= 5 the pruned one.
+QueryRoute knn_query_route(const QueryRouteInputs &in)
+{
+    QueryRoute r;
+    CellTopkInputs t = in.t;
+    const int m = t.q.m, path = in.path;
+    const bool grid_serves = in.has_grid && (path == 0 || path == 3);
+    // (with a cell-sorted layout even one query is served faster by the pruned scan than by reading the shard)
+    const bool cells_live = t.has_cells && (t.cells_option != 2 || t.sharded);
+    const bool sized = t.n >= 65536 || in.filter_wanted;
+    if (t.K == 0) {
+        const bool use_filter = t.sharded || (in.filter_usable && (path == 2 || (path == 0 && (m >= 5 || cells_live) && sized)));
+        if (grid_serves)
+            r.way = QueryWay::Grid;
+        else if (use_filter)
+            r.way = t.has_cells && t.q.kt <= 2 && (t.sharded || t.cells_option != 2 || t.q.centred) ? QueryWay::Cells : QueryWay::Filter;
+        // the filter ways start the keys themselves when asked to (the cell-pruned one inside its first kernel)
+        r.fill_keys_first = in.init_keys && (r.way == QueryWay::Exact || r.way == QueryWay::Grid);
+        return r;
+    }
+    // Top-K: the cell-pruned top-K where knn_cells_topk_plan takes the call; else the MFMA filter for the dense
+    // layouts and for a cell-sorted fp16 layout in the shard's frame (scanned in full), under the 1-NN rule's options and sizes;
+    // exact top-K for per-cell frames (centred), 8-bit rows the plan declines, grid indexes, cell-range shards whose call does not
+    // carry KNN_QUERY_TOPK_PARTIAL (the pruned form's lists are not the shard's own top-K: include/knn_mi355x.h §2c), tiny
+    // shards, few queries, and outlier lists longer than half a query's candidate room.
+    t.ccap = r.ccap = knn_topk_ccap(t.K, m);
+    t.other_path = grid_serves || path == 1 || path == 3;
+    r.topk = knn_cells_topk_plan(t);
+    if (r.topk.use)
+        r.way = QueryWay::Cells;
+    else if (!t.sharded && in.filter_usable && !grid_serves && !(t.has_cells && (t.q.centred || t.q.rows_u8)) &&
+             t.n_outliers <= r.ccap / 2 && r.ccap >= 64 && (path == 2 || (path == 0 && m >= 5 && sized)))
+        r.way = QueryWay::Filter;
+    return r;
+}
+
+namespace {
+
+// The route's inputs for a call on idx: the index's facts and the option globals, read here and nowhere else on the query side.
+QueryRouteInputs route_inputs(const knn_index *idx, int m, int K, unsigned flags)
+{
+    QueryRouteInputs in;
+    const FilterState &f = idx->filter;
+    const CellIndex *c = f.usable ? f.cells : nullptr;
+    CellTopkInputs &t = in.t;
+    // (several_slots false: a top-K call does not feed the index's record of recent slots; one batch at a time shapes)
+    t.q = CellQueryInputs{idx->k, f.kt, c && c->centred, c && c->rows_u8, c ? c->ncells : 0u, c ? c->nitems : 0u, c ? c->cap : 0u, false,
+                          (int)g_opt_scan_blocks, (int)g_opt_scan_deal, 1, m, idx->num_cu, KNN_RECORD_CAPACITY};
+    t.has_cells = c != nullptr;
+    t.bins = c && c->bins;
+    t.K = K;
+    t.n = idx->n;
+    t.topk_cells = (int)g_opt_topk_cells;
+    t.cells_option = (int)g_opt_cells;
+    t.sharded = idx->sharded;
+    t.shard_partial = idx->sharded && (flags & KNN_QUERY_TOPK_PARTIAL) != 0u;
+    t.n_outliers = f.n_outliers;
+    in.filter_usable = f.usable;
+    in.has_grid = idx->grid != nullptr;
+    in.filter_wanted = idx->filter_wanted;
+    in.init_keys = (flags & KNN_QUERY_INIT_KEYS) != 0u;
+    in.path = (int)g_opt_path;
+    return in;
+}
+
+// The options of a filter call from the globals (several_slots: the 1-NN entry's, slots_differ).
+FilterCallOptions filter_call_options()
+{
+    FilterCallOptions opt;
+    opt.force_qt = (int)g_opt_filter_qt;
+    opt.force_rounds = (int)g_opt_filter_rounds;
+    opt.chain_policy = (int)g_opt_filter_chain;
+    opt.run_thresholds = (int)g_opt_run_thresholds;
+    opt.sample_stride = (int)g_opt_sample_stride;
+    opt.scan_blocks = (int)g_opt_scan_blocks;
+    opt.scan_deal = (int)g_opt_scan_deal;
+    opt.cells_lists = (int)g_opt_cells_lists;
+    return opt;
+}
+
+// Notes the call's workspace slot; true when the last eight calls named more than one.  Batches in flight on several
+// workspace slots = a caller after throughput: the pruned scan of a small shard then takes ONE block per CU, so that the next
+// batch's preparation kernels find registers beside it (knn_cells_query).  Derived from the last eight calls (the
+// flag used to stick for the life of the index once any call had named a slot other than 0 — a caller that went back to one
+// batch at a time kept the throughput shapes).
+bool slots_differ(knn_index *idx, int slot)
+{
+    idx->recent_slots = (idx->recent_slots << 8) | (unsigned long long)(unsigned)slot;
+    if (idx->recent_calls < 8)
+        ++idx->recent_calls;
+    bool several = false;
+    for (int i = 1; i < idx->recent_calls; ++i)
+        several = several || ((idx->recent_slots >> (8 * i)) & 0xFFull) != (unsigned long long)(unsigned)slot;
+    return several;
+}
+
+typedef std::pair<hipEvent_t, hipEvent_t> EventPair;
+
+// *out = the pair that brackets this call's dominant kernel, null when the call is not a timed one.  make_more: when the pairs
+// knn_index_timing made are used up, create one (the 1-NN entry: every N-th batch is timed however long the run); else the
+// call goes untimed (the top-K entry: its callers read the timing long before 64 calls).
+int next_event_pair(knn_index *idx, bool make_more, EventPair **out)
+{
+    *out = nullptr;
+    if (idx->timing <= 0 || idx->timing_seq++ % (unsigned long long)idx->timing != 0)
+        return KNN_OK;
+    if (idx->events_used == idx->events.size()) {
+        if (!make_more)
+            return KNN_OK;
+        EventPair fresh;
+        HIP_TRY(hipEventCreate(&fresh.first));
+        HIP_TRY(hipEventCreate(&fresh.second));
+        idx->events.push_back(fresh);
+    }
+    *out = &idx->events[idx->events_used++];
+    return KNN_OK;
+}
+
+// A per-slot scratch buffer of at least `need` bytes: one too small is freed (which waits for the device: it may be in use)
+// and allocated anew.
+int slot_buffer_grow(u64 *&buf, size_t &bytes, size_t need)
+{
+    if (bytes >= need)
+        return KNN_OK;
+    HIP_TRY(knn_dev_free(buf));
+    buf = nullptr;
+    bytes = 0;
+    HIP_TRY(knn_dev_alloc((void **)&buf, need));
+    bytes = need;
+    return KNN_OK;
+}
+
+#define KNN_TRY(call)           \
+    do {                        \
+        const int rc_ = (call); \
+        if (rc_ != KNN_OK)      \
+            return rc_;         \
+    } while (0)
+
+}  // namespace
+
+extern "C" {
+
 int knn_index_query(knn_index *idx, int slot, int m, const float *queries_dev, unsigned long long *keys_dev,
                     int *indices_dev, void *stream, unsigned flags)
 {
@@ -888,93 +959,57 @@ int knn_index_query(knn_index *idx, int slot, int m, const float *queries_dev, u
     if (idx->sharded && !init_keys)
         return fail(KNN_EINVAL, "knn_index_query: a cell-range shard WRITES its keys (pass KNN_QUERY_INIT_KEYS): they carry local "
                                 "rows until the batch's last kernel, so they cannot fold into keys other shards have written");
+    hipStream_t s = (hipStream_t)stream;
+    u64 *keys = (u64 *)keys_dev;
     if (idx->n == 0) {   // an empty shard leaves (+INF, 0)
         if (init_keys)
-            HIP_TRY(knn_keys_fill_launch((u64 *)keys_dev, m, (hipStream_t)stream));
+            HIP_TRY(knn_keys_fill_launch(keys, m, s));
         if (indices_dev)
-            HIP_TRY(knn_keys_unpack_launch((const u64 *)keys_dev, m, indices_dev, (hipStream_t)stream));
+            HIP_TRY(knn_keys_unpack_launch(keys, m, indices_dev, s));
         return KNN_OK;
     }
-    idx->stats[0] = 1;
+    EventPair *ev = nullptr;
+    KNN_TRY(next_event_pair(idx, true, &ev));
+    const QueryRoute route = knn_query_route(route_inputs(idx, m, 0, flags));
+    idx->stats[0] = (long long)route.way;
     idx->stats[1] = 0;
     idx->stats[2] = 0;
-    hipStream_t s = (hipStream_t)stream;
-    std::pair<hipEvent_t, hipEvent_t> *ev = nullptr;
-    if (idx->timing > 0 && idx->timing_seq++ % (unsigned long long)idx->timing == 0) {
-        if (idx->events_used == idx->events.size()) {
-            std::pair<hipEvent_t, hipEvent_t> fresh;
-            HIP_TRY(hipEventCreate(&fresh.first));
-            HIP_TRY(hipEventCreate(&fresh.second));
-            idx->events.push_back(fresh);
-        }
-        ev = &idx->events[idx->events_used++];
-    }
-    const long long path = g_opt_path;
-    const bool cells_live = idx->filter.cells && (g_opt_cells != 2 || idx->sharded);
-    const bool use_filter = idx->sharded ||
-                            (idx->filter.usable && !(idx->grid && (path == 0 || path == 3)) &&
-                             (path == 2 || (path == 0 && (m >= 5 || cells_live) && (idx->n >= 65536 || idx->filter_wanted))));
-    // the filter paths start the keys themselves when asked to (the cell-pruned one inside its first kernel)
-    if (init_keys && !use_filter)
-        HIP_TRY(knn_keys_fill_launch((u64 *)keys_dev, m, s));
-    if (idx->grid && (path == 0 || path == 3)) {
+    if (route.fill_keys_first)
+        HIP_TRY(knn_keys_fill_launch(keys, m, s));
+    switch (route.way) {
+    case QueryWay::Grid: {
         // k <= 4 spatial index: one wave per query walks the grid rings; the brute-force scan behind it is
         // gated on the "some query gave up" word (far-outside queries, empty regions)
-        idx->stats[0] = 3;
         idx->last_slot = slot;
         if (ev)
             HIP_TRY(hipEventRecord(ev->first, s));
         const unsigned *gate = nullptr;
-        HIP_TRY(knn_grid_query(idx->grid, slot, m, queries_dev, idx->base, (u64 *)keys_dev, &gate, s));
+        HIP_TRY(knn_grid_query(idx->grid, slot, m, queries_dev, idx->base, keys, &gate, s));
         if (ev)
             HIP_TRY(hipEventRecord(ev->second, s));
-        HIP_TRY(knn_exact_launch(idx->k, m, idx->n, idx->base, queries_dev, idx->refs, (u64 *)keys_dev, idx->num_cu, gate, s));
-        if (indices_dev)
-            HIP_TRY(knn_keys_unpack_launch((const u64 *)keys_dev, m, indices_dev, s));
-        return KNN_OK;
+        HIP_TRY(knn_exact_launch(idx->k, m, idx->n, idx->base, queries_dev, idx->refs, keys, idx->num_cu, gate, s));
+        break;
     }
-    // (with a cell-sorted layout even one query is served faster by the pruned scan than by reading the shard)
-    if (use_filter) {
-        // the event pair brackets the MFMA filter kernel alone (the dominant kernel)
-        idx->stats[0] = 2;
-        FilterCallOptions opt;
-        opt.force_qt = (int)g_opt_filter_qt;
-        opt.force_rounds = (int)g_opt_filter_rounds;
-        opt.chain_policy = (int)g_opt_filter_chain;
-        opt.run_thresholds = (int)g_opt_run_thresholds;
-        opt.sample_stride = (int)g_opt_sample_stride;
-        opt.cells_policy = idx->sharded ? 0 : (int)g_opt_cells;   // (a cell-range shard has no other layout)
-        // batches in flight on several workspace slots = a caller after throughput: the pruned scan of a small shard then
-        // takes ONE block per CU, so that the next batch's preparation kernels find registers beside it (knn_cells_query).
-        // Derived from the last eight calls (the flag used to stick for the life of the index once any call
-        // had named a slot other than 0 — a caller that went back to one batch at a time kept the throughput shapes).
-        idx->recent_slots = (idx->recent_slots << 8) | (unsigned long long)(unsigned)slot;
-        if (idx->recent_calls < 8)
-            ++idx->recent_calls;
-        {
-            bool several = false;
-            for (int i = 1; i < idx->recent_calls; ++i)
-                several = several || ((idx->recent_slots >> (8 * i)) & 0xFFull) != (unsigned long long)(unsigned)slot;
-            opt.several_slots = several;
-        }
-        opt.scan_blocks = (int)g_opt_scan_blocks;
-        opt.scan_deal = (int)g_opt_scan_deal;
-        opt.cells_lists = (int)g_opt_cells_lists;
+    case QueryWay::Filter:
+    case QueryWay::Cells: {
+        // the event pair brackets the MFMA filter kernel alone (the dominant kernel); the indices come from the path's own launches
+        FilterCallOptions opt = filter_call_options();
+        opt.several_slots = slots_differ(idx, slot);
         idx->last_slot = slot;
-        HIP_TRY(knn_filter_query(idx->filter, opt, slot, m, queries_dev, idx->refs, idx->base, (u64 *)keys_dev,
+        HIP_TRY(knn_filter_query(idx->filter, opt, route.way == QueryWay::Cells, slot, m, queries_dev, idx->refs, idx->base, keys,
                                  idx->num_cu, s, ev ? ev->first : nullptr, ev ? ev->second : nullptr, init_keys, indices_dev));
-        if (idx->filter.ws[slot].last_used_cells)
-            idx->stats[0] = 4;
         return KNN_OK;
     }
-    if (ev)
-        HIP_TRY(hipEventRecord(ev->first, s));
-    HIP_TRY(knn_exact_launch(idx->k, m, idx->n, idx->base, queries_dev, idx->refs, (u64 *)keys_dev,
-                             idx->num_cu, nullptr, s));
-    if (ev)
-        HIP_TRY(hipEventRecord(ev->second, s));
+    case QueryWay::Exact:
+        if (ev)
+            HIP_TRY(hipEventRecord(ev->first, s));
+        HIP_TRY(knn_exact_launch(idx->k, m, idx->n, idx->base, queries_dev, idx->refs, keys, idx->num_cu, nullptr, s));
+        if (ev)
+            HIP_TRY(hipEventRecord(ev->second, s));
+        break;
+    }
     if (indices_dev)
-        HIP_TRY(knn_keys_unpack_launch((const u64 *)keys_dev, m, indices_dev, s));
+        HIP_TRY(knn_keys_unpack_launch(keys, m, indices_dev, s));
     return KNN_OK;
 }
 
@@ -990,6 +1025,7 @@ int knn_index_query_topk(knn_index *idx, int slot, int m, int K, const float *qu
         return fail(KNN_EHIP, "knn_index_query_topk: hipSetDevice failed");
     const int init = (flags & KNN_QUERY_INIT_KEYS) != 0u;
     hipStream_t s = (hipStream_t)stream;
+    u64 *keys = (u64 *)keys_dev;
     idx->stats[0] = 1;
     idx->stats[1] = 0;
     idx->stats[2] = 0;
@@ -997,110 +1033,60 @@ int knn_index_query_topk(knn_index *idx, int slot, int m, int K, const float *qu
     const int mk = m * K;
     if (idx->n == 0) {   // an empty shard adds nothing
         if (init)
-            HIP_TRY(knn_keys_fill_launch((u64 *)keys_dev, mk, s));
-    } else {
-        // Which path: the cell-pruned top-K where knn_cells_topk_plan takes the call (below); else the MFMA filter for
-        // the dense layouts and for a cell-sorted fp16 layout in the shard's frame (scanned in full), under the 1-NN rule's options
-        // and sizes; exact top-K for per-cell frames (centred), 8-bit rows the plan declines, grid
-        // indexes, cell-range shards whose call does not carry KNN_QUERY_TOPK_PARTIAL (the pruned form's lists are not the
-        // shard's own top-K: include/knn_mi355x.h §2c), tiny shards, few queries, and outlier lists longer than half a query's
-        // candidate room.
-        const long long path = g_opt_path;
-        const unsigned ccap = (unsigned)std::min<long long>(4096 + 128 * (long long)K, ((long long)32 << 20) / m);
-        const bool use_filter = !idx->sharded && idx->filter.usable && !(idx->grid && (path == 0 || path == 3)) &&
-                                !(idx->filter.cells && (idx->filter.cells->centred || idx->filter.cells->rows_u8)) &&
-                                idx->filter.n_outliers <= ccap / 2 &&
-                                ccap >= 64 &&
-                                (path == 2 || (path == 0 && m >= 5 && (idx->n >= 65536 || idx->filter_wanted)));
-        // Top-K on the cell-pruned scan (knn_cells_topk_plan decides; option `topk_cells`): layouts in the shard's frame, in passes
-        // of KNN_CELL_BATCH queries.
-        CellTopkInputs ti;
-        if (idx->filter.usable && idx->filter.cells) {
-            const CellIndex &c = *idx->filter.cells;
-            // (several_slots false: a top-K call does not feed the index's record of recent slots; one batch at a time shapes)
-            ti.q = CellQueryInputs{idx->filter.k, idx->filter.kt, c.centred, c.rows_u8, c.ncells, c.nitems, c.cap, false,
-                                   (int)g_opt_scan_blocks, (int)g_opt_scan_deal, 1, m, idx->num_cu, KNN_RECORD_CAPACITY};
-            ti.has_cells = true;
-            ti.bins = c.bins;
-        } else {
-            ti.q.m = m;
-        }
-        ti.K = K;
-        ti.n = idx->n;
-        ti.topk_cells = (int)g_opt_topk_cells;
-        ti.cells_option = (int)g_opt_cells;
-        ti.sharded = idx->sharded;
-        ti.shard_partial = idx->sharded && (flags & KNN_QUERY_TOPK_PARTIAL) != 0u;
-        ti.other_path = (idx->grid && (path == 0 || path == 3)) || path == 1 || path == 3;
-        ti.n_outliers = idx->filter.n_outliers;
-        const CellTopkPlan tp = knn_cells_topk_plan(ti);
-        // (the gated exact top-K of a pass sizes its lists by the pass's queries)
-        size_t need = knn_topk_part_bytes(m, K, idx->n, idx->num_cu);
-        if (tp.use) {
-            need = std::max(need, knn_topk_part_bytes(tp.pass_m, K, idx->n, idx->num_cu));
-            if (m % KNN_CELL_BATCH)
-                need = std::max(need, knn_topk_part_bytes(m % KNN_CELL_BATCH, K, idx->n, idx->num_cu));
-        }
-        if (idx->topk_bytes[slot] < need) {
-            HIP_TRY(knn_dev_free(idx->topk_part[slot]));   // (waits for the device: the old buffer may be in use)
-            idx->topk_part[slot] = nullptr;
-            idx->topk_bytes[slot] = 0;
-            HIP_TRY(knn_dev_alloc((void **)&idx->topk_part[slot], need));
-            idx->topk_bytes[slot] = need;
-        }
-        std::pair<hipEvent_t, hipEvent_t> *ev = nullptr;
-        if (idx->timing > 0 && idx->timing_seq++ % (unsigned long long)idx->timing == 0 && idx->events_used < idx->events.size())
-            ev = &idx->events[idx->events_used++];
-        if (tp.use) {
-            const size_t cbytes = (size_t)m * tp.ccap * sizeof(u64) + (size_t)m * sizeof(unsigned);
-            if (idx->topk_cand_bytes[slot] < cbytes) {
-                HIP_TRY(knn_dev_free(idx->topk_cand[slot]));
-                idx->topk_cand[slot] = nullptr;
-                idx->topk_cand_bytes[slot] = 0;
-                HIP_TRY(knn_dev_alloc((void **)&idx->topk_cand[slot], cbytes));
-                idx->topk_cand_bytes[slot] = cbytes;
-            }
-            idx->stats[0] = 4;
-            u64 *cand = idx->topk_cand[slot];
-            unsigned *ccount = (unsigned *)(cand + (size_t)m * tp.ccap);
-            HIP_TRY(knn_filter_query_topk_cells(idx->filter, tp, slot, m, K, queries_dev, idx->refs, idx->base, (u64 *)keys_dev,
-                                                init != 0, cand, ccount, idx->topk_part[slot], idx->topk_bytes[slot], idx->num_cu, s,
-                                                ev ? ev->first : nullptr, ev ? ev->second : nullptr));
-        } else if (use_filter) {
-            const size_t cbytes = (size_t)m * ccap * sizeof(u64) + (size_t)m * sizeof(unsigned);
-            if (idx->topk_cand_bytes[slot] < cbytes) {
-                HIP_TRY(knn_dev_free(idx->topk_cand[slot]));
-                idx->topk_cand[slot] = nullptr;
-                idx->topk_cand_bytes[slot] = 0;
-                HIP_TRY(knn_dev_alloc((void **)&idx->topk_cand[slot], cbytes));
-                idx->topk_cand_bytes[slot] = cbytes;
-            }
-            idx->stats[0] = 2;
-            FilterCallOptions opt;
-            opt.force_qt = (int)g_opt_filter_qt;
-            opt.force_rounds = (int)g_opt_filter_rounds;
-            opt.chain_policy = (int)g_opt_filter_chain;
-            opt.run_thresholds = 2;   // running thresholds are a 1-NN argument; the non-running sample stride with them
-            opt.sample_stride = 0;
-            opt.topk = K;
-            u64 *cand = idx->topk_cand[slot];
-            unsigned *ccount = (unsigned *)(cand + (size_t)m * ccap);
-            HIP_TRY(knn_filter_query_topk(idx->filter, opt, slot, m, queries_dev, idx->refs, idx->base, (u64 *)keys_dev, init != 0,
-                                          cand, ccount, ccap, idx->topk_part[slot], idx->topk_bytes[slot], idx->num_cu, s,
-                                          ev ? ev->first : nullptr, ev ? ev->second : nullptr));
-        } else {
-            // a cell-range shard's keys carry its rows' global numbers (gids); an index-range shard's base + row
-            const unsigned *gids = idx->sharded && idx->filter.cells ? idx->filter.cells->gids : nullptr;
-            if (ev)
-                HIP_TRY(hipEventRecord(ev->first, s));
-            HIP_TRY(knn_exact_topk_launch(idx->k, m, K, idx->n, idx->base, gids, queries_dev, idx->refs, (u64 *)keys_dev, init,
-                                          idx->topk_part[slot], idx->topk_bytes[slot], idx->num_cu, s));
-            if (ev)
-                HIP_TRY(hipEventRecord(ev->second, s));
-        }
+            HIP_TRY(knn_keys_fill_launch(keys, mk, s));
+        if (indices_dev)
+            HIP_TRY(knn_keys_unpack_launch(keys, mk, indices_dev, s));
+        return KNN_OK;
+    }
+    const QueryRoute route = knn_query_route(route_inputs(idx, m, K, flags));
+    const CellTopkPlan &tp = route.topk;
+    idx->stats[0] = (long long)route.way;
+    // the exact top-K scan's per-slice lists (the gated exact top-K of a pruned pass sizes its lists by the pass's queries)
+    size_t need = knn_topk_part_bytes(m, K, idx->n, idx->num_cu);
+    if (tp.use) {
+        need = std::max(need, knn_topk_part_bytes(tp.pass_m, K, idx->n, idx->num_cu));
+        if (m % KNN_CELL_BATCH)
+            need = std::max(need, knn_topk_part_bytes(m % KNN_CELL_BATCH, K, idx->n, idx->num_cu));
+    }
+    u64 *&part = idx->topk_part[slot];
+    size_t &part_bytes = idx->topk_bytes[slot];
+    KNN_TRY(slot_buffer_grow(part, part_bytes, need));
+    EventPair *ev = nullptr;
+    KNN_TRY(next_event_pair(idx, false, &ev));
+    hipEvent_t ev0 = ev ? ev->first : nullptr, ev1 = ev ? ev->second : nullptr;
+    // the filter ways' candidate lists [m][ccap] and counts [m]
+    u64 *&cand = idx->topk_cand[slot];
+    if (route.way != QueryWay::Exact)
+        KNN_TRY(slot_buffer_grow(cand, idx->topk_cand_bytes[slot], (size_t)m * route.ccap * sizeof(u64) + (size_t)m * sizeof(unsigned)));
+    unsigned *ccount = route.way != QueryWay::Exact ? (unsigned *)(cand + (size_t)m * route.ccap) : nullptr;
+    switch (route.way) {
+    case QueryWay::Cells:
+        // layouts in the shard's frame, in passes of KNN_CELL_BATCH queries (option `topk_cells`)
+        HIP_TRY(knn_filter_query_topk_cells(idx->filter, tp, slot, m, K, queries_dev, idx->refs, idx->base, keys, init != 0, cand, ccount,
+                                            part, part_bytes, idx->num_cu, s, ev0, ev1));
+        break;
+    case QueryWay::Filter: {
+        FilterCallOptions opt = filter_call_options();
+        opt.run_thresholds = 2;   // running thresholds are a 1-NN argument; the non-running sample stride with them
+        opt.sample_stride = 0;
+        opt.topk = K;
+        HIP_TRY(knn_filter_query_topk(idx->filter, opt, slot, m, queries_dev, idx->refs, idx->base, keys, init != 0, cand, ccount,
+                                      route.ccap, part, part_bytes, idx->num_cu, s, ev0, ev1));
+        break;
+    }
+    default: {   // (QueryWay::Exact: a top-K call is never routed to the grid index)
+        // a cell-range shard's keys carry its rows' global numbers (gids); an index-range shard's base + row
+        const unsigned *gids = idx->sharded && idx->filter.cells ? idx->filter.cells->gids : nullptr;
+        if (ev)
+            HIP_TRY(hipEventRecord(ev0, s));
+        HIP_TRY(knn_exact_topk_launch(idx->k, m, K, idx->n, idx->base, gids, queries_dev, idx->refs, keys, init, part, part_bytes,
+                                      idx->num_cu, s));
+        if (ev)
+            HIP_TRY(hipEventRecord(ev1, s));
+    }
     }
     if (indices_dev)
-        HIP_TRY(knn_keys_unpack_launch((const u64 *)keys_dev, mk, indices_dev, s));
+        HIP_TRY(knn_keys_unpack_launch(keys, mk, indices_dev, s));
     return KNN_OK;
 }
 
@@ -1273,10 +1259,12 @@ int knn_debug_cells_query_plan(const long long in[14], long long out[28])
     return KNN_OK;
 }
 
-int knn_debug_cells_topk_plan(const long long in[20], long long out[25])
+}  // extern "C"
+
+namespace {
+// in[0 .. 20) of knn_debug_cells_topk_plan and of knn_debug_query_route
+CellTopkInputs topk_inputs_of(const long long in[20])
 {
-    if (!in || !out || in[0] < 1 || in[0] > 4096 || in[2] < 1 || in[2] > INT_MAX || in[17] < 1 || in[3] < 0)
-        return fail(KNN_EINVAL, "knn_debug_cells_topk_plan: bad arguments");
     CellTopkInputs ti;
     ti.q.k = (int)in[0];
     ti.q.kt = knn_kt_of(ti.q.k);
@@ -1301,6 +1289,18 @@ int knn_debug_cells_topk_plan(const long long in[20], long long out[25])
     ti.q.rec_cap = (unsigned)in[18];
     ti.cells_option = (int)in[19];
     ti.q.cells_lists = 1;
+    return ti;
+}
+}  // namespace
+
+extern "C" {
+
+int knn_debug_cells_topk_plan(const long long in[20], long long out[25])
+{
+    if (!in || !out || in[0] < 1 || in[0] > 4096 || in[2] < 1 || in[2] > INT_MAX || in[17] < 1 || in[3] < 0)
+        return fail(KNN_EINVAL, "knn_debug_cells_topk_plan: bad arguments");
+    CellTopkInputs ti = topk_inputs_of(in);
+    ti.ccap = knn_topk_ccap(ti.K, ti.q.m);
     const CellTopkPlan t = knn_cells_topk_plan(ti);
     const CellQueryPlan &p = t.batch;
     const long long v[25] = {t.use, p.prep_pw, p.prep_kt, p.prep_ctr, p.match_waves, p.stage,
@@ -1342,6 +1342,37 @@ int knn_debug_filter_query_plan(const long long in[11], long long out[49])
         v[45 + i] = p.rerank.qrow_base[i];
     }
     v[40] = p.rerank.n;
+    memcpy(out, v, sizeof v);
+    return KNN_OK;
+}
+
+int knn_debug_query_route(const long long in[25], long long out[6])
+{
+    if (!in || !out || in[0] < 1 || in[0] > 4096 || in[1] < 0 || in[1] > KNN_TOPK_MAX || in[2] < 1 || in[2] > INT_MAX || in[3] < 1 ||
+        in[4] < 0 || in[4] > 2 || in[9] < 0 || in[9] > 2 || in[17] < 1 || in[19] < 0 || in[19] > 2 || in[20] < 0 || in[20] > 3 ||
+        (in[22] != 0 && in[9] != 0))   // (a cell-range shard has no grid index)
+        return fail(KNN_EINVAL, "knn_debug_query_route: bad arguments");
+    QueryRouteInputs ri;
+    ri.t = topk_inputs_of(in);
+    ri.path = (int)in[20];
+    ri.filter_usable = in[21] != 0;
+    ri.has_grid = in[22] != 0;
+    ri.filter_wanted = in[23] != 0;
+    ri.init_keys = in[24] != 0;
+    const QueryRoute r = knn_query_route(ri);
+    const long long v[6] = {(long long)r.way, r.fill_keys_first, r.ccap, r.topk.use, r.topk.passes, r.topk.pass_m};
+    memcpy(out, v, sizeof v);
+    return KNN_OK;
+}
+
+int knn_debug_index_build_plan(const long long in[9], long long out[6])
+{
+    if (!in || !out || in[0] < 1 || in[0] > INT_MAX || in[1] < 0 || in[3] < -1 || in[3] > 2 || in[4] < -1 || in[4] > 1 || in[5] < 0 ||
+        in[5] > 3 || in[6] < 0 || in[6] > 2 || in[7] < 0 || in[7] > 1 || in[8] < 0 || in[8] > 2)
+        return fail(KNN_EINVAL, "knn_debug_index_build_plan: bad arguments");
+    const IndexBuildPlan p = knn_index_build_plan({(int)in[0], in[1], in[2] != 0, (int)in[3], (int)in[4], (int)in[5], (int)in[6],
+                                                   (int)in[7], (int)in[8]});
+    const long long v[6] = {p.filter_wanted, p.want_cells, p.build_filter, p.grid_planned, p.want_layouts, (long long)p.ingest};
     memcpy(out, v, sizeof v);
     return KNN_OK;
 }
@@ -1602,7 +1633,16 @@ struct ShardPlan {
     double seconds = 0.0;    // the chosen way
 };
 
-ShardPlan plan_shard(int k, int m, long long rows)
+// The options the cost model reads, filled by its callers.
+struct ShardOptions {
+    long long path = 0, cells = 0, ingest = 0, cells_build = 0, stream = 0;
+};
+ShardOptions shard_options()
+{
+    return {g_opt_path, g_opt_cells, g_opt_ingest, g_opt_cells_build, g_opt_stream};
+}
+
+ShardPlan plan_shard(int k, int m, long long rows, const ShardOptions &o)
 {
     ShardPlan p;
     const double pairs = (double)m * (double)rows;
@@ -1612,8 +1652,8 @@ ShardPlan plan_shard(int k, int m, long long rows)
     const int kt = knn_kt_of(k);   // 0: no fp16 layouts for this k (k > 4096)
     const double t_filter = kt == 0 ? 1e30 : 1.0e-3 + 2.5 * 4.0 * k * (double)rows / 4e12 + 3.4e-14 * kt * pairs + 1e-4;
     const double t_filter_under_copy = 6e-4 + 3.4e-14 * kt * pairs + 1e-4;   // host rows: layouts built under the copy
-    p.want_filter = g_opt_path == 2 ||
-                    (g_opt_path == 0 && m >= 5 && kt != 0 && (g_opt_ingest == 1 ? t_filter : t_filter_under_copy) < t_exact);
+    p.want_filter = o.path == 2 ||
+                    (o.path == 0 && m >= 5 && kt != 0 && (o.ingest == 1 ? t_filter : t_filter_under_copy) < t_exact);
     // The pruned scan for a one-shot call (round 5: the cell sort's bucket pass runs under the copy, knn_filter_build_cells_from_host):
     // ~1.0 ms per 2^24 rows stay behind the last byte (cell prefix + placement) where the plain layouts leave 0.07, and a
     // batch of 1024 queries then costs 0.04 ms + 6.5 ps per row instead of 3.4e-14 s per pair — it repays the sort from about
@@ -1621,8 +1661,8 @@ ShardPlan plan_shard(int k, int m, long long rows)
     // resident indexes on the cells (k <= 16, >= 2^19 / 2^20 rows), and only with the default build options.
     // (same fixed costs as the plain layouts' line above, so that the two differ by what differs)
     const double t_cells_query = 6e-4 + 1.0e-3 * (double)rows / 16777216.0 + ceil(m / 1024.0) * (4e-5 + 6.5e-12 * (double)rows) + 1e-4;
-    if (p.want_filter && g_opt_path == 0 && g_opt_cells == 0 && g_opt_ingest == 0 && g_opt_cells_build == 0 && k <= 16 &&
-        rows >= (k <= 12 ? (1ll << 19) : (1ll << 20)) && (double)rows * 96.0 <= 2147483648.0 && t_cells_query < t_filter_under_copy)
+    if (p.want_filter && o.path == 0 && o.cells == 0 && o.ingest == 0 && o.cells_build == 0 && k <= 16 &&
+        rows >= knn_cells_size_rule(k) && (double)rows * 96.0 <= 2147483648.0 && t_cells_query < t_filter_under_copy)
         p.want_filter = 2;
     // Third option: the exact scan chunk by chunk under the copy: costs the longer of the two plus one chunk's scan.  The
     // staged alternatives pay the copy in one piece; the filter layouts are then built under the copy's tail
@@ -1635,12 +1675,12 @@ ShardPlan plan_shard(int k, int m, long long rows)
     p.nchunks = (int)nchunks;
     p.t_streamed = std::max(t_h2d, t_exact) + t_exact / nchunks + kCopyCall * nchunks + 1e-4;
     const double t_filter_query = 6e-4 + 3.4e-14 * kt * pairs + 1e-4;   // layouts under the copy + query
-    const double t_query = p.want_filter == 2 ? t_cells_query : p.want_filter ? (g_opt_ingest == 1 ? t_filter : t_filter_query) : t_exact;
+    const double t_query = p.want_filter == 2 ? t_cells_query : p.want_filter ? (o.ingest == 1 ? t_filter : t_filter_query) : t_exact;
     const double t_grid = k <= 4 ? 1.5e-4 + 1.5e-10 * (double)rows + 2e-8 * m : 1e30;
-    p.want_grid = k <= 4 && (g_opt_path == 3 || (g_opt_path == 0 && rows >= 65536 && t_grid < t_query));
+    p.want_grid = k <= 4 && (o.path == 3 || (o.path == 0 && rows >= 65536 && t_grid < t_query));
     p.t_staged = t_h2d + kCopyCall + (p.want_grid ? t_grid : t_query);
-    p.streamed = g_opt_path != 2 && !p.want_grid && g_opt_stream != 1 && bytes >= (double)(64u << 20) &&
-                 (g_opt_stream == 2 || p.t_streamed < p.t_staged);
+    p.streamed = o.path != 2 && !p.want_grid && o.stream != 1 && bytes >= (double)(64u << 20) &&
+                 (o.stream == 2 || p.t_streamed < p.t_staged);
     p.seconds = p.streamed ? p.t_streamed : p.t_staged;
     return p;
 }
@@ -1651,7 +1691,7 @@ ShardPlan plan_shard(int k, int m, long long rows)
 // PCIe link and copies its own range) plus what fanning out costs — a host thread, an index create / query / destroy and
 // a share of the key exchange per GPU — is lowest; of the counts within 10 % of the best the smallest is taken.  The fan-out constants (0.2 ms + 0.02 ms per GPU)
 // are estimates: no multi-GPU node was available to measure them.
-int shard_policy(int k, int m, long long n, int ndev)
+int shard_policy(int k, int m, long long n, int ndev, const ShardOptions &o)
 {
     long long cap = std::min<long long>(ndev, n);                           // core.cu:867-868
     if (cap <= 1 || n <= std::min<long long>(1ll << 18, (long long)m << 10))   // core.cu:871-872
@@ -1665,7 +1705,7 @@ int shard_policy(int k, int m, long long n, int ndev)
     double t_min = 1e30;
     for (size_t i = 0; i < cand.size(); ++i) {
         const int g = cand[i];
-        t[i] = plan_shard(k, m, (n + g - 1) / g).seconds + (g > 1 ? 2e-4 + 2e-5 * g : 0.0);
+        t[i] = plan_shard(k, m, (n + g - 1) / g, o).seconds + (g > 1 ? 2e-4 + 2e-5 * g : 0.0);
         t_min = std::min(t_min, t[i]);
     }
     size_t pick = 0;
@@ -1683,7 +1723,7 @@ extern "C" int knn_debug_plan_shard(int k, int m, long long rows, long long out[
 {
     if (k < 1 || m < 1 || rows < 1 || !out)
         return fail(KNN_EINVAL, "knn_debug_plan_shard: bad arguments");
-    const ShardPlan p = plan_shard(k, m, rows);
+    const ShardPlan p = plan_shard(k, m, rows, shard_options());
     out[0] = p.want_filter;
     out[1] = p.streamed ? 1 : 0;
     out[2] = p.want_grid ? 1 : 0;
@@ -1695,7 +1735,7 @@ extern "C" int knn_debug_shard_policy(int k, int m, long long n, int ndev)
 {
     if (k < 1 || m < 1 || n < 1 || ndev < 1)
         return fail(KNN_EINVAL, "knn_debug_shard_policy: bad arguments");
-    return shard_policy(k, m, n, ndev);
+    return shard_policy(k, m, n, ndev, shard_options());
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1716,7 +1756,7 @@ extern "C" void cudaCallback(int k, int m, int n, float *searchPoints, float *re
     }
     // core.cu:865-872: how many GPUs take part (never more shards than points; one GPU for the small sets of the TA
     // harness; beyond that by the cost model: shard_policy).  Option `shards` forces a count (test hook).
-    long long shards = g_opt_shards > 0 ? (long long)g_opt_shards : (long long)shard_policy(k, m, n, ndev);
+    long long shards = g_opt_shards > 0 ? (long long)g_opt_shards : (long long)shard_policy(k, m, n, ndev, shard_options());
     if (shards > n)
         shards = n;
     g_last_shards = shards;
@@ -1789,7 +1829,7 @@ extern "C" void cudaCallback(int k, int m, int n, float *searchPoints, float *re
         }
         knn_index *idx = nullptr;
         // which of the three ways serves this shard: plan_shard (cost model)
-        const ShardPlan plan = plan_shard(k, m, hi - lo);
+        const ShardPlan plan = plan_shard(k, m, hi - lo, shard_options());
         const int want_filter = plan.want_filter;
         const bool want_grid = plan.want_grid, streamed = plan.streamed;
         const double t_streamed = plan.t_streamed, t_staged = plan.t_staged;

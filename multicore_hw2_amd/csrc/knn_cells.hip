@@ -3526,9 +3526,10 @@ CellTopkPlan knn_cells_topk_plan(const CellTopkInputs &in)
     const CellQueryInputs &qi = in.q;
     if (in.K < 1 || in.K > KNN_TOPK_MAX || qi.m < 1)
         return t;
-    // candidate room: the filter top-K's rule.  The K-th seed bound admits about K times the 1-NN bound's rows, nearly each its own
-    // record, but the re-rank's distance gate (knn_topk_gate) lets about one key of a record's sixteen through
-    t.ccap = (unsigned)std::min<long long>(4096 + 128 * (long long)in.K, ((long long)32 << 20) / qi.m);
+    // candidate room: the filter top-K's rule (knn_topk_ccap, from the caller).  The K-th seed bound admits about K times the 1-NN
+    // bound's rows, nearly each its own record, but the re-rank's distance gate (knn_topk_gate) lets about one key of a record's
+    // sixteen through
+    t.ccap = in.ccap;
     const bool layout = in.has_cells && (!in.sharded || in.shard_partial) && !in.other_path && !qi.centred && (!qi.rows_u8 || in.bins) && qi.kt >= 1 &&
                         qi.kt <= 2 && qi.k <= 32;
     const bool call = qi.m >= 5 && t.ccap >= 64u && in.n_outliers <= t.ccap / 2u;

@@ -141,7 +141,6 @@ struct FilterWorkspace {
     float *dup = nullptr;                  // device [m_cap]: largest scaled squared distance a candidate can have
     float *lo_tab = nullptr, *hi_tab = nullptr;  // device [m_cap][2^sa], [2^(bits-sa)][m_cap]
     int cell_m_cap = 0;
-    bool last_used_cells = false;
 };
 
 // 16-wide K steps of the fp16 layouts for dimension k: 1, 2, 4, 8 (register / LDS-tiled scans), 16 and 32 (LDS-tiled scan with
@@ -257,7 +256,7 @@ struct CellIndex {
 #define KNN_NIF_MAX_K 30   // 16 < k <= 30: the cell-sorted fragments carry the rows' norms in K-slots 30, 31 (knn_cells.hip: cell_tile_step_nif)
 
 // The options of one filter query, filled from the global options by knn_index_query / knn_index_query_topk and passed by value:
-// nothing of a call stays in the index.
+// nothing of a call stays in the index.  (Whether the call is pruned is not an option here: knn_query_route decides it.)
 struct FilterCallOptions {
     // the dense scan (knn_filter_query_plan)
     int force_qt = 0;          // "filter_qt": query tiles per wave of the register scan at k <= 16 (0 = pick by m)
@@ -271,7 +270,6 @@ struct FilterCallOptions {
                                // two it scores; 0 = library policy
     int topk = 0;              // K of a top-K call (the threshold comes from the K-th smallest per-block sample minimum); 0 = 1-NN
     // the cell-pruned scan (knn_cells_query_plan)
-    int cells_policy = 0;      // 0 use the cells when present, 2 full scan
     bool several_slots = false;// the index's recent calls named more than one workspace slot: batches are in flight side by side
     int scan_blocks = 0;       // blocks per CU: 0 auto (one for small shards when several_slots, else two), 1, 2
     int scan_deal = 0;         // 0 auto (block counter unless several_slots), 1 fixed deal, 2 items from a block counter
@@ -386,6 +384,7 @@ struct CellTopkInputs {
     bool shard_partial = false;    // ... whose call carries KNN_QUERY_TOPK_PARTIAL (the only top-K a cell-range shard prunes)
     bool other_path = false;       // the grid index or a forced exact path answers this index
     unsigned n_outliers = 0;
+    unsigned ccap = 0;             // knn_topk_ccap(K, q.m), from the caller (knn_query_route)
 };
 struct CellTopkPlan {
     bool use = false;              // false: the call stays on the path it had (filter top-K or exact top-K)
@@ -401,7 +400,58 @@ static inline long long knn_cells_size_rule(int k)
     return k <= 12 ? (1ll << 19) : k <= 16 ? (1ll << 20) : k <= 21 ? (1ll << 22) : k <= 23 ? (1ll << 23)
          : k <= KNN_CELLS_AUTO_MAX_K ? (1ll << 24) : (1ll << 62);
 }
+// candidate keys a query of a top-K call of m queries has room for (the filter top-K's and the cell-pruned top-K's lists)
+static inline unsigned knn_topk_ccap(int K, int m)
+{
+    return (unsigned)std::min<long long>(4096 + 128 * (long long)K, ((long long)32 << 20) / m);
+}
 CellTopkPlan knn_cells_topk_plan(const CellTopkInputs &in);
+
+// ---- which path answers a call, and what an index is built with (knn_api.cpp; host arithmetic only) ---------------------------
+// knn_query_route is the ONE place a call's path is chosen (DESIGN, "which path answers a call"): nothing is allocated or
+// launched, no global is read — the options are inputs.  tests/test_route_logic.py restates the rules on the CPU through
+// knn_debug_query_route.
+enum class QueryWay { Exact = 1, Filter = 2, Grid = 3, Cells = 4 };   // the values are knn_index_last_stats' [0]
+struct QueryRouteInputs {
+    // the index, the call and the options `cells` (t.cells_option), `topk_cells` and the scan's, as the cell-pruned top-K's plan
+    // takes them: t.q.m = the call's queries, t.K = K (0: a 1-NN call), t.n > 0 (an empty shard is answered before any route),
+    // t.has_cells = filter layouts exist AND are cell-sorted.  t.other_path and t.ccap are the route's to fill.
+    // Invariant: a cell-range shard (t.sharded) has no grid index — knn_index_create_sharded never builds one.
+    CellTopkInputs t;
+    bool filter_usable = false;    // the index has filter layouts
+    bool has_grid = false;         // ... a grid index (k <= 4)
+    bool filter_wanted = false;    // its creator asked for the layouts below the size the library builds them from
+    bool init_keys = false;        // KNN_QUERY_INIT_KEYS
+    int path = 0;                  // option `path`
+};
+struct QueryRoute {
+    QueryWay way = QueryWay::Exact;
+    bool fill_keys_first = false;  // 1-NN: the keys are set to (+INF, 0) by a launch of their own ahead of the path's
+    unsigned ccap = 0;             // top-K: candidate keys per query (the filter's lists and the pruned scan's)
+    CellTopkPlan topk;             // top-K: knn_cells_topk_plan's answer (use == (way == Cells))
+};
+QueryRoute knn_query_route(const QueryRouteInputs &in);
+
+// What index_create_impl builds, decided up front.  What only the run can tell stays there: no streams for an ingest, a grid
+// build that rules the grid out, a cell sort under the copy that reports unusable, no memory for the layouts.
+enum class IngestForm { CopyThenBuild = 0, LayoutsUnderCopy = 1, CellsUnderCopy = 2 };
+struct IndexBuildInputs {
+    int k = 0;
+    long long n_local = 0;
+    bool refs_on_device = false;
+    int build_filter = -1;         // 1 the MFMA filter layouts, 2 cell-sorted, 0 none, -1 library policy
+    int build_grid = -1;           // (k <= 4) 1 the grid index, 0 none, -1 library policy
+    int path = 0, cells = 0, ingest = 0, cells_build = 0;   // the options
+};
+struct IndexBuildPlan {
+    bool filter_wanted = false;    // knn_index::filter_wanted
+    bool want_cells = false;       // the layouts are cell-sorted
+    int build_filter = 0;          // resolved: never -1
+    bool grid_planned = false;     // the grid index is tried first (a shard it serves gets no MFMA layouts)
+    bool want_layouts = false;
+    IngestForm ingest = IngestForm::CopyThenBuild;   // host rows: how they reach the device
+};
+IndexBuildPlan knn_index_build_plan(const IndexBuildInputs &in);
 // Every choice and size one batch of the dense filter query launches with (knn_filter_query_plan in knn_filter.hip; host
 // arithmetic only).  The scan comes in three forms: pieces of the batch on the register scan (knn_filter_kernel, k <= 32, and
 // k <= 128 below 16 query tiles), the LDS-tiled scan (knn_filter_tiled_kernel, k <= 512) and the chunked-K scan
@@ -523,7 +573,8 @@ void knn_filter_free(FilterState &st);
 // Asynchronous on `stream`: sample pre-pass + MFMA filter + exact re-rank + gated exact fallback.
 // init_keys: the keys are written from scratch ((+INF, 0) first) instead of min-folded into what they hold.
 // out_idx (nullable): the int32 indices of the batch as well (no separate unpack launch on the cell-pruned path).
-hipError_t knn_filter_query(FilterState &st, FilterCallOptions opt, int slot, int m, const float *q_dev, const float *r_dev,
+// pruned: the cell-pruned scan answers the call (knn_query_route's QueryWay::Cells), else the full scan.
+hipError_t knn_filter_query(FilterState &st, FilterCallOptions opt, bool pruned, int slot, int m, const float *q_dev, const float *r_dev,
                             long long base, u64 *keys_dev, int num_cu, hipStream_t stream,
                             hipEvent_t ev_begin, hipEvent_t ev_end, bool init_keys = false, int *out_idx = nullptr);
 // opt.topk = K (1 .. KNN_TOPK_MAX).

@@ -2587,7 +2587,7 @@ static hipError_t filter_scan(FilterState &st, FilterWorkspace &w, const FilterQ
     return hipSuccess;
 }
 
-hipError_t knn_filter_query(FilterState &st, FilterCallOptions opt, int slot, int m, const float *q, const float *r, long long base,
+hipError_t knn_filter_query(FilterState &st, FilterCallOptions opt, bool pruned, int slot, int m, const float *q, const float *r, long long base,
                             u64 *keys, int num_cu, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end, bool init_keys,
                             int *out_idx)
 {
@@ -2598,11 +2598,12 @@ hipError_t knn_filter_query(FilterState &st, FilterCallOptions opt, int slot, in
     // raises its own FALLBACK flag on the device and is answered by the gated exact scan; the next batch is back on
     // the pruned path.  (Round 2 sent the whole index to full scans for 256 calls after such a batch, on a pinned
     // host word read here whenever the host happened to get to it.)
-    const bool cells = st.cells && (opt.cells_policy != 2 || st.cells->centred) && st.kt <= 2;   // (per-cell frames: the full scan cannot read them)
-    w.last_used_cells = cells;
+    // (pruned or not is the caller's: knn_query_route.  Per-cell frames: the full scan cannot read them.)
+    if (pruned ? (!st.cells || st.kt > 2) : (st.cells && st.cells->centred))
+        return hipErrorInvalidValue;
     w.ev_begin = ev_begin;
     w.ev_end = ev_end;
-    if (cells) {
+    if (pruned) {
         const int cell_batch = KNN_CELL_BATCH;   // (the scan's LDS holds a pass's B operands: 36 KiB, 68 KiB for 16 < k <= 32)
         FTRY(ensure_workspace(st, w, std::min(m, cell_batch)));
         for (int q0 = 0; q0 < m; q0 += cell_batch) {
@@ -2640,7 +2641,6 @@ hipError_t knn_filter_query_topk(FilterState &st, FilterCallOptions opt, int slo
     if (st.cells && st.cells->centred)
         return hipErrorInvalidValue;   // per-cell frames: the full scan cannot read them (the caller sends these to exact top-K)
     FilterWorkspace &w = st.ws[slot];
-    w.last_used_cells = false;
     w.ev_begin = ev_begin;
     w.ev_end = ev_end;
     const int K = opt.topk;
@@ -2669,7 +2669,6 @@ hipError_t knn_filter_query_topk_cells(FilterState &st, const CellTopkPlan &tp, 
     if (!st.cells || !tp.use)
         return hipErrorInvalidValue;
     FilterWorkspace &w = st.ws[slot];
-    w.last_used_cells = true;
     w.ev_begin = ev_begin;
     w.ev_end = ev_end;
     const int cell_batch = KNN_CELL_BATCH;

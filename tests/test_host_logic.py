@@ -96,6 +96,48 @@ def test_option_hooks_reject_unknown_names():
         assert pkg.get_option(name) == -1
 
 
+# every option of include/knn_mi355x.h's list: (lowest, highest legal value, legal values when they are not the whole range)
+OPTION_TABLE = {
+    "path": (0, 3, None), "shards": (0, 1024, None), "filter_qt": (0, 32, (0, 2, 8, 16, 32)), "stream": (0, 2, None),
+    "ingest": (0, 1, None), "rccl": (0, 2, None), "cells": (0, 2, None), "scan_blocks": (0, 2, None), "run_thresholds": (0, 2, None),
+    "sample_stride": (0, 1024, None), "cells_centre": (0, 2, None), "cells_rows": (0, 2, None), "cells_u8_frame": (0, 2, None),
+    "topk_cells": (0, 2, None), "cells_lists": (0, 2, None), "scan_deal": (0, 2, None), "cells_build": (0, 2, None),
+    "filter_rounds": (0, 64, None), "filter_chain": (0, 2, None),
+}
+READ_ONLY_COUNTERS = ("cells_centred_builds", "cells_u8_builds", "cells_u8_bin_builds", "rccl_reductions", "rccl_comm_sets",
+                      "last_shards", "last_cells", "rccl_version")
+
+
+def test_option_table_keeps_every_name_its_bounds_and_its_message():
+    _built_lib()
+    import multicore_hw2_amd as pkg
+    with open(os.path.join(ROOT, "include", "knn_mi355x.h")) as f:
+        header = f.read()
+    listed = set(re.findall(r'^ \*   "([a-z0-9_]+)"', header, flags=re.M))
+    assert listed == set(OPTION_TABLE), listed ^ set(OPTION_TABLE)
+    for name, (lo, hi, legal) in OPTION_TABLE.items():
+        try:
+            for v in (legal or (lo, hi)):
+                pkg.set_option(name, v)
+                assert pkg.get_option(name) == v, (name, v)
+            holes = [v for v in range(lo, hi + 1) if v not in legal] if legal else []
+            for v in [lo - 1, hi + 1] + holes:
+                with pytest.raises(pkg.KnnError, match=f"knn_set_option: {name} must be"):
+                    pkg.set_option(name, v)
+                assert pkg.get_option(name) == (legal or (lo, hi))[-1], (name, v)      # a refused value changes nothing
+        finally:
+            pkg.set_option(name, 0)
+        assert pkg.get_option(name) == 0
+    for name in READ_ONLY_COUNTERS:
+        assert pkg.get_option(name) >= 0, name
+        with pytest.raises(pkg.KnnError, match="unknown option"):                      # nobody sets a counter
+            pkg.set_option(name, 0)
+    with pytest.raises(pkg.KnnError, match="unknown option: no_such_option"):
+        pkg.set_option("no_such_option", 0)
+    assert pkg.get_option("no_such_option") == -1
+    assert pkg.lib().knn_set_option(None, 0) != 0 and pkg.lib().knn_get_option(None) == -1
+
+
 def test_product_does_not_link_or_reference_the_oracle():
     path = _built_lib()
     out = subprocess.run(["ldd", path], capture_output=True, text=True).stdout
