@@ -446,6 +446,13 @@ int knn_debug_query_route(const long long in[25], long long out[6]);
  * 1 if the grid index is tried first, 1 if the layouts are built (unless the grid index serves the shard), how host rows reach
  * the device: 0 copy then build, 1 layouts under the copy, 2 cell sort under the copy}. */
 int knn_debug_index_build_plan(const long long in[9], long long out[6]);
+/* Test hook (host arithmetic only, no GPU needed): how an index created from host rows splits the copy of its shard.
+ * in = {k, n_local (0 .. 2^40), the granule in rows (a multiple of 32 up to 2^20: 1024 for the plain layouts under the copy,
+ * 4096 for the cell sort under the copy)};
+ * out = {rows of the first copy: everything but the last 64 MiB, rounded down to the granule, when the shard is larger than
+ * 128 MiB — or n_local, one copy, for smaller shards and where that would leave less than one granule; the second copy is
+ * the rest}. */
+int knn_debug_ingest_head_rows(const long long in[3], long long out[1]);
 
 /* Test hook for the filter's error bound: raw MFMA filter scores S[m][n_local] (row-major,
  * device) for a query batch, the fp32 squared norms M[m] of the fp16 query rows (device), and

@@ -28,7 +28,7 @@ EXPORTED_SYMBOLS = [
     "knn_index_query_host", "knn_set_option", "knn_get_option", "knn_index_last_stats",
     "knn_synth_fill_device", "knn_index_timing", "knn_index_timing_read",
     "knn_debug_filter_scores", "knn_index_query_keys_slot", "knn_trim", "knn_keys_allreduce_min",
-    "knn_index_query_keys_ex", "knn_index_debug_counters", "knn_debug_scan_plan", "knn_debug_scan_plan_ex", "knn_debug_cells_query_plan", "knn_debug_cells_topk_plan", "knn_debug_seed_kth", "knn_debug_topk_gate", "knn_debug_filter_query_plan", "knn_debug_query_route", "knn_debug_index_build_plan", "knn_debug_shard_policy", "knn_debug_plan_shard", "knn_debug_u8_row", "knn_debug_u8_bin_row", "knn_debug_u8_bin_threshold", "knn_index_query",
+    "knn_index_query_keys_ex", "knn_index_debug_counters", "knn_debug_scan_plan", "knn_debug_scan_plan_ex", "knn_debug_cells_query_plan", "knn_debug_cells_topk_plan", "knn_debug_seed_kth", "knn_debug_topk_gate", "knn_debug_filter_query_plan", "knn_debug_query_route", "knn_debug_index_build_plan", "knn_debug_ingest_head_rows", "knn_debug_shard_policy", "knn_debug_plan_shard", "knn_debug_u8_row", "knn_debug_u8_bin_row", "knn_debug_u8_bin_threshold", "knn_index_query",
     "knn_geom_create", "knn_geom_destroy", "knn_geom_info", "knn_geom_assign", "knn_index_create_sharded",
     "knn_index_seed_export", "knn_index_seed_attach", "knn_geom_first_cell",
     "knn_index_query_topk", "knn_keys_topk_merge", "knn_index_query_topk_host",
@@ -258,6 +258,18 @@ def debug_index_build_plan(**inputs):
     f.argtypes = [ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)]
     _check(f(vin, out))
     return dict(zip(INDEX_BUILD_PLAN, list(out)))
+
+
+def debug_ingest_head_rows(k, n, granule):
+    """knn_debug_ingest_head_rows: rows of the first of the (at most two) copies an index created from host rows ships its
+    shard in (granule 1024: plain layouts under the copy, 4096: cell sort under the copy); the second copy is the rest.  Host
+    arithmetic; works without a GPU."""
+    vin = (ctypes.c_longlong * 3)(int(k), int(n), int(granule))
+    out = (ctypes.c_longlong * 1)()
+    f = lib().knn_debug_ingest_head_rows
+    f.argtypes = [ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)]
+    _check(f(vin, out))
+    return int(out[0])
 
 
 def debug_plan_shard(k, m, rows):

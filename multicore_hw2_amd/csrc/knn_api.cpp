@@ -1377,6 +1377,15 @@ int knn_debug_index_build_plan(const long long in[9], long long out[6])
     return KNN_OK;
 }
 
+int knn_debug_ingest_head_rows(const long long in[3], long long out[1])
+{
+    if (!in || !out || in[0] < 1 || in[0] > INT_MAX || in[1] < 0 || in[1] > (1ll << 40) || in[2] < 32 || in[2] > (1ll << 20) ||
+        in[2] % 32 != 0)
+        return fail(KNN_EINVAL, "knn_debug_ingest_head_rows: bad arguments");
+    out[0] = knn_ingest_head_rows((int)in[0], in[1], in[2]);
+    return KNN_OK;
+}
+
 int knn_keys_to_indices(int device, const unsigned long long *keys_dev, int m, int *out_dev,
                         void *stream)
 {

@@ -569,6 +569,9 @@ hipError_t knn_filter_build_from_host(FilterState &st, int k, long long n, float
 // device; st.usable says whether the layouts stand (else the caller builds from the resident rows).  Synchronous.
 hipError_t knn_filter_build_cells_from_host(FilterState &st, int k, long long n, float *r_dev, const float *r_host,
                                             hipStream_t copy, hipStream_t compute);
+// Rows of the first of the (at most two) copies both ingests ship a shard of n rows x k floats in, a multiple of `granule` rows
+// or n (one piece).  Host arithmetic only; knn_debug_ingest_head_rows.
+long long knn_ingest_head_rows(int k, long long n, long long granule);
 void knn_filter_free(FilterState &st);
 // Asynchronous on `stream`: sample pre-pass + MFMA filter + exact re-rank + gated exact fallback.
 // init_keys: the keys are written from scratch ((+INF, 0) first) instead of min-folded into what they hold.

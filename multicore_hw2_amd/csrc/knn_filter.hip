@@ -1557,9 +1557,32 @@ static double robust_box(const std::vector<float> &samp, long long samples, int 
     return h;
 }
 
-// Centre (kp entries, 0 beyond k) and power-of-two scale of a sample's robust box — the frame of the builds that start from a
-// sample of 4096 rows (or fewer): false when the sample holds non-finite values or its box is degenerate.
-static bool box_from_sample(const float *sample, long long samples, int k, int kp, std::vector<float> &center, float *sigma_out)
+// A layout's frame: the centre (16 kt floats, 0 beyond k) and the power-of-two scale its fp16 fragments are made in.  Three
+// makers: frame_from_sample (a strided sample, host or device rows), frame_of_geom (a cell-range shard's global grid) and
+// frame_from_range (the full-range statistics of resident rows).
+struct Frame {
+    std::vector<float> center;
+    float sigma = 1.0f;
+};
+
+// The scale of a box whose widest half-width is h: false when the box is degenerate (or not finite).
+static bool frame_scale(double h, float *sigma)
+{
+    if (!(h <= 1e15) || (h != 0.0 && h < 1e-15))
+        return false;
+    *sigma = 1.0f;
+    if (h > 0.0) {
+        int ex;
+        (void)frexp(h, &ex);  // h = f * 2^ex, f in [0.5, 1)  ->  h * 2^-ex < 1
+        *sigma = (float)ldexp(1.0, -ex);
+    }
+    return true;
+}
+
+// The frame of the builds that start from a sample of 4096 rows (or fewer), kp = 16 kt: the robust box of every fourth row
+// inside the sample's range widened by 1 / 32.  False — no layouts from here — when the sample holds non-finite values or its
+// box is degenerate.
+static bool frame_from_sample(Frame &f, const float *sample, long long samples, int k, int kp)
 {
     const long long sub = samples >= 4096 ? 4 : 1, nsub = samples / sub;
     std::vector<float> samp((size_t)nsub * k), dlo((size_t)k, INFINITY), dhi((size_t)k, -INFINITY);
@@ -1580,17 +1603,17 @@ static bool box_from_sample(const float *sample, long long samples, int k, int k
         dlo[(size_t)d] -= pad;
         dhi[(size_t)d] += pad;
     }
-    const double h = robust_box(samp, nsub, k, kp, dlo, dhi, center);
-    if (!(h <= 1e15) || (h != 0.0 && h < 1e-15))
-        return false;
-    float sigma = 1.0f;
-    if (h > 0.0) {
-        int ex;
-        (void)frexp(h, &ex);
-        sigma = (float)ldexp(1.0, -ex);
-    }
-    *sigma_out = sigma;
-    return true;
+    return frame_scale(robust_box(samp, nsub, k, kp, dlo, dhi, f.center), &f.sigma);
+}
+
+// The frame of a cell-range shard: the global grid's (identical on every rank: the ranks' fp16 fragments — the seed layer —
+// must live in one frame).
+static Frame frame_of_geom(const ShardGeom &g)
+{
+    Frame f;
+    f.center.assign(g.center, g.center + 16);
+    f.sigma = g.sigma;
+    return f;
 }
 
 bool knn_geom_from_sample(ShardGeom &g, int k, long long n_global, int nranks, const float *sample, long long samples,
@@ -1598,15 +1621,14 @@ bool knn_geom_from_sample(ShardGeom &g, int k, long long n_global, int nranks, c
 {
     if (!sample || k < 1 || k > 16)
         return false;
-    std::vector<float> center;
-    float sigma = 1.0f;
-    if (!box_from_sample(sample, samples, k, 16, center, &sigma))
+    Frame f;
+    if (!frame_from_sample(f, sample, samples, k, 16))
         return false;
     if (!knn_geom_cells(g, k, n_global, nranks, sample, samples, seed_tiles))
         return false;
     for (int d = 0; d < 16; ++d)
-        g.center[d] = d < k ? center[(size_t)d] : 0.0f;
-    g.sigma = sigma;
+        g.center[d] = d < k ? f.center[(size_t)d] : 0.0f;
+    g.sigma = f.sigma;
     return true;
 }
 
@@ -1662,152 +1684,14 @@ static std::vector<float> cut_sample(const std::vector<float> &samp, int k)
     return cuts;
 }
 
-// st's shape and the buffers of its layouts: `ntiles` tiles (cells: + the split norms of a cell-sorted layout), the outlier
-// list, the fragment kernels' 4 statistics words (*dout, zeroed) and the centre (16 kt floats, uploaded from `center`, which
-// must outlive the next synchronisation).  Enqueues on `s`.
-static hipError_t layouts_alloc(FilterState &st, int k, long long n, long long ntiles, const float *center, float sigma, bool cells,
-                                unsigned **dout, hipStream_t s)
+// The frame from the FULL RANGE of resident rows — the classic build's: 1. the per-dimension range (one pass over the shard
+// and a round trip to the host), 1b. the robust box (robust_box) clipped to [min, max], from a strided sample of up to 1024
+// rows.  `samp` / `*samples` hand that sample back, finite rows only (the cell plan reads it).  *ok false: no layouts from
+// here — the shard is mostly non-finite rows, a dimension has no finite value, the box is degenerate.
+static hipError_t frame_from_range(Frame &f, bool *ok, std::vector<float> &samp, long long *samples, int k, long long n, const float *r,
+                                   hipStream_t s, BuildTrace &tr)
 {
-    st.k = k;
-    st.kt = knn_kt_of(k);
-    st.n = n;
-    st.ntiles = ntiles;
-    st.sigma = sigma;
-    FTRY(KNN_DEV_ALLOC((void **)&st.center, (size_t)16 * st.kt * sizeof(float)));
-    FTRY(KNN_DEV_ALLOC(&st.ref_frags, (size_t)ntiles * st.kt * 64 * 16));
-    FTRY(KNN_DEV_ALLOC((void **)&st.ref_norms, (size_t)ntiles * 32 * sizeof(float)));
-    if (cells)
-        FTRY(KNN_DEV_ALLOC((void **)&st.ref_norms2, (size_t)ntiles * 32 * sizeof(unsigned)));
-    FTRY(KNN_DEV_ALLOC((void **)&st.outliers, (size_t)outlier_cap(n) * sizeof(unsigned)));
-    FTRY(KNN_DEV_ALLOC((void **)dout, 4 * sizeof(unsigned)));
-    FTRY(hipMemsetAsync(*dout, 0, 4 * sizeof(unsigned), s));
-    return hipMemcpyAsync(st.center, center, (size_t)16 * st.kt * sizeof(float), hipMemcpyHostToDevice, s);
-}
-
-static const char *staged(const CellStaging &stg)
-{
-    return !stg.c ? "cell codes (not kept)" : stg.c->build_res ? "buckets + cell prefix (enqueued)" : "cell codes + counts";
-}
-
-// The end of every cell-sorted build, once the layout is staged (st.cells = stg.c) and its buffers are allocated (layouts_alloc,
-// whose error is `e`): the rows placed, the statistics — and the fast build's build_res — read behind ONE synchronisation (of
-// `s`, and of an ingest's `copy` stream), the build scratch released, then the layout accepted or rejected: fp16 range
-// trouble, too many rows outside the box (no layouts from this frame), or *overflow — a bucket of the fast build outgrew its
-// fixed room.  An accepted layout gets per-cell frames or 8-bit rows where knn_cells_maybe_recentre wants them (samp: the
-// build's host sample, null when there is none).  Leaves st reset unless the layout stands.
-static hipError_t cells_finish(FilterState &st, CellStaging &stg, hipError_t e, const float *r, unsigned *dout, const float *samp,
-                               long long samples, hipStream_t s, BuildTrace &tr, bool *overflow, hipStream_t copy = nullptr)
-{
-    *overflow = false;
-    const unsigned ocap = outlier_cap(st.n);
-    const bool fast = stg.c->build_res != nullptr;
-    unsigned hout[4] = {0, 0, 0, 0}, hres[4] = {0, 0, 0, 0};
-    if (e == hipSuccess)
-        e = knn_cells_place_rows(st, r, stg.code, stg.fill, dout, ocap, s);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(hout, dout, sizeof hout, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && fast)
-        e = hipMemcpyAsync(hres, stg.c->build_res, sizeof hres, hipMemcpyDeviceToHost, s);
-    const hipError_t e1 = copy ? hipStreamSynchronize(copy) : hipSuccess, e2 = hipStreamSynchronize(s);
-    if (e == hipSuccess)
-        e = e1 != hipSuccess ? e1 : e2;
-    tr.lap(fast ? "build kernels + placement + sync" : "placement + sync");
-    if (e == hipSuccess && fast) {
-        // the fast build's verdict: tiles, items, the largest cell — or a bucket that outgrew its fixed room
-        st.ntiles = hres[0];
-        st.cells->nitems = hres[1];
-        st.cells->max_cell_rows = hres[2];
-        *overflow = hres[3] != 0u || hres[1] == 0u;
-        if (tr.on)
-            fprintf(stderr, "[%s] fast build: %u tiles (room for %lld), %u items, largest cell %u rows, overflow %u, outside the box %u\n",
-                    tr.tag, hres[0], stg.ntiles, hres[1], hres[2], hres[3], hout[3]);
-    }
-    stg.release();
-    (void)KNN_DEV_FREE(dout);
-    if (e != hipSuccess || *overflow || hout[2] != 0u || hout[3] > ocap) {
-        knn_filter_free(st);
-        return e;
-    }
-    st.n_outliers = hout[3];
-    memcpy(&st.bmax, &hout[0], 4);
-    memcpy(&st.nmax, &hout[1], 4);
-    st.usable = true;
-    e = knn_cells_maybe_recentre(st, r, samp, samples, s);   // clustered data (or on request): each cell in its own frame
-    tr.lap("per-cell frames (if any)");
-    if (e != hipSuccess)
-        knn_filter_free(st);
-    return e;
-}
-
-hipError_t knn_filter_build(FilterState &st, int k, long long n, const float *r, hipStream_t s, bool want_cells, int cells_build,
-                            const ShardGeom *geom, int rank, unsigned *bad_rows_out)
-{
-    st = FilterState();
-    const int kt = knn_kt_of(k);
-    if (n <= 0 || kt == 0 || (geom && (kt != 1 || geom->k != k)))
-        return hipSuccess;
-    BuildTrace tr{"knn build"};
-    if (geom || (want_cells && kt <= 2 && n >= (1ll << 17))) {
-        // The cell-sorted layout from a GIVEN frame (centre, scale) and either a shard geometry's cuts or cuts taken from a sample.
-        // Cell-range shard of a global grid: centre, scale and cuts are the grid's (identical on every rank: the ranks' fp16
-        // fragments — the seed layer — must live in one frame), the layout is this rank's cells of it.
-        // Round 4: else the frame from a strided SAMPLE of the rows (4096 of them: range widened by 1 / 32, median / MAD box
-        // inside it — what knn_filter_build_from_host does for host rows), not from a pass over the whole shard: the
-        // full-range statistics kernel read 1 GiB for a box that any representative sample gives, and its round trip to the
-        // host stood in front of everything else (0.25 of the build's 3.4 ms at C3).  ANY box is correct: rows outside it go
-        // to the exact list; if the sample was not representative (more than n / 32 rows outside, or values that are not
-        // finite in the sample) the classic build below starts over with full-range statistics.
-        std::vector<float> samp, cuts, center;
-        float sigma = 1.0f;
-        bool box_ok = true;
-        std::future<bool> frame;   // (every way out of this block waits for its thread)
-        if (geom) {
-            center.assign(geom->center, geom->center + 16);
-            sigma = geom->sigma;
-        } else {
-            const long long samples = 4096;
-            FTRY(device_sample(r, n, k, samples, s, samp));
-            tr.lap("sample rows + copy");
-            // (the frame is host arithmetic on the sample — 0.25 ms — and only the placement needs it: it is worked out on a
-            // thread of its own while the cell codes and buckets are made on the GPU)
-            frame = std::async(std::launch::async, [&] { return box_from_sample(samp.data(), samples, k, 16 * kt, center, &sigma); });
-            cuts = cut_sample(samp, k);
-        }
-        const long long ncuts = (long long)cuts.size() / k;
-        CellIndex plan;
-        if (knn_cells_plan(plan, k, n, cuts.data(), ncuts, geom, rank)) {
-            CellBuild how = knn_cells_first_build(plan, k, n, cells_build, CellRows::Sample);
-            for (;;) {
-                CellStaging stg;
-                FTRY(knn_cells_stage(stg, plan, how, CellRows::Sample, k, n, r, s, bad_rows_out));
-                tr.lap(staged(stg));
-                if (!(st.cells = stg.c))
-                    break;
-                if (frame.valid())
-                    box_ok = frame.get();
-                if (!box_ok) {   // (the sample is not finite, or its box degenerate)
-                    stg.release();
-                    knn_filter_free(st);
-                    break;
-                }
-                unsigned *dout = nullptr;
-                const hipError_t e = layouts_alloc(st, k, n, stg.ntiles, center.data(), sigma, true, &dout, s);
-                tr.lap("allocations");
-                bool overflow = false;
-                FTRY(cells_finish(st, stg, e, r, dout, ncuts > 0 ? cuts.data() : nullptr, ncuts, s, tr, &overflow));
-                if (st.usable || !overflow)
-                    break;
-                tr.lap("fast build: bucket overflow");   // (rows the cuts do not spread evenly)
-                how = knn_cells_next_build(how, CellRows::Sample);
-            }
-        }
-        if (st.usable || geom)
-            return hipSuccess;
-        st = FilterState();   // (declined, or the sampled frame left too many rows out: the classic build decides)
-    }
-    const int kp = 16 * kt;
-    const long long ntiles = (n + 31) / 32;
-
+    *ok = false;
     // 1. per-dimension range
     std::vector<unsigned> hstats((size_t)2 * k + 1);
     for (int d = 0; d < k; ++d) {
@@ -1843,98 +1727,335 @@ hipError_t knn_filter_build(FilterState &st, int k, long long n, const float *r,
         if (hstats[(size_t)d] == 0xFFFFFFFFu || hstats[(size_t)k + d] == 0u)
             return hipSuccess;  // a dimension without a single finite value
 
-    // 1b. robust box (robust_box) clipped to [min, max], from a strided sample of up to 1024 rows
+    // 1b. robust box
     const long long want = k <= 16 ? 1024 : (16384 / k > 256 ? 16384 / k : 256);  // host work ~0.2 ms at any k
-    const long long samples = n < want ? n : want;
-    std::vector<float> samp;
-    FTRY(device_sample(r, n, k, samples, s, samp));
+    const long long taken = n < want ? n : want;
+    FTRY(device_sample(r, n, k, taken, s, samp));
     tr.lap("sample rows + copy");
-    long long samples_used = samples;
+    *samples = taken;
     if (has_nonfinite) {   // the statistics below want finite rows only
-        samples_used = 0;
-        for (long long i = 0; i < samples; ++i) {
+        *samples = 0;
+        for (long long i = 0; i < taken; ++i) {
             bool fin = true;
             for (int d = 0; d < k; ++d)
                 fin = fin && fabsf(samp[(size_t)i * k + d]) < INFINITY;
             if (fin) {
-                if (samples_used != i)
-                    memcpy(&samp[(size_t)samples_used * k], &samp[(size_t)i * k], (size_t)k * sizeof(float));
-                ++samples_used;
+                if (*samples != i)
+                    memcpy(&samp[(size_t)*samples * k], &samp[(size_t)i * k], (size_t)k * sizeof(float));
+                ++*samples;
             }
         }
-        if (samples_used < 1)
+        if (*samples < 1)
             return hipSuccess;
     }
-    std::vector<float> center, dlo((size_t)k), dhi((size_t)k);
+    std::vector<float> dlo((size_t)k), dhi((size_t)k);
     for (int d = 0; d < k; ++d) {
         dlo[(size_t)d] = ord2f_host(hstats[(size_t)d]);
         dhi[(size_t)d] = ord2f_host(hstats[(size_t)k + d]);
     }
-    const double h = robust_box(samp, samples_used, k, kp, dlo, dhi, center);
+    const double h = robust_box(samp, *samples, k, 16 * knn_kt_of(k), dlo, dhi, f.center);
     tr.lap("median / MAD box (host)");
-    if (!(h <= 1e15) || (h != 0.0 && h < 1e-15))
-        return hipSuccess;
-    float sigma = 1.0f;
-    if (h > 0.0) {
-        int ex;
-        (void)frexp(h, &ex);  // h = f * 2^ex, f in [0.5, 1)  ->  h * 2^-ex < 1
-        sigma = (float)ldexp(1.0, -ex);
-    }
+    *ok = frame_scale(h, &f.sigma);
+    return hipSuccess;
+}
 
-    // 1c. cell-sorted layout (k <= 16, resident indexes): the counted build, or the one-pass placement
-    if (want_cells && kt == 1) {
-        CellIndex plan;
-        CellStaging stg;
-        if (knn_cells_plan(plan, k, n, samp.data(), samples_used, nullptr, 0))
-            FTRY(knn_cells_stage(stg, plan, knn_cells_first_build(plan, k, n, cells_build, CellRows::FullRange), CellRows::FullRange, k, n,
-                                 r, s));
-        tr.lap(staged(stg));
-        if ((st.cells = stg.c)) {
-            unsigned *dout = nullptr;
-            e = layouts_alloc(st, k, n, stg.ntiles, center.data(), sigma, true, &dout, s);
-            tr.lap("allocations");
-            bool overflow = false;
-            return cells_finish(st, stg, e, r, dout, samp.data(), samples_used, s, tr, &overflow);
-        }
-    }
+// st's shape and the buffers of its layouts — the only place they are allocated: `ntiles` tiles (cells: + the split norms of a
+// cell-sorted layout), the outlier list, the fragment kernels' 4 statistics words (*dout, zeroed) and the centre (16 kt floats,
+// uploaded from `f`, which must outlive the next synchronisation).  Enqueues on `s`.
+static hipError_t layouts_alloc(FilterState &st, int k, long long n, long long ntiles, const Frame &f, bool cells, unsigned **dout,
+                                hipStream_t s)
+{
+    st.k = k;
+    st.kt = knn_kt_of(k);
+    st.n = n;
+    st.ntiles = ntiles;
+    st.sigma = f.sigma;
+    FTRY(KNN_DEV_ALLOC((void **)&st.center, (size_t)16 * st.kt * sizeof(float)));
+    FTRY(KNN_DEV_ALLOC(&st.ref_frags, (size_t)ntiles * st.kt * 64 * 16));
+    FTRY(KNN_DEV_ALLOC((void **)&st.ref_norms, (size_t)ntiles * 32 * sizeof(float)));
+    if (cells)
+        FTRY(KNN_DEV_ALLOC((void **)&st.ref_norms2, (size_t)ntiles * 32 * sizeof(unsigned)));
+    FTRY(KNN_DEV_ALLOC((void **)&st.outliers, (size_t)outlier_cap(n) * sizeof(unsigned)));
+    FTRY(KNN_DEV_ALLOC((void **)dout, 4 * sizeof(unsigned)));
+    FTRY(hipMemsetAsync(*dout, 0, 4 * sizeof(unsigned), s));
+    return hipMemcpyAsync(st.center, f.center.data(), (size_t)16 * st.kt * sizeof(float), hipMemcpyHostToDevice, s);
+}
 
-    // 2. fragments + norms
-    unsigned *dout = nullptr;
-    const unsigned ocap = outlier_cap(n);
-    e = layouts_alloc(st, k, n, ntiles, center.data(), sigma, false, &dout, s);
-    unsigned hout[4] = {0, 0, 0, 0};
-    tr.lap("allocations");
-    if (e == hipSuccess) {
-        const long long rows_padded = ntiles * 32;
-        if (k == 16 && ((uintptr_t)r & 15u) == 0)
-            hipLaunchKernelGGL(knn_frag16_kernel, dim3((unsigned)((rows_padded + 255) / 256)), dim3(256), 0, s,
-                               (const f4v *)r, n, rows_padded, st.center, sigma, (h8 *)st.ref_frags,
-                               st.ref_norms, dout, st.outliers, ocap);
-        else
-            hipLaunchKernelGGL(knn_frag_kernel, dim3((unsigned)((rows_padded + 255) / 256)), dim3(256), 0, s, r,
-                               n, rows_padded, k, kt, st.center, sigma, 1.0f, INFINITY, (h8 *)st.ref_frags,
-                               st.ref_norms, dout, 0, nullptr, nullptr, st.outliers, ocap);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(hout, dout, sizeof hout, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(s);  // also keeps `center` alive until the copy is done
-    tr.lap("fragment kernel + sync");
-    (void)KNN_DEV_FREE(dout);
-    if (e != hipSuccess) {
-        knn_filter_free(st);
-        return e;
-    }
-    if (hout[2] != 0u || hout[3] > ocap) {  // fp16 range trouble, or too many rows outside the box
-        knn_filter_free(st);
-        return hipSuccess;
-    }
+// The plain layout's fill: fragments + norms of rows row0 .. row0 + rows of the resident rows (row0 a multiple of 32;
+// rows_padded: up to the end of the last tile where the rows end the shard, else = rows), outliers listed by their row in the
+// shard, statistics into dout.  The whole shard at once (row0 = 0), or one landed chunk of an ingest.
+static hipError_t plain_fill(const FilterState &st, const float *r_dev, long long row0, long long rows, long long rows_padded,
+                             unsigned *dout, hipStream_t s)
+{
+    const float *x = r_dev + (size_t)row0 * st.k;
+    h8 *frag = (h8 *)st.ref_frags + (size_t)(row0 / 32) * st.kt * 64;
+    float *norms = st.ref_norms + row0;
+    const unsigned blocks = (unsigned)((rows_padded + 255) / 256), ocap = outlier_cap(st.n);
+    if (st.k == 16 && ((uintptr_t)x & 15u) == 0)
+        hipLaunchKernelGGL(knn_frag16_kernel, dim3(blocks), dim3(256), 0, s, (const f4v *)x, rows, rows_padded, st.center, st.sigma,
+                           frag, norms, dout, st.outliers, ocap, (unsigned)row0);
+    else
+        hipLaunchKernelGGL(knn_frag_kernel, dim3(blocks), dim3(256), 0, s, x, rows, rows_padded, st.k, st.kt, st.center, st.sigma,
+                           1.0f, INFINITY, frag, norms, dout, 0, nullptr, nullptr, st.outliers, ocap, (unsigned)row0);
+    return hipGetLastError();
+}
+
+// The verdict on a finished layout, from the fragment kernels' four statistics words (largest |coordinate| and norm in the
+// frame, fp16 range trouble, rows outside the box): false — no layouts from this frame — on range trouble or more outliers
+// than outlier_cap; else st takes the statistics and is usable.
+static bool layout_accept(FilterState &st, const unsigned hout[4])
+{
+    if (hout[2] != 0u || hout[3] > outlier_cap(st.n))
+        return false;
     st.n_outliers = hout[3];
     memcpy(&st.bmax, &hout[0], 4);
     memcpy(&st.nmax, &hout[1], 4);
     st.usable = true;
+    return true;
+}
+
+static const char *staged(const CellStaging &stg)
+{
+    return !stg.c ? "cell codes (not kept)" : stg.c->build_res ? "buckets + cell prefix (enqueued)" : "cell codes + counts";
+}
+
+// The end of every cell-sorted build, once the layout is staged (st.cells = stg.c) and its buffers are allocated (layouts_alloc,
+// whose error is `e`): the rows placed, the statistics — and the fast build's build_res — read behind ONE synchronisation (of
+// `s`, and of an ingest's `copy` stream), the build scratch released, then the layout accepted or rejected: fp16 range
+// trouble, too many rows outside the box (layout_accept: no layouts from this frame), or *overflow — a bucket of the fast build
+// outgrew its fixed room.  An accepted layout gets per-cell frames or 8-bit rows where knn_cells_maybe_recentre wants them
+// (samp: the build's host sample, null when there is none).  Leaves st reset unless the layout stands.
+static hipError_t cells_finish(FilterState &st, CellStaging &stg, hipError_t e, const float *r, unsigned *dout, const float *samp,
+                               long long samples, hipStream_t s, BuildTrace &tr, bool *overflow, hipStream_t copy = nullptr)
+{
+    *overflow = false;
+    const bool fast = stg.c->build_res != nullptr;
+    unsigned hout[4] = {0, 0, 0, 0}, hres[4] = {0, 0, 0, 0};
+    if (e == hipSuccess)
+        e = knn_cells_place_rows(st, r, stg.code, stg.fill, dout, outlier_cap(st.n), s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(hout, dout, sizeof hout, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && fast)
+        e = hipMemcpyAsync(hres, stg.c->build_res, sizeof hres, hipMemcpyDeviceToHost, s);
+    const hipError_t e1 = copy ? hipStreamSynchronize(copy) : hipSuccess, e2 = hipStreamSynchronize(s);
+    if (e == hipSuccess)
+        e = e1 != hipSuccess ? e1 : e2;
+    tr.lap(fast ? "build kernels + placement + sync" : "placement + sync");
+    if (e == hipSuccess && fast) {
+        // the fast build's verdict: tiles, items, the largest cell — or a bucket that outgrew its fixed room
+        st.ntiles = hres[0];
+        st.cells->nitems = hres[1];
+        st.cells->max_cell_rows = hres[2];
+        *overflow = hres[3] != 0u || hres[1] == 0u;
+        if (tr.on)
+            fprintf(stderr, "[%s] fast build: %u tiles (room for %lld), %u items, largest cell %u rows, overflow %u, outside the box %u\n",
+                    tr.tag, hres[0], stg.ntiles, hres[1], hres[2], hres[3], hout[3]);
+    }
+    stg.release();
+    (void)KNN_DEV_FREE(dout);
+    if (e != hipSuccess || *overflow || !layout_accept(st, hout)) {
+        knn_filter_free(st);
+        return e;
+    }
+    e = knn_cells_maybe_recentre(st, r, samp, samples, s);   // clustered data (or on request): each cell in its own frame
+    tr.lap("per-cell frames (if any)");
+    if (e != hipSuccess)
+        knn_filter_free(st);
+    return e;
+}
+
+// What a step of knn_filter_build answers beside its hipError_t (an error leaves st reset): the layout Stands (st.usable);
+// the step Declined and st is reset — the next step decides; or the build Ends here without layouts, st reset.
+enum class BuildStep { Stands, Declined, Ends };
+
+// Step 1.  The cell-sorted layout from a GIVEN frame (centre, scale) and either a shard geometry's cuts or cuts taken from a
+// sample.  Cell-range shard of a global grid: centre, scale and cuts are the grid's (frame_of_geom), the layout is this rank's
+// cells of it.
+// Round 4: else the frame from a strided SAMPLE of the rows (4096 of them: range widened by 1 / 32, median / MAD box
+// inside it — what knn_filter_build_from_host does for host rows), not from a pass over the whole shard: the
+// full-range statistics kernel read 1 GiB for a box that any representative sample gives, and its round trip to the
+// host stood in front of everything else (0.25 of the build's 3.4 ms at C3).  ANY box is correct: rows outside it go
+// to the exact list; if the sample was not representative (more than n / 32 rows outside, or values that are not
+// finite in the sample) the step declines and the classic build starts over with full-range statistics.
+// A fast build whose bucket overflowed (rows the cuts do not spread evenly) is followed by the next build of the same frame.
+static hipError_t cells_from_given_frame(FilterState &st, BuildStep *step, int k, long long n, const float *r, hipStream_t s,
+                                         int cells_build, const ShardGeom *geom, int rank, unsigned *bad_rows_out, BuildTrace &tr)
+{
+    *step = BuildStep::Declined;
+    std::vector<float> samp, cuts;
+    Frame frame;
+    std::future<bool> framed;   // (every way out of this function waits for its thread)
+    if (geom)
+        frame = frame_of_geom(*geom);
+    else {
+        const long long samples = 4096;
+        FTRY(device_sample(r, n, k, samples, s, samp));
+        tr.lap("sample rows + copy");
+        // (the frame is host arithmetic on the sample — 0.25 ms — and only the placement needs it: it is worked out on a
+        // thread of its own while the cell codes and buckets are made on the GPU)
+        framed = std::async(std::launch::async, [&] { return frame_from_sample(frame, samp.data(), samples, k, 16 * knn_kt_of(k)); });
+        cuts = cut_sample(samp, k);
+    }
+    const long long ncuts = (long long)cuts.size() / k;
+    CellIndex plan;
+    if (!knn_cells_plan(plan, k, n, cuts.data(), ncuts, geom, rank))
+        return hipSuccess;
+    for (CellBuild how = knn_cells_first_build(plan, k, n, cells_build, CellRows::Sample);;
+         how = knn_cells_next_build(how, CellRows::Sample)) {
+        CellStaging stg;
+        FTRY(knn_cells_stage(stg, plan, how, CellRows::Sample, k, n, r, s, bad_rows_out));
+        tr.lap(staged(stg));
+        if (!(st.cells = stg.c))
+            return hipSuccess;
+        if (framed.valid() && !framed.get()) {   // (the sample is not finite, or its box degenerate)
+            stg.release();
+            knn_filter_free(st);
+            return hipSuccess;
+        }
+        unsigned *dout = nullptr;
+        const hipError_t e = layouts_alloc(st, k, n, stg.ntiles, frame, true, &dout, s);
+        tr.lap("allocations");
+        bool overflow = false;
+        FTRY(cells_finish(st, stg, e, r, dout, ncuts > 0 ? cuts.data() : nullptr, ncuts, s, tr, &overflow));
+        if (st.usable)
+            *step = BuildStep::Stands;
+        if (st.usable || !overflow)
+            return hipSuccess;
+        tr.lap("fast build: bucket overflow");   // (rows the cuts do not spread evenly)
+    }
+}
+
+// Step 3 (1c of the classic build).  The cell-sorted layout (k <= 16, resident indexes) from the full-range frame and its
+// sample: the counted build, or the one-pass placement.  Declined: the shard does not suit the cells.
+static hipError_t cells_from_full_range(FilterState &st, BuildStep *step, int k, long long n, const float *r, hipStream_t s,
+                                        int cells_build, const Frame &frame, const std::vector<float> &samp, long long samples,
+                                        BuildTrace &tr)
+{
+    *step = BuildStep::Declined;
+    CellIndex plan;
+    CellStaging stg;
+    if (knn_cells_plan(plan, k, n, samp.data(), samples, nullptr, 0))
+        FTRY(knn_cells_stage(stg, plan, knn_cells_first_build(plan, k, n, cells_build, CellRows::FullRange), CellRows::FullRange, k, n,
+                             r, s));
+    tr.lap(staged(stg));
+    if (!(st.cells = stg.c))
+        return hipSuccess;
+    unsigned *dout = nullptr;
+    const hipError_t e = layouts_alloc(st, k, n, stg.ntiles, frame, true, &dout, s);
+    tr.lap("allocations");
+    bool overflow = false;
+    FTRY(cells_finish(st, stg, e, r, dout, samp.data(), samples, s, tr, &overflow));
+    *step = st.usable ? BuildStep::Stands : BuildStep::Ends;
     return hipSuccess;
+}
+
+// Step 4 (2 of the classic build), the last.  The plain layout: fragments + norms of every row in row order, in `frame`;
+// st.usable says whether it stands (else st is reset).
+static hipError_t plain_layout(FilterState &st, int k, long long n, const float *r, hipStream_t s, const Frame &frame, BuildTrace &tr)
+{
+    const long long ntiles = (n + 31) / 32;
+    unsigned *dout = nullptr;
+    hipError_t e = layouts_alloc(st, k, n, ntiles, frame, false, &dout, s);
+    unsigned hout[4] = {0, 0, 0, 0};
+    tr.lap("allocations");
+    if (e == hipSuccess)
+        e = plain_fill(st, r, 0, n, ntiles * 32, dout, s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(hout, dout, sizeof hout, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(s);  // also keeps the frame's centre alive until the copy is done
+    tr.lap("fragment kernel + sync");
+    (void)KNN_DEV_FREE(dout);
+    if (e != hipSuccess || !layout_accept(st, hout))
+        knn_filter_free(st);
+    return e;
+}
+
+hipError_t knn_filter_build(FilterState &st, int k, long long n, const float *r, hipStream_t s, bool want_cells, int cells_build,
+                            const ShardGeom *geom, int rank, unsigned *bad_rows_out)
+{
+    st = FilterState();
+    const int kt = knn_kt_of(k);
+    if (n <= 0 || kt == 0 || (geom && (kt != 1 || geom->k != k)))
+        return hipSuccess;
+    BuildTrace tr{"knn build"};
+    BuildStep step = BuildStep::Declined;
+    // 1. cell-sorted from a geometry's frame or a sampled one (a geometry never falls through to the classic build)
+    if (geom || (want_cells && kt <= 2 && n >= (1ll << 17))) {
+        FTRY(cells_from_given_frame(st, &step, k, n, r, s, cells_build, geom, rank, bad_rows_out, tr));
+        if (step != BuildStep::Declined || geom)
+            return hipSuccess;
+    }
+    // 2. declined, or the sampled frame left too many rows out: the classic build decides, in the full-range frame
+    Frame frame;
+    std::vector<float> samp;
+    long long samples = 0;
+    bool framed = false;
+    FTRY(frame_from_range(frame, &framed, samp, &samples, k, n, r, s, tr));
+    if (!framed)
+        return hipSuccess;
+    // 3. cell-sorted from it
+    if (want_cells && kt == 1) {
+        FTRY(cells_from_full_range(st, &step, k, n, r, s, cells_build, frame, samp, samples, tr));
+        if (step != BuildStep::Declined)
+            return hipSuccess;
+    }
+    // 4. else the plain layout
+    return plain_layout(st, k, n, r, s, frame, tr);
+}
+
+// Rows of the first of an ingest's (at most) two copies, a multiple of `granule`: everything but the last 64 MiB (rounded up to
+// the granule), or n — one piece — for shards up to 128 MiB, and where that rule would leave the head less than one granule
+// (rows wider than ~32 KiB in a shard just over 128 MiB: k 12000 with n 2797), which would never advance the copy.
+long long knn_ingest_head_rows(int k, long long n, long long granule)
+{
+    const size_t row_bytes = (size_t)k * sizeof(float);
+    const long long tail_rows = ((long long)((64u << 20) / row_bytes) + granule - 1) / granule * granule;
+    const long long head_rows = (size_t)n * row_bytes > ((size_t)128u << 20) ? (n - tail_rows) / granule * granule : n;
+    return head_rows < granule ? n : head_rows;
+}
+
+// The events of an ingest's chunks, destroyed once both streams have drained (when this goes out of scope).
+struct ChunkEvents {
+    std::vector<hipEvent_t> v;
+    ~ChunkEvents()
+    {
+        for (hipEvent_t ev : v)
+            (void)hipEventDestroy(ev);
+    }
+};
+
+// Host rows -> r_dev on `copy`, in two chunks: everything but the last 64 MiB in ONE pageable copy, then the tail
+// (knn_ingest_head_rows).  A pageable hipMemcpy runs at the link rate (55 GB/s: the runtime pins the caller's pages as it goes)
+// but every call costs ~0.25 ms of pipeline fill, so sixteen 64 MiB chunks lost 4 ms against one 1 GiB copy
+// (profiles/r02_ingest_timing.txt) where the whole layout build is 0.8 ms.  With `events`, every chunk gets an event that
+// `compute` waits for, and landed(r0, r1) enqueues there what rows r0 .. r1 allow: the big chunk's work runs under the tail's
+// copy, what is left after the last byte is the tail's own.  Without: the bare copies.
+template <class Landed>
+static hipError_t copy_in_chunks(float *r_dev, const float *r_host, int k, long long n, long long granule, hipStream_t copy,
+                                 hipStream_t compute, ChunkEvents *events, BuildTrace &tr, Landed landed)
+{
+    const long long head_rows = knn_ingest_head_rows(k, n, granule);
+    hipError_t e = hipSuccess;
+    for (long long r0 = 0; r0 < n && e == hipSuccess;) {
+        const long long r1 = r0 == 0 ? head_rows : n;
+        e = hipMemcpyAsync(r_dev + (size_t)r0 * k, r_host + (size_t)r0 * k, (size_t)(r1 - r0) * k * sizeof(float), hipMemcpyHostToDevice,
+                           copy);
+        tr.lap("copy call returned");
+        hipEvent_t ev = nullptr;
+        if (events && e == hipSuccess)
+            e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+        if (ev) {
+            events->v.push_back(ev);
+            e = hipEventRecord(ev, copy);
+            if (e == hipSuccess)
+                e = hipStreamWaitEvent(compute, ev, 0);
+            if (e == hipSuccess)
+                e = landed(r0, r1);
+        }
+        r0 = r1;
+    }
+    return e;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1958,132 +2079,61 @@ hipError_t knn_filter_build_from_host(FilterState &st, int k, long long n, float
 {
     st = FilterState();
     BuildTrace tr{"knn ingest"};
-    const size_t row_bytes = (size_t)k * sizeof(float);
     const bool layouts = n > 0 && knn_kt_of(k) != 0;
-    const int kt = layouts ? knn_kt_of(k) : 1;
-    const int kp = 16 * kt;
-    const long long ntiles = (n + 31) / 32;
 
-    // 1. box from a host sample: 4096 strided rows give the range (every read is a cache + TLB miss: 16384 rows cost 3.6 ms,
-    // more than the layouts), every 4th of them — 1024 rows, as in knn_filter_build — the median / MAD (box_from_sample;
+    // 1. frame from a host sample: 4096 strided rows give the range (every read is a cache + TLB miss: 16384 rows cost 3.6 ms,
+    // more than the layouts), every 4th of them — 1024 rows, as in knn_filter_build — the median / MAD (frame_from_sample;
     // non-finite rows in the sample: leave it to the classic build)
+    Frame frame;
     bool usable = layouts;
-    std::vector<float> center;
-    float sigma = 1.0f;
     if (usable) {
         const long long samples = n < 4096 ? n : 4096;
-        usable = box_from_sample(host_sample(r_host, n, k, samples).data(), samples, k, kp, center, &sigma);
+        usable = frame_from_sample(frame, host_sample(r_host, n, k, samples).data(), samples, k, 16 * knn_kt_of(k));
     }
-
     tr.lap("host sample + box");
+
     // 2. buffers
     unsigned *dout = nullptr;
-    const unsigned ocap = outlier_cap(n);
-    hipError_t e = hipSuccess;
     if (usable) {
-        st.k = k;
-        st.kt = kt;
-        st.n = n;
-        st.ntiles = ntiles;
-        st.sigma = sigma;
-        e = KNN_DEV_ALLOC((void **)&st.center, (size_t)kp * sizeof(float));
-        if (e == hipSuccess)
-            e = KNN_DEV_ALLOC(&st.ref_frags, (size_t)ntiles * kt * 64 * 16);
-        if (e == hipSuccess)
-            e = KNN_DEV_ALLOC((void **)&st.ref_norms, (size_t)ntiles * 32 * sizeof(float));
-        if (e == hipSuccess)
-            e = KNN_DEV_ALLOC((void **)&st.outliers, (size_t)ocap * sizeof(unsigned));
-        if (e == hipSuccess)
-            e = KNN_DEV_ALLOC((void **)&dout, 4 * sizeof(unsigned));
-        if (e == hipSuccess)
-            e = hipMemsetAsync(dout, 0, 4 * sizeof(unsigned), compute);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(st.center, center.data(), (size_t)kp * sizeof(float), hipMemcpyHostToDevice, compute);
-        if (e == hipErrorOutOfMemory) {   // no room for the layouts beside the rows: rows only
-            (void)hipGetLastError();
+        const hipError_t e = layouts_alloc(st, k, n, (n + 31) / 32, frame, false, &dout, compute);
+        if (e != hipSuccess) {
             (void)KNN_DEV_FREE(dout);
             dout = nullptr;
             knn_filter_free(st);
+            if (e != hipErrorOutOfMemory)
+                return e;
+            (void)hipGetLastError();   // no room for the layouts beside the rows: rows only
             usable = false;
-            e = hipSuccess;
-        }
-        if (e != hipSuccess) {
-            (void)KNN_DEV_FREE(dout);
-            knn_filter_free(st);
-            return e;
         }
     }
-
     tr.lap("allocations");
-    // 3. Two chunks: everything but the last 64 MiB in ONE pageable copy, then the tail.  A pageable
-    // hipMemcpy runs at the link rate (55 GB/s: the runtime pins the caller's pages as it goes) but every
-    // call costs ~0.25 ms of pipeline fill, so sixteen 64 MiB chunks lost 4 ms against one 1 GiB copy
-    // (profiles/r02_ingest_timing.txt) where the whole layout build is 0.8 ms.  The big chunk's fragment
-    // kernels (0.8 ms for 960 MiB) run under the tail's copy (1.2 ms); what is left after the last byte is
-    // the tail's own fragment kernel (~0.05 ms).  Shards up to 128 MiB go over in one piece.
-    const long long tail_rows = ((long long)((64u << 20) / row_bytes) + 1023) / 1024 * 1024;
-    const long long head_rows = (size_t)n * row_bytes > ((size_t)128u << 20) ? (n - tail_rows) / 1024 * 1024 : n;
-    std::vector<hipEvent_t> events;
-    for (long long r0 = 0; r0 < n && e == hipSuccess;) {
-        const long long chunk_rows = r0 == 0 ? head_rows : n - r0;
-        const long long r1 = std::min(n, r0 + chunk_rows);
-        e = hipMemcpyAsync(r_dev + (size_t)r0 * k, r_host + (size_t)r0 * k, (size_t)(r1 - r0) * row_bytes,
-                           hipMemcpyHostToDevice, copy);
-        const long long r0_this = r0;
-        r0 = r1;
-        tr.lap("copy call returned");
-        if (!usable || e != hipSuccess)
-            continue;
-        hipEvent_t ev = nullptr;
-        e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-        if (e != hipSuccess)
-            break;
-        events.push_back(ev);
-        e = hipEventRecord(ev, copy);
-        if (e == hipSuccess)
-            e = hipStreamWaitEvent(compute, ev, 0);
-        if (e != hipSuccess)
-            break;
-        // rows c0 .. r1 (c0 is a multiple of 1024): tiles c0/32 .., the last chunk pads its last tile
-        const long long c0 = r0_this;
-        const long long rows = r1 - c0;
-        const long long rows_padded = r1 == n ? ntiles * 32 - c0 : rows;
-        const float *x = r_dev + (size_t)c0 * k;
-        h8 *frag = (h8 *)st.ref_frags + (size_t)(c0 / 32) * kt * 64;
-        float *norms = st.ref_norms + c0;
-        const unsigned blocks = (unsigned)((rows_padded + 255) / 256);
-        if (k == 16 && ((uintptr_t)x & 15u) == 0)
-            hipLaunchKernelGGL(knn_frag16_kernel, dim3(blocks), dim3(256), 0, compute, (const f4v *)x, rows, rows_padded,
-                               st.center, sigma, frag, norms, dout, st.outliers, ocap, (unsigned)c0);
-        else
-            hipLaunchKernelGGL(knn_frag_kernel, dim3(blocks), dim3(256), 0, compute, x, rows, rows_padded, k, kt, st.center,
-                               sigma, 1.0f, INFINITY, frag, norms, dout, 0, nullptr, nullptr, st.outliers, ocap, (unsigned)c0);
-        e = hipGetLastError();
-    }
+
+    // 3. the chunks (copy_in_chunks), every one filled into the plain layout as it lands: the big chunk's fragment kernels
+    // (0.8 ms for 960 MiB) run under the tail's copy (1.2 ms); what is left after the last byte is the tail's own fragment
+    // kernel (~0.05 ms).  Chunks start at multiples of 1024 rows: whole tiles; the last chunk pads its last tile.
+    const long long rows_padded = (n + 31) / 32 * 32;
     unsigned hout[4] = {0, 0, 0, 0};
-    if (usable && e == hipSuccess)
-        e = hipMemcpyAsync(hout, dout, sizeof hout, hipMemcpyDeviceToHost, compute);
-    const hipError_t e1 = hipStreamSynchronize(copy), e2 = hipStreamSynchronize(compute);
-    tr.lap("streams drained");
-    if (e == hipSuccess)
-        e = e1 != hipSuccess ? e1 : e2;
-    for (hipEvent_t ev : events)
-        (void)hipEventDestroy(ev);
+    hipError_t e;
+    {
+        ChunkEvents events;
+        e = copy_in_chunks(r_dev, r_host, k, n, 1024, copy, compute, usable ? &events : nullptr, tr, [&](long long r0, long long r1) {
+            return plain_fill(st, r_dev, r0, r1 - r0, (r1 == n ? rows_padded : r1) - r0, dout, compute);
+        });
+        if (usable && e == hipSuccess)
+            e = hipMemcpyAsync(hout, dout, sizeof hout, hipMemcpyDeviceToHost, compute);
+        const hipError_t e1 = hipStreamSynchronize(copy), e2 = hipStreamSynchronize(compute);
+        tr.lap("streams drained");
+        if (e == hipSuccess)
+            e = e1 != hipSuccess ? e1 : e2;
+    }
     (void)KNN_DEV_FREE(dout);
     tr.lap("events + scratch released");
     if (e != hipSuccess) {
         knn_filter_free(st);
         return e;
     }
-    if (!layouts)
+    if (!layouts || (usable && layout_accept(st, hout)))
         return hipSuccess;
-    if (usable && hout[2] == 0u && hout[3] <= ocap) {
-        st.n_outliers = hout[3];
-        memcpy(&st.bmax, &hout[0], 4);
-        memcpy(&st.nmax, &hout[1], 4);
-        st.usable = true;
-        return hipSuccess;
-    }
     // the sampled box did not fit the data (or the sample held non-finite values): classic build from
     // the rows that are now resident
     knn_filter_free(st);
@@ -2106,9 +2156,8 @@ hipError_t knn_filter_build_cells_from_host(FilterState &st, int k, long long n,
 {
     st = FilterState();
     BuildTrace tr{"knn ingest"};
-    const size_t row_bytes = (size_t)k * sizeof(float);
     auto plain_copy = [&]() -> hipError_t {
-        FTRY(hipMemcpyAsync(r_dev, r_host, (size_t)n * row_bytes, hipMemcpyHostToDevice, copy));
+        FTRY(hipMemcpyAsync(r_dev, r_host, (size_t)n * k * sizeof(float), hipMemcpyHostToDevice, copy));
         return hipStreamSynchronize(copy);
     };
     if (k > 16 || n < (1ll << 17))
@@ -2116,9 +2165,8 @@ hipError_t knn_filter_build_cells_from_host(FilterState &st, int k, long long n,
     // 1. frame and cuts from a host sample
     const long long samples = 4096;
     const std::vector<float> samp = host_sample(r_host, n, k, samples);
-    std::vector<float> center;
-    float sigma = 1.0f;
-    if (!box_from_sample(samp.data(), samples, k, 16, center, &sigma))
+    Frame frame;
+    if (!frame_from_sample(frame, samp.data(), samples, k, 16))
         return plain_copy();
     const std::vector<float> cuts = cut_sample(samp, k);
     tr.lap("host sample, box, cuts");
@@ -2130,7 +2178,7 @@ hipError_t knn_filter_build_cells_from_host(FilterState &st, int k, long long n,
     if (!(st.cells = stg.c))
         return plain_copy();
     unsigned *dout = nullptr;
-    hipError_t e = layouts_alloc(st, k, n, stg.ntiles, center.data(), sigma, true, &dout, compute);
+    hipError_t e = layouts_alloc(st, k, n, stg.ntiles, frame, true, &dout, compute);
     if (e != hipSuccess) {   // no room for the layouts: rows only (the caller's build will find the same and say so)
         (void)hipGetLastError();
         (void)hipStreamSynchronize(compute);
@@ -2140,37 +2188,16 @@ hipError_t knn_filter_build_cells_from_host(FilterState &st, int k, long long n,
         return plain_copy();
     }
     tr.lap("allocations");
-    // 3. two chunks (see knn_filter_build_from_host: a pageable copy runs at the link rate but every call costs ~0.25 ms of
-    // pipeline fill): everything but the last 64 MiB, then the tail; each is scattered into the buckets as soon as it is there
-    const long long tail_rows = ((long long)((64u << 20) / row_bytes) + 4095) / 4096 * 4096;
-    const long long head_rows = (size_t)n * row_bytes > ((size_t)128u << 20) ? (n - tail_rows) / 4096 * 4096 : n;
-    std::vector<hipEvent_t> events;
-    for (long long r0 = 0; r0 < n && e == hipSuccess;) {
-        const long long r1 = r0 == 0 ? head_rows : n;
-        e = hipMemcpyAsync(r_dev + (size_t)r0 * k, r_host + (size_t)r0 * k, (size_t)(r1 - r0) * row_bytes, hipMemcpyHostToDevice, copy);
-        tr.lap("copy call returned");
-        hipEvent_t ev = nullptr;
-        if (e == hipSuccess)
-            e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-        if (e == hipSuccess) {
-            events.push_back(ev);
-            e = hipEventRecord(ev, copy);
-        }
-        if (e == hipSuccess)
-            e = hipStreamWaitEvent(compute, ev, 0);
-        if (e == hipSuccess)
-            e = knn_cells_fast_scatter(*st.cells, k, r_dev, r0, r1, compute);
-        r0 = r1;
-    }
+    // 3. the chunks (copy_in_chunks, in multiples of 4096 rows), each scattered into the buckets as soon as it is there
+    ChunkEvents events;
+    e = copy_in_chunks(r_dev, r_host, k, n, 4096, copy, compute, &events, tr,
+                       [&](long long r0, long long r1) { return knn_cells_fast_scatter(*st.cells, k, r_dev, r0, r1, compute); });
     // 4. cell prefix, placement, padding — and ONE synchronisation of both streams.  Not usable (a bucket overflowed, the
     // sample was not representative): the caller builds from the resident rows.
     if (e == hipSuccess)
         e = knn_cells_fast_finish(*st.cells, stg.fill, compute);
     bool overflow = false;
-    e = cells_finish(st, stg, e, r_dev, dout, cuts.data(), samples / 4, compute, tr, &overflow, copy);
-    for (hipEvent_t ev : events)
-        (void)hipEventDestroy(ev);
-    return e;
+    return cells_finish(st, stg, e, r_dev, dout, cuts.data(), samples / 4, compute, tr, &overflow, copy);
 }
 
 static hipError_t ensure_workspace(FilterState &st, FilterWorkspace &w, int m)

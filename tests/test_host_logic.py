@@ -653,3 +653,43 @@ def test_bench_dump_outputs_writes_indices_and_distances_exactly(tmp_path):
     got_i = np.load(tmp_path / "big" / "indices.npy")
     assert got_i.shape == (b.DUMP_MAX_QUERIES,) and got_i[-1] == b.DUMP_MAX_QUERIES - 1
     assert (tmp_path / "big" / "indices.npy").stat().st_size + (tmp_path / "big" / "dist2.npy").stat().st_size <= 64 << 20
+
+
+def test_ingest_split_is_the_two_piece_rule_and_always_advances():
+    """knn_ingest_head_rows (both ingests' chunk split, through knn_debug_ingest_head_rows) against the rule restated: shards
+    above 128 MiB go over as everything but the last 64 MiB (the tail rounded up, the head rounded down to the granule), smaller
+    ones in one piece.  Rows wider than ~32 KiB in a shard just over 128 MiB would leave a head of no rows — a copy loop that never
+    advances; those go over in one piece too."""
+    _built_lib()
+    import multicore_hw2_amd as pkg
+
+    def rule(k, n, g):
+        row_bytes = 4 * k
+        tail = ((64 << 20) // row_bytes + g - 1) // g * g
+        return (n - tail) // g * g if n * row_bytes > (128 << 20) else n
+
+    two_pieces = 0
+    for g, ks in ((1024, range(1, 4097)), (4096, range(1, 17))):
+        for k in ks:
+            at = (128 << 20) // (4 * k)
+            for n in (at, at + 1, at + 2, at + 1023, at + 4095, 1 << 24):
+                head = pkg.debug_ingest_head_rows(k, n, g)
+                assert head == rule(k, n, g), (k, n, g)
+                assert head % g == 0 or head == n, (k, n, g, head)
+                assert 0 < head <= n, (k, n, g, head)
+                pieces, r0 = 0, 0
+                while r0 < n and pieces < 3:      # the copy loop: the head, then the rest
+                    r0 = head if r0 == 0 else n
+                    pieces += 1
+                assert r0 == n and pieces <= 2, (k, n, g, pieces)
+                two_pieces += pieces == 2
+    assert two_pieces > 4096
+    assert pkg.debug_ingest_head_rows(16, (1 << 21) + 4097, 1024) == pkg.debug_ingest_head_rows(16, (1 << 21) + 4097, 4096) == 1052672
+    # the rule's head is 0 (or below) here: one piece
+    for k, n in ((12000, 2797), (16000, 2098), (20000, 1678), (100000, 336)):
+        assert rule(k, n, 1024) < 1024 and 4 * k * n > (128 << 20)
+        assert pkg.debug_ingest_head_rows(k, n, 1024) == n, (k, n)
+    for bad in ((0, 1, 1024), (1 << 31, 1, 1024), (16, -1, 1024), (16, (1 << 40) + 1, 1024), (16, 1 << 20, 0), (16, 1 << 20, 1000),
+                (16, 1 << 20, -1024), (16, 1 << 20, (1 << 20) + 32)):
+        with pytest.raises(pkg.KnnError):
+            pkg.debug_ingest_head_rows(*bad)
