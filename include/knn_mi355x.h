@@ -213,6 +213,7 @@ int knn_index_query_host(knn_index *idx, int m, const float *queries_host, int *
  * (a query nothing bounds, fewer than K sampled blocks with a real row, more candidates than the buffers hold) raises [2] = 1
  * and is answered by the exact top-K scan; [1] = records re-ranked.  1 = the exact top-K scan (v0 arithmetic over every
  * row): per-cell frames (centred or 8-bit rows), grid indexes, cell-range shards, shards or batches below the filter's sizes.
+ * 3 = the grid index, only for calls that carry KNN_QUERY_TOPK_GRID (below).
  * Results are bit-exact either way.
  * Any K outside 1 .. 64, or m < 1, is KNN_EINVAL (knn_last_error says why) and launches nothing.
  *
@@ -233,6 +234,16 @@ int knn_index_query_host(knn_index *idx, int m, const float *queries_host, int *
  * and changes nothing: full lists satisfy the contract.
  * ---------------------------------------------------------------------- */
 #define KNN_QUERY_TOPK_PARTIAL 2u
+/* KNN_QUERY_TOPK_GRID (knn_index_query_topk only; the 1-NN entry points reject it): the grid index may answer this top-K call.
+ * With the flag, a call on an index that has a grid index, under option "path" 0 or 3, is served by it (knn_index_last_stats
+ * [0] = 3): one wave per query walks the grid's rings as the 1-NN query does, keeps the K smallest keys seen — one per lane — and
+ * stops once no unseen row can reach the K-th; a few hundred rows per query where the exact top-K scan reads the shard.  A
+ * batch with a query the rings cannot finish (far outside the rows' box, an empty region) is answered by the exact top-K scan
+ * instead ([2] = 1); [1] and [3] are 0.  On any other index or path the flag is accepted and changes nothing, and without it
+ * every call goes exactly where it went before.  Results are bit-identical either way.  The library will take this path on its
+ * own once it is measured against the exact top-K scan: the policy sends a call to a path only where it is measured faster than
+ * the one it replaces (tools/grid_topk_timing.py takes those measurements). */
+#define KNN_QUERY_TOPK_GRID 4u
 /* keys_dev [m][K]; indices_dev [m][K] or NULL: the int32 indices, unpacked after the fold.  Slot rules as knn_index_query:
  * eight workspaces, calls sharing one must be stream-ordered; asynchronous on `stream`. */
 int knn_index_query_topk(knn_index *idx, int slot, int m, int K, const float *queries_dev, unsigned long long *keys_dev,
@@ -439,6 +450,12 @@ int knn_debug_filter_query_plan(const long long in[11], long long out[49]);
  * first (1-NN); top-K: candidate keys per query, 1 if knn_debug_cells_topk_plan takes the call, its passes and the first pass's
  * queries}. */
 int knn_debug_query_route(const long long in[25], long long out[6]);
+/* Test hook (host arithmetic only, no GPU needed): what a top-K call that carries KNN_QUERY_TOPK_GRID launches with.
+ * in = {k (1 .. 4), K, m, 1 if the index has a grid index, option path, 1 if the call carries the flag};
+ * out = {1 if the grid index answers the call; rings a query walks before it gives up; blocks; waves per block (one query each);
+ * bytes of the slot's list scratch for a folding call ([m][K] keys); launches of a folding call: the grid kernel, the gated exact
+ * top-K (a scan and a select per 65536 queries), the fold}.  Everything after out[0] is 0 when the grid does not answer. */
+int knn_debug_grid_topk_plan(const long long in[6], long long out[6]);
 /* Test hook (host arithmetic only, no GPU needed): what an index is built with.  in = {k, n_local, 1 if the rows are on the
  * device, build_filter (-1 library policy: knn_index_create; 0 none, 1 the MFMA filter layouts, 2 cell-sorted), build_grid (-1
  * library policy, 0, 1), and the options path, cells, ingest, cells_build};

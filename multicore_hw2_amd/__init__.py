@@ -31,10 +31,11 @@ EXPORTED_SYMBOLS = [
     "knn_index_query_keys_ex", "knn_index_debug_counters", "knn_debug_scan_plan", "knn_debug_scan_plan_ex", "knn_debug_cells_query_plan", "knn_debug_cells_topk_plan", "knn_debug_seed_kth", "knn_debug_topk_gate", "knn_debug_filter_query_plan", "knn_debug_query_route", "knn_debug_index_build_plan", "knn_debug_ingest_head_rows", "knn_debug_shard_policy", "knn_debug_plan_shard", "knn_debug_u8_row", "knn_debug_u8_bin_row", "knn_debug_u8_bin_threshold", "knn_index_query",
     "knn_geom_create", "knn_geom_destroy", "knn_geom_info", "knn_geom_assign", "knn_index_create_sharded",
     "knn_index_seed_export", "knn_index_seed_attach", "knn_geom_first_cell",
-    "knn_index_query_topk", "knn_keys_topk_merge", "knn_index_query_topk_host",
+    "knn_index_query_topk", "knn_keys_topk_merge", "knn_index_query_topk_host", "knn_debug_grid_topk_plan",
 ]
 QUERY_INIT_KEYS = 1   # KNN_QUERY_INIT_KEYS
 QUERY_TOPK_PARTIAL = 2   # KNN_QUERY_TOPK_PARTIAL
+QUERY_TOPK_GRID = 4   # KNN_QUERY_TOPK_GRID
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # KNN_MI355X_LIB: A/B hook — load another build of the same C-ABI (e.g. a previous commit's .so)
@@ -245,6 +246,21 @@ def debug_query_route(**inputs):
     return dict(zip(QUERY_ROUTE, list(out)))
 
 
+GRID_TOPK_INPUTS = ("k", "K", "m", "has_grid", "path", "flag")
+GRID_TOPK_PLAN = ("use", "rmax", "blocks", "waves", "scratch_bytes", "launches")
+
+
+def debug_grid_topk_plan(**inputs):
+    """knn_debug_grid_topk_plan: whether the grid index answers a top-K call that carries KNN_QUERY_TOPK_GRID and what the
+    call launches with, for the inputs named in GRID_TOPK_INPUTS.  Host arithmetic; works without a GPU."""
+    vin = (ctypes.c_longlong * len(GRID_TOPK_INPUTS))(*[int(inputs[n]) for n in GRID_TOPK_INPUTS])
+    out = (ctypes.c_longlong * len(GRID_TOPK_PLAN))()
+    f = lib().knn_debug_grid_topk_plan
+    f.argtypes = [ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)]
+    _check(f(vin, out))
+    return dict(zip(GRID_TOPK_PLAN, list(out)))
+
+
 INDEX_BUILD_INPUTS = ("k", "n_local", "refs_on_device", "build_filter", "build_grid", "path", "cells", "ingest", "cells_build")
 INDEX_BUILD_PLAN = ("filter_wanted", "want_cells", "build_filter", "grid_planned", "want_layouts", "ingest")
 
@@ -426,17 +442,20 @@ class KnnIndex:
                                           out.ctypes.data_as(ctypes.c_void_p)))
         return out
 
-    def query_topk(self, m, K, queries_dev, keys_dev, stream=0, slot=0, init_keys=False, indices_dev=None, partial=False):
+    def query_topk(self, m, K, queries_dev, keys_dev, stream=0, slot=0, init_keys=False, indices_dev=None, partial=False,
+                   grid=False):
         """Async (knn_index_query_topk): keys_dev[m][K] <- the K smallest (distance, global index) keys of (this shard's rows
         and, unless init_keys, the K sorted keys per query keys_dev already holds), sorted.  indices_dev: also the int32
         indices [m][K].  partial (KNN_QUERY_TOPK_PARTIAL): the caller merges every shard's lists, so this shard need only
         report the rows that can belong to the global top-K — what lets a cell-range shard take the cell-pruned scan
-        (option topk_cells = 1); see include/knn_mi355x.h, 2c, for the contract."""
+        (option topk_cells = 1); see include/knn_mi355x.h, 2c, for the contract.  grid (KNN_QUERY_TOPK_GRID): an index that
+        has a grid index answers the call with it (last_stats()[0] == 3); on any other index the flag changes nothing."""
         _check(lib().knn_index_query_topk(self._h, int(slot), int(m), int(K), ctypes.c_void_p(int(queries_dev)),
                                           ctypes.c_void_p(int(keys_dev)),
                                           ctypes.c_void_p(int(indices_dev)) if indices_dev is not None else None,
                                           ctypes.c_void_p(stream),
-                                          (QUERY_INIT_KEYS if init_keys else 0) | (QUERY_TOPK_PARTIAL if partial else 0)))
+                                          (QUERY_INIT_KEYS if init_keys else 0) | (QUERY_TOPK_PARTIAL if partial else 0) |
+                                          (QUERY_TOPK_GRID if grid else 0)))
 
     def query_topk_host(self, queries, K):
         """Synchronous top-K of this shard alone: (indices int32 [m][K], dist2 float32 [m][K])."""

@@ -259,6 +259,7 @@ struct knn_index {
     long long stats[4] = {0, 0, 0, 0};
     FilterState filter;           // MFMA filter layouts + workspace (usable == false: exact only)
     GridState *grid = nullptr;    // k <= 4: uniform-grid spatial index (null: not built / ruled out)
+    const unsigned *grid_topk_gate = nullptr;   // the last call was a top-K on the grid: its give-up word (knn_index_last_stats)
     int timing = 0;            // 0 off, N > 0: bracket every N-th dominant-kernel launch with events
     unsigned long long timing_seq = 0;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;  // one pair per timed launch
@@ -822,10 +823,15 @@ QueryRoute knn_query_route(const QueryRouteInputs &in)
     }
     // Top-K: the cell-pruned top-K where knn_cells_topk_plan takes the call; else the MFMA filter for the dense
     // layouts and for a cell-sorted fp16 layout in the shard's frame (scanned in full), under the 1-NN rule's options and sizes;
-    // exact top-K for per-cell frames (centred), 8-bit rows the plan declines, grid indexes, cell-range shards whose call does not
+    // exact top-K for per-cell frames (centred), 8-bit rows the plan declines, grid indexes (unless the call carries
+    // KNN_QUERY_TOPK_GRID: then the grid's own top-K, DESIGN §4.6 "Grid top-K"), cell-range shards whose call does not
     // carry KNN_QUERY_TOPK_PARTIAL (the pruned form's lists are not the shard's own top-K: include/knn_mi355x.h §2c), tiny
     // shards, few queries, and outlier lists longer than half a query's candidate room.
     t.ccap = r.ccap = knn_topk_ccap(t.K, m);
+    if (grid_serves && in.topk_grid) {   // KNN_QUERY_TOPK_GRID: on request, until it is measured against the exact top-K
+        r.way = QueryWay::Grid;
+        return r;
+    }
     t.other_path = grid_serves || path == 1 || path == 3;
     r.topk = knn_cells_topk_plan(t);
     if (r.topk.use)
@@ -862,6 +868,7 @@ QueryRouteInputs route_inputs(const knn_index *idx, int m, int K, unsigned flags
     in.filter_wanted = idx->filter_wanted;
     in.init_keys = (flags & KNN_QUERY_INIT_KEYS) != 0u;
     in.path = (int)g_opt_path;
+    in.topk_grid = K > 0 && (flags & KNN_QUERY_TOPK_GRID) != 0u;
     return in;
 }
 
@@ -974,6 +981,7 @@ int knn_index_query(knn_index *idx, int slot, int m, const float *queries_dev, u
     idx->stats[0] = (long long)route.way;
     idx->stats[1] = 0;
     idx->stats[2] = 0;
+    idx->grid_topk_gate = nullptr;
     if (route.fill_keys_first)
         HIP_TRY(knn_keys_fill_launch(keys, m, s));
     switch (route.way) {
@@ -1017,7 +1025,7 @@ int knn_index_query_topk(knn_index *idx, int slot, int m, int K, const float *qu
                          int *indices_dev, void *stream, unsigned flags)
 {
     if (!idx || m < 1 || K < 1 || K > KNN_TOPK_MAX || (long long)m * K > INT_MAX || slot < 0 || slot >= KNN_SLOTS ||
-        !queries_dev || !keys_dev || (flags & ~(unsigned)(KNN_QUERY_INIT_KEYS | KNN_QUERY_TOPK_PARTIAL)) != 0u)
+        !queries_dev || !keys_dev || (flags & ~(unsigned)(KNN_QUERY_INIT_KEYS | KNN_QUERY_TOPK_PARTIAL | KNN_QUERY_TOPK_GRID)) != 0u)
         return fail(KNN_EINVAL, "knn_index_query_topk: bad arguments (1 <= K <= 64, m >= 1, slot 0 .. 7)");
     std::lock_guard<std::recursive_mutex> lock(idx->mu);
     DeviceGuard guard(idx->device);
@@ -1029,6 +1037,7 @@ int knn_index_query_topk(knn_index *idx, int slot, int m, int K, const float *qu
     idx->stats[0] = 1;
     idx->stats[1] = 0;
     idx->stats[2] = 0;
+    idx->grid_topk_gate = nullptr;
     idx->last_slot = slot;
     const int mk = m * K;
     if (idx->n == 0) {   // an empty shard adds nothing
@@ -1056,6 +1065,18 @@ int knn_index_query_topk(knn_index *idx, int slot, int m, int K, const float *qu
     hipEvent_t ev0 = ev ? ev->first : nullptr, ev1 = ev ? ev->second : nullptr;
     // the filter ways' candidate lists [m][ccap] and counts [m]
     u64 *&cand = idx->topk_cand[slot];
+    if (route.way == QueryWay::Grid) {
+        // the grid way (KNN_QUERY_TOPK_GRID): the kernel's lists are the caller's keys, or — a folding call — the slot's scratch
+        const GridTopkPlan gp = knn_grid_topk_plan(idx->k, K, m, true, 0, true);
+        if (!init)
+            KNN_TRY(slot_buffer_grow(cand, idx->topk_cand_bytes[slot], gp.scratch_bytes));
+        idx->stats[3] = 0;
+        HIP_TRY(knn_grid_query_topk(idx->grid, gp, slot, m, K, idx->n, queries_dev, idx->refs, idx->base, keys, init, cand, part,
+                                    part_bytes, idx->num_cu, s, ev0, ev1, &idx->grid_topk_gate));
+        if (indices_dev)
+            HIP_TRY(knn_keys_unpack_launch(keys, mk, indices_dev, s));
+        return KNN_OK;
+    }
     if (route.way != QueryWay::Exact)
         KNN_TRY(slot_buffer_grow(cand, idx->topk_cand_bytes[slot], (size_t)m * route.ccap * sizeof(u64) + (size_t)m * sizeof(unsigned)));
     unsigned *ccount = route.way != QueryWay::Exact ? (unsigned *)(cand + (size_t)m * route.ccap) : nullptr;
@@ -1074,7 +1095,7 @@ int knn_index_query_topk(knn_index *idx, int slot, int m, int K, const float *qu
                                       route.ccap, part, part_bytes, idx->num_cu, s, ev0, ev1));
         break;
     }
-    default: {   // (QueryWay::Exact: a top-K call is never routed to the grid index)
+    default: {   // (QueryWay::Exact; the grid way was taken above)
         // a cell-range shard's keys carry its rows' global numbers (gids); an index-range shard's base + row
         const unsigned *gids = idx->sharded && idx->filter.cells ? idx->filter.cells->gids : nullptr;
         if (ev)
@@ -1182,6 +1203,12 @@ int knn_index_last_stats(knn_index *idx, long long stats[4])
         idx->stats[1] = records;
         idx->stats[2] = ctl[KNN_CTL_FALLBACK] ? 1 : ctl[KNN_CTL_EXACT_CELLS] ? 2 : 0;   // 2: the batch's listed (cell, query) pairs were evaluated exactly
         idx->stats[3] = idx->filter.n_outliers;
+    }
+    if (idx->stats[0] == 3 && idx->grid_topk_gate) {   // a top-K call on the grid: 1 = some query gave up, the exact top-K answered
+        DeviceGuard guard(idx->device);
+        unsigned word = 0u;
+        HIP_TRY(hipMemcpy(&word, idx->grid_topk_gate, sizeof word, hipMemcpyDeviceToHost));
+        idx->stats[2] = word ? 1 : 0;
     }
     memcpy(stats, idx->stats, sizeof idx->stats);
     return KNN_OK;
@@ -1361,6 +1388,17 @@ int knn_debug_query_route(const long long in[25], long long out[6])
     ri.init_keys = in[24] != 0;
     const QueryRoute r = knn_query_route(ri);
     const long long v[6] = {(long long)r.way, r.fill_keys_first, r.ccap, r.topk.use, r.topk.passes, r.topk.pass_m};
+    memcpy(out, v, sizeof v);
+    return KNN_OK;
+}
+
+int knn_debug_grid_topk_plan(const long long in[6], long long out[6])
+{
+    if (!in || !out || in[0] < 1 || in[0] > 4 || in[1] < 1 || in[1] > KNN_TOPK_MAX || in[2] < 1 || in[2] > INT_MAX ||
+        in[2] * in[1] > INT_MAX || in[3] < 0 || in[3] > 1 || in[4] < 0 || in[4] > 3 || in[5] < 0 || in[5] > 1)
+        return fail(KNN_EINVAL, "knn_debug_grid_topk_plan: bad arguments (1 <= k <= 4, 1 <= K <= 64, m >= 1, path 0 .. 3)");
+    const GridTopkPlan p = knn_grid_topk_plan((int)in[0], (int)in[1], (int)in[2], in[3] != 0, (int)in[4], in[5] != 0);
+    const long long v[6] = {p.use, p.rmax, p.blocks, p.waves, (long long)p.scratch_bytes, p.launches};
     memcpy(out, v, sizeof v);
     return KNN_OK;
 }

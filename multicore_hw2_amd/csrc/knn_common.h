@@ -423,6 +423,7 @@ struct QueryRouteInputs {
     bool filter_wanted = false;    // its creator asked for the layouts below the size the library builds them from
     bool init_keys = false;        // KNN_QUERY_INIT_KEYS
     int path = 0;                  // option `path`
+    bool topk_grid = false;        // KNN_QUERY_TOPK_GRID: the grid index may answer this top-K call
 };
 struct QueryRoute {
     QueryWay way = QueryWay::Exact;
@@ -535,6 +536,19 @@ void knn_grid_free(GridState *&gs);
 // unfinished (the caller queues the gated brute-force scan behind it).
 hipError_t knn_grid_query(const GridState *gs, int slot, int m, const float *q_dev, long long base, u64 *keys_dev,
                           const unsigned **gate_out, hipStream_t stream);
+// Top-K on the grid index (KNN_QUERY_TOPK_GRID; knn_grid_topk_kernel): what a call launches with.  Host arithmetic only.
+struct GridTopkPlan {
+    bool use = false;          // the grid answers the call (everything below is 0 otherwise)
+    int rmax = 0;              // rings a query walks before it gives up
+    unsigned blocks = 0;
+    int waves = 0;             // per block: one query each
+    size_t scratch_bytes = 0;  // a folding call's lists [m][K] (the slot's topk_cand)
+    int launches = 0;          // of a folding call: grid kernel, gated exact top-K (scan + select per chunk), fold
+};
+GridTopkPlan knn_grid_topk_plan(int k, int K, int m, bool has_grid, int path, bool flag);
+hipError_t knn_grid_query_topk(const GridState *gs, const GridTopkPlan &plan, int slot, int m, int K, long long n, const float *q_dev,
+                               const float *r_dev, long long base, u64 *keys, int init, u64 *scratch, u64 *part, size_t part_bytes,
+                               int num_cu, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const unsigned **gate_out);
 void knn_grid_info(const GridState *gs, long long info[4]);
 
 // ---- RCCL exchange step (knn_rccl.cpp; librccl is dlopen'ed at first use) -------------------

@@ -15,6 +15,8 @@
 //            the search stops as soon as  best < LB(r)^2 (1 - 1e-6)  — strictly below what v0 could compute
 //            for any unseen row, so neither the minimum nor a tie for it can be outside (lowest index among
 //            equal distances is decided by the packed key among the rows seen).
+//   top-K  : the same walk with the K smallest keys seen, one per lane, in place of the minimum, and the stop rule on the
+//            K-th key (knn_grid_topk_kernel; on request: KNN_QUERY_TOPK_GRID).
 // Never used when the rows hold non-finite values or the grid degenerates (a cell with > 4096 rows):
 // the brute-force kernels take those shards.
 #include "knn_common.h"
@@ -22,6 +24,7 @@
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
+#include <algorithm>
 #include <vector>
 
 #define GRID_BLOCK 256
@@ -218,6 +221,59 @@ __device__ __forceinline__ u64 grid_wave_min(u64 v)
     return v;
 }
 
+// Position idx of the (2r+1)^K block of cells around the query's cell c: true when it is a cell of the grid that belongs to
+// ring r (largest |offset| exactly r; `first`: rings 0 .. r together), *cell_out = its linear id.
+template <int K>
+__device__ __forceinline__ bool grid_ring_cell(const GridGeom &gg, const int c[4], int r, int side, int idx, bool first,
+                                               unsigned *cell_out)
+{
+    int rem = idx, far = 0;
+    bool inside = true;
+    unsigned cell = 0u;
+#pragma unroll
+    for (int d = 0; d < K; ++d) {
+        const int off = rem % side - r;
+        rem /= side;
+        const int cd = c[d] + off;
+        far = abs(off) > far ? abs(off) : far;
+        inside = inside && cd >= 0 && cd < gg.g[d];
+        cell += (unsigned)(inside ? cd : 0) * gg.stride[d];
+    }
+    *cell_out = cell;
+    return inside && !(first ? far > r : far != r);
+}
+
+// The stop rule's bound after ring r: rows not yet seen are outside the block of rings 0..r; along the axis where they leave
+// it they are at least `lb` from the query (faces beyond the grid bound nothing: no rows out there).
+// A row's cell comes from fp32 arithmetic, t = fl(fl(x - lo) * inv_w): a row of a cell below face F
+// (an integer) has t < F, hence x < lo + F w (1 + 2^-22) — two roundings and the rounding of inv_w itself —
+// and a row of a cell at or above F has x >= lo + F w (1 - 2^-21).  The error grows with the face's distance
+// from the corner, at most g w 2^-21: gg.slack[d] = (1e-3 + g 2^-21) w covers it (knn_grid_build keeps
+// g <= 2^19 so that this stays a quarter of a cell; the 1e-3 w alone, the round-2 form, was short of it
+// from g ~ 4000 up on a single live axis).
+// *covers_all: the block is the whole grid (nothing is unseen).
+template <int K>
+__device__ __forceinline__ double grid_face_bound(const GridGeom &gg, const int c[4], const float q[4], int r, bool *covers_all)
+{
+    double lb = INFINITY;
+    bool all = true;
+#pragma unroll
+    for (int d = 0; d < K; ++d) {
+        if (c[d] - r > 0) {
+            all = false;
+            const double face = gg.dlo[d] + (double)(c[d] - r) * gg.w[d];
+            lb = fmin(lb, (double)q[d] - face - gg.slack[d]);
+        }
+        if (c[d] + r < gg.g[d] - 1) {
+            all = false;
+            const double face = gg.dlo[d] + (double)(c[d] + r + 1) * gg.w[d];
+            lb = fmin(lb, face - (double)q[d] - gg.slack[d]);
+        }
+    }
+    *covers_all = all;
+    return lb;
+}
+
 template <int K>
 __global__ __launch_bounds__(GRID_BLOCK) void knn_grid_query_kernel(const float *__restrict__ Q, int m, GridGeom gg,
                                                                     const unsigned *__restrict__ start,
@@ -268,19 +324,8 @@ __global__ __launch_bounds__(GRID_BLOCK) void knn_grid_query_kernel(const float 
             total *= side;
         u64 mine = kKeyInit;
         for (int idx = lane; idx < total; idx += KNN_WAVE) {
-            int rem = idx, far = 0;
-            bool inside = true;
-            unsigned cell = 0u;
-#pragma unroll
-            for (int d = 0; d < K; ++d) {
-                const int off = rem % side - r;
-                rem /= side;
-                const int cd = c[d] + off;
-                far = abs(off) > far ? abs(off) : far;
-                inside = inside && cd >= 0 && cd < gg.g[d];
-                cell += (unsigned)(inside ? cd : 0) * gg.stride[d];
-            }
-            if (!inside || (first ? far > r : far != r))
+            unsigned cell;
+            if (!grid_ring_cell<K>(gg, c, r, side, idx, first, &cell))
                 continue;
             const unsigned p0 = start[cell], p1 = start[cell + 1];
             for (unsigned p = p0; p < p1; ++p) {
@@ -301,29 +346,9 @@ __global__ __launch_bounds__(GRID_BLOCK) void knn_grid_query_kernel(const float 
         first = false;
         mine = grid_wave_min(mine);
         best = mine < best ? mine : best;
-        // stop rule: rows not yet seen are outside the block of rings 0..r; along the axis where they leave
-        // it they are at least `lb` from the query (faces beyond the grid bound nothing: no rows out there).
-        // A row's cell comes from fp32 arithmetic, t = fl(fl(x - lo) * inv_w): a row of a cell below face F
-        // (an integer) has t < F, hence x < lo + F w (1 + 2^-22) — two roundings and the rounding of inv_w itself —
-        // and a row of a cell at or above F has x >= lo + F w (1 - 2^-21).  The error grows with the face's distance
-        // from the corner, at most g w 2^-21: gg.slack[d] = (1e-3 + g 2^-21) w covers it (knn_grid_build keeps
-        // g <= 2^19 so that this stays a quarter of a cell; the 1e-3 w alone, the round-2 form, was short of it
-        // from g ~ 4000 up on a single live axis).
-        double lb = INFINITY;
-        bool covers_all = true;
-#pragma unroll
-        for (int d = 0; d < K; ++d) {
-            if (c[d] - r > 0) {
-                covers_all = false;
-                const double face = gg.dlo[d] + (double)(c[d] - r) * gg.w[d];
-                lb = fmin(lb, (double)q[d] - face - gg.slack[d]);
-            }
-            if (c[d] + r < gg.g[d] - 1) {
-                covers_all = false;
-                const double face = gg.dlo[d] + (double)(c[d] + r + 1) * gg.w[d];
-                lb = fmin(lb, face - (double)q[d] - gg.slack[d]);
-            }
-        }
+        // stop rule (grid_face_bound): every unseen row is at least lb away
+        bool covers_all;
+        const double lb = grid_face_bound<K>(gg, c, q, r, &covers_all);
         if (covers_all) {
             done = true;
             break;
@@ -344,8 +369,138 @@ __global__ __launch_bounds__(GRID_BLOCK) void knn_grid_query_kernel(const float 
     }
 }
 
+// ---- top-K query (KNN_QUERY_TOPK_GRID) ------------------------------------------------------------
+// Lane `src`'s value of a 64-bit register, wave-uniform.
+__device__ __forceinline__ u64 grid_readlane64(u64 v, int src)
+{
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, src);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), src);
+    return ((u64)hi << 32) | (u64)lo;
+}
+
+// The K smallest keys of a query (KK <= 64 = the wave width), the 1-NN kernel's walk with a list in place of the running
+// minimum.  The sorted list lives in registers, one packed key per lane: lane t < KK holds the t-th smallest key seen
+// (KNN_KEY_INIT while fewer than t + 1 rows are in), lanes >= KK hold ~0; the K-th key is lane KK - 1's, kept wave-uniform in
+// `kth`.  A row is a candidate when its v0 distance is finite and its key is below the K-th; candidates are taken one at a
+// time: broadcast, its place = #{list < candidate}, the lanes from that place up take their lower neighbour's key.  (Keys are
+// distinct — every row is seen once and carries its own number — so places are never ambiguous.)
+// A ring's cells go to the lanes as in the 1-NN kernel, 64 at a time; while a ring has at most 32 positions (the first pass of
+// k <= 3) `split` = 2, 4, ... lanes share a cell and take every split-th row of it.  The row loop runs to the wave's longest
+// share under a predicate, so every cross-lane step is executed by the whole wave.
+// Stop rule, after ring r: the block of rings 0..r is the whole grid, or lane KK - 1 holds a real key whose distance is
+// < lb^2 (1 - 1e-6) — every unseen row's computed distance is strictly above that, so none can enter the list or tie its K-th
+// place.  The list goes to out[q][0 .. KK) and is never folded here: a batch that gives up is answered again by the exact
+// top-K behind this kernel, and a row folded by both would stand in the caller's keys twice.
+template <int KD>
+__global__ __launch_bounds__(GRID_BLOCK) void knn_grid_topk_kernel(const float *__restrict__ Q, int m, int KK, GridGeom gg,
+                                                                   const unsigned *__restrict__ start,
+                                                                   const f4g *__restrict__ pts,
+                                                                   const unsigned *__restrict__ orig, long long base,
+                                                                   u64 *__restrict__ out, int rmax,
+                                                                   unsigned *__restrict__ giveup,
+                                                                   unsigned *__restrict__ giveup_next)
+{
+#pragma clang fp contract(off)
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        *giveup_next = 0u;   // (the slot's other word, as the 1-NN kernel)
+    const int lane = threadIdx.x & 63;
+    const int qi = blockIdx.x * (GRID_BLOCK / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (qi >= m)
+        return;
+    u64 *__restrict__ o = out + (size_t)qi * KK;
+    u64 list = lane < KK ? kKeyInit : ~0ull;
+    float q[4] = {0.f, 0.f, 0.f, 0.f};
+    bool finite = true;
+#pragma unroll
+    for (int d = 0; d < KD; ++d) {
+        q[d] = Q[(size_t)qi * KD + d];
+        finite = finite && fabsf(q[d]) < INFINITY;
+    }
+    if (!finite) {   // every distance is NaN or +INF: no row is a candidate (and nothing to give up on)
+        if (lane < KK)
+            o[lane] = kKeyInit;
+        return;
+    }
+    int c[4];
+    (void)grid_cell_of(gg, q, c);
+    int gmax = 1;
+#pragma unroll
+    for (int d = 0; d < KD; ++d)
+        gmax = gg.g[d] > gmax ? gg.g[d] : gmax;
+
+    u64 kth = kKeyInit;
+    bool done = false;
+    bool first = true;
+    for (int r = gmax > 1 ? 1 : 0; r < gmax && r <= rmax; ++r) {
+        const int side = 2 * r + 1;
+        int total = 1;
+#pragma unroll
+        for (int d = 0; d < KD; ++d)
+            total *= side;
+        int shift = 0;   // split = 1 << shift lanes per cell
+        while ((total << (shift + 1)) <= KNN_WAVE)
+            ++shift;
+        const int sub = lane & ((1 << shift) - 1), step = 1 << shift, per = KNN_WAVE >> shift;
+        for (int idx0 = 0; idx0 < total; idx0 += per) {
+            const int idx = idx0 + (lane >> shift);
+            unsigned p = 0u, p1 = 0u, cell;
+            if (idx < total && grid_ring_cell<KD>(gg, c, r, side, idx, first, &cell)) {
+                p = start[cell] + (unsigned)sub;
+                p1 = start[cell + 1];
+            }
+            while (__ballot(p < p1) != 0ull) {
+                u64 key = ~0ull;
+                if (p < p1) {
+                    const f4g x = pts[p];
+                    float acc = 0.0f;
+#pragma unroll
+                    for (int d = 0; d < KD; ++d) {
+                        const float diff = q[d] - x[d];   // v0: search - reference, squared, summed in order
+                        const float sq = diff * diff;
+                        acc = acc + sq;
+                    }
+                    if (acc < INFINITY)                   // NaN / +INF never beat +INF (v0's strict >)
+                        key = ((u64)__float_as_uint(acc) << 32) | (u64)(unsigned)(base + orig[p]);
+                }
+                p += (unsigned)step;
+                u64 pend = __ballot(key < kth);
+                while (pend != 0ull) {
+                    const int src = __builtin_ctzll(pend);
+                    pend &= pend - 1ull;
+                    const u64 cand = grid_readlane64(key, src);
+                    if (cand < kth) {   // (the K-th key may have come down since the ballot)
+                        const int pos = __popcll(__ballot(list < cand));
+                        const u64 up = __shfl_up(list, 1, KNN_WAVE);
+                        if (lane < KK)
+                            list = lane < pos ? list : lane == pos ? cand : up;
+                        kth = grid_readlane64(list, KK - 1);
+                    }
+                }
+            }
+        }
+        first = false;
+        bool covers_all;
+        const double lb = grid_face_bound<KD>(gg, c, q, r, &covers_all);
+        if (covers_all) {   // (the list may hold fewer than KK real keys: the rest stay KNN_KEY_INIT)
+            done = true;
+            break;
+        }
+        if (lb > 0.0 && kth < kKeyInit) {
+            const float kd = __uint_as_float((unsigned)(kth >> 32));
+            if ((double)kd < lb * lb * (1.0 - 1e-6)) {
+                done = true;
+                break;
+            }
+        }
+    }
+    if (lane < KK)
+        o[lane] = list;
+    if (lane == 0 && !done && gmax > rmax + 1)
+        *giveup = 1u;      // benign race: every writer stores 1
+}
+
 // ---- host -------------------------------------------------------------------------------------------
-#define GTRY(call)                       \
+#define GTRY(call)                     \
     do {                                 \
         hipError_t e_ = (call);          \
         if (e_ != hipSuccess)            \
@@ -509,6 +664,12 @@ hipError_t knn_grid_build(GridState **out, int k, long long n, const float *r, h
     return hipSuccess;
 }
 
+// rings a 1-NN query walks before it gives up
+static inline int grid_rmax_1nn(int k)
+{
+    return k == 1 ? 64 : k == 2 ? 16 : k == 3 ? 6 : 4;
+}
+
 // Asynchronous on `s`.  *gate_out = the device word the brute-force scan queued behind this must be gated on.
 hipError_t knn_grid_query(const GridState *gs, int slot, int m, const float *q, long long base, u64 *keys,
                           const unsigned **gate_out, hipStream_t s)
@@ -520,7 +681,7 @@ hipError_t knn_grid_query(const GridState *gs, int slot, int m, const float *q, 
     unsigned *giveup = gs->giveup + 2 * slot + (call & 1u);
     unsigned *giveup_next = gs->giveup + 2 * slot + ((call + 1u) & 1u);
     const int k = gs->geom.k;
-    const int rmax = k == 1 ? 64 : k == 2 ? 16 : k == 3 ? 6 : 4;
+    const int rmax = grid_rmax_1nn(k);
     const dim3 grid((unsigned)((m + GRID_BLOCK / 64 - 1) / (GRID_BLOCK / 64))), block(GRID_BLOCK);
     switch (k) {
     case 1: hipLaunchKernelGGL(knn_grid_query_kernel<1>, grid, block, 0, s, q, m, gs->geom, gs->start, gs->pts, gs->orig, base, keys, rmax, giveup, giveup_next); break;
@@ -530,6 +691,69 @@ hipError_t knn_grid_query(const GridState *gs, int slot, int m, const float *q, 
     }
     *gate_out = giveup;
     return hipGetLastError();
+}
+
+// Top-K on the grid (host arithmetic only).  rmax: a K-th neighbour lies deeper than the nearest — the first ring whose block
+// holds 4 K rows at the build's 3 rows per cell, doubled (+ 2) for queries at a cell's edge and uneven cells; never below the
+// 1-NN kernel's.
+GridTopkPlan knn_grid_topk_plan(int k, int K, int m, bool has_grid, int path, bool flag)
+{
+    GridTopkPlan p;
+    p.use = has_grid && flag && (path == 0 || path == 3);
+    if (!p.use)
+        return p;
+    int need = 0;
+    for (;; ++need) {
+        long long block = 3;
+        for (int d = 0; d < k; ++d)
+            block *= 2 * need + 1;
+        if (block >= 4ll * K)
+            break;
+    }
+    p.rmax = std::max(grid_rmax_1nn(k), 2 * need + 2);
+    p.waves = GRID_BLOCK / 64;
+    p.blocks = (unsigned)((m + p.waves - 1) / p.waves);
+    p.scratch_bytes = (size_t)m * (size_t)K * sizeof(u64);
+    p.launches = 1 + 2 * ((m + KNN_TOPK_CHUNK - 1) / KNN_TOPK_CHUNK) + 1;
+    return p;
+}
+
+// The whole top-K call on the grid way, asynchronous on `s`: the grid kernel writes the batch's lists [m][K] — into keys
+// itself when the call starts them (init), else into `scratch` (>= plan.scratch_bytes) —, the exact top-K behind it, gated on
+// the batch's give-up word, overwrites them when some query gave up, and a folding call then merges the scratch into keys.
+// ev0 / ev1 (nullable) bracket the grid kernel.  *gate_out = the give-up word (knn_index_last_stats reads it back).
+hipError_t knn_grid_query_topk(const GridState *gs, const GridTopkPlan &plan, int slot, int m, int K, long long n, const float *q,
+                               const float *r, long long base, u64 *keys, int init, u64 *scratch, u64 *part, size_t part_bytes,
+                               int num_cu, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, const unsigned **gate_out)
+{
+    *gate_out = nullptr;
+    if (!gs || !gs->usable || !plan.use || m <= 0 || K < 1 || K > KNN_WAVE || (!init && !scratch))
+        return hipErrorInvalidValue;
+    const unsigned call = gs->calls[slot]++;
+    unsigned *giveup = gs->giveup + 2 * slot + (call & 1u);
+    unsigned *giveup_next = gs->giveup + 2 * slot + ((call + 1u) & 1u);
+    u64 *lists = init ? keys : scratch;
+    const dim3 grid(plan.blocks), block(GRID_BLOCK);
+    if (ev0)
+        GTRY(hipEventRecord(ev0, s));
+#define GRID_TOPK(KDV)                                                                                                          \
+    hipLaunchKernelGGL(knn_grid_topk_kernel<KDV>, grid, block, 0, s, q, m, K, gs->geom, gs->start, gs->pts, gs->orig, base, lists, \
+                       plan.rmax, giveup, giveup_next)
+    switch (gs->geom.k) {
+    case 1: GRID_TOPK(1); break;
+    case 2: GRID_TOPK(2); break;
+    case 3: GRID_TOPK(3); break;
+    default: GRID_TOPK(4); break;
+    }
+#undef GRID_TOPK
+    GTRY(hipGetLastError());
+    if (ev1)
+        GTRY(hipEventRecord(ev1, s));
+    *gate_out = giveup;
+    GTRY(knn_exact_topk_launch(gs->geom.k, m, K, n, base, nullptr, q, r, lists, 1, part, part_bytes, num_cu, s, giveup));
+    if (!init)
+        GTRY(knn_topk_merge_launch(m, K, scratch, keys, s));
+    return hipSuccess;
 }
 
 void knn_grid_info(const GridState *gs, long long info[4])
