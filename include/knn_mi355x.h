@@ -387,6 +387,13 @@ int knn_debug_shard_policy(int k, int m, long long n, int ndev);
  * current options: out = {filter layouts (0 none: exact kernels, 1 plain, 2 cell-sorted: the pruned scan), 1 if the exact scan
  * runs chunk by chunk under the copy, 1 if the grid index (k <= 4) serves it, copy calls of the streamed form}. */
 int knn_debug_plan_shard(int k, int m, long long rows, long long out[4]);
+/* Test hook (host arithmetic only, no GPU needed): everything a cudaCallback(k, m, n, ...) decides before it runs, under the
+ * current options: in = {k, m, n, visible devices (faked), 1 if RCCL could be used (the answer its probe would give)};
+ * out = {shards, rows per shard, host threads, exchange step (0 keys merged on the host, 1 RCCL all-reduce), refusal (0 none;
+ * option rccl = 1 but 1: the shards are not the visible devices, 2: RCCL cannot be used), empty shards, rows of the last
+ * non-empty shard, 1 if the RCCL probe was asked at all, [8..11] the way the plan gives shard 0 and [12..15] the way it gives the
+ * last non-empty shard, each as knn_debug_plan_shard's four outputs}.  KNN_EINVAL unless k, m, n and the devices are >= 1. */
+int knn_debug_call_plan(const long long in[5], long long out[16]);
 /* Test hook (host arithmetic, no GPU): one row of k <= 16 coordinates through the 8-bit rows' quantiser (option "cells_rows"),
  * v = (row - centre) x scale in fp32: codes[k] = its bytes, out[0] = the largest per-coordinate error bound, out[1] = eta for a
  * query of largest |coordinate| amax.  0 on success. */

@@ -28,7 +28,7 @@ EXPORTED_SYMBOLS = [
     "knn_index_query_host", "knn_set_option", "knn_get_option", "knn_index_last_stats",
     "knn_synth_fill_device", "knn_index_timing", "knn_index_timing_read",
     "knn_debug_filter_scores", "knn_index_query_keys_slot", "knn_trim", "knn_keys_allreduce_min",
-    "knn_index_query_keys_ex", "knn_index_debug_counters", "knn_debug_scan_plan", "knn_debug_scan_plan_ex", "knn_debug_cells_query_plan", "knn_debug_cells_topk_plan", "knn_debug_seed_kth", "knn_debug_topk_gate", "knn_debug_filter_query_plan", "knn_debug_query_route", "knn_debug_index_build_plan", "knn_debug_ingest_head_rows", "knn_debug_shard_policy", "knn_debug_plan_shard", "knn_debug_u8_row", "knn_debug_u8_bin_row", "knn_debug_u8_bin_threshold", "knn_index_query",
+    "knn_index_query_keys_ex", "knn_index_debug_counters", "knn_debug_scan_plan", "knn_debug_scan_plan_ex", "knn_debug_cells_query_plan", "knn_debug_cells_topk_plan", "knn_debug_seed_kth", "knn_debug_topk_gate", "knn_debug_filter_query_plan", "knn_debug_query_route", "knn_debug_index_build_plan", "knn_debug_ingest_head_rows", "knn_debug_shard_policy", "knn_debug_plan_shard", "knn_debug_call_plan", "knn_debug_u8_row", "knn_debug_u8_bin_row", "knn_debug_u8_bin_threshold", "knn_index_query",
     "knn_geom_create", "knn_geom_destroy", "knn_geom_info", "knn_geom_assign", "knn_index_create_sharded",
     "knn_index_seed_export", "knn_index_seed_attach", "knn_geom_first_cell",
     "knn_index_query_topk", "knn_keys_topk_merge", "knn_index_query_topk_host", "knn_debug_grid_topk_plan",
@@ -295,6 +295,24 @@ def debug_plan_shard(k, m, rows):
     f.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)]
     _check(f(int(k), int(m), int(rows), out))
     return dict(zip(("filter", "streamed", "grid", "chunks"), list(out)))
+
+
+CALL_PLAN_FIELDS = ("shards", "per", "threads", "rccl", "refusal", "empty", "last_rows", "probed")
+
+
+def debug_call_plan(k, m, n, ndev, rccl_usable=True):
+    """knn_debug_call_plan: what a cudaCallback(k, m, n) decides under the current options on a node with ndev devices where
+    RCCL can (not) be used; first_way / last_way: how shard 0 and the last non-empty shard are served (host arithmetic; works
+    without a GPU)."""
+    vin = (ctypes.c_longlong * 5)(int(k), int(m), int(n), int(ndev), 1 if rccl_usable else 0)
+    out = (ctypes.c_longlong * 16)()
+    f = lib().knn_debug_call_plan
+    f.argtypes = [ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)]
+    _check(f(vin, out))
+    plan = dict(zip(CALL_PLAN_FIELDS, list(out)[:8]))
+    ways = ("filter", "streamed", "grid", "chunks")            # as debug_plan_shard names them
+    plan["first_way"], plan["last_way"] = dict(zip(ways, list(out)[8:12])), dict(zip(ways, list(out)[12:16]))
+    return plan
 
 
 def shard_bounds(n, shards):

@@ -18,6 +18,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <functional>
 #include <mutex>
 #include <unordered_map>
 #include <string>
@@ -165,6 +166,48 @@ void pool_put(int dev, void *p, size_t bytes)
     for (void *d : drop)
         (void)hipFree(d);
 }
+
+// Owner of staging buffers taken from the pool on one device: they go back when it leaves scope or on release().  It
+// keeps the pool's rule: unless its user has said waited() — all work that used the buffers has been waited for, by a
+// blocking copy or a synchronised stream — it waits for the whole device first.
+class Staging {
+    int dev_;
+    bool waited_ = false;
+    std::vector<PoolEntry> held_;
+public:
+    explicit Staging(int dev) : dev_(dev) {}
+    Staging(Staging &&o) noexcept : dev_(o.dev_), waited_(o.waited_) { held_.swap(o.held_); }
+    ~Staging() { release(); }
+    // device `dev` must be current
+    template <class T> hipError_t get(T **out, size_t bytes)
+    {
+        const hipError_t e = pool_get(dev_, bytes, (void **)out);
+        held_.push_back(PoolEntry{*out, bytes});   // (null after a failure: pool_put skips it)
+        waited_ = false;
+        return e;
+    }
+    void waited() { waited_ = true; }
+    void release()
+    {
+        if (!waited_ && !held_.empty()) {
+            DeviceGuard guard(dev_);
+            (void)hipDeviceSynchronize();
+        }
+        for (const PoolEntry &e : held_)
+            pool_put(dev_, e.p, e.bytes);
+        held_.clear();
+    }
+};
+
+// What one shard of a cudaCallback leaves: its m packed keys, on the host or (RCCL exchange) in `owner`'s buffer `dev`, or an error.
+struct ShardKeys {
+    std::vector<u64> host;
+    Staging owner;
+    u64 *dev = nullptr;   // (complete when rc is KNN_OK)
+    int rc = 0;
+    std::string err;
+    explicit ShardKeys(int device) : owner(device) {}
+};
 
 std::unordered_map<void *, std::pair<int, size_t>> g_live;  // pooled buffers handed to the filter code
 
@@ -1474,43 +1517,42 @@ int knn_synth_fill_device(int device, float *dst_dev, long long count, unsigned 
 
 namespace {
 
-// Queries on the host, packed keys back on the host; everything else stays on `idx->device`.
-// keep_dev != nullptr: the keys stay on the device instead (*keep_dev = pooled buffer of m keys, complete
-// on return; the caller gives it back with pool_put) — the RCCL merge of cudaCallback reads them there.
-int query_keys_host(knn_index *idx, int m, const float *queries_host, u64 *keys_host, u64 **keep_dev = nullptr)
+// One query with the queries on the host — K = 0: the nearest neighbour, one key per query; K >= 1: the top-K, K keys
+// per query.  The queries are staged into a pooled buffer, the query runs on the null stream and the packed keys come
+// back to keys_host; everything else stays on `idx->device`.  keep != nullptr: the keys stay on the device instead, in a
+// buffer that keep->owner holds (keep->dev, complete on return) — the RCCL merge of cudaCallback reads them there.
+int staged_query(knn_index *idx, const char *who, int m, int K, const float *queries_host, u64 *keys_host, ShardKeys *keep = nullptr)
 {
+    const std::string name(who);
     DeviceGuard guard(idx->device);
     if (!guard.ok)
-        return fail(KNN_EHIP, "query: hipSetDevice failed");
+        return fail(KNN_EHIP, (name + ": hipSetDevice failed").c_str());
+    Staging stage(idx->device);
     float *q_dev = nullptr;
     u64 *keys_dev = nullptr;
-    const size_t qbytes = (size_t)m * (size_t)idx->k * sizeof(float);
-    const size_t kbytes = (size_t)m * sizeof(u64);
-    int rc = KNN_OK;
-    hipError_t e = pool_get(idx->device, qbytes, (void **)&q_dev);
+    const size_t qbytes = (size_t)m * (size_t)idx->k * sizeof(float), kbytes = (size_t)m * (size_t)std::max(K, 1) * sizeof(u64);
+    hipError_t e = stage.get(&q_dev, qbytes);
     if (e == hipSuccess)
-        e = pool_get(idx->device, kbytes, (void **)&keys_dev);
+        e = (keep ? keep->owner : stage).get(&keys_dev, kbytes);
     if (e == hipSuccess)
         e = hipMemcpy(q_dev, queries_host, qbytes, hipMemcpyHostToDevice);
     if (e != hipSuccess)
-        rc = fail(KNN_EHIP, "query: staging queries", hipGetErrorString(e));
-    if (rc == KNN_OK)
-        rc = knn_keys_init(idx->device, keys_dev, m, nullptr);
-    if (rc == KNN_OK)
+        return fail(KNN_EHIP, (name + ": staging queries").c_str(), hipGetErrorString(e));
+    int rc = K > 0 ? knn_index_query_topk(idx, 0, m, K, q_dev, keys_dev, nullptr, nullptr, KNN_QUERY_INIT_KEYS)
+                   : knn_keys_init(idx->device, keys_dev, m, nullptr);
+    if (rc == KNN_OK && K == 0)
         rc = knn_index_query_keys(idx, m, q_dev, keys_dev, nullptr);
-    if (rc == KNN_OK) {
-        e = keep_dev ? hipStreamSynchronize(nullptr) : hipMemcpy(keys_host, keys_dev, kbytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess)
-            rc = fail(KNN_EHIP, "query: D2H keys", hipGetErrorString(e));
-    }
     if (rc != KNN_OK)
-        (void)hipDeviceSynchronize();  // nothing in flight may still use the buffers going back to the pool
-    pool_put(idx->device, q_dev, qbytes);
-    if (keep_dev && rc == KNN_OK)
-        *keep_dev = keys_dev;
-    else
-        pool_put(idx->device, keys_dev, kbytes);
-    return rc;
+        return rc;
+    e = keep ? hipStreamSynchronize(nullptr) : hipMemcpy(keys_host, keys_dev, kbytes, hipMemcpyDeviceToHost);
+    if (e != hipSuccess)
+        return fail(KNN_EHIP, (name + ": D2H keys").c_str(), hipGetErrorString(e));
+    if (keep)
+        keep->dev = keys_dev;
+    if (K == 0)
+        stage.waited();   // by the blocking copy / the synchronised null stream
+    // K >= 1: not declared, so that the top-K's buffers go back after the device-wide wait `stage` then makes itself
+    return KNN_OK;
 }
 
 }  // namespace
@@ -1523,7 +1565,7 @@ extern "C" int knn_index_query_host(knn_index *idx, int m, const float *queries_
         return KNN_OK;
     std::vector<u64> keys((size_t)m, kKeyInit);
     if (idx->n > 0) {
-        int rc = query_keys_host(idx, m, queries_host, keys.data());
+        int rc = staged_query(idx, "query", m, 0, queries_host, keys.data());
         if (rc != KNN_OK)
             return rc;
     }
@@ -1538,32 +1580,9 @@ extern "C" int knn_index_query_topk_host(knn_index *idx, int m, int K, const flo
     if (!idx || m < 1 || K < 1 || K > KNN_TOPK_MAX || (long long)m * K > INT_MAX || !queries_host || !indices_host)
         return fail(KNN_EINVAL, "knn_index_query_topk_host: bad arguments (1 <= K <= 64, m >= 1)");
     std::lock_guard<std::recursive_mutex> lock(idx->mu);
-    DeviceGuard guard(idx->device);
-    if (!guard.ok)
-        return fail(KNN_EHIP, "knn_index_query_topk_host: hipSetDevice failed");
     const size_t mk = (size_t)m * (size_t)K;
-    const size_t qbytes = (size_t)m * (size_t)idx->k * sizeof(float), kbytes = mk * sizeof(u64);
-    float *q_dev = nullptr;
-    u64 *keys_dev = nullptr;
     std::vector<u64> keys(mk);
-    int rc = KNN_OK;
-    hipError_t e = pool_get(idx->device, qbytes, (void **)&q_dev);
-    if (e == hipSuccess)
-        e = pool_get(idx->device, kbytes, (void **)&keys_dev);
-    if (e == hipSuccess)
-        e = hipMemcpy(q_dev, queries_host, qbytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess)
-        rc = fail(KNN_EHIP, "knn_index_query_topk_host: staging queries", hipGetErrorString(e));
-    if (rc == KNN_OK)
-        rc = knn_index_query_topk(idx, 0, m, K, q_dev, keys_dev, nullptr, nullptr, KNN_QUERY_INIT_KEYS);
-    if (rc == KNN_OK) {
-        e = hipMemcpy(keys.data(), keys_dev, kbytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess)
-            rc = fail(KNN_EHIP, "knn_index_query_topk_host: D2H keys", hipGetErrorString(e));
-    }
-    (void)hipDeviceSynchronize();   // nothing in flight may still use the buffers going back to the pool
-    pool_put(idx->device, q_dev, qbytes);
-    pool_put(idx->device, keys_dev, kbytes);
+    const int rc = staged_query(idx, "knn_index_query_topk_host", m, K, queries_host, keys.data());
     if (rc != KNN_OK)
         return rc;
     for (size_t i = 0; i < mk; ++i) {
@@ -1585,7 +1604,7 @@ namespace {
 // k = 16, m <= ~1300 the exact scan of a chunk takes less than its PCIe transfer, so the call
 // costs the transfer plus one chunk's scan.
 int run_shard_streamed(int device, int k, int m, long long rows, long long base, const float *queries_host,
-                       const float *refs_host, u64 *keys_host, u64 **keep_dev = nullptr, int nchunks_hint = 8)
+                       const float *refs_host, u64 *keys_host, ShardKeys *keep = nullptr, int nchunks_hint = 8)
 {
     DeviceGuard guard(device);
     if (!guard.ok)
@@ -1612,11 +1631,12 @@ int run_shard_streamed(int device, int k, int m, long long rows, long long base,
     float *r_dev = nullptr, *q_dev = nullptr;
     u64 *keys_dev = nullptr;
     std::vector<hipEvent_t> events;
-    hipError_t e = pool_get(device, rbytes, (void **)&r_dev);
+    Staging stage(device);
+    hipError_t e = stage.get(&r_dev, rbytes);
     if (e == hipSuccess)
-        e = pool_get(device, qbytes, (void **)&q_dev);
+        e = stage.get(&q_dev, qbytes);
     if (e == hipSuccess)
-        e = pool_get(device, kbytes, (void **)&keys_dev);
+        e = (keep ? keep->owner : stage).get(&keys_dev, kbytes);
     if (e == hipSuccess)
         e = hipMemcpyAsync(q_dev, queries_host, qbytes, hipMemcpyHostToDevice, st.compute);
     if (e == hipSuccess)
@@ -1640,7 +1660,7 @@ int run_shard_streamed(int device, int k, int m, long long rows, long long base,
             e = knn_exact_launch(k, m, r1 - r0, base + r0, q_dev, r_dev + (size_t)r0 * k, keys_dev, num_cu, nullptr,
                                  st.compute);
     }
-    if (e == hipSuccess && !keep_dev)
+    if (e == hipSuccess && !keep)
         e = hipMemcpyAsync(keys_host, keys_dev, kbytes, hipMemcpyDeviceToHost, st.compute);
     const hipError_t e_sync1 = hipStreamSynchronize(st.copy);
     const hipError_t e_sync2 = hipStreamSynchronize(st.compute);
@@ -1649,15 +1669,10 @@ int run_shard_streamed(int device, int k, int m, long long rows, long long base,
     for (hipEvent_t ev : events)
         (void)hipEventDestroy(ev);
     if (e != hipSuccess)
-        (void)hipDeviceSynchronize();  // nothing in flight may still use the buffers going back to the pool
-    pool_put(device, r_dev, rbytes);
-    pool_put(device, q_dev, qbytes);
-    if (keep_dev && e == hipSuccess)
-        *keep_dev = keys_dev;
-    else
-        pool_put(device, keys_dev, kbytes);
-    if (e != hipSuccess)
         return fail(KNN_EHIP, "cudaCallback: streamed shard", hipGetErrorString(e));
+    stage.waited();   // both streams have been synchronised
+    if (keep)
+        keep->dev = keys_dev;
     return KNN_OK;
 }
 
@@ -1680,13 +1695,13 @@ struct ShardPlan {
     double seconds = 0.0;    // the chosen way
 };
 
-// The options the cost model reads, filled by its callers.
+// The options the cost model and the call plan read, filled by their callers.
 struct ShardOptions {
-    long long path = 0, cells = 0, ingest = 0, cells_build = 0, stream = 0;
+    long long path = 0, cells = 0, ingest = 0, cells_build = 0, stream = 0, shards = 0, rccl = 0;
 };
 ShardOptions shard_options()
 {
-    return {g_opt_path, g_opt_cells, g_opt_ingest, g_opt_cells_build, g_opt_stream};
+    return {g_opt_path, g_opt_cells, g_opt_ingest, g_opt_cells_build, g_opt_stream, g_opt_shards, g_opt_rccl};
 }
 
 ShardPlan plan_shard(int k, int m, long long rows, const ShardOptions &o)
@@ -1785,41 +1800,43 @@ extern "C" int knn_debug_shard_policy(int k, int m, long long n, int ndev)
     return shard_policy(k, m, n, ndev, shard_options());
 }
 
-// ---------------------------------------------------------------------------------------------
-// The drop-in entry point (reference core.h:71, core.cu:1282-1297 -> v8, core.cu:856-958).
-// ---------------------------------------------------------------------------------------------
-extern "C" void cudaCallback(int k, int m, int n, float *searchPoints, float *referencePoints,
-                             int **results)
+namespace {
+
+// Everything one cudaCallback decides, decided once from the call's sizes, the visible devices and ONE reading of the
+// options (a knn_set_option from another thread cannot make the shards and the exchange step disagree).
+struct CallShard {
+    int device;
+    long long lo, hi;   // its rows; hi <= lo: an empty shard (no `way`)
+    ShardPlan way;      // which of the three ways serves it: plan_shard (cost model)
+};
+struct CallPlan {
+    int k, m;
+    ShardOptions opt;
+    long long per = 0;         // rows per shard
+    int threads = 1;           // one host thread per GPU (core.cu:873); shards that share a device run back to back
+    bool rccl_wanted = false, use_rccl = false;   // the exchange step: RCCL all-reduce on the devices, else a merge on the host
+    int refusal = 0;           // option rccl = 1, but 1: the shards are not the visible devices, 2: RCCL cannot be used
+    std::string rccl_why;      // why it cannot
+    std::vector<CallShard> shard;
+};
+
+// rccl_usable (knn_rccl_available: it dlopens librccl) is asked only for a call whose rule wants RCCL.
+CallPlan plan_call(int k, int m, long long n, int ndev, const ShardOptions &o, const std::function<int(std::string *)> &rccl_usable)
 {
-    if (k < 1 || m < 1 || n < 1 || !searchPoints || !referencePoints || !results) {
-        fail(KNN_EINVAL, "cudaCallback: k, m, n must be >= 1 and pointers non-null");
-        die(__FILE__, __LINE__, KNN_EINVAL, g_err.c_str());
-    }
-    const int ndev = knn_device_count();
-    if (ndev < 1) {
-        // The reference computes on the CPU here (core.cu:869-870); this library has no CPU path.
-        fail(KNN_ENODEV, "cudaCallback: no HIP device visible (this library has no CPU fallback)");
-        die(__FILE__, __LINE__, KNN_ENODEV, g_err.c_str());
-    }
+    CallPlan p;
+    p.k = k, p.m = m, p.opt = o;
     // core.cu:865-872: how many GPUs take part (never more shards than points; one GPU for the small sets of the TA
     // harness; beyond that by the cost model: shard_policy).  Option `shards` forces a count (test hook).
-    long long shards = g_opt_shards > 0 ? (long long)g_opt_shards : (long long)shard_policy(k, m, n, ndev, shard_options());
-    if (shards > n)
-        shards = n;
-    g_last_shards = shards;
-    g_last_cells = 0;
-    static const bool trace = getenv("KNN_MI355X_TRACE_CALL") != nullptr;
-    if (trace)
-        fprintf(stderr, "[knn call] k %d m %d n %d: %d GPU(s) visible -> %lld shard(s)%s\n", k, m, n, ndev, shards,
-                g_opt_shards > 0 ? " (option shards)" : "");
+    const long long shards = std::min(n, o.shards > 0 ? o.shards : (long long)shard_policy(k, m, n, ndev, o));
     // core.cu:875: thread_n = divup(n, num_gpus); the last shard takes what is left.  A shard
     // past the end is empty here (the reference patches it to one overlapping point,
     // core.cu:881-882; an empty shard gives the same minimum).
-    const long long per = (n + shards - 1) / shards;
-
-    std::vector<std::vector<u64>> shard_keys((size_t)shards);
-    std::vector<int> shard_rc((size_t)shards, KNN_OK);
-    std::vector<std::string> shard_err((size_t)shards);
+    p.per = (n + shards - 1) / shards;
+    p.threads = (int)std::min<long long>(shards, ndev);
+    for (long long g = 0; g < shards; ++g) {
+        const long long lo = std::min(g * p.per, n), hi = std::min(lo + p.per, n);
+        p.shard.push_back({(int)(g % ndev), lo, hi, hi > lo ? plan_shard(k, m, hi - lo, o) : ShardPlan()});
+    }
     // The exchange step.  Several GPUs with one shard each (the reference's configuration, core.cu:873):
     // every shard leaves its m packed keys ON ITS DEVICE and one RCCL all-reduce(uint64, min) merges them
     // (knn_rccl.cpp); device 0's copy comes back to the host.  More shards than devices (the single-GPU
@@ -1827,219 +1844,235 @@ extern "C" void cudaCallback(int k, int m, int n, float *searchPoints, float *re
     // min-merged on the host — the same unsigned minimum.
     // ONE communicator set per process, for all visible devices (ncclCommInitAll takes seconds on an 8-GPU node): a call
     // that uses fewer GPUs than are visible merges on the host instead of creating a second set.
-    std::string rccl_why;
-    const bool rccl_wanted = g_opt_rccl != 2 && shards == ndev && (g_opt_rccl == 1 || shards > 1);
-    const bool use_rccl = rccl_wanted && knn_rccl_available(&rccl_why) != 0;
-    if (g_opt_rccl == 1 && shards > 1 && shards != ndev) {
-        // (`rccl` = 1 means "always, and die when RCCL cannot serve" — a call that the policy or option `shards`
-        // splits over another number of GPUs than are visible has no communicator set, and merging on the host in silence
-        // would break that contract)
-        char why[160];
-        snprintf(why, sizeof why, "%lld shards on %d visible GPU(s): the one communicator set of the process spans all visible devices", shards, ndev);
-        fail(KNN_EINVAL, "cudaCallback: option rccl = 1 but the call's shards are not the visible devices", why);
-        die(__FILE__, __LINE__, KNN_EINVAL, g_err.c_str());
-    }
-    if (trace && shards > 1 && !use_rccl)
-        fprintf(stderr, "[knn call] keys merged on the host: %s\n",
-                g_opt_rccl == 2 ? "option rccl = 2" : shards != ndev ? "the shards are not the visible devices" : rccl_why.c_str());
-    if (rccl_wanted && !use_rccl && g_opt_rccl == 1) {
-        fail(KNN_EHIP, "cudaCallback: option rccl = 1 but RCCL cannot be used", rccl_why.c_str());
-        die(__FILE__, __LINE__, KNN_EHIP, g_err.c_str());
-    }
-    std::vector<u64 *> shard_dev_keys((size_t)shards, nullptr);   // use_rccl: pooled, on device g % ndev
-
-    auto run_shard = [&](long long g) {
-        const long long lo = std::min<long long>(g * per, n);
-        const long long hi = std::min<long long>(lo + per, n);
-        std::vector<u64> &keys = shard_keys[(size_t)g];
-        u64 **keep_dev = use_rccl ? &shard_dev_keys[(size_t)g] : nullptr;
-        if (!use_rccl)
-            keys.assign((size_t)m, kKeyInit);
-        if (hi <= lo) {
-            if (use_rccl) {   // an empty shard still takes part in the all-reduce: m keys of (+INF, 0)
-                DeviceGuard guard((int)(g % ndev));
-                u64 *kd = nullptr;
-                hipError_t e = guard.ok ? pool_get((int)(g % ndev), (size_t)m * sizeof(u64), (void **)&kd) : hipErrorInvalidDevice;
-                if (e == hipSuccess)
-                    e = knn_keys_fill_launch(kd, m, nullptr);
-                if (e == hipSuccess)
-                    e = hipStreamSynchronize(nullptr);
-                if (e != hipSuccess) {
-                    shard_rc[(size_t)g] = fail(KNN_EHIP, "cudaCallback: empty shard keys", hipGetErrorString(e));
-                    shard_err[(size_t)g] = g_err;
-                    pool_put((int)(g % ndev), kd, (size_t)m * sizeof(u64));
-                } else {
-                    *keep_dev = kd;
-                }
-            }
-            return;
-        }
-        knn_index *idx = nullptr;
-        // which of the three ways serves this shard: plan_shard (cost model)
-        const ShardPlan plan = plan_shard(k, m, hi - lo, shard_options());
-        const int want_filter = plan.want_filter;
-        const bool want_grid = plan.want_grid, streamed = plan.streamed;
-        const double t_streamed = plan.t_streamed, t_staged = plan.t_staged;
-        const double nchunks = plan.nchunks;
-        const auto t0 = std::chrono::steady_clock::now();
-        if (streamed) {
-            const int rc = run_shard_streamed((int)(g % ndev), k, m, hi - lo, lo, searchPoints,
-                                              referencePoints + (size_t)lo * (size_t)k, keys.data(), keep_dev, (int)nchunks);
-            shard_rc[(size_t)g] = rc;
-            if (rc != KNN_OK)
-                shard_err[(size_t)g] = g_err;
-            if (trace)
-                fprintf(stderr, "[knn call] shard %lld rows %lld streamed exact scan: %.3f ms (model: streamed %.3f, staged %.3f)\n",
-                        g, hi - lo, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(),
-                        t_streamed * 1e3, t_staged * 1e3);
-            return;
-        }
-        int rc = index_create_impl(&idx, (int)(g % ndev), k, hi - lo,
-                                   referencePoints + (size_t)lo * (size_t)k, 0, lo, nullptr, want_grid ? 0 : want_filter,
-                                   want_grid ? 1 : 0);
-        const auto t1 = std::chrono::steady_clock::now();
-        if (rc == KNN_OK)
-            rc = query_keys_host(idx, m, searchPoints, keys.data(), keep_dev);
-        if (rc == KNN_OK && idx->stats[0] == 4)
-            ++g_last_cells;
-        const auto t2 = std::chrono::steady_clock::now();
-        knn_index_destroy(idx);
-        if (trace) {
-            const auto t3 = std::chrono::steady_clock::now();
-            auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-                return std::chrono::duration<double, std::milli>(b - a).count();
-            };
-            fprintf(stderr, "[knn call] shard %lld rows %lld filter %d: create (alloc + H2D + layouts) %.3f ms, "
-                            "query (stage + scan + D2H) %.3f ms, destroy %.3f ms\n",
-                    g, hi - lo, want_filter, ms(t0, t1), ms(t1, t2), ms(t2, t3));
-        }
-        shard_rc[(size_t)g] = rc;
-        if (rc != KNN_OK)
-            shard_err[(size_t)g] = g_err;
-    };
-
-    // One host thread per GPU (core.cu:873); shards that share a device run back to back.
-    const int nthreads = (int)std::min<long long>(shards, ndev);
-    if (nthreads <= 1) {
-        for (long long g = 0; g < shards; ++g)
-            run_shard(g);
-    } else {
-        std::vector<std::thread> pool;
-        for (int t = 0; t < nthreads; ++t)
-            pool.emplace_back([&, t] {
-                for (long long g = t; g < shards; g += nthreads)
-                    run_shard(g);
-            });
-        for (auto &th : pool)
-            th.join();
-    }
-    auto release_dev_keys = [&]() {
-        for (long long g = 0; g < shards; ++g)
-            if (shard_dev_keys[(size_t)g]) {
-                DeviceGuard guard((int)(g % ndev));
-                pool_put((int)(g % ndev), shard_dev_keys[(size_t)g], (size_t)m * sizeof(u64));
-                shard_dev_keys[(size_t)g] = nullptr;
-            }
-    };
-    for (long long g = 0; g < shards; ++g)
-        if (shard_rc[(size_t)g] != KNN_OK) {
-            release_dev_keys();
-            die(__FILE__, __LINE__, shard_rc[(size_t)g], shard_err[(size_t)g].c_str());
-        }
-
-    int *out = (int *)malloc(sizeof(int) * (size_t)m);  // caller free()s (main.cu:98,175)
-    if (!out) {
-        release_dev_keys();
-        die(__FILE__, __LINE__, KNN_ENOMEM, "malloc(results)");
-    }
-    bool merged_on_gpus = false;
-    if (use_rccl) {
-        // Final reduce on the GPUs: ncclAllReduce(uint64, min) over the shards' keys, one D2H from shard 0's device.
-        // The reduction writes to scratch buffers, never to the keys: if RCCL fails at run time (communicator
-        // creation on a node it does not like, a failed collective) and the option is 0 = "RCCL where possible", the
-        // shards' keys are still what the scans left and the host merge below takes over; `rccl` = 1 insists.
-        std::vector<int> devs((size_t)shards);
-        for (long long g = 0; g < shards; ++g)
-            devs[(size_t)g] = (int)(g % ndev);
-        std::string err;
-        std::vector<u64> merged((size_t)m);
-        std::vector<u64 *> scratch((size_t)shards, nullptr);
-        int rc = 0;
-        for (long long g = 0; g < shards && rc == 0; ++g) {
-            DeviceGuard guard(devs[(size_t)g]);
-            const hipError_t e = guard.ok ? pool_get(devs[(size_t)g], (size_t)m * sizeof(u64), (void **)&scratch[(size_t)g])
-                                          : hipErrorInvalidDevice;
-            if (e != hipSuccess) {
-                err = std::string("scratch keys for the reduction: ") + hipGetErrorString(e);
-                rc = -1;
-            }
-        }
-        // (test hook: a run-time RCCL failure, and — a one-GPU box can only reach this code with `rccl` = 1 — the
-        // fallback of the automatic mode with it)
-        const bool test_fail = getenv("KNN_MI355X_TEST_RCCL_FAIL") != nullptr;
-        if (rc == 0 && test_fail) {
-            err = "KNN_MI355X_TEST_RCCL_FAIL is set";
-            rc = -1;
-        }
-        if (rc == 0)
-            rc = knn_rccl_allreduce_min((int)shards, devs.data(), shard_dev_keys.data(), m, nullptr, err, scratch.data());
-        if (rc == 0) {
-            DeviceGuard guard(devs[0]);
-            const hipError_t e = hipMemcpy(merged.data(), scratch[0], (size_t)m * sizeof(u64), hipMemcpyDeviceToHost);
-            if (e != hipSuccess) {
-                err = std::string("D2H of the reduced keys: ") + hipGetErrorString(e);
-                rc = -1;
-            }
-        }
-        for (long long g = 0; g < shards; ++g) {   // nothing may still be reading the buffers going back to the pool
-            DeviceGuard guard(devs[(size_t)g]);
-            (void)hipStreamSynchronize(nullptr);
-            if (scratch[(size_t)g])
-                pool_put(devs[(size_t)g], scratch[(size_t)g], (size_t)m * sizeof(u64));
-        }
-        if (rc != 0 && (g_opt_rccl == 0 || test_fail)) {
-            // host merge of the (untouched) per-shard keys
-            static bool warned = false;
-            if (!warned) {
-                warned = true;
-                fprintf(stderr, "knn_mi355x: RCCL key reduction failed (%s); merging the shards' keys on the host\n", err.c_str());
-            }
-            (void)hipGetLastError();
-            for (long long g = 0; g < shards && rc != 0; ++g) {
-                DeviceGuard guard(devs[(size_t)g]);
-                shard_keys[(size_t)g].assign((size_t)m, kKeyInit);
-                const hipError_t e = hipMemcpy(shard_keys[(size_t)g].data(), shard_dev_keys[(size_t)g], (size_t)m * sizeof(u64),
-                                               hipMemcpyDeviceToHost);
-                if (e != hipSuccess) {
-                    err += std::string("; D2H of shard keys: ") + hipGetErrorString(e);
-                    rc = -2;
-                }
-            }
-            if (rc == -1)
-                rc = 1;   // keys are on the host: merge below
-        }
-        release_dev_keys();
-        if (rc < 0) {
-            free(out);
-            fail(KNN_EHIP, "cudaCallback: RCCL key reduction", err.c_str());
-            die(__FILE__, __LINE__, KNN_EHIP, g_err.c_str());
-        }
-        if (rc == 0) {
-            merged_on_gpus = true;
-            ++g_rccl_reductions;
-            for (int j = 0; j < m; ++j)
-                out[j] = (int)(unsigned)(merged[(size_t)j] & 0xFFFFFFFFull);
-        }
-    }
-    if (!merged_on_gpus) {
-        // Host merge: unsigned min of packed keys == lexicographic (distance, global index).
-        for (int j = 0; j < m; ++j) {
-            u64 best = kKeyInit;
-            for (long long g = 0; g < shards; ++g)
-                best = std::min(best, shard_keys[(size_t)g][(size_t)j]);
-            out[j] = (int)(unsigned)(best & 0xFFFFFFFFull);
-        }
-    }
-    *results = out;
+    p.rccl_wanted = o.rccl != 2 && shards == ndev && (o.rccl == 1 || shards > 1);
+    p.use_rccl = p.rccl_wanted && rccl_usable(&p.rccl_why) != 0;
+    // (`rccl` = 1 means "always, and die when RCCL cannot serve" — a call that the policy or option `shards`
+    // splits over another number of GPUs than are visible has no communicator set, and merging on the host in silence
+    // would break that contract)
+    p.refusal = o.rccl != 1 ? 0 : shards > 1 && shards != ndev ? 1 : p.rccl_wanted && !p.use_rccl ? 2 : 0;
+    return p;
 }
 
+// One shard of a call, on the calling thread: its rows of the references against all m queries.
+void run_call_shard(const CallPlan &plan, size_t g, const float *queries, const float *refs, bool trace, ShardKeys &out)
+{
+    using Clock = std::chrono::steady_clock;
+    auto ms = [](Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    const CallShard &s = plan.shard[g];
+    const int k = plan.k, m = plan.m;
+    const long long rows = s.hi - s.lo;
+    const float *rows_host = refs + (size_t)s.lo * (size_t)k;
+    ShardKeys *keep = plan.use_rccl ? &out : nullptr;
+    if (!keep)
+        out.host.assign((size_t)m, kKeyInit);   // (all that an empty shard leaves)
+    int rc = KNN_OK;
+    const auto t0 = Clock::now();
+    if (rows <= 0 && keep) {   // an empty shard still takes part in the all-reduce: m keys of (+INF, 0)
+        DeviceGuard guard(s.device);
+        hipError_t e = guard.ok ? keep->owner.get(&keep->dev, (size_t)m * sizeof(u64)) : hipErrorInvalidDevice;
+        if (e == hipSuccess)
+            e = knn_keys_fill_launch(keep->dev, m, nullptr);
+        if (e == hipSuccess)
+            e = hipStreamSynchronize(nullptr);
+        if (e != hipSuccess)
+            rc = fail(KNN_EHIP, "cudaCallback: empty shard keys", hipGetErrorString(e));
+    } else if (rows > 0 && s.way.streamed) {
+        rc = run_shard_streamed(s.device, k, m, rows, s.lo, queries, rows_host, out.host.data(), keep, s.way.nchunks);
+        if (trace)
+            fprintf(stderr, "[knn call] shard %zu rows %lld streamed exact scan: %.3f ms (model: streamed %.3f, staged %.3f)\n",
+                    g, rows, ms(t0, Clock::now()), s.way.t_streamed * 1e3, s.way.t_staged * 1e3);
+    } else if (rows > 0) {
+        knn_index *idx = nullptr;
+        rc = index_create_impl(&idx, s.device, k, rows, rows_host, 0, s.lo, nullptr, s.way.want_grid ? 0 : s.way.want_filter,
+                               s.way.want_grid ? 1 : 0);
+        const auto t1 = Clock::now();
+        if (rc == KNN_OK)
+            rc = staged_query(idx, "query", m, 0, queries, out.host.data(), keep);
+        if (rc == KNN_OK && idx->stats[0] == 4)
+            ++g_last_cells;
+        const auto t2 = Clock::now();
+        knn_index_destroy(idx);
+        if (trace)
+            fprintf(stderr, "[knn call] shard %zu rows %lld filter %d: create (alloc + H2D + layouts) %.3f ms, "
+                            "query (stage + scan + D2H) %.3f ms, destroy %.3f ms\n",
+                    g, rows, s.way.want_filter, ms(t0, t1), ms(t1, t2), ms(t2, Clock::now()));
+    }
+    out.rc = rc;
+    if (rc != KNN_OK)
+        out.err = g_err;
+}
+
+// The exchange step on the GPUs: ncclAllReduce(uint64, min) over the shards' keys, one D2H from shard 0's device.
+// The reduction writes to scratch buffers, never to the keys: if RCCL fails at run time (communicator
+// creation on a node it does not like, a failed collective), the shards' keys are still what the scans left.
+bool rccl_merge(const CallPlan &plan, std::vector<ShardKeys> &sk, std::vector<u64> &merged, std::string &err)
+{
+    const size_t shards = sk.size(), kbytes = (size_t)plan.m * sizeof(u64);
+    std::vector<int> devs(shards);
+    std::vector<u64 *> keys(shards), scratch(shards, nullptr);   // (scratch: with the shard's keys, in its owner)
+    for (size_t g = 0; g < shards; ++g) {
+        devs[g] = plan.shard[g].device;
+        keys[g] = sk[g].dev;
+        DeviceGuard guard(devs[g]);
+        const hipError_t e = guard.ok ? sk[g].owner.get(&scratch[g], kbytes) : hipErrorInvalidDevice;
+        if (e != hipSuccess) {
+            err = std::string("scratch keys for the reduction: ") + hipGetErrorString(e);
+            return false;
+        }
+    }
+    // (test hook: a run-time RCCL failure, and — a one-GPU box can only reach this code with `rccl` = 1 — the
+    // fallback of the automatic mode with it)
+    if (getenv("KNN_MI355X_TEST_RCCL_FAIL")) {
+        err = "KNN_MI355X_TEST_RCCL_FAIL is set";
+        return false;
+    }
+    if (knn_rccl_allreduce_min((int)shards, devs.data(), keys.data(), plan.m, nullptr, err, scratch.data()) != 0)
+        return false;
+    merged.resize((size_t)plan.m);
+    DeviceGuard guard0(devs[0]);
+    const hipError_t e = hipMemcpy(merged.data(), scratch[0], kbytes, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) {
+        err = std::string("D2H of the reduced keys: ") + hipGetErrorString(e);
+        return false;
+    }
+    for (size_t g = 0; g < shards; ++g) {   // nothing may still be reading the buffers going back to the pool
+        DeviceGuard guard(devs[g]);
+        if (hipStreamSynchronize(nullptr) == hipSuccess)
+            sk[g].owner.waited();
+    }
+    return true;
+}
+
+// The exchange step: the shards' keys -> the call's m merged keys.
+int exchange_keys(const CallPlan &plan, std::vector<ShardKeys> &sk, std::vector<u64> &merged)
+{
+    const size_t m = (size_t)plan.m;
+    std::string err;
+    if (plan.use_rccl) {
+        if (rccl_merge(plan, sk, merged, err)) {
+            ++g_rccl_reductions;
+            return KNN_OK;
+        }
+        // option 0 = "RCCL where possible" (and the test hook): the host merge takes over; `rccl` = 1 insists
+        if (plan.opt.rccl != 0 && !getenv("KNN_MI355X_TEST_RCCL_FAIL"))
+            return fail(KNN_EHIP, "cudaCallback: RCCL key reduction", err.c_str());
+        static bool warned = false;
+        if (!warned) {
+            warned = true;
+            fprintf(stderr, "knn_mi355x: RCCL key reduction failed (%s); merging the shards' keys on the host\n", err.c_str());
+        }
+        (void)hipGetLastError();
+        for (size_t g = 0; g < sk.size(); ++g) {   // the (untouched) per-shard keys
+            DeviceGuard guard(plan.shard[g].device);
+            sk[g].host.resize(m);
+            const hipError_t e = hipMemcpy(sk[g].host.data(), sk[g].dev, m * sizeof(u64), hipMemcpyDeviceToHost);
+            if (e != hipSuccess)
+                return fail(KNN_EHIP, "cudaCallback: RCCL key reduction", (err + "; D2H of shard keys: " + hipGetErrorString(e)).c_str());
+        }
+    }
+    // Host merge: unsigned min of packed keys == lexicographic (distance, global index).
+    merged.assign(m, kKeyInit);
+    for (const ShardKeys &s : sk)
+        for (size_t j = 0; j < m; ++j)
+            merged[j] = std::min(merged[j], s.host[j]);
+    return KNN_OK;
+}
+
+}  // namespace
+
+// Test hook (host arithmetic): the plan of a cudaCallback(k, m, n) under the current options on a node of in[3] devices
+// where the RCCL probe would answer in[4] (include/knn_mi355x.h lists `out`).
+extern "C" int knn_debug_call_plan(const long long in[5], long long out[16])
+{
+    if (!in || !out || in[0] < 1 || in[1] < 1 || in[2] < 1 || in[3] < 1 || in[0] > INT_MAX || in[1] > INT_MAX || in[3] > INT_MAX)
+        return fail(KNN_EINVAL, "knn_debug_call_plan: bad arguments");
+    bool asked = false;
+    const CallPlan p = plan_call((int)in[0], (int)in[1], in[2], (int)in[3], shard_options(), [&](std::string *) {
+        asked = true;
+        return in[4] != 0;
+    });
+    out[0] = (long long)p.shard.size();
+    out[1] = p.per;
+    out[2] = p.threads;
+    out[3] = p.use_rccl ? 1 : 0;
+    out[4] = p.refusal;
+    out[5] = out[6] = 0;
+    for (size_t g = 0; g < p.shard.size(); ++g) {
+        const CallShard &s = p.shard[g];
+        if (s.hi <= s.lo) {
+            ++out[5];
+            continue;
+        }
+        out[6] = s.hi - s.lo;
+        const long long way[4] = {s.way.want_filter, s.way.streamed ? 1 : 0, s.way.want_grid ? 1 : 0, s.way.nchunks};
+        for (int i = 0; i < 4; ++i) {   // shard 0's way, and the last non-empty shard's
+            if (g == 0)
+                out[8 + i] = way[i];
+            out[12 + i] = way[i];
+        }
+    }
+    out[7] = asked ? 1 : 0;
+    return KNN_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The drop-in entry point (reference core.h:71, core.cu:1282-1297 -> v8, core.cu:856-958):
+// plan the call, run its shards, exchange their keys, unpack the indices.
+// ---------------------------------------------------------------------------------------------
+extern "C" void cudaCallback(int k, int m, int n, float *searchPoints, float *referencePoints,
+                             int **results)
+{
+    if (k < 1 || m < 1 || n < 1 || !searchPoints || !referencePoints || !results)
+        DIE_IF(fail(KNN_EINVAL, "cudaCallback: k, m, n must be >= 1 and pointers non-null"));
+    const int ndev = knn_device_count();
+    // The reference computes on the CPU here (core.cu:869-870); this library has no CPU path.
+    if (ndev < 1)
+        DIE_IF(fail(KNN_ENODEV, "cudaCallback: no HIP device visible (this library has no CPU fallback)"));
+    const CallPlan plan = plan_call(k, m, n, ndev, shard_options(), knn_rccl_available);
+    const size_t shards = plan.shard.size();
+    g_last_shards = (long long)shards;
+    g_last_cells = 0;
+    static const bool trace = getenv("KNN_MI355X_TRACE_CALL") != nullptr;
+    if (trace)
+        fprintf(stderr, "[knn call] k %d m %d n %d: %d GPU(s) visible -> %zu shard(s)%s\n", k, m, n, ndev, shards,
+                plan.opt.shards > 0 ? " (option shards)" : "");
+    if (plan.refusal == 1) {
+        char why[160];
+        snprintf(why, sizeof why, "%zu shards on %d visible GPU(s): the one communicator set of the process spans all visible devices", shards, ndev);
+        DIE_IF(fail(KNN_EINVAL, "cudaCallback: option rccl = 1 but the call's shards are not the visible devices", why));
+    }
+    if (trace && shards > 1 && !plan.use_rccl)
+        fprintf(stderr, "[knn call] keys merged on the host: %s\n",
+                plan.opt.rccl == 2 ? "option rccl = 2" : shards != (size_t)ndev ? "the shards are not the visible devices" : plan.rccl_why.c_str());
+    if (plan.refusal == 2)
+        DIE_IF(fail(KNN_EHIP, "cudaCallback: option rccl = 1 but RCCL cannot be used", plan.rccl_why.c_str()));
+    std::vector<ShardKeys> keys;
+    for (const CallShard &s : plan.shard)
+        keys.emplace_back(s.device);
+    auto run_shards = [&](size_t first) {
+        for (size_t g = first; g < shards; g += (size_t)plan.threads)
+            run_call_shard(plan, g, searchPoints, referencePoints, trace, keys[g]);
+    };
+    std::vector<std::thread> pool;
+    for (int t = 0; plan.threads > 1 && t < plan.threads; ++t)
+        pool.emplace_back(run_shards, (size_t)t);
+    if (pool.empty())
+        run_shards(0);   // one thread: this one
+    for (auto &th : pool)
+        th.join();
+    int rc = KNN_OK;
+    for (size_t g = 0; g < shards && rc == KNN_OK; ++g)   // the first failed shard's error
+        if (keys[g].rc != KNN_OK)
+            rc = fail(keys[g].rc, keys[g].err.c_str());
+    std::vector<u64> merged;
+    if (rc == KNN_OK)
+        rc = exchange_keys(plan, keys, merged);
+    keys.clear();   // exit() runs no destructor of this frame: the pooled buffers go back before the call dies
+    DIE_IF(rc);
+    int *out = (int *)malloc(sizeof(int) * (size_t)m);  // caller free()s (main.cu:98,175)
+    if (!out)
+        die(__FILE__, __LINE__, KNN_ENOMEM, "malloc(results)");
+    for (int j = 0; j < m; ++j)
+        out[j] = (int)(unsigned)(merged[(size_t)j] & 0xFFFFFFFFull);
+    *results = out;
+}

@@ -516,6 +516,73 @@ def test_shard_count_policy_of_the_drop_in_on_a_faked_eight_gpu_node():
     assert pkg.get_option("rccl_comm_sets") == 0 and pkg.get_option("last_shards") == 0   # nothing has run in this process
 
 
+def test_call_plan_of_the_drop_in_shards_exchange_refusals_and_the_lazy_rccl_probe():
+    """cudaCallback decides everything once, in plan_call (knn_debug_call_plan: host arithmetic on a faked node): the shard
+    count and ranges, the host threads, the exchange step, the two refusals of option rccl = 1, and whether librccl is
+    probed at all ("probed"), and each shard's way.  The expectations are those of the single 250-line function the plan
+    replaced."""
+    _built_lib()
+    import multicore_hw2_amd as pkg
+    plan = pkg.debug_call_plan
+    host = dict(rccl=0, refusal=0)
+
+    def expect(got, **want):
+        assert {f: got[f] for f in want} == want, (got, want)
+
+    try:
+        # the TA harness' shapes: one shard on one thread, nothing to exchange, librccl never opened
+        for ndev in (1, 8):
+            for (k, m, n) in TA_SHAPES:
+                expect(plan(k, m, n, ndev), shards=1, per=n, threads=1, empty=0, last_rows=n, probed=0, **host)
+        # rccl = 1 insists on the exchange step, also for one shard on the one device
+        pkg.set_option("rccl", 1)
+        expect(plan(16, 1024, 65536, 1, rccl_usable=True), shards=1, rccl=1, refusal=0, probed=1)
+        expect(plan(16, 1024, 65536, 1, rccl_usable=False), shards=1, rccl=0, refusal=2, probed=1)
+        expect(plan(16, 1024, 65536, 8), shards=1, probed=0, **host)          # 1 shard != 8 devices; refusal 1 needs > 1 shard
+        pkg.set_option("rccl", 0)
+        # option shards: ceil(n / shards) rows each, the last takes the rest, a shard past the end is empty
+        pkg.set_option("shards", 3)
+        expect(plan(3, 5, 4, 1), shards=3, per=2, threads=1, empty=1, last_rows=2, probed=0, **host)
+        expect(plan(3, 5, 7, 1), shards=3, per=3, threads=1, empty=0, last_rows=1, probed=0, **host)
+        pkg.set_option("rccl", 1)
+        for n in (4, 7):
+            expect(plan(3, 5, n, 1), shards=3, rccl=0, refusal=1, probed=0)
+        pkg.set_option("rccl", 0)
+        pkg.set_option("shards", 8)                                            # never more shards than points
+        expect(plan(3, 5, 3, 1), shards=3, per=1, empty=0, last_rows=1, **host)
+        pkg.set_option("shards", 0)
+        # the metric's shape on eight GPUs: the policy's count, one thread per GPU, RCCL where it can be used
+        k, m, n = 16, 1024, 1 << 24
+        assert pkg.debug_shard_policy(k, m, n, 8) == 8
+        expect(plan(k, m, n, 8, rccl_usable=True), shards=8, per=n // 8, threads=8, rccl=1, refusal=0, empty=0, last_rows=n // 8,
+               probed=1)
+        expect(plan(k, m, n, 8, rccl_usable=False), shards=8, threads=8, probed=1, **host)
+        pkg.set_option("rccl", 2)
+        expect(plan(k, m, n, 8), shards=8, threads=8, probed=0, **host)
+        pkg.set_option("rccl", 0)
+        pkg.set_option("shards", 4)
+        expect(plan(k, m, n, 8), shards=4, threads=4, probed=0, **host)
+        pkg.set_option("shards", 16)
+        expect(plan(k, m, n, 8), shards=16, threads=8, probed=0, **host)
+        # each shard's way is plan_shard's for ITS rows (the plan decides it now, not the shard's thread): shard 0 and the last
+        # non-empty shard against knn_debug_plan_shard — also where the short last shard is served another way than the rest
+        pkg.set_option("shards", 0)
+        ways = [((3, 5, 7), 1, 3), ((16, 1024, 1 << 24), 8, 0), ((16, 65536, 1024 * 13000 - 1000), 1, 1024)]
+        for (k, m, n), ndev, shards in ways:
+            pkg.set_option("shards", shards)
+            got = plan(k, m, n, ndev)
+            assert got["first_way"] == pkg.debug_plan_shard(k, m, got["per"]), (k, m, n, got)
+            assert got["last_way"] == pkg.debug_plan_shard(k, m, got["last_rows"]), (k, m, n, got)
+        expect(got, shards=1024, per=13000, empty=0, last_rows=12000)
+        assert got["first_way"]["filter"] == 1 and got["last_way"]["filter"] == 0, got      # 13000 rows repay the layouts, 12000 do not
+    finally:
+        for name in ("shards", "rccl"):
+            pkg.set_option(name, 0)
+    for bad in [(0, 1, 1, 1), (1, 0, 1, 1), (1, 1, 0, 1), (1, 1, 1, 0)]:
+        vin = (ctypes.c_longlong * 5)(*bad, 1)
+        assert pkg.lib().knn_debug_call_plan(vin, (ctypes.c_longlong * 16)()) == -1, bad
+
+
 def test_rccl_entry_point_validates_its_arguments_without_a_gpu():
     """knn_keys_allreduce_min: argument errors come back as KNN_EINVAL before RCCL is touched; librccl itself
     is opened lazily (the version query either finds it or returns 0, never raises)."""

@@ -139,6 +139,9 @@ def test_sharded_callback_equals_single_shard(oracle, path):
     # more shards than points (core.cu:867-868)
     pkg.set_option("shards", 8)
     np.testing.assert_array_equal(pkg.cudaCallback(k, m, 3, Q, R[:9]), oracle.v0(k, Q, R[:9]))
+    # an empty shard in the host merge: 3 shards of ceil(4 / 3) = 2 rows are [0,2) [2,4) [4,4)
+    pkg.set_option("shards", 3)
+    np.testing.assert_array_equal(pkg.cudaCallback(k, 5, 4, Q[:15], R[:12]), oracle.v0(k, Q[:15], R[:12]))
     pkg.set_option("shards", 0)
 
 
