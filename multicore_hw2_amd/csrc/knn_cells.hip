@@ -257,7 +257,12 @@ __global__ __launch_bounds__(256) void knn_cells_scatter_frag2_kernel(
             vmax = 0.0f;
             nrm = 0.0f;
         }
-        if (k <= KNN_NIF_MAX_K) {   // the norm's two fp16 halves in the free K-slots 30, 31 (see cell_tile_step_nif); a row that is out: a score no threshold passes
+        // the norm's two fp16 halves in the free K-slots 30, 31 (see cell_tile_step_nif).  A row that is out scores the finite 65504:
+        // above the threshold of any query near the box, but NOT of one near kAmaxLimit (N + 2|q.r| alone reaches ~61 000 at
+        // k = 30).  Such a position then becomes a record: the 1-NN re-rank evaluates the row exactly (it is in the exact list as
+        // well; the same key folds twice), the top-K re-rank skips it (the outlier kernel has it), and a batch whose slices flood
+        // with them ends in the exact evaluation of its listed pairs — tests/test_filter_margin_gpu.py walks queries up to there.
+        if (k <= KNN_NIF_MAX_K) {
             const unsigned nw = real ? pack_norm22(nrm) : 0x00007BFFu;   // (65504, 0)
             v[3][6] = __builtin_bit_cast(_Float16, (unsigned short)(nw & 0xFFFFu));
             v[3][7] = __builtin_bit_cast(_Float16, (unsigned short)(nw >> 16));
@@ -832,7 +837,9 @@ __global__ __launch_bounds__(256) void knn_cells_pad_kernel(const unsigned *__re
     if (pos < end) {
         for (int t = 0; t < 2 * kt; ++t) {   // (kt K-steps x two halves of 32 lanes)
             h8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-            if (nif && t == 3)   // (kt = 2, k <= 30: K-slot 30 carries the norm — a padding row's: 65504, above every threshold)
+            // (kt = 2, k <= 30: K-slot 30 carries the norm — a padding row's: the finite 65504.  A query near kAmaxLimit can have a
+            // threshold above it; the position is then a record that the re-rank ignores, perm = ~0: see knn_cells_scatter_frag2_kernel's note)
+            if (nif && t == 3)
                 z[6] = __builtin_bit_cast(_Float16, (unsigned short)0x7BFFu);
             frag[(pos >> 5) * 64 * kt + t * 32 + (pos & 31)] = z;
         }
