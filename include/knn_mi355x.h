@@ -213,7 +213,8 @@ int knn_index_query_host(knn_index *idx, int m, const float *queries_host, int *
  * (a query nothing bounds, fewer than K sampled blocks with a real row, more candidates than the buffers hold) raises [2] = 1
  * and is answered by the exact top-K scan; [1] = records re-ranked.  1 = the exact top-K scan (v0 arithmetic over every
  * row): per-cell frames (centred or 8-bit rows), grid indexes, cell-range shards, shards or batches below the filter's sizes.
- * 3 = the grid index, only for calls that carry KNN_QUERY_TOPK_GRID (below).
+ * 3 = the grid index, only for calls that carry KNN_QUERY_TOPK_GRID (below).  4 = the cell-pruned top-K (option "topk_cells");
+ * on per-cell frames only for calls that carry KNN_QUERY_TOPK_FRAMES (below).
  * Results are bit-exact either way.
  * Any K outside 1 .. 64, or m < 1, is KNN_EINVAL (knn_last_error says why) and launches nothing.
  *
@@ -244,6 +245,18 @@ int knn_index_query_host(knn_index *idx, int m, const float *queries_host, int *
  * own once it is measured against the exact top-K scan: the policy sends a call to a path only where it is measured faster than
  * the one it replaces (tools/grid_topk_timing.py takes those measurements). */
 #define KNN_QUERY_TOPK_GRID 4u
+/* KNN_QUERY_TOPK_FRAMES (knn_index_query_topk only; the 1-NN entry points reject it): a cell-sorted layout in per-cell frames may
+ * answer this top-K call with the cell-pruned scan.  With the flag AND option "topk_cells" = 1, a call on a resident, non-sharded
+ * index whose cell-sorted layout has per-cell frames — fp16 rows centred per cell ("cells_centre"), or 8-bit rows in each cell's
+ * own frame ("cells_rows" 2 with "cells_u8_frame" 1); k <= 16 — takes the cell-pruned top-K (knn_index_last_stats [0] = 4) under
+ * that path's call conditions: m >= 5, room for >= 64 candidate keys per query, out-of-box rows at most half that room, option
+ * "path" 0 or 2.  Its bound is the K-th smallest of the FRAME-FREE distance bounds the seed cells' K smallest scores imply, each
+ * through its own cell's constants ("Per-cell frames").  [1], [2] and [3] mean what they mean on the pruned top-K of
+ * the one-frame layouts; folding, passes of 1024 queries, slots and indices_dev are unchanged.  On any other index, option or
+ * path the flag is accepted and changes nothing, and without it every call goes exactly where it went before: per-cell frames
+ * then take the exact top-K scan whatever "topk_cells" says.  Results are bit-identical either way.  On request: it has
+ * not been measured against the exact top-K scan yet. */
+#define KNN_QUERY_TOPK_FRAMES 8u
 /* keys_dev [m][K]; indices_dev [m][K] or NULL: the int32 indices, unpacked after the fold.  Slot rules as knn_index_query:
  * eight workspaces, calls sharing one must be stream-ordered; asynchronous on `stream`. */
 int knn_index_query_topk(knn_index *idx, int slot, int m, int K, const float *queries_dev, unsigned long long *keys_dev,
@@ -327,10 +340,11 @@ int knn_index_query_topk_host(knn_index *idx, int m, int K, const float *queries
  *             frame, 0 = auto (bins where they fit the cells — uniform-like rows —, per-cell frames on clustered data).  Read when
  *             an index is built; results are identical either way.  knn_get_option("cells_u8_bin_builds") counts the layouts built
  *             with bin frames (read-only).  Top-K queries: bin frames can take the cell-pruned scan ("topk_cells"), per-cell
- *             frames take the exact top-K scan.
+ *             frames take the exact top-K scan unless the call carries KNN_QUERY_TOPK_FRAMES (2c).
  *   "topk_cells" top-K queries (knn_index_query_topk) on the cell-pruned scan, for cell-sorted layouts in the shard's one frame
  *             (fp16 rows without per-cell frames, 8-bit rows in bin frames; k <= 32, m >= 5; a cell-range shard only for calls
- *             that carry KNN_QUERY_TOPK_PARTIAL, and only under 1):
+ *             that carry KNN_QUERY_TOPK_PARTIAL, and only under 1; a layout in per-cell frames, k <= 16, only for calls that carry
+ *             KNN_QUERY_TOPK_FRAMES, and only under 1 — without the flag per-cell frames take the exact top-K scan):
  *             0 = library policy: for now the same as 2 — the policy sends a call to this path only where it is measured faster
  *             than the path it replaces, and those measurements are not taken yet (it will start at the row count from which the
  *             library builds the cell-sorted layout on its own for that k);
@@ -422,7 +436,8 @@ int knn_debug_scan_plan_ex(int num_cu, int blocks_per_cu, unsigned nitems, int m
 int knn_debug_cells_query_plan(const long long in[14], long long out[28]);
 /* Test hook (host arithmetic only, no GPU needed): whether a top-K call takes the cell-pruned scan and what one of its passes
  * launches with.  in = {k, K, m (the call's queries), rows of the shard, option topk_cells, 1 if a cell-sorted layout exists,
- * centred, rows_u8, 1 if the 8-bit rows are in bin frames, 1 for a cell-range shard (2: and the call carries
+ * centred (1: per-cell frames; 2: per-cell frames and the call carries KNN_QUERY_TOPK_FRAMES — with 8-bit rows in bin frames, which
+ * are never centred, 2 means the flag alone), rows_u8, 1 if the 8-bit rows are in bin frames, 1 for a cell-range shard (2: and the call carries
  * KNN_QUERY_TOPK_PARTIAL), out-of-box rows, ncells, nitems, cap,
  * several_slots, scan_blocks, scan_deal, num_cu, rec_cap, option cells};
  * out = {1 if pruned; prep: PW, KT, CTR; match: waves, stage; the record-only scan's form: DYN, KT, NIF, U8, SELF, CTR; its grid:
@@ -439,6 +454,12 @@ int knn_debug_seed_kth(const float *seed, int nseed, const float *wide, int nwid
  * norm mq: out = {the score threshold, Dup (the largest scaled squared distance a candidate can have, fp32 rounded up), the
  * distance gate of the top-K re-rank: the largest v0 distance (rows' own units) a row of the top-K can have}.  0 on success. */
 int knn_debug_topk_gate(int k, float sigma, double amax, double bmax, double nmax, double u, double mq, double out[3]);
+/* Test hook (host arithmetic, no GPU): what the per-cell-frame top-K form of the preparation kernel makes of one seed score
+ * (knn_frame_dup.h: the kernel runs the same lines).  frame = {the cell's centre [16], scale, ratio = scale / sigma (a power of
+ * two), largest |fp16 row coordinate|, largest row norm} (KNN_CELL_FRAME_WORDS = 20 floats), query_row = k floats, u = a finite
+ * seed score of that cell (the far branch takes any finite value): out = {Dup — the bound on that row's real squared distance in
+ * the SHARD's scaled units, fp32 rounded up, +INF when nothing bounds it; 1 if the query does not fit the frame (far branch)}. */
+int knn_debug_frame_dup(int k, const float frame[20], const float *query_row, float u, float out[2]);
 /* Test hook (host arithmetic only, no GPU needed): every choice and size one batch of the dense filter query launches with.
  * in = {kt, ntiles, m, num_cu, rec_cap, K (0 = 1-NN), and the options filter_qt, filter_rounds, filter_chain, run_thresholds,
  * sample_stride};

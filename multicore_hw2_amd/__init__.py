@@ -32,10 +32,12 @@ EXPORTED_SYMBOLS = [
     "knn_geom_create", "knn_geom_destroy", "knn_geom_info", "knn_geom_assign", "knn_index_create_sharded",
     "knn_index_seed_export", "knn_index_seed_attach", "knn_geom_first_cell",
     "knn_index_query_topk", "knn_keys_topk_merge", "knn_index_query_topk_host", "knn_debug_grid_topk_plan",
+    "knn_debug_frame_dup",
 ]
 QUERY_INIT_KEYS = 1   # KNN_QUERY_INIT_KEYS
 QUERY_TOPK_PARTIAL = 2   # KNN_QUERY_TOPK_PARTIAL
 QUERY_TOPK_GRID = 4   # KNN_QUERY_TOPK_GRID
+QUERY_TOPK_FRAMES = 8   # KNN_QUERY_TOPK_FRAMES
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # KNN_MI355X_LIB: A/B hook — load another build of the same C-ABI (e.g. a previous commit's .so)
@@ -206,6 +208,24 @@ def debug_topk_gate(k, sigma, amax, bmax, nmax, u, mq):
     return tuple(out)
 
 
+CELL_FRAME_WORDS = 20   # KNN_CELL_FRAME_WORDS: a cell's centre [16], scale, ratio, bmax, nmax
+
+
+def debug_frame_dup(k, frame, query_row, u):
+    """knn_debug_frame_dup: (Dup, far) — the frame-free bound, in the shard's scaled units, that the per-cell-frame top-K form of
+    the preparation kernel makes of seed score u of a cell with this frame for this query row, and whether the query does not fit
+    the frame (the far branch).  Host arithmetic, the kernel's own lines (knn_frame_dup.h); works without a GPU."""
+    fr = np.ascontiguousarray(frame, dtype=np.float32).reshape(-1)
+    q = np.ascontiguousarray(query_row, dtype=np.float32).reshape(-1)
+    if fr.size != CELL_FRAME_WORDS or q.size < int(k):
+        raise KnnError("debug_frame_dup: frame of %d floats and a query row of k floats" % CELL_FRAME_WORDS)
+    out = (ctypes.c_float * 2)()
+    f = lib().knn_debug_frame_dup
+    f.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.POINTER(ctypes.c_float)]
+    _check(f(int(k), fr.ctypes.data, q.ctypes.data, float(u), out))
+    return float(out[0]), bool(out[1])
+
+
 FILTER_QUERY_INPUTS = ("kt", "ntiles", "m", "num_cu", "rec_cap", "topk", "filter_qt", "filter_rounds", "filter_chain",
                        "run_thresholds", "sample_stride")
 FILTER_QUERY_PLAN = ("ok", "form", "kt", "npieces", "nlists", "slice", "stride", "sample_blocks", "umin_floats", "topk", "thr_nb",
@@ -236,8 +256,8 @@ WAY_EXACT, WAY_FILTER, WAY_GRID, WAY_CELLS = 1, 2, 3, 4   # last_stats()[0]
 
 def debug_query_route(**inputs):
     """knn_debug_query_route: which path answers a call (last_stats()[0]) for the inputs named in QUERY_ROUTE_INPUTS — K = 0: a
-    1-NN call; sharded: 0, 1, or 2 (a cell-range shard whose call carries KNN_QUERY_TOPK_PARTIAL).  Host arithmetic; works
-    without a GPU."""
+    1-NN call; sharded: 0, 1, or 2 (a cell-range shard whose call carries KNN_QUERY_TOPK_PARTIAL); centred: 0, 1, or 2 (per-cell
+    frames and the call carries KNN_QUERY_TOPK_FRAMES).  Host arithmetic; works without a GPU."""
     vin = (ctypes.c_longlong * len(QUERY_ROUTE_INPUTS))(*[int(inputs[n]) for n in QUERY_ROUTE_INPUTS])
     out = (ctypes.c_longlong * len(QUERY_ROUTE))()
     f = lib().knn_debug_query_route
@@ -461,19 +481,21 @@ class KnnIndex:
         return out
 
     def query_topk(self, m, K, queries_dev, keys_dev, stream=0, slot=0, init_keys=False, indices_dev=None, partial=False,
-                   grid=False):
+                   grid=False, frames=False):
         """Async (knn_index_query_topk): keys_dev[m][K] <- the K smallest (distance, global index) keys of (this shard's rows
         and, unless init_keys, the K sorted keys per query keys_dev already holds), sorted.  indices_dev: also the int32
         indices [m][K].  partial (KNN_QUERY_TOPK_PARTIAL): the caller merges every shard's lists, so this shard need only
         report the rows that can belong to the global top-K — what lets a cell-range shard take the cell-pruned scan
         (option topk_cells = 1); see include/knn_mi355x.h, 2c, for the contract.  grid (KNN_QUERY_TOPK_GRID): an index that
-        has a grid index answers the call with it (last_stats()[0] == 3); on any other index the flag changes nothing."""
+        has a grid index answers the call with it (last_stats()[0] == 3); on any other index the flag changes nothing.
+        frames (KNN_QUERY_TOPK_FRAMES): a cell-sorted layout in per-cell frames answers the call with the cell-pruned top-K
+        (last_stats()[0] == 4) under option topk_cells = 1; on any other index or option the flag changes nothing."""
         _check(lib().knn_index_query_topk(self._h, int(slot), int(m), int(K), ctypes.c_void_p(int(queries_dev)),
                                           ctypes.c_void_p(int(keys_dev)),
                                           ctypes.c_void_p(int(indices_dev)) if indices_dev is not None else None,
                                           ctypes.c_void_p(stream),
                                           (QUERY_INIT_KEYS if init_keys else 0) | (QUERY_TOPK_PARTIAL if partial else 0) |
-                                          (QUERY_TOPK_GRID if grid else 0)))
+                                          (QUERY_TOPK_GRID if grid else 0) | (QUERY_TOPK_FRAMES if frames else 0)))
 
     def query_topk_host(self, queries, K):
         """Synchronous top-K of this shard alone: (indices int32 [m][K], dist2 float32 [m][K])."""

@@ -866,7 +866,7 @@ QueryRoute knn_query_route(const QueryRouteInputs &in)
     }
     // Top-K: the cell-pruned top-K where knn_cells_topk_plan takes the call; else the MFMA filter for the dense
     // layouts and for a cell-sorted fp16 layout in the shard's frame (scanned in full), under the 1-NN rule's options and sizes;
-    // exact top-K for per-cell frames (centred), 8-bit rows the plan declines, grid indexes (unless the call carries
+    // exact top-K for per-cell frames (centred) the plan declines (it takes them only with KNN_QUERY_TOPK_FRAMES), 8-bit rows it declines, grid indexes (unless the call carries
     // KNN_QUERY_TOPK_GRID: then the grid's own top-K, DESIGN §4.6 "Grid top-K"), cell-range shards whose call does not
     // carry KNN_QUERY_TOPK_PARTIAL (the pruned form's lists are not the shard's own top-K: include/knn_mi355x.h §2c), tiny
     // shards, few queries, and outlier lists longer than half a query's candidate room.
@@ -905,6 +905,7 @@ QueryRouteInputs route_inputs(const knn_index *idx, int m, int K, unsigned flags
     t.cells_option = (int)g_opt_cells;
     t.sharded = idx->sharded;
     t.shard_partial = idx->sharded && (flags & KNN_QUERY_TOPK_PARTIAL) != 0u;
+    t.frames_flag = K > 0 && (flags & KNN_QUERY_TOPK_FRAMES) != 0u;
     t.n_outliers = f.n_outliers;
     in.filter_usable = f.usable;
     in.has_grid = idx->grid != nullptr;
@@ -1068,7 +1069,7 @@ int knn_index_query_topk(knn_index *idx, int slot, int m, int K, const float *qu
                          int *indices_dev, void *stream, unsigned flags)
 {
     if (!idx || m < 1 || K < 1 || K > KNN_TOPK_MAX || (long long)m * K > INT_MAX || slot < 0 || slot >= KNN_SLOTS ||
-        !queries_dev || !keys_dev || (flags & ~(unsigned)(KNN_QUERY_INIT_KEYS | KNN_QUERY_TOPK_PARTIAL | KNN_QUERY_TOPK_GRID)) != 0u)
+        !queries_dev || !keys_dev || (flags & ~(unsigned)(KNN_QUERY_INIT_KEYS | KNN_QUERY_TOPK_PARTIAL | KNN_QUERY_TOPK_GRID | KNN_QUERY_TOPK_FRAMES)) != 0u)
         return fail(KNN_EINVAL, "knn_index_query_topk: bad arguments (1 <= K <= 64, m >= 1, slot 0 .. 7)");
     std::lock_guard<std::recursive_mutex> lock(idx->mu);
     DeviceGuard guard(idx->device);
@@ -1125,7 +1126,8 @@ int knn_index_query_topk(knn_index *idx, int slot, int m, int K, const float *qu
     unsigned *ccount = route.way != QueryWay::Exact ? (unsigned *)(cand + (size_t)m * route.ccap) : nullptr;
     switch (route.way) {
     case QueryWay::Cells:
-        // layouts in the shard's frame, in passes of KNN_CELL_BATCH queries (option `topk_cells`)
+        // layouts in the shard's frame — or, with KNN_QUERY_TOPK_FRAMES, in per-cell frames —, in passes of KNN_CELL_BATCH queries
+        // (option `topk_cells`)
         HIP_TRY(knn_filter_query_topk_cells(idx->filter, tp, slot, m, K, queries_dev, idx->refs, idx->base, keys, init != 0, cand, ccount,
                                             part, part_bytes, idx->num_cu, s, ev0, ev1));
         break;
@@ -1343,9 +1345,12 @@ CellTopkInputs topk_inputs_of(const long long in[20])
     ti.n = in[3];
     ti.topk_cells = (int)in[4];
     ti.has_cells = in[5] != 0;
-    ti.q.centred = in[6] != 0;
     ti.q.rows_u8 = in[7] != 0;
     ti.bins = in[8] != 0;
+    // centred: 1 = per-cell frames; 2 = per-cell frames and the call carries KNN_QUERY_TOPK_FRAMES (as `sharded` = 2 is a shard whose
+    // call carries its flag).  Bin frames are the shard's one frame: 2 there is the flag alone, which changes nothing.
+    ti.frames_flag = in[6] == 2;
+    ti.q.centred = in[6] != 0 && !(in[6] == 2 && ti.q.rows_u8 && ti.bins);
     ti.sharded = in[9] != 0;
     ti.shard_partial = in[9] == 2;
     ti.n_outliers = (unsigned)in[10];

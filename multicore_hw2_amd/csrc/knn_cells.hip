@@ -5,6 +5,7 @@
 #include "knn_filter_dev.h"
 #include "knn_exact_dev.h"
 #include "knn_seed_kth.h"
+#include "knn_frame_dup.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -1080,6 +1081,7 @@ __device__ __forceinline__ u64 cell_tile_step_nif(const h8 (&a)[KT], const h8 (&
 // |coordinate| a query may have in a cell's frame: twice that must stay an fp16 number (the B operand is -2 x the query); the
 // bounds do not mind the size — every error term is relative to the pair's own amax (64 box half-widths at the largest scale).
 #define CELL_FRAME_AMAX 16384.0f
+static_assert(CELL_FRAME_AMAX == KNN_FRAME_AMAX, "knn_frame_dup.h restates the frame's limit");
 
 // The centred scan's B operand and threshold for one (query, cell) pair (per-cell frames, knn_cells_recentre): lane = (query
 // of the block, half of the dimensions).  The query is rounded in the CELL's frame exactly as knn_cells_prep_kernel rounds it
@@ -1180,11 +1182,12 @@ struct SeedLayer {
 // CTR: per-cell frames (knn_cells_recentre; KT = 1, no seed layer): every seed cell is scored with the query rounded in THAT
 //     cell's frame, each gives its own bound Dup (frame-free: a squared distance) and the smallest stands; thr[q] = an upper
 //     bound of sqrt(Dup_q) — what the centred scan's per-pair thresholds start from — instead of a score threshold
-// TK: a top-K batch (knn_cells_query_topk; not with CTR): u = the K-th smallest (K arrives in lo_by_entry) finite score among the scored
+// TK: a top-K batch (knn_cells_query_topk): u = the K-th smallest (K arrives in lo_by_entry) finite score among the scored
 //     rows instead of the smallest — knn_seed_kth.h has the rule, the argument and the mechanism; thr_q and Dup_q come from it
 //     through the same lines below.  keys_init is null there (the select kernel starts or folds the m x K keys).  On a cell-range
 //     shard (KNN_QUERY_TOPK_PARTIAL) the scored rows include other ranks' rows from the seed layer: u is then a bound over the GLOBAL
 //     set, under bmax / nmax taken over all ranks' parts (knn_index_seed_attach) exactly as the 1-NN form's — DESIGN §6.1.
+//     With CTR (KNN_QUERY_TOPK_FRAMES): the K-th smallest of the frame-free bounds Dup_c(u) instead — the `CTR && TK` branch below.
 template <int PW, int SD, int KT = 1, bool CTR = false, bool TK = false>
 __global__ __launch_bounds__(64 * PW, KT == 1 && !CTR ? 4 : 3) void knn_cells_prep_kernel(   // (4 waves per SIMD: a batch of 1024 queries is resident at once)
     const float *__restrict__ Q, int m, int m_padded, CellGeom g, const float *__restrict__ bounds, double sigma2,
@@ -1199,7 +1202,6 @@ __global__ __launch_bounds__(64 * PW, KT == 1 && !CTR ? 4 : 3) void knn_cells_pr
     const float *__restrict__ frame, const unsigned *__restrict__ tile_cell)   // CTR only
 {
 #pragma clang fp contract(off)
-    static_assert(!(TK && CTR), "the K-th seed bound is derived for layouts in the shard's frame");
     constexpr int SEEDS = 1 << SD, NS = SEEDS / PW;   // seed cells in all, per wave
     // seed tiles a wave requests at once (KT KiB each); TK: fewer — the selection network's registers come on top of the tiles in
     // flight, and the form must stay within its 1-NN twin's registers without scratch (a top-K call is worth milliseconds: the
@@ -1474,7 +1476,135 @@ __global__ __launch_bounds__(64 * PW, KT == 1 && !CTR ? 4 : 3) void knn_cells_pr
                 }
         }
     };
-    if constexpr (CTR) {
+    if constexpr (CTR && TK) {
+        // A top-K batch on per-cell frames (KNN_QUERY_TOPK_FRAMES; DESIGN §4.6 "Per-cell frames", knn_frame_dup.h): scores of cells in
+        // different frames do not compare, the frame-free bounds they imply do.  Per seed cell: the query rounded in the cell's frame,
+        // the K smallest finite per-row scores of its (sampled) tiles by knn_seed_kth.h's selection, each converted to Dup_c(u) in the
+        // shard's units — lane t converts list entry t; Dup_c is non-decreasing in u, so the list stays sorted — and, as keys, merged
+        // across the wave's cells, then across the block's waves.  Dup_(K), the K-th smallest, bounds the K-th smallest true distance:
+        // K finite scores of distinct positions are K distinct real in-box rows, each within its own Dup_c(u) <= Dup_(K).  The far
+        // branch gives every finite position of the cell the triangle inequality's bound.  Fewer than K: the 64 tiles spread over
+        // the layout, each in its own cell's frame, minus those inside a seed cell; still fewer: +INF, FALLBACK.
+        const int topk = lo_by_entry;
+        unsigned v_tb = 0u, v_own = 0u;   // the tiles of the layout seed cell `lane` stands for (the wide sample leaves them out)
+        {
+            const unsigned l = code - g.cell_base;
+            if (ok && code >= g.cell_base && l < g.ncells) {
+                v_tb = tile_start[l];
+                v_own = v_nt;
+            }
+        }
+        // (The tile walk — request PREP_TILES tiles, norm MFMA + score MFMA, lane select — exists three times in this kernel: score_runs,
+        // score_runs_tk and here; each form's text is kept apart so that the others compile as they did.  A change to the seed
+        // scoring goes into all three.)
+        // fv: the cell's frame, word w on lane w -> the cell's 64 smallest Dup keys, ascending over the lanes (cnt0 tiles f0 + v
+        // stride0 KiB, norm words n0 + v stride0 128 B; all wave-uniform)
+        auto cell_dups = [&](float fv, unsigned long long f0, unsigned long long n0, unsigned cnt0,
+                             unsigned stride0) __attribute__((always_inline)) -> unsigned {
+            float fr[KNN_CELL_FRAME_WORDS];
+#pragma unroll
+            for (int w_ = 0; w_ < KNN_CELL_FRAME_WORDS; ++w_)
+                fr[w_] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, fv), w_));
+            _Float16 bv[16];
+            const KnnFrameQuery fq = knn_frame_query(g.k, fr, qrow, bv);
+            h8 bqc;
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                bqc[j] = half ? bv[8 + j] : bv[j];
+            unsigned cur = KNN_SEED_NONE;
+            for (unsigned v0 = 0u; v0 < cnt0; v0 += PREP_TILES) {
+                h8 ar[PREP_TILES];
+                unsigned nw[PREP_TILES];
+                unsigned sel[PREP_TILES];   // the tiles' score keys, one per lane
+#pragma unroll
+                for (int p = 0; p < PREP_TILES; ++p) {
+                    nw[p] = 0u;
+                    if (v0 + (unsigned)p < cnt0) {
+                        const size_t t = (size_t)(v0 + (unsigned)p) * stride0;
+                        ar[p] = ((const h8 *)f0)[t * 64 + lane];
+                        if (lane < 32)
+                            nw[p] = ((const unsigned *)n0)[t * 32 + lane];
+                    }
+                }
+#pragma unroll
+                for (int p = 0; p < PREP_TILES; ++p)
+                    if (v0 + (unsigned)p < cnt0) {
+                        f16v d = __builtin_amdgcn_mfma_f32_32x32x16_f16(norm_a_operand(nw[p]), norm_b_operand(), zero_acc(), 0, 0, 0);
+                        d = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[p], bqc, d, 0, 0, 0);
+                        float sc = d[0];
+#pragma unroll
+                        for (int i = 1; i < 16; ++i)
+                            sc = (lane & 15) == i ? d[i] : sc;
+                        sel[p] = knn_seed_lane_holds_row(lane) ? knn_seed_key(sc) : KNN_SEED_NONE;
+                    }
+#pragma unroll
+                for (int p = 0; p < PREP_TILES; ++p)
+                    if (v0 + (unsigned)p < cnt0) {
+                        const unsigned kth = (unsigned)__shfl((int)cur, topk - 1, KNN_WAVE);
+                        if (__ballot(sel[p] < kth) != 0ull)   // wave-uniform: a tile with nothing below the K-th changes nothing
+                            cur = seed_merge64(cur, seed_sort64(sel[p], lane), lane);
+                    }
+            }
+            const float s = knn_seed_score(cur);   // lane t: list entry t (+INF: none)
+            return knn_seed_key(s < INFINITY ? knn_frame_dup(g.k, fr[16], fr[17], fr[18], fr[19], fq, s) : INFINITY);
+        };
+        unsigned cur = KNN_SEED_NONE;
+#pragma unroll
+        for (int c = 0; c < NS; ++c) {   // this wave's seed cells
+            const int sl = wib + PW * c;
+            const unsigned nt = (unsigned)__builtin_amdgcn_readlane((int)v_nt, sl);
+            if (nt != 0u) {   // wave-uniform
+                const unsigned long long f0 = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v_fa >> 32), sl) << 32) |
+                                              (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)v_fa, sl);
+                const unsigned long long n0 = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v_na >> 32), sl) << 32) |
+                                              (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)v_na, sl);
+                // a fat cell: the per-cell-frame form's strided sample (strided positions are distinct)
+                const unsigned scap = min(CELL_SEED_MAX_TILES_CTR, max(CELL_SEED_MAX_TILES, (nt * 9u) >> 9));
+                const unsigned st0 = (nt + scap - 1u) / scap;
+                cur = seed_merge64(cur, cell_dups(fv_seed[c], f0, n0, (nt + st0 - 1u) / st0, st0), lane);
+            }
+        }
+        // the block's K-th smallest: every wave merges all the waves' lists (the same value everywhere: block-uniform below)
+        __shared__ unsigned s_topf[PW][64];
+        s_topf[wib][lane] = cur;
+        __syncthreads();
+        unsigned all = s_topf[0][lane];
+#pragma unroll
+        for (int i = 1; i < PW; ++i)
+            all = seed_merge64(all, s_topf[i][lane], lane);
+        if ((unsigned)__shfl((int)all, topk - 1, KNN_WAVE) == KNN_SEED_NONE && ntiles > 0) {   // block-uniform
+            __syncthreads();   // s_topf has been read by everybody
+            const unsigned total = (unsigned)(ntiles > 64 ? 64 : ntiles);
+            const unsigned wstride = (unsigned)(ntiles > 64 ? ntiles / 64 : 1);
+            cur = KNN_SEED_NONE;
+            for (unsigned i = (unsigned)wib * (64u / PW); i < min(((unsigned)wib + 1u) * (64u / PW), total); ++i) {
+                const unsigned t = i * wstride;
+                if (__ballot(lane < SEEDS && v_own != 0u && t >= v_tb && t - v_tb < v_own) != 0ull)   // inside a seed cell: counted already
+                    continue;
+                const float fv = lane < KNN_CELL_FRAME_WORDS ? frame[(size_t)tile_cell[t] * KNN_CELL_FRAME_WORDS + lane] : 0.0f;
+                cur = seed_merge64(cur, cell_dups(fv, (unsigned long long)(rf + (size_t)t * 64), (unsigned long long)(rn2 + (size_t)t * 32), 1u, 1u),
+                                   lane);
+            }
+            s_topf[wib][lane] = cur;
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < PW; ++i)
+                all = seed_merge64(all, s_topf[i][lane], lane);
+            if (tid == 0)
+                atomicAdd(&ctl[KNN_CTL_WIDE_SEEDS], 1u);   // rare; statistics only
+        }
+        const float u = knn_seed_score((unsigned)__shfl((int)all, topk - 1, KNN_WAVE));   // Dup_(K), the shard's units
+        if (tid == 0) {
+            const bool bad = qbad || !(amax <= amax_limit) || !(u < INFINITY);
+            float sq = sqrtf(u);
+            sq = nextafterf(nextafterf(sq, INFINITY), INFINITY);
+            thr[qi] = bad ? -INFINITY : sq;
+            dup_out[qi] = bad ? -INFINITY : u;
+            if (bad)
+                ctl[KNN_CTL_FALLBACK] = 1u;  // benign race: every writer stores 1
+        }
+        return;
+    } else if constexpr (CTR) {
         // One seed cell (or sampled tile) at a time: the query rounded in the cell's frame — what knn_frag_kernel would write
         // for it with (centre_c, scale_c) —, the cell's tiles scored against it, the bound on the answer's distance they give
         // in the SHARD's scaled units (the two frames differ by the power of two frame[17]).  All lanes do all of it.
@@ -1530,23 +1660,12 @@ __global__ __launch_bounds__(64 * PW, KT == 1 && !CTR ? 4 : 3) void knn_cells_pr
                 um = fminf(um, __shfl_xor(um, off, KNN_WAVE));
             if (!(um < INFINITY))
                 return INFINITY;
-            const BoundConsts cst = knn_bound_consts(g.k, 1, scale, far ? 0.0f : amaxc, fr[18], fr[19]);
-            double dup = 0.0;
-            if (far) {
-                const double reach = sqrt((double)n32) * (1.0 + 1e-6) + sqrt((double)g.k) * (double)fr[18] * 1.001 + 0.001;
-                dup = reach * reach * (1.0 + 1e-5) * (1.0 + cst.g2) * (1.0 + cst.g2) + cst.sigma2 * cst.tau;
-                if (!(dup < 1e300))
-                    return INFINITY;
-            } else {
-                const float t = knn_threshold(cst, um, nrmc, &dup);
-                if (!(t < INFINITY))
-                    return INFINITY;
-            }
-            dup = dup / ((double)ratio * (double)ratio) * (1.0 + 1e-6);
-            float df = (float)dup;
-            if ((double)df < dup)
-                df = nextafterf(df, INFINITY);
-            return df;
+            KnnFrameQuery fq;
+            fq.amax = amaxc;
+            fq.nrm = nrmc;
+            fq.n32 = n32;
+            fq.far = far;
+            return knn_frame_dup(g.k, scale, ratio, fr[18], fr[19], fq, um);
         };
         float best = INFINITY;
 #pragma unroll
@@ -1935,6 +2054,26 @@ __global__ __launch_bounds__(64 * (KT == 1 ? CELL_SCAN_WAVES : CELL_SCAN_WAVES_K
     constexpr int K = 0;
     const float *const Q = nullptr;   // (read by the per-cell-frame fill only: a form this kernel does not have)
 #define KNN_CELLS_SCAN_RECORD_ONLY   // the body without the 1-NN epilogue (inline re-rank, finalisation) and what only that reads
+#include "knn_cells_scan_body.inc"
+#undef KNN_CELLS_SCAN_RECORD_ONLY
+}
+
+// The record-only scan of a top-K pass on per-cell frames (KNN_QUERY_TOPK_FRAMES): the body with TOPK = true and CTR = true — the B
+// operand and the threshold of a (query, cell) pair made from the fp32 query rows, the cell's frame and the prep kernel's
+// Dup_(K) / sqrt(Dup_(K)), exactly as the 1-NN per-cell-frame scan makes them from its Dup.  fp16 rows with both item deals, the
+// 8-bit per-cell rows with the counter deal; block shape and register cap of knn_cells_scan_kernel<DYN, 0, false, 1, true, false, U8>.
+template <bool DYN, bool U8>
+__global__ __launch_bounds__(64 * CELL_SCAN_WAVES_KT2, 4) void knn_cells_frame_records_kernel(
+    const h8 *__restrict__ rf, const float *__restrict__ rn, const u64 *__restrict__ items, unsigned nitems,
+    const h8 *__restrict__ qfg, const float *__restrict__ thrg, int m, int m_padded,
+    const unsigned *__restrict__ cell_counts, const unsigned short *__restrict__ lists, unsigned cap,
+    u64 *__restrict__ rec, unsigned *__restrict__ counts, unsigned *__restrict__ ctl, unsigned slice,
+    unsigned ovf_base, unsigned ovf_cap, const float *__restrict__ Q, int krt, CellSelf self)
+{
+#pragma clang fp contract(off)
+    constexpr bool TOPK = true, SELF = false, CTR = true, NIF = false;
+    constexpr int K = 0, KT = 1;
+#define KNN_CELLS_SCAN_RECORD_ONLY
 #include "knn_cells_scan_body.inc"
 #undef KNN_CELLS_SCAN_RECORD_ONLY
 }
@@ -3164,10 +3303,23 @@ static void cells_prep_topk_as(const CellBatch &b)
                        st.nmax, kAmaxLimit, b.w.thr, b.w.dup, b.w.ctl_cur, b.ctl_next, b.w.counts, b.w.nlists, (u64 *)nullptr,
                        b.topk, (const float *)nullptr, (const unsigned *)nullptr);
 }
+// ... on per-cell frames: the K-th smallest frame-free bound (knn_frame_dup.h)
+template <int PW>
+static void cells_prep_topk_frames_as(const CellBatch &b)
+{
+    const FilterState &st = b.st;
+    hipLaunchKernelGGL((knn_cells_prep_kernel<PW, 2, 1, true, true>), dim3((unsigned)b.m_padded), dim3(64 * PW), 0, b.s, b.q, b.m, b.m_padded,
+                       cell_geom_of(b.c, st.k), b.c.bounds, (double)st.sigma * (double)st.sigma, st.center, st.sigma, b.c.tile_start,
+                       st.ntiles, (const h8 *)st.ref_frags, st.ref_norms2, b.layer, (h8 *)b.w.qry_frags, b.w.lo_tab, b.w.hi_tab, st.bmax,
+                       st.nmax, kAmaxLimit, b.w.thr, b.w.dup, b.w.ctl_cur, b.ctl_next, b.w.counts, b.w.nlists, (u64 *)nullptr,
+                       b.topk, b.c.cell_frame, b.c.tile_cell);
+}
 static void cells_prep_topk_launch(const CellBatch &b)
 {
     const bool two = b.p.prep_pw == 2;
-    if (b.p.prep_kt == 2)
+    if (b.p.prep_ctr)
+        (two ? cells_prep_topk_frames_as<2> : cells_prep_topk_frames_as<4>)(b);
+    else if (b.p.prep_kt == 2)
         (two ? cells_prep_topk_as<2, 2> : cells_prep_topk_as<4, 2>)(b);
     else
         (two ? cells_prep_topk_as<2, 1> : cells_prep_topk_as<4, 1>)(b);
@@ -3245,9 +3397,25 @@ static CellKernel cells_records_of()
             },
             (const void *)knn_cells_records_kernel<DYN, KT, NIF, U8>};
 }
-// The record-only scan's forms (knn_cells_topk_plan picks one): the 7 instantiations of knn_cells_records_kernel.
+template <bool DYN, bool U8>
+static CellKernel cells_frame_records_of()
+{
+    return {[](const CellBatch &b) {
+                const CellIndex &c = b.c;
+                const FilterWorkspace &w = b.w;
+                hipLaunchKernelGGL((knn_cells_frame_records_kernel<DYN, U8>), dim3(b.p.grid.blocks), dim3(64 * b.p.grid.waves),
+                                   b.p.grid.lds_bytes, b.s, U8 ? (const h8 *)c.rows8 : (const h8 *)b.st.ref_frags, U8 ? c.norms8 : b.st.ref_norms,
+                                   c.items, c.nitems, (const h8 *)w.qry_frags, w.thr, b.m, b.m_padded, w.cell_counts, w.cell_lists,
+                                   b.p.list_cap, w.records, w.counts, w.ctl_cur, w.slice, w.ovf_base, w.ovf_cap, b.q, b.st.k, b.self);
+            },
+            (const void *)knn_cells_frame_records_kernel<DYN, U8>};
+}
+// The record-only scan's forms (knn_cells_topk_plan picks one): the 7 instantiations of knn_cells_records_kernel and, for per-cell
+// frames, the 3 of knn_cells_frame_records_kernel.
 static CellKernel cells_records_kernel(const CellScanForm &f)
 {
+    if (f.ctr)
+        return f.u8 ? cells_frame_records_of<true, true>() : f.dyn ? cells_frame_records_of<true, false>() : cells_frame_records_of<false, false>();
     if (f.u8)
         return cells_records_of<true, 1, false, true>();
     if (f.kt == 2)
@@ -3524,8 +3692,11 @@ hipError_t knn_cells_query(FilterState &st, FilterWorkspace &w, FilterCallOption
 // Served: a resident, non-sharded index whose cell-sorted layout is in the shard's frame — fp16 rows not centred, or 8-bit rows in
 // bin frames —, k <= 32, m >= 5, out-of-box rows at most half a query's candidate room; and a cell-range shard (always fp16, not
 // centred, KT 1) under the same conditions when the call carries KNN_QUERY_TOPK_PARTIAL (shard_partial: the lists are then what
-// the global top-K needs of this rank, not the rank's own top-K) and topk_cells is 1.  Not served (they keep the exact top-K):
-// per-cell frames (the bound is per (query, cell) there), cell-range shards without the flag, grid indexes, m < 5.
+// the global top-K needs of this rank, not the rank's own top-K) and topk_cells is 1.  Per-cell frames (fp16 centred, or 8-bit rows in
+// each cell's own frame; k <= 16, not sharded): under the same conditions when the call carries KNN_QUERY_TOPK_FRAMES (frames_flag)
+// and topk_cells is 1 — the pass then has the per-cell-frame prep form and scan grid (prep_ctr, scan.ctr: knn_cells_query_plan's
+// choice for a centred layout).  Not served (they keep the exact top-K): per-cell frames without the flag, cell-range shards
+// without theirs, grid indexes, m < 5.
 // Policy (topk_cells = 0): declines for now (see below); topk_cells = 1 serves every such call.
 CellTopkPlan knn_cells_topk_plan(const CellTopkInputs &in)
 {
@@ -3537,7 +3708,10 @@ CellTopkPlan knn_cells_topk_plan(const CellTopkInputs &in)
     // bound's rows, nearly each its own record, but the re-rank's distance gate (knn_topk_gate) lets about one key of a record's
     // sixteen through
     t.ccap = in.ccap;
-    const bool layout = in.has_cells && (!in.sharded || in.shard_partial) && !in.other_path && !qi.centred && (!qi.rows_u8 || in.bins) && qi.kt >= 1 &&
+    // per-cell frames (fp16 centred, or 8-bit rows in each cell's own frame): only for a call that carries KNN_QUERY_TOPK_FRAMES
+    const bool frames = qi.centred && in.frames_flag && !in.sharded && !in.bins && qi.kt == 1 && qi.k <= 16;
+    const bool one_frame = !qi.centred && (!qi.rows_u8 || in.bins);
+    const bool layout = in.has_cells && (!in.sharded || in.shard_partial) && !in.other_path && (frames || one_frame) && qi.kt >= 1 &&
                         qi.kt <= 2 && qi.k <= 32;
     const bool call = qi.m >= 5 && t.ccap >= 64u && in.n_outliers <= t.ccap / 2u;
     // Policy (0) declines every call for now: the issue's condition for sending a (shape, K) to this path by default is a measured
@@ -3569,7 +3743,7 @@ hipError_t knn_cells_query_topk(FilterState &st, FilterWorkspace &w, const CellT
 {
     const CellIndex &c = *st.cells;
     const CellQueryPlan &p = tp.batch;
-    if (!tp.use || m > tp.pass_m || tp.scan.self || tp.scan.ctr || c.centred || (c.geom && (!c.gids || base != 0)))
+    if (!tp.use || m > tp.pass_m || tp.scan.self || tp.scan.ctr != c.centred || p.prep_ctr != c.centred || (c.geom && (!c.gids || base != 0)))
         return hipErrorInvalidValue;
     const CellKernel scan = cells_records_kernel(tp.scan);
     FTRY(ensure_cells_workspace(st, w, m, p, scan));
@@ -3642,6 +3816,21 @@ extern "C" int knn_debug_seed_kth(const float *seed, int nseed, const float *wid
     std::copy(seed, seed + nseed, a.begin());
     std::copy(wide, wide + nwide, b.begin());
     *out = knn_seed_kth_host(a.data(), (int)a.size() / 32, b.data(), (int)b.size() / 32, K, pw);
+    return 0;
+}
+
+// Test hook (host arithmetic, no GPU): the per-cell-frame top-K prep form's conversion of one seed score (knn_frame_dup.h: the
+// kernel's own lines) for one cell frame and one fp32 query row — out = {Dup in the shard's units, 1 if far}.
+extern "C" int knn_debug_frame_dup(int k, const float frame[KNN_CELL_FRAME_WORDS], const float *query_row, float u, float out[2])
+{
+    if (k < 1 || k > 16 || !frame || !query_row || !out || !(frame[16] > 0.0f) || !(frame[17] > 0.0f))
+        return -1;   // KNN_EINVAL
+    float fr[KNN_CELL_FRAME_WORDS];
+    std::copy(frame, frame + KNN_CELL_FRAME_WORDS, fr);
+    _Float16 b[16];
+    const KnnFrameQuery fq = knn_frame_query(k, fr, query_row, b);
+    out[0] = fabsf(u) < INFINITY ? knn_frame_dup(k, fr[16], fr[17], fr[18], fr[19], fq, u) : INFINITY;   // (the kernel converts finite scores only)
+    out[1] = fq.far ? 1.0f : 0.0f;
     return 0;
 }
 

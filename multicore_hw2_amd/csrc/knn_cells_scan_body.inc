@@ -370,8 +370,11 @@
                                             seen = atomicAdd(&ctl[KNN_CTL_TOTAL], steps_new) + steps_new;
                                         seen = (unsigned)__builtin_amdgcn_readfirstlane((int)seen);
                                         if (seen > (TOPK ? CELL_TOPK_RECORD_LIMIT : CELL_BATCH_RECORD_LIMIT) / 64u) {
+                                            unsigned full = ovf_cap;
+                                            if constexpr (TOPK && CTR)   // (the record-only per-cell-frame forms: ovf_cap + 1 is made here, in this
+                                                __asm__ volatile("" : "+s"(full));   //  rare branch — hoisted out of the item loop as a vector register it was spilled: 8 bytes of scratch in the 8-bit form)
                                             if (lane == 0)
-                                                atomicMax(&ctl[KNN_CTL_RECORDS], ovf_cap + 1u);   // what the tail kernel reads as "over-full"
+                                                atomicMax(&ctl[KNN_CTL_RECORDS], full + 1u);   // what the tail kernel reads as "over-full"
                                             dead = true;
                                         }
                                     } else if (__hip_atomic_load(&ctl[KNN_CTL_RECORDS], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > ovf_cap) {

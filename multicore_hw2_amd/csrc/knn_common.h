@@ -383,6 +383,7 @@ struct CellTopkInputs {
     bool sharded = false;          // cell-range shard
     bool shard_partial = false;    // ... whose call carries KNN_QUERY_TOPK_PARTIAL (the only top-K a cell-range shard prunes)
     bool other_path = false;       // the grid index or a forced exact path answers this index
+    bool frames_flag = false;      // the call carries KNN_QUERY_TOPK_FRAMES (the only top-K a layout in per-cell frames prunes)
     unsigned n_outliers = 0;
     unsigned ccap = 0;             // knn_topk_ccap(K, q.m), from the caller (knn_query_route)
 };
@@ -390,7 +391,7 @@ struct CellTopkPlan {
     bool use = false;              // false: the call stays on the path it had (filter top-K or exact top-K)
     int passes = 0, pass_m = 0;    // passes of <= KNN_CELL_BATCH queries; the first pass's queries
     CellQueryPlan batch;           // prep_pw / prep_kt, the match launch, the scan's grid and record lists, list_cap, LDS limits
-    CellScanForm scan;             // knn_cells_records_kernel<dyn, kt, nif, u8> (self, ctr: never)
+    CellScanForm scan;             // knn_cells_records_kernel<dyn, kt, nif, u8> (self: never); ctr: knn_cells_frame_records_kernel<dyn, u8>
     unsigned ccap = 0;             // candidate keys a query has room for
     // (the launches behind the scan are knn_cells_query_topk's fixed sequence: nothing of them is a choice)
 };
