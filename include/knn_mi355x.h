@@ -268,6 +268,29 @@ int knn_keys_topk_merge(int device, int m, int K, const unsigned long long *a_de
  * key's high word (+INF in padding slots). */
 int knn_index_query_topk_host(knn_index *idx, int m, int K, const float *queries_host, int *indices_host, float *dist2_host);
 
+/* Radius-bounded top-K: the K nearest rows WITHIN a distance.  Everything knn_index_query_topk says holds, with one change: a row
+ * of the shard is a candidate when its v0 distance E is finite and E <= max_dist2 — an fp32 compare on the value in the key's high
+ * word, equality inside.  keys_dev[j*K + t] holds the K smallest such keys, ascending, padded with KNN_KEY_INIT.
+ * max_dist2 = +INF gives knn_index_query_topk's keys bit for bit; max_dist2 = 0 (-0 counts as 0) exact duplicates of the query
+ * only; max_dist2 < 0 or NaN, and the plain call's bad arguments, are KNN_EINVAL and launch nothing.
+ * The same four flags with the same meaning; under KNN_QUERY_TOPK_PARTIAL the list guarantee reads "every row with key <= the
+ * global K-th key AND E <= max_dist2".  Without KNN_QUERY_INIT_KEYS the result is the K smallest of what keys_dev held and this
+ * shard's candidates: the keys already there are the caller's and are NOT clipped.  Slots, passes of 1024, indices_dev and
+ * knn_index_last_stats are as for the plain call, and the path is the plain call's for the same flags and options: the radius
+ * changes no route.  The cap holds on every way out, a batch that falls back included.
+ * What the radius buys ("Within a radius"): the grid index stops a query's ring walk as soon as the face bound passes
+ * the radius — a query in an empty region or outside the rows' box ends with a short or empty list instead of sending its batch
+ * to the exact top-K —; the cell-pruned scan of a one-frame layout caps its distance bound with the radius (fewer cells and
+ * records, and a query with fewer than K rows in its seed cells is bounded and does not fall back); in the exact top-K scan a
+ * row beyond the radius never enters a list.  The dense filter and per-cell frames (KNN_QUERY_TOPK_FRAMES) answer as for the
+ * plain call and clip their lists in one more launch. */
+int knn_index_query_topk_within(knn_index *idx, int slot, int m, int K, const float *queries_dev, float max_dist2,
+                                unsigned long long *keys_dev, int *indices_dev, void *stream, unsigned flags);
+/* Synchronous, as knn_index_query_topk_host; counts_host [m] (may be NULL) receives the number of entries of each list that are
+ * not padding. */
+int knn_index_query_topk_within_host(knn_index *idx, int m, int K, const float *queries_host, float max_dist2,
+                                     int *indices_host, float *dist2_host, int *counts_host /* may be NULL */);
+
 /* Tuning / test hooks.  Known names:
  *   "path"    0 = auto, 1 = exact VALU kernels only, 2 = force the MFMA filter
  *             (+ exact re-rank) where its preconditions hold, 3 = the uniform-grid spatial index
@@ -454,6 +477,11 @@ int knn_debug_seed_kth(const float *seed, int nseed, const float *wide, int nwid
  * norm mq: out = {the score threshold, Dup (the largest scaled squared distance a candidate can have, fp32 rounded up), the
  * distance gate of the top-K re-rank: the largest v0 distance (rows' own units) a row of the top-K can have}.  0 on success. */
 int knn_debug_topk_gate(int k, float sigma, double amax, double bmax, double nmax, double u, double mq, double out[3]);
+/* The same three for a call of knn_index_query_topk_within with radius max_dist2 (>= 0, +INF allowed): Dup is capped at
+ * sigma^2 (max_dist2 (1 + g2) + tau), u = +INF (fewer than K finite seed scores) leaves that cap alone, and the gate then lies
+ * slightly above max_dist2 (the exact cut is made behind).  max_dist2 = +INF gives knn_debug_topk_gate's values exactly. */
+int knn_debug_within_bound(int k, float sigma, double amax, double bmax, double nmax, double u, double mq, float max_dist2,
+                           double out[3]);
 /* Test hook (host arithmetic, no GPU): what the per-cell-frame top-K form of the preparation kernel makes of one seed score
  * (knn_frame_dup.h: the kernel runs the same lines).  frame = {the cell's centre [16], scale, ratio = scale / sigma (a power of
  * two), largest |fp16 row coordinate|, largest row norm} (KNN_CELL_FRAME_WORDS = 20 floats), query_row = k floats, u = a finite
@@ -484,6 +512,11 @@ int knn_debug_query_route(const long long in[25], long long out[6]);
  * bytes of the slot's list scratch for a folding call ([m][K] keys); launches of a folding call: the grid kernel, the gated exact
  * top-K (a scan and a select per 65536 queries), the fold}.  Everything after out[0] is 0 when the grid does not answer. */
 int knn_debug_grid_topk_plan(const long long in[6], long long out[6]);
+/* The same for knn_index_query_topk_within: in = {the six inputs of knn_debug_grid_topk_plan, the rings the radius spans on the
+ * grid (the library computes them from the cell widths, a degenerate axis ignored; 0 = none)}; out = the same six.  The rings
+ * raise out[1] to themselves while a walk of that many rings stays within 2^15 cells, (2 rings + 1)^k; beyond that the plain
+ * value and the give-up rule stand. */
+int knn_debug_grid_within_plan(const long long in[7], long long out[6]);
 /* Test hook (host arithmetic only, no GPU needed): what an index is built with.  in = {k, n_local, 1 if the rows are on the
  * device, build_filter (-1 library policy: knn_index_create; 0 none, 1 the MFMA filter layouts, 2 cell-sorted), build_grid (-1
  * library policy, 0, 1), and the options path, cells, ingest, cells_build};

@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = [
     "knn_geom_create", "knn_geom_destroy", "knn_geom_info", "knn_geom_assign", "knn_index_create_sharded",
     "knn_index_seed_export", "knn_index_seed_attach", "knn_geom_first_cell",
     "knn_index_query_topk", "knn_keys_topk_merge", "knn_index_query_topk_host", "knn_debug_grid_topk_plan",
+    "knn_index_query_topk_within", "knn_index_query_topk_within_host", "knn_debug_grid_within_plan", "knn_debug_within_bound",
     "knn_debug_frame_dup",
 ]
 QUERY_INIT_KEYS = 1   # KNN_QUERY_INIT_KEYS
@@ -102,6 +103,8 @@ def lib():
     L.knn_index_query_topk.argtypes = [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, ctypes.c_uint]
     L.knn_keys_topk_merge.argtypes = [c_int, c_int, c_int, c_vp, c_vp, c_vp]
     L.knn_index_query_topk_host.argtypes = [c_vp, c_int, c_int, c_vp, c_vp, c_vp]
+    L.knn_index_query_topk_within.argtypes = [c_vp, c_int, c_int, c_int, c_vp, ctypes.c_float, c_vp, c_vp, c_vp, ctypes.c_uint]
+    L.knn_index_query_topk_within_host.argtypes = [c_vp, c_int, c_int, c_vp, ctypes.c_float, c_vp, c_vp, c_vp]
     _lib = L
     return L
 
@@ -208,6 +211,16 @@ def debug_topk_gate(k, sigma, amax, bmax, nmax, u, mq):
     return tuple(out)
 
 
+def debug_within_bound(k, sigma, amax, bmax, nmax, u, mq, max_dist2):
+    """knn_debug_within_bound: debug_topk_gate's three values for a call of query_topk_within with radius max_dist2 (squared):
+    Dup capped at sigma^2 (max_dist2 (1 + g2) + tau); u = +INF leaves the cap alone.  Host arithmetic."""
+    out = (ctypes.c_double * 3)()
+    f = lib().knn_debug_within_bound
+    f.argtypes = [ctypes.c_int, ctypes.c_float] + [ctypes.c_double] * 5 + [ctypes.c_float, ctypes.POINTER(ctypes.c_double)]
+    _check(f(int(k), float(sigma), float(amax), float(bmax), float(nmax), float(u), float(mq), float(max_dist2), out))
+    return tuple(out)
+
+
 CELL_FRAME_WORDS = 20   # KNN_CELL_FRAME_WORDS: a cell's centre [16], scale, ratio, bmax, nmax
 
 
@@ -276,6 +289,20 @@ def debug_grid_topk_plan(**inputs):
     vin = (ctypes.c_longlong * len(GRID_TOPK_INPUTS))(*[int(inputs[n]) for n in GRID_TOPK_INPUTS])
     out = (ctypes.c_longlong * len(GRID_TOPK_PLAN))()
     f = lib().knn_debug_grid_topk_plan
+    f.argtypes = [ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)]
+    _check(f(vin, out))
+    return dict(zip(GRID_TOPK_PLAN, list(out)))
+
+
+GRID_WITHIN_INPUTS = GRID_TOPK_INPUTS + ("radius_rings",)
+
+
+def debug_grid_within_plan(**inputs):
+    """knn_debug_grid_within_plan: debug_grid_topk_plan for a call of query_topk_within whose radius spans radius_rings rings of
+    the grid (GRID_WITHIN_INPUTS).  Host arithmetic; works without a GPU."""
+    vin = (ctypes.c_longlong * len(GRID_WITHIN_INPUTS))(*[int(inputs[n]) for n in GRID_WITHIN_INPUTS])
+    out = (ctypes.c_longlong * len(GRID_TOPK_PLAN))()
+    f = lib().knn_debug_grid_within_plan
     f.argtypes = [ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)]
     _check(f(vin, out))
     return dict(zip(GRID_TOPK_PLAN, list(out)))
@@ -496,6 +523,31 @@ class KnnIndex:
                                           ctypes.c_void_p(stream),
                                           (QUERY_INIT_KEYS if init_keys else 0) | (QUERY_TOPK_PARTIAL if partial else 0) |
                                           (QUERY_TOPK_GRID if grid else 0) | (QUERY_TOPK_FRAMES if frames else 0)))
+
+    def query_topk_within(self, m, K, queries_dev, max_dist2, keys_dev, stream=0, slot=0, init_keys=False, indices_dev=None,
+                          partial=False, grid=False, frames=False):
+        """Async (knn_index_query_topk_within): query_topk with a distance cap — only rows whose v0 squared distance is
+        <= max_dist2 (fp32, equality inside) are candidates; shorter lists are padded with KEY_INIT.  +INF gives query_topk's
+        keys; a negative or NaN radius raises.  Keys keys_dev already holds (a fold) are the caller's and are not clipped."""
+        _check(lib().knn_index_query_topk_within(self._h, int(slot), int(m), int(K), ctypes.c_void_p(int(queries_dev)),
+                                                 float(max_dist2), ctypes.c_void_p(int(keys_dev)),
+                                                 ctypes.c_void_p(int(indices_dev)) if indices_dev is not None else None,
+                                                 ctypes.c_void_p(stream),
+                                                 (QUERY_INIT_KEYS if init_keys else 0) | (QUERY_TOPK_PARTIAL if partial else 0) |
+                                                 (QUERY_TOPK_GRID if grid else 0) | (QUERY_TOPK_FRAMES if frames else 0)))
+
+    def query_topk_within_host(self, queries, K, max_dist2):
+        """Synchronous radius-bounded top-K of this shard alone: (indices int32 [m][K], dist2 float32 [m][K] with +INF in
+        padding, counts int32 [m]: the entries of each list that are not padding)."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1)
+        m = q.size // self.k
+        idx = np.empty((m, int(K)), dtype=np.int32)
+        d2 = np.empty((m, int(K)), dtype=np.float32)
+        counts = np.empty(m, dtype=np.int32)
+        _check(lib().knn_index_query_topk_within_host(self._h, m, int(K), q.ctypes.data_as(ctypes.c_void_p), float(max_dist2),
+                                                      idx.ctypes.data_as(ctypes.c_void_p), d2.ctypes.data_as(ctypes.c_void_p),
+                                                      counts.ctypes.data_as(ctypes.c_void_p)))
+        return idx, d2, counts
 
     def query_topk_host(self, queries, K):
         """Synchronous top-K of this shard alone: (indices int32 [m][K], dist2 float32 [m][K])."""

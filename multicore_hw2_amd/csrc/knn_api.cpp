@@ -318,6 +318,8 @@ struct knn_index {
     size_t topk_bytes[KNN_SLOTS] = {};
     u64 *topk_cand[KNN_SLOTS] = {};      // per slot: the filter top-K's candidate lists [m][cap] + counts [m] (grown on first use)
     size_t topk_cand_bytes[KNN_SLOTS] = {};
+    u64 *topk_lists[KNN_SLOTS] = {};     // per slot: a radius call's unclipped lists [m][K] on the ways that clip behind (grown on first use)
+    size_t topk_lists_bytes[KNN_SLOTS] = {};
     // Calls on one index from several host threads are serialised (enqueueing a batch is ~20 us of host work; the GPU
     // work of different slots still overlaps): the workspaces' lazily grown buffers, the event list, the statistics and
     // the chain events are plain members.  Recursive: knn_index_query_host calls the keyed entry points.
@@ -798,6 +800,7 @@ void knn_index_destroy(knn_index *idx)
         for (int i = 0; i < KNN_SLOTS; ++i) {
             (void)knn_dev_free(idx->topk_part[i]);
             (void)knn_dev_free(idx->topk_cand[i]);
+            (void)knn_dev_free(idx->topk_lists[i]);
         }
         knn_dev_free_end_synced();
         for (auto &ev : idx->events) {
@@ -1065,19 +1068,25 @@ int knn_index_query(knn_index *idx, int slot, int m, const float *queries_dev, u
     return KNN_OK;
 }
 
-int knn_index_query_topk(knn_index *idx, int slot, int m, int K, const float *queries_dev, unsigned long long *keys_dev,
-                         int *indices_dev, void *stream, unsigned flags)
+}  // extern "C"
+
+namespace {
+
+// knn_index_query_topk and knn_index_query_topk_within behind their argument checks.  max_dist2 = +INF: the plain call, launch
+// for launch.  A finite radius changes no route (knn_query_route never sees it): the exact top-K and the grid way carry the limit
+// key in their kernels, the cell-pruned scan of a one-frame layout caps its bound with it, and the filter ways — whose lists may
+// hold rows just beyond it, or come from a fallback — make their top-K into the slot's list scratch, which one clip launch turns
+// into the caller's keys.
+int query_topk(knn_index *idx, int slot, int m, int K, const float *queries_dev, float max_dist2, u64 *keys, int *indices_dev,
+               hipStream_t s, unsigned flags, const char *who)
 {
-    if (!idx || m < 1 || K < 1 || K > KNN_TOPK_MAX || (long long)m * K > INT_MAX || slot < 0 || slot >= KNN_SLOTS ||
-        !queries_dev || !keys_dev || (flags & ~(unsigned)(KNN_QUERY_INIT_KEYS | KNN_QUERY_TOPK_PARTIAL | KNN_QUERY_TOPK_GRID | KNN_QUERY_TOPK_FRAMES)) != 0u)
-        return fail(KNN_EINVAL, "knn_index_query_topk: bad arguments (1 <= K <= 64, m >= 1, slot 0 .. 7)");
     std::lock_guard<std::recursive_mutex> lock(idx->mu);
     DeviceGuard guard(idx->device);
     if (!guard.ok)
-        return fail(KNN_EHIP, "knn_index_query_topk: hipSetDevice failed");
+        return fail(KNN_EHIP, who, "hipSetDevice failed");
     const int init = (flags & KNN_QUERY_INIT_KEYS) != 0u;
-    hipStream_t s = (hipStream_t)stream;
-    u64 *keys = (u64 *)keys_dev;
+    const bool within = max_dist2 < INFINITY;
+    const u64 lim = within ? knn_topk_limit_key(max_dist2) : kKeyInit;
     idx->stats[0] = 1;
     idx->stats[1] = 0;
     idx->stats[2] = 0;
@@ -1111,15 +1120,24 @@ int knn_index_query_topk(knn_index *idx, int slot, int m, int K, const float *qu
     u64 *&cand = idx->topk_cand[slot];
     if (route.way == QueryWay::Grid) {
         // the grid way (KNN_QUERY_TOPK_GRID): the kernel's lists are the caller's keys, or — a folding call — the slot's scratch
-        const GridTopkPlan gp = knn_grid_topk_plan(idx->k, K, m, true, 0, true);
+        // (a radius call: the rings its radius spans size rmax, the kernel's face bound decides)
+        const GridTopkPlan gp = knn_grid_topk_plan(idx->k, K, m, true, 0, true, within ? knn_grid_radius_rings(idx->grid, max_dist2) : 0);
         if (!init)
             KNN_TRY(slot_buffer_grow(cand, idx->topk_cand_bytes[slot], gp.scratch_bytes));
         idx->stats[3] = 0;
         HIP_TRY(knn_grid_query_topk(idx->grid, gp, slot, m, K, idx->n, queries_dev, idx->refs, idx->base, keys, init, cand, part,
-                                    part_bytes, idx->num_cu, s, ev0, ev1, &idx->grid_topk_gate));
+                                    part_bytes, idx->num_cu, s, ev0, ev1, &idx->grid_topk_gate, within, max_dist2));
         if (indices_dev)
             HIP_TRY(knn_keys_unpack_launch(keys, mk, indices_dev, s));
         return KNN_OK;
+    }
+    // a radius call on the filter ways: the top-K starts the slot's list scratch, the clip behind writes or folds the caller's keys
+    u64 *const caller_keys = keys;
+    const int caller_init = init;
+    const bool clip = within && route.way != QueryWay::Exact;
+    if (clip) {
+        KNN_TRY(slot_buffer_grow(idx->topk_lists[slot], idx->topk_lists_bytes[slot], (size_t)mk * sizeof(u64)));
+        keys = idx->topk_lists[slot];
     }
     if (route.way != QueryWay::Exact)
         KNN_TRY(slot_buffer_grow(cand, idx->topk_cand_bytes[slot], (size_t)m * route.ccap * sizeof(u64) + (size_t)m * sizeof(unsigned)));
@@ -1128,15 +1146,15 @@ int knn_index_query_topk(knn_index *idx, int slot, int m, int K, const float *qu
     case QueryWay::Cells:
         // layouts in the shard's frame — or, with KNN_QUERY_TOPK_FRAMES, in per-cell frames —, in passes of KNN_CELL_BATCH queries
         // (option `topk_cells`)
-        HIP_TRY(knn_filter_query_topk_cells(idx->filter, tp, slot, m, K, queries_dev, idx->refs, idx->base, keys, init != 0, cand, ccount,
-                                            part, part_bytes, idx->num_cu, s, ev0, ev1));
+        HIP_TRY(knn_filter_query_topk_cells(idx->filter, tp, slot, m, K, queries_dev, idx->refs, idx->base, keys, clip || init, cand, ccount,
+                                            part, part_bytes, idx->num_cu, s, ev0, ev1, max_dist2));
         break;
     case QueryWay::Filter: {
         FilterCallOptions opt = filter_call_options();
         opt.run_thresholds = 2;   // running thresholds are a 1-NN argument; the non-running sample stride with them
         opt.sample_stride = 0;
         opt.topk = K;
-        HIP_TRY(knn_filter_query_topk(idx->filter, opt, slot, m, queries_dev, idx->refs, idx->base, keys, init != 0, cand, ccount,
+        HIP_TRY(knn_filter_query_topk(idx->filter, opt, slot, m, queries_dev, idx->refs, idx->base, keys, clip || init, cand, ccount,
                                       route.ccap, part, part_bytes, idx->num_cu, s, ev0, ev1));
         break;
     }
@@ -1146,14 +1164,46 @@ int knn_index_query_topk(knn_index *idx, int slot, int m, int K, const float *qu
         if (ev)
             HIP_TRY(hipEventRecord(ev0, s));
         HIP_TRY(knn_exact_topk_launch(idx->k, m, K, idx->n, idx->base, gids, queries_dev, idx->refs, keys, init, part, part_bytes,
-                                      idx->num_cu, s));
+                                      idx->num_cu, s, nullptr, lim));
         if (ev)
             HIP_TRY(hipEventRecord(ev1, s));
     }
     }
+    if (clip)
+        HIP_TRY(knn_topk_clip_launch(m, K, keys, lim, caller_keys, caller_init, s));
     if (indices_dev)
-        HIP_TRY(knn_keys_unpack_launch(keys, mk, indices_dev, s));
+        HIP_TRY(knn_keys_unpack_launch(caller_keys, mk, indices_dev, s));
     return KNN_OK;
+}
+
+// The arguments both top-K entries reject (the four flags they admit: values up to 15).
+bool topk_args_bad(const knn_index *idx, int slot, int m, int K, const float *queries_dev, const unsigned long long *keys_dev, unsigned flags)
+{
+    return !idx || m < 1 || K < 1 || K > KNN_TOPK_MAX || (long long)m * K > INT_MAX || slot < 0 || slot >= KNN_SLOTS ||
+        !queries_dev || !keys_dev || (flags & ~(unsigned)(KNN_QUERY_INIT_KEYS | KNN_QUERY_TOPK_PARTIAL | KNN_QUERY_TOPK_GRID | KNN_QUERY_TOPK_FRAMES)) != 0u;
+}
+
+}  // namespace
+
+extern "C" {
+
+int knn_index_query_topk(knn_index *idx, int slot, int m, int K, const float *queries_dev, unsigned long long *keys_dev,
+                         int *indices_dev, void *stream, unsigned flags)
+{
+    if (topk_args_bad(idx, slot, m, K, queries_dev, keys_dev, flags))
+        return fail(KNN_EINVAL, "knn_index_query_topk: bad arguments (1 <= K <= 64, m >= 1, slot 0 .. 7)");
+    return query_topk(idx, slot, m, K, queries_dev, INFINITY, (u64 *)keys_dev, indices_dev, (hipStream_t)stream, flags,
+                      "knn_index_query_topk");
+}
+
+int knn_index_query_topk_within(knn_index *idx, int slot, int m, int K, const float *queries_dev, float max_dist2,
+                                unsigned long long *keys_dev, int *indices_dev, void *stream, unsigned flags)
+{
+    if (topk_args_bad(idx, slot, m, K, queries_dev, keys_dev, flags) || !(max_dist2 >= 0.0f))
+        return fail(KNN_EINVAL, "knn_index_query_topk_within: bad arguments (1 <= K <= 64, m >= 1, slot 0 .. 7, max_dist2 >= 0 and not NaN)");
+    // (-0 counts as 0: the limit key is made from the bits)
+    return query_topk(idx, slot, m, K, queries_dev, max_dist2 == 0.0f ? 0.0f : max_dist2, (u64 *)keys_dev, indices_dev,
+                      (hipStream_t)stream, flags, "knn_index_query_topk_within");
 }
 
 int knn_keys_topk_merge(int device, int m, int K, const unsigned long long *a_dev, unsigned long long *b_dev, void *stream)
@@ -1451,6 +1501,17 @@ int knn_debug_grid_topk_plan(const long long in[6], long long out[6])
     return KNN_OK;
 }
 
+int knn_debug_grid_within_plan(const long long in[7], long long out[6])
+{
+    if (!in || !out || in[0] < 1 || in[0] > 4 || in[1] < 1 || in[1] > KNN_TOPK_MAX || in[2] < 1 || in[2] > INT_MAX ||
+        in[2] * in[1] > INT_MAX || in[3] < 0 || in[3] > 1 || in[4] < 0 || in[4] > 3 || in[5] < 0 || in[5] > 1 || in[6] < 0)
+        return fail(KNN_EINVAL, "knn_debug_grid_within_plan: bad arguments (1 <= k <= 4, 1 <= K <= 64, m >= 1, path 0 .. 3, rings >= 0)");
+    const GridTopkPlan p = knn_grid_topk_plan((int)in[0], (int)in[1], (int)in[2], in[3] != 0, (int)in[4], in[5] != 0, in[6]);
+    const long long v[6] = {p.use, p.rmax, p.blocks, p.waves, (long long)p.scratch_bytes, p.launches};
+    memcpy(out, v, sizeof v);
+    return KNN_OK;
+}
+
 int knn_debug_index_build_plan(const long long in[9], long long out[6])
 {
     if (!in || !out || in[0] < 1 || in[0] > INT_MAX || in[1] < 0 || in[3] < -1 || in[3] > 2 || in[4] < -1 || in[4] > 1 || in[5] < 0 ||
@@ -1526,7 +1587,9 @@ namespace {
 // per query.  The queries are staged into a pooled buffer, the query runs on the null stream and the packed keys come
 // back to keys_host; everything else stays on `idx->device`.  keep != nullptr: the keys stay on the device instead, in a
 // buffer that keep->owner holds (keep->dev, complete on return) — the RCCL merge of cudaCallback reads them there.
-int staged_query(knn_index *idx, const char *who, int m, int K, const float *queries_host, u64 *keys_host, ShardKeys *keep = nullptr)
+// max_dist2 finite (K >= 1): knn_index_query_topk_within.
+int staged_query(knn_index *idx, const char *who, int m, int K, const float *queries_host, u64 *keys_host, ShardKeys *keep = nullptr,
+                 float max_dist2 = INFINITY)
 {
     const std::string name(who);
     DeviceGuard guard(idx->device);
@@ -1543,8 +1606,10 @@ int staged_query(knn_index *idx, const char *who, int m, int K, const float *que
         e = hipMemcpy(q_dev, queries_host, qbytes, hipMemcpyHostToDevice);
     if (e != hipSuccess)
         return fail(KNN_EHIP, (name + ": staging queries").c_str(), hipGetErrorString(e));
-    int rc = K > 0 ? knn_index_query_topk(idx, 0, m, K, q_dev, keys_dev, nullptr, nullptr, KNN_QUERY_INIT_KEYS)
-                   : knn_keys_init(idx->device, keys_dev, m, nullptr);
+    int rc = K > 0 && max_dist2 < INFINITY
+                 ? knn_index_query_topk_within(idx, 0, m, K, q_dev, max_dist2, keys_dev, nullptr, nullptr, KNN_QUERY_INIT_KEYS)
+             : K > 0 ? knn_index_query_topk(idx, 0, m, K, q_dev, keys_dev, nullptr, nullptr, KNN_QUERY_INIT_KEYS)
+                     : knn_keys_init(idx->device, keys_dev, m, nullptr);
     if (rc == KNN_OK && K == 0)
         rc = knn_index_query_keys(idx, m, q_dev, keys_dev, nullptr);
     if (rc != KNN_OK)
@@ -1597,6 +1662,34 @@ extern "C" int knn_index_query_topk_host(knn_index *idx, int m, int K, const flo
             memcpy(&dist2_host[i], &hi, sizeof hi);
         }
     }
+    return KNN_OK;
+}
+
+extern "C" int knn_index_query_topk_within_host(knn_index *idx, int m, int K, const float *queries_host, float max_dist2,
+                                                int *indices_host, float *dist2_host, int *counts_host)
+{
+    if (!idx || m < 1 || K < 1 || K > KNN_TOPK_MAX || (long long)m * K > INT_MAX || !queries_host || !indices_host || !(max_dist2 >= 0.0f))
+        return fail(KNN_EINVAL, "knn_index_query_topk_within_host: bad arguments (1 <= K <= 64, m >= 1, max_dist2 >= 0 and not NaN)");
+    std::lock_guard<std::recursive_mutex> lock(idx->mu);
+    const size_t mk = (size_t)m * (size_t)K;
+    std::vector<u64> keys(mk);
+    const int rc = staged_query(idx, "knn_index_query_topk_within_host", m, K, queries_host, keys.data(), nullptr, max_dist2);
+    if (rc != KNN_OK)
+        return rc;
+    for (size_t i = 0; i < mk; ++i) {
+        indices_host[i] = (int)(unsigned)(keys[i] & 0xFFFFFFFFull);
+        if (dist2_host) {
+            const unsigned hi = (unsigned)(keys[i] >> 32);
+            memcpy(&dist2_host[i], &hi, sizeof hi);
+        }
+    }
+    if (counts_host)
+        for (int j = 0; j < m; ++j) {   // padding is KNN_KEY_INIT; a real key is below it
+            int c = 0;
+            while (c < K && keys[(size_t)j * K + c] < kKeyInit)
+                ++c;
+            counts_host[j] = c;
+        }
     return KNN_OK;
 }
 

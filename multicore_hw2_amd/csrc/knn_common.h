@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 #include <algorithm>
 
 #define KNN_WAVE 64
@@ -59,9 +60,22 @@ size_t knn_topk_part_bytes(int m, int K, long long n, int num_cu);
 // keys[m][K] <- the K smallest of (keys unless init, this shard's finite-distance rows), sorted; v0 arithmetic.  Global
 // numbers: gids[row] when gids != nullptr, else base + row.  part: part_bytes of scratch (knn_topk_part_bytes), stream-ordered.
 // gate != nullptr: the launches do nothing unless *gate != 0 (the filter top-K's FALLBACK word).
+// lim (knn_index_query_topk_within): only rows whose key is below it are candidates (knn_topk_limit_key); KNN_KEY_INIT = none.
+// The keys the call folds into are the caller's and are not clipped.
 hipError_t knn_exact_topk_launch(int k, int m, int K, long long n, long long base, const unsigned *gids, const float *q,
                                  const float *r, u64 *keys, int init, u64 *part, size_t part_bytes, int num_cu,
-                                 hipStream_t stream, const unsigned *gate = nullptr);
+                                 hipStream_t stream, const unsigned *gate = nullptr, u64 lim = kKeyInit);
+// The limit key of a radius: a key is within max_dist2 >= 0 (not NaN; -0 counts as 0) exactly when it is below
+// (bits(max_dist2) + 1) << 32 — the fp32 compare E <= max_dist2 on the key's high word, equality inside.  +INF gives a key above
+// KNN_KEY_INIT: no limit.
+static inline u64 knn_topk_limit_key(float max_dist2)
+{
+    unsigned bits;
+    memcpy(&bits, &max_dist2, sizeof bits);
+    return ((u64)(bits & 0x7FFFFFFFu) + 1ull) << 32;
+}
+// keys[j] <- lists[j] with every key >= lim turned into KNN_KEY_INIT (init), or the K smallest of that and keys[j] (a fold).
+hipError_t knn_topk_clip_launch(int m, int K, const u64 *lists, u64 lim, u64 *keys, int init, hipStream_t stream);
 // Filter top-K: umin[0][q] <- K-th smallest finite per-block minimum (one row for knn_thr_kernel).
 hipError_t knn_topk_umin_launch(float *umin, int nb, int m_padded, int K, hipStream_t stream);
 // Filter top-K after the scan: records + outlier rows -> per-query candidate lists (overflow -> FALLBACK), then, unless
@@ -512,12 +526,13 @@ void knn_cells_workspace_free(FilterWorkspace &w);
 // init_keys: the batch's keys are set to (+INF, 0) by the first kernel of the chain.
 hipError_t knn_cells_query(FilterState &st, FilterWorkspace &w, FilterCallOptions opt, int m, const float *q_dev, const float *r_dev,
                            long long base, u64 *keys, int num_cu, bool timed, hipStream_t s, bool init_keys, int *out_idx = nullptr);
+// max_dist2 finite (a radius call, one-frame layouts): the prep kernel caps Dup_q with the radius (knn_threshold_within).
 // One pass of <= KNN_CELL_BATCH queries of a top-K call: prep (K-th seed bound) -> match -> record-only scan -> re-rank of the
 // slices and of the shared overflow area -> out-of-box rows -> select -> the exact top-K, gated on FALLBACK.  keys: the pass's
 // [m][K]; cand / ccount: the pass's candidate lists [m][tp.ccap] and counters [m].
 hipError_t knn_cells_query_topk(FilterState &st, FilterWorkspace &w, const CellTopkPlan &tp, int m, int K, const float *q_dev,
                                 const float *r_dev, long long base, u64 *keys, bool init_keys, u64 *cand, unsigned *ccount, u64 *part,
-                                size_t part_bytes, int num_cu, bool timed, hipStream_t s);
+                                size_t part_bytes, int num_cu, bool timed, hipStream_t s, float max_dist2 = INFINITY);
 
 // Builds the filter layouts for refs[0..n) (device, AoS).  Synchronous.  Leaves st.usable false
 // (and returns hipSuccess) when the data rules the filter out.
@@ -546,10 +561,17 @@ struct GridTopkPlan {
     size_t scratch_bytes = 0;  // a folding call's lists [m][K] (the slot's topk_cand)
     int launches = 0;          // of a folding call: grid kernel, gated exact top-K (scan + select per chunk), fold
 };
-GridTopkPlan knn_grid_topk_plan(int k, int K, int m, bool has_grid, int path, bool flag);
+// radius_rings (knn_index_query_topk_within): the rings the radius spans (knn_grid_radius_rings); 0 = a plain call.
+GridTopkPlan knn_grid_topk_plan(int k, int K, int m, bool has_grid, int path, bool flag, long long radius_rings = 0);
+// The rings a radius of max_dist2 (squared, >= 0) spans on the grid: ceil(radius / the narrowest live axis' cell width) + 1,
+// capped at 2^30; a degenerate axis (one cell) is ignored, 0 when every axis is.  Sizes the plan's rmax only.
+long long knn_grid_radius_rings(const GridState *gs, float max_dist2);
+// within != 0 (knn_index_query_topk_within): only rows with v0 distance <= max_dist2 are candidates, in the grid kernel and in
+// the gated exact top-K behind it; a query stops as soon as the face bound passes the radius.
 hipError_t knn_grid_query_topk(const GridState *gs, const GridTopkPlan &plan, int slot, int m, int K, long long n, const float *q_dev,
                                const float *r_dev, long long base, u64 *keys, int init, u64 *scratch, u64 *part, size_t part_bytes,
-                               int num_cu, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const unsigned **gate_out);
+                               int num_cu, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const unsigned **gate_out,
+                               int within = 0, float max_dist2 = 0.0f);
 void knn_grid_info(const GridState *gs, long long info[4]);
 
 // ---- RCCL exchange step (knn_rccl.cpp; librccl is dlopen'ed at first use) -------------------
@@ -602,7 +624,10 @@ hipError_t knn_filter_query_topk(FilterState &st, FilterCallOptions opt, int slo
 // Top-K on the cell-pruned scan, the whole call in passes of KNN_CELL_BATCH queries (knn_cells_query_topk); cand / ccount: [m][tp.ccap], [m].
 hipError_t knn_filter_query_topk_cells(FilterState &st, const CellTopkPlan &tp, int slot, int m, int K, const float *q, const float *r,
                                        long long base, u64 *keys, bool init_keys, u64 *cand, unsigned *ccount, u64 *part,
-                                       size_t part_bytes, int num_cu, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end);
+                                       size_t part_bytes, int num_cu, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end,
+                                       // a radius call (finite): one-frame layouts cap their bound with it; the lists are NOT cut at
+                                       // it here (the gate lies slightly above): the caller clips them
+                                       float max_dist2 = INFINITY);
 // Test hook: raw filter scores S[m][n] (row-major) and the per-query thresholds for a query
 // batch, plus {sigma, eta, rho, amax, bmax}.  Synchronous.
 hipError_t knn_filter_debug(FilterState &st, int m, const float *q_dev, const float *r_dev,

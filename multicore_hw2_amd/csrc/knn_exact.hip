@@ -873,12 +873,17 @@ hipError_t knn_synth_fill_launch(float *dst, long long count, u64 seed, long lon
 // the K-th key never exceeds it.  At the end the column goes to part[slice][query][K] with the global row numbers (base +
 // row, or gids[row]: both ascending in the local row, so the order the scan decided is kept).
 // KC = chunks of 16 dimensions held in VGPRs (k <= 128); KC = 0: any k, the query's coordinates re-read from memory.
+// LIM (knn_index_query_topk_within): a row is a candidate only when its key is below `lim` = (bits(max_dist2) + 1) << 32, i.e.
+// its v0 distance is <= max_dist2.  The K-th key a row is compared with is min(column[K - 1], lim) — the column's last place is
+// KNN_KEY_INIT until K rows are in, and read back bare it would let rows beyond the radius in after the first insertion.  The
+// plain form (LIM = false) never reads `lim`.
 // ------------------------------------------------------------------------------------------
-template <int KC>
+template <int KC, bool LIM = false>
 __global__ __launch_bounds__(KNN_WAVE) void knn_exact_topk_kernel(const float *__restrict__ Q, const float *__restrict__ R,
                                                                  int k, int m, long long n, int K, long long rows_per_slice,
                                                                  long long base, const unsigned *__restrict__ gids,
-                                                                 u64 *__restrict__ part, const unsigned *__restrict__ gate)
+                                                                 u64 *__restrict__ part, const unsigned *__restrict__ gate,
+                                                                 u64 lim)
 {
 #pragma clang fp contract(off)
     extern __shared__ u64 topk_lst[];   // [K][KNN_WAVE]
@@ -894,7 +899,7 @@ __global__ __launch_bounds__(KNN_WAVE) void knn_exact_topk_kernel(const float *_
         qv[d] = KC > 0 && d < k ? Q[(size_t)qa * k + d] : 0.0f;
     for (int t = 0; t < K; ++t)
         topk_lst[t * KNN_WAVE + lane] = kKeyInit;
-    u64 kth = kKeyInit;
+    u64 kth = LIM && lim < kKeyInit ? lim : kKeyInit;
     const long long i0 = (long long)blockIdx.x * rows_per_slice;
     const long long i1 = min(n, i0 + rows_per_slice);
     const float *__restrict__ r = R + (size_t)i0 * k;
@@ -945,6 +950,8 @@ __global__ __launch_bounds__(KNN_WAVE) void knn_exact_topk_kernel(const float *_
             }
             topk_lst[p * KNN_WAVE + lane] = key;
             kth = topk_lst[(K - 1) * KNN_WAVE + lane];
+            if (LIM)
+                kth = kth < lim ? kth : lim;
         }
     }
     if (q >= m)
@@ -1056,8 +1063,9 @@ size_t knn_topk_part_bytes(int m, int K, long long n, int num_cu)
 
 hipError_t knn_exact_topk_launch(int k, int m, int K, long long n, long long base, const unsigned *gids, const float *q,
                                  const float *r, u64 *keys, int init, u64 *part, size_t part_bytes, int num_cu,
-                                 hipStream_t s, const unsigned *gate)
+                                 hipStream_t s, const unsigned *gate, u64 lim)
 {
+    const bool within = lim < kKeyInit;   // (a limit at or above (+INF, 0) admits what the plain form admits)
     if (m <= 0 || K < 1 || K > KNN_TOPK_MAX)
         return m <= 0 ? hipSuccess : hipErrorInvalidValue;
     if (n <= 0) {   // nothing to add: the keys stay (or start at (+INF, 0))
@@ -1075,8 +1083,12 @@ hipError_t knn_exact_topk_launch(int k, int m, int K, long long n, long long bas
         const dim3 grid((unsigned)slices, qg), block(KNN_WAVE);
         const size_t lds = (size_t)K * KNN_WAVE * sizeof(u64);
         const float *qc = q + (size_t)c0 * k;
-#define KNN_TOPK_SCAN(KCV)                                                                                         \
-    hipLaunchKernelGGL((knn_exact_topk_kernel<KCV>), grid, block, lds, s, qc, r, k, mc, n, K, per, base, gids, part, gate)
+#define KNN_TOPK_SCAN(KCV)                                                                                                       \
+    if (within)                                                                                                                  \
+        hipLaunchKernelGGL((knn_exact_topk_kernel<KCV, true>), grid, block, lds, s, qc, r, k, mc, n, K, per, base, gids, part, gate, \
+                           lim);                                                                                                 \
+    else                                                                                                                         \
+        hipLaunchKernelGGL((knn_exact_topk_kernel<KCV>), grid, block, lds, s, qc, r, k, mc, n, K, per, base, gids, part, gate, lim)
         switch ((k + 15) / 16) {
         case 1: KNN_TOPK_SCAN(1); break;
         case 2: KNN_TOPK_SCAN(2); break;
@@ -1108,6 +1120,35 @@ hipError_t knn_topk_merge_launch(int m, int K, const u64 *a, u64 *b, hipStream_t
     if (K < 1 || K > KNN_TOPK_MAX)
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(knn_topk_select_kernel, dim3((unsigned)m), dim3(KNN_WAVE), 0, s, a, 1, m, K, b, 0, (const unsigned *)nullptr);
+    return hipGetLastError();
+}
+
+// knn_index_query_topk_within on the ways whose kernels carry no radius: one wave (block) per query.  lists[q][0..K) is a sorted
+// top-K list; every key >= lim becomes KNN_KEY_INIT — a sorted top-K list clipped at a key is the top-K of the clipped set, and
+// the clipped places are the list's tail, so it stays sorted — and the list is written to keys[q] (init) or folded into it.
+__global__ __launch_bounds__(KNN_WAVE) void knn_topk_clip_kernel(const u64 *__restrict__ lists, int K, u64 lim,
+                                                                u64 *__restrict__ keys, int init)
+{
+    __shared__ u64 sa[KNN_WAVE], sb[KNN_WAVE], so[KNN_WAVE];
+    const int q = blockIdx.x;
+    const int lane = threadIdx.x;
+    u64 b = ~0ull;
+    if (lane < K) {
+        b = lists[(size_t)q * K + lane];
+        b = b < lim ? b : kKeyInit;
+    }
+    const u64 cur = init ? b : topk_wave_merge(lane < K ? keys[(size_t)q * K + lane] : ~0ull, b, K, lane, sa, sb, so);
+    if (lane < K)
+        keys[(size_t)q * K + lane] = cur;
+}
+
+hipError_t knn_topk_clip_launch(int m, int K, const u64 *lists, u64 lim, u64 *keys, int init, hipStream_t s)
+{
+    if (m <= 0)
+        return hipSuccess;
+    if (K < 1 || K > KNN_TOPK_MAX)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(knn_topk_clip_kernel, dim3((unsigned)m), dim3(KNN_WAVE), 0, s, lists, K, lim, keys, init);
     return hipGetLastError();
 }
 

@@ -2691,7 +2691,8 @@ hipError_t knn_filter_query_topk(FilterState &st, FilterCallOptions opt, int slo
 // answered exactly, the next is pruned again.
 hipError_t knn_filter_query_topk_cells(FilterState &st, const CellTopkPlan &tp, int slot, int m, int K, const float *q, const float *r,
                                        long long base, u64 *keys, bool init_keys, u64 *cand, unsigned *ccount, u64 *part,
-                                       size_t part_bytes, int num_cu, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end)
+                                       size_t part_bytes, int num_cu, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end,
+                                       float max_dist2)
 {
     if (!st.cells || !tp.use)
         return hipErrorInvalidValue;
@@ -2703,7 +2704,7 @@ hipError_t knn_filter_query_topk_cells(FilterState &st, const CellTopkPlan &tp, 
     for (int q0 = 0; q0 < m; q0 += cell_batch) {
         const int mb = std::min(cell_batch, m - q0);
         FTRY(knn_cells_query_topk(st, w, tp, mb, K, q + (size_t)q0 * st.k, r, base, keys + (size_t)q0 * K, init_keys,
-                                  cand + (size_t)q0 * tp.ccap, ccount + q0, part, part_bytes, num_cu, q0 == 0, s));
+                                  cand + (size_t)q0 * tp.ccap, ccount + q0, part, part_bytes, num_cu, q0 == 0, s, max_dist2));
     }
     return hipSuccess;
 }

@@ -229,6 +229,35 @@ __host__ __device__ inline float knn_threshold(const BoundConsts &c, double u, d
     return nextafterf(tf, INFINITY);                  // the kernel tests S < thr (strict)
 }
 
+// The same for a radius-bounded top-K (knn_index_query_topk_within) on a one-frame layout.  C = the shard's rows with v0 distance
+// E <= max_dist2; wanted: the K smallest keys of C.  For a row c among them:
+//   (a) E_c <= max_dist2, hence — the line the derivation above rests on, D <= sigma^2 (E (1+g2) + tau) —
+//       D_c <= dup_r = sigma^2 (max_dist2 (1+g2) + tau);
+//   (b) with u = u_(K) finite (K distinct seed rows j0 scoring <= u, knn_seed_kth.h): E_c <= max E_j0.  Otherwise all K seed rows
+//       had E_j0 < E_c <= max_dist2: they were in C and before c in key order, so c were not among C's K smallest (nor in C at all
+//       when C holds fewer than K rows).  Then D_c <= Dup(u) by knn_threshold's own argument, however many rows C holds.
+// So D_c <= min(Dup(u), dup_r) in every case, and with u = +INF (no or fewer than K finite seed scores) (a) alone stands: a finite
+// radius bounds the query by itself.  Under KNN_QUERY_TOPK_PARTIAL read "the global set" for "the shard" in (b).
+// The score bound is knn_threshold's last line — monotone in Dup —, with the same slack and the same rounding up;
+// max_dist2 = +INF gives knn_threshold's values exactly.
+__host__ __device__ inline float knn_threshold_within(const BoundConsts &c, double u, double mq, double max_dist2, double *dup_out = nullptr)
+{
+    double dt = u + mq * (1.0 + 1.01 * c.gam) + c.rho;   // (u = +INF: +INF from here to dup)
+    if (dt < 0.0)
+        dt = 0.0;
+    const double sq0 = c.eta + sqrt(dt + 2.0 * c.eta2);
+    double dup = sq0 * sq0 * (1.0 + c.g2) * (1.0 + c.g2) + c.sigma2 * c.tau;
+    const double dup_r = c.sigma2 * (max_dist2 * (1.0 + c.g2) + c.tau);
+    dup = dup_r < dup ? dup_r : dup;
+    if (dup_out)
+        *dup_out = dup;
+    double thr = dup + 2.0 * c.eta * sqrt(dup) + c.eta2 + c.rho - mq * (1.0 - c.gam);
+    thr += fabs(thr) * 1e-6 + 1e-30;
+    float tf = (float)thr;
+    if ((double)tf < thr)
+        tf = nextafterf(tf, INFINITY);
+    return nextafterf(tf, INFINITY);
+}
 
 __device__ __forceinline__ float min3f(float a, float b, float c)
 {

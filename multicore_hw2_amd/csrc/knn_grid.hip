@@ -391,6 +391,14 @@ __device__ __forceinline__ u64 grid_readlane64(u64 v, int src)
 // < lb^2 (1 - 1e-6) — every unseen row's computed distance is strictly above that, so none can enter the list or tie its K-th
 // place.  The list goes to out[q][0 .. KK) and is never folded here: a batch that gives up is answered again by the exact
 // top-K behind this kernel, and a row folded by both would stand in the caller's keys twice.
+// WR (knn_index_query_topk_within): the radius form.  A row is a candidate when its key is below min(kth, lim), lim =
+// (bits(max_dist2) + 1) << 32: the limit is kept apart from `kth`, which is re-read from lane KK - 1 after every insertion and is
+// KNN_KEY_INIT there until the list is full — `kth < kKeyInit` stays the "K-th is a real key" test.  The stop rule gains a
+// clause: done when max_dist2 < lb^2 (1 - 1e-6), the same argument with the radius in place of the K-th distance (every unseen
+// row's computed distance is strictly above that bound, so none is within the radius).  A query in an empty region or outside
+// the rows' box then ends after the few rings its radius spans, with a short or empty list, where the plain form gives up.
+// (The body is a file of its own, knn_grid_topk_body.inc, so that the radius form can be a kernel of its own with one argument
+// more: the plain form keeps its argument list, its name and its code as they are.)
 template <int KD>
 __global__ __launch_bounds__(GRID_BLOCK) void knn_grid_topk_kernel(const float *__restrict__ Q, int m, int KK, GridGeom gg,
                                                                    const unsigned *__restrict__ start,
@@ -401,102 +409,24 @@ __global__ __launch_bounds__(GRID_BLOCK) void knn_grid_topk_kernel(const float *
                                                                    unsigned *__restrict__ giveup_next)
 {
 #pragma clang fp contract(off)
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        *giveup_next = 0u;   // (the slot's other word, as the 1-NN kernel)
-    const int lane = threadIdx.x & 63;
-    const int qi = blockIdx.x * (GRID_BLOCK / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    if (qi >= m)
-        return;
-    u64 *__restrict__ o = out + (size_t)qi * KK;
-    u64 list = lane < KK ? kKeyInit : ~0ull;
-    float q[4] = {0.f, 0.f, 0.f, 0.f};
-    bool finite = true;
-#pragma unroll
-    for (int d = 0; d < KD; ++d) {
-        q[d] = Q[(size_t)qi * KD + d];
-        finite = finite && fabsf(q[d]) < INFINITY;
-    }
-    if (!finite) {   // every distance is NaN or +INF: no row is a candidate (and nothing to give up on)
-        if (lane < KK)
-            o[lane] = kKeyInit;
-        return;
-    }
-    int c[4];
-    (void)grid_cell_of(gg, q, c);
-    int gmax = 1;
-#pragma unroll
-    for (int d = 0; d < KD; ++d)
-        gmax = gg.g[d] > gmax ? gg.g[d] : gmax;
+    constexpr bool WR = false;
+    constexpr float max_dist2 = 0.0f;
+#include "knn_grid_topk_body.inc"
+}
 
-    u64 kth = kKeyInit;
-    bool done = false;
-    bool first = true;
-    for (int r = gmax > 1 ? 1 : 0; r < gmax && r <= rmax; ++r) {
-        const int side = 2 * r + 1;
-        int total = 1;
-#pragma unroll
-        for (int d = 0; d < KD; ++d)
-            total *= side;
-        int shift = 0;   // split = 1 << shift lanes per cell
-        while ((total << (shift + 1)) <= KNN_WAVE)
-            ++shift;
-        const int sub = lane & ((1 << shift) - 1), step = 1 << shift, per = KNN_WAVE >> shift;
-        for (int idx0 = 0; idx0 < total; idx0 += per) {
-            const int idx = idx0 + (lane >> shift);
-            unsigned p = 0u, p1 = 0u, cell;
-            if (idx < total && grid_ring_cell<KD>(gg, c, r, side, idx, first, &cell)) {
-                p = start[cell] + (unsigned)sub;
-                p1 = start[cell + 1];
-            }
-            while (__ballot(p < p1) != 0ull) {
-                u64 key = ~0ull;
-                if (p < p1) {
-                    const f4g x = pts[p];
-                    float acc = 0.0f;
-#pragma unroll
-                    for (int d = 0; d < KD; ++d) {
-                        const float diff = q[d] - x[d];   // v0: search - reference, squared, summed in order
-                        const float sq = diff * diff;
-                        acc = acc + sq;
-                    }
-                    if (acc < INFINITY)                   // NaN / +INF never beat +INF (v0's strict >)
-                        key = ((u64)__float_as_uint(acc) << 32) | (u64)(unsigned)(base + orig[p]);
-                }
-                p += (unsigned)step;
-                u64 pend = __ballot(key < kth);
-                while (pend != 0ull) {
-                    const int src = __builtin_ctzll(pend);
-                    pend &= pend - 1ull;
-                    const u64 cand = grid_readlane64(key, src);
-                    if (cand < kth) {   // (the K-th key may have come down since the ballot)
-                        const int pos = __popcll(__ballot(list < cand));
-                        const u64 up = __shfl_up(list, 1, KNN_WAVE);
-                        if (lane < KK)
-                            list = lane < pos ? list : lane == pos ? cand : up;
-                        kth = grid_readlane64(list, KK - 1);
-                    }
-                }
-            }
-        }
-        first = false;
-        bool covers_all;
-        const double lb = grid_face_bound<KD>(gg, c, q, r, &covers_all);
-        if (covers_all) {   // (the list may hold fewer than KK real keys: the rest stay KNN_KEY_INIT)
-            done = true;
-            break;
-        }
-        if (lb > 0.0 && kth < kKeyInit) {
-            const float kd = __uint_as_float((unsigned)(kth >> 32));
-            if ((double)kd < lb * lb * (1.0 - 1e-6)) {
-                done = true;
-                break;
-            }
-        }
-    }
-    if (lane < KK)
-        o[lane] = list;
-    if (lane == 0 && !done && gmax > rmax + 1)
-        *giveup = 1u;      // benign race: every writer stores 1
+// The radius form (knn_index_query_topk_within).
+template <int KD>
+__global__ __launch_bounds__(GRID_BLOCK) void knn_grid_within_kernel(const float *__restrict__ Q, int m, int KK, GridGeom gg,
+                                                                     const unsigned *__restrict__ start,
+                                                                     const f4g *__restrict__ pts,
+                                                                     const unsigned *__restrict__ orig, long long base,
+                                                                     u64 *__restrict__ out, int rmax,
+                                                                     unsigned *__restrict__ giveup,
+                                                                     unsigned *__restrict__ giveup_next, float max_dist2)
+{
+#pragma clang fp contract(off)
+    constexpr bool WR = true;
+#include "knn_grid_topk_body.inc"
 }
 
 // ---- host -------------------------------------------------------------------------------------------
@@ -696,7 +626,10 @@ hipError_t knn_grid_query(const GridState *gs, int slot, int m, const float *q, 
 // Top-K on the grid (host arithmetic only).  rmax: a K-th neighbour lies deeper than the nearest — the first ring whose block
 // holds 4 K rows at the build's 3 rows per cell, doubled (+ 2) for queries at a cell's edge and uneven cells; never below the
 // 1-NN kernel's.
-GridTopkPlan knn_grid_topk_plan(int k, int K, int m, bool has_grid, int path, bool flag)
+// A radius call (radius_rings > 0) walks as far as its radius spans: rmax = max(plain rmax, radius_rings) while a walk of that
+// many rings stays within kGridWithinCells cells, (2 rings + 1)^k <= 2^15 — the size of the largest walk the plain plan already
+// allows (k 4, K 64: 13^4), a chosen budget, not a measured one.  Beyond it the plain rmax and the give-up rule stand.
+GridTopkPlan knn_grid_topk_plan(int k, int K, int m, bool has_grid, int path, bool flag, long long radius_rings)
 {
     GridTopkPlan p;
     p.use = has_grid && flag && (path == 0 || path == 3);
@@ -711,6 +644,15 @@ GridTopkPlan knn_grid_topk_plan(int k, int K, int m, bool has_grid, int path, bo
             break;
     }
     p.rmax = std::max(grid_rmax_1nn(k), 2 * need + 2);
+    if (radius_rings > p.rmax) {
+        constexpr long long kGridWithinCells = 1ll << 15;
+        const long long side = 2 * std::min(radius_rings, kGridWithinCells) + 1;
+        long long cells = 1;
+        for (int d = 0; d < k; ++d)
+            cells = std::min(cells * side, kGridWithinCells + 1);
+        if (cells <= kGridWithinCells)
+            p.rmax = (int)radius_rings;
+    }
     p.waves = GRID_BLOCK / 64;
     p.blocks = (unsigned)((m + p.waves - 1) / p.waves);
     p.scratch_bytes = (size_t)m * (size_t)K * sizeof(u64);
@@ -724,7 +666,8 @@ GridTopkPlan knn_grid_topk_plan(int k, int K, int m, bool has_grid, int path, bo
 // ev0 / ev1 (nullable) bracket the grid kernel.  *gate_out = the give-up word (knn_index_last_stats reads it back).
 hipError_t knn_grid_query_topk(const GridState *gs, const GridTopkPlan &plan, int slot, int m, int K, long long n, const float *q,
                                const float *r, long long base, u64 *keys, int init, u64 *scratch, u64 *part, size_t part_bytes,
-                               int num_cu, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, const unsigned **gate_out)
+                               int num_cu, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, const unsigned **gate_out, int within,
+                               float max_dist2)
 {
     *gate_out = nullptr;
     if (!gs || !gs->usable || !plan.use || m <= 0 || K < 1 || K > KNN_WAVE || (!init && !scratch))
@@ -736,9 +679,13 @@ hipError_t knn_grid_query_topk(const GridState *gs, const GridTopkPlan &plan, in
     const dim3 grid(plan.blocks), block(GRID_BLOCK);
     if (ev0)
         GTRY(hipEventRecord(ev0, s));
-#define GRID_TOPK(KDV)                                                                                                          \
-    hipLaunchKernelGGL(knn_grid_topk_kernel<KDV>, grid, block, 0, s, q, m, K, gs->geom, gs->start, gs->pts, gs->orig, base, lists, \
-                       plan.rmax, giveup, giveup_next)
+#define GRID_TOPK(KDV)                                                                                                             \
+    if (within)                                                                                                                    \
+        hipLaunchKernelGGL(knn_grid_within_kernel<KDV>, grid, block, 0, s, q, m, K, gs->geom, gs->start, gs->pts, gs->orig, base,  \
+                           lists, plan.rmax, giveup, giveup_next, max_dist2);                                                      \
+    else                                                                                                                           \
+        hipLaunchKernelGGL(knn_grid_topk_kernel<KDV>, grid, block, 0, s, q, m, K, gs->geom, gs->start, gs->pts, gs->orig, base,    \
+                           lists, plan.rmax, giveup, giveup_next)
     switch (gs->geom.k) {
     case 1: GRID_TOPK(1); break;
     case 2: GRID_TOPK(2); break;
@@ -750,10 +697,25 @@ hipError_t knn_grid_query_topk(const GridState *gs, const GridTopkPlan &plan, in
     if (ev1)
         GTRY(hipEventRecord(ev1, s));
     *gate_out = giveup;
-    GTRY(knn_exact_topk_launch(gs->geom.k, m, K, n, base, nullptr, q, r, lists, 1, part, part_bytes, num_cu, s, giveup));
+    GTRY(knn_exact_topk_launch(gs->geom.k, m, K, n, base, nullptr, q, r, lists, 1, part, part_bytes, num_cu, s, giveup,
+                               within ? knn_topk_limit_key(max_dist2) : kKeyInit));
     if (!init)
         GTRY(knn_topk_merge_launch(m, K, scratch, keys, s));
     return hipSuccess;
+}
+
+long long knn_grid_radius_rings(const GridState *gs, float max_dist2)
+{
+    if (!gs || !gs->usable || !(max_dist2 >= 0.0f))
+        return 0;
+    double wmin = INFINITY;
+    for (int d = 0; d < gs->geom.k; ++d)
+        if (gs->geom.g[d] > 1 && gs->geom.w[d] > 0.0)
+            wmin = std::min(wmin, (double)gs->geom.w[d]);
+    if (!(wmin < INFINITY))
+        return 0;
+    const double rings = ceil(sqrt((double)max_dist2) / wmin) + 1.0;
+    return rings < 0x1p30 ? (long long)rings : 1ll << 30;
 }
 
 void knn_grid_info(const GridState *gs, long long info[4])
