@@ -517,6 +517,13 @@ int knn_debug_grid_topk_plan(const long long in[6], long long out[6]);
  * raise out[1] to themselves while a walk of that many rings stays within 2^15 cells, (2 rings + 1)^k; beyond that the plain
  * value and the give-up rule stand. */
 int knn_debug_grid_within_plan(const long long in[7], long long out[6]);
+/* Test hook (host arithmetic only, no GPU needed): the bytes a workspace slot's three top-K buffers must hold for a call.
+ * in = {the way that answers it (knn_index_last_stats' [0]: 1 exact, 2 filter, 3 grid, 4 cell-pruned), m, K, the shard's rows,
+ * the device's compute units, 1 if the call carries KNN_QUERY_INIT_KEYS, 1 if it has a finite radius, the queries of a pass of
+ * the cell-pruned way (0 on the others), out[4] of knn_debug_grid_topk_plan on the grid way (0 on the others)};
+ * out = {the exact top-K scan's per-slice lists; the filter ways' candidate lists and counters, or a folding grid call's lists;
+ * the unclipped lists of a radius call on the filter ways}. */
+int knn_debug_topk_scratch(const long long in[9], long long out[3]);
 /* Test hook (host arithmetic only, no GPU needed): what an index is built with.  in = {k, n_local, 1 if the rows are on the
  * device, build_filter (-1 library policy: knn_index_create; 0 none, 1 the MFMA filter layouts, 2 cell-sorted), build_grid (-1
  * library policy, 0, 1), and the options path, cells, ingest, cells_build};

@@ -33,7 +33,7 @@ EXPORTED_SYMBOLS = [
     "knn_index_seed_export", "knn_index_seed_attach", "knn_geom_first_cell",
     "knn_index_query_topk", "knn_keys_topk_merge", "knn_index_query_topk_host", "knn_debug_grid_topk_plan",
     "knn_index_query_topk_within", "knn_index_query_topk_within_host", "knn_debug_grid_within_plan", "knn_debug_within_bound",
-    "knn_debug_frame_dup",
+    "knn_debug_frame_dup", "knn_debug_topk_scratch",
 ]
 QUERY_INIT_KEYS = 1   # KNN_QUERY_INIT_KEYS
 QUERY_TOPK_PARTIAL = 2   # KNN_QUERY_TOPK_PARTIAL
@@ -306,6 +306,21 @@ def debug_grid_within_plan(**inputs):
     f.argtypes = [ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)]
     _check(f(vin, out))
     return dict(zip(GRID_TOPK_PLAN, list(out)))
+
+
+TOPK_SCRATCH_INPUTS = ("way", "m", "K", "n", "num_cu", "init", "within", "pass_m", "grid_scratch_bytes")
+TOPK_SCRATCH_PLAN = ("part_bytes", "cand_bytes", "lists_bytes")
+
+
+def debug_topk_scratch(**inputs):
+    """knn_debug_topk_scratch: the bytes a workspace slot's three top-K buffers must hold for a call, for the inputs named in
+    TOPK_SCRATCH_INPUTS (way: WAY_EXACT .. WAY_CELLS).  Host arithmetic; works without a GPU."""
+    vin = (ctypes.c_longlong * len(TOPK_SCRATCH_INPUTS))(*[int(inputs[n]) for n in TOPK_SCRATCH_INPUTS])
+    out = (ctypes.c_longlong * len(TOPK_SCRATCH_PLAN))()
+    f = lib().knn_debug_topk_scratch
+    f.argtypes = [ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)]
+    _check(f(vin, out))
+    return dict(zip(TOPK_SCRATCH_PLAN, list(out)))
 
 
 INDEX_BUILD_INPUTS = ("k", "n_local", "refs_on_device", "build_filter", "build_grid", "path", "cells", "ingest", "cells_build")

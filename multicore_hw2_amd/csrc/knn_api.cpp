@@ -314,12 +314,12 @@ struct knn_index {
     bool sharded = false;        // a cell-range shard (knn_index_create_sharded): always served by the cell-pruned path
     ShardGeom geom;              // its copy of the global grid (filter.cells->geom points here)
     int rank = 0;
-    u64 *topk_part[KNN_SLOTS] = {};      // per slot: the exact top-K scan's per-slice lists (grown on first use)
-    size_t topk_bytes[KNN_SLOTS] = {};
-    u64 *topk_cand[KNN_SLOTS] = {};      // per slot: the filter top-K's candidate lists [m][cap] + counts [m] (grown on first use)
-    size_t topk_cand_bytes[KNN_SLOTS] = {};
-    u64 *topk_lists[KNN_SLOTS] = {};     // per slot: a radius call's unclipped lists [m][K] on the ways that clip behind (grown on first use)
-    size_t topk_lists_bytes[KNN_SLOTS] = {};
+    // per slot, grown on first use to what knn_topk_scratch_plan says (never shrunk): the exact top-K scan's per-slice lists; the
+    // filter ways' candidate lists and counters (the grid way: a folding call's lists); a radius call's unclipped lists
+    struct TopkSlot {
+        u64 *part = nullptr, *cand = nullptr, *lists = nullptr;
+        size_t part_bytes = 0, cand_bytes = 0, lists_bytes = 0;
+    } topk[KNN_SLOTS];
     // Calls on one index from several host threads are serialised (enqueueing a batch is ~20 us of host work; the GPU
     // work of different slots still overlaps): the workspaces' lazily grown buffers, the event list, the statistics and
     // the chain events are plain members.  Recursive: knn_index_query_host calls the keyed entry points.
@@ -797,10 +797,10 @@ void knn_index_destroy(knn_index *idx)
             pool_put(idx->device, idx->owned_refs, idx->owned_bytes);
         knn_filter_free(idx->filter);
         knn_grid_free(idx->grid);
-        for (int i = 0; i < KNN_SLOTS; ++i) {
-            (void)knn_dev_free(idx->topk_part[i]);
-            (void)knn_dev_free(idx->topk_cand[i]);
-            (void)knn_dev_free(idx->topk_lists[i]);
+        for (auto &t : idx->topk) {
+            (void)knn_dev_free(t.part);
+            (void)knn_dev_free(t.cand);
+            (void)knn_dev_free(t.lists);
         }
         knn_dev_free_end_synced();
         for (auto &ev : idx->events) {
@@ -886,6 +886,27 @@ QueryRoute knn_query_route(const QueryRouteInputs &in)
              t.n_outliers <= r.ccap / 2 && r.ccap >= 64 && (path == 2 || (path == 0 && m >= 5 && sized)))
         r.way = QueryWay::Filter;
     return r;
+}
+
+// What a slot's top-K buffers must hold for a call: the one place their sizes are decided (tests/test_topk_scratch_logic.py
+// restates the rules through knn_debug_topk_scratch).
+TopkScratchPlan knn_topk_scratch_plan(const TopkScratchInputs &in)
+{
+    TopkScratchPlan p;
+    const bool filter_way = in.way == QueryWay::Filter || in.way == QueryWay::Cells;
+    p.part_bytes = knn_topk_part_bytes(in.m, in.K, in.n, in.num_cu);
+    if (in.way == QueryWay::Cells) {   // the gated exact top-K of a pass sizes its lists by the pass's queries
+        p.part_bytes = std::max(p.part_bytes, knn_topk_part_bytes(in.pass_m, in.K, in.n, in.num_cu));
+        if (in.m % KNN_CELL_BATCH)
+            p.part_bytes = std::max(p.part_bytes, knn_topk_part_bytes(in.m % KNN_CELL_BATCH, in.K, in.n, in.num_cu));
+    }
+    if (filter_way)   // candidate lists [m][ccap], then the counters [m]
+        p.cand_bytes = (size_t)in.m * knn_topk_ccap(in.K, in.m) * sizeof(u64) + (size_t)in.m * sizeof(unsigned);
+    else if (in.way == QueryWay::Grid && !in.init)
+        p.cand_bytes = in.grid_scratch_bytes;
+    if (filter_way && in.within)
+        p.lists_bytes = (size_t)in.m * (size_t)in.K * sizeof(u64);
+    return p;
 }
 
 namespace {
@@ -1077,103 +1098,108 @@ namespace {
 // key in their kernels, the cell-pruned scan of a one-frame layout caps its bound with it, and the filter ways — whose lists may
 // hold rows just beyond it, or come from a fallback — make their top-K into the slot's list scratch, which one clip launch turns
 // into the caller's keys.
-int query_topk(knn_index *idx, int slot, int m, int K, const float *queries_dev, float max_dist2, u64 *keys, int *indices_dev,
-               hipStream_t s, unsigned flags, const char *who)
+int query_topk(knn_index *idx, int slot, TopkCall call, int *indices_dev, unsigned flags, const char *who)
 {
     std::lock_guard<std::recursive_mutex> lock(idx->mu);
     DeviceGuard guard(idx->device);
     if (!guard.ok)
         return fail(KNN_EHIP, who, "hipSetDevice failed");
-    const int init = (flags & KNN_QUERY_INIT_KEYS) != 0u;
-    const bool within = max_dist2 < INFINITY;
-    const u64 lim = within ? knn_topk_limit_key(max_dist2) : kKeyInit;
+    hipStream_t s = call.stream;
+    const int m = call.m, K = call.K, mk = m * K;
+    call.init = (flags & KNN_QUERY_INIT_KEYS) != 0u;
     idx->stats[0] = 1;
     idx->stats[1] = 0;
     idx->stats[2] = 0;
     idx->grid_topk_gate = nullptr;
     idx->last_slot = slot;
-    const int mk = m * K;
     if (idx->n == 0) {   // an empty shard adds nothing
-        if (init)
-            HIP_TRY(knn_keys_fill_launch(keys, mk, s));
+        if (call.init)
+            HIP_TRY(knn_keys_fill_launch(call.keys, mk, s));
         if (indices_dev)
-            HIP_TRY(knn_keys_unpack_launch(keys, mk, indices_dev, s));
+            HIP_TRY(knn_keys_unpack_launch(call.keys, mk, indices_dev, s));
         return KNN_OK;
     }
     const QueryRoute route = knn_query_route(route_inputs(idx, m, K, flags));
-    const CellTopkPlan &tp = route.topk;
-    idx->stats[0] = (long long)route.way;
-    // the exact top-K scan's per-slice lists (the gated exact top-K of a pruned pass sizes its lists by the pass's queries)
-    size_t need = knn_topk_part_bytes(m, K, idx->n, idx->num_cu);
-    if (tp.use) {
-        need = std::max(need, knn_topk_part_bytes(tp.pass_m, K, idx->n, idx->num_cu));
-        if (m % KNN_CELL_BATCH)
-            need = std::max(need, knn_topk_part_bytes(m % KNN_CELL_BATCH, K, idx->n, idx->num_cu));
-    }
-    u64 *&part = idx->topk_part[slot];
-    size_t &part_bytes = idx->topk_bytes[slot];
-    KNN_TRY(slot_buffer_grow(part, part_bytes, need));
+    const QueryWay way = route.way;
+    idx->stats[0] = (long long)way;
+    // the grid way (KNN_QUERY_TOPK_GRID) — a radius call: the rings its radius spans size rmax, the kernel's face bound decides
+    GridTopkPlan gp;
+    if (way == QueryWay::Grid)
+        gp = knn_grid_topk_plan(idx->k, K, m, true, 0, true, call.within() ? knn_grid_radius_rings(idx->grid, call.max_dist2) : 0);
+    // the slot's scratch, grown before the first launch
+    const TopkScratchPlan sp = knn_topk_scratch_plan({way, m, K, idx->n, idx->num_cu, call.init != 0, call.within(), route.topk.pass_m,
+                                                      gp.scratch_bytes});
+    knn_index::TopkSlot &ts = idx->topk[slot];
+    KNN_TRY(slot_buffer_grow(ts.part, ts.part_bytes, sp.part_bytes));
+    KNN_TRY(slot_buffer_grow(ts.cand, ts.cand_bytes, sp.cand_bytes));
+    KNN_TRY(slot_buffer_grow(ts.lists, ts.lists_bytes, sp.lists_bytes));
     EventPair *ev = nullptr;
     KNN_TRY(next_event_pair(idx, false, &ev));
-    hipEvent_t ev0 = ev ? ev->first : nullptr, ev1 = ev ? ev->second : nullptr;
-    // the filter ways' candidate lists [m][ccap] and counts [m]
-    u64 *&cand = idx->topk_cand[slot];
-    if (route.way == QueryWay::Grid) {
-        // the grid way (KNN_QUERY_TOPK_GRID): the kernel's lists are the caller's keys, or — a folding call — the slot's scratch
-        // (a radius call: the rings its radius spans size rmax, the kernel's face bound decides)
-        const GridTopkPlan gp = knn_grid_topk_plan(idx->k, K, m, true, 0, true, within ? knn_grid_radius_rings(idx->grid, max_dist2) : 0);
-        if (!init)
-            KNN_TRY(slot_buffer_grow(cand, idx->topk_cand_bytes[slot], gp.scratch_bytes));
-        idx->stats[3] = 0;
-        HIP_TRY(knn_grid_query_topk(idx->grid, gp, slot, m, K, idx->n, queries_dev, idx->refs, idx->base, keys, init, cand, part,
-                                    part_bytes, idx->num_cu, s, ev0, ev1, &idx->grid_topk_gate, within, max_dist2));
-        if (indices_dev)
-            HIP_TRY(knn_keys_unpack_launch(keys, mk, indices_dev, s));
-        return KNN_OK;
-    }
+    call.k = idx->k;
+    call.n = idx->n;
+    call.base = idx->base;
+    // a cell-range shard's keys carry its rows' global numbers (gids); an index-range shard's base + row
+    call.gids = idx->sharded && idx->filter.cells ? idx->filter.cells->gids : nullptr;
+    call.r = idx->refs;
+    call.num_cu = idx->num_cu;
+    call.ev0 = ev ? ev->first : nullptr;
+    call.ev1 = ev ? ev->second : nullptr;
+    call.part = ts.part;
+    call.part_bytes = ts.part_bytes;
+    call.cand = ts.cand;
+    call.ccap = route.ccap;
+    const bool filter_way = way == QueryWay::Filter || way == QueryWay::Cells;
+    call.ccount = filter_way ? (unsigned *)(ts.cand + (size_t)m * route.ccap) : nullptr;
     // a radius call on the filter ways: the top-K starts the slot's list scratch, the clip behind writes or folds the caller's keys
-    u64 *const caller_keys = keys;
-    const int caller_init = init;
-    const bool clip = within && route.way != QueryWay::Exact;
-    if (clip) {
-        KNN_TRY(slot_buffer_grow(idx->topk_lists[slot], idx->topk_lists_bytes[slot], (size_t)mk * sizeof(u64)));
-        keys = idx->topk_lists[slot];
-    }
-    if (route.way != QueryWay::Exact)
-        KNN_TRY(slot_buffer_grow(cand, idx->topk_cand_bytes[slot], (size_t)m * route.ccap * sizeof(u64) + (size_t)m * sizeof(unsigned)));
-    unsigned *ccount = route.way != QueryWay::Exact ? (unsigned *)(cand + (size_t)m * route.ccap) : nullptr;
-    switch (route.way) {
+    const bool clip = filter_way && call.within();
+    const TopkCall way_call = clip ? call.writing(ts.lists) : call;
+    switch (way) {
+    case QueryWay::Grid:
+        // the kernel's lists are the caller's keys, or — a folding call — the slot's scratch
+        idx->stats[3] = 0;
+        HIP_TRY(knn_grid_query_topk(idx->grid, gp, slot, call, &idx->grid_topk_gate));
+        break;
     case QueryWay::Cells:
         // layouts in the shard's frame — or, with KNN_QUERY_TOPK_FRAMES, in per-cell frames —, in passes of KNN_CELL_BATCH queries
         // (option `topk_cells`)
-        HIP_TRY(knn_filter_query_topk_cells(idx->filter, tp, slot, m, K, queries_dev, idx->refs, idx->base, keys, clip || init, cand, ccount,
-                                            part, part_bytes, idx->num_cu, s, ev0, ev1, max_dist2));
+        HIP_TRY(knn_filter_query_topk_cells(idx->filter, route.topk, slot, way_call));
         break;
     case QueryWay::Filter: {
         FilterCallOptions opt = filter_call_options();
         opt.run_thresholds = 2;   // running thresholds are a 1-NN argument; the non-running sample stride with them
         opt.sample_stride = 0;
         opt.topk = K;
-        HIP_TRY(knn_filter_query_topk(idx->filter, opt, slot, m, queries_dev, idx->refs, idx->base, keys, clip || init, cand, ccount,
-                                      route.ccap, part, part_bytes, idx->num_cu, s, ev0, ev1));
+        TopkCall plain = way_call;   // the dense scan has no use for the radius: it is handed none
+        plain.max_dist2 = INFINITY;
+        HIP_TRY(knn_filter_query_topk(idx->filter, opt, slot, plain));
         break;
     }
-    default: {   // (QueryWay::Exact; the grid way was taken above)
-        // a cell-range shard's keys carry its rows' global numbers (gids); an index-range shard's base + row
-        const unsigned *gids = idx->sharded && idx->filter.cells ? idx->filter.cells->gids : nullptr;
+    case QueryWay::Exact:
         if (ev)
-            HIP_TRY(hipEventRecord(ev0, s));
-        HIP_TRY(knn_exact_topk_launch(idx->k, m, K, idx->n, idx->base, gids, queries_dev, idx->refs, keys, init, part, part_bytes,
-                                      idx->num_cu, s, nullptr, lim));
+            HIP_TRY(hipEventRecord(call.ev0, s));
+        HIP_TRY(knn_exact_topk_launch(call, nullptr, true));
         if (ev)
-            HIP_TRY(hipEventRecord(ev1, s));
-    }
+            HIP_TRY(hipEventRecord(call.ev1, s));
+        break;
     }
     if (clip)
-        HIP_TRY(knn_topk_clip_launch(m, K, keys, lim, caller_keys, caller_init, s));
+        HIP_TRY(knn_topk_clip_launch(m, K, ts.lists, call.limit_key(), call.keys, call.init, s));
     if (indices_dev)
-        HIP_TRY(knn_keys_unpack_launch(caller_keys, mk, indices_dev, s));
+        HIP_TRY(knn_keys_unpack_launch(call.keys, mk, indices_dev, s));
     return KNN_OK;
+}
+
+// What the caller of a top-K entry states; query_topk adds the index's side and the slot's scratch.
+TopkCall topk_call_of(int m, int K, const float *queries_dev, unsigned long long *keys_dev, void *stream, float max_dist2)
+{
+    TopkCall c;
+    c.m = m;
+    c.K = K;
+    c.q = queries_dev;
+    c.keys = (u64 *)keys_dev;
+    c.stream = (hipStream_t)stream;
+    c.max_dist2 = max_dist2;
+    return c;
 }
 
 // The arguments both top-K entries reject (the four flags they admit: values up to 15).
@@ -1192,8 +1218,7 @@ int knn_index_query_topk(knn_index *idx, int slot, int m, int K, const float *qu
 {
     if (topk_args_bad(idx, slot, m, K, queries_dev, keys_dev, flags))
         return fail(KNN_EINVAL, "knn_index_query_topk: bad arguments (1 <= K <= 64, m >= 1, slot 0 .. 7)");
-    return query_topk(idx, slot, m, K, queries_dev, INFINITY, (u64 *)keys_dev, indices_dev, (hipStream_t)stream, flags,
-                      "knn_index_query_topk");
+    return query_topk(idx, slot, topk_call_of(m, K, queries_dev, keys_dev, stream, INFINITY), indices_dev, flags, "knn_index_query_topk");
 }
 
 int knn_index_query_topk_within(knn_index *idx, int slot, int m, int K, const float *queries_dev, float max_dist2,
@@ -1202,8 +1227,8 @@ int knn_index_query_topk_within(knn_index *idx, int slot, int m, int K, const fl
     if (topk_args_bad(idx, slot, m, K, queries_dev, keys_dev, flags) || !(max_dist2 >= 0.0f))
         return fail(KNN_EINVAL, "knn_index_query_topk_within: bad arguments (1 <= K <= 64, m >= 1, slot 0 .. 7, max_dist2 >= 0 and not NaN)");
     // (-0 counts as 0: the limit key is made from the bits)
-    return query_topk(idx, slot, m, K, queries_dev, max_dist2 == 0.0f ? 0.0f : max_dist2, (u64 *)keys_dev, indices_dev,
-                      (hipStream_t)stream, flags, "knn_index_query_topk_within");
+    return query_topk(idx, slot, topk_call_of(m, K, queries_dev, keys_dev, stream, max_dist2 == 0.0f ? 0.0f : max_dist2), indices_dev,
+                      flags, "knn_index_query_topk_within");
 }
 
 int knn_keys_topk_merge(int device, int m, int K, const unsigned long long *a_dev, unsigned long long *b_dev, void *stream)
@@ -1508,6 +1533,19 @@ int knn_debug_grid_within_plan(const long long in[7], long long out[6])
         return fail(KNN_EINVAL, "knn_debug_grid_within_plan: bad arguments (1 <= k <= 4, 1 <= K <= 64, m >= 1, path 0 .. 3, rings >= 0)");
     const GridTopkPlan p = knn_grid_topk_plan((int)in[0], (int)in[1], (int)in[2], in[3] != 0, (int)in[4], in[5] != 0, in[6]);
     const long long v[6] = {p.use, p.rmax, p.blocks, p.waves, (long long)p.scratch_bytes, p.launches};
+    memcpy(out, v, sizeof v);
+    return KNN_OK;
+}
+
+int knn_debug_topk_scratch(const long long in[9], long long out[3])
+{
+    if (!in || !out || in[0] < 1 || in[0] > 4 || in[1] < 1 || in[1] > INT_MAX || in[2] < 1 || in[2] > KNN_TOPK_MAX ||
+        in[1] * in[2] > INT_MAX || in[3] < 0 || in[4] < 1 || in[4] > INT_MAX || in[7] < 0 || in[7] > KNN_CELL_BATCH || in[8] < 0)
+        return fail(KNN_EINVAL, "knn_debug_topk_scratch: bad arguments (way 1 .. 4, m >= 1, 1 <= K <= 64, n >= 0, num_cu >= 1, "
+                                "0 <= pass_m <= 1024, grid_scratch_bytes >= 0)");
+    const TopkScratchPlan p = knn_topk_scratch_plan({(QueryWay)in[0], (int)in[1], (int)in[2], in[3], (int)in[4], in[5] != 0, in[6] != 0,
+                                                     (int)in[7], (size_t)in[8]});
+    const long long v[3] = {(long long)p.part_bytes, (long long)p.cand_bytes, (long long)p.lists_bytes};
     memcpy(out, v, sizeof v);
     return KNN_OK;
 }

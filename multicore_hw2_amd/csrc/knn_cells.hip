@@ -3027,13 +3027,14 @@ CellTopkPlan knn_cells_topk_plan(const CellTopkInputs &in)
     return t;
 }
 
-hipError_t knn_cells_query_topk(FilterState &st, FilterWorkspace &w, const CellTopkPlan &tp, int m, int K, const float *q, const float *r,
-                                long long base, u64 *keys, bool init_keys, u64 *cand, unsigned *ccount, u64 *part, size_t part_bytes,
-                                int num_cu, bool timed, hipStream_t s, float max_dist2)
+hipError_t knn_cells_query_topk(FilterState &st, FilterWorkspace &w, const CellTopkPlan &tp, bool timed, const TopkCall &call)
 {
     const CellIndex &c = *st.cells;
     const CellQueryPlan &p = tp.batch;
-    if (!tp.use || m > tp.pass_m || tp.scan.self || tp.scan.ctr != c.centred || p.prep_ctr != c.centred || (c.geom && (!c.gids || base != 0)))
+    const int m = call.m;
+    hipStream_t s = call.stream;
+    if (!tp.use || m > tp.pass_m || tp.scan.self || tp.scan.ctr != c.centred || p.prep_ctr != c.centred || call.ccap != tp.ccap ||
+        call.gids != c.gids || (c.geom && (!c.gids || call.base != 0)))
         return hipErrorInvalidValue;
     const CellKernel scan = cells_records_kernel(tp.scan);
     FTRY(ensure_cells_workspace(st, w, m, p, scan));
@@ -3053,9 +3054,9 @@ hipError_t knn_cells_query_topk(FilterState &st, FilterWorkspace &w, const CellT
     // prep kernel scores a seed cell of another rank from the layer's tiles, as the 1-NN form does —, and gids on the keys from the
     // moment they are candidates (the select sorts them, a fold compares them with other ranks'): CellFinal stays empty, nothing is
     // translated behind the select, while a 1-NN batch on the same slot keeps translating in its own last kernel.
-    const CellBatch b{st, c, w, p, m, m_padded, q, r, base, keys, nullptr, CellFinal{nullptr, nullptr, 0}, cells_self(p, c, w, m_padded),
-                      cells_seed_layer(c), ctl_next, s, K, max_dist2};
-    FTRY(hipMemsetAsync(ccount, 0, (size_t)m * sizeof(unsigned), s));
+    const CellBatch b{st, c, w, p, m, m_padded, call.q, call.r, call.base, call.keys, nullptr, CellFinal{nullptr, nullptr, 0},
+                      cells_self(p, c, w, m_padded), cells_seed_layer(c), ctl_next, s, call.K, call.max_dist2};
+    FTRY(hipMemsetAsync(call.ccount, 0, (size_t)m * sizeof(unsigned), s));
     cells_prep_topk_launch(b);
     FTRY(hipGetLastError());
     cells_match_kernel(p.match_waves).launch(b);
@@ -3069,13 +3070,26 @@ hipError_t knn_cells_query_topk(FilterState &st, FilterWorkspace &w, const CellT
     // every row of every record with v0's arithmetic -> the queries' candidate lists, behind the distance gate knn_topk_gate(Dup_q)
     // (the slices, then the shared overflow area as a list of one), the out-of-box rows, the select; all of them look at FALLBACK, which a query nothing bounds, fewer than K
     // real seed rows, an over-full record area or candidate list raise
-    FTRY(knn_topk_filter_finish(st.k, m, K, st.ntiles * 32, base, q, r, w.records, nullptr, w.counts, w.nlists, w.slice, w.ctl_cur,
-                                RerankPieces(), c.perm, st.n_outliers, st.outliers, cand, ccount, tp.ccap, keys, init_keys ? 1 : 0, s,
-                                w.records + w.ovf_base, w.ctl_cur + KNN_CTL_RECORDS, w.ovf_cap, w.dup,
-                                (float)(1.0 / ((double)st.sigma * (double)st.sigma)), st.ref_norms, c.gids));
-    // gated: the exact top-K answers a pass that raised FALLBACK; it folds into the keys the select left alone
-    return knn_exact_topk_launch(st.k, m, K, st.n, base, c.gids, q, r, keys, init_keys ? 1 : 0, part, part_bytes, num_cu, s,
-                                 w.ctl_cur + KNN_CTL_FALLBACK);
+    TopkRecords rs;
+    rs.positions = st.ntiles * 32;
+    rs.rec = w.records;
+    rs.counts = w.counts;
+    rs.nlists = w.nlists;
+    rs.slice = w.slice;
+    rs.ctl = w.ctl_cur;
+    rs.perm = c.perm;
+    rs.n_outliers = st.n_outliers;
+    rs.outliers = st.outliers;
+    rs.ovf_rec = w.records + w.ovf_base;
+    rs.ovf_count = w.ctl_cur + KNN_CTL_RECORDS;
+    rs.ovf_slice = w.ovf_cap;
+    rs.gate_dup = w.dup;
+    rs.inv_sigma2 = (float)(1.0 / ((double)st.sigma * (double)st.sigma));
+    rs.pos_norms = st.ref_norms;
+    FTRY(knn_topk_filter_finish(call, rs));
+    // gated: the exact top-K answers a pass that raised FALLBACK; it folds into the keys the select left alone (no limit: the caller
+    // clips a radius call's lists)
+    return knn_exact_topk_launch(call, w.ctl_cur + KNN_CTL_FALLBACK, false);
 }
 
 // Test hook (host arithmetic, no GPU): knn_threshold's Dup for a seed score u — out = {thr, Dup as the prep kernel stores it (fp32,

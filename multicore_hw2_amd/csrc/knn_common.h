@@ -57,14 +57,6 @@ hipError_t knn_synth_fill_launch(float *dst, long long count, u64 seed, long lon
 #define KNN_TOPK_CHUNK 65536   // queries per scan launch of the exact top-K (bounds the per-slice lists)
 // Bytes of the per-slice list buffer the exact top-K scan of m queries, K neighbours, n rows uses (part of a workspace slot).
 size_t knn_topk_part_bytes(int m, int K, long long n, int num_cu);
-// keys[m][K] <- the K smallest of (keys unless init, this shard's finite-distance rows), sorted; v0 arithmetic.  Global
-// numbers: gids[row] when gids != nullptr, else base + row.  part: part_bytes of scratch (knn_topk_part_bytes), stream-ordered.
-// gate != nullptr: the launches do nothing unless *gate != 0 (the filter top-K's FALLBACK word).
-// lim (knn_index_query_topk_within): only rows whose key is below it are candidates (knn_topk_limit_key); KNN_KEY_INIT = none.
-// The keys the call folds into are the caller's and are not clipped.
-hipError_t knn_exact_topk_launch(int k, int m, int K, long long n, long long base, const unsigned *gids, const float *q,
-                                 const float *r, u64 *keys, int init, u64 *part, size_t part_bytes, int num_cu,
-                                 hipStream_t stream, const unsigned *gate = nullptr, u64 lim = kKeyInit);
 // The limit key of a radius: a key is within max_dist2 >= 0 (not NaN; -0 counts as 0) exactly when it is below
 // (bits(max_dist2) + 1) << 32 — the fp32 compare E <= max_dist2 on the key's high word, equality inside.  +INF gives a key above
 // KNN_KEY_INIT: no limit.
@@ -74,27 +66,87 @@ static inline u64 knn_topk_limit_key(float max_dist2)
     memcpy(&bits, &max_dist2, sizeof bits);
     return ((u64)(bits & 0x7FFFFFFFu) + 1ull) << 32;
 }
+// One top-K call (knn_index_query_topk, knn_index_query_topk_within) as every way that answers it takes it: query_topk
+// (knn_api.cpp) fills it once, the launchers read it and add only what is their own.
+struct TopkCall {
+    int k = 0, m = 0, K = 0;       // dimension, queries, neighbours per query
+    long long n = 0, base = 0;     // the shard's rows; global number of row 0 ...
+    const unsigned *gids = nullptr;   // ... or, cell-range shards (base 0), of every row; null: base + row
+    const float *q = nullptr, *r = nullptr;   // device [m][k], [n][k]
+    u64 *keys = nullptr;           // device [m][K]: written (init) or folded into, sorted lists
+    int init = 0;
+    int num_cu = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;   // nullable: bracket the way's dominant kernel
+    float max_dist2 = INFINITY;    // the radius, squared (>= 0, never -0); +INF: a plain call
+    // the slot's scratch (knn_topk_scratch_plan): the exact top-K scan's per-slice lists; the filter ways' candidate lists
+    // [m][ccap] and counters [m] — on the grid way cand is a folding call's lists [m][K], ccount null
+    u64 *part = nullptr;
+    size_t part_bytes = 0;
+    u64 *cand = nullptr;
+    unsigned *ccount = nullptr;
+    unsigned ccap = 0;
+
+    bool within() const { return max_dist2 < INFINITY; }
+    // the one place a radius becomes a limit key: only keys below it are candidates; KNN_KEY_INIT = none
+    u64 limit_key() const { return within() ? knn_topk_limit_key(max_dist2) : kKeyInit; }
+    // the same call writing its lists to `lists` from scratch (a way whose answer something behind it turns into the keys)
+    TopkCall writing(u64 *lists) const
+    {
+        TopkCall c = *this;
+        c.keys = lists;
+        c.init = 1;
+        return c;
+    }
+    // queries [q0, q0 + mb) of the call: a pass of the cell-pruned way
+    TopkCall pass(int q0, int mb) const
+    {
+        TopkCall c = *this;
+        c.m = mb;
+        c.q = q + (size_t)q0 * k;
+        c.keys = keys + (size_t)q0 * K;
+        c.cand = cand + (size_t)q0 * ccap;
+        c.ccount = ccount + q0;
+        return c;
+    }
+};
+// c.keys[m][K] <- the K smallest of (keys unless init, this shard's finite-distance rows), sorted; v0 arithmetic.  c.part:
+// c.part_bytes of scratch (knn_topk_part_bytes), stream-ordered.
+// gate != nullptr: the launches do nothing unless *gate != 0 (the filter top-K's FALLBACK word, the grid's give-up word).
+// limit: the scan carries the call's radius — only rows whose key is below c.limit_key() are candidates; false: every row is (the
+// ways that clip behind).  The keys the call folds into are the caller's and are not clipped.
+hipError_t knn_exact_topk_launch(const TopkCall &c, const unsigned *gate, bool limit);
 // keys[j] <- lists[j] with every key >= lim turned into KNN_KEY_INIT (init), or the K smallest of that and keys[j] (a fold).
 hipError_t knn_topk_clip_launch(int m, int K, const u64 *lists, u64 lim, u64 *keys, int init, hipStream_t stream);
 // Filter top-K: umin[0][q] <- K-th smallest finite per-block minimum (one row for knn_thr_kernel).
 hipError_t knn_topk_umin_launch(float *umin, int nb, int m_padded, int K, hipStream_t stream);
+// The records side of a filter top-K batch: what the scan left in its workspace and the layout it scanned.
+struct TopkRecords {
+    long long positions = 0;       // rows the records can name (a cell-sorted layout: its padded positions)
+    const u64 *rec = nullptr;      // nlists slices of `slice` records; counts[i]: records list i produced (may exceed slice)
+    const unsigned short *rec_rows = nullptr;   // nullable: a row mask next to every record
+    const unsigned *counts = nullptr;
+    unsigned nlists = 0, slice = 0;
+    unsigned *ctl = nullptr;       // the batch's control words (FALLBACK)
+    RerankPieces pieces;
+    const unsigned *perm = nullptr;   // nullable: the records name positions of a permuted layout
+    unsigned n_outliers = 0;       // rows outside the robust box: never in the scan, every one a candidate
+    const unsigned *outliers = nullptr;
+    // the cell-pruned scan's shared overflow area, re-ranked as a list of one: ovf_count records (a device word) at ovf_rec,
+    // room ovf_slice — more than that raises FALLBACK
+    const u64 *ovf_rec = nullptr;
+    const unsigned *ovf_count = nullptr;
+    unsigned ovf_slice = 0;
+    // the cell-pruned top-K's distance gate: the pass's Dup_q values and sigma^-2 (knn_topk_gate); null: every finite key is a
+    // candidate (the filter top-K).  With the gate: the layout's norms by position (+INF: padding, out-of-box rows — not
+    // re-ranked), and c.gids (cell-range shards, base 0) become the candidates' index half
+    const float *gate_dup = nullptr;
+    float inv_sigma2 = 0.0f;
+    const float *pos_norms = nullptr;
+};
 // Filter top-K after the scan: records + outlier rows -> per-query candidate lists (overflow -> FALLBACK), then, unless
-// FALLBACK, keys <- K smallest of (keys unless init, candidates).
-hipError_t knn_topk_filter_finish(int k, int m, int K, long long positions, long long base, const float *q, const float *r,
-                                  const u64 *rec, const unsigned short *rec_rows, const unsigned *counts, unsigned nlists,
-                                  unsigned slice, unsigned *ctl, RerankPieces pieces, const unsigned *perm,
-                                  unsigned n_outliers, const unsigned *outliers, u64 *cand, unsigned *ccount, unsigned ccap,
-                                  u64 *keys, int init, hipStream_t stream,
-                                  // the cell-pruned scan's shared overflow area, re-ranked as a list of one: ovf_count records
-                                  // (a device word) at ovf_rec, room ovf_slice — more than that raises FALLBACK
-                                  const u64 *ovf_rec = nullptr, const unsigned *ovf_count = nullptr, unsigned ovf_slice = 0u,
-                                  // the cell-pruned top-K's distance gate: the pass's Dup_q values and sigma^-2 (knn_topk_gate);
-                                  // null: every finite key is a candidate (the filter top-K)
-                                  const float *gate_dup = nullptr, float inv_sigma2 = 0.0f,
-                                  // with the gate: the layout's norms by position (+INF: padding, out-of-box rows — not re-ranked)
-                                  const float *pos_norms = nullptr,
-                                  // with the gate, cell-range shards (base 0): the candidates' index half is gids[row]
-                                  const unsigned *gids = nullptr);
+// FALLBACK, c.keys <- K smallest of (keys unless init, candidates).
+hipError_t knn_topk_filter_finish(const TopkCall &c, const TopkRecords &rs);
 // b[j] <- the K smallest of a[j] and b[j] (both sorted lists of K keys), sorted.
 hipError_t knn_topk_merge_launch(int m, int K, const u64 *a, u64 *b, hipStream_t stream);
 
@@ -447,6 +499,23 @@ struct QueryRoute {
     CellTopkPlan topk;             // top-K: knn_cells_topk_plan's answer (use == (way == Cells))
 };
 QueryRoute knn_query_route(const QueryRouteInputs &in);
+// What a slot's three top-K buffers must hold for a call (host arithmetic only; knn_debug_topk_scratch): `part` the exact top-K
+// scan's per-slice lists — on the cell-pruned way also at a pass's and at the last pass's queries, whose gated exact top-K sizes
+// its lists by them —, `cand` the filter ways' candidate lists [m][knn_topk_ccap] + counters [m] or a folding grid call's lists,
+// `lists` the unclipped lists [m][K] of a radius call on the ways that clip behind.
+struct TopkScratchInputs {
+    QueryWay way = QueryWay::Exact;
+    int m = 0, K = 0;
+    long long n = 0;
+    int num_cu = 0;
+    bool init = false, within = false;
+    int pass_m = 0;                // QueryWay::Cells: CellTopkPlan::pass_m
+    size_t grid_scratch_bytes = 0; // QueryWay::Grid: GridTopkPlan::scratch_bytes
+};
+struct TopkScratchPlan {
+    size_t part_bytes = 0, cand_bytes = 0, lists_bytes = 0;
+};
+TopkScratchPlan knn_topk_scratch_plan(const TopkScratchInputs &in);
 
 // What index_create_impl builds, decided up front.  What only the run can tell stays there: no streams for an ingest, a grid
 // build that rules the grid out, a cell sort under the copy that reports unusable, no memory for the layouts.
@@ -526,13 +595,11 @@ void knn_cells_workspace_free(FilterWorkspace &w);
 // init_keys: the batch's keys are set to (+INF, 0) by the first kernel of the chain.
 hipError_t knn_cells_query(FilterState &st, FilterWorkspace &w, FilterCallOptions opt, int m, const float *q_dev, const float *r_dev,
                            long long base, u64 *keys, int num_cu, bool timed, hipStream_t s, bool init_keys, int *out_idx = nullptr);
-// max_dist2 finite (a radius call, one-frame layouts): the prep kernel caps Dup_q with the radius (knn_threshold_within).
-// One pass of <= KNN_CELL_BATCH queries of a top-K call: prep (K-th seed bound) -> match -> record-only scan -> re-rank of the
-// slices and of the shared overflow area -> out-of-box rows -> select -> the exact top-K, gated on FALLBACK.  keys: the pass's
-// [m][K]; cand / ccount: the pass's candidate lists [m][tp.ccap] and counters [m].
-hipError_t knn_cells_query_topk(FilterState &st, FilterWorkspace &w, const CellTopkPlan &tp, int m, int K, const float *q_dev,
-                                const float *r_dev, long long base, u64 *keys, bool init_keys, u64 *cand, unsigned *ccount, u64 *part,
-                                size_t part_bytes, int num_cu, bool timed, hipStream_t s, float max_dist2 = INFINITY);
+// One pass of <= KNN_CELL_BATCH queries of a top-K call (c: TopkCall::pass): prep (K-th seed bound) -> match -> record-only scan
+// -> re-rank of the slices and of the shared overflow area -> out-of-box rows -> select -> the exact top-K, gated on FALLBACK and
+// without the limit.  c.max_dist2 finite (a radius call, one-frame layouts): the prep kernel caps Dup_q with the radius
+// (knn_threshold_within).  timed: the pass records the call's events around its scan.
+hipError_t knn_cells_query_topk(FilterState &st, FilterWorkspace &w, const CellTopkPlan &tp, bool timed, const TopkCall &c);
 
 // Builds the filter layouts for refs[0..n) (device, AoS).  Synchronous.  Leaves st.usable false
 // (and returns hipSuccess) when the data rules the filter out.
@@ -558,7 +625,7 @@ struct GridTopkPlan {
     int rmax = 0;              // rings a query walks before it gives up
     unsigned blocks = 0;
     int waves = 0;             // per block: one query each
-    size_t scratch_bytes = 0;  // a folding call's lists [m][K] (the slot's topk_cand)
+    size_t scratch_bytes = 0;  // a folding call's lists [m][K] (the slot's cand buffer: knn_topk_scratch_plan)
     int launches = 0;          // of a folding call: grid kernel, gated exact top-K (scan + select per chunk), fold
 };
 // radius_rings (knn_index_query_topk_within): the rings the radius spans (knn_grid_radius_rings); 0 = a plain call.
@@ -566,12 +633,10 @@ GridTopkPlan knn_grid_topk_plan(int k, int K, int m, bool has_grid, int path, bo
 // The rings a radius of max_dist2 (squared, >= 0) spans on the grid: ceil(radius / the narrowest live axis' cell width) + 1,
 // capped at 2^30; a degenerate axis (one cell) is ignored, 0 when every axis is.  Sizes the plan's rmax only.
 long long knn_grid_radius_rings(const GridState *gs, float max_dist2);
-// within != 0 (knn_index_query_topk_within): only rows with v0 distance <= max_dist2 are candidates, in the grid kernel and in
-// the gated exact top-K behind it; a query stops as soon as the face bound passes the radius.
-hipError_t knn_grid_query_topk(const GridState *gs, const GridTopkPlan &plan, int slot, int m, int K, long long n, const float *q_dev,
-                               const float *r_dev, long long base, u64 *keys, int init, u64 *scratch, u64 *part, size_t part_bytes,
-                               int num_cu, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, const unsigned **gate_out,
-                               int within = 0, float max_dist2 = 0.0f);
+// c.init 0: the kernel's lists go to c.cand (>= plan.scratch_bytes) and are merged into c.keys.  A radius call (c.within()):
+// only rows with v0 distance <= c.max_dist2 are candidates, in the grid kernel and in the gated exact top-K behind it; a query
+// stops as soon as the face bound passes the radius.
+hipError_t knn_grid_query_topk(const GridState *gs, const GridTopkPlan &plan, int slot, const TopkCall &c, const unsigned **gate_out);
 void knn_grid_info(const GridState *gs, long long info[4]);
 
 // ---- RCCL exchange step (knn_rccl.cpp; librccl is dlopen'ed at first use) -------------------
@@ -617,17 +682,12 @@ void knn_filter_free(FilterState &st);
 hipError_t knn_filter_query(FilterState &st, FilterCallOptions opt, bool pruned, int slot, int m, const float *q_dev, const float *r_dev,
                             long long base, u64 *keys_dev, int num_cu, hipStream_t stream,
                             hipEvent_t ev_begin, hipEvent_t ev_end, bool init_keys = false, int *out_idx = nullptr);
-// opt.topk = K (1 .. KNN_TOPK_MAX).
-hipError_t knn_filter_query_topk(FilterState &st, FilterCallOptions opt, int slot, int m, const float *q, const float *r, long long base,
-                                 u64 *keys, bool init_keys, u64 *cand, unsigned *ccount, unsigned ccap, u64 *part,
-                                 size_t part_bytes, int num_cu, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end);
-// Top-K on the cell-pruned scan, the whole call in passes of KNN_CELL_BATCH queries (knn_cells_query_topk); cand / ccount: [m][tp.ccap], [m].
-hipError_t knn_filter_query_topk_cells(FilterState &st, const CellTopkPlan &tp, int slot, int m, int K, const float *q, const float *r,
-                                       long long base, u64 *keys, bool init_keys, u64 *cand, unsigned *ccount, u64 *part,
-                                       size_t part_bytes, int num_cu, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end,
-                                       // a radius call (finite): one-frame layouts cap their bound with it; the lists are NOT cut at
-                                       // it here (the gate lies slightly above): the caller clips them
-                                       float max_dist2 = INFINITY);
+// opt.topk = c.K (1 .. KNN_TOPK_MAX).  A radius call reaches it as a plain one: the caller clips its lists behind.
+hipError_t knn_filter_query_topk(FilterState &st, FilterCallOptions opt, int slot, const TopkCall &c);
+// Top-K on the cell-pruned scan, the whole call in passes of KNN_CELL_BATCH queries (knn_cells_query_topk; c.ccap = tp.ccap).  A
+// radius call: one-frame layouts cap their bound with it; the lists are NOT cut at it here (the gate lies slightly above): the
+// caller clips them.
+hipError_t knn_filter_query_topk_cells(FilterState &st, const CellTopkPlan &tp, int slot, const TopkCall &c);
 // Test hook: raw filter scores S[m][n] (row-major) and the per-query thresholds for a query
 // batch, plus {sigma, eta, rho, amax, bmax}.  Synchronous.
 hipError_t knn_filter_debug(FilterState &st, int m, const float *q_dev, const float *r_dev,

@@ -1061,35 +1061,37 @@ size_t knn_topk_part_bytes(int m, int K, long long n, int num_cu)
     return (size_t)topk_slices(mc, K, n, num_cu) * (size_t)mc * (size_t)K * sizeof(u64);
 }
 
-hipError_t knn_exact_topk_launch(int k, int m, int K, long long n, long long base, const unsigned *gids, const float *q,
-                                 const float *r, u64 *keys, int init, u64 *part, size_t part_bytes, int num_cu,
-                                 hipStream_t s, const unsigned *gate, u64 lim)
+hipError_t knn_exact_topk_launch(const TopkCall &c, const unsigned *gate, bool limit)
 {
+    const u64 lim = limit ? c.limit_key() : kKeyInit;
     const bool within = lim < kKeyInit;   // (a limit at or above (+INF, 0) admits what the plain form admits)
-    if (m <= 0 || K < 1 || K > KNN_TOPK_MAX)
-        return m <= 0 ? hipSuccess : hipErrorInvalidValue;
-    if (n <= 0) {   // nothing to add: the keys stay (or start at (+INF, 0))
-        if (init && !gate)
-            return knn_keys_fill_launch(keys, (int)((long long)m * K), s);
+    const int K = c.K;
+    hipStream_t s = c.stream;
+    if (c.m <= 0 || K < 1 || K > KNN_TOPK_MAX)
+        return c.m <= 0 ? hipSuccess : hipErrorInvalidValue;
+    if (c.n <= 0) {   // nothing to add: the keys stay (or start at (+INF, 0))
+        if (c.init && !gate)
+            return knn_keys_fill_launch(c.keys, (int)((long long)c.m * K), s);
         return hipSuccess;
     }
-    for (int c0 = 0; c0 < m; c0 += KNN_TOPK_CHUNK) {
-        const int mc = m - c0 < KNN_TOPK_CHUNK ? m - c0 : KNN_TOPK_CHUNK;
+    for (int c0 = 0; c0 < c.m; c0 += KNN_TOPK_CHUNK) {
+        const int mc = c.m - c0 < KNN_TOPK_CHUNK ? c.m - c0 : KNN_TOPK_CHUNK;
         const unsigned qg = (unsigned)knn_divup(mc, KNN_WAVE);
-        const long long slices = topk_slices(mc, K, n, num_cu);
-        if ((size_t)slices * (size_t)mc * (size_t)K * sizeof(u64) > part_bytes)
+        const long long slices = topk_slices(mc, K, c.n, c.num_cu);
+        if ((size_t)slices * (size_t)mc * (size_t)K * sizeof(u64) > c.part_bytes)
             return hipErrorInvalidValue;
-        const long long per = (n + slices - 1) / slices;
+        const long long per = (c.n + slices - 1) / slices;
         const dim3 grid((unsigned)slices, qg), block(KNN_WAVE);
         const size_t lds = (size_t)K * KNN_WAVE * sizeof(u64);
-        const float *qc = q + (size_t)c0 * k;
+        const float *qc = c.q + (size_t)c0 * c.k;
 #define KNN_TOPK_SCAN(KCV)                                                                                                       \
     if (within)                                                                                                                  \
-        hipLaunchKernelGGL((knn_exact_topk_kernel<KCV, true>), grid, block, lds, s, qc, r, k, mc, n, K, per, base, gids, part, gate, \
-                           lim);                                                                                                 \
+        hipLaunchKernelGGL((knn_exact_topk_kernel<KCV, true>), grid, block, lds, s, qc, c.r, c.k, mc, c.n, K, per, c.base, c.gids,  \
+                           c.part, gate, lim);                                                                                   \
     else                                                                                                                         \
-        hipLaunchKernelGGL((knn_exact_topk_kernel<KCV>), grid, block, lds, s, qc, r, k, mc, n, K, per, base, gids, part, gate, lim)
-        switch ((k + 15) / 16) {
+        hipLaunchKernelGGL((knn_exact_topk_kernel<KCV>), grid, block, lds, s, qc, c.r, c.k, mc, c.n, K, per, c.base, c.gids, c.part, \
+                           gate, lim)
+        switch ((c.k + 15) / 16) {
         case 1: KNN_TOPK_SCAN(1); break;
         case 2: KNN_TOPK_SCAN(2); break;
         case 3: KNN_TOPK_SCAN(3); break;
@@ -1104,8 +1106,8 @@ hipError_t knn_exact_topk_launch(int k, int m, int K, long long n, long long bas
         hipError_t e = hipGetLastError();
         if (e != hipSuccess)
             return e;
-        hipLaunchKernelGGL(knn_topk_select_kernel, dim3((unsigned)mc), dim3(KNN_WAVE), 0, s, (const u64 *)part, (int)slices, mc,
-                           K, keys + (size_t)c0 * K, init, gate);
+        hipLaunchKernelGGL(knn_topk_select_kernel, dim3((unsigned)mc), dim3(KNN_WAVE), 0, s, (const u64 *)c.part, (int)slices, mc,
+                           K, c.keys + (size_t)c0 * K, c.init, gate);
         e = hipGetLastError();
         if (e != hipSuccess)
             return e;
@@ -1338,44 +1340,41 @@ hipError_t knn_topk_umin_launch(float *umin, int nb, int m_padded, int K, hipStr
     return hipGetLastError();
 }
 
-hipError_t knn_topk_filter_finish(int k, int m, int K, long long positions, long long base, const float *q, const float *r,
-                                  const u64 *rec, const unsigned short *rec_rows, const unsigned *counts, unsigned nlists,
-                                  unsigned slice, unsigned *ctl, RerankPieces pieces, const unsigned *perm,
-                                  unsigned n_outliers, const unsigned *outliers, u64 *cand, unsigned *ccount, unsigned ccap,
-                                  u64 *keys, int init, hipStream_t s, const u64 *ovf_rec, const unsigned *ovf_count,
-                                  unsigned ovf_slice, const float *gate_dup, float inv_sigma2, const float *pos_norms,
-                                  const unsigned *gids)
+hipError_t knn_topk_filter_finish(const TopkCall &c, const TopkRecords &rs)
 {
-    if (gate_dup) {   // the cell-pruned top-K: the gated re-rank over the waves' slices and over the shared overflow area
-        if (rec_rows || !perm || !pos_norms || (gids && base != 0))
+    hipStream_t s = c.stream;
+    if (rs.gate_dup) {   // the cell-pruned top-K: the gated re-rank over the waves' slices and over the shared overflow area
+        if (rs.rec_rows || !rs.perm || !rs.pos_norms || (c.gids && c.base != 0))
             return hipErrorInvalidValue;
-        if (nlists)
-            hipLaunchKernelGGL(knn_topk_rerank_gated_kernel, dim3(nlists), dim3(KNN_BLOCK), 0, s, q, r, k, positions, base, rec, counts,
-                               nlists, slice, ctl, perm, pos_norms, gate_dup, inv_sigma2, cand, ccount, ccap, gids);
-        if (ovf_rec && ovf_count)   // (its `want > slice` rule raises FALLBACK for an over-full area)
-            hipLaunchKernelGGL(knn_topk_rerank_gated_kernel, dim3(1), dim3(KNN_BLOCK), 0, s, q, r, k, positions, base, ovf_rec, ovf_count,
-                               1u, ovf_slice, ctl, perm, pos_norms, gate_dup, inv_sigma2, cand, ccount, ccap, gids);
+        if (rs.nlists)
+            hipLaunchKernelGGL(knn_topk_rerank_gated_kernel, dim3(rs.nlists), dim3(KNN_BLOCK), 0, s, c.q, c.r, c.k, rs.positions, c.base,
+                               rs.rec, rs.counts, rs.nlists, rs.slice, rs.ctl, rs.perm, rs.pos_norms, rs.gate_dup, rs.inv_sigma2, c.cand,
+                               c.ccount, c.ccap, c.gids);
+        if (rs.ovf_rec && rs.ovf_count)   // (its `want > slice` rule raises FALLBACK for an over-full area)
+            hipLaunchKernelGGL(knn_topk_rerank_gated_kernel, dim3(1), dim3(KNN_BLOCK), 0, s, c.q, c.r, c.k, rs.positions, c.base,
+                               rs.ovf_rec, rs.ovf_count, 1u, rs.ovf_slice, rs.ctl, rs.perm, rs.pos_norms, rs.gate_dup, rs.inv_sigma2,
+                               c.cand, c.ccount, c.ccap, c.gids);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess)
             return e;
-    } else if (gids) {   // (the ungated re-rank of the filter's full scan pushes base + row: not for cell-range shards)
+    } else if (c.gids) {   // (the ungated re-rank of the filter's full scan pushes base + row: not for cell-range shards)
         return hipErrorInvalidValue;
-    } else if (nlists) {
-        hipLaunchKernelGGL(knn_topk_rerank_kernel, dim3(nlists), dim3(KNN_BLOCK), 0, s, q, r, k, positions, base, rec, rec_rows,
-                           counts, nlists, slice, ctl, pieces, perm, cand, ccount, ccap);
+    } else if (rs.nlists) {
+        hipLaunchKernelGGL(knn_topk_rerank_kernel, dim3(rs.nlists), dim3(KNN_BLOCK), 0, s, c.q, c.r, c.k, rs.positions, c.base, rs.rec,
+                           rs.rec_rows, rs.counts, rs.nlists, rs.slice, rs.ctl, rs.pieces, rs.perm, c.cand, c.ccount, c.ccap);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess)
             return e;
     }
-    if (n_outliers) {
-        const unsigned gx = (n_outliers + KNN_BLOCK - 1) / KNN_BLOCK < 64u ? (n_outliers + KNN_BLOCK - 1) / KNN_BLOCK : 64u;
-        hipLaunchKernelGGL(knn_topk_outlier_kernel, dim3(gx, (unsigned)m), dim3(KNN_BLOCK), 0, s, q, r, k, n_outliers, base,
-                           outliers, ctl, cand, ccount, ccap, gids);
+    if (rs.n_outliers) {
+        const unsigned gx = (rs.n_outliers + KNN_BLOCK - 1) / KNN_BLOCK < 64u ? (rs.n_outliers + KNN_BLOCK - 1) / KNN_BLOCK : 64u;
+        hipLaunchKernelGGL(knn_topk_outlier_kernel, dim3(gx, (unsigned)c.m), dim3(KNN_BLOCK), 0, s, c.q, c.r, c.k, rs.n_outliers, c.base,
+                           rs.outliers, rs.ctl, c.cand, c.ccount, c.ccap, c.gids);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess)
             return e;
     }
-    hipLaunchKernelGGL(knn_topk_select_cand_kernel, dim3((unsigned)m), dim3(KNN_WAVE), 0, s, (const u64 *)cand,
-                       (const unsigned *)ccount, ccap, K, keys, init, (const unsigned *)(ctl + KNN_CTL_FALLBACK));
+    hipLaunchKernelGGL(knn_topk_select_cand_kernel, dim3((unsigned)c.m), dim3(KNN_WAVE), 0, s, (const u64 *)c.cand,
+                       (const unsigned *)c.ccount, c.ccap, c.K, c.keys, c.init, (const unsigned *)(rs.ctl + KNN_CTL_FALLBACK));
     return hipGetLastError();
 }

@@ -2661,51 +2661,49 @@ hipError_t knn_filter_query(FilterState &st, FilterCallOptions opt, bool pruned,
 // minimum (opt.topk = K), running thresholds are off (the caller's options say so).  Records and outlier rows go to per-query
 // candidate lists, a select kernel keeps the K smallest; a batch that raised FALLBACK (a query nothing bounds, fewer than K
 // sampled blocks with a real row, records or candidates overflowing) is answered by the gated exact top-K instead.
-hipError_t knn_filter_query_topk(FilterState &st, FilterCallOptions opt, int slot, int m, const float *q, const float *r, long long base,
-                                 u64 *keys, bool init_keys, u64 *cand, unsigned *ccount, unsigned ccap, u64 *part,
-                                 size_t part_bytes, int num_cu, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end)
+hipError_t knn_filter_query_topk(FilterState &st, FilterCallOptions opt, int slot, const TopkCall &c)
 {
     if (st.cells && st.cells->centred)
         return hipErrorInvalidValue;   // per-cell frames: the full scan cannot read them (the caller sends these to exact top-K)
     FilterWorkspace &w = st.ws[slot];
-    w.ev_begin = ev_begin;
-    w.ev_end = ev_end;
-    const int K = opt.topk;
-    FTRY(filter_prelude(st, w, m, q, nullptr, s));
-    FTRY(hipMemsetAsync(ccount, 0, (size_t)m * sizeof(unsigned), s));
-    FTRY(filter_scan(st, w, knn_filter_query_plan({st.kt, st.ntiles, m, num_cu, w.rec_cap, opt}), m, s));
-    const unsigned *perm = st.cells ? st.cells->perm : nullptr;
-    const long long positions = st.cells ? st.ntiles * 32 : st.n;
-    FTRY(knn_topk_filter_finish(st.k, m, K, positions, base, q, r, w.records,
-                                w.has_rows ? (const unsigned short *)(w.records + w.rec_cap) : nullptr, w.counts, w.nlists,
-                                w.slice, w.ctl, w.pieces, perm, st.n_outliers, st.outliers, cand, ccount, ccap, keys,
-                                init_keys ? 1 : 0, s));
+    w.ev_begin = c.ev0;
+    w.ev_end = c.ev1;
+    hipStream_t s = c.stream;
+    FTRY(filter_prelude(st, w, c.m, c.q, nullptr, s));
+    FTRY(hipMemsetAsync(c.ccount, 0, (size_t)c.m * sizeof(unsigned), s));
+    FTRY(filter_scan(st, w, knn_filter_query_plan({st.kt, st.ntiles, c.m, c.num_cu, w.rec_cap, opt}), c.m, s));
+    TopkRecords rs;
+    rs.positions = st.cells ? st.ntiles * 32 : st.n;
+    rs.rec = w.records;
+    rs.rec_rows = w.has_rows ? (const unsigned short *)(w.records + w.rec_cap) : nullptr;
+    rs.counts = w.counts;
+    rs.nlists = w.nlists;
+    rs.slice = w.slice;
+    rs.ctl = w.ctl;
+    rs.pieces = w.pieces;
+    rs.perm = st.cells ? st.cells->perm : nullptr;
+    rs.n_outliers = st.n_outliers;
+    rs.outliers = st.outliers;
+    FTRY(knn_topk_filter_finish(c, rs));
     // gated: runs only if the batch raised FALLBACK; folds into the keys the select left alone
-    FTRY(knn_exact_topk_launch(st.k, m, K, st.n, base, nullptr, q, r, keys, init_keys ? 1 : 0, part, part_bytes, num_cu, s,
-                               w.ctl + KNN_CTL_FALLBACK));
+    FTRY(knn_exact_topk_launch(c, w.ctl + KNN_CTL_FALLBACK, false));
     return hipSuccess;
 }
 
 // Top-K on the cell-pruned scan: passes of KNN_CELL_BATCH queries, each its own prep -> match -> record-only scan ->
 // re-rank -> select -> gated exact top-K (knn_cells_query_topk).  Every pass decides for itself: one that raised FALLBACK is
 // answered exactly, the next is pruned again.
-hipError_t knn_filter_query_topk_cells(FilterState &st, const CellTopkPlan &tp, int slot, int m, int K, const float *q, const float *r,
-                                       long long base, u64 *keys, bool init_keys, u64 *cand, unsigned *ccount, u64 *part,
-                                       size_t part_bytes, int num_cu, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end,
-                                       float max_dist2)
+hipError_t knn_filter_query_topk_cells(FilterState &st, const CellTopkPlan &tp, int slot, const TopkCall &c)
 {
-    if (!st.cells || !tp.use)
+    if (!st.cells || !tp.use || c.ccap != tp.ccap)
         return hipErrorInvalidValue;
     FilterWorkspace &w = st.ws[slot];
-    w.ev_begin = ev_begin;
-    w.ev_end = ev_end;
+    w.ev_begin = c.ev0;
+    w.ev_end = c.ev1;
     const int cell_batch = KNN_CELL_BATCH;
-    FTRY(ensure_workspace(st, w, std::min(m, cell_batch)));
-    for (int q0 = 0; q0 < m; q0 += cell_batch) {
-        const int mb = std::min(cell_batch, m - q0);
-        FTRY(knn_cells_query_topk(st, w, tp, mb, K, q + (size_t)q0 * st.k, r, base, keys + (size_t)q0 * K, init_keys,
-                                  cand + (size_t)q0 * tp.ccap, ccount + q0, part, part_bytes, num_cu, q0 == 0, s, max_dist2));
-    }
+    FTRY(ensure_workspace(st, w, std::min(c.m, cell_batch)));
+    for (int q0 = 0; q0 < c.m; q0 += cell_batch)
+        FTRY(knn_cells_query_topk(st, w, tp, q0 == 0, c.pass(q0, std::min(cell_batch, c.m - q0))));
     return hipSuccess;
 }
 

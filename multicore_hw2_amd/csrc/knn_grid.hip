@@ -660,32 +660,31 @@ GridTopkPlan knn_grid_topk_plan(int k, int K, int m, bool has_grid, int path, bo
     return p;
 }
 
-// The whole top-K call on the grid way, asynchronous on `s`: the grid kernel writes the batch's lists [m][K] — into keys
-// itself when the call starts them (init), else into `scratch` (>= plan.scratch_bytes) —, the exact top-K behind it, gated on
-// the batch's give-up word, overwrites them when some query gave up, and a folding call then merges the scratch into keys.
-// ev0 / ev1 (nullable) bracket the grid kernel.  *gate_out = the give-up word (knn_index_last_stats reads it back).
-hipError_t knn_grid_query_topk(const GridState *gs, const GridTopkPlan &plan, int slot, int m, int K, long long n, const float *q,
-                               const float *r, long long base, u64 *keys, int init, u64 *scratch, u64 *part, size_t part_bytes,
-                               int num_cu, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, const unsigned **gate_out, int within,
-                               float max_dist2)
+// The whole top-K call on the grid way, asynchronous on c.stream: the grid kernel writes the batch's lists [m][K] — into c.keys
+// itself when the call starts them (init), else into c.cand (>= plan.scratch_bytes) —, the exact top-K behind it, gated on
+// the batch's give-up word, overwrites them when some query gave up, and a folding call then merges the scratch into the keys.
+// A radius call: the radius kernel and the exact top-K both carry the limit.
+// c.ev0 / c.ev1 (nullable) bracket the grid kernel.  *gate_out = the give-up word (knn_index_last_stats reads it back).
+hipError_t knn_grid_query_topk(const GridState *gs, const GridTopkPlan &plan, int slot, const TopkCall &c, const unsigned **gate_out)
 {
     *gate_out = nullptr;
-    if (!gs || !gs->usable || !plan.use || m <= 0 || K < 1 || K > KNN_WAVE || (!init && !scratch))
+    if (!gs || !gs->usable || !plan.use || c.m <= 0 || c.K < 1 || c.K > KNN_WAVE || (!c.init && !c.cand))
         return hipErrorInvalidValue;
     const unsigned call = gs->calls[slot]++;
     unsigned *giveup = gs->giveup + 2 * slot + (call & 1u);
     unsigned *giveup_next = gs->giveup + 2 * slot + ((call + 1u) & 1u);
-    u64 *lists = init ? keys : scratch;
+    u64 *lists = c.init ? c.keys : c.cand;
+    hipStream_t s = c.stream;
     const dim3 grid(plan.blocks), block(GRID_BLOCK);
-    if (ev0)
-        GTRY(hipEventRecord(ev0, s));
+    if (c.ev0)
+        GTRY(hipEventRecord(c.ev0, s));
 #define GRID_TOPK(KDV)                                                                                                             \
-    if (within)                                                                                                                    \
-        hipLaunchKernelGGL(knn_grid_within_kernel<KDV>, grid, block, 0, s, q, m, K, gs->geom, gs->start, gs->pts, gs->orig, base,  \
-                           lists, plan.rmax, giveup, giveup_next, max_dist2);                                                      \
+    if (c.within())                                                                                                                \
+        hipLaunchKernelGGL(knn_grid_within_kernel<KDV>, grid, block, 0, s, c.q, c.m, c.K, gs->geom, gs->start, gs->pts, gs->orig,  \
+                           c.base, lists, plan.rmax, giveup, giveup_next, c.max_dist2);                                            \
     else                                                                                                                           \
-        hipLaunchKernelGGL(knn_grid_topk_kernel<KDV>, grid, block, 0, s, q, m, K, gs->geom, gs->start, gs->pts, gs->orig, base,    \
-                           lists, plan.rmax, giveup, giveup_next)
+        hipLaunchKernelGGL(knn_grid_topk_kernel<KDV>, grid, block, 0, s, c.q, c.m, c.K, gs->geom, gs->start, gs->pts, gs->orig,    \
+                           c.base, lists, plan.rmax, giveup, giveup_next)
     switch (gs->geom.k) {
     case 1: GRID_TOPK(1); break;
     case 2: GRID_TOPK(2); break;
@@ -694,13 +693,12 @@ hipError_t knn_grid_query_topk(const GridState *gs, const GridTopkPlan &plan, in
     }
 #undef GRID_TOPK
     GTRY(hipGetLastError());
-    if (ev1)
-        GTRY(hipEventRecord(ev1, s));
+    if (c.ev1)
+        GTRY(hipEventRecord(c.ev1, s));
     *gate_out = giveup;
-    GTRY(knn_exact_topk_launch(gs->geom.k, m, K, n, base, nullptr, q, r, lists, 1, part, part_bytes, num_cu, s, giveup,
-                               within ? knn_topk_limit_key(max_dist2) : kKeyInit));
-    if (!init)
-        GTRY(knn_topk_merge_launch(m, K, scratch, keys, s));
+    GTRY(knn_exact_topk_launch(c.writing(lists), giveup, true));
+    if (!c.init)
+        GTRY(knn_topk_merge_launch(c.m, c.K, c.cand, c.keys, s));
     return hipSuccess;
 }
 
