@@ -291,6 +291,36 @@ int knn_index_query_topk_within(knn_index *idx, int slot, int m, int K, const fl
 int knn_index_query_topk_within_host(knn_index *idx, int m, int K, const float *queries_host, float max_dist2,
                                      int *indices_host, float *dist2_host, int *counts_host /* may be NULL */);
 
+/* ------------------------------------------------------------------------
+ * 2d. Counts within a radius: how many rows of the shard lie within a distance of each query.
+ *
+ * counts_dev[j] receives the number of rows of this shard whose v0 distance E to query j is finite and E <= max_dist2: fp32,
+ * accumulated in dimension order, no FMA, an fp32 compare with equality inside — exactly the candidate rule of
+ * knn_index_query_topk_within, whose lists hold at most 64 entries and cannot tell a complete list from one cut at K.
+ * max_dist2 = +INF counts the rows with a finite distance; 0 (and -0) exact duplicates of the query; a query with a non-finite
+ * coordinate has count 0.  max_dist2 < 0 or NaN, m < 1, a slot outside 0 .. 7, a null pointer or any flag other than the three
+ * below are KNN_EINVAL with a knn_last_error text, and nothing is launched.
+ * Folding: without KNN_QUERY_INIT_KEYS counts_dev[j] += this shard's count, with it counts_dev[j] = the count.  Counts of
+ * disjoint shards add: index-range shards, cell-range shards (knn_index_create_sharded: as they are — no seed layer and no
+ * KNN_QUERY_TOPK_PARTIAL contract is needed), GPUs after the caller has summed.  Counts are unsigned 32-bit: one shard's count is
+ * at most n_local < 2^32, a fold wraps modulo 2^32.  An empty shard adds nothing (writes zeros under the init flag).
+ * Asynchronous on `stream`; slots as for every other query (eight workspaces, calls that share one are stream-ordered by the
+ * caller); 1-NN, top-K and count calls may follow one another on a slot in any order.
+ * Ways (knn_index_last_stats [0]): 1 = the exact count scan, the default and what every call without a flag takes.  3 = the grid
+ * index, when the index has one, the call carries KNN_QUERY_COUNT_GRID and option "path" is 0 or 3: a query's ring walk ends when
+ * the face bound passes the radius.  4 = the cell-pruned scan, when the call carries KNN_QUERY_COUNT_CELLS, max_dist2 is finite,
+ * the index has a cell-sorted layout in the shard's one frame (fp16 rows without per-cell frames, or 8-bit rows in bin frames),
+ * k <= 32, m >= 5, "path" is 0 or 2 and "cells" is not 2; passes of 1024 queries.  On every other index a flag is accepted and
+ * changes nothing.  Both fast ways are on request until they are measured against the exact count ("Counts within a
+ * radius").  knn_index_last_stats: [1] records re-ranked (way 4; the last pass), [2] = 1 when the grid gave up or a cell pass
+ * fell back and the exact count answered, [3] rows outside the robust box (way 4).  The count is exact on every way out. */
+#define KNN_QUERY_COUNT_GRID  16u
+#define KNN_QUERY_COUNT_CELLS 32u
+int knn_index_count_within(knn_index *idx, int slot, int m, const float *queries_dev, float max_dist2,
+                           unsigned *counts_dev, void *stream, unsigned flags);
+/* Synchronous: host queries [m][k] in, counts_host [m] out (this shard alone, written from scratch, the default way). */
+int knn_index_count_within_host(knn_index *idx, int m, const float *queries_host, float max_dist2, unsigned *counts_host);
+
 /* Tuning / test hooks.  Known names:
  *   "path"    0 = auto, 1 = exact VALU kernels only, 2 = force the MFMA filter
  *             (+ exact re-rank) where its preconditions hold, 3 = the uniform-grid spatial index
@@ -517,6 +547,12 @@ int knn_debug_grid_topk_plan(const long long in[6], long long out[6]);
  * raise out[1] to themselves while a walk of that many rings stays within 2^15 cells, (2 rings + 1)^k; beyond that the plain
  * value and the give-up rule stand. */
 int knn_debug_grid_within_plan(const long long in[7], long long out[6]);
+/* Which way answers a knn_index_count_within call and what it launches with (host arithmetic, no GPU).  in = {k, m, rows, 1 if
+ * the radius is finite, KNN_QUERY_COUNT_GRID given, KNN_QUERY_COUNT_CELLS given, has a grid index, has a cell-sorted layout,
+ * per-cell frames, 8-bit rows, bin frames, cell-range shard, option "path", option "cells", CUs, the rings the radius spans on the
+ * grid}; out = {way (1, 3, 4), passes and the first pass's queries (way 4), the grid's rmax, blocks and waves per block (way 3),
+ * slices of the exact count scan, bytes of the slot's count scratch}.  Bad inputs are KNN_EINVAL. */
+int knn_debug_count_plan(const long long in[16], long long out[8]);
 /* Test hook (host arithmetic only, no GPU needed): the bytes a workspace slot's three top-K buffers must hold for a call.
  * in = {the way that answers it (knn_index_last_stats' [0]: 1 exact, 2 filter, 3 grid, 4 cell-pruned), m, K, the shard's rows,
  * the device's compute units, 1 if the call carries KNN_QUERY_INIT_KEYS, 1 if it has a finite radius, the queries of a pass of

@@ -34,11 +34,14 @@ EXPORTED_SYMBOLS = [
     "knn_index_query_topk", "knn_keys_topk_merge", "knn_index_query_topk_host", "knn_debug_grid_topk_plan",
     "knn_index_query_topk_within", "knn_index_query_topk_within_host", "knn_debug_grid_within_plan", "knn_debug_within_bound",
     "knn_debug_frame_dup", "knn_debug_topk_scratch",
+    "knn_index_count_within", "knn_index_count_within_host", "knn_debug_count_plan",
 ]
 QUERY_INIT_KEYS = 1   # KNN_QUERY_INIT_KEYS
 QUERY_TOPK_PARTIAL = 2   # KNN_QUERY_TOPK_PARTIAL
 QUERY_TOPK_GRID = 4   # KNN_QUERY_TOPK_GRID
 QUERY_TOPK_FRAMES = 8   # KNN_QUERY_TOPK_FRAMES
+QUERY_COUNT_GRID = 16   # KNN_QUERY_COUNT_GRID
+QUERY_COUNT_CELLS = 32   # KNN_QUERY_COUNT_CELLS
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # KNN_MI355X_LIB: A/B hook — load another build of the same C-ABI (e.g. a previous commit's .so)
@@ -308,6 +311,22 @@ def debug_grid_within_plan(**inputs):
     return dict(zip(GRID_TOPK_PLAN, list(out)))
 
 
+COUNT_PLAN_INPUTS = ("k", "m", "n", "radius_finite", "flag_grid", "flag_cells", "has_grid", "has_cells", "centred", "rows_u8", "bins",
+                     "sharded", "path", "cells", "num_cu", "radius_rings")
+COUNT_PLAN = ("way", "passes", "pass_m", "rmax", "blocks", "waves", "slices", "scratch_bytes")
+
+
+def debug_count_plan(**inputs):
+    """knn_debug_count_plan: which way answers a count_within call (last_stats()[0]) and what it launches with, for the inputs
+    named in COUNT_PLAN_INPUTS.  Host arithmetic; works without a GPU."""
+    vin = (ctypes.c_longlong * len(COUNT_PLAN_INPUTS))(*[int(inputs[n]) for n in COUNT_PLAN_INPUTS])
+    out = (ctypes.c_longlong * len(COUNT_PLAN))()
+    f = lib().knn_debug_count_plan
+    f.argtypes = [ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)]
+    _check(f(vin, out))
+    return dict(zip(COUNT_PLAN, list(out)))
+
+
 TOPK_SCRATCH_INPUTS = ("way", "m", "K", "n", "num_cu", "init", "within", "pass_m", "grid_scratch_bytes")
 TOPK_SCRATCH_PLAN = ("part_bytes", "cand_bytes", "lists_bytes")
 
@@ -407,6 +426,15 @@ def cudaCallback(k, m, n, searchPoints, referencePoints):
     out = np.ctypeslib.as_array(res, shape=(m,)).astype(np.int32, copy=True)
     ctypes.CDLL(None).free(res)
     return out
+
+
+def count_within_c():
+    """knn_index_count_within with its argument types (set here, not in lib(): a library loaded through KNN_MI355X_LIB for an
+    A/B run may predate the symbol and must still load)."""
+    f = lib().knn_index_count_within
+    f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
+                  ctypes.c_uint]
+    return f
 
 
 class KnnGeom:
@@ -563,6 +591,25 @@ class KnnIndex:
                                                       idx.ctypes.data_as(ctypes.c_void_p), d2.ctypes.data_as(ctypes.c_void_p),
                                                       counts.ctypes.data_as(ctypes.c_void_p)))
         return idx, d2, counts
+
+    def count_within(self, m, queries_dev, max_dist2, counts_dev, stream=0, slot=0, init=False, grid=False, cells=False):
+        """Async (knn_index_count_within): counts_dev[m] (uint32) += the rows of this shard whose v0 squared distance is finite
+        and <= max_dist2 (fp32, equality inside); init (KNN_QUERY_INIT_KEYS): = instead of +=.  grid (KNN_QUERY_COUNT_GRID) /
+        cells (KNN_QUERY_COUNT_CELLS): an index that has a grid index / a one-frame cell-sorted layout answers with it
+        (last_stats()[0] == 3 / 4); on any other index the flag changes nothing.  A negative or NaN radius raises."""
+        _check(count_within_c()(self._h, int(slot), int(m), ctypes.c_void_p(int(queries_dev)), float(max_dist2),
+                           ctypes.c_void_p(int(counts_dev)), ctypes.c_void_p(stream),
+                           (QUERY_INIT_KEYS if init else 0) | (QUERY_COUNT_GRID if grid else 0) | (QUERY_COUNT_CELLS if cells else 0)))
+
+    def count_within_host(self, queries, max_dist2):
+        """Synchronous count of this shard alone: uint32 [m]."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1)
+        m = q.size // self.k
+        counts = np.empty(m, dtype=np.uint32)
+        f = lib().knn_index_count_within_host
+        f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p]
+        _check(f(self._h, m, q.ctypes.data_as(ctypes.c_void_p), float(max_dist2), counts.ctypes.data_as(ctypes.c_void_p)))
+        return counts
 
     def query_topk_host(self, queries, K):
         """Synchronous top-K of this shard alone: (indices int32 [m][K], dist2 float32 [m][K])."""

@@ -319,6 +319,8 @@ struct knn_index {
     struct TopkSlot {
         u64 *part = nullptr, *cand = nullptr, *lists = nullptr;
         size_t part_bytes = 0, cand_bytes = 0, lists_bytes = 0;
+        u64 *count = nullptr;      // knn_index_count_within on the grid and cell ways: the per-query count scratch [m] unsigned
+        size_t count_bytes = 0;
     } topk[KNN_SLOTS];
     // Calls on one index from several host threads are serialised (enqueueing a batch is ~20 us of host work; the GPU
     // work of different slots still overlaps): the workspaces' lazily grown buffers, the event list, the statistics and
@@ -801,6 +803,7 @@ void knn_index_destroy(knn_index *idx)
             (void)knn_dev_free(t.part);
             (void)knn_dev_free(t.cand);
             (void)knn_dev_free(t.lists);
+            (void)knn_dev_free(t.count);
         }
         knn_dev_free_end_synced();
         for (auto &ev : idx->events) {
@@ -886,6 +889,36 @@ QueryRoute knn_query_route(const QueryRouteInputs &in)
              t.n_outliers <= r.ccap / 2 && r.ccap >= 64 && (path == 2 || (path == 0 && m >= 5 && sized)))
         r.way = QueryWay::Filter;
     return r;
+}
+
+// Which way answers a count call (knn_index_count_within; DESIGN §4.0, §4.6 "Counts within a radius"): the one place it is chosen.
+// The exact count scan is the default — a path becomes a default only once it is measured faster than what it replaces —, the grid
+// index and the cell-pruned scan answer on request, by flag; on an index that lacks the structure a flag changes nothing.
+CountPlan knn_count_route(const CountRouteInputs &in)
+{
+    CountPlan p;
+    p.slices = knn_count_slices(std::min(in.m, KNN_TOPK_CHUNK), in.n, in.num_cu);
+    const int path = in.path;
+    if (in.has_grid && in.flag_grid && (path == 0 || path == 3)) {
+        // rmax: the radius-bounded top-K's rule at K = 1, the 2^15-cell budget included (chosen, not measured)
+        const GridTopkPlan g = knn_grid_topk_plan(in.k, 1, in.m, true, path, true, in.radius_finite ? in.radius_rings : 0);
+        p.way = QueryWay::Grid;
+        p.rmax = g.rmax;
+        p.blocks = g.blocks;
+        p.waves = g.waves;
+        p.scratch_bytes = (size_t)in.m * sizeof(unsigned);
+        return p;
+    }
+    // a cell-sorted layout in the shard's ONE frame: fp16 rows without per-cell frames, or 8-bit rows in bin frames.  Cell-range
+    // shards as they are: the ranks' counts add, so no seed layer and no PARTIAL contract.  +INF has no cap to prune with.
+    const bool one_frame = in.has_cells && !in.centred && (!in.rows_u8 || in.bins);
+    if (in.flag_cells && in.radius_finite && one_frame && in.k <= 32 && in.m >= 5 && (path == 0 || path == 2) && in.cells_option != 2) {
+        p.way = QueryWay::Cells;
+        p.passes = (in.m + KNN_CELL_BATCH - 1) / KNN_CELL_BATCH;
+        p.pass_m = std::min(in.m, KNN_CELL_BATCH);
+        p.scratch_bytes = (size_t)in.m * sizeof(unsigned);
+    }
+    return p;
 }
 
 // What a slot's top-K buffers must hold for a call: the one place their sizes are decided (tests/test_topk_scratch_logic.py
@@ -1239,6 +1272,141 @@ int knn_keys_topk_merge(int device, int m, int K, const unsigned long long *a_de
     if (!guard.ok)
         return fail(KNN_EHIP, "knn_keys_topk_merge: hipSetDevice failed");
     HIP_TRY(knn_topk_merge_launch(m, K, (const u64 *)a_dev, (u64 *)b_dev, (hipStream_t)stream));
+    return KNN_OK;
+}
+
+int knn_index_count_within(knn_index *idx, int slot, int m, const float *queries_dev, float max_dist2, unsigned *counts_dev,
+                           void *stream, unsigned flags)
+{
+    // (one message per rule, the index last: tests/test_count_logic.py tells them apart without a GPU)
+    if (!(max_dist2 >= 0.0f))
+        return fail(KNN_EINVAL, "knn_index_count_within: max_dist2 must be >= 0 and not NaN");
+    constexpr unsigned kCountFlags = KNN_QUERY_INIT_KEYS | KNN_QUERY_COUNT_GRID | KNN_QUERY_COUNT_CELLS;   // the three it admits
+    if ((flags & ~kCountFlags) != 0u)
+        return fail(KNN_EINVAL, "knn_index_count_within: unknown flag (KNN_QUERY_INIT_KEYS, KNN_QUERY_COUNT_GRID, KNN_QUERY_COUNT_CELLS)");
+    if (slot < 0 || slot >= KNN_SLOTS)
+        return fail(KNN_EINVAL, "knn_index_count_within: slot outside 0 .. 7");
+    if (m < 1)
+        return fail(KNN_EINVAL, "knn_index_count_within: m < 1");
+    if (!queries_dev || !counts_dev)
+        return fail(KNN_EINVAL, "knn_index_count_within: null queries or counts");
+    if (!idx)
+        return fail(KNN_EINVAL, "knn_index_count_within: null index");
+    std::lock_guard<std::recursive_mutex> lock(idx->mu);
+    DeviceGuard guard(idx->device);
+    if (!guard.ok)
+        return fail(KNN_EHIP, "knn_index_count_within: hipSetDevice failed");
+    CountCall call;
+    call.k = idx->k;
+    call.m = m;
+    call.n = idx->n;
+    call.q = queries_dev;
+    call.r = idx->refs;
+    call.counts = counts_dev;
+    call.max_dist2 = max_dist2 == 0.0f ? 0.0f : max_dist2;   // (-0 counts as 0)
+    call.num_cu = idx->num_cu;
+    call.stream = (hipStream_t)stream;
+    hipStream_t s = call.stream;
+    idx->stats[0] = 1;
+    idx->stats[1] = 0;
+    idx->stats[2] = 0;
+    idx->stats[3] = 0;
+    idx->grid_topk_gate = nullptr;
+    idx->last_slot = slot;
+    // every way ADDS to the caller's counts: an init call zeroes them first
+    if ((flags & KNN_QUERY_INIT_KEYS) != 0u)
+        HIP_TRY(hipMemsetAsync(counts_dev, 0, (size_t)m * sizeof(unsigned), s));
+    if (idx->n == 0)   // an empty shard adds nothing
+        return KNN_OK;
+    const QueryRouteInputs ri = route_inputs(idx, m, 1, 0u);
+    CountRouteInputs ci;
+    ci.k = idx->k;
+    ci.m = m;
+    ci.n = idx->n;
+    ci.radius_finite = call.max_dist2 < INFINITY;
+    ci.flag_grid = (flags & KNN_QUERY_COUNT_GRID) != 0u;
+    ci.flag_cells = (flags & KNN_QUERY_COUNT_CELLS) != 0u;
+    ci.has_grid = ri.has_grid;
+    ci.has_cells = ri.t.has_cells;
+    ci.centred = ri.t.q.centred;
+    ci.rows_u8 = ri.t.q.rows_u8;
+    ci.bins = ri.t.bins;
+    ci.sharded = ri.t.sharded;
+    ci.path = ri.path;
+    ci.cells_option = ri.t.cells_option;
+    ci.num_cu = idx->num_cu;
+    ci.radius_rings = ci.has_grid && ci.radius_finite ? knn_grid_radius_rings(idx->grid, call.max_dist2) : 0;
+    const CountPlan plan = knn_count_route(ci);
+    idx->stats[0] = (long long)plan.way;
+    // the slot's count scratch, grown before the first launch
+    knn_index::TopkSlot &ts = idx->topk[slot];
+    KNN_TRY(slot_buffer_grow(ts.count, ts.count_bytes, plan.scratch_bytes));
+    call.scratch = (unsigned *)ts.count;
+    EventPair *ev = nullptr;
+    KNN_TRY(next_event_pair(idx, false, &ev));
+    call.ev0 = ev ? ev->first : nullptr;
+    call.ev1 = ev ? ev->second : nullptr;
+    switch (plan.way) {
+    case QueryWay::Grid:
+        HIP_TRY(knn_grid_query_count(idx->grid, plan.rmax, slot, call, &idx->grid_topk_gate));
+        break;
+    case QueryWay::Cells: {
+        // the passes' shapes: the cell-pruned top-K's plan at K = 1 — prep shape, match launch, the record-only scan's grid and lists
+        CellTopkInputs t = ri.t;
+        t.K = 1;
+        t.topk_cells = 1;
+        t.shard_partial = t.sharded;
+        t.frames_flag = false;
+        t.other_path = false;
+        t.n_outliers = 0u;   // (a count has no candidate list for them to crowd)
+        t.ccap = 64u;
+        const CellTopkPlan tp = knn_cells_topk_plan(t);
+        if (!tp.use)
+            return fail(KNN_EHIP, "knn_index_count_within: the cell-pruned scan has no pass shape for this layout");
+        HIP_TRY(knn_filter_query_count_cells(idx->filter, tp, slot, call));
+        break;
+    }
+    default:
+        if (ev)
+            HIP_TRY(hipEventRecord(call.ev0, s));
+        HIP_TRY(knn_exact_count_launch(call, nullptr));
+        if (ev)
+            HIP_TRY(hipEventRecord(call.ev1, s));
+        break;
+    }
+    return KNN_OK;
+}
+
+int knn_debug_count_plan(const long long in[16], long long out[8])
+{
+    if (!in || !out || in[0] < 1 || in[0] > 4096 || in[1] < 1 || in[1] > INT_MAX || in[2] < 1 || in[12] < 0 || in[12] > 3 || in[13] < 0 ||
+        in[13] > 2 || in[14] < 1 || in[14] > INT_MAX || in[15] < 0 || (in[6] != 0 && in[0] > 4) ||
+        (in[6] != 0 && in[11] != 0))   // (a grid index needs k <= 4; a cell-range shard has none)
+        return fail(KNN_EINVAL, "knn_debug_count_plan: bad arguments (1 <= k <= 4096, m >= 1, rows >= 1, path 0 .. 3, cells 0 .. 2, num_cu >= 1, "
+                                "rings >= 0; a grid index only with k <= 4 and never on a cell-range shard)");
+    for (int i = 3; i <= 11; ++i)
+        if (in[i] != 0 && in[i] != 1)
+            return fail(KNN_EINVAL, "knn_debug_count_plan: inputs 3 .. 11 are 0 or 1");
+    CountRouteInputs ci;
+    ci.k = (int)in[0];
+    ci.m = (int)in[1];
+    ci.n = in[2];
+    ci.radius_finite = in[3] != 0;
+    ci.flag_grid = in[4] != 0;
+    ci.flag_cells = in[5] != 0;
+    ci.has_grid = in[6] != 0;
+    ci.has_cells = in[7] != 0;
+    ci.centred = in[8] != 0;
+    ci.rows_u8 = in[9] != 0;
+    ci.bins = in[10] != 0;
+    ci.sharded = in[11] != 0;
+    ci.path = (int)in[12];
+    ci.cells_option = (int)in[13];
+    ci.num_cu = (int)in[14];
+    ci.radius_rings = in[15];
+    const CountPlan p = knn_count_route(ci);
+    const long long v[8] = {(long long)p.way, p.passes, p.pass_m, p.rmax, p.blocks, p.waves, p.slices, (long long)p.scratch_bytes};
+    memcpy(out, v, sizeof v);
     return KNN_OK;
 }
 
@@ -1728,6 +1896,35 @@ extern "C" int knn_index_query_topk_within_host(knn_index *idx, int m, int K, co
                 ++c;
             counts_host[j] = c;
         }
+    return KNN_OK;
+}
+
+extern "C" int knn_index_count_within_host(knn_index *idx, int m, const float *queries_host, float max_dist2, unsigned *counts_host)
+{
+    if (!idx || m < 1 || !queries_host || !counts_host || !(max_dist2 >= 0.0f))
+        return fail(KNN_EINVAL, "knn_index_count_within_host: bad arguments (m >= 1, max_dist2 >= 0 and not NaN)");
+    std::lock_guard<std::recursive_mutex> lock(idx->mu);
+    DeviceGuard guard(idx->device);
+    if (!guard.ok)
+        return fail(KNN_EHIP, "knn_index_count_within_host: hipSetDevice failed");
+    Staging stage(idx->device);
+    float *q_dev = nullptr;
+    unsigned *c_dev = nullptr;
+    const size_t qbytes = (size_t)m * (size_t)idx->k * sizeof(float), cbytes = (size_t)m * sizeof(unsigned);
+    hipError_t e = stage.get(&q_dev, qbytes);
+    if (e == hipSuccess)
+        e = stage.get(&c_dev, cbytes);
+    if (e == hipSuccess)
+        e = hipMemcpy(q_dev, queries_host, qbytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess)
+        return fail(KNN_EHIP, "knn_index_count_within_host: staging queries", hipGetErrorString(e));
+    const int rc = knn_index_count_within(idx, 0, m, q_dev, max_dist2, c_dev, nullptr, KNN_QUERY_INIT_KEYS);
+    if (rc != KNN_OK)
+        return rc;
+    e = hipMemcpy(counts_host, c_dev, cbytes, hipMemcpyDeviceToHost);
+    if (e != hipSuccess)
+        return fail(KNN_EHIP, "knn_index_count_within_host: D2H counts", hipGetErrorString(e));
+    // (not declared waited: the slot's buffers go back after the device-wide wait `stage` then makes itself, as the top-K host calls)
     return KNN_OK;
 }
 

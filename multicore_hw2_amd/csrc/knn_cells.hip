@@ -1206,7 +1206,7 @@ __global__ __launch_bounds__(64 * PW, KT == 1 && !CTR ? 4 : 3) void knn_cells_pr
     const float *__restrict__ frame, const unsigned *__restrict__ tile_cell)   // CTR only
 {
 #pragma clang fp contract(off)
-    constexpr bool WR = false;
+    constexpr bool WR = false, CNT = false;
     constexpr float max_dist2 = 0.0f;
 #include "knn_cells_prep_body.inc"
 }
@@ -1223,8 +1223,33 @@ __global__ __launch_bounds__(64 * PW, KT == 1 ? 4 : 3) void knn_cells_prep_withi
     unsigned *__restrict__ counts, unsigned nlists, int lo_by_entry /* K */, float max_dist2)
 {
 #pragma clang fp contract(off)
-    constexpr bool CTR = false, TK = true, WR = true;
+    constexpr bool CTR = false, TK = true, WR = true, CNT = false;
     u64 *const keys_init = nullptr;
+    const float *const frame = nullptr;
+    const unsigned *const tile_cell = nullptr;
+#include "knn_cells_prep_body.inc"
+}
+
+// The count form (knn_index_count_within on the cell-pruned way, knn_cells_query_count): the radius form's body with CNT — query
+// fragments, gap tables, control-word and counter clearing as every form, and thr[q] / dup_out[q] = knn_threshold_within at
+// u = +INF, the radius cap alone: no seed tile is read, no selection network, no seed layer.  A kernel of its own, so that the
+// other forms' instantiations compile as they did.
+template <int PW, int SD, int KT>
+__global__ __launch_bounds__(64 * PW, KT == 1 ? 4 : 3) void knn_cells_prep_count_kernel(
+    const float *__restrict__ Q, int m, int m_padded, CellGeom g, const float *__restrict__ bounds, double sigma2,
+    const float *__restrict__ center, float sigma, const unsigned *__restrict__ tile_start, h8 *__restrict__ qfg,
+    float *__restrict__ lo_tab, float *__restrict__ hi_tab, float bmax, float nmax, float amax_limit, float *__restrict__ thr,
+    float *__restrict__ dup_out, unsigned *__restrict__ ctl, unsigned *__restrict__ ctl_next, unsigned *__restrict__ counts,
+    unsigned nlists, float max_dist2)
+{
+#pragma clang fp contract(off)
+    constexpr bool CTR = false, TK = true, WR = true, CNT = true;
+    constexpr int lo_by_entry = 1;   // (TK: the low table is [query][entry]; K has no meaning here)
+    constexpr long long ntiles = 0;
+    u64 *const keys_init = nullptr;
+    const h8 *const rf = nullptr;
+    const unsigned *const rn2 = nullptr;
+    const SeedLayer layer = {nullptr, 0u, 0u, 0u, 0ull, {0u}};   // the empty seed layer: a count needs no seed
     const float *const frame = nullptr;
     const unsigned *const tile_cell = nullptr;
 #include "knn_cells_prep_body.inc"
@@ -2614,6 +2639,24 @@ static void cells_prep_topk_launch(const CellBatch &b)
     else
         (two ? cells_prep_topk_as<2, 1> : cells_prep_topk_as<4, 1>)(b);
 }
+// ... of a count pass (knn_index_count_within): the radius cap alone
+template <int PW, int KT>
+static void cells_prep_count_as(const CellBatch &b)
+{
+    const FilterState &st = b.st;
+    hipLaunchKernelGGL((knn_cells_prep_count_kernel<PW, 2, KT>), dim3((unsigned)b.m_padded), dim3(64 * PW), 0, b.s, b.q, b.m, b.m_padded,
+                       cell_geom_of(b.c, st.k), b.c.bounds, (double)st.sigma * (double)st.sigma, st.center, st.sigma, b.c.tile_start,
+                       (h8 *)b.w.qry_frags, b.w.lo_tab, b.w.hi_tab, st.bmax, st.nmax, kAmaxLimit, b.w.thr, b.w.dup, b.w.ctl_cur, b.ctl_next,
+                       b.w.counts, b.w.nlists, b.max_dist2);
+}
+static void cells_prep_count_launch(const CellBatch &b)
+{
+    const bool two = b.p.prep_pw == 2;
+    if (b.p.prep_kt == 2)
+        (two ? cells_prep_count_as<2, 2> : cells_prep_count_as<4, 2>)(b);
+    else
+        (two ? cells_prep_count_as<2, 1> : cells_prep_count_as<4, 1>)(b);
+}
 static void cells_prep_launch(const CellBatch &b)
 {
     const bool two = b.p.prep_pw == 2;
@@ -3090,6 +3133,65 @@ hipError_t knn_cells_query_topk(FilterState &st, FilterWorkspace &w, const CellT
     // gated: the exact top-K answers a pass that raised FALLBACK; it folds into the keys the select left alone (no limit: the caller
     // clips a radius call's lists)
     return knn_exact_topk_launch(call, w.ctl_cur + KNN_CTL_FALLBACK, false);
+}
+
+// One pass of <= KNN_CELL_BATCH queries of a count call (knn_index_count_within with KNN_QUERY_COUNT_CELLS; DESIGN §4.6 "Counts
+// within a radius"): count prep (the radius cap alone: no seed scoring) -> match -> record-only scan, both unchanged -> count
+// re-rank of the slices and of the shared overflow area -> out-of-box rows -> commit, gated on no FALLBACK -> the exact count,
+// gated on FALLBACK.  call.scratch (the pass's part of the slot's count scratch) is zero on entry.
+hipError_t knn_cells_query_count(FilterState &st, FilterWorkspace &w, const CellTopkPlan &tp, bool timed, const CountCall &call)
+{
+    const CellIndex &c = *st.cells;
+    const CellQueryPlan &p = tp.batch;
+    const int m = call.m;
+    hipStream_t s = call.stream;
+    if (!tp.use || m > tp.pass_m || tp.scan.self || tp.scan.ctr || c.centred || p.prep_ctr || !(call.max_dist2 < INFINITY) || !call.scratch)
+        return hipErrorInvalidValue;
+    const CellKernel scan = cells_records_kernel(tp.scan);
+    FTRY(ensure_cells_workspace(st, w, m, p, scan));
+    const int m_padded = (m + 31) / 32 * 32;
+    w.has_rows = false;
+    w.pieces = RerankPieces();
+    w.nlists = p.grid.nlists;
+    w.ovf_cap = p.grid.ovf_cap;
+    w.ovf_base = p.grid.ovf_base;
+    w.slice = p.grid.slice;
+    // the control words alternate exactly as in knn_cells_query and knn_cells_query_topk: 1-NN batches, top-K passes and count
+    // passes may follow one another on a slot
+    const unsigned parity = w.cell_batches++ & 1u;
+    w.ctl_cur = w.ctl + KNN_CTL_WORDS * (1u + parity);
+    unsigned *ctl_next = w.ctl + KNN_CTL_WORDS * (2u - parity);
+    // (no keys, no gids, the empty seed layer: counts of a cell-range shard are its own rows' and simply add across ranks)
+    const SeedLayer no_layer = {nullptr, 0u, 0u, 0u, 0ull, {0u}};
+    const CellBatch b{st, c, w, p, m, m_padded, call.q, call.r, 0ll, nullptr, nullptr, CellFinal{nullptr, nullptr, 0},
+                      cells_self(p, c, w, m_padded), no_layer, ctl_next, s, 1, call.max_dist2};
+    cells_prep_count_launch(b);
+    FTRY(hipGetLastError());
+    cells_match_kernel(p.match_waves).launch(b);
+    FTRY(hipGetLastError());
+    if (timed && w.ev_begin)
+        FTRY(hipEventRecord(w.ev_begin, s));
+    scan.launch(b);
+    FTRY(hipGetLastError());
+    if (timed && w.ev_end)
+        FTRY(hipEventRecord(w.ev_end, s));
+    TopkRecords rs;
+    rs.positions = st.ntiles * 32;
+    rs.rec = w.records;
+    rs.counts = w.counts;
+    rs.nlists = w.nlists;
+    rs.slice = w.slice;
+    rs.ctl = w.ctl_cur;
+    rs.perm = c.perm;
+    rs.n_outliers = st.n_outliers;
+    rs.outliers = st.outliers;
+    rs.ovf_rec = w.records + w.ovf_base;
+    rs.ovf_count = w.ctl_cur + KNN_CTL_RECORDS;
+    rs.ovf_slice = w.ovf_cap;
+    rs.pos_norms = st.ref_norms;
+    FTRY(knn_count_records_finish(call, rs, call.scratch));
+    // gated: the exact count answers a pass that raised FALLBACK (its scratch was not committed)
+    return knn_exact_count_launch(call, w.ctl_cur + KNN_CTL_FALLBACK);
 }
 
 // Test hook (host arithmetic, no GPU): knn_threshold's Dup for a seed score u — out = {thr, Dup as the prep kernel stores it (fp32,

@@ -1,8 +1,10 @@
 // knn_cells_prep_body.inc — the body of the cell-pruned path's preparation kernel (knn_cells.hip has the description), included
 // into knn_cells_prep_kernel<PW, SD, KT, CTR, TK> and into knn_cells_prep_within_kernel<PW, SD, KT>, the radius form of the top-K
 // prep kernel, which takes one argument more.  The including kernel provides the template parameters PW, SD, KT, the arguments of
-// knn_cells_prep_kernel by their names, and the constants CTR, TK, WR and max_dist2 (WR only: finite, >= 0).
+// knn_cells_prep_kernel by their names, and the constants CTR, TK, WR, CNT and max_dist2 (WR only: finite, >= 0).  CNT (with WR:
+// knn_index_count_within, knn_cells_prep_count_kernel): the count form, which scores no seed tile at all.
     static_assert(!WR || (TK && !CTR), "the radius form is a top-K form of the one-frame layouts");
+    static_assert(!CNT || WR, "the count form is a radius form");
     constexpr int SEEDS = 1 << SD, NS = SEEDS / PW;   // seed cells in all, per wave
     // seed tiles a wave requests at once (KT KiB each); TK: fewer — the selection network's registers come on top of the tiles in
     // flight, and the form must stay within its 1-NN twin's registers without scratch (a top-K call is worth milliseconds: the
@@ -163,7 +165,7 @@
     // the replicated seed layer.
     unsigned long long v_fa = 0ull, v_na = 0ull;
     unsigned v_nt = 0u, v_cell = 0u;
-    if (ok) {
+    if (!CNT && ok) {   // (the count form reads no seed tile: rf, rn2 and the layer are null there)
         const unsigned l = code - g.cell_base;
         if (code >= g.cell_base && l < g.ncells) {
             const unsigned tb = tile_start[l];
@@ -531,7 +533,11 @@
         return;
     }
     float u;
-    if constexpr (TK) {
+    if constexpr (CNT) {
+        // the count form (knn_cells_prep_count_kernel): no seed tile is scored — the radius alone bounds the query, knn_threshold_within
+        // at u = +INF (its case (a)); everything above that only the seed scores read is dead here
+        u = INFINITY;
+    } else if constexpr (TK) {
         const int topk = lo_by_entry;
         unsigned cur = KNN_SEED_NONE;   // the wave's 64 smallest score keys so far, ascending over the lanes
         unsigned wide_first = 0xFFFFFFFFu, wide_stride = 0u;   // the wide sample: list position v is tile (wide_first + v) wide_stride

@@ -150,6 +150,42 @@ hipError_t knn_topk_filter_finish(const TopkCall &c, const TopkRecords &rs);
 // b[j] <- the K smallest of a[j] and b[j] (both sorted lists of K keys), sorted.
 hipError_t knn_topk_merge_launch(int m, int K, const u64 *a, u64 *b, hipStream_t stream);
 
+// ---- counts within a radius (knn_index_count_within; DESIGN §4.6 "Counts within a radius") -------------------------------------
+// One count call as every way that answers it takes it: count_within (knn_api.cpp) fills it once.
+struct CountCall {
+    int k = 0, m = 0;
+    long long n = 0;               // the shard's rows
+    const float *q = nullptr, *r = nullptr;   // device [m][k], [n][k]
+    unsigned *counts = nullptr;    // device [m], the caller's: every way ADDS to it (an init call zeroes it ahead of the way's launches)
+    float max_dist2 = INFINITY;    // the radius, squared (>= 0, never -0; +INF: every row with a finite distance)
+    int num_cu = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;   // nullable: bracket the way's dominant kernel
+    unsigned *scratch = nullptr;   // the slot's count scratch [m] (the grid and cell ways; the exact way does not use it)
+
+    // queries [q0, q0 + mb) of the call: a pass of the cell-pruned way
+    CountCall pass(int q0, int mb) const
+    {
+        CountCall c = *this;
+        c.m = mb;
+        c.q = q + (size_t)q0 * k;
+        c.counts = counts + q0;
+        c.scratch = scratch + q0;
+        return c;
+    }
+};
+// Slices of the shard the exact count scan splits one chunk of mc queries into: the K <= 16 top-K scan's rule (about 32 waves
+// per CU, >= 1024 rows each) without the list room.  Host arithmetic only.
+long long knn_count_slices(int mc, long long n, int num_cu);
+// c.counts[j] += #{rows of the shard with a finite v0 distance E <= c.max_dist2}.  gate != nullptr: the launches do nothing unless
+// *gate != 0 (the grid way's give-up word).
+hipError_t knn_exact_count_launch(const CountCall &c, const unsigned *gate);
+// counts[j] += scratch[j] for j < m unless *giveup != 0: the grid way's commit, the opposite gate of the exact count behind it.
+hipError_t knn_count_commit_launch(int m, const unsigned *scratch, unsigned *counts, const unsigned *giveup, hipStream_t stream);
+// A cell-pruned count pass behind its record-only scan: every row of every record (the slices, then the shared overflow area as a
+// list of one; rs.perm and rs.pos_norms set, rs.gate_dup unused) and every out-of-box row with v0's arithmetic -> qcount[j] (the
+// pass's scratch, zero on entry), then the commit, gated on no FALLBACK.  An over-full record area raises FALLBACK.
+hipError_t knn_count_records_finish(const CountCall &c, const TopkRecords &rs, unsigned *qcount);
 // ---- MFMA filter + exact re-rank (knn_filter.hip) ---------------------------
 // Device-side control words of one filter query (FilterState::ctl).
 enum {
@@ -499,6 +535,30 @@ struct QueryRoute {
     CellTopkPlan topk;             // top-K: knn_cells_topk_plan's answer (use == (way == Cells))
 };
 QueryRoute knn_query_route(const QueryRouteInputs &in);
+// What a count call launches with (knn_count_route in knn_api.cpp: the ONE place its way is chosen; host arithmetic only,
+// knn_debug_count_plan).  The default is the exact count scan; the grid and the cell-pruned scan answer on request by flag.
+struct CountRouteInputs {
+    int k = 0, m = 0;
+    long long n = 0;               // rows of the shard (> 0)
+    bool radius_finite = false;
+    bool flag_grid = false, flag_cells = false;   // KNN_QUERY_COUNT_GRID, KNN_QUERY_COUNT_CELLS
+    bool has_grid = false;         // the index has a grid index
+    bool has_cells = false;        // ... a cell-sorted layout
+    bool centred = false, rows_u8 = false, bins = false, sharded = false;   // as CellTopkInputs
+    int path = 0, cells_option = 0;
+    int num_cu = 0;
+    long long radius_rings = 0;    // the rings the radius spans on the grid (knn_grid_radius_rings)
+};
+struct CountPlan {
+    QueryWay way = QueryWay::Exact;
+    int passes = 0, pass_m = 0;    // Cells: passes of <= KNN_CELL_BATCH queries; the first pass's queries
+    int rmax = 0;                  // Grid: rings a query walks before it gives up (knn_grid_topk_plan's rule at K = 1)
+    unsigned blocks = 0;
+    int waves = 0;                 // Grid: the kernel's blocks, waves per block (one query each)
+    long long slices = 0;          // slices of the exact count scan for the call's first chunk of queries
+    size_t scratch_bytes = 0;      // the slot's count scratch: [m] unsigned on the grid and cell ways, none on the exact way
+};
+CountPlan knn_count_route(const CountRouteInputs &in);
 // What a slot's three top-K buffers must hold for a call (host arithmetic only; knn_debug_topk_scratch): `part` the exact top-K
 // scan's per-slice lists — on the cell-pruned way also at a pass's and at the last pass's queries, whose gated exact top-K sizes
 // its lists by them —, `cand` the filter ways' candidate lists [m][knn_topk_ccap] + counters [m] or a folding grid call's lists,
@@ -600,6 +660,10 @@ hipError_t knn_cells_query(FilterState &st, FilterWorkspace &w, FilterCallOption
 // without the limit.  c.max_dist2 finite (a radius call, one-frame layouts): the prep kernel caps Dup_q with the radius
 // (knn_threshold_within).  timed: the pass records the call's events around its scan.
 hipError_t knn_cells_query_topk(FilterState &st, FilterWorkspace &w, const CellTopkPlan &tp, bool timed, const TopkCall &c);
+// One pass of <= KNN_CELL_BATCH queries of a count call (c: CountCall::pass; c.max_dist2 finite, one-frame layouts): count prep
+// (the radius cap alone) -> match -> record-only scan -> count re-rank -> out-of-box rows -> commit (no FALLBACK) -> the exact
+// count, gated on FALLBACK.  tp: knn_cells_topk_plan's pass shapes (knn_count_route asks it at K = 1).
+hipError_t knn_cells_query_count(FilterState &st, FilterWorkspace &w, const CellTopkPlan &tp, bool timed, const CountCall &c);
 
 // Builds the filter layouts for refs[0..n) (device, AoS).  Synchronous.  Leaves st.usable false
 // (and returns hipSuccess) when the data rules the filter out.
@@ -637,6 +701,9 @@ long long knn_grid_radius_rings(const GridState *gs, float max_dist2);
 // only rows with v0 distance <= c.max_dist2 are candidates, in the grid kernel and in the gated exact top-K behind it; a query
 // stops as soon as the face bound passes the radius.
 hipError_t knn_grid_query_topk(const GridState *gs, const GridTopkPlan &plan, int slot, const TopkCall &c, const unsigned **gate_out);
+// Counts on the grid index (KNN_QUERY_COUNT_GRID; knn_grid_count_kernel): c.scratch [m] receives the kernel's counts, the commit
+// (no give-up) or the gated exact count (give-up) adds the batch to c.counts.  rmax: CountPlan::rmax.
+hipError_t knn_grid_query_count(const GridState *gs, int rmax, int slot, const CountCall &c, const unsigned **gate_out);
 void knn_grid_info(const GridState *gs, long long info[4]);
 
 // ---- RCCL exchange step (knn_rccl.cpp; librccl is dlopen'ed at first use) -------------------
@@ -688,6 +755,9 @@ hipError_t knn_filter_query_topk(FilterState &st, FilterCallOptions opt, int slo
 // radius call: one-frame layouts cap their bound with it; the lists are NOT cut at it here (the gate lies slightly above): the
 // caller clips them.
 hipError_t knn_filter_query_topk_cells(FilterState &st, const CellTopkPlan &tp, int slot, const TopkCall &c);
+// Counts on the cell-pruned scan (KNN_QUERY_COUNT_CELLS), the whole call in passes of KNN_CELL_BATCH queries (knn_cells_query_count).
+// c.scratch [c.m] is zeroed here, once per call.
+hipError_t knn_filter_query_count_cells(FilterState &st, const CellTopkPlan &tp, int slot, const CountCall &c);
 // Test hook: raw filter scores S[m][n] (row-major) and the per-query thresholds for a query
 // batch, plus {sigma, eta, rho, amax, bmax}.  Synchronous.
 hipError_t knn_filter_debug(FilterState &st, int m, const float *q_dev, const float *r_dev,

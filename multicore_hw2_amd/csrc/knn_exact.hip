@@ -1378,3 +1378,237 @@ hipError_t knn_topk_filter_finish(const TopkCall &c, const TopkRecords &rs)
                        (const unsigned *)c.ccount, c.ccap, c.K, c.keys, c.init, (const unsigned *)(rs.ctl + KNN_CTL_FALLBACK));
     return hipGetLastError();
 }
+
+// ------------------------------------------------------------------------------------------
+// Counts within a radius (knn_index_count_within; DESIGN §4.6 "Counts within a radius").
+//
+// knn_exact_count_kernel<KC> — the skeleton of knn_exact_topk_kernel without its list: one wave per block, lanes = queries
+// (coordinates in VGPRs), rows of the block's slice as wave-uniform scalar loads, v0's arithmetic.  A row counts for a lane when
+// its distance E is finite and E <= max_dist2 (fp32 compare, equality inside: the candidate rule of knn_index_query_topk_within).
+// Each lane keeps ONE counter register and adds it to counts[q] once, at the end of the slice, when it is not zero: no LDS, no
+// list, no atomic per hit.  Integer adds: the result does not depend on the order the slices arrive in.
+// KC = chunks of 16 dimensions held in VGPRs (k <= 128); KC = 0: any k, the query's coordinates re-read from memory.
+// gate (nullable): returns at once when *gate == 0 (the fallback of the grid way and of a cell-pruned pass).
+// ------------------------------------------------------------------------------------------
+template <int KC>
+__global__ __launch_bounds__(KNN_WAVE) void knn_exact_count_kernel(const float *__restrict__ Q, const float *__restrict__ R, int k,
+                                                                  int m, long long n, long long rows_per_slice, float max_dist2,
+                                                                  unsigned *__restrict__ counts, const unsigned *__restrict__ gate)
+{
+#pragma clang fp contract(off)
+    if (gate && *gate == 0u)
+        return;
+    constexpr int KM = KC > 0 ? 16 * KC : 1;
+    const int lane = threadIdx.x;
+    const int q = blockIdx.y * KNN_WAVE + lane;
+    const int qa = min(q, m - 1);
+    float qv[KM];
+#pragma unroll
+    for (int d = 0; d < KM; ++d)
+        qv[d] = KC > 0 && d < k ? Q[(size_t)qa * k + d] : 0.0f;
+    unsigned cnt = 0u;
+    const long long i0 = (long long)blockIdx.x * rows_per_slice;
+    const long long i1 = min(n, i0 + rows_per_slice);
+    const float *__restrict__ r = R + (size_t)i0 * k;
+    const float *__restrict__ qp = Q + (size_t)qa * k;
+    for (long long i = i0; i < i1; ++i, r += k) {
+        float acc = 0.0f;
+        if (KC > 0) {
+#pragma unroll
+            for (int c = 0; c < (KC > 0 ? KC : 1); ++c) {
+                const int rem = k - 16 * c;   // wave-uniform
+                if (rem >= 16) {
+                    float rv[16];
+#pragma unroll
+                    for (int j = 0; j < 16; ++j)
+                        rv[j] = r[16 * c + j];   // wave-uniform address -> scalar loads
+#pragma unroll
+                    for (int j = 0; j < 16; ++j) {
+                        const float diff = qv[16 * c + j] - rv[j];
+                        const float sq = diff * diff;
+                        acc = acc + sq;
+                    }
+                } else if (rem > 0) {
+#pragma unroll
+                    for (int j = 0; j < 15; ++j)
+                        if (j < rem) {
+                            const float diff = qv[16 * c + j] - r[16 * c + j];
+                            const float sq = diff * diff;
+                            acc = acc + sq;
+                        }
+                }
+            }
+        } else {
+            for (int d = 0; d < k; ++d) {
+                const float diff = qp[d] - r[d];
+                const float sq = diff * diff;
+                acc = acc + sq;
+            }
+        }
+        cnt += acc < INFINITY && acc <= max_dist2 ? 1u : 0u;   // (NaN fails both compares)
+    }
+    if (q < m && cnt != 0u)
+        atomicAdd(&counts[q], cnt);
+}
+
+// counts[j] += scratch[j] unless *giveup != 0: what the grid way or a cell-pruned pass counted is committed only when nothing
+// handed the batch to the exact count, which runs under the opposite gate on the same word — one of the two adds, never both.
+__global__ __launch_bounds__(KNN_BLOCK) void knn_count_commit_kernel(const unsigned *__restrict__ scratch, int m,
+                                                                    unsigned *__restrict__ counts, const unsigned *__restrict__ giveup)
+{
+    if (*giveup != 0u)
+        return;
+    const int j = blockIdx.x * KNN_BLOCK + threadIdx.x;
+    if (j < m)
+        counts[j] += scratch[j];
+}
+
+// The cell-pruned count's re-rank (knn_cells_query_count): every row of every record with v0's arithmetic through perm, as
+// knn_topk_rerank_gated_kernel walks them — one block per list, positions whose layout norm is +INF (padding, rows outside the
+// robust box) skipped —, and a row within the radius adds one to its query's scratch count.  The 16 rows of a record sit on 16
+// neighbouring lanes and belong to one query: their hits are summed from one ballot and the record's first lane adds them.
+__global__ __launch_bounds__(KNN_BLOCK) void knn_count_rerank_kernel(const float *__restrict__ Q, const float *__restrict__ R, int k,
+                                                                    long long n, const u64 *__restrict__ rec,
+                                                                    const unsigned *__restrict__ counts, unsigned nlists,
+                                                                    unsigned slice, unsigned *__restrict__ ctl,
+                                                                    const unsigned *__restrict__ perm, const float *__restrict__ norms,
+                                                                    float max_dist2, unsigned *__restrict__ qcount)
+{
+    const unsigned list_id = blockIdx.x;
+    if (ctl[KNN_CTL_FALLBACK] != 0u || list_id >= nlists)
+        return;
+    const unsigned want = counts[list_id];
+    const unsigned nrec = min(want, slice);
+    if (threadIdx.x == 0 && want > slice)
+        ctl[KNN_CTL_FALLBACK] = 1u;
+    const u64 *__restrict__ list = rec + (size_t)list_id * slice;
+    const unsigned lane = threadIdx.x & 63u;
+    // (every wave runs the same number of rounds: the ballot below is taken by all 64 lanes)
+    for (unsigned c0 = 0u; c0 < nrec * 16u; c0 += KNN_BLOCK) {
+        const unsigned c = c0 + threadIdx.x;
+        bool hit = false;
+        unsigned qi = 0u;
+        if (c < nrec * 16u) {
+            const u64 e = list[c >> 4];
+            const unsigned lo = (unsigned)e, reg = c & 15u;
+            const long long pos = (long long)(lo >> 1) * 32 + 8 * (reg >> 2) + 4 * (lo & 1u) + (reg & 3u);   // (rerank_pair's)
+            const unsigned rmask = pos < n && norms[pos] < INFINITY ? 0xFFFFu : 0u;
+            const u64 key = rerank_pair<0>(Q, R, k, n, 0ll, e, reg, rmask, 0u, perm, qi);   // ~0: nothing there, or not finite
+            hit = key != ~0ull && __uint_as_float((unsigned)(key >> 32)) <= max_dist2;
+        }
+        const u64 hits = __ballot(hit);
+        const unsigned mine = (unsigned)__popcll((hits >> (lane & 48u)) & 0xFFFFull);
+        if ((lane & 15u) == 0u && mine != 0u)
+            atomicAdd(&qcount[qi], mine);
+    }
+}
+
+// Rows outside the filter's robust box never enter the scan: every (query, listed row) pair once, with v0's arithmetic.
+// grid (row blocks, queries); one add per wave.
+__global__ __launch_bounds__(KNN_BLOCK) void knn_count_outlier_kernel(const float *__restrict__ Q, const float *__restrict__ R, int k,
+                                                                     unsigned count, const unsigned *__restrict__ list,
+                                                                     const unsigned *__restrict__ ctl, float max_dist2,
+                                                                     unsigned *__restrict__ qcount)
+{
+#pragma clang fp contract(off)
+    if (ctl[KNN_CTL_FALLBACK] != 0u)
+        return;
+    const unsigned q = blockIdx.y;
+    const float *__restrict__ qp = Q + (size_t)q * k;
+    unsigned cnt = 0u;
+    for (unsigned j = blockIdx.x * KNN_BLOCK + threadIdx.x; j < count; j += gridDim.x * KNN_BLOCK) {
+        const float *__restrict__ r = R + (size_t)list[j] * k;
+        float acc = 0.0f;
+        for (int d = 0; d < k; ++d) {
+            const float diff = qp[d] - r[d];
+            const float sq = diff * diff;
+            acc = acc + sq;
+        }
+        cnt += acc < INFINITY && acc <= max_dist2 ? 1u : 0u;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+        cnt += (unsigned)__shfl_xor((int)cnt, off, KNN_WAVE);
+    if ((threadIdx.x & 63u) == 0u && cnt != 0u)
+        atomicAdd(&qcount[q], cnt);
+}
+
+long long knn_count_slices(int mc, long long n, int num_cu)
+{
+    const unsigned qg = (unsigned)knn_divup(mc, KNN_WAVE);
+    long long slices = (long long)num_cu * 32 / qg;
+    const long long by_rows = (n + 1023) / 1024;
+    if (slices > by_rows)
+        slices = by_rows;
+    if (slices > 65535)
+        slices = 65535;
+    if (slices < 1)
+        slices = 1;
+    const long long per = (n + slices - 1) / slices;
+    return (n + per - 1) / per;
+}
+
+hipError_t knn_exact_count_launch(const CountCall &c, const unsigned *gate)
+{
+    if (c.m <= 0 || c.n <= 0)
+        return hipSuccess;
+    hipStream_t s = c.stream;
+    for (int c0 = 0; c0 < c.m; c0 += KNN_TOPK_CHUNK) {
+        const int mc = c.m - c0 < KNN_TOPK_CHUNK ? c.m - c0 : KNN_TOPK_CHUNK;
+        const long long slices = knn_count_slices(mc, c.n, c.num_cu);
+        const long long per = (c.n + slices - 1) / slices;
+        const dim3 grid((unsigned)slices, (unsigned)knn_divup(mc, KNN_WAVE)), block(KNN_WAVE);
+        const float *qc = c.q + (size_t)c0 * c.k;
+#define KNN_COUNT_SCAN(KCV) \
+    hipLaunchKernelGGL(knn_exact_count_kernel<KCV>, grid, block, 0, s, qc, c.r, c.k, mc, c.n, per, c.max_dist2, c.counts + c0, gate)
+        switch ((c.k + 15) / 16) {
+        case 1: KNN_COUNT_SCAN(1); break;
+        case 2: KNN_COUNT_SCAN(2); break;
+        case 3: KNN_COUNT_SCAN(3); break;
+        case 4: KNN_COUNT_SCAN(4); break;
+        case 5: KNN_COUNT_SCAN(5); break;
+        case 6: KNN_COUNT_SCAN(6); break;
+        case 7: KNN_COUNT_SCAN(7); break;
+        case 8: KNN_COUNT_SCAN(8); break;
+        default: KNN_COUNT_SCAN(0); break;
+        }
+#undef KNN_COUNT_SCAN
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess)
+            return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t knn_count_commit_launch(int m, const unsigned *scratch, unsigned *counts, const unsigned *giveup, hipStream_t s)
+{
+    if (m <= 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(knn_count_commit_kernel, dim3((unsigned)knn_divup(m, KNN_BLOCK)), dim3(KNN_BLOCK), 0, s, scratch, m, counts, giveup);
+    return hipGetLastError();
+}
+
+hipError_t knn_count_records_finish(const CountCall &c, const TopkRecords &rs, unsigned *qcount)
+{
+    hipStream_t s = c.stream;
+    if (rs.rec_rows || !rs.perm || !rs.pos_norms || !qcount)
+        return hipErrorInvalidValue;
+    if (rs.nlists)
+        hipLaunchKernelGGL(knn_count_rerank_kernel, dim3(rs.nlists), dim3(KNN_BLOCK), 0, s, c.q, c.r, c.k, rs.positions, rs.rec, rs.counts,
+                           rs.nlists, rs.slice, rs.ctl, rs.perm, rs.pos_norms, c.max_dist2, qcount);
+    if (rs.ovf_rec && rs.ovf_count)   // the shared overflow area as a list of one (its `want > slice` rule raises FALLBACK when over-full)
+        hipLaunchKernelGGL(knn_count_rerank_kernel, dim3(1), dim3(KNN_BLOCK), 0, s, c.q, c.r, c.k, rs.positions, rs.ovf_rec, rs.ovf_count,
+                           1u, rs.ovf_slice, rs.ctl, rs.perm, rs.pos_norms, c.max_dist2, qcount);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess)
+        return e;
+    if (rs.n_outliers) {
+        const unsigned gx = (rs.n_outliers + KNN_BLOCK - 1) / KNN_BLOCK < 64u ? (rs.n_outliers + KNN_BLOCK - 1) / KNN_BLOCK : 64u;
+        hipLaunchKernelGGL(knn_count_outlier_kernel, dim3(gx, (unsigned)c.m), dim3(KNN_BLOCK), 0, s, c.q, c.r, c.k, rs.n_outliers,
+                           rs.outliers, (const unsigned *)rs.ctl, c.max_dist2, qcount);
+        e = hipGetLastError();
+        if (e != hipSuccess)
+            return e;
+    }
+    return knn_count_commit_launch(c.m, qcount, c.counts, rs.ctl + KNN_CTL_FALLBACK, s);
+}

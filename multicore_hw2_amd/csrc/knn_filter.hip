@@ -2707,6 +2707,21 @@ hipError_t knn_filter_query_topk_cells(FilterState &st, const CellTopkPlan &tp, 
     return hipSuccess;
 }
 
+hipError_t knn_filter_query_count_cells(FilterState &st, const CellTopkPlan &tp, int slot, const CountCall &c)
+{
+    if (!st.cells || !tp.use || !c.scratch)
+        return hipErrorInvalidValue;
+    FilterWorkspace &w = st.ws[slot];
+    w.ev_begin = c.ev0;
+    w.ev_end = c.ev1;
+    const int cell_batch = KNN_CELL_BATCH;
+    FTRY(ensure_workspace(st, w, std::min(c.m, cell_batch)));
+    FTRY(hipMemsetAsync(c.scratch, 0, (size_t)c.m * sizeof(unsigned), c.stream));
+    for (int q0 = 0; q0 < c.m; q0 += cell_batch)
+        FTRY(knn_cells_query_count(st, w, tp, q0 == 0, c.pass(q0, std::min(cell_batch, c.m - q0))));
+    return hipSuccess;
+}
+
 // knn_filter_debug's scores: knn_filter_scores_kernel<KT>, KT = 0: knn_filter_scores_rt_kernel (run-time kt, k > 512).
 template <int KT>
 static void filter_scores_as(const FilterState &st, const FilterWorkspace &w, int m, float *scores, hipStream_t s)

@@ -429,6 +429,97 @@ __global__ __launch_bounds__(GRID_BLOCK) void knn_grid_within_kernel(const float
 #include "knn_grid_topk_body.inc"
 }
 
+// ---- counts within a radius (KNN_QUERY_COUNT_GRID; knn_index_count_within) ------------------------
+// One wave per query, the 1-NN kernel's walk: lanes take the cells of ring r and count the rows whose v0 distance E is finite and
+// <= max_dist2 (fp32 compare, equality inside) in a register each.  After ring r the wave stops when the block of rings 0..r is
+// the whole grid, or when max_dist2 < lb^2 (1 - 1e-6) — the radius clause of knn_grid_within_kernel with its argument: every
+// unseen row's computed distance is strictly above that bound, so none is within the radius; the test is wave-uniform (the
+// query, its cell and r decide it).  Every cell of rings 0..r is visited once (grid_ring_cell: a position of the (2r+1)^K block
+// belongs to exactly one ring), every row sits in one cell: no row is counted twice.  One wave reduction at the end, lane 0 stores
+// the query's count to out[q] — the slot's scratch, never the caller's counts: a batch that gives up is answered again by the
+// exact count behind this kernel, and knn_count_commit_kernel adds the scratch only when nobody gave up.  Past rmax rings the
+// query raises the give-up word (the slot's two words alternate as in the other grid kernels).  No LDS, no block barrier.
+template <int KD>
+__global__ __launch_bounds__(GRID_BLOCK) void knn_grid_count_kernel(const float *__restrict__ Q, int m, GridGeom gg,
+                                                                    const unsigned *__restrict__ start,
+                                                                    const f4g *__restrict__ pts, unsigned *__restrict__ out,
+                                                                    int rmax, unsigned *__restrict__ giveup,
+                                                                    unsigned *__restrict__ giveup_next, float max_dist2)
+{
+#pragma clang fp contract(off)
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        *giveup_next = 0u;   // (the slot's other word, as the 1-NN kernel)
+    const int lane = threadIdx.x & 63;
+    const int qi = blockIdx.x * (GRID_BLOCK / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (qi >= m)
+        return;
+    float q[4] = {0.f, 0.f, 0.f, 0.f};
+    bool finite = true;
+#pragma unroll
+    for (int d = 0; d < KD; ++d) {
+        q[d] = Q[(size_t)qi * KD + d];
+        finite = finite && fabsf(q[d]) < INFINITY;
+    }
+    if (!finite) {   // every distance is NaN or +INF: no row counts (and nothing to give up on)
+        if (lane == 0)
+            out[qi] = 0u;
+        return;
+    }
+    int c[4];
+    (void)grid_cell_of(gg, q, c);
+    int gmax = 1;
+#pragma unroll
+    for (int d = 0; d < KD; ++d)
+        gmax = gg.g[d] > gmax ? gg.g[d] : gmax;
+
+    unsigned cnt = 0u;
+    bool done = false;
+    bool first = true;   // (rings 0 and 1 together, as the 1-NN kernel)
+    for (int r = gmax > 1 ? 1 : 0; r < gmax && r <= rmax; ++r) {
+        const int side = 2 * r + 1;
+        int total = 1;
+#pragma unroll
+        for (int d = 0; d < KD; ++d)
+            total *= side;
+        for (int idx = lane; idx < total; idx += KNN_WAVE) {
+            unsigned cell;
+            if (!grid_ring_cell<KD>(gg, c, r, side, idx, first, &cell))
+                continue;
+            const unsigned p0 = start[cell], p1 = start[cell + 1];
+            for (unsigned p = p0; p < p1; ++p) {
+                const f4g x = pts[p];
+                float acc = 0.0f;
+#pragma unroll
+                for (int d = 0; d < KD; ++d) {
+                    const float diff = q[d] - x[d];   // v0: search - reference, squared, summed in order
+                    const float sq = diff * diff;
+                    acc = acc + sq;
+                }
+                cnt += acc < INFINITY && acc <= max_dist2 ? 1u : 0u;
+            }
+        }
+        first = false;
+        bool covers_all;
+        const double lb = grid_face_bound<KD>(gg, c, q, r, &covers_all);
+        if (covers_all) {
+            done = true;
+            break;
+        }
+        if (lb > 0.0 && (double)max_dist2 < lb * lb * (1.0 - 1e-6)) {   // no unseen row is within the radius
+            done = true;
+            break;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+        cnt += (unsigned)__shfl_xor((int)cnt, off, KNN_WAVE);
+    if (lane == 0) {
+        out[qi] = cnt;
+        if (!done && gmax > rmax + 1)
+            *giveup = 1u;      // benign race: every writer stores 1
+    }
+}
+
 // ---- host -------------------------------------------------------------------------------------------
 #define GTRY(call)                     \
     do {                                 \
@@ -700,6 +791,40 @@ hipError_t knn_grid_query_topk(const GridState *gs, const GridTopkPlan &plan, in
     if (!c.init)
         GTRY(knn_topk_merge_launch(c.m, c.K, c.cand, c.keys, s));
     return hipSuccess;
+}
+
+// The whole count call on the grid way (KNN_QUERY_COUNT_GRID), asynchronous on c.stream: the grid kernel writes every query's
+// count to c.scratch [m]; the commit, gated on NO give-up, adds the scratch to c.counts; the exact count, gated on the give-up
+// word, adds the batch's counts itself.  One of the two runs, so no row is counted twice.  rmax: knn_grid_topk_plan's at K = 1 with
+// the rings the radius spans.  c.ev0 / c.ev1 (nullable) bracket the grid kernel.  *gate_out = the give-up word.
+hipError_t knn_grid_query_count(const GridState *gs, int rmax, int slot, const CountCall &c, const unsigned **gate_out)
+{
+    *gate_out = nullptr;
+    if (!gs || !gs->usable || c.m <= 0 || !c.scratch || !c.counts || rmax < 0)
+        return hipErrorInvalidValue;
+    const unsigned call = gs->calls[slot]++;
+    unsigned *giveup = gs->giveup + 2 * slot + (call & 1u);
+    unsigned *giveup_next = gs->giveup + 2 * slot + ((call + 1u) & 1u);
+    hipStream_t s = c.stream;
+    const dim3 grid((unsigned)((c.m + GRID_BLOCK / 64 - 1) / (GRID_BLOCK / 64))), block(GRID_BLOCK);
+    if (c.ev0)
+        GTRY(hipEventRecord(c.ev0, s));
+#define GRID_COUNT(KDV)                                                                                                       \
+    hipLaunchKernelGGL(knn_grid_count_kernel<KDV>, grid, block, 0, s, c.q, c.m, gs->geom, gs->start, gs->pts, c.scratch, rmax, \
+                       giveup, giveup_next, c.max_dist2)
+    switch (gs->geom.k) {
+    case 1: GRID_COUNT(1); break;
+    case 2: GRID_COUNT(2); break;
+    case 3: GRID_COUNT(3); break;
+    default: GRID_COUNT(4); break;
+    }
+#undef GRID_COUNT
+    GTRY(hipGetLastError());
+    if (c.ev1)
+        GTRY(hipEventRecord(c.ev1, s));
+    *gate_out = giveup;
+    GTRY(knn_count_commit_launch(c.m, c.scratch, c.counts, giveup, s));
+    return knn_exact_count_launch(c, giveup);
 }
 
 long long knn_grid_radius_rings(const GridState *gs, float max_dist2)
