@@ -1351,16 +1351,7 @@ int knn_index_count_within(knn_index *idx, int slot, int m, const float *queries
         HIP_TRY(knn_grid_query_count(idx->grid, plan.rmax, slot, call, &idx->grid_topk_gate));
         break;
     case QueryWay::Cells: {
-        // the passes' shapes: the cell-pruned top-K's plan at K = 1 — prep shape, match launch, the record-only scan's grid and lists
-        CellTopkInputs t = ri.t;
-        t.K = 1;
-        t.topk_cells = 1;
-        t.shard_partial = t.sharded;
-        t.frames_flag = false;
-        t.other_path = false;
-        t.n_outliers = 0u;   // (a count has no candidate list for them to crowd)
-        t.ccap = 64u;
-        const CellTopkPlan tp = knn_cells_topk_plan(t);
+        const CellTopkPlan tp = knn_cells_count_plan(ri.t);
         if (!tp.use)
             return fail(KNN_EHIP, "knn_index_count_within: the cell-pruned scan has no pass shape for this layout");
         HIP_TRY(knn_filter_query_count_cells(idx->filter, tp, slot, call));

@@ -2554,23 +2554,25 @@ static hipError_t cells_lds_limit(const void *fn, size_t limit)
     return hipSuccess;
 }
 
-// What the launches of one batch read: the index, the slot's workspace, the plan and the call's arguments.
+// What the launches of one batch read: the index, the slot's workspace, the plan and the call's arguments.  A driver fills in
+// the call's part; cells_pass_front adds the last three, which follow from the workspace.
 struct CellBatch {
     const FilterState &st;
     const CellIndex &c;
     const FilterWorkspace &w;
     const CellQueryPlan &p;
-    int m, m_padded;
+    int m;
     const float *q, *r;
     long long base;
     u64 *keys, *keys_init;
     CellFinal fin;
-    CellSelf self;
     SeedLayer layer;
-    unsigned *ctl_next;
     hipStream_t s;
     int topk = 0;   // a top-K pass: K (the prep kernel's TK form)
-    float max_dist2 = INFINITY;   // a top-K pass of a radius call: the radius (finite: the prep kernel's WR form)
+    float max_dist2 = INFINITY;   // a top-K pass of a radius call, a count pass: the radius (finite: the prep kernel's WR form)
+    int m_padded = 0;
+    CellSelf self = CellSelf{};
+    unsigned *ctl_next = nullptr;
 };
 
 struct CellKernel {   // a kernel the plan picked: its launch for a batch, and the kernel itself (for its attributes)
@@ -2583,89 +2585,72 @@ struct CellKernel {   // a kernel the plan picked: its launch for a batch, and t
 // of dependent round trips, and at a rank's size the step is made of those — emulated rank of N = 8, ms per step / one
 // batch at a time: 16 cells x 2 tiles 0.0302 / 0.0526, 8 x 2 0.0279 / 0.0493, 4 x 2 0.0275 / 0.0471, 4 x 4 0.0271 / 0.0473;
 // N = 4: 0.0432 / 0.0423 / 0.0414 / 0.0408.  profiles/r04_seed_sweep.txt)
-template <int PW, int KT, bool CTR>
-static void cells_prep_as(const CellBatch &b)
+// knn_cells_prep_kernel's three forms, told apart by its last four arguments:
+//   1-NN (TK false)             keys_init, the low table's order, the cells' frames (read with CTR only)
+//   top-K (TK, one frame)       no keys (the select kernel starts them), K — the K-th smallest seed score (knn_seed_kth.h) —, no frames
+//   top-K on per-cell frames    no keys, K — the K-th smallest frame-free bound (knn_frame_dup.h) —, the cells' frames
+template <int PW, int KT, bool CTR, bool TK>
+static CellKernel cells_prep_of()
 {
-    const FilterState &st = b.st;
-    hipLaunchKernelGGL((knn_cells_prep_kernel<PW, 2, KT, CTR>), dim3((unsigned)b.m_padded), dim3(64 * PW), 0, b.s, b.q, b.m, b.m_padded,
-                       cell_geom_of(b.c, st.k), b.c.bounds, (double)st.sigma * (double)st.sigma, st.center, st.sigma, b.c.tile_start,
-                       st.ntiles, (const h8 *)st.ref_frags, st.ref_norms2, b.layer, (h8 *)b.w.qry_frags, b.w.lo_tab, b.w.hi_tab, st.bmax,
-                       st.nmax, kAmaxLimit, b.w.thr, b.w.dup, b.w.ctl_cur, b.ctl_next, b.w.counts, b.w.nlists, b.keys_init,
-                       b.p.self_lists ? 1 : 0, b.c.cell_frame, b.c.tile_cell);
-}
-// the top-K form: the K-th smallest seed score (knn_seed_kth.h); the select kernel starts the keys
-template <int PW, int KT>
-static void cells_prep_topk_as(const CellBatch &b)
-{
-    const FilterState &st = b.st;
-    hipLaunchKernelGGL((knn_cells_prep_kernel<PW, 2, KT, false, true>), dim3((unsigned)b.m_padded), dim3(64 * PW), 0, b.s, b.q, b.m, b.m_padded,
-                       cell_geom_of(b.c, st.k), b.c.bounds, (double)st.sigma * (double)st.sigma, st.center, st.sigma, b.c.tile_start,
-                       st.ntiles, (const h8 *)st.ref_frags, st.ref_norms2, b.layer, (h8 *)b.w.qry_frags, b.w.lo_tab, b.w.hi_tab, st.bmax,
-                       st.nmax, kAmaxLimit, b.w.thr, b.w.dup, b.w.ctl_cur, b.ctl_next, b.w.counts, b.w.nlists, (u64 *)nullptr,
-                       b.topk, (const float *)nullptr, (const unsigned *)nullptr);
+    return {[](const CellBatch &b) {
+                const FilterState &st = b.st;
+                const bool frames = CTR || !TK;
+                hipLaunchKernelGGL((knn_cells_prep_kernel<PW, 2, KT, CTR, TK>), dim3((unsigned)b.m_padded), dim3(64 * PW), 0, b.s, b.q, b.m,
+                                   b.m_padded, cell_geom_of(b.c, st.k), b.c.bounds, (double)st.sigma * (double)st.sigma, st.center, st.sigma,
+                                   b.c.tile_start, st.ntiles, (const h8 *)st.ref_frags, st.ref_norms2, b.layer, (h8 *)b.w.qry_frags, b.w.lo_tab,
+                                   b.w.hi_tab, st.bmax, st.nmax, kAmaxLimit, b.w.thr, b.w.dup, b.w.ctl_cur, b.ctl_next, b.w.counts, b.w.nlists,
+                                   TK ? (u64 *)nullptr : b.keys_init, TK ? b.topk : b.p.self_lists ? 1 : 0,
+                                   frames ? b.c.cell_frame : (const float *)nullptr, frames ? b.c.tile_cell : (const unsigned *)nullptr);
+            },
+            (const void *)knn_cells_prep_kernel<PW, 2, KT, CTR, TK>};
 }
 // ... of a radius call (knn_index_query_topk_within): Dup_q capped by the radius
 template <int PW, int KT>
-static void cells_prep_within_as(const CellBatch &b)
+static CellKernel cells_prep_within_of()
 {
-    const FilterState &st = b.st;
-    hipLaunchKernelGGL((knn_cells_prep_within_kernel<PW, 2, KT>), dim3((unsigned)b.m_padded), dim3(64 * PW), 0, b.s, b.q, b.m, b.m_padded,
-                       cell_geom_of(b.c, st.k), b.c.bounds, (double)st.sigma * (double)st.sigma, st.center, st.sigma, b.c.tile_start,
-                       st.ntiles, (const h8 *)st.ref_frags, st.ref_norms2, b.layer, (h8 *)b.w.qry_frags, b.w.lo_tab, b.w.hi_tab, st.bmax,
-                       st.nmax, kAmaxLimit, b.w.thr, b.w.dup, b.w.ctl_cur, b.ctl_next, b.w.counts, b.w.nlists, b.topk, b.max_dist2);
-}
-// ... on per-cell frames: the K-th smallest frame-free bound (knn_frame_dup.h)
-template <int PW>
-static void cells_prep_topk_frames_as(const CellBatch &b)
-{
-    const FilterState &st = b.st;
-    hipLaunchKernelGGL((knn_cells_prep_kernel<PW, 2, 1, true, true>), dim3((unsigned)b.m_padded), dim3(64 * PW), 0, b.s, b.q, b.m, b.m_padded,
-                       cell_geom_of(b.c, st.k), b.c.bounds, (double)st.sigma * (double)st.sigma, st.center, st.sigma, b.c.tile_start,
-                       st.ntiles, (const h8 *)st.ref_frags, st.ref_norms2, b.layer, (h8 *)b.w.qry_frags, b.w.lo_tab, b.w.hi_tab, st.bmax,
-                       st.nmax, kAmaxLimit, b.w.thr, b.w.dup, b.w.ctl_cur, b.ctl_next, b.w.counts, b.w.nlists, (u64 *)nullptr,
-                       b.topk, b.c.cell_frame, b.c.tile_cell);
-}
-static void cells_prep_topk_launch(const CellBatch &b)
-{
-    const bool two = b.p.prep_pw == 2;
-    if (b.p.prep_ctr)   // (per-cell frames are not capped: a radius call clips their lists behind)
-        (two ? cells_prep_topk_frames_as<2> : cells_prep_topk_frames_as<4>)(b);
-    else if (b.max_dist2 < INFINITY && b.p.prep_kt == 2)
-        (two ? cells_prep_within_as<2, 2> : cells_prep_within_as<4, 2>)(b);
-    else if (b.max_dist2 < INFINITY)
-        (two ? cells_prep_within_as<2, 1> : cells_prep_within_as<4, 1>)(b);
-    else if (b.p.prep_kt == 2)
-        (two ? cells_prep_topk_as<2, 2> : cells_prep_topk_as<4, 2>)(b);
-    else
-        (two ? cells_prep_topk_as<2, 1> : cells_prep_topk_as<4, 1>)(b);
+    return {[](const CellBatch &b) {
+                const FilterState &st = b.st;
+                hipLaunchKernelGGL((knn_cells_prep_within_kernel<PW, 2, KT>), dim3((unsigned)b.m_padded), dim3(64 * PW), 0, b.s, b.q, b.m,
+                                   b.m_padded, cell_geom_of(b.c, st.k), b.c.bounds, (double)st.sigma * (double)st.sigma, st.center, st.sigma,
+                                   b.c.tile_start, st.ntiles, (const h8 *)st.ref_frags, st.ref_norms2, b.layer, (h8 *)b.w.qry_frags, b.w.lo_tab,
+                                   b.w.hi_tab, st.bmax, st.nmax, kAmaxLimit, b.w.thr, b.w.dup, b.w.ctl_cur, b.ctl_next, b.w.counts, b.w.nlists,
+                                   b.topk, b.max_dist2);
+            },
+            (const void *)knn_cells_prep_within_kernel<PW, 2, KT>};
 }
 // ... of a count pass (knn_index_count_within): the radius cap alone
 template <int PW, int KT>
-static void cells_prep_count_as(const CellBatch &b)
+static CellKernel cells_prep_count_of()
 {
-    const FilterState &st = b.st;
-    hipLaunchKernelGGL((knn_cells_prep_count_kernel<PW, 2, KT>), dim3((unsigned)b.m_padded), dim3(64 * PW), 0, b.s, b.q, b.m, b.m_padded,
-                       cell_geom_of(b.c, st.k), b.c.bounds, (double)st.sigma * (double)st.sigma, st.center, st.sigma, b.c.tile_start,
-                       (h8 *)b.w.qry_frags, b.w.lo_tab, b.w.hi_tab, st.bmax, st.nmax, kAmaxLimit, b.w.thr, b.w.dup, b.w.ctl_cur, b.ctl_next,
-                       b.w.counts, b.w.nlists, b.max_dist2);
+    return {[](const CellBatch &b) {
+                const FilterState &st = b.st;
+                hipLaunchKernelGGL((knn_cells_prep_count_kernel<PW, 2, KT>), dim3((unsigned)b.m_padded), dim3(64 * PW), 0, b.s, b.q, b.m,
+                                   b.m_padded, cell_geom_of(b.c, st.k), b.c.bounds, (double)st.sigma * (double)st.sigma, st.center, st.sigma,
+                                   b.c.tile_start, (h8 *)b.w.qry_frags, b.w.lo_tab, b.w.hi_tab, st.bmax, st.nmax, kAmaxLimit, b.w.thr, b.w.dup,
+                                   b.w.ctl_cur, b.ctl_next, b.w.counts, b.w.nlists, b.max_dist2);
+            },
+            (const void *)knn_cells_prep_count_kernel<PW, 2, KT>};
 }
-static void cells_prep_count_launch(const CellBatch &b)
+// The prep kernel's forms: what the pass is for, then the plan's prep shape (prep_pw waves per query, prep_kt, prep_ctr) — the 12
+// instantiations of knn_cells_prep_kernel and the 4 each of the radius and the count kernel.
+enum class CellPrepForm { Nearest, Topk, TopkWithin, Count };
+static CellKernel cells_prep_kernel(CellPrepForm form, const CellQueryPlan &p)
 {
-    const bool two = b.p.prep_pw == 2;
-    if (b.p.prep_kt == 2)
-        (two ? cells_prep_count_as<2, 2> : cells_prep_count_as<4, 2>)(b);
-    else
-        (two ? cells_prep_count_as<2, 1> : cells_prep_count_as<4, 1>)(b);
-}
-static void cells_prep_launch(const CellBatch &b)
-{
-    const bool two = b.p.prep_pw == 2;
-    if (b.p.prep_ctr)
-        (two ? cells_prep_as<2, 1, true> : cells_prep_as<4, 1, true>)(b);
-    else if (b.p.prep_kt == 2)
-        (two ? cells_prep_as<2, 2, false> : cells_prep_as<4, 2, false>)(b);
-    else
-        (two ? cells_prep_as<2, 1, false> : cells_prep_as<4, 1, false>)(b);
+    const bool two = p.prep_pw == 2, kt2 = p.prep_kt == 2;
+    if (form == CellPrepForm::Count)
+        return kt2 ? (two ? cells_prep_count_of<2, 2>() : cells_prep_count_of<4, 2>()) : (two ? cells_prep_count_of<2, 1>() : cells_prep_count_of<4, 1>());
+    if (form == CellPrepForm::Nearest) {
+        if (p.prep_ctr)
+            return two ? cells_prep_of<2, 1, true, false>() : cells_prep_of<4, 1, true, false>();
+        return kt2 ? (two ? cells_prep_of<2, 2, false, false>() : cells_prep_of<4, 2, false, false>())
+                   : (two ? cells_prep_of<2, 1, false, false>() : cells_prep_of<4, 1, false, false>());
+    }
+    if (p.prep_ctr)   // (per-cell frames are not capped: a radius call clips their lists behind)
+        return two ? cells_prep_of<2, 1, true, true>() : cells_prep_of<4, 1, true, true>();
+    if (form == CellPrepForm::TopkWithin)
+        return kt2 ? (two ? cells_prep_within_of<2, 2>() : cells_prep_within_of<4, 2>()) : (two ? cells_prep_within_of<2, 1>() : cells_prep_within_of<4, 1>());
+    return kt2 ? (two ? cells_prep_of<2, 2, false, true>() : cells_prep_of<4, 2, false, true>())
+               : (two ? cells_prep_of<2, 1, false, true>() : cells_prep_of<4, 1, false, true>());
 }
 
 template <int WAVES>
@@ -2770,7 +2755,7 @@ static void cells_tail_launch(const CellBatch &b)
     (b.p.tail_kt == 2 ? cells_tail_as<0, 2> : b.p.tail_k == 16 ? cells_tail_as<16> : b.p.tail_k == 8 ? cells_tail_as<8> : cells_tail_as<0>)(b);
 }
 
-static hipError_t ensure_cells_workspace(FilterState &st, FilterWorkspace &w, int m, const CellQueryPlan &p, const CellKernel &scan)
+static hipError_t ensure_cells_workspace(const FilterState &st,FilterWorkspace &w, int m, const CellQueryPlan &p, const CellKernel &scan)
 {
     const CellIndex &c = *st.cells;
     if (!w.cell_counts)
@@ -2973,6 +2958,68 @@ static SeedLayer cells_seed_layer(const CellIndex &c)
     return layer;
 }
 
+// The front half of every cell-pruned pass — a 1-NN batch, a top-K pass, a count pass of <= KNN_CELL_BATCH queries —: the
+// slot's workspace and the kernels' LDS limits, the plan's record-list sizes into the workspace, the pass's control words, then
+// prep -> match (when the plan has a match launch) -> scan, the scan between the slot's events when `timed`.  b: the driver's
+// part of the batch, on workspace w (= b.w); m_padded, self and ctl_next are filled in here.  Behind it the driver finds the
+// scan's records in w, and the pass's control words at w.ctl_cur.
+// The control words: the slot has two blocks of them and consecutive passes alternate — the prep kernel of a pass clears the
+// other block and the record counters for the pass behind it, in every form —, so 1-NN batches, top-K passes and count passes
+// may follow one another on a slot in any order: this is the one place that hands a block out.  (The words of the first pass
+// were cleared at allocation.)
+static hipError_t cells_pass_front(FilterWorkspace &w, CellBatch &b, const CellKernel &scan, CellPrepForm prep, bool timed)
+{
+    const CellQueryPlan &p = b.p;
+    FTRY(ensure_cells_workspace(b.st, w, b.m, p, scan));
+    b.m_padded = (b.m + 31) / 32 * 32;
+    w.has_rows = false;
+    w.pieces = RerankPieces();
+    w.nlists = p.grid.nlists;
+    w.ovf_cap = p.grid.ovf_cap;
+    w.ovf_base = p.grid.ovf_base;
+    w.slice = p.grid.slice;
+    const unsigned parity = w.cell_batches++ & 1u;
+    w.ctl_cur = w.ctl + KNN_CTL_WORDS * (1u + parity);
+    b.ctl_next = w.ctl + KNN_CTL_WORDS * (2u - parity);
+    b.self = cells_self(p, b.c, w, b.m_padded);
+    cells_prep_kernel(prep, p).launch(b);
+    FTRY(hipGetLastError());
+    if (p.match_waves)
+        cells_match_kernel(p.match_waves).launch(b);
+    FTRY(hipGetLastError());
+    static const bool trace_cells = getenv("KNN_MI355X_TRACE_CELLS") != nullptr;   // (read once: a query may run beside a thread that changes the environment)
+    if (trace_cells && !p.self_lists)
+        FTRY(cells_trace_lists(b.c, w, b.m, b.s));
+    if (timed && w.ev_begin)
+        FTRY(hipEventRecord(w.ev_begin, b.s));
+    scan.launch(b);
+    FTRY(hipGetLastError());
+    if (timed && w.ev_end)
+        FTRY(hipEventRecord(w.ev_end, b.s));
+    return hipSuccess;
+}
+
+// The records a pass's scan left in the workspace, as the re-rank kernels of a top-K or a count pass read them: the waves'
+// slices, the shared overflow area as a list of one, the out-of-box rows, the layout's norms by position.
+static TopkRecords cells_pass_records(const FilterState &st, const FilterWorkspace &w)
+{
+    TopkRecords rs;
+    rs.positions = st.ntiles * 32;
+    rs.rec = w.records;
+    rs.counts = w.counts;
+    rs.nlists = w.nlists;
+    rs.slice = w.slice;
+    rs.ctl = w.ctl_cur;
+    rs.perm = st.cells->perm;
+    rs.n_outliers = st.n_outliers;
+    rs.outliers = st.outliers;
+    rs.ovf_rec = w.records + w.ovf_base;
+    rs.ovf_count = w.ctl_cur + KNN_CTL_RECORDS;
+    rs.ovf_slice = w.ovf_cap;
+    rs.pos_norms = st.ref_norms;
+    return rs;
+}
+
 // One batch of <= KNN_CELL_BATCH queries, the whole chain: prep -> match -> scan (its waves re-rank their own records) ->
 // [rows outside the robust box, exactly] -> the exact scan of the shard, gated on FALLBACK -> the tail kernel (gated: records
 // in the shared area, the listed pairs exactly when that area is over-full, the finalisation when the scan could not do it).
@@ -2983,35 +3030,9 @@ hipError_t knn_cells_query(FilterState &st, FilterWorkspace &w, FilterCallOption
     const CellIndex &c = *st.cells;
     const CellQueryPlan p = knn_cells_query_plan({st.k, st.kt, c.centred, c.rows_u8, c.ncells, c.nitems, c.cap, opt.several_slots,
                                                   opt.scan_blocks, opt.scan_deal, opt.cells_lists, m, num_cu, w.rec_cap});
-    FTRY(ensure_cells_workspace(st, w, m, p, cells_scan_kernel(p.scan)));
-    const int m_padded = (m + 31) / 32 * 32;
-    w.has_rows = false;
-    w.pieces = RerankPieces();
-    w.nlists = p.grid.nlists;
-    w.ovf_cap = p.grid.ovf_cap;
-    w.ovf_base = p.grid.ovf_base;
-    w.slice = p.grid.slice;
-
-    // the control words of this batch were cleared by the previous batch on this slot (or at allocation)
-    const unsigned parity = w.cell_batches++ & 1u;
-    w.ctl_cur = w.ctl + KNN_CTL_WORDS * (1u + parity);
-    unsigned *ctl_next = w.ctl + KNN_CTL_WORDS * (2u - parity);
-    const CellBatch b{st, c, w, p, m, m_padded, q, r, base, keys, init_keys ? keys : nullptr,
-                      CellFinal{c.gids, out_idx, st.n_outliers != 0u ? 1 : 0}, cells_self(p, c, w, m_padded), cells_seed_layer(c), ctl_next, s};
-    cells_prep_launch(b);
-    FTRY(hipGetLastError());
-    if (p.match_waves)
-        cells_match_kernel(p.match_waves).launch(b);
-    FTRY(hipGetLastError());
-    static const bool trace_cells = getenv("KNN_MI355X_TRACE_CELLS") != nullptr;   // (read once: a query may run beside a thread that changes the environment)
-    if (trace_cells && !p.self_lists)
-        FTRY(cells_trace_lists(c, w, m, s));
-    if (timed && w.ev_begin)
-        FTRY(hipEventRecord(w.ev_begin, s));
-    cells_scan_kernel(p.scan).launch(b);
-    FTRY(hipGetLastError());
-    if (timed && w.ev_end)
-        FTRY(hipEventRecord(w.ev_end, s));
+    CellBatch b{st, c, w, p, m, q, r, base, keys, init_keys ? keys : nullptr, CellFinal{c.gids, out_idx, st.n_outliers != 0u ? 1 : 0},
+                cells_seed_layer(c), s};
+    FTRY(cells_pass_front(w, b, cells_scan_kernel(p.scan), CellPrepForm::Nearest, timed));
     // rows outside the robust box never entered the layouts: exact scan of that (short) list
     FTRY(knn_exact_gather_launch(st.k, m, st.n_outliers, base, q, r, st.outliers, keys, num_cu, nullptr, s));
     if (p.exact_launch)
@@ -3070,6 +3091,22 @@ CellTopkPlan knn_cells_topk_plan(const CellTopkInputs &in)
     return t;
 }
 
+// The passes of a count call (knn_index_count_within on the cell-pruned way): the top-K pass plan at K = 1 on a one-frame layout —
+// prep shape, match launch, the record-only scan's grid and lists.  knn_count_route has chosen the way; here only the shapes are
+// made (use false: the layout has none), and knn_cells_query_count's guard holds the pass to them.
+CellTopkPlan knn_cells_count_plan(const CellTopkInputs &in)
+{
+    CellTopkInputs t = in;
+    t.K = 1;
+    t.topk_cells = 1;
+    t.shard_partial = t.sharded;
+    t.frames_flag = false;
+    t.other_path = false;
+    t.n_outliers = 0u;   // (a count has no candidate list for them to crowd)
+    t.ccap = 64u;
+    return knn_cells_topk_plan(t);
+}
+
 hipError_t knn_cells_query_topk(FilterState &st, FilterWorkspace &w, const CellTopkPlan &tp, bool timed, const TopkCall &call)
 {
     const CellIndex &c = *st.cells;
@@ -3079,56 +3116,21 @@ hipError_t knn_cells_query_topk(FilterState &st, FilterWorkspace &w, const CellT
     if (!tp.use || m > tp.pass_m || tp.scan.self || tp.scan.ctr != c.centred || p.prep_ctr != c.centred || call.ccap != tp.ccap ||
         call.gids != c.gids || (c.geom && (!c.gids || call.base != 0)))
         return hipErrorInvalidValue;
-    const CellKernel scan = cells_records_kernel(tp.scan);
-    FTRY(ensure_cells_workspace(st, w, m, p, scan));
-    const int m_padded = (m + 31) / 32 * 32;
-    w.has_rows = false;
-    w.pieces = RerankPieces();
-    w.nlists = p.grid.nlists;
-    w.ovf_cap = p.grid.ovf_cap;
-    w.ovf_base = p.grid.ovf_base;
-    w.slice = p.grid.slice;
-    // the control words: the two blocks alternate exactly as in knn_cells_query, so 1-NN batches and top-K passes may follow
-    // one another on a slot (the prep kernel clears the next one's words and the record counters in both forms)
-    const unsigned parity = w.cell_batches++ & 1u;
-    w.ctl_cur = w.ctl + KNN_CTL_WORDS * (1u + parity);
-    unsigned *ctl_next = w.ctl + KNN_CTL_WORDS * (2u - parity);
     // A cell-range shard (KNN_QUERY_TOPK_PARTIAL): the K-th seed bound over the rows of the GLOBAL set the seed layer reaches — the
     // prep kernel scores a seed cell of another rank from the layer's tiles, as the 1-NN form does —, and gids on the keys from the
     // moment they are candidates (the select sorts them, a fold compares them with other ranks'): CellFinal stays empty, nothing is
     // translated behind the select, while a 1-NN batch on the same slot keeps translating in its own last kernel.
-    const CellBatch b{st, c, w, p, m, m_padded, call.q, call.r, call.base, call.keys, nullptr, CellFinal{nullptr, nullptr, 0},
-                      cells_self(p, c, w, m_padded), cells_seed_layer(c), ctl_next, s, call.K, call.max_dist2};
+    CellBatch b{st, c, w, p, m, call.q, call.r, call.base, call.keys, nullptr, CellFinal{nullptr, nullptr, 0}, cells_seed_layer(c), s,
+                call.K, call.max_dist2};
     FTRY(hipMemsetAsync(call.ccount, 0, (size_t)m * sizeof(unsigned), s));
-    cells_prep_topk_launch(b);
-    FTRY(hipGetLastError());
-    cells_match_kernel(p.match_waves).launch(b);
-    FTRY(hipGetLastError());
-    if (timed && w.ev_begin)
-        FTRY(hipEventRecord(w.ev_begin, s));
-    scan.launch(b);
-    FTRY(hipGetLastError());
-    if (timed && w.ev_end)
-        FTRY(hipEventRecord(w.ev_end, s));
+    FTRY(cells_pass_front(w, b, cells_records_kernel(tp.scan), call.max_dist2 < INFINITY ? CellPrepForm::TopkWithin : CellPrepForm::Topk,
+                          timed));
     // every row of every record with v0's arithmetic -> the queries' candidate lists, behind the distance gate knn_topk_gate(Dup_q)
     // (the slices, then the shared overflow area as a list of one), the out-of-box rows, the select; all of them look at FALLBACK, which a query nothing bounds, fewer than K
     // real seed rows, an over-full record area or candidate list raise
-    TopkRecords rs;
-    rs.positions = st.ntiles * 32;
-    rs.rec = w.records;
-    rs.counts = w.counts;
-    rs.nlists = w.nlists;
-    rs.slice = w.slice;
-    rs.ctl = w.ctl_cur;
-    rs.perm = c.perm;
-    rs.n_outliers = st.n_outliers;
-    rs.outliers = st.outliers;
-    rs.ovf_rec = w.records + w.ovf_base;
-    rs.ovf_count = w.ctl_cur + KNN_CTL_RECORDS;
-    rs.ovf_slice = w.ovf_cap;
+    TopkRecords rs = cells_pass_records(st, w);
     rs.gate_dup = w.dup;
     rs.inv_sigma2 = (float)(1.0 / ((double)st.sigma * (double)st.sigma));
-    rs.pos_norms = st.ref_norms;
     FTRY(knn_topk_filter_finish(call, rs));
     // gated: the exact top-K answers a pass that raised FALLBACK; it folds into the keys the select left alone (no limit: the caller
     // clips a radius call's lists)
@@ -3144,52 +3146,13 @@ hipError_t knn_cells_query_count(FilterState &st, FilterWorkspace &w, const Cell
     const CellIndex &c = *st.cells;
     const CellQueryPlan &p = tp.batch;
     const int m = call.m;
-    hipStream_t s = call.stream;
     if (!tp.use || m > tp.pass_m || tp.scan.self || tp.scan.ctr || c.centred || p.prep_ctr || !(call.max_dist2 < INFINITY) || !call.scratch)
         return hipErrorInvalidValue;
-    const CellKernel scan = cells_records_kernel(tp.scan);
-    FTRY(ensure_cells_workspace(st, w, m, p, scan));
-    const int m_padded = (m + 31) / 32 * 32;
-    w.has_rows = false;
-    w.pieces = RerankPieces();
-    w.nlists = p.grid.nlists;
-    w.ovf_cap = p.grid.ovf_cap;
-    w.ovf_base = p.grid.ovf_base;
-    w.slice = p.grid.slice;
-    // the control words alternate exactly as in knn_cells_query and knn_cells_query_topk: 1-NN batches, top-K passes and count
-    // passes may follow one another on a slot
-    const unsigned parity = w.cell_batches++ & 1u;
-    w.ctl_cur = w.ctl + KNN_CTL_WORDS * (1u + parity);
-    unsigned *ctl_next = w.ctl + KNN_CTL_WORDS * (2u - parity);
     // (no keys, no gids, the empty seed layer: counts of a cell-range shard are its own rows' and simply add across ranks)
     const SeedLayer no_layer = {nullptr, 0u, 0u, 0u, 0ull, {0u}};
-    const CellBatch b{st, c, w, p, m, m_padded, call.q, call.r, 0ll, nullptr, nullptr, CellFinal{nullptr, nullptr, 0},
-                      cells_self(p, c, w, m_padded), no_layer, ctl_next, s, 1, call.max_dist2};
-    cells_prep_count_launch(b);
-    FTRY(hipGetLastError());
-    cells_match_kernel(p.match_waves).launch(b);
-    FTRY(hipGetLastError());
-    if (timed && w.ev_begin)
-        FTRY(hipEventRecord(w.ev_begin, s));
-    scan.launch(b);
-    FTRY(hipGetLastError());
-    if (timed && w.ev_end)
-        FTRY(hipEventRecord(w.ev_end, s));
-    TopkRecords rs;
-    rs.positions = st.ntiles * 32;
-    rs.rec = w.records;
-    rs.counts = w.counts;
-    rs.nlists = w.nlists;
-    rs.slice = w.slice;
-    rs.ctl = w.ctl_cur;
-    rs.perm = c.perm;
-    rs.n_outliers = st.n_outliers;
-    rs.outliers = st.outliers;
-    rs.ovf_rec = w.records + w.ovf_base;
-    rs.ovf_count = w.ctl_cur + KNN_CTL_RECORDS;
-    rs.ovf_slice = w.ovf_cap;
-    rs.pos_norms = st.ref_norms;
-    FTRY(knn_count_records_finish(call, rs, call.scratch));
+    CellBatch b{st, c, w, p, m, call.q, call.r, 0ll, nullptr, nullptr, CellFinal{nullptr, nullptr, 0}, no_layer, call.stream, 1, call.max_dist2};
+    FTRY(cells_pass_front(w, b, cells_records_kernel(tp.scan), CellPrepForm::Count, timed));
+    FTRY(knn_count_records_finish(call, cells_pass_records(st, w), call.scratch));
     // gated: the exact count answers a pass that raised FALLBACK (its scratch was not committed)
     return knn_exact_count_launch(call, w.ctl_cur + KNN_CTL_FALLBACK);
 }

@@ -509,6 +509,8 @@ static inline unsigned knn_topk_ccap(int K, int m)
     return (unsigned)std::min<long long>(4096 + 128 * (long long)K, ((long long)32 << 20) / m);
 }
 CellTopkPlan knn_cells_topk_plan(const CellTopkInputs &in);
+// the passes of a count call on the cell-pruned way: knn_cells_topk_plan at K = 1 on a one-frame layout (in: the call's route inputs)
+CellTopkPlan knn_cells_count_plan(const CellTopkInputs &in);
 
 // ---- which path answers a call, and what an index is built with (knn_api.cpp; host arithmetic only) ---------------------------
 // knn_query_route is the ONE place a call's path is chosen (DESIGN, "which path answers a call"): nothing is allocated or
@@ -662,7 +664,7 @@ hipError_t knn_cells_query(FilterState &st, FilterWorkspace &w, FilterCallOption
 hipError_t knn_cells_query_topk(FilterState &st, FilterWorkspace &w, const CellTopkPlan &tp, bool timed, const TopkCall &c);
 // One pass of <= KNN_CELL_BATCH queries of a count call (c: CountCall::pass; c.max_dist2 finite, one-frame layouts): count prep
 // (the radius cap alone) -> match -> record-only scan -> count re-rank -> out-of-box rows -> commit (no FALLBACK) -> the exact
-// count, gated on FALLBACK.  tp: knn_cells_topk_plan's pass shapes (knn_count_route asks it at K = 1).
+// count, gated on FALLBACK.  tp: knn_cells_count_plan's pass shapes.
 hipError_t knn_cells_query_count(FilterState &st, FilterWorkspace &w, const CellTopkPlan &tp, bool timed, const CountCall &c);
 
 // Builds the filter layouts for refs[0..n) (device, AoS).  Synchronous.  Leaves st.usable false

@@ -2614,6 +2614,21 @@ static hipError_t filter_scan(FilterState &st, FilterWorkspace &w, const FilterQ
     return hipSuccess;
 }
 
+// The passes of a call on the cell-pruned scan: the slot's events (the first pass records them around its scan), the workspace
+// sized for a pass, then pass(q0, mb, first) for every KNN_CELL_BATCH queries [q0, q0 + mb) of the call's m.
+// (a pass is what the scan's LDS holds the B operands of: 36 KiB, 68 KiB for 16 < k <= 32)
+template <typename Pass>
+static hipError_t cell_passes(FilterState &st, FilterWorkspace &w, hipEvent_t ev_begin, hipEvent_t ev_end, int m, Pass pass)
+{
+    w.ev_begin = ev_begin;
+    w.ev_end = ev_end;
+    const int cell_batch = KNN_CELL_BATCH;
+    FTRY(ensure_workspace(st, w, std::min(m, cell_batch)));
+    for (int q0 = 0; q0 < m; q0 += cell_batch)
+        FTRY(pass(q0, std::min(cell_batch, m - q0), q0 == 0));
+    return hipSuccess;
+}
+
 hipError_t knn_filter_query(FilterState &st, FilterCallOptions opt, bool pruned, int slot, int m, const float *q, const float *r, long long base,
                             u64 *keys, int num_cu, hipStream_t s, hipEvent_t ev_begin, hipEvent_t ev_end, bool init_keys,
                             int *out_idx)
@@ -2628,19 +2643,13 @@ hipError_t knn_filter_query(FilterState &st, FilterCallOptions opt, bool pruned,
     // (pruned or not is the caller's: knn_query_route.  Per-cell frames: the full scan cannot read them.)
     if (pruned ? (!st.cells || st.kt > 2) : (st.cells && st.cells->centred))
         return hipErrorInvalidValue;
+    if (pruned)
+        return cell_passes(st, w, ev_begin, ev_end, m, [&](int q0, int mb, bool first) {
+            return knn_cells_query(st, w, opt, mb, q + (size_t)q0 * st.k, r, base, keys + q0, num_cu, first, s, init_keys,
+                                   out_idx ? out_idx + q0 : nullptr);
+        });
     w.ev_begin = ev_begin;
     w.ev_end = ev_end;
-    if (pruned) {
-        const int cell_batch = KNN_CELL_BATCH;   // (the scan's LDS holds a pass's B operands: 36 KiB, 68 KiB for 16 < k <= 32)
-        FTRY(ensure_workspace(st, w, std::min(m, cell_batch)));
-        for (int q0 = 0; q0 < m; q0 += cell_batch) {
-            const int mb = std::min(cell_batch, m - q0);
-            const float *qb = q + (size_t)q0 * st.k;
-            u64 *kb = keys + q0;
-            FTRY(knn_cells_query(st, w, opt, mb, qb, r, base, kb, num_cu, q0 == 0, s, init_keys, out_idx ? out_idx + q0 : nullptr));
-        }
-        return hipSuccess;
-    }
     FTRY(filter_prelude(st, w, m, q, init_keys ? keys : nullptr, s));
     FTRY(filter_scan(st, w, knn_filter_query_plan({st.kt, st.ntiles, m, num_cu, w.rec_cap, opt}), m, s));
     // exact re-rank of the survivors; a list that overflowed its slice raises the fallback flag
@@ -2698,13 +2707,7 @@ hipError_t knn_filter_query_topk_cells(FilterState &st, const CellTopkPlan &tp, 
     if (!st.cells || !tp.use || c.ccap != tp.ccap)
         return hipErrorInvalidValue;
     FilterWorkspace &w = st.ws[slot];
-    w.ev_begin = c.ev0;
-    w.ev_end = c.ev1;
-    const int cell_batch = KNN_CELL_BATCH;
-    FTRY(ensure_workspace(st, w, std::min(c.m, cell_batch)));
-    for (int q0 = 0; q0 < c.m; q0 += cell_batch)
-        FTRY(knn_cells_query_topk(st, w, tp, q0 == 0, c.pass(q0, std::min(cell_batch, c.m - q0))));
-    return hipSuccess;
+    return cell_passes(st, w, c.ev0, c.ev1, c.m, [&](int q0, int mb, bool first) { return knn_cells_query_topk(st, w, tp, first, c.pass(q0, mb)); });
 }
 
 hipError_t knn_filter_query_count_cells(FilterState &st, const CellTopkPlan &tp, int slot, const CountCall &c)
@@ -2712,14 +2715,8 @@ hipError_t knn_filter_query_count_cells(FilterState &st, const CellTopkPlan &tp,
     if (!st.cells || !tp.use || !c.scratch)
         return hipErrorInvalidValue;
     FilterWorkspace &w = st.ws[slot];
-    w.ev_begin = c.ev0;
-    w.ev_end = c.ev1;
-    const int cell_batch = KNN_CELL_BATCH;
-    FTRY(ensure_workspace(st, w, std::min(c.m, cell_batch)));
-    FTRY(hipMemsetAsync(c.scratch, 0, (size_t)c.m * sizeof(unsigned), c.stream));
-    for (int q0 = 0; q0 < c.m; q0 += cell_batch)
-        FTRY(knn_cells_query_count(st, w, tp, q0 == 0, c.pass(q0, std::min(cell_batch, c.m - q0))));
-    return hipSuccess;
+    FTRY(hipMemsetAsync(c.scratch, 0, (size_t)c.m * sizeof(unsigned), c.stream));   // (every pass adds to its part)
+    return cell_passes(st, w, c.ev0, c.ev1, c.m, [&](int q0, int mb, bool first) { return knn_cells_query_count(st, w, tp, first, c.pass(q0, mb)); });
 }
 
 // knn_filter_debug's scores: knn_filter_scores_kernel<KT>, KT = 0: knn_filter_scores_rt_kernel (run-time kt, k > 512).

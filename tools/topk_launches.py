@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""The launches of a top-K call on every way and form, for comparing two builds of the library launch for launch.
+"""The launches of a top-K call on every way and form, and of the cell-pruned scan's three kinds of pass, for comparing two
+builds of the library launch for launch.
 
 Run (no arguments) it issues, on one stream and one workspace slot, the calls below; under
   rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 tools/topk_launches.py
@@ -9,7 +10,9 @@ the trace then holds their kernels in order.  KNN_MI355X_LIB names the build und
   cells   k 16, n 2^17 + 999, fp16 one-frame cell-sorted layout, option topk_cells 1 (two passes)   (m, K) = (1100, 8)
   grid    k 3, n 16384 (the smallest shard that gets a grid index), KNN_QUERY_TOPK_GRID   (m, K) = (70, 2), (70, 64)
 Each (index, m, K): a plain call and a call with a finite radius (the median 1-NN distance of the batch), each once writing
-its keys and once folding into them.  Each call's way (knn_index_last_stats()[0]) is printed as one JSON line.
+its keys and once folding into them.  The cells index then answers one 1-NN call (two batches) and one count call with
+KNN_QUERY_COUNT_CELLS at that radius (two passes) of the same m = 1100 queries: with its top-K passes, all three drivers of the
+cell-pruned scan.  Each call's way (knn_index_last_stats()[0]) is printed as one JSON line.
 
   topk_launches.py --compare A.csv B.csv
 reads two such kernel traces and prints the sequences of (kernel, grid, block) of the library's kernels and whether they are
@@ -61,6 +64,14 @@ def calls():
                             ix.query_topk_within(m, K, q.data_ptr(), radius, keys.data_ptr(), init_keys=init, **flags)
                         torch.cuda.synchronize()
                         print(json.dumps(dict(index=name, m=m, K=K, radius=radius, init=init, way=ix.last_stats()[0])), flush=True)
+                if name == "cells":
+                    ix.query_keys(m, q.data_ptr(), keys.data_ptr(), init_keys=True)
+                    torch.cuda.synchronize()
+                    print(json.dumps(dict(index=name, call="query_keys", m=m, way=ix.last_stats()[0])), flush=True)
+                    counts = torch.empty(m, dtype=torch.int32, device=dev)
+                    ix.count_within(m, q.data_ptr(), r2, counts.data_ptr(), init=True, cells=True)
+                    torch.cuda.synchronize()
+                    print(json.dumps(dict(index=name, call="count_within", m=m, radius=r2, way=ix.last_stats()[0])), flush=True)
         finally:
             ix.close()
     for o in options:
