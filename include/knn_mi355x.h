@@ -321,6 +321,49 @@ int knn_index_count_within(knn_index *idx, int slot, int m, const float *queries
 /* Synchronous: host queries [m][k] in, counts_host [m] out (this shard alone, written from scratch, the default way). */
 int knn_index_count_within_host(knn_index *idx, int m, const float *queries_host, float max_dist2, unsigned *counts_host);
 
+/* ------------------------------------------------------------------------
+ * 2e. Lists within a radius (range queries): WHICH rows of the shard lie within a distance of each query — the second pass of the
+ * classic count -> offsets -> fill scheme; 2d is its first.
+ *
+ *   knn_index_count_within (every shard, folding)  ->  knn_counts_to_offsets  ->  knn_index_list_within (every shard, appending)
+ *   ->  knn_keys_sort_segments (when an order is wanted)
+ *
+ * Segment j of keys_dev is [offsets_dev[j], offsets_dev[j + 1]); its room is the difference, capped at 2^32 - 1 (descending
+ * offsets: no room).  A row of the shard is a hit under exactly knn_index_count_within's rule: its v0 distance E is finite and
+ * E <= max_dist2 — fp32, accumulated in dimension order, no FMA, an fp32 compare with equality inside, -0 counts as 0.  A hit's
+ * packed key has E's bits in the high word and in the low word the global number the top-K keys carry (base_index + row, or the
+ * gid on a cell-range shard).  It is stored at keys_dev[offsets_dev[j] + p], p being the value fill_dev[j] had when the hit
+ * reserved its place; fill_dev[j] ends as its entry value plus this shard's number of hits, whether or not a hit was stored: a hit
+ * whose p is not below the room is NOT stored, nothing is ever stored outside a query's segment, and fill_dev[j] > room is how the
+ * caller sees an overflow — on the device, without a synchronisation.  With KNN_QUERY_INIT_KEYS the call zeroes fill_dev first;
+ * without it the call appends, so disjoint shards fold by calling one after the other on a stream: index-range shards and
+ * cell-range shards as they are (no seed layer, no KNN_QUERY_TOPK_PARTIAL contract), exactly as for counts.  fill_dev is unsigned
+ * 32-bit, as the counts are.  Within a segment the order of the keys is unspecified, and so is what lies beyond fill_dev[j];
+ * knn_keys_sort_segments gives the ascending (distance, global number) order.  An empty shard appends nothing.
+ * max_dist2 < 0 or NaN, m < 1, a slot outside 0 .. 7, a null pointer or any flag other than KNN_QUERY_INIT_KEYS,
+ * KNN_QUERY_COUNT_GRID and KNN_QUERY_COUNT_CELLS are KNN_EINVAL, each with its own knn_last_error text, checked before the index,
+ * and nothing is launched.  Asynchronous on `stream`; slots as for every other query; 1-NN, top-K, count and list calls may follow
+ * one another on a slot in any order.
+ * Ways: chosen exactly as for a count call (2d; knn_debug_count_plan describes a list call too).  1 = the exact list scan, the
+ * default.  3 = the grid index and 4 = the cell-pruned scan, by the same two flags under the same conditions; both reserve in the
+ * slot's scratch cursor — a copy of fill_dev — and store behind it, and the cursor becomes fill_dev only when no query gave up and
+ * no pass fell back; otherwise the exact list answers from the untouched fill_dev over the same places.  knn_index_last_stats: [0]
+ * the way, [1], [2], [3] as for the count.  The lists are exact on every way out. */
+/* offsets_dev[0] = 0, offsets_dev[j + 1] = offsets_dev[j] + counts_dev[j] (64-bit: totals pass 2^32).  Asynchronous. */
+int knn_counts_to_offsets(int device, const unsigned *counts_dev, int m, unsigned long long *offsets_dev /*[m+1]*/, void *stream);
+int knn_index_list_within(knn_index *idx, int slot, int m, const float *queries_dev, float max_dist2,
+                          const unsigned long long *offsets_dev /*[m+1]*/, unsigned *fill_dev /*[m]*/,
+                          unsigned long long *keys_dev, void *stream, unsigned flags);
+/* Sorts the first min(fill_dev[j], room of segment j) keys of every segment ascending; the entries beyond keep their bytes.
+ * Asynchronous. */
+int knn_keys_sort_segments(int device, int m, const unsigned long long *offsets_dev, const unsigned *fill_dev,
+                           unsigned long long *keys_dev, void *stream);
+/* Synchronous: count, offsets, list, sort on this shard alone (the default way).  offsets_host [m + 1]; *indices_out and
+ * *dist2_out (dist2_out may be NULL) receive malloc()'d arrays of offsets_host[m] entries — a 1-entry allocation when the total
+ * is 0 — that the caller free()s: query j's rows, nearest first, are entries offsets_host[j] .. offsets_host[j + 1] - 1. */
+int knn_index_list_within_host(knn_index *idx, int m, const float *queries_host, float max_dist2,
+                               long long *offsets_host, int **indices_out, float **dist2_out);
+
 /* Tuning / test hooks.  Known names:
  *   "path"    0 = auto, 1 = exact VALU kernels only, 2 = force the MFMA filter
  *             (+ exact re-rank) where its preconditions hold, 3 = the uniform-grid spatial index
@@ -551,7 +594,9 @@ int knn_debug_grid_within_plan(const long long in[7], long long out[6]);
  * the radius is finite, KNN_QUERY_COUNT_GRID given, KNN_QUERY_COUNT_CELLS given, has a grid index, has a cell-sorted layout,
  * per-cell frames, 8-bit rows, bin frames, cell-range shard, option "path", option "cells", CUs, the rings the radius spans on the
  * grid}; out = {way (1, 3, 4), passes and the first pass's queries (way 4), the grid's rmax, blocks and waves per block (way 3),
- * slices of the exact count scan, bytes of the slot's count scratch}.  Bad inputs are KNN_EINVAL. */
+ * slices of the exact count scan, bytes of the slot's count scratch}.  Bad inputs are KNN_EINVAL.  A knn_index_list_within call
+ * with the same arguments takes the same way, slices and passes, and the bytes also cover it: the count scratch [m] serves as its
+ * scratch cursor. */
 int knn_debug_count_plan(const long long in[16], long long out[8]);
 /* Test hook (host arithmetic only, no GPU needed): the bytes a workspace slot's three top-K buffers must hold for a call.
  * in = {the way that answers it (knn_index_last_stats' [0]: 1 exact, 2 filter, 3 grid, 4 cell-pruned), m, K, the shard's rows,

@@ -17,7 +17,8 @@ import sys
 import numpy as np
 
 __all__ = ["lib", "lib_path", "cudaCallback", "KnnIndex", "KnnGeom", "KnnError", "KEY_INIT", "set_option",
-           "get_option", "trim", "device_count", "EXPORTED_SYMBOLS", "shard_bounds", "keys_topk_merge"]
+           "get_option", "trim", "device_count", "EXPORTED_SYMBOLS", "shard_bounds", "keys_topk_merge", "counts_to_offsets",
+           "keys_sort_segments"]
 
 KEY_INIT = 0x7F80000000000000
 
@@ -35,6 +36,7 @@ EXPORTED_SYMBOLS = [
     "knn_index_query_topk_within", "knn_index_query_topk_within_host", "knn_debug_grid_within_plan", "knn_debug_within_bound",
     "knn_debug_frame_dup", "knn_debug_topk_scratch",
     "knn_index_count_within", "knn_index_count_within_host", "knn_debug_count_plan",
+    "knn_counts_to_offsets", "knn_index_list_within", "knn_keys_sort_segments", "knn_index_list_within_host",
 ]
 QUERY_INIT_KEYS = 1   # KNN_QUERY_INIT_KEYS
 QUERY_TOPK_PARTIAL = 2   # KNN_QUERY_TOPK_PARTIAL
@@ -437,6 +439,38 @@ def count_within_c():
     return f
 
 
+def list_within_c():
+    """knn_index_list_within with its argument types (set here, not in lib(), as count_within_c)."""
+    f = lib().knn_index_list_within
+    f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
+                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint]
+    return f
+
+
+def counts_to_offsets_c():
+    f = lib().knn_counts_to_offsets
+    f.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    return f
+
+
+def keys_sort_segments_c():
+    f = lib().knn_keys_sort_segments
+    f.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    return f
+
+
+def counts_to_offsets(counts_dev, m, offsets_dev, device=0, stream=0):
+    """Async (knn_counts_to_offsets): offsets_dev[m + 1] (uint64) <- the exclusive 64-bit prefix sums of counts_dev[m] (uint32)."""
+    _check(counts_to_offsets_c()(int(device), ctypes.c_void_p(int(counts_dev)), int(m), ctypes.c_void_p(int(offsets_dev)),
+                                 ctypes.c_void_p(stream)))
+
+
+def keys_sort_segments(m, offsets_dev, fill_dev, keys_dev, device=0, stream=0):
+    """Async (knn_keys_sort_segments): the first min(fill_dev[j], room of segment j) keys of every segment ascending."""
+    _check(keys_sort_segments_c()(int(device), int(m), ctypes.c_void_p(int(offsets_dev)), ctypes.c_void_p(int(fill_dev)),
+                                  ctypes.c_void_p(int(keys_dev)), ctypes.c_void_p(stream)))
+
+
 class KnnGeom:
     """Global grid of a cell-range sharded set (knn_geom_* in include/knn_mi355x.h): built from a sample of the GLOBAL set,
     identical on every rank that passes the same sample.  Host arithmetic only: works without a GPU (assign needs one)."""
@@ -610,6 +644,41 @@ class KnnIndex:
         f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p]
         _check(f(self._h, m, q.ctypes.data_as(ctypes.c_void_p), float(max_dist2), counts.ctypes.data_as(ctypes.c_void_p)))
         return counts
+
+    def list_within(self, m, queries_dev, max_dist2, offsets_dev, fill_dev, keys_dev, stream=0, slot=0, init=False, grid=False,
+                    cells=False):
+        """Async (knn_index_list_within): every row of this shard whose v0 squared distance to query j is finite and <= max_dist2
+        reserves place p = fill_dev[j]++ (uint32) and, when p is below the room of segment [offsets_dev[j], offsets_dev[j + 1])
+        (uint64), stores its packed key at keys_dev[offsets_dev[j] + p]; init (KNN_QUERY_INIT_KEYS): fill_dev is zeroed first,
+        else the call appends.  fill_dev[j] above the room: the segment overflowed (nothing was stored outside it).  grid /
+        cells: as count_within.  The order within a segment is unspecified (keys_sort_segments)."""
+        _check(list_within_c()(self._h, int(slot), int(m), ctypes.c_void_p(int(queries_dev)), float(max_dist2),
+                               ctypes.c_void_p(int(offsets_dev)), ctypes.c_void_p(int(fill_dev)), ctypes.c_void_p(int(keys_dev)),
+                               ctypes.c_void_p(stream),
+                               (QUERY_INIT_KEYS if init else 0) | (QUERY_COUNT_GRID if grid else 0) | (QUERY_COUNT_CELLS if cells else 0)))
+
+    def list_within_host(self, queries, max_dist2):
+        """Synchronous lists of this shard alone (knn_index_list_within_host): (offsets int64 [m + 1], indices int32 [total],
+        dist2 float32 [total]); query j's rows, nearest first, are entries offsets[j] .. offsets[j + 1] - 1."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1)
+        m = q.size // self.k
+        offsets = np.empty(m + 1, dtype=np.int64)
+        ind, d2 = ctypes.POINTER(ctypes.c_int)(), ctypes.POINTER(ctypes.c_float)()
+        f = lib().knn_index_list_within_host
+        f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p,
+                      ctypes.POINTER(ctypes.POINTER(ctypes.c_int)), ctypes.POINTER(ctypes.POINTER(ctypes.c_float))]
+        _check(f(self._h, m, q.ctypes.data_as(ctypes.c_void_p), float(max_dist2), offsets.ctypes.data_as(ctypes.c_void_p),
+                 ctypes.byref(ind), ctypes.byref(d2)))
+        total = int(offsets[m])
+        free = ctypes.CDLL(None).free
+        free.argtypes = [ctypes.c_void_p]
+        try:
+            indices = np.ctypeslib.as_array(ind, shape=(max(total, 1),))[:total].astype(np.int32, copy=True)
+            dist2 = np.ctypeslib.as_array(d2, shape=(max(total, 1),))[:total].astype(np.float32, copy=True)
+        finally:
+            free(ind)
+            free(d2)
+        return offsets, indices, dist2
 
     def query_topk_host(self, queries, K):
         """Synchronous top-K of this shard alone: (indices int32 [m][K], dist2 float32 [m][K])."""

@@ -1242,6 +1242,29 @@ bool topk_args_bad(const knn_index *idx, int slot, int m, int K, const float *qu
         !queries_dev || !keys_dev || (flags & ~(unsigned)(KNN_QUERY_INIT_KEYS | KNN_QUERY_TOPK_PARTIAL | KNN_QUERY_TOPK_GRID | KNN_QUERY_TOPK_FRAMES)) != 0u;
 }
 
+// The way of a count or list call on idx (knn_count_route's inputs from the index's facts, the call's radius and its two flags).
+CountPlan count_plan_of(const knn_index *idx, const QueryRouteInputs &ri, int m, float max_dist2, unsigned flags)
+{
+    CountRouteInputs ci;
+    ci.k = idx->k;
+    ci.m = m;
+    ci.n = idx->n;
+    ci.radius_finite = max_dist2 < INFINITY;
+    ci.flag_grid = (flags & KNN_QUERY_COUNT_GRID) != 0u;
+    ci.flag_cells = (flags & KNN_QUERY_COUNT_CELLS) != 0u;
+    ci.has_grid = ri.has_grid;
+    ci.has_cells = ri.t.has_cells;
+    ci.centred = ri.t.q.centred;
+    ci.rows_u8 = ri.t.q.rows_u8;
+    ci.bins = ri.t.bins;
+    ci.sharded = ri.t.sharded;
+    ci.path = ri.path;
+    ci.cells_option = ri.t.cells_option;
+    ci.num_cu = idx->num_cu;
+    ci.radius_rings = ci.has_grid && ci.radius_finite ? knn_grid_radius_rings(idx->grid, max_dist2) : 0;
+    return knn_count_route(ci);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1319,24 +1342,7 @@ int knn_index_count_within(knn_index *idx, int slot, int m, const float *queries
     if (idx->n == 0)   // an empty shard adds nothing
         return KNN_OK;
     const QueryRouteInputs ri = route_inputs(idx, m, 1, 0u);
-    CountRouteInputs ci;
-    ci.k = idx->k;
-    ci.m = m;
-    ci.n = idx->n;
-    ci.radius_finite = call.max_dist2 < INFINITY;
-    ci.flag_grid = (flags & KNN_QUERY_COUNT_GRID) != 0u;
-    ci.flag_cells = (flags & KNN_QUERY_COUNT_CELLS) != 0u;
-    ci.has_grid = ri.has_grid;
-    ci.has_cells = ri.t.has_cells;
-    ci.centred = ri.t.q.centred;
-    ci.rows_u8 = ri.t.q.rows_u8;
-    ci.bins = ri.t.bins;
-    ci.sharded = ri.t.sharded;
-    ci.path = ri.path;
-    ci.cells_option = ri.t.cells_option;
-    ci.num_cu = idx->num_cu;
-    ci.radius_rings = ci.has_grid && ci.radius_finite ? knn_grid_radius_rings(idx->grid, call.max_dist2) : 0;
-    const CountPlan plan = knn_count_route(ci);
+    const CountPlan plan = count_plan_of(idx, ri, m, call.max_dist2, flags);
     idx->stats[0] = (long long)plan.way;
     // the slot's count scratch, grown before the first launch
     knn_index::TopkSlot &ts = idx->topk[slot];
@@ -1398,6 +1404,115 @@ int knn_debug_count_plan(const long long in[16], long long out[8])
     const CountPlan p = knn_count_route(ci);
     const long long v[8] = {(long long)p.way, p.passes, p.pass_m, p.rmax, p.blocks, p.waves, p.slices, (long long)p.scratch_bytes};
     memcpy(out, v, sizeof v);
+    return KNN_OK;
+}
+
+int knn_counts_to_offsets(int device, const unsigned *counts_dev, int m, unsigned long long *offsets_dev, void *stream)
+{
+    if (m < 1)
+        return fail(KNN_EINVAL, "knn_counts_to_offsets: m < 1");
+    if (!counts_dev || !offsets_dev)
+        return fail(KNN_EINVAL, "knn_counts_to_offsets: null counts or offsets");
+    DeviceGuard guard(device);
+    if (!guard.ok)
+        return fail(KNN_EHIP, "knn_counts_to_offsets: hipSetDevice failed");
+    HIP_TRY(knn_counts_to_offsets_launch(counts_dev, m, (u64 *)offsets_dev, (hipStream_t)stream));
+    return KNN_OK;
+}
+
+int knn_keys_sort_segments(int device, int m, const unsigned long long *offsets_dev, const unsigned *fill_dev,
+                           unsigned long long *keys_dev, void *stream)
+{
+    if (m < 1)
+        return fail(KNN_EINVAL, "knn_keys_sort_segments: m < 1");
+    if (!offsets_dev || !fill_dev || !keys_dev)
+        return fail(KNN_EINVAL, "knn_keys_sort_segments: null offsets, fill or keys");
+    DeviceGuard guard(device);
+    if (!guard.ok)
+        return fail(KNN_EHIP, "knn_keys_sort_segments: hipSetDevice failed");
+    HIP_TRY(knn_keys_sort_segments_launch(m, (const u64 *)offsets_dev, fill_dev, (u64 *)keys_dev, (hipStream_t)stream));
+    return KNN_OK;
+}
+
+int knn_index_list_within(knn_index *idx, int slot, int m, const float *queries_dev, float max_dist2,
+                          const unsigned long long *offsets_dev, unsigned *fill_dev, unsigned long long *keys_dev, void *stream,
+                          unsigned flags)
+{
+    // (one message per rule, the index last, as knn_index_count_within: tests/test_list_logic.py tells them apart without a GPU)
+    if (!(max_dist2 >= 0.0f))
+        return fail(KNN_EINVAL, "knn_index_list_within: max_dist2 must be >= 0 and not NaN");
+    constexpr unsigned kListFlags = KNN_QUERY_INIT_KEYS | KNN_QUERY_COUNT_GRID | KNN_QUERY_COUNT_CELLS;   // the three it admits
+    if ((flags & ~kListFlags) != 0u)
+        return fail(KNN_EINVAL, "knn_index_list_within: unknown flag (KNN_QUERY_INIT_KEYS, KNN_QUERY_COUNT_GRID, KNN_QUERY_COUNT_CELLS)");
+    if (slot < 0 || slot >= KNN_SLOTS)
+        return fail(KNN_EINVAL, "knn_index_list_within: slot outside 0 .. 7");
+    if (m < 1)
+        return fail(KNN_EINVAL, "knn_index_list_within: m < 1");
+    if (!queries_dev || !offsets_dev || !fill_dev || !keys_dev)
+        return fail(KNN_EINVAL, "knn_index_list_within: null queries, offsets, fill or keys");
+    if (!idx)
+        return fail(KNN_EINVAL, "knn_index_list_within: null index");
+    std::lock_guard<std::recursive_mutex> lock(idx->mu);
+    DeviceGuard guard(idx->device);
+    if (!guard.ok)
+        return fail(KNN_EHIP, "knn_index_list_within: hipSetDevice failed");
+    ListCall call;
+    call.k = idx->k;
+    call.m = m;
+    call.n = idx->n;
+    call.base = idx->base;
+    // a cell-range shard's keys carry its rows' global numbers (gids); an index-range shard's base + row
+    call.gids = idx->sharded && idx->filter.cells ? idx->filter.cells->gids : nullptr;
+    call.q = queries_dev;
+    call.r = idx->refs;
+    call.offsets = (const u64 *)offsets_dev;
+    call.fill = fill_dev;
+    call.keys = (u64 *)keys_dev;
+    call.max_dist2 = max_dist2 == 0.0f ? 0.0f : max_dist2;   // (-0 counts as 0)
+    call.num_cu = idx->num_cu;
+    call.stream = (hipStream_t)stream;
+    hipStream_t s = call.stream;
+    idx->stats[0] = 1;
+    idx->stats[1] = 0;
+    idx->stats[2] = 0;
+    idx->stats[3] = 0;
+    idx->grid_topk_gate = nullptr;
+    idx->last_slot = slot;
+    // every way APPENDS behind the caller's fill: an init call zeroes it first
+    if ((flags & KNN_QUERY_INIT_KEYS) != 0u)
+        HIP_TRY(hipMemsetAsync(fill_dev, 0, (size_t)m * sizeof(unsigned), s));
+    if (idx->n == 0)   // an empty shard appends nothing
+        return KNN_OK;
+    const QueryRouteInputs ri = route_inputs(idx, m, 1, 0u);
+    const CountPlan plan = count_plan_of(idx, ri, m, call.max_dist2, flags);
+    idx->stats[0] = (long long)plan.way;
+    // the slot's count scratch — the scratch cursor of the grid and cell ways —, grown before the first launch
+    knn_index::TopkSlot &ts = idx->topk[slot];
+    KNN_TRY(slot_buffer_grow(ts.count, ts.count_bytes, plan.scratch_bytes));
+    call.scratch = (unsigned *)ts.count;
+    EventPair *ev = nullptr;
+    KNN_TRY(next_event_pair(idx, false, &ev));
+    call.ev0 = ev ? ev->first : nullptr;
+    call.ev1 = ev ? ev->second : nullptr;
+    switch (plan.way) {
+    case QueryWay::Grid:
+        HIP_TRY(knn_grid_query_list(idx->grid, plan.rmax, slot, call, &idx->grid_topk_gate));
+        break;
+    case QueryWay::Cells: {
+        const CellTopkPlan tp = knn_cells_count_plan(ri.t);
+        if (!tp.use)
+            return fail(KNN_EHIP, "knn_index_list_within: the cell-pruned scan has no pass shape for this layout");
+        HIP_TRY(knn_filter_query_list_cells(idx->filter, tp, slot, call));
+        break;
+    }
+    default:
+        if (ev)
+            HIP_TRY(hipEventRecord(call.ev0, s));
+        HIP_TRY(knn_exact_list_launch(call, nullptr));
+        if (ev)
+            HIP_TRY(hipEventRecord(call.ev1, s));
+        break;
+    }
     return KNN_OK;
 }
 
@@ -1916,6 +2031,84 @@ extern "C" int knn_index_count_within_host(knn_index *idx, int m, const float *q
     if (e != hipSuccess)
         return fail(KNN_EHIP, "knn_index_count_within_host: D2H counts", hipGetErrorString(e));
     // (not declared waited: the slot's buffers go back after the device-wide wait `stage` then makes itself, as the top-K host calls)
+    return KNN_OK;
+}
+
+extern "C" int knn_index_list_within_host(knn_index *idx, int m, const float *queries_host, float max_dist2, long long *offsets_host,
+                                          int **indices_out, float **dist2_out)
+{
+    if (!idx || m < 1 || !queries_host || !offsets_host || !indices_out || !(max_dist2 >= 0.0f))
+        return fail(KNN_EINVAL, "knn_index_list_within_host: bad arguments (m >= 1, max_dist2 >= 0 and not NaN)");
+    *indices_out = nullptr;
+    if (dist2_out)
+        *dist2_out = nullptr;
+    std::lock_guard<std::recursive_mutex> lock(idx->mu);
+    DeviceGuard guard(idx->device);
+    if (!guard.ok)
+        return fail(KNN_EHIP, "knn_index_list_within_host: hipSetDevice failed");
+    Staging stage(idx->device);
+    float *q_dev = nullptr;
+    unsigned *c_dev = nullptr, *fill_dev = nullptr;
+    u64 *off_dev = nullptr, *keys_dev = nullptr;
+    const size_t qbytes = (size_t)m * (size_t)idx->k * sizeof(float), cbytes = (size_t)m * sizeof(unsigned);
+    const size_t obytes = ((size_t)m + 1) * sizeof(u64);
+    hipError_t e = stage.get(&q_dev, qbytes);
+    if (e == hipSuccess)
+        e = stage.get(&c_dev, cbytes);
+    if (e == hipSuccess)
+        e = stage.get(&fill_dev, cbytes);
+    if (e == hipSuccess)
+        e = stage.get(&off_dev, obytes);
+    if (e == hipSuccess)
+        e = hipMemcpy(q_dev, queries_host, qbytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess)
+        return fail(KNN_EHIP, "knn_index_list_within_host: staging queries", hipGetErrorString(e));
+    // count -> offsets, then the one synchronisation: the total sizes the keys
+    int rc = knn_index_count_within(idx, 0, m, q_dev, max_dist2, c_dev, nullptr, KNN_QUERY_INIT_KEYS);
+    if (rc == KNN_OK)
+        rc = knn_counts_to_offsets(idx->device, c_dev, m, off_dev, nullptr);
+    if (rc != KNN_OK)
+        return rc;
+    std::vector<u64> offs((size_t)m + 1);
+    e = hipMemcpy(offs.data(), off_dev, obytes, hipMemcpyDeviceToHost);
+    if (e != hipSuccess)
+        return fail(KNN_EHIP, "knn_index_list_within_host: D2H offsets", hipGetErrorString(e));
+    const u64 total = offs[(size_t)m];
+    std::vector<u64> keys((size_t)total);
+    if (total) {   // list -> sort
+        e = stage.get(&keys_dev, (size_t)total * sizeof(u64));
+        if (e != hipSuccess)
+            return fail(KNN_EHIP, "knn_index_list_within_host: staging keys", hipGetErrorString(e));
+        rc = knn_index_list_within(idx, 0, m, q_dev, max_dist2, off_dev, fill_dev, keys_dev, nullptr, KNN_QUERY_INIT_KEYS);
+        if (rc == KNN_OK)
+            rc = knn_keys_sort_segments(idx->device, m, off_dev, fill_dev, keys_dev, nullptr);
+        if (rc != KNN_OK)
+            return rc;
+        e = hipMemcpy(keys.data(), keys_dev, (size_t)total * sizeof(u64), hipMemcpyDeviceToHost);
+        if (e != hipSuccess)
+            return fail(KNN_EHIP, "knn_index_list_within_host: D2H keys", hipGetErrorString(e));
+    }
+    const size_t room = total ? (size_t)total : 1u;
+    int *ind = (int *)malloc(room * sizeof(int));
+    float *d2 = dist2_out ? (float *)malloc(room * sizeof(float)) : nullptr;
+    if (!ind || (dist2_out && !d2)) {
+        free(ind);
+        free(d2);
+        return fail(KNN_EHIP, "knn_index_list_within_host: out of host memory");
+    }
+    for (size_t i = 0; i < (size_t)total; ++i) {
+        ind[i] = (int)(unsigned)(keys[i] & 0xFFFFFFFFull);
+        if (d2) {
+            const unsigned hi = (unsigned)(keys[i] >> 32);
+            memcpy(&d2[i], &hi, sizeof hi);
+        }
+    }
+    for (int j = 0; j <= m; ++j)
+        offsets_host[j] = (long long)offs[(size_t)j];
+    *indices_out = ind;
+    if (dist2_out)
+        *dist2_out = d2;
+    // (not declared waited: the slot's buffers go back after the device-wide wait `stage` then makes itself, as the other host calls)
     return KNN_OK;
 }
 

@@ -3157,6 +3157,27 @@ hipError_t knn_cells_query_count(FilterState &st, FilterWorkspace &w, const Cell
     return knn_exact_count_launch(call, w.ctl_cur + KNN_CTL_FALLBACK);
 }
 
+// One pass of <= KNN_CELL_BATCH queries of a list call (knn_index_list_within with KNN_QUERY_COUNT_CELLS; DESIGN §4.6 "Lists within
+// a radius"): the count pass unchanged up to its finish — count prep -> match -> record-only scan —, then the list re-rank of the
+// slices and of the shared overflow area -> out-of-box rows, all reserving in call.scratch (on entry a copy of call.fill) and
+// storing behind it -> commit, gated on no FALLBACK -> the exact list, gated on FALLBACK, from the untouched call.fill.
+hipError_t knn_cells_query_list(FilterState &st, FilterWorkspace &w, const CellTopkPlan &tp, bool timed, const ListCall &call)
+{
+    const CellIndex &c = *st.cells;
+    const CellQueryPlan &p = tp.batch;
+    const int m = call.m;
+    if (!tp.use || m > tp.pass_m || tp.scan.self || tp.scan.ctr || c.centred || p.prep_ctr || !(call.max_dist2 < INFINITY) || !call.scratch ||
+        call.gids != c.gids || (c.geom && (!c.gids || call.base != 0)))
+        return hipErrorInvalidValue;
+    // (the empty seed layer: the lists of a cell-range shard are its own rows' and simply append across ranks)
+    const SeedLayer no_layer = {nullptr, 0u, 0u, 0u, 0ull, {0u}};
+    CellBatch b{st, c, w, p, m, call.q, call.r, 0ll, nullptr, nullptr, CellFinal{nullptr, nullptr, 0}, no_layer, call.stream, 1, call.max_dist2};
+    FTRY(cells_pass_front(w, b, cells_records_kernel(tp.scan), CellPrepForm::Count, timed));
+    FTRY(knn_list_records_finish(call, cells_pass_records(st, w)));
+    // gated: the exact list answers a pass that raised FALLBACK (its scratch cursor was not committed)
+    return knn_exact_list_launch(call, w.ctl_cur + KNN_CTL_FALLBACK);
+}
+
 // Test hook (host arithmetic, no GPU): knn_threshold's Dup for a seed score u — out = {thr, Dup as the prep kernel stores it (fp32,
 // rounded up), knn_topk_gate of that Dup: the largest v0 distance a top-K row can have}.
 extern "C" int knn_debug_topk_gate(int k, float sigma, double amax, double bmax, double nmax, double u, double mq, double out[3])

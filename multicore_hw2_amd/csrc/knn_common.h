@@ -186,6 +186,52 @@ hipError_t knn_count_commit_launch(int m, const unsigned *scratch, unsigned *cou
 // list of one; rs.perm and rs.pos_norms set, rs.gate_dup unused) and every out-of-box row with v0's arithmetic -> qcount[j] (the
 // pass's scratch, zero on entry), then the commit, gated on no FALLBACK.  An over-full record area raises FALLBACK.
 hipError_t knn_count_records_finish(const CountCall &c, const TopkRecords &rs, unsigned *qcount);
+
+// ---- lists within a radius (knn_index_list_within; DESIGN §4.6 "Lists within a radius") -----------------------------------------
+// One list call as every way that answers it takes it: the count call's fields, where the hits go and the number a key carries.
+// knn_index_list_within (knn_api.cpp) fills it once.
+struct ListCall {
+    int k = 0, m = 0;
+    long long n = 0, base = 0;     // the shard's rows; global number of row 0 ...
+    const unsigned *gids = nullptr;   // ... or, cell-range shards (base 0), of every row; null: base + row
+    const float *q = nullptr, *r = nullptr;   // device [m][k], [n][k]
+    const u64 *offsets = nullptr;  // device [m + 1], the caller's: segment j of keys is [offsets[j], offsets[j + 1])
+    unsigned *fill = nullptr;      // device [m], the caller's cursor: every way ADDS this shard's hits (an init call zeroes it first)
+    u64 *keys = nullptr;           // device, the caller's: a hit that reserved place p < room is stored at keys[offsets[j] + p]
+    float max_dist2 = INFINITY;    // the radius, squared (>= 0, never -0; +INF: every row with a finite distance)
+    int num_cu = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;   // nullable: bracket the way's dominant kernel
+    unsigned *scratch = nullptr;   // the slot's count scratch [m]: the scratch cursor of the grid and cell ways (the exact way does not use it)
+
+    // queries [q0, q0 + mb) of the call: a pass of the cell-pruned way (offsets are absolute: keys stays)
+    ListCall pass(int q0, int mb) const
+    {
+        ListCall c = *this;
+        c.m = mb;
+        c.q = q + (size_t)q0 * k;
+        c.offsets = offsets + q0;
+        c.fill = fill + q0;
+        c.scratch = scratch + q0;
+        return c;
+    }
+};
+// Every row of the shard with a finite v0 distance E <= c.max_dist2 reserves p = c.fill[j]++ and, when p is below the segment's
+// room, stores its key at c.keys[c.offsets[j] + p].  Slices and chunks of queries as knn_exact_count_launch.  gate != nullptr: the
+// launches do nothing unless *gate != 0.
+hipError_t knn_exact_list_launch(const ListCall &c, const unsigned *gate);
+// fill[j] = cursor[j] for j < m unless *giveup != 0: the commit of the grid way and of a cell-pruned pass, the opposite gate of the
+// exact list behind it.
+hipError_t knn_list_commit_launch(int m, const unsigned *cursor, unsigned *fill, const unsigned *giveup, hipStream_t stream);
+// A cell-pruned list pass behind its record-only scan (knn_count_records_finish's walk): every hit reserves its place in c.scratch
+// — on entry a copy of c.fill — and stores its key behind it; then the commit, gated on no FALLBACK.
+hipError_t knn_list_records_finish(const ListCall &c, const TopkRecords &rs);
+// offsets[0] = 0, offsets[j + 1] = offsets[j] + counts[j]: one block, a 64-bit running sum over chunks of the counts.
+hipError_t knn_counts_to_offsets_launch(const unsigned *counts, int m, u64 *offsets, hipStream_t stream);
+// The first min(fill[j], room of segment j) keys of every segment ascending: one block per segment, a bitonic network in LDS up to
+// KNN_SORT_LDS_KEYS keys and in global memory beyond.
+#define KNN_SORT_LDS_KEYS 4096
+hipError_t knn_keys_sort_segments_launch(int m, const u64 *offsets, const unsigned *fill, u64 *keys, hipStream_t stream);
 // ---- MFMA filter + exact re-rank (knn_filter.hip) ---------------------------
 // Device-side control words of one filter query (FilterState::ctl).
 enum {
@@ -666,6 +712,10 @@ hipError_t knn_cells_query_topk(FilterState &st, FilterWorkspace &w, const CellT
 // (the radius cap alone) -> match -> record-only scan -> count re-rank -> out-of-box rows -> commit (no FALLBACK) -> the exact
 // count, gated on FALLBACK.  tp: knn_cells_count_plan's pass shapes.
 hipError_t knn_cells_query_count(FilterState &st, FilterWorkspace &w, const CellTopkPlan &tp, bool timed, const CountCall &c);
+// One pass of a list call (c: ListCall::pass): the count pass up to its finish, then the list re-rank and out-of-box rows (they
+// reserve in c.scratch, a copy of c.fill, and store behind it) -> commit (no FALLBACK) -> the exact list, gated on FALLBACK, from
+// the untouched c.fill over the same places.
+hipError_t knn_cells_query_list(FilterState &st, FilterWorkspace &w, const CellTopkPlan &tp, bool timed, const ListCall &c);
 
 // Builds the filter layouts for refs[0..n) (device, AoS).  Synchronous.  Leaves st.usable false
 // (and returns hipSuccess) when the data rules the filter out.
@@ -706,6 +756,10 @@ hipError_t knn_grid_query_topk(const GridState *gs, const GridTopkPlan &plan, in
 // Counts on the grid index (KNN_QUERY_COUNT_GRID; knn_grid_count_kernel): c.scratch [m] receives the kernel's counts, the commit
 // (no give-up) or the gated exact count (give-up) adds the batch to c.counts.  rmax: CountPlan::rmax.
 hipError_t knn_grid_query_count(const GridState *gs, int rmax, int slot, const CountCall &c, const unsigned **gate_out);
+// Lists on the grid index (KNN_QUERY_COUNT_GRID; knn_grid_list_kernel): c.scratch [m] starts as a copy of c.fill, the walk reserves
+// in it and stores the keys behind it; the commit (no give-up) copies it to c.fill, or the gated exact list (give-up) answers the
+// batch from the untouched c.fill over the same places.
+hipError_t knn_grid_query_list(const GridState *gs, int rmax, int slot, const ListCall &c, const unsigned **gate_out);
 void knn_grid_info(const GridState *gs, long long info[4]);
 
 // ---- RCCL exchange step (knn_rccl.cpp; librccl is dlopen'ed at first use) -------------------
@@ -760,6 +814,8 @@ hipError_t knn_filter_query_topk_cells(FilterState &st, const CellTopkPlan &tp, 
 // Counts on the cell-pruned scan (KNN_QUERY_COUNT_CELLS), the whole call in passes of KNN_CELL_BATCH queries (knn_cells_query_count).
 // c.scratch [c.m] is zeroed here, once per call.
 hipError_t knn_filter_query_count_cells(FilterState &st, const CellTopkPlan &tp, int slot, const CountCall &c);
+// Lists on the cell-pruned scan (KNN_QUERY_COUNT_CELLS), the whole call in passes of KNN_CELL_BATCH queries (knn_cells_query_list).
+hipError_t knn_filter_query_list_cells(FilterState &st, const CellTopkPlan &tp, int slot, const ListCall &c);
 // Test hook: raw filter scores S[m][n] (row-major) and the per-query thresholds for a query
 // batch, plus {sigma, eta, rho, amax, bmax}.  Synchronous.
 hipError_t knn_filter_debug(FilterState &st, int m, const float *q_dev, const float *r_dev,

@@ -1612,3 +1612,353 @@ hipError_t knn_count_records_finish(const CountCall &c, const TopkRecords &rs, u
     }
     return knn_count_commit_launch(c.m, qcount, c.counts, rs.ctl + KNN_CTL_FALLBACK, s);
 }
+
+// ------------------------------------------------------------------------------------------
+// Lists within a radius (knn_index_list_within; DESIGN §4.6 "Lists within a radius"): the second pass of count -> offsets -> fill.
+//
+// A hit — a row whose v0 distance E is finite and E <= max_dist2, knn_exact_count_kernel's rule — reserves place p of its query's
+// segment with one atomicAdd on the query's cursor and, when p is below the segment's room, stores its packed key at
+// keys[offsets[q] + p]: one 8-byte vector store.  The cursor counts every hit, stored or not, so a cursor above the room is how the
+// caller sees an overflow; nothing is stored outside [offsets[q], offsets[q + 1]).
+// ------------------------------------------------------------------------------------------
+// The room of segment q: offsets[q + 1] - offsets[q], capped at 2^32 - 1 (the cursor is 32-bit); descending offsets: none.
+__device__ __forceinline__ unsigned list_room(const u64 *__restrict__ offsets, unsigned q, u64 &off)
+{
+    off = offsets[q];
+    const u64 end = offsets[q + 1];
+    const u64 room = end > off ? end - off : 0ull;
+    return room < 0xFFFFFFFFull ? (unsigned)room : 0xFFFFFFFFu;
+}
+
+__device__ __forceinline__ void list_put(unsigned *__restrict__ cursor, u64 *__restrict__ keys, u64 off, unsigned room, u64 key)
+{
+    const unsigned p = atomicAdd(cursor, 1u);
+    if (p < room)
+        keys[off + p] = key;
+}
+
+// knn_exact_list_kernel<KC> — knn_exact_count_kernel's skeleton: one wave per block, lanes = queries (coordinates in VGPRs), rows
+// of the block's slice as wave-uniform scalar loads, v0's arithmetic; KC and gate as there.  On a hit the lane reserves and stores
+// (list_put) instead of adding to a register: hits are sparse at the radii the call is meant for, so no staging in LDS.
+// gids (nullable; cell-range shards, where base is 0): the key's index half is gids[row], else base + row.
+template <int KC>
+__global__ __launch_bounds__(KNN_WAVE) void knn_exact_list_kernel(const float *__restrict__ Q, const float *__restrict__ R, int k,
+                                                                 int m, long long n, long long rows_per_slice, float max_dist2,
+                                                                 long long base, const unsigned *__restrict__ gids,
+                                                                 const u64 *__restrict__ offsets, unsigned *__restrict__ fill,
+                                                                 u64 *__restrict__ keys, const unsigned *__restrict__ gate)
+{
+#pragma clang fp contract(off)
+    if (gate && *gate == 0u)
+        return;
+    constexpr int KM = KC > 0 ? 16 * KC : 1;
+    const int lane = threadIdx.x;
+    const int q = blockIdx.y * KNN_WAVE + lane;
+    const int qa = min(q, m - 1);
+    float qv[KM];
+#pragma unroll
+    for (int d = 0; d < KM; ++d)
+        qv[d] = KC > 0 && d < k ? Q[(size_t)qa * k + d] : 0.0f;
+    u64 off;
+    const unsigned room = list_room(offsets, (unsigned)qa, off);
+    const long long i0 = (long long)blockIdx.x * rows_per_slice;
+    const long long i1 = min(n, i0 + rows_per_slice);
+    const float *__restrict__ r = R + (size_t)i0 * k;
+    const float *__restrict__ qp = Q + (size_t)qa * k;
+    for (long long i = i0; i < i1; ++i, r += k) {
+        float acc = 0.0f;
+        if (KC > 0) {
+#pragma unroll
+            for (int c = 0; c < (KC > 0 ? KC : 1); ++c) {
+                const int rem = k - 16 * c;   // wave-uniform
+                if (rem >= 16) {
+                    float rv[16];
+#pragma unroll
+                    for (int j = 0; j < 16; ++j)
+                        rv[j] = r[16 * c + j];   // wave-uniform address -> scalar loads
+#pragma unroll
+                    for (int j = 0; j < 16; ++j) {
+                        const float diff = qv[16 * c + j] - rv[j];
+                        const float sq = diff * diff;
+                        acc = acc + sq;
+                    }
+                } else if (rem > 0) {
+#pragma unroll
+                    for (int j = 0; j < 15; ++j)
+                        if (j < rem) {
+                            const float diff = qv[16 * c + j] - r[16 * c + j];
+                            const float sq = diff * diff;
+                            acc = acc + sq;
+                        }
+                }
+            }
+        } else {
+            for (int d = 0; d < k; ++d) {
+                const float diff = qp[d] - r[d];
+                const float sq = diff * diff;
+                acc = acc + sq;
+            }
+        }
+        if (q < m && acc < INFINITY && acc <= max_dist2)   // (NaN fails both compares)
+            list_put(&fill[q], keys, off, room, pack_key(acc, gids ? gids[i] : (unsigned)(base + i)));
+    }
+}
+
+// fill[j] = cursor[j] unless *giveup != 0: the places the grid way or a cell-pruned pass reserved in the scratch cursor become the
+// caller's only when nothing handed the batch to the exact list, which runs under the opposite gate from the untouched fill over
+// the same places — one of the two moves the caller's cursor, never both.
+__global__ __launch_bounds__(KNN_BLOCK) void knn_list_commit_kernel(const unsigned *__restrict__ cursor, int m,
+                                                                   unsigned *__restrict__ fill, const unsigned *__restrict__ giveup)
+{
+    if (*giveup != 0u)
+        return;
+    const int j = blockIdx.x * KNN_BLOCK + threadIdx.x;
+    if (j < m)
+        fill[j] = cursor[j];
+}
+
+// The cell-pruned list's re-rank: knn_count_rerank_kernel's walk (one block per list, positions whose layout norm is +INF skipped),
+// and a row within the radius reserves in its query's scratch cursor and stores its key.  base / gids as in the exact list.
+__global__ __launch_bounds__(KNN_BLOCK) void knn_list_rerank_kernel(const float *__restrict__ Q, const float *__restrict__ R, int k,
+                                                                   long long n, long long base, const u64 *__restrict__ rec,
+                                                                   const unsigned *__restrict__ counts, unsigned nlists,
+                                                                   unsigned slice, unsigned *__restrict__ ctl,
+                                                                   const unsigned *__restrict__ perm, const float *__restrict__ norms,
+                                                                   float max_dist2, const unsigned *__restrict__ gids,
+                                                                   const u64 *__restrict__ offsets, unsigned *__restrict__ cursor,
+                                                                   u64 *__restrict__ keys)
+{
+    const unsigned list_id = blockIdx.x;
+    if (ctl[KNN_CTL_FALLBACK] != 0u || list_id >= nlists)
+        return;
+    const unsigned want = counts[list_id];
+    const unsigned nrec = min(want, slice);
+    if (threadIdx.x == 0 && want > slice)
+        ctl[KNN_CTL_FALLBACK] = 1u;
+    const u64 *__restrict__ list = rec + (size_t)list_id * slice;
+    for (unsigned c = threadIdx.x; c < nrec * 16u; c += KNN_BLOCK) {
+        unsigned qi = 0u;
+        const u64 e = list[c >> 4];
+        const unsigned lo = (unsigned)e, reg = c & 15u;
+        const long long pos = (long long)(lo >> 1) * 32 + 8 * (reg >> 2) + 4 * (lo & 1u) + (reg & 3u);   // (rerank_pair's)
+        const unsigned rmask = pos < n && norms[pos] < INFINITY ? 0xFFFFu : 0u;
+        const u64 key = rerank_pair<0>(Q, R, k, n, base, e, reg, rmask, 0u, perm, qi);   // ~0: nothing there, or not finite
+        if (key != ~0ull && __uint_as_float((unsigned)(key >> 32)) <= max_dist2) {
+            u64 off;
+            const unsigned room = list_room(offsets, qi, off);
+            list_put(&cursor[qi], keys, off, room, gids ? (key & 0xFFFFFFFF00000000ull) | (u64)gids[(unsigned)key] : key);
+        }
+    }
+}
+
+// Rows outside the filter's robust box never enter the scan: every (query, listed row) pair once, with v0's arithmetic.
+// grid (row blocks, queries).
+__global__ __launch_bounds__(KNN_BLOCK) void knn_list_outlier_kernel(const float *__restrict__ Q, const float *__restrict__ R, int k,
+                                                                    unsigned count, long long base, const unsigned *__restrict__ list,
+                                                                    const unsigned *__restrict__ ctl, float max_dist2,
+                                                                    const unsigned *__restrict__ gids, const u64 *__restrict__ offsets,
+                                                                    unsigned *__restrict__ cursor, u64 *__restrict__ keys)
+{
+#pragma clang fp contract(off)
+    if (ctl[KNN_CTL_FALLBACK] != 0u)
+        return;
+    const unsigned q = blockIdx.y;
+    const float *__restrict__ qp = Q + (size_t)q * k;
+    u64 off;
+    const unsigned room = list_room(offsets, q, off);
+    for (unsigned j = blockIdx.x * KNN_BLOCK + threadIdx.x; j < count; j += gridDim.x * KNN_BLOCK) {
+        const unsigned row = list[j];
+        const float *__restrict__ r = R + (size_t)row * k;
+        float acc = 0.0f;
+        for (int d = 0; d < k; ++d) {
+            const float diff = qp[d] - r[d];
+            const float sq = diff * diff;
+            acc = acc + sq;
+        }
+        if (acc < INFINITY && acc <= max_dist2)
+            list_put(&cursor[q], keys, off, room, pack_key(acc, gids ? gids[row] : (unsigned)(base + (long long)row)));
+    }
+}
+
+// offsets[0] = 0, offsets[j + 1] = offsets[j] + counts[j]: ONE block walks the counts in chunks of 8 per thread and carries a 64-bit
+// running sum from chunk to chunk (m is small next to n: no multi-block scan).  Per chunk: a thread sums its 8 counts, the waves
+// scan the thread sums by shuffles, the wave totals meet in LDS.
+#define KNN_OFFSETS_PER_THREAD 8
+__global__ __launch_bounds__(KNN_BLOCK) void knn_counts_to_offsets_kernel(const unsigned *__restrict__ counts, int m,
+                                                                         u64 *__restrict__ offsets)
+{
+    __shared__ u64 wave_total[KNN_WAVES];
+    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    u64 running = 0ull;
+    if (threadIdx.x == 0)
+        offsets[0] = 0ull;
+    for (long long c0 = 0; c0 < m; c0 += (long long)KNN_BLOCK * KNN_OFFSETS_PER_THREAD) {
+        const long long j0 = c0 + (long long)threadIdx.x * KNN_OFFSETS_PER_THREAD;
+        unsigned v[KNN_OFFSETS_PER_THREAD];
+        u64 mine = 0ull;
+#pragma unroll
+        for (int t = 0; t < KNN_OFFSETS_PER_THREAD; ++t) {
+            v[t] = j0 + t < m ? counts[j0 + t] : 0u;
+            mine += v[t];
+        }
+        u64 incl = mine;   // inclusive scan of the thread sums within the wave
+#pragma unroll
+        for (int d = 1; d < KNN_WAVE; d <<= 1) {
+            const u64 o = __shfl_up(incl, d, KNN_WAVE);
+            if (lane >= (unsigned)d)
+                incl += o;
+        }
+        if (lane == KNN_WAVE - 1)
+            wave_total[wave] = incl;
+        __syncthreads();
+        u64 before = running, total = 0ull;
+#pragma unroll
+        for (unsigned w = 0; w < KNN_WAVES; ++w) {
+            before += w < wave ? wave_total[w] : 0ull;
+            total += wave_total[w];
+        }
+        u64 sum = before + incl - mine;   // everything ahead of this thread's first count
+#pragma unroll
+        for (int t = 0; t < KNN_OFFSETS_PER_THREAD; ++t) {
+            sum += v[t];
+            if (j0 + t < m)
+                offsets[j0 + t + 1] = sum;
+        }
+        running += total;
+        __syncthreads();   // (wave_total is rewritten by the next chunk)
+    }
+}
+
+// One block per segment: the first cnt = min(fill, room) keys ascending, by a bitonic network whose comparators all put the smaller
+// key at the lower place (a merge of 2h keys opens with the mirror step i <-> i ^ (2h - 1), then halves as usual).  With every
+// comparator pointing the same way the places from cnt up to the next power of two behave as +INF padding that never moves, so a
+// comparator whose upper place is >= cnt is simply skipped: any length sorts, nothing beyond cnt is read or written.  Equal keys are
+// never exchanged.  cnt <= KNN_SORT_LDS_KEYS: in LDS (32 KB); beyond: the same network on the segment in global memory, the block's
+// barriers ordering its own stores and loads.
+__device__ __forceinline__ void sort_network(u64 *a, unsigned cnt)
+{
+    unsigned P = 1u;
+    while (P < cnt)
+        P <<= 1;
+    for (unsigned h = 1u; h < P; h <<= 1) {          // merge runs of h into runs of 2h
+        for (unsigned j = h; j >= 1u; j >>= 1) {
+            for (unsigned t = threadIdx.x; t < P / 2u; t += KNN_BLOCK) {
+                const unsigned i = (t / j) * 2u * j + (t % j);
+                const unsigned l = j == h ? (i | (2u * h - 1u)) - (i & (h - 1u)) : i + j;   // mirror within the run of 2h, or i + j
+                if (l < cnt) {
+                    const u64 x = a[i], y = a[l];
+                    if (x > y) {
+                        a[i] = y;
+                        a[l] = x;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+__global__ __launch_bounds__(KNN_BLOCK) void knn_keys_sort_segments_kernel(const u64 *__restrict__ offsets,
+                                                                          const unsigned *__restrict__ fill, u64 *keys)
+{
+    __shared__ u64 lds[KNN_SORT_LDS_KEYS];
+    const unsigned seg = blockIdx.x;
+    u64 off;
+    const unsigned room = list_room(offsets, seg, off);
+    const unsigned cnt = min(fill[seg], room);   // block-uniform
+    if (cnt < 2u)
+        return;
+    u64 *a = keys + off;
+    if (cnt <= KNN_SORT_LDS_KEYS) {
+        for (unsigned i = threadIdx.x; i < cnt; i += KNN_BLOCK)
+            lds[i] = a[i];
+        __syncthreads();
+        sort_network(lds, cnt);
+        for (unsigned i = threadIdx.x; i < cnt; i += KNN_BLOCK)
+            a[i] = lds[i];
+    } else {
+        sort_network(a, cnt);
+    }
+}
+
+hipError_t knn_exact_list_launch(const ListCall &c, const unsigned *gate)
+{
+    if (c.m <= 0 || c.n <= 0)
+        return hipSuccess;
+    hipStream_t s = c.stream;
+    for (int c0 = 0; c0 < c.m; c0 += KNN_TOPK_CHUNK) {
+        const int mc = c.m - c0 < KNN_TOPK_CHUNK ? c.m - c0 : KNN_TOPK_CHUNK;
+        const long long slices = knn_count_slices(mc, c.n, c.num_cu);
+        const long long per = (c.n + slices - 1) / slices;
+        const dim3 grid((unsigned)slices, (unsigned)knn_divup(mc, KNN_WAVE)), block(KNN_WAVE);
+        const float *qc = c.q + (size_t)c0 * c.k;
+#define KNN_LIST_SCAN(KCV)                                                                                                        \
+    hipLaunchKernelGGL(knn_exact_list_kernel<KCV>, grid, block, 0, s, qc, c.r, c.k, mc, c.n, per, c.max_dist2, c.base, c.gids, \
+                       c.offsets + c0, c.fill + c0, c.keys, gate)
+        switch ((c.k + 15) / 16) {
+        case 1: KNN_LIST_SCAN(1); break;
+        case 2: KNN_LIST_SCAN(2); break;
+        case 3: KNN_LIST_SCAN(3); break;
+        case 4: KNN_LIST_SCAN(4); break;
+        case 5: KNN_LIST_SCAN(5); break;
+        case 6: KNN_LIST_SCAN(6); break;
+        case 7: KNN_LIST_SCAN(7); break;
+        case 8: KNN_LIST_SCAN(8); break;
+        default: KNN_LIST_SCAN(0); break;
+        }
+#undef KNN_LIST_SCAN
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess)
+            return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t knn_list_commit_launch(int m, const unsigned *cursor, unsigned *fill, const unsigned *giveup, hipStream_t s)
+{
+    if (m <= 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(knn_list_commit_kernel, dim3((unsigned)knn_divup(m, KNN_BLOCK)), dim3(KNN_BLOCK), 0, s, cursor, m, fill, giveup);
+    return hipGetLastError();
+}
+
+hipError_t knn_list_records_finish(const ListCall &c, const TopkRecords &rs)
+{
+    hipStream_t s = c.stream;
+    if (rs.rec_rows || !rs.perm || !rs.pos_norms || !c.scratch)
+        return hipErrorInvalidValue;
+    if (rs.nlists)
+        hipLaunchKernelGGL(knn_list_rerank_kernel, dim3(rs.nlists), dim3(KNN_BLOCK), 0, s, c.q, c.r, c.k, rs.positions, c.base, rs.rec,
+                           rs.counts, rs.nlists, rs.slice, rs.ctl, rs.perm, rs.pos_norms, c.max_dist2, c.gids, c.offsets, c.scratch, c.keys);
+    if (rs.ovf_rec && rs.ovf_count)   // the shared overflow area as a list of one (its `want > slice` rule raises FALLBACK when over-full)
+        hipLaunchKernelGGL(knn_list_rerank_kernel, dim3(1), dim3(KNN_BLOCK), 0, s, c.q, c.r, c.k, rs.positions, c.base, rs.ovf_rec,
+                           rs.ovf_count, 1u, rs.ovf_slice, rs.ctl, rs.perm, rs.pos_norms, c.max_dist2, c.gids, c.offsets, c.scratch, c.keys);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess)
+        return e;
+    if (rs.n_outliers) {
+        const unsigned gx = (rs.n_outliers + KNN_BLOCK - 1) / KNN_BLOCK < 64u ? (rs.n_outliers + KNN_BLOCK - 1) / KNN_BLOCK : 64u;
+        hipLaunchKernelGGL(knn_list_outlier_kernel, dim3(gx, (unsigned)c.m), dim3(KNN_BLOCK), 0, s, c.q, c.r, c.k, rs.n_outliers, c.base,
+                           rs.outliers, (const unsigned *)rs.ctl, c.max_dist2, c.gids, c.offsets, c.scratch, c.keys);
+        e = hipGetLastError();
+        if (e != hipSuccess)
+            return e;
+    }
+    return knn_list_commit_launch(c.m, c.scratch, c.fill, rs.ctl + KNN_CTL_FALLBACK, s);
+}
+
+hipError_t knn_counts_to_offsets_launch(const unsigned *counts, int m, u64 *offsets, hipStream_t s)
+{
+    if (m <= 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(knn_counts_to_offsets_kernel, dim3(1), dim3(KNN_BLOCK), 0, s, counts, m, offsets);
+    return hipGetLastError();
+}
+
+hipError_t knn_keys_sort_segments_launch(int m, const u64 *offsets, const unsigned *fill, u64 *keys, hipStream_t s)
+{
+    if (m <= 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(knn_keys_sort_segments_kernel, dim3((unsigned)m), dim3(KNN_BLOCK), 0, s, offsets, fill, keys);
+    return hipGetLastError();
+}

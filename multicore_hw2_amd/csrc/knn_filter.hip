@@ -2719,6 +2719,16 @@ hipError_t knn_filter_query_count_cells(FilterState &st, const CellTopkPlan &tp,
     return cell_passes(st, w, c.ev0, c.ev1, c.m, [&](int q0, int mb, bool first) { return knn_cells_query_count(st, w, tp, first, c.pass(q0, mb)); });
 }
 
+hipError_t knn_filter_query_list_cells(FilterState &st, const CellTopkPlan &tp, int slot, const ListCall &c)
+{
+    if (!st.cells || !tp.use || !c.scratch)
+        return hipErrorInvalidValue;
+    FilterWorkspace &w = st.ws[slot];
+    // the scratch cursor starts where the caller's fill stands (every pass moves its part)
+    FTRY(hipMemcpyAsync(c.scratch, c.fill, (size_t)c.m * sizeof(unsigned), hipMemcpyDeviceToDevice, c.stream));
+    return cell_passes(st, w, c.ev0, c.ev1, c.m, [&](int q0, int mb, bool first) { return knn_cells_query_list(st, w, tp, first, c.pass(q0, mb)); });
+}
+
 // knn_filter_debug's scores: knn_filter_scores_kernel<KT>, KT = 0: knn_filter_scores_rt_kernel (run-time kt, k > 512).
 template <int KT>
 static void filter_scores_as(const FilterState &st, const FilterWorkspace &w, int m, float *scores, hipStream_t s)

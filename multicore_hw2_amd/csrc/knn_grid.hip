@@ -520,6 +520,93 @@ __global__ __launch_bounds__(GRID_BLOCK) void knn_grid_count_kernel(const float 
     }
 }
 
+// ---- lists within a radius (KNN_QUERY_COUNT_GRID; knn_index_list_within) --------------------------
+// knn_grid_count_kernel's walk and stop rules; a row within the radius reserves place p of its query's segment with one atomicAdd on
+// cursor[q] and, when p is below the segment's room, stores its key — the distance's bits and base + orig[position] — at
+// keys[offsets[q] + p].  cursor is the slot's scratch, on entry a copy of the caller's fill, never the caller's fill itself: a batch
+// that gives up is answered again by the exact list behind this kernel from the untouched fill, over the same places, and
+// knn_list_commit_kernel copies the cursor to fill only when nobody gave up.  Every cell of rings 0..r is visited once and every
+// row sits in one cell: no row is listed twice.  A query with a non-finite coordinate has no hit: its cursor stays where it was.
+template <int KD>
+__global__ __launch_bounds__(GRID_BLOCK) void knn_grid_list_kernel(const float *__restrict__ Q, int m, GridGeom gg,
+                                                                   const unsigned *__restrict__ start,
+                                                                   const f4g *__restrict__ pts, const unsigned *__restrict__ orig,
+                                                                   long long base, const u64 *__restrict__ offsets,
+                                                                   unsigned *__restrict__ cursor, u64 *__restrict__ keys, int rmax,
+                                                                   unsigned *__restrict__ giveup,
+                                                                   unsigned *__restrict__ giveup_next, float max_dist2)
+{
+#pragma clang fp contract(off)
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        *giveup_next = 0u;   // (the slot's other word, as the 1-NN kernel)
+    const int lane = threadIdx.x & 63;
+    const int qi = blockIdx.x * (GRID_BLOCK / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (qi >= m)
+        return;
+    float q[4] = {0.f, 0.f, 0.f, 0.f};
+    bool finite = true;
+#pragma unroll
+    for (int d = 0; d < KD; ++d) {
+        q[d] = Q[(size_t)qi * KD + d];
+        finite = finite && fabsf(q[d]) < INFINITY;
+    }
+    if (!finite)   // every distance is NaN or +INF: no row is a hit (and nothing to give up on)
+        return;
+    int c[4];
+    (void)grid_cell_of(gg, q, c);
+    int gmax = 1;
+#pragma unroll
+    for (int d = 0; d < KD; ++d)
+        gmax = gg.g[d] > gmax ? gg.g[d] : gmax;
+    const u64 off = offsets[qi], end = offsets[qi + 1];
+    const u64 room64 = end > off ? end - off : 0ull;
+    const unsigned room = room64 < 0xFFFFFFFFull ? (unsigned)room64 : 0xFFFFFFFFu;   // (the cursor is 32-bit)
+
+    bool done = false;
+    bool first = true;   // (rings 0 and 1 together, as the 1-NN kernel)
+    for (int r = gmax > 1 ? 1 : 0; r < gmax && r <= rmax; ++r) {
+        const int side = 2 * r + 1;
+        int total = 1;
+#pragma unroll
+        for (int d = 0; d < KD; ++d)
+            total *= side;
+        for (int idx = lane; idx < total; idx += KNN_WAVE) {
+            unsigned cell;
+            if (!grid_ring_cell<KD>(gg, c, r, side, idx, first, &cell))
+                continue;
+            const unsigned p0 = start[cell], p1 = start[cell + 1];
+            for (unsigned p = p0; p < p1; ++p) {
+                const f4g x = pts[p];
+                float acc = 0.0f;
+#pragma unroll
+                for (int d = 0; d < KD; ++d) {
+                    const float diff = q[d] - x[d];   // v0: search - reference, squared, summed in order
+                    const float sq = diff * diff;
+                    acc = acc + sq;
+                }
+                if (acc < INFINITY && acc <= max_dist2) {
+                    const unsigned place = atomicAdd(&cursor[qi], 1u);
+                    if (place < room)
+                        keys[off + place] = ((u64)__float_as_uint(acc) << 32) | (u64)(unsigned)(base + (long long)orig[p]);
+                }
+            }
+        }
+        first = false;
+        bool covers_all;
+        const double lb = grid_face_bound<KD>(gg, c, q, r, &covers_all);
+        if (covers_all) {
+            done = true;
+            break;
+        }
+        if (lb > 0.0 && (double)max_dist2 < lb * lb * (1.0 - 1e-6)) {   // no unseen row is within the radius
+            done = true;
+            break;
+        }
+    }
+    if (lane == 0 && !done && gmax > rmax + 1)
+        *giveup = 1u;      // benign race: every writer stores 1
+}
+
 // ---- host -------------------------------------------------------------------------------------------
 #define GTRY(call)                     \
     do {                                 \
@@ -825,6 +912,42 @@ hipError_t knn_grid_query_count(const GridState *gs, int rmax, int slot, const C
     *gate_out = giveup;
     GTRY(knn_count_commit_launch(c.m, c.scratch, c.counts, giveup, s));
     return knn_exact_count_launch(c, giveup);
+}
+
+// The whole list call on the grid way (KNN_QUERY_COUNT_GRID), asynchronous on c.stream: c.scratch [m] <- c.fill, the grid kernel
+// reserves in c.scratch and stores the keys into the caller's segments behind it; the commit, gated on NO give-up, copies c.scratch
+// to c.fill; the exact list, gated on the give-up word, lists the batch itself from the untouched c.fill over the same places.  One
+// of the two runs, so no hit is listed twice and a batch that gives up leaves no half-moved cursor.  rmax, events, *gate_out: as
+// knn_grid_query_count.
+hipError_t knn_grid_query_list(const GridState *gs, int rmax, int slot, const ListCall &c, const unsigned **gate_out)
+{
+    *gate_out = nullptr;
+    if (!gs || !gs->usable || c.m <= 0 || !c.scratch || !c.fill || !c.offsets || !c.keys || c.gids || rmax < 0)
+        return hipErrorInvalidValue;
+    const unsigned call = gs->calls[slot]++;
+    unsigned *giveup = gs->giveup + 2 * slot + (call & 1u);
+    unsigned *giveup_next = gs->giveup + 2 * slot + ((call + 1u) & 1u);
+    hipStream_t s = c.stream;
+    GTRY(hipMemcpyAsync(c.scratch, c.fill, (size_t)c.m * sizeof(unsigned), hipMemcpyDeviceToDevice, s));
+    const dim3 grid((unsigned)((c.m + GRID_BLOCK / 64 - 1) / (GRID_BLOCK / 64))), block(GRID_BLOCK);
+    if (c.ev0)
+        GTRY(hipEventRecord(c.ev0, s));
+#define GRID_LIST(KDV)                                                                                                          \
+    hipLaunchKernelGGL(knn_grid_list_kernel<KDV>, grid, block, 0, s, c.q, c.m, gs->geom, gs->start, gs->pts, gs->orig, c.base, \
+                       c.offsets, c.scratch, c.keys, rmax, giveup, giveup_next, c.max_dist2)
+    switch (gs->geom.k) {
+    case 1: GRID_LIST(1); break;
+    case 2: GRID_LIST(2); break;
+    case 3: GRID_LIST(3); break;
+    default: GRID_LIST(4); break;
+    }
+#undef GRID_LIST
+    GTRY(hipGetLastError());
+    if (c.ev1)
+        GTRY(hipEventRecord(c.ev1, s));
+    *gate_out = giveup;
+    GTRY(knn_list_commit_launch(c.m, c.scratch, c.fill, giveup, s));
+    return knn_exact_list_launch(c, giveup);
 }
 
 long long knn_grid_radius_rings(const GridState *gs, float max_dist2)
