@@ -364,6 +364,47 @@ int knn_keys_sort_segments(int device, int m, const unsigned long long *offsets_
 int knn_index_list_within_host(knn_index *idx, int m, const float *queries_host, float max_dist2,
                                long long *offsets_host, int **indices_out, float **dist2_out);
 
+/* ------------------------------------------------------------------------
+ * 2f. Top-K beyond 64: the exact K nearest rows for 1 <= K <= 4096.
+ *
+ * The contract of knn_index_query_topk_within (2c) holds word for word with 1 <= K <= KNN_TOPK_LARGE_MAX: a row of the shard is a
+ * candidate when its v0 distance E is finite and E <= max_dist2 — fp32, accumulated in dimension order, no FMA, an fp32 compare
+ * with equality inside, -0 counts as 0; max_dist2 = +INF is the plain top-K.  keys_dev[j*K + t] holds the K smallest candidate
+ * keys ascending — distance first, then the lowest global number (base_index + row, or the gid on a cell-range shard) —, the
+ * remaining slots KNN_KEY_INIT.  For K <= 64 the keys equal those of the radius-bounded call of 2c bit for bit on every input,
+ * NaN and overflowing rows and non-finite queries included.
+ * Flags: KNN_QUERY_INIT_KEYS alone.  With it the call writes the lists; without it the result is the K smallest of what keys_dev
+ * held (K sorted keys per query, the caller's, NOT clipped) and this shard's candidates, so index-range shards or cell-range
+ * shards (as they are: no seed layer) fold into the global list by calling one after the other on a stream.  Every other flag —
+ * KNN_QUERY_TOPK_PARTIAL, KNN_QUERY_TOPK_GRID, KNN_QUERY_TOPK_FRAMES, both KNN_QUERY_COUNT_* — is KNN_EINVAL.
+ * K outside 1 .. 4096, m < 1, m*K > INT_MAX, a slot outside 0 .. 7, max_dist2 < 0 or NaN and a null pointer are KNN_EINVAL, each
+ * with its own knn_last_error text, checked before the index, and nothing is launched.  An empty shard leaves the keys alone
+ * (writes padding under the init flag).  Asynchronous on `stream`; slots as for every other query; 1-NN, top-K, count, list and
+ * large calls may follow one another on a slot in any order.  indices_dev (may be NULL) receives the keys' low words.
+ * One way on every index (knn_index_last_stats [0] = 1; DESIGN §4.6 "Top-K beyond 64"): a radix select over the packed keys finds
+ * each query's K-th smallest candidate key in four scans of the shard — eight when some query's cut falls inside a class of equal
+ * distances —, one more scan fills the lists, one launch sorts them.  knn_index_last_stats: [1] = 0, [2] = 1 when the index
+ * word's passes ran (the last chunk of 65536 queries), [3] = 0.  The call it leaves alone has its limit of 64 as before. */
+#define KNN_TOPK_LARGE_MAX 4096
+int knn_index_query_topk_large(knn_index *idx, int slot, int m, int K, const float *queries_dev, float max_dist2,
+                               unsigned long long *keys_dev /*[m][K]*/, int *indices_dev /*[m][K] or NULL*/,
+                               void *stream, unsigned flags);
+/* b_dev[j] <- the K smallest of a_dev[j] and b_dev[j], both sorted lists of K keys, 1 <= K <= 4096, in place: the any-K sibling
+ * of the 64-key merge of 2c, for callers that gather GPUs' lists.  Asynchronous. */
+int knn_keys_topk_merge_large(int device, int m, int K, const unsigned long long *a_dev, unsigned long long *b_dev, void *stream);
+/* Synchronous, this shard alone: host queries [m][k] in, indices_host [m][K] out; dist2_host [m][K] (may be NULL) the float of each
+ * key's high word (+INF in padding); counts_host [m] (may be NULL) the entries of each list that are not padding. */
+int knn_index_query_topk_large_host(knn_index *idx, int m, int K, const float *queries_host, float max_dist2,
+                                    int *indices_host, float *dist2_host /*NULL ok*/, int *counts_host /*NULL ok*/);
+/* Test hooks, host arithmetic only.  knn_debug_topk_large_plan: in = {k, m, K, rows, CUs, 1 if init}; out = {chunks, slices of a
+ * pass, distance passes, index passes at most, LDS bytes of the select kernel, scratch bytes of the slot, launches of a call whose
+ * index passes stay gated off, launches with ties}.  knn_debug_radix_kth: the whole select over n given keys through the pick
+ * kernel's own lines — *kth = the threshold T the fill uses: the K-th smallest key down to the last digit a pass had to fix, ones
+ * below it (of distinct keys exactly K are <= T, and T is below the next one), or 0x7F7FFFFFFFFFFFFF when n < K; *passes_run =
+ * the passes not gated off (above 4: the index word's passes ran). */
+int knn_debug_topk_large_plan(const long long in[6], long long out[8]);
+int knn_debug_radix_kth(const unsigned long long *keys, long long n, int K, unsigned long long *kth, int *passes_run);
+
 /* Tuning / test hooks.  Known names:
  *   "path"    0 = auto, 1 = exact VALU kernels only, 2 = force the MFMA filter
  *             (+ exact re-rank) where its preconditions hold, 3 = the uniform-grid spatial index

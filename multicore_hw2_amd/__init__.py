@@ -18,7 +18,7 @@ import numpy as np
 
 __all__ = ["lib", "lib_path", "cudaCallback", "KnnIndex", "KnnGeom", "KnnError", "KEY_INIT", "set_option",
            "get_option", "trim", "device_count", "EXPORTED_SYMBOLS", "shard_bounds", "keys_topk_merge", "counts_to_offsets",
-           "keys_sort_segments"]
+           "keys_sort_segments", "keys_topk_merge_large", "debug_topk_large_plan", "debug_radix_kth", "TOPK_LARGE_MAX"]
 
 KEY_INIT = 0x7F80000000000000
 
@@ -37,7 +37,10 @@ EXPORTED_SYMBOLS = [
     "knn_debug_frame_dup", "knn_debug_topk_scratch",
     "knn_index_count_within", "knn_index_count_within_host", "knn_debug_count_plan",
     "knn_counts_to_offsets", "knn_index_list_within", "knn_keys_sort_segments", "knn_index_list_within_host",
+    "knn_index_query_topk_large", "knn_keys_topk_merge_large", "knn_index_query_topk_large_host", "knn_debug_topk_large_plan",
+    "knn_debug_radix_kth",
 ]
+TOPK_LARGE_MAX = 4096   # KNN_TOPK_LARGE_MAX
 QUERY_INIT_KEYS = 1   # KNN_QUERY_INIT_KEYS
 QUERY_TOPK_PARTIAL = 2   # KNN_QUERY_TOPK_PARTIAL
 QUERY_TOPK_GRID = 4   # KNN_QUERY_TOPK_GRID
@@ -447,6 +450,61 @@ def list_within_c():
     return f
 
 
+def query_topk_large_c():
+    """knn_index_query_topk_large with its argument types (set here, not in lib(), as count_within_c)."""
+    f = lib().knn_index_query_topk_large
+    f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p,
+                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint]
+    return f
+
+
+def keys_topk_merge_large_c():
+    f = lib().knn_keys_topk_merge_large
+    f.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    return f
+
+
+def query_topk_large_host_c():
+    f = lib().knn_index_query_topk_large_host
+    f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
+                  ctypes.c_void_p]
+    return f
+
+
+def keys_topk_merge_large(a_dev, b_dev, m, K, device=0, stream=0):
+    """Async (knn_keys_topk_merge_large): b[j] <- the K smallest of a[j] and b[j], device arrays of m sorted lists of K <= 4096
+    keys, in place."""
+    _check(keys_topk_merge_large_c()(int(device), int(m), int(K), ctypes.c_void_p(int(a_dev)), ctypes.c_void_p(int(b_dev)),
+                                     ctypes.c_void_p(stream)))
+
+
+TOPK_LARGE_INPUTS = ("k", "m", "K", "rows", "num_cu", "init")
+TOPK_LARGE_PLAN = ("chunks", "slices", "dist_passes", "index_passes", "lds_bytes", "scratch_bytes", "launches_clean", "launches_ties")
+
+
+def debug_topk_large_plan(**inputs):
+    """knn_debug_topk_large_plan: what a query_topk_large call launches with and the slot scratch it needs, for the inputs named
+    in TOPK_LARGE_INPUTS.  Host arithmetic; works without a GPU."""
+    vin = (ctypes.c_longlong * len(TOPK_LARGE_INPUTS))(*[int(inputs[n]) for n in TOPK_LARGE_INPUTS])
+    out = (ctypes.c_longlong * len(TOPK_LARGE_PLAN))()
+    f = lib().knn_debug_topk_large_plan
+    f.argtypes = [ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)]
+    _check(f(vin, out))
+    return dict(zip(TOPK_LARGE_PLAN, list(out)))
+
+
+def debug_radix_kth(keys, K):
+    """knn_debug_radix_kth: (T, passes_run) of the radix select over the given uint64 keys, through the pick kernel's own lines
+    (knn_radix_pick.h) — exactly min(K, n) of distinct keys are <= T; passes_run above 4: the index word's passes ran.  Host
+    arithmetic; works without a GPU."""
+    a = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1)
+    kth, passes = ctypes.c_ulonglong(), ctypes.c_int()
+    f = lib().knn_debug_radix_kth
+    f.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_int)]
+    _check(f(a.ctypes.data if a.size else None, a.size, int(K), ctypes.byref(kth), ctypes.byref(passes)))
+    return int(kth.value), int(passes.value)
+
+
 def counts_to_offsets_c():
     f = lib().knn_counts_to_offsets
     f.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
@@ -679,6 +737,31 @@ class KnnIndex:
             free(ind)
             free(d2)
         return offsets, indices, dist2
+
+    def query_topk_large(self, m, K, queries_dev, keys_dev, max_dist2=float("inf"), stream=0, slot=0, init_keys=False,
+                         indices_dev=None, flags=0):
+        """Async (knn_index_query_topk_large): query_topk_within for 1 <= K <= 4096 — keys_dev[m][K] <- the K smallest keys of
+        (this shard's rows with a finite v0 squared distance <= max_dist2 and, unless init_keys, the K sorted keys per query
+        keys_dev already holds, which are not clipped), sorted, padded with KEY_INIT.  One way on every index (last_stats()[0]
+        == 1; [2] == 1: some query's cut fell inside a class of equal distances).  flags: further flag bits as they are (every
+        one of them raises)."""
+        _check(query_topk_large_c()(self._h, int(slot), int(m), int(K), ctypes.c_void_p(int(queries_dev)), float(max_dist2),
+                                    ctypes.c_void_p(int(keys_dev)),
+                                    ctypes.c_void_p(int(indices_dev)) if indices_dev is not None else None,
+                                    ctypes.c_void_p(stream), (QUERY_INIT_KEYS if init_keys else 0) | int(flags)))
+
+    def query_topk_large_host(self, queries, K, max_dist2=float("inf")):
+        """Synchronous large top-K of this shard alone: (indices int32 [m][K], dist2 float32 [m][K] with +INF in padding, counts
+        int32 [m]: the entries of each list that are not padding)."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1)
+        m = q.size // self.k
+        idx = np.empty((m, int(K)), dtype=np.int32)
+        d2 = np.empty((m, int(K)), dtype=np.float32)
+        counts = np.empty(m, dtype=np.int32)
+        _check(query_topk_large_host_c()(self._h, m, int(K), q.ctypes.data_as(ctypes.c_void_p), float(max_dist2),
+                                         idx.ctypes.data_as(ctypes.c_void_p), d2.ctypes.data_as(ctypes.c_void_p),
+                                         counts.ctypes.data_as(ctypes.c_void_p)))
+        return idx, d2, counts
 
     def query_topk_host(self, queries, K):
         """Synchronous top-K of this shard alone: (indices int32 [m][K], dist2 float32 [m][K])."""

@@ -8,6 +8,7 @@
 // core.cu:935-957, whose indexing is wrong for m > 1 — SURVEY.md §8 a2').
 #include "../../include/knn_mi355x.h"
 #include "knn_common.h"
+#include "knn_radix_pick.h"
 
 #include <limits.h>
 #include <math.h>
@@ -302,7 +303,9 @@ struct knn_index {
     long long stats[4] = {0, 0, 0, 0};
     FilterState filter;           // MFMA filter layouts + workspace (usable == false: exact only)
     GridState *grid = nullptr;    // k <= 4: uniform-grid spatial index (null: not built / ruled out)
-    const unsigned *grid_topk_gate = nullptr;   // the last call was a top-K on the grid: its give-up word (knn_index_last_stats)
+    // the device word behind the last call's stats[2] (knn_index_last_stats): a call on the grid — its give-up word; a large
+    // top-K (way 1) — the word that says the index word's passes ran
+    const unsigned *grid_topk_gate = nullptr;
     int timing = 0;            // 0 off, N > 0: bracket every N-th dominant-kernel launch with events
     unsigned long long timing_seq = 0;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;  // one pair per timed launch
@@ -321,6 +324,8 @@ struct knn_index {
         size_t part_bytes = 0, cand_bytes = 0, lists_bytes = 0;
         u64 *count = nullptr;      // knn_index_count_within on the grid and cell ways: the per-query count scratch [m] unsigned
         size_t count_bytes = 0;
+        u64 *large = nullptr;      // knn_index_query_topk_large: what knn_topk_large_plan says (histograms, select state, a fold's lists)
+        size_t large_bytes = 0;
     } topk[KNN_SLOTS];
     // Calls on one index from several host threads are serialised (enqueueing a batch is ~20 us of host work; the GPU
     // work of different slots still overlaps): the workspaces' lazily grown buffers, the event list, the statistics and
@@ -804,6 +809,7 @@ void knn_index_destroy(knn_index *idx)
             (void)knn_dev_free(t.cand);
             (void)knn_dev_free(t.lists);
             (void)knn_dev_free(t.count);
+            (void)knn_dev_free(t.large);
         }
         knn_dev_free_end_synced();
         for (auto &ev : idx->events) {
@@ -1516,6 +1522,118 @@ int knn_index_list_within(knn_index *idx, int slot, int m, const float *queries_
     return KNN_OK;
 }
 
+int knn_index_query_topk_large(knn_index *idx, int slot, int m, int K, const float *queries_dev, float max_dist2,
+                               unsigned long long *keys_dev, int *indices_dev, void *stream, unsigned flags)
+{
+    // (one message per rule, the index last, as knn_index_count_within: tests/test_topk_large_logic.py tells them apart without a GPU)
+    if (K < 1 || K > KNN_TOPK_LARGE_MAX)
+        return fail(KNN_EINVAL, "knn_index_query_topk_large: K outside 1 .. 4096");
+    if (m < 1)
+        return fail(KNN_EINVAL, "knn_index_query_topk_large: m < 1");
+    if ((long long)m * K > INT_MAX)
+        return fail(KNN_EINVAL, "knn_index_query_topk_large: m * K above INT_MAX");
+    if (slot < 0 || slot >= KNN_SLOTS)
+        return fail(KNN_EINVAL, "knn_index_query_topk_large: slot outside 0 .. 7");
+    if (!(max_dist2 >= 0.0f))
+        return fail(KNN_EINVAL, "knn_index_query_topk_large: max_dist2 must be >= 0 and not NaN");
+    if ((flags & ~(unsigned)KNN_QUERY_INIT_KEYS) != 0u)
+        return fail(KNN_EINVAL, "knn_index_query_topk_large: unknown flag (KNN_QUERY_INIT_KEYS alone is admitted)");
+    if (!queries_dev || !keys_dev)
+        return fail(KNN_EINVAL, "knn_index_query_topk_large: null queries or keys");
+    if (!idx)
+        return fail(KNN_EINVAL, "knn_index_query_topk_large: null index");
+    std::lock_guard<std::recursive_mutex> lock(idx->mu);
+    DeviceGuard guard(idx->device);
+    if (!guard.ok)
+        return fail(KNN_EHIP, "knn_index_query_topk_large: hipSetDevice failed");
+    // (-0 counts as 0)
+    TopkCall call = topk_call_of(m, K, queries_dev, keys_dev, stream, max_dist2 == 0.0f ? 0.0f : max_dist2);
+    call.init = (flags & KNN_QUERY_INIT_KEYS) != 0u;
+    hipStream_t s = call.stream;
+    const int mk = m * K;
+    idx->stats[0] = 1;
+    idx->stats[1] = 0;
+    idx->stats[2] = 0;
+    idx->stats[3] = 0;
+    idx->grid_topk_gate = nullptr;
+    idx->last_slot = slot;
+    if (idx->n > 0) {   // (an empty shard adds nothing)
+        call.k = idx->k;
+        call.n = idx->n;
+        call.base = idx->base;
+        // a cell-range shard's keys carry its rows' global numbers (gids); an index-range shard's base + row
+        call.gids = idx->sharded && idx->filter.cells ? idx->filter.cells->gids : nullptr;
+        call.r = idx->refs;
+        call.num_cu = idx->num_cu;
+        // the slot's scratch, grown before the first launch
+        const TopkLargePlan plan = knn_topk_large_plan(idx->k, m, K, idx->n, idx->num_cu, call.init != 0);
+        knn_index::TopkSlot &ts = idx->topk[slot];
+        KNN_TRY(slot_buffer_grow(ts.large, ts.large_bytes, plan.scratch_bytes));
+        call.part = ts.large;
+        call.part_bytes = ts.large_bytes;
+        EventPair *ev = nullptr;
+        KNN_TRY(next_event_pair(idx, false, &ev));
+        call.ev0 = ev ? ev->first : nullptr;
+        call.ev1 = ev ? ev->second : nullptr;
+        HIP_TRY(knn_topk_large_launch(call, plan, &idx->grid_topk_gate));
+    } else if (call.init) {
+        HIP_TRY(knn_keys_fill_launch(call.keys, mk, s));
+    }
+    if (indices_dev)
+        HIP_TRY(knn_keys_unpack_launch(call.keys, mk, indices_dev, s));
+    return KNN_OK;
+}
+
+int knn_keys_topk_merge_large(int device, int m, int K, const unsigned long long *a_dev, unsigned long long *b_dev, void *stream)
+{
+    if (K < 1 || K > KNN_TOPK_LARGE_MAX)
+        return fail(KNN_EINVAL, "knn_keys_topk_merge_large: K outside 1 .. 4096");
+    if (m < 1)
+        return fail(KNN_EINVAL, "knn_keys_topk_merge_large: m < 1");
+    if (!a_dev || !b_dev)
+        return fail(KNN_EINVAL, "knn_keys_topk_merge_large: null list");
+    DeviceGuard guard(device);
+    if (!guard.ok)
+        return fail(KNN_EHIP, "knn_keys_topk_merge_large: hipSetDevice failed");
+    HIP_TRY(knn_topk_merge_large_launch(m, K, (const u64 *)a_dev, (u64 *)b_dev, (hipStream_t)stream));
+    return KNN_OK;
+}
+
+int knn_debug_topk_large_plan(const long long in[6], long long out[8])
+{
+    if (!in || !out || in[0] < 1 || in[0] > INT_MAX || in[1] < 1 || in[1] > INT_MAX || in[2] < 1 || in[2] > KNN_TOPK_LARGE_MAX ||
+        in[1] * in[2] > INT_MAX || in[3] < 1 || in[4] < 1 || in[4] > INT_MAX || (in[5] != 0 && in[5] != 1))
+        return fail(KNN_EINVAL, "knn_debug_topk_large_plan: bad arguments (k >= 1, m >= 1, 1 <= K <= 4096, m * K <= INT_MAX, rows >= 1, "
+                                "CUs >= 1, init 0 or 1)");
+    const TopkLargePlan p = knn_topk_large_plan((int)in[0], (int)in[1], (int)in[2], in[3], (int)in[4], in[5] != 0);
+    const long long v[8] = {p.chunks, p.slices, p.dist_passes, p.index_passes, (long long)p.lds_bytes, (long long)p.scratch_bytes,
+                            p.launches_clean, p.launches_ties};
+    memcpy(out, v, sizeof v);
+    return KNN_OK;
+}
+
+int knn_debug_radix_kth(const unsigned long long *keys, long long n, int K, unsigned long long *kth, int *passes_run)
+{
+    if (!kth || !passes_run || n < 0 || (n > 0 && !keys) || K < 1 || K > KNN_TOPK_LARGE_MAX)
+        return fail(KNN_EINVAL, "knn_debug_radix_kth: bad arguments (n >= 0, 1 <= K <= 4096)");
+    // the device sequence for one query: per pass the histogram of the keys under the prefix, then the pick; a pass runs only
+    // when the one before left the query open
+    u64 prefix = 0ull;
+    unsigned need = (unsigned)K;
+    int passes = 0;
+    bool open = true;
+    for (int pass = 0; pass < KNN_RADIX_PASSES && open; ++pass, ++passes) {
+        unsigned hist[KNN_RADIX_BINS] = {0u};
+        for (long long i = 0; i < n; ++i)
+            if (knn_radix_match(keys[i], prefix, pass))
+                ++hist[knn_radix_digit(keys[i], pass)];
+        open = knn_radix_pick(hist, 1ull, pass, prefix, need);
+    }
+    *kth = prefix;
+    *passes_run = passes;
+    return KNN_OK;
+}
+
 int knn_debug_filter_scores(knn_index *idx, int m, const float *queries_dev, float *scores_dev,
                             float *qnorm_dev, double consts[8])
 {
@@ -1599,6 +1717,12 @@ int knn_index_last_stats(knn_index *idx, long long stats[4])
         idx->stats[3] = idx->filter.n_outliers;
     }
     if (idx->stats[0] == 3 && idx->grid_topk_gate) {   // a top-K call on the grid: 1 = some query gave up, the exact top-K answered
+        DeviceGuard guard(idx->device);
+        unsigned word = 0u;
+        HIP_TRY(hipMemcpy(&word, idx->grid_topk_gate, sizeof word, hipMemcpyDeviceToHost));
+        idx->stats[2] = word ? 1 : 0;
+    }
+    if (idx->stats[0] == 1 && idx->grid_topk_gate) {   // a large top-K: 1 = some query's cut fell inside a class of equal distances
         DeviceGuard guard(idx->device);
         unsigned word = 0u;
         HIP_TRY(hipMemcpy(&word, idx->grid_topk_gate, sizeof word, hipMemcpyDeviceToHost));
@@ -1988,6 +2112,64 @@ extern "C" int knn_index_query_topk_within_host(knn_index *idx, int m, int K, co
     const int rc = staged_query(idx, "knn_index_query_topk_within_host", m, K, queries_host, keys.data(), nullptr, max_dist2);
     if (rc != KNN_OK)
         return rc;
+    for (size_t i = 0; i < mk; ++i) {
+        indices_host[i] = (int)(unsigned)(keys[i] & 0xFFFFFFFFull);
+        if (dist2_host) {
+            const unsigned hi = (unsigned)(keys[i] >> 32);
+            memcpy(&dist2_host[i], &hi, sizeof hi);
+        }
+    }
+    if (counts_host)
+        for (int j = 0; j < m; ++j) {   // padding is KNN_KEY_INIT; a real key is below it
+            int c = 0;
+            while (c < K && keys[(size_t)j * K + c] < kKeyInit)
+                ++c;
+            counts_host[j] = c;
+        }
+    return KNN_OK;
+}
+
+extern "C" int knn_index_query_topk_large_host(knn_index *idx, int m, int K, const float *queries_host, float max_dist2,
+                                               int *indices_host, float *dist2_host, int *counts_host)
+{
+    if (K < 1 || K > KNN_TOPK_LARGE_MAX)
+        return fail(KNN_EINVAL, "knn_index_query_topk_large_host: K outside 1 .. 4096");
+    if (m < 1)
+        return fail(KNN_EINVAL, "knn_index_query_topk_large_host: m < 1");
+    if ((long long)m * K > INT_MAX)
+        return fail(KNN_EINVAL, "knn_index_query_topk_large_host: m * K above INT_MAX");
+    if (!(max_dist2 >= 0.0f))
+        return fail(KNN_EINVAL, "knn_index_query_topk_large_host: max_dist2 must be >= 0 and not NaN");
+    if (!queries_host || !indices_host)
+        return fail(KNN_EINVAL, "knn_index_query_topk_large_host: null queries or indices");
+    if (!idx)
+        return fail(KNN_EINVAL, "knn_index_query_topk_large_host: null index");
+    std::lock_guard<std::recursive_mutex> lock(idx->mu);
+    DeviceGuard guard(idx->device);
+    if (!guard.ok)
+        return fail(KNN_EHIP, "knn_index_query_topk_large_host: hipSetDevice failed");
+    const size_t mk = (size_t)m * (size_t)K;
+    std::vector<u64> keys(mk);
+    {
+        Staging stage(idx->device);
+        float *q_dev = nullptr;
+        u64 *keys_dev = nullptr;
+        const size_t qbytes = (size_t)m * (size_t)idx->k * sizeof(float);
+        hipError_t e = stage.get(&q_dev, qbytes);
+        if (e == hipSuccess)
+            e = stage.get(&keys_dev, mk * sizeof(u64));
+        if (e == hipSuccess)
+            e = hipMemcpy(q_dev, queries_host, qbytes, hipMemcpyHostToDevice);
+        if (e != hipSuccess)
+            return fail(KNN_EHIP, "knn_index_query_topk_large_host: staging queries", hipGetErrorString(e));
+        const int rc = knn_index_query_topk_large(idx, 0, m, K, q_dev, max_dist2, keys_dev, nullptr, nullptr, KNN_QUERY_INIT_KEYS);
+        if (rc != KNN_OK)
+            return rc;
+        e = hipMemcpy(keys.data(), keys_dev, mk * sizeof(u64), hipMemcpyDeviceToHost);
+        if (e != hipSuccess)
+            return fail(KNN_EHIP, "knn_index_query_topk_large_host: D2H keys", hipGetErrorString(e));
+        // (not declared waited: the buffers go back after the device-wide wait `stage` then makes itself, as the top-K's)
+    }
     for (size_t i = 0; i < mk; ++i) {
         indices_host[i] = (int)(unsigned)(keys[i] & 0xFFFFFFFFull);
         if (dist2_host) {

@@ -232,6 +232,31 @@ hipError_t knn_counts_to_offsets_launch(const unsigned *counts, int m, u64 *offs
 // KNN_SORT_LDS_KEYS keys and in global memory beyond.
 #define KNN_SORT_LDS_KEYS 4096
 hipError_t knn_keys_sort_segments_launch(int m, const u64 *offsets, const unsigned *fill, u64 *keys, hipStream_t stream);
+
+// ---- top-K beyond 64 (knn_select.hip; knn_index_query_topk_large; DESIGN §4.6 "Top-K beyond 64") --------------------------------
+#define KNN_TOPK_LARGE_MAX 4096   // largest K of knn_index_query_topk_large (= KNN_SORT_LDS_KEYS: a list sorts in LDS)
+#define KNN_SELECT_WAVES 8        // waves of a select block: they hold the same 64 queries and split the slice's rows
+// Everything one large call launches with and the slot's scratch it needs: the one place both are decided
+// (knn_debug_topk_large_plan shows it).  The scratch, per chunk of <= KNN_TOPK_CHUNK queries (mcp = the chunk's queries rounded up
+// to whole waves): the per-query histograms [256][mcp] unsigned (bin-major), prefix [mcp] u64, need [mcp], cursor [mcp], the
+// passes' gate words [8], and — a folding call — the chunk's lists [chunk_m][K].
+struct TopkLargePlan {
+    int chunks = 0, chunk_m = 0;     // launches sequences; queries of the largest chunk
+    long long mcp = 0;               // chunk_m rounded up to a multiple of KNN_WAVE
+    long long slices = 0;            // blocks along the rows of one select pass (the largest chunk)
+    int dist_passes = 0, index_passes = 0;
+    size_t lds_bytes = 0;            // static LDS of the select kernel: the block's histogram
+    size_t hist_off = 0, prefix_off = 0, need_off = 0, cursor_off = 0, gate_off = 0, state_bytes = 0, list_off = 0;
+    size_t scratch_bytes = 0;
+    long long launches_clean = 0, launches_ties = 0;   // launches that do work: no query's cut inside a distance class / some
+};
+TopkLargePlan knn_topk_large_plan(int k, int m, int K, long long n, int num_cu, bool init);
+// c.keys[m][K] <- the K smallest of (keys unless c.init, this shard's candidates: finite v0 distance E <= c.max_dist2), sorted,
+// padded with KNN_KEY_INIT; 1 <= K <= KNN_TOPK_LARGE_MAX.  c.part: p.scratch_bytes of the slot's scratch, stream-ordered.
+// *tie_word <- the device word that is non-zero when the index word's passes ran on the last chunk.
+hipError_t knn_topk_large_launch(const TopkCall &c, const TopkLargePlan &p, const unsigned **tie_word);
+// b[j] <- the K smallest of a[j] and b[j] (sorted lists of K <= KNN_TOPK_LARGE_MAX keys), sorted, in place: one block per query.
+hipError_t knn_topk_merge_large_launch(int m, int K, const u64 *a, u64 *b, hipStream_t stream);
 // ---- MFMA filter + exact re-rank (knn_filter.hip) ---------------------------
 // Device-side control words of one filter query (FilterState::ctl).
 enum {

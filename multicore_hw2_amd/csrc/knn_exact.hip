@@ -1834,30 +1834,7 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_counts_to_offsets_kernel(const 
 // comparator pointing the same way the places from cnt up to the next power of two behave as +INF padding that never moves, so a
 // comparator whose upper place is >= cnt is simply skipped: any length sorts, nothing beyond cnt is read or written.  Equal keys are
 // never exchanged.  cnt <= KNN_SORT_LDS_KEYS: in LDS (32 KB); beyond: the same network on the segment in global memory, the block's
-// barriers ordering its own stores and loads.
-__device__ __forceinline__ void sort_network(u64 *a, unsigned cnt)
-{
-    unsigned P = 1u;
-    while (P < cnt)
-        P <<= 1;
-    for (unsigned h = 1u; h < P; h <<= 1) {          // merge runs of h into runs of 2h
-        for (unsigned j = h; j >= 1u; j >>= 1) {
-            for (unsigned t = threadIdx.x; t < P / 2u; t += KNN_BLOCK) {
-                const unsigned i = (t / j) * 2u * j + (t % j);
-                const unsigned l = j == h ? (i | (2u * h - 1u)) - (i & (h - 1u)) : i + j;   // mirror within the run of 2h, or i + j
-                if (l < cnt) {
-                    const u64 x = a[i], y = a[l];
-                    if (x > y) {
-                        a[i] = y;
-                        a[l] = x;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
-}
-
+// barriers ordering its own stores and loads.  (sort_network: knn_exact_dev.h — the large top-K sorts its lists with it too.)
 __global__ __launch_bounds__(KNN_BLOCK) void knn_keys_sort_segments_kernel(const u64 *__restrict__ offsets,
                                                                           const unsigned *__restrict__ fill, u64 *keys)
 {

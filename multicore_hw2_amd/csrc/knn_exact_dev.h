@@ -34,6 +34,31 @@ __device__ __forceinline__ u64 wave_min_u64(u64 v)
     return v;
 }
 
+// The first cnt keys of a[] ascending, by one block of KNN_BLOCK threads (knn_keys_sort_segments_kernel describes the network;
+// knn_topk_large_sort_kernel, knn_select.hip, sorts its lists with it too).  a: LDS or global memory of the block's own.
+__device__ __forceinline__ void sort_network(u64 *a, unsigned cnt)
+{
+    unsigned P = 1u;
+    while (P < cnt)
+        P <<= 1;
+    for (unsigned h = 1u; h < P; h <<= 1) {          // merge runs of h into runs of 2h
+        for (unsigned j = h; j >= 1u; j >>= 1) {
+            for (unsigned t = threadIdx.x; t < P / 2u; t += KNN_BLOCK) {
+                const unsigned i = (t / j) * 2u * j + (t % j);
+                const unsigned l = j == h ? (i | (2u * h - 1u)) - (i & (h - 1u)) : i + j;   // mirror within the run of 2h, or i + j
+                if (l < cnt) {
+                    const u64 x = a[i], y = a[l];
+                    if (x > y) {
+                        a[i] = y;
+                        a[l] = x;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
 // One (record, row) pair: the packed key of row `reg` of record e for its query, ~0 when there is nothing to evaluate.
 template <int K>
 __device__ __forceinline__ u64 rerank_pair(const float *__restrict__ Q, const float *__restrict__ R, int k, long long n,
