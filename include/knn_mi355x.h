@@ -405,6 +405,57 @@ int knn_index_query_topk_large_host(knn_index *idx, int m, int K, const float *q
 int knn_debug_topk_large_plan(const long long in[6], long long out[8]);
 int knn_debug_radix_kth(const unsigned long long *keys, long long n, int K, unsigned long long *kth, int *passes_run);
 
+/* ------------------------------------------------------------------------
+ * 2g. Queries over a subset of the rows: the top-K and the count within a radius, asked of the rows a bit mask admits — the rows
+ * of one tenant or label, the rows not deleted, everything but the rows already returned — without a second index and without
+ * over-fetching.
+ *
+ * The mask: mask_dev is a device array of (n_local + 31) / 32 unsigned words on the index's device, borrowed for the call.  Bit
+ * i % 32 of word i / 32 admits LOCAL row i: row i of the refs given to knn_index_create, row i of the refs_dev given to
+ * knn_index_create_sharded — the order the exact scans read the rows in and number them base_index + row / gids[row].  Bits at and
+ * beyond n_local in the last word are ignored, whatever they hold.
+ * The contract is that of knn_index_query_topk_within (2c) and knn_index_count_within (2d) with one change: a row is a candidate
+ * only when its mask bit is set AND its v0 distance E is finite and E <= max_dist2 — fp32, accumulated in dimension order, no FMA,
+ * an fp32 compare with equality inside, -0 counts as 0; max_dist2 = +INF is the plain filtered top-K.  Keys carry the ORIGINAL
+ * global numbers (base_index + row, or the gid), lists are ascending and padded with KNN_KEY_INIT, 1 <= K <= 64.  An all-ones mask
+ * gives knn_index_query_topk_within's keys and knn_index_count_within's counts bit for bit on every input, NaN and overflowing rows
+ * and non-finite queries included; an all-zero mask gives padding and zero counts.
+ * Flags: KNN_QUERY_INIT_KEYS alone.  Without it the call folds into the K sorted keys held (the caller's, NOT clipped) or adds to
+ * the counts, so disjoint shards, each with its own mask, fold by calling one after the other on a stream; with it the call writes
+ * (an empty shard writes padding or zeros under it and otherwise leaves things alone).  Every other flag is KNN_EINVAL.
+ * Argument errors are KNN_EINVAL, each with its own knn_last_error text, checked in this order — the first that fails speaks —:
+ * max_dist2 < 0 or NaN, an unknown flag, a slot outside 0 .. 7, m < 1, K outside 1 .. 64, m * K > INT_MAX, a null queries, mask,
+ * keys or counts pointer, a null index; nothing is launched.  Asynchronous on `stream`; slots as for every other query; masked
+ * calls may follow or precede any other call on a slot.
+ * One way on every index (knn_index_last_stats: [0] = 1, [1] = [2] = [3] = 0; DESIGN §4.6 "Over a subset of the rows"): the exact
+ * masked scan.  No layout is consulted, so grid, cell-sorted, per-cell-framed and sharded indexes all answer.  The scan walks the
+ * mask words — a zero word skips 32 rows without touching them, an admitted row costs what a row costs the exact scan — and cuts
+ * the shard into slices of equal numbers of ADMITTED rows, so a mask that admits one contiguous range is spread over the whole
+ * device like any other.  The mask may change between calls: every call counts it anew. */
+int knn_index_query_topk_masked(knn_index *idx, int slot, int m, int K, const float *queries_dev, float max_dist2,
+                                const unsigned *mask_dev, unsigned long long *keys_dev /*[m][K]*/,
+                                int *indices_dev /*[m][K] or NULL*/, void *stream, unsigned flags);
+int knn_index_count_within_masked(knn_index *idx, int slot, int m, const float *queries_dev, float max_dist2,
+                                  const unsigned *mask_dev, unsigned *counts_dev, void *stream, unsigned flags);
+/* mask_dev bits of the listed local rows <- value (1 set, 0 clear); rows outside 0 .. n_local-1 are ignored; async.
+ * Serves allow-lists (memset 0, then set) and tombstones (memset 0xFF, then clear). */
+int knn_mask_set_rows(int device, long long n_local, const unsigned *rows_dev, long long count, int value,
+                      unsigned *mask_dev, void *stream);
+/* Synchronous, this shard alone; mask_host: the words on the host.  dist2_host / counts_host may be NULL. */
+int knn_index_query_topk_masked_host(knn_index *idx, int m, int K, const float *queries_host, float max_dist2,
+                                     const unsigned *mask_host, int *indices_host, float *dist2_host, int *counts_host);
+/* Test hooks, host arithmetic only.  knn_debug_masked_plan: in = {k, m, K (0 = a count call), rows, CUs, 1 if init}; out =
+ * {granules of 1024 rows, slices of the first chunk of queries (the unmasked exact scan's number), chunks of 65536 queries, LDS
+ * bytes of the scan, bytes of the slot's mask scratch, bytes of the slot's per-slice lists, kernel launches of an init call
+ * (granule counts, prefix, per chunk the scan and — top-K — the select), queries of the first chunk}.  knn_debug_mask_split: the
+ * cut the scan's blocks make, through their own lines (knn_mask_split.h), at its first step: first_granule[b], b = 0 .. slices, is
+ * the least g with P[g] * slices >= b * T, P the exclusive prefix of granule_counts and T its total.  knn_debug_mask_split_rows:
+ * the whole cut for a mask on the host: first_row[b] is the least row r with A(r) * slices >= b * T, A(r) the admitted rows before
+ * row r — found inside granule first_granule[b] - 1 —; slice b is the rows [first_row[b], first_row[b + 1]). */
+int knn_debug_masked_plan(const long long in[6], long long out[8]);
+int knn_debug_mask_split(const unsigned *granule_counts, long long granules, int slices, long long *first_granule /*[slices+1]*/);
+int knn_debug_mask_split_rows(const unsigned *mask_host, long long n_local, int slices, long long *first_row /*[slices+1]*/);
+
 /* Tuning / test hooks.  Known names:
  *   "path"    0 = auto, 1 = exact VALU kernels only, 2 = force the MFMA filter
  *             (+ exact re-rank) where its preconditions hold, 3 = the uniform-grid spatial index

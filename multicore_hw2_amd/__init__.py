@@ -18,7 +18,8 @@ import numpy as np
 
 __all__ = ["lib", "lib_path", "cudaCallback", "KnnIndex", "KnnGeom", "KnnError", "KEY_INIT", "set_option",
            "get_option", "trim", "device_count", "EXPORTED_SYMBOLS", "shard_bounds", "keys_topk_merge", "counts_to_offsets",
-           "keys_sort_segments", "keys_topk_merge_large", "debug_topk_large_plan", "debug_radix_kth", "TOPK_LARGE_MAX"]
+           "keys_sort_segments", "keys_topk_merge_large", "debug_topk_large_plan", "debug_radix_kth", "TOPK_LARGE_MAX",
+           "mask_words", "mask_set_rows", "debug_masked_plan", "debug_mask_split", "debug_mask_split_rows"]
 
 KEY_INIT = 0x7F80000000000000
 
@@ -39,6 +40,8 @@ EXPORTED_SYMBOLS = [
     "knn_counts_to_offsets", "knn_index_list_within", "knn_keys_sort_segments", "knn_index_list_within_host",
     "knn_index_query_topk_large", "knn_keys_topk_merge_large", "knn_index_query_topk_large_host", "knn_debug_topk_large_plan",
     "knn_debug_radix_kth",
+    "knn_index_query_topk_masked", "knn_index_count_within_masked", "knn_mask_set_rows", "knn_index_query_topk_masked_host",
+    "knn_debug_masked_plan", "knn_debug_mask_split", "knn_debug_mask_split_rows",
 ]
 TOPK_LARGE_MAX = 4096   # KNN_TOPK_LARGE_MAX
 QUERY_INIT_KEYS = 1   # KNN_QUERY_INIT_KEYS
@@ -505,6 +508,88 @@ def debug_radix_kth(keys, K):
     return int(kth.value), int(passes.value)
 
 
+def query_topk_masked_c():
+    """knn_index_query_topk_masked with its argument types (set here, not in lib(), as count_within_c)."""
+    f = lib().knn_index_query_topk_masked
+    f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p,
+                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint]
+    return f
+
+
+def count_within_masked_c():
+    """knn_index_count_within_masked with its argument types (set here, not in lib(), as count_within_c)."""
+    f = lib().knn_index_count_within_masked
+    f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
+                  ctypes.c_void_p, ctypes.c_uint]
+    return f
+
+
+def query_topk_masked_host_c():
+    f = lib().knn_index_query_topk_masked_host
+    f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
+                  ctypes.c_void_p, ctypes.c_void_p]
+    return f
+
+
+def mask_set_rows_c():
+    f = lib().knn_mask_set_rows
+    f.argtypes = [ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    return f
+
+
+def mask_words(n):
+    """The uint32 words of a row mask over n local rows: bit i % 32 of word i // 32 admits row i."""
+    return (int(n) + 31) // 32
+
+
+def mask_set_rows(n_local, rows_dev, count, value, mask_dev, device=0, stream=0):
+    """Async (knn_mask_set_rows): the mask bits of the local rows rows_dev[count] (uint32) <- value (1 set, 0 clear); rows outside
+    0 .. n_local - 1 are ignored.  Allow-lists: zero the mask, then set; tombstones: fill it with ones, then clear."""
+    _check(mask_set_rows_c()(int(device), int(n_local), ctypes.c_void_p(int(rows_dev)) if rows_dev else None, int(count),
+                             int(value), ctypes.c_void_p(int(mask_dev)), ctypes.c_void_p(stream)))
+
+
+MASKED_PLAN_INPUTS = ("k", "m", "K", "rows", "num_cu", "init")
+MASKED_PLAN = ("granules", "slices", "chunks", "lds_bytes", "mask_bytes", "part_bytes", "launches", "chunk_m")
+
+
+def debug_masked_plan(**inputs):
+    """knn_debug_masked_plan: what a query_topk_masked (K >= 1) or count_within_masked (K = 0) call launches with and the slot
+    scratch it needs, for the inputs named in MASKED_PLAN_INPUTS.  Host arithmetic; works without a GPU."""
+    vin = (ctypes.c_longlong * len(MASKED_PLAN_INPUTS))(*[int(inputs[n]) for n in MASKED_PLAN_INPUTS])
+    out = (ctypes.c_longlong * len(MASKED_PLAN))()
+    f = lib().knn_debug_masked_plan
+    f.argtypes = [ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)]
+    _check(f(vin, out))
+    return dict(zip(MASKED_PLAN, list(out)))
+
+
+def debug_mask_split(granule_counts, slices):
+    """knn_debug_mask_split: first_granule[0 .. slices] (int64) — the granules [first[b],
+    first[b + 1]) at the cut's first step — for the given admitted rows per granule, through the kernels' own lines
+    (knn_mask_split.h).  Host arithmetic; works without a GPU."""
+    a = np.ascontiguousarray(granule_counts, dtype=np.uint32).reshape(-1)
+    out = np.empty(int(slices) + 1 if int(slices) >= 0 else 1, dtype=np.int64)
+    f = lib().knn_debug_mask_split
+    f.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p]
+    _check(f(a.ctypes.data if a.size else None, a.size, int(slices), out.ctypes.data))
+    return out
+
+
+def debug_mask_split_rows(mask, n_local, slices):
+    """knn_debug_mask_split_rows: first_row[0 .. slices] (int64) — slice b of the masked scans is the rows [first[b],
+    first[b + 1]) — for the uint32 words of a mask over n_local rows, through the kernels' own lines (knn_mask_split.h).  Host
+    arithmetic; works without a GPU."""
+    a = np.ascontiguousarray(mask, dtype=np.uint32).reshape(-1)
+    if a.size != mask_words(n_local):
+        raise ValueError("mask: expected %d words, got %d" % (mask_words(n_local), a.size))
+    out = np.empty(int(slices) + 1 if int(slices) >= 0 else 1, dtype=np.int64)
+    f = lib().knn_debug_mask_split_rows
+    f.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p]
+    _check(f(a.ctypes.data if a.size else None, int(n_local), int(slices), out.ctypes.data))
+    return out
+
+
 def counts_to_offsets_c():
     f = lib().knn_counts_to_offsets
     f.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
@@ -761,6 +846,42 @@ class KnnIndex:
         _check(query_topk_large_host_c()(self._h, m, int(K), q.ctypes.data_as(ctypes.c_void_p), float(max_dist2),
                                          idx.ctypes.data_as(ctypes.c_void_p), d2.ctypes.data_as(ctypes.c_void_p),
                                          counts.ctypes.data_as(ctypes.c_void_p)))
+        return idx, d2, counts
+
+    def query_topk_masked(self, m, K, queries_dev, mask_dev, keys_dev, max_dist2=float("inf"), stream=0, slot=0, init_keys=False,
+                          indices_dev=None, flags=0):
+        """Async (knn_index_query_topk_masked): query_topk_within over the rows the mask admits — keys_dev[m][K] <- the K smallest
+        keys of (this shard's rows whose bit is set in mask_dev (uint32 [mask_words(n)], bit i % 32 of word i // 32 = local row i)
+        and whose v0 squared distance is finite and <= max_dist2 and, unless init_keys, the K sorted keys per query keys_dev already
+        holds, which are not clipped), sorted, padded with KEY_INIT; keys carry the original global numbers.  1 <= K <= 64.  One way
+        on every index (last_stats() == [1, 0, 0, 0]).  flags: further flag bits as they are (every one of them raises)."""
+        _check(query_topk_masked_c()(self._h, int(slot), int(m), int(K), ctypes.c_void_p(int(queries_dev)), float(max_dist2),
+                                     ctypes.c_void_p(int(mask_dev)), ctypes.c_void_p(int(keys_dev)),
+                                     ctypes.c_void_p(int(indices_dev)) if indices_dev is not None else None,
+                                     ctypes.c_void_p(stream), (QUERY_INIT_KEYS if init_keys else 0) | int(flags)))
+
+    def count_within_masked(self, m, queries_dev, max_dist2, mask_dev, counts_dev, stream=0, slot=0, init=False, flags=0):
+        """Async (knn_index_count_within_masked): counts_dev[m] (uint32) += the rows of this shard whose mask bit is set and whose
+        v0 squared distance is finite and <= max_dist2; init (KNN_QUERY_INIT_KEYS): = instead of +=."""
+        _check(count_within_masked_c()(self._h, int(slot), int(m), ctypes.c_void_p(int(queries_dev)), float(max_dist2),
+                                       ctypes.c_void_p(int(mask_dev)), ctypes.c_void_p(int(counts_dev)), ctypes.c_void_p(stream),
+                                       (QUERY_INIT_KEYS if init else 0) | int(flags)))
+
+    def query_topk_masked_host(self, queries, K, mask, max_dist2=float("inf")):
+        """Synchronous masked top-K of this shard alone, mask: the uint32 words on the host: (indices int32 [m][K], dist2 float32
+        [m][K] with +INF in padding, counts int32 [m]: the entries of each list that are not padding)."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1)
+        w = np.ascontiguousarray(mask, dtype=np.uint32).reshape(-1)
+        if w.size != mask_words(self.n):
+            raise ValueError("mask: expected %d words, got %d" % (mask_words(self.n), w.size))
+        m = q.size // self.k
+        idx = np.empty((m, int(K)), dtype=np.int32)
+        d2 = np.empty((m, int(K)), dtype=np.float32)
+        counts = np.empty(m, dtype=np.int32)
+        wp = w.ctypes.data_as(ctypes.c_void_p) if w.size else (ctypes.c_uint * 1)()
+        _check(query_topk_masked_host_c()(self._h, m, int(K), q.ctypes.data_as(ctypes.c_void_p), float(max_dist2), wp,
+                                          idx.ctypes.data_as(ctypes.c_void_p), d2.ctypes.data_as(ctypes.c_void_p),
+                                          counts.ctypes.data_as(ctypes.c_void_p)))
         return idx, d2, counts
 
     def query_topk_host(self, queries, K):

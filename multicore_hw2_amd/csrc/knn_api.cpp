@@ -9,6 +9,7 @@
 #include "../../include/knn_mi355x.h"
 #include "knn_common.h"
 #include "knn_radix_pick.h"
+#include "knn_mask_split.h"
 
 #include <limits.h>
 #include <math.h>
@@ -326,6 +327,8 @@ struct knn_index {
         size_t count_bytes = 0;
         u64 *large = nullptr;      // knn_index_query_topk_large: what knn_topk_large_plan says (histograms, select state, a fold's lists)
         size_t large_bytes = 0;
+        u64 *mask = nullptr;       // the masked calls: what knn_masked_plan says (the prefix of the granules' admitted rows, their counts)
+        size_t mask_bytes = 0;
     } topk[KNN_SLOTS];
     // Calls on one index from several host threads are serialised (enqueueing a batch is ~20 us of host work; the GPU
     // work of different slots still overlaps): the workspaces' lazily grown buffers, the event list, the statistics and
@@ -810,6 +813,7 @@ void knn_index_destroy(knn_index *idx)
             (void)knn_dev_free(t.lists);
             (void)knn_dev_free(t.count);
             (void)knn_dev_free(t.large);
+            (void)knn_dev_free(t.mask);
         }
         knn_dev_free_end_synced();
         for (auto &ev : idx->events) {
@@ -1634,6 +1638,188 @@ int knn_debug_radix_kth(const unsigned long long *keys, long long n, int K, unsi
     return KNN_OK;
 }
 
+// ---- queries over a subset of the rows (include/knn_mi355x.h 2g; knn_masked.hip) ------------------------------------------------
+// (one message per rule, in the header's order, the index last, as knn_index_count_within: tests/test_masked_logic.py tells them
+// apart without a GPU)
+int knn_index_query_topk_masked(knn_index *idx, int slot, int m, int K, const float *queries_dev, float max_dist2,
+                                const unsigned *mask_dev, unsigned long long *keys_dev, int *indices_dev, void *stream, unsigned flags)
+{
+    if (!(max_dist2 >= 0.0f))
+        return fail(KNN_EINVAL, "knn_index_query_topk_masked: max_dist2 must be >= 0 and not NaN");
+    if ((flags & ~(unsigned)KNN_QUERY_INIT_KEYS) != 0u)
+        return fail(KNN_EINVAL, "knn_index_query_topk_masked: unknown flag (KNN_QUERY_INIT_KEYS alone is admitted)");
+    if (slot < 0 || slot >= KNN_SLOTS)
+        return fail(KNN_EINVAL, "knn_index_query_topk_masked: slot outside 0 .. 7");
+    if (m < 1)
+        return fail(KNN_EINVAL, "knn_index_query_topk_masked: m < 1");
+    if (K < 1 || K > KNN_TOPK_MAX)
+        return fail(KNN_EINVAL, "knn_index_query_topk_masked: K outside 1 .. 64");
+    if ((long long)m * K > INT_MAX)
+        return fail(KNN_EINVAL, "knn_index_query_topk_masked: m * K above INT_MAX");
+    if (!queries_dev || !mask_dev || !keys_dev)
+        return fail(KNN_EINVAL, "knn_index_query_topk_masked: null queries, mask or keys");
+    if (!idx)
+        return fail(KNN_EINVAL, "knn_index_query_topk_masked: null index");
+    std::lock_guard<std::recursive_mutex> lock(idx->mu);
+    DeviceGuard guard(idx->device);
+    if (!guard.ok)
+        return fail(KNN_EHIP, "knn_index_query_topk_masked: hipSetDevice failed");
+    // (-0 counts as 0)
+    TopkCall call = topk_call_of(m, K, queries_dev, keys_dev, stream, max_dist2 == 0.0f ? 0.0f : max_dist2);
+    call.init = (flags & KNN_QUERY_INIT_KEYS) != 0u;
+    hipStream_t s = call.stream;
+    const int mk = m * K;
+    // one way on every index: no layout is consulted
+    idx->stats[0] = 1;
+    idx->stats[1] = 0;
+    idx->stats[2] = 0;
+    idx->stats[3] = 0;
+    idx->grid_topk_gate = nullptr;
+    idx->last_slot = slot;
+    if (idx->n > 0) {   // (an empty shard adds nothing)
+        call.k = idx->k;
+        call.n = idx->n;
+        call.base = idx->base;
+        // a cell-range shard's keys carry its rows' global numbers (gids); an index-range shard's base + row
+        call.gids = idx->sharded && idx->filter.cells ? idx->filter.cells->gids : nullptr;
+        call.r = idx->refs;
+        call.num_cu = idx->num_cu;
+        // the slot's scratch, grown before the first launch
+        const MaskedPlan plan = knn_masked_plan(idx->k, m, K, idx->n, idx->num_cu, call.init != 0);
+        knn_index::TopkSlot &ts = idx->topk[slot];
+        KNN_TRY(slot_buffer_grow(ts.mask, ts.mask_bytes, plan.mask_bytes));
+        KNN_TRY(slot_buffer_grow(ts.part, ts.part_bytes, plan.part_bytes));
+        call.part = ts.part;
+        call.part_bytes = ts.part_bytes;
+        EventPair *ev = nullptr;
+        KNN_TRY(next_event_pair(idx, false, &ev));
+        call.ev0 = ev ? ev->first : nullptr;
+        call.ev1 = ev ? ev->second : nullptr;
+        HIP_TRY(knn_masked_topk_launch(call, plan, mask_dev, ts.mask));
+    } else if (call.init) {
+        HIP_TRY(knn_keys_fill_launch(call.keys, mk, s));
+    }
+    if (indices_dev)
+        HIP_TRY(knn_keys_unpack_launch(call.keys, mk, indices_dev, s));
+    return KNN_OK;
+}
+
+int knn_index_count_within_masked(knn_index *idx, int slot, int m, const float *queries_dev, float max_dist2,
+                                  const unsigned *mask_dev, unsigned *counts_dev, void *stream, unsigned flags)
+{
+    if (!(max_dist2 >= 0.0f))
+        return fail(KNN_EINVAL, "knn_index_count_within_masked: max_dist2 must be >= 0 and not NaN");
+    if ((flags & ~(unsigned)KNN_QUERY_INIT_KEYS) != 0u)
+        return fail(KNN_EINVAL, "knn_index_count_within_masked: unknown flag (KNN_QUERY_INIT_KEYS alone is admitted)");
+    if (slot < 0 || slot >= KNN_SLOTS)
+        return fail(KNN_EINVAL, "knn_index_count_within_masked: slot outside 0 .. 7");
+    if (m < 1)
+        return fail(KNN_EINVAL, "knn_index_count_within_masked: m < 1");
+    if (!queries_dev || !mask_dev || !counts_dev)
+        return fail(KNN_EINVAL, "knn_index_count_within_masked: null queries, mask or counts");
+    if (!idx)
+        return fail(KNN_EINVAL, "knn_index_count_within_masked: null index");
+    std::lock_guard<std::recursive_mutex> lock(idx->mu);
+    DeviceGuard guard(idx->device);
+    if (!guard.ok)
+        return fail(KNN_EHIP, "knn_index_count_within_masked: hipSetDevice failed");
+    CountCall call;
+    call.k = idx->k;
+    call.m = m;
+    call.n = idx->n;
+    call.q = queries_dev;
+    call.r = idx->refs;
+    call.counts = counts_dev;
+    call.max_dist2 = max_dist2 == 0.0f ? 0.0f : max_dist2;   // (-0 counts as 0)
+    call.num_cu = idx->num_cu;
+    call.stream = (hipStream_t)stream;
+    hipStream_t s = call.stream;
+    idx->stats[0] = 1;
+    idx->stats[1] = 0;
+    idx->stats[2] = 0;
+    idx->stats[3] = 0;
+    idx->grid_topk_gate = nullptr;
+    idx->last_slot = slot;
+    // the scan ADDS to the caller's counts: an init call zeroes them first
+    if ((flags & KNN_QUERY_INIT_KEYS) != 0u)
+        HIP_TRY(hipMemsetAsync(counts_dev, 0, (size_t)m * sizeof(unsigned), s));
+    if (idx->n == 0)   // an empty shard adds nothing
+        return KNN_OK;
+    const MaskedPlan plan = knn_masked_plan(idx->k, m, 0, idx->n, idx->num_cu, (flags & KNN_QUERY_INIT_KEYS) != 0u);
+    knn_index::TopkSlot &ts = idx->topk[slot];
+    KNN_TRY(slot_buffer_grow(ts.mask, ts.mask_bytes, plan.mask_bytes));
+    EventPair *ev = nullptr;
+    KNN_TRY(next_event_pair(idx, false, &ev));
+    call.ev0 = ev ? ev->first : nullptr;
+    call.ev1 = ev ? ev->second : nullptr;
+    HIP_TRY(knn_masked_count_launch(call, plan, mask_dev, ts.mask));
+    return KNN_OK;
+}
+
+int knn_mask_set_rows(int device, long long n_local, const unsigned *rows_dev, long long count, int value, unsigned *mask_dev,
+                      void *stream)
+{
+    if (n_local < 0)
+        return fail(KNN_EINVAL, "knn_mask_set_rows: n_local < 0");
+    if (count < 0)
+        return fail(KNN_EINVAL, "knn_mask_set_rows: count < 0");
+    if (value != 0 && value != 1)
+        return fail(KNN_EINVAL, "knn_mask_set_rows: value is 0 (clear) or 1 (set)");
+    if ((count > 0 && !rows_dev) || !mask_dev)
+        return fail(KNN_EINVAL, "knn_mask_set_rows: null rows or mask");
+    DeviceGuard guard(device);
+    if (!guard.ok)
+        return fail(KNN_EHIP, "knn_mask_set_rows: hipSetDevice failed");
+    HIP_TRY(knn_mask_set_rows_launch(n_local, rows_dev, count, value, mask_dev, (hipStream_t)stream));
+    return KNN_OK;
+}
+
+int knn_debug_masked_plan(const long long in[6], long long out[8])
+{
+    if (!in || !out || in[0] < 1 || in[0] > INT_MAX || in[1] < 1 || in[1] > INT_MAX || in[2] < 0 || in[2] > KNN_TOPK_MAX ||
+        in[1] * in[2] > INT_MAX || in[3] < 0 || in[3] > (1ll << 32) || in[4] < 1 || in[4] > INT_MAX || (in[5] != 0 && in[5] != 1))
+        return fail(KNN_EINVAL, "knn_debug_masked_plan: bad arguments (k >= 1, m >= 1, 0 <= K <= 64, m * K <= INT_MAX, 0 <= rows <= 2^32, "
+                                "CUs >= 1, init 0 or 1)");
+    const MaskedPlan p = knn_masked_plan((int)in[0], (int)in[1], (int)in[2], in[3], (int)in[4], in[5] != 0);
+    const long long v[8] = {p.granules, p.slices, p.chunks, (long long)p.lds_bytes, (long long)p.mask_bytes, (long long)p.part_bytes,
+                            p.launches, p.chunk_m};
+    memcpy(out, v, sizeof v);
+    return KNN_OK;
+}
+
+int knn_debug_mask_split(const unsigned *granule_counts, long long granules, int slices, long long *first_granule)
+{
+    if (granules < 0 || granules > (1ll << 22) || (granules > 0 && !granule_counts) || slices < 1 || slices > 65535 || !first_granule)
+        return fail(KNN_EINVAL, "knn_debug_mask_split: bad arguments (0 <= granules <= 2^22, 1 <= slices <= 65535)");
+    // the device sequence: the exclusive 64-bit prefix of the counts, then every block's search over it
+    std::vector<u64> P((size_t)granules + 1, 0ull);
+    for (long long g = 0; g < granules; ++g)
+        P[(size_t)g + 1] = P[(size_t)g] + granule_counts[g];
+    if (P[(size_t)granules] >= (1ull << 48))   // (T * S must stay below 2^64; a shard's rows are far below)
+        return fail(KNN_EINVAL, "knn_debug_mask_split: more than 2^48 admitted rows");
+    for (int b = 0; b <= slices; ++b)
+        first_granule[b] = knn_mask_split_first(P.data(), granules, (u64)slices, (u64)b);
+    return KNN_OK;
+}
+
+int knn_debug_mask_split_rows(const unsigned *mask_host, long long n_local, int slices, long long *first_row)
+{
+    if (n_local < 0 || n_local > (1ll << 32) || (n_local > 0 && !mask_host) || slices < 1 || slices > 65535 || !first_row)
+        return fail(KNN_EINVAL, "knn_debug_mask_split_rows: bad arguments (0 <= n_local <= 2^32, 1 <= slices <= 65535)");
+    // the device sequence: every granule's admitted rows, their exclusive 64-bit prefix, then every block's cut
+    const long long G = (n_local + KNN_MASK_GRANULE_ROWS - 1) / KNN_MASK_GRANULE_ROWS;
+    std::vector<u64> P((size_t)G + 1, 0ull);
+    for (long long g = 0; g < G; ++g) {
+        u64 c = 0ull;
+        for (int j = 0; j < KNN_MASK_GRANULE_WORDS; ++j)
+            c += (unsigned)__builtin_popcount(knn_mask_word(mask_host, n_local, g * KNN_MASK_GRANULE_WORDS + j));
+        P[(size_t)g + 1] = P[(size_t)g] + c;
+    }
+    for (int b = 0; b <= slices; ++b)
+        first_row[b] = knn_mask_split_row(mask_host, n_local, P.data(), G, (u64)slices, (u64)b);
+    return KNN_OK;
+}
+
 int knn_debug_filter_scores(knn_index *idx, int m, const float *queries_dev, float *scores_dev,
                             float *qnorm_dev, double consts[8])
 {
@@ -2168,6 +2354,70 @@ extern "C" int knn_index_query_topk_large_host(knn_index *idx, int m, int K, con
         e = hipMemcpy(keys.data(), keys_dev, mk * sizeof(u64), hipMemcpyDeviceToHost);
         if (e != hipSuccess)
             return fail(KNN_EHIP, "knn_index_query_topk_large_host: D2H keys", hipGetErrorString(e));
+        // (not declared waited: the buffers go back after the device-wide wait `stage` then makes itself, as the top-K's)
+    }
+    for (size_t i = 0; i < mk; ++i) {
+        indices_host[i] = (int)(unsigned)(keys[i] & 0xFFFFFFFFull);
+        if (dist2_host) {
+            const unsigned hi = (unsigned)(keys[i] >> 32);
+            memcpy(&dist2_host[i], &hi, sizeof hi);
+        }
+    }
+    if (counts_host)
+        for (int j = 0; j < m; ++j) {   // padding is KNN_KEY_INIT; a real key is below it
+            int c = 0;
+            while (c < K && keys[(size_t)j * K + c] < kKeyInit)
+                ++c;
+            counts_host[j] = c;
+        }
+    return KNN_OK;
+}
+
+extern "C" int knn_index_query_topk_masked_host(knn_index *idx, int m, int K, const float *queries_host, float max_dist2,
+                                                const unsigned *mask_host, int *indices_host, float *dist2_host, int *counts_host)
+{
+    if (!(max_dist2 >= 0.0f))
+        return fail(KNN_EINVAL, "knn_index_query_topk_masked_host: max_dist2 must be >= 0 and not NaN");
+    if (m < 1)
+        return fail(KNN_EINVAL, "knn_index_query_topk_masked_host: m < 1");
+    if (K < 1 || K > KNN_TOPK_MAX)
+        return fail(KNN_EINVAL, "knn_index_query_topk_masked_host: K outside 1 .. 64");
+    if ((long long)m * K > INT_MAX)
+        return fail(KNN_EINVAL, "knn_index_query_topk_masked_host: m * K above INT_MAX");
+    if (!queries_host || !mask_host || !indices_host)
+        return fail(KNN_EINVAL, "knn_index_query_topk_masked_host: null queries, mask or indices");
+    if (!idx)
+        return fail(KNN_EINVAL, "knn_index_query_topk_masked_host: null index");
+    std::lock_guard<std::recursive_mutex> lock(idx->mu);
+    DeviceGuard guard(idx->device);
+    if (!guard.ok)
+        return fail(KNN_EHIP, "knn_index_query_topk_masked_host: hipSetDevice failed");
+    const size_t mk = (size_t)m * (size_t)K;
+    std::vector<u64> keys(mk);
+    {
+        Staging stage(idx->device);
+        float *q_dev = nullptr;
+        u64 *keys_dev = nullptr;
+        unsigned *mask_dev = nullptr;
+        const size_t qbytes = (size_t)m * (size_t)idx->k * sizeof(float);
+        const size_t mbytes = std::max<size_t>((size_t)((idx->n + 31) / 32), 1) * sizeof(unsigned);   // (an empty shard: one word, unread)
+        hipError_t e = stage.get(&q_dev, qbytes);
+        if (e == hipSuccess)
+            e = stage.get(&keys_dev, mk * sizeof(u64));
+        if (e == hipSuccess)
+            e = stage.get(&mask_dev, mbytes);
+        if (e == hipSuccess)
+            e = hipMemcpy(q_dev, queries_host, qbytes, hipMemcpyHostToDevice);
+        if (e == hipSuccess && idx->n > 0)
+            e = hipMemcpy(mask_dev, mask_host, mbytes, hipMemcpyHostToDevice);
+        if (e != hipSuccess)
+            return fail(KNN_EHIP, "knn_index_query_topk_masked_host: staging queries and mask", hipGetErrorString(e));
+        const int rc = knn_index_query_topk_masked(idx, 0, m, K, q_dev, max_dist2, mask_dev, keys_dev, nullptr, nullptr, KNN_QUERY_INIT_KEYS);
+        if (rc != KNN_OK)
+            return rc;
+        e = hipMemcpy(keys.data(), keys_dev, mk * sizeof(u64), hipMemcpyDeviceToHost);
+        if (e != hipSuccess)
+            return fail(KNN_EHIP, "knn_index_query_topk_masked_host: D2H keys", hipGetErrorString(e));
         // (not declared waited: the buffers go back after the device-wide wait `stage` then makes itself, as the top-K's)
     }
     for (size_t i = 0; i < mk; ++i) {

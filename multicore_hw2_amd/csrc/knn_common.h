@@ -257,6 +257,34 @@ TopkLargePlan knn_topk_large_plan(int k, int m, int K, long long n, int num_cu, 
 hipError_t knn_topk_large_launch(const TopkCall &c, const TopkLargePlan &p, const unsigned **tie_word);
 // b[j] <- the K smallest of a[j] and b[j] (sorted lists of K <= KNN_TOPK_LARGE_MAX keys), sorted, in place: one block per query.
 hipError_t knn_topk_merge_large_launch(int m, int K, const u64 *a, u64 *b, hipStream_t stream);
+// ---- queries over a subset of the rows (knn_masked.hip; DESIGN §4.6 "Over a subset of the rows") --------------------------------
+// The slices of the exact top-K scan for one chunk of mc queries (knn_exact.hip's rule, what knn_topk_part_bytes sizes `part` by).
+long long knn_topk_slices(int mc, int K, long long n, int num_cu);
+// keys[q] <- the K smallest of (keys[q] unless init, lists[0][q] .. lists[nl - 1][q]), sorted: knn_topk_select_kernel, the fold of
+// a scan's per-slice lists [nl][m][K].
+hipError_t knn_topk_select_launch(const u64 *lists, int nl, int m, int K, u64 *keys, int init, hipStream_t stream);
+// Everything one masked call launches with and the slot's scratch it needs: the one place both are decided
+// (knn_debug_masked_plan shows it).  K = 0: a count call.  The mask scratch: the prefix P [granules + 1] u64, then the granules'
+// admitted rows [granules] unsigned.
+struct MaskedPlan {
+    long long granules = 0;          // ceil(n / 1024)
+    long long slices = 0;            // blocks along the rows for the first chunk of queries: the unmasked exact scan's number
+    int chunks = 0, chunk_m = 0;     // launch sequences of <= KNN_TOPK_CHUNK queries; queries of the first
+    size_t lds_bytes = 0;            // dynamic LDS of the scan: the top-K's sorted columns [K][64] u64; a count has none
+    size_t counts_off = 0, mask_bytes = 0;   // where the granule counts start in the mask scratch; its bytes
+    size_t part_bytes = 0;           // the top-K scan's per-slice lists (knn_topk_part_bytes); a count has none
+    long long launches = 0;          // kernel launches of an init call: granule counts, prefix, per chunk the scan (and the select)
+};
+MaskedPlan knn_masked_plan(int k, int m, int K, long long n, int num_cu, bool init);
+// c.keys[m][K] <- the K smallest of (keys unless c.init, the rows of the shard whose mask bit is set and whose v0 distance E is
+// finite and <= c.max_dist2), sorted, padded with KNN_KEY_INIT; 1 <= K <= KNN_TOPK_MAX.  mask: (c.n + 31) / 32 words, bit i % 32
+// of word i / 32 admits local row i.  scratch: p.mask_bytes; c.part: p.part_bytes; both stream-ordered.  c.n > 0.
+hipError_t knn_masked_topk_launch(const TopkCall &c, const MaskedPlan &p, const unsigned *mask, u64 *scratch);
+// c.counts[j] += the number of those rows.  c.n > 0.
+hipError_t knn_masked_count_launch(const CountCall &c, const MaskedPlan &p, const unsigned *mask, u64 *scratch);
+// The mask bits of rows[0 .. count) that lie in 0 .. n - 1 <- value (0 or 1).
+hipError_t knn_mask_set_rows_launch(long long n, const unsigned *rows, long long count, int value, unsigned *mask, hipStream_t stream);
+
 // ---- MFMA filter + exact re-rank (knn_filter.hip) ---------------------------
 // Device-side control words of one filter query (FilterState::ctl).
 enum {

@@ -1053,6 +1053,17 @@ long long topk_slices(int mc, int K, long long n, int num_cu)
 }
 }  // namespace
 
+long long knn_topk_slices(int mc, int K, long long n, int num_cu) { return topk_slices(mc, K, n, num_cu); }
+
+hipError_t knn_topk_select_launch(const u64 *lists, int nl, int m, int K, u64 *keys, int init, hipStream_t s)
+{
+    if (m <= 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(knn_topk_select_kernel, dim3((unsigned)m), dim3(KNN_WAVE), 0, s, lists, nl, m, K, keys, init,
+                       (const unsigned *)nullptr);
+    return hipGetLastError();
+}
+
 size_t knn_topk_part_bytes(int m, int K, long long n, int num_cu)
 {
     if (n <= 0 || m <= 0)

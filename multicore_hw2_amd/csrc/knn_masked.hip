@@ -1,0 +1,404 @@
+// knn_masked.hip — queries over a subset of the rows (include/knn_mi355x.h 2g; DESIGN §4.6 "Over a subset of the rows"):
+// knn_index_query_topk_masked, knn_index_count_within_masked, knn_mask_set_rows.
+//
+// The subset is a bit mask over the shard's local rows: bit i % 32 of word i / 32 admits row i.  The two scans are the skeletons of
+// knn_exact_topk_kernel<KC, true> and knn_exact_count_kernel<KC> (knn_exact.hip) — one wave per block, lanes = queries, rows as
+// wave-uniform scalar loads, v0's arithmetic — with one change in the row loop: the block walks the mask words of its slice, four
+// at a time, and visits the set bits of every non-zero word in ascending order.  The mask words, the bit positions and the row
+// addresses are wave-uniform: a zero word costs no row load, a set bit costs what a row costs the unmasked scan.  A granule of 1024 rows
+// that admits nothing is not walked at all: the walk jumps over runs of them through the prefix below.
+//
+// Slices hold equal numbers of ADMITTED rows (knn_mask_split.h).  A call first counts the admitted rows of every granule of 1024
+// rows and turns the counts into a 64-bit exclusive prefix (knn_counts_to_offsets_kernel); block b of S finds the granule its cut
+// falls into from the prefix by a binary search every lane performs identically, and the row inside it from that granule's 32
+// words — no host synchronisation, and S is the unmasked scan's number, so the slot's per-slice lists are sized as before.  A mask is the
+// caller's and may change between calls: nothing is kept.
+#include "knn_exact_dev.h"
+#include "knn_mask_split.h"
+
+#include <math.h>
+
+// counts[g] <- the admitted rows of granule g: one mask word per thread (bits at and beyond n dropped), a granule per 32 lanes.
+__global__ __launch_bounds__(KNN_BLOCK) void knn_mask_granule_counts_kernel(const unsigned *__restrict__ mask, long long n, long long G,
+                                                                           unsigned *__restrict__ counts)
+{
+    const long long w = (long long)blockIdx.x * KNN_BLOCK + threadIdx.x;
+    const unsigned v = knn_mask_word(mask, n, w);
+    unsigned c = (unsigned)__popc(v);
+#pragma unroll
+    for (int off = KNN_MASK_GRANULE_WORDS / 2; off > 0; off >>= 1)
+        c += __shfl_xor(c, off, KNN_MASK_GRANULE_WORDS);
+    const long long g = w / KNN_MASK_GRANULE_WORDS;
+    if ((threadIdx.x & (KNN_MASK_GRANULE_WORDS - 1)) == 0 && g < G)
+        counts[g] = c;
+}
+
+// The mask bit of every listed row in 0 .. n - 1 <- value: one atomic on the row's word (rows may repeat and share words).
+__global__ __launch_bounds__(KNN_BLOCK) void knn_mask_set_rows_kernel(long long n, const unsigned *__restrict__ rows, long long count,
+                                                                     int value, unsigned *__restrict__ mask)
+{
+    const long long stride = (long long)gridDim.x * KNN_BLOCK;
+    for (long long i = (long long)blockIdx.x * KNN_BLOCK + threadIdx.x; i < count; i += stride) {
+        const unsigned row = rows[i];
+        if ((long long)row >= n)
+            continue;
+        const unsigned bit = 1u << (row & 31u);
+        if (value)
+            atomicOr(&mask[row >> 5], bit);
+        else
+            atomicAnd(&mask[row >> 5], ~bit);
+    }
+}
+
+// A wave-uniform 64-bit value made scalar by name.
+__device__ __forceinline__ long long masked_uniform(long long v)
+{
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(unsigned long long)v);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((unsigned long long)v >> 32));
+    return (long long)(((unsigned long long)hi << 32) | lo);
+}
+
+// The block's rows [r0, r1): slice blockIdx.x of gridDim.x by admitted rows (knn_mask_split.h).  Every lane runs the same search
+// over the same prefix and the same words; the results are made scalar by name so that everything derived from them — mask words,
+// rows, addresses — stays scalar.
+__device__ __forceinline__ void masked_slice(const unsigned *__restrict__ mask, long long n, const u64 *__restrict__ P, int G,
+                                             long long &r0, long long &r1)
+{
+    const u64 S = gridDim.x, b = blockIdx.x;
+    r0 = masked_uniform(knn_mask_split_row(mask, n, P, G, S, b));
+    r1 = masked_uniform(knn_mask_split_row(mask, n, P, G, S, b + 1ull));
+}
+
+// Mask word wi with the bits of rows outside [r0, r1) dropped.
+__device__ __forceinline__ unsigned masked_clip(unsigned m, long long wi, long long r0, long long r1)
+{
+    const long long lo = r0 - wi * 32, hi = r1 - wi * 32;   // the word's bits [lo, hi) are rows of the slice
+    if (lo > 0)
+        m &= ~knn_mask_below(lo < 32 ? (int)lo : 32);
+    if (hi < 32)
+        m &= knn_mask_below(hi > 0 ? (int)hi : 0);
+    return m;
+}
+
+// row(i) for every admitted row i of [r0, r1), r1 <= n, ascending: the mask words that hold those rows, four at a time (groups
+// aligned to four words), the first and the last cut to the slice.  Where the walk enters a granule that admits nothing — the
+// prefix says so — it jumps behind the last of the empty granules that follow, found by a binary search over the prefix: a slice
+// that begins in front of a long empty stretch (slice 0 of a mask whose first admitted row is far into the shard) would otherwise
+// read that stretch word by word, and the whole launch would wait for it (measured: 0.75 ms for 340 empty granules).  Nothing
+// beyond the word of row r1 - 1 is read, no row outside the slice is visited.
+template <class F>
+__device__ __forceinline__ void masked_walk(const unsigned *__restrict__ mask, const u64 *__restrict__ P, int G, long long r0,
+                                            long long r1, F &&row)
+{
+    const long long wbeg = (r0 >> 5) & ~3ll, wend = (r1 + 31) >> 5;
+    for (long long w = wbeg; w < wend; w += 4) {
+        if ((w & (KNN_MASK_GRANULE_WORDS - 1)) == 0) {
+            const long long g = w / KNN_MASK_GRANULE_WORDS;   // below G: w is a word of the mask
+            const u64 here = P[g];
+            if (P[g + 1] == here) {
+                long long lo = g + 1, hi = G;   // the last granule number whose prefix is still `here` lies in [lo, hi]
+                while (lo < hi) {
+                    const long long mid = (lo + hi + 1) >> 1;
+                    if (P[mid] == here)
+                        lo = mid;
+                    else
+                        hi = mid - 1;
+                }
+                w = lo * KNN_MASK_GRANULE_WORDS - 4;   // granules g .. lo - 1 admit nothing
+                continue;
+            }
+        }
+        unsigned m0, m1, m2, m3;
+        if (w + 4 <= wend) {   // wave-uniform addresses -> scalar loads
+            m0 = mask[w];
+            m1 = mask[w + 1];
+            m2 = mask[w + 2];
+            m3 = mask[w + 3];
+        } else {
+            m0 = mask[w];
+            m1 = w + 1 < wend ? mask[w + 1] : 0u;
+            m2 = w + 2 < wend ? mask[w + 2] : 0u;
+            m3 = 0u;
+        }
+        if (w == wbeg || w + 4 >= wend) {   // the group holds the slice's first or last word
+            m0 = masked_clip(m0, w, r0, r1);
+            m1 = masked_clip(m1, w + 1, r0, r1);
+            m2 = masked_clip(m2, w + 2, r0, r1);
+            m3 = masked_clip(m3, w + 3, r0, r1);
+        }
+        if ((m0 | m1 | m2 | m3) == 0u)
+            continue;
+#pragma unroll 1
+        for (int j = 0; j < 4; ++j) {
+            unsigned word = j == 0 ? m0 : j == 1 ? m1 : j == 2 ? m2 : m3;
+            const long long row0 = (w + j) << 5;
+            while (word) {
+                const int bit = __builtin_ctz(word);   // find-first-set, then clear the lowest
+                word &= word - 1u;
+                row(row0 + bit);
+            }
+        }
+    }
+}
+
+// v0's distance of one row at the wave-uniform address r to the lane's query: knn_exact_topk_kernel's lines.
+template <int KC>
+__device__ __forceinline__ float masked_dist2(const float (&qv)[KC > 0 ? 16 * KC : 1], const float *__restrict__ qp,
+                                              const float *__restrict__ r, int k)
+{
+#pragma clang fp contract(off)
+    float acc = 0.0f;
+    if (KC > 0) {
+#pragma unroll
+        for (int c = 0; c < (KC > 0 ? KC : 1); ++c) {
+            const int rem = k - 16 * c;   // wave-uniform
+            if (rem >= 16) {
+                float rv[16];
+#pragma unroll
+                for (int j = 0; j < 16; ++j)
+                    rv[j] = r[16 * c + j];   // wave-uniform address -> scalar loads
+#pragma unroll
+                for (int j = 0; j < 16; ++j) {
+                    const float diff = qv[16 * c + j] - rv[j];
+                    const float sq = diff * diff;
+                    acc = acc + sq;
+                }
+            } else if (rem > 0) {
+#pragma unroll
+                for (int j = 0; j < 15; ++j)
+                    if (j < rem) {
+                        const float diff = qv[16 * c + j] - r[16 * c + j];
+                        const float sq = diff * diff;
+                        acc = acc + sq;
+                    }
+            }
+        }
+    } else {
+        for (int d = 0; d < k; ++d) {
+            const float diff = qp[d] - r[d];
+            const float sq = diff * diff;
+            acc = acc + sq;
+        }
+    }
+    return acc;
+}
+
+// knn_masked_topk_kernel<KC> — knn_exact_topk_kernel<KC, true> over the admitted rows of the block's slice: the sorted LDS column,
+// the K-th key in a register and the min(column[K - 1], lim) rule as there (lim = KNN_KEY_INIT: no radius).  An empty slice writes
+// a padding list.  grid = (slices, query groups of 64).
+template <int KC>
+__global__ __launch_bounds__(KNN_WAVE) void knn_masked_topk_kernel(const float *__restrict__ Q, const float *__restrict__ R, int k,
+                                                                  int m, long long n, int K, const unsigned *__restrict__ mask,
+                                                                  const u64 *__restrict__ P, int G, long long base,
+                                                                  const unsigned *__restrict__ gids, u64 *__restrict__ part, u64 lim)
+{
+#pragma clang fp contract(off)
+    extern __shared__ u64 masked_lst[];   // [K][KNN_WAVE]
+    constexpr int KM = KC > 0 ? 16 * KC : 1;
+    const int lane = threadIdx.x;
+    const int q = blockIdx.y * KNN_WAVE + lane;
+    const int qa = min(q, m - 1);
+    float qv[KM];
+#pragma unroll
+    for (int d = 0; d < KM; ++d)
+        qv[d] = KC > 0 && d < k ? Q[(size_t)qa * k + d] : 0.0f;
+    for (int t = 0; t < K; ++t)
+        masked_lst[t * KNN_WAVE + lane] = kKeyInit;
+    u64 kth = lim < kKeyInit ? lim : kKeyInit;
+    const float *__restrict__ qp = Q + (size_t)qa * k;
+    long long r0, r1;
+    masked_slice(mask, n, P, G, r0, r1);
+    masked_walk(mask, P, G, r0, r1, [&](long long i) {
+        const float acc = masked_dist2<KC>(qv, qp, R + (size_t)i * k, k);
+        const u64 key = pack_key(acc, (unsigned)i);
+        if (key < kth) {
+            int p = K - 1;
+            while (p > 0) {
+                const u64 prev = masked_lst[(p - 1) * KNN_WAVE + lane];
+                if (prev < key)
+                    break;
+                masked_lst[p * KNN_WAVE + lane] = prev;
+                --p;
+            }
+            masked_lst[p * KNN_WAVE + lane] = key;
+            kth = masked_lst[(K - 1) * KNN_WAVE + lane];
+            kth = kth < lim ? kth : lim;
+        }
+    });
+    if (q >= m)
+        return;
+    u64 *__restrict__ out = part + ((size_t)blockIdx.x * m + q) * K;
+    for (int t = 0; t < K; ++t) {
+        const u64 key = masked_lst[t * KNN_WAVE + lane];
+        const unsigned row = (unsigned)key;
+        const bool real = (key >> 32) < 0x7F800000ull;
+        const unsigned g = gids ? (real ? gids[row] : 0u) : (unsigned)(base + (long long)row);
+        out[t] = real ? ((key & 0xFFFFFFFF00000000ull) | (u64)g) : kKeyInit;
+    }
+}
+
+// knn_masked_count_kernel<KC> — knn_exact_count_kernel<KC> over the admitted rows of the block's slice: one counter per lane, one
+// atomicAdd at the end when it is not zero.
+template <int KC>
+__global__ __launch_bounds__(KNN_WAVE) void knn_masked_count_kernel(const float *__restrict__ Q, const float *__restrict__ R, int k,
+                                                                   int m, long long n, const unsigned *__restrict__ mask,
+                                                                   const u64 *__restrict__ P, int G, float max_dist2,
+                                                                   unsigned *__restrict__ counts)
+{
+#pragma clang fp contract(off)
+    constexpr int KM = KC > 0 ? 16 * KC : 1;
+    const int lane = threadIdx.x;
+    const int q = blockIdx.y * KNN_WAVE + lane;
+    const int qa = min(q, m - 1);
+    float qv[KM];
+#pragma unroll
+    for (int d = 0; d < KM; ++d)
+        qv[d] = KC > 0 && d < k ? Q[(size_t)qa * k + d] : 0.0f;
+    unsigned cnt = 0u;
+    const float *__restrict__ qp = Q + (size_t)qa * k;
+    long long r0, r1;
+    masked_slice(mask, n, P, G, r0, r1);
+    masked_walk(mask, P, G, r0, r1, [&](long long i) {
+        const float acc = masked_dist2<KC>(qv, qp, R + (size_t)i * k, k);
+        cnt += acc < INFINITY && acc <= max_dist2 ? 1u : 0u;   // (NaN fails both compares)
+    });
+    if (q < m && cnt != 0u)
+        atomicAdd(&counts[q], cnt);
+}
+
+MaskedPlan knn_masked_plan(int k, int m, int K, long long n, int num_cu, bool init)
+{
+    MaskedPlan p;
+    if (m <= 0)
+        return p;
+    p.chunk_m = m < KNN_TOPK_CHUNK ? m : KNN_TOPK_CHUNK;
+    p.chunks = knn_divup(m, KNN_TOPK_CHUNK);
+    if (n <= 0) {   // an empty shard: an init top-K fills the keys, everything else launches nothing
+        p.launches = K > 0 && init ? 1 : 0;
+        return p;
+    }
+    p.granules = (n + KNN_MASK_GRANULE_ROWS - 1) / KNN_MASK_GRANULE_ROWS;
+    p.slices = K > 0 ? knn_topk_slices(p.chunk_m, K, n, num_cu) : knn_count_slices(p.chunk_m, n, num_cu);
+    p.lds_bytes = K > 0 ? (size_t)K * KNN_WAVE * sizeof(u64) : 0;
+    p.counts_off = (size_t)(p.granules + 1) * sizeof(u64);
+    p.mask_bytes = p.counts_off + (((size_t)p.granules * sizeof(unsigned) + 7) & ~(size_t)7);
+    if (K > 0) {   // knn_topk_part_bytes sizes by the first chunk; the last, of fewer queries, may cut the rows finer
+        const int ml = m - (p.chunks - 1) * KNN_TOPK_CHUNK;
+        const size_t last = (size_t)knn_topk_slices(ml, K, n, num_cu) * (size_t)ml * (size_t)K * sizeof(u64);
+        p.part_bytes = std::max(knn_topk_part_bytes(m, K, n, num_cu), last);
+    }
+    p.launches = 2 + (long long)p.chunks * (K > 0 ? 2 : 1);
+    return p;
+}
+
+namespace {
+// counts and prefix of the call's mask into the slot's scratch: once per call, ahead of every chunk's scan
+hipError_t masked_prefix_launch(const MaskedPlan &p, long long n, const unsigned *mask, u64 *scratch, hipStream_t s)
+{
+    unsigned *counts = (unsigned *)((char *)scratch + p.counts_off);
+    const long long words = p.granules * KNN_MASK_GRANULE_WORDS;
+    hipLaunchKernelGGL(knn_mask_granule_counts_kernel, dim3((unsigned)knn_divup(words, KNN_BLOCK)), dim3(KNN_BLOCK), 0, s, mask, n,
+                       p.granules, counts);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess)
+        return e;
+    return knn_counts_to_offsets_launch(counts, (int)p.granules, scratch, s);
+}
+}  // namespace
+
+hipError_t knn_masked_topk_launch(const TopkCall &c, const MaskedPlan &p, const unsigned *mask, u64 *scratch)
+{
+    const int K = c.K;
+    hipStream_t s = c.stream;
+    if (c.m <= 0 || c.n <= 0 || K < 1 || K > KNN_TOPK_MAX || !mask || !scratch || p.granules > (1ll << 22))
+        return hipErrorInvalidValue;
+    hipError_t e = masked_prefix_launch(p, c.n, mask, scratch, s);
+    if (e != hipSuccess)
+        return e;
+    if (c.ev0 && (e = hipEventRecord(c.ev0, s)) != hipSuccess)
+        return e;
+    const u64 lim = c.limit_key();
+    for (int c0 = 0; c0 < c.m; c0 += KNN_TOPK_CHUNK) {
+        const int mc = c.m - c0 < KNN_TOPK_CHUNK ? c.m - c0 : KNN_TOPK_CHUNK;
+        const long long slices = knn_topk_slices(mc, K, c.n, c.num_cu);
+        if ((size_t)slices * (size_t)mc * (size_t)K * sizeof(u64) > c.part_bytes)
+            return hipErrorInvalidValue;
+        const dim3 grid((unsigned)slices, (unsigned)knn_divup(mc, KNN_WAVE)), block(KNN_WAVE);
+        const size_t lds = (size_t)K * KNN_WAVE * sizeof(u64);
+        const float *qc = c.q + (size_t)c0 * c.k;
+#define KNN_MASKED_TOPK(KCV)                                                                                                    \
+    hipLaunchKernelGGL(knn_masked_topk_kernel<KCV>, grid, block, lds, s, qc, c.r, c.k, mc, c.n, K, mask, (const u64 *)scratch, \
+                       (int)p.granules, c.base, c.gids, c.part, lim)
+        switch ((c.k + 15) / 16) {
+        case 1: KNN_MASKED_TOPK(1); break;
+        case 2: KNN_MASKED_TOPK(2); break;
+        case 3: KNN_MASKED_TOPK(3); break;
+        case 4: KNN_MASKED_TOPK(4); break;
+        case 5: KNN_MASKED_TOPK(5); break;
+        case 6: KNN_MASKED_TOPK(6); break;
+        case 7: KNN_MASKED_TOPK(7); break;
+        case 8: KNN_MASKED_TOPK(8); break;
+        default: KNN_MASKED_TOPK(0); break;
+        }
+#undef KNN_MASKED_TOPK
+        e = hipGetLastError();
+        if (e != hipSuccess)
+            return e;
+        e = knn_topk_select_launch(c.part, (int)slices, mc, K, c.keys + (size_t)c0 * K, c.init, s);
+        if (e != hipSuccess)
+            return e;
+    }
+    if (c.ev1 && (e = hipEventRecord(c.ev1, s)) != hipSuccess)
+        return e;
+    return hipSuccess;
+}
+
+hipError_t knn_masked_count_launch(const CountCall &c, const MaskedPlan &p, const unsigned *mask, u64 *scratch)
+{
+    hipStream_t s = c.stream;
+    if (c.m <= 0 || c.n <= 0 || !mask || !scratch || p.granules > (1ll << 22))
+        return hipErrorInvalidValue;
+    hipError_t e = masked_prefix_launch(p, c.n, mask, scratch, s);
+    if (e != hipSuccess)
+        return e;
+    if (c.ev0 && (e = hipEventRecord(c.ev0, s)) != hipSuccess)
+        return e;
+    for (int c0 = 0; c0 < c.m; c0 += KNN_TOPK_CHUNK) {
+        const int mc = c.m - c0 < KNN_TOPK_CHUNK ? c.m - c0 : KNN_TOPK_CHUNK;
+        const long long slices = knn_count_slices(mc, c.n, c.num_cu);
+        const dim3 grid((unsigned)slices, (unsigned)knn_divup(mc, KNN_WAVE)), block(KNN_WAVE);
+        const float *qc = c.q + (size_t)c0 * c.k;
+#define KNN_MASKED_COUNT(KCV)                                                                                                   \
+    hipLaunchKernelGGL(knn_masked_count_kernel<KCV>, grid, block, 0, s, qc, c.r, c.k, mc, c.n, mask, (const u64 *)scratch,     \
+                       (int)p.granules, c.max_dist2, c.counts + c0)
+        switch ((c.k + 15) / 16) {
+        case 1: KNN_MASKED_COUNT(1); break;
+        case 2: KNN_MASKED_COUNT(2); break;
+        case 3: KNN_MASKED_COUNT(3); break;
+        case 4: KNN_MASKED_COUNT(4); break;
+        case 5: KNN_MASKED_COUNT(5); break;
+        case 6: KNN_MASKED_COUNT(6); break;
+        case 7: KNN_MASKED_COUNT(7); break;
+        case 8: KNN_MASKED_COUNT(8); break;
+        default: KNN_MASKED_COUNT(0); break;
+        }
+#undef KNN_MASKED_COUNT
+        e = hipGetLastError();
+        if (e != hipSuccess)
+            return e;
+    }
+    if (c.ev1 && (e = hipEventRecord(c.ev1, s)) != hipSuccess)
+        return e;
+    return hipSuccess;
+}
+
+hipError_t knn_mask_set_rows_launch(long long n, const unsigned *rows, long long count, int value, unsigned *mask, hipStream_t s)
+{
+    if (count <= 0 || n <= 0)
+        return hipSuccess;
+    long long blocks = (count + KNN_BLOCK - 1) / KNN_BLOCK;
+    if (blocks > 8192)
+        blocks = 8192;
+    hipLaunchKernelGGL(knn_mask_set_rows_kernel, dim3((unsigned)blocks), dim3(KNN_BLOCK), 0, s, n, rows, count, value, mask);
+    return hipGetLastError();
+}
