@@ -431,7 +431,8 @@ int knn_debug_radix_kth(const unsigned long long *keys, long long n, int K, unsi
  * masked scan.  No layout is consulted, so grid, cell-sorted, per-cell-framed and sharded indexes all answer.  The scan walks the
  * mask words — a zero word skips 32 rows without touching them, an admitted row costs what a row costs the exact scan — and cuts
  * the shard into slices of equal numbers of ADMITTED rows, so a mask that admits one contiguous range is spread over the whole
- * device like any other.  The mask may change between calls: every call counts it anew. */
+ * device like any other.  The mask may change between calls: every call counts it anew.
+ * Lists within a radius and top-K beyond 64 over a mask: 2h. */
 int knn_index_query_topk_masked(knn_index *idx, int slot, int m, int K, const float *queries_dev, float max_dist2,
                                 const unsigned *mask_dev, unsigned long long *keys_dev /*[m][K]*/,
                                 int *indices_dev /*[m][K] or NULL*/, void *stream, unsigned flags);
@@ -455,6 +456,61 @@ int knn_index_query_topk_masked_host(knn_index *idx, int m, int K, const float *
 int knn_debug_masked_plan(const long long in[6], long long out[8]);
 int knn_debug_mask_split(const unsigned *granule_counts, long long granules, int slices, long long *first_granule /*[slices+1]*/);
 int knn_debug_mask_split_rows(const unsigned *mask_host, long long n_local, int slices, long long *first_row /*[slices+1]*/);
+
+/* ------------------------------------------------------------------------
+ * 2h. Lists within a radius and top-K beyond 64 over a subset of the rows: with 2g, every query kind the index answers — top-K up
+ * to 64, top-K up to 4096, count, list — respects a mask.
+ *
+ * The mask is 2g's, layout and lifetime: (n_local + 31) / 32 words, bit i % 32 of word i / 32 admits LOCAL row i, bits at and
+ * beyond n_local are ignored, borrowed for the call and counted anew on every call.  A row is a candidate only when its mask bit
+ * is set AND its v0 distance E is finite and E <= max_dist2 (fp32, dimension order, no FMA, equality inside, -0 counts as 0).
+ *
+ * knn_index_list_within_masked: the contract of knn_index_list_within (2e) with that candidate rule — the third step of
+ * knn_index_count_within_masked -> knn_counts_to_offsets -> this call -> knn_keys_sort_segments.  Keys carry the ORIGINAL global
+ * numbers (base_index + row, or the gid).  A hit reserves p = fill_dev[j]++ and is stored at keys_dev[offsets_dev[j] + p] only
+ * when p is below the segment's room; fill_dev[j] ends as its entry value plus this shard's admitted hits, stored or not; nothing
+ * is ever stored outside a segment; the order inside a segment is unspecified.  KNN_QUERY_INIT_KEYS zeroes fill_dev first;
+ * without it the call appends, so disjoint shards, each with its own mask, fold by calling one after the other.  An all-ones
+ * mask gives exactly the set of keys the unmasked call gives; an all-zero mask stores nothing and leaves fill_dev at its entry
+ * value.
+ *
+ * knn_index_query_topk_large_masked: the contract of knn_index_query_topk_large (2f) with that candidate rule.  1 <= K <=
+ * KNN_TOPK_LARGE_MAX, lists ascending and padded with KNN_KEY_INIT; without KNN_QUERY_INIT_KEYS the call folds into the K sorted
+ * keys held (the caller's, NOT clipped).  An all-ones mask gives knn_index_query_topk_large's keys bit for bit; for K <= 64 the
+ * keys equal knn_index_query_topk_masked's bit for bit on every input, NaN and overflowing rows and non-finite queries included.
+ * knn_index_last_stats reads [1, 0, t, 0], t = 1 when the index word's passes ran — some query's cut fell inside a class of
+ * equal distances among the ADMITTED rows.
+ *
+ * Flags: KNN_QUERY_INIT_KEYS alone.  Argument errors are KNN_EINVAL, each with its own knn_last_error text, checked in this order
+ * — the first that fails speaks, nothing is launched —: max_dist2 < 0 or NaN, an unknown flag, a slot outside 0 .. 7, m < 1,
+ * (large) K outside 1 .. 4096, (large) m * K > INT_MAX, a null queries pointer, a null mask pointer, a null offsets, fill or keys
+ * pointer, a null index.  Asynchronous on `stream`; slots as for every other query; these calls may follow or precede any other
+ * call on a slot.  One way on every index (DESIGN §4.6 "Lists and large K over a subset of the rows"): no layout is consulted, so
+ * grid, cell-sorted, per-cell-framed and sharded indexes all answer.  An empty shard appends nothing, or leaves the keys alone
+ * (writes padding under the init flag). */
+int knn_index_list_within_masked(knn_index *idx, int slot, int m, const float *queries_dev, float max_dist2,
+                                 const unsigned *mask_dev, const unsigned long long *offsets_dev /*[m+1]*/,
+                                 unsigned *fill_dev /*[m]*/, unsigned long long *keys_dev, void *stream, unsigned flags);
+int knn_index_query_topk_large_masked(knn_index *idx, int slot, int m, int K, const float *queries_dev, float max_dist2,
+                                      const unsigned *mask_dev, unsigned long long *keys_dev /*[m][K]*/,
+                                      int *indices_dev /*[m][K] or NULL*/, void *stream, unsigned flags);
+/* Synchronous, this shard alone; mask_host: the words on the host.  The list call runs masked count -> offsets -> masked list ->
+ * sort and returns malloc'd arrays as knn_index_list_within_host does (a 1-entry allocation when the total is 0; the caller
+ * frees them); the large call mirrors knn_index_query_topk_large_host.  dist2 / counts outputs may be NULL. */
+int knn_index_list_within_masked_host(knn_index *idx, int m, const float *queries_host, float max_dist2,
+                                      const unsigned *mask_host, long long *offsets_host /*[m+1]*/,
+                                      int **indices_out, float **dist2_out /*NULL ok*/);
+int knn_index_query_topk_large_masked_host(knn_index *idx, int m, int K, const float *queries_host, float max_dist2,
+                                           const unsigned *mask_host, int *indices_host, float *dist2_host /*NULL ok*/,
+                                           int *counts_host /*NULL ok*/);
+/* Test hook, host arithmetic only.  in = {k, m, K (0 = a list call), rows, CUs, 1 if init}; out = {granules of 1024 rows, blocks
+ * along the rows of the first chunk's scan (a list call: the masked count's slices; a large call: the select's), waves per block
+ * that each take their own admitted-row slice (1; KNN_SELECT_WAVES = 8 for the select passes), chunks of 65536 queries, LDS bytes
+ * of the scan, bytes of the slot's mask scratch, bytes of the slot's select scratch (0 for a list call), launches of an init call
+ * whose index passes stay gated off: granule counts, prefix, then per chunk the list scan — or what knn_debug_topk_large_plan
+ * counts for a call without ties, the state's memset included}.  A list call's [0], [1], [3], [5] are knn_debug_masked_plan's
+ * [0], [1], [2], [4] for a count call on the same inputs: the count pass and the list pass cut the shard identically. */
+int knn_debug_masked_lists_plan(const long long in[6], long long out[8]);
 
 /* Tuning / test hooks.  Known names:
  *   "path"    0 = auto, 1 = exact VALU kernels only, 2 = force the MFMA filter

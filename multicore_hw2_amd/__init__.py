@@ -19,7 +19,9 @@ import numpy as np
 __all__ = ["lib", "lib_path", "cudaCallback", "KnnIndex", "KnnGeom", "KnnError", "KEY_INIT", "set_option",
            "get_option", "trim", "device_count", "EXPORTED_SYMBOLS", "shard_bounds", "keys_topk_merge", "counts_to_offsets",
            "keys_sort_segments", "keys_topk_merge_large", "debug_topk_large_plan", "debug_radix_kth", "TOPK_LARGE_MAX",
-           "mask_words", "mask_set_rows", "debug_masked_plan", "debug_mask_split", "debug_mask_split_rows"]
+           "mask_words", "mask_set_rows", "debug_masked_plan", "debug_mask_split", "debug_mask_split_rows",
+           "list_within_masked_c", "query_topk_large_masked_c", "list_within_masked_host_c", "query_topk_large_masked_host_c",
+           "debug_masked_lists_plan"]
 
 KEY_INIT = 0x7F80000000000000
 
@@ -42,6 +44,8 @@ EXPORTED_SYMBOLS = [
     "knn_debug_radix_kth",
     "knn_index_query_topk_masked", "knn_index_count_within_masked", "knn_mask_set_rows", "knn_index_query_topk_masked_host",
     "knn_debug_masked_plan", "knn_debug_mask_split", "knn_debug_mask_split_rows",
+    "knn_index_list_within_masked", "knn_index_list_within_masked_host", "knn_index_query_topk_large_masked",
+    "knn_index_query_topk_large_masked_host", "knn_debug_masked_lists_plan",
 ]
 TOPK_LARGE_MAX = 4096   # KNN_TOPK_LARGE_MAX
 QUERY_INIT_KEYS = 1   # KNN_QUERY_INIT_KEYS
@@ -590,6 +594,50 @@ def debug_mask_split_rows(mask, n_local, slices):
     return out
 
 
+def list_within_masked_c():
+    """knn_index_list_within_masked with its argument types (set here, not in lib(), as count_within_c)."""
+    f = lib().knn_index_list_within_masked
+    f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
+                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint]
+    return f
+
+
+def query_topk_large_masked_c():
+    """knn_index_query_topk_large_masked with its argument types (set here, not in lib(), as count_within_c)."""
+    f = lib().knn_index_query_topk_large_masked
+    f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p,
+                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint]
+    return f
+
+
+def list_within_masked_host_c():
+    f = lib().knn_index_list_within_masked_host
+    f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
+                  ctypes.POINTER(ctypes.POINTER(ctypes.c_int)), ctypes.POINTER(ctypes.POINTER(ctypes.c_float))]
+    return f
+
+
+def query_topk_large_masked_host_c():
+    f = lib().knn_index_query_topk_large_masked_host
+    f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
+                  ctypes.c_void_p, ctypes.c_void_p]
+    return f
+
+
+MASKED_LISTS_PLAN = ("granules", "slices", "slice_waves", "chunks", "lds_bytes", "mask_bytes", "select_bytes", "launches")
+
+
+def debug_masked_lists_plan(**inputs):
+    """knn_debug_masked_lists_plan: what a list_within_masked (K = 0) or query_topk_large_masked (K >= 1) call launches with and
+    the slot scratch it needs, for the inputs named in MASKED_PLAN_INPUTS.  Host arithmetic; works without a GPU."""
+    vin = (ctypes.c_longlong * len(MASKED_PLAN_INPUTS))(*[int(inputs[n]) for n in MASKED_PLAN_INPUTS])
+    out = (ctypes.c_longlong * len(MASKED_LISTS_PLAN))()
+    f = lib().knn_debug_masked_lists_plan
+    f.argtypes = [ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)]
+    _check(f(vin, out))
+    return dict(zip(MASKED_LISTS_PLAN, list(out)))
+
+
 def counts_to_offsets_c():
     f = lib().knn_counts_to_offsets
     f.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
@@ -882,6 +930,73 @@ class KnnIndex:
         _check(query_topk_masked_host_c()(self._h, m, int(K), q.ctypes.data_as(ctypes.c_void_p), float(max_dist2), wp,
                                           idx.ctypes.data_as(ctypes.c_void_p), d2.ctypes.data_as(ctypes.c_void_p),
                                           counts.ctypes.data_as(ctypes.c_void_p)))
+        return idx, d2, counts
+
+    def list_within_masked(self, m, queries_dev, max_dist2, mask_dev, offsets_dev, fill_dev, keys_dev, stream=0, slot=0, init=False,
+                           flags=0):
+        """Async (knn_index_list_within_masked): list_within over the rows the mask admits — every row of this shard whose bit is
+        set in mask_dev (uint32 [mask_words(n)], bit i % 32 of word i // 32 = local row i) and whose v0 squared distance to query j
+        is finite and <= max_dist2 reserves place p = fill_dev[j]++ and, when p is below the room of segment [offsets_dev[j],
+        offsets_dev[j + 1]), stores its packed key at keys_dev[offsets_dev[j] + p]; init (KNN_QUERY_INIT_KEYS): fill_dev is zeroed
+        first, else the call appends.  The third step of count_within_masked -> counts_to_offsets -> this -> keys_sort_segments.
+        flags: further flag bits as they are (every one of them raises)."""
+        _check(list_within_masked_c()(self._h, int(slot), int(m), ctypes.c_void_p(int(queries_dev)), float(max_dist2),
+                                      ctypes.c_void_p(int(mask_dev)), ctypes.c_void_p(int(offsets_dev)),
+                                      ctypes.c_void_p(int(fill_dev)), ctypes.c_void_p(int(keys_dev)), ctypes.c_void_p(stream),
+                                      (QUERY_INIT_KEYS if init else 0) | int(flags)))
+
+    def list_within_masked_host(self, queries, max_dist2, mask):
+        """Synchronous masked lists of this shard alone (knn_index_list_within_masked_host), mask: the uint32 words on the host:
+        (offsets int64 [m + 1], indices int32 [total], dist2 float32 [total]); query j's admitted rows, nearest first, are entries
+        offsets[j] .. offsets[j + 1] - 1."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1)
+        w = np.ascontiguousarray(mask, dtype=np.uint32).reshape(-1)
+        if w.size != mask_words(self.n):
+            raise ValueError("mask: expected %d words, got %d" % (mask_words(self.n), w.size))
+        m = q.size // self.k
+        offsets = np.empty(m + 1, dtype=np.int64)
+        ind, d2 = ctypes.POINTER(ctypes.c_int)(), ctypes.POINTER(ctypes.c_float)()
+        wp = w.ctypes.data_as(ctypes.c_void_p) if w.size else ctypes.cast((ctypes.c_uint * 1)(), ctypes.c_void_p)
+        _check(list_within_masked_host_c()(self._h, m, q.ctypes.data_as(ctypes.c_void_p), float(max_dist2), wp,
+                                           offsets.ctypes.data_as(ctypes.c_void_p), ctypes.byref(ind), ctypes.byref(d2)))
+        total = int(offsets[m])
+        free = ctypes.CDLL(None).free
+        free.argtypes = [ctypes.c_void_p]
+        try:
+            indices = np.ctypeslib.as_array(ind, shape=(max(total, 1),))[:total].astype(np.int32, copy=True)
+            dist2 = np.ctypeslib.as_array(d2, shape=(max(total, 1),))[:total].astype(np.float32, copy=True)
+        finally:
+            free(ind)
+            free(d2)
+        return offsets, indices, dist2
+
+    def query_topk_large_masked(self, m, K, queries_dev, mask_dev, keys_dev, max_dist2=float("inf"), stream=0, slot=0,
+                                init_keys=False, indices_dev=None, flags=0):
+        """Async (knn_index_query_topk_large_masked): query_topk_large over the rows the mask admits, 1 <= K <= 4096 —
+        keys_dev[m][K] <- the K smallest keys of (this shard's rows whose mask bit is set and whose v0 squared distance is finite
+        and <= max_dist2 and, unless init_keys, the K sorted keys per query keys_dev already holds, which are not clipped), sorted,
+        padded with KEY_INIT; keys carry the original global numbers.  One way on every index (last_stats()[0] == 1; [2] == 1: some
+        query's cut fell inside a class of equal distances).  flags: further flag bits as they are (every one of them raises)."""
+        _check(query_topk_large_masked_c()(self._h, int(slot), int(m), int(K), ctypes.c_void_p(int(queries_dev)), float(max_dist2),
+                                           ctypes.c_void_p(int(mask_dev)), ctypes.c_void_p(int(keys_dev)),
+                                           ctypes.c_void_p(int(indices_dev)) if indices_dev is not None else None,
+                                           ctypes.c_void_p(stream), (QUERY_INIT_KEYS if init_keys else 0) | int(flags)))
+
+    def query_topk_large_masked_host(self, queries, K, mask, max_dist2=float("inf")):
+        """Synchronous masked large top-K of this shard alone, mask: the uint32 words on the host: (indices int32 [m][K], dist2
+        float32 [m][K] with +INF in padding, counts int32 [m]: the entries of each list that are not padding)."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1)
+        w = np.ascontiguousarray(mask, dtype=np.uint32).reshape(-1)
+        if w.size != mask_words(self.n):
+            raise ValueError("mask: expected %d words, got %d" % (mask_words(self.n), w.size))
+        m = q.size // self.k
+        idx = np.empty((m, int(K)), dtype=np.int32)
+        d2 = np.empty((m, int(K)), dtype=np.float32)
+        counts = np.empty(m, dtype=np.int32)
+        wp = w.ctypes.data_as(ctypes.c_void_p) if w.size else ctypes.cast((ctypes.c_uint * 1)(), ctypes.c_void_p)
+        _check(query_topk_large_masked_host_c()(self._h, m, int(K), q.ctypes.data_as(ctypes.c_void_p), float(max_dist2), wp,
+                                                idx.ctypes.data_as(ctypes.c_void_p), d2.ctypes.data_as(ctypes.c_void_p),
+                                                counts.ctypes.data_as(ctypes.c_void_p)))
         return idx, d2, counts
 
     def query_topk_host(self, queries, K):

@@ -1820,6 +1820,152 @@ int knn_debug_mask_split_rows(const unsigned *mask_host, long long n_local, int 
     return KNN_OK;
 }
 
+// ---- lists and top-K beyond 64 over a subset of the rows (include/knn_mi355x.h 2h; knn_masked_lists.hip) ------------------------
+// (one message per rule, in the header's order, the index last: tests/test_masked_lists_logic.py tells them apart without a GPU)
+int knn_index_list_within_masked(knn_index *idx, int slot, int m, const float *queries_dev, float max_dist2, const unsigned *mask_dev,
+                                 const unsigned long long *offsets_dev, unsigned *fill_dev, unsigned long long *keys_dev, void *stream,
+                                 unsigned flags)
+{
+    if (!(max_dist2 >= 0.0f))
+        return fail(KNN_EINVAL, "knn_index_list_within_masked: max_dist2 must be >= 0 and not NaN");
+    if ((flags & ~(unsigned)KNN_QUERY_INIT_KEYS) != 0u)
+        return fail(KNN_EINVAL, "knn_index_list_within_masked: unknown flag (KNN_QUERY_INIT_KEYS alone is admitted)");
+    if (slot < 0 || slot >= KNN_SLOTS)
+        return fail(KNN_EINVAL, "knn_index_list_within_masked: slot outside 0 .. 7");
+    if (m < 1)
+        return fail(KNN_EINVAL, "knn_index_list_within_masked: m < 1");
+    if (!queries_dev)
+        return fail(KNN_EINVAL, "knn_index_list_within_masked: null queries");
+    if (!mask_dev)
+        return fail(KNN_EINVAL, "knn_index_list_within_masked: null mask");
+    if (!offsets_dev || !fill_dev || !keys_dev)
+        return fail(KNN_EINVAL, "knn_index_list_within_masked: null offsets, fill or keys");
+    if (!idx)
+        return fail(KNN_EINVAL, "knn_index_list_within_masked: null index");
+    std::lock_guard<std::recursive_mutex> lock(idx->mu);
+    DeviceGuard guard(idx->device);
+    if (!guard.ok)
+        return fail(KNN_EHIP, "knn_index_list_within_masked: hipSetDevice failed");
+    ListCall call;
+    call.k = idx->k;
+    call.m = m;
+    call.n = idx->n;
+    call.base = idx->base;
+    // a cell-range shard's keys carry its rows' global numbers (gids); an index-range shard's base + row
+    call.gids = idx->sharded && idx->filter.cells ? idx->filter.cells->gids : nullptr;
+    call.q = queries_dev;
+    call.r = idx->refs;
+    call.offsets = (const u64 *)offsets_dev;
+    call.fill = fill_dev;
+    call.keys = (u64 *)keys_dev;
+    call.max_dist2 = max_dist2 == 0.0f ? 0.0f : max_dist2;   // (-0 counts as 0)
+    call.num_cu = idx->num_cu;
+    call.stream = (hipStream_t)stream;
+    hipStream_t s = call.stream;
+    // one way on every index: no layout is consulted
+    idx->stats[0] = 1;
+    idx->stats[1] = 0;
+    idx->stats[2] = 0;
+    idx->stats[3] = 0;
+    idx->grid_topk_gate = nullptr;
+    idx->last_slot = slot;
+    // the scan APPENDS behind the caller's fill: an init call zeroes it first
+    if ((flags & KNN_QUERY_INIT_KEYS) != 0u)
+        HIP_TRY(hipMemsetAsync(fill_dev, 0, (size_t)m * sizeof(unsigned), s));
+    if (idx->n == 0)   // an empty shard appends nothing
+        return KNN_OK;
+    const MaskedListsPlan plan = knn_masked_lists_plan(idx->k, m, 0, idx->n, idx->num_cu, (flags & KNN_QUERY_INIT_KEYS) != 0u);
+    knn_index::TopkSlot &ts = idx->topk[slot];
+    KNN_TRY(slot_buffer_grow(ts.mask, ts.mask_bytes, plan.cut.mask_bytes));
+    EventPair *ev = nullptr;
+    KNN_TRY(next_event_pair(idx, false, &ev));
+    call.ev0 = ev ? ev->first : nullptr;
+    call.ev1 = ev ? ev->second : nullptr;
+    HIP_TRY(knn_masked_list_launch(call, plan, mask_dev, ts.mask));
+    return KNN_OK;
+}
+
+int knn_index_query_topk_large_masked(knn_index *idx, int slot, int m, int K, const float *queries_dev, float max_dist2,
+                                      const unsigned *mask_dev, unsigned long long *keys_dev, int *indices_dev, void *stream,
+                                      unsigned flags)
+{
+    if (!(max_dist2 >= 0.0f))
+        return fail(KNN_EINVAL, "knn_index_query_topk_large_masked: max_dist2 must be >= 0 and not NaN");
+    if ((flags & ~(unsigned)KNN_QUERY_INIT_KEYS) != 0u)
+        return fail(KNN_EINVAL, "knn_index_query_topk_large_masked: unknown flag (KNN_QUERY_INIT_KEYS alone is admitted)");
+    if (slot < 0 || slot >= KNN_SLOTS)
+        return fail(KNN_EINVAL, "knn_index_query_topk_large_masked: slot outside 0 .. 7");
+    if (m < 1)
+        return fail(KNN_EINVAL, "knn_index_query_topk_large_masked: m < 1");
+    if (K < 1 || K > KNN_TOPK_LARGE_MAX)
+        return fail(KNN_EINVAL, "knn_index_query_topk_large_masked: K outside 1 .. 4096");
+    if ((long long)m * K > INT_MAX)
+        return fail(KNN_EINVAL, "knn_index_query_topk_large_masked: m * K above INT_MAX");
+    if (!queries_dev)
+        return fail(KNN_EINVAL, "knn_index_query_topk_large_masked: null queries");
+    if (!mask_dev)
+        return fail(KNN_EINVAL, "knn_index_query_topk_large_masked: null mask");
+    if (!keys_dev)
+        return fail(KNN_EINVAL, "knn_index_query_topk_large_masked: null keys");
+    if (!idx)
+        return fail(KNN_EINVAL, "knn_index_query_topk_large_masked: null index");
+    std::lock_guard<std::recursive_mutex> lock(idx->mu);
+    DeviceGuard guard(idx->device);
+    if (!guard.ok)
+        return fail(KNN_EHIP, "knn_index_query_topk_large_masked: hipSetDevice failed");
+    // (-0 counts as 0)
+    TopkCall call = topk_call_of(m, K, queries_dev, keys_dev, stream, max_dist2 == 0.0f ? 0.0f : max_dist2);
+    call.init = (flags & KNN_QUERY_INIT_KEYS) != 0u;
+    hipStream_t s = call.stream;
+    const int mk = m * K;
+    // one way on every index: no layout is consulted
+    idx->stats[0] = 1;
+    idx->stats[1] = 0;
+    idx->stats[2] = 0;
+    idx->stats[3] = 0;
+    idx->grid_topk_gate = nullptr;
+    idx->last_slot = slot;
+    if (idx->n > 0) {   // (an empty shard adds nothing)
+        call.k = idx->k;
+        call.n = idx->n;
+        call.base = idx->base;
+        // a cell-range shard's keys carry its rows' global numbers (gids); an index-range shard's base + row
+        call.gids = idx->sharded && idx->filter.cells ? idx->filter.cells->gids : nullptr;
+        call.r = idx->refs;
+        call.num_cu = idx->num_cu;
+        // the slot's mask scratch and large scratch, grown before the first launch
+        const MaskedListsPlan plan = knn_masked_lists_plan(idx->k, m, K, idx->n, idx->num_cu, call.init != 0);
+        knn_index::TopkSlot &ts = idx->topk[slot];
+        KNN_TRY(slot_buffer_grow(ts.mask, ts.mask_bytes, plan.cut.mask_bytes));
+        KNN_TRY(slot_buffer_grow(ts.large, ts.large_bytes, plan.select_bytes));
+        call.part = ts.large;
+        call.part_bytes = ts.large_bytes;
+        EventPair *ev = nullptr;
+        KNN_TRY(next_event_pair(idx, false, &ev));
+        call.ev0 = ev ? ev->first : nullptr;
+        call.ev1 = ev ? ev->second : nullptr;
+        HIP_TRY(knn_masked_large_launch(call, plan, mask_dev, ts.mask, &idx->grid_topk_gate));
+    } else if (call.init) {
+        HIP_TRY(knn_keys_fill_launch(call.keys, mk, s));
+    }
+    if (indices_dev)
+        HIP_TRY(knn_keys_unpack_launch(call.keys, mk, indices_dev, s));
+    return KNN_OK;
+}
+
+int knn_debug_masked_lists_plan(const long long in[6], long long out[8])
+{
+    if (!in || !out || in[0] < 1 || in[0] > INT_MAX || in[1] < 1 || in[1] > INT_MAX || in[2] < 0 || in[2] > KNN_TOPK_LARGE_MAX ||
+        in[1] * in[2] > INT_MAX || in[3] < 0 || in[3] > (1ll << 32) || in[4] < 1 || in[4] > INT_MAX || (in[5] != 0 && in[5] != 1))
+        return fail(KNN_EINVAL, "knn_debug_masked_lists_plan: bad arguments (k >= 1, m >= 1, 0 <= K <= 4096, m * K <= INT_MAX, "
+                                "0 <= rows <= 2^32, CUs >= 1, init 0 or 1)");
+    const MaskedListsPlan p = knn_masked_lists_plan((int)in[0], (int)in[1], (int)in[2], in[3], (int)in[4], in[5] != 0);
+    const long long v[8] = {p.cut.granules, p.slices, p.slice_waves, p.cut.chunks, (long long)p.lds_bytes, (long long)p.cut.mask_bytes,
+                            (long long)p.select_bytes, p.launches};
+    memcpy(out, v, sizeof v);
+    return KNN_OK;
+}
+
 int knn_debug_filter_scores(knn_index *idx, int m, const float *queries_dev, float *scores_dev,
                             float *qnorm_dev, double consts[8])
 {
@@ -2541,6 +2687,154 @@ extern "C" int knn_index_list_within_host(knn_index *idx, int m, const float *qu
     if (dist2_out)
         *dist2_out = d2;
     // (not declared waited: the slot's buffers go back after the device-wide wait `stage` then makes itself, as the other host calls)
+    return KNN_OK;
+}
+
+extern "C" int knn_index_list_within_masked_host(knn_index *idx, int m, const float *queries_host, float max_dist2,
+                                                 const unsigned *mask_host, long long *offsets_host, int **indices_out, float **dist2_out)
+{
+    if (!idx || m < 1 || !queries_host || !mask_host || !offsets_host || !indices_out || !(max_dist2 >= 0.0f))
+        return fail(KNN_EINVAL, "knn_index_list_within_masked_host: bad arguments (m >= 1, max_dist2 >= 0 and not NaN)");
+    *indices_out = nullptr;
+    if (dist2_out)
+        *dist2_out = nullptr;
+    std::lock_guard<std::recursive_mutex> lock(idx->mu);
+    DeviceGuard guard(idx->device);
+    if (!guard.ok)
+        return fail(KNN_EHIP, "knn_index_list_within_masked_host: hipSetDevice failed");
+    Staging stage(idx->device);
+    float *q_dev = nullptr;
+    unsigned *c_dev = nullptr, *fill_dev = nullptr, *mask_dev = nullptr;
+    u64 *off_dev = nullptr, *keys_dev = nullptr;
+    const size_t qbytes = (size_t)m * (size_t)idx->k * sizeof(float), cbytes = (size_t)m * sizeof(unsigned);
+    const size_t obytes = ((size_t)m + 1) * sizeof(u64);
+    const size_t mbytes = std::max<size_t>((size_t)((idx->n + 31) / 32), 1) * sizeof(unsigned);   // (an empty shard: one word, unread)
+    hipError_t e = stage.get(&q_dev, qbytes);
+    if (e == hipSuccess)
+        e = stage.get(&c_dev, cbytes);
+    if (e == hipSuccess)
+        e = stage.get(&fill_dev, cbytes);
+    if (e == hipSuccess)
+        e = stage.get(&off_dev, obytes);
+    if (e == hipSuccess)
+        e = stage.get(&mask_dev, mbytes);
+    if (e == hipSuccess)
+        e = hipMemcpy(q_dev, queries_host, qbytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess && idx->n > 0)
+        e = hipMemcpy(mask_dev, mask_host, mbytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess)
+        return fail(KNN_EHIP, "knn_index_list_within_masked_host: staging queries and mask", hipGetErrorString(e));
+    // masked count -> offsets, then the one synchronisation: the total sizes the keys
+    int rc = knn_index_count_within_masked(idx, 0, m, q_dev, max_dist2, mask_dev, c_dev, nullptr, KNN_QUERY_INIT_KEYS);
+    if (rc == KNN_OK)
+        rc = knn_counts_to_offsets(idx->device, c_dev, m, off_dev, nullptr);
+    if (rc != KNN_OK)
+        return rc;
+    std::vector<u64> offs((size_t)m + 1);
+    e = hipMemcpy(offs.data(), off_dev, obytes, hipMemcpyDeviceToHost);
+    if (e != hipSuccess)
+        return fail(KNN_EHIP, "knn_index_list_within_masked_host: D2H offsets", hipGetErrorString(e));
+    const u64 total = offs[(size_t)m];
+    std::vector<u64> keys((size_t)total);
+    if (total) {   // masked list -> sort
+        e = stage.get(&keys_dev, (size_t)total * sizeof(u64));
+        if (e != hipSuccess)
+            return fail(KNN_EHIP, "knn_index_list_within_masked_host: staging keys", hipGetErrorString(e));
+        rc = knn_index_list_within_masked(idx, 0, m, q_dev, max_dist2, mask_dev, off_dev, fill_dev, keys_dev, nullptr, KNN_QUERY_INIT_KEYS);
+        if (rc == KNN_OK)
+            rc = knn_keys_sort_segments(idx->device, m, off_dev, fill_dev, keys_dev, nullptr);
+        if (rc != KNN_OK)
+            return rc;
+        e = hipMemcpy(keys.data(), keys_dev, (size_t)total * sizeof(u64), hipMemcpyDeviceToHost);
+        if (e != hipSuccess)
+            return fail(KNN_EHIP, "knn_index_list_within_masked_host: D2H keys", hipGetErrorString(e));
+    }
+    const size_t room = total ? (size_t)total : 1u;
+    int *ind = (int *)malloc(room * sizeof(int));
+    float *d2 = dist2_out ? (float *)malloc(room * sizeof(float)) : nullptr;
+    if (!ind || (dist2_out && !d2)) {
+        free(ind);
+        free(d2);
+        return fail(KNN_EHIP, "knn_index_list_within_masked_host: out of host memory");
+    }
+    for (size_t i = 0; i < (size_t)total; ++i) {
+        ind[i] = (int)(unsigned)(keys[i] & 0xFFFFFFFFull);
+        if (d2) {
+            const unsigned hi = (unsigned)(keys[i] >> 32);
+            memcpy(&d2[i], &hi, sizeof hi);
+        }
+    }
+    for (int j = 0; j <= m; ++j)
+        offsets_host[j] = (long long)offs[(size_t)j];
+    *indices_out = ind;
+    if (dist2_out)
+        *dist2_out = d2;
+    // (not declared waited: the slot's buffers go back after the device-wide wait `stage` then makes itself, as the other host calls)
+    return KNN_OK;
+}
+
+extern "C" int knn_index_query_topk_large_masked_host(knn_index *idx, int m, int K, const float *queries_host, float max_dist2,
+                                                      const unsigned *mask_host, int *indices_host, float *dist2_host, int *counts_host)
+{
+    if (!(max_dist2 >= 0.0f))
+        return fail(KNN_EINVAL, "knn_index_query_topk_large_masked_host: max_dist2 must be >= 0 and not NaN");
+    if (m < 1)
+        return fail(KNN_EINVAL, "knn_index_query_topk_large_masked_host: m < 1");
+    if (K < 1 || K > KNN_TOPK_LARGE_MAX)
+        return fail(KNN_EINVAL, "knn_index_query_topk_large_masked_host: K outside 1 .. 4096");
+    if ((long long)m * K > INT_MAX)
+        return fail(KNN_EINVAL, "knn_index_query_topk_large_masked_host: m * K above INT_MAX");
+    if (!queries_host || !mask_host || !indices_host)
+        return fail(KNN_EINVAL, "knn_index_query_topk_large_masked_host: null queries, mask or indices");
+    if (!idx)
+        return fail(KNN_EINVAL, "knn_index_query_topk_large_masked_host: null index");
+    std::lock_guard<std::recursive_mutex> lock(idx->mu);
+    DeviceGuard guard(idx->device);
+    if (!guard.ok)
+        return fail(KNN_EHIP, "knn_index_query_topk_large_masked_host: hipSetDevice failed");
+    const size_t mk = (size_t)m * (size_t)K;
+    std::vector<u64> keys(mk);
+    {
+        Staging stage(idx->device);
+        float *q_dev = nullptr;
+        u64 *keys_dev = nullptr;
+        unsigned *mask_dev = nullptr;
+        const size_t qbytes = (size_t)m * (size_t)idx->k * sizeof(float);
+        const size_t mbytes = std::max<size_t>((size_t)((idx->n + 31) / 32), 1) * sizeof(unsigned);   // (an empty shard: one word, unread)
+        hipError_t e = stage.get(&q_dev, qbytes);
+        if (e == hipSuccess)
+            e = stage.get(&keys_dev, mk * sizeof(u64));
+        if (e == hipSuccess)
+            e = stage.get(&mask_dev, mbytes);
+        if (e == hipSuccess)
+            e = hipMemcpy(q_dev, queries_host, qbytes, hipMemcpyHostToDevice);
+        if (e == hipSuccess && idx->n > 0)
+            e = hipMemcpy(mask_dev, mask_host, mbytes, hipMemcpyHostToDevice);
+        if (e != hipSuccess)
+            return fail(KNN_EHIP, "knn_index_query_topk_large_masked_host: staging queries and mask", hipGetErrorString(e));
+        const int rc = knn_index_query_topk_large_masked(idx, 0, m, K, q_dev, max_dist2, mask_dev, keys_dev, nullptr, nullptr,
+                                                         KNN_QUERY_INIT_KEYS);
+        if (rc != KNN_OK)
+            return rc;
+        e = hipMemcpy(keys.data(), keys_dev, mk * sizeof(u64), hipMemcpyDeviceToHost);
+        if (e != hipSuccess)
+            return fail(KNN_EHIP, "knn_index_query_topk_large_masked_host: D2H keys", hipGetErrorString(e));
+        // (not declared waited: the buffers go back after the device-wide wait `stage` then makes itself, as the top-K's)
+    }
+    for (size_t i = 0; i < mk; ++i) {
+        indices_host[i] = (int)(unsigned)(keys[i] & 0xFFFFFFFFull);
+        if (dist2_host) {
+            const unsigned hi = (unsigned)(keys[i] >> 32);
+            memcpy(&dist2_host[i], &hi, sizeof hi);
+        }
+    }
+    if (counts_host)
+        for (int j = 0; j < m; ++j) {   // padding is KNN_KEY_INIT; a real key is below it
+            int c = 0;
+            while (c < K && keys[(size_t)j * K + c] < kKeyInit)
+                ++c;
+            counts_host[j] = c;
+        }
     return KNN_OK;
 }
 

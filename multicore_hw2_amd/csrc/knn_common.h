@@ -236,6 +236,8 @@ hipError_t knn_keys_sort_segments_launch(int m, const u64 *offsets, const unsign
 // ---- top-K beyond 64 (knn_select.hip; knn_index_query_topk_large; DESIGN §4.6 "Top-K beyond 64") --------------------------------
 #define KNN_TOPK_LARGE_MAX 4096   // largest K of knn_index_query_topk_large (= KNN_SORT_LDS_KEYS: a list sorts in LDS)
 #define KNN_SELECT_WAVES 8        // waves of a select block: they hold the same 64 queries and split the slice's rows
+#define KNN_SELECT_BLOCK (KNN_SELECT_WAVES * KNN_WAVE)
+#define KNN_SELECT_HIST_WORDS (KNN_RADIX_BINS * KNN_WAVE)   // a select block's LDS histogram [bin][lane]: 64 KiB (KNN_RADIX_BINS: knn_radix_pick.h)
 // Everything one large call launches with and the slot's scratch it needs: the one place both are decided
 // (knn_debug_topk_large_plan shows it).  The scratch, per chunk of <= KNN_TOPK_CHUNK queries (mcp = the chunk's queries rounded up
 // to whole waves): the per-query histograms [256][mcp] unsigned (bin-major), prefix [mcp] u64, need [mcp], cursor [mcp], the
@@ -284,6 +286,37 @@ hipError_t knn_masked_topk_launch(const TopkCall &c, const MaskedPlan &p, const 
 hipError_t knn_masked_count_launch(const CountCall &c, const MaskedPlan &p, const unsigned *mask, u64 *scratch);
 // The mask bits of rows[0 .. count) that lie in 0 .. n - 1 <- value (0 or 1).
 hipError_t knn_mask_set_rows_launch(long long n, const unsigned *rows, long long count, int value, unsigned *mask, hipStream_t stream);
+// The granule counts and their prefix of one call's mask into the mask scratch (p.mask_bytes): what every masked call launches
+// first, once, ahead of every chunk and pass.  n > 0.
+hipError_t knn_masked_prefix_launch(const MaskedPlan &p, long long n, const unsigned *mask, u64 *scratch, hipStream_t stream);
+
+// ---- lists and top-K beyond 64 over a subset of the rows (knn_masked_lists.hip; DESIGN §4.6 "Lists and large K over a subset of
+// the rows") ------------------------------------------------------------------------------------------------------------------
+// The select's pieces that do not look at rows (knn_select.hip), shared with the select over a subset: the slices of one pass over
+// a chunk of mc queries; the pick of one pass and the sort of the filled lists on the state in `scratch` (laid out by p).
+long long knn_select_slices(int mc, long long n, int num_cu);
+hipError_t knn_select_pick_launch(const TopkLargePlan &p, u64 *scratch, int mc, int pass, int K, hipStream_t stream);
+hipError_t knn_topk_large_sort_launch(const TopkLargePlan &p, const u64 *scratch, int mc, int K, u64 *list, hipStream_t stream);
+// Everything a masked list call (K = 0) or a masked large call (1 <= K <= KNN_TOPK_LARGE_MAX) launches with and the slot's scratch
+// it needs: the one place both are decided (knn_debug_masked_lists_plan shows it).  cut: the masked count's plan for the same
+// inputs — granules, chunks, the mask scratch and, for a list call, the slices: the count pass and the list pass cut the shard
+// identically.  sel: the unmasked large call's plan — the select's state and a fold's lists in the slot's large scratch.
+struct MaskedListsPlan {
+    MaskedPlan cut;
+    TopkLargePlan sel;               // a list call: all zero
+    long long slices = 0;            // blocks along the rows of the first chunk's scan: knn_count_slices / the select's slices
+    int slice_waves = 0;             // waves of a block that each take their own admitted-row slice: 1 / KNN_SELECT_WAVES
+    size_t lds_bytes = 0;            // LDS of the scan: none / the select block's histogram
+    size_t select_bytes = 0;         // bytes of the slot's large scratch: 0 / sel.scratch_bytes
+    long long launches = 0;          // an init call whose index passes stay gated off: granule counts, prefix, and per chunk the
+                                     // list scan / sel.launches_clean (the state's memset counted as there)
+};
+MaskedListsPlan knn_masked_lists_plan(int k, int m, int K, long long n, int num_cu, bool init);
+// knn_exact_list_launch's contract over the rows whose mask bit is set.  scratch: p.cut.mask_bytes, stream-ordered.  c.n > 0.
+hipError_t knn_masked_list_launch(const ListCall &c, const MaskedListsPlan &p, const unsigned *mask, u64 *scratch);
+// knn_topk_large_launch's contract over the rows whose mask bit is set.  scratch: p.cut.mask_bytes; c.part: p.select_bytes.  c.n > 0.
+hipError_t knn_masked_large_launch(const TopkCall &c, const MaskedListsPlan &p, const unsigned *mask, u64 *scratch,
+                                   const unsigned **tie_word);
 
 // ---- MFMA filter + exact re-rank (knn_filter.hip) ---------------------------
 // Device-side control words of one filter query (FilterState::ctl).

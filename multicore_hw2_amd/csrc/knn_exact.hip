@@ -1630,24 +1630,9 @@ hipError_t knn_count_records_finish(const CountCall &c, const TopkRecords &rs, u
 // A hit — a row whose v0 distance E is finite and E <= max_dist2, knn_exact_count_kernel's rule — reserves place p of its query's
 // segment with one atomicAdd on the query's cursor and, when p is below the segment's room, stores its packed key at
 // keys[offsets[q] + p]: one 8-byte vector store.  The cursor counts every hit, stored or not, so a cursor above the room is how the
-// caller sees an overflow; nothing is stored outside [offsets[q], offsets[q + 1]).
+// caller sees an overflow; nothing is stored outside [offsets[q], offsets[q + 1]).  (list_room, list_put: knn_exact_dev.h, shared
+// with the list scan over a subset of the rows, knn_masked_lists.hip.)
 // ------------------------------------------------------------------------------------------
-// The room of segment q: offsets[q + 1] - offsets[q], capped at 2^32 - 1 (the cursor is 32-bit); descending offsets: none.
-__device__ __forceinline__ unsigned list_room(const u64 *__restrict__ offsets, unsigned q, u64 &off)
-{
-    off = offsets[q];
-    const u64 end = offsets[q + 1];
-    const u64 room = end > off ? end - off : 0ull;
-    return room < 0xFFFFFFFFull ? (unsigned)room : 0xFFFFFFFFu;
-}
-
-__device__ __forceinline__ void list_put(unsigned *__restrict__ cursor, u64 *__restrict__ keys, u64 off, unsigned room, u64 key)
-{
-    const unsigned p = atomicAdd(cursor, 1u);
-    if (p < room)
-        keys[off + p] = key;
-}
-
 // knn_exact_list_kernel<KC> — knn_exact_count_kernel's skeleton: one wave per block, lanes = queries (coordinates in VGPRs), rows
 // of the block's slice as wave-uniform scalar loads, v0's arithmetic; KC and gate as there.  On a hit the lane reserves and stores
 // (list_put) instead of adding to a register: hits are sparse at the radii the call is meant for, so no staging in LDS.

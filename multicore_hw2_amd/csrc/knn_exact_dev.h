@@ -59,6 +59,23 @@ __device__ __forceinline__ void sort_network(u64 *a, unsigned cnt)
     }
 }
 
+// How a list scan (knn_exact_list_kernel and its kin, knn_exact.hip; knn_masked_list_kernel, knn_masked_lists.hip) places a hit.
+// The room of segment q: offsets[q + 1] - offsets[q], capped at 2^32 - 1 (the cursor is 32-bit); descending offsets: none.
+__device__ __forceinline__ unsigned list_room(const u64 *__restrict__ offsets, unsigned q, u64 &off)
+{
+    off = offsets[q];
+    const u64 end = offsets[q + 1];
+    const u64 room = end > off ? end - off : 0ull;
+    return room < 0xFFFFFFFFull ? (unsigned)room : 0xFFFFFFFFu;
+}
+
+__device__ __forceinline__ void list_put(unsigned *__restrict__ cursor, u64 *__restrict__ keys, u64 off, unsigned room, u64 key)
+{
+    const unsigned p = atomicAdd(cursor, 1u);
+    if (p < room)
+        keys[off + p] = key;
+}
+
 // One (record, row) pair: the packed key of row `reg` of record e for its query, ~0 when there is nothing to evaluate.
 template <int K>
 __device__ __forceinline__ u64 rerank_pair(const float *__restrict__ Q, const float *__restrict__ R, int k, long long n,

@@ -1,0 +1,265 @@
+// knn_masked_lists.hip — lists within a radius and top-K beyond 64 over a subset of the rows (include/knn_mi355x.h 2h; DESIGN §4.6
+// "Lists and large K over a subset of the rows"): knn_index_list_within_masked, knn_index_query_topk_large_masked.
+//
+// The subset is knn_masked.hip's bit mask over the shard's local rows, cut into slices of equal numbers of ADMITTED rows
+// (knn_mask_split.h) and walked word by word (knn_masked_dev.h).  The three scans here are the skeletons of the unmasked calls'
+// scans with that walk in place of the row loop:
+//   knn_masked_list_kernel<KC>   knn_exact_list_kernel<KC> (knn_exact.hip): the second pass of masked count -> offsets -> list;
+//   knn_masked_hist_kernel<KC>   knn_select_hist_kernel<KC> (knn_select.hip): one pass of the radix select;
+//   knn_masked_fill_kernel<KC>   knn_select_fill_kernel<KC>: the rows with key <= T into the query's K places.
+// A masked select is a select over the admitted rows: the histograms count admitted candidates only, so the pick
+// (knn_select_pick_kernel), the sort and the fold behind them are the unmasked call's own, through their launchers.
+#include "knn_masked_dev.h"
+#include "knn_radix_pick.h"
+
+// knn_masked_list_kernel<KC> — knn_exact_list_kernel<KC> over the admitted rows of the block's slice: one wave per block, lanes =
+// queries, a hit reserves and stores through list_put.  The walk gives the LOCAL row i; the key carries gids[i] or base + i.
+// grid = the masked count's for the same call: (knn_count_slices, query groups of 64).
+template <int KC>
+__global__ __launch_bounds__(KNN_WAVE) void knn_masked_list_kernel(const float *__restrict__ Q, const float *__restrict__ R, int k,
+                                                                  int m, long long n, const unsigned *__restrict__ mask,
+                                                                  const u64 *__restrict__ P, int G, float max_dist2, long long base,
+                                                                  const unsigned *__restrict__ gids,
+                                                                  const u64 *__restrict__ offsets, unsigned *__restrict__ fill,
+                                                                  u64 *__restrict__ keys)
+{
+#pragma clang fp contract(off)
+    constexpr int KM = KC > 0 ? 16 * KC : 1;
+    const int lane = threadIdx.x;
+    const int q = blockIdx.y * KNN_WAVE + lane;
+    const int qa = min(q, m - 1);
+    float qv[KM];
+#pragma unroll
+    for (int d = 0; d < KM; ++d)
+        qv[d] = KC > 0 && d < k ? Q[(size_t)qa * k + d] : 0.0f;
+    u64 off;
+    const unsigned room = list_room(offsets, (unsigned)qa, off);
+    const float *__restrict__ qp = Q + (size_t)qa * k;
+    long long r0, r1;
+    masked_slice(mask, n, P, G, r0, r1);
+    masked_walk(mask, P, G, r0, r1, [&](long long i) {
+        const float acc = masked_dist2<KC>(qv, qp, R + (size_t)i * k, k);
+        if (q < m && acc < INFINITY && acc <= max_dist2)   // (NaN fails both compares)
+            list_put(&fill[q], keys, off, room, pack_key(acc, gids ? gids[i] : (unsigned)(base + i)));
+    });
+}
+
+// knn_masked_hist_kernel<KC> — one pass of the select (knn_select_hist_kernel's histogram, gate and flush) over the admitted rows.
+// The block's KNN_SELECT_WAVES waves hold the SAME 64 queries; each walks its OWN slice by admitted rows — wave w of block b takes
+// slice b * W + w of gridDim.x * W — so a mask that admits one contiguous range loads every wave alike, where a share of the
+// block's rows by position would leave most waves of most blocks idle.
+template <int KC>
+__global__ __launch_bounds__(KNN_SELECT_BLOCK) void knn_masked_hist_kernel(const float *__restrict__ Q, const float *__restrict__ R, int k,
+                                                                          int m, long long n, const unsigned *__restrict__ mask,
+                                                                          const u64 *__restrict__ P, int G, float max_dist2,
+                                                                          long long base, const unsigned *__restrict__ gids, int pass,
+                                                                          const u64 *__restrict__ prefix, const unsigned *__restrict__ need,
+                                                                          unsigned *__restrict__ ghist, long long mcp,
+                                                                          const unsigned *__restrict__ gate)
+{
+#pragma clang fp contract(off)
+    __shared__ unsigned hist[KNN_SELECT_HIST_WORDS];
+    if (gate && *gate == 0u)
+        return;
+    for (unsigned w = threadIdx.x; w < KNN_SELECT_HIST_WORDS; w += KNN_SELECT_BLOCK)
+        hist[w] = 0u;
+    __syncthreads();
+    constexpr int KM = KC > 0 ? 16 * KC : 1;
+    const int lane = threadIdx.x & (KNN_WAVE - 1);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / KNN_WAVE));   // (uniform: the walk stays scalar)
+    const int q = blockIdx.y * KNN_WAVE + lane;
+    const int qa = min(q, m - 1);
+    float qv[KM];
+#pragma unroll
+    for (int d = 0; d < KM; ++d)
+        qv[d] = KC > 0 && d < k ? Q[(size_t)qa * k + d] : 0.0f;
+    const bool live = q < m && (pass == 0 || need[qa] != 0u);
+    const u64 pre = pass == 0 ? 0ull : prefix[qa];
+    const float *__restrict__ qp = Q + (size_t)qa * k;
+    long long r0, r1;
+    masked_wave_slice(mask, n, P, G, KNN_SELECT_WAVES, wave, r0, r1);
+    masked_walk(mask, P, G, r0, r1, [&](long long i) {
+        const float acc = masked_dist2<KC>(qv, qp, R + (size_t)i * k, k);
+        if (live && acc < INFINITY && acc <= max_dist2) {   // (NaN fails both compares)
+            const u64 key = pack_key(acc, gids ? gids[i] : (unsigned)(base + i));
+            if (knn_radix_match(key, pre, pass))
+                atomicAdd(&hist[knn_radix_digit(key, pass) * KNN_WAVE + lane], 1u);
+        }
+    });
+    __syncthreads();
+    unsigned *__restrict__ mine = ghist + (size_t)blockIdx.y * KNN_WAVE;
+    for (unsigned w = threadIdx.x; w < KNN_SELECT_HIST_WORDS; w += KNN_SELECT_BLOCK) {
+        const unsigned c = hist[w];
+        if (c != 0u)
+            atomicAdd(&mine[(size_t)(w / KNN_WAVE) * mcp + (w % KNN_WAVE)], c);
+    }
+}
+
+// knn_masked_fill_kernel<KC> — knn_select_fill_kernel<KC> over the admitted rows of the block's slice (one wave per block, the
+// masked count's slices): an admitted candidate with key <= T[q] reserves p = cursor[q]++ and stores at list[q * K + p] when p < K.
+template <int KC>
+__global__ __launch_bounds__(KNN_WAVE) void knn_masked_fill_kernel(const float *__restrict__ Q, const float *__restrict__ R, int k, int m,
+                                                                  long long n, const unsigned *__restrict__ mask,
+                                                                  const u64 *__restrict__ P, int G, float max_dist2, long long base,
+                                                                  const unsigned *__restrict__ gids, const u64 *__restrict__ T,
+                                                                  unsigned *__restrict__ cursor, int K, u64 *__restrict__ list)
+{
+#pragma clang fp contract(off)
+    constexpr int KM = KC > 0 ? 16 * KC : 1;
+    const int lane = threadIdx.x;
+    const int q = blockIdx.y * KNN_WAVE + lane;
+    const int qa = min(q, m - 1);
+    float qv[KM];
+#pragma unroll
+    for (int d = 0; d < KM; ++d)
+        qv[d] = KC > 0 && d < k ? Q[(size_t)qa * k + d] : 0.0f;
+    const u64 t = T[qa];
+    const float *__restrict__ qp = Q + (size_t)qa * k;
+    long long r0, r1;
+    masked_slice(mask, n, P, G, r0, r1);
+    masked_walk(mask, P, G, r0, r1, [&](long long i) {
+        const float acc = masked_dist2<KC>(qv, qp, R + (size_t)i * k, k);
+        if (q < m && acc < INFINITY && acc <= max_dist2) {   // (NaN fails both compares)
+            const u64 key = pack_key(acc, gids ? gids[i] : (unsigned)(base + i));
+            if (key <= t) {
+                const unsigned p = atomicAdd(&cursor[q], 1u);
+                if (p < (unsigned)K)
+                    list[(size_t)q * K + p] = key;
+            }
+        }
+    });
+}
+
+MaskedListsPlan knn_masked_lists_plan(int k, int m, int K, long long n, int num_cu, bool init)
+{
+    MaskedListsPlan p;
+    p.cut = knn_masked_plan(k, m, 0, n, num_cu, init);   // granules, chunks, the mask scratch; a list call's slices
+    if (m <= 0)
+        return p;
+    if (n <= 0) {   // an empty shard: an init large call fills the keys, everything else launches nothing
+        p.launches = K > 0 && init ? 1 : 0;
+        return p;
+    }
+    if (K > 0) {
+        p.sel = knn_topk_large_plan(k, m, K, n, num_cu, init);
+        p.slices = p.sel.slices;
+        p.slice_waves = KNN_SELECT_WAVES;
+        p.lds_bytes = p.sel.lds_bytes;
+        p.select_bytes = p.sel.scratch_bytes;
+        p.launches = 2 + p.sel.launches_clean;
+    } else {
+        p.slices = p.cut.slices;
+        p.slice_waves = 1;
+        p.launches = 2 + (long long)p.cut.chunks;
+    }
+    return p;
+}
+
+#define KNN_MASKED_FORMS(CALL)   \
+    switch ((c.k + 15) / 16) {   \
+    case 1: CALL(1); break;      \
+    case 2: CALL(2); break;      \
+    case 3: CALL(3); break;      \
+    case 4: CALL(4); break;      \
+    case 5: CALL(5); break;      \
+    case 6: CALL(6); break;      \
+    case 7: CALL(7); break;      \
+    case 8: CALL(8); break;      \
+    default: CALL(0); break;     \
+    }
+
+hipError_t knn_masked_list_launch(const ListCall &c, const MaskedListsPlan &p, const unsigned *mask, u64 *scratch)
+{
+    hipStream_t s = c.stream;
+    if (c.m <= 0 || c.n <= 0 || !mask || !scratch || !c.offsets || !c.fill || !c.keys)
+        return hipErrorInvalidValue;
+    hipError_t e = knn_masked_prefix_launch(p.cut, c.n, mask, scratch, s);
+    if (e != hipSuccess)
+        return e;
+    if (c.ev0 && (e = hipEventRecord(c.ev0, s)) != hipSuccess)
+        return e;
+    for (int c0 = 0; c0 < c.m; c0 += KNN_TOPK_CHUNK) {
+        const int mc = c.m - c0 < KNN_TOPK_CHUNK ? c.m - c0 : KNN_TOPK_CHUNK;
+        const long long slices = knn_count_slices(mc, c.n, c.num_cu);
+        const dim3 grid((unsigned)slices, (unsigned)knn_divup(mc, KNN_WAVE)), block(KNN_WAVE);
+        const float *qc = c.q + (size_t)c0 * c.k;
+#define KNN_MASKED_LIST(KCV)                                                                                                   \
+    hipLaunchKernelGGL(knn_masked_list_kernel<KCV>, grid, block, 0, s, qc, c.r, c.k, mc, c.n, mask, (const u64 *)scratch,     \
+                       (int)p.cut.granules, c.max_dist2, c.base, c.gids, c.offsets + c0, c.fill + c0, c.keys)
+        KNN_MASKED_FORMS(KNN_MASKED_LIST)
+#undef KNN_MASKED_LIST
+        e = hipGetLastError();
+        if (e != hipSuccess)
+            return e;
+    }
+    if (c.ev1 && (e = hipEventRecord(c.ev1, s)) != hipSuccess)
+        return e;
+    return hipSuccess;
+}
+
+hipError_t knn_masked_large_launch(const TopkCall &c, const MaskedListsPlan &p, const unsigned *mask, u64 *scratch,
+                                   const unsigned **tie_word)
+{
+    if (c.m <= 0 || c.n <= 0 || c.K < 1 || c.K > KNN_TOPK_LARGE_MAX || !mask || !scratch || !c.part || c.part_bytes < p.select_bytes ||
+        p.select_bytes < p.sel.state_bytes || p.sel.state_bytes == 0)
+        return hipErrorInvalidValue;
+    hipStream_t s = c.stream;
+    const TopkLargePlan &sp = p.sel;
+    unsigned char *st = (unsigned char *)c.part;
+    const u64 *P = (const u64 *)scratch;
+    const int G = (int)p.cut.granules;
+    hipError_t e = knn_masked_prefix_launch(p.cut, c.n, mask, scratch, s);
+    if (e != hipSuccess)
+        return e;
+    for (int c0 = 0; c0 < c.m; c0 += KNN_TOPK_CHUNK) {
+        const int mc = c.m - c0 < KNN_TOPK_CHUNK ? c.m - c0 : KNN_TOPK_CHUNK;
+        const float *qc = c.q + (size_t)c0 * c.k;
+        u64 *keys = c.keys + (size_t)c0 * c.K;
+        u64 *list = c.init ? keys : (u64 *)(st + sp.list_off);
+        const long long mcp = (long long)knn_divup(mc, KNN_WAVE) * KNN_WAVE;
+        const dim3 grid_hist((unsigned)knn_select_slices(mc, c.n, c.num_cu), (unsigned)knn_divup(mc, KNN_WAVE));
+        const dim3 grid_fill((unsigned)knn_count_slices(mc, c.n, c.num_cu), (unsigned)knn_divup(mc, KNN_WAVE));
+        e = hipMemsetAsync(st, 0, sp.state_bytes, s);
+        if (e != hipSuccess)
+            return e;
+        if (c.ev0 && c0 == 0)
+            (void)hipEventRecord(c.ev0, s);
+        const unsigned *gates = (const unsigned *)(st + sp.gate_off);
+        for (int pass = 0; pass < KNN_RADIX_PASSES; ++pass) {
+#define KNN_MASKED_HIST(KCV)                                                                                                        \
+    hipLaunchKernelGGL(knn_masked_hist_kernel<KCV>, grid_hist, dim3(KNN_SELECT_BLOCK), 0, s, qc, c.r, c.k, mc, c.n, mask, P, G, \
+                       c.max_dist2, c.base, c.gids, pass, (const u64 *)(st + sp.prefix_off), (const unsigned *)(st + sp.need_off), \
+                       (unsigned *)(st + sp.hist_off), mcp, pass == 0 ? (const unsigned *)nullptr : gates + pass)
+            KNN_MASKED_FORMS(KNN_MASKED_HIST)
+#undef KNN_MASKED_HIST
+            e = hipGetLastError();
+            if (e != hipSuccess)
+                return e;
+            e = knn_select_pick_launch(sp, c.part, mc, pass, c.K, s);
+            if (e != hipSuccess)
+                return e;
+        }
+#define KNN_MASKED_FILL(KCV)                                                                                                    \
+    hipLaunchKernelGGL(knn_masked_fill_kernel<KCV>, grid_fill, dim3(KNN_WAVE), 0, s, qc, c.r, c.k, mc, c.n, mask, P, G,    \
+                       c.max_dist2, c.base, c.gids, (const u64 *)(st + sp.prefix_off), (unsigned *)(st + sp.cursor_off), c.K, list)
+        KNN_MASKED_FORMS(KNN_MASKED_FILL)
+#undef KNN_MASKED_FILL
+        e = hipGetLastError();
+        if (e != hipSuccess)
+            return e;
+        if (c.ev1 && c0 + mc == c.m)
+            (void)hipEventRecord(c.ev1, s);
+        e = knn_topk_large_sort_launch(sp, c.part, mc, c.K, list, s);
+        if (e != hipSuccess)
+            return e;
+        if (!c.init) {
+            e = knn_topk_merge_large_launch(mc, c.K, list, keys, s);
+            if (e != hipSuccess)
+                return e;
+        }
+    }
+    if (tie_word)
+        *tie_word = (const unsigned *)(st + sp.gate_off) + KNN_RADIX_DIST_PASSES;
+    return hipSuccess;
+}
+#undef KNN_MASKED_FORMS

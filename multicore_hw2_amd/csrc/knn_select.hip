@@ -14,9 +14,6 @@
 #include "knn_exact_dev.h"
 #include "knn_radix_pick.h"
 
-#define KNN_SELECT_BLOCK (KNN_SELECT_WAVES * KNN_WAVE)
-#define KNN_SELECT_HIST_WORDS (KNN_RADIX_BINS * KNN_WAVE)   // [bin][lane]: 64 KiB
-
 // v0's distance of one row to the lane's query — the body of knn_exact_count_kernel's row loop.  r: wave-uniform.
 template <int KC>
 __device__ __forceinline__ float select_row_dist(const float (&qv)[KC > 0 ? 16 * KC : 1], const float *__restrict__ qp,
@@ -364,6 +361,29 @@ hipError_t knn_topk_large_launch(const TopkCall &c, const TopkLargePlan &p, cons
     if (tie_word)
         *tie_word = (const unsigned *)(st + p.gate_off) + KNN_RADIX_DIST_PASSES;
     return hipSuccess;
+}
+
+// The select's pieces that do not look at rows, for the select over a subset of the rows (knn_masked_lists.hip).
+long long knn_select_slices(int mc, long long n, int num_cu) { return select_slices(mc, n, num_cu); }
+
+hipError_t knn_select_pick_launch(const TopkLargePlan &p, u64 *scratch, int mc, int pass, int K, hipStream_t s)
+{
+    if (!scratch || mc <= 0 || mc > p.mcp || pass < 0 || pass >= KNN_RADIX_PASSES || K < 1 || K > KNN_TOPK_LARGE_MAX)
+        return hipErrorInvalidValue;
+    unsigned char *st = (unsigned char *)scratch;
+    hipLaunchKernelGGL(knn_select_pick_kernel, dim3((unsigned)knn_divup(mc, KNN_BLOCK)), dim3(KNN_BLOCK), 0, s,
+                       (unsigned *)(st + p.hist_off), (long long)knn_divup(mc, KNN_WAVE) * KNN_WAVE, mc, pass, K,
+                       (u64 *)(st + p.prefix_off), (unsigned *)(st + p.need_off), (unsigned *)(st + p.gate_off));
+    return hipGetLastError();
+}
+
+hipError_t knn_topk_large_sort_launch(const TopkLargePlan &p, const u64 *scratch, int mc, int K, u64 *list, hipStream_t s)
+{
+    if (!scratch || !list || mc <= 0 || mc > p.mcp || K < 1 || K > KNN_TOPK_LARGE_MAX)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(knn_topk_large_sort_kernel, dim3((unsigned)mc), dim3(KNN_BLOCK), 0, s,
+                       (const unsigned *)((const unsigned char *)scratch + p.cursor_off), K, list);
+    return hipGetLastError();
 }
 
 hipError_t knn_topk_merge_large_launch(int m, int K, const u64 *a, u64 *b, hipStream_t s)
