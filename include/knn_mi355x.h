@@ -512,6 +512,74 @@ int knn_index_query_topk_large_masked_host(knn_index *idx, int m, int K, const f
  * [0], [1], [2], [4] for a count call on the same inputs: the count pass and the list pass cut the shard identically. */
 int knn_debug_masked_lists_plan(const long long in[6], long long out[8]);
 
+/* ------------------------------------------------------------------------
+ * 2i. Queries about the shard's own rows: the K nearest OTHER rows of every row (the kNN graph), the number of other rows within a
+ * radius (the degree of the radius graph) and the list of them (its adjacency).
+ *
+ * Query j of a call is LOCAL row row_first + j of the index: row row_first + j of the refs given to knn_index_create, or of the
+ * refs_dev given to knn_index_create_sharded.  0 <= row_first, rows >= 1, row_first + rows <= n_local.  There is no queries
+ * pointer: the coordinates are read from the resident rows, nothing is uploaded or gathered.
+ *
+ * Row i is a candidate for query j when i != row_first + j — identity by LOCAL ROW NUMBER: other copies of the row stay candidates,
+ * at distance 0 —, its v0 distance E is finite, and E <= max_dist2 (fp32, dimension order, no FMA, equality inside, -0 counts as 0;
+ * +INF: no radius).  Keys carry the global numbers every other call carries (base_index + row, or the gid).  A query row with a
+ * non-finite coordinate has no candidate (every E is NaN or +INF): a padding list, count 0, nothing listed.
+ *
+ * knn_index_self_topk: 1 <= K <= 64; lists ascending, padded with KNN_KEY_INIT.  KNN_QUERY_INIT_KEYS writes; without it the call
+ * folds into the K sorted keys held, which are the caller's and are NOT clipped.  indices_dev may be NULL.
+ * knn_index_self_count_within, knn_index_self_list_within: 2d and 2e word for word with the candidate rule above — counts ADD; a
+ * hit reserves p = fill_dev[j]++ and is stored at keys_dev[offsets_dev[j] + p] only when p is below the segment's room, so an
+ * overflow shows in the cursor and nothing is ever stored outside a segment; the order inside a segment is unspecified;
+ * KNN_QUERY_INIT_KEYS zeroes counts_dev / fill_dev first.
+ *
+ * Flags.  Count and list: KNN_QUERY_INIT_KEYS alone — one way on every index, the exact self-scan (DESIGN §4.6 "About the shard's
+ * own rows"), as for the masked calls; knn_index_last_stats reads [1, 0, 0, 0].  Top-K also admits KNN_QUERY_TOPK_GRID and
+ * KNN_QUERY_TOPK_FRAMES with their 2c meaning; KNN_QUERY_TOPK_PARTIAL and the KNN_QUERY_COUNT_* flags are KNN_EINVAL.  The top-K's
+ * way is the one the plain top-K call of K + 1 neighbours (self is among ITS candidates) would take for `rows` queries under the
+ * same flags and options: where that is the exact scan, always for K = 64, and where rows * (K + 1) would exceed INT_MAX (the plain
+ * call's own limit), the exact self-scan answers with K; otherwise the
+ * plain call runs as it is for K + 1 into slot scratch and one more launch removes self (the last entry when self is not among
+ * the K + 1: then K + 1 other rows precede it) — so the grid index (with its flag), the MFMA filter and the cell-pruned scan
+ * (option "topk_cells" 1, and KNN_QUERY_TOPK_FRAMES on per-cell frames) all serve the kNN graph, bit-exact, with the plain call's
+ * own fallbacks inside, and knn_index_last_stats reports what the plain call reports.  A cell-range shard takes the self-scan.
+ *
+ * The graph of a set split over shards needs nothing new, because a row lives in one shard: make the self call on the row's own
+ * shard, then the plain knn_index_query_topk_within, knn_index_count_within or knn_index_list_within call on every other shard
+ * with the row block as queries_dev, folding (or the other way round: the self call folds too).
+ *
+ * Argument errors are KNN_EINVAL, each with its own knn_last_error text prefixed by the function's name, checked in this order —
+ * the first that fails speaks, nothing is launched —: max_dist2 < 0 or NaN, an unknown flag, a slot outside 0 .. 7, rows < 1,
+ * row_first < 0, (top-K) K outside 1 .. 64, (top-K) rows * K > INT_MAX, a null keys, counts, offsets or fill pointer, a null
+ * index, row_first + rows > n_local (which needs the index: any call on an empty shard fails here).  Asynchronous on `stream`;
+ * slots as for every other query; these calls may follow or precede any other call on a slot. */
+int knn_index_self_topk(knn_index *idx, int slot, long long row_first, int rows, int K, float max_dist2,
+                        unsigned long long *keys_dev /*[rows][K]*/, int *indices_dev /*[rows][K] or NULL*/, void *stream,
+                        unsigned flags);
+int knn_index_self_count_within(knn_index *idx, int slot, long long row_first, int rows, float max_dist2,
+                                unsigned *counts_dev /*[rows]*/, void *stream, unsigned flags);
+int knn_index_self_list_within(knn_index *idx, int slot, long long row_first, int rows, float max_dist2,
+                               const unsigned long long *offsets_dev /*[rows+1]*/, unsigned *fill_dev /*[rows]*/,
+                               unsigned long long *keys_dev, void *stream, unsigned flags);
+/* Synchronous, the WHOLE shard, in blocks of 65536 rows on the default way (no flag but the init flag).  The top-K call fills
+ * indices_host [n_local][K] (dist2_host: +INF in padding; counts_host: the entries of each list that are not padding; both may be
+ * NULL).  The list call runs self count -> knn_counts_to_offsets -> self list -> knn_keys_sort_segments and returns the CSR
+ * adjacency: offsets_host [n_local + 1] and malloc'd arrays as knn_index_list_within_host does (nearest first within a row; a
+ * 1-entry allocation when the total is 0; the caller frees them); n_local <= INT_MAX there. */
+int knn_index_self_topk_host(knn_index *idx, int K, float max_dist2, int *indices_host /*[n_local][K]*/,
+                             float *dist2_host /*NULL ok*/, int *counts_host /*NULL ok*/);
+int knn_index_self_list_within_host(knn_index *idx, float max_dist2, long long *offsets_host /*[n_local+1]*/,
+                                    int **indices_out, float **dist2_out /*NULL ok*/);
+/* Test hooks, host arithmetic only.  knn_debug_self_plan: in = {k, rows, K (0 = a count call, -1 = a list call), the shard's rows,
+ * CUs, 1 if init}; out = {chunks of 65536 rows, slices of the first chunk (the plain exact scan's number for `rows` queries),
+ * query groups of 64 of the first chunk, LDS bytes of the scan, bytes of the slot's per-slice lists, kernel launches of an init
+ * call on the self-scan (per chunk the scan and — top-K — the select), rows of the first chunk, bytes of the through way's scratch
+ * for this call: [rows][K + 1] keys, and [rows][K] more when the call folds; 0 for K = 64, count and list}.
+ * knn_debug_self_ranges: the cut a block of the self-scans makes of its slice [i0, i1) around its window of own rows [w0, w1),
+ * through the kernels' own lines (knn_self_window.h): out = {b0, b1, w0', w1', a0, a1} — the rows before the window, inside it
+ * and after it: three disjoint ranges, ascending, whose union is [i0, i1). */
+int knn_debug_self_plan(const long long in[6], long long out[8]);
+int knn_debug_self_ranges(long long i0, long long i1, long long w0, long long w1, long long out[6]);
+
 /* Tuning / test hooks.  Known names:
  *   "path"    0 = auto, 1 = exact VALU kernels only, 2 = force the MFMA filter
  *             (+ exact re-rank) where its preconditions hold, 3 = the uniform-grid spatial index

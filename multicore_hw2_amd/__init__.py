@@ -21,7 +21,9 @@ __all__ = ["lib", "lib_path", "cudaCallback", "KnnIndex", "KnnGeom", "KnnError",
            "keys_sort_segments", "keys_topk_merge_large", "debug_topk_large_plan", "debug_radix_kth", "TOPK_LARGE_MAX",
            "mask_words", "mask_set_rows", "debug_masked_plan", "debug_mask_split", "debug_mask_split_rows",
            "list_within_masked_c", "query_topk_large_masked_c", "list_within_masked_host_c", "query_topk_large_masked_host_c",
-           "debug_masked_lists_plan"]
+           "debug_masked_lists_plan",
+           "self_topk_c", "self_count_within_c", "self_list_within_c", "self_topk_host_c", "self_list_within_host_c",
+           "debug_self_plan", "debug_self_ranges"]
 
 KEY_INIT = 0x7F80000000000000
 
@@ -46,6 +48,8 @@ EXPORTED_SYMBOLS = [
     "knn_debug_masked_plan", "knn_debug_mask_split", "knn_debug_mask_split_rows",
     "knn_index_list_within_masked", "knn_index_list_within_masked_host", "knn_index_query_topk_large_masked",
     "knn_index_query_topk_large_masked_host", "knn_debug_masked_lists_plan",
+    "knn_index_self_topk", "knn_index_self_count_within", "knn_index_self_list_within", "knn_index_self_topk_host",
+    "knn_index_self_list_within_host", "knn_debug_self_plan", "knn_debug_self_ranges",
 ]
 TOPK_LARGE_MAX = 4096   # KNN_TOPK_LARGE_MAX
 QUERY_INIT_KEYS = 1   # KNN_QUERY_INIT_KEYS
@@ -638,6 +642,69 @@ def debug_masked_lists_plan(**inputs):
     return dict(zip(MASKED_LISTS_PLAN, list(out)))
 
 
+def self_topk_c():
+    """knn_index_self_topk with its argument types (set here, not in lib(), as count_within_c)."""
+    f = lib().knn_index_self_topk
+    f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_void_p,
+                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint]
+    return f
+
+
+def self_count_within_c():
+    """knn_index_self_count_within with its argument types (set here, not in lib(), as count_within_c)."""
+    f = lib().knn_index_self_count_within
+    f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
+                  ctypes.c_uint]
+    return f
+
+
+def self_list_within_c():
+    """knn_index_self_list_within with its argument types (set here, not in lib(), as count_within_c)."""
+    f = lib().knn_index_self_list_within
+    f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
+                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint]
+    return f
+
+
+def self_topk_host_c():
+    f = lib().knn_index_self_topk_host
+    f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    return f
+
+
+def self_list_within_host_c():
+    f = lib().knn_index_self_list_within_host
+    f.argtypes = [ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.POINTER(ctypes.POINTER(ctypes.c_int)),
+                  ctypes.POINTER(ctypes.POINTER(ctypes.c_float))]
+    return f
+
+
+SELF_PLAN_INPUTS = ("k", "rows", "K", "shard_rows", "num_cu", "init")
+SELF_PLAN = ("chunks", "slices", "groups", "lds_bytes", "part_bytes", "launches", "chunk_rows", "through_bytes")
+SELF_RANGES = ("b0", "b1", "w0", "w1", "a0", "a1")
+
+
+def debug_self_plan(**inputs):
+    """knn_debug_self_plan: what a self_topk (K >= 1), self_count_within (K = 0) or self_list_within (K = -1) call launches with
+    and the slot scratch it needs, for the inputs named in SELF_PLAN_INPUTS.  Host arithmetic; works without a GPU."""
+    vin = (ctypes.c_longlong * len(SELF_PLAN_INPUTS))(*[int(inputs[n]) for n in SELF_PLAN_INPUTS])
+    out = (ctypes.c_longlong * len(SELF_PLAN))()
+    f = lib().knn_debug_self_plan
+    f.argtypes = [ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)]
+    _check(f(vin, out))
+    return dict(zip(SELF_PLAN, list(out)))
+
+
+def debug_self_ranges(i0, i1, w0, w1):
+    """knn_debug_self_ranges: how a block of the self-scans cuts its slice [i0, i1) around its window of own rows [w0, w1), through
+    the kernels' own lines (knn_self_window.h): the six bounds named in SELF_RANGES.  Host arithmetic; works without a GPU."""
+    out = (ctypes.c_longlong * 6)()
+    f = lib().knn_debug_self_ranges
+    f.argtypes = [ctypes.c_longlong] * 4 + [ctypes.POINTER(ctypes.c_longlong)]
+    _check(f(int(i0), int(i1), int(w0), int(w1), out))
+    return dict(zip(SELF_RANGES, list(out)))
+
+
 def counts_to_offsets_c():
     f = lib().knn_counts_to_offsets
     f.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
@@ -998,6 +1065,62 @@ class KnnIndex:
                                                 idx.ctypes.data_as(ctypes.c_void_p), d2.ctypes.data_as(ctypes.c_void_p),
                                                 counts.ctypes.data_as(ctypes.c_void_p)))
         return idx, d2, counts
+
+    def self_topk(self, row_first, rows, K, keys_dev, max_dist2=float("inf"), stream=0, slot=0, init_keys=False, indices_dev=None,
+                  grid=False, frames=False, flags=0):
+        """Async (knn_index_self_topk): the K nearest OTHER rows of the local rows row_first .. row_first + rows - 1 —
+        keys_dev[rows][K] <- the K smallest keys of (this shard's rows but the query's own, with a finite v0 squared distance <=
+        max_dist2, and, unless init_keys, the K sorted keys per row keys_dev already holds, which are not clipped), sorted, padded
+        with KEY_INIT.  1 <= K <= 64.  The way is the plain top-K's for K + 1 (grid / frames as query_topk; last_stats() reports
+        it); the exact self-scan where that is the exact scan and for K = 64.  flags: further flag bits as they are."""
+        _check(self_topk_c()(self._h, int(slot), int(row_first), int(rows), int(K), float(max_dist2), ctypes.c_void_p(int(keys_dev)),
+                             ctypes.c_void_p(int(indices_dev)) if indices_dev is not None else None, ctypes.c_void_p(stream),
+                             (QUERY_INIT_KEYS if init_keys else 0) | (QUERY_TOPK_GRID if grid else 0) |
+                             (QUERY_TOPK_FRAMES if frames else 0) | int(flags)))
+
+    def self_count_within(self, row_first, rows, max_dist2, counts_dev, stream=0, slot=0, init=False, flags=0):
+        """Async (knn_index_self_count_within): counts_dev[rows] (uint32) += the OTHER rows of this shard whose v0 squared distance
+        to local row row_first + j is finite and <= max_dist2; init: = instead of +=.  flags: further flag bits as they are
+        (every one of them raises)."""
+        _check(self_count_within_c()(self._h, int(slot), int(row_first), int(rows), float(max_dist2), ctypes.c_void_p(int(counts_dev)),
+                                     ctypes.c_void_p(stream), (QUERY_INIT_KEYS if init else 0) | int(flags)))
+
+    def self_list_within(self, row_first, rows, max_dist2, offsets_dev, fill_dev, keys_dev, stream=0, slot=0, init=False, flags=0):
+        """Async (knn_index_self_list_within): list_within for the queries that are the local rows row_first .. row_first + rows - 1,
+        each without itself.  The third step of self_count_within -> counts_to_offsets -> this -> keys_sort_segments."""
+        _check(self_list_within_c()(self._h, int(slot), int(row_first), int(rows), float(max_dist2), ctypes.c_void_p(int(offsets_dev)),
+                                    ctypes.c_void_p(int(fill_dev)), ctypes.c_void_p(int(keys_dev)), ctypes.c_void_p(stream),
+                                    (QUERY_INIT_KEYS if init else 0) | int(flags)))
+
+    def self_topk_host(self, K, max_dist2=float("inf")):
+        """Synchronous kNN graph of this shard (knn_index_self_topk_host): (indices int32 [n][K], dist2 float32 [n][K] with +INF in
+        padding, counts int32 [n]: the entries of each list that are not padding)."""
+        n = int(self.n)
+        idx = np.empty((n, int(K)), dtype=np.int32)
+        d2 = np.empty((n, int(K)), dtype=np.float32)
+        counts = np.empty(n, dtype=np.int32)
+        _check(self_topk_host_c()(self._h, int(K), float(max_dist2), idx.ctypes.data_as(ctypes.c_void_p),
+                                  d2.ctypes.data_as(ctypes.c_void_p), counts.ctypes.data_as(ctypes.c_void_p)))
+        return idx, d2, counts
+
+    def self_list_within_host(self, max_dist2):
+        """Synchronous radius graph of this shard (knn_index_self_list_within_host) in CSR form: (offsets int64 [n + 1], indices
+        int32 [total], dist2 float32 [total]); row j's neighbours, nearest first, are entries offsets[j] .. offsets[j + 1] - 1."""
+        n = int(self.n)
+        offsets = np.empty(n + 1, dtype=np.int64)
+        ind, d2 = ctypes.POINTER(ctypes.c_int)(), ctypes.POINTER(ctypes.c_float)()
+        _check(self_list_within_host_c()(self._h, float(max_dist2), offsets.ctypes.data_as(ctypes.c_void_p), ctypes.byref(ind),
+                                         ctypes.byref(d2)))
+        total = int(offsets[n])
+        free = ctypes.CDLL(None).free
+        free.argtypes = [ctypes.c_void_p]
+        try:
+            indices = np.ctypeslib.as_array(ind, shape=(max(total, 1),))[:total].astype(np.int32, copy=True)
+            dist2 = np.ctypeslib.as_array(d2, shape=(max(total, 1),))[:total].astype(np.float32, copy=True)
+        finally:
+            free(ind)
+            free(d2)
+        return offsets, indices, dist2
 
     def query_topk_host(self, queries, K):
         """Synchronous top-K of this shard alone: (indices int32 [m][K], dist2 float32 [m][K])."""

@@ -10,6 +10,7 @@
 #include "knn_common.h"
 #include "knn_radix_pick.h"
 #include "knn_mask_split.h"
+#include "knn_self_window.h"
 
 #include <limits.h>
 #include <math.h>
@@ -329,6 +330,8 @@ struct knn_index {
         size_t large_bytes = 0;
         u64 *mask = nullptr;       // the masked calls: what knn_masked_plan says (the prefix of the granules' admitted rows, their counts)
         size_t mask_bytes = 0;
+        u64 *self = nullptr;       // knn_index_self_topk's through way: what knn_self_plan says (the plain call's K + 1 keys per row, a fold's K)
+        size_t self_bytes = 0;
     } topk[KNN_SLOTS];
     // Calls on one index from several host threads are serialised (enqueueing a batch is ~20 us of host work; the GPU
     // work of different slots still overlaps): the workspaces' lazily grown buffers, the event list, the statistics and
@@ -814,6 +817,7 @@ void knn_index_destroy(knn_index *idx)
             (void)knn_dev_free(t.count);
             (void)knn_dev_free(t.large);
             (void)knn_dev_free(t.mask);
+            (void)knn_dev_free(t.self);
         }
         knn_dev_free_end_synced();
         for (auto &ev : idx->events) {
@@ -1966,6 +1970,216 @@ int knn_debug_masked_lists_plan(const long long in[6], long long out[8])
     return KNN_OK;
 }
 
+// ---- queries about the shard's own rows (include/knn_mi355x.h 2i; knn_self.hip) -------------------------------------------------
+// (one message per rule, in the header's order, the index before the one rule that needs it: tests/test_self_logic.py tells them
+// apart without a GPU)
+int knn_index_self_topk(knn_index *idx, int slot, long long row_first, int rows, int K, float max_dist2, unsigned long long *keys_dev,
+                        int *indices_dev, void *stream, unsigned flags)
+{
+    if (!(max_dist2 >= 0.0f))
+        return fail(KNN_EINVAL, "knn_index_self_topk: max_dist2 must be >= 0 and not NaN");
+    constexpr unsigned kSelfTopkFlags = KNN_QUERY_INIT_KEYS | KNN_QUERY_TOPK_GRID | KNN_QUERY_TOPK_FRAMES;   // the three it admits
+    if ((flags & ~kSelfTopkFlags) != 0u)
+        return fail(KNN_EINVAL, "knn_index_self_topk: unknown flag (KNN_QUERY_INIT_KEYS, KNN_QUERY_TOPK_GRID, KNN_QUERY_TOPK_FRAMES)");
+    if (slot < 0 || slot >= KNN_SLOTS)
+        return fail(KNN_EINVAL, "knn_index_self_topk: slot outside 0 .. 7");
+    if (rows < 1)
+        return fail(KNN_EINVAL, "knn_index_self_topk: rows < 1");
+    if (row_first < 0)
+        return fail(KNN_EINVAL, "knn_index_self_topk: row_first < 0");
+    if (K < 1 || K > KNN_TOPK_MAX)
+        return fail(KNN_EINVAL, "knn_index_self_topk: K outside 1 .. 64");
+    if ((long long)rows * K > INT_MAX)
+        return fail(KNN_EINVAL, "knn_index_self_topk: rows * K above INT_MAX");
+    if (!keys_dev)
+        return fail(KNN_EINVAL, "knn_index_self_topk: null keys");
+    if (!idx)
+        return fail(KNN_EINVAL, "knn_index_self_topk: null index");
+    std::lock_guard<std::recursive_mutex> lock(idx->mu);
+    if (row_first > idx->n || (long long)rows > idx->n - row_first)
+        return fail(KNN_EINVAL, "knn_index_self_topk: row_first + rows above the shard's rows");
+    DeviceGuard guard(idx->device);
+    if (!guard.ok)
+        return fail(KNN_EHIP, "knn_index_self_topk: hipSetDevice failed");
+    // (-0 counts as 0; the queries are the resident rows: the scans read them in place, the through way is handed their address)
+    TopkCall call = topk_call_of(rows, K, idx->refs + (size_t)row_first * (size_t)idx->k, keys_dev, stream, max_dist2 == 0.0f ? 0.0f : max_dist2);
+    call.init = (flags & KNN_QUERY_INIT_KEYS) != 0u;
+    hipStream_t s = call.stream;
+    const int mk = rows * K;
+    const SelfPlan plan = knn_self_plan(idx->k, rows, K, idx->n, idx->num_cu, call.init != 0);
+    knn_index::TopkSlot &ts = idx->topk[slot];
+    // a cell-range shard's keys carry its rows' global numbers (gids); an index-range shard's base + row
+    const unsigned *gids = idx->sharded && idx->filter.cells ? idx->filter.cells->gids : nullptr;
+    // The way: what the one route function says for the plain call of K + 1 neighbours — self is among ITS candidates — with
+    // this call's rows, flags and options.  Exact, or no room for K + 1 keys — K = 64, or rows * (K + 1) beyond the plain call's
+    // own INT_MAX limit —: the self-scan with K (the header's 2i says so).
+    const bool through = K + 1 <= KNN_TOPK_MAX && (long long)rows * (K + 1) <= INT_MAX && knn_query_route(route_inputs(idx, rows, K + 1, flags)).way != QueryWay::Exact;
+    if (through) {
+        // the plain call as it is, K + 1 keys per row into the slot's scratch; its fallbacks and statistics are its own
+        KNN_TRY(slot_buffer_grow(ts.self, ts.self_bytes, plan.through_bytes));
+        const TopkCall plain = topk_call_of(rows, K + 1, call.q, ts.self, stream, call.max_dist2);
+        KNN_TRY(query_topk(idx, slot, plain, nullptr, flags | KNN_QUERY_INIT_KEYS, "knn_index_self_topk"));
+        u64 *kept = call.init ? call.keys : ts.self + (size_t)rows * (size_t)(K + 1);
+        HIP_TRY(knn_self_drop_launch(rows, K, ts.self, row_first, idx->base, gids, kept, s));
+        if (!call.init)
+            HIP_TRY(knn_topk_merge_launch(rows, K, kept, call.keys, s));
+    } else {
+        idx->stats[0] = 1;
+        idx->stats[1] = 0;
+        idx->stats[2] = 0;
+        idx->stats[3] = 0;
+        idx->grid_topk_gate = nullptr;
+        idx->last_slot = slot;
+        call.k = idx->k;
+        call.n = idx->n;
+        call.base = idx->base;
+        call.gids = gids;
+        call.r = idx->refs;
+        call.num_cu = idx->num_cu;
+        KNN_TRY(slot_buffer_grow(ts.part, ts.part_bytes, plan.part_bytes));
+        call.part = ts.part;
+        call.part_bytes = ts.part_bytes;
+        EventPair *ev = nullptr;
+        KNN_TRY(next_event_pair(idx, false, &ev));
+        call.ev0 = ev ? ev->first : nullptr;
+        call.ev1 = ev ? ev->second : nullptr;
+        HIP_TRY(knn_self_topk_launch(call, row_first));
+    }
+    if (indices_dev)
+        HIP_TRY(knn_keys_unpack_launch(call.keys, mk, indices_dev, s));
+    return KNN_OK;
+}
+
+int knn_index_self_count_within(knn_index *idx, int slot, long long row_first, int rows, float max_dist2, unsigned *counts_dev,
+                                void *stream, unsigned flags)
+{
+    if (!(max_dist2 >= 0.0f))
+        return fail(KNN_EINVAL, "knn_index_self_count_within: max_dist2 must be >= 0 and not NaN");
+    if ((flags & ~(unsigned)KNN_QUERY_INIT_KEYS) != 0u)
+        return fail(KNN_EINVAL, "knn_index_self_count_within: unknown flag (KNN_QUERY_INIT_KEYS alone is admitted)");
+    if (slot < 0 || slot >= KNN_SLOTS)
+        return fail(KNN_EINVAL, "knn_index_self_count_within: slot outside 0 .. 7");
+    if (rows < 1)
+        return fail(KNN_EINVAL, "knn_index_self_count_within: rows < 1");
+    if (row_first < 0)
+        return fail(KNN_EINVAL, "knn_index_self_count_within: row_first < 0");
+    if (!counts_dev)
+        return fail(KNN_EINVAL, "knn_index_self_count_within: null counts");
+    if (!idx)
+        return fail(KNN_EINVAL, "knn_index_self_count_within: null index");
+    std::lock_guard<std::recursive_mutex> lock(idx->mu);
+    if (row_first > idx->n || (long long)rows > idx->n - row_first)
+        return fail(KNN_EINVAL, "knn_index_self_count_within: row_first + rows above the shard's rows");
+    DeviceGuard guard(idx->device);
+    if (!guard.ok)
+        return fail(KNN_EHIP, "knn_index_self_count_within: hipSetDevice failed");
+    CountCall call;
+    call.k = idx->k;
+    call.m = rows;
+    call.n = idx->n;
+    call.r = idx->refs;
+    call.counts = counts_dev;
+    call.max_dist2 = max_dist2 == 0.0f ? 0.0f : max_dist2;   // (-0 counts as 0)
+    call.num_cu = idx->num_cu;
+    call.stream = (hipStream_t)stream;
+    hipStream_t s = call.stream;
+    // one way on every index: no layout is consulted
+    idx->stats[0] = 1;
+    idx->stats[1] = 0;
+    idx->stats[2] = 0;
+    idx->stats[3] = 0;
+    idx->grid_topk_gate = nullptr;
+    idx->last_slot = slot;
+    // the scan ADDS to the caller's counts: an init call zeroes them first
+    if ((flags & KNN_QUERY_INIT_KEYS) != 0u)
+        HIP_TRY(hipMemsetAsync(counts_dev, 0, (size_t)rows * sizeof(unsigned), s));
+    EventPair *ev = nullptr;
+    KNN_TRY(next_event_pair(idx, false, &ev));
+    call.ev0 = ev ? ev->first : nullptr;
+    call.ev1 = ev ? ev->second : nullptr;
+    HIP_TRY(knn_self_count_launch(call, row_first));
+    return KNN_OK;
+}
+
+int knn_index_self_list_within(knn_index *idx, int slot, long long row_first, int rows, float max_dist2,
+                               const unsigned long long *offsets_dev, unsigned *fill_dev, unsigned long long *keys_dev, void *stream,
+                               unsigned flags)
+{
+    if (!(max_dist2 >= 0.0f))
+        return fail(KNN_EINVAL, "knn_index_self_list_within: max_dist2 must be >= 0 and not NaN");
+    if ((flags & ~(unsigned)KNN_QUERY_INIT_KEYS) != 0u)
+        return fail(KNN_EINVAL, "knn_index_self_list_within: unknown flag (KNN_QUERY_INIT_KEYS alone is admitted)");
+    if (slot < 0 || slot >= KNN_SLOTS)
+        return fail(KNN_EINVAL, "knn_index_self_list_within: slot outside 0 .. 7");
+    if (rows < 1)
+        return fail(KNN_EINVAL, "knn_index_self_list_within: rows < 1");
+    if (row_first < 0)
+        return fail(KNN_EINVAL, "knn_index_self_list_within: row_first < 0");
+    if (!offsets_dev || !fill_dev || !keys_dev)
+        return fail(KNN_EINVAL, "knn_index_self_list_within: null offsets, fill or keys");
+    if (!idx)
+        return fail(KNN_EINVAL, "knn_index_self_list_within: null index");
+    std::lock_guard<std::recursive_mutex> lock(idx->mu);
+    if (row_first > idx->n || (long long)rows > idx->n - row_first)
+        return fail(KNN_EINVAL, "knn_index_self_list_within: row_first + rows above the shard's rows");
+    DeviceGuard guard(idx->device);
+    if (!guard.ok)
+        return fail(KNN_EHIP, "knn_index_self_list_within: hipSetDevice failed");
+    ListCall call;
+    call.k = idx->k;
+    call.m = rows;
+    call.n = idx->n;
+    call.base = idx->base;
+    // a cell-range shard's keys carry its rows' global numbers (gids); an index-range shard's base + row
+    call.gids = idx->sharded && idx->filter.cells ? idx->filter.cells->gids : nullptr;
+    call.r = idx->refs;
+    call.offsets = (const u64 *)offsets_dev;
+    call.fill = fill_dev;
+    call.keys = (u64 *)keys_dev;
+    call.max_dist2 = max_dist2 == 0.0f ? 0.0f : max_dist2;   // (-0 counts as 0)
+    call.num_cu = idx->num_cu;
+    call.stream = (hipStream_t)stream;
+    hipStream_t s = call.stream;
+    // one way on every index: no layout is consulted
+    idx->stats[0] = 1;
+    idx->stats[1] = 0;
+    idx->stats[2] = 0;
+    idx->stats[3] = 0;
+    idx->grid_topk_gate = nullptr;
+    idx->last_slot = slot;
+    // the scan APPENDS behind the caller's fill: an init call zeroes it first
+    if ((flags & KNN_QUERY_INIT_KEYS) != 0u)
+        HIP_TRY(hipMemsetAsync(fill_dev, 0, (size_t)rows * sizeof(unsigned), s));
+    EventPair *ev = nullptr;
+    KNN_TRY(next_event_pair(idx, false, &ev));
+    call.ev0 = ev ? ev->first : nullptr;
+    call.ev1 = ev ? ev->second : nullptr;
+    HIP_TRY(knn_self_list_launch(call, row_first));
+    return KNN_OK;
+}
+
+int knn_debug_self_plan(const long long in[6], long long out[8])
+{
+    if (!in || !out || in[0] < 1 || in[0] > INT_MAX || in[1] < 1 || in[1] > INT_MAX || in[2] < -1 || in[2] > KNN_TOPK_MAX ||
+        (in[2] > 0 && in[1] * in[2] > INT_MAX) || in[3] < in[1] || in[3] > (1ll << 32) || in[4] < 1 || in[4] > INT_MAX ||
+        (in[5] != 0 && in[5] != 1))
+        return fail(KNN_EINVAL, "knn_debug_self_plan: bad arguments (k >= 1, rows >= 1, -1 <= K <= 64, rows * K <= INT_MAX, "
+                                "rows <= the shard's rows <= 2^32, CUs >= 1, init 0 or 1)");
+    const SelfPlan p = knn_self_plan((int)in[0], (int)in[1], (int)in[2], in[3], (int)in[4], in[5] != 0);
+    const long long v[8] = {p.chunks, p.slices, p.groups, (long long)p.lds_bytes, (long long)p.part_bytes, p.launches, p.chunk_m,
+                            (long long)p.through_bytes};
+    memcpy(out, v, sizeof v);
+    return KNN_OK;
+}
+
+int knn_debug_self_ranges(long long i0, long long i1, long long w0, long long w1, long long out[6])
+{
+    if (!out)
+        return fail(KNN_EINVAL, "knn_debug_self_ranges: null out");
+    knn_self_ranges(i0, i1, w0, w1, out);
+    return KNN_OK;
+}
+
 int knn_debug_filter_scores(knn_index *idx, int m, const float *queries_dev, float *scores_dev,
                             float *qnorm_dev, double consts[8])
 {
@@ -2682,6 +2896,145 @@ extern "C" int knn_index_list_within_host(knn_index *idx, int m, const float *qu
         }
     }
     for (int j = 0; j <= m; ++j)
+        offsets_host[j] = (long long)offs[(size_t)j];
+    *indices_out = ind;
+    if (dist2_out)
+        *dist2_out = d2;
+    // (not declared waited: the slot's buffers go back after the device-wide wait `stage` then makes itself, as the other host calls)
+    return KNN_OK;
+}
+
+// ---- the whole shard about its own rows (include/knn_mi355x.h 2i): the kNN graph and the radius graph, synchronous ---------------
+extern "C" int knn_index_self_topk_host(knn_index *idx, int K, float max_dist2, int *indices_host, float *dist2_host, int *counts_host)
+{
+    if (!(max_dist2 >= 0.0f))
+        return fail(KNN_EINVAL, "knn_index_self_topk_host: max_dist2 must be >= 0 and not NaN");
+    if (K < 1 || K > KNN_TOPK_MAX)
+        return fail(KNN_EINVAL, "knn_index_self_topk_host: K outside 1 .. 64");
+    if (!indices_host)
+        return fail(KNN_EINVAL, "knn_index_self_topk_host: null indices");
+    if (!idx)
+        return fail(KNN_EINVAL, "knn_index_self_topk_host: null index");
+    std::lock_guard<std::recursive_mutex> lock(idx->mu);
+    if (idx->n == 0)
+        return KNN_OK;
+    DeviceGuard guard(idx->device);
+    if (!guard.ok)
+        return fail(KNN_EHIP, "knn_index_self_topk_host: hipSetDevice failed");
+    const long long step = KNN_TOPK_CHUNK;   // rows per call: step * K stays far below INT_MAX
+    Staging stage(idx->device);
+    u64 *keys_dev = nullptr;
+    hipError_t e = stage.get(&keys_dev, (size_t)std::min(step, idx->n) * (size_t)K * sizeof(u64));
+    if (e != hipSuccess)
+        return fail(KNN_EHIP, "knn_index_self_topk_host: staging keys", hipGetErrorString(e));
+    std::vector<u64> keys((size_t)std::min(step, idx->n) * (size_t)K);
+    for (long long r0 = 0; r0 < idx->n; r0 += step) {
+        const int rc = (int)std::min(step, idx->n - r0);
+        const int rv = knn_index_self_topk(idx, 0, r0, rc, K, max_dist2, keys_dev, nullptr, nullptr, KNN_QUERY_INIT_KEYS);
+        if (rv != KNN_OK)
+            return rv;
+        const size_t mk = (size_t)rc * (size_t)K, at = (size_t)r0 * (size_t)K;
+        e = hipMemcpy(keys.data(), keys_dev, mk * sizeof(u64), hipMemcpyDeviceToHost);
+        if (e != hipSuccess)
+            return fail(KNN_EHIP, "knn_index_self_topk_host: D2H keys", hipGetErrorString(e));
+        for (size_t i = 0; i < mk; ++i) {
+            indices_host[at + i] = (int)(unsigned)(keys[i] & 0xFFFFFFFFull);
+            if (dist2_host) {
+                const unsigned hi = (unsigned)(keys[i] >> 32);
+                memcpy(&dist2_host[at + i], &hi, sizeof hi);
+            }
+        }
+        if (counts_host)
+            for (int j = 0; j < rc; ++j) {   // padding is KNN_KEY_INIT; a real key is below it
+                int c = 0;
+                while (c < K && keys[(size_t)j * K + c] < kKeyInit)
+                    ++c;
+                counts_host[r0 + j] = c;
+            }
+    }
+    // (not declared waited: the buffers go back after the device-wide wait `stage` then makes itself, as the other host calls)
+    return KNN_OK;
+}
+
+extern "C" int knn_index_self_list_within_host(knn_index *idx, float max_dist2, long long *offsets_host, int **indices_out,
+                                               float **dist2_out)
+{
+    if (!(max_dist2 >= 0.0f))
+        return fail(KNN_EINVAL, "knn_index_self_list_within_host: max_dist2 must be >= 0 and not NaN");
+    if (!offsets_host || !indices_out)
+        return fail(KNN_EINVAL, "knn_index_self_list_within_host: null offsets or indices");
+    if (!idx)
+        return fail(KNN_EINVAL, "knn_index_self_list_within_host: null index");
+    *indices_out = nullptr;
+    if (dist2_out)
+        *dist2_out = nullptr;
+    std::lock_guard<std::recursive_mutex> lock(idx->mu);
+    if (idx->n > INT_MAX)
+        return fail(KNN_EINVAL, "knn_index_self_list_within_host: more than INT_MAX rows (use the device calls, a block of rows at a time)");
+    DeviceGuard guard(idx->device);
+    if (!guard.ok)
+        return fail(KNN_EHIP, "knn_index_self_list_within_host: hipSetDevice failed");
+    const int n = (int)idx->n;
+    const int step = KNN_TOPK_CHUNK;   // rows per call
+    std::vector<u64> offs((size_t)n + 1, 0ull);
+    std::vector<u64> keys;
+    Staging stage(idx->device);
+    if (n > 0) {
+        unsigned *c_dev = nullptr, *fill_dev = nullptr;
+        u64 *off_dev = nullptr, *keys_dev = nullptr;
+        const size_t cbytes = (size_t)n * sizeof(unsigned), obytes = ((size_t)n + 1) * sizeof(u64);
+        hipError_t e = stage.get(&c_dev, cbytes);
+        if (e == hipSuccess)
+            e = stage.get(&fill_dev, cbytes);
+        if (e == hipSuccess)
+            e = stage.get(&off_dev, obytes);
+        if (e != hipSuccess)
+            return fail(KNN_EHIP, "knn_index_self_list_within_host: staging counts", hipGetErrorString(e));
+        // count -> offsets, then the one synchronisation: the total sizes the keys
+        int rv = KNN_OK;
+        for (int r0 = 0; r0 < n && rv == KNN_OK; r0 += step)
+            rv = knn_index_self_count_within(idx, 0, r0, std::min(step, n - r0), max_dist2, c_dev + r0, nullptr, KNN_QUERY_INIT_KEYS);
+        if (rv == KNN_OK)
+            rv = knn_counts_to_offsets(idx->device, c_dev, n, off_dev, nullptr);
+        if (rv != KNN_OK)
+            return rv;
+        e = hipMemcpy(offs.data(), off_dev, obytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess)
+            return fail(KNN_EHIP, "knn_index_self_list_within_host: D2H offsets", hipGetErrorString(e));
+        const u64 total = offs[(size_t)n];
+        keys.resize((size_t)total);
+        if (total) {   // list -> sort (the offsets are absolute: every block of rows stores into the one keys array)
+            e = stage.get(&keys_dev, (size_t)total * sizeof(u64));
+            if (e != hipSuccess)
+                return fail(KNN_EHIP, "knn_index_self_list_within_host: staging keys", hipGetErrorString(e));
+            for (int r0 = 0; r0 < n && rv == KNN_OK; r0 += step)
+                rv = knn_index_self_list_within(idx, 0, r0, std::min(step, n - r0), max_dist2, off_dev + r0, fill_dev + r0, keys_dev, nullptr,
+                                                KNN_QUERY_INIT_KEYS);
+            if (rv == KNN_OK)
+                rv = knn_keys_sort_segments(idx->device, n, off_dev, fill_dev, keys_dev, nullptr);
+            if (rv != KNN_OK)
+                return rv;
+            e = hipMemcpy(keys.data(), keys_dev, (size_t)total * sizeof(u64), hipMemcpyDeviceToHost);
+            if (e != hipSuccess)
+                return fail(KNN_EHIP, "knn_index_self_list_within_host: D2H keys", hipGetErrorString(e));
+        }
+    }
+    const size_t total = keys.size(), room = total ? total : 1u;
+    int *ind = (int *)malloc(room * sizeof(int));
+    float *d2 = dist2_out ? (float *)malloc(room * sizeof(float)) : nullptr;
+    if (!ind || (dist2_out && !d2)) {
+        free(ind);
+        free(d2);
+        return fail(KNN_EHIP, "knn_index_self_list_within_host: out of host memory");
+    }
+    for (size_t i = 0; i < total; ++i) {
+        ind[i] = (int)(unsigned)(keys[i] & 0xFFFFFFFFull);
+        if (d2) {
+            const unsigned hi = (unsigned)(keys[i] >> 32);
+            memcpy(&d2[i], &hi, sizeof hi);
+        }
+    }
+    for (int j = 0; j <= n; ++j)
         offsets_host[j] = (long long)offs[(size_t)j];
     *indices_out = ind;
     if (dist2_out)

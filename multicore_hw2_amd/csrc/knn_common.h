@@ -318,6 +318,31 @@ hipError_t knn_masked_list_launch(const ListCall &c, const MaskedListsPlan &p, c
 hipError_t knn_masked_large_launch(const TopkCall &c, const MaskedListsPlan &p, const unsigned *mask, u64 *scratch,
                                    const unsigned **tie_word);
 
+// ---- queries about the shard's own rows (knn_self.hip; DESIGN §4.6 "About the shard's own rows") --------------------------------
+// Everything one self call launches with and the slot's scratch it needs: the one place both are decided (knn_debug_self_plan
+// shows it).  m: the call's rows (its queries); K >= 1: a top-K call, K <= 0: a count or a list call.  Chunks, slices, LDS and the
+// per-slice lists are the plain exact scan's for m queries, so the slot's buffers are sized as before.
+struct SelfPlan {
+    int chunks = 0, chunk_m = 0;     // launch sequences of <= KNN_TOPK_CHUNK rows; rows of the first
+    long long slices = 0;            // blocks along the shard's rows for the first chunk: knn_topk_slices / knn_count_slices
+    long long groups = 0;            // query groups of 64 of the first chunk: the grid's other side, one window each
+    size_t lds_bytes = 0;            // dynamic LDS of the scan: the top-K's sorted columns [K][64] u64; count and list have none
+    size_t part_bytes = 0;           // the top-K scan's per-slice lists; count and list have none
+    long long launches = 0;          // kernel launches of an init call on the self-scan: per chunk the scan (and the select)
+    size_t through_bytes = 0;        // top-K, K + 1 <= KNN_TOPK_MAX: the through way's lists [m][K + 1], plus [m][K] for a folding call
+};
+SelfPlan knn_self_plan(int k, int m, int K, long long n, int num_cu, bool init);
+// The three exact self-scans: the contracts of knn_exact_topk_launch (limit = true), knn_exact_count_launch and
+// knn_exact_list_launch with query j = local row row_first + j of the shard, which is no candidate for itself (identity by local
+// row number: other copies of the row stay candidates).  c.q is not read.  0 <= row_first, row_first + c.m <= c.n.
+hipError_t knn_self_topk_launch(const TopkCall &c, long long row_first);
+hipError_t knn_self_count_launch(const CountCall &c, long long row_first);
+hipError_t knn_self_list_launch(const ListCall &c, long long row_first);
+// out[j][0 .. K) <- lists[j][0 .. K] (sorted, K + 1 <= KNN_TOPK_MAX keys) without the real key that carries the global number of
+// local row row_first + j (base + row, or gids[row]) — without the last key when there is none.
+hipError_t knn_self_drop_launch(int m, int K, const u64 *lists, long long row_first, long long base, const unsigned *gids, u64 *out,
+                                hipStream_t stream);
+
 // ---- MFMA filter + exact re-rank (knn_filter.hip) ---------------------------
 // Device-side control words of one filter query (FilterState::ctl).
 enum {
