@@ -580,6 +580,59 @@ int knn_index_self_list_within_host(knn_index *idx, float max_dist2, long long *
 int knn_debug_self_plan(const long long in[6], long long out[8]);
 int knn_debug_self_ranges(long long i0, long long i1, long long w0, long long w1, long long out[6]);
 
+/* ------------------------------------------------------------------------
+ * 2j. A radius per query: the counts and lists of 2d, 2e and 2i with ONE RADIUS FOR EVERY QUERY, read from a device array — ball
+ * queries at each point's own scale, and "everything within the K-th neighbour's distance" (k-distance neighbourhoods with their
+ * ties, core distances, locally scaled kernels) without a copy to the host or a synchronisation in between:
+ *
+ *   a top-K call  ->  knn_keys_column_dist2 (column K - 1)  ->  knn_index_count_within_each  ->  knn_counts_to_offsets
+ *   ->  knn_index_list_within_each  ->  knn_keys_sort_segments
+ *
+ * max_dist2_dev is a device array of m (self forms: rows) floats on the index's device, borrowed for the call and read by its
+ * kernels; no value in it is ever checked on the host.  cap is a host float, >= 0 or +INF, not NaN: an upper bound the caller
+ * states for the radii; pass +INF when there is none.
+ * Candidate rule: a row is a hit for query j when its v0 distance E is finite AND E <= max_dist2_dev[j] AND E <= cap — E in fp32,
+ * accumulated in dimension order, no FMA; both tests plain fp32 compares with equality inside.  So a NaN or negative radius gives
+ * query j no hit (never an error, never a fallback), -0 counts as 0, +INF is every row with a finite distance (under cap), and a
+ * query with a non-finite coordinate has no hit, as in 2d.  Where a kernel prunes or stops by the radius it uses the query's bound,
+ * max_dist2_dev[j] <= cap ? max_dist2_dev[j] : cap, and a query without candidates (max_dist2_dev[j] >= 0 fails) does no work.
+ * cap is what lets the host plan: the way is chosen exactly as for the scalar call at max_dist2 = cap — the grid's ring limit from
+ * cap, the cell-pruned way only at a finite cap — so knn_debug_count_plan describes these calls too.
+ *
+ * knn_index_count_within_each, knn_index_list_within_each: 2d and 2e word for word with the rule above — folding and
+ * KNN_QUERY_INIT_KEYS, slots, the fill_dev / room / overflow contract, the global numbers in the keys (base_index + row, or the
+ * gid), knn_index_last_stats; flags KNN_QUERY_INIT_KEYS, KNN_QUERY_COUNT_GRID, KNN_QUERY_COUNT_CELLS with their 2d meaning.  On the
+ * grid way a query without candidates never makes the batch give up.
+ * knn_index_self_count_within_each, knn_index_self_list_within_each: 2i's count and list with the rule above (and i != row_first +
+ * j); max_dist2_dev[j] belongs to LOCAL row row_first + j; KNN_QUERY_INIT_KEYS is the only flag, the exact self-scan the only way.
+ * knn_keys_column_dist2: dist2_dev[j] = the float in the high word of keys_dev[j * K + column], 0 <= column < K, m >= 1; a
+ * padding key gives +INF.  Asynchronous on `stream`; m < 1, K < 1, a column outside 0 .. K - 1 or a null pointer are KNN_EINVAL.
+ *
+ * Argument errors of the four device calls are KNN_EINVAL, each with its own knn_last_error text prefixed by the function's name,
+ * checked in this order — the first that fails speaks, nothing is launched —: cap < 0 or NaN, an unknown flag, a slot outside
+ * 0 .. 7, m < 1 (self: rows < 1, then row_first < 0), a null queries pointer (not the self forms), a null radii pointer, a null
+ * counts pointer or a null offsets, fill or keys pointer, a null index, (self) row_first + rows > n_local. */
+int knn_index_count_within_each(knn_index *idx, int slot, int m, const float *queries_dev, const float *max_dist2_dev, float cap,
+                                unsigned *counts_dev, void *stream, unsigned flags);
+int knn_index_list_within_each(knn_index *idx, int slot, int m, const float *queries_dev, const float *max_dist2_dev, float cap,
+                               const unsigned long long *offsets_dev /*[m+1]*/, unsigned *fill_dev /*[m]*/,
+                               unsigned long long *keys_dev, void *stream, unsigned flags);
+int knn_index_self_count_within_each(knn_index *idx, int slot, long long row_first, int rows, const float *max_dist2_dev /*[rows]*/,
+                                     float cap, unsigned *counts_dev /*[rows]*/, void *stream, unsigned flags);
+int knn_index_self_list_within_each(knn_index *idx, int slot, long long row_first, int rows, const float *max_dist2_dev /*[rows]*/,
+                                    float cap, const unsigned long long *offsets_dev /*[rows+1]*/, unsigned *fill_dev /*[rows]*/,
+                                    unsigned long long *keys_dev, void *stream, unsigned flags);
+int knn_keys_column_dist2(int device, const unsigned long long *keys_dev, int m, int K, int column, float *dist2_dev, void *stream);
+/* Synchronous, host arrays in and out, this shard alone on the default way: knn_index_count_within_host and
+ * knn_index_list_within_host (its malloc'd arrays and their 1-entry rule included) with max_dist2_host [m] and cap. */
+int knn_index_count_within_each_host(knn_index *idx, int m, const float *queries_host, const float *max_dist2_host, float cap,
+                                     unsigned *counts_host);
+int knn_index_list_within_each_host(knn_index *idx, int m, const float *queries_host, const float *max_dist2_host, float cap,
+                                    long long *offsets_host, int **indices_out, float **dist2_out /*NULL ok*/);
+/* Test hook, host arithmetic only, through the kernels' own lines (knn_each_radius.h): out = {1 if a query of this radius has
+ * candidates else 0, its bound under cap (0 when it has none)}.  cap < 0 or NaN is KNN_EINVAL. */
+int knn_debug_each_radius(float radius, float cap, float out[2]);
+
 /* Tuning / test hooks.  Known names:
  *   "path"    0 = auto, 1 = exact VALU kernels only, 2 = force the MFMA filter
  *             (+ exact re-rank) where its preconditions hold, 3 = the uniform-grid spatial index

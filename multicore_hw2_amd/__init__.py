@@ -23,7 +23,9 @@ __all__ = ["lib", "lib_path", "cudaCallback", "KnnIndex", "KnnGeom", "KnnError",
            "list_within_masked_c", "query_topk_large_masked_c", "list_within_masked_host_c", "query_topk_large_masked_host_c",
            "debug_masked_lists_plan",
            "self_topk_c", "self_count_within_c", "self_list_within_c", "self_topk_host_c", "self_list_within_host_c",
-           "debug_self_plan", "debug_self_ranges"]
+           "debug_self_plan", "debug_self_ranges",
+           "count_within_each_c", "list_within_each_c", "self_count_within_each_c", "self_list_within_each_c",
+           "count_within_each_host_c", "list_within_each_host_c", "keys_column_dist2_c", "keys_column_dist2", "debug_each_radius"]
 
 KEY_INIT = 0x7F80000000000000
 
@@ -50,6 +52,9 @@ EXPORTED_SYMBOLS = [
     "knn_index_query_topk_large_masked_host", "knn_debug_masked_lists_plan",
     "knn_index_self_topk", "knn_index_self_count_within", "knn_index_self_list_within", "knn_index_self_topk_host",
     "knn_index_self_list_within_host", "knn_debug_self_plan", "knn_debug_self_ranges",
+    "knn_index_count_within_each", "knn_index_list_within_each", "knn_index_self_count_within_each",
+    "knn_index_self_list_within_each", "knn_keys_column_dist2", "knn_index_count_within_each_host",
+    "knn_index_list_within_each_host", "knn_debug_each_radius",
 ]
 TOPK_LARGE_MAX = 4096   # KNN_TOPK_LARGE_MAX
 QUERY_INIT_KEYS = 1   # KNN_QUERY_INIT_KEYS
@@ -705,6 +710,74 @@ def debug_self_ranges(i0, i1, w0, w1):
     return dict(zip(SELF_RANGES, list(out)))
 
 
+def count_within_each_c():
+    """knn_index_count_within_each with its argument types (set here, not in lib(), as count_within_c)."""
+    f = lib().knn_index_count_within_each
+    f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p,
+                  ctypes.c_void_p, ctypes.c_uint]
+    return f
+
+
+def list_within_each_c():
+    """knn_index_list_within_each with its argument types (set here, not in lib(), as count_within_c)."""
+    f = lib().knn_index_list_within_each
+    f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p,
+                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint]
+    return f
+
+
+def self_count_within_each_c():
+    """knn_index_self_count_within_each with its argument types (set here, not in lib(), as count_within_c)."""
+    f = lib().knn_index_self_count_within_each
+    f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p,
+                  ctypes.c_void_p, ctypes.c_uint]
+    return f
+
+
+def self_list_within_each_c():
+    """knn_index_self_list_within_each with its argument types (set here, not in lib(), as count_within_c)."""
+    f = lib().knn_index_self_list_within_each
+    f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p,
+                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint]
+    return f
+
+
+def count_within_each_host_c():
+    f = lib().knn_index_count_within_each_host
+    f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p]
+    return f
+
+
+def list_within_each_host_c():
+    f = lib().knn_index_list_within_each_host
+    f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p,
+                  ctypes.POINTER(ctypes.POINTER(ctypes.c_int)), ctypes.POINTER(ctypes.POINTER(ctypes.c_float))]
+    return f
+
+
+def keys_column_dist2_c():
+    f = lib().knn_keys_column_dist2
+    f.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    return f
+
+
+def keys_column_dist2(keys_dev, m, K, column, dist2_dev, device=0, stream=0):
+    """Async (knn_keys_column_dist2): dist2_dev[j] (float32) <- the distance half of keys_dev[j * K + column], +INF for a padding
+    key: a column of a top-K call's lists as the radii of a *_within_each call, without leaving the device."""
+    _check(keys_column_dist2_c()(int(device), ctypes.c_void_p(int(keys_dev)), int(m), int(K), int(column),
+                                 ctypes.c_void_p(int(dist2_dev)), ctypes.c_void_p(stream)))
+
+
+def debug_each_radius(radius, cap):
+    """knn_debug_each_radius: (whether a query of this radius has candidates, its bound under cap) through the kernels' own lines
+    (knn_each_radius.h).  Host arithmetic; works without a GPU."""
+    out = (ctypes.c_float * 2)()
+    f = lib().knn_debug_each_radius
+    f.argtypes = [ctypes.c_float, ctypes.c_float, ctypes.POINTER(ctypes.c_float)]
+    _check(f(float(radius), float(cap), out))
+    return bool(out[0]), float(out[1])
+
+
 def counts_to_offsets_c():
     f = lib().knn_counts_to_offsets
     f.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
@@ -938,6 +1011,62 @@ class KnnIndex:
             free(d2)
         return offsets, indices, dist2
 
+    def count_within_each(self, m, queries_dev, max_dist2_dev, counts_dev, cap=float("inf"), stream=0, slot=0, init=False,
+                          grid=False, cells=False):
+        """Async (knn_index_count_within_each): count_within with a radius per query — max_dist2_dev[m] (float32, on the device):
+        a row counts for query j when its v0 squared distance is finite, <= max_dist2_dev[j] and <= cap.  A NaN or negative radius
+        counts nothing.  cap (>= 0 or +INF): the caller's bound for the radii; the way is the scalar call's at max_dist2 = cap
+        (cells needs a finite cap).  init, grid, cells: as count_within."""
+        _check(count_within_each_c()(self._h, int(slot), int(m), ctypes.c_void_p(int(queries_dev)), ctypes.c_void_p(int(max_dist2_dev)),
+                                     float(cap), ctypes.c_void_p(int(counts_dev)), ctypes.c_void_p(stream),
+                                     (QUERY_INIT_KEYS if init else 0) | (QUERY_COUNT_GRID if grid else 0) |
+                                     (QUERY_COUNT_CELLS if cells else 0)))
+
+    def list_within_each(self, m, queries_dev, max_dist2_dev, offsets_dev, fill_dev, keys_dev, cap=float("inf"), stream=0, slot=0,
+                         init=False, grid=False, cells=False):
+        """Async (knn_index_list_within_each): list_within with a radius per query, under count_within_each's rule.  The third
+        step of count_within_each -> counts_to_offsets -> this -> keys_sort_segments."""
+        _check(list_within_each_c()(self._h, int(slot), int(m), ctypes.c_void_p(int(queries_dev)), ctypes.c_void_p(int(max_dist2_dev)),
+                                    float(cap), ctypes.c_void_p(int(offsets_dev)), ctypes.c_void_p(int(fill_dev)),
+                                    ctypes.c_void_p(int(keys_dev)), ctypes.c_void_p(stream),
+                                    (QUERY_INIT_KEYS if init else 0) | (QUERY_COUNT_GRID if grid else 0) |
+                                    (QUERY_COUNT_CELLS if cells else 0)))
+
+    def count_within_each_host(self, queries, max_dist2, cap=float("inf")):
+        """Synchronous count of this shard alone with a radius per query (max_dist2: float32 [m] on the host): uint32 [m]."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1)
+        m = q.size // self.k
+        r = np.ascontiguousarray(max_dist2, dtype=np.float32).reshape(-1)
+        if r.size != m:
+            raise ValueError("max_dist2 must hold one radius per query")
+        counts = np.empty(m, dtype=np.uint32)
+        _check(count_within_each_host_c()(self._h, m, q.ctypes.data_as(ctypes.c_void_p), r.ctypes.data_as(ctypes.c_void_p), float(cap),
+                                          counts.ctypes.data_as(ctypes.c_void_p)))
+        return counts
+
+    def list_within_each_host(self, queries, max_dist2, cap=float("inf")):
+        """Synchronous lists of this shard alone with a radius per query (knn_index_list_within_each_host): what list_within_host
+        returns — (offsets int64 [m + 1], indices int32 [total], dist2 float32 [total]), nearest first within a query."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1)
+        m = q.size // self.k
+        r = np.ascontiguousarray(max_dist2, dtype=np.float32).reshape(-1)
+        if r.size != m:
+            raise ValueError("max_dist2 must hold one radius per query")
+        offsets = np.empty(m + 1, dtype=np.int64)
+        ind, d2 = ctypes.POINTER(ctypes.c_int)(), ctypes.POINTER(ctypes.c_float)()
+        _check(list_within_each_host_c()(self._h, m, q.ctypes.data_as(ctypes.c_void_p), r.ctypes.data_as(ctypes.c_void_p), float(cap),
+                                         offsets.ctypes.data_as(ctypes.c_void_p), ctypes.byref(ind), ctypes.byref(d2)))
+        total = int(offsets[m])
+        free = ctypes.CDLL(None).free
+        free.argtypes = [ctypes.c_void_p]
+        try:
+            indices = np.ctypeslib.as_array(ind, shape=(max(total, 1),))[:total].astype(np.int32, copy=True)
+            dist2 = np.ctypeslib.as_array(d2, shape=(max(total, 1),))[:total].astype(np.float32, copy=True)
+        finally:
+            free(ind)
+            free(d2)
+        return offsets, indices, dist2
+
     def query_topk_large(self, m, K, queries_dev, keys_dev, max_dist2=float("inf"), stream=0, slot=0, init_keys=False,
                          indices_dev=None, flags=0):
         """Async (knn_index_query_topk_large): query_topk_within for 1 <= K <= 4096 — keys_dev[m][K] <- the K smallest keys of
@@ -1102,6 +1231,24 @@ class KnnIndex:
         _check(self_topk_host_c()(self._h, int(K), float(max_dist2), idx.ctypes.data_as(ctypes.c_void_p),
                                   d2.ctypes.data_as(ctypes.c_void_p), counts.ctypes.data_as(ctypes.c_void_p)))
         return idx, d2, counts
+
+    def self_count_within_each(self, row_first, rows, max_dist2_dev, counts_dev, cap=float("inf"), stream=0, slot=0, init=False,
+                               flags=0):
+        """Async (knn_index_self_count_within_each): self_count_within with a radius per row — max_dist2_dev[j] (float32, on the
+        device) belongs to local row row_first + j; another row counts when its v0 squared distance is finite, <= that radius and
+        <= cap.  A NaN or negative radius counts nothing."""
+        _check(self_count_within_each_c()(self._h, int(slot), int(row_first), int(rows), ctypes.c_void_p(int(max_dist2_dev)), float(cap),
+                                          ctypes.c_void_p(int(counts_dev)), ctypes.c_void_p(stream),
+                                          (QUERY_INIT_KEYS if init else 0) | int(flags)))
+
+    def self_list_within_each(self, row_first, rows, max_dist2_dev, offsets_dev, fill_dev, keys_dev, cap=float("inf"), stream=0,
+                              slot=0, init=False, flags=0):
+        """Async (knn_index_self_list_within_each): self_list_within under self_count_within_each's rule.  The third step of
+        self_count_within_each -> counts_to_offsets -> this -> keys_sort_segments."""
+        _check(self_list_within_each_c()(self._h, int(slot), int(row_first), int(rows), ctypes.c_void_p(int(max_dist2_dev)), float(cap),
+                                         ctypes.c_void_p(int(offsets_dev)), ctypes.c_void_p(int(fill_dev)),
+                                         ctypes.c_void_p(int(keys_dev)), ctypes.c_void_p(stream),
+                                         (QUERY_INIT_KEYS if init else 0) | int(flags)))
 
     def self_list_within_host(self, max_dist2):
         """Synchronous radius graph of this shard (knn_index_self_list_within_host) in CSR form: (offsets int64 [n + 1], indices

@@ -11,6 +11,7 @@
 #include "knn_radix_pick.h"
 #include "knn_mask_split.h"
 #include "knn_self_window.h"
+#include "knn_each_radius.h"
 
 #include <limits.h>
 #include <math.h>
@@ -40,6 +41,13 @@ int fail(int code, const char *what, const char *detail = nullptr)
         g_err += detail;
     }
     return code;
+}
+
+// "<who>: <what>[: <detail>]" — the text of a step that several entry points share
+int fail_in(int code, const char *who, const char *what, const char *detail = nullptr)
+{
+    const std::string text = std::string(who) + ": " + what;
+    return fail(code, text.c_str(), detail);
 }
 
 #define HIP_TRY(call)                                                                      \
@@ -1150,7 +1158,7 @@ int query_topk(knn_index *idx, int slot, TopkCall call, int *indices_dev, unsign
     std::lock_guard<std::recursive_mutex> lock(idx->mu);
     DeviceGuard guard(idx->device);
     if (!guard.ok)
-        return fail(KNN_EHIP, who, "hipSetDevice failed");
+        return fail_in(KNN_EHIP, who, "hipSetDevice failed");
     hipStream_t s = call.stream;
     const int m = call.m, K = call.K, mk = m * K;
     call.init = (flags & KNN_QUERY_INIT_KEYS) != 0u;
@@ -1312,27 +1320,15 @@ int knn_keys_topk_merge(int device, int m, int K, const unsigned long long *a_de
     return KNN_OK;
 }
 
-int knn_index_count_within(knn_index *idx, int slot, int m, const float *queries_dev, float max_dist2, unsigned *counts_dev,
-                           void *stream, unsigned flags)
+// A count call behind its argument checks: knn_index_count_within (radii_dev null, max_dist2 the radius) and
+// knn_index_count_within_each (radii_dev the radii, max_dist2 the cap — the way is chosen at the cap, the kernels are the each-forms).
+static int count_within_run(knn_index *idx, const char *who, int slot, int m, const float *queries_dev, const float *radii_dev,
+                            float max_dist2, unsigned *counts_dev, void *stream, unsigned flags)
 {
-    // (one message per rule, the index last: tests/test_count_logic.py tells them apart without a GPU)
-    if (!(max_dist2 >= 0.0f))
-        return fail(KNN_EINVAL, "knn_index_count_within: max_dist2 must be >= 0 and not NaN");
-    constexpr unsigned kCountFlags = KNN_QUERY_INIT_KEYS | KNN_QUERY_COUNT_GRID | KNN_QUERY_COUNT_CELLS;   // the three it admits
-    if ((flags & ~kCountFlags) != 0u)
-        return fail(KNN_EINVAL, "knn_index_count_within: unknown flag (KNN_QUERY_INIT_KEYS, KNN_QUERY_COUNT_GRID, KNN_QUERY_COUNT_CELLS)");
-    if (slot < 0 || slot >= KNN_SLOTS)
-        return fail(KNN_EINVAL, "knn_index_count_within: slot outside 0 .. 7");
-    if (m < 1)
-        return fail(KNN_EINVAL, "knn_index_count_within: m < 1");
-    if (!queries_dev || !counts_dev)
-        return fail(KNN_EINVAL, "knn_index_count_within: null queries or counts");
-    if (!idx)
-        return fail(KNN_EINVAL, "knn_index_count_within: null index");
     std::lock_guard<std::recursive_mutex> lock(idx->mu);
     DeviceGuard guard(idx->device);
     if (!guard.ok)
-        return fail(KNN_EHIP, "knn_index_count_within: hipSetDevice failed");
+        return fail_in(KNN_EHIP, who, "hipSetDevice failed");
     CountCall call;
     call.k = idx->k;
     call.m = m;
@@ -1340,6 +1336,7 @@ int knn_index_count_within(knn_index *idx, int slot, int m, const float *queries
     call.q = queries_dev;
     call.r = idx->refs;
     call.counts = counts_dev;
+    call.radii = radii_dev;
     call.max_dist2 = max_dist2 == 0.0f ? 0.0f : max_dist2;   // (-0 counts as 0)
     call.num_cu = idx->num_cu;
     call.stream = (hipStream_t)stream;
@@ -1373,7 +1370,7 @@ int knn_index_count_within(knn_index *idx, int slot, int m, const float *queries
     case QueryWay::Cells: {
         const CellTopkPlan tp = knn_cells_count_plan(ri.t);
         if (!tp.use)
-            return fail(KNN_EHIP, "knn_index_count_within: the cell-pruned scan has no pass shape for this layout");
+            return fail_in(KNN_EHIP, who, "the cell-pruned scan has no pass shape for this layout");
         HIP_TRY(knn_filter_query_count_cells(idx->filter, tp, slot, call));
         break;
     }
@@ -1386,6 +1383,26 @@ int knn_index_count_within(knn_index *idx, int slot, int m, const float *queries
         break;
     }
     return KNN_OK;
+}
+
+int knn_index_count_within(knn_index *idx, int slot, int m, const float *queries_dev, float max_dist2, unsigned *counts_dev,
+                           void *stream, unsigned flags)
+{
+    // (one message per rule, the index last: tests/test_count_logic.py tells them apart without a GPU)
+    if (!(max_dist2 >= 0.0f))
+        return fail(KNN_EINVAL, "knn_index_count_within: max_dist2 must be >= 0 and not NaN");
+    constexpr unsigned kCountFlags = KNN_QUERY_INIT_KEYS | KNN_QUERY_COUNT_GRID | KNN_QUERY_COUNT_CELLS;   // the three it admits
+    if ((flags & ~kCountFlags) != 0u)
+        return fail(KNN_EINVAL, "knn_index_count_within: unknown flag (KNN_QUERY_INIT_KEYS, KNN_QUERY_COUNT_GRID, KNN_QUERY_COUNT_CELLS)");
+    if (slot < 0 || slot >= KNN_SLOTS)
+        return fail(KNN_EINVAL, "knn_index_count_within: slot outside 0 .. 7");
+    if (m < 1)
+        return fail(KNN_EINVAL, "knn_index_count_within: m < 1");
+    if (!queries_dev || !counts_dev)
+        return fail(KNN_EINVAL, "knn_index_count_within: null queries or counts");
+    if (!idx)
+        return fail(KNN_EINVAL, "knn_index_count_within: null index");
+    return count_within_run(idx, "knn_index_count_within", slot, m, queries_dev, nullptr, max_dist2, counts_dev, stream, flags);
 }
 
 int knn_debug_count_plan(const long long in[16], long long out[8])
@@ -1448,28 +1465,15 @@ int knn_keys_sort_segments(int device, int m, const unsigned long long *offsets_
     return KNN_OK;
 }
 
-int knn_index_list_within(knn_index *idx, int slot, int m, const float *queries_dev, float max_dist2,
-                          const unsigned long long *offsets_dev, unsigned *fill_dev, unsigned long long *keys_dev, void *stream,
-                          unsigned flags)
+// A list call behind its argument checks: knn_index_list_within and knn_index_list_within_each, as count_within_run.
+static int list_within_run(knn_index *idx, const char *who, int slot, int m, const float *queries_dev, const float *radii_dev,
+                           float max_dist2, const unsigned long long *offsets_dev, unsigned *fill_dev, unsigned long long *keys_dev,
+                           void *stream, unsigned flags)
 {
-    // (one message per rule, the index last, as knn_index_count_within: tests/test_list_logic.py tells them apart without a GPU)
-    if (!(max_dist2 >= 0.0f))
-        return fail(KNN_EINVAL, "knn_index_list_within: max_dist2 must be >= 0 and not NaN");
-    constexpr unsigned kListFlags = KNN_QUERY_INIT_KEYS | KNN_QUERY_COUNT_GRID | KNN_QUERY_COUNT_CELLS;   // the three it admits
-    if ((flags & ~kListFlags) != 0u)
-        return fail(KNN_EINVAL, "knn_index_list_within: unknown flag (KNN_QUERY_INIT_KEYS, KNN_QUERY_COUNT_GRID, KNN_QUERY_COUNT_CELLS)");
-    if (slot < 0 || slot >= KNN_SLOTS)
-        return fail(KNN_EINVAL, "knn_index_list_within: slot outside 0 .. 7");
-    if (m < 1)
-        return fail(KNN_EINVAL, "knn_index_list_within: m < 1");
-    if (!queries_dev || !offsets_dev || !fill_dev || !keys_dev)
-        return fail(KNN_EINVAL, "knn_index_list_within: null queries, offsets, fill or keys");
-    if (!idx)
-        return fail(KNN_EINVAL, "knn_index_list_within: null index");
     std::lock_guard<std::recursive_mutex> lock(idx->mu);
     DeviceGuard guard(idx->device);
     if (!guard.ok)
-        return fail(KNN_EHIP, "knn_index_list_within: hipSetDevice failed");
+        return fail_in(KNN_EHIP, who, "hipSetDevice failed");
     ListCall call;
     call.k = idx->k;
     call.m = m;
@@ -1482,6 +1486,7 @@ int knn_index_list_within(knn_index *idx, int slot, int m, const float *queries_
     call.offsets = (const u64 *)offsets_dev;
     call.fill = fill_dev;
     call.keys = (u64 *)keys_dev;
+    call.radii = radii_dev;
     call.max_dist2 = max_dist2 == 0.0f ? 0.0f : max_dist2;   // (-0 counts as 0)
     call.num_cu = idx->num_cu;
     call.stream = (hipStream_t)stream;
@@ -1515,7 +1520,7 @@ int knn_index_list_within(knn_index *idx, int slot, int m, const float *queries_
     case QueryWay::Cells: {
         const CellTopkPlan tp = knn_cells_count_plan(ri.t);
         if (!tp.use)
-            return fail(KNN_EHIP, "knn_index_list_within: the cell-pruned scan has no pass shape for this layout");
+            return fail_in(KNN_EHIP, who, "the cell-pruned scan has no pass shape for this layout");
         HIP_TRY(knn_filter_query_list_cells(idx->filter, tp, slot, call));
         break;
     }
@@ -1528,6 +1533,28 @@ int knn_index_list_within(knn_index *idx, int slot, int m, const float *queries_
         break;
     }
     return KNN_OK;
+}
+
+int knn_index_list_within(knn_index *idx, int slot, int m, const float *queries_dev, float max_dist2,
+                          const unsigned long long *offsets_dev, unsigned *fill_dev, unsigned long long *keys_dev, void *stream,
+                          unsigned flags)
+{
+    // (one message per rule, the index last, as knn_index_count_within: tests/test_list_logic.py tells them apart without a GPU)
+    if (!(max_dist2 >= 0.0f))
+        return fail(KNN_EINVAL, "knn_index_list_within: max_dist2 must be >= 0 and not NaN");
+    constexpr unsigned kListFlags = KNN_QUERY_INIT_KEYS | KNN_QUERY_COUNT_GRID | KNN_QUERY_COUNT_CELLS;   // the three it admits
+    if ((flags & ~kListFlags) != 0u)
+        return fail(KNN_EINVAL, "knn_index_list_within: unknown flag (KNN_QUERY_INIT_KEYS, KNN_QUERY_COUNT_GRID, KNN_QUERY_COUNT_CELLS)");
+    if (slot < 0 || slot >= KNN_SLOTS)
+        return fail(KNN_EINVAL, "knn_index_list_within: slot outside 0 .. 7");
+    if (m < 1)
+        return fail(KNN_EINVAL, "knn_index_list_within: m < 1");
+    if (!queries_dev || !offsets_dev || !fill_dev || !keys_dev)
+        return fail(KNN_EINVAL, "knn_index_list_within: null queries, offsets, fill or keys");
+    if (!idx)
+        return fail(KNN_EINVAL, "knn_index_list_within: null index");
+    return list_within_run(idx, "knn_index_list_within", slot, m, queries_dev, nullptr, max_dist2, offsets_dev, fill_dev, keys_dev, stream,
+                           flags);
 }
 
 int knn_index_query_topk_large(knn_index *idx, int slot, int m, int K, const float *queries_dev, float max_dist2,
@@ -2050,35 +2077,24 @@ int knn_index_self_topk(knn_index *idx, int slot, long long row_first, int rows,
     return KNN_OK;
 }
 
-int knn_index_self_count_within(knn_index *idx, int slot, long long row_first, int rows, float max_dist2, unsigned *counts_dev,
-                                void *stream, unsigned flags)
+// A self count call behind its host-only argument checks: knn_index_self_count_within (radii_dev null) and
+// knn_index_self_count_within_each (radii_dev the radii of the call's rows, max_dist2 the cap).
+static int self_count_run(knn_index *idx, const char *who, int slot, long long row_first, int rows, const float *radii_dev,
+                          float max_dist2, unsigned *counts_dev, void *stream, unsigned flags)
 {
-    if (!(max_dist2 >= 0.0f))
-        return fail(KNN_EINVAL, "knn_index_self_count_within: max_dist2 must be >= 0 and not NaN");
-    if ((flags & ~(unsigned)KNN_QUERY_INIT_KEYS) != 0u)
-        return fail(KNN_EINVAL, "knn_index_self_count_within: unknown flag (KNN_QUERY_INIT_KEYS alone is admitted)");
-    if (slot < 0 || slot >= KNN_SLOTS)
-        return fail(KNN_EINVAL, "knn_index_self_count_within: slot outside 0 .. 7");
-    if (rows < 1)
-        return fail(KNN_EINVAL, "knn_index_self_count_within: rows < 1");
-    if (row_first < 0)
-        return fail(KNN_EINVAL, "knn_index_self_count_within: row_first < 0");
-    if (!counts_dev)
-        return fail(KNN_EINVAL, "knn_index_self_count_within: null counts");
-    if (!idx)
-        return fail(KNN_EINVAL, "knn_index_self_count_within: null index");
     std::lock_guard<std::recursive_mutex> lock(idx->mu);
     if (row_first > idx->n || (long long)rows > idx->n - row_first)
-        return fail(KNN_EINVAL, "knn_index_self_count_within: row_first + rows above the shard's rows");
+        return fail_in(KNN_EINVAL, who, "row_first + rows above the shard's rows");
     DeviceGuard guard(idx->device);
     if (!guard.ok)
-        return fail(KNN_EHIP, "knn_index_self_count_within: hipSetDevice failed");
+        return fail_in(KNN_EHIP, who, "hipSetDevice failed");
     CountCall call;
     call.k = idx->k;
     call.m = rows;
     call.n = idx->n;
     call.r = idx->refs;
     call.counts = counts_dev;
+    call.radii = radii_dev;
     call.max_dist2 = max_dist2 == 0.0f ? 0.0f : max_dist2;   // (-0 counts as 0)
     call.num_cu = idx->num_cu;
     call.stream = (hipStream_t)stream;
@@ -2101,30 +2117,17 @@ int knn_index_self_count_within(knn_index *idx, int slot, long long row_first, i
     return KNN_OK;
 }
 
-int knn_index_self_list_within(knn_index *idx, int slot, long long row_first, int rows, float max_dist2,
-                               const unsigned long long *offsets_dev, unsigned *fill_dev, unsigned long long *keys_dev, void *stream,
-                               unsigned flags)
+// ... and a self list call: knn_index_self_list_within and knn_index_self_list_within_each.
+static int self_list_run(knn_index *idx, const char *who, int slot, long long row_first, int rows, const float *radii_dev,
+                         float max_dist2, const unsigned long long *offsets_dev, unsigned *fill_dev, unsigned long long *keys_dev,
+                         void *stream, unsigned flags)
 {
-    if (!(max_dist2 >= 0.0f))
-        return fail(KNN_EINVAL, "knn_index_self_list_within: max_dist2 must be >= 0 and not NaN");
-    if ((flags & ~(unsigned)KNN_QUERY_INIT_KEYS) != 0u)
-        return fail(KNN_EINVAL, "knn_index_self_list_within: unknown flag (KNN_QUERY_INIT_KEYS alone is admitted)");
-    if (slot < 0 || slot >= KNN_SLOTS)
-        return fail(KNN_EINVAL, "knn_index_self_list_within: slot outside 0 .. 7");
-    if (rows < 1)
-        return fail(KNN_EINVAL, "knn_index_self_list_within: rows < 1");
-    if (row_first < 0)
-        return fail(KNN_EINVAL, "knn_index_self_list_within: row_first < 0");
-    if (!offsets_dev || !fill_dev || !keys_dev)
-        return fail(KNN_EINVAL, "knn_index_self_list_within: null offsets, fill or keys");
-    if (!idx)
-        return fail(KNN_EINVAL, "knn_index_self_list_within: null index");
     std::lock_guard<std::recursive_mutex> lock(idx->mu);
     if (row_first > idx->n || (long long)rows > idx->n - row_first)
-        return fail(KNN_EINVAL, "knn_index_self_list_within: row_first + rows above the shard's rows");
+        return fail_in(KNN_EINVAL, who, "row_first + rows above the shard's rows");
     DeviceGuard guard(idx->device);
     if (!guard.ok)
-        return fail(KNN_EHIP, "knn_index_self_list_within: hipSetDevice failed");
+        return fail_in(KNN_EHIP, who, "hipSetDevice failed");
     ListCall call;
     call.k = idx->k;
     call.m = rows;
@@ -2136,6 +2139,7 @@ int knn_index_self_list_within(knn_index *idx, int slot, long long row_first, in
     call.offsets = (const u64 *)offsets_dev;
     call.fill = fill_dev;
     call.keys = (u64 *)keys_dev;
+    call.radii = radii_dev;
     call.max_dist2 = max_dist2 == 0.0f ? 0.0f : max_dist2;   // (-0 counts as 0)
     call.num_cu = idx->num_cu;
     call.stream = (hipStream_t)stream;
@@ -2155,6 +2159,171 @@ int knn_index_self_list_within(knn_index *idx, int slot, long long row_first, in
     call.ev0 = ev ? ev->first : nullptr;
     call.ev1 = ev ? ev->second : nullptr;
     HIP_TRY(knn_self_list_launch(call, row_first));
+    return KNN_OK;
+}
+
+int knn_index_self_count_within(knn_index *idx, int slot, long long row_first, int rows, float max_dist2, unsigned *counts_dev,
+                                void *stream, unsigned flags)
+{
+    if (!(max_dist2 >= 0.0f))
+        return fail(KNN_EINVAL, "knn_index_self_count_within: max_dist2 must be >= 0 and not NaN");
+    if ((flags & ~(unsigned)KNN_QUERY_INIT_KEYS) != 0u)
+        return fail(KNN_EINVAL, "knn_index_self_count_within: unknown flag (KNN_QUERY_INIT_KEYS alone is admitted)");
+    if (slot < 0 || slot >= KNN_SLOTS)
+        return fail(KNN_EINVAL, "knn_index_self_count_within: slot outside 0 .. 7");
+    if (rows < 1)
+        return fail(KNN_EINVAL, "knn_index_self_count_within: rows < 1");
+    if (row_first < 0)
+        return fail(KNN_EINVAL, "knn_index_self_count_within: row_first < 0");
+    if (!counts_dev)
+        return fail(KNN_EINVAL, "knn_index_self_count_within: null counts");
+    if (!idx)
+        return fail(KNN_EINVAL, "knn_index_self_count_within: null index");
+    return self_count_run(idx, "knn_index_self_count_within", slot, row_first, rows, nullptr, max_dist2, counts_dev, stream, flags);
+}
+
+int knn_index_self_list_within(knn_index *idx, int slot, long long row_first, int rows, float max_dist2,
+                               const unsigned long long *offsets_dev, unsigned *fill_dev, unsigned long long *keys_dev, void *stream,
+                               unsigned flags)
+{
+    if (!(max_dist2 >= 0.0f))
+        return fail(KNN_EINVAL, "knn_index_self_list_within: max_dist2 must be >= 0 and not NaN");
+    if ((flags & ~(unsigned)KNN_QUERY_INIT_KEYS) != 0u)
+        return fail(KNN_EINVAL, "knn_index_self_list_within: unknown flag (KNN_QUERY_INIT_KEYS alone is admitted)");
+    if (slot < 0 || slot >= KNN_SLOTS)
+        return fail(KNN_EINVAL, "knn_index_self_list_within: slot outside 0 .. 7");
+    if (rows < 1)
+        return fail(KNN_EINVAL, "knn_index_self_list_within: rows < 1");
+    if (row_first < 0)
+        return fail(KNN_EINVAL, "knn_index_self_list_within: row_first < 0");
+    if (!offsets_dev || !fill_dev || !keys_dev)
+        return fail(KNN_EINVAL, "knn_index_self_list_within: null offsets, fill or keys");
+    if (!idx)
+        return fail(KNN_EINVAL, "knn_index_self_list_within: null index");
+    return self_list_run(idx, "knn_index_self_list_within", slot, row_first, rows, nullptr, max_dist2, offsets_dev, fill_dev, keys_dev,
+                         stream, flags);
+}
+
+// ---- 2j. A radius per query --------------------------------------------------------------------------------------------------
+// (one message per rule, in the header's order, the index last: tests/test_each_logic.py tells them apart without a GPU)
+int knn_index_count_within_each(knn_index *idx, int slot, int m, const float *queries_dev, const float *max_dist2_dev, float cap,
+                                unsigned *counts_dev, void *stream, unsigned flags)
+{
+    if (!(cap >= 0.0f))
+        return fail(KNN_EINVAL, "knn_index_count_within_each: cap must be >= 0 (or +INF) and not NaN");
+    constexpr unsigned kCountFlags = KNN_QUERY_INIT_KEYS | KNN_QUERY_COUNT_GRID | KNN_QUERY_COUNT_CELLS;   // the three it admits
+    if ((flags & ~kCountFlags) != 0u)
+        return fail(KNN_EINVAL, "knn_index_count_within_each: unknown flag (KNN_QUERY_INIT_KEYS, KNN_QUERY_COUNT_GRID, KNN_QUERY_COUNT_CELLS)");
+    if (slot < 0 || slot >= KNN_SLOTS)
+        return fail(KNN_EINVAL, "knn_index_count_within_each: slot outside 0 .. 7");
+    if (m < 1)
+        return fail(KNN_EINVAL, "knn_index_count_within_each: m < 1");
+    if (!queries_dev)
+        return fail(KNN_EINVAL, "knn_index_count_within_each: null queries");
+    if (!max_dist2_dev)
+        return fail(KNN_EINVAL, "knn_index_count_within_each: null radii");
+    if (!counts_dev)
+        return fail(KNN_EINVAL, "knn_index_count_within_each: null counts");
+    if (!idx)
+        return fail(KNN_EINVAL, "knn_index_count_within_each: null index");
+    return count_within_run(idx, "knn_index_count_within_each", slot, m, queries_dev, max_dist2_dev, cap, counts_dev, stream, flags);
+}
+
+int knn_index_list_within_each(knn_index *idx, int slot, int m, const float *queries_dev, const float *max_dist2_dev, float cap,
+                               const unsigned long long *offsets_dev, unsigned *fill_dev, unsigned long long *keys_dev, void *stream,
+                               unsigned flags)
+{
+    if (!(cap >= 0.0f))
+        return fail(KNN_EINVAL, "knn_index_list_within_each: cap must be >= 0 (or +INF) and not NaN");
+    constexpr unsigned kListFlags = KNN_QUERY_INIT_KEYS | KNN_QUERY_COUNT_GRID | KNN_QUERY_COUNT_CELLS;   // the three it admits
+    if ((flags & ~kListFlags) != 0u)
+        return fail(KNN_EINVAL, "knn_index_list_within_each: unknown flag (KNN_QUERY_INIT_KEYS, KNN_QUERY_COUNT_GRID, KNN_QUERY_COUNT_CELLS)");
+    if (slot < 0 || slot >= KNN_SLOTS)
+        return fail(KNN_EINVAL, "knn_index_list_within_each: slot outside 0 .. 7");
+    if (m < 1)
+        return fail(KNN_EINVAL, "knn_index_list_within_each: m < 1");
+    if (!queries_dev)
+        return fail(KNN_EINVAL, "knn_index_list_within_each: null queries");
+    if (!max_dist2_dev)
+        return fail(KNN_EINVAL, "knn_index_list_within_each: null radii");
+    if (!offsets_dev || !fill_dev || !keys_dev)
+        return fail(KNN_EINVAL, "knn_index_list_within_each: null offsets, fill or keys");
+    if (!idx)
+        return fail(KNN_EINVAL, "knn_index_list_within_each: null index");
+    return list_within_run(idx, "knn_index_list_within_each", slot, m, queries_dev, max_dist2_dev, cap, offsets_dev, fill_dev, keys_dev,
+                           stream, flags);
+}
+
+int knn_index_self_count_within_each(knn_index *idx, int slot, long long row_first, int rows, const float *max_dist2_dev, float cap,
+                                     unsigned *counts_dev, void *stream, unsigned flags)
+{
+    if (!(cap >= 0.0f))
+        return fail(KNN_EINVAL, "knn_index_self_count_within_each: cap must be >= 0 (or +INF) and not NaN");
+    if ((flags & ~(unsigned)KNN_QUERY_INIT_KEYS) != 0u)
+        return fail(KNN_EINVAL, "knn_index_self_count_within_each: unknown flag (KNN_QUERY_INIT_KEYS alone is admitted)");
+    if (slot < 0 || slot >= KNN_SLOTS)
+        return fail(KNN_EINVAL, "knn_index_self_count_within_each: slot outside 0 .. 7");
+    if (rows < 1)
+        return fail(KNN_EINVAL, "knn_index_self_count_within_each: rows < 1");
+    if (row_first < 0)
+        return fail(KNN_EINVAL, "knn_index_self_count_within_each: row_first < 0");
+    if (!max_dist2_dev)
+        return fail(KNN_EINVAL, "knn_index_self_count_within_each: null radii");
+    if (!counts_dev)
+        return fail(KNN_EINVAL, "knn_index_self_count_within_each: null counts");
+    if (!idx)
+        return fail(KNN_EINVAL, "knn_index_self_count_within_each: null index");
+    return self_count_run(idx, "knn_index_self_count_within_each", slot, row_first, rows, max_dist2_dev, cap, counts_dev, stream, flags);
+}
+
+int knn_index_self_list_within_each(knn_index *idx, int slot, long long row_first, int rows, const float *max_dist2_dev, float cap,
+                                    const unsigned long long *offsets_dev, unsigned *fill_dev, unsigned long long *keys_dev,
+                                    void *stream, unsigned flags)
+{
+    if (!(cap >= 0.0f))
+        return fail(KNN_EINVAL, "knn_index_self_list_within_each: cap must be >= 0 (or +INF) and not NaN");
+    if ((flags & ~(unsigned)KNN_QUERY_INIT_KEYS) != 0u)
+        return fail(KNN_EINVAL, "knn_index_self_list_within_each: unknown flag (KNN_QUERY_INIT_KEYS alone is admitted)");
+    if (slot < 0 || slot >= KNN_SLOTS)
+        return fail(KNN_EINVAL, "knn_index_self_list_within_each: slot outside 0 .. 7");
+    if (rows < 1)
+        return fail(KNN_EINVAL, "knn_index_self_list_within_each: rows < 1");
+    if (row_first < 0)
+        return fail(KNN_EINVAL, "knn_index_self_list_within_each: row_first < 0");
+    if (!max_dist2_dev)
+        return fail(KNN_EINVAL, "knn_index_self_list_within_each: null radii");
+    if (!offsets_dev || !fill_dev || !keys_dev)
+        return fail(KNN_EINVAL, "knn_index_self_list_within_each: null offsets, fill or keys");
+    if (!idx)
+        return fail(KNN_EINVAL, "knn_index_self_list_within_each: null index");
+    return self_list_run(idx, "knn_index_self_list_within_each", slot, row_first, rows, max_dist2_dev, cap, offsets_dev, fill_dev,
+                         keys_dev, stream, flags);
+}
+
+int knn_keys_column_dist2(int device, const unsigned long long *keys_dev, int m, int K, int column, float *dist2_dev, void *stream)
+{
+    if (m < 1)
+        return fail(KNN_EINVAL, "knn_keys_column_dist2: m < 1");
+    if (K < 1 || column < 0 || column >= K)
+        return fail(KNN_EINVAL, "knn_keys_column_dist2: K < 1 or column outside 0 .. K - 1");
+    if (!keys_dev || !dist2_dev)
+        return fail(KNN_EINVAL, "knn_keys_column_dist2: null keys or dist2");
+    DeviceGuard guard(device);
+    if (!guard.ok)
+        return fail(KNN_EHIP, "knn_keys_column_dist2: hipSetDevice failed");
+    HIP_TRY(knn_keys_column_dist2_launch((const u64 *)keys_dev, m, K, column, dist2_dev, (hipStream_t)stream));
+    return KNN_OK;
+}
+
+int knn_debug_each_radius(float radius, float cap, float out[2])
+{
+    if (!out)
+        return fail(KNN_EINVAL, "knn_debug_each_radius: null out");
+    if (!(cap >= 0.0f))
+        return fail(KNN_EINVAL, "knn_debug_each_radius: cap must be >= 0 (or +INF) and not NaN");
+    const bool has = knn_each_has(radius);
+    out[0] = has ? 1.0f : 0.0f;
+    out[1] = has ? knn_each_bound(radius, cap) : 0.0f;   // (the kernels never form the bound of a query without candidates)
     return KNN_OK;
 }
 
@@ -2797,53 +2966,58 @@ extern "C" int knn_index_query_topk_masked_host(knn_index *idx, int m, int K, co
     return KNN_OK;
 }
 
-extern "C" int knn_index_count_within_host(knn_index *idx, int m, const float *queries_host, float max_dist2, unsigned *counts_host)
+// The synchronous count and list calls behind their argument checks: radii_host null — the scalar calls at max_dist2 —, or the
+// radii of knn_index_count_within_each_host / knn_index_list_within_each_host, max_dist2 then being the cap.
+static int count_within_host_run(knn_index *idx, const char *who, int m, const float *queries_host, const float *radii_host,
+                                 float max_dist2, unsigned *counts_host)
 {
-    if (!idx || m < 1 || !queries_host || !counts_host || !(max_dist2 >= 0.0f))
-        return fail(KNN_EINVAL, "knn_index_count_within_host: bad arguments (m >= 1, max_dist2 >= 0 and not NaN)");
     std::lock_guard<std::recursive_mutex> lock(idx->mu);
     DeviceGuard guard(idx->device);
     if (!guard.ok)
-        return fail(KNN_EHIP, "knn_index_count_within_host: hipSetDevice failed");
+        return fail_in(KNN_EHIP, who, "hipSetDevice failed");
     Staging stage(idx->device);
-    float *q_dev = nullptr;
+    float *q_dev = nullptr, *r_dev = nullptr;
     unsigned *c_dev = nullptr;
     const size_t qbytes = (size_t)m * (size_t)idx->k * sizeof(float), cbytes = (size_t)m * sizeof(unsigned);
+    const size_t rbytes = (size_t)m * sizeof(float);
     hipError_t e = stage.get(&q_dev, qbytes);
     if (e == hipSuccess)
         e = stage.get(&c_dev, cbytes);
+    if (e == hipSuccess && radii_host)
+        e = stage.get(&r_dev, rbytes);
     if (e == hipSuccess)
         e = hipMemcpy(q_dev, queries_host, qbytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess && radii_host)
+        e = hipMemcpy(r_dev, radii_host, rbytes, hipMemcpyHostToDevice);
     if (e != hipSuccess)
-        return fail(KNN_EHIP, "knn_index_count_within_host: staging queries", hipGetErrorString(e));
-    const int rc = knn_index_count_within(idx, 0, m, q_dev, max_dist2, c_dev, nullptr, KNN_QUERY_INIT_KEYS);
+        return fail_in(KNN_EHIP, who, "staging queries", hipGetErrorString(e));
+    const int rc = radii_host ? knn_index_count_within_each(idx, 0, m, q_dev, r_dev, max_dist2, c_dev, nullptr, KNN_QUERY_INIT_KEYS)
+                              : knn_index_count_within(idx, 0, m, q_dev, max_dist2, c_dev, nullptr, KNN_QUERY_INIT_KEYS);
     if (rc != KNN_OK)
         return rc;
     e = hipMemcpy(counts_host, c_dev, cbytes, hipMemcpyDeviceToHost);
     if (e != hipSuccess)
-        return fail(KNN_EHIP, "knn_index_count_within_host: D2H counts", hipGetErrorString(e));
+        return fail_in(KNN_EHIP, who, "D2H counts", hipGetErrorString(e));
     // (not declared waited: the slot's buffers go back after the device-wide wait `stage` then makes itself, as the top-K host calls)
     return KNN_OK;
 }
 
-extern "C" int knn_index_list_within_host(knn_index *idx, int m, const float *queries_host, float max_dist2, long long *offsets_host,
-                                          int **indices_out, float **dist2_out)
+static int list_within_host_run(knn_index *idx, const char *who, int m, const float *queries_host, const float *radii_host,
+                                float max_dist2, long long *offsets_host, int **indices_out, float **dist2_out)
 {
-    if (!idx || m < 1 || !queries_host || !offsets_host || !indices_out || !(max_dist2 >= 0.0f))
-        return fail(KNN_EINVAL, "knn_index_list_within_host: bad arguments (m >= 1, max_dist2 >= 0 and not NaN)");
     *indices_out = nullptr;
     if (dist2_out)
         *dist2_out = nullptr;
     std::lock_guard<std::recursive_mutex> lock(idx->mu);
     DeviceGuard guard(idx->device);
     if (!guard.ok)
-        return fail(KNN_EHIP, "knn_index_list_within_host: hipSetDevice failed");
+        return fail_in(KNN_EHIP, who, "hipSetDevice failed");
     Staging stage(idx->device);
-    float *q_dev = nullptr;
+    float *q_dev = nullptr, *r_dev = nullptr;
     unsigned *c_dev = nullptr, *fill_dev = nullptr;
     u64 *off_dev = nullptr, *keys_dev = nullptr;
     const size_t qbytes = (size_t)m * (size_t)idx->k * sizeof(float), cbytes = (size_t)m * sizeof(unsigned);
-    const size_t obytes = ((size_t)m + 1) * sizeof(u64);
+    const size_t obytes = ((size_t)m + 1) * sizeof(u64), rbytes = (size_t)m * sizeof(float);
     hipError_t e = stage.get(&q_dev, qbytes);
     if (e == hipSuccess)
         e = stage.get(&c_dev, cbytes);
@@ -2851,12 +3025,17 @@ extern "C" int knn_index_list_within_host(knn_index *idx, int m, const float *qu
         e = stage.get(&fill_dev, cbytes);
     if (e == hipSuccess)
         e = stage.get(&off_dev, obytes);
+    if (e == hipSuccess && radii_host)
+        e = stage.get(&r_dev, rbytes);
     if (e == hipSuccess)
         e = hipMemcpy(q_dev, queries_host, qbytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess && radii_host)
+        e = hipMemcpy(r_dev, radii_host, rbytes, hipMemcpyHostToDevice);
     if (e != hipSuccess)
-        return fail(KNN_EHIP, "knn_index_list_within_host: staging queries", hipGetErrorString(e));
+        return fail_in(KNN_EHIP, who, "staging queries", hipGetErrorString(e));
     // count -> offsets, then the one synchronisation: the total sizes the keys
-    int rc = knn_index_count_within(idx, 0, m, q_dev, max_dist2, c_dev, nullptr, KNN_QUERY_INIT_KEYS);
+    int rc = radii_host ? knn_index_count_within_each(idx, 0, m, q_dev, r_dev, max_dist2, c_dev, nullptr, KNN_QUERY_INIT_KEYS)
+                        : knn_index_count_within(idx, 0, m, q_dev, max_dist2, c_dev, nullptr, KNN_QUERY_INIT_KEYS);
     if (rc == KNN_OK)
         rc = knn_counts_to_offsets(idx->device, c_dev, m, off_dev, nullptr);
     if (rc != KNN_OK)
@@ -2864,21 +3043,23 @@ extern "C" int knn_index_list_within_host(knn_index *idx, int m, const float *qu
     std::vector<u64> offs((size_t)m + 1);
     e = hipMemcpy(offs.data(), off_dev, obytes, hipMemcpyDeviceToHost);
     if (e != hipSuccess)
-        return fail(KNN_EHIP, "knn_index_list_within_host: D2H offsets", hipGetErrorString(e));
+        return fail_in(KNN_EHIP, who, "D2H offsets", hipGetErrorString(e));
     const u64 total = offs[(size_t)m];
     std::vector<u64> keys((size_t)total);
     if (total) {   // list -> sort
         e = stage.get(&keys_dev, (size_t)total * sizeof(u64));
         if (e != hipSuccess)
-            return fail(KNN_EHIP, "knn_index_list_within_host: staging keys", hipGetErrorString(e));
-        rc = knn_index_list_within(idx, 0, m, q_dev, max_dist2, off_dev, fill_dev, keys_dev, nullptr, KNN_QUERY_INIT_KEYS);
+            return fail_in(KNN_EHIP, who, "staging keys", hipGetErrorString(e));
+        rc = radii_host ? knn_index_list_within_each(idx, 0, m, q_dev, r_dev, max_dist2, off_dev, fill_dev, keys_dev, nullptr,
+                                                     KNN_QUERY_INIT_KEYS)
+                        : knn_index_list_within(idx, 0, m, q_dev, max_dist2, off_dev, fill_dev, keys_dev, nullptr, KNN_QUERY_INIT_KEYS);
         if (rc == KNN_OK)
             rc = knn_keys_sort_segments(idx->device, m, off_dev, fill_dev, keys_dev, nullptr);
         if (rc != KNN_OK)
             return rc;
         e = hipMemcpy(keys.data(), keys_dev, (size_t)total * sizeof(u64), hipMemcpyDeviceToHost);
         if (e != hipSuccess)
-            return fail(KNN_EHIP, "knn_index_list_within_host: D2H keys", hipGetErrorString(e));
+            return fail_in(KNN_EHIP, who, "D2H keys", hipGetErrorString(e));
     }
     const size_t room = total ? (size_t)total : 1u;
     int *ind = (int *)malloc(room * sizeof(int));
@@ -2886,7 +3067,7 @@ extern "C" int knn_index_list_within_host(knn_index *idx, int m, const float *qu
     if (!ind || (dist2_out && !d2)) {
         free(ind);
         free(d2);
-        return fail(KNN_EHIP, "knn_index_list_within_host: out of host memory");
+        return fail_in(KNN_EHIP, who, "out of host memory");
     }
     for (size_t i = 0; i < (size_t)total; ++i) {
         ind[i] = (int)(unsigned)(keys[i] & 0xFFFFFFFFull);
@@ -2902,6 +3083,39 @@ extern "C" int knn_index_list_within_host(knn_index *idx, int m, const float *qu
         *dist2_out = d2;
     // (not declared waited: the slot's buffers go back after the device-wide wait `stage` then makes itself, as the other host calls)
     return KNN_OK;
+}
+
+extern "C" int knn_index_count_within_host(knn_index *idx, int m, const float *queries_host, float max_dist2, unsigned *counts_host)
+{
+    if (!idx || m < 1 || !queries_host || !counts_host || !(max_dist2 >= 0.0f))
+        return fail(KNN_EINVAL, "knn_index_count_within_host: bad arguments (m >= 1, max_dist2 >= 0 and not NaN)");
+    return count_within_host_run(idx, "knn_index_count_within_host", m, queries_host, nullptr, max_dist2, counts_host);
+}
+
+extern "C" int knn_index_list_within_host(knn_index *idx, int m, const float *queries_host, float max_dist2, long long *offsets_host,
+                                          int **indices_out, float **dist2_out)
+{
+    if (!idx || m < 1 || !queries_host || !offsets_host || !indices_out || !(max_dist2 >= 0.0f))
+        return fail(KNN_EINVAL, "knn_index_list_within_host: bad arguments (m >= 1, max_dist2 >= 0 and not NaN)");
+    return list_within_host_run(idx, "knn_index_list_within_host", m, queries_host, nullptr, max_dist2, offsets_host, indices_out, dist2_out);
+}
+
+// (2j) the same two with a radius per query, host arrays in and out, this shard alone on the default way
+extern "C" int knn_index_count_within_each_host(knn_index *idx, int m, const float *queries_host, const float *max_dist2_host, float cap,
+                                                unsigned *counts_host)
+{
+    if (!idx || m < 1 || !queries_host || !max_dist2_host || !counts_host || !(cap >= 0.0f))
+        return fail(KNN_EINVAL, "knn_index_count_within_each_host: bad arguments (m >= 1, cap >= 0 and not NaN)");
+    return count_within_host_run(idx, "knn_index_count_within_each_host", m, queries_host, max_dist2_host, cap, counts_host);
+}
+
+extern "C" int knn_index_list_within_each_host(knn_index *idx, int m, const float *queries_host, const float *max_dist2_host, float cap,
+                                               long long *offsets_host, int **indices_out, float **dist2_out)
+{
+    if (!idx || m < 1 || !queries_host || !max_dist2_host || !offsets_host || !indices_out || !(cap >= 0.0f))
+        return fail(KNN_EINVAL, "knn_index_list_within_each_host: bad arguments (m >= 1, cap >= 0 and not NaN)");
+    return list_within_host_run(idx, "knn_index_list_within_each_host", m, queries_host, max_dist2_host, cap, offsets_host, indices_out,
+                                dist2_out);
 }
 
 // ---- the whole shard about its own rows (include/knn_mi355x.h 2i): the kNN graph and the radius graph, synchronous ---------------

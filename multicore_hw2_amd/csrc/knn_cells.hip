@@ -6,6 +6,7 @@
 #include "knn_exact_dev.h"
 #include "knn_seed_kth.h"
 #include "knn_frame_dup.h"
+#include "knn_each_radius.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -1206,7 +1207,7 @@ __global__ __launch_bounds__(64 * PW, KT == 1 && !CTR ? 4 : 3) void knn_cells_pr
     const float *__restrict__ frame, const unsigned *__restrict__ tile_cell)   // CTR only
 {
 #pragma clang fp contract(off)
-    constexpr bool WR = false, CNT = false;
+    constexpr bool WR = false, CNT = false, EACH = false;
     constexpr float max_dist2 = 0.0f;
 #include "knn_cells_prep_body.inc"
 }
@@ -1223,7 +1224,7 @@ __global__ __launch_bounds__(64 * PW, KT == 1 ? 4 : 3) void knn_cells_prep_withi
     unsigned *__restrict__ counts, unsigned nlists, int lo_by_entry /* K */, float max_dist2)
 {
 #pragma clang fp contract(off)
-    constexpr bool CTR = false, TK = true, WR = true, CNT = false;
+    constexpr bool CTR = false, TK = true, WR = true, CNT = false, EACH = false;
     u64 *const keys_init = nullptr;
     const float *const frame = nullptr;
     const unsigned *const tile_cell = nullptr;
@@ -1243,7 +1244,7 @@ __global__ __launch_bounds__(64 * PW, KT == 1 ? 4 : 3) void knn_cells_prep_count
     unsigned nlists, float max_dist2)
 {
 #pragma clang fp contract(off)
-    constexpr bool CTR = false, TK = true, WR = true, CNT = true;
+    constexpr bool CTR = false, TK = true, WR = true, CNT = true, EACH = false;
     constexpr int lo_by_entry = 1;   // (TK: the low table is [query][entry]; K has no meaning here)
     constexpr long long ntiles = 0;
     u64 *const keys_init = nullptr;
@@ -1252,6 +1253,37 @@ __global__ __launch_bounds__(64 * PW, KT == 1 ? 4 : 3) void knn_cells_prep_count
     const SeedLayer layer = {nullptr, 0u, 0u, 0u, 0ull, {0u}};   // the empty seed layer: a count needs no seed
     const float *const frame = nullptr;
     const unsigned *const tile_cell = nullptr;
+#include "knn_cells_prep_body.inc"
+}
+
+// The count form with a radius per query (knn_index_count_within_each, knn_index_list_within_each on the cell-pruned way): one
+// block per query, so the block turns its OWN query's radius into the body's max_dist2 — the query's bound min(radii[qi], cap)
+// (knn_each_radius.h; cap finite), or -1 when the query has no candidates (a NaN or negative radius), which the body's last lines
+// answer with the threshold of a padding query.  A padding block qi >= m reads no radius.  The scan behind it never sees a radius.
+template <int PW, int SD, int KT>
+__global__ __launch_bounds__(64 * PW, KT == 1 ? 4 : 3) void knn_cells_prep_each_kernel(
+    const float *__restrict__ Q, int m, int m_padded, CellGeom g, const float *__restrict__ bounds, double sigma2,
+    const float *__restrict__ center, float sigma, const unsigned *__restrict__ tile_start, h8 *__restrict__ qfg,
+    float *__restrict__ lo_tab, float *__restrict__ hi_tab, float bmax, float nmax, float amax_limit, float *__restrict__ thr,
+    float *__restrict__ dup_out, unsigned *__restrict__ ctl, unsigned *__restrict__ ctl_next, unsigned *__restrict__ counts,
+    unsigned nlists, const float *__restrict__ radii, float cap)
+{
+#pragma clang fp contract(off)
+    constexpr bool CTR = false, TK = true, WR = true, CNT = true, EACH = true;
+    constexpr int lo_by_entry = 1;
+    constexpr long long ntiles = 0;
+    u64 *const keys_init = nullptr;
+    const h8 *const rf = nullptr;
+    const unsigned *const rn2 = nullptr;
+    const SeedLayer layer = {nullptr, 0u, 0u, 0u, 0ull, {0u}};
+    const float *const frame = nullptr;
+    const unsigned *const tile_cell = nullptr;
+    float max_dist2 = -1.0f;
+    if ((int)blockIdx.x < m) {   // block-uniform
+        const float rad = radii[blockIdx.x];
+        if (knn_each_has(rad))
+            max_dist2 = knn_each_bound(rad, cap) + 0.0f;   // (-0 -> +0: the threshold's arithmetic sees the scalar call's 0)
+    }
 #include "knn_cells_prep_body.inc"
 }
 
@@ -2573,6 +2605,7 @@ struct CellBatch {
     int m_padded = 0;
     CellSelf self = CellSelf{};
     unsigned *ctl_next = nullptr;
+    const float *radii = nullptr;   // a count pass with a radius per query: the pass's radii (max_dist2 the cap; the prep kernel's EACH form)
 };
 
 struct CellKernel {   // a kernel the plan picked: its launch for a batch, and the kernel itself (for its attributes)
@@ -2631,12 +2664,27 @@ static CellKernel cells_prep_count_of()
             },
             (const void *)knn_cells_prep_count_kernel<PW, 2, KT>};
 }
+// ... of a count pass with a radius per query (knn_index_count_within_each): the block's own query's bound
+template <int PW, int KT>
+static CellKernel cells_prep_each_of()
+{
+    return {[](const CellBatch &b) {
+                const FilterState &st = b.st;
+                hipLaunchKernelGGL((knn_cells_prep_each_kernel<PW, 2, KT>), dim3((unsigned)b.m_padded), dim3(64 * PW), 0, b.s, b.q, b.m,
+                                   b.m_padded, cell_geom_of(b.c, st.k), b.c.bounds, (double)st.sigma * (double)st.sigma, st.center, st.sigma,
+                                   b.c.tile_start, (h8 *)b.w.qry_frags, b.w.lo_tab, b.w.hi_tab, st.bmax, st.nmax, kAmaxLimit, b.w.thr, b.w.dup,
+                                   b.w.ctl_cur, b.ctl_next, b.w.counts, b.w.nlists, b.radii, b.max_dist2);
+            },
+            (const void *)knn_cells_prep_each_kernel<PW, 2, KT>};
+}
 // The prep kernel's forms: what the pass is for, then the plan's prep shape (prep_pw waves per query, prep_kt, prep_ctr) — the 12
-// instantiations of knn_cells_prep_kernel and the 4 each of the radius and the count kernel.
-enum class CellPrepForm { Nearest, Topk, TopkWithin, Count };
+// instantiations of knn_cells_prep_kernel and the 4 each of the radius, the count and the radius-per-query kernel.
+enum class CellPrepForm { Nearest, Topk, TopkWithin, Count, CountEach };
 static CellKernel cells_prep_kernel(CellPrepForm form, const CellQueryPlan &p)
 {
     const bool two = p.prep_pw == 2, kt2 = p.prep_kt == 2;
+    if (form == CellPrepForm::CountEach)
+        return kt2 ? (two ? cells_prep_each_of<2, 2>() : cells_prep_each_of<4, 2>()) : (two ? cells_prep_each_of<2, 1>() : cells_prep_each_of<4, 1>());
     if (form == CellPrepForm::Count)
         return kt2 ? (two ? cells_prep_count_of<2, 2>() : cells_prep_count_of<4, 2>()) : (two ? cells_prep_count_of<2, 1>() : cells_prep_count_of<4, 1>());
     if (form == CellPrepForm::Nearest) {
@@ -3151,7 +3199,8 @@ hipError_t knn_cells_query_count(FilterState &st, FilterWorkspace &w, const Cell
     // (no keys, no gids, the empty seed layer: counts of a cell-range shard are its own rows' and simply add across ranks)
     const SeedLayer no_layer = {nullptr, 0u, 0u, 0u, 0ull, {0u}};
     CellBatch b{st, c, w, p, m, call.q, call.r, 0ll, nullptr, nullptr, CellFinal{nullptr, nullptr, 0}, no_layer, call.stream, 1, call.max_dist2};
-    FTRY(cells_pass_front(w, b, cells_records_kernel(tp.scan), CellPrepForm::Count, timed));
+    b.radii = call.radii;
+    FTRY(cells_pass_front(w, b, cells_records_kernel(tp.scan), call.radii ? CellPrepForm::CountEach : CellPrepForm::Count, timed));
     FTRY(knn_count_records_finish(call, cells_pass_records(st, w), call.scratch));
     // gated: the exact count answers a pass that raised FALLBACK (its scratch was not committed)
     return knn_exact_count_launch(call, w.ctl_cur + KNN_CTL_FALLBACK);
@@ -3172,7 +3221,8 @@ hipError_t knn_cells_query_list(FilterState &st, FilterWorkspace &w, const CellT
     // (the empty seed layer: the lists of a cell-range shard are its own rows' and simply append across ranks)
     const SeedLayer no_layer = {nullptr, 0u, 0u, 0u, 0ull, {0u}};
     CellBatch b{st, c, w, p, m, call.q, call.r, 0ll, nullptr, nullptr, CellFinal{nullptr, nullptr, 0}, no_layer, call.stream, 1, call.max_dist2};
-    FTRY(cells_pass_front(w, b, cells_records_kernel(tp.scan), CellPrepForm::Count, timed));
+    b.radii = call.radii;
+    FTRY(cells_pass_front(w, b, cells_records_kernel(tp.scan), call.radii ? CellPrepForm::CountEach : CellPrepForm::Count, timed));
     FTRY(knn_list_records_finish(call, cells_pass_records(st, w)));
     // gated: the exact list answers a pass that raised FALLBACK (its scratch cursor was not committed)
     return knn_exact_list_launch(call, w.ctl_cur + KNN_CTL_FALLBACK);

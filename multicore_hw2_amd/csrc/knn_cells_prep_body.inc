@@ -2,9 +2,12 @@
 // into knn_cells_prep_kernel<PW, SD, KT, CTR, TK> and into knn_cells_prep_within_kernel<PW, SD, KT>, the radius form of the top-K
 // prep kernel, which takes one argument more.  The including kernel provides the template parameters PW, SD, KT, the arguments of
 // knn_cells_prep_kernel by their names, and the constants CTR, TK, WR, CNT and max_dist2 (WR only: finite, >= 0).  CNT (with WR:
-// knn_index_count_within, knn_cells_prep_count_kernel): the count form, which scores no seed tile at all.
+// knn_index_count_within, knn_cells_prep_count_kernel): the count form, which scores no seed tile at all.  EACH (with CNT:
+// knn_index_count_within_each, knn_cells_prep_each_kernel): max_dist2 is the block's OWN query's bound (knn_each_radius.h), or
+// negative when the query has no candidates — it is then listed for no cell and sends nothing to the exact count.
     static_assert(!WR || (TK && !CTR), "the radius form is a top-K form of the one-frame layouts");
     static_assert(!CNT || WR, "the count form is a radius form");
+    static_assert(!EACH || CNT, "the form with a radius per query is a count form");
     constexpr int SEEDS = 1 << SD, NS = SEEDS / PW;   // seed cells in all, per wave
     // seed tiles a wave requests at once (KT KiB each); TK: fewer — the selection network's registers come on top of the tiles in
     // flight, and the form must stay within its 1-NN twin's registers without scratch (a top-K call is worth milliseconds: the
@@ -759,6 +762,10 @@
                 if ((double)dupf < dup)
                     dupf = nextafterf(dupf, INFINITY);
             }
+        }
+        if (EACH && !(s_radius >= 0.0f)) {   // no candidates: a padding query's threshold, and no fallback — the count is 0
+            bad = false;
+            t = dupf = -INFINITY;
         }
         thr[qi] = bad ? -INFINITY : t;
         dup_out[qi] = bad ? -INFINITY : dupf;

@@ -162,6 +162,9 @@ struct CountCall {
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;   // nullable: bracket the way's dominant kernel
     unsigned *scratch = nullptr;   // the slot's count scratch [m] (the grid and cell ways; the exact way does not use it)
+    // nullable; a call with a radius per query (2j): device [m], query j's radius.  max_dist2 is then the call's cap, and a row is
+    // a hit when E <= radii[j] and E <= max_dist2; every way launches its each-form kernels (knn_each_radius.h)
+    const float *radii = nullptr;
 
     // queries [q0, q0 + mb) of the call: a pass of the cell-pruned way
     CountCall pass(int q0, int mb) const
@@ -171,6 +174,7 @@ struct CountCall {
         c.q = q + (size_t)q0 * k;
         c.counts = counts + q0;
         c.scratch = scratch + q0;
+        c.radii = radii ? radii + q0 : nullptr;
         return c;
     }
 };
@@ -203,6 +207,7 @@ struct ListCall {
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;   // nullable: bracket the way's dominant kernel
     unsigned *scratch = nullptr;   // the slot's count scratch [m]: the scratch cursor of the grid and cell ways (the exact way does not use it)
+    const float *radii = nullptr;  // nullable; a radius per query, device [m], max_dist2 the cap: as CountCall::radii
 
     // queries [q0, q0 + mb) of the call: a pass of the cell-pruned way (offsets are absolute: keys stays)
     ListCall pass(int q0, int mb) const
@@ -213,6 +218,7 @@ struct ListCall {
         c.offsets = offsets + q0;
         c.fill = fill + q0;
         c.scratch = scratch + q0;
+        c.radii = radii ? radii + q0 : nullptr;
         return c;
     }
 };
@@ -232,6 +238,13 @@ hipError_t knn_counts_to_offsets_launch(const unsigned *counts, int m, u64 *offs
 // KNN_SORT_LDS_KEYS keys and in global memory beyond.
 #define KNN_SORT_LDS_KEYS 4096
 hipError_t knn_keys_sort_segments_launch(int m, const u64 *offsets, const unsigned *fill, u64 *keys, hipStream_t stream);
+// dist2[j] = the float in the high word of keys[j * K + column] (a padding key: +INF), j < m: a column of a top-K call's lists as
+// the radii of a call with a radius per query (knn_keys_column_dist2).
+hipError_t knn_keys_column_dist2_launch(const u64 *keys, int m, int K, int column, float *dist2, hipStream_t stream);
+// knn_count_records_finish and knn_list_records_finish for a pass that carries radii (c.radii; knn_each.hip): the same walks with
+// the radius of the record's own query, the same commit.  The plain functions hand such a pass over after their own checks.
+hipError_t knn_count_each_records_finish(const CountCall &c, const TopkRecords &rs, unsigned *qcount);
+hipError_t knn_list_each_records_finish(const ListCall &c, const TopkRecords &rs);
 
 // ---- top-K beyond 64 (knn_select.hip; knn_index_query_topk_large; DESIGN §4.6 "Top-K beyond 64") --------------------------------
 #define KNN_TOPK_LARGE_MAX 4096   // largest K of knn_index_query_topk_large (= KNN_SORT_LDS_KEYS: a list sorts in LDS)

@@ -21,6 +21,7 @@
 // This is not a translation of the reference's one-block-per-query kernels (core.cu:808-855):
 // no SoA transpose pass, no per-block result array, no host second-level reduce.
 #include "knn_exact_dev.h"
+#include "knn_masked_dev.h"   // masked_dist2: v0's distance of one row, the each-forms' row lines
 
 #include <math.h>
 #include <stdlib.h>
@@ -1559,10 +1560,17 @@ long long knn_count_slices(int mc, long long n, int num_cu)
     return (n + per - 1) / per;
 }
 
+// (a call with a radius per query — c.radii — takes the each-forms: the scans at the end of this file, the cell-pruned way's
+// re-rank in knn_each.hip)
+static hipError_t exact_count_each_launch(const CountCall &c, const unsigned *gate);
+static hipError_t exact_list_each_launch(const ListCall &c, const unsigned *gate);
+
 hipError_t knn_exact_count_launch(const CountCall &c, const unsigned *gate)
 {
     if (c.m <= 0 || c.n <= 0)
         return hipSuccess;
+    if (c.radii)
+        return exact_count_each_launch(c, gate);
     hipStream_t s = c.stream;
     for (int c0 = 0; c0 < c.m; c0 += KNN_TOPK_CHUNK) {
         const int mc = c.m - c0 < KNN_TOPK_CHUNK ? c.m - c0 : KNN_TOPK_CHUNK;
@@ -1604,6 +1612,8 @@ hipError_t knn_count_records_finish(const CountCall &c, const TopkRecords &rs, u
     hipStream_t s = c.stream;
     if (rs.rec_rows || !rs.perm || !rs.pos_norms || !qcount)
         return hipErrorInvalidValue;
+    if (c.radii)
+        return knn_count_each_records_finish(c, rs, qcount);   // (knn_each.hip)
     if (rs.nlists)
         hipLaunchKernelGGL(knn_count_rerank_kernel, dim3(rs.nlists), dim3(KNN_BLOCK), 0, s, c.q, c.r, c.k, rs.positions, rs.rec, rs.counts,
                            rs.nlists, rs.slice, rs.ctl, rs.perm, rs.pos_norms, c.max_dist2, qcount);
@@ -1858,6 +1868,8 @@ hipError_t knn_exact_list_launch(const ListCall &c, const unsigned *gate)
 {
     if (c.m <= 0 || c.n <= 0)
         return hipSuccess;
+    if (c.radii)
+        return exact_list_each_launch(c, gate);
     hipStream_t s = c.stream;
     for (int c0 = 0; c0 < c.m; c0 += KNN_TOPK_CHUNK) {
         const int mc = c.m - c0 < KNN_TOPK_CHUNK ? c.m - c0 : KNN_TOPK_CHUNK;
@@ -1900,6 +1912,8 @@ hipError_t knn_list_records_finish(const ListCall &c, const TopkRecords &rs)
     hipStream_t s = c.stream;
     if (rs.rec_rows || !rs.perm || !rs.pos_norms || !c.scratch)
         return hipErrorInvalidValue;
+    if (c.radii)
+        return knn_list_each_records_finish(c, rs);   // (knn_each.hip)
     if (rs.nlists)
         hipLaunchKernelGGL(knn_list_rerank_kernel, dim3(rs.nlists), dim3(KNN_BLOCK), 0, s, c.q, c.r, c.k, rs.positions, c.base, rs.rec,
                            rs.counts, rs.nlists, rs.slice, rs.ctl, rs.perm, rs.pos_norms, c.max_dist2, c.gids, c.offsets, c.scratch, c.keys);
@@ -1935,3 +1949,134 @@ hipError_t knn_keys_sort_segments_launch(int m, const u64 *offsets, const unsign
     hipLaunchKernelGGL(knn_keys_sort_segments_kernel, dim3((unsigned)m), dim3(KNN_BLOCK), 0, s, offsets, fill, keys);
     return hipGetLastError();
 }
+
+// ------------------------------------------------------------------------------------------
+// A radius per query (include/knn_mi355x.h 2j; DESIGN §4.6 "A radius per query"): the each-forms of the count and list kernels.
+// A row is a hit for query j when its v0 distance E is finite, E <= radii[j] and E <= cap — two fp32 compares, equality inside; a
+// NaN or negative radius fails the first for every row.  The kernels are their scalar twins with the radius read per query;
+// the launchers hand a call that carries radii (CountCall::radii, ListCall::radii; max_dist2 is then the cap) to the ones below.
+// ------------------------------------------------------------------------------------------
+// knn_exact_count_each_kernel<KC> — knn_exact_count_kernel<KC>'s skeleton (masked_dist2 holds its row lines): the lanes ARE the
+// queries, so the lane loads its own radius once and the compare reads a VGPR where the twin reads an SGPR.  gate as there.
+template <int KC>
+__global__ __launch_bounds__(KNN_WAVE) void knn_exact_count_each_kernel(const float *__restrict__ Q, const float *__restrict__ R, int k,
+                                                                       int m, long long n, long long rows_per_slice,
+                                                                       const float *__restrict__ radii, float cap,
+                                                                       unsigned *__restrict__ counts, const unsigned *__restrict__ gate)
+{
+#pragma clang fp contract(off)
+    if (gate && *gate == 0u)
+        return;
+    constexpr int KM = KC > 0 ? 16 * KC : 1;
+    const int lane = threadIdx.x;
+    const int q = blockIdx.y * KNN_WAVE + lane;
+    const int qa = min(q, m - 1);
+    const float *__restrict__ qp = Q + (size_t)qa * k;
+    float qv[KM];
+#pragma unroll
+    for (int d = 0; d < KM; ++d)
+        qv[d] = KC > 0 && d < k ? qp[d] : 0.0f;
+    const float rad = radii[qa];
+    unsigned cnt = 0u;
+    const long long i0 = (long long)blockIdx.x * rows_per_slice;
+    const long long i1 = min(n, i0 + rows_per_slice);
+    const float *__restrict__ r = R + (size_t)i0 * k;
+    for (long long i = i0; i < i1; ++i, r += k) {
+        const float acc = masked_dist2<KC>(qv, qp, r, k);
+        cnt += acc < INFINITY && acc <= rad && acc <= cap ? 1u : 0u;   // (NaN — the distance or the radius — fails)
+    }
+    if (q < m && cnt != 0u)
+        atomicAdd(&counts[q], cnt);
+}
+
+// knn_exact_list_each_kernel<KC> — knn_exact_list_kernel<KC> with the lane's own radius, as the count form.
+template <int KC>
+__global__ __launch_bounds__(KNN_WAVE) void knn_exact_list_each_kernel(const float *__restrict__ Q, const float *__restrict__ R, int k,
+                                                                      int m, long long n, long long rows_per_slice,
+                                                                      const float *__restrict__ radii, float cap, long long base,
+                                                                      const unsigned *__restrict__ gids,
+                                                                      const u64 *__restrict__ offsets, unsigned *__restrict__ fill,
+                                                                      u64 *__restrict__ keys, const unsigned *__restrict__ gate)
+{
+#pragma clang fp contract(off)
+    if (gate && *gate == 0u)
+        return;
+    constexpr int KM = KC > 0 ? 16 * KC : 1;
+    const int lane = threadIdx.x;
+    const int q = blockIdx.y * KNN_WAVE + lane;
+    const int qa = min(q, m - 1);
+    const float *__restrict__ qp = Q + (size_t)qa * k;
+    float qv[KM];
+#pragma unroll
+    for (int d = 0; d < KM; ++d)
+        qv[d] = KC > 0 && d < k ? qp[d] : 0.0f;
+    const float rad = radii[qa];
+    u64 off;
+    const unsigned room = list_room(offsets, (unsigned)qa, off);
+    const long long i0 = (long long)blockIdx.x * rows_per_slice;
+    const long long i1 = min(n, i0 + rows_per_slice);
+    const float *__restrict__ r = R + (size_t)i0 * k;
+    for (long long i = i0; i < i1; ++i, r += k) {
+        const float acc = masked_dist2<KC>(qv, qp, r, k);
+        if (q < m && acc < INFINITY && acc <= rad && acc <= cap)   // (NaN — the distance or the radius — fails)
+            list_put(&fill[q], keys, off, room, pack_key(acc, gids ? gids[i] : (unsigned)(base + i)));
+    }
+}
+
+#define KNN_EACH_SWITCH(k, LAUNCH) \
+    switch (((k) + 15) / 16) {     \
+    case 1: LAUNCH(1); break;      \
+    case 2: LAUNCH(2); break;      \
+    case 3: LAUNCH(3); break;      \
+    case 4: LAUNCH(4); break;      \
+    case 5: LAUNCH(5); break;      \
+    case 6: LAUNCH(6); break;      \
+    case 7: LAUNCH(7); break;      \
+    case 8: LAUNCH(8); break;      \
+    default: LAUNCH(0); break;     \
+    }
+
+// knn_exact_count_launch for a call with radii: its slices and chunks; the radii advance with the queries, chunk by chunk.
+static hipError_t exact_count_each_launch(const CountCall &c, const unsigned *gate)
+{
+    hipStream_t s = c.stream;
+    for (int c0 = 0; c0 < c.m; c0 += KNN_TOPK_CHUNK) {
+        const int mc = c.m - c0 < KNN_TOPK_CHUNK ? c.m - c0 : KNN_TOPK_CHUNK;
+        const long long slices = knn_count_slices(mc, c.n, c.num_cu);
+        const long long per = (c.n + slices - 1) / slices;
+        const dim3 grid((unsigned)slices, (unsigned)knn_divup(mc, KNN_WAVE)), block(KNN_WAVE);
+        const float *qc = c.q + (size_t)c0 * c.k;
+#define KNN_COUNT_EACH_SCAN(KCV)                                                                                                  \
+    hipLaunchKernelGGL(knn_exact_count_each_kernel<KCV>, grid, block, 0, s, qc, c.r, c.k, mc, c.n, per, c.radii + c0, c.max_dist2, \
+                       c.counts + c0, gate)
+        KNN_EACH_SWITCH(c.k, KNN_COUNT_EACH_SCAN)
+#undef KNN_COUNT_EACH_SCAN
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess)
+            return e;
+    }
+    return hipSuccess;
+}
+
+// knn_exact_list_launch for a call with radii.
+static hipError_t exact_list_each_launch(const ListCall &c, const unsigned *gate)
+{
+    hipStream_t s = c.stream;
+    for (int c0 = 0; c0 < c.m; c0 += KNN_TOPK_CHUNK) {
+        const int mc = c.m - c0 < KNN_TOPK_CHUNK ? c.m - c0 : KNN_TOPK_CHUNK;
+        const long long slices = knn_count_slices(mc, c.n, c.num_cu);
+        const long long per = (c.n + slices - 1) / slices;
+        const dim3 grid((unsigned)slices, (unsigned)knn_divup(mc, KNN_WAVE)), block(KNN_WAVE);
+        const float *qc = c.q + (size_t)c0 * c.k;
+#define KNN_LIST_EACH_SCAN(KCV)                                                                                                  \
+    hipLaunchKernelGGL(knn_exact_list_each_kernel<KCV>, grid, block, 0, s, qc, c.r, c.k, mc, c.n, per, c.radii + c0, c.max_dist2, \
+                       c.base, c.gids, c.offsets + c0, c.fill + c0, c.keys, gate)
+        KNN_EACH_SWITCH(c.k, KNN_LIST_EACH_SCAN)
+#undef KNN_LIST_EACH_SCAN
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess)
+            return e;
+    }
+    return hipSuccess;
+}
+#undef KNN_EACH_SWITCH

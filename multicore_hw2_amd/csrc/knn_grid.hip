@@ -20,6 +20,7 @@
 // Never used when the rows hold non-finite values or the grid degenerates (a cell with > 4096 rows):
 // the brute-force kernels take those shards.
 #include "knn_common.h"
+#include "knn_each_radius.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -607,6 +608,179 @@ __global__ __launch_bounds__(GRID_BLOCK) void knn_grid_list_kernel(const float *
         *giveup = 1u;      // benign race: every writer stores 1
 }
 
+// ---- a radius per query (include/knn_mi355x.h 2j; knn_index_count_within_each, knn_index_list_within_each) ---------------
+// knn_grid_count_kernel's and knn_grid_list_kernel's walks with the wave's own radius: one wave per query, so radii[qi] is
+// wave-uniform as max_dist2 is there.  A row is a hit when E is finite, E <= radii[qi] and E <= cap.  The stop clause takes the
+// query's bound (knn_each_radius.h) in the scalar radius's place: every hit lies within it.  A query without candidates (a NaN or
+// negative radius) walks nothing, counts 0 / leaves its cursor alone and never raises the give-up word; rmax is made from cap's
+// rings, so a query whose bound is below cap stops no later than the scalar call at cap would.
+template <int KD>
+__global__ __launch_bounds__(GRID_BLOCK) void knn_grid_each_count_kernel(const float *__restrict__ Q, int m, GridGeom gg,
+                                                                         const unsigned *__restrict__ start,
+                                                                         const f4g *__restrict__ pts, unsigned *__restrict__ out,
+                                                                         int rmax, unsigned *__restrict__ giveup,
+                                                                         unsigned *__restrict__ giveup_next,
+                                                                         const float *__restrict__ radii, float cap)
+{
+#pragma clang fp contract(off)
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        *giveup_next = 0u;   // (the slot's other word, as the 1-NN kernel)
+    const int lane = threadIdx.x & 63;
+    const int qi = blockIdx.x * (GRID_BLOCK / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (qi >= m)
+        return;
+    float q[4] = {0.f, 0.f, 0.f, 0.f};
+    bool finite = true;
+#pragma unroll
+    for (int d = 0; d < KD; ++d) {
+        q[d] = Q[(size_t)qi * KD + d];
+        finite = finite && fabsf(q[d]) < INFINITY;
+    }
+    const float rad = radii[qi];
+    if (!finite || !knn_each_has(rad)) {   // no row can be a hit (and nothing to give up on)
+        if (lane == 0)
+            out[qi] = 0u;
+        return;
+    }
+    const float bound = knn_each_bound(rad, cap);
+    int c[4];
+    (void)grid_cell_of(gg, q, c);
+    int gmax = 1;
+#pragma unroll
+    for (int d = 0; d < KD; ++d)
+        gmax = gg.g[d] > gmax ? gg.g[d] : gmax;
+
+    unsigned cnt = 0u;
+    bool done = false;
+    bool first = true;   // (rings 0 and 1 together, as the 1-NN kernel)
+    for (int r = gmax > 1 ? 1 : 0; r < gmax && r <= rmax; ++r) {
+        const int side = 2 * r + 1;
+        int total = 1;
+#pragma unroll
+        for (int d = 0; d < KD; ++d)
+            total *= side;
+        for (int idx = lane; idx < total; idx += KNN_WAVE) {
+            unsigned cell;
+            if (!grid_ring_cell<KD>(gg, c, r, side, idx, first, &cell))
+                continue;
+            const unsigned p0 = start[cell], p1 = start[cell + 1];
+            for (unsigned p = p0; p < p1; ++p) {
+                const f4g x = pts[p];
+                float acc = 0.0f;
+#pragma unroll
+                for (int d = 0; d < KD; ++d) {
+                    const float diff = q[d] - x[d];   // v0: search - reference, squared, summed in order
+                    const float sq = diff * diff;
+                    acc = acc + sq;
+                }
+                cnt += acc < INFINITY && acc <= rad && acc <= cap ? 1u : 0u;
+            }
+        }
+        first = false;
+        bool covers_all;
+        const double lb = grid_face_bound<KD>(gg, c, q, r, &covers_all);
+        if (covers_all) {
+            done = true;
+            break;
+        }
+        if (lb > 0.0 && (double)bound < lb * lb * (1.0 - 1e-6)) {   // no unseen row is within the query's bound
+            done = true;
+            break;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+        cnt += (unsigned)__shfl_xor((int)cnt, off, KNN_WAVE);
+    if (lane == 0) {
+        out[qi] = cnt;
+        if (!done && gmax > rmax + 1)
+            *giveup = 1u;      // benign race: every writer stores 1
+    }
+}
+
+template <int KD>
+__global__ __launch_bounds__(GRID_BLOCK) void knn_grid_each_list_kernel(const float *__restrict__ Q, int m, GridGeom gg,
+                                                                        const unsigned *__restrict__ start,
+                                                                        const f4g *__restrict__ pts, const unsigned *__restrict__ orig,
+                                                                        long long base, const u64 *__restrict__ offsets,
+                                                                        unsigned *__restrict__ cursor, u64 *__restrict__ keys, int rmax,
+                                                                        unsigned *__restrict__ giveup,
+                                                                        unsigned *__restrict__ giveup_next,
+                                                                        const float *__restrict__ radii, float cap)
+{
+#pragma clang fp contract(off)
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        *giveup_next = 0u;   // (the slot's other word, as the 1-NN kernel)
+    const int lane = threadIdx.x & 63;
+    const int qi = blockIdx.x * (GRID_BLOCK / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (qi >= m)
+        return;
+    float q[4] = {0.f, 0.f, 0.f, 0.f};
+    bool finite = true;
+#pragma unroll
+    for (int d = 0; d < KD; ++d) {
+        q[d] = Q[(size_t)qi * KD + d];
+        finite = finite && fabsf(q[d]) < INFINITY;
+    }
+    const float rad = radii[qi];
+    if (!finite || !knn_each_has(rad))   // no row can be a hit: the cursor stays where it was (and nothing to give up on)
+        return;
+    const float bound = knn_each_bound(rad, cap);
+    int c[4];
+    (void)grid_cell_of(gg, q, c);
+    int gmax = 1;
+#pragma unroll
+    for (int d = 0; d < KD; ++d)
+        gmax = gg.g[d] > gmax ? gg.g[d] : gmax;
+    const u64 off = offsets[qi], end = offsets[qi + 1];
+    const u64 room64 = end > off ? end - off : 0ull;
+    const unsigned room = room64 < 0xFFFFFFFFull ? (unsigned)room64 : 0xFFFFFFFFu;   // (the cursor is 32-bit)
+
+    bool done = false;
+    bool first = true;   // (rings 0 and 1 together, as the 1-NN kernel)
+    for (int r = gmax > 1 ? 1 : 0; r < gmax && r <= rmax; ++r) {
+        const int side = 2 * r + 1;
+        int total = 1;
+#pragma unroll
+        for (int d = 0; d < KD; ++d)
+            total *= side;
+        for (int idx = lane; idx < total; idx += KNN_WAVE) {
+            unsigned cell;
+            if (!grid_ring_cell<KD>(gg, c, r, side, idx, first, &cell))
+                continue;
+            const unsigned p0 = start[cell], p1 = start[cell + 1];
+            for (unsigned p = p0; p < p1; ++p) {
+                const f4g x = pts[p];
+                float acc = 0.0f;
+#pragma unroll
+                for (int d = 0; d < KD; ++d) {
+                    const float diff = q[d] - x[d];   // v0: search - reference, squared, summed in order
+                    const float sq = diff * diff;
+                    acc = acc + sq;
+                }
+                if (acc < INFINITY && acc <= rad && acc <= cap) {
+                    const unsigned place = atomicAdd(&cursor[qi], 1u);
+                    if (place < room)
+                        keys[off + place] = ((u64)__float_as_uint(acc) << 32) | (u64)(unsigned)(base + (long long)orig[p]);
+                }
+            }
+        }
+        first = false;
+        bool covers_all;
+        const double lb = grid_face_bound<KD>(gg, c, q, r, &covers_all);
+        if (covers_all) {
+            done = true;
+            break;
+        }
+        if (lb > 0.0 && (double)bound < lb * lb * (1.0 - 1e-6)) {   // no unseen row is within the query's bound
+            done = true;
+            break;
+        }
+    }
+    if (lane == 0 && !done && gmax > rmax + 1)
+        *giveup = 1u;      // benign race: every writer stores 1
+}
+
 // ---- host -------------------------------------------------------------------------------------------
 #define GTRY(call)                     \
     do {                                 \
@@ -896,9 +1070,13 @@ hipError_t knn_grid_query_count(const GridState *gs, int rmax, int slot, const C
     const dim3 grid((unsigned)((c.m + GRID_BLOCK / 64 - 1) / (GRID_BLOCK / 64))), block(GRID_BLOCK);
     if (c.ev0)
         GTRY(hipEventRecord(c.ev0, s));
-#define GRID_COUNT(KDV)                                                                                                       \
-    hipLaunchKernelGGL(knn_grid_count_kernel<KDV>, grid, block, 0, s, c.q, c.m, gs->geom, gs->start, gs->pts, c.scratch, rmax, \
-                       giveup, giveup_next, c.max_dist2)
+#define GRID_COUNT(KDV)                                                                                                              \
+    if (c.radii)   /* a radius per query; c.max_dist2 is the cap */                                                                  \
+        hipLaunchKernelGGL(knn_grid_each_count_kernel<KDV>, grid, block, 0, s, c.q, c.m, gs->geom, gs->start, gs->pts, c.scratch, rmax, \
+                           giveup, giveup_next, c.radii, c.max_dist2);                                                               \
+    else                                                                                                                             \
+        hipLaunchKernelGGL(knn_grid_count_kernel<KDV>, grid, block, 0, s, c.q, c.m, gs->geom, gs->start, gs->pts, c.scratch, rmax,    \
+                           giveup, giveup_next, c.max_dist2)
     switch (gs->geom.k) {
     case 1: GRID_COUNT(1); break;
     case 2: GRID_COUNT(2); break;
@@ -932,9 +1110,13 @@ hipError_t knn_grid_query_list(const GridState *gs, int rmax, int slot, const Li
     const dim3 grid((unsigned)((c.m + GRID_BLOCK / 64 - 1) / (GRID_BLOCK / 64))), block(GRID_BLOCK);
     if (c.ev0)
         GTRY(hipEventRecord(c.ev0, s));
-#define GRID_LIST(KDV)                                                                                                          \
-    hipLaunchKernelGGL(knn_grid_list_kernel<KDV>, grid, block, 0, s, c.q, c.m, gs->geom, gs->start, gs->pts, gs->orig, c.base, \
-                       c.offsets, c.scratch, c.keys, rmax, giveup, giveup_next, c.max_dist2)
+#define GRID_LIST(KDV)                                                                                                                \
+    if (c.radii)   /* a radius per query; c.max_dist2 is the cap */                                                                   \
+        hipLaunchKernelGGL(knn_grid_each_list_kernel<KDV>, grid, block, 0, s, c.q, c.m, gs->geom, gs->start, gs->pts, gs->orig, c.base, \
+                           c.offsets, c.scratch, c.keys, rmax, giveup, giveup_next, c.radii, c.max_dist2);                            \
+    else                                                                                                                              \
+        hipLaunchKernelGGL(knn_grid_list_kernel<KDV>, grid, block, 0, s, c.q, c.m, gs->geom, gs->start, gs->pts, gs->orig, c.base,     \
+                           c.offsets, c.scratch, c.keys, rmax, giveup, giveup_next, c.max_dist2)
     switch (gs->geom.k) {
     case 1: GRID_LIST(1); break;
     case 2: GRID_LIST(2); break;

@@ -227,6 +227,72 @@ __global__ __launch_bounds__(KNN_WAVE) void knn_self_list_kernel(const float *__
     });
 }
 
+// A radius per query (include/knn_mi355x.h 2j; DESIGN §4.6 "A radius per query"): knn_self_count_kernel<KC> and
+// knn_self_list_kernel<KC> with the lane's own radius.  radii is the CALL's array — radii[j] belongs to query j, local row
+// first + j —, so the lane reads radii[q], never radii[its row number]; the launchers advance it with the chunks.  A hit:
+// E finite, E <= radii[q] and E <= cap, two fp32 compares (a NaN or negative radius fails the first for every row).
+template <int KC>
+__global__ __launch_bounds__(KNN_WAVE) void knn_self_count_each_kernel(const float *__restrict__ R, int k, long long first, int m,
+                                                                      long long n, long long rows_per_slice,
+                                                                      const float *__restrict__ radii, float cap,
+                                                                      unsigned *__restrict__ counts)
+{
+#pragma clang fp contract(off)
+    constexpr int KM = KC > 0 ? 16 * KC : 1;
+    const int lane = threadIdx.x;
+    const int q = blockIdx.y * KNN_WAVE + lane;
+    const int qa = min(q, m - 1);
+    const float *__restrict__ qp = R + (size_t)(first + qa) * k;
+    float qv[KM];
+#pragma unroll
+    for (int d = 0; d < KM; ++d)
+        qv[d] = KC > 0 && d < k ? qp[d] : 0.0f;
+    const float rad = radii[qa];
+    unsigned cnt = 0u;
+    const unsigned own = (unsigned)(first + q);
+    const long long i0 = (long long)blockIdx.x * rows_per_slice;
+    const long long i1 = min(n, i0 + rows_per_slice);
+    const long long w0 = first + (long long)blockIdx.y * KNN_WAVE;
+    const long long w1 = min(w0 + KNN_WAVE, first + m);
+    self_scan<KC>(qv, qp, R, k, i0, i1, w0, w1, own, [&](float acc, unsigned) {
+        cnt += acc < INFINITY && acc <= rad && acc <= cap ? 1u : 0u;   // (NaN — the distance or the radius — fails)
+    });
+    if (q < m && cnt != 0u)
+        atomicAdd(&counts[q], cnt);
+}
+
+template <int KC>
+__global__ __launch_bounds__(KNN_WAVE) void knn_self_list_each_kernel(const float *__restrict__ R, int k, long long first, int m,
+                                                                     long long n, long long rows_per_slice,
+                                                                     const float *__restrict__ radii, float cap, long long base,
+                                                                     const unsigned *__restrict__ gids,
+                                                                     const u64 *__restrict__ offsets, unsigned *__restrict__ fill,
+                                                                     u64 *__restrict__ keys)
+{
+#pragma clang fp contract(off)
+    constexpr int KM = KC > 0 ? 16 * KC : 1;
+    const int lane = threadIdx.x;
+    const int q = blockIdx.y * KNN_WAVE + lane;
+    const int qa = min(q, m - 1);
+    const float *__restrict__ qp = R + (size_t)(first + qa) * k;
+    float qv[KM];
+#pragma unroll
+    for (int d = 0; d < KM; ++d)
+        qv[d] = KC > 0 && d < k ? qp[d] : 0.0f;
+    const float rad = radii[qa];
+    u64 off;
+    const unsigned room = list_room(offsets, (unsigned)qa, off);
+    const unsigned own = (unsigned)(first + q);
+    const long long i0 = (long long)blockIdx.x * rows_per_slice;
+    const long long i1 = min(n, i0 + rows_per_slice);
+    const long long w0 = first + (long long)blockIdx.y * KNN_WAVE;
+    const long long w1 = min(w0 + KNN_WAVE, first + m);
+    self_scan_one<KC>(qv, qp, R, k, i0, i1, w0, w1, own, [&](float acc, unsigned row, bool other) {
+        if (other && q < m && acc < INFINITY && acc <= rad && acc <= cap)   // (NaN — the distance or the radius — fails)
+            list_put(&fill[q], keys, off, room, pack_key(acc, gids ? gids[row] : (unsigned)(base + (long long)row)));
+    });
+}
+
 // knn_self_drop_kernel — one wave (block) per query: lists[q][0 .. K] is the plain call's sorted top-(K + 1) for the query that is
 // local row first + q, self among the candidates.  The entry that is a real key (high word below +INF's bits) and carries the
 // query's own global number goes; when there is none — more than K other rows at or before self's place, or a self-distance that is
@@ -338,8 +404,12 @@ hipError_t knn_self_count_launch(const CountCall &c, long long row_first)
         if (per > 0xFFFFFFFFll)   // (the kernels count a slice's rows in 32 bits)
             return hipErrorInvalidValue;
         const dim3 grid((unsigned)slices, (unsigned)knn_divup(mc, KNN_WAVE)), block(KNN_WAVE);
-#define KNN_SELF_COUNT(KCV) \
-    hipLaunchKernelGGL(knn_self_count_kernel<KCV>, grid, block, 0, s, c.r, c.k, row_first + c0, mc, c.n, per, c.max_dist2, c.counts + c0)
+#define KNN_SELF_COUNT(KCV)                                                                                                          \
+    if (c.radii)   /* a radius per query: the radii advance with the chunk */                                                        \
+        hipLaunchKernelGGL(knn_self_count_each_kernel<KCV>, grid, block, 0, s, c.r, c.k, row_first + c0, mc, c.n, per, c.radii + c0,  \
+                           c.max_dist2, c.counts + c0);                                                                              \
+    else                                                                                                                             \
+        hipLaunchKernelGGL(knn_self_count_kernel<KCV>, grid, block, 0, s, c.r, c.k, row_first + c0, mc, c.n, per, c.max_dist2, c.counts + c0)
         KNN_SELF_SWITCH(c.k, KNN_SELF_COUNT)
 #undef KNN_SELF_COUNT
         e = hipGetLastError();
@@ -366,9 +436,13 @@ hipError_t knn_self_list_launch(const ListCall &c, long long row_first)
         if (per > 0xFFFFFFFFll)   // (the kernels count a slice's rows in 32 bits)
             return hipErrorInvalidValue;
         const dim3 grid((unsigned)slices, (unsigned)knn_divup(mc, KNN_WAVE)), block(KNN_WAVE);
-#define KNN_SELF_LIST(KCV)                                                                                                          \
-    hipLaunchKernelGGL(knn_self_list_kernel<KCV>, grid, block, 0, s, c.r, c.k, row_first + c0, mc, c.n, per, c.max_dist2, c.base, c.gids, \
-                       c.offsets + c0, c.fill + c0, c.keys)
+#define KNN_SELF_LIST(KCV)                                                                                                              \
+    if (c.radii)   /* a radius per query: the radii advance with the chunk */                                                           \
+        hipLaunchKernelGGL(knn_self_list_each_kernel<KCV>, grid, block, 0, s, c.r, c.k, row_first + c0, mc, c.n, per, c.radii + c0,      \
+                           c.max_dist2, c.base, c.gids, c.offsets + c0, c.fill + c0, c.keys);                                           \
+    else                                                                                                                                \
+        hipLaunchKernelGGL(knn_self_list_kernel<KCV>, grid, block, 0, s, c.r, c.k, row_first + c0, mc, c.n, per, c.max_dist2, c.base, c.gids, \
+                           c.offsets + c0, c.fill + c0, c.keys)
         KNN_SELF_SWITCH(c.k, KNN_SELF_LIST)
 #undef KNN_SELF_LIST
         e = hipGetLastError();
