@@ -633,6 +633,48 @@ int knn_index_list_within_each_host(knn_index *idx, int m, const float *queries_
  * candidates else 0, its bound under cap (0 when it has none)}.  cap < 0 or NaN is KNN_EINVAL. */
 int knn_debug_each_radius(float radius, float cap, float out[2]);
 
+/* ------------------------------------------------------------------------
+ * 2k. The radius graph on the grid and cell-pruned ways: 2i's count and list (and their 2j forms) with the two pruned ways the
+ * plain calls of 2d and 2e have on request.  The self calls of 2i and 2j know the exact self-scan alone and refuse every flag but
+ * the init flag; these entry points admit KNN_QUERY_COUNT_GRID and KNN_QUERY_COUNT_CELLS as well.
+ *
+ * Candidate rule: exactly 2i's with 2j's radius rule.  Row i is a hit for query j — LOCAL row row_first + j — when
+ * i != row_first + j (identity by local row number: other copies of the row stay hits, at distance 0), its v0 distance E is finite,
+ * E <= the query's radius and E <= cap.  max_dist2_dev == NULL is the scalar form: every query's radius is cap, which may then be
+ * +INF.  Otherwise max_dist2_dev [rows] is 2j's array word for word: a NaN or negative radius gives no hit and never an error, the
+ * bound a kernel prunes or stops by is the smaller of the radius and cap.  Keys carry base_index + row, or the gid on a cell-range
+ * shard.  Folding, KNN_QUERY_INIT_KEYS, the fill_dev / room / overflow contract, slots and asynchrony are 2i's.  For every input the
+ * counts equal what the calls of 2i and 2j give, and every segment holds the same set of keys.
+ *
+ * Flags: KNN_QUERY_INIT_KEYS, KNN_QUERY_COUNT_GRID, KNN_QUERY_COUNT_CELLS; anything else is KNN_EINVAL.  The way is the one
+ * knn_index_count_within would take for `rows` queries at max_dist2 = cap under the same flags and options (knn_debug_count_plan
+ * describes it), with the exact self-scan in the exact count's place: without a flag the call launches exactly what the call of 2i
+ * or 2j launches.  On the grid way (k <= 4) a row's own position is dropped behind the distance; on the cell-pruned way (a finite
+ * cap, a one-frame cell-sorted layout, rows >= 5) the pass's preparation, match and scan are the plain count's, launched on the
+ * resident rows, and the kernels that turn its records into hits drop the query's own row.  Nothing is uploaded or gathered.  A
+ * grid batch that gives up, and a cell-pruned pass that falls back, are answered by the exact self-scan, gated on the device.
+ * knn_index_last_stats reports [0] = 1 / 3 / 4; [1], [2] and [3] mean what 2d says.
+ *
+ * Argument errors are KNN_EINVAL, each with its own knn_last_error text prefixed by the function's name, checked in this order —
+ * the first that fails speaks, nothing is launched —: cap < 0 or NaN, an unknown flag, a slot outside 0 .. 7, rows < 1,
+ * row_first < 0, a null counts pointer or a null offsets, fill or keys pointer, a null index, row_first + rows > n_local. */
+int knn_index_self_count_within_routed(knn_index *idx, int slot, long long row_first, int rows,
+                                       const float *max_dist2_dev /*[rows] or NULL*/, float cap, unsigned *counts_dev /*[rows]*/,
+                                       void *stream, unsigned flags);
+int knn_index_self_list_within_routed(knn_index *idx, int slot, long long row_first, int rows,
+                                      const float *max_dist2_dev /*[rows] or NULL*/, float cap,
+                                      const unsigned long long *offsets_dev /*[rows+1]*/, unsigned *fill_dev /*[rows]*/,
+                                      unsigned long long *keys_dev, void *stream, unsigned flags);
+/* Synchronous, the WHOLE shard in blocks of 65536 rows: routed self count -> knn_counts_to_offsets -> routed self list ->
+ * knn_keys_sort_segments under `flags` (the init flag is implied); the CSR adjacency comes out as knn_index_self_list_within_host
+ * returns it (malloc'd arrays, the 1-entry rule; n_local <= INT_MAX).  max_dist2_host [n_local] or NULL (the scalar form).  cap < 0
+ * or NaN, an unknown flag, a null offsets or indices pointer and a null index are KNN_EINVAL, in this order. */
+int knn_index_self_list_within_routed_host(knn_index *idx, const float *max_dist2_host, float cap, unsigned flags,
+                                           long long *offsets_host /*[n_local+1]*/, int **indices_out, float **dist2_out /*NULL ok*/);
+/* Test hook, host arithmetic only: knn_debug_count_plan's sixteen inputs with m = the call's rows (1 <= rows <= the shard's rows
+ * <= 2^32) and its eight outputs; out[6] is the slices of the exact self-scan (knn_debug_self_plan's for a count call). */
+int knn_debug_self_routed_plan(const long long in[16], long long out[8]);
+
 /* Tuning / test hooks.  Known names:
  *   "path"    0 = auto, 1 = exact VALU kernels only, 2 = force the MFMA filter
  *             (+ exact re-rank) where its preconditions hold, 3 = the uniform-grid spatial index

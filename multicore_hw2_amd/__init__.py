@@ -25,7 +25,8 @@ __all__ = ["lib", "lib_path", "cudaCallback", "KnnIndex", "KnnGeom", "KnnError",
            "self_topk_c", "self_count_within_c", "self_list_within_c", "self_topk_host_c", "self_list_within_host_c",
            "debug_self_plan", "debug_self_ranges",
            "count_within_each_c", "list_within_each_c", "self_count_within_each_c", "self_list_within_each_c",
-           "count_within_each_host_c", "list_within_each_host_c", "keys_column_dist2_c", "keys_column_dist2", "debug_each_radius"]
+           "count_within_each_host_c", "list_within_each_host_c", "keys_column_dist2_c", "keys_column_dist2", "debug_each_radius",
+           "self_count_within_routed_c", "self_list_within_routed_c", "self_list_within_routed_host_c", "debug_self_routed_plan"]
 
 KEY_INIT = 0x7F80000000000000
 
@@ -55,6 +56,8 @@ EXPORTED_SYMBOLS = [
     "knn_index_count_within_each", "knn_index_list_within_each", "knn_index_self_count_within_each",
     "knn_index_self_list_within_each", "knn_keys_column_dist2", "knn_index_count_within_each_host",
     "knn_index_list_within_each_host", "knn_debug_each_radius",
+    "knn_index_self_count_within_routed", "knn_index_self_list_within_routed", "knn_index_self_list_within_routed_host",
+    "knn_debug_self_routed_plan",
 ]
 TOPK_LARGE_MAX = 4096   # KNN_TOPK_LARGE_MAX
 QUERY_INIT_KEYS = 1   # KNN_QUERY_INIT_KEYS
@@ -742,6 +745,41 @@ def self_list_within_each_c():
     return f
 
 
+def self_count_within_routed_c():
+    """knn_index_self_count_within_routed with its argument types (set here, not in lib(), as count_within_c)."""
+    f = lib().knn_index_self_count_within_routed
+    f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p,
+                  ctypes.c_void_p, ctypes.c_uint]
+    return f
+
+
+def self_list_within_routed_c():
+    """knn_index_self_list_within_routed with its argument types (set here, not in lib(), as count_within_c)."""
+    f = lib().knn_index_self_list_within_routed
+    f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p,
+                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint]
+    return f
+
+
+def self_list_within_routed_host_c():
+    f = lib().knn_index_self_list_within_routed_host
+    f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_uint, ctypes.c_void_p,
+                  ctypes.POINTER(ctypes.POINTER(ctypes.c_int)), ctypes.POINTER(ctypes.POINTER(ctypes.c_float))]
+    return f
+
+
+def debug_self_routed_plan(**inputs):
+    """knn_debug_self_routed_plan: which way answers a self_count_within_routed / self_list_within_routed call and what it launches
+    with, for the inputs named in COUNT_PLAN_INPUTS (m: the call's rows); the outputs are COUNT_PLAN's, slices the exact self-scan's.
+    Host arithmetic; works without a GPU."""
+    vin = (ctypes.c_longlong * len(COUNT_PLAN_INPUTS))(*[int(inputs[n]) for n in COUNT_PLAN_INPUTS])
+    out = (ctypes.c_longlong * len(COUNT_PLAN))()
+    f = lib().knn_debug_self_routed_plan
+    f.argtypes = [ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)]
+    _check(f(vin, out))
+    return dict(zip(COUNT_PLAN, list(out)))
+
+
 def count_within_each_host_c():
     f = lib().knn_index_count_within_each_host
     f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p]
@@ -1249,6 +1287,52 @@ class KnnIndex:
                                          ctypes.c_void_p(int(offsets_dev)), ctypes.c_void_p(int(fill_dev)),
                                          ctypes.c_void_p(int(keys_dev)), ctypes.c_void_p(stream),
                                          (QUERY_INIT_KEYS if init else 0) | int(flags)))
+
+    def self_count_within_routed(self, row_first, rows, counts_dev, cap=float("inf"), max_dist2_dev=None, stream=0, slot=0, init=False,
+                                 grid=False, cells=False, flags=0):
+        """Async (knn_index_self_count_within_routed): self_count_within (max_dist2_dev None: every row's radius is cap) or
+        self_count_within_each (max_dist2_dev: float32 on the device, a radius per row, under cap) on the way count_within would
+        take for `rows` queries at cap: grid / cells ask for the grid index / the cell-pruned scan (QUERY_COUNT_GRID /
+        QUERY_COUNT_CELLS); without them the exact self-scan.  flags: further flag bits as they are (every one of them raises)."""
+        _check(self_count_within_routed_c()(self._h, int(slot), int(row_first), int(rows),
+                                            ctypes.c_void_p(int(max_dist2_dev)) if max_dist2_dev is not None else None, float(cap),
+                                            ctypes.c_void_p(int(counts_dev)), ctypes.c_void_p(stream),
+                                            (QUERY_INIT_KEYS if init else 0) | (QUERY_COUNT_GRID if grid else 0) |
+                                            (QUERY_COUNT_CELLS if cells else 0) | int(flags)))
+
+    def self_list_within_routed(self, row_first, rows, offsets_dev, fill_dev, keys_dev, cap=float("inf"), max_dist2_dev=None, stream=0,
+                                slot=0, init=False, grid=False, cells=False, flags=0):
+        """Async (knn_index_self_list_within_routed): self_list_within / self_list_within_each on self_count_within_routed's way.
+        The third step of self_count_within_routed -> counts_to_offsets -> this -> keys_sort_segments."""
+        _check(self_list_within_routed_c()(self._h, int(slot), int(row_first), int(rows),
+                                           ctypes.c_void_p(int(max_dist2_dev)) if max_dist2_dev is not None else None, float(cap),
+                                           ctypes.c_void_p(int(offsets_dev)), ctypes.c_void_p(int(fill_dev)),
+                                           ctypes.c_void_p(int(keys_dev)), ctypes.c_void_p(stream),
+                                           (QUERY_INIT_KEYS if init else 0) | (QUERY_COUNT_GRID if grid else 0) |
+                                           (QUERY_COUNT_CELLS if cells else 0) | int(flags)))
+
+    def self_list_within_routed_host(self, cap, max_dist2=None, grid=False, cells=False, flags=0):
+        """Synchronous radius graph of this shard on the routed self calls (knn_index_self_list_within_routed_host), in
+        self_list_within_host's CSR form.  max_dist2: None, or a radius per row (float32 [n]) under cap."""
+        n = int(self.n)
+        offsets = np.empty(n + 1, dtype=np.int64)
+        rad = None if max_dist2 is None else np.ascontiguousarray(max_dist2, dtype=np.float32).reshape(-1)
+        if rad is not None and rad.size != n:
+            raise ValueError("max_dist2 must hold one radius per row of the shard")
+        ind, d2 = ctypes.POINTER(ctypes.c_int)(), ctypes.POINTER(ctypes.c_float)()
+        _check(self_list_within_routed_host_c()(self._h, rad.ctypes.data_as(ctypes.c_void_p) if rad is not None else None, float(cap),
+                                                (QUERY_COUNT_GRID if grid else 0) | (QUERY_COUNT_CELLS if cells else 0) | int(flags),
+                                                offsets.ctypes.data_as(ctypes.c_void_p), ctypes.byref(ind), ctypes.byref(d2)))
+        total = int(offsets[n])
+        free = ctypes.CDLL(None).free
+        free.argtypes = [ctypes.c_void_p]
+        try:
+            indices = np.ctypeslib.as_array(ind, shape=(max(total, 1),))[:total].astype(np.int32, copy=True)
+            dist2 = np.ctypeslib.as_array(d2, shape=(max(total, 1),))[:total].astype(np.float32, copy=True)
+        finally:
+            free(ind)
+            free(d2)
+        return offsets, indices, dist2
 
     def self_list_within_host(self, max_dist2):
         """Synchronous radius graph of this shard (knn_index_self_list_within_host) in CSR form: (offsets int64 [n + 1], indices

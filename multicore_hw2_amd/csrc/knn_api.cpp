@@ -2300,6 +2300,198 @@ int knn_index_self_list_within_each(knn_index *idx, int slot, long long row_firs
                          keys_dev, stream, flags);
 }
 
+// The radius graph on the grid and cell-pruned ways (include/knn_mi355x.h 2k; DESIGN §4.6 "The radius graph on the pruned ways").
+// A routed self count call behind its host-only argument checks, built as count_within_run with the queries that are the rows
+// themselves: the way is knn_count_route's for `rows` queries at max_dist2 = cap under the same flags and options — way 1 the
+// exact self-scan in the exact count's place —, and call.self_first tells the grid and cell ways to drop a query's own row and to
+// gate the self-scan behind them.  radii_dev null: the scalar form, every row's radius the cap.
+static int self_routed_count_run(knn_index *idx, const char *who, int slot, long long row_first, int rows, const float *radii_dev,
+                                 float cap, unsigned *counts_dev, void *stream, unsigned flags)
+{
+    std::lock_guard<std::recursive_mutex> lock(idx->mu);
+    if (row_first > idx->n || (long long)rows > idx->n - row_first)
+        return fail_in(KNN_EINVAL, who, "row_first + rows above the shard's rows");
+    DeviceGuard guard(idx->device);
+    if (!guard.ok)
+        return fail_in(KNN_EHIP, who, "hipSetDevice failed");
+    CountCall call;
+    call.k = idx->k;
+    call.m = rows;
+    call.n = idx->n;
+    call.r = idx->refs;
+    call.q = idx->refs + (size_t)row_first * (size_t)idx->k;   // the queries are resident: nothing is uploaded
+    call.self_first = row_first;
+    call.counts = counts_dev;
+    call.radii = radii_dev;
+    call.max_dist2 = cap == 0.0f ? 0.0f : cap;   // (-0 counts as 0)
+    call.num_cu = idx->num_cu;
+    call.stream = (hipStream_t)stream;
+    hipStream_t s = call.stream;
+    idx->stats[0] = 1;
+    idx->stats[1] = 0;
+    idx->stats[2] = 0;
+    idx->stats[3] = 0;
+    idx->grid_topk_gate = nullptr;
+    idx->last_slot = slot;
+    // every way ADDS to the caller's counts: an init call zeroes them first
+    if ((flags & KNN_QUERY_INIT_KEYS) != 0u)
+        HIP_TRY(hipMemsetAsync(counts_dev, 0, (size_t)rows * sizeof(unsigned), s));
+    const QueryRouteInputs ri = route_inputs(idx, rows, 1, 0u);
+    const CountPlan plan = count_plan_of(idx, ri, rows, call.max_dist2, flags);
+    idx->stats[0] = (long long)plan.way;
+    // the slot's count scratch, grown before the first launch
+    knn_index::TopkSlot &ts = idx->topk[slot];
+    KNN_TRY(slot_buffer_grow(ts.count, ts.count_bytes, plan.scratch_bytes));
+    call.scratch = (unsigned *)ts.count;
+    EventPair *ev = nullptr;
+    KNN_TRY(next_event_pair(idx, false, &ev));
+    call.ev0 = ev ? ev->first : nullptr;
+    call.ev1 = ev ? ev->second : nullptr;
+    switch (plan.way) {
+    case QueryWay::Grid:
+        HIP_TRY(knn_grid_query_count(idx->grid, plan.rmax, slot, call, &idx->grid_topk_gate));
+        break;
+    case QueryWay::Cells: {
+        const CellTopkPlan tp = knn_cells_count_plan(ri.t);
+        if (!tp.use)
+            return fail_in(KNN_EHIP, who, "the cell-pruned scan has no pass shape for this layout");
+        HIP_TRY(knn_filter_query_count_cells(idx->filter, tp, slot, call));
+        break;
+    }
+    default:   // exactly what the existing self call launches
+        HIP_TRY(knn_self_count_launch(call, row_first));
+        break;
+    }
+    return KNN_OK;
+}
+
+// ... and a routed self list call, built as list_within_run.
+static int self_routed_list_run(knn_index *idx, const char *who, int slot, long long row_first, int rows, const float *radii_dev,
+                                float cap, const unsigned long long *offsets_dev, unsigned *fill_dev, unsigned long long *keys_dev,
+                                void *stream, unsigned flags)
+{
+    std::lock_guard<std::recursive_mutex> lock(idx->mu);
+    if (row_first > idx->n || (long long)rows > idx->n - row_first)
+        return fail_in(KNN_EINVAL, who, "row_first + rows above the shard's rows");
+    DeviceGuard guard(idx->device);
+    if (!guard.ok)
+        return fail_in(KNN_EHIP, who, "hipSetDevice failed");
+    ListCall call;
+    call.k = idx->k;
+    call.m = rows;
+    call.n = idx->n;
+    call.base = idx->base;
+    // a cell-range shard's keys carry its rows' global numbers (gids); an index-range shard's base + row
+    call.gids = idx->sharded && idx->filter.cells ? idx->filter.cells->gids : nullptr;
+    call.r = idx->refs;
+    call.q = idx->refs + (size_t)row_first * (size_t)idx->k;   // the queries are resident: nothing is uploaded
+    call.self_first = row_first;
+    call.offsets = (const u64 *)offsets_dev;
+    call.fill = fill_dev;
+    call.keys = (u64 *)keys_dev;
+    call.radii = radii_dev;
+    call.max_dist2 = cap == 0.0f ? 0.0f : cap;   // (-0 counts as 0)
+    call.num_cu = idx->num_cu;
+    call.stream = (hipStream_t)stream;
+    hipStream_t s = call.stream;
+    idx->stats[0] = 1;
+    idx->stats[1] = 0;
+    idx->stats[2] = 0;
+    idx->stats[3] = 0;
+    idx->grid_topk_gate = nullptr;
+    idx->last_slot = slot;
+    // every way APPENDS behind the caller's fill: an init call zeroes it first
+    if ((flags & KNN_QUERY_INIT_KEYS) != 0u)
+        HIP_TRY(hipMemsetAsync(fill_dev, 0, (size_t)rows * sizeof(unsigned), s));
+    const QueryRouteInputs ri = route_inputs(idx, rows, 1, 0u);
+    const CountPlan plan = count_plan_of(idx, ri, rows, call.max_dist2, flags);
+    idx->stats[0] = (long long)plan.way;
+    // the slot's count scratch — the scratch cursor of the grid and cell ways —, grown before the first launch
+    knn_index::TopkSlot &ts = idx->topk[slot];
+    KNN_TRY(slot_buffer_grow(ts.count, ts.count_bytes, plan.scratch_bytes));
+    call.scratch = (unsigned *)ts.count;
+    EventPair *ev = nullptr;
+    KNN_TRY(next_event_pair(idx, false, &ev));
+    call.ev0 = ev ? ev->first : nullptr;
+    call.ev1 = ev ? ev->second : nullptr;
+    switch (plan.way) {
+    case QueryWay::Grid:
+        HIP_TRY(knn_grid_query_list(idx->grid, plan.rmax, slot, call, &idx->grid_topk_gate));
+        break;
+    case QueryWay::Cells: {
+        const CellTopkPlan tp = knn_cells_count_plan(ri.t);
+        if (!tp.use)
+            return fail_in(KNN_EHIP, who, "the cell-pruned scan has no pass shape for this layout");
+        HIP_TRY(knn_filter_query_list_cells(idx->filter, tp, slot, call));
+        break;
+    }
+    default:   // exactly what the existing self call launches
+        HIP_TRY(knn_self_list_launch(call, row_first));
+        break;
+    }
+    return KNN_OK;
+}
+
+int knn_index_self_count_within_routed(knn_index *idx, int slot, long long row_first, int rows, const float *max_dist2_dev, float cap,
+                                       unsigned *counts_dev, void *stream, unsigned flags)
+{
+    // (one message per rule, the index last but for the rule that needs it: tests/test_self_routed_logic.py tells them apart)
+    if (!(cap >= 0.0f))
+        return fail(KNN_EINVAL, "knn_index_self_count_within_routed: cap must be >= 0 (or +INF) and not NaN");
+    constexpr unsigned kFlags = KNN_QUERY_INIT_KEYS | KNN_QUERY_COUNT_GRID | KNN_QUERY_COUNT_CELLS;   // the three it admits
+    if ((flags & ~kFlags) != 0u)
+        return fail(KNN_EINVAL, "knn_index_self_count_within_routed: unknown flag (KNN_QUERY_INIT_KEYS, KNN_QUERY_COUNT_GRID, "
+                                "KNN_QUERY_COUNT_CELLS)");
+    if (slot < 0 || slot >= KNN_SLOTS)
+        return fail(KNN_EINVAL, "knn_index_self_count_within_routed: slot outside 0 .. 7");
+    if (rows < 1)
+        return fail(KNN_EINVAL, "knn_index_self_count_within_routed: rows < 1");
+    if (row_first < 0)
+        return fail(KNN_EINVAL, "knn_index_self_count_within_routed: row_first < 0");
+    if (!counts_dev)
+        return fail(KNN_EINVAL, "knn_index_self_count_within_routed: null counts");
+    if (!idx)
+        return fail(KNN_EINVAL, "knn_index_self_count_within_routed: null index");
+    return self_routed_count_run(idx, "knn_index_self_count_within_routed", slot, row_first, rows, max_dist2_dev, cap, counts_dev, stream,
+                                 flags);
+}
+
+int knn_index_self_list_within_routed(knn_index *idx, int slot, long long row_first, int rows, const float *max_dist2_dev, float cap,
+                                      const unsigned long long *offsets_dev, unsigned *fill_dev, unsigned long long *keys_dev,
+                                      void *stream, unsigned flags)
+{
+    if (!(cap >= 0.0f))
+        return fail(KNN_EINVAL, "knn_index_self_list_within_routed: cap must be >= 0 (or +INF) and not NaN");
+    constexpr unsigned kFlags = KNN_QUERY_INIT_KEYS | KNN_QUERY_COUNT_GRID | KNN_QUERY_COUNT_CELLS;   // the three it admits
+    if ((flags & ~kFlags) != 0u)
+        return fail(KNN_EINVAL, "knn_index_self_list_within_routed: unknown flag (KNN_QUERY_INIT_KEYS, KNN_QUERY_COUNT_GRID, "
+                                "KNN_QUERY_COUNT_CELLS)");
+    if (slot < 0 || slot >= KNN_SLOTS)
+        return fail(KNN_EINVAL, "knn_index_self_list_within_routed: slot outside 0 .. 7");
+    if (rows < 1)
+        return fail(KNN_EINVAL, "knn_index_self_list_within_routed: rows < 1");
+    if (row_first < 0)
+        return fail(KNN_EINVAL, "knn_index_self_list_within_routed: row_first < 0");
+    if (!offsets_dev || !fill_dev || !keys_dev)
+        return fail(KNN_EINVAL, "knn_index_self_list_within_routed: null offsets, fill or keys");
+    if (!idx)
+        return fail(KNN_EINVAL, "knn_index_self_list_within_routed: null index");
+    return self_routed_list_run(idx, "knn_index_self_list_within_routed", slot, row_first, rows, max_dist2_dev, cap, offsets_dev, fill_dev,
+                                keys_dev, stream, flags);
+}
+
+int knn_debug_self_routed_plan(const long long in[16], long long out[8])
+{
+    // knn_debug_count_plan's inputs with m = the call's rows, which lie inside the shard; its outputs, [6] from the self-scan's plan
+    if (!in || !out || in[1] < 1 || in[1] > in[2] || in[2] > (1ll << 32))
+        return fail(KNN_EINVAL, "knn_debug_self_routed_plan: bad arguments (knn_debug_count_plan's, and 1 <= rows <= the shard's rows <= 2^32)");
+    const int rv = knn_debug_count_plan(in, out);
+    if (rv != KNN_OK)
+        return fail(rv, "knn_debug_self_routed_plan: bad arguments (knn_debug_count_plan's, and 1 <= rows <= the shard's rows <= 2^32)");
+    out[6] = knn_self_plan((int)in[0], (int)in[1], 0, in[2], (int)in[14], true).slices;
+    return KNN_OK;
+}
+
 int knn_keys_column_dist2(int device, const unsigned long long *keys_dev, int m, int K, int column, float *dist2_dev, void *stream)
 {
     if (m < 1)
@@ -3170,67 +3362,77 @@ extern "C" int knn_index_self_topk_host(knn_index *idx, int K, float max_dist2, 
     return KNN_OK;
 }
 
-extern "C" int knn_index_self_list_within_host(knn_index *idx, float max_dist2, long long *offsets_host, int **indices_out,
-                                               float **dist2_out)
+// The radius graph of the whole shard on the host, behind the argument checks: knn_index_self_list_within_host (routed false: the
+// existing self calls, max_dist2 the radius) and knn_index_self_list_within_routed_host (routed: the 2k calls under `flags`,
+// radii_host [n_local] or null, max_dist2 the cap).  Blocks of 65536 rows: count -> offsets -> list -> sort.
+static int self_list_host_run(knn_index *idx, const char *who, bool routed, const float *radii_host, float max_dist2, unsigned flags,
+                              long long *offsets_host, int **indices_out, float **dist2_out)
 {
-    if (!(max_dist2 >= 0.0f))
-        return fail(KNN_EINVAL, "knn_index_self_list_within_host: max_dist2 must be >= 0 and not NaN");
-    if (!offsets_host || !indices_out)
-        return fail(KNN_EINVAL, "knn_index_self_list_within_host: null offsets or indices");
-    if (!idx)
-        return fail(KNN_EINVAL, "knn_index_self_list_within_host: null index");
     *indices_out = nullptr;
     if (dist2_out)
         *dist2_out = nullptr;
     std::lock_guard<std::recursive_mutex> lock(idx->mu);
     if (idx->n > INT_MAX)
-        return fail(KNN_EINVAL, "knn_index_self_list_within_host: more than INT_MAX rows (use the device calls, a block of rows at a time)");
+        return fail_in(KNN_EINVAL, who, "more than INT_MAX rows (use the device calls, a block of rows at a time)");
     DeviceGuard guard(idx->device);
     if (!guard.ok)
-        return fail(KNN_EHIP, "knn_index_self_list_within_host: hipSetDevice failed");
+        return fail_in(KNN_EHIP, who, "hipSetDevice failed");
     const int n = (int)idx->n;
     const int step = KNN_TOPK_CHUNK;   // rows per call
+    const unsigned fl = KNN_QUERY_INIT_KEYS | flags;
     std::vector<u64> offs((size_t)n + 1, 0ull);
     std::vector<u64> keys;
     Staging stage(idx->device);
     if (n > 0) {
         unsigned *c_dev = nullptr, *fill_dev = nullptr;
         u64 *off_dev = nullptr, *keys_dev = nullptr;
+        float *rad_dev = nullptr;
         const size_t cbytes = (size_t)n * sizeof(unsigned), obytes = ((size_t)n + 1) * sizeof(u64);
         hipError_t e = stage.get(&c_dev, cbytes);
         if (e == hipSuccess)
             e = stage.get(&fill_dev, cbytes);
         if (e == hipSuccess)
             e = stage.get(&off_dev, obytes);
+        if (e == hipSuccess && radii_host)
+            e = stage.get(&rad_dev, (size_t)n * sizeof(float));
         if (e != hipSuccess)
-            return fail(KNN_EHIP, "knn_index_self_list_within_host: staging counts", hipGetErrorString(e));
+            return fail_in(KNN_EHIP, who, "staging counts", hipGetErrorString(e));
+        if (radii_host) {
+            e = hipMemcpy(rad_dev, radii_host, (size_t)n * sizeof(float), hipMemcpyHostToDevice);
+            if (e != hipSuccess)
+                return fail_in(KNN_EHIP, who, "H2D radii", hipGetErrorString(e));
+        }
         // count -> offsets, then the one synchronisation: the total sizes the keys
         int rv = KNN_OK;
         for (int r0 = 0; r0 < n && rv == KNN_OK; r0 += step)
-            rv = knn_index_self_count_within(idx, 0, r0, std::min(step, n - r0), max_dist2, c_dev + r0, nullptr, KNN_QUERY_INIT_KEYS);
+            rv = routed ? knn_index_self_count_within_routed(idx, 0, r0, std::min(step, n - r0), rad_dev ? rad_dev + r0 : nullptr, max_dist2,
+                                                             c_dev + r0, nullptr, fl)
+                        : knn_index_self_count_within(idx, 0, r0, std::min(step, n - r0), max_dist2, c_dev + r0, nullptr, fl);
         if (rv == KNN_OK)
             rv = knn_counts_to_offsets(idx->device, c_dev, n, off_dev, nullptr);
         if (rv != KNN_OK)
             return rv;
         e = hipMemcpy(offs.data(), off_dev, obytes, hipMemcpyDeviceToHost);
         if (e != hipSuccess)
-            return fail(KNN_EHIP, "knn_index_self_list_within_host: D2H offsets", hipGetErrorString(e));
+            return fail_in(KNN_EHIP, who, "D2H offsets", hipGetErrorString(e));
         const u64 total = offs[(size_t)n];
         keys.resize((size_t)total);
         if (total) {   // list -> sort (the offsets are absolute: every block of rows stores into the one keys array)
             e = stage.get(&keys_dev, (size_t)total * sizeof(u64));
             if (e != hipSuccess)
-                return fail(KNN_EHIP, "knn_index_self_list_within_host: staging keys", hipGetErrorString(e));
+                return fail_in(KNN_EHIP, who, "staging keys", hipGetErrorString(e));
             for (int r0 = 0; r0 < n && rv == KNN_OK; r0 += step)
-                rv = knn_index_self_list_within(idx, 0, r0, std::min(step, n - r0), max_dist2, off_dev + r0, fill_dev + r0, keys_dev, nullptr,
-                                                KNN_QUERY_INIT_KEYS);
+                rv = routed ? knn_index_self_list_within_routed(idx, 0, r0, std::min(step, n - r0), rad_dev ? rad_dev + r0 : nullptr,
+                                                                max_dist2, off_dev + r0, fill_dev + r0, keys_dev, nullptr, fl)
+                            : knn_index_self_list_within(idx, 0, r0, std::min(step, n - r0), max_dist2, off_dev + r0, fill_dev + r0,
+                                                         keys_dev, nullptr, fl);
             if (rv == KNN_OK)
                 rv = knn_keys_sort_segments(idx->device, n, off_dev, fill_dev, keys_dev, nullptr);
             if (rv != KNN_OK)
                 return rv;
             e = hipMemcpy(keys.data(), keys_dev, (size_t)total * sizeof(u64), hipMemcpyDeviceToHost);
             if (e != hipSuccess)
-                return fail(KNN_EHIP, "knn_index_self_list_within_host: D2H keys", hipGetErrorString(e));
+                return fail_in(KNN_EHIP, who, "D2H keys", hipGetErrorString(e));
         }
     }
     const size_t total = keys.size(), room = total ? total : 1u;
@@ -3239,7 +3441,7 @@ extern "C" int knn_index_self_list_within_host(knn_index *idx, float max_dist2, 
     if (!ind || (dist2_out && !d2)) {
         free(ind);
         free(d2);
-        return fail(KNN_EHIP, "knn_index_self_list_within_host: out of host memory");
+        return fail_in(KNN_EHIP, who, "out of host memory");
     }
     for (size_t i = 0; i < total; ++i) {
         ind[i] = (int)(unsigned)(keys[i] & 0xFFFFFFFFull);
@@ -3256,6 +3458,36 @@ extern "C" int knn_index_self_list_within_host(knn_index *idx, float max_dist2, 
     // (not declared waited: the slot's buffers go back after the device-wide wait `stage` then makes itself, as the other host calls)
     return KNN_OK;
 }
+
+extern "C" int knn_index_self_list_within_host(knn_index *idx, float max_dist2, long long *offsets_host, int **indices_out,
+                                               float **dist2_out)
+{
+    if (!(max_dist2 >= 0.0f))
+        return fail(KNN_EINVAL, "knn_index_self_list_within_host: max_dist2 must be >= 0 and not NaN");
+    if (!offsets_host || !indices_out)
+        return fail(KNN_EINVAL, "knn_index_self_list_within_host: null offsets or indices");
+    if (!idx)
+        return fail(KNN_EINVAL, "knn_index_self_list_within_host: null index");
+    return self_list_host_run(idx, "knn_index_self_list_within_host", false, nullptr, max_dist2, 0u, offsets_host, indices_out, dist2_out);
+}
+
+extern "C" int knn_index_self_list_within_routed_host(knn_index *idx, const float *max_dist2_host, float cap, unsigned flags,
+                                                      long long *offsets_host, int **indices_out, float **dist2_out)
+{
+    if (!(cap >= 0.0f))
+        return fail(KNN_EINVAL, "knn_index_self_list_within_routed_host: cap must be >= 0 (or +INF) and not NaN");
+    constexpr unsigned kFlags = KNN_QUERY_INIT_KEYS | KNN_QUERY_COUNT_GRID | KNN_QUERY_COUNT_CELLS;   // the three it admits
+    if ((flags & ~kFlags) != 0u)
+        return fail(KNN_EINVAL, "knn_index_self_list_within_routed_host: unknown flag (KNN_QUERY_INIT_KEYS, KNN_QUERY_COUNT_GRID, "
+                                "KNN_QUERY_COUNT_CELLS)");
+    if (!offsets_host || !indices_out)
+        return fail(KNN_EINVAL, "knn_index_self_list_within_routed_host: null offsets or indices");
+    if (!idx)
+        return fail(KNN_EINVAL, "knn_index_self_list_within_routed_host: null index");
+    return self_list_host_run(idx, "knn_index_self_list_within_routed_host", true, max_dist2_host, cap, flags, offsets_host, indices_out,
+                              dist2_out);
+}
+
 
 extern "C" int knn_index_list_within_masked_host(knn_index *idx, int m, const float *queries_host, float max_dist2,
                                                  const unsigned *mask_host, long long *offsets_host, int **indices_out, float **dist2_out)

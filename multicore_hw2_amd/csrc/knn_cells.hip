@@ -3202,8 +3202,8 @@ hipError_t knn_cells_query_count(FilterState &st, FilterWorkspace &w, const Cell
     b.radii = call.radii;
     FTRY(cells_pass_front(w, b, cells_records_kernel(tp.scan), call.radii ? CellPrepForm::CountEach : CellPrepForm::Count, timed));
     FTRY(knn_count_records_finish(call, cells_pass_records(st, w), call.scratch));
-    // gated: the exact count answers a pass that raised FALLBACK (its scratch was not committed)
-    return knn_exact_count_launch(call, w.ctl_cur + KNN_CTL_FALLBACK);
+    // gated: the exact count — a routed self call: the self-scan — answers a pass that raised FALLBACK (its scratch was not committed)
+    return knn_gated_count_launch(call, w.ctl_cur + KNN_CTL_FALLBACK);
 }
 
 // One pass of <= KNN_CELL_BATCH queries of a list call (knn_index_list_within with KNN_QUERY_COUNT_CELLS; DESIGN §4.6 "Lists within
@@ -3224,8 +3224,9 @@ hipError_t knn_cells_query_list(FilterState &st, FilterWorkspace &w, const CellT
     b.radii = call.radii;
     FTRY(cells_pass_front(w, b, cells_records_kernel(tp.scan), call.radii ? CellPrepForm::CountEach : CellPrepForm::Count, timed));
     FTRY(knn_list_records_finish(call, cells_pass_records(st, w)));
-    // gated: the exact list answers a pass that raised FALLBACK (its scratch cursor was not committed)
-    return knn_exact_list_launch(call, w.ctl_cur + KNN_CTL_FALLBACK);
+    // gated: the exact list — a routed self call: the self-scan — answers a pass that raised FALLBACK (its scratch cursor was not
+    // committed)
+    return knn_gated_list_launch(call, w.ctl_cur + KNN_CTL_FALLBACK);
 }
 
 // Test hook (host arithmetic, no GPU): knn_threshold's Dup for a seed score u — out = {thr, Dup as the prep kernel stores it (fp32,

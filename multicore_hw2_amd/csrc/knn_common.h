@@ -165,6 +165,9 @@ struct CountCall {
     // nullable; a call with a radius per query (2j): device [m], query j's radius.  max_dist2 is then the call's cap, and a row is
     // a hit when E <= radii[j] and E <= max_dist2; every way launches its each-form kernels (knn_each_radius.h)
     const float *radii = nullptr;
+    // >= 0: a routed call about the shard's own rows (2k): query j is LOCAL row self_first + j (q = r + self_first * k), which is
+    // no candidate for itself; the grid and cell ways launch their self forms and the gated self-scan.  -1: a plain call
+    long long self_first = -1;
 
     // queries [q0, q0 + mb) of the call: a pass of the cell-pruned way
     CountCall pass(int q0, int mb) const
@@ -175,6 +178,7 @@ struct CountCall {
         c.counts = counts + q0;
         c.scratch = scratch + q0;
         c.radii = radii ? radii + q0 : nullptr;
+        c.self_first = self_first < 0 ? -1 : self_first + q0;   // (the own rows advance with the queries)
         return c;
     }
 };
@@ -208,6 +212,7 @@ struct ListCall {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;   // nullable: bracket the way's dominant kernel
     unsigned *scratch = nullptr;   // the slot's count scratch [m]: the scratch cursor of the grid and cell ways (the exact way does not use it)
     const float *radii = nullptr;  // nullable; a radius per query, device [m], max_dist2 the cap: as CountCall::radii
+    long long self_first = -1;     // >= 0: a routed call about the shard's own rows, as CountCall::self_first
 
     // queries [q0, q0 + mb) of the call: a pass of the cell-pruned way (offsets are absolute: keys stays)
     ListCall pass(int q0, int mb) const
@@ -219,6 +224,7 @@ struct ListCall {
         c.fill = fill + q0;
         c.scratch = scratch + q0;
         c.radii = radii ? radii + q0 : nullptr;
+        c.self_first = self_first < 0 ? -1 : self_first + q0;   // (the own rows advance with the queries)
         return c;
     }
 };
@@ -245,6 +251,11 @@ hipError_t knn_keys_column_dist2_launch(const u64 *keys, int m, int K, int colum
 // the radius of the record's own query, the same commit.  The plain functions hand such a pass over after their own checks.
 hipError_t knn_count_each_records_finish(const CountCall &c, const TopkRecords &rs, unsigned *qcount);
 hipError_t knn_list_each_records_finish(const ListCall &c, const TopkRecords &rs);
+// ... and for a pass of a routed call about the shard's own rows (c.self_first >= 0; knn_self_routed.hip): the same walks, a
+// candidate whose LOCAL row is the record's query's own (c.self_first + the pass's query number) dropped; c.radii null: every
+// query's radius is c.max_dist2.  The plain functions hand such a pass over after their own checks, ahead of the each-forms.
+hipError_t knn_count_self_records_finish(const CountCall &c, const TopkRecords &rs, unsigned *qcount);
+hipError_t knn_list_self_records_finish(const ListCall &c, const TopkRecords &rs);
 
 // ---- top-K beyond 64 (knn_select.hip; knn_index_query_topk_large; DESIGN §4.6 "Top-K beyond 64") --------------------------------
 #define KNN_TOPK_LARGE_MAX 4096   // largest K of knn_index_query_topk_large (= KNN_SORT_LDS_KEYS: a list sorts in LDS)
@@ -349,8 +360,19 @@ SelfPlan knn_self_plan(int k, int m, int K, long long n, int num_cu, bool init);
 // knn_exact_list_launch with query j = local row row_first + j of the shard, which is no candidate for itself (identity by local
 // row number: other copies of the row stay candidates).  c.q is not read.  0 <= row_first, row_first + c.m <= c.n.
 hipError_t knn_self_topk_launch(const TopkCall &c, long long row_first);
-hipError_t knn_self_count_launch(const CountCall &c, long long row_first);
-hipError_t knn_self_list_launch(const ListCall &c, long long row_first);
+// gate != nullptr (count and list): the launches do nothing unless *gate != 0 — the exact answer behind the grid way and behind a
+// cell-pruned pass of a routed self call, as knn_exact_count_launch's gate; the call's events are not recorded then.
+hipError_t knn_self_count_launch(const CountCall &c, long long row_first, const unsigned *gate = nullptr);
+hipError_t knn_self_list_launch(const ListCall &c, long long row_first, const unsigned *gate = nullptr);
+// The exact answer behind a pruned way, gated: the self-scan for a routed self call (c.self_first >= 0), else the exact count / list.
+static inline hipError_t knn_gated_count_launch(const CountCall &c, const unsigned *gate)
+{
+    return c.self_first >= 0 ? knn_self_count_launch(c, c.self_first, gate) : knn_exact_count_launch(c, gate);
+}
+static inline hipError_t knn_gated_list_launch(const ListCall &c, const unsigned *gate)
+{
+    return c.self_first >= 0 ? knn_self_list_launch(c, c.self_first, gate) : knn_exact_list_launch(c, gate);
+}
 // out[j][0 .. K) <- lists[j][0 .. K] (sorted, K + 1 <= KNN_TOPK_MAX keys) without the real key that carries the global number of
 // local row row_first + j (base + row, or gids[row]) — without the last key when there is none.
 hipError_t knn_self_drop_launch(int m, int K, const u64 *lists, long long row_first, long long base, const unsigned *gids, u64 *out,

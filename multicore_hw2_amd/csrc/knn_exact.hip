@@ -1612,6 +1612,8 @@ hipError_t knn_count_records_finish(const CountCall &c, const TopkRecords &rs, u
     hipStream_t s = c.stream;
     if (rs.rec_rows || !rs.perm || !rs.pos_norms || !qcount)
         return hipErrorInvalidValue;
+    if (c.self_first >= 0)
+        return knn_count_self_records_finish(c, rs, qcount);   // (knn_self_routed.hip)
     if (c.radii)
         return knn_count_each_records_finish(c, rs, qcount);   // (knn_each.hip)
     if (rs.nlists)
@@ -1912,6 +1914,8 @@ hipError_t knn_list_records_finish(const ListCall &c, const TopkRecords &rs)
     hipStream_t s = c.stream;
     if (rs.rec_rows || !rs.perm || !rs.pos_norms || !c.scratch)
         return hipErrorInvalidValue;
+    if (c.self_first >= 0)
+        return knn_list_self_records_finish(c, rs);   // (knn_self_routed.hip)
     if (c.radii)
         return knn_list_each_records_finish(c, rs);   // (knn_each.hip)
     if (rs.nlists)

@@ -781,6 +781,186 @@ __global__ __launch_bounds__(GRID_BLOCK) void knn_grid_each_list_kernel(const fl
         *giveup = 1u;      // benign race: every writer stores 1
 }
 
+// ---- the radius graph on the grid (include/knn_mi355x.h 2k; knn_index_self_count_within_routed, knn_index_self_list_within_routed) --
+// The four walks above for the queries that are the shard's own rows: query qi is LOCAL row first + qi — Q = R + first * k, the rows
+// themselves —, and the row at position p is no hit when orig[p] == first + qi (identity by local row number: another copy of the
+// row stays a hit at distance 0).  The compare sits on the hit side, behind the distance; the walk, the stop clause, the give-up
+// word and what the commit sees are the twins'.  EACH: the wave's own radius radii[qi] under cap, as knn_grid_each_count_kernel;
+// else the scalar form, radii not read, cap the radius, as knn_grid_count_kernel.
+template <int KD, bool EACH>
+__global__ __launch_bounds__(GRID_BLOCK) void knn_grid_self_count_kernel(const float *__restrict__ Q, int m, GridGeom gg,
+                                                                         const unsigned *__restrict__ start,
+                                                                         const f4g *__restrict__ pts, const unsigned *__restrict__ orig,
+                                                                         unsigned first, unsigned *__restrict__ out, int rmax,
+                                                                         unsigned *__restrict__ giveup,
+                                                                         unsigned *__restrict__ giveup_next,
+                                                                         const float *__restrict__ radii, float cap)
+{
+#pragma clang fp contract(off)
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        *giveup_next = 0u;   // (the slot's other word, as the 1-NN kernel)
+    const int lane = threadIdx.x & 63;
+    const int qi = blockIdx.x * (GRID_BLOCK / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (qi >= m)
+        return;
+    float q[4] = {0.f, 0.f, 0.f, 0.f};
+    bool finite = true;
+#pragma unroll
+    for (int d = 0; d < KD; ++d) {
+        q[d] = Q[(size_t)qi * KD + d];
+        finite = finite && fabsf(q[d]) < INFINITY;
+    }
+    const float rad = EACH ? radii[qi] : cap;
+    if (!finite || (EACH && !knn_each_has(rad))) {   // no row can be a hit (and nothing to give up on)
+        if (lane == 0)
+            out[qi] = 0u;
+        return;
+    }
+    const float bound = EACH ? knn_each_bound(rad, cap) : cap;
+    const unsigned own = first + (unsigned)qi;
+    int c[4];
+    (void)grid_cell_of(gg, q, c);
+    int gmax = 1;
+#pragma unroll
+    for (int d = 0; d < KD; ++d)
+        gmax = gg.g[d] > gmax ? gg.g[d] : gmax;
+
+    unsigned cnt = 0u;
+    bool done = false;
+    bool first_ring = true;   // (rings 0 and 1 together, as the 1-NN kernel)
+    for (int r = gmax > 1 ? 1 : 0; r < gmax && r <= rmax; ++r) {
+        const int side = 2 * r + 1;
+        int total = 1;
+#pragma unroll
+        for (int d = 0; d < KD; ++d)
+            total *= side;
+        for (int idx = lane; idx < total; idx += KNN_WAVE) {
+            unsigned cell;
+            if (!grid_ring_cell<KD>(gg, c, r, side, idx, first_ring, &cell))
+                continue;
+            const unsigned p0 = start[cell], p1 = start[cell + 1];
+            for (unsigned p = p0; p < p1; ++p) {
+                const f4g x = pts[p];
+                float acc = 0.0f;
+#pragma unroll
+                for (int d = 0; d < KD; ++d) {
+                    const float diff = q[d] - x[d];   // v0: search - reference, squared, summed in order
+                    const float sq = diff * diff;
+                    acc = acc + sq;
+                }
+                if (acc < INFINITY && acc <= rad && acc <= cap)
+                    cnt += orig[p] != own ? 1u : 0u;
+            }
+        }
+        first_ring = false;
+        bool covers_all;
+        const double lb = grid_face_bound<KD>(gg, c, q, r, &covers_all);
+        if (covers_all) {
+            done = true;
+            break;
+        }
+        if (lb > 0.0 && (double)bound < lb * lb * (1.0 - 1e-6)) {   // no unseen row is within the query's bound
+            done = true;
+            break;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+        cnt += (unsigned)__shfl_xor((int)cnt, off, KNN_WAVE);
+    if (lane == 0) {
+        out[qi] = cnt;
+        if (!done && gmax > rmax + 1)
+            *giveup = 1u;      // benign race: every writer stores 1
+    }
+}
+
+template <int KD, bool EACH>
+__global__ __launch_bounds__(GRID_BLOCK) void knn_grid_self_list_kernel(const float *__restrict__ Q, int m, GridGeom gg,
+                                                                        const unsigned *__restrict__ start,
+                                                                        const f4g *__restrict__ pts, const unsigned *__restrict__ orig,
+                                                                        unsigned first, long long base, const u64 *__restrict__ offsets,
+                                                                        unsigned *__restrict__ cursor, u64 *__restrict__ keys, int rmax,
+                                                                        unsigned *__restrict__ giveup,
+                                                                        unsigned *__restrict__ giveup_next,
+                                                                        const float *__restrict__ radii, float cap)
+{
+#pragma clang fp contract(off)
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        *giveup_next = 0u;   // (the slot's other word, as the 1-NN kernel)
+    const int lane = threadIdx.x & 63;
+    const int qi = blockIdx.x * (GRID_BLOCK / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (qi >= m)
+        return;
+    float q[4] = {0.f, 0.f, 0.f, 0.f};
+    bool finite = true;
+#pragma unroll
+    for (int d = 0; d < KD; ++d) {
+        q[d] = Q[(size_t)qi * KD + d];
+        finite = finite && fabsf(q[d]) < INFINITY;
+    }
+    const float rad = EACH ? radii[qi] : cap;
+    if (!finite || (EACH && !knn_each_has(rad)))   // no row can be a hit: the cursor stays where it was (and nothing to give up on)
+        return;
+    const float bound = EACH ? knn_each_bound(rad, cap) : cap;
+    const unsigned own = first + (unsigned)qi;
+    int c[4];
+    (void)grid_cell_of(gg, q, c);
+    int gmax = 1;
+#pragma unroll
+    for (int d = 0; d < KD; ++d)
+        gmax = gg.g[d] > gmax ? gg.g[d] : gmax;
+    const u64 off = offsets[qi], end = offsets[qi + 1];
+    const u64 room64 = end > off ? end - off : 0ull;
+    const unsigned room = room64 < 0xFFFFFFFFull ? (unsigned)room64 : 0xFFFFFFFFu;   // (the cursor is 32-bit)
+
+    bool done = false;
+    bool first_ring = true;   // (rings 0 and 1 together, as the 1-NN kernel)
+    for (int r = gmax > 1 ? 1 : 0; r < gmax && r <= rmax; ++r) {
+        const int side = 2 * r + 1;
+        int total = 1;
+#pragma unroll
+        for (int d = 0; d < KD; ++d)
+            total *= side;
+        for (int idx = lane; idx < total; idx += KNN_WAVE) {
+            unsigned cell;
+            if (!grid_ring_cell<KD>(gg, c, r, side, idx, first_ring, &cell))
+                continue;
+            const unsigned p0 = start[cell], p1 = start[cell + 1];
+            for (unsigned p = p0; p < p1; ++p) {
+                const f4g x = pts[p];
+                float acc = 0.0f;
+#pragma unroll
+                for (int d = 0; d < KD; ++d) {
+                    const float diff = q[d] - x[d];   // v0: search - reference, squared, summed in order
+                    const float sq = diff * diff;
+                    acc = acc + sq;
+                }
+                if (acc < INFINITY && acc <= rad && acc <= cap) {
+                    const unsigned row = orig[p];
+                    if (row != own) {
+                        const unsigned place = atomicAdd(&cursor[qi], 1u);
+                        if (place < room)
+                            keys[off + place] = ((u64)__float_as_uint(acc) << 32) | (u64)(unsigned)(base + (long long)row);
+                    }
+                }
+            }
+        }
+        first_ring = false;
+        bool covers_all;
+        const double lb = grid_face_bound<KD>(gg, c, q, r, &covers_all);
+        if (covers_all) {
+            done = true;
+            break;
+        }
+        if (lb > 0.0 && (double)bound < lb * lb * (1.0 - 1e-6)) {   // no unseen row is within the query's bound
+            done = true;
+            break;
+        }
+    }
+    if (lane == 0 && !done && gmax > rmax + 1)
+        *giveup = 1u;      // benign race: every writer stores 1
+}
+
 // ---- host -------------------------------------------------------------------------------------------
 #define GTRY(call)                     \
     do {                                 \
@@ -1071,7 +1251,13 @@ hipError_t knn_grid_query_count(const GridState *gs, int rmax, int slot, const C
     if (c.ev0)
         GTRY(hipEventRecord(c.ev0, s));
 #define GRID_COUNT(KDV)                                                                                                              \
-    if (c.radii)   /* a radius per query; c.max_dist2 is the cap */                                                                  \
+    if (c.self_first >= 0 && c.radii)   /* the shard's own rows (2k): the self forms */                                              \
+        hipLaunchKernelGGL((knn_grid_self_count_kernel<KDV, true>), grid, block, 0, s, c.q, c.m, gs->geom, gs->start, gs->pts, gs->orig, \
+                           (unsigned)c.self_first, c.scratch, rmax, giveup, giveup_next, c.radii, c.max_dist2);                      \
+    else if (c.self_first >= 0)                                                                                                      \
+        hipLaunchKernelGGL((knn_grid_self_count_kernel<KDV, false>), grid, block, 0, s, c.q, c.m, gs->geom, gs->start, gs->pts, gs->orig, \
+                           (unsigned)c.self_first, c.scratch, rmax, giveup, giveup_next, (const float *)nullptr, c.max_dist2);       \
+    else if (c.radii)   /* a radius per query; c.max_dist2 is the cap */                                                             \
         hipLaunchKernelGGL(knn_grid_each_count_kernel<KDV>, grid, block, 0, s, c.q, c.m, gs->geom, gs->start, gs->pts, c.scratch, rmax, \
                            giveup, giveup_next, c.radii, c.max_dist2);                                                               \
     else                                                                                                                             \
@@ -1089,7 +1275,7 @@ hipError_t knn_grid_query_count(const GridState *gs, int rmax, int slot, const C
         GTRY(hipEventRecord(c.ev1, s));
     *gate_out = giveup;
     GTRY(knn_count_commit_launch(c.m, c.scratch, c.counts, giveup, s));
-    return knn_exact_count_launch(c, giveup);
+    return knn_gated_count_launch(c, giveup);   // (a routed self call: the gated self-scan)
 }
 
 // The whole list call on the grid way (KNN_QUERY_COUNT_GRID), asynchronous on c.stream: c.scratch [m] <- c.fill, the grid kernel
@@ -1111,7 +1297,15 @@ hipError_t knn_grid_query_list(const GridState *gs, int rmax, int slot, const Li
     if (c.ev0)
         GTRY(hipEventRecord(c.ev0, s));
 #define GRID_LIST(KDV)                                                                                                                \
-    if (c.radii)   /* a radius per query; c.max_dist2 is the cap */                                                                   \
+    if (c.self_first >= 0 && c.radii)   /* the shard's own rows (2k): the self forms */                                               \
+        hipLaunchKernelGGL((knn_grid_self_list_kernel<KDV, true>), grid, block, 0, s, c.q, c.m, gs->geom, gs->start, gs->pts, gs->orig, \
+                           (unsigned)c.self_first, c.base, c.offsets, c.scratch, c.keys, rmax, giveup, giveup_next, c.radii,          \
+                           c.max_dist2);                                                                                              \
+    else if (c.self_first >= 0)                                                                                                       \
+        hipLaunchKernelGGL((knn_grid_self_list_kernel<KDV, false>), grid, block, 0, s, c.q, c.m, gs->geom, gs->start, gs->pts, gs->orig, \
+                           (unsigned)c.self_first, c.base, c.offsets, c.scratch, c.keys, rmax, giveup, giveup_next,                   \
+                           (const float *)nullptr, c.max_dist2);                                                                      \
+    else if (c.radii)   /* a radius per query; c.max_dist2 is the cap */                                                              \
         hipLaunchKernelGGL(knn_grid_each_list_kernel<KDV>, grid, block, 0, s, c.q, c.m, gs->geom, gs->start, gs->pts, gs->orig, c.base, \
                            c.offsets, c.scratch, c.keys, rmax, giveup, giveup_next, c.radii, c.max_dist2);                            \
     else                                                                                                                              \
@@ -1129,7 +1323,7 @@ hipError_t knn_grid_query_list(const GridState *gs, int rmax, int slot, const Li
         GTRY(hipEventRecord(c.ev1, s));
     *gate_out = giveup;
     GTRY(knn_list_commit_launch(c.m, c.scratch, c.fill, giveup, s));
-    return knn_exact_list_launch(c, giveup);
+    return knn_gated_list_launch(c, giveup);   // (a routed self call: the gated self-scan)
 }
 
 long long knn_grid_radius_rings(const GridState *gs, float max_dist2)

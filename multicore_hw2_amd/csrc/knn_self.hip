@@ -14,6 +14,9 @@
 //
 // knn_self_drop_kernel finishes the top-K's through way (knn_api.cpp): the plain call's K + 1 nearest, self among the candidates,
 // become the K nearest others.
+//
+// knn_self_count_gated_kernel and knn_self_list_gated_kernel are the count and list scans behind a device gate: the exact answer of
+// the routed self calls (include/knn_mi355x.h 2k) when the grid gave up or a cell-pruned pass fell back.
 #include "knn_masked_dev.h"
 #include "knn_self_window.h"
 
@@ -293,6 +296,78 @@ __global__ __launch_bounds__(KNN_WAVE) void knn_self_list_each_kernel(const floa
     });
 }
 
+// The gated twins (include/knn_mi355x.h 2k; DESIGN §4.6 "The radius graph on the pruned ways"): the exact answer behind the grid
+// way and behind a cell-pruned pass of a routed self call.  They do nothing unless *gate != 0 — the grid's give-up word, a pass's
+// FALLBACK word —, as the gated exact count and list do behind the plain calls.  The bodies are knn_self_count_each_kernel's and
+// knn_self_list_each_kernel's, copied: a body shared with those two changed the code the compiler makes of them (tools/isa_same.py),
+// and they are to stay as measured.  One difference: radii may be null — the scalar form, every lane's radius the cap.
+template <int KC>
+__global__ __launch_bounds__(KNN_WAVE) void knn_self_count_gated_kernel(const float *__restrict__ R, int k, long long first, int m,
+                                                                       long long n, long long rows_per_slice,
+                                                                       const float *__restrict__ radii, float cap,
+                                                                       unsigned *__restrict__ counts,
+                                                                       const unsigned *__restrict__ gate)
+{
+#pragma clang fp contract(off)
+    if (*gate == 0u)
+        return;
+    constexpr int KM = KC > 0 ? 16 * KC : 1;
+    const int lane = threadIdx.x;
+    const int q = blockIdx.y * KNN_WAVE + lane;
+    const int qa = min(q, m - 1);
+    const float *__restrict__ qp = R + (size_t)(first + qa) * k;
+    float qv[KM];
+#pragma unroll
+    for (int d = 0; d < KM; ++d)
+        qv[d] = KC > 0 && d < k ? qp[d] : 0.0f;
+    const float rad = radii ? radii[qa] : cap;
+    unsigned cnt = 0u;
+    const unsigned own = (unsigned)(first + q);
+    const long long i0 = (long long)blockIdx.x * rows_per_slice;
+    const long long i1 = min(n, i0 + rows_per_slice);
+    const long long w0 = first + (long long)blockIdx.y * KNN_WAVE;
+    const long long w1 = min(w0 + KNN_WAVE, first + m);
+    self_scan<KC>(qv, qp, R, k, i0, i1, w0, w1, own, [&](float acc, unsigned) {
+        cnt += acc < INFINITY && acc <= rad && acc <= cap ? 1u : 0u;   // (NaN — the distance or the radius — fails)
+    });
+    if (q < m && cnt != 0u)
+        atomicAdd(&counts[q], cnt);
+}
+
+template <int KC>
+__global__ __launch_bounds__(KNN_WAVE) void knn_self_list_gated_kernel(const float *__restrict__ R, int k, long long first, int m,
+                                                                      long long n, long long rows_per_slice,
+                                                                      const float *__restrict__ radii, float cap, long long base,
+                                                                      const unsigned *__restrict__ gids,
+                                                                      const u64 *__restrict__ offsets, unsigned *__restrict__ fill,
+                                                                      u64 *__restrict__ keys, const unsigned *__restrict__ gate)
+{
+#pragma clang fp contract(off)
+    if (*gate == 0u)
+        return;
+    constexpr int KM = KC > 0 ? 16 * KC : 1;
+    const int lane = threadIdx.x;
+    const int q = blockIdx.y * KNN_WAVE + lane;
+    const int qa = min(q, m - 1);
+    const float *__restrict__ qp = R + (size_t)(first + qa) * k;
+    float qv[KM];
+#pragma unroll
+    for (int d = 0; d < KM; ++d)
+        qv[d] = KC > 0 && d < k ? qp[d] : 0.0f;
+    const float rad = radii ? radii[qa] : cap;
+    u64 off;
+    const unsigned room = list_room(offsets, (unsigned)qa, off);
+    const unsigned own = (unsigned)(first + q);
+    const long long i0 = (long long)blockIdx.x * rows_per_slice;
+    const long long i1 = min(n, i0 + rows_per_slice);
+    const long long w0 = first + (long long)blockIdx.y * KNN_WAVE;
+    const long long w1 = min(w0 + KNN_WAVE, first + m);
+    self_scan_one<KC>(qv, qp, R, k, i0, i1, w0, w1, own, [&](float acc, unsigned row, bool other) {
+        if (other && q < m && acc < INFINITY && acc <= rad && acc <= cap)   // (NaN — the distance or the radius — fails)
+            list_put(&fill[q], keys, off, room, pack_key(acc, gids ? gids[row] : (unsigned)(base + (long long)row)));
+    });
+}
+
 // knn_self_drop_kernel — one wave (block) per query: lists[q][0 .. K] is the plain call's sorted top-(K + 1) for the query that is
 // local row first + q, self among the candidates.  The entry that is a real key (high word below +INF's bits) and carries the
 // query's own global number goes; when there is none — more than K other rows at or before self's place, or a self-distance that is
@@ -389,13 +464,13 @@ hipError_t knn_self_topk_launch(const TopkCall &c, long long row_first)
     return hipSuccess;
 }
 
-hipError_t knn_self_count_launch(const CountCall &c, long long row_first)
+hipError_t knn_self_count_launch(const CountCall &c, long long row_first, const unsigned *gate)
 {
     hipStream_t s = c.stream;
     if (c.m <= 0 || row_first < 0 || row_first + c.m > c.n)
         return hipErrorInvalidValue;
     hipError_t e;
-    if (c.ev0 && (e = hipEventRecord(c.ev0, s)) != hipSuccess)
+    if (!gate && c.ev0 && (e = hipEventRecord(c.ev0, s)) != hipSuccess)   // (a gated scan is not its way's dominant kernel)
         return e;
     for (int c0 = 0; c0 < c.m; c0 += KNN_TOPK_CHUNK) {
         const int mc = c.m - c0 < KNN_TOPK_CHUNK ? c.m - c0 : KNN_TOPK_CHUNK;
@@ -405,7 +480,10 @@ hipError_t knn_self_count_launch(const CountCall &c, long long row_first)
             return hipErrorInvalidValue;
         const dim3 grid((unsigned)slices, (unsigned)knn_divup(mc, KNN_WAVE)), block(KNN_WAVE);
 #define KNN_SELF_COUNT(KCV)                                                                                                          \
-    if (c.radii)   /* a radius per query: the radii advance with the chunk */                                                        \
+    if (gate)      /* the gated twin: scalar form and radii alike */                                                                 \
+        hipLaunchKernelGGL(knn_self_count_gated_kernel<KCV>, grid, block, 0, s, c.r, c.k, row_first + c0, mc, c.n, per,               \
+                           c.radii ? c.radii + c0 : nullptr, c.max_dist2, c.counts + c0, gate);                                      \
+    else if (c.radii)   /* a radius per query: the radii advance with the chunk */                                                   \
         hipLaunchKernelGGL(knn_self_count_each_kernel<KCV>, grid, block, 0, s, c.r, c.k, row_first + c0, mc, c.n, per, c.radii + c0,  \
                            c.max_dist2, c.counts + c0);                                                                              \
     else                                                                                                                             \
@@ -416,18 +494,18 @@ hipError_t knn_self_count_launch(const CountCall &c, long long row_first)
         if (e != hipSuccess)
             return e;
     }
-    if (c.ev1 && (e = hipEventRecord(c.ev1, s)) != hipSuccess)
+    if (!gate && c.ev1 && (e = hipEventRecord(c.ev1, s)) != hipSuccess)
         return e;
     return hipSuccess;
 }
 
-hipError_t knn_self_list_launch(const ListCall &c, long long row_first)
+hipError_t knn_self_list_launch(const ListCall &c, long long row_first, const unsigned *gate)
 {
     hipStream_t s = c.stream;
     if (c.m <= 0 || row_first < 0 || row_first + c.m > c.n)
         return hipErrorInvalidValue;
     hipError_t e;
-    if (c.ev0 && (e = hipEventRecord(c.ev0, s)) != hipSuccess)
+    if (!gate && c.ev0 && (e = hipEventRecord(c.ev0, s)) != hipSuccess)   // (a gated scan is not its way's dominant kernel)
         return e;
     for (int c0 = 0; c0 < c.m; c0 += KNN_TOPK_CHUNK) {
         const int mc = c.m - c0 < KNN_TOPK_CHUNK ? c.m - c0 : KNN_TOPK_CHUNK;
@@ -437,7 +515,10 @@ hipError_t knn_self_list_launch(const ListCall &c, long long row_first)
             return hipErrorInvalidValue;
         const dim3 grid((unsigned)slices, (unsigned)knn_divup(mc, KNN_WAVE)), block(KNN_WAVE);
 #define KNN_SELF_LIST(KCV)                                                                                                              \
-    if (c.radii)   /* a radius per query: the radii advance with the chunk */                                                           \
+    if (gate)      /* the gated twin: scalar form and radii alike */                                                                    \
+        hipLaunchKernelGGL(knn_self_list_gated_kernel<KCV>, grid, block, 0, s, c.r, c.k, row_first + c0, mc, c.n, per,                   \
+                           c.radii ? c.radii + c0 : nullptr, c.max_dist2, c.base, c.gids, c.offsets + c0, c.fill + c0, c.keys, gate);   \
+    else if (c.radii)   /* a radius per query: the radii advance with the chunk */                                                      \
         hipLaunchKernelGGL(knn_self_list_each_kernel<KCV>, grid, block, 0, s, c.r, c.k, row_first + c0, mc, c.n, per, c.radii + c0,      \
                            c.max_dist2, c.base, c.gids, c.offsets + c0, c.fill + c0, c.keys);                                           \
     else                                                                                                                                \
@@ -449,7 +530,7 @@ hipError_t knn_self_list_launch(const ListCall &c, long long row_first)
         if (e != hipSuccess)
             return e;
     }
-    if (c.ev1 && (e = hipEventRecord(c.ev1, s)) != hipSuccess)
+    if (!gate && c.ev1 && (e = hipEventRecord(c.ev1, s)) != hipSuccess)
         return e;
     return hipSuccess;
 }
