@@ -1069,6 +1069,34 @@ int slot_buffer_grow(u64 *&buf, size_t &bytes, size_t need)
             return rc_;         \
     } while (0)
 
+// The global numbers of a cell-range shard's rows, which its keys carry (gids); null: an index-range shard's keys carry base + row.
+const unsigned *shard_gids(const knn_index *idx)
+{
+    return idx->sharded && idx->filter.cells ? idx->filter.cells->gids : nullptr;
+}
+
+// What every index call that consults no layout, or none yet, leaves for knn_index_last_stats: way 1, nothing counted.
+void begin_call(knn_index *idx, int slot)
+{
+    idx->stats[0] = 1;
+    idx->stats[1] = 0;
+    idx->stats[2] = 0;
+    idx->stats[3] = 0;
+    idx->grid_topk_gate = nullptr;
+    idx->last_slot = slot;
+}
+
+// call.ev0 / ev1 = the pair that brackets the call's dominant kernel, null when the call is not a timed one.
+template <class Call>
+int take_events(knn_index *idx, Call &call)
+{
+    EventPair *ev = nullptr;
+    KNN_TRY(next_event_pair(idx, false, &ev));
+    call.ev0 = ev ? ev->first : nullptr;
+    call.ev1 = ev ? ev->second : nullptr;
+    return KNN_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1193,8 +1221,7 @@ int query_topk(knn_index *idx, int slot, TopkCall call, int *indices_dev, unsign
     call.k = idx->k;
     call.n = idx->n;
     call.base = idx->base;
-    // a cell-range shard's keys carry its rows' global numbers (gids); an index-range shard's base + row
-    call.gids = idx->sharded && idx->filter.cells ? idx->filter.cells->gids : nullptr;
+    call.gids = shard_gids(idx);
     call.r = idx->refs;
     call.num_cu = idx->num_cu;
     call.ev0 = ev ? ev->first : nullptr;
@@ -1287,6 +1314,166 @@ CountPlan count_plan_of(const knn_index *idx, const QueryRouteInputs &ri, int m,
     return knn_count_route(ci);
 }
 
+// ---- the radius family (include/knn_mi355x.h 2e .. 2k): one description, one argument ladder, one call front ---------------------
+// What an entry of the family is, and what its caller states.  m: the queries, or the rows of a self call (queries null: they are
+// the shard's rows from row_first).  max_dist2: the radius, or the cap over `radii` (nullable, device [m]).
+enum : unsigned {
+    kCap = 1u,      // the entry's texts speak of a cap, not of max_dist2 (the each and routed forms)
+    kRouted = 2u,   // admits KNN_QUERY_COUNT_GRID / _CELLS and takes the way knn_count_route names; else way 1 on every index
+    kSelf = 4u,     // about the shard's own rows: rows and row_first in m's place, a query's own row no candidate
+};
+struct WithinCall {
+    const char *who;
+    unsigned form;
+    int slot, m;
+    const float *queries;
+    long long row_first;
+    const float *radii;
+    float max_dist2;
+    void *stream;
+    unsigned flags;
+};
+struct NullRule {
+    bool broken;
+    const char *what;
+};
+const char *const kNullLists = "null offsets, fill or keys";
+
+// The family's argument rules, one message per rule in one order — radius or cap, flags, slot, m or rows (+ row_first), the entry's
+// pointer groups, the index last —: the *_logic.py tests tell them apart without a GPU.
+int within_check(const WithinCall &w, std::initializer_list<NullRule> pointers, const knn_index *idx)
+{
+    const bool routed = (w.form & kRouted) != 0u, self = (w.form & kSelf) != 0u;
+    if (!(w.max_dist2 >= 0.0f))
+        return fail_in(KNN_EINVAL, w.who, (w.form & kCap) ? "cap must be >= 0 (or +INF) and not NaN" : "max_dist2 must be >= 0 and not NaN");
+    if ((w.flags & ~(routed ? KNN_QUERY_INIT_KEYS | KNN_QUERY_COUNT_GRID | KNN_QUERY_COUNT_CELLS : (unsigned)KNN_QUERY_INIT_KEYS)) != 0u)
+        return fail_in(KNN_EINVAL, w.who, routed ? "unknown flag (KNN_QUERY_INIT_KEYS, KNN_QUERY_COUNT_GRID, KNN_QUERY_COUNT_CELLS)"
+                                                 : "unknown flag (KNN_QUERY_INIT_KEYS alone is admitted)");
+    if (w.slot < 0 || w.slot >= KNN_SLOTS)
+        return fail_in(KNN_EINVAL, w.who, "slot outside 0 .. 7");
+    if (w.m < 1)
+        return fail_in(KNN_EINVAL, w.who, self ? "rows < 1" : "m < 1");
+    if (self && w.row_first < 0)
+        return fail_in(KNN_EINVAL, w.who, "row_first < 0");
+    for (const NullRule &p : pointers)
+        if (p.broken)
+            return fail_in(KNN_EINVAL, w.who, p.what);
+    if (!idx)
+        return fail_in(KNN_EINVAL, w.who, "null index");
+    return KNN_OK;
+}
+
+// Where a call's hits go: the two call structs as their entries start them.
+CountCall counts_into(unsigned *counts_dev)
+{
+    CountCall c;
+    c.counts = counts_dev;
+    return c;
+}
+ListCall lists_into(const unsigned long long *offsets_dev, unsigned *fill_dev, unsigned long long *keys_dev)
+{
+    ListCall c;
+    c.offsets = (const u64 *)offsets_dev;
+    c.fill = fill_dev;
+    c.keys = (u64 *)keys_dev;
+    return c;
+}
+// What the two differ in on the host: the array every way adds to, the number a key carries, and the launchers' names.
+unsigned *added_to(const CountCall &c) { return c.counts; }
+unsigned *added_to(const ListCall &c) { return c.fill; }
+void key_numbers(const knn_index *, CountCall &) {}
+void key_numbers(const knn_index *idx, ListCall &c)
+{
+    c.base = idx->base;
+    c.gids = shard_gids(idx);
+}
+hipError_t grid_within(const GridState *gs, int rmax, int slot, const CountCall &c, const unsigned **gate) { return knn_grid_query_count(gs, rmax, slot, c, gate); }
+hipError_t grid_within(const GridState *gs, int rmax, int slot, const ListCall &c, const unsigned **gate) { return knn_grid_query_list(gs, rmax, slot, c, gate); }
+hipError_t cells_within(FilterState &st, const CellTopkPlan &tp, int slot, const CountCall &c) { return knn_filter_query_count_cells(st, tp, slot, c); }
+hipError_t cells_within(FilterState &st, const CellTopkPlan &tp, int slot, const ListCall &c) { return knn_filter_query_list_cells(st, tp, slot, c); }
+hipError_t exact_within(const CountCall &c) { return knn_exact_count_launch(c, nullptr); }
+hipError_t exact_within(const ListCall &c) { return knn_exact_list_launch(c, nullptr); }
+hipError_t self_within(const CountCall &c, long long row_first) { return knn_self_count_launch(c, row_first); }
+hipError_t self_within(const ListCall &c, long long row_first) { return knn_self_list_launch(c, row_first); }
+
+// Behind the lock and the device, every call of the family: the fields both call structs share (q: the queries as the launches
+// take them), way 1 in the statistics, and — every way ADDS to the caller's counts or fill — an init call's zeroes.
+template <class Call>
+int within_begin(knn_index *idx, const WithinCall &w, const float *q, Call &call)
+{
+    call.k = idx->k;
+    call.m = w.m;
+    call.n = idx->n;
+    call.q = q;
+    call.r = idx->refs;
+    call.radii = w.radii;
+    call.max_dist2 = w.max_dist2 == 0.0f ? 0.0f : w.max_dist2;   // (-0 counts as 0)
+    call.num_cu = idx->num_cu;
+    call.stream = (hipStream_t)w.stream;
+    key_numbers(idx, call);
+    begin_call(idx, w.slot);
+    if ((w.flags & KNN_QUERY_INIT_KEYS) != 0u)
+        HIP_TRY(hipMemsetAsync(added_to(call), 0, (size_t)w.m * sizeof(unsigned), call.stream));
+    return KNN_OK;
+}
+
+// A count or list call behind within_check, on the way knn_count_route names for m queries at max_dist2 (the cap of a call with
+// radii: the kernels are then the each-forms) under the call's flags and the options.  A self call's queries are the resident rows:
+// nothing is uploaded.  Routed (2k), call.self_first tells the grid and cell ways to drop a query's own row and to gate the
+// self-scan behind them, and way 1 is the exact self-scan in the exact scan's place; not routed (2i, 2j), no layout is consulted
+// and the self-scan — which reads neither call.q nor call.scratch — is launched as it always was.
+template <class Call>
+int within_run(knn_index *idx, const WithinCall &w, Call call)
+{
+    const bool routed = (w.form & kRouted) != 0u, self = (w.form & kSelf) != 0u;
+    std::lock_guard<std::recursive_mutex> lock(idx->mu);
+    if (self && (w.row_first > idx->n || (long long)w.m > idx->n - w.row_first))
+        return fail_in(KNN_EINVAL, w.who, "row_first + rows above the shard's rows");
+    DeviceGuard guard(idx->device);
+    if (!guard.ok)
+        return fail_in(KNN_EHIP, w.who, "hipSetDevice failed");
+    KNN_TRY(within_begin(idx, w, !self ? w.queries : routed ? idx->refs + (size_t)w.row_first * (size_t)idx->k : nullptr, call));
+    if (idx->n == 0)   // an empty shard adds nothing (a self call's range check has failed by here)
+        return KNN_OK;
+    QueryRouteInputs ri;
+    CountPlan plan;   // (way 1)
+    if (routed) {
+        call.self_first = self ? w.row_first : -1;
+        ri = route_inputs(idx, w.m, 1, 0u);
+        plan = count_plan_of(idx, ri, w.m, call.max_dist2, w.flags);
+        idx->stats[0] = (long long)plan.way;
+        // the slot's count scratch — a list's scratch cursor — of the grid and cell ways, grown before the first launch
+        knn_index::TopkSlot &ts = idx->topk[w.slot];
+        KNN_TRY(slot_buffer_grow(ts.count, ts.count_bytes, plan.scratch_bytes));
+        call.scratch = (unsigned *)ts.count;
+    }
+    KNN_TRY(take_events(idx, call));
+    switch (plan.way) {
+    case QueryWay::Grid:
+        HIP_TRY(grid_within(idx->grid, plan.rmax, w.slot, call, &idx->grid_topk_gate));
+        break;
+    case QueryWay::Cells: {
+        const CellTopkPlan tp = knn_cells_count_plan(ri.t);
+        if (!tp.use)
+            return fail_in(KNN_EHIP, w.who, "the cell-pruned scan has no pass shape for this layout");
+        HIP_TRY(cells_within(idx->filter, tp, w.slot, call));
+        break;
+    }
+    default:
+        if (self) {   // (ungated, the self-scan records the call's events itself)
+            HIP_TRY(self_within(call, w.row_first));
+            break;
+        }
+        if (call.ev0)
+            HIP_TRY(hipEventRecord(call.ev0, call.stream));
+        HIP_TRY(exact_within(call));
+        if (call.ev1)
+            HIP_TRY(hipEventRecord(call.ev1, call.stream));
+        break;
+    }
+    return KNN_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1320,89 +1507,12 @@ int knn_keys_topk_merge(int device, int m, int K, const unsigned long long *a_de
     return KNN_OK;
 }
 
-// A count call behind its argument checks: knn_index_count_within (radii_dev null, max_dist2 the radius) and
-// knn_index_count_within_each (radii_dev the radii, max_dist2 the cap — the way is chosen at the cap, the kernels are the each-forms).
-static int count_within_run(knn_index *idx, const char *who, int slot, int m, const float *queries_dev, const float *radii_dev,
-                            float max_dist2, unsigned *counts_dev, void *stream, unsigned flags)
-{
-    std::lock_guard<std::recursive_mutex> lock(idx->mu);
-    DeviceGuard guard(idx->device);
-    if (!guard.ok)
-        return fail_in(KNN_EHIP, who, "hipSetDevice failed");
-    CountCall call;
-    call.k = idx->k;
-    call.m = m;
-    call.n = idx->n;
-    call.q = queries_dev;
-    call.r = idx->refs;
-    call.counts = counts_dev;
-    call.radii = radii_dev;
-    call.max_dist2 = max_dist2 == 0.0f ? 0.0f : max_dist2;   // (-0 counts as 0)
-    call.num_cu = idx->num_cu;
-    call.stream = (hipStream_t)stream;
-    hipStream_t s = call.stream;
-    idx->stats[0] = 1;
-    idx->stats[1] = 0;
-    idx->stats[2] = 0;
-    idx->stats[3] = 0;
-    idx->grid_topk_gate = nullptr;
-    idx->last_slot = slot;
-    // every way ADDS to the caller's counts: an init call zeroes them first
-    if ((flags & KNN_QUERY_INIT_KEYS) != 0u)
-        HIP_TRY(hipMemsetAsync(counts_dev, 0, (size_t)m * sizeof(unsigned), s));
-    if (idx->n == 0)   // an empty shard adds nothing
-        return KNN_OK;
-    const QueryRouteInputs ri = route_inputs(idx, m, 1, 0u);
-    const CountPlan plan = count_plan_of(idx, ri, m, call.max_dist2, flags);
-    idx->stats[0] = (long long)plan.way;
-    // the slot's count scratch, grown before the first launch
-    knn_index::TopkSlot &ts = idx->topk[slot];
-    KNN_TRY(slot_buffer_grow(ts.count, ts.count_bytes, plan.scratch_bytes));
-    call.scratch = (unsigned *)ts.count;
-    EventPair *ev = nullptr;
-    KNN_TRY(next_event_pair(idx, false, &ev));
-    call.ev0 = ev ? ev->first : nullptr;
-    call.ev1 = ev ? ev->second : nullptr;
-    switch (plan.way) {
-    case QueryWay::Grid:
-        HIP_TRY(knn_grid_query_count(idx->grid, plan.rmax, slot, call, &idx->grid_topk_gate));
-        break;
-    case QueryWay::Cells: {
-        const CellTopkPlan tp = knn_cells_count_plan(ri.t);
-        if (!tp.use)
-            return fail_in(KNN_EHIP, who, "the cell-pruned scan has no pass shape for this layout");
-        HIP_TRY(knn_filter_query_count_cells(idx->filter, tp, slot, call));
-        break;
-    }
-    default:
-        if (ev)
-            HIP_TRY(hipEventRecord(call.ev0, s));
-        HIP_TRY(knn_exact_count_launch(call, nullptr));
-        if (ev)
-            HIP_TRY(hipEventRecord(call.ev1, s));
-        break;
-    }
-    return KNN_OK;
-}
-
 int knn_index_count_within(knn_index *idx, int slot, int m, const float *queries_dev, float max_dist2, unsigned *counts_dev,
                            void *stream, unsigned flags)
 {
-    // (one message per rule, the index last: tests/test_count_logic.py tells them apart without a GPU)
-    if (!(max_dist2 >= 0.0f))
-        return fail(KNN_EINVAL, "knn_index_count_within: max_dist2 must be >= 0 and not NaN");
-    constexpr unsigned kCountFlags = KNN_QUERY_INIT_KEYS | KNN_QUERY_COUNT_GRID | KNN_QUERY_COUNT_CELLS;   // the three it admits
-    if ((flags & ~kCountFlags) != 0u)
-        return fail(KNN_EINVAL, "knn_index_count_within: unknown flag (KNN_QUERY_INIT_KEYS, KNN_QUERY_COUNT_GRID, KNN_QUERY_COUNT_CELLS)");
-    if (slot < 0 || slot >= KNN_SLOTS)
-        return fail(KNN_EINVAL, "knn_index_count_within: slot outside 0 .. 7");
-    if (m < 1)
-        return fail(KNN_EINVAL, "knn_index_count_within: m < 1");
-    if (!queries_dev || !counts_dev)
-        return fail(KNN_EINVAL, "knn_index_count_within: null queries or counts");
-    if (!idx)
-        return fail(KNN_EINVAL, "knn_index_count_within: null index");
-    return count_within_run(idx, "knn_index_count_within", slot, m, queries_dev, nullptr, max_dist2, counts_dev, stream, flags);
+    const WithinCall w = {"knn_index_count_within", kRouted, slot, m, queries_dev, 0, nullptr, max_dist2, stream, flags};
+    KNN_TRY(within_check(w, {{!queries_dev || !counts_dev, "null queries or counts"}}, idx));
+    return within_run(idx, w, counts_into(counts_dev));
 }
 
 int knn_debug_count_plan(const long long in[16], long long out[8])
@@ -1465,96 +1575,13 @@ int knn_keys_sort_segments(int device, int m, const unsigned long long *offsets_
     return KNN_OK;
 }
 
-// A list call behind its argument checks: knn_index_list_within and knn_index_list_within_each, as count_within_run.
-static int list_within_run(knn_index *idx, const char *who, int slot, int m, const float *queries_dev, const float *radii_dev,
-                           float max_dist2, const unsigned long long *offsets_dev, unsigned *fill_dev, unsigned long long *keys_dev,
-                           void *stream, unsigned flags)
-{
-    std::lock_guard<std::recursive_mutex> lock(idx->mu);
-    DeviceGuard guard(idx->device);
-    if (!guard.ok)
-        return fail_in(KNN_EHIP, who, "hipSetDevice failed");
-    ListCall call;
-    call.k = idx->k;
-    call.m = m;
-    call.n = idx->n;
-    call.base = idx->base;
-    // a cell-range shard's keys carry its rows' global numbers (gids); an index-range shard's base + row
-    call.gids = idx->sharded && idx->filter.cells ? idx->filter.cells->gids : nullptr;
-    call.q = queries_dev;
-    call.r = idx->refs;
-    call.offsets = (const u64 *)offsets_dev;
-    call.fill = fill_dev;
-    call.keys = (u64 *)keys_dev;
-    call.radii = radii_dev;
-    call.max_dist2 = max_dist2 == 0.0f ? 0.0f : max_dist2;   // (-0 counts as 0)
-    call.num_cu = idx->num_cu;
-    call.stream = (hipStream_t)stream;
-    hipStream_t s = call.stream;
-    idx->stats[0] = 1;
-    idx->stats[1] = 0;
-    idx->stats[2] = 0;
-    idx->stats[3] = 0;
-    idx->grid_topk_gate = nullptr;
-    idx->last_slot = slot;
-    // every way APPENDS behind the caller's fill: an init call zeroes it first
-    if ((flags & KNN_QUERY_INIT_KEYS) != 0u)
-        HIP_TRY(hipMemsetAsync(fill_dev, 0, (size_t)m * sizeof(unsigned), s));
-    if (idx->n == 0)   // an empty shard appends nothing
-        return KNN_OK;
-    const QueryRouteInputs ri = route_inputs(idx, m, 1, 0u);
-    const CountPlan plan = count_plan_of(idx, ri, m, call.max_dist2, flags);
-    idx->stats[0] = (long long)plan.way;
-    // the slot's count scratch — the scratch cursor of the grid and cell ways —, grown before the first launch
-    knn_index::TopkSlot &ts = idx->topk[slot];
-    KNN_TRY(slot_buffer_grow(ts.count, ts.count_bytes, plan.scratch_bytes));
-    call.scratch = (unsigned *)ts.count;
-    EventPair *ev = nullptr;
-    KNN_TRY(next_event_pair(idx, false, &ev));
-    call.ev0 = ev ? ev->first : nullptr;
-    call.ev1 = ev ? ev->second : nullptr;
-    switch (plan.way) {
-    case QueryWay::Grid:
-        HIP_TRY(knn_grid_query_list(idx->grid, plan.rmax, slot, call, &idx->grid_topk_gate));
-        break;
-    case QueryWay::Cells: {
-        const CellTopkPlan tp = knn_cells_count_plan(ri.t);
-        if (!tp.use)
-            return fail_in(KNN_EHIP, who, "the cell-pruned scan has no pass shape for this layout");
-        HIP_TRY(knn_filter_query_list_cells(idx->filter, tp, slot, call));
-        break;
-    }
-    default:
-        if (ev)
-            HIP_TRY(hipEventRecord(call.ev0, s));
-        HIP_TRY(knn_exact_list_launch(call, nullptr));
-        if (ev)
-            HIP_TRY(hipEventRecord(call.ev1, s));
-        break;
-    }
-    return KNN_OK;
-}
-
 int knn_index_list_within(knn_index *idx, int slot, int m, const float *queries_dev, float max_dist2,
                           const unsigned long long *offsets_dev, unsigned *fill_dev, unsigned long long *keys_dev, void *stream,
                           unsigned flags)
 {
-    // (one message per rule, the index last, as knn_index_count_within: tests/test_list_logic.py tells them apart without a GPU)
-    if (!(max_dist2 >= 0.0f))
-        return fail(KNN_EINVAL, "knn_index_list_within: max_dist2 must be >= 0 and not NaN");
-    constexpr unsigned kListFlags = KNN_QUERY_INIT_KEYS | KNN_QUERY_COUNT_GRID | KNN_QUERY_COUNT_CELLS;   // the three it admits
-    if ((flags & ~kListFlags) != 0u)
-        return fail(KNN_EINVAL, "knn_index_list_within: unknown flag (KNN_QUERY_INIT_KEYS, KNN_QUERY_COUNT_GRID, KNN_QUERY_COUNT_CELLS)");
-    if (slot < 0 || slot >= KNN_SLOTS)
-        return fail(KNN_EINVAL, "knn_index_list_within: slot outside 0 .. 7");
-    if (m < 1)
-        return fail(KNN_EINVAL, "knn_index_list_within: m < 1");
-    if (!queries_dev || !offsets_dev || !fill_dev || !keys_dev)
-        return fail(KNN_EINVAL, "knn_index_list_within: null queries, offsets, fill or keys");
-    if (!idx)
-        return fail(KNN_EINVAL, "knn_index_list_within: null index");
-    return list_within_run(idx, "knn_index_list_within", slot, m, queries_dev, nullptr, max_dist2, offsets_dev, fill_dev, keys_dev, stream,
-                           flags);
+    const WithinCall w = {"knn_index_list_within", kRouted, slot, m, queries_dev, 0, nullptr, max_dist2, stream, flags};
+    KNN_TRY(within_check(w, {{!queries_dev || !offsets_dev || !fill_dev || !keys_dev, "null queries, offsets, fill or keys"}}, idx));
+    return within_run(idx, w, lists_into(offsets_dev, fill_dev, keys_dev));
 }
 
 int knn_index_query_topk_large(knn_index *idx, int slot, int m, int K, const float *queries_dev, float max_dist2,
@@ -1586,18 +1613,12 @@ int knn_index_query_topk_large(knn_index *idx, int slot, int m, int K, const flo
     call.init = (flags & KNN_QUERY_INIT_KEYS) != 0u;
     hipStream_t s = call.stream;
     const int mk = m * K;
-    idx->stats[0] = 1;
-    idx->stats[1] = 0;
-    idx->stats[2] = 0;
-    idx->stats[3] = 0;
-    idx->grid_topk_gate = nullptr;
-    idx->last_slot = slot;
+    begin_call(idx, slot);
     if (idx->n > 0) {   // (an empty shard adds nothing)
         call.k = idx->k;
         call.n = idx->n;
         call.base = idx->base;
-        // a cell-range shard's keys carry its rows' global numbers (gids); an index-range shard's base + row
-        call.gids = idx->sharded && idx->filter.cells ? idx->filter.cells->gids : nullptr;
+        call.gids = shard_gids(idx);
         call.r = idx->refs;
         call.num_cu = idx->num_cu;
         // the slot's scratch, grown before the first launch
@@ -1606,10 +1627,7 @@ int knn_index_query_topk_large(knn_index *idx, int slot, int m, int K, const flo
         KNN_TRY(slot_buffer_grow(ts.large, ts.large_bytes, plan.scratch_bytes));
         call.part = ts.large;
         call.part_bytes = ts.large_bytes;
-        EventPair *ev = nullptr;
-        KNN_TRY(next_event_pair(idx, false, &ev));
-        call.ev0 = ev ? ev->first : nullptr;
-        call.ev1 = ev ? ev->second : nullptr;
+        KNN_TRY(take_events(idx, call));
         HIP_TRY(knn_topk_large_launch(call, plan, &idx->grid_topk_gate));
     } else if (call.init) {
         HIP_TRY(knn_keys_fill_launch(call.keys, mk, s));
@@ -1701,18 +1719,12 @@ int knn_index_query_topk_masked(knn_index *idx, int slot, int m, int K, const fl
     hipStream_t s = call.stream;
     const int mk = m * K;
     // one way on every index: no layout is consulted
-    idx->stats[0] = 1;
-    idx->stats[1] = 0;
-    idx->stats[2] = 0;
-    idx->stats[3] = 0;
-    idx->grid_topk_gate = nullptr;
-    idx->last_slot = slot;
+    begin_call(idx, slot);
     if (idx->n > 0) {   // (an empty shard adds nothing)
         call.k = idx->k;
         call.n = idx->n;
         call.base = idx->base;
-        // a cell-range shard's keys carry its rows' global numbers (gids); an index-range shard's base + row
-        call.gids = idx->sharded && idx->filter.cells ? idx->filter.cells->gids : nullptr;
+        call.gids = shard_gids(idx);
         call.r = idx->refs;
         call.num_cu = idx->num_cu;
         // the slot's scratch, grown before the first launch
@@ -1722,10 +1734,7 @@ int knn_index_query_topk_masked(knn_index *idx, int slot, int m, int K, const fl
         KNN_TRY(slot_buffer_grow(ts.part, ts.part_bytes, plan.part_bytes));
         call.part = ts.part;
         call.part_bytes = ts.part_bytes;
-        EventPair *ev = nullptr;
-        KNN_TRY(next_event_pair(idx, false, &ev));
-        call.ev0 = ev ? ev->first : nullptr;
-        call.ev1 = ev ? ev->second : nullptr;
+        KNN_TRY(take_events(idx, call));
         HIP_TRY(knn_masked_topk_launch(call, plan, mask_dev, ts.mask));
     } else if (call.init) {
         HIP_TRY(knn_keys_fill_launch(call.keys, mk, s));
@@ -1738,51 +1747,21 @@ int knn_index_query_topk_masked(knn_index *idx, int slot, int m, int K, const fl
 int knn_index_count_within_masked(knn_index *idx, int slot, int m, const float *queries_dev, float max_dist2,
                                   const unsigned *mask_dev, unsigned *counts_dev, void *stream, unsigned flags)
 {
-    if (!(max_dist2 >= 0.0f))
-        return fail(KNN_EINVAL, "knn_index_count_within_masked: max_dist2 must be >= 0 and not NaN");
-    if ((flags & ~(unsigned)KNN_QUERY_INIT_KEYS) != 0u)
-        return fail(KNN_EINVAL, "knn_index_count_within_masked: unknown flag (KNN_QUERY_INIT_KEYS alone is admitted)");
-    if (slot < 0 || slot >= KNN_SLOTS)
-        return fail(KNN_EINVAL, "knn_index_count_within_masked: slot outside 0 .. 7");
-    if (m < 1)
-        return fail(KNN_EINVAL, "knn_index_count_within_masked: m < 1");
-    if (!queries_dev || !mask_dev || !counts_dev)
-        return fail(KNN_EINVAL, "knn_index_count_within_masked: null queries, mask or counts");
-    if (!idx)
-        return fail(KNN_EINVAL, "knn_index_count_within_masked: null index");
+    const WithinCall w = {"knn_index_count_within_masked", 0u, slot, m, queries_dev, 0, nullptr, max_dist2, stream, flags};
+    KNN_TRY(within_check(w, {{!queries_dev || !mask_dev || !counts_dev, "null queries, mask or counts"}}, idx));
     std::lock_guard<std::recursive_mutex> lock(idx->mu);
     DeviceGuard guard(idx->device);
     if (!guard.ok)
-        return fail(KNN_EHIP, "knn_index_count_within_masked: hipSetDevice failed");
-    CountCall call;
-    call.k = idx->k;
-    call.m = m;
-    call.n = idx->n;
-    call.q = queries_dev;
-    call.r = idx->refs;
-    call.counts = counts_dev;
-    call.max_dist2 = max_dist2 == 0.0f ? 0.0f : max_dist2;   // (-0 counts as 0)
-    call.num_cu = idx->num_cu;
-    call.stream = (hipStream_t)stream;
-    hipStream_t s = call.stream;
-    idx->stats[0] = 1;
-    idx->stats[1] = 0;
-    idx->stats[2] = 0;
-    idx->stats[3] = 0;
-    idx->grid_topk_gate = nullptr;
-    idx->last_slot = slot;
-    // the scan ADDS to the caller's counts: an init call zeroes them first
-    if ((flags & KNN_QUERY_INIT_KEYS) != 0u)
-        HIP_TRY(hipMemsetAsync(counts_dev, 0, (size_t)m * sizeof(unsigned), s));
+        return fail_in(KNN_EHIP, w.who, "hipSetDevice failed");
+    // one way on every index: no layout is consulted
+    CountCall call = counts_into(counts_dev);
+    KNN_TRY(within_begin(idx, w, queries_dev, call));
     if (idx->n == 0)   // an empty shard adds nothing
         return KNN_OK;
     const MaskedPlan plan = knn_masked_plan(idx->k, m, 0, idx->n, idx->num_cu, (flags & KNN_QUERY_INIT_KEYS) != 0u);
     knn_index::TopkSlot &ts = idx->topk[slot];
     KNN_TRY(slot_buffer_grow(ts.mask, ts.mask_bytes, plan.mask_bytes));
-    EventPair *ev = nullptr;
-    KNN_TRY(next_event_pair(idx, false, &ev));
-    call.ev0 = ev ? ev->first : nullptr;
-    call.ev1 = ev ? ev->second : nullptr;
+    KNN_TRY(take_events(idx, call));
     HIP_TRY(knn_masked_count_launch(call, plan, mask_dev, ts.mask));
     return KNN_OK;
 }
@@ -1857,61 +1836,22 @@ int knn_index_list_within_masked(knn_index *idx, int slot, int m, const float *q
                                  const unsigned long long *offsets_dev, unsigned *fill_dev, unsigned long long *keys_dev, void *stream,
                                  unsigned flags)
 {
-    if (!(max_dist2 >= 0.0f))
-        return fail(KNN_EINVAL, "knn_index_list_within_masked: max_dist2 must be >= 0 and not NaN");
-    if ((flags & ~(unsigned)KNN_QUERY_INIT_KEYS) != 0u)
-        return fail(KNN_EINVAL, "knn_index_list_within_masked: unknown flag (KNN_QUERY_INIT_KEYS alone is admitted)");
-    if (slot < 0 || slot >= KNN_SLOTS)
-        return fail(KNN_EINVAL, "knn_index_list_within_masked: slot outside 0 .. 7");
-    if (m < 1)
-        return fail(KNN_EINVAL, "knn_index_list_within_masked: m < 1");
-    if (!queries_dev)
-        return fail(KNN_EINVAL, "knn_index_list_within_masked: null queries");
-    if (!mask_dev)
-        return fail(KNN_EINVAL, "knn_index_list_within_masked: null mask");
-    if (!offsets_dev || !fill_dev || !keys_dev)
-        return fail(KNN_EINVAL, "knn_index_list_within_masked: null offsets, fill or keys");
-    if (!idx)
-        return fail(KNN_EINVAL, "knn_index_list_within_masked: null index");
+    const WithinCall w = {"knn_index_list_within_masked", 0u, slot, m, queries_dev, 0, nullptr, max_dist2, stream, flags};
+    KNN_TRY(within_check(w, {{!queries_dev, "null queries"}, {!mask_dev, "null mask"}, {!offsets_dev || !fill_dev || !keys_dev, kNullLists}},
+                         idx));
     std::lock_guard<std::recursive_mutex> lock(idx->mu);
     DeviceGuard guard(idx->device);
     if (!guard.ok)
-        return fail(KNN_EHIP, "knn_index_list_within_masked: hipSetDevice failed");
-    ListCall call;
-    call.k = idx->k;
-    call.m = m;
-    call.n = idx->n;
-    call.base = idx->base;
-    // a cell-range shard's keys carry its rows' global numbers (gids); an index-range shard's base + row
-    call.gids = idx->sharded && idx->filter.cells ? idx->filter.cells->gids : nullptr;
-    call.q = queries_dev;
-    call.r = idx->refs;
-    call.offsets = (const u64 *)offsets_dev;
-    call.fill = fill_dev;
-    call.keys = (u64 *)keys_dev;
-    call.max_dist2 = max_dist2 == 0.0f ? 0.0f : max_dist2;   // (-0 counts as 0)
-    call.num_cu = idx->num_cu;
-    call.stream = (hipStream_t)stream;
-    hipStream_t s = call.stream;
+        return fail_in(KNN_EHIP, w.who, "hipSetDevice failed");
     // one way on every index: no layout is consulted
-    idx->stats[0] = 1;
-    idx->stats[1] = 0;
-    idx->stats[2] = 0;
-    idx->stats[3] = 0;
-    idx->grid_topk_gate = nullptr;
-    idx->last_slot = slot;
-    // the scan APPENDS behind the caller's fill: an init call zeroes it first
-    if ((flags & KNN_QUERY_INIT_KEYS) != 0u)
-        HIP_TRY(hipMemsetAsync(fill_dev, 0, (size_t)m * sizeof(unsigned), s));
+    ListCall call = lists_into(offsets_dev, fill_dev, keys_dev);
+    KNN_TRY(within_begin(idx, w, queries_dev, call));
     if (idx->n == 0)   // an empty shard appends nothing
         return KNN_OK;
     const MaskedListsPlan plan = knn_masked_lists_plan(idx->k, m, 0, idx->n, idx->num_cu, (flags & KNN_QUERY_INIT_KEYS) != 0u);
     knn_index::TopkSlot &ts = idx->topk[slot];
     KNN_TRY(slot_buffer_grow(ts.mask, ts.mask_bytes, plan.cut.mask_bytes));
-    EventPair *ev = nullptr;
-    KNN_TRY(next_event_pair(idx, false, &ev));
-    call.ev0 = ev ? ev->first : nullptr;
-    call.ev1 = ev ? ev->second : nullptr;
+    KNN_TRY(take_events(idx, call));
     HIP_TRY(knn_masked_list_launch(call, plan, mask_dev, ts.mask));
     return KNN_OK;
 }
@@ -1950,18 +1890,12 @@ int knn_index_query_topk_large_masked(knn_index *idx, int slot, int m, int K, co
     hipStream_t s = call.stream;
     const int mk = m * K;
     // one way on every index: no layout is consulted
-    idx->stats[0] = 1;
-    idx->stats[1] = 0;
-    idx->stats[2] = 0;
-    idx->stats[3] = 0;
-    idx->grid_topk_gate = nullptr;
-    idx->last_slot = slot;
+    begin_call(idx, slot);
     if (idx->n > 0) {   // (an empty shard adds nothing)
         call.k = idx->k;
         call.n = idx->n;
         call.base = idx->base;
-        // a cell-range shard's keys carry its rows' global numbers (gids); an index-range shard's base + row
-        call.gids = idx->sharded && idx->filter.cells ? idx->filter.cells->gids : nullptr;
+        call.gids = shard_gids(idx);
         call.r = idx->refs;
         call.num_cu = idx->num_cu;
         // the slot's mask scratch and large scratch, grown before the first launch
@@ -1971,10 +1905,7 @@ int knn_index_query_topk_large_masked(knn_index *idx, int slot, int m, int K, co
         KNN_TRY(slot_buffer_grow(ts.large, ts.large_bytes, plan.select_bytes));
         call.part = ts.large;
         call.part_bytes = ts.large_bytes;
-        EventPair *ev = nullptr;
-        KNN_TRY(next_event_pair(idx, false, &ev));
-        call.ev0 = ev ? ev->first : nullptr;
-        call.ev1 = ev ? ev->second : nullptr;
+        KNN_TRY(take_events(idx, call));
         HIP_TRY(knn_masked_large_launch(call, plan, mask_dev, ts.mask, &idx->grid_topk_gate));
     } else if (call.init) {
         HIP_TRY(knn_keys_fill_launch(call.keys, mk, s));
@@ -2035,8 +1966,7 @@ int knn_index_self_topk(knn_index *idx, int slot, long long row_first, int rows,
     const int mk = rows * K;
     const SelfPlan plan = knn_self_plan(idx->k, rows, K, idx->n, idx->num_cu, call.init != 0);
     knn_index::TopkSlot &ts = idx->topk[slot];
-    // a cell-range shard's keys carry its rows' global numbers (gids); an index-range shard's base + row
-    const unsigned *gids = idx->sharded && idx->filter.cells ? idx->filter.cells->gids : nullptr;
+    const unsigned *gids = shard_gids(idx);
     // The way: what the one route function says for the plain call of K + 1 neighbours — self is among ITS candidates — with
     // this call's rows, flags and options.  Exact, or no room for K + 1 keys — K = 64, or rows * (K + 1) beyond the plain call's
     // own INT_MAX limit —: the self-scan with K (the header's 2i says so).
@@ -2051,12 +1981,7 @@ int knn_index_self_topk(knn_index *idx, int slot, long long row_first, int rows,
         if (!call.init)
             HIP_TRY(knn_topk_merge_launch(rows, K, kept, call.keys, s));
     } else {
-        idx->stats[0] = 1;
-        idx->stats[1] = 0;
-        idx->stats[2] = 0;
-        idx->stats[3] = 0;
-        idx->grid_topk_gate = nullptr;
-        idx->last_slot = slot;
+        begin_call(idx, slot);
         call.k = idx->k;
         call.n = idx->n;
         call.base = idx->base;
@@ -2066,10 +1991,7 @@ int knn_index_self_topk(knn_index *idx, int slot, long long row_first, int rows,
         KNN_TRY(slot_buffer_grow(ts.part, ts.part_bytes, plan.part_bytes));
         call.part = ts.part;
         call.part_bytes = ts.part_bytes;
-        EventPair *ev = nullptr;
-        KNN_TRY(next_event_pair(idx, false, &ev));
-        call.ev0 = ev ? ev->first : nullptr;
-        call.ev1 = ev ? ev->second : nullptr;
+        KNN_TRY(take_events(idx, call));
         HIP_TRY(knn_self_topk_launch(call, row_first));
     }
     if (indices_dev)
@@ -2077,407 +1999,78 @@ int knn_index_self_topk(knn_index *idx, int slot, long long row_first, int rows,
     return KNN_OK;
 }
 
-// A self count call behind its host-only argument checks: knn_index_self_count_within (radii_dev null) and
-// knn_index_self_count_within_each (radii_dev the radii of the call's rows, max_dist2 the cap).
-static int self_count_run(knn_index *idx, const char *who, int slot, long long row_first, int rows, const float *radii_dev,
-                          float max_dist2, unsigned *counts_dev, void *stream, unsigned flags)
-{
-    std::lock_guard<std::recursive_mutex> lock(idx->mu);
-    if (row_first > idx->n || (long long)rows > idx->n - row_first)
-        return fail_in(KNN_EINVAL, who, "row_first + rows above the shard's rows");
-    DeviceGuard guard(idx->device);
-    if (!guard.ok)
-        return fail_in(KNN_EHIP, who, "hipSetDevice failed");
-    CountCall call;
-    call.k = idx->k;
-    call.m = rows;
-    call.n = idx->n;
-    call.r = idx->refs;
-    call.counts = counts_dev;
-    call.radii = radii_dev;
-    call.max_dist2 = max_dist2 == 0.0f ? 0.0f : max_dist2;   // (-0 counts as 0)
-    call.num_cu = idx->num_cu;
-    call.stream = (hipStream_t)stream;
-    hipStream_t s = call.stream;
-    // one way on every index: no layout is consulted
-    idx->stats[0] = 1;
-    idx->stats[1] = 0;
-    idx->stats[2] = 0;
-    idx->stats[3] = 0;
-    idx->grid_topk_gate = nullptr;
-    idx->last_slot = slot;
-    // the scan ADDS to the caller's counts: an init call zeroes them first
-    if ((flags & KNN_QUERY_INIT_KEYS) != 0u)
-        HIP_TRY(hipMemsetAsync(counts_dev, 0, (size_t)rows * sizeof(unsigned), s));
-    EventPair *ev = nullptr;
-    KNN_TRY(next_event_pair(idx, false, &ev));
-    call.ev0 = ev ? ev->first : nullptr;
-    call.ev1 = ev ? ev->second : nullptr;
-    HIP_TRY(knn_self_count_launch(call, row_first));
-    return KNN_OK;
-}
-
-// ... and a self list call: knn_index_self_list_within and knn_index_self_list_within_each.
-static int self_list_run(knn_index *idx, const char *who, int slot, long long row_first, int rows, const float *radii_dev,
-                         float max_dist2, const unsigned long long *offsets_dev, unsigned *fill_dev, unsigned long long *keys_dev,
-                         void *stream, unsigned flags)
-{
-    std::lock_guard<std::recursive_mutex> lock(idx->mu);
-    if (row_first > idx->n || (long long)rows > idx->n - row_first)
-        return fail_in(KNN_EINVAL, who, "row_first + rows above the shard's rows");
-    DeviceGuard guard(idx->device);
-    if (!guard.ok)
-        return fail_in(KNN_EHIP, who, "hipSetDevice failed");
-    ListCall call;
-    call.k = idx->k;
-    call.m = rows;
-    call.n = idx->n;
-    call.base = idx->base;
-    // a cell-range shard's keys carry its rows' global numbers (gids); an index-range shard's base + row
-    call.gids = idx->sharded && idx->filter.cells ? idx->filter.cells->gids : nullptr;
-    call.r = idx->refs;
-    call.offsets = (const u64 *)offsets_dev;
-    call.fill = fill_dev;
-    call.keys = (u64 *)keys_dev;
-    call.radii = radii_dev;
-    call.max_dist2 = max_dist2 == 0.0f ? 0.0f : max_dist2;   // (-0 counts as 0)
-    call.num_cu = idx->num_cu;
-    call.stream = (hipStream_t)stream;
-    hipStream_t s = call.stream;
-    // one way on every index: no layout is consulted
-    idx->stats[0] = 1;
-    idx->stats[1] = 0;
-    idx->stats[2] = 0;
-    idx->stats[3] = 0;
-    idx->grid_topk_gate = nullptr;
-    idx->last_slot = slot;
-    // the scan APPENDS behind the caller's fill: an init call zeroes it first
-    if ((flags & KNN_QUERY_INIT_KEYS) != 0u)
-        HIP_TRY(hipMemsetAsync(fill_dev, 0, (size_t)rows * sizeof(unsigned), s));
-    EventPair *ev = nullptr;
-    KNN_TRY(next_event_pair(idx, false, &ev));
-    call.ev0 = ev ? ev->first : nullptr;
-    call.ev1 = ev ? ev->second : nullptr;
-    HIP_TRY(knn_self_list_launch(call, row_first));
-    return KNN_OK;
-}
-
 int knn_index_self_count_within(knn_index *idx, int slot, long long row_first, int rows, float max_dist2, unsigned *counts_dev,
                                 void *stream, unsigned flags)
 {
-    if (!(max_dist2 >= 0.0f))
-        return fail(KNN_EINVAL, "knn_index_self_count_within: max_dist2 must be >= 0 and not NaN");
-    if ((flags & ~(unsigned)KNN_QUERY_INIT_KEYS) != 0u)
-        return fail(KNN_EINVAL, "knn_index_self_count_within: unknown flag (KNN_QUERY_INIT_KEYS alone is admitted)");
-    if (slot < 0 || slot >= KNN_SLOTS)
-        return fail(KNN_EINVAL, "knn_index_self_count_within: slot outside 0 .. 7");
-    if (rows < 1)
-        return fail(KNN_EINVAL, "knn_index_self_count_within: rows < 1");
-    if (row_first < 0)
-        return fail(KNN_EINVAL, "knn_index_self_count_within: row_first < 0");
-    if (!counts_dev)
-        return fail(KNN_EINVAL, "knn_index_self_count_within: null counts");
-    if (!idx)
-        return fail(KNN_EINVAL, "knn_index_self_count_within: null index");
-    return self_count_run(idx, "knn_index_self_count_within", slot, row_first, rows, nullptr, max_dist2, counts_dev, stream, flags);
+    const WithinCall w = {"knn_index_self_count_within", kSelf, slot, rows, nullptr, row_first, nullptr, max_dist2, stream, flags};
+    KNN_TRY(within_check(w, {{!counts_dev, "null counts"}}, idx));
+    return within_run(idx, w, counts_into(counts_dev));
 }
 
 int knn_index_self_list_within(knn_index *idx, int slot, long long row_first, int rows, float max_dist2,
                                const unsigned long long *offsets_dev, unsigned *fill_dev, unsigned long long *keys_dev, void *stream,
                                unsigned flags)
 {
-    if (!(max_dist2 >= 0.0f))
-        return fail(KNN_EINVAL, "knn_index_self_list_within: max_dist2 must be >= 0 and not NaN");
-    if ((flags & ~(unsigned)KNN_QUERY_INIT_KEYS) != 0u)
-        return fail(KNN_EINVAL, "knn_index_self_list_within: unknown flag (KNN_QUERY_INIT_KEYS alone is admitted)");
-    if (slot < 0 || slot >= KNN_SLOTS)
-        return fail(KNN_EINVAL, "knn_index_self_list_within: slot outside 0 .. 7");
-    if (rows < 1)
-        return fail(KNN_EINVAL, "knn_index_self_list_within: rows < 1");
-    if (row_first < 0)
-        return fail(KNN_EINVAL, "knn_index_self_list_within: row_first < 0");
-    if (!offsets_dev || !fill_dev || !keys_dev)
-        return fail(KNN_EINVAL, "knn_index_self_list_within: null offsets, fill or keys");
-    if (!idx)
-        return fail(KNN_EINVAL, "knn_index_self_list_within: null index");
-    return self_list_run(idx, "knn_index_self_list_within", slot, row_first, rows, nullptr, max_dist2, offsets_dev, fill_dev, keys_dev,
-                         stream, flags);
+    const WithinCall w = {"knn_index_self_list_within", kSelf, slot, rows, nullptr, row_first, nullptr, max_dist2, stream, flags};
+    KNN_TRY(within_check(w, {{!offsets_dev || !fill_dev || !keys_dev, kNullLists}}, idx));
+    return within_run(idx, w, lists_into(offsets_dev, fill_dev, keys_dev));
 }
 
-// ---- 2j. A radius per query --------------------------------------------------------------------------------------------------
-// (one message per rule, in the header's order, the index last: tests/test_each_logic.py tells them apart without a GPU)
+// ---- 2j. A radius per query: max_dist2_dev the radii, cap the radius the way is chosen at -----------------------------------------
 int knn_index_count_within_each(knn_index *idx, int slot, int m, const float *queries_dev, const float *max_dist2_dev, float cap,
                                 unsigned *counts_dev, void *stream, unsigned flags)
 {
-    if (!(cap >= 0.0f))
-        return fail(KNN_EINVAL, "knn_index_count_within_each: cap must be >= 0 (or +INF) and not NaN");
-    constexpr unsigned kCountFlags = KNN_QUERY_INIT_KEYS | KNN_QUERY_COUNT_GRID | KNN_QUERY_COUNT_CELLS;   // the three it admits
-    if ((flags & ~kCountFlags) != 0u)
-        return fail(KNN_EINVAL, "knn_index_count_within_each: unknown flag (KNN_QUERY_INIT_KEYS, KNN_QUERY_COUNT_GRID, KNN_QUERY_COUNT_CELLS)");
-    if (slot < 0 || slot >= KNN_SLOTS)
-        return fail(KNN_EINVAL, "knn_index_count_within_each: slot outside 0 .. 7");
-    if (m < 1)
-        return fail(KNN_EINVAL, "knn_index_count_within_each: m < 1");
-    if (!queries_dev)
-        return fail(KNN_EINVAL, "knn_index_count_within_each: null queries");
-    if (!max_dist2_dev)
-        return fail(KNN_EINVAL, "knn_index_count_within_each: null radii");
-    if (!counts_dev)
-        return fail(KNN_EINVAL, "knn_index_count_within_each: null counts");
-    if (!idx)
-        return fail(KNN_EINVAL, "knn_index_count_within_each: null index");
-    return count_within_run(idx, "knn_index_count_within_each", slot, m, queries_dev, max_dist2_dev, cap, counts_dev, stream, flags);
+    const WithinCall w = {"knn_index_count_within_each", kCap | kRouted, slot, m, queries_dev, 0, max_dist2_dev, cap, stream, flags};
+    KNN_TRY(within_check(w, {{!queries_dev, "null queries"}, {!max_dist2_dev, "null radii"}, {!counts_dev, "null counts"}}, idx));
+    return within_run(idx, w, counts_into(counts_dev));
 }
 
 int knn_index_list_within_each(knn_index *idx, int slot, int m, const float *queries_dev, const float *max_dist2_dev, float cap,
                                const unsigned long long *offsets_dev, unsigned *fill_dev, unsigned long long *keys_dev, void *stream,
                                unsigned flags)
 {
-    if (!(cap >= 0.0f))
-        return fail(KNN_EINVAL, "knn_index_list_within_each: cap must be >= 0 (or +INF) and not NaN");
-    constexpr unsigned kListFlags = KNN_QUERY_INIT_KEYS | KNN_QUERY_COUNT_GRID | KNN_QUERY_COUNT_CELLS;   // the three it admits
-    if ((flags & ~kListFlags) != 0u)
-        return fail(KNN_EINVAL, "knn_index_list_within_each: unknown flag (KNN_QUERY_INIT_KEYS, KNN_QUERY_COUNT_GRID, KNN_QUERY_COUNT_CELLS)");
-    if (slot < 0 || slot >= KNN_SLOTS)
-        return fail(KNN_EINVAL, "knn_index_list_within_each: slot outside 0 .. 7");
-    if (m < 1)
-        return fail(KNN_EINVAL, "knn_index_list_within_each: m < 1");
-    if (!queries_dev)
-        return fail(KNN_EINVAL, "knn_index_list_within_each: null queries");
-    if (!max_dist2_dev)
-        return fail(KNN_EINVAL, "knn_index_list_within_each: null radii");
-    if (!offsets_dev || !fill_dev || !keys_dev)
-        return fail(KNN_EINVAL, "knn_index_list_within_each: null offsets, fill or keys");
-    if (!idx)
-        return fail(KNN_EINVAL, "knn_index_list_within_each: null index");
-    return list_within_run(idx, "knn_index_list_within_each", slot, m, queries_dev, max_dist2_dev, cap, offsets_dev, fill_dev, keys_dev,
-                           stream, flags);
+    const WithinCall w = {"knn_index_list_within_each", kCap | kRouted, slot, m, queries_dev, 0, max_dist2_dev, cap, stream, flags};
+    KNN_TRY(within_check(w, {{!queries_dev, "null queries"}, {!max_dist2_dev, "null radii"},
+                             {!offsets_dev || !fill_dev || !keys_dev, kNullLists}}, idx));
+    return within_run(idx, w, lists_into(offsets_dev, fill_dev, keys_dev));
 }
 
 int knn_index_self_count_within_each(knn_index *idx, int slot, long long row_first, int rows, const float *max_dist2_dev, float cap,
                                      unsigned *counts_dev, void *stream, unsigned flags)
 {
-    if (!(cap >= 0.0f))
-        return fail(KNN_EINVAL, "knn_index_self_count_within_each: cap must be >= 0 (or +INF) and not NaN");
-    if ((flags & ~(unsigned)KNN_QUERY_INIT_KEYS) != 0u)
-        return fail(KNN_EINVAL, "knn_index_self_count_within_each: unknown flag (KNN_QUERY_INIT_KEYS alone is admitted)");
-    if (slot < 0 || slot >= KNN_SLOTS)
-        return fail(KNN_EINVAL, "knn_index_self_count_within_each: slot outside 0 .. 7");
-    if (rows < 1)
-        return fail(KNN_EINVAL, "knn_index_self_count_within_each: rows < 1");
-    if (row_first < 0)
-        return fail(KNN_EINVAL, "knn_index_self_count_within_each: row_first < 0");
-    if (!max_dist2_dev)
-        return fail(KNN_EINVAL, "knn_index_self_count_within_each: null radii");
-    if (!counts_dev)
-        return fail(KNN_EINVAL, "knn_index_self_count_within_each: null counts");
-    if (!idx)
-        return fail(KNN_EINVAL, "knn_index_self_count_within_each: null index");
-    return self_count_run(idx, "knn_index_self_count_within_each", slot, row_first, rows, max_dist2_dev, cap, counts_dev, stream, flags);
+    const WithinCall w = {"knn_index_self_count_within_each", kCap | kSelf, slot, rows, nullptr, row_first, max_dist2_dev, cap, stream, flags};
+    KNN_TRY(within_check(w, {{!max_dist2_dev, "null radii"}, {!counts_dev, "null counts"}}, idx));
+    return within_run(idx, w, counts_into(counts_dev));
 }
 
 int knn_index_self_list_within_each(knn_index *idx, int slot, long long row_first, int rows, const float *max_dist2_dev, float cap,
                                     const unsigned long long *offsets_dev, unsigned *fill_dev, unsigned long long *keys_dev,
                                     void *stream, unsigned flags)
 {
-    if (!(cap >= 0.0f))
-        return fail(KNN_EINVAL, "knn_index_self_list_within_each: cap must be >= 0 (or +INF) and not NaN");
-    if ((flags & ~(unsigned)KNN_QUERY_INIT_KEYS) != 0u)
-        return fail(KNN_EINVAL, "knn_index_self_list_within_each: unknown flag (KNN_QUERY_INIT_KEYS alone is admitted)");
-    if (slot < 0 || slot >= KNN_SLOTS)
-        return fail(KNN_EINVAL, "knn_index_self_list_within_each: slot outside 0 .. 7");
-    if (rows < 1)
-        return fail(KNN_EINVAL, "knn_index_self_list_within_each: rows < 1");
-    if (row_first < 0)
-        return fail(KNN_EINVAL, "knn_index_self_list_within_each: row_first < 0");
-    if (!max_dist2_dev)
-        return fail(KNN_EINVAL, "knn_index_self_list_within_each: null radii");
-    if (!offsets_dev || !fill_dev || !keys_dev)
-        return fail(KNN_EINVAL, "knn_index_self_list_within_each: null offsets, fill or keys");
-    if (!idx)
-        return fail(KNN_EINVAL, "knn_index_self_list_within_each: null index");
-    return self_list_run(idx, "knn_index_self_list_within_each", slot, row_first, rows, max_dist2_dev, cap, offsets_dev, fill_dev,
-                         keys_dev, stream, flags);
+    const WithinCall w = {"knn_index_self_list_within_each", kCap | kSelf, slot, rows, nullptr, row_first, max_dist2_dev, cap, stream, flags};
+    KNN_TRY(within_check(w, {{!max_dist2_dev, "null radii"}, {!offsets_dev || !fill_dev || !keys_dev, kNullLists}}, idx));
+    return within_run(idx, w, lists_into(offsets_dev, fill_dev, keys_dev));
 }
 
-// The radius graph on the grid and cell-pruned ways (include/knn_mi355x.h 2k; DESIGN §4.6 "The radius graph on the pruned ways").
-// A routed self count call behind its host-only argument checks, built as count_within_run with the queries that are the rows
-// themselves: the way is knn_count_route's for `rows` queries at max_dist2 = cap under the same flags and options — way 1 the
-// exact self-scan in the exact count's place —, and call.self_first tells the grid and cell ways to drop a query's own row and to
-// gate the self-scan behind them.  radii_dev null: the scalar form, every row's radius the cap.
-static int self_routed_count_run(knn_index *idx, const char *who, int slot, long long row_first, int rows, const float *radii_dev,
-                                 float cap, unsigned *counts_dev, void *stream, unsigned flags)
-{
-    std::lock_guard<std::recursive_mutex> lock(idx->mu);
-    if (row_first > idx->n || (long long)rows > idx->n - row_first)
-        return fail_in(KNN_EINVAL, who, "row_first + rows above the shard's rows");
-    DeviceGuard guard(idx->device);
-    if (!guard.ok)
-        return fail_in(KNN_EHIP, who, "hipSetDevice failed");
-    CountCall call;
-    call.k = idx->k;
-    call.m = rows;
-    call.n = idx->n;
-    call.r = idx->refs;
-    call.q = idx->refs + (size_t)row_first * (size_t)idx->k;   // the queries are resident: nothing is uploaded
-    call.self_first = row_first;
-    call.counts = counts_dev;
-    call.radii = radii_dev;
-    call.max_dist2 = cap == 0.0f ? 0.0f : cap;   // (-0 counts as 0)
-    call.num_cu = idx->num_cu;
-    call.stream = (hipStream_t)stream;
-    hipStream_t s = call.stream;
-    idx->stats[0] = 1;
-    idx->stats[1] = 0;
-    idx->stats[2] = 0;
-    idx->stats[3] = 0;
-    idx->grid_topk_gate = nullptr;
-    idx->last_slot = slot;
-    // every way ADDS to the caller's counts: an init call zeroes them first
-    if ((flags & KNN_QUERY_INIT_KEYS) != 0u)
-        HIP_TRY(hipMemsetAsync(counts_dev, 0, (size_t)rows * sizeof(unsigned), s));
-    const QueryRouteInputs ri = route_inputs(idx, rows, 1, 0u);
-    const CountPlan plan = count_plan_of(idx, ri, rows, call.max_dist2, flags);
-    idx->stats[0] = (long long)plan.way;
-    // the slot's count scratch, grown before the first launch
-    knn_index::TopkSlot &ts = idx->topk[slot];
-    KNN_TRY(slot_buffer_grow(ts.count, ts.count_bytes, plan.scratch_bytes));
-    call.scratch = (unsigned *)ts.count;
-    EventPair *ev = nullptr;
-    KNN_TRY(next_event_pair(idx, false, &ev));
-    call.ev0 = ev ? ev->first : nullptr;
-    call.ev1 = ev ? ev->second : nullptr;
-    switch (plan.way) {
-    case QueryWay::Grid:
-        HIP_TRY(knn_grid_query_count(idx->grid, plan.rmax, slot, call, &idx->grid_topk_gate));
-        break;
-    case QueryWay::Cells: {
-        const CellTopkPlan tp = knn_cells_count_plan(ri.t);
-        if (!tp.use)
-            return fail_in(KNN_EHIP, who, "the cell-pruned scan has no pass shape for this layout");
-        HIP_TRY(knn_filter_query_count_cells(idx->filter, tp, slot, call));
-        break;
-    }
-    default:   // exactly what the existing self call launches
-        HIP_TRY(knn_self_count_launch(call, row_first));
-        break;
-    }
-    return KNN_OK;
-}
-
-// ... and a routed self list call, built as list_within_run.
-static int self_routed_list_run(knn_index *idx, const char *who, int slot, long long row_first, int rows, const float *radii_dev,
-                                float cap, const unsigned long long *offsets_dev, unsigned *fill_dev, unsigned long long *keys_dev,
-                                void *stream, unsigned flags)
-{
-    std::lock_guard<std::recursive_mutex> lock(idx->mu);
-    if (row_first > idx->n || (long long)rows > idx->n - row_first)
-        return fail_in(KNN_EINVAL, who, "row_first + rows above the shard's rows");
-    DeviceGuard guard(idx->device);
-    if (!guard.ok)
-        return fail_in(KNN_EHIP, who, "hipSetDevice failed");
-    ListCall call;
-    call.k = idx->k;
-    call.m = rows;
-    call.n = idx->n;
-    call.base = idx->base;
-    // a cell-range shard's keys carry its rows' global numbers (gids); an index-range shard's base + row
-    call.gids = idx->sharded && idx->filter.cells ? idx->filter.cells->gids : nullptr;
-    call.r = idx->refs;
-    call.q = idx->refs + (size_t)row_first * (size_t)idx->k;   // the queries are resident: nothing is uploaded
-    call.self_first = row_first;
-    call.offsets = (const u64 *)offsets_dev;
-    call.fill = fill_dev;
-    call.keys = (u64 *)keys_dev;
-    call.radii = radii_dev;
-    call.max_dist2 = cap == 0.0f ? 0.0f : cap;   // (-0 counts as 0)
-    call.num_cu = idx->num_cu;
-    call.stream = (hipStream_t)stream;
-    hipStream_t s = call.stream;
-    idx->stats[0] = 1;
-    idx->stats[1] = 0;
-    idx->stats[2] = 0;
-    idx->stats[3] = 0;
-    idx->grid_topk_gate = nullptr;
-    idx->last_slot = slot;
-    // every way APPENDS behind the caller's fill: an init call zeroes it first
-    if ((flags & KNN_QUERY_INIT_KEYS) != 0u)
-        HIP_TRY(hipMemsetAsync(fill_dev, 0, (size_t)rows * sizeof(unsigned), s));
-    const QueryRouteInputs ri = route_inputs(idx, rows, 1, 0u);
-    const CountPlan plan = count_plan_of(idx, ri, rows, call.max_dist2, flags);
-    idx->stats[0] = (long long)plan.way;
-    // the slot's count scratch — the scratch cursor of the grid and cell ways —, grown before the first launch
-    knn_index::TopkSlot &ts = idx->topk[slot];
-    KNN_TRY(slot_buffer_grow(ts.count, ts.count_bytes, plan.scratch_bytes));
-    call.scratch = (unsigned *)ts.count;
-    EventPair *ev = nullptr;
-    KNN_TRY(next_event_pair(idx, false, &ev));
-    call.ev0 = ev ? ev->first : nullptr;
-    call.ev1 = ev ? ev->second : nullptr;
-    switch (plan.way) {
-    case QueryWay::Grid:
-        HIP_TRY(knn_grid_query_list(idx->grid, plan.rmax, slot, call, &idx->grid_topk_gate));
-        break;
-    case QueryWay::Cells: {
-        const CellTopkPlan tp = knn_cells_count_plan(ri.t);
-        if (!tp.use)
-            return fail_in(KNN_EHIP, who, "the cell-pruned scan has no pass shape for this layout");
-        HIP_TRY(knn_filter_query_list_cells(idx->filter, tp, slot, call));
-        break;
-    }
-    default:   // exactly what the existing self call launches
-        HIP_TRY(knn_self_list_launch(call, row_first));
-        break;
-    }
-    return KNN_OK;
-}
-
+// ---- 2k. The radius graph on the grid and cell-pruned ways (DESIGN §4.6 "The radius graph on the pruned ways") --------------------
+// max_dist2_dev null: the scalar form, every row's radius the cap.
 int knn_index_self_count_within_routed(knn_index *idx, int slot, long long row_first, int rows, const float *max_dist2_dev, float cap,
                                        unsigned *counts_dev, void *stream, unsigned flags)
 {
-    // (one message per rule, the index last but for the rule that needs it: tests/test_self_routed_logic.py tells them apart)
-    if (!(cap >= 0.0f))
-        return fail(KNN_EINVAL, "knn_index_self_count_within_routed: cap must be >= 0 (or +INF) and not NaN");
-    constexpr unsigned kFlags = KNN_QUERY_INIT_KEYS | KNN_QUERY_COUNT_GRID | KNN_QUERY_COUNT_CELLS;   // the three it admits
-    if ((flags & ~kFlags) != 0u)
-        return fail(KNN_EINVAL, "knn_index_self_count_within_routed: unknown flag (KNN_QUERY_INIT_KEYS, KNN_QUERY_COUNT_GRID, "
-                                "KNN_QUERY_COUNT_CELLS)");
-    if (slot < 0 || slot >= KNN_SLOTS)
-        return fail(KNN_EINVAL, "knn_index_self_count_within_routed: slot outside 0 .. 7");
-    if (rows < 1)
-        return fail(KNN_EINVAL, "knn_index_self_count_within_routed: rows < 1");
-    if (row_first < 0)
-        return fail(KNN_EINVAL, "knn_index_self_count_within_routed: row_first < 0");
-    if (!counts_dev)
-        return fail(KNN_EINVAL, "knn_index_self_count_within_routed: null counts");
-    if (!idx)
-        return fail(KNN_EINVAL, "knn_index_self_count_within_routed: null index");
-    return self_routed_count_run(idx, "knn_index_self_count_within_routed", slot, row_first, rows, max_dist2_dev, cap, counts_dev, stream,
-                                 flags);
+    const WithinCall w = {"knn_index_self_count_within_routed", kCap | kRouted | kSelf, slot, rows, nullptr, row_first, max_dist2_dev, cap,
+                          stream, flags};
+    KNN_TRY(within_check(w, {{!counts_dev, "null counts"}}, idx));
+    return within_run(idx, w, counts_into(counts_dev));
 }
 
 int knn_index_self_list_within_routed(knn_index *idx, int slot, long long row_first, int rows, const float *max_dist2_dev, float cap,
                                       const unsigned long long *offsets_dev, unsigned *fill_dev, unsigned long long *keys_dev,
                                       void *stream, unsigned flags)
 {
-    if (!(cap >= 0.0f))
-        return fail(KNN_EINVAL, "knn_index_self_list_within_routed: cap must be >= 0 (or +INF) and not NaN");
-    constexpr unsigned kFlags = KNN_QUERY_INIT_KEYS | KNN_QUERY_COUNT_GRID | KNN_QUERY_COUNT_CELLS;   // the three it admits
-    if ((flags & ~kFlags) != 0u)
-        return fail(KNN_EINVAL, "knn_index_self_list_within_routed: unknown flag (KNN_QUERY_INIT_KEYS, KNN_QUERY_COUNT_GRID, "
-                                "KNN_QUERY_COUNT_CELLS)");
-    if (slot < 0 || slot >= KNN_SLOTS)
-        return fail(KNN_EINVAL, "knn_index_self_list_within_routed: slot outside 0 .. 7");
-    if (rows < 1)
-        return fail(KNN_EINVAL, "knn_index_self_list_within_routed: rows < 1");
-    if (row_first < 0)
-        return fail(KNN_EINVAL, "knn_index_self_list_within_routed: row_first < 0");
-    if (!offsets_dev || !fill_dev || !keys_dev)
-        return fail(KNN_EINVAL, "knn_index_self_list_within_routed: null offsets, fill or keys");
-    if (!idx)
-        return fail(KNN_EINVAL, "knn_index_self_list_within_routed: null index");
-    return self_routed_list_run(idx, "knn_index_self_list_within_routed", slot, row_first, rows, max_dist2_dev, cap, offsets_dev, fill_dev,
-                                keys_dev, stream, flags);
+    const WithinCall w = {"knn_index_self_list_within_routed", kCap | kRouted | kSelf, slot, rows, nullptr, row_first, max_dist2_dev, cap,
+                          stream, flags};
+    KNN_TRY(within_check(w, {{!offsets_dev || !fill_dev || !keys_dev, kNullLists}}, idx));
+    return within_run(idx, w, lists_into(offsets_dev, fill_dev, keys_dev));
 }
 
 int knn_debug_self_routed_plan(const long long in[16], long long out[8])
@@ -2968,6 +2561,54 @@ int staged_query(knn_index *idx, const char *who, int m, int K, const float *que
     return KNN_OK;
 }
 
+// A packed key's halves: the row number (low word) and, dist2 non-null, the distance whose bits the high word holds.
+inline void unpack_key(u64 key, int *index, float *dist2)
+{
+    *index = (int)(unsigned)(key & 0xFFFFFFFFull);
+    if (dist2) {
+        const unsigned hi = (unsigned)(key >> 32);
+        memcpy(dist2, &hi, sizeof hi);
+    }
+}
+
+// The host arrays of a top-K host call from its m lists of K keys: indices and (nullable) dist2 [m][K], and (nullable) counts [m],
+// the real keys of a list — padding is KNN_KEY_INIT; a real key is below it.
+void unpack_topk(const u64 *keys, int m, int K, int *indices, float *dist2, int *counts)
+{
+    for (size_t i = 0; i < (size_t)m * (size_t)K; ++i)
+        unpack_key(keys[i], &indices[i], dist2 ? &dist2[i] : nullptr);
+    if (counts)
+        for (int j = 0; j < m; ++j) {
+            int c = 0;
+            while (c < K && keys[(size_t)j * K + c] < kKeyInit)
+                ++c;
+            counts[j] = c;
+        }
+}
+
+// The tail of a list host call: the sorted keys of all segments -> malloc'd indices and (dist2_out non-null) dist2, one element of
+// room for an empty result, and the offsets [offs.size()] to the caller's array.  Nothing stays allocated on failure.
+int lists_to_host(const char *who, const std::vector<u64> &offs, const std::vector<u64> &keys, long long *offsets_host,
+                  int **indices_out, float **dist2_out)
+{
+    const size_t total = keys.size(), room = total ? total : 1u;
+    int *ind = (int *)malloc(room * sizeof(int));
+    float *d2 = dist2_out ? (float *)malloc(room * sizeof(float)) : nullptr;
+    if (!ind || (dist2_out && !d2)) {
+        free(ind);
+        free(d2);
+        return fail_in(KNN_EHIP, who, "out of host memory");
+    }
+    for (size_t i = 0; i < total; ++i)
+        unpack_key(keys[i], &ind[i], d2 ? &d2[i] : nullptr);
+    for (size_t j = 0; j < offs.size(); ++j)
+        offsets_host[j] = (long long)offs[j];
+    *indices_out = ind;
+    if (dist2_out)
+        *dist2_out = d2;
+    return KNN_OK;
+}
+
 }  // namespace
 
 extern "C" int knn_index_query_host(knn_index *idx, int m, const float *queries_host, int *out_host)
@@ -2983,7 +2624,7 @@ extern "C" int knn_index_query_host(knn_index *idx, int m, const float *queries_
             return rc;
     }
     for (int j = 0; j < m; ++j)
-        out_host[j] = (int)(unsigned)(keys[(size_t)j] & 0xFFFFFFFFull);
+        unpack_key(keys[(size_t)j], &out_host[j], nullptr);
     return KNN_OK;
 }
 
@@ -2998,13 +2639,7 @@ extern "C" int knn_index_query_topk_host(knn_index *idx, int m, int K, const flo
     const int rc = staged_query(idx, "knn_index_query_topk_host", m, K, queries_host, keys.data());
     if (rc != KNN_OK)
         return rc;
-    for (size_t i = 0; i < mk; ++i) {
-        indices_host[i] = (int)(unsigned)(keys[i] & 0xFFFFFFFFull);
-        if (dist2_host) {
-            const unsigned hi = (unsigned)(keys[i] >> 32);
-            memcpy(&dist2_host[i], &hi, sizeof hi);
-        }
-    }
+    unpack_topk(keys.data(), m, K, indices_host, dist2_host, nullptr);
     return KNN_OK;
 }
 
@@ -3019,20 +2654,7 @@ extern "C" int knn_index_query_topk_within_host(knn_index *idx, int m, int K, co
     const int rc = staged_query(idx, "knn_index_query_topk_within_host", m, K, queries_host, keys.data(), nullptr, max_dist2);
     if (rc != KNN_OK)
         return rc;
-    for (size_t i = 0; i < mk; ++i) {
-        indices_host[i] = (int)(unsigned)(keys[i] & 0xFFFFFFFFull);
-        if (dist2_host) {
-            const unsigned hi = (unsigned)(keys[i] >> 32);
-            memcpy(&dist2_host[i], &hi, sizeof hi);
-        }
-    }
-    if (counts_host)
-        for (int j = 0; j < m; ++j) {   // padding is KNN_KEY_INIT; a real key is below it
-            int c = 0;
-            while (c < K && keys[(size_t)j * K + c] < kKeyInit)
-                ++c;
-            counts_host[j] = c;
-        }
+    unpack_topk(keys.data(), m, K, indices_host, dist2_host, counts_host);
     return KNN_OK;
 }
 
@@ -3077,20 +2699,7 @@ extern "C" int knn_index_query_topk_large_host(knn_index *idx, int m, int K, con
             return fail(KNN_EHIP, "knn_index_query_topk_large_host: D2H keys", hipGetErrorString(e));
         // (not declared waited: the buffers go back after the device-wide wait `stage` then makes itself, as the top-K's)
     }
-    for (size_t i = 0; i < mk; ++i) {
-        indices_host[i] = (int)(unsigned)(keys[i] & 0xFFFFFFFFull);
-        if (dist2_host) {
-            const unsigned hi = (unsigned)(keys[i] >> 32);
-            memcpy(&dist2_host[i], &hi, sizeof hi);
-        }
-    }
-    if (counts_host)
-        for (int j = 0; j < m; ++j) {   // padding is KNN_KEY_INIT; a real key is below it
-            int c = 0;
-            while (c < K && keys[(size_t)j * K + c] < kKeyInit)
-                ++c;
-            counts_host[j] = c;
-        }
+    unpack_topk(keys.data(), m, K, indices_host, dist2_host, counts_host);
     return KNN_OK;
 }
 
@@ -3141,20 +2750,7 @@ extern "C" int knn_index_query_topk_masked_host(knn_index *idx, int m, int K, co
             return fail(KNN_EHIP, "knn_index_query_topk_masked_host: D2H keys", hipGetErrorString(e));
         // (not declared waited: the buffers go back after the device-wide wait `stage` then makes itself, as the top-K's)
     }
-    for (size_t i = 0; i < mk; ++i) {
-        indices_host[i] = (int)(unsigned)(keys[i] & 0xFFFFFFFFull);
-        if (dist2_host) {
-            const unsigned hi = (unsigned)(keys[i] >> 32);
-            memcpy(&dist2_host[i], &hi, sizeof hi);
-        }
-    }
-    if (counts_host)
-        for (int j = 0; j < m; ++j) {   // padding is KNN_KEY_INIT; a real key is below it
-            int c = 0;
-            while (c < K && keys[(size_t)j * K + c] < kKeyInit)
-                ++c;
-            counts_host[j] = c;
-        }
+    unpack_topk(keys.data(), m, K, indices_host, dist2_host, counts_host);
     return KNN_OK;
 }
 
@@ -3253,28 +2849,8 @@ static int list_within_host_run(knn_index *idx, const char *who, int m, const fl
         if (e != hipSuccess)
             return fail_in(KNN_EHIP, who, "D2H keys", hipGetErrorString(e));
     }
-    const size_t room = total ? (size_t)total : 1u;
-    int *ind = (int *)malloc(room * sizeof(int));
-    float *d2 = dist2_out ? (float *)malloc(room * sizeof(float)) : nullptr;
-    if (!ind || (dist2_out && !d2)) {
-        free(ind);
-        free(d2);
-        return fail_in(KNN_EHIP, who, "out of host memory");
-    }
-    for (size_t i = 0; i < (size_t)total; ++i) {
-        ind[i] = (int)(unsigned)(keys[i] & 0xFFFFFFFFull);
-        if (d2) {
-            const unsigned hi = (unsigned)(keys[i] >> 32);
-            memcpy(&d2[i], &hi, sizeof hi);
-        }
-    }
-    for (int j = 0; j <= m; ++j)
-        offsets_host[j] = (long long)offs[(size_t)j];
-    *indices_out = ind;
-    if (dist2_out)
-        *dist2_out = d2;
     // (not declared waited: the slot's buffers go back after the device-wide wait `stage` then makes itself, as the other host calls)
-    return KNN_OK;
+    return lists_to_host(who, offs, keys, offsets_host, indices_out, dist2_out);
 }
 
 extern "C" int knn_index_count_within_host(knn_index *idx, int m, const float *queries_host, float max_dist2, unsigned *counts_host)
@@ -3343,20 +2919,7 @@ extern "C" int knn_index_self_topk_host(knn_index *idx, int K, float max_dist2, 
         e = hipMemcpy(keys.data(), keys_dev, mk * sizeof(u64), hipMemcpyDeviceToHost);
         if (e != hipSuccess)
             return fail(KNN_EHIP, "knn_index_self_topk_host: D2H keys", hipGetErrorString(e));
-        for (size_t i = 0; i < mk; ++i) {
-            indices_host[at + i] = (int)(unsigned)(keys[i] & 0xFFFFFFFFull);
-            if (dist2_host) {
-                const unsigned hi = (unsigned)(keys[i] >> 32);
-                memcpy(&dist2_host[at + i], &hi, sizeof hi);
-            }
-        }
-        if (counts_host)
-            for (int j = 0; j < rc; ++j) {   // padding is KNN_KEY_INIT; a real key is below it
-                int c = 0;
-                while (c < K && keys[(size_t)j * K + c] < kKeyInit)
-                    ++c;
-                counts_host[r0 + j] = c;
-            }
+        unpack_topk(keys.data(), rc, K, indices_host + at, dist2_host ? dist2_host + at : nullptr, counts_host ? counts_host + r0 : nullptr);
     }
     // (not declared waited: the buffers go back after the device-wide wait `stage` then makes itself, as the other host calls)
     return KNN_OK;
@@ -3435,28 +2998,8 @@ static int self_list_host_run(knn_index *idx, const char *who, bool routed, cons
                 return fail_in(KNN_EHIP, who, "D2H keys", hipGetErrorString(e));
         }
     }
-    const size_t total = keys.size(), room = total ? total : 1u;
-    int *ind = (int *)malloc(room * sizeof(int));
-    float *d2 = dist2_out ? (float *)malloc(room * sizeof(float)) : nullptr;
-    if (!ind || (dist2_out && !d2)) {
-        free(ind);
-        free(d2);
-        return fail_in(KNN_EHIP, who, "out of host memory");
-    }
-    for (size_t i = 0; i < total; ++i) {
-        ind[i] = (int)(unsigned)(keys[i] & 0xFFFFFFFFull);
-        if (d2) {
-            const unsigned hi = (unsigned)(keys[i] >> 32);
-            memcpy(&d2[i], &hi, sizeof hi);
-        }
-    }
-    for (int j = 0; j <= n; ++j)
-        offsets_host[j] = (long long)offs[(size_t)j];
-    *indices_out = ind;
-    if (dist2_out)
-        *dist2_out = d2;
     // (not declared waited: the slot's buffers go back after the device-wide wait `stage` then makes itself, as the other host calls)
-    return KNN_OK;
+    return lists_to_host(who, offs, keys, offsets_host, indices_out, dist2_out);
 }
 
 extern "C" int knn_index_self_list_within_host(knn_index *idx, float max_dist2, long long *offsets_host, int **indices_out,
@@ -3548,28 +3091,8 @@ extern "C" int knn_index_list_within_masked_host(knn_index *idx, int m, const fl
         if (e != hipSuccess)
             return fail(KNN_EHIP, "knn_index_list_within_masked_host: D2H keys", hipGetErrorString(e));
     }
-    const size_t room = total ? (size_t)total : 1u;
-    int *ind = (int *)malloc(room * sizeof(int));
-    float *d2 = dist2_out ? (float *)malloc(room * sizeof(float)) : nullptr;
-    if (!ind || (dist2_out && !d2)) {
-        free(ind);
-        free(d2);
-        return fail(KNN_EHIP, "knn_index_list_within_masked_host: out of host memory");
-    }
-    for (size_t i = 0; i < (size_t)total; ++i) {
-        ind[i] = (int)(unsigned)(keys[i] & 0xFFFFFFFFull);
-        if (d2) {
-            const unsigned hi = (unsigned)(keys[i] >> 32);
-            memcpy(&d2[i], &hi, sizeof hi);
-        }
-    }
-    for (int j = 0; j <= m; ++j)
-        offsets_host[j] = (long long)offs[(size_t)j];
-    *indices_out = ind;
-    if (dist2_out)
-        *dist2_out = d2;
     // (not declared waited: the slot's buffers go back after the device-wide wait `stage` then makes itself, as the other host calls)
-    return KNN_OK;
+    return lists_to_host("knn_index_list_within_masked_host", offs, keys, offsets_host, indices_out, dist2_out);
 }
 
 extern "C" int knn_index_query_topk_large_masked_host(knn_index *idx, int m, int K, const float *queries_host, float max_dist2,
@@ -3620,20 +3143,7 @@ extern "C" int knn_index_query_topk_large_masked_host(knn_index *idx, int m, int
             return fail(KNN_EHIP, "knn_index_query_topk_large_masked_host: D2H keys", hipGetErrorString(e));
         // (not declared waited: the buffers go back after the device-wide wait `stage` then makes itself, as the top-K's)
     }
-    for (size_t i = 0; i < mk; ++i) {
-        indices_host[i] = (int)(unsigned)(keys[i] & 0xFFFFFFFFull);
-        if (dist2_host) {
-            const unsigned hi = (unsigned)(keys[i] >> 32);
-            memcpy(&dist2_host[i], &hi, sizeof hi);
-        }
-    }
-    if (counts_host)
-        for (int j = 0; j < m; ++j) {   // padding is KNN_KEY_INIT; a real key is below it
-            int c = 0;
-            while (c < K && keys[(size_t)j * K + c] < kKeyInit)
-                ++c;
-            counts_host[j] = c;
-        }
+    unpack_topk(keys.data(), m, K, indices_host, dist2_host, counts_host);
     return KNN_OK;
 }
 
