@@ -801,6 +801,19 @@ int knn_index_last_stats(knn_index *idx, long long stats[4]);
  * [2] cells of the index, [3] rows of its largest cell. */
 int knn_index_debug_counters(knn_index *idx, long long out[4]);
 
+/* Test hook: what the match launch of the most recent cell-pruned batch on workspace `slot` read and wrote, copied to the host
+ * (waits for the device first).  what = 0 nothing (dims only), 1 the cells' list lengths (unsigned [ncells]; above cap: the list
+ * is cut short), 2 the lists (unsigned short [ncells][cap]: the first min(length, cap) entries of a row are the cell's queries,
+ * in the order of the block's queue), 3 the low pruning table (float [m_padded][low entries]), 4 the high one (float [high entries][m_padded]), 5 the
+ * smallest of every 64 consecutive low entries (float [low entries / 64][m_padded]), 6 Dup (float [m_padded]); m_padded = the
+ * batch's queries rounded up to 32.  At most `bytes` bytes are copied.  dims = {ncells, cap, low entries, high entries, queries
+ * the tables have room for, first cell code of the index}. */
+int knn_debug_cells_fetch(knn_index *idx, int slot, int what, void *out, long long bytes, long long dims[6]);
+/* Test hook (host arithmetic only, no GPU needed): the match kernel's two tests, by the kernel's own lines, on n cases of one
+ * high entry hi[i], one Dup dup[i] and 64 low entries lo[64 i .. 64 i + 63]: queued[i] = 1 if a block of those 64 cells takes the
+ * query into its queue (the test on the smallest low entry), listed[i] = how many of the 64 cells keep it on their list. */
+int knn_debug_match_tests(long long n, const float *lo, const float *hi, const float *dup, unsigned char *queued, unsigned char *listed);
+
 /* Test hook (host arithmetic only, no GPU needed): the number of GPUs a cudaCallback(k, m, n, ...) is split over on a
  * node with ndev visible devices — the reference's rule (core.cu:865-872) plus the library's cost model. */
 int knn_debug_shard_policy(int k, int m, long long n, int ndev);

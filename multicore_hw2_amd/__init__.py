@@ -26,7 +26,8 @@ __all__ = ["lib", "lib_path", "cudaCallback", "KnnIndex", "KnnGeom", "KnnError",
            "debug_self_plan", "debug_self_ranges",
            "count_within_each_c", "list_within_each_c", "self_count_within_each_c", "self_list_within_each_c",
            "count_within_each_host_c", "list_within_each_host_c", "keys_column_dist2_c", "keys_column_dist2", "debug_each_radius",
-           "self_count_within_routed_c", "self_list_within_routed_c", "self_list_within_routed_host_c", "debug_self_routed_plan"]
+           "self_count_within_routed_c", "self_list_within_routed_c", "self_list_within_routed_host_c", "debug_self_routed_plan",
+           "debug_match_tests"]
 
 KEY_INIT = 0x7F80000000000000
 
@@ -58,6 +59,7 @@ EXPORTED_SYMBOLS = [
     "knn_index_list_within_each_host", "knn_debug_each_radius",
     "knn_index_self_count_within_routed", "knn_index_self_list_within_routed", "knn_index_self_list_within_routed_host",
     "knn_debug_self_routed_plan",
+    "knn_debug_cells_fetch", "knn_debug_match_tests",
 ]
 TOPK_LARGE_MAX = 4096   # KNN_TOPK_LARGE_MAX
 QUERY_INIT_KEYS = 1   # KNN_QUERY_INIT_KEYS
@@ -816,6 +818,24 @@ def debug_each_radius(radius, cap):
     return bool(out[0]), float(out[1])
 
 
+def debug_match_tests(lo, hi, dup):
+    """knn_debug_match_tests: the match kernel's two tests through the kernel's own lines, on n cases of 64 low entries lo[n][64],
+    one high entry hi[n] and one Dup dup[n] -> (queued[n] bool: the block of those 64 cells queues the query on its smallest low
+    entry; listed[n]: how many of the 64 cells keep it on their list).  Host arithmetic; works without a GPU."""
+    import numpy as np
+    lo = np.ascontiguousarray(lo, dtype=np.float32)
+    hi = np.ascontiguousarray(hi, dtype=np.float32)
+    dup = np.ascontiguousarray(dup, dtype=np.float32)
+    n = hi.shape[0]
+    if lo.shape != (n, 64) or dup.shape != (n,):
+        raise ValueError("debug_match_tests: lo must be [n][64], hi and dup [n]")
+    queued, listed = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+    f = lib().knn_debug_match_tests
+    f.argtypes = [ctypes.c_longlong] + [ctypes.c_void_p] * 5
+    _check(f(n, lo.ctypes.data, hi.ctypes.data, dup.ctypes.data, queued.ctypes.data, listed.ctypes.data))
+    return queued.astype(bool), listed
+
+
 def counts_to_offsets_c():
     f = lib().knn_counts_to_offsets
     f.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
@@ -1375,6 +1395,32 @@ class KnnIndex:
         f.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong)]
         _check(f(self._h, out))
         return list(out)
+
+    def debug_cells_fetch(self, m, slot=0, tables=False):
+        """Test hook (knn_debug_cells_fetch): what the match launch of the last cell-pruned batch of m queries on `slot` wrote —
+        dict(ncells, cap, nl, nh, cell_base, counts[ncells], lists[ncells][cap]: the first min(count, cap) entries of a row are
+        the cell's queries) and, with tables, what it read: lo[m_padded][nl], hi[nh][m_padded], lo_min[nl / 64][m_padded],
+        dup[m_padded].  Waits for the device."""
+        import numpy as np
+        f = lib().knn_debug_cells_fetch
+        f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)]
+        dims = (ctypes.c_longlong * 6)()
+        _check(f(self._h, int(slot), 0, None, 0, dims))
+        ncells, cap, nl, nh, m_cap, cell_base = (int(v) for v in dims)
+        mp = (int(m) + 31) // 32 * 32
+        if mp > m_cap:
+            raise ValueError("debug_cells_fetch: the slot's tables are smaller than m")
+
+        def fetch(what, dtype, shape):
+            a = np.empty(shape, dtype=dtype)
+            _check(f(self._h, int(slot), what, a.ctypes.data, a.nbytes, dims))
+            return a
+        out = dict(ncells=ncells, cap=cap, nl=nl, nh=nh, cell_base=cell_base, counts=fetch(1, np.uint32, (ncells,)),
+                   lists=fetch(2, np.uint16, (ncells, cap)))
+        if tables:
+            out.update(lo=fetch(3, np.float32, (mp, nl)), hi=fetch(4, np.float32, (nh, mp)), lo_min=fetch(5, np.float32, (nl // 64, mp)),
+                       dup=fetch(6, np.float32, (mp,)))
+        return out
 
     def debug_filter_scores(self, m, queries_dev, scores_dev, qnorm_dev):
         """Test hook (knn_debug_filter_scores): returns the 8 bound constants."""

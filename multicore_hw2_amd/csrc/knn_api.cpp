@@ -2251,6 +2251,53 @@ int knn_index_debug_counters(knn_index *idx, long long out[4])
     return KNN_OK;
 }
 
+// Test hook: what the match launch of the most recent cell-pruned batch on `slot` read and wrote, copied to the host once the
+// device is idle.  what 0: nothing (dims only); 1 cell_counts, unsigned [ncells]; 2 the lists, unsigned short [ncells][cap] (the first
+// min(count, cap) entries of a row are its list); 3 the low table, 4 the high table, 5 the group minima, 6 Dup — floats, laid out
+// for the m_padded of that batch.  dims = {ncells, cap, 2^sa, entries of the high table, m_cap, cell_base}.  At most `bytes` bytes.
+int knn_debug_cells_fetch(knn_index *idx, int slot, int what, void *out, long long bytes, long long dims[6])
+{
+    if (!idx || slot < 0 || slot >= KNN_SLOTS || what < 0 || what > 6 || !dims || bytes < 0 || (what && !out))
+        return fail(KNN_EINVAL, "knn_debug_cells_fetch: bad arguments");
+    std::lock_guard<std::recursive_mutex> lock(idx->mu);
+    const CellIndex *c = idx->filter.cells;
+    const FilterWorkspace &w = idx->filter.ws[slot];
+    if (!c || !w.cell_counts || !w.cell_lists || !w.lo_min)
+        return fail(KNN_EINVAL, "knn_debug_cells_fetch: no cell-pruned batch has run on this slot");
+    const size_t nl = (size_t)1 << c->sa, nh = (c->ncells + nl - 1) >> c->sa, mc = (size_t)w.cell_m_cap;
+    const long long d[6] = {c->ncells, c->cap, (long long)nl, (long long)nh, (long long)mc, c->cell_base};
+    memcpy(dims, d, sizeof d);
+    const void *src[7] = {nullptr, w.cell_counts, w.cell_lists, w.lo_tab, w.hi_tab, w.lo_min, w.dup};
+    const size_t size[7] = {0, (size_t)c->ncells * sizeof(unsigned), (size_t)c->ncells * c->cap * sizeof(unsigned short), mc * nl * sizeof(float),
+                            mc * nh * sizeof(float), mc * (nl / 64) * sizeof(float), mc * sizeof(float)};
+    if (what) {
+        DeviceGuard guard(idx->device);
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemcpy(out, src[what], std::min(size[what], (size_t)bytes), hipMemcpyDeviceToHost));
+    }
+    return KNN_OK;
+}
+
+// Test hook (host arithmetic, no GPU): the match kernel's two tests (knn_cell_queued, knn_cell_listed: the kernel's own lines) on
+// `n` (block, query) cases — hi[i], dup[i] and 64 low entries lo[64 i ..].  queued[i] = the block's queue takes the query on the
+// smallest of its 64 low entries; listed[i] = how many of the 64 cells keep it on their list.
+int knn_debug_match_tests(long long n, const float *lo, const float *hi, const float *dup, unsigned char *queued, unsigned char *listed)
+{
+    if (n < 0 || !lo || !hi || !dup || !queued || !listed)
+        return fail(KNN_EINVAL, "knn_debug_match_tests: bad arguments");
+    for (long long i = 0; i < n; ++i) {
+        float lo_min = lo[64 * i];
+        unsigned cnt = 0;
+        for (int l = 0; l < 64; ++l) {
+            lo_min = fminf(lo_min, lo[64 * i + l]);
+            cnt += knn_cell_listed(lo[64 * i + l], hi[i], dup[i]) ? 1u : 0u;
+        }
+        queued[i] = knn_cell_queued(lo_min, hi[i], dup[i]) ? 1 : 0;
+        listed[i] = (unsigned char)cnt;
+    }
+    return KNN_OK;
+}
+
 int knn_debug_scan_plan(int num_cu, int blocks_per_cu, unsigned nitems, int m, long long out[8])
 {
     return knn_debug_scan_plan_ex(num_cu, blocks_per_cu, nitems, m, 0, out);

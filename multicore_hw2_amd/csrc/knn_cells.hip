@@ -864,16 +864,19 @@ __device__ __forceinline__ float min_tree16(const f16v &x, float seed)
 }
 
 // Cell-major matching: a block of 8 waves owns cells 64b .. 64b+63 (one high-table entry, 64 consecutive
-// low-table entries).  Pass 1 (queries on the lanes, an eighth of the batch per wave): which queries get past
-// the high table alone — about a third for uniform data — compacted into an LDS queue.  Pass 2 (cells on
-// the lanes, the queue cut into one run per wave): the low-table entry of each queued query, 16 loads in
-// flight per wave; survivors go to the cell's list at offsets prefix-summed over the waves.  cell_counts[c] = queries
+// low-table entries).  Pass 1 (queries on the lanes, an eighth of the batch per wave): which queries at least ONE of the
+// block's 64 cells will list — the list test (knn_cell_listed) on the smallest of the block's 64 low entries, which the prep
+// kernel left in lo_min[group][query]; fp32 addition does not decrease when an operand grows, so this queue is exactly the
+// union of the 64 lists (knn_cell_queued, tests/test_match_prefilter_logic.py) — compacted into an LDS queue: 153 of 1024
+// queries at C3 on uniform data, against 258 that get past the high table alone (what this pass queued before; a final list
+// holds 27).  Pass 2 (cells on the lanes, the queue cut into one run per wave): the low-table entry of each queued query, 24 loads
+// in flight per wave; survivors go to the cell's list at offsets prefix-summed over the waves.  cell_counts[c] = queries
 // that could not rule cell c out, lists[c][0..) = their numbers.  No global atomics: per-cell
 // appends with returning atomics ran at 22 per ns, 0.13 ms for this batch (tools/atomic_probe).
 #define CELL_MATCH_STAGED_CAP 640u
 template <int CELL_MATCH_WAVES>   // 8, or 16 for shards of few cells (one block per 64 cells: 128 blocks at 2^13 cells)
 __global__ __launch_bounds__(64 * CELL_MATCH_WAVES) void knn_cells_match_kernel(
-    const float *__restrict__ lo_tab, const float *__restrict__ hi_tab, const float *__restrict__ dup, int m,
+    const float *__restrict__ lo_tab, const float *__restrict__ hi_tab, const float *__restrict__ lo_min, const float *__restrict__ dup, int m,
     int m_padded, CellGeom g, unsigned ncells, unsigned cap, unsigned short *__restrict__ lists,
     unsigned *__restrict__ cell_counts, unsigned *__restrict__ ctl,
     unsigned stage)   // entries of a list assembled in LDS (<= cap; 0: none): the launch's dynamic LDS holds 64 x (stage + 2) of them
@@ -899,6 +902,7 @@ __global__ __launch_bounds__(64 * CELL_MATCH_WAVES) void knn_cells_match_kernel(
     const unsigned h = c0 >> g.sa;                      // block-uniform: nl >= 64
     const unsigned l = cell & (unsigned)(nl - 1);
     const float *__restrict__ hrow = hi_tab + (size_t)h * m_padded;
+    const float *__restrict__ mrow = lo_min + (size_t)((c0 & (unsigned)(nl - 1)) >> 6) * m_padded;   // block-uniform: the block's 64 low entries are one group
     if (threadIdx.x == 0)
         s_npass = 0u;
     __syncthreads();
@@ -906,17 +910,18 @@ __global__ __launch_bounds__(64 * CELL_MATCH_WAVES) void knn_cells_match_kernel(
         return;
     {   // pass 1: this wave's share of the batch (m <= 1024: 16 chunks of 64 queries over the waves)
         constexpr int U = 16 / CELL_MATCH_WAVES;
-        float hv[U], dq[U];
+        float hv[U], dq[U], lm[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int q = (u * CELL_MATCH_WAVES + wib) * 64 + lane;
             hv[u] = q < m ? hrow[q] : INFINITY;
             dq[u] = q < m ? dup[q] : -INFINITY;
+            lm[u] = q < m ? mrow[q] : INFINITY;
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int q = (u * CELL_MATCH_WAVES + wib) * 64 + lane;
-            const bool pass = q < m && !(hv[u] > dq[u]);
+            const bool pass = q < m && knn_cell_queued(lm[u], hv[u], dq[u]);
             const u64 mask = __ballot(pass);
             if (mask != 0ull) {   // wave-uniform
                 unsigned base = 0u;
@@ -939,10 +944,14 @@ __global__ __launch_bounds__(64 * CELL_MATCH_WAVES) void knn_cells_match_kernel(
     // pass 2: the queue in contiguous runs, one per wave (<= 1024 / WAVES entries); a lane keeps "my cell could not
     // rule entry j out" as bit j of a mask, the waves' counts are prefix-summed through LDS, and the second sweep
     // writes every survivor to its final place — no LDS atomics (16 waves adding to the same 64 counters cost
-    // more than the table loads at 2^13 cells, where a list holds ~125 of 1024 queries), lists in query order.
+    // more than the table loads at 2^13 cells, where a list holds ~125 of 1024 queries), lists in the queue's order (the
+    // waves' chunks of the batch in the order they reached s_npass, ascending inside a chunk).
     // (64 loads outstanding — a wave's whole run of the queue in one round trip instead of three — measured in round 4: 76-80
-    // registers instead of 55-58, C3 one batch at a time 0.150 -> 0.155 ms, pipelined 0.1195 -> 0.1235.  16 stays.)
-    constexpr int EPW = 1024 / CELL_MATCH_WAVES, INFLIGHT = 16;   // entries per wave; low-table loads outstanding
+    // registers instead of 55-58, C3 one batch at a time 0.150 -> 0.155 ms, pipelined 0.1195 -> 0.1235.  With the queue on the
+    // group minima a wave's run at C3 is 19.5 entries on average, 26 at most: 24 outstanding take it in one round trip where
+    // 16 need two, at the same 64 registers — C3 pipelined 0.1011-0.1022 ms with 16, 0.0995-0.1003 with 24, 0.0994-0.1002 with
+    // 28; 32 are 70 registers, three blocks per CU instead of four, 0.1017-0.1020.  profiles/r17_match_prefilter.txt)
+    constexpr int EPW = 1024 / CELL_MATCH_WAVES, INFLIGHT = 24;   // entries per wave; low-table loads outstanding
     const unsigned per = (npass + CELL_MATCH_WAVES - 1u) / CELL_MATCH_WAVES;
     const unsigned e_begin = min((unsigned)wib * per, npass), e_end = min(e_begin + per, npass);
     u64 keep[EPW / 64];
@@ -960,9 +969,8 @@ __global__ __launch_bounds__(64 * CELL_MATCH_WAVES) void knn_cells_match_kernel(
         for (int u = 0; u < INFLIGHT; ++u) {
             const unsigned e = e0 + (unsigned)u;
             if (e < e_end) {
-                const float lb = lo[u] + s_hv[e];
                 const unsigned j = e - e_begin;
-                if (!(lb > s_dq[e])) {
+                if (knn_cell_listed(lo[u], s_hv[e], s_dq[e])) {
 #pragma unroll
                     for (int w64 = 0; w64 < EPW / 64; ++w64)
                         if ((int)(j >> 6) == w64)
@@ -1198,7 +1206,7 @@ __global__ __launch_bounds__(64 * PW, KT == 1 && !CTR ? 4 : 3) void knn_cells_pr
     const float *__restrict__ Q, int m, int m_padded, CellGeom g, const float *__restrict__ bounds, double sigma2,
     const float *__restrict__ center, float sigma, const unsigned *__restrict__ tile_start, long long ntiles,
     const h8 *__restrict__ rf, const unsigned *__restrict__ rn2, SeedLayer layer, h8 *__restrict__ qfg, float *__restrict__ lo_tab,
-    float *__restrict__ hi_tab, float bmax, float nmax, float amax_limit, float *__restrict__ thr,
+    float *__restrict__ hi_tab, float *__restrict__ lo_min, float bmax, float nmax, float amax_limit, float *__restrict__ thr,
     float *__restrict__ dup_out, unsigned *__restrict__ ctl, unsigned *__restrict__ ctl_next,
     unsigned *__restrict__ counts, unsigned nlists, u64 *__restrict__ keys_init,
     int lo_by_entry,   // != 0: the low table as [entry][query] (what the self-listing scan reads: a cell's row is contiguous)
@@ -1219,7 +1227,7 @@ __global__ __launch_bounds__(64 * PW, KT == 1 ? 4 : 3) void knn_cells_prep_withi
     const float *__restrict__ Q, int m, int m_padded, CellGeom g, const float *__restrict__ bounds, double sigma2,
     const float *__restrict__ center, float sigma, const unsigned *__restrict__ tile_start, long long ntiles,
     const h8 *__restrict__ rf, const unsigned *__restrict__ rn2, SeedLayer layer, h8 *__restrict__ qfg, float *__restrict__ lo_tab,
-    float *__restrict__ hi_tab, float bmax, float nmax, float amax_limit, float *__restrict__ thr,
+    float *__restrict__ hi_tab, float *__restrict__ lo_min, float bmax, float nmax, float amax_limit, float *__restrict__ thr,
     float *__restrict__ dup_out, unsigned *__restrict__ ctl, unsigned *__restrict__ ctl_next,
     unsigned *__restrict__ counts, unsigned nlists, int lo_by_entry /* K */, float max_dist2)
 {
@@ -1239,7 +1247,7 @@ template <int PW, int SD, int KT>
 __global__ __launch_bounds__(64 * PW, KT == 1 ? 4 : 3) void knn_cells_prep_count_kernel(
     const float *__restrict__ Q, int m, int m_padded, CellGeom g, const float *__restrict__ bounds, double sigma2,
     const float *__restrict__ center, float sigma, const unsigned *__restrict__ tile_start, h8 *__restrict__ qfg,
-    float *__restrict__ lo_tab, float *__restrict__ hi_tab, float bmax, float nmax, float amax_limit, float *__restrict__ thr,
+    float *__restrict__ lo_tab, float *__restrict__ hi_tab, float *__restrict__ lo_min, float bmax, float nmax, float amax_limit, float *__restrict__ thr,
     float *__restrict__ dup_out, unsigned *__restrict__ ctl, unsigned *__restrict__ ctl_next, unsigned *__restrict__ counts,
     unsigned nlists, float max_dist2)
 {
@@ -1264,7 +1272,7 @@ template <int PW, int SD, int KT>
 __global__ __launch_bounds__(64 * PW, KT == 1 ? 4 : 3) void knn_cells_prep_each_kernel(
     const float *__restrict__ Q, int m, int m_padded, CellGeom g, const float *__restrict__ bounds, double sigma2,
     const float *__restrict__ center, float sigma, const unsigned *__restrict__ tile_start, h8 *__restrict__ qfg,
-    float *__restrict__ lo_tab, float *__restrict__ hi_tab, float bmax, float nmax, float amax_limit, float *__restrict__ thr,
+    float *__restrict__ lo_tab, float *__restrict__ hi_tab, float *__restrict__ lo_min, float bmax, float nmax, float amax_limit, float *__restrict__ thr,
     float *__restrict__ dup_out, unsigned *__restrict__ ctl, unsigned *__restrict__ ctl_next, unsigned *__restrict__ counts,
     unsigned nlists, const float *__restrict__ radii, float cap)
 {
@@ -2559,9 +2567,10 @@ void knn_cells_workspace_free(FilterWorkspace &w)
     (void)KNN_DEV_FREE(w.dup);
     (void)KNN_DEV_FREE(w.lo_tab);
     (void)KNN_DEV_FREE(w.hi_tab);
+    (void)KNN_DEV_FREE(w.lo_min);
     w.cell_counts = nullptr;
     w.cell_lists = nullptr;
-    w.dup = w.lo_tab = w.hi_tab = nullptr;
+    w.dup = w.lo_tab = w.hi_tab = w.lo_min = nullptr;
     w.cell_m_cap = 0;
 }
 
@@ -2631,7 +2640,7 @@ static CellKernel cells_prep_of()
                 hipLaunchKernelGGL((knn_cells_prep_kernel<PW, 2, KT, CTR, TK>), dim3((unsigned)b.m_padded), dim3(64 * PW), 0, b.s, b.q, b.m,
                                    b.m_padded, cell_geom_of(b.c, st.k), b.c.bounds, (double)st.sigma * (double)st.sigma, st.center, st.sigma,
                                    b.c.tile_start, st.ntiles, (const h8 *)st.ref_frags, st.ref_norms2, b.layer, (h8 *)b.w.qry_frags, b.w.lo_tab,
-                                   b.w.hi_tab, st.bmax, st.nmax, kAmaxLimit, b.w.thr, b.w.dup, b.w.ctl_cur, b.ctl_next, b.w.counts, b.w.nlists,
+                                   b.w.hi_tab, b.w.lo_min, st.bmax, st.nmax, kAmaxLimit, b.w.thr, b.w.dup, b.w.ctl_cur, b.ctl_next, b.w.counts, b.w.nlists,
                                    TK ? (u64 *)nullptr : b.keys_init, TK ? b.topk : b.p.self_lists ? 1 : 0,
                                    frames ? b.c.cell_frame : (const float *)nullptr, frames ? b.c.tile_cell : (const unsigned *)nullptr);
             },
@@ -2646,7 +2655,7 @@ static CellKernel cells_prep_within_of()
                 hipLaunchKernelGGL((knn_cells_prep_within_kernel<PW, 2, KT>), dim3((unsigned)b.m_padded), dim3(64 * PW), 0, b.s, b.q, b.m,
                                    b.m_padded, cell_geom_of(b.c, st.k), b.c.bounds, (double)st.sigma * (double)st.sigma, st.center, st.sigma,
                                    b.c.tile_start, st.ntiles, (const h8 *)st.ref_frags, st.ref_norms2, b.layer, (h8 *)b.w.qry_frags, b.w.lo_tab,
-                                   b.w.hi_tab, st.bmax, st.nmax, kAmaxLimit, b.w.thr, b.w.dup, b.w.ctl_cur, b.ctl_next, b.w.counts, b.w.nlists,
+                                   b.w.hi_tab, b.w.lo_min, st.bmax, st.nmax, kAmaxLimit, b.w.thr, b.w.dup, b.w.ctl_cur, b.ctl_next, b.w.counts, b.w.nlists,
                                    b.topk, b.max_dist2);
             },
             (const void *)knn_cells_prep_within_kernel<PW, 2, KT>};
@@ -2659,7 +2668,7 @@ static CellKernel cells_prep_count_of()
                 const FilterState &st = b.st;
                 hipLaunchKernelGGL((knn_cells_prep_count_kernel<PW, 2, KT>), dim3((unsigned)b.m_padded), dim3(64 * PW), 0, b.s, b.q, b.m,
                                    b.m_padded, cell_geom_of(b.c, st.k), b.c.bounds, (double)st.sigma * (double)st.sigma, st.center, st.sigma,
-                                   b.c.tile_start, (h8 *)b.w.qry_frags, b.w.lo_tab, b.w.hi_tab, st.bmax, st.nmax, kAmaxLimit, b.w.thr, b.w.dup,
+                                   b.c.tile_start, (h8 *)b.w.qry_frags, b.w.lo_tab, b.w.hi_tab, b.w.lo_min, st.bmax, st.nmax, kAmaxLimit, b.w.thr, b.w.dup,
                                    b.w.ctl_cur, b.ctl_next, b.w.counts, b.w.nlists, b.max_dist2);
             },
             (const void *)knn_cells_prep_count_kernel<PW, 2, KT>};
@@ -2672,7 +2681,7 @@ static CellKernel cells_prep_each_of()
                 const FilterState &st = b.st;
                 hipLaunchKernelGGL((knn_cells_prep_each_kernel<PW, 2, KT>), dim3((unsigned)b.m_padded), dim3(64 * PW), 0, b.s, b.q, b.m,
                                    b.m_padded, cell_geom_of(b.c, st.k), b.c.bounds, (double)st.sigma * (double)st.sigma, st.center, st.sigma,
-                                   b.c.tile_start, (h8 *)b.w.qry_frags, b.w.lo_tab, b.w.hi_tab, st.bmax, st.nmax, kAmaxLimit, b.w.thr, b.w.dup,
+                                   b.c.tile_start, (h8 *)b.w.qry_frags, b.w.lo_tab, b.w.hi_tab, b.w.lo_min, st.bmax, st.nmax, kAmaxLimit, b.w.thr, b.w.dup,
                                    b.w.ctl_cur, b.ctl_next, b.w.counts, b.w.nlists, b.radii, b.max_dist2);
             },
             (const void *)knn_cells_prep_each_kernel<PW, 2, KT>};
@@ -2706,7 +2715,7 @@ static CellKernel cells_match_of()
 {
     return {[](const CellBatch &b) {
                 hipLaunchKernelGGL(knn_cells_match_kernel<WAVES>, dim3(b.c.ncells / 64u), dim3(64 * WAVES), b.p.match_lds, b.s, b.w.lo_tab,
-                                   b.w.hi_tab, b.w.dup, b.m, b.m_padded, cell_geom_of(b.c, b.st.k), b.c.ncells, b.c.cap, b.w.cell_lists,
+                                   b.w.hi_tab, b.w.lo_min, b.w.dup, b.m, b.m_padded, cell_geom_of(b.c, b.st.k), b.c.ncells, b.c.cap, b.w.cell_lists,
                                    b.w.cell_counts, b.w.ctl_cur, b.p.stage);
             },
             (const void *)knn_cells_match_kernel<WAVES>};
@@ -2815,11 +2824,13 @@ static hipError_t ensure_cells_workspace(const FilterState &st,FilterWorkspace &
         (void)KNN_DEV_FREE(w.dup);
         (void)KNN_DEV_FREE(w.lo_tab);
         (void)KNN_DEV_FREE(w.hi_tab);
-        w.dup = w.lo_tab = w.hi_tab = nullptr;
+        (void)KNN_DEV_FREE(w.lo_min);
+        w.dup = w.lo_tab = w.hi_tab = w.lo_min = nullptr;
         w.cell_m_cap = 0;
         FTRY(KNN_DEV_ALLOC((void **)&w.dup, (size_t)m_padded * sizeof(float)));
         FTRY(KNN_DEV_ALLOC((void **)&w.lo_tab, (size_t)m_padded * ((size_t)1 << c.sa) * sizeof(float)));
         FTRY(KNN_DEV_ALLOC((void **)&w.hi_tab, (size_t)m_padded * (size_t)((c.ncells + (1u << c.sa) - 1u) >> c.sa) * sizeof(float)));
+        FTRY(KNN_DEV_ALLOC((void **)&w.lo_min, (size_t)m_padded * (((size_t)1 << c.sa) / 64u) * sizeof(float)));   // (2^sa >= 64)
         w.cell_m_cap = m_padded;
     }
     FTRY(cells_lds_limit(scan.fn, p.scan_lds_limit));

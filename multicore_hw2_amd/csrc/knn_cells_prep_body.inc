@@ -236,6 +236,17 @@
             else
                 hi_tab[(size_t)(e - nl) * m_padded + qi] = v;
         }
+        // the smallest of a group of 64 low entries AS STORED (no new sum), [group][query]: the wave's 64 entries are one group —
+        // the 64 cells of one block of the match kernel, whose pass 1 queues the query iff that smallest entry passes.  Lists made
+        // by the scan's own waves (1-NN, lo_by_entry) have no match launch and no reader of it.
+        if (low && (TK || !lo_by_entry)) {   // wave-uniform
+            float vmin = v;                  // (nl is a multiple of 64: every lane of a low wave holds an entry)
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1)
+                vmin = fminf(vmin, __shfl_xor(vmin, off, KNN_WAVE));
+            if (lane == 0)
+                lo_min[(size_t)(e0 >> 6) * m_padded + qi] = vmin;
+        }
     }
     // ---- seed scores.  A wave's seed tiles — those of its NS cells, a cell of many tiles sampled (every stride-th,
     // at most CELL_SEED_MAX_TILES: any real row's score bounds the answer, and one query per MFMA against the thousands of

@@ -434,6 +434,7 @@ struct FilterWorkspace {
     unsigned short *cell_lists = nullptr;  // device [ncells][cap]
     float *dup = nullptr;                  // device [m_cap]: largest scaled squared distance a candidate can have
     float *lo_tab = nullptr, *hi_tab = nullptr;  // device [m_cap][2^sa], [2^(bits-sa)][m_cap]
+    float *lo_min = nullptr;               // device [2^sa / 64][m_cap]: the smallest of every 64 consecutive entries of a query's low table
     int cell_m_cap = 0;
 };
 
@@ -623,6 +624,19 @@ hipError_t knn_cells_stage(CellStaging &stg, const CellIndex &plan, CellBuild ho
 hipError_t knn_cells_fast_scatter(CellIndex &c, int k, const float *r_dev, long long row0, long long row1, hipStream_t s);
 hipError_t knn_cells_fast_finish(CellIndex &c, unsigned *counts, hipStream_t s);
 #endif
+// The two tests of knn_cells_match_kernel, fp32 with one rounding each.  knn_cell_listed: query q stays on cell (h, l)'s list —
+// its lower bound lo[q][l] + hi[h][q] is not above Dup_q.  knn_cell_queued: q enters the queue of a block of 64 cells, lo_min the
+// smallest of the block's 64 low entries as stored.  fl(a + b) does not decrease when b grows, so the smallest entry gives the
+// smallest of the 64 sums: queued <=> listed for at least one cell of the block (tests/test_match_prefilter_logic.py).
+__host__ __device__ static inline bool knn_cell_listed(float lo, float hi, float dup)
+{
+    return !(lo + hi > dup);
+}
+__host__ __device__ static inline bool knn_cell_queued(float lo_min, float hi, float dup)
+{
+    return knn_cell_listed(lo_min, hi, dup);
+}
+
 // Sizes of one scan launch of the cell-pruned path (knn_cells.hip; host arithmetic only).
 struct CellScanPlan {
     unsigned blocks = 0, waves = 0, nlists = 0, slice = 0, ovf_base = 0, ovf_cap = 0;
