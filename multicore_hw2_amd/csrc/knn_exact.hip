@@ -1475,10 +1475,13 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_count_commit_kernel(const unsig
         counts[j] += scratch[j];
 }
 
-// The cell-pruned count's re-rank (knn_cells_query_count): every row of every record with v0's arithmetic through perm, as
-// knn_topk_rerank_gated_kernel walks them — one block per list, positions whose layout norm is +INF (padding, rows outside the
-// robust box) skipped —, and a row within the radius adds one to its query's scratch count.  The 16 rows of a record sit on 16
-// neighbouring lanes and belong to one query: their hits are summed from one ballot and the record's first lane adds them.
+// The cell-pruned count's re-rank and out-of-box rows, scalar radius: knn_rec_count_rerank_body.inc, knn_rec_count_outlier_body.inc
+// (the walks the each-forms, knn_each.hip, and the self forms, knn_self_routed.hip, include too).  What a scalar form lacks:
+#define KNN_REC_SCALAR_FORM                  \
+    constexpr int FORM = KNN_REC_SCALAR;     \
+    constexpr const float *radii = nullptr;  \
+    constexpr unsigned first = 0u;           \
+    const float cap = max_dist2
 __global__ __launch_bounds__(KNN_BLOCK) void knn_count_rerank_kernel(const float *__restrict__ Q, const float *__restrict__ R, int k,
                                                                     long long n, const u64 *__restrict__ rec,
                                                                     const unsigned *__restrict__ counts, unsigned nlists,
@@ -1486,63 +1489,18 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_count_rerank_kernel(const float
                                                                     const unsigned *__restrict__ perm, const float *__restrict__ norms,
                                                                     float max_dist2, unsigned *__restrict__ qcount)
 {
-    const unsigned list_id = blockIdx.x;
-    if (ctl[KNN_CTL_FALLBACK] != 0u || list_id >= nlists)
-        return;
-    const unsigned want = counts[list_id];
-    const unsigned nrec = min(want, slice);
-    if (threadIdx.x == 0 && want > slice)
-        ctl[KNN_CTL_FALLBACK] = 1u;
-    const u64 *__restrict__ list = rec + (size_t)list_id * slice;
-    const unsigned lane = threadIdx.x & 63u;
-    // (every wave runs the same number of rounds: the ballot below is taken by all 64 lanes)
-    for (unsigned c0 = 0u; c0 < nrec * 16u; c0 += KNN_BLOCK) {
-        const unsigned c = c0 + threadIdx.x;
-        bool hit = false;
-        unsigned qi = 0u;
-        if (c < nrec * 16u) {
-            const u64 e = list[c >> 4];
-            const unsigned lo = (unsigned)e, reg = c & 15u;
-            const long long pos = (long long)(lo >> 1) * 32 + 8 * (reg >> 2) + 4 * (lo & 1u) + (reg & 3u);   // (rerank_pair's)
-            const unsigned rmask = pos < n && norms[pos] < INFINITY ? 0xFFFFu : 0u;
-            const u64 key = rerank_pair<0>(Q, R, k, n, 0ll, e, reg, rmask, 0u, perm, qi);   // ~0: nothing there, or not finite
-            hit = key != ~0ull && __uint_as_float((unsigned)(key >> 32)) <= max_dist2;
-        }
-        const u64 hits = __ballot(hit);
-        const unsigned mine = (unsigned)__popcll((hits >> (lane & 48u)) & 0xFFFFull);
-        if ((lane & 15u) == 0u && mine != 0u)
-            atomicAdd(&qcount[qi], mine);
-    }
+    KNN_REC_SCALAR_FORM;
+#include "knn_rec_count_rerank_body.inc"
 }
 
-// Rows outside the filter's robust box never enter the scan: every (query, listed row) pair once, with v0's arithmetic.
-// grid (row blocks, queries); one add per wave.
 __global__ __launch_bounds__(KNN_BLOCK) void knn_count_outlier_kernel(const float *__restrict__ Q, const float *__restrict__ R, int k,
                                                                      unsigned count, const unsigned *__restrict__ list,
                                                                      const unsigned *__restrict__ ctl, float max_dist2,
                                                                      unsigned *__restrict__ qcount)
 {
 #pragma clang fp contract(off)
-    if (ctl[KNN_CTL_FALLBACK] != 0u)
-        return;
-    const unsigned q = blockIdx.y;
-    const float *__restrict__ qp = Q + (size_t)q * k;
-    unsigned cnt = 0u;
-    for (unsigned j = blockIdx.x * KNN_BLOCK + threadIdx.x; j < count; j += gridDim.x * KNN_BLOCK) {
-        const float *__restrict__ r = R + (size_t)list[j] * k;
-        float acc = 0.0f;
-        for (int d = 0; d < k; ++d) {
-            const float diff = qp[d] - r[d];
-            const float sq = diff * diff;
-            acc = acc + sq;
-        }
-        cnt += acc < INFINITY && acc <= max_dist2 ? 1u : 0u;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        cnt += (unsigned)__shfl_xor((int)cnt, off, KNN_WAVE);
-    if ((threadIdx.x & 63u) == 0u && cnt != 0u)
-        atomicAdd(&qcount[q], cnt);
+    KNN_REC_SCALAR_FORM;
+#include "knn_rec_count_outlier_body.inc"
 }
 
 long long knn_count_slices(int mc, long long n, int num_cu)
@@ -1616,24 +1574,17 @@ hipError_t knn_count_records_finish(const CountCall &c, const TopkRecords &rs, u
         return knn_count_self_records_finish(c, rs, qcount);   // (knn_self_routed.hip)
     if (c.radii)
         return knn_count_each_records_finish(c, rs, qcount);   // (knn_each.hip)
-    if (rs.nlists)
-        hipLaunchKernelGGL(knn_count_rerank_kernel, dim3(rs.nlists), dim3(KNN_BLOCK), 0, s, c.q, c.r, c.k, rs.positions, rs.rec, rs.counts,
-                           rs.nlists, rs.slice, rs.ctl, rs.perm, rs.pos_norms, c.max_dist2, qcount);
-    if (rs.ovf_rec && rs.ovf_count)   // the shared overflow area as a list of one (its `want > slice` rule raises FALLBACK when over-full)
-        hipLaunchKernelGGL(knn_count_rerank_kernel, dim3(1), dim3(KNN_BLOCK), 0, s, c.q, c.r, c.k, rs.positions, rs.ovf_rec, rs.ovf_count,
-                           1u, rs.ovf_slice, rs.ctl, rs.perm, rs.pos_norms, c.max_dist2, qcount);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        return e;
-    if (rs.n_outliers) {
-        const unsigned gx = (rs.n_outliers + KNN_BLOCK - 1) / KNN_BLOCK < 64u ? (rs.n_outliers + KNN_BLOCK - 1) / KNN_BLOCK : 64u;
-        hipLaunchKernelGGL(knn_count_outlier_kernel, dim3(gx, (unsigned)c.m), dim3(KNN_BLOCK), 0, s, c.q, c.r, c.k, rs.n_outliers,
-                           rs.outliers, (const unsigned *)rs.ctl, c.max_dist2, qcount);
-        e = hipGetLastError();
-        if (e != hipSuccess)
-            return e;
-    }
-    return knn_count_commit_launch(c.m, qcount, c.counts, rs.ctl + KNN_CTL_FALLBACK, s);
+    return knn_records_finish_launches(
+        rs, c.m,
+        [&](dim3 grid, const u64 *rec, const unsigned *counts, unsigned nlists, unsigned slice) {
+            hipLaunchKernelGGL(knn_count_rerank_kernel, grid, dim3(KNN_BLOCK), 0, s, c.q, c.r, c.k, rs.positions, rec, counts, nlists, slice,
+                               rs.ctl, rs.perm, rs.pos_norms, c.max_dist2, qcount);
+        },
+        [&](dim3 grid) {
+            hipLaunchKernelGGL(knn_count_outlier_kernel, grid, dim3(KNN_BLOCK), 0, s, c.q, c.r, c.k, rs.n_outliers, rs.outliers,
+                               (const unsigned *)rs.ctl, c.max_dist2, qcount);
+        },
+        [&] { return knn_count_commit_launch(c.m, qcount, c.counts, rs.ctl + KNN_CTL_FALLBACK, s); });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1725,8 +1676,7 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_list_commit_kernel(const unsign
         fill[j] = cursor[j];
 }
 
-// The cell-pruned list's re-rank: knn_count_rerank_kernel's walk (one block per list, positions whose layout norm is +INF skipped),
-// and a row within the radius reserves in its query's scratch cursor and stores its key.  base / gids as in the exact list.
+// The cell-pruned list's re-rank and out-of-box rows, scalar radius: knn_rec_list_rerank_body.inc, knn_rec_list_outlier_body.inc.
 __global__ __launch_bounds__(KNN_BLOCK) void knn_list_rerank_kernel(const float *__restrict__ Q, const float *__restrict__ R, int k,
                                                                    long long n, long long base, const u64 *__restrict__ rec,
                                                                    const unsigned *__restrict__ counts, unsigned nlists,
@@ -1736,31 +1686,10 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_list_rerank_kernel(const float 
                                                                    const u64 *__restrict__ offsets, unsigned *__restrict__ cursor,
                                                                    u64 *__restrict__ keys)
 {
-    const unsigned list_id = blockIdx.x;
-    if (ctl[KNN_CTL_FALLBACK] != 0u || list_id >= nlists)
-        return;
-    const unsigned want = counts[list_id];
-    const unsigned nrec = min(want, slice);
-    if (threadIdx.x == 0 && want > slice)
-        ctl[KNN_CTL_FALLBACK] = 1u;
-    const u64 *__restrict__ list = rec + (size_t)list_id * slice;
-    for (unsigned c = threadIdx.x; c < nrec * 16u; c += KNN_BLOCK) {
-        unsigned qi = 0u;
-        const u64 e = list[c >> 4];
-        const unsigned lo = (unsigned)e, reg = c & 15u;
-        const long long pos = (long long)(lo >> 1) * 32 + 8 * (reg >> 2) + 4 * (lo & 1u) + (reg & 3u);   // (rerank_pair's)
-        const unsigned rmask = pos < n && norms[pos] < INFINITY ? 0xFFFFu : 0u;
-        const u64 key = rerank_pair<0>(Q, R, k, n, base, e, reg, rmask, 0u, perm, qi);   // ~0: nothing there, or not finite
-        if (key != ~0ull && __uint_as_float((unsigned)(key >> 32)) <= max_dist2) {
-            u64 off;
-            const unsigned room = list_room(offsets, qi, off);
-            list_put(&cursor[qi], keys, off, room, gids ? (key & 0xFFFFFFFF00000000ull) | (u64)gids[(unsigned)key] : key);
-        }
-    }
+    KNN_REC_SCALAR_FORM;
+#include "knn_rec_list_rerank_body.inc"
 }
 
-// Rows outside the filter's robust box never enter the scan: every (query, listed row) pair once, with v0's arithmetic.
-// grid (row blocks, queries).
 __global__ __launch_bounds__(KNN_BLOCK) void knn_list_outlier_kernel(const float *__restrict__ Q, const float *__restrict__ R, int k,
                                                                     unsigned count, long long base, const unsigned *__restrict__ list,
                                                                     const unsigned *__restrict__ ctl, float max_dist2,
@@ -1768,25 +1697,10 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_list_outlier_kernel(const float
                                                                     unsigned *__restrict__ cursor, u64 *__restrict__ keys)
 {
 #pragma clang fp contract(off)
-    if (ctl[KNN_CTL_FALLBACK] != 0u)
-        return;
-    const unsigned q = blockIdx.y;
-    const float *__restrict__ qp = Q + (size_t)q * k;
-    u64 off;
-    const unsigned room = list_room(offsets, q, off);
-    for (unsigned j = blockIdx.x * KNN_BLOCK + threadIdx.x; j < count; j += gridDim.x * KNN_BLOCK) {
-        const unsigned row = list[j];
-        const float *__restrict__ r = R + (size_t)row * k;
-        float acc = 0.0f;
-        for (int d = 0; d < k; ++d) {
-            const float diff = qp[d] - r[d];
-            const float sq = diff * diff;
-            acc = acc + sq;
-        }
-        if (acc < INFINITY && acc <= max_dist2)
-            list_put(&cursor[q], keys, off, room, pack_key(acc, gids ? gids[row] : (unsigned)(base + (long long)row)));
-    }
+    KNN_REC_SCALAR_FORM;
+#include "knn_rec_list_outlier_body.inc"
 }
+#undef KNN_REC_SCALAR_FORM
 
 // offsets[0] = 0, offsets[j + 1] = offsets[j] + counts[j]: ONE block walks the counts in chunks of 8 per thread and carries a 64-bit
 // running sum from chunk to chunk (m is small next to n: no multi-block scan).  Per chunk: a thread sums its 8 counts, the waves
@@ -1918,24 +1832,17 @@ hipError_t knn_list_records_finish(const ListCall &c, const TopkRecords &rs)
         return knn_list_self_records_finish(c, rs);   // (knn_self_routed.hip)
     if (c.radii)
         return knn_list_each_records_finish(c, rs);   // (knn_each.hip)
-    if (rs.nlists)
-        hipLaunchKernelGGL(knn_list_rerank_kernel, dim3(rs.nlists), dim3(KNN_BLOCK), 0, s, c.q, c.r, c.k, rs.positions, c.base, rs.rec,
-                           rs.counts, rs.nlists, rs.slice, rs.ctl, rs.perm, rs.pos_norms, c.max_dist2, c.gids, c.offsets, c.scratch, c.keys);
-    if (rs.ovf_rec && rs.ovf_count)   // the shared overflow area as a list of one (its `want > slice` rule raises FALLBACK when over-full)
-        hipLaunchKernelGGL(knn_list_rerank_kernel, dim3(1), dim3(KNN_BLOCK), 0, s, c.q, c.r, c.k, rs.positions, c.base, rs.ovf_rec,
-                           rs.ovf_count, 1u, rs.ovf_slice, rs.ctl, rs.perm, rs.pos_norms, c.max_dist2, c.gids, c.offsets, c.scratch, c.keys);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        return e;
-    if (rs.n_outliers) {
-        const unsigned gx = (rs.n_outliers + KNN_BLOCK - 1) / KNN_BLOCK < 64u ? (rs.n_outliers + KNN_BLOCK - 1) / KNN_BLOCK : 64u;
-        hipLaunchKernelGGL(knn_list_outlier_kernel, dim3(gx, (unsigned)c.m), dim3(KNN_BLOCK), 0, s, c.q, c.r, c.k, rs.n_outliers, c.base,
-                           rs.outliers, (const unsigned *)rs.ctl, c.max_dist2, c.gids, c.offsets, c.scratch, c.keys);
-        e = hipGetLastError();
-        if (e != hipSuccess)
-            return e;
-    }
-    return knn_list_commit_launch(c.m, c.scratch, c.fill, rs.ctl + KNN_CTL_FALLBACK, s);
+    return knn_records_finish_launches(
+        rs, c.m,
+        [&](dim3 grid, const u64 *rec, const unsigned *counts, unsigned nlists, unsigned slice) {
+            hipLaunchKernelGGL(knn_list_rerank_kernel, grid, dim3(KNN_BLOCK), 0, s, c.q, c.r, c.k, rs.positions, c.base, rec, counts, nlists,
+                               slice, rs.ctl, rs.perm, rs.pos_norms, c.max_dist2, c.gids, c.offsets, c.scratch, c.keys);
+        },
+        [&](dim3 grid) {
+            hipLaunchKernelGGL(knn_list_outlier_kernel, grid, dim3(KNN_BLOCK), 0, s, c.q, c.r, c.k, rs.n_outliers, c.base, rs.outliers,
+                               (const unsigned *)rs.ctl, c.max_dist2, c.gids, c.offsets, c.scratch, c.keys);
+        },
+        [&] { return knn_list_commit_launch(c.m, c.scratch, c.fill, rs.ctl + KNN_CTL_FALLBACK, s); });
 }
 
 hipError_t knn_counts_to_offsets_launch(const unsigned *counts, int m, u64 *offsets, hipStream_t s)

@@ -141,6 +141,37 @@ __device__ __forceinline__ u64 rerank_pair(const float *__restrict__ Q, const fl
     return ~0ull;
 }
 
+// ---- a cell-pruned count or list pass behind its record-only scan: records and out-of-box rows -> hits ------------------------
+// Four walks — count re-rank, count outlier, list re-rank, list outlier: knn_rec_*_body.inc — in three forms each, kernels of
+// their own that include the walk with FORM fixed: the scalar radius (knn_exact.hip), a radius per query (knn_each.hip: one more
+// compare, radii[query] under cap), the shard's own rows (knn_self_routed.hip: radii nullable, and the query's own LOCAL row
+// dropped).  A hit: E finite, E <= the query's radius and E <= cap, fp32 compares with equality inside; a NaN or negative radius
+// fails the first for every row.
+enum { KNN_REC_SCALAR = 0, KNN_REC_EACH = 1, KNN_REC_SELF = 2 };
+#define KNN_REC_RADIUS(qv) (FORM == KNN_REC_SCALAR ? cap : FORM == KNN_REC_EACH ? radii[qv] : radii ? radii[qv] : cap)
+
+// The launches of such a pass, in order: the re-rank of the nlists per-list slices, the re-rank of the shared overflow area as a
+// list of one (its `want > slice` rule raises FALLBACK when over-full), the outlier grid (min(ceil(n_outliers / KNN_BLOCK), 64), m),
+// then the commit gated on FALLBACK.  rerank(grid, rec, counts, nlists, slice), outlier(grid) and commit() issue the form's kernels.
+template <class Rerank, class Outlier, class Commit>
+static inline hipError_t knn_records_finish_launches(const TopkRecords &rs, int m, Rerank rerank, Outlier outlier, Commit commit)
+{
+    if (rs.nlists)
+        rerank(dim3(rs.nlists), rs.rec, rs.counts, rs.nlists, rs.slice);
+    if (rs.ovf_rec && rs.ovf_count)
+        rerank(dim3(1), rs.ovf_rec, rs.ovf_count, 1u, rs.ovf_slice);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess)
+        return e;
+    if (rs.n_outliers) {
+        const unsigned gx = (rs.n_outliers + KNN_BLOCK - 1) / KNN_BLOCK < 64u ? (rs.n_outliers + KNN_BLOCK - 1) / KNN_BLOCK : 64u;
+        outlier(dim3(gx, (unsigned)m));
+        e = hipGetLastError();
+        if (e != hipSuccess)
+            return e;
+    }
+    return commit();
+}
 
 // The body of knn_exact_qreg (knn_exact.hip): block (bx of gx, by) scans slices bx, bx + gx, ... of refs_per_block rows for
 // the queries of group `by`.  Shared with the cell-pruned path's tail kernel, which runs it when a batch has a query nothing

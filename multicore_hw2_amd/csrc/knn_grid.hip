@@ -430,16 +430,18 @@ __global__ __launch_bounds__(GRID_BLOCK) void knn_grid_within_kernel(const float
 #include "knn_grid_topk_body.inc"
 }
 
-// ---- counts within a radius (KNN_QUERY_COUNT_GRID; knn_index_count_within) ------------------------
-// One wave per query, the 1-NN kernel's walk: lanes take the cells of ring r and count the rows whose v0 distance E is finite and
-// <= max_dist2 (fp32 compare, equality inside) in a register each.  After ring r the wave stops when the block of rings 0..r is
-// the whole grid, or when max_dist2 < lb^2 (1 - 1e-6) — the radius clause of knn_grid_within_kernel with its argument: every
-// unseen row's computed distance is strictly above that bound, so none is within the radius; the test is wave-uniform (the
-// query, its cell and r decide it).  Every cell of rings 0..r is visited once (grid_ring_cell: a position of the (2r+1)^K block
-// belongs to exactly one ring), every row sits in one cell: no row is counted twice.  One wave reduction at the end, lane 0 stores
-// the query's count to out[q] — the slot's scratch, never the caller's counts: a batch that gives up is answered again by the
-// exact count behind this kernel, and knn_count_commit_kernel adds the scratch only when nobody gave up.  Past rmax rings the
-// query raises the give-up word (the slot's two words alternate as in the other grid kernels).  No LDS, no block barrier.
+// ---- counts and lists within a radius (KNN_QUERY_COUNT_GRID) ---------------------------------------
+// Six entry points of one walk, knn_grid_radius_body.inc (the description is there): each fixes the switches LIST, EACH and SELF
+// and names, as null or zero constants, the arguments it does not take.  (A body file and not a function template, as the top-K
+// kernels above: every form keeps its argument list, its name and its code.)
+#define GRID_RADIUS_NO_LIST /* a count form reserves and stores nothing */   \
+    constexpr long long base = 0;                                            \
+    constexpr const u64 *offsets = nullptr;                                  \
+    constexpr unsigned *cursor = nullptr;                                    \
+    constexpr u64 *keys = nullptr
+#define GRID_RADIUS_NO_SELF /* no own row to drop */ constexpr unsigned first = 0u
+
+// knn_index_count_within
 template <int KD>
 __global__ __launch_bounds__(GRID_BLOCK) void knn_grid_count_kernel(const float *__restrict__ Q, int m, GridGeom gg,
                                                                     const unsigned *__restrict__ start,
@@ -448,86 +450,16 @@ __global__ __launch_bounds__(GRID_BLOCK) void knn_grid_count_kernel(const float 
                                                                     unsigned *__restrict__ giveup_next, float max_dist2)
 {
 #pragma clang fp contract(off)
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        *giveup_next = 0u;   // (the slot's other word, as the 1-NN kernel)
-    const int lane = threadIdx.x & 63;
-    const int qi = blockIdx.x * (GRID_BLOCK / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    if (qi >= m)
-        return;
-    float q[4] = {0.f, 0.f, 0.f, 0.f};
-    bool finite = true;
-#pragma unroll
-    for (int d = 0; d < KD; ++d) {
-        q[d] = Q[(size_t)qi * KD + d];
-        finite = finite && fabsf(q[d]) < INFINITY;
-    }
-    if (!finite) {   // every distance is NaN or +INF: no row counts (and nothing to give up on)
-        if (lane == 0)
-            out[qi] = 0u;
-        return;
-    }
-    int c[4];
-    (void)grid_cell_of(gg, q, c);
-    int gmax = 1;
-#pragma unroll
-    for (int d = 0; d < KD; ++d)
-        gmax = gg.g[d] > gmax ? gg.g[d] : gmax;
-
-    unsigned cnt = 0u;
-    bool done = false;
-    bool first = true;   // (rings 0 and 1 together, as the 1-NN kernel)
-    for (int r = gmax > 1 ? 1 : 0; r < gmax && r <= rmax; ++r) {
-        const int side = 2 * r + 1;
-        int total = 1;
-#pragma unroll
-        for (int d = 0; d < KD; ++d)
-            total *= side;
-        for (int idx = lane; idx < total; idx += KNN_WAVE) {
-            unsigned cell;
-            if (!grid_ring_cell<KD>(gg, c, r, side, idx, first, &cell))
-                continue;
-            const unsigned p0 = start[cell], p1 = start[cell + 1];
-            for (unsigned p = p0; p < p1; ++p) {
-                const f4g x = pts[p];
-                float acc = 0.0f;
-#pragma unroll
-                for (int d = 0; d < KD; ++d) {
-                    const float diff = q[d] - x[d];   // v0: search - reference, squared, summed in order
-                    const float sq = diff * diff;
-                    acc = acc + sq;
-                }
-                cnt += acc < INFINITY && acc <= max_dist2 ? 1u : 0u;
-            }
-        }
-        first = false;
-        bool covers_all;
-        const double lb = grid_face_bound<KD>(gg, c, q, r, &covers_all);
-        if (covers_all) {
-            done = true;
-            break;
-        }
-        if (lb > 0.0 && (double)max_dist2 < lb * lb * (1.0 - 1e-6)) {   // no unseen row is within the radius
-            done = true;
-            break;
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        cnt += (unsigned)__shfl_xor((int)cnt, off, KNN_WAVE);
-    if (lane == 0) {
-        out[qi] = cnt;
-        if (!done && gmax > rmax + 1)
-            *giveup = 1u;      // benign race: every writer stores 1
-    }
+    constexpr bool LIST = false, EACH = false, SELF = false;
+    constexpr const unsigned *orig = nullptr;
+    constexpr const float *radii = nullptr;
+    const float cap = max_dist2;
+    GRID_RADIUS_NO_LIST;
+    GRID_RADIUS_NO_SELF;
+#include "knn_grid_radius_body.inc"
 }
 
-// ---- lists within a radius (KNN_QUERY_COUNT_GRID; knn_index_list_within) --------------------------
-// knn_grid_count_kernel's walk and stop rules; a row within the radius reserves place p of its query's segment with one atomicAdd on
-// cursor[q] and, when p is below the segment's room, stores its key — the distance's bits and base + orig[position] — at
-// keys[offsets[q] + p].  cursor is the slot's scratch, on entry a copy of the caller's fill, never the caller's fill itself: a batch
-// that gives up is answered again by the exact list behind this kernel from the untouched fill, over the same places, and
-// knn_list_commit_kernel copies the cursor to fill only when nobody gave up.  Every cell of rings 0..r is visited once and every
-// row sits in one cell: no row is listed twice.  A query with a non-finite coordinate has no hit: its cursor stays where it was.
+// knn_index_list_within
 template <int KD>
 __global__ __launch_bounds__(GRID_BLOCK) void knn_grid_list_kernel(const float *__restrict__ Q, int m, GridGeom gg,
                                                                    const unsigned *__restrict__ start,
@@ -538,82 +470,15 @@ __global__ __launch_bounds__(GRID_BLOCK) void knn_grid_list_kernel(const float *
                                                                    unsigned *__restrict__ giveup_next, float max_dist2)
 {
 #pragma clang fp contract(off)
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        *giveup_next = 0u;   // (the slot's other word, as the 1-NN kernel)
-    const int lane = threadIdx.x & 63;
-    const int qi = blockIdx.x * (GRID_BLOCK / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    if (qi >= m)
-        return;
-    float q[4] = {0.f, 0.f, 0.f, 0.f};
-    bool finite = true;
-#pragma unroll
-    for (int d = 0; d < KD; ++d) {
-        q[d] = Q[(size_t)qi * KD + d];
-        finite = finite && fabsf(q[d]) < INFINITY;
-    }
-    if (!finite)   // every distance is NaN or +INF: no row is a hit (and nothing to give up on)
-        return;
-    int c[4];
-    (void)grid_cell_of(gg, q, c);
-    int gmax = 1;
-#pragma unroll
-    for (int d = 0; d < KD; ++d)
-        gmax = gg.g[d] > gmax ? gg.g[d] : gmax;
-    const u64 off = offsets[qi], end = offsets[qi + 1];
-    const u64 room64 = end > off ? end - off : 0ull;
-    const unsigned room = room64 < 0xFFFFFFFFull ? (unsigned)room64 : 0xFFFFFFFFu;   // (the cursor is 32-bit)
-
-    bool done = false;
-    bool first = true;   // (rings 0 and 1 together, as the 1-NN kernel)
-    for (int r = gmax > 1 ? 1 : 0; r < gmax && r <= rmax; ++r) {
-        const int side = 2 * r + 1;
-        int total = 1;
-#pragma unroll
-        for (int d = 0; d < KD; ++d)
-            total *= side;
-        for (int idx = lane; idx < total; idx += KNN_WAVE) {
-            unsigned cell;
-            if (!grid_ring_cell<KD>(gg, c, r, side, idx, first, &cell))
-                continue;
-            const unsigned p0 = start[cell], p1 = start[cell + 1];
-            for (unsigned p = p0; p < p1; ++p) {
-                const f4g x = pts[p];
-                float acc = 0.0f;
-#pragma unroll
-                for (int d = 0; d < KD; ++d) {
-                    const float diff = q[d] - x[d];   // v0: search - reference, squared, summed in order
-                    const float sq = diff * diff;
-                    acc = acc + sq;
-                }
-                if (acc < INFINITY && acc <= max_dist2) {
-                    const unsigned place = atomicAdd(&cursor[qi], 1u);
-                    if (place < room)
-                        keys[off + place] = ((u64)__float_as_uint(acc) << 32) | (u64)(unsigned)(base + (long long)orig[p]);
-                }
-            }
-        }
-        first = false;
-        bool covers_all;
-        const double lb = grid_face_bound<KD>(gg, c, q, r, &covers_all);
-        if (covers_all) {
-            done = true;
-            break;
-        }
-        if (lb > 0.0 && (double)max_dist2 < lb * lb * (1.0 - 1e-6)) {   // no unseen row is within the radius
-            done = true;
-            break;
-        }
-    }
-    if (lane == 0 && !done && gmax > rmax + 1)
-        *giveup = 1u;      // benign race: every writer stores 1
+    constexpr bool LIST = true, EACH = false, SELF = false;
+    constexpr unsigned *out = nullptr;
+    constexpr const float *radii = nullptr;
+    const float cap = max_dist2;
+    GRID_RADIUS_NO_SELF;
+#include "knn_grid_radius_body.inc"
 }
 
-// ---- a radius per query (include/knn_mi355x.h 2j; knn_index_count_within_each, knn_index_list_within_each) ---------------
-// knn_grid_count_kernel's and knn_grid_list_kernel's walks with the wave's own radius: one wave per query, so radii[qi] is
-// wave-uniform as max_dist2 is there.  A row is a hit when E is finite, E <= radii[qi] and E <= cap.  The stop clause takes the
-// query's bound (knn_each_radius.h) in the scalar radius's place: every hit lies within it.  A query without candidates (a NaN or
-// negative radius) walks nothing, counts 0 / leaves its cursor alone and never raises the give-up word; rmax is made from cap's
-// rings, so a query whose bound is below cap stops no later than the scalar call at cap would.
+// a radius per query (include/knn_mi355x.h 2j): knn_index_count_within_each, knn_index_list_within_each
 template <int KD>
 __global__ __launch_bounds__(GRID_BLOCK) void knn_grid_each_count_kernel(const float *__restrict__ Q, int m, GridGeom gg,
                                                                          const unsigned *__restrict__ start,
@@ -623,79 +488,11 @@ __global__ __launch_bounds__(GRID_BLOCK) void knn_grid_each_count_kernel(const f
                                                                          const float *__restrict__ radii, float cap)
 {
 #pragma clang fp contract(off)
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        *giveup_next = 0u;   // (the slot's other word, as the 1-NN kernel)
-    const int lane = threadIdx.x & 63;
-    const int qi = blockIdx.x * (GRID_BLOCK / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    if (qi >= m)
-        return;
-    float q[4] = {0.f, 0.f, 0.f, 0.f};
-    bool finite = true;
-#pragma unroll
-    for (int d = 0; d < KD; ++d) {
-        q[d] = Q[(size_t)qi * KD + d];
-        finite = finite && fabsf(q[d]) < INFINITY;
-    }
-    const float rad = radii[qi];
-    if (!finite || !knn_each_has(rad)) {   // no row can be a hit (and nothing to give up on)
-        if (lane == 0)
-            out[qi] = 0u;
-        return;
-    }
-    const float bound = knn_each_bound(rad, cap);
-    int c[4];
-    (void)grid_cell_of(gg, q, c);
-    int gmax = 1;
-#pragma unroll
-    for (int d = 0; d < KD; ++d)
-        gmax = gg.g[d] > gmax ? gg.g[d] : gmax;
-
-    unsigned cnt = 0u;
-    bool done = false;
-    bool first = true;   // (rings 0 and 1 together, as the 1-NN kernel)
-    for (int r = gmax > 1 ? 1 : 0; r < gmax && r <= rmax; ++r) {
-        const int side = 2 * r + 1;
-        int total = 1;
-#pragma unroll
-        for (int d = 0; d < KD; ++d)
-            total *= side;
-        for (int idx = lane; idx < total; idx += KNN_WAVE) {
-            unsigned cell;
-            if (!grid_ring_cell<KD>(gg, c, r, side, idx, first, &cell))
-                continue;
-            const unsigned p0 = start[cell], p1 = start[cell + 1];
-            for (unsigned p = p0; p < p1; ++p) {
-                const f4g x = pts[p];
-                float acc = 0.0f;
-#pragma unroll
-                for (int d = 0; d < KD; ++d) {
-                    const float diff = q[d] - x[d];   // v0: search - reference, squared, summed in order
-                    const float sq = diff * diff;
-                    acc = acc + sq;
-                }
-                cnt += acc < INFINITY && acc <= rad && acc <= cap ? 1u : 0u;
-            }
-        }
-        first = false;
-        bool covers_all;
-        const double lb = grid_face_bound<KD>(gg, c, q, r, &covers_all);
-        if (covers_all) {
-            done = true;
-            break;
-        }
-        if (lb > 0.0 && (double)bound < lb * lb * (1.0 - 1e-6)) {   // no unseen row is within the query's bound
-            done = true;
-            break;
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        cnt += (unsigned)__shfl_xor((int)cnt, off, KNN_WAVE);
-    if (lane == 0) {
-        out[qi] = cnt;
-        if (!done && gmax > rmax + 1)
-            *giveup = 1u;      // benign race: every writer stores 1
-    }
+    constexpr bool LIST = false, EACH = true, SELF = false;
+    constexpr const unsigned *orig = nullptr;
+    GRID_RADIUS_NO_LIST;
+    GRID_RADIUS_NO_SELF;
+#include "knn_grid_radius_body.inc"
 }
 
 template <int KD>
@@ -709,84 +506,13 @@ __global__ __launch_bounds__(GRID_BLOCK) void knn_grid_each_list_kernel(const fl
                                                                         const float *__restrict__ radii, float cap)
 {
 #pragma clang fp contract(off)
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        *giveup_next = 0u;   // (the slot's other word, as the 1-NN kernel)
-    const int lane = threadIdx.x & 63;
-    const int qi = blockIdx.x * (GRID_BLOCK / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    if (qi >= m)
-        return;
-    float q[4] = {0.f, 0.f, 0.f, 0.f};
-    bool finite = true;
-#pragma unroll
-    for (int d = 0; d < KD; ++d) {
-        q[d] = Q[(size_t)qi * KD + d];
-        finite = finite && fabsf(q[d]) < INFINITY;
-    }
-    const float rad = radii[qi];
-    if (!finite || !knn_each_has(rad))   // no row can be a hit: the cursor stays where it was (and nothing to give up on)
-        return;
-    const float bound = knn_each_bound(rad, cap);
-    int c[4];
-    (void)grid_cell_of(gg, q, c);
-    int gmax = 1;
-#pragma unroll
-    for (int d = 0; d < KD; ++d)
-        gmax = gg.g[d] > gmax ? gg.g[d] : gmax;
-    const u64 off = offsets[qi], end = offsets[qi + 1];
-    const u64 room64 = end > off ? end - off : 0ull;
-    const unsigned room = room64 < 0xFFFFFFFFull ? (unsigned)room64 : 0xFFFFFFFFu;   // (the cursor is 32-bit)
-
-    bool done = false;
-    bool first = true;   // (rings 0 and 1 together, as the 1-NN kernel)
-    for (int r = gmax > 1 ? 1 : 0; r < gmax && r <= rmax; ++r) {
-        const int side = 2 * r + 1;
-        int total = 1;
-#pragma unroll
-        for (int d = 0; d < KD; ++d)
-            total *= side;
-        for (int idx = lane; idx < total; idx += KNN_WAVE) {
-            unsigned cell;
-            if (!grid_ring_cell<KD>(gg, c, r, side, idx, first, &cell))
-                continue;
-            const unsigned p0 = start[cell], p1 = start[cell + 1];
-            for (unsigned p = p0; p < p1; ++p) {
-                const f4g x = pts[p];
-                float acc = 0.0f;
-#pragma unroll
-                for (int d = 0; d < KD; ++d) {
-                    const float diff = q[d] - x[d];   // v0: search - reference, squared, summed in order
-                    const float sq = diff * diff;
-                    acc = acc + sq;
-                }
-                if (acc < INFINITY && acc <= rad && acc <= cap) {
-                    const unsigned place = atomicAdd(&cursor[qi], 1u);
-                    if (place < room)
-                        keys[off + place] = ((u64)__float_as_uint(acc) << 32) | (u64)(unsigned)(base + (long long)orig[p]);
-                }
-            }
-        }
-        first = false;
-        bool covers_all;
-        const double lb = grid_face_bound<KD>(gg, c, q, r, &covers_all);
-        if (covers_all) {
-            done = true;
-            break;
-        }
-        if (lb > 0.0 && (double)bound < lb * lb * (1.0 - 1e-6)) {   // no unseen row is within the query's bound
-            done = true;
-            break;
-        }
-    }
-    if (lane == 0 && !done && gmax > rmax + 1)
-        *giveup = 1u;      // benign race: every writer stores 1
+    constexpr bool LIST = true, EACH = true, SELF = false;
+    constexpr unsigned *out = nullptr;
+    GRID_RADIUS_NO_SELF;
+#include "knn_grid_radius_body.inc"
 }
 
-// ---- the radius graph on the grid (include/knn_mi355x.h 2k; knn_index_self_count_within_routed, knn_index_self_list_within_routed) --
-// The four walks above for the queries that are the shard's own rows: query qi is LOCAL row first + qi — Q = R + first * k, the rows
-// themselves —, and the row at position p is no hit when orig[p] == first + qi (identity by local row number: another copy of the
-// row stays a hit at distance 0).  The compare sits on the hit side, behind the distance; the walk, the stop clause, the give-up
-// word and what the commit sees are the twins'.  EACH: the wave's own radius radii[qi] under cap, as knn_grid_each_count_kernel;
-// else the scalar form, radii not read, cap the radius, as knn_grid_count_kernel.
+// the radius graph on the grid (include/knn_mi355x.h 2k): knn_index_self_count_within_routed, knn_index_self_list_within_routed
 template <int KD, bool EACH>
 __global__ __launch_bounds__(GRID_BLOCK) void knn_grid_self_count_kernel(const float *__restrict__ Q, int m, GridGeom gg,
                                                                          const unsigned *__restrict__ start,
@@ -797,81 +523,9 @@ __global__ __launch_bounds__(GRID_BLOCK) void knn_grid_self_count_kernel(const f
                                                                          const float *__restrict__ radii, float cap)
 {
 #pragma clang fp contract(off)
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        *giveup_next = 0u;   // (the slot's other word, as the 1-NN kernel)
-    const int lane = threadIdx.x & 63;
-    const int qi = blockIdx.x * (GRID_BLOCK / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    if (qi >= m)
-        return;
-    float q[4] = {0.f, 0.f, 0.f, 0.f};
-    bool finite = true;
-#pragma unroll
-    for (int d = 0; d < KD; ++d) {
-        q[d] = Q[(size_t)qi * KD + d];
-        finite = finite && fabsf(q[d]) < INFINITY;
-    }
-    const float rad = EACH ? radii[qi] : cap;
-    if (!finite || (EACH && !knn_each_has(rad))) {   // no row can be a hit (and nothing to give up on)
-        if (lane == 0)
-            out[qi] = 0u;
-        return;
-    }
-    const float bound = EACH ? knn_each_bound(rad, cap) : cap;
-    const unsigned own = first + (unsigned)qi;
-    int c[4];
-    (void)grid_cell_of(gg, q, c);
-    int gmax = 1;
-#pragma unroll
-    for (int d = 0; d < KD; ++d)
-        gmax = gg.g[d] > gmax ? gg.g[d] : gmax;
-
-    unsigned cnt = 0u;
-    bool done = false;
-    bool first_ring = true;   // (rings 0 and 1 together, as the 1-NN kernel)
-    for (int r = gmax > 1 ? 1 : 0; r < gmax && r <= rmax; ++r) {
-        const int side = 2 * r + 1;
-        int total = 1;
-#pragma unroll
-        for (int d = 0; d < KD; ++d)
-            total *= side;
-        for (int idx = lane; idx < total; idx += KNN_WAVE) {
-            unsigned cell;
-            if (!grid_ring_cell<KD>(gg, c, r, side, idx, first_ring, &cell))
-                continue;
-            const unsigned p0 = start[cell], p1 = start[cell + 1];
-            for (unsigned p = p0; p < p1; ++p) {
-                const f4g x = pts[p];
-                float acc = 0.0f;
-#pragma unroll
-                for (int d = 0; d < KD; ++d) {
-                    const float diff = q[d] - x[d];   // v0: search - reference, squared, summed in order
-                    const float sq = diff * diff;
-                    acc = acc + sq;
-                }
-                if (acc < INFINITY && acc <= rad && acc <= cap)
-                    cnt += orig[p] != own ? 1u : 0u;
-            }
-        }
-        first_ring = false;
-        bool covers_all;
-        const double lb = grid_face_bound<KD>(gg, c, q, r, &covers_all);
-        if (covers_all) {
-            done = true;
-            break;
-        }
-        if (lb > 0.0 && (double)bound < lb * lb * (1.0 - 1e-6)) {   // no unseen row is within the query's bound
-            done = true;
-            break;
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        cnt += (unsigned)__shfl_xor((int)cnt, off, KNN_WAVE);
-    if (lane == 0) {
-        out[qi] = cnt;
-        if (!done && gmax > rmax + 1)
-            *giveup = 1u;      // benign race: every writer stores 1
-    }
+    constexpr bool LIST = false, SELF = true;
+    GRID_RADIUS_NO_LIST;
+#include "knn_grid_radius_body.inc"
 }
 
 template <int KD, bool EACH>
@@ -885,81 +539,12 @@ __global__ __launch_bounds__(GRID_BLOCK) void knn_grid_self_list_kernel(const fl
                                                                         const float *__restrict__ radii, float cap)
 {
 #pragma clang fp contract(off)
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        *giveup_next = 0u;   // (the slot's other word, as the 1-NN kernel)
-    const int lane = threadIdx.x & 63;
-    const int qi = blockIdx.x * (GRID_BLOCK / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    if (qi >= m)
-        return;
-    float q[4] = {0.f, 0.f, 0.f, 0.f};
-    bool finite = true;
-#pragma unroll
-    for (int d = 0; d < KD; ++d) {
-        q[d] = Q[(size_t)qi * KD + d];
-        finite = finite && fabsf(q[d]) < INFINITY;
-    }
-    const float rad = EACH ? radii[qi] : cap;
-    if (!finite || (EACH && !knn_each_has(rad)))   // no row can be a hit: the cursor stays where it was (and nothing to give up on)
-        return;
-    const float bound = EACH ? knn_each_bound(rad, cap) : cap;
-    const unsigned own = first + (unsigned)qi;
-    int c[4];
-    (void)grid_cell_of(gg, q, c);
-    int gmax = 1;
-#pragma unroll
-    for (int d = 0; d < KD; ++d)
-        gmax = gg.g[d] > gmax ? gg.g[d] : gmax;
-    const u64 off = offsets[qi], end = offsets[qi + 1];
-    const u64 room64 = end > off ? end - off : 0ull;
-    const unsigned room = room64 < 0xFFFFFFFFull ? (unsigned)room64 : 0xFFFFFFFFu;   // (the cursor is 32-bit)
-
-    bool done = false;
-    bool first_ring = true;   // (rings 0 and 1 together, as the 1-NN kernel)
-    for (int r = gmax > 1 ? 1 : 0; r < gmax && r <= rmax; ++r) {
-        const int side = 2 * r + 1;
-        int total = 1;
-#pragma unroll
-        for (int d = 0; d < KD; ++d)
-            total *= side;
-        for (int idx = lane; idx < total; idx += KNN_WAVE) {
-            unsigned cell;
-            if (!grid_ring_cell<KD>(gg, c, r, side, idx, first_ring, &cell))
-                continue;
-            const unsigned p0 = start[cell], p1 = start[cell + 1];
-            for (unsigned p = p0; p < p1; ++p) {
-                const f4g x = pts[p];
-                float acc = 0.0f;
-#pragma unroll
-                for (int d = 0; d < KD; ++d) {
-                    const float diff = q[d] - x[d];   // v0: search - reference, squared, summed in order
-                    const float sq = diff * diff;
-                    acc = acc + sq;
-                }
-                if (acc < INFINITY && acc <= rad && acc <= cap) {
-                    const unsigned row = orig[p];
-                    if (row != own) {
-                        const unsigned place = atomicAdd(&cursor[qi], 1u);
-                        if (place < room)
-                            keys[off + place] = ((u64)__float_as_uint(acc) << 32) | (u64)(unsigned)(base + (long long)row);
-                    }
-                }
-            }
-        }
-        first_ring = false;
-        bool covers_all;
-        const double lb = grid_face_bound<KD>(gg, c, q, r, &covers_all);
-        if (covers_all) {
-            done = true;
-            break;
-        }
-        if (lb > 0.0 && (double)bound < lb * lb * (1.0 - 1e-6)) {   // no unseen row is within the query's bound
-            done = true;
-            break;
-        }
-    }
-    if (lane == 0 && !done && gmax > rmax + 1)
-        *giveup = 1u;      // benign race: every writer stores 1
+    constexpr bool LIST = true, SELF = true;
+    constexpr unsigned *out = nullptr;
+#include "knn_grid_radius_body.inc"
 }
+#undef GRID_RADIUS_NO_LIST
+#undef GRID_RADIUS_NO_SELF
 
 // ---- host -------------------------------------------------------------------------------------------
 #define GTRY(call)                     \
@@ -1192,6 +777,34 @@ GridTopkPlan knn_grid_topk_plan(int k, int K, int m, bool has_grid, int path, bo
     return p;
 }
 
+// What the top-K, count and list calls share around their grid kernel: the slot's two give-up words (they alternate from batch to
+// batch: the kernel clears the next batch's), one block of GRID_BLOCK threads per GRID_BLOCK / 64 queries unless the plan says
+// otherwise (blocks != 0), and the events ev0 / ev1 (nullable) that bracket the kernel.  grid_batch_begin comes right before the
+// launch, grid_batch_end right behind it; *gate_out = the batch's give-up word once the kernel is issued.
+struct GridBatch {
+    unsigned *giveup, *giveup_next;
+    dim3 grid, block;
+};
+
+static hipError_t grid_batch_begin(const GridState *gs, int slot, int m, unsigned blocks, hipStream_t s, hipEvent_t ev0, GridBatch *b)
+{
+    const unsigned call = gs->calls[slot]++;
+    b->giveup = gs->giveup + 2 * slot + (call & 1u);
+    b->giveup_next = gs->giveup + 2 * slot + ((call + 1u) & 1u);
+    b->grid = dim3(blocks ? blocks : (unsigned)((m + GRID_BLOCK / 64 - 1) / (GRID_BLOCK / 64)));
+    b->block = dim3(GRID_BLOCK);
+    return ev0 ? hipEventRecord(ev0, s) : hipSuccess;
+}
+
+static hipError_t grid_batch_end(const GridBatch &b, hipStream_t s, hipEvent_t ev1, const unsigned **gate_out)
+{
+    GTRY(hipGetLastError());
+    if (ev1)
+        GTRY(hipEventRecord(ev1, s));
+    *gate_out = b.giveup;
+    return hipSuccess;
+}
+
 // The whole top-K call on the grid way, asynchronous on c.stream: the grid kernel writes the batch's lists [m][K] — into c.keys
 // itself when the call starts them (init), else into c.cand (>= plan.scratch_bytes) —, the exact top-K behind it, gated on
 // the batch's give-up word, overwrites them when some query gave up, and a folding call then merges the scratch into the keys.
@@ -1202,21 +815,17 @@ hipError_t knn_grid_query_topk(const GridState *gs, const GridTopkPlan &plan, in
     *gate_out = nullptr;
     if (!gs || !gs->usable || !plan.use || c.m <= 0 || c.K < 1 || c.K > KNN_WAVE || (!c.init && !c.cand))
         return hipErrorInvalidValue;
-    const unsigned call = gs->calls[slot]++;
-    unsigned *giveup = gs->giveup + 2 * slot + (call & 1u);
-    unsigned *giveup_next = gs->giveup + 2 * slot + ((call + 1u) & 1u);
     u64 *lists = c.init ? c.keys : c.cand;
     hipStream_t s = c.stream;
-    const dim3 grid(plan.blocks), block(GRID_BLOCK);
-    if (c.ev0)
-        GTRY(hipEventRecord(c.ev0, s));
-#define GRID_TOPK(KDV)                                                                                                             \
-    if (c.within())                                                                                                                \
-        hipLaunchKernelGGL(knn_grid_within_kernel<KDV>, grid, block, 0, s, c.q, c.m, c.K, gs->geom, gs->start, gs->pts, gs->orig,  \
-                           c.base, lists, plan.rmax, giveup, giveup_next, c.max_dist2);                                            \
-    else                                                                                                                           \
-        hipLaunchKernelGGL(knn_grid_topk_kernel<KDV>, grid, block, 0, s, c.q, c.m, c.K, gs->geom, gs->start, gs->pts, gs->orig,    \
-                           c.base, lists, plan.rmax, giveup, giveup_next)
+    GridBatch b;
+    GTRY(grid_batch_begin(gs, slot, c.m, plan.blocks, s, c.ev0, &b));
+#define GRID_TOPK(KDV)                                                                                                               \
+    if (c.within())                                                                                                                  \
+        hipLaunchKernelGGL(knn_grid_within_kernel<KDV>, b.grid, b.block, 0, s, c.q, c.m, c.K, gs->geom, gs->start, gs->pts, gs->orig, \
+                           c.base, lists, plan.rmax, b.giveup, b.giveup_next, c.max_dist2);                                          \
+    else                                                                                                                             \
+        hipLaunchKernelGGL(knn_grid_topk_kernel<KDV>, b.grid, b.block, 0, s, c.q, c.m, c.K, gs->geom, gs->start, gs->pts, gs->orig,  \
+                           c.base, lists, plan.rmax, b.giveup, b.giveup_next)
     switch (gs->geom.k) {
     case 1: GRID_TOPK(1); break;
     case 2: GRID_TOPK(2); break;
@@ -1224,11 +833,8 @@ hipError_t knn_grid_query_topk(const GridState *gs, const GridTopkPlan &plan, in
     default: GRID_TOPK(4); break;
     }
 #undef GRID_TOPK
-    GTRY(hipGetLastError());
-    if (c.ev1)
-        GTRY(hipEventRecord(c.ev1, s));
-    *gate_out = giveup;
-    GTRY(knn_exact_topk_launch(c.writing(lists), giveup, true));
+    GTRY(grid_batch_end(b, s, c.ev1, gate_out));
+    GTRY(knn_exact_topk_launch(c.writing(lists), b.giveup, true));
     if (!c.init)
         GTRY(knn_topk_merge_launch(c.m, c.K, c.cand, c.keys, s));
     return hipSuccess;
@@ -1243,26 +849,23 @@ hipError_t knn_grid_query_count(const GridState *gs, int rmax, int slot, const C
     *gate_out = nullptr;
     if (!gs || !gs->usable || c.m <= 0 || !c.scratch || !c.counts || rmax < 0)
         return hipErrorInvalidValue;
-    const unsigned call = gs->calls[slot]++;
-    unsigned *giveup = gs->giveup + 2 * slot + (call & 1u);
-    unsigned *giveup_next = gs->giveup + 2 * slot + ((call + 1u) & 1u);
     hipStream_t s = c.stream;
-    const dim3 grid((unsigned)((c.m + GRID_BLOCK / 64 - 1) / (GRID_BLOCK / 64))), block(GRID_BLOCK);
-    if (c.ev0)
-        GTRY(hipEventRecord(c.ev0, s));
+    GridBatch b;
+    GTRY(grid_batch_begin(gs, slot, c.m, 0u, s, c.ev0, &b));
+#define GRID_COUNT_SELF(KDV, EACHV) /* the shard's own rows (2k); radii null in the scalar form */                                   \
+    hipLaunchKernelGGL((knn_grid_self_count_kernel<KDV, EACHV>), b.grid, b.block, 0, s, c.q, c.m, gs->geom, gs->start, gs->pts,      \
+                       gs->orig, (unsigned)c.self_first, c.scratch, rmax, b.giveup, b.giveup_next, c.radii, c.max_dist2)
 #define GRID_COUNT(KDV)                                                                                                              \
-    if (c.self_first >= 0 && c.radii)   /* the shard's own rows (2k): the self forms */                                              \
-        hipLaunchKernelGGL((knn_grid_self_count_kernel<KDV, true>), grid, block, 0, s, c.q, c.m, gs->geom, gs->start, gs->pts, gs->orig, \
-                           (unsigned)c.self_first, c.scratch, rmax, giveup, giveup_next, c.radii, c.max_dist2);                      \
+    if (c.self_first >= 0 && c.radii)                                                                                                \
+        GRID_COUNT_SELF(KDV, true);                                                                                                  \
     else if (c.self_first >= 0)                                                                                                      \
-        hipLaunchKernelGGL((knn_grid_self_count_kernel<KDV, false>), grid, block, 0, s, c.q, c.m, gs->geom, gs->start, gs->pts, gs->orig, \
-                           (unsigned)c.self_first, c.scratch, rmax, giveup, giveup_next, (const float *)nullptr, c.max_dist2);       \
+        GRID_COUNT_SELF(KDV, false);                                                                                                 \
     else if (c.radii)   /* a radius per query; c.max_dist2 is the cap */                                                             \
-        hipLaunchKernelGGL(knn_grid_each_count_kernel<KDV>, grid, block, 0, s, c.q, c.m, gs->geom, gs->start, gs->pts, c.scratch, rmax, \
-                           giveup, giveup_next, c.radii, c.max_dist2);                                                               \
+        hipLaunchKernelGGL(knn_grid_each_count_kernel<KDV>, b.grid, b.block, 0, s, c.q, c.m, gs->geom, gs->start, gs->pts, c.scratch, \
+                           rmax, b.giveup, b.giveup_next, c.radii, c.max_dist2);                                                     \
     else                                                                                                                             \
-        hipLaunchKernelGGL(knn_grid_count_kernel<KDV>, grid, block, 0, s, c.q, c.m, gs->geom, gs->start, gs->pts, c.scratch, rmax,    \
-                           giveup, giveup_next, c.max_dist2)
+        hipLaunchKernelGGL(knn_grid_count_kernel<KDV>, b.grid, b.block, 0, s, c.q, c.m, gs->geom, gs->start, gs->pts, c.scratch,     \
+                           rmax, b.giveup, b.giveup_next, c.max_dist2)
     switch (gs->geom.k) {
     case 1: GRID_COUNT(1); break;
     case 2: GRID_COUNT(2); break;
@@ -1270,12 +873,10 @@ hipError_t knn_grid_query_count(const GridState *gs, int rmax, int slot, const C
     default: GRID_COUNT(4); break;
     }
 #undef GRID_COUNT
-    GTRY(hipGetLastError());
-    if (c.ev1)
-        GTRY(hipEventRecord(c.ev1, s));
-    *gate_out = giveup;
-    GTRY(knn_count_commit_launch(c.m, c.scratch, c.counts, giveup, s));
-    return knn_gated_count_launch(c, giveup);   // (a routed self call: the gated self-scan)
+#undef GRID_COUNT_SELF
+    GTRY(grid_batch_end(b, s, c.ev1, gate_out));
+    GTRY(knn_count_commit_launch(c.m, c.scratch, c.counts, b.giveup, s));
+    return knn_gated_count_launch(c, b.giveup);   // (a routed self call: the gated self-scan)
 }
 
 // The whole list call on the grid way (KNN_QUERY_COUNT_GRID), asynchronous on c.stream: c.scratch [m] <- c.fill, the grid kernel
@@ -1288,29 +889,25 @@ hipError_t knn_grid_query_list(const GridState *gs, int rmax, int slot, const Li
     *gate_out = nullptr;
     if (!gs || !gs->usable || c.m <= 0 || !c.scratch || !c.fill || !c.offsets || !c.keys || c.gids || rmax < 0)
         return hipErrorInvalidValue;
-    const unsigned call = gs->calls[slot]++;
-    unsigned *giveup = gs->giveup + 2 * slot + (call & 1u);
-    unsigned *giveup_next = gs->giveup + 2 * slot + ((call + 1u) & 1u);
     hipStream_t s = c.stream;
     GTRY(hipMemcpyAsync(c.scratch, c.fill, (size_t)c.m * sizeof(unsigned), hipMemcpyDeviceToDevice, s));
-    const dim3 grid((unsigned)((c.m + GRID_BLOCK / 64 - 1) / (GRID_BLOCK / 64))), block(GRID_BLOCK);
-    if (c.ev0)
-        GTRY(hipEventRecord(c.ev0, s));
-#define GRID_LIST(KDV)                                                                                                                \
-    if (c.self_first >= 0 && c.radii)   /* the shard's own rows (2k): the self forms */                                               \
-        hipLaunchKernelGGL((knn_grid_self_list_kernel<KDV, true>), grid, block, 0, s, c.q, c.m, gs->geom, gs->start, gs->pts, gs->orig, \
-                           (unsigned)c.self_first, c.base, c.offsets, c.scratch, c.keys, rmax, giveup, giveup_next, c.radii,          \
-                           c.max_dist2);                                                                                              \
-    else if (c.self_first >= 0)                                                                                                       \
-        hipLaunchKernelGGL((knn_grid_self_list_kernel<KDV, false>), grid, block, 0, s, c.q, c.m, gs->geom, gs->start, gs->pts, gs->orig, \
-                           (unsigned)c.self_first, c.base, c.offsets, c.scratch, c.keys, rmax, giveup, giveup_next,                   \
-                           (const float *)nullptr, c.max_dist2);                                                                      \
-    else if (c.radii)   /* a radius per query; c.max_dist2 is the cap */                                                              \
-        hipLaunchKernelGGL(knn_grid_each_list_kernel<KDV>, grid, block, 0, s, c.q, c.m, gs->geom, gs->start, gs->pts, gs->orig, c.base, \
-                           c.offsets, c.scratch, c.keys, rmax, giveup, giveup_next, c.radii, c.max_dist2);                            \
-    else                                                                                                                              \
-        hipLaunchKernelGGL(knn_grid_list_kernel<KDV>, grid, block, 0, s, c.q, c.m, gs->geom, gs->start, gs->pts, gs->orig, c.base,     \
-                           c.offsets, c.scratch, c.keys, rmax, giveup, giveup_next, c.max_dist2)
+    GridBatch b;
+    GTRY(grid_batch_begin(gs, slot, c.m, 0u, s, c.ev0, &b));
+#define GRID_LIST_SELF(KDV, EACHV) /* the shard's own rows (2k); radii null in the scalar form */                                    \
+    hipLaunchKernelGGL((knn_grid_self_list_kernel<KDV, EACHV>), b.grid, b.block, 0, s, c.q, c.m, gs->geom, gs->start, gs->pts,       \
+                       gs->orig, (unsigned)c.self_first, c.base, c.offsets, c.scratch, c.keys, rmax, b.giveup, b.giveup_next,        \
+                       c.radii, c.max_dist2)
+#define GRID_LIST(KDV)                                                                                                               \
+    if (c.self_first >= 0 && c.radii)                                                                                                \
+        GRID_LIST_SELF(KDV, true);                                                                                                   \
+    else if (c.self_first >= 0)                                                                                                      \
+        GRID_LIST_SELF(KDV, false);                                                                                                  \
+    else if (c.radii)   /* a radius per query; c.max_dist2 is the cap */                                                             \
+        hipLaunchKernelGGL(knn_grid_each_list_kernel<KDV>, b.grid, b.block, 0, s, c.q, c.m, gs->geom, gs->start, gs->pts, gs->orig,  \
+                           c.base, c.offsets, c.scratch, c.keys, rmax, b.giveup, b.giveup_next, c.radii, c.max_dist2);               \
+    else                                                                                                                             \
+        hipLaunchKernelGGL(knn_grid_list_kernel<KDV>, b.grid, b.block, 0, s, c.q, c.m, gs->geom, gs->start, gs->pts, gs->orig,       \
+                           c.base, c.offsets, c.scratch, c.keys, rmax, b.giveup, b.giveup_next, c.max_dist2)
     switch (gs->geom.k) {
     case 1: GRID_LIST(1); break;
     case 2: GRID_LIST(2); break;
@@ -1318,12 +915,10 @@ hipError_t knn_grid_query_list(const GridState *gs, int rmax, int slot, const Li
     default: GRID_LIST(4); break;
     }
 #undef GRID_LIST
-    GTRY(hipGetLastError());
-    if (c.ev1)
-        GTRY(hipEventRecord(c.ev1, s));
-    *gate_out = giveup;
-    GTRY(knn_list_commit_launch(c.m, c.scratch, c.fill, giveup, s));
-    return knn_gated_list_launch(c, giveup);   // (a routed self call: the gated self-scan)
+#undef GRID_LIST_SELF
+    GTRY(grid_batch_end(b, s, c.ev1, gate_out));
+    GTRY(knn_list_commit_launch(c.m, c.scratch, c.fill, b.giveup, s));
+    return knn_gated_list_launch(c, b.giveup);   // (a routed self call: the gated self-scan)
 }
 
 long long knn_grid_radius_rings(const GridState *gs, float max_dist2)

@@ -1,0 +1,128 @@
+// knn_grid_radius_body.inc — the one walk of the grid's radius kernels (KNN_QUERY_COUNT_GRID): included into knn_grid_count_kernel,
+// knn_grid_list_kernel, their each-forms and their self forms (knn_grid.hip), which fix three compile-time switches —
+//   LIST  a hit reserves a place and stores its key; else it bumps the lane's register;
+//   EACH  the wave's own radius radii[qi] under cap (include/knn_mi355x.h 2j); else the scalar radius cap, radii not read;
+//   SELF  query qi is the shard's LOCAL row first + qi, and that row is no hit (2k)
+// — and provide KD, the arguments Q, m, gg, start, pts, rmax, giveup, giveup_next by their names, and every one of orig, first,
+// base, out, offsets, cursor, keys, radii, cap: as its argument, or as a constant null / zero stand-in where the form has none.
+//
+// One wave per query, the 1-NN kernel's walk: lanes take the cells of ring r, and a row is a hit when its v0 distance E is finite,
+// E <= rad and E <= cap (fp32 compares, equality inside; the scalar forms' rad is cap, so theirs is one compare).  One wave per
+// query, so radii[qi] is wave-uniform as the scalar radius is.
+// Stop rule, after ring r: the block of rings 0..r is the whole grid, or bound < lb^2 (1 - 1e-6) — the radius clause of
+// knn_grid_within_kernel: every unseen row's computed distance is strictly above that bound, so none is within the radius; the test
+// is wave-uniform (the query, its cell and r decide it).  The clause takes the query's bound (knn_each_radius.h; the scalar forms'
+// is cap): every hit lies within it, and rmax is made from cap's rings, so a query whose bound is below cap stops no later than the
+// scalar call at cap would.  Past rmax rings the query raises the give-up word (the slot's two words alternate as in the other grid
+// kernels).  No LDS, no block barrier.
+// Every cell of rings 0..r is visited once (grid_ring_cell: a position of the (2r+1)^K block belongs to exactly one ring), every row
+// sits in one cell: no row is counted or listed twice.
+// Counts: one wave reduction at the end, lane 0 stores the query's count to out[q] — the slot's scratch, never the caller's counts: a
+// batch that gives up is answered again by the exact count behind this kernel, and knn_count_commit_kernel adds the scratch only when
+// nobody gave up.
+// Lists: a hit reserves place p of its query's segment with one atomicAdd on cursor[q] and, when p is below the segment's room,
+// stores its key — the distance's bits and base + orig[position] — at keys[offsets[q] + p].  cursor is the slot's scratch, on entry
+// a copy of the caller's fill, never the caller's fill itself: a batch that gives up is answered again by the exact list behind
+// this kernel from the untouched fill, over the same places, and knn_list_commit_kernel copies the cursor to fill only when nobody
+// gave up.
+// A query without candidates — a non-finite coordinate (every distance is NaN or +INF), or with EACH a NaN or negative radius —
+// walks nothing, counts 0 / leaves its cursor where it was, and never raises the give-up word: there is nothing to give up on.
+// SELF: Q = R + first * k, the rows themselves, and the row at position p is no hit when orig[p] == first + qi — identity by local
+// row number: another copy of the row stays a hit at distance 0.  The compare sits on the hit side, behind the distance; the walk,
+// the stop clause, the give-up word and what the commit sees are the twins'.  (The self list reads orig[p] once, before the
+// reservation; the other lists read it only at the store.)
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        *giveup_next = 0u;   // (the slot's other word, as the 1-NN kernel)
+    const int lane = threadIdx.x & 63;
+    const int qi = blockIdx.x * (GRID_BLOCK / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (qi >= m)
+        return;
+    float q[4] = {0.f, 0.f, 0.f, 0.f};
+    bool finite = true;
+#pragma unroll
+    for (int d = 0; d < KD; ++d) {
+        q[d] = Q[(size_t)qi * KD + d];
+        finite = finite && fabsf(q[d]) < INFINITY;
+    }
+    const float rad = EACH ? radii[qi] : cap;
+    if (!finite || (EACH && !knn_each_has(rad))) {   // no row can be a hit (and nothing to give up on)
+        if (!LIST && lane == 0)
+            out[qi] = 0u;
+        return;
+    }
+    const float bound = EACH ? knn_each_bound(rad, cap) : cap;
+    const unsigned own = first + (unsigned)qi;
+    int c[4];
+    (void)grid_cell_of(gg, q, c);
+    int gmax = 1;
+#pragma unroll
+    for (int d = 0; d < KD; ++d)
+        gmax = gg.g[d] > gmax ? gg.g[d] : gmax;
+    const u64 off = LIST ? offsets[qi] : 0ull, end = LIST ? offsets[qi + 1] : 0ull;
+    const u64 room64 = end > off ? end - off : 0ull;
+    const unsigned room = room64 < 0xFFFFFFFFull ? (unsigned)room64 : 0xFFFFFFFFu;   // (the cursor is 32-bit)
+
+    unsigned cnt = 0u;
+    bool done = false;
+    bool first_ring = true;   // (rings 0 and 1 together, as the 1-NN kernel)
+    for (int r = gmax > 1 ? 1 : 0; r < gmax && r <= rmax; ++r) {
+        const int side = 2 * r + 1;
+        int total = 1;
+#pragma unroll
+        for (int d = 0; d < KD; ++d)
+            total *= side;
+        for (int idx = lane; idx < total; idx += KNN_WAVE) {
+            unsigned cell;
+            if (!grid_ring_cell<KD>(gg, c, r, side, idx, first_ring, &cell))
+                continue;
+            const unsigned p0 = start[cell], p1 = start[cell + 1];
+            for (unsigned p = p0; p < p1; ++p) {
+                const f4g x = pts[p];
+                float acc = 0.0f;
+#pragma unroll
+                for (int d = 0; d < KD; ++d) {
+                    const float diff = q[d] - x[d];   // v0: search - reference, squared, summed in order
+                    const float sq = diff * diff;
+                    acc = acc + sq;
+                }
+                if (acc < INFINITY && acc <= rad && acc <= cap) {
+                    if (!LIST) {
+                        cnt += !SELF || orig[p] != own ? 1u : 0u;
+                    } else if (SELF) {
+                        const unsigned row = orig[p];
+                        if (row != own) {
+                            const unsigned place = atomicAdd(&cursor[qi], 1u);
+                            if (place < room)
+                                keys[off + place] = ((u64)__float_as_uint(acc) << 32) | (u64)(unsigned)(base + (long long)row);
+                        }
+                    } else {
+                        const unsigned place = atomicAdd(&cursor[qi], 1u);
+                        if (place < room)
+                            keys[off + place] = ((u64)__float_as_uint(acc) << 32) | (u64)(unsigned)(base + (long long)orig[p]);
+                    }
+                }
+            }
+        }
+        first_ring = false;
+        bool covers_all;
+        const double lb = grid_face_bound<KD>(gg, c, q, r, &covers_all);
+        if (covers_all) {
+            done = true;
+            break;
+        }
+        if (lb > 0.0 && (double)bound < lb * lb * (1.0 - 1e-6)) {   // no unseen row is within the query's bound
+            done = true;
+            break;
+        }
+    }
+    if (!LIST) {
+#pragma unroll
+        for (int step = 32; step > 0; step >>= 1)
+            cnt += (unsigned)__shfl_xor((int)cnt, step, KNN_WAVE);
+    }
+    if (lane == 0) {
+        if (!LIST)
+            out[qi] = cnt;
+        if (!done && gmax > rmax + 1)
+            *giveup = 1u;      // benign race: every writer stores 1
+    }
