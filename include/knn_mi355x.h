@@ -675,6 +675,50 @@ int knn_index_self_list_within_routed_host(knn_index *idx, const float *max_dist
  * <= 2^32) and its eight outputs; out[6] is the slices of the exact self-scan (knn_debug_self_plan's for a count call). */
 int knn_debug_self_routed_plan(const long long in[16], long long out[8]);
 
+/* ------------------------------------------------------------------------
+ * 2l. Counts and lists within a radius over a subset of the rows, on the grid and cell-pruned ways: the masked count of 2g and the
+ * masked list of 2h with the two pruned ways the plain calls of 2d and 2e have on request.  The masked calls of 2g and 2h know the
+ * exact masked scan alone and refuse every flag but the init flag; these entry points admit KNN_QUERY_COUNT_GRID and
+ * KNN_QUERY_COUNT_CELLS as well.  A tenant filter or a tombstone mask no longer takes a range query off the pruned ways.
+ *
+ * The contract is 2g's (count) and 2h's (list) word for word.  The mask: mask_dev is a device array of (n_local + 31) / 32
+ * unsigned words on the index's device, borrowed for the call; bit i % 32 of word i / 32 admits LOCAL row i — the order of the refs
+ * the index was created from, whatever order a layout keeps them in —; bits at and beyond n_local in the last word are ignored,
+ * whatever they hold; the mask may change between calls.  A row is a candidate only when its mask bit is set AND its v0 distance E
+ * is finite and E <= max_dist2 (fp32, accumulated in dimension order, no FMA, an fp32 compare with equality inside, -0 counts as
+ * 0).  Keys carry the ORIGINAL global numbers: base_index + row, or the gid on a cell-range shard.  Without KNN_QUERY_INIT_KEYS the
+ * call adds to the counts / appends behind fill_dev, so disjoint shards, each with its own mask, fold by calling one after the
+ * other on a stream; with it counts_dev / fill_dev are zeroed first.  A hit reserves p = fill_dev[j]++ and is stored at
+ * keys_dev[offsets_dev[j] + p] only when p is below the segment's room; fill_dev[j] ends as its entry value plus this shard's
+ * admitted hits, stored or not; nothing is ever stored outside a segment; the order inside a segment is unspecified.  Asynchronous
+ * on `stream`; slots as for every other query; these calls may follow or precede any other call on a slot.
+ * For every input the counts equal knn_index_count_within_masked's and every segment holds the same set of keys as
+ * knn_index_list_within_masked's; an all-ones mask gives what knn_index_count_within / knn_index_list_within give under the same
+ * flags.
+ *
+ * Flags: KNN_QUERY_INIT_KEYS, KNN_QUERY_COUNT_GRID, KNN_QUERY_COUNT_CELLS; anything else is KNN_EINVAL.  The way is the one
+ * knn_index_count_within would take for m queries at max_dist2 under the same flags and options (knn_debug_count_plan describes
+ * these calls too), with the exact masked scan in the exact scan's place: without a routing flag the call launches exactly what
+ * the call of 2g / 2h launches.  On the grid way (k <= 4) a row inside the radius is a hit only when its bit is set; on the
+ * cell-pruned way (a finite radius, a one-frame cell-sorted layout, m >= 5) the pass's preparation, match and scan are the plain
+ * count's — they know no mask, their records name masked-out rows too — and the kernels that turn records into hits drop a row
+ * whose bit is clear.  Either way the mask is read by LOCAL row number, for the rows inside the radius alone.  A grid batch that
+ * gives up, and a cell-pruned pass that falls back, are answered by the exact masked scan, gated on the device.
+ * knn_index_last_stats reports [0] = 1 / 3 / 4; [1], [2] and [3] mean what 2d says.
+ *
+ * Argument errors are KNN_EINVAL, each with its own knn_last_error text prefixed by the function's name, checked in this order —
+ * the first that fails speaks, nothing is launched —: max_dist2 < 0 or NaN, an unknown flag, a slot outside 0 .. 7, m < 1, a null
+ * queries pointer, a null mask pointer, a null counts pointer or a null offsets, fill or keys pointer, a null index.
+ *
+ * Not built: a radius per query under a mask (that needs an each-form of the exact masked scans); masked self calls; the masked
+ * top-K on the pruned ways; a default policy — both pruned ways stay on request, as for the unmasked calls; using the mask to skip
+ * whole cells (the walk and the scan visit what the unmasked call visits). */
+int knn_index_count_within_masked_routed(knn_index *idx, int slot, int m, const float *queries_dev, float max_dist2,
+                                         const unsigned *mask_dev, unsigned *counts_dev, void *stream, unsigned flags);
+int knn_index_list_within_masked_routed(knn_index *idx, int slot, int m, const float *queries_dev, float max_dist2,
+                                        const unsigned *mask_dev, const unsigned long long *offsets_dev /*[m+1]*/,
+                                        unsigned *fill_dev /*[m]*/, unsigned long long *keys_dev, void *stream, unsigned flags);
+
 /* Tuning / test hooks.  Known names:
  *   "path"    0 = auto, 1 = exact VALU kernels only, 2 = force the MFMA filter
  *             (+ exact re-rank) where its preconditions hold, 3 = the uniform-grid spatial index

@@ -27,6 +27,7 @@ __all__ = ["lib", "lib_path", "cudaCallback", "KnnIndex", "KnnGeom", "KnnError",
            "count_within_each_c", "list_within_each_c", "self_count_within_each_c", "self_list_within_each_c",
            "count_within_each_host_c", "list_within_each_host_c", "keys_column_dist2_c", "keys_column_dist2", "debug_each_radius",
            "self_count_within_routed_c", "self_list_within_routed_c", "self_list_within_routed_host_c", "debug_self_routed_plan",
+           "count_within_masked_routed_c", "list_within_masked_routed_c",
            "debug_match_tests"]
 
 KEY_INIT = 0x7F80000000000000
@@ -59,6 +60,7 @@ EXPORTED_SYMBOLS = [
     "knn_index_list_within_each_host", "knn_debug_each_radius",
     "knn_index_self_count_within_routed", "knn_index_self_list_within_routed", "knn_index_self_list_within_routed_host",
     "knn_debug_self_routed_plan",
+    "knn_index_count_within_masked_routed", "knn_index_list_within_masked_routed",
     "knn_debug_cells_fetch", "knn_debug_match_tests",
 ]
 TOPK_LARGE_MAX = 4096   # KNN_TOPK_LARGE_MAX
@@ -763,6 +765,22 @@ def self_list_within_routed_c():
     return f
 
 
+def count_within_masked_routed_c():
+    """knn_index_count_within_masked_routed with its argument types (set here, not in lib(), as count_within_c)."""
+    f = lib().knn_index_count_within_masked_routed
+    f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
+                  ctypes.c_void_p, ctypes.c_uint]
+    return f
+
+
+def list_within_masked_routed_c():
+    """knn_index_list_within_masked_routed with its argument types (set here, not in lib(), as count_within_c)."""
+    f = lib().knn_index_list_within_masked_routed
+    f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
+                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint]
+    return f
+
+
 def self_list_within_routed_host_c():
     f = lib().knn_index_self_list_within_routed_host
     f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_uint, ctypes.c_void_p,
@@ -1330,6 +1348,26 @@ class KnnIndex:
                                            ctypes.c_void_p(int(keys_dev)), ctypes.c_void_p(stream),
                                            (QUERY_INIT_KEYS if init else 0) | (QUERY_COUNT_GRID if grid else 0) |
                                            (QUERY_COUNT_CELLS if cells else 0) | int(flags)))
+
+    def count_within_masked_routed(self, m, queries_dev, max_dist2, mask_dev, counts_dev, stream=0, slot=0, init=False, grid=False,
+                                   cells=False, flags=0):
+        """Async (knn_index_count_within_masked_routed): count_within_masked on the way count_within would take for m queries at
+        max_dist2: grid / cells ask for the grid index / the cell-pruned scan (QUERY_COUNT_GRID / QUERY_COUNT_CELLS); without them
+        the exact masked scan.  flags: further flag bits as they are (every one of them raises)."""
+        _check(count_within_masked_routed_c()(self._h, int(slot), int(m), ctypes.c_void_p(int(queries_dev)), float(max_dist2),
+                                              ctypes.c_void_p(int(mask_dev)), ctypes.c_void_p(int(counts_dev)), ctypes.c_void_p(stream),
+                                              (QUERY_INIT_KEYS if init else 0) | (QUERY_COUNT_GRID if grid else 0) |
+                                              (QUERY_COUNT_CELLS if cells else 0) | int(flags)))
+
+    def list_within_masked_routed(self, m, queries_dev, max_dist2, mask_dev, offsets_dev, fill_dev, keys_dev, stream=0, slot=0,
+                                  init=False, grid=False, cells=False, flags=0):
+        """Async (knn_index_list_within_masked_routed): list_within_masked on count_within_masked_routed's way.  The third step of
+        count_within_masked_routed -> counts_to_offsets -> this -> keys_sort_segments."""
+        _check(list_within_masked_routed_c()(self._h, int(slot), int(m), ctypes.c_void_p(int(queries_dev)), float(max_dist2),
+                                             ctypes.c_void_p(int(mask_dev)), ctypes.c_void_p(int(offsets_dev)),
+                                             ctypes.c_void_p(int(fill_dev)), ctypes.c_void_p(int(keys_dev)), ctypes.c_void_p(stream),
+                                             (QUERY_INIT_KEYS if init else 0) | (QUERY_COUNT_GRID if grid else 0) |
+                                             (QUERY_COUNT_CELLS if cells else 0) | int(flags)))
 
     def self_list_within_routed_host(self, cap, max_dist2=None, grid=False, cells=False, flags=0):
         """Synchronous radius graph of this shard on the routed self calls (knn_index_self_list_within_routed_host), in

@@ -1314,13 +1314,14 @@ CountPlan count_plan_of(const knn_index *idx, const QueryRouteInputs &ri, int m,
     return knn_count_route(ci);
 }
 
-// ---- the radius family (include/knn_mi355x.h 2e .. 2k): one description, one argument ladder, one call front ---------------------
+// ---- the radius family (include/knn_mi355x.h 2e .. 2l): one description, one argument ladder, one call front ---------------------
 // What an entry of the family is, and what its caller states.  m: the queries, or the rows of a self call (queries null: they are
 // the shard's rows from row_first).  max_dist2: the radius, or the cap over `radii` (nullable, device [m]).
 enum : unsigned {
     kCap = 1u,      // the entry's texts speak of a cap, not of max_dist2 (the each and routed forms)
     kRouted = 2u,   // admits KNN_QUERY_COUNT_GRID / _CELLS and takes the way knn_count_route names; else way 1 on every index
     kSelf = 4u,     // about the shard's own rows: rows and row_first in m's place, a query's own row no candidate
+    kMasked = 8u,   // over a subset of the rows: `mask` admits them; way 1 is the exact masked scan (never with radii or kSelf)
 };
 struct WithinCall {
     const char *who;
@@ -1332,6 +1333,7 @@ struct WithinCall {
     float max_dist2;
     void *stream;
     unsigned flags;
+    const unsigned *mask = nullptr;   // kMasked: device (n_local + 31) / 32 words
 };
 struct NullRule {
     bool broken;
@@ -1395,6 +1397,15 @@ hipError_t exact_within(const CountCall &c) { return knn_exact_count_launch(c, n
 hipError_t exact_within(const ListCall &c) { return knn_exact_list_launch(c, nullptr); }
 hipError_t self_within(const CountCall &c, long long row_first) { return knn_self_count_launch(c, row_first); }
 hipError_t self_within(const ListCall &c, long long row_first) { return knn_self_list_launch(c, row_first); }
+// (the exact masked scans: they make their prefix in c.mask_scratch and record the call's events themselves, behind it)
+hipError_t masked_within(const CountCall &c, bool init)
+{
+    return knn_masked_count_launch(c, knn_masked_plan(c.k, c.m, 0, c.n, c.num_cu, init), c.mask, c.mask_scratch);
+}
+hipError_t masked_within(const ListCall &c, bool init)
+{
+    return knn_masked_list_launch(c, knn_masked_lists_plan(c.k, c.m, 0, c.n, c.num_cu, init), c.mask, c.mask_scratch);
+}
 
 // Behind the lock and the device, every call of the family: the fields both call structs share (q: the queries as the launches
 // take them), way 1 in the statistics, and — every way ADDS to the caller's counts or fill — an init call's zeroes.
@@ -1422,10 +1433,13 @@ int within_begin(knn_index *idx, const WithinCall &w, const float *q, Call &call
 // nothing is uploaded.  Routed (2k), call.self_first tells the grid and cell ways to drop a query's own row and to gate the
 // self-scan behind them, and way 1 is the exact self-scan in the exact scan's place; not routed (2i, 2j), no layout is consulted
 // and the self-scan — which reads neither call.q nor call.scratch — is launched as it always was.
+// Masked (2g, 2h, 2l): way 1 is the exact masked scan in the exact scan's place; routed (2l), call.mask tells the grid and cell ways
+// to drop the rows it does not admit and to gate the masked scan behind them.  The slot's mask scratch is grown before the first
+// launch whichever way is taken: the host cannot know whether the scan behind a pruned way will run.
 template <class Call>
 int within_run(knn_index *idx, const WithinCall &w, Call call)
 {
-    const bool routed = (w.form & kRouted) != 0u, self = (w.form & kSelf) != 0u;
+    const bool routed = (w.form & kRouted) != 0u, self = (w.form & kSelf) != 0u, masked = (w.form & kMasked) != 0u;
     std::lock_guard<std::recursive_mutex> lock(idx->mu);
     if (self && (w.row_first > idx->n || (long long)w.m > idx->n - w.row_first))
         return fail_in(KNN_EINVAL, w.who, "row_first + rows above the shard's rows");
@@ -1447,6 +1461,12 @@ int within_run(knn_index *idx, const WithinCall &w, Call call)
         KNN_TRY(slot_buffer_grow(ts.count, ts.count_bytes, plan.scratch_bytes));
         call.scratch = (unsigned *)ts.count;
     }
+    if (masked) {
+        knn_index::TopkSlot &ts = idx->topk[w.slot];
+        KNN_TRY(slot_buffer_grow(ts.mask, ts.mask_bytes, knn_masked_plan(idx->k, w.m, 0, idx->n, idx->num_cu, false).mask_bytes));
+        call.mask = w.mask;
+        call.mask_scratch = ts.mask;
+    }
     KNN_TRY(take_events(idx, call));
     switch (plan.way) {
     case QueryWay::Grid:
@@ -1462,6 +1482,10 @@ int within_run(knn_index *idx, const WithinCall &w, Call call)
     default:
         if (self) {   // (ungated, the self-scan records the call's events itself)
             HIP_TRY(self_within(call, w.row_first));
+            break;
+        }
+        if (masked) {   // (ungated, the masked scan records the call's events itself)
+            HIP_TRY(masked_within(call, (w.flags & KNN_QUERY_INIT_KEYS) != 0u));
             break;
         }
         if (call.ev0)
@@ -1747,23 +1771,9 @@ int knn_index_query_topk_masked(knn_index *idx, int slot, int m, int K, const fl
 int knn_index_count_within_masked(knn_index *idx, int slot, int m, const float *queries_dev, float max_dist2,
                                   const unsigned *mask_dev, unsigned *counts_dev, void *stream, unsigned flags)
 {
-    const WithinCall w = {"knn_index_count_within_masked", 0u, slot, m, queries_dev, 0, nullptr, max_dist2, stream, flags};
+    const WithinCall w = {"knn_index_count_within_masked", kMasked, slot, m, queries_dev, 0, nullptr, max_dist2, stream, flags, mask_dev};
     KNN_TRY(within_check(w, {{!queries_dev || !mask_dev || !counts_dev, "null queries, mask or counts"}}, idx));
-    std::lock_guard<std::recursive_mutex> lock(idx->mu);
-    DeviceGuard guard(idx->device);
-    if (!guard.ok)
-        return fail_in(KNN_EHIP, w.who, "hipSetDevice failed");
-    // one way on every index: no layout is consulted
-    CountCall call = counts_into(counts_dev);
-    KNN_TRY(within_begin(idx, w, queries_dev, call));
-    if (idx->n == 0)   // an empty shard adds nothing
-        return KNN_OK;
-    const MaskedPlan plan = knn_masked_plan(idx->k, m, 0, idx->n, idx->num_cu, (flags & KNN_QUERY_INIT_KEYS) != 0u);
-    knn_index::TopkSlot &ts = idx->topk[slot];
-    KNN_TRY(slot_buffer_grow(ts.mask, ts.mask_bytes, plan.mask_bytes));
-    KNN_TRY(take_events(idx, call));
-    HIP_TRY(knn_masked_count_launch(call, plan, mask_dev, ts.mask));
-    return KNN_OK;
+    return within_run(idx, w, counts_into(counts_dev));   // (not routed: one way on every index, no layout is consulted)
 }
 
 int knn_mask_set_rows(int device, long long n_local, const unsigned *rows_dev, long long count, int value, unsigned *mask_dev,
@@ -1836,24 +1846,10 @@ int knn_index_list_within_masked(knn_index *idx, int slot, int m, const float *q
                                  const unsigned long long *offsets_dev, unsigned *fill_dev, unsigned long long *keys_dev, void *stream,
                                  unsigned flags)
 {
-    const WithinCall w = {"knn_index_list_within_masked", 0u, slot, m, queries_dev, 0, nullptr, max_dist2, stream, flags};
+    const WithinCall w = {"knn_index_list_within_masked", kMasked, slot, m, queries_dev, 0, nullptr, max_dist2, stream, flags, mask_dev};
     KNN_TRY(within_check(w, {{!queries_dev, "null queries"}, {!mask_dev, "null mask"}, {!offsets_dev || !fill_dev || !keys_dev, kNullLists}},
                          idx));
-    std::lock_guard<std::recursive_mutex> lock(idx->mu);
-    DeviceGuard guard(idx->device);
-    if (!guard.ok)
-        return fail_in(KNN_EHIP, w.who, "hipSetDevice failed");
-    // one way on every index: no layout is consulted
-    ListCall call = lists_into(offsets_dev, fill_dev, keys_dev);
-    KNN_TRY(within_begin(idx, w, queries_dev, call));
-    if (idx->n == 0)   // an empty shard appends nothing
-        return KNN_OK;
-    const MaskedListsPlan plan = knn_masked_lists_plan(idx->k, m, 0, idx->n, idx->num_cu, (flags & KNN_QUERY_INIT_KEYS) != 0u);
-    knn_index::TopkSlot &ts = idx->topk[slot];
-    KNN_TRY(slot_buffer_grow(ts.mask, ts.mask_bytes, plan.cut.mask_bytes));
-    KNN_TRY(take_events(idx, call));
-    HIP_TRY(knn_masked_list_launch(call, plan, mask_dev, ts.mask));
-    return KNN_OK;
+    return within_run(idx, w, lists_into(offsets_dev, fill_dev, keys_dev));   // (not routed: one way on every index)
 }
 
 int knn_index_query_topk_large_masked(knn_index *idx, int slot, int m, int K, const float *queries_dev, float max_dist2,
@@ -2070,6 +2066,28 @@ int knn_index_self_list_within_routed(knn_index *idx, int slot, long long row_fi
     const WithinCall w = {"knn_index_self_list_within_routed", kCap | kRouted | kSelf, slot, rows, nullptr, row_first, max_dist2_dev, cap,
                           stream, flags};
     KNN_TRY(within_check(w, {{!offsets_dev || !fill_dev || !keys_dev, kNullLists}}, idx));
+    return within_run(idx, w, lists_into(offsets_dev, fill_dev, keys_dev));
+}
+
+// ---- over a subset of the rows, on the pruned ways (include/knn_mi355x.h 2l; knn_masked_routed.hip, knn_grid.hip) ---------------
+// (one message per rule, in the header's order, the index last: tests/test_masked_routed_logic.py tells them apart without a GPU)
+int knn_index_count_within_masked_routed(knn_index *idx, int slot, int m, const float *queries_dev, float max_dist2,
+                                         const unsigned *mask_dev, unsigned *counts_dev, void *stream, unsigned flags)
+{
+    const WithinCall w = {"knn_index_count_within_masked_routed", kRouted | kMasked, slot, m, queries_dev, 0, nullptr, max_dist2, stream,
+                          flags, mask_dev};
+    KNN_TRY(within_check(w, {{!queries_dev, "null queries"}, {!mask_dev, "null mask"}, {!counts_dev, "null counts"}}, idx));
+    return within_run(idx, w, counts_into(counts_dev));
+}
+
+int knn_index_list_within_masked_routed(knn_index *idx, int slot, int m, const float *queries_dev, float max_dist2,
+                                        const unsigned *mask_dev, const unsigned long long *offsets_dev, unsigned *fill_dev,
+                                        unsigned long long *keys_dev, void *stream, unsigned flags)
+{
+    const WithinCall w = {"knn_index_list_within_masked_routed", kRouted | kMasked, slot, m, queries_dev, 0, nullptr, max_dist2, stream,
+                          flags, mask_dev};
+    KNN_TRY(within_check(w, {{!queries_dev, "null queries"}, {!mask_dev, "null mask"}, {!offsets_dev || !fill_dev || !keys_dev, kNullLists}},
+                         idx));
     return within_run(idx, w, lists_into(offsets_dev, fill_dev, keys_dev));
 }
 

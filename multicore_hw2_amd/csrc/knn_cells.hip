@@ -3213,7 +3213,7 @@ hipError_t knn_cells_query_count(FilterState &st, FilterWorkspace &w, const Cell
     b.radii = call.radii;
     FTRY(cells_pass_front(w, b, cells_records_kernel(tp.scan), call.radii ? CellPrepForm::CountEach : CellPrepForm::Count, timed));
     FTRY(knn_count_records_finish(call, cells_pass_records(st, w), call.scratch));
-    // gated: the exact count — a routed self call: the self-scan — answers a pass that raised FALLBACK (its scratch was not committed)
+    // gated: the exact count — a routed self call: the self-scan, a masked one: the masked scan — answers a pass that raised FALLBACK (its scratch was not committed)
     return knn_gated_count_launch(call, w.ctl_cur + KNN_CTL_FALLBACK);
 }
 
@@ -3235,8 +3235,8 @@ hipError_t knn_cells_query_list(FilterState &st, FilterWorkspace &w, const CellT
     b.radii = call.radii;
     FTRY(cells_pass_front(w, b, cells_records_kernel(tp.scan), call.radii ? CellPrepForm::CountEach : CellPrepForm::Count, timed));
     FTRY(knn_list_records_finish(call, cells_pass_records(st, w)));
-    // gated: the exact list — a routed self call: the self-scan — answers a pass that raised FALLBACK (its scratch cursor was not
-    // committed)
+    // gated: the exact list — a routed self call: the self-scan, a masked one: the masked scan — answers a pass that raised
+    // FALLBACK (its scratch cursor was not committed)
     return knn_gated_list_launch(call, w.ctl_cur + KNN_CTL_FALLBACK);
 }
 

@@ -168,8 +168,13 @@ struct CountCall {
     // >= 0: a routed call about the shard's own rows (2k): query j is LOCAL row self_first + j (q = r + self_first * k), which is
     // no candidate for itself; the grid and cell ways launch their self forms and the gated self-scan.  -1: a plain call
     long long self_first = -1;
+    // nullable; a routed call over a subset of the rows (2l): device (n + 31) / 32 words, bit i % 32 of word i / 32 admits LOCAL
+    // row i.  The grid and cell ways launch their masked forms and the gated masked scan, which works in mask_scratch (the slot's
+    // mask scratch, MaskedPlan::mask_bytes).  Not with radii, not with self_first >= 0
+    const unsigned *mask = nullptr;
+    u64 *mask_scratch = nullptr;
 
-    // queries [q0, q0 + mb) of the call: a pass of the cell-pruned way
+    // queries [q0, q0 + mb) of the call: a pass of the cell-pruned way (the mask belongs to the rows, not to the queries: it stays)
     CountCall pass(int q0, int mb) const
     {
         CountCall c = *this;
@@ -213,8 +218,11 @@ struct ListCall {
     unsigned *scratch = nullptr;   // the slot's count scratch [m]: the scratch cursor of the grid and cell ways (the exact way does not use it)
     const float *radii = nullptr;  // nullable; a radius per query, device [m], max_dist2 the cap: as CountCall::radii
     long long self_first = -1;     // >= 0: a routed call about the shard's own rows, as CountCall::self_first
+    const unsigned *mask = nullptr;   // nullable; a routed call over a subset of the rows, as CountCall::mask ...
+    u64 *mask_scratch = nullptr;      // ... and the slot's mask scratch (MaskedListsPlan::cut.mask_bytes)
 
-    // queries [q0, q0 + mb) of the call: a pass of the cell-pruned way (offsets are absolute: keys stays)
+    // queries [q0, q0 + mb) of the call: a pass of the cell-pruned way (offsets are absolute: keys stays; so does the mask, which
+    // belongs to the rows)
     ListCall pass(int q0, int mb) const
     {
         ListCall c = *this;
@@ -256,6 +264,11 @@ hipError_t knn_list_each_records_finish(const ListCall &c, const TopkRecords &rs
 // query's radius is c.max_dist2.  The plain functions hand such a pass over after their own checks, ahead of the each-forms.
 hipError_t knn_count_self_records_finish(const CountCall &c, const TopkRecords &rs, unsigned *qcount);
 hipError_t knn_list_self_records_finish(const ListCall &c, const TopkRecords &rs);
+// ... and for a pass of a routed call over a subset of the rows (c.mask; knn_masked_routed.hip): the scalar forms' walks, a candidate
+// whose LOCAL row's bit in c.mask is clear dropped.  The plain functions hand such a pass over first of all; with c.radii or
+// c.self_first >= 0 it is hipErrorInvalidValue.
+hipError_t knn_count_masked_records_finish(const CountCall &c, const TopkRecords &rs, unsigned *qcount);
+hipError_t knn_list_masked_records_finish(const ListCall &c, const TopkRecords &rs);
 
 // ---- top-K beyond 64 (knn_select.hip; knn_index_query_topk_large; DESIGN §4.6 "Top-K beyond 64") --------------------------------
 #define KNN_TOPK_LARGE_MAX 4096   // largest K of knn_index_query_topk_large (= KNN_SORT_LDS_KEYS: a list sorts in LDS)
@@ -306,13 +319,16 @@ MaskedPlan knn_masked_plan(int k, int m, int K, long long n, int num_cu, bool in
 // finite and <= c.max_dist2), sorted, padded with KNN_KEY_INIT; 1 <= K <= KNN_TOPK_MAX.  mask: (c.n + 31) / 32 words, bit i % 32
 // of word i / 32 admits local row i.  scratch: p.mask_bytes; c.part: p.part_bytes; both stream-ordered.  c.n > 0.
 hipError_t knn_masked_topk_launch(const TopkCall &c, const MaskedPlan &p, const unsigned *mask, u64 *scratch);
-// c.counts[j] += the number of those rows.  c.n > 0.
-hipError_t knn_masked_count_launch(const CountCall &c, const MaskedPlan &p, const unsigned *mask, u64 *scratch);
+// c.counts[j] += the number of those rows.  c.n > 0.  gate != nullptr: every kernel of the sequence — the prefix's too — returns at
+// once unless *gate != 0 (the exact answer behind a pruned way of a routed masked call); the call's events are not recorded then.
+hipError_t knn_masked_count_launch(const CountCall &c, const MaskedPlan &p, const unsigned *mask, u64 *scratch,
+                                   const unsigned *gate = nullptr);
 // The mask bits of rows[0 .. count) that lie in 0 .. n - 1 <- value (0 or 1).
 hipError_t knn_mask_set_rows_launch(long long n, const unsigned *rows, long long count, int value, unsigned *mask, hipStream_t stream);
 // The granule counts and their prefix of one call's mask into the mask scratch (p.mask_bytes): what every masked call launches
-// first, once, ahead of every chunk and pass.  n > 0.
-hipError_t knn_masked_prefix_launch(const MaskedPlan &p, long long n, const unsigned *mask, u64 *scratch, hipStream_t stream);
+// first, once, ahead of every chunk and pass.  n > 0.  gate: as knn_masked_count_launch's.
+hipError_t knn_masked_prefix_launch(const MaskedPlan &p, long long n, const unsigned *mask, u64 *scratch, hipStream_t stream,
+                                    const unsigned *gate = nullptr);
 
 // ---- lists and top-K beyond 64 over a subset of the rows (knn_masked_lists.hip; DESIGN §4.6 "Lists and large K over a subset of
 // the rows") ------------------------------------------------------------------------------------------------------------------
@@ -337,7 +353,9 @@ struct MaskedListsPlan {
 };
 MaskedListsPlan knn_masked_lists_plan(int k, int m, int K, long long n, int num_cu, bool init);
 // knn_exact_list_launch's contract over the rows whose mask bit is set.  scratch: p.cut.mask_bytes, stream-ordered.  c.n > 0.
-hipError_t knn_masked_list_launch(const ListCall &c, const MaskedListsPlan &p, const unsigned *mask, u64 *scratch);
+// gate: as knn_masked_count_launch's.
+hipError_t knn_masked_list_launch(const ListCall &c, const MaskedListsPlan &p, const unsigned *mask, u64 *scratch,
+                                  const unsigned *gate = nullptr);
 // knn_topk_large_launch's contract over the rows whose mask bit is set.  scratch: p.cut.mask_bytes; c.part: p.select_bytes.  c.n > 0.
 hipError_t knn_masked_large_launch(const TopkCall &c, const MaskedListsPlan &p, const unsigned *mask, u64 *scratch,
                                    const unsigned **tie_word);
@@ -364,13 +382,19 @@ hipError_t knn_self_topk_launch(const TopkCall &c, long long row_first);
 // cell-pruned pass of a routed self call, as knn_exact_count_launch's gate; the call's events are not recorded then.
 hipError_t knn_self_count_launch(const CountCall &c, long long row_first, const unsigned *gate = nullptr);
 hipError_t knn_self_list_launch(const ListCall &c, long long row_first, const unsigned *gate = nullptr);
-// The exact answer behind a pruned way, gated: the self-scan for a routed self call (c.self_first >= 0), else the exact count / list.
+// The exact answer behind a pruned way, gated: the masked scan for a routed masked call (c.mask; the plan is host arithmetic on the
+// pass's own m — the mask scratch's layout depends on the rows alone), the self-scan for a routed self call (c.self_first >= 0),
+// else the exact count / list.
 static inline hipError_t knn_gated_count_launch(const CountCall &c, const unsigned *gate)
 {
+    if (c.mask)
+        return knn_masked_count_launch(c, knn_masked_plan(c.k, c.m, 0, c.n, c.num_cu, false), c.mask, c.mask_scratch, gate);
     return c.self_first >= 0 ? knn_self_count_launch(c, c.self_first, gate) : knn_exact_count_launch(c, gate);
 }
 static inline hipError_t knn_gated_list_launch(const ListCall &c, const unsigned *gate)
 {
+    if (c.mask)
+        return knn_masked_list_launch(c, knn_masked_lists_plan(c.k, c.m, 0, c.n, c.num_cu, false), c.mask, c.mask_scratch, gate);
     return c.self_first >= 0 ? knn_self_list_launch(c, c.self_first, gate) : knn_exact_list_launch(c, gate);
 }
 // out[j][0 .. K) <- lists[j][0 .. K] (sorted, K + 1 <= KNN_TOPK_MAX keys) without the real key that carries the global number of

@@ -14,6 +14,7 @@
 // (CountCall::pass advances it with the queries).
 #define KNN_REC_EACH_FORM /* what an each-form lacks: an own row */ \
     constexpr int FORM = KNN_REC_EACH;                              \
+    constexpr const unsigned *mask = nullptr;                       \
     constexpr unsigned first = 0u
 __global__ __launch_bounds__(KNN_BLOCK) void knn_count_each_rerank_kernel(const float *__restrict__ Q, const float *__restrict__ R, int k,
                                                                          long long n, const u64 *__restrict__ rec,

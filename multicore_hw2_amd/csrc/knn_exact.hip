@@ -1481,6 +1481,7 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_count_commit_kernel(const unsig
     constexpr int FORM = KNN_REC_SCALAR;     \
     constexpr const float *radii = nullptr;  \
     constexpr unsigned first = 0u;           \
+    constexpr const unsigned *mask = nullptr; \
     const float cap = max_dist2
 __global__ __launch_bounds__(KNN_BLOCK) void knn_count_rerank_kernel(const float *__restrict__ Q, const float *__restrict__ R, int k,
                                                                     long long n, const u64 *__restrict__ rec,
@@ -1570,6 +1571,8 @@ hipError_t knn_count_records_finish(const CountCall &c, const TopkRecords &rs, u
     hipStream_t s = c.stream;
     if (rs.rec_rows || !rs.perm || !rs.pos_norms || !qcount)
         return hipErrorInvalidValue;
+    if (c.mask)
+        return knn_count_masked_records_finish(c, rs, qcount);   // (knn_masked_routed.hip)
     if (c.self_first >= 0)
         return knn_count_self_records_finish(c, rs, qcount);   // (knn_self_routed.hip)
     if (c.radii)
@@ -1705,50 +1708,10 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_list_outlier_kernel(const float
 // offsets[0] = 0, offsets[j + 1] = offsets[j] + counts[j]: ONE block walks the counts in chunks of 8 per thread and carries a 64-bit
 // running sum from chunk to chunk (m is small next to n: no multi-block scan).  Per chunk: a thread sums its 8 counts, the waves
 // scan the thread sums by shuffles, the wave totals meet in LDS.
-#define KNN_OFFSETS_PER_THREAD 8
 __global__ __launch_bounds__(KNN_BLOCK) void knn_counts_to_offsets_kernel(const unsigned *__restrict__ counts, int m,
                                                                          u64 *__restrict__ offsets)
 {
-    __shared__ u64 wave_total[KNN_WAVES];
-    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    u64 running = 0ull;
-    if (threadIdx.x == 0)
-        offsets[0] = 0ull;
-    for (long long c0 = 0; c0 < m; c0 += (long long)KNN_BLOCK * KNN_OFFSETS_PER_THREAD) {
-        const long long j0 = c0 + (long long)threadIdx.x * KNN_OFFSETS_PER_THREAD;
-        unsigned v[KNN_OFFSETS_PER_THREAD];
-        u64 mine = 0ull;
-#pragma unroll
-        for (int t = 0; t < KNN_OFFSETS_PER_THREAD; ++t) {
-            v[t] = j0 + t < m ? counts[j0 + t] : 0u;
-            mine += v[t];
-        }
-        u64 incl = mine;   // inclusive scan of the thread sums within the wave
-#pragma unroll
-        for (int d = 1; d < KNN_WAVE; d <<= 1) {
-            const u64 o = __shfl_up(incl, d, KNN_WAVE);
-            if (lane >= (unsigned)d)
-                incl += o;
-        }
-        if (lane == KNN_WAVE - 1)
-            wave_total[wave] = incl;
-        __syncthreads();
-        u64 before = running, total = 0ull;
-#pragma unroll
-        for (unsigned w = 0; w < KNN_WAVES; ++w) {
-            before += w < wave ? wave_total[w] : 0ull;
-            total += wave_total[w];
-        }
-        u64 sum = before + incl - mine;   // everything ahead of this thread's first count
-#pragma unroll
-        for (int t = 0; t < KNN_OFFSETS_PER_THREAD; ++t) {
-            sum += v[t];
-            if (j0 + t < m)
-                offsets[j0 + t + 1] = sum;
-        }
-        running += total;
-        __syncthreads();   // (wave_total is rewritten by the next chunk)
-    }
+#include "knn_counts_to_offsets_body.inc"
 }
 
 // One block per segment: the first cnt = min(fill, room) keys ascending, by a bitonic network whose comparators all put the smaller
@@ -1828,6 +1791,8 @@ hipError_t knn_list_records_finish(const ListCall &c, const TopkRecords &rs)
     hipStream_t s = c.stream;
     if (rs.rec_rows || !rs.perm || !rs.pos_norms || !c.scratch)
         return hipErrorInvalidValue;
+    if (c.mask)
+        return knn_list_masked_records_finish(c, rs);   // (knn_masked_routed.hip)
     if (c.self_first >= 0)
         return knn_list_self_records_finish(c, rs);   // (knn_self_routed.hip)
     if (c.radii)

@@ -76,6 +76,8 @@ __device__ __forceinline__ void list_put(unsigned *__restrict__ cursor, u64 *__r
         keys[off + p] = key;
 }
 
+#define KNN_OFFSETS_PER_THREAD 8   // counts a thread takes per chunk in knn_counts_to_offsets_body.inc
+
 // One (record, row) pair: the packed key of row `reg` of record e for its query, ~0 when there is nothing to evaluate.
 template <int K>
 __device__ __forceinline__ u64 rerank_pair(const float *__restrict__ Q, const float *__restrict__ R, int k, long long n,
@@ -142,13 +144,17 @@ __device__ __forceinline__ u64 rerank_pair(const float *__restrict__ Q, const fl
 }
 
 // ---- a cell-pruned count or list pass behind its record-only scan: records and out-of-box rows -> hits ------------------------
-// Four walks — count re-rank, count outlier, list re-rank, list outlier: knn_rec_*_body.inc — in three forms each, kernels of
+// Four walks — count re-rank, count outlier, list re-rank, list outlier: knn_rec_*_body.inc — in four forms each, kernels of
 // their own that include the walk with FORM fixed: the scalar radius (knn_exact.hip), a radius per query (knn_each.hip: one more
 // compare, radii[query] under cap), the shard's own rows (knn_self_routed.hip: radii nullable, and the query's own LOCAL row
-// dropped).  A hit: E finite, E <= the query's radius and E <= cap, fp32 compares with equality inside; a NaN or negative radius
-// fails the first for every row.
-enum { KNN_REC_SCALAR = 0, KNN_REC_EACH = 1, KNN_REC_SELF = 2 };
-#define KNN_REC_RADIUS(qv) (FORM == KNN_REC_SCALAR ? cap : FORM == KNN_REC_EACH ? radii[qv] : radii ? radii[qv] : cap)
+// dropped), a subset of the rows (knn_masked_routed.hip: the scalar radius, and a row whose bit in `mask` is clear dropped).  A hit:
+// E finite, E <= the query's radius and E <= cap, fp32 compares with equality inside; a NaN or negative radius fails the first for
+// every row.  Every including kernel names `mask`: the masked forms as their argument, the others as a constant null.
+enum { KNN_REC_SCALAR = 0, KNN_REC_EACH = 1, KNN_REC_SELF = 2, KNN_REC_MASKED = 3 };
+#define KNN_REC_RADIUS(qv) \
+    (FORM == KNN_REC_SCALAR || FORM == KNN_REC_MASKED ? cap : FORM == KNN_REC_EACH ? radii[qv] : radii ? radii[qv] : cap)
+// The mask bit of LOCAL row `row` (below the shard's rows: no word beyond (n + 31) / 32 is read).
+#define KNN_REC_ADMITS(row) (((mask[(row) >> 5] >> ((row) & 31u)) & 1u) != 0u)
 
 // The launches of such a pass, in order: the re-rank of the nlists per-list slices, the re-rank of the shared overflow area as a
 // list of one (its `want > slice` rule raises FALLBACK when over-full), the outlier grid (min(ceil(n_outliers / KNN_BLOCK), 64), m),

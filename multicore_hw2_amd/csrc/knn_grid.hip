@@ -431,7 +431,7 @@ __global__ __launch_bounds__(GRID_BLOCK) void knn_grid_within_kernel(const float
 }
 
 // ---- counts and lists within a radius (KNN_QUERY_COUNT_GRID) ---------------------------------------
-// Six entry points of one walk, knn_grid_radius_body.inc (the description is there): each fixes the switches LIST, EACH and SELF
+// Eight entry points of one walk, knn_grid_radius_body.inc (the description is there): each fixes the switches LIST, EACH, SELF and MASKED
 // and names, as null or zero constants, the arguments it does not take.  (A body file and not a function template, as the top-K
 // kernels above: every form keeps its argument list, its name and its code.)
 #define GRID_RADIUS_NO_LIST /* a count form reserves and stores nothing */   \
@@ -440,6 +440,9 @@ __global__ __launch_bounds__(GRID_BLOCK) void knn_grid_within_kernel(const float
     constexpr unsigned *cursor = nullptr;                                    \
     constexpr u64 *keys = nullptr
 #define GRID_RADIUS_NO_SELF /* no own row to drop */ constexpr unsigned first = 0u
+#define GRID_RADIUS_NO_MASK /* every row admitted */ \
+    constexpr bool MASKED = false;                   \
+    constexpr const unsigned *mask = nullptr
 
 // knn_index_count_within
 template <int KD>
@@ -456,6 +459,7 @@ __global__ __launch_bounds__(GRID_BLOCK) void knn_grid_count_kernel(const float 
     const float cap = max_dist2;
     GRID_RADIUS_NO_LIST;
     GRID_RADIUS_NO_SELF;
+    GRID_RADIUS_NO_MASK;
 #include "knn_grid_radius_body.inc"
 }
 
@@ -475,6 +479,7 @@ __global__ __launch_bounds__(GRID_BLOCK) void knn_grid_list_kernel(const float *
     constexpr const float *radii = nullptr;
     const float cap = max_dist2;
     GRID_RADIUS_NO_SELF;
+    GRID_RADIUS_NO_MASK;
 #include "knn_grid_radius_body.inc"
 }
 
@@ -492,6 +497,7 @@ __global__ __launch_bounds__(GRID_BLOCK) void knn_grid_each_count_kernel(const f
     constexpr const unsigned *orig = nullptr;
     GRID_RADIUS_NO_LIST;
     GRID_RADIUS_NO_SELF;
+    GRID_RADIUS_NO_MASK;
 #include "knn_grid_radius_body.inc"
 }
 
@@ -509,6 +515,7 @@ __global__ __launch_bounds__(GRID_BLOCK) void knn_grid_each_list_kernel(const fl
     constexpr bool LIST = true, EACH = true, SELF = false;
     constexpr unsigned *out = nullptr;
     GRID_RADIUS_NO_SELF;
+    GRID_RADIUS_NO_MASK;
 #include "knn_grid_radius_body.inc"
 }
 
@@ -525,6 +532,7 @@ __global__ __launch_bounds__(GRID_BLOCK) void knn_grid_self_count_kernel(const f
 #pragma clang fp contract(off)
     constexpr bool LIST = false, SELF = true;
     GRID_RADIUS_NO_LIST;
+    GRID_RADIUS_NO_MASK;
 #include "knn_grid_radius_body.inc"
 }
 
@@ -541,10 +549,48 @@ __global__ __launch_bounds__(GRID_BLOCK) void knn_grid_self_list_kernel(const fl
 #pragma clang fp contract(off)
     constexpr bool LIST = true, SELF = true;
     constexpr unsigned *out = nullptr;
+    GRID_RADIUS_NO_MASK;
+#include "knn_grid_radius_body.inc"
+}
+
+// over a subset of the rows on the grid (include/knn_mi355x.h 2l): knn_index_count_within_masked_routed, knn_index_list_within_masked_routed
+template <int KD>
+__global__ __launch_bounds__(GRID_BLOCK) void knn_grid_masked_count_kernel(const float *__restrict__ Q, int m, GridGeom gg,
+                                                                           const unsigned *__restrict__ start,
+                                                                           const f4g *__restrict__ pts, const unsigned *__restrict__ orig,
+                                                                           const unsigned *__restrict__ mask, unsigned *__restrict__ out,
+                                                                           int rmax, unsigned *__restrict__ giveup,
+                                                                           unsigned *__restrict__ giveup_next, float max_dist2)
+{
+#pragma clang fp contract(off)
+    constexpr bool LIST = false, EACH = false, SELF = false, MASKED = true;
+    constexpr const float *radii = nullptr;
+    const float cap = max_dist2;
+    GRID_RADIUS_NO_LIST;
+    GRID_RADIUS_NO_SELF;
+#include "knn_grid_radius_body.inc"
+}
+
+template <int KD>
+__global__ __launch_bounds__(GRID_BLOCK) void knn_grid_masked_list_kernel(const float *__restrict__ Q, int m, GridGeom gg,
+                                                                          const unsigned *__restrict__ start,
+                                                                          const f4g *__restrict__ pts, const unsigned *__restrict__ orig,
+                                                                          const unsigned *__restrict__ mask, long long base,
+                                                                          const u64 *__restrict__ offsets, unsigned *__restrict__ cursor,
+                                                                          u64 *__restrict__ keys, int rmax, unsigned *__restrict__ giveup,
+                                                                          unsigned *__restrict__ giveup_next, float max_dist2)
+{
+#pragma clang fp contract(off)
+    constexpr bool LIST = true, EACH = false, SELF = false, MASKED = true;
+    constexpr unsigned *out = nullptr;
+    constexpr const float *radii = nullptr;
+    const float cap = max_dist2;
+    GRID_RADIUS_NO_SELF;
 #include "knn_grid_radius_body.inc"
 }
 #undef GRID_RADIUS_NO_LIST
 #undef GRID_RADIUS_NO_SELF
+#undef GRID_RADIUS_NO_MASK
 
 // ---- host -------------------------------------------------------------------------------------------
 #define GTRY(call)                     \
@@ -847,7 +893,7 @@ hipError_t knn_grid_query_topk(const GridState *gs, const GridTopkPlan &plan, in
 hipError_t knn_grid_query_count(const GridState *gs, int rmax, int slot, const CountCall &c, const unsigned **gate_out)
 {
     *gate_out = nullptr;
-    if (!gs || !gs->usable || c.m <= 0 || !c.scratch || !c.counts || rmax < 0)
+    if (!gs || !gs->usable || c.m <= 0 || !c.scratch || !c.counts || rmax < 0 || (c.mask && (c.self_first >= 0 || c.radii)))
         return hipErrorInvalidValue;
     hipStream_t s = c.stream;
     GridBatch b;
@@ -856,7 +902,10 @@ hipError_t knn_grid_query_count(const GridState *gs, int rmax, int slot, const C
     hipLaunchKernelGGL((knn_grid_self_count_kernel<KDV, EACHV>), b.grid, b.block, 0, s, c.q, c.m, gs->geom, gs->start, gs->pts,      \
                        gs->orig, (unsigned)c.self_first, c.scratch, rmax, b.giveup, b.giveup_next, c.radii, c.max_dist2)
 #define GRID_COUNT(KDV)                                                                                                              \
-    if (c.self_first >= 0 && c.radii)                                                                                                \
+    if (c.mask)   /* over a subset of the rows (2l), scalar radius */                                                                \
+        hipLaunchKernelGGL(knn_grid_masked_count_kernel<KDV>, b.grid, b.block, 0, s, c.q, c.m, gs->geom, gs->start, gs->pts,         \
+                           gs->orig, c.mask, c.scratch, rmax, b.giveup, b.giveup_next, c.max_dist2);                                 \
+    else if (c.self_first >= 0 && c.radii)                                                                                           \
         GRID_COUNT_SELF(KDV, true);                                                                                                  \
     else if (c.self_first >= 0)                                                                                                      \
         GRID_COUNT_SELF(KDV, false);                                                                                                 \
@@ -876,7 +925,7 @@ hipError_t knn_grid_query_count(const GridState *gs, int rmax, int slot, const C
 #undef GRID_COUNT_SELF
     GTRY(grid_batch_end(b, s, c.ev1, gate_out));
     GTRY(knn_count_commit_launch(c.m, c.scratch, c.counts, b.giveup, s));
-    return knn_gated_count_launch(c, b.giveup);   // (a routed self call: the gated self-scan)
+    return knn_gated_count_launch(c, b.giveup);   // (a routed self call: the gated self-scan; a masked one: the gated masked scan)
 }
 
 // The whole list call on the grid way (KNN_QUERY_COUNT_GRID), asynchronous on c.stream: c.scratch [m] <- c.fill, the grid kernel
@@ -887,7 +936,8 @@ hipError_t knn_grid_query_count(const GridState *gs, int rmax, int slot, const C
 hipError_t knn_grid_query_list(const GridState *gs, int rmax, int slot, const ListCall &c, const unsigned **gate_out)
 {
     *gate_out = nullptr;
-    if (!gs || !gs->usable || c.m <= 0 || !c.scratch || !c.fill || !c.offsets || !c.keys || c.gids || rmax < 0)
+    if (!gs || !gs->usable || c.m <= 0 || !c.scratch || !c.fill || !c.offsets || !c.keys || c.gids || rmax < 0 ||
+        (c.mask && (c.self_first >= 0 || c.radii)))
         return hipErrorInvalidValue;
     hipStream_t s = c.stream;
     GTRY(hipMemcpyAsync(c.scratch, c.fill, (size_t)c.m * sizeof(unsigned), hipMemcpyDeviceToDevice, s));
@@ -898,7 +948,10 @@ hipError_t knn_grid_query_list(const GridState *gs, int rmax, int slot, const Li
                        gs->orig, (unsigned)c.self_first, c.base, c.offsets, c.scratch, c.keys, rmax, b.giveup, b.giveup_next,        \
                        c.radii, c.max_dist2)
 #define GRID_LIST(KDV)                                                                                                               \
-    if (c.self_first >= 0 && c.radii)                                                                                                \
+    if (c.mask)   /* over a subset of the rows (2l), scalar radius */                                                                \
+        hipLaunchKernelGGL(knn_grid_masked_list_kernel<KDV>, b.grid, b.block, 0, s, c.q, c.m, gs->geom, gs->start, gs->pts,          \
+                           gs->orig, c.mask, c.base, c.offsets, c.scratch, c.keys, rmax, b.giveup, b.giveup_next, c.max_dist2);      \
+    else if (c.self_first >= 0 && c.radii)                                                                                           \
         GRID_LIST_SELF(KDV, true);                                                                                                   \
     else if (c.self_first >= 0)                                                                                                      \
         GRID_LIST_SELF(KDV, false);                                                                                                  \
@@ -918,7 +971,7 @@ hipError_t knn_grid_query_list(const GridState *gs, int rmax, int slot, const Li
 #undef GRID_LIST_SELF
     GTRY(grid_batch_end(b, s, c.ev1, gate_out));
     GTRY(knn_list_commit_launch(c.m, c.scratch, c.fill, b.giveup, s));
-    return knn_gated_list_launch(c, b.giveup);   // (a routed self call: the gated self-scan)
+    return knn_gated_list_launch(c, b.giveup);   // (a routed self call: the gated self-scan; a masked one: the gated masked scan)
 }
 
 long long knn_grid_radius_rings(const GridState *gs, float max_dist2)

@@ -1,10 +1,12 @@
 // knn_grid_radius_body.inc — the one walk of the grid's radius kernels (KNN_QUERY_COUNT_GRID): included into knn_grid_count_kernel,
-// knn_grid_list_kernel, their each-forms and their self forms (knn_grid.hip), which fix three compile-time switches —
-//   LIST  a hit reserves a place and stores its key; else it bumps the lane's register;
-//   EACH  the wave's own radius radii[qi] under cap (include/knn_mi355x.h 2j); else the scalar radius cap, radii not read;
-//   SELF  query qi is the shard's LOCAL row first + qi, and that row is no hit (2k)
+// knn_grid_list_kernel, their each-forms, their self forms and their masked forms (knn_grid.hip), which fix four compile-time
+// switches —
+//   LIST    a hit reserves a place and stores its key; else it bumps the lane's register;
+//   EACH    the wave's own radius radii[qi] under cap (include/knn_mi355x.h 2j); else the scalar radius cap, radii not read;
+//   SELF    query qi is the shard's LOCAL row first + qi, and that row is no hit (2k);
+//   MASKED  a row is a hit only when the bit of its LOCAL number is set in mask (2l)
 // — and provide KD, the arguments Q, m, gg, start, pts, rmax, giveup, giveup_next by their names, and every one of orig, first,
-// base, out, offsets, cursor, keys, radii, cap: as its argument, or as a constant null / zero stand-in where the form has none.
+// base, out, offsets, cursor, keys, radii, cap, mask: as its argument, or as a constant null / zero stand-in where the form has none.
 //
 // One wave per query, the 1-NN kernel's walk: lanes take the cells of ring r, and a row is a hit when its v0 distance E is finite,
 // E <= rad and E <= cap (fp32 compares, equality inside; the scalar forms' rad is cap, so theirs is one compare).  One wave per
@@ -31,6 +33,10 @@
 // row number: another copy of the row stays a hit at distance 0.  The compare sits on the hit side, behind the distance; the walk,
 // the stop clause, the give-up word and what the commit sees are the twins'.  (The self list reads orig[p] once, before the
 // reservation; the other lists read it only at the store.)
+// MASKED: the row at position p is a hit only when bit orig[p] & 31 of mask[orig[p] >> 5] is set — the caller's mask, in the shard's
+// local row order, read by the rows inside the radius alone: the test sits behind the distance compare, as SELF's, and nothing
+// else of the walk knows of the mask (a cell is never skipped for it).  orig[p] < n, so no word beyond (n + 31) / 32 is read and
+// the bits at and beyond n in the last word belong to no row.  The masked list reads orig[p] once, before the reservation.
     if (blockIdx.x == 0 && threadIdx.x == 0)
         *giveup_next = 0u;   // (the slot's other word, as the 1-NN kernel)
     const int lane = threadIdx.x & 63;
@@ -86,11 +92,14 @@
                     acc = acc + sq;
                 }
                 if (acc < INFINITY && acc <= rad && acc <= cap) {
-                    if (!LIST) {
-                        cnt += !SELF || orig[p] != own ? 1u : 0u;
-                    } else if (SELF) {
+                    if (!LIST && MASKED) {
                         const unsigned row = orig[p];
-                        if (row != own) {
+                        cnt += (mask[row >> 5] >> (row & 31u)) & 1u;
+                    } else if (!LIST) {
+                        cnt += !SELF || orig[p] != own ? 1u : 0u;
+                    } else if (SELF || MASKED) {
+                        const unsigned row = orig[p];
+                        if (SELF ? row != own : ((mask[row >> 5] >> (row & 31u)) & 1u) != 0u) {
                             const unsigned place = atomicAdd(&cursor[qi], 1u);
                             if (place < room)
                                 keys[off + place] = ((u64)__float_as_uint(acc) << 32) | (u64)(unsigned)(base + (long long)row);

@@ -13,12 +13,19 @@
 // falls into from the prefix by a binary search every lane performs identically, and the row inside it from that granule's 32
 // words — no host synchronisation, and S is the unmasked scan's number, so the slot's per-slice lists are sized as before.  A mask is the
 // caller's and may change between calls: nothing is kept.
+//
+// Behind a pruned way of a routed masked call (2l) the count's whole sequence is gated on a device word: every kernel of it — the
+// granule counts, the prefix (a gated twin of knn_counts_to_offsets_kernel around the same block body), the scan — returns at once
+// unless *gate != 0, so the query path never synchronises with the host.  gate null: the launches of 2g, unchanged.
 #include "knn_masked_dev.h"
 
 // counts[g] <- the admitted rows of granule g: one mask word per thread (bits at and beyond n dropped), a granule per 32 lanes.
 __global__ __launch_bounds__(KNN_BLOCK) void knn_mask_granule_counts_kernel(const unsigned *__restrict__ mask, long long n, long long G,
-                                                                           unsigned *__restrict__ counts)
+                                                                           unsigned *__restrict__ counts,
+                                                                           const unsigned *__restrict__ gate)
 {
+    if (gate && *gate == 0u)
+        return;
     const long long w = (long long)blockIdx.x * KNN_BLOCK + threadIdx.x;
     const unsigned v = knn_mask_word(mask, n, w);
     unsigned c = (unsigned)__popc(v);
@@ -28,6 +35,15 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_mask_granule_counts_kernel(cons
     const long long g = w / KNN_MASK_GRANULE_WORDS;
     if ((threadIdx.x & (KNN_MASK_GRANULE_WORDS - 1)) == 0 && g < G)
         counts[g] = c;
+}
+
+// knn_counts_to_offsets_kernel behind a gate: the prefix of the granule counts of a gated masked scan.  One block.
+__global__ __launch_bounds__(KNN_BLOCK) void knn_mask_prefix_gated_kernel(const unsigned *__restrict__ counts, int m,
+                                                                         u64 *__restrict__ offsets, const unsigned *__restrict__ gate)
+{
+    if (*gate == 0u)   // (block-uniform: every thread leaves, or every thread reaches the block's barriers)
+        return;
+#include "knn_counts_to_offsets_body.inc"
 }
 
 // The mask bit of every listed row in 0 .. n - 1 <- value: one atomic on the row's word (rows may repeat and share words).
@@ -107,9 +123,11 @@ template <int KC>
 __global__ __launch_bounds__(KNN_WAVE) void knn_masked_count_kernel(const float *__restrict__ Q, const float *__restrict__ R, int k,
                                                                    int m, long long n, const unsigned *__restrict__ mask,
                                                                    const u64 *__restrict__ P, int G, float max_dist2,
-                                                                   unsigned *__restrict__ counts)
+                                                                   unsigned *__restrict__ counts, const unsigned *__restrict__ gate)
 {
 #pragma clang fp contract(off)
+    if (gate && *gate == 0u)
+        return;
     constexpr int KM = KC > 0 ? 16 * KC : 1;
     const int lane = threadIdx.x;
     const int q = blockIdx.y * KNN_WAVE + lane;
@@ -157,24 +175,29 @@ MaskedPlan knn_masked_plan(int k, int m, int K, long long n, int num_cu, bool in
 
 namespace {
 // counts and prefix of the call's mask into the slot's scratch: once per call, ahead of every chunk's scan
-hipError_t masked_prefix_launch(const MaskedPlan &p, long long n, const unsigned *mask, u64 *scratch, hipStream_t s)
+hipError_t masked_prefix_launch(const MaskedPlan &p, long long n, const unsigned *mask, u64 *scratch, hipStream_t s,
+                                const unsigned *gate = nullptr)
 {
     unsigned *counts = (unsigned *)((char *)scratch + p.counts_off);
     const long long words = p.granules * KNN_MASK_GRANULE_WORDS;
     hipLaunchKernelGGL(knn_mask_granule_counts_kernel, dim3((unsigned)knn_divup(words, KNN_BLOCK)), dim3(KNN_BLOCK), 0, s, mask, n,
-                       p.granules, counts);
+                       p.granules, counts, gate);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess)
         return e;
-    return knn_counts_to_offsets_launch(counts, (int)p.granules, scratch, s);
+    if (!gate)
+        return knn_counts_to_offsets_launch(counts, (int)p.granules, scratch, s);
+    hipLaunchKernelGGL(knn_mask_prefix_gated_kernel, dim3(1), dim3(KNN_BLOCK), 0, s, (const unsigned *)counts, (int)p.granules, scratch, gate);
+    return hipGetLastError();
 }
 }  // namespace
 
-hipError_t knn_masked_prefix_launch(const MaskedPlan &p, long long n, const unsigned *mask, u64 *scratch, hipStream_t s)
+hipError_t knn_masked_prefix_launch(const MaskedPlan &p, long long n, const unsigned *mask, u64 *scratch, hipStream_t s,
+                                    const unsigned *gate)
 {
     if (n <= 0 || !mask || !scratch || p.granules > (1ll << 22))
         return hipErrorInvalidValue;
-    return masked_prefix_launch(p, n, mask, scratch, s);
+    return masked_prefix_launch(p, n, mask, scratch, s, gate);
 }
 
 hipError_t knn_masked_topk_launch(const TopkCall &c, const MaskedPlan &p, const unsigned *mask, u64 *scratch)
@@ -224,15 +247,15 @@ hipError_t knn_masked_topk_launch(const TopkCall &c, const MaskedPlan &p, const 
     return hipSuccess;
 }
 
-hipError_t knn_masked_count_launch(const CountCall &c, const MaskedPlan &p, const unsigned *mask, u64 *scratch)
+hipError_t knn_masked_count_launch(const CountCall &c, const MaskedPlan &p, const unsigned *mask, u64 *scratch, const unsigned *gate)
 {
     hipStream_t s = c.stream;
-    if (c.m <= 0 || c.n <= 0 || !mask || !scratch || p.granules > (1ll << 22))
+    if (c.m <= 0 || c.n <= 0 || !mask || !scratch || p.granules > (1ll << 22) || c.radii || c.self_first >= 0)
         return hipErrorInvalidValue;
-    hipError_t e = masked_prefix_launch(p, c.n, mask, scratch, s);
+    hipError_t e = masked_prefix_launch(p, c.n, mask, scratch, s, gate);
     if (e != hipSuccess)
         return e;
-    if (c.ev0 && (e = hipEventRecord(c.ev0, s)) != hipSuccess)
+    if (!gate && c.ev0 && (e = hipEventRecord(c.ev0, s)) != hipSuccess)
         return e;
     for (int c0 = 0; c0 < c.m; c0 += KNN_TOPK_CHUNK) {
         const int mc = c.m - c0 < KNN_TOPK_CHUNK ? c.m - c0 : KNN_TOPK_CHUNK;
@@ -241,7 +264,7 @@ hipError_t knn_masked_count_launch(const CountCall &c, const MaskedPlan &p, cons
         const float *qc = c.q + (size_t)c0 * c.k;
 #define KNN_MASKED_COUNT(KCV)                                                                                                   \
     hipLaunchKernelGGL(knn_masked_count_kernel<KCV>, grid, block, 0, s, qc, c.r, c.k, mc, c.n, mask, (const u64 *)scratch,     \
-                       (int)p.granules, c.max_dist2, c.counts + c0)
+                       (int)p.granules, c.max_dist2, c.counts + c0, gate)
         switch ((c.k + 15) / 16) {
         case 1: KNN_MASKED_COUNT(1); break;
         case 2: KNN_MASKED_COUNT(2); break;
@@ -258,7 +281,7 @@ hipError_t knn_masked_count_launch(const CountCall &c, const MaskedPlan &p, cons
         if (e != hipSuccess)
             return e;
     }
-    if (c.ev1 && (e = hipEventRecord(c.ev1, s)) != hipSuccess)
+    if (!gate && c.ev1 && (e = hipEventRecord(c.ev1, s)) != hipSuccess)
         return e;
     return hipSuccess;
 }

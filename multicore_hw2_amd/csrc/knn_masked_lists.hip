@@ -21,9 +21,11 @@ __global__ __launch_bounds__(KNN_WAVE) void knn_masked_list_kernel(const float *
                                                                   const u64 *__restrict__ P, int G, float max_dist2, long long base,
                                                                   const unsigned *__restrict__ gids,
                                                                   const u64 *__restrict__ offsets, unsigned *__restrict__ fill,
-                                                                  u64 *__restrict__ keys)
+                                                                  u64 *__restrict__ keys, const unsigned *__restrict__ gate)
 {
 #pragma clang fp contract(off)
+    if (gate && *gate == 0u)   // (the exact answer behind a pruned way of a routed masked call, 2l; null: always)
+        return;
     constexpr int KM = KC > 0 ? 16 * KC : 1;
     const int lane = threadIdx.x;
     const int q = blockIdx.y * KNN_WAVE + lane;
@@ -168,15 +170,15 @@ MaskedListsPlan knn_masked_lists_plan(int k, int m, int K, long long n, int num_
     default: CALL(0); break;     \
     }
 
-hipError_t knn_masked_list_launch(const ListCall &c, const MaskedListsPlan &p, const unsigned *mask, u64 *scratch)
+hipError_t knn_masked_list_launch(const ListCall &c, const MaskedListsPlan &p, const unsigned *mask, u64 *scratch, const unsigned *gate)
 {
     hipStream_t s = c.stream;
-    if (c.m <= 0 || c.n <= 0 || !mask || !scratch || !c.offsets || !c.fill || !c.keys)
+    if (c.m <= 0 || c.n <= 0 || !mask || !scratch || !c.offsets || !c.fill || !c.keys || c.radii || c.self_first >= 0)
         return hipErrorInvalidValue;
-    hipError_t e = knn_masked_prefix_launch(p.cut, c.n, mask, scratch, s);
+    hipError_t e = knn_masked_prefix_launch(p.cut, c.n, mask, scratch, s, gate);
     if (e != hipSuccess)
         return e;
-    if (c.ev0 && (e = hipEventRecord(c.ev0, s)) != hipSuccess)
+    if (!gate && c.ev0 && (e = hipEventRecord(c.ev0, s)) != hipSuccess)
         return e;
     for (int c0 = 0; c0 < c.m; c0 += KNN_TOPK_CHUNK) {
         const int mc = c.m - c0 < KNN_TOPK_CHUNK ? c.m - c0 : KNN_TOPK_CHUNK;
@@ -185,14 +187,14 @@ hipError_t knn_masked_list_launch(const ListCall &c, const MaskedListsPlan &p, c
         const float *qc = c.q + (size_t)c0 * c.k;
 #define KNN_MASKED_LIST(KCV)                                                                                                   \
     hipLaunchKernelGGL(knn_masked_list_kernel<KCV>, grid, block, 0, s, qc, c.r, c.k, mc, c.n, mask, (const u64 *)scratch,     \
-                       (int)p.cut.granules, c.max_dist2, c.base, c.gids, c.offsets + c0, c.fill + c0, c.keys)
+                       (int)p.cut.granules, c.max_dist2, c.base, c.gids, c.offsets + c0, c.fill + c0, c.keys, gate)
         KNN_MASKED_FORMS(KNN_MASKED_LIST)
 #undef KNN_MASKED_LIST
         e = hipGetLastError();
         if (e != hipSuccess)
             return e;
     }
-    if (c.ev1 && (e = hipEventRecord(c.ev1, s)) != hipSuccess)
+    if (!gate && c.ev1 && (e = hipEventRecord(c.ev1, s)) != hipSuccess)
         return e;
     return hipSuccess;
 }

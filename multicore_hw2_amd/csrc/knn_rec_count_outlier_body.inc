@@ -1,8 +1,10 @@
 // knn_rec_count_outlier_body.inc — the cell-pruned count's out-of-box rows, the one walk of knn_count_outlier_kernel,
-// knn_count_each_outlier_kernel and knn_count_self_outlier_kernel (FORM and the names: as knn_rec_count_rerank_body.inc).
+// knn_count_each_outlier_kernel, knn_count_self_outlier_kernel and knn_count_masked_outlier_kernel (FORM and the names: as
+// knn_rec_count_rerank_body.inc).
 //
 // Rows outside the filter's robust box never enter the scan: every (query, listed row) pair once, with v0's arithmetic.
-// grid (row blocks, queries); one add per wave.  SELF: the listed row first + q, the query's own, is no hit.
+// grid (row blocks, queries); one add per wave.  SELF: the listed row first + q, the query's own, is no hit.  MASKED: a listed row
+// whose bit is clear is passed over before its distance is accumulated.
     if (ctl[KNN_CTL_FALLBACK] != 0u)
         return;
     const unsigned q = blockIdx.y;
@@ -12,6 +14,8 @@
     unsigned cnt = 0u;
     for (unsigned j = blockIdx.x * KNN_BLOCK + threadIdx.x; j < count; j += gridDim.x * KNN_BLOCK) {
         const unsigned row = list[j];
+        if (FORM == KNN_REC_MASKED && !KNN_REC_ADMITS(row))
+            continue;
         const float *__restrict__ r = R + (size_t)row * k;
         float acc = 0.0f;
         for (int d = 0; d < k; ++d) {

@@ -14,6 +14,10 @@
 
 #include <math.h>
 
+#define KNN_REC_SELF_FORM /* what a self form lacks: a row mask */ \
+    constexpr int FORM = KNN_REC_SELF;                             \
+    constexpr const unsigned *mask = nullptr
+
 __global__ __launch_bounds__(KNN_BLOCK) void knn_count_self_rerank_kernel(const float *__restrict__ Q, const float *__restrict__ R, int k,
                                                                          long long n, const u64 *__restrict__ rec,
                                                                          const unsigned *__restrict__ counts, unsigned nlists,
@@ -22,7 +26,7 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_count_self_rerank_kernel(const 
                                                                          const float *__restrict__ radii, float cap, unsigned first,
                                                                          unsigned *__restrict__ qcount)
 {
-    constexpr int FORM = KNN_REC_SELF;
+    KNN_REC_SELF_FORM;
 #include "knn_rec_count_rerank_body.inc"
 }
 
@@ -33,7 +37,7 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_count_self_outlier_kernel(const
                                                                           unsigned *__restrict__ qcount)
 {
 #pragma clang fp contract(off)
-    constexpr int FORM = KNN_REC_SELF;
+    KNN_REC_SELF_FORM;
 #include "knn_rec_count_outlier_body.inc"
 }
 
@@ -47,7 +51,7 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_list_self_rerank_kernel(const f
                                                                         const u64 *__restrict__ offsets, unsigned *__restrict__ cursor,
                                                                         u64 *__restrict__ keys)
 {
-    constexpr int FORM = KNN_REC_SELF;
+    KNN_REC_SELF_FORM;
 #include "knn_rec_list_rerank_body.inc"
 }
 
@@ -59,16 +63,17 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_list_self_outlier_kernel(const 
                                                                          unsigned *__restrict__ cursor, u64 *__restrict__ keys)
 {
 #pragma clang fp contract(off)
-    constexpr int FORM = KNN_REC_SELF;
+    KNN_REC_SELF_FORM;
 #include "knn_rec_list_outlier_body.inc"
 }
+#undef KNN_REC_SELF_FORM
 
 // knn_count_each_records_finish for a pass of a routed self call (c: the pass — c.self_first its first own row, c.q the rows
 // themselves; the caller has checked rs): the same launches (knn_records_finish_launches) of the self forms.
 hipError_t knn_count_self_records_finish(const CountCall &c, const TopkRecords &rs, unsigned *qcount)
 {
     hipStream_t s = c.stream;
-    if (c.self_first < 0 || c.self_first + c.m > c.n || c.q != c.r + (size_t)c.self_first * c.k)
+    if (c.mask || c.self_first < 0 || c.self_first + c.m > c.n || c.q != c.r + (size_t)c.self_first * c.k)
         return hipErrorInvalidValue;
     const unsigned first = (unsigned)c.self_first;
     return knn_records_finish_launches(
@@ -88,7 +93,7 @@ hipError_t knn_count_self_records_finish(const CountCall &c, const TopkRecords &
 hipError_t knn_list_self_records_finish(const ListCall &c, const TopkRecords &rs)
 {
     hipStream_t s = c.stream;
-    if (c.self_first < 0 || c.self_first + c.m > c.n || c.q != c.r + (size_t)c.self_first * c.k)
+    if (c.mask || c.self_first < 0 || c.self_first + c.m > c.n || c.q != c.r + (size_t)c.self_first * c.k)
         return hipErrorInvalidValue;
     const unsigned first = (unsigned)c.self_first;
     return knn_records_finish_launches(
