@@ -719,6 +719,72 @@ int knn_index_list_within_masked_routed(knn_index *idx, int slot, int m, const f
                                         const unsigned *mask_dev, const unsigned long long *offsets_dev /*[m+1]*/,
                                         unsigned *fill_dev /*[m]*/, unsigned long long *keys_dev, void *stream, unsigned flags);
 
+/* ------------------------------------------------------------------------
+ * 2m. Clusters of the radius graph: density clustering (DBSCAN), friends-of-friends groups, the connected components of "closer
+ * than r" — of the shard's own rows, straight from the index.  2i .. 2k give the radius graph's degrees and adjacency; this call
+ * gives what they are for, without the adjacency ever being stored: one degree per row, then one idempotent unite per pair of core
+ * rows within the radius, in the scans' hit path (a lock-free union-find in the labels array itself).  The device call always
+ * answers about the WHOLE shard — clusters are a property of the set — so it takes no row_first / rows window.
+ *
+ * The definition; the answer depends neither on the way nor on thread timing.
+ *   Degree.  deg(i) = the number of rows j != i (by LOCAL row number: another copy of the row counts) whose v0 distance E(i, j)
+ *     is finite and <= max_dist2 — 2i's candidate rule word for word: fp32, accumulated in dimension order, no FMA, an fp32
+ *     compare with equality inside, -0 counts as 0, +INF means no radius.
+ *   Symmetry.  E is a sum of squares of differences; (a - b) and (b - a) differ in sign alone, their squares are the same
+ *     float, and the sum runs over the dimensions in the same order: E(i, j) == E(j, i) bit for bit.  So "within the radius" is a
+ *     symmetric relation, and everything below rests on it: a pair is seen from both rows alike, by every way.
+ *   Core.  Row i is core when deg(i) + 1 >= min_pts: the row counts itself, as scikit-learn's min_samples does.
+ *   Core labels.  Two core rows within the radius of each other belong to one cluster; a cluster is a connected component of the
+ *     core rows under that relation.  labels_dev[i] of a core row = the SMALLEST local row number of a core row in its component.
+ *   Border rows.  A row that is not core but has at least one core row within the radius takes the label of the core row with
+ *     the smallest packed key (E's bits, local row number) among those: the nearest core row, the lower row number on a tie.
+ *     (A border row joins no two clusters: only core rows link.)
+ *   Noise.  Every other row gets KNN_CLUSTER_NOISE.  A row with a non-finite coordinate has deg 0: noise, or — min_pts == 1 — a
+ *     cluster of its own.
+ *   Label space.  Labels are LOCAL row numbers on every index: base_index and gids do not enter.  n_local <= INT_MAX.
+ *   core_dev, when not NULL, receives the core rows as a bit mask in 2g's format ((n_local + 31) / 32 words, bit i % 32 of word
+ *     i / 32), bits at and beyond n_local written 0: it can be handed straight to the masked calls ("query the core rows only").
+ *   min_pts == 1 makes every row core: the labels are the connected components of the radius graph.
+ * labels_dev is also the call's working memory (the degrees, then the union-find forest): its contents are the answer only once
+ * the call's work on `stream` is done.
+ *
+ * Flags: KNN_QUERY_COUNT_GRID alone.  KNN_QUERY_INIT_KEYS has no meaning (the call always writes); every other flag,
+ * KNN_QUERY_COUNT_CELLS included, is KNN_EINVAL.  The way is the one knn_index_self_count_within_routed takes for the shard's rows
+ * at cap = max_dist2 under the same flag and options: the grid way on a grid index (k <= 4) with the flag and option "path" 0 or
+ * 3, the exact self-scan everywhere else (a cell-range shard included).  Both the degree step and the link sweep take it.  A grid
+ * batch that gives up is answered by the gated exact twins: the degrees through the routed count's commit, the links by a whole
+ * exact sweep over whatever the grid walk left — unite and the border key's minimum are idempotent.  knn_index_last_stats
+ * reports [0] = 1 or 3, [2] = 1 when a grid batch gave up.  Asynchronous on `stream`; slots as for every other query; the scratch
+ * (8 bytes per row, and the mask's words when core_dev is NULL; on the grid way the routed count's 4 bytes per row as well) is the
+ * slot's, grown on demand.
+ *
+ * Argument errors are KNN_EINVAL, each with its own knn_last_error text prefixed by the function's name, checked in this order —
+ * the first that fails speaks, nothing is launched —: max_dist2 < 0 or NaN, an unknown flag, a slot outside 0 .. 7, min_pts < 1,
+ * a null labels pointer, a null index, n_local > INT_MAX.  An empty shard succeeds and writes nothing.
+ *
+ * knn_index_self_cluster_within_host: synchronous, the device call on the default stream, copied back and RENUMBERED — clusters
+ * 0 .. C - 1 in ascending order of their representative (smallest core) row, which for core rows is scikit-learn's numbering;
+ * noise stays -1.  core_host [n_local] (NULL ok): 1 for a core row.  info (NULL ok) = {clusters, core rows, border rows, noise
+ * rows}.  Errors, in this order: max_dist2, an unknown flag, min_pts < 1, a null labels pointer, a null index, n_local > INT_MAX.
+ *
+ * Test hooks, host arithmetic only.  knn_debug_cluster_plan: in = {k, the shard's rows, CUs, 1 if core_dev is given, 1 if the grid
+ * way answers (k <= 4)}; out = {chunks of 65536 rows of the exact link sweep, slices of its first chunk, kernel launches of the
+ * whole call on the exact way (per chunk the self count and the link sweep; core; flatten), the same on the grid way (grid count,
+ * commit, the gated self count per chunk; core; grid link, the gated link sweep per chunk; flatten), bytes of the slot's cluster
+ * scratch, bytes of the slot's count scratch on this way, the way (1 / 3), the launches on this way}.
+ * knn_debug_cluster_unite: the kernels' own find / unite lines (knn_cluster_uf.h) with the host's atomics, one unite per pair, in
+ * order, on parent [n] (on entry parent[x] <= x, e.g. parent[x] = x; pairs of rows 0 .. n - 1).
+ *
+ * Not built: the cell-pruned way; clusters across shards (merging the ranks' components); a radius per row; compact numbering on
+ * the device; a mask of admitted rows; evaluating a pair once for both rows (each sweep still meets a pair from either side). */
+#define KNN_CLUSTER_NOISE (-1)
+int knn_index_self_cluster_within(knn_index *idx, int slot, float max_dist2, int min_pts, int *labels_dev /*[n_local]*/,
+                                  unsigned *core_dev /*[(n_local+31)/32] or NULL*/, void *stream, unsigned flags);
+int knn_index_self_cluster_within_host(knn_index *idx, float max_dist2, int min_pts, unsigned flags, int *labels_host /*[n_local]*/,
+                                       unsigned char *core_host /*[n_local] or NULL*/, long long info[4] /*NULL ok*/);
+int knn_debug_cluster_plan(const long long in[], long long out[]);   /* host arithmetic only */
+int knn_debug_cluster_unite(int *parent, long long n, const int *pairs /*[npairs][2]*/, long long npairs);
+
 /* Tuning / test hooks.  Known names:
  *   "path"    0 = auto, 1 = exact VALU kernels only, 2 = force the MFMA filter
  *             (+ exact re-rank) where its preconditions hold, 3 = the uniform-grid spatial index

@@ -28,6 +28,7 @@ __all__ = ["lib", "lib_path", "cudaCallback", "KnnIndex", "KnnGeom", "KnnError",
            "count_within_each_host_c", "list_within_each_host_c", "keys_column_dist2_c", "keys_column_dist2", "debug_each_radius",
            "self_count_within_routed_c", "self_list_within_routed_c", "self_list_within_routed_host_c", "debug_self_routed_plan",
            "count_within_masked_routed_c", "list_within_masked_routed_c",
+           "self_cluster_within_c", "self_cluster_within_host_c", "debug_cluster_plan", "debug_cluster_unite", "CLUSTER_NOISE",
            "debug_match_tests"]
 
 KEY_INIT = 0x7F80000000000000
@@ -61,6 +62,7 @@ EXPORTED_SYMBOLS = [
     "knn_index_self_count_within_routed", "knn_index_self_list_within_routed", "knn_index_self_list_within_routed_host",
     "knn_debug_self_routed_plan",
     "knn_index_count_within_masked_routed", "knn_index_list_within_masked_routed",
+    "knn_index_self_cluster_within", "knn_index_self_cluster_within_host", "knn_debug_cluster_plan", "knn_debug_cluster_unite",
     "knn_debug_cells_fetch", "knn_debug_match_tests",
 ]
 TOPK_LARGE_MAX = 4096   # KNN_TOPK_LARGE_MAX
@@ -70,6 +72,7 @@ QUERY_TOPK_GRID = 4   # KNN_QUERY_TOPK_GRID
 QUERY_TOPK_FRAMES = 8   # KNN_QUERY_TOPK_FRAMES
 QUERY_COUNT_GRID = 16   # KNN_QUERY_COUNT_GRID
 QUERY_COUNT_CELLS = 32   # KNN_QUERY_COUNT_CELLS
+CLUSTER_NOISE = -1   # KNN_CLUSTER_NOISE
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # KNN_MI355X_LIB: A/B hook — load another build of the same C-ABI (e.g. a previous commit's .so)
@@ -781,6 +784,49 @@ def list_within_masked_routed_c():
     return f
 
 
+def self_cluster_within_c():
+    """knn_index_self_cluster_within with its argument types (set here, not in lib(), as count_within_c)."""
+    f = lib().knn_index_self_cluster_within
+    f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                  ctypes.c_uint]
+    return f
+
+
+def self_cluster_within_host_c():
+    f = lib().knn_index_self_cluster_within_host
+    f.argtypes = [ctypes.c_void_p, ctypes.c_float, ctypes.c_int, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p,
+                  ctypes.POINTER(ctypes.c_longlong)]
+    return f
+
+
+CLUSTER_PLAN_INPUTS = ("k", "n", "num_cu", "core_given", "grid")
+CLUSTER_PLAN = ("chunks", "slices", "launches_exact", "launches_grid", "scratch_bytes", "count_bytes", "way", "launches")
+
+
+def debug_cluster_plan(**inputs):
+    """knn_debug_cluster_plan: what a self_cluster_within call on a shard of n rows launches and the slot scratch it needs, for the
+    inputs named in CLUSTER_PLAN_INPUTS (core_given: the caller passes core_dev; grid: the grid way answers, k <= 4).  Host
+    arithmetic; works without a GPU."""
+    vin = (ctypes.c_longlong * len(CLUSTER_PLAN_INPUTS))(*[int(inputs[n]) for n in CLUSTER_PLAN_INPUTS])
+    out = (ctypes.c_longlong * len(CLUSTER_PLAN))()
+    f = lib().knn_debug_cluster_plan
+    f.argtypes = [ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)]
+    _check(f(vin, out))
+    return dict(zip(CLUSTER_PLAN, list(out)))
+
+
+def debug_cluster_unite(parent, pairs):
+    """knn_debug_cluster_unite: the kernels' own union-find lines (knn_cluster_uf.h) with the host's atomics — unite(a, b) for every
+    row of pairs [npairs][2], in order, on parent (int32 [n], changed IN PLACE; parent[x] <= x on entry).  Works without a GPU."""
+    if not (isinstance(parent, np.ndarray) and parent.dtype == np.int32 and parent.flags.c_contiguous and parent.ndim == 1):
+        raise ValueError("parent must be a contiguous one-dimensional int32 array (it is changed in place)")
+    pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    f = lib().knn_debug_cluster_unite
+    f.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong]
+    _check(f(parent.ctypes.data_as(ctypes.c_void_p), parent.size, pr.ctypes.data_as(ctypes.c_void_p), pr.shape[0]))
+    return parent
+
+
 def self_list_within_routed_host_c():
     f = lib().knn_index_self_list_within_routed_host
     f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_uint, ctypes.c_void_p,
@@ -1368,6 +1414,27 @@ class KnnIndex:
                                              ctypes.c_void_p(int(fill_dev)), ctypes.c_void_p(int(keys_dev)), ctypes.c_void_p(stream),
                                              (QUERY_INIT_KEYS if init else 0) | (QUERY_COUNT_GRID if grid else 0) |
                                              (QUERY_COUNT_CELLS if cells else 0) | int(flags)))
+
+    def self_cluster_within(self, max_dist2, min_pts, labels_dev, core_dev=None, stream=0, slot=0, grid=False, flags=0):
+        """Async (knn_index_self_cluster_within): density clusters (DBSCAN) of this shard's rows on the radius graph.  labels_dev:
+        int32 [n] on the device — LOCAL row numbers: a core row's is the smallest core row of its component, a border row's its
+        nearest core row's, CLUSTER_NOISE for the rest; core_dev: None, or (n + 31) // 32 uint32 words that receive the core rows
+        as a mask for the masked calls.  grid asks for the grid index (QUERY_COUNT_GRID); without it the exact self-scan.
+        flags: further flag bits as they are (every one of them raises)."""
+        _check(self_cluster_within_c()(self._h, int(slot), float(max_dist2), int(min_pts), ctypes.c_void_p(int(labels_dev)),
+                                       ctypes.c_void_p(int(core_dev)) if core_dev is not None else None, ctypes.c_void_p(stream),
+                                       (QUERY_COUNT_GRID if grid else 0) | int(flags)))
+
+    def self_cluster_within_host(self, max_dist2, min_pts, grid=False, flags=0):
+        """Synchronous (knn_index_self_cluster_within_host): (labels int32 [n] — clusters 0 .. C - 1 in ascending order of their
+        smallest core row, -1 noise —, core bool [n], info dict(clusters, core, border, noise))."""
+        n = int(self.n)
+        labels = np.empty(n, dtype=np.int32)
+        core = np.zeros(n, dtype=np.uint8)
+        info = (ctypes.c_longlong * 4)()
+        _check(self_cluster_within_host_c()(self._h, float(max_dist2), int(min_pts), (QUERY_COUNT_GRID if grid else 0) | int(flags),
+                                            labels.ctypes.data_as(ctypes.c_void_p), core.ctypes.data_as(ctypes.c_void_p), info))
+        return labels, core.astype(bool), dict(zip(("clusters", "core", "border", "noise"), list(info)))
 
     def self_list_within_routed_host(self, cap, max_dist2=None, grid=False, cells=False, flags=0):
         """Synchronous radius graph of this shard on the routed self calls (knn_index_self_list_within_routed_host), in

@@ -12,6 +12,7 @@
 #include "knn_mask_split.h"
 #include "knn_self_window.h"
 #include "knn_each_radius.h"
+#include "knn_cluster_uf.h"
 
 #include <limits.h>
 #include <math.h>
@@ -340,6 +341,8 @@ struct knn_index {
         size_t mask_bytes = 0;
         u64 *self = nullptr;       // knn_index_self_topk's through way: what knn_self_plan says (the plain call's K + 1 keys per row, a fold's K)
         size_t self_bytes = 0;
+        u64 *cluster = nullptr;    // knn_index_self_cluster_within: what knn_cluster_plan says (best [n_local], the core mask when the caller keeps none)
+        size_t cluster_bytes = 0;
     } topk[KNN_SLOTS];
     // Calls on one index from several host threads are serialised (enqueueing a batch is ~20 us of host work; the GPU
     // work of different slots still overlaps): the workspaces' lazily grown buffers, the event list, the statistics and
@@ -826,6 +829,7 @@ void knn_index_destroy(knn_index *idx)
             (void)knn_dev_free(t.large);
             (void)knn_dev_free(t.mask);
             (void)knn_dev_free(t.self);
+            (void)knn_dev_free(t.cluster);
         }
         knn_dev_free_end_synced();
         for (auto &ev : idx->events) {
@@ -2091,6 +2095,110 @@ int knn_index_list_within_masked_routed(knn_index *idx, int slot, int m, const f
     return within_run(idx, w, lists_into(offsets_dev, fill_dev, keys_dev));
 }
 
+// ---- 2m. Clusters of the radius graph (include/knn_mi355x.h 2m; knn_cluster.hip, knn_grid.hip) -----------------------
+// (one message per rule, in the header's order, the index before the one rule that needs it: tests/test_cluster_logic.py tells
+// them apart without a GPU)
+// (the two rules the device call and the host form share word for word)
+constexpr unsigned kClusterFlags = KNN_QUERY_COUNT_GRID;   // the one flag the cluster calls admit
+static int cluster_check(const char *who, float max_dist2, unsigned flags)
+{
+    if (!(max_dist2 >= 0.0f))
+        return fail_in(KNN_EINVAL, who, "max_dist2 must be >= 0 and not NaN");
+    if ((flags & ~kClusterFlags) != 0u)
+        return fail_in(KNN_EINVAL, who, "unknown flag (KNN_QUERY_COUNT_GRID alone is admitted: the call always writes its labels, and "
+                                        "the cell-pruned way is not built for it)");
+    return KNN_OK;
+}
+
+int knn_index_self_cluster_within(knn_index *idx, int slot, float max_dist2, int min_pts, int *labels_dev, unsigned *core_dev,
+                                  void *stream, unsigned flags)
+{
+    const char *const who = "knn_index_self_cluster_within";
+    KNN_TRY(cluster_check(who, max_dist2, flags));
+    if (slot < 0 || slot >= KNN_SLOTS)
+        return fail_in(KNN_EINVAL, who, "slot outside 0 .. 7");
+    if (min_pts < 1)
+        return fail_in(KNN_EINVAL, who, "min_pts < 1");
+    if (!labels_dev)
+        return fail_in(KNN_EINVAL, who, "null labels");
+    if (!idx)
+        return fail_in(KNN_EINVAL, who, "null index");
+    std::lock_guard<std::recursive_mutex> lock(idx->mu);
+    if (idx->n > INT_MAX)
+        return fail_in(KNN_EINVAL, who, "more than INT_MAX rows (labels are int row numbers)");
+    DeviceGuard guard(idx->device);
+    if (!guard.ok)
+        return fail_in(KNN_EHIP, who, "hipSetDevice failed");
+    begin_call(idx, slot);
+    if (idx->n == 0)   // an empty shard has no row to label
+        return KNN_OK;
+    const int n = (int)idx->n;
+    // the slot's scratch, grown before the first launch
+    const ClusterPlan plan = knn_cluster_plan(idx->n, idx->num_cu, core_dev == nullptr);
+    knn_index::TopkSlot &ts = idx->topk[slot];
+    KNN_TRY(slot_buffer_grow(ts.cluster, ts.cluster_bytes, plan.scratch_bytes));
+    ClusterCall c;
+    c.k = idx->k;
+    c.n = idx->n;
+    c.r = idx->refs;
+    c.max_dist2 = max_dist2 == 0.0f ? 0.0f : max_dist2;   // (-0 counts as 0)
+    c.min_pts = min_pts;
+    c.num_cu = idx->num_cu;
+    c.stream = (hipStream_t)stream;
+    c.parent = labels_dev;
+    c.best = ts.cluster;
+    c.core = core_dev ? core_dev : (unsigned *)(ts.cluster + (size_t)n);
+    // 1. degrees: the routed self count of the whole shard at cap = max_dist2 under the call's flag, zeroed first, into the labels.
+    //    It decides the way (and leaves it in the statistics); its rules have passed above, so its texts cannot be met here.
+    const WithinCall w = {who, kCap | kRouted | kSelf, slot, n, nullptr, 0, nullptr, max_dist2, stream, flags | KNN_QUERY_INIT_KEYS};
+    KNN_TRY(within_run(idx, w, counts_into((unsigned *)labels_dev)));
+    HIP_TRY(knn_cluster_core_launch(c));
+    // 2. the link sweep on the same way; the grid's is followed by the exact one, gated on its give-up word
+    if (idx->stats[0] == (long long)QueryWay::Grid) {
+        const CountPlan cp = count_plan_of(idx, route_inputs(idx, n, 1, 0u), n, c.max_dist2, flags);
+        const unsigned *gate = nullptr;
+        HIP_TRY(knn_grid_cluster_link(idx->grid, cp.rmax, slot, c, &gate));
+        idx->grid_topk_gate = gate;   // (the degree batch's walks are the same walks: both words say the same)
+        HIP_TRY(knn_cluster_link_launch(c, gate));
+    } else {
+        HIP_TRY(knn_cluster_link_launch(c, nullptr));
+    }
+    // 3. forest -> labels
+    HIP_TRY(knn_cluster_flatten_launch(c));
+    return KNN_OK;
+}
+
+int knn_debug_cluster_plan(const long long in[], long long out[])
+{
+    // in = {k, the shard's rows, CUs, 1 if the caller passes core_dev, 1 if the grid way answers}
+    if (!in || !out || in[0] < 1 || in[0] > INT_MAX || in[1] < 0 || in[1] > INT_MAX || in[2] < 1 || in[2] > INT_MAX ||
+        (in[3] != 0 && in[3] != 1) || (in[4] != 0 && in[4] != 1) || (in[4] != 0 && in[0] > 4))
+        return fail(KNN_EINVAL, "knn_debug_cluster_plan: bad arguments (k >= 1, 0 <= rows <= INT_MAX, CUs >= 1, core_dev given 0 or 1, "
+                                "grid way 0 or 1 and only with k <= 4)");
+    const ClusterPlan p = knn_cluster_plan(in[1], (int)in[2], in[3] == 0);
+    const bool grid = in[4] != 0 && in[1] > 0;
+    const long long v[8] = {p.chunks, p.slices, p.launches_exact, p.launches_grid, (long long)p.scratch_bytes,
+                            grid ? (long long)p.count_bytes : 0, in[1] > 0 ? (grid ? 3 : 1) : 1, grid ? p.launches_grid : p.launches_exact};
+    memcpy(out, v, sizeof v);
+    return KNN_OK;
+}
+
+int knn_debug_cluster_unite(int *parent, long long n, const int *pairs, long long npairs)
+{
+    if (n < 0 || n > INT_MAX || npairs < 0 || (n > 0 && !parent) || (npairs > 0 && !pairs))
+        return fail(KNN_EINVAL, "knn_debug_cluster_unite: bad arguments (0 <= n <= INT_MAX, npairs >= 0, no null array)");
+    for (long long t = 0; t < 2 * npairs; ++t)
+        if (pairs[t] < 0 || pairs[t] >= n)
+            return fail(KNN_EINVAL, "knn_debug_cluster_unite: a pair names a row outside 0 .. n - 1");
+    for (long long i = 0; i < n; ++i)
+        if (parent[i] < 0 || parent[i] > i)
+            return fail(KNN_EINVAL, "knn_debug_cluster_unite: parent[x] <= x does not hold on entry (start from parent[x] = x)");
+    // the kernels' own lines (knn_cluster_uf.h) with the host's atomics
+    for (long long t = 0; t < npairs; ++t)
+        (void)knn_uf_unite<KnnUfHost>(parent, pairs[2 * t], pairs[2 * t + 1]);
+    return KNN_OK;
+}
+
 int knn_debug_self_routed_plan(const long long in[16], long long out[8])
 {
     // knn_debug_count_plan's inputs with m = the call's rows, which lie inside the shard; its outputs, [6] from the self-scan's plan
@@ -3096,6 +3204,67 @@ extern "C" int knn_index_self_list_within_routed_host(knn_index *idx, const floa
                               dist2_out);
 }
 
+
+// The clusters of the whole shard on the host: the device call on the default stream, then the renumbering — clusters 0 .. C - 1 in
+// ascending order of their representative row (the smallest core row: the label the device call gives) — and the tallies.
+extern "C" int knn_index_self_cluster_within_host(knn_index *idx, float max_dist2, int min_pts, unsigned flags, int *labels_host,
+                                                  unsigned char *core_host, long long info[4])
+{
+    const char *const who = "knn_index_self_cluster_within_host";
+    KNN_TRY(cluster_check(who, max_dist2, flags));
+    if (min_pts < 1)
+        return fail_in(KNN_EINVAL, who, "min_pts < 1");
+    if (!labels_host)
+        return fail_in(KNN_EINVAL, who, "null labels");
+    if (!idx)
+        return fail_in(KNN_EINVAL, who, "null index");
+    std::lock_guard<std::recursive_mutex> lock(idx->mu);
+    if (idx->n > INT_MAX)
+        return fail_in(KNN_EINVAL, who, "more than INT_MAX rows (labels are int row numbers)");
+    DeviceGuard guard(idx->device);
+    if (!guard.ok)
+        return fail_in(KNN_EHIP, who, "hipSetDevice failed");
+    const size_t n = (size_t)idx->n, words = (n + 31) / 32;
+    long long tally[4] = {0, 0, 0, 0};
+    if (n > 0) {
+        Staging stage(idx->device);
+        int *labels_dev = nullptr;
+        unsigned *core_dev = nullptr;
+        hipError_t e = stage.get(&labels_dev, n * sizeof(int));
+        if (e == hipSuccess)
+            e = stage.get(&core_dev, words * sizeof(unsigned));
+        if (e != hipSuccess)
+            return fail_in(KNN_EHIP, who, "staging labels", hipGetErrorString(e));
+        const int rv = knn_index_self_cluster_within(idx, 0, max_dist2, min_pts, labels_dev, core_dev, nullptr, flags);
+        if (rv != KNN_OK)
+            return rv;
+        std::vector<unsigned> core(words);
+        e = hipMemcpy(labels_host, labels_dev, n * sizeof(int), hipMemcpyDeviceToHost);
+        if (e == hipSuccess)
+            e = hipMemcpy(core.data(), core_dev, words * sizeof(unsigned), hipMemcpyDeviceToHost);
+        if (e != hipSuccess)
+            return fail_in(KNN_EHIP, who, "D2H labels", hipGetErrorString(e));
+        // a representative is the row that carries its own number; they are met in ascending order
+        std::vector<int> number(n, -1);
+        int next = 0;
+        for (size_t i = 0; i < n; ++i)
+            if (labels_host[i] == (int)i)
+                number[i] = next++;
+        for (size_t i = 0; i < n; ++i) {
+            const bool is_core = ((core[i >> 5] >> (i & 31)) & 1u) != 0u;
+            if (core_host)
+                core_host[i] = is_core ? 1 : 0;
+            const int rep = labels_host[i];
+            labels_host[i] = rep < 0 ? KNN_CLUSTER_NOISE : number[(size_t)rep];
+            ++tally[is_core ? 1 : rep < 0 ? 3 : 2];
+        }
+        tally[0] = next;
+        // (not declared waited: the buffers go back after the device-wide wait `stage` then makes itself, as the other host calls)
+    }
+    if (info)
+        memcpy(info, tally, sizeof tally);
+    return KNN_OK;
+}
 
 extern "C" int knn_index_list_within_masked_host(knn_index *idx, int m, const float *queries_host, float max_dist2,
                                                  const unsigned *mask_host, long long *offsets_host, int **indices_out, float **dist2_out)

@@ -946,6 +946,45 @@ hipError_t knn_grid_query_count(const GridState *gs, int rmax, int slot, const C
 hipError_t knn_grid_query_list(const GridState *gs, int rmax, int slot, const ListCall &c, const unsigned **gate_out);
 void knn_grid_info(const GridState *gs, long long info[4]);
 
+// ---- clusters of the radius graph (knn_cluster.hip, knn_grid.hip; DESIGN §4.6 "Clusters of the radius graph") -------------------
+// One knn_index_self_cluster_within call behind its degree step, as the launches below take it.  parent is the caller's labels
+// array: the degrees on entry to knn_cluster_core_launch, the union-find forest (parent[i] = a core row <= i of i's set, -1 for a
+// row that is not core) from there to knn_cluster_flatten_launch, the labels behind it.
+struct ClusterCall {
+    int k = 0;
+    long long n = 0;               // the shard's rows, <= INT_MAX
+    const float *r = nullptr;      // device [n][k]
+    float max_dist2 = INFINITY;    // the radius, squared (>= 0, never -0; +INF: every row with a finite distance)
+    int min_pts = 1;
+    int num_cu = 0;
+    hipStream_t stream = nullptr;
+    int *parent = nullptr;         // device [n]
+    unsigned *core = nullptr;      // device [(n + 31) / 32]: bit i % 32 of word i / 32 = row i is core (the caller's core_dev or slot scratch)
+    u64 *best = nullptr;           // device [n], slot scratch: the smallest key (distance bits, row) of a core row within the radius
+};
+// Everything a call launches and the slot scratch it needs (host arithmetic only; knn_debug_cluster_plan shows it).
+struct ClusterPlan {
+    int chunks = 0;                  // launches of the exact link sweep: chunks of <= KNN_TOPK_CHUNK rows
+    long long slices = 0;            // blocks along the shard's rows of the first chunk's sweep (knn_count_slices)
+    long long launches_exact = 0;    // kernel launches of the whole call on the exact way: degrees, core, links, flatten
+    long long launches_grid = 0;     // ... on the grid way: + the grid kernels, the count's commit, the gated exact twins
+    size_t scratch_bytes = 0;        // best [n] u64 + the core mask words when the caller passes no core_dev
+    size_t count_bytes = 0;          // the grid way's count scratch [n] unsigned (the routed self count's own)
+};
+ClusterPlan knn_cluster_plan(long long n, int num_cu, bool own_mask);
+// parent[i] (holding deg(i)) <- i when deg(i) + 1 >= c.min_pts, else -1; c.core <- the core bits, the words' bits at and beyond
+// n zero; c.best[i] <- KNN_KEY_INIT.
+hipError_t knn_cluster_core_launch(const ClusterCall &c);
+// The link sweep on the exact way: for every pair of core rows i < j within the radius unite(i, j); for every row j that is not
+// core, c.best[j] <- the smallest key of a core row within the radius.  gate != nullptr: the launches do nothing unless
+// *gate != 0 (behind the grid sweep: its give-up word).
+hipError_t knn_cluster_link_launch(const ClusterCall &c, const unsigned *gate);
+// The same sweep on the grid (knn_grid.hip): one wave per row walks its rings; *gate_out = the batch's give-up word, on which the
+// caller gates knn_cluster_link_launch behind it.  rmax: CountPlan::rmax at the call's radius.
+hipError_t knn_grid_cluster_link(const GridState *gs, int rmax, int slot, const ClusterCall &c, const unsigned **gate_out);
+// parent -> labels: a core row's root, a border row's (c.best[i] holds a key) nearest core row's root, -1 for every other row.
+hipError_t knn_cluster_flatten_launch(const ClusterCall &c);
+
 // ---- RCCL exchange step (knn_rccl.cpp; librccl is dlopen'ed at first use) -------------------
 #ifdef __cplusplus
 #include <string>

@@ -20,6 +20,7 @@
 // Never used when the rows hold non-finite values or the grid degenerates (a cell with > 4096 rows):
 // the brute-force kernels take those shards.
 #include "knn_common.h"
+#include "knn_cluster_uf.h"
 #include "knn_each_radius.h"
 
 #include <math.h>
@@ -592,6 +593,113 @@ __global__ __launch_bounds__(GRID_BLOCK) void knn_grid_masked_list_kernel(const 
 #undef GRID_RADIUS_NO_SELF
 #undef GRID_RADIUS_NO_MASK
 
+// ---- the link sweep of knn_index_self_cluster_within on the grid (include/knn_mi355x.h 2m; knn_cluster.hip describes the call) ----
+// knn_grid_radius_body.inc's walk with SELF at the scalar radius — one wave per query (local row qi), lanes take the cells of a
+// ring, the same stop clause, ring limit and give-up word — written out here as a sibling and not as a fifth switch of the body
+// file: the eight kernels made from that file keep their code.  A hit is a row i = orig[p] != qi with E finite and E <= cap; the
+// hit path is knn_cluster_link_kernel's: both rows core and i < qi — the lane unites (knn_cluster_uf.h; every lane has its own
+// cached root, a member of row qi's set); row qi not core and i core — the key (E's bits, i) goes into the lane's minimum, the
+// wave reduces it with shuffles and lane 0 issues one atomic min on best[qi], only when some lane folded a key.
+// A wave that gives up raises the word and leaves what it has united and folded where it is: the gated exact sweep behind this
+// kernel does every pair again, and unite and min are idempotent.  A row with a non-finite coordinate has no hit and walks nothing.
+template <int KD>
+__global__ __launch_bounds__(GRID_BLOCK) void knn_grid_cluster_link_kernel(const float *__restrict__ Q, int m, GridGeom gg,
+                                                                           const unsigned *__restrict__ start,
+                                                                           const f4g *__restrict__ pts, const unsigned *__restrict__ orig,
+                                                                           int *parent, const unsigned *__restrict__ core,
+                                                                           u64 *__restrict__ best, int rmax,
+                                                                           unsigned *__restrict__ giveup,
+                                                                           unsigned *__restrict__ giveup_next, float cap)
+{
+#pragma clang fp contract(off)
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        *giveup_next = 0u;   // (the slot's other word, as the 1-NN kernel)
+    const int lane = threadIdx.x & 63;
+    const int qi = blockIdx.x * (GRID_BLOCK / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (qi >= m)
+        return;
+    float q[4] = {0.f, 0.f, 0.f, 0.f};
+    bool finite = true;
+#pragma unroll
+    for (int d = 0; d < KD; ++d) {
+        q[d] = Q[(size_t)qi * KD + d];
+        finite = finite && fabsf(q[d]) < INFINITY;
+    }
+    if (!finite)   // no row can be a hit (and nothing to give up on)
+        return;
+    const unsigned own = (unsigned)qi;
+    const bool jcore = ((core[own >> 5] >> (own & 31u)) & 1u) != 0u;   // wave-uniform
+    int croot = qi;
+    u64 near = kKeyInit;
+    int c[4];
+    (void)grid_cell_of(gg, q, c);
+    int gmax = 1;
+#pragma unroll
+    for (int d = 0; d < KD; ++d)
+        gmax = gg.g[d] > gmax ? gg.g[d] : gmax;
+    bool done = false;
+    bool first_ring = true;   // (rings 0 and 1 together, as the 1-NN kernel)
+    for (int r = gmax > 1 ? 1 : 0; r < gmax && r <= rmax; ++r) {
+        const int side = 2 * r + 1;
+        int total = 1;
+#pragma unroll
+        for (int d = 0; d < KD; ++d)
+            total *= side;
+        for (int idx = lane; idx < total; idx += KNN_WAVE) {
+            unsigned cell;
+            if (!grid_ring_cell<KD>(gg, c, r, side, idx, first_ring, &cell))
+                continue;
+            const unsigned p0 = start[cell], p1 = start[cell + 1];
+            for (unsigned p = p0; p < p1; ++p) {
+                const f4g x = pts[p];
+                float acc = 0.0f;
+#pragma unroll
+                for (int d = 0; d < KD; ++d) {
+                    const float diff = q[d] - x[d];   // v0: search - reference, squared, summed in order
+                    const float sq = diff * diff;
+                    acc = acc + sq;
+                }
+                if (acc < INFINITY && acc <= cap) {
+                    const unsigned row = orig[p];
+                    if (row != own && ((core[row >> 5] >> (row & 31u)) & 1u) != 0u) {
+                        if (jcore) {
+                            if (row < own && KnnUfDevice::load(&parent[row]) != croot)
+                                croot = knn_uf_unite<KnnUfDevice>(parent, (int)row, croot);
+                        } else {
+                            const u64 key = ((u64)__float_as_uint(acc) << 32) | (u64)row;
+                            near = key < near ? key : near;
+                        }
+                    }
+                }
+            }
+        }
+        first_ring = false;
+        bool covers_all;
+        const double lb = grid_face_bound<KD>(gg, c, q, r, &covers_all);
+        if (covers_all) {
+            done = true;
+            break;
+        }
+        if (lb > 0.0 && (double)cap < lb * lb * (1.0 - 1e-6)) {   // no unseen row is within the radius
+            done = true;
+            break;
+        }
+    }
+    if (!jcore) {   // (wave-uniform)
+#pragma unroll
+        for (int step = 32; step > 0; step >>= 1) {
+            const u64 o = __shfl_xor(near, step, KNN_WAVE);
+            near = o < near ? o : near;
+        }
+    }
+    if (lane == 0) {
+        if (near != kKeyInit)
+            __hip_atomic_fetch_min(&best[qi], near, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (!done && gmax > rmax + 1)
+            *giveup = 1u;      // benign race: every writer stores 1
+    }
+}
+
 // ---- host -------------------------------------------------------------------------------------------
 #define GTRY(call)                     \
     do {                                 \
@@ -972,6 +1080,31 @@ hipError_t knn_grid_query_list(const GridState *gs, int rmax, int slot, const Li
     GTRY(grid_batch_end(b, s, c.ev1, gate_out));
     GTRY(knn_list_commit_launch(c.m, c.scratch, c.fill, b.giveup, s));
     return knn_gated_list_launch(c, b.giveup);   // (a routed self call: the gated self-scan; a masked one: the gated masked scan)
+}
+
+// The link sweep of a cluster call on the grid way, asynchronous on c.stream: one batch of c.n queries — the shard's rows in local
+// order — through knn_grid_cluster_link_kernel.  Nothing is committed behind it: the caller queues knn_cluster_link_launch gated
+// on *gate_out, which does every pair again when some row gave up.
+hipError_t knn_grid_cluster_link(const GridState *gs, int rmax, int slot, const ClusterCall &c, const unsigned **gate_out)
+{
+    *gate_out = nullptr;
+    if (!gs || !gs->usable || c.n <= 0 || c.n > 0x7FFFFFFFll || c.k != gs->geom.k || !c.r || !c.parent || !c.core || !c.best || rmax < 0)
+        return hipErrorInvalidValue;
+    hipStream_t s = c.stream;
+    const int m = (int)c.n;
+    GridBatch b;
+    GTRY(grid_batch_begin(gs, slot, m, 0u, s, nullptr, &b));
+#define GRID_CLUSTER_LINK(KDV)                                                                                                       \
+    hipLaunchKernelGGL(knn_grid_cluster_link_kernel<KDV>, b.grid, b.block, 0, s, c.r, m, gs->geom, gs->start, gs->pts, gs->orig,     \
+                       c.parent, (const unsigned *)c.core, c.best, rmax, b.giveup, b.giveup_next, c.max_dist2)
+    switch (gs->geom.k) {
+    case 1: GRID_CLUSTER_LINK(1); break;
+    case 2: GRID_CLUSTER_LINK(2); break;
+    case 3: GRID_CLUSTER_LINK(3); break;
+    default: GRID_CLUSTER_LINK(4); break;
+    }
+#undef GRID_CLUSTER_LINK
+    return grid_batch_end(b, s, nullptr, gate_out);
 }
 
 long long knn_grid_radius_rings(const GridState *gs, float max_dist2)

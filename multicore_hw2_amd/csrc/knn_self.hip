@@ -17,71 +17,7 @@
 //
 // knn_self_count_gated_kernel and knn_self_list_gated_kernel are the count and list scans behind a device gate: the exact answer of
 // the routed self calls (include/knn_mi355x.h 2k) when the grid gave up or a cell-pruned pass fell back.
-#include "knn_masked_dev.h"
-#include "knn_self_window.h"
-
-// hit(acc, row) for the next `count` rows but — WIN — the lane's own: the one row-loop body of the three scans.  r: the first of
-// them, row: its local number's low word (what a key carries and what `own` is compared with); both are left behind the last.
-// The counter is 32-bit: the loop's test is scalar arithmetic.
-template <int KC, bool WIN, class Hit>
-__device__ __forceinline__ void self_rows(const float (&qv)[KC > 0 ? 16 * KC : 1], const float *__restrict__ qp,
-                                          const float *__restrict__ &r, int k, unsigned &row, unsigned count, unsigned own, Hit &&hit)
-{
-    for (unsigned c = 0; c < count; ++c, ++row, r += k) {
-        const float acc = masked_dist2<KC>(qv, qp, r, k);
-        if (!WIN || row != own)
-            hit(acc, row);
-    }
-}
-
-// The block's slice [i0, i1) around its window [w0, w1) (a slice is shorter than 2^32 rows: the launchers see to it): the rows
-// before the window, inside it and after it, in that order, through two copies of the loop — the plain one and the window's.
-template <int KC, class Hit>
-__device__ __forceinline__ void self_scan(const float (&qv)[KC > 0 ? 16 * KC : 1], const float *__restrict__ qp,
-                                          const float *__restrict__ R, int k, long long i0, long long i1, long long w0, long long w1,
-                                          unsigned own, Hit &&hit)
-{
-    long long rg[6];
-    knn_self_ranges(i0, i1, w0, w1, rg);
-    const unsigned n0 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(rg[1] - rg[0]));
-    const unsigned n1 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(rg[3] - rg[2]));
-    const unsigned n2 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(rg[5] - rg[4]));
-    const float *__restrict__ r = R + (size_t)i0 * k;
-    unsigned row = (unsigned)i0;
-#pragma clang loop unroll(disable)
-    for (int t = 0; t < 3; ++t) {
-        if (t == 1)
-            self_rows<KC, true>(qv, qp, r, k, row, n1, own, hit);
-        else
-            self_rows<KC, false>(qv, qp, r, k, row, t ? n2 : n0, own, hit);
-    }
-}
-
-// The same cut through ONE copy of the loop: `win` — the range is the window's — is wave-uniform, so outside the window the own-row
-// compare is skipped by a scalar branch.  For a scan whose hit path is long (the list's reserve-and-store): two copies of it cost
-// registers (17-19 VGPRs in the list form, a wave of occupancy at KC 6), one does not.
-template <int KC, class Hit>
-__device__ __forceinline__ void self_scan_one(const float (&qv)[KC > 0 ? 16 * KC : 1], const float *__restrict__ qp,
-                                              const float *__restrict__ R, int k, long long i0, long long i1, long long w0, long long w1,
-                                              unsigned own, Hit &&hit)
-{
-    long long rg[6];
-    knn_self_ranges(i0, i1, w0, w1, rg);
-    const unsigned n0 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(rg[1] - rg[0]));
-    const unsigned n1 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(rg[3] - rg[2]));
-    const unsigned n2 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(rg[5] - rg[4]));
-    const float *__restrict__ r = R + (size_t)i0 * k;
-    unsigned row = (unsigned)i0;
-#pragma clang loop unroll(disable)
-    for (int t = 0; t < 3; ++t) {
-        const bool win = t == 1;
-        const unsigned count = t == 0 ? n0 : t == 1 ? n1 : n2;
-        for (unsigned c = 0; c < count; ++c, ++row, r += k) {
-            const float acc = masked_dist2<KC>(qv, qp, r, k);
-            hit(acc, row, !(win && row == own));
-        }
-    }
-}
+#include "knn_self_scan.h"   // self_rows, self_scan, self_scan_one: the row loops (shared with knn_cluster.hip)
 
 // knn_self_topk_kernel<KC, LIM> — knn_exact_topk_kernel<KC, LIM> for the m queries that are the rows first .. first + m - 1.  LIM as
 // there: the call has a radius, the K-th key a row is compared with is min(column[K - 1], lim); the plain form never reads `lim`
