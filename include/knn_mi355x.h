@@ -378,8 +378,9 @@ int knn_index_list_within_host(knn_index *idx, int m, const float *queries_host,
  * shards (as they are: no seed layer) fold into the global list by calling one after the other on a stream.  Every other flag —
  * KNN_QUERY_TOPK_PARTIAL, KNN_QUERY_TOPK_GRID, KNN_QUERY_TOPK_FRAMES, both KNN_QUERY_COUNT_* — is KNN_EINVAL.
  * K outside 1 .. 4096, m < 1, m*K > INT_MAX, a slot outside 0 .. 7, max_dist2 < 0 or NaN and a null pointer are KNN_EINVAL, each
- * with its own knn_last_error text, checked before the index, and nothing is launched.  An empty shard leaves the keys alone
- * (writes padding under the init flag).  Asynchronous on `stream`; slots as for every other query; 1-NN, top-K, count, list and
+ * with its own knn_last_error text, checked in that order (a flag after the radius) — the sizes first, unlike 2g .. 2i, which look
+ * at radius, flags and slot first; the host call below likewise — and before the index, and nothing is launched.
+ * An empty shard leaves the keys alone (writes padding under the init flag).  Asynchronous on `stream`; slots as for every other query; 1-NN, top-K, count, list and
  * large calls may follow one another on a slot in any order.  indices_dev (may be NULL) receives the keys' low words.
  * One way on every index (knn_index_last_stats [0] = 1; DESIGN §4.6 "Top-K beyond 64"): a radix select over the packed keys finds
  * each query's K-th smallest candidate key in four scans of the shard — eight when some query's cut falls inside a class of equal

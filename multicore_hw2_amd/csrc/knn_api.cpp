@@ -1180,6 +1180,17 @@ int knn_index_query(knn_index *idx, int slot, int m, const float *queries_dev, u
 
 namespace {
 
+// The index's side of a TopkCall: the shard's rows, the numbers their keys carry and the device's size.
+void topk_index_side(const knn_index *idx, TopkCall &call)
+{
+    call.k = idx->k;
+    call.n = idx->n;
+    call.base = idx->base;
+    call.gids = shard_gids(idx);
+    call.r = idx->refs;
+    call.num_cu = idx->num_cu;
+}
+
 // knn_index_query_topk and knn_index_query_topk_within behind their argument checks.  max_dist2 = +INF: the plain call, launch
 // for launch.  A finite radius changes no route (knn_query_route never sees it): the exact top-K and the grid way carry the limit
 // key in their kernels, the cell-pruned scan of a one-frame layout caps its bound with it, and the filter ways — whose lists may
@@ -1222,12 +1233,7 @@ int query_topk(knn_index *idx, int slot, TopkCall call, int *indices_dev, unsign
     KNN_TRY(slot_buffer_grow(ts.lists, ts.lists_bytes, sp.lists_bytes));
     EventPair *ev = nullptr;
     KNN_TRY(next_event_pair(idx, false, &ev));
-    call.k = idx->k;
-    call.n = idx->n;
-    call.base = idx->base;
-    call.gids = shard_gids(idx);
-    call.r = idx->refs;
-    call.num_cu = idx->num_cu;
+    topk_index_side(idx, call);
     call.ev0 = ev ? ev->first : nullptr;
     call.ev1 = ev ? ev->second : nullptr;
     call.part = ts.part;
@@ -1275,7 +1281,7 @@ int query_topk(knn_index *idx, int slot, TopkCall call, int *indices_dev, unsign
     return KNN_OK;
 }
 
-// What the caller of a top-K entry states; query_topk adds the index's side and the slot's scratch.
+// What the caller of a top-K entry states; query_topk and topk_one_way add the index's side and the slot's scratch.
 TopkCall topk_call_of(int m, int K, const float *queries_dev, unsigned long long *keys_dev, void *stream, float max_dist2)
 {
     TopkCall c;
@@ -1502,6 +1508,154 @@ int within_run(knn_index *idx, const WithinCall &w, Call call)
     return KNN_OK;
 }
 
+// ---- the one-way top-K forms (include/knn_mi355x.h 2f .. 2i): one description, one argument ladder, one call front ---------------
+// What an entry of the forms is (kMasked and kSelf as the radius family's), and what its caller states.  m: the queries, or the rows
+// of a self entry (queries null: they are the shard's rows from row_first).  A *_host entry states host arrays, names no slot (0)
+// and takes no flags (0): those two rules cannot speak for it.
+enum : unsigned {
+    kLarge = 16u,        // K up to KNN_TOPK_LARGE_MAX (the radix select), else up to KNN_TOPK_MAX
+    kSizesFirst = 32u,   // K, m and m * K are looked at before slot, radius and flags (the order the header's 2f states for its two entries)
+};
+struct TopkEntry {
+    const char *who;
+    unsigned form;
+    int slot, m, K;
+    const float *queries;
+    long long row_first;
+    float max_dist2;
+    const unsigned *mask = nullptr;   // kMasked: (n_local + 31) / 32 words
+    unsigned long long *keys = nullptr;
+    void *stream = nullptr;
+    unsigned flags = 0u, admits = KNN_QUERY_INIT_KEYS;   // admits: the flags the entry takes
+};
+
+// The forms' argument rules, one message per rule in one order — radius, flags, slot, m or rows (+ row_first), K, m * K, the entry's
+// pointer groups, the index last — or, kSizesFirst, K, m, m * K, slot, radius, flags in front of the pointers: the *_logic.py tests
+// and tests/golden/topk_arg_errors.json tell them apart, and which of two broken rules speaks, without a GPU.
+int topk_check(const TopkEntry &t, std::initializer_list<NullRule> pointers, const knn_index *idx)
+{
+    enum Rule { Radius, Flags, Slot, Rows, Neighbours, Product };
+    static const Rule usual[6] = {Radius, Flags, Slot, Rows, Neighbours, Product};
+    static const Rule sizes_first[6] = {Neighbours, Rows, Product, Slot, Radius, Flags};
+    const bool self = (t.form & kSelf) != 0u, large = (t.form & kLarge) != 0u;
+    const Rule *const order = (t.form & kSizesFirst) ? sizes_first : usual;
+    for (int i = 0; i < 6; ++i) {
+        const char *broken = nullptr;
+        switch (order[i]) {
+        case Radius:
+            if (!(t.max_dist2 >= 0.0f))
+                broken = "max_dist2 must be >= 0 and not NaN";
+            break;
+        case Flags:
+            if ((t.flags & ~t.admits) != 0u)
+                broken = t.admits == KNN_QUERY_INIT_KEYS ? "unknown flag (KNN_QUERY_INIT_KEYS alone is admitted)"
+                                                         : "unknown flag (KNN_QUERY_INIT_KEYS, KNN_QUERY_TOPK_GRID, KNN_QUERY_TOPK_FRAMES)";
+            break;
+        case Slot:
+            if (t.slot < 0 || t.slot >= KNN_SLOTS)
+                broken = "slot outside 0 .. 7";
+            break;
+        case Rows:
+            if (t.m < 1)
+                broken = self ? "rows < 1" : "m < 1";
+            else if (self && t.row_first < 0)
+                broken = "row_first < 0";
+            break;
+        case Neighbours:
+            if (t.K < 1 || t.K > (large ? KNN_TOPK_LARGE_MAX : KNN_TOPK_MAX))
+                broken = large ? "K outside 1 .. 4096" : "K outside 1 .. 64";
+            break;
+        case Product:
+            if ((long long)t.m * t.K > INT_MAX)
+                broken = self ? "rows * K above INT_MAX" : "m * K above INT_MAX";
+            break;
+        }
+        if (broken)
+            return fail_in(KNN_EINVAL, t.who, broken);
+    }
+    for (const NullRule &p : pointers)
+        if (p.broken)
+            return fail_in(KNN_EINVAL, t.who, p.what);
+    if (!idx)
+        return fail_in(KNN_EINVAL, t.who, "null index");
+    return KNN_OK;
+}
+
+// A device entry of the forms behind topk_check (a self entry: behind its range rule too): one way on every index, no layout is
+// consulted.  The forms differ in their plan, in the slot buffers it sizes — the mask scratch of a masked form; the per-slice
+// lists (part), or the large scratch of a kLarge form, which the call is handed as call.part — and in their launcher, which
+// records the call's events itself; the two large forms leave the word behind knn_index_last_stats()[2].
+int topk_one_way(knn_index *idx, const TopkEntry &t, int *indices_dev)
+{
+    const unsigned kind = t.form & (kLarge | kMasked | kSelf);
+    std::lock_guard<std::recursive_mutex> lock(idx->mu);
+    DeviceGuard guard(idx->device);
+    if (!guard.ok)
+        return fail_in(KNN_EHIP, t.who, "hipSetDevice failed");
+    // (-0 counts as 0; a self entry's queries are the resident rows: its scan reads them in place)
+    TopkCall call = topk_call_of(t.m, t.K, kind == kSelf ? idx->refs + (size_t)t.row_first * (size_t)idx->k : t.queries, t.keys, t.stream,
+                                 t.max_dist2 == 0.0f ? 0.0f : t.max_dist2);
+    call.init = (t.flags & KNN_QUERY_INIT_KEYS) != 0u;
+    const int mk = t.m * t.K;
+    begin_call(idx, t.slot);
+    if (idx->n > 0) {   // (an empty shard adds nothing)
+        topk_index_side(idx, call);
+        // the slot's scratch, grown before the first launch
+        const bool init = call.init != 0;
+        knn_index::TopkSlot &ts = idx->topk[t.slot];
+        TopkLargePlan large;
+        MaskedPlan masked;
+        MaskedListsPlan both;
+        size_t mask_bytes = 0, part_bytes = 0;
+        switch (kind) {
+        case kLarge:
+            large = knn_topk_large_plan(idx->k, t.m, t.K, idx->n, idx->num_cu, init);
+            part_bytes = large.scratch_bytes;
+            break;
+        case kMasked:
+            masked = knn_masked_plan(idx->k, t.m, t.K, idx->n, idx->num_cu, init);
+            mask_bytes = masked.mask_bytes;
+            part_bytes = masked.part_bytes;
+            break;
+        case kLarge | kMasked:
+            both = knn_masked_lists_plan(idx->k, t.m, t.K, idx->n, idx->num_cu, init);
+            mask_bytes = both.cut.mask_bytes;
+            part_bytes = both.select_bytes;
+            break;
+        default:   // kSelf
+            part_bytes = knn_self_plan(idx->k, t.m, t.K, idx->n, idx->num_cu, init).part_bytes;
+            break;
+        }
+        if ((kind & kMasked) != 0u)
+            KNN_TRY(slot_buffer_grow(ts.mask, ts.mask_bytes, mask_bytes));
+        u64 *&part = (kind & kLarge) != 0u ? ts.large : ts.part;
+        size_t &held = (kind & kLarge) != 0u ? ts.large_bytes : ts.part_bytes;
+        KNN_TRY(slot_buffer_grow(part, held, part_bytes));
+        call.part = part;
+        call.part_bytes = held;
+        KNN_TRY(take_events(idx, call));
+        switch (kind) {
+        case kLarge:
+            HIP_TRY(knn_topk_large_launch(call, large, &idx->grid_topk_gate));
+            break;
+        case kMasked:
+            HIP_TRY(knn_masked_topk_launch(call, masked, t.mask, ts.mask));
+            break;
+        case kLarge | kMasked:
+            HIP_TRY(knn_masked_large_launch(call, both, t.mask, ts.mask, &idx->grid_topk_gate));
+            break;
+        default:
+            HIP_TRY(knn_self_topk_launch(call, t.row_first));
+            break;
+        }
+    } else if (call.init) {
+        HIP_TRY(knn_keys_fill_launch(call.keys, mk, call.stream));
+    }
+    if (indices_dev)
+        HIP_TRY(knn_keys_unpack_launch(call.keys, mk, indices_dev, call.stream));
+    return KNN_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1615,54 +1769,10 @@ int knn_index_list_within(knn_index *idx, int slot, int m, const float *queries_
 int knn_index_query_topk_large(knn_index *idx, int slot, int m, int K, const float *queries_dev, float max_dist2,
                                unsigned long long *keys_dev, int *indices_dev, void *stream, unsigned flags)
 {
-    // (one message per rule, the index last, as knn_index_count_within: tests/test_topk_large_logic.py tells them apart without a GPU)
-    if (K < 1 || K > KNN_TOPK_LARGE_MAX)
-        return fail(KNN_EINVAL, "knn_index_query_topk_large: K outside 1 .. 4096");
-    if (m < 1)
-        return fail(KNN_EINVAL, "knn_index_query_topk_large: m < 1");
-    if ((long long)m * K > INT_MAX)
-        return fail(KNN_EINVAL, "knn_index_query_topk_large: m * K above INT_MAX");
-    if (slot < 0 || slot >= KNN_SLOTS)
-        return fail(KNN_EINVAL, "knn_index_query_topk_large: slot outside 0 .. 7");
-    if (!(max_dist2 >= 0.0f))
-        return fail(KNN_EINVAL, "knn_index_query_topk_large: max_dist2 must be >= 0 and not NaN");
-    if ((flags & ~(unsigned)KNN_QUERY_INIT_KEYS) != 0u)
-        return fail(KNN_EINVAL, "knn_index_query_topk_large: unknown flag (KNN_QUERY_INIT_KEYS alone is admitted)");
-    if (!queries_dev || !keys_dev)
-        return fail(KNN_EINVAL, "knn_index_query_topk_large: null queries or keys");
-    if (!idx)
-        return fail(KNN_EINVAL, "knn_index_query_topk_large: null index");
-    std::lock_guard<std::recursive_mutex> lock(idx->mu);
-    DeviceGuard guard(idx->device);
-    if (!guard.ok)
-        return fail(KNN_EHIP, "knn_index_query_topk_large: hipSetDevice failed");
-    // (-0 counts as 0)
-    TopkCall call = topk_call_of(m, K, queries_dev, keys_dev, stream, max_dist2 == 0.0f ? 0.0f : max_dist2);
-    call.init = (flags & KNN_QUERY_INIT_KEYS) != 0u;
-    hipStream_t s = call.stream;
-    const int mk = m * K;
-    begin_call(idx, slot);
-    if (idx->n > 0) {   // (an empty shard adds nothing)
-        call.k = idx->k;
-        call.n = idx->n;
-        call.base = idx->base;
-        call.gids = shard_gids(idx);
-        call.r = idx->refs;
-        call.num_cu = idx->num_cu;
-        // the slot's scratch, grown before the first launch
-        const TopkLargePlan plan = knn_topk_large_plan(idx->k, m, K, idx->n, idx->num_cu, call.init != 0);
-        knn_index::TopkSlot &ts = idx->topk[slot];
-        KNN_TRY(slot_buffer_grow(ts.large, ts.large_bytes, plan.scratch_bytes));
-        call.part = ts.large;
-        call.part_bytes = ts.large_bytes;
-        KNN_TRY(take_events(idx, call));
-        HIP_TRY(knn_topk_large_launch(call, plan, &idx->grid_topk_gate));
-    } else if (call.init) {
-        HIP_TRY(knn_keys_fill_launch(call.keys, mk, s));
-    }
-    if (indices_dev)
-        HIP_TRY(knn_keys_unpack_launch(call.keys, mk, indices_dev, s));
-    return KNN_OK;
+    // (its sizes before slot, radius and flags: tests/test_topk_large_logic.py tells the rules apart without a GPU)
+    const TopkEntry t = {"knn_index_query_topk_large", kLarge | kSizesFirst, slot, m, K, queries_dev, 0, max_dist2, nullptr, keys_dev, stream, flags};
+    KNN_TRY(topk_check(t, {{!queries_dev || !keys_dev, "null queries or keys"}}, idx));
+    return topk_one_way(idx, t, indices_dev);
 }
 
 int knn_keys_topk_merge_large(int device, int m, int K, const unsigned long long *a_dev, unsigned long long *b_dev, void *stream)
@@ -1716,60 +1826,13 @@ int knn_debug_radix_kth(const unsigned long long *keys, long long n, int K, unsi
 }
 
 // ---- queries over a subset of the rows (include/knn_mi355x.h 2g; knn_masked.hip) ------------------------------------------------
-// (one message per rule, in the header's order, the index last, as knn_index_count_within: tests/test_masked_logic.py tells them
-// apart without a GPU)
+// (tests/test_masked_logic.py tells the rules apart without a GPU)
 int knn_index_query_topk_masked(knn_index *idx, int slot, int m, int K, const float *queries_dev, float max_dist2,
                                 const unsigned *mask_dev, unsigned long long *keys_dev, int *indices_dev, void *stream, unsigned flags)
 {
-    if (!(max_dist2 >= 0.0f))
-        return fail(KNN_EINVAL, "knn_index_query_topk_masked: max_dist2 must be >= 0 and not NaN");
-    if ((flags & ~(unsigned)KNN_QUERY_INIT_KEYS) != 0u)
-        return fail(KNN_EINVAL, "knn_index_query_topk_masked: unknown flag (KNN_QUERY_INIT_KEYS alone is admitted)");
-    if (slot < 0 || slot >= KNN_SLOTS)
-        return fail(KNN_EINVAL, "knn_index_query_topk_masked: slot outside 0 .. 7");
-    if (m < 1)
-        return fail(KNN_EINVAL, "knn_index_query_topk_masked: m < 1");
-    if (K < 1 || K > KNN_TOPK_MAX)
-        return fail(KNN_EINVAL, "knn_index_query_topk_masked: K outside 1 .. 64");
-    if ((long long)m * K > INT_MAX)
-        return fail(KNN_EINVAL, "knn_index_query_topk_masked: m * K above INT_MAX");
-    if (!queries_dev || !mask_dev || !keys_dev)
-        return fail(KNN_EINVAL, "knn_index_query_topk_masked: null queries, mask or keys");
-    if (!idx)
-        return fail(KNN_EINVAL, "knn_index_query_topk_masked: null index");
-    std::lock_guard<std::recursive_mutex> lock(idx->mu);
-    DeviceGuard guard(idx->device);
-    if (!guard.ok)
-        return fail(KNN_EHIP, "knn_index_query_topk_masked: hipSetDevice failed");
-    // (-0 counts as 0)
-    TopkCall call = topk_call_of(m, K, queries_dev, keys_dev, stream, max_dist2 == 0.0f ? 0.0f : max_dist2);
-    call.init = (flags & KNN_QUERY_INIT_KEYS) != 0u;
-    hipStream_t s = call.stream;
-    const int mk = m * K;
-    // one way on every index: no layout is consulted
-    begin_call(idx, slot);
-    if (idx->n > 0) {   // (an empty shard adds nothing)
-        call.k = idx->k;
-        call.n = idx->n;
-        call.base = idx->base;
-        call.gids = shard_gids(idx);
-        call.r = idx->refs;
-        call.num_cu = idx->num_cu;
-        // the slot's scratch, grown before the first launch
-        const MaskedPlan plan = knn_masked_plan(idx->k, m, K, idx->n, idx->num_cu, call.init != 0);
-        knn_index::TopkSlot &ts = idx->topk[slot];
-        KNN_TRY(slot_buffer_grow(ts.mask, ts.mask_bytes, plan.mask_bytes));
-        KNN_TRY(slot_buffer_grow(ts.part, ts.part_bytes, plan.part_bytes));
-        call.part = ts.part;
-        call.part_bytes = ts.part_bytes;
-        KNN_TRY(take_events(idx, call));
-        HIP_TRY(knn_masked_topk_launch(call, plan, mask_dev, ts.mask));
-    } else if (call.init) {
-        HIP_TRY(knn_keys_fill_launch(call.keys, mk, s));
-    }
-    if (indices_dev)
-        HIP_TRY(knn_keys_unpack_launch(call.keys, mk, indices_dev, s));
-    return KNN_OK;
+    const TopkEntry t = {"knn_index_query_topk_masked", kMasked, slot, m, K, queries_dev, 0, max_dist2, mask_dev, keys_dev, stream, flags};
+    KNN_TRY(topk_check(t, {{!queries_dev || !mask_dev || !keys_dev, "null queries, mask or keys"}}, idx));
+    return topk_one_way(idx, t, indices_dev);
 }
 
 int knn_index_count_within_masked(knn_index *idx, int slot, int m, const float *queries_dev, float max_dist2,
@@ -1860,59 +1923,10 @@ int knn_index_query_topk_large_masked(knn_index *idx, int slot, int m, int K, co
                                       const unsigned *mask_dev, unsigned long long *keys_dev, int *indices_dev, void *stream,
                                       unsigned flags)
 {
-    if (!(max_dist2 >= 0.0f))
-        return fail(KNN_EINVAL, "knn_index_query_topk_large_masked: max_dist2 must be >= 0 and not NaN");
-    if ((flags & ~(unsigned)KNN_QUERY_INIT_KEYS) != 0u)
-        return fail(KNN_EINVAL, "knn_index_query_topk_large_masked: unknown flag (KNN_QUERY_INIT_KEYS alone is admitted)");
-    if (slot < 0 || slot >= KNN_SLOTS)
-        return fail(KNN_EINVAL, "knn_index_query_topk_large_masked: slot outside 0 .. 7");
-    if (m < 1)
-        return fail(KNN_EINVAL, "knn_index_query_topk_large_masked: m < 1");
-    if (K < 1 || K > KNN_TOPK_LARGE_MAX)
-        return fail(KNN_EINVAL, "knn_index_query_topk_large_masked: K outside 1 .. 4096");
-    if ((long long)m * K > INT_MAX)
-        return fail(KNN_EINVAL, "knn_index_query_topk_large_masked: m * K above INT_MAX");
-    if (!queries_dev)
-        return fail(KNN_EINVAL, "knn_index_query_topk_large_masked: null queries");
-    if (!mask_dev)
-        return fail(KNN_EINVAL, "knn_index_query_topk_large_masked: null mask");
-    if (!keys_dev)
-        return fail(KNN_EINVAL, "knn_index_query_topk_large_masked: null keys");
-    if (!idx)
-        return fail(KNN_EINVAL, "knn_index_query_topk_large_masked: null index");
-    std::lock_guard<std::recursive_mutex> lock(idx->mu);
-    DeviceGuard guard(idx->device);
-    if (!guard.ok)
-        return fail(KNN_EHIP, "knn_index_query_topk_large_masked: hipSetDevice failed");
-    // (-0 counts as 0)
-    TopkCall call = topk_call_of(m, K, queries_dev, keys_dev, stream, max_dist2 == 0.0f ? 0.0f : max_dist2);
-    call.init = (flags & KNN_QUERY_INIT_KEYS) != 0u;
-    hipStream_t s = call.stream;
-    const int mk = m * K;
-    // one way on every index: no layout is consulted
-    begin_call(idx, slot);
-    if (idx->n > 0) {   // (an empty shard adds nothing)
-        call.k = idx->k;
-        call.n = idx->n;
-        call.base = idx->base;
-        call.gids = shard_gids(idx);
-        call.r = idx->refs;
-        call.num_cu = idx->num_cu;
-        // the slot's mask scratch and large scratch, grown before the first launch
-        const MaskedListsPlan plan = knn_masked_lists_plan(idx->k, m, K, idx->n, idx->num_cu, call.init != 0);
-        knn_index::TopkSlot &ts = idx->topk[slot];
-        KNN_TRY(slot_buffer_grow(ts.mask, ts.mask_bytes, plan.cut.mask_bytes));
-        KNN_TRY(slot_buffer_grow(ts.large, ts.large_bytes, plan.select_bytes));
-        call.part = ts.large;
-        call.part_bytes = ts.large_bytes;
-        KNN_TRY(take_events(idx, call));
-        HIP_TRY(knn_masked_large_launch(call, plan, mask_dev, ts.mask, &idx->grid_topk_gate));
-    } else if (call.init) {
-        HIP_TRY(knn_keys_fill_launch(call.keys, mk, s));
-    }
-    if (indices_dev)
-        HIP_TRY(knn_keys_unpack_launch(call.keys, mk, indices_dev, s));
-    return KNN_OK;
+    const TopkEntry t = {"knn_index_query_topk_large_masked", kLarge | kMasked, slot, m, K, queries_dev, 0, max_dist2, mask_dev, keys_dev, stream,
+                         flags};
+    KNN_TRY(topk_check(t, {{!queries_dev, "null queries"}, {!mask_dev, "null mask"}, {!keys_dev, "null keys"}}, idx));
+    return topk_one_way(idx, t, indices_dev);
 }
 
 int knn_debug_masked_lists_plan(const long long in[6], long long out[8])
@@ -1934,68 +1948,36 @@ int knn_debug_masked_lists_plan(const long long in[6], long long out[8])
 int knn_index_self_topk(knn_index *idx, int slot, long long row_first, int rows, int K, float max_dist2, unsigned long long *keys_dev,
                         int *indices_dev, void *stream, unsigned flags)
 {
-    if (!(max_dist2 >= 0.0f))
-        return fail(KNN_EINVAL, "knn_index_self_topk: max_dist2 must be >= 0 and not NaN");
-    constexpr unsigned kSelfTopkFlags = KNN_QUERY_INIT_KEYS | KNN_QUERY_TOPK_GRID | KNN_QUERY_TOPK_FRAMES;   // the three it admits
-    if ((flags & ~kSelfTopkFlags) != 0u)
-        return fail(KNN_EINVAL, "knn_index_self_topk: unknown flag (KNN_QUERY_INIT_KEYS, KNN_QUERY_TOPK_GRID, KNN_QUERY_TOPK_FRAMES)");
-    if (slot < 0 || slot >= KNN_SLOTS)
-        return fail(KNN_EINVAL, "knn_index_self_topk: slot outside 0 .. 7");
-    if (rows < 1)
-        return fail(KNN_EINVAL, "knn_index_self_topk: rows < 1");
-    if (row_first < 0)
-        return fail(KNN_EINVAL, "knn_index_self_topk: row_first < 0");
-    if (K < 1 || K > KNN_TOPK_MAX)
-        return fail(KNN_EINVAL, "knn_index_self_topk: K outside 1 .. 64");
-    if ((long long)rows * K > INT_MAX)
-        return fail(KNN_EINVAL, "knn_index_self_topk: rows * K above INT_MAX");
-    if (!keys_dev)
-        return fail(KNN_EINVAL, "knn_index_self_topk: null keys");
-    if (!idx)
-        return fail(KNN_EINVAL, "knn_index_self_topk: null index");
+    const TopkEntry t = {"knn_index_self_topk", kSelf, slot, rows, K, nullptr, row_first, max_dist2, nullptr, keys_dev, stream, flags,
+                         KNN_QUERY_INIT_KEYS | KNN_QUERY_TOPK_GRID | KNN_QUERY_TOPK_FRAMES};   // the three it admits
+    KNN_TRY(topk_check(t, {{!keys_dev, "null keys"}}, idx));
     std::lock_guard<std::recursive_mutex> lock(idx->mu);
     if (row_first > idx->n || (long long)rows > idx->n - row_first)
         return fail(KNN_EINVAL, "knn_index_self_topk: row_first + rows above the shard's rows");
+    // The way: what the one route function says for the plain call of K + 1 neighbours — self is among ITS candidates — with
+    // this call's rows, flags and options.  Exact, or no room for K + 1 keys — K = 64, or rows * (K + 1) beyond the plain call's
+    // own INT_MAX limit —: the self-scan with K (the header's 2i says so), on the one-way front.
+    const bool through = K + 1 <= KNN_TOPK_MAX && (long long)rows * (K + 1) <= INT_MAX && knn_query_route(route_inputs(idx, rows, K + 1, flags)).way != QueryWay::Exact;
+    if (!through)
+        return topk_one_way(idx, t, indices_dev);
     DeviceGuard guard(idx->device);
     if (!guard.ok)
         return fail(KNN_EHIP, "knn_index_self_topk: hipSetDevice failed");
-    // (-0 counts as 0; the queries are the resident rows: the scans read them in place, the through way is handed their address)
-    TopkCall call = topk_call_of(rows, K, idx->refs + (size_t)row_first * (size_t)idx->k, keys_dev, stream, max_dist2 == 0.0f ? 0.0f : max_dist2);
-    call.init = (flags & KNN_QUERY_INIT_KEYS) != 0u;
-    hipStream_t s = call.stream;
-    const int mk = rows * K;
-    const SelfPlan plan = knn_self_plan(idx->k, rows, K, idx->n, idx->num_cu, call.init != 0);
+    // the plain call as it is — its queries the resident rows, handed by address; -0 counts as 0 —, K + 1 keys per row into the slot's
+    // scratch; its fallbacks and statistics are its own
+    const bool init = (flags & KNN_QUERY_INIT_KEYS) != 0u;
+    hipStream_t s = (hipStream_t)stream;
+    u64 *keys = (u64 *)keys_dev;
     knn_index::TopkSlot &ts = idx->topk[slot];
-    const unsigned *gids = shard_gids(idx);
-    // The way: what the one route function says for the plain call of K + 1 neighbours — self is among ITS candidates — with
-    // this call's rows, flags and options.  Exact, or no room for K + 1 keys — K = 64, or rows * (K + 1) beyond the plain call's
-    // own INT_MAX limit —: the self-scan with K (the header's 2i says so).
-    const bool through = K + 1 <= KNN_TOPK_MAX && (long long)rows * (K + 1) <= INT_MAX && knn_query_route(route_inputs(idx, rows, K + 1, flags)).way != QueryWay::Exact;
-    if (through) {
-        // the plain call as it is, K + 1 keys per row into the slot's scratch; its fallbacks and statistics are its own
-        KNN_TRY(slot_buffer_grow(ts.self, ts.self_bytes, plan.through_bytes));
-        const TopkCall plain = topk_call_of(rows, K + 1, call.q, ts.self, stream, call.max_dist2);
-        KNN_TRY(query_topk(idx, slot, plain, nullptr, flags | KNN_QUERY_INIT_KEYS, "knn_index_self_topk"));
-        u64 *kept = call.init ? call.keys : ts.self + (size_t)rows * (size_t)(K + 1);
-        HIP_TRY(knn_self_drop_launch(rows, K, ts.self, row_first, idx->base, gids, kept, s));
-        if (!call.init)
-            HIP_TRY(knn_topk_merge_launch(rows, K, kept, call.keys, s));
-    } else {
-        begin_call(idx, slot);
-        call.k = idx->k;
-        call.n = idx->n;
-        call.base = idx->base;
-        call.gids = gids;
-        call.r = idx->refs;
-        call.num_cu = idx->num_cu;
-        KNN_TRY(slot_buffer_grow(ts.part, ts.part_bytes, plan.part_bytes));
-        call.part = ts.part;
-        call.part_bytes = ts.part_bytes;
-        KNN_TRY(take_events(idx, call));
-        HIP_TRY(knn_self_topk_launch(call, row_first));
-    }
+    KNN_TRY(slot_buffer_grow(ts.self, ts.self_bytes, knn_self_plan(idx->k, rows, K, idx->n, idx->num_cu, init).through_bytes));
+    const TopkCall plain = topk_call_of(rows, K + 1, idx->refs + (size_t)row_first * (size_t)idx->k, ts.self, stream, max_dist2 == 0.0f ? 0.0f : max_dist2);
+    KNN_TRY(query_topk(idx, slot, plain, nullptr, flags | KNN_QUERY_INIT_KEYS, "knn_index_self_topk"));
+    u64 *kept = init ? keys : ts.self + (size_t)rows * (size_t)(K + 1);
+    HIP_TRY(knn_self_drop_launch(rows, K, ts.self, row_first, idx->base, shard_gids(idx), kept, s));
+    if (!init)
+        HIP_TRY(knn_topk_merge_launch(rows, K, kept, keys, s));
     if (indices_dev)
-        HIP_TRY(knn_keys_unpack_launch(call.keys, mk, indices_dev, s));
+        HIP_TRY(knn_keys_unpack_launch(keys, rows * K, indices_dev, s));
     return KNN_OK;
 }
 
@@ -2782,6 +2764,85 @@ int lists_to_host(const char *who, const std::vector<u64> &offs, const std::vect
     return KNN_OK;
 }
 
+// The synchronous top-K calls over queries on the host (2f, 2g, 2h) behind topk_check: t.queries and t.mask are host arrays.  The
+// queries, the keys and a masked form's mask — max((n_local + 31) / 32, 1) words, copied unless the shard is empty — are staged,
+// device_call(queries, mask, keys) is the entry's device call on the null stream, slot 0, writing its keys, and the keys come
+// back through unpack_topk.
+template <class DeviceCall>
+int topk_host_run(knn_index *idx, const TopkEntry &t, int *indices_host, float *dist2_host, int *counts_host, DeviceCall device_call)
+{
+    const bool masked = (t.form & kMasked) != 0u;
+    std::lock_guard<std::recursive_mutex> lock(idx->mu);
+    DeviceGuard guard(idx->device);
+    if (!guard.ok)
+        return fail_in(KNN_EHIP, t.who, "hipSetDevice failed");
+    const size_t mk = (size_t)t.m * (size_t)t.K;
+    std::vector<u64> keys(mk);
+    {
+        Staging stage(idx->device);
+        float *q_dev = nullptr;
+        u64 *keys_dev = nullptr;
+        unsigned *mask_dev = nullptr;
+        const size_t qbytes = (size_t)t.m * (size_t)idx->k * sizeof(float);
+        const size_t mbytes = std::max<size_t>((size_t)((idx->n + 31) / 32), 1) * sizeof(unsigned);   // (an empty shard: one word, unread)
+        hipError_t e = stage.get(&q_dev, qbytes);
+        if (e == hipSuccess)
+            e = stage.get(&keys_dev, mk * sizeof(u64));
+        if (e == hipSuccess && masked)
+            e = stage.get(&mask_dev, mbytes);
+        if (e == hipSuccess)
+            e = hipMemcpy(q_dev, t.queries, qbytes, hipMemcpyHostToDevice);
+        if (e == hipSuccess && masked && idx->n > 0)
+            e = hipMemcpy(mask_dev, t.mask, mbytes, hipMemcpyHostToDevice);
+        if (e != hipSuccess)
+            return fail_in(KNN_EHIP, t.who, masked ? "staging queries and mask" : "staging queries", hipGetErrorString(e));
+        KNN_TRY(device_call(q_dev, mask_dev, keys_dev));
+        e = hipMemcpy(keys.data(), keys_dev, mk * sizeof(u64), hipMemcpyDeviceToHost);
+        if (e != hipSuccess)
+            return fail_in(KNN_EHIP, t.who, "D2H keys", hipGetErrorString(e));
+        // (not declared waited: the buffers go back after the device-wide wait `stage` then makes itself, as the top-K's)
+    }
+    unpack_topk(keys.data(), t.m, t.K, indices_host, dist2_host, counts_host);
+    return KNN_OK;
+}
+
+// The round every synchronous list call makes once its inputs are staged: counts() issues the counts of the `segments` queries or
+// rows into c_dev, lists(keys_dev) their lists into off_dev / fill_dev / keys_dev, both on the null stream.  count -> offsets, the
+// one synchronisation (the total sizes the keys, staged in `stage` when it is non-zero), list -> sort, and the sorted keys to the
+// caller through lists_to_host.
+template <class Counts, class Lists>
+int lists_host_round(knn_index *idx, const char *who, Staging &stage, int segments, const unsigned *c_dev, const unsigned *fill_dev,
+                     u64 *off_dev, long long *offsets_host, int **indices_out, float **dist2_out, Counts counts, Lists lists)
+{
+    int rc = counts();
+    if (rc == KNN_OK)
+        rc = knn_counts_to_offsets(idx->device, c_dev, segments, off_dev, nullptr);
+    if (rc != KNN_OK)
+        return rc;
+    std::vector<u64> offs((size_t)segments + 1);
+    hipError_t e = hipMemcpy(offs.data(), off_dev, offs.size() * sizeof(u64), hipMemcpyDeviceToHost);
+    if (e != hipSuccess)
+        return fail_in(KNN_EHIP, who, "D2H offsets", hipGetErrorString(e));
+    const u64 total = offs[(size_t)segments];
+    std::vector<u64> keys((size_t)total);
+    if (total) {
+        u64 *keys_dev = nullptr;
+        e = stage.get(&keys_dev, (size_t)total * sizeof(u64));
+        if (e != hipSuccess)
+            return fail_in(KNN_EHIP, who, "staging keys", hipGetErrorString(e));
+        rc = lists(keys_dev);
+        if (rc == KNN_OK)
+            rc = knn_keys_sort_segments(idx->device, segments, off_dev, fill_dev, keys_dev, nullptr);
+        if (rc != KNN_OK)
+            return rc;
+        e = hipMemcpy(keys.data(), keys_dev, (size_t)total * sizeof(u64), hipMemcpyDeviceToHost);
+        if (e != hipSuccess)
+            return fail_in(KNN_EHIP, who, "D2H keys", hipGetErrorString(e));
+    }
+    // (not declared waited: the slot's buffers go back after the device-wide wait `stage` then makes itself, as the other host calls)
+    return lists_to_host(who, offs, keys, offsets_host, indices_out, dist2_out);
+}
+
 }  // namespace
 
 extern "C" int knn_index_query_host(knn_index *idx, int m, const float *queries_host, int *out_host)
@@ -2834,97 +2895,21 @@ extern "C" int knn_index_query_topk_within_host(knn_index *idx, int m, int K, co
 extern "C" int knn_index_query_topk_large_host(knn_index *idx, int m, int K, const float *queries_host, float max_dist2,
                                                int *indices_host, float *dist2_host, int *counts_host)
 {
-    if (K < 1 || K > KNN_TOPK_LARGE_MAX)
-        return fail(KNN_EINVAL, "knn_index_query_topk_large_host: K outside 1 .. 4096");
-    if (m < 1)
-        return fail(KNN_EINVAL, "knn_index_query_topk_large_host: m < 1");
-    if ((long long)m * K > INT_MAX)
-        return fail(KNN_EINVAL, "knn_index_query_topk_large_host: m * K above INT_MAX");
-    if (!(max_dist2 >= 0.0f))
-        return fail(KNN_EINVAL, "knn_index_query_topk_large_host: max_dist2 must be >= 0 and not NaN");
-    if (!queries_host || !indices_host)
-        return fail(KNN_EINVAL, "knn_index_query_topk_large_host: null queries or indices");
-    if (!idx)
-        return fail(KNN_EINVAL, "knn_index_query_topk_large_host: null index");
-    std::lock_guard<std::recursive_mutex> lock(idx->mu);
-    DeviceGuard guard(idx->device);
-    if (!guard.ok)
-        return fail(KNN_EHIP, "knn_index_query_topk_large_host: hipSetDevice failed");
-    const size_t mk = (size_t)m * (size_t)K;
-    std::vector<u64> keys(mk);
-    {
-        Staging stage(idx->device);
-        float *q_dev = nullptr;
-        u64 *keys_dev = nullptr;
-        const size_t qbytes = (size_t)m * (size_t)idx->k * sizeof(float);
-        hipError_t e = stage.get(&q_dev, qbytes);
-        if (e == hipSuccess)
-            e = stage.get(&keys_dev, mk * sizeof(u64));
-        if (e == hipSuccess)
-            e = hipMemcpy(q_dev, queries_host, qbytes, hipMemcpyHostToDevice);
-        if (e != hipSuccess)
-            return fail(KNN_EHIP, "knn_index_query_topk_large_host: staging queries", hipGetErrorString(e));
-        const int rc = knn_index_query_topk_large(idx, 0, m, K, q_dev, max_dist2, keys_dev, nullptr, nullptr, KNN_QUERY_INIT_KEYS);
-        if (rc != KNN_OK)
-            return rc;
-        e = hipMemcpy(keys.data(), keys_dev, mk * sizeof(u64), hipMemcpyDeviceToHost);
-        if (e != hipSuccess)
-            return fail(KNN_EHIP, "knn_index_query_topk_large_host: D2H keys", hipGetErrorString(e));
-        // (not declared waited: the buffers go back after the device-wide wait `stage` then makes itself, as the top-K's)
-    }
-    unpack_topk(keys.data(), m, K, indices_host, dist2_host, counts_host);
-    return KNN_OK;
+    const TopkEntry t = {"knn_index_query_topk_large_host", kLarge | kSizesFirst, 0, m, K, queries_host, 0, max_dist2};
+    KNN_TRY(topk_check(t, {{!queries_host || !indices_host, "null queries or indices"}}, idx));
+    return topk_host_run(idx, t, indices_host, dist2_host, counts_host, [&](const float *q_dev, const unsigned *, u64 *keys_dev) {
+        return knn_index_query_topk_large(idx, 0, m, K, q_dev, max_dist2, keys_dev, nullptr, nullptr, KNN_QUERY_INIT_KEYS);
+    });
 }
 
 extern "C" int knn_index_query_topk_masked_host(knn_index *idx, int m, int K, const float *queries_host, float max_dist2,
                                                 const unsigned *mask_host, int *indices_host, float *dist2_host, int *counts_host)
 {
-    if (!(max_dist2 >= 0.0f))
-        return fail(KNN_EINVAL, "knn_index_query_topk_masked_host: max_dist2 must be >= 0 and not NaN");
-    if (m < 1)
-        return fail(KNN_EINVAL, "knn_index_query_topk_masked_host: m < 1");
-    if (K < 1 || K > KNN_TOPK_MAX)
-        return fail(KNN_EINVAL, "knn_index_query_topk_masked_host: K outside 1 .. 64");
-    if ((long long)m * K > INT_MAX)
-        return fail(KNN_EINVAL, "knn_index_query_topk_masked_host: m * K above INT_MAX");
-    if (!queries_host || !mask_host || !indices_host)
-        return fail(KNN_EINVAL, "knn_index_query_topk_masked_host: null queries, mask or indices");
-    if (!idx)
-        return fail(KNN_EINVAL, "knn_index_query_topk_masked_host: null index");
-    std::lock_guard<std::recursive_mutex> lock(idx->mu);
-    DeviceGuard guard(idx->device);
-    if (!guard.ok)
-        return fail(KNN_EHIP, "knn_index_query_topk_masked_host: hipSetDevice failed");
-    const size_t mk = (size_t)m * (size_t)K;
-    std::vector<u64> keys(mk);
-    {
-        Staging stage(idx->device);
-        float *q_dev = nullptr;
-        u64 *keys_dev = nullptr;
-        unsigned *mask_dev = nullptr;
-        const size_t qbytes = (size_t)m * (size_t)idx->k * sizeof(float);
-        const size_t mbytes = std::max<size_t>((size_t)((idx->n + 31) / 32), 1) * sizeof(unsigned);   // (an empty shard: one word, unread)
-        hipError_t e = stage.get(&q_dev, qbytes);
-        if (e == hipSuccess)
-            e = stage.get(&keys_dev, mk * sizeof(u64));
-        if (e == hipSuccess)
-            e = stage.get(&mask_dev, mbytes);
-        if (e == hipSuccess)
-            e = hipMemcpy(q_dev, queries_host, qbytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess && idx->n > 0)
-            e = hipMemcpy(mask_dev, mask_host, mbytes, hipMemcpyHostToDevice);
-        if (e != hipSuccess)
-            return fail(KNN_EHIP, "knn_index_query_topk_masked_host: staging queries and mask", hipGetErrorString(e));
-        const int rc = knn_index_query_topk_masked(idx, 0, m, K, q_dev, max_dist2, mask_dev, keys_dev, nullptr, nullptr, KNN_QUERY_INIT_KEYS);
-        if (rc != KNN_OK)
-            return rc;
-        e = hipMemcpy(keys.data(), keys_dev, mk * sizeof(u64), hipMemcpyDeviceToHost);
-        if (e != hipSuccess)
-            return fail(KNN_EHIP, "knn_index_query_topk_masked_host: D2H keys", hipGetErrorString(e));
-        // (not declared waited: the buffers go back after the device-wide wait `stage` then makes itself, as the top-K's)
-    }
-    unpack_topk(keys.data(), m, K, indices_host, dist2_host, counts_host);
-    return KNN_OK;
+    const TopkEntry t = {"knn_index_query_topk_masked_host", kMasked, 0, m, K, queries_host, 0, max_dist2, mask_host};
+    KNN_TRY(topk_check(t, {{!queries_host || !mask_host || !indices_host, "null queries, mask or indices"}}, idx));
+    return topk_host_run(idx, t, indices_host, dist2_host, counts_host, [&](const float *q_dev, const unsigned *mask_dev, u64 *keys_dev) {
+        return knn_index_query_topk_masked(idx, 0, m, K, q_dev, max_dist2, mask_dev, keys_dev, nullptr, nullptr, KNN_QUERY_INIT_KEYS);
+    });
 }
 
 // The synchronous count and list calls behind their argument checks: radii_host null — the scalar calls at max_dist2 —, or the
@@ -2976,7 +2961,7 @@ static int list_within_host_run(knn_index *idx, const char *who, int m, const fl
     Staging stage(idx->device);
     float *q_dev = nullptr, *r_dev = nullptr;
     unsigned *c_dev = nullptr, *fill_dev = nullptr;
-    u64 *off_dev = nullptr, *keys_dev = nullptr;
+    u64 *off_dev = nullptr;
     const size_t qbytes = (size_t)m * (size_t)idx->k * sizeof(float), cbytes = (size_t)m * sizeof(unsigned);
     const size_t obytes = ((size_t)m + 1) * sizeof(u64), rbytes = (size_t)m * sizeof(float);
     hipError_t e = stage.get(&q_dev, qbytes);
@@ -2994,36 +2979,17 @@ static int list_within_host_run(knn_index *idx, const char *who, int m, const fl
         e = hipMemcpy(r_dev, radii_host, rbytes, hipMemcpyHostToDevice);
     if (e != hipSuccess)
         return fail_in(KNN_EHIP, who, "staging queries", hipGetErrorString(e));
-    // count -> offsets, then the one synchronisation: the total sizes the keys
-    int rc = radii_host ? knn_index_count_within_each(idx, 0, m, q_dev, r_dev, max_dist2, c_dev, nullptr, KNN_QUERY_INIT_KEYS)
-                        : knn_index_count_within(idx, 0, m, q_dev, max_dist2, c_dev, nullptr, KNN_QUERY_INIT_KEYS);
-    if (rc == KNN_OK)
-        rc = knn_counts_to_offsets(idx->device, c_dev, m, off_dev, nullptr);
-    if (rc != KNN_OK)
-        return rc;
-    std::vector<u64> offs((size_t)m + 1);
-    e = hipMemcpy(offs.data(), off_dev, obytes, hipMemcpyDeviceToHost);
-    if (e != hipSuccess)
-        return fail_in(KNN_EHIP, who, "D2H offsets", hipGetErrorString(e));
-    const u64 total = offs[(size_t)m];
-    std::vector<u64> keys((size_t)total);
-    if (total) {   // list -> sort
-        e = stage.get(&keys_dev, (size_t)total * sizeof(u64));
-        if (e != hipSuccess)
-            return fail_in(KNN_EHIP, who, "staging keys", hipGetErrorString(e));
-        rc = radii_host ? knn_index_list_within_each(idx, 0, m, q_dev, r_dev, max_dist2, off_dev, fill_dev, keys_dev, nullptr,
-                                                     KNN_QUERY_INIT_KEYS)
-                        : knn_index_list_within(idx, 0, m, q_dev, max_dist2, off_dev, fill_dev, keys_dev, nullptr, KNN_QUERY_INIT_KEYS);
-        if (rc == KNN_OK)
-            rc = knn_keys_sort_segments(idx->device, m, off_dev, fill_dev, keys_dev, nullptr);
-        if (rc != KNN_OK)
-            return rc;
-        e = hipMemcpy(keys.data(), keys_dev, (size_t)total * sizeof(u64), hipMemcpyDeviceToHost);
-        if (e != hipSuccess)
-            return fail_in(KNN_EHIP, who, "D2H keys", hipGetErrorString(e));
-    }
-    // (not declared waited: the slot's buffers go back after the device-wide wait `stage` then makes itself, as the other host calls)
-    return lists_to_host(who, offs, keys, offsets_host, indices_out, dist2_out);
+    return lists_host_round(
+        idx, who, stage, m, c_dev, fill_dev, off_dev, offsets_host, indices_out, dist2_out,
+        [&] {
+            return radii_host ? knn_index_count_within_each(idx, 0, m, q_dev, r_dev, max_dist2, c_dev, nullptr, KNN_QUERY_INIT_KEYS)
+                              : knn_index_count_within(idx, 0, m, q_dev, max_dist2, c_dev, nullptr, KNN_QUERY_INIT_KEYS);
+        },
+        [&](u64 *keys_dev) {
+            return radii_host ? knn_index_list_within_each(idx, 0, m, q_dev, r_dev, max_dist2, off_dev, fill_dev, keys_dev, nullptr,
+                                                           KNN_QUERY_INIT_KEYS)
+                              : knn_index_list_within(idx, 0, m, q_dev, max_dist2, off_dev, fill_dev, keys_dev, nullptr, KNN_QUERY_INIT_KEYS);
+        });
 }
 
 extern "C" int knn_index_count_within_host(knn_index *idx, int m, const float *queries_host, float max_dist2, unsigned *counts_host)
@@ -3062,14 +3028,9 @@ extern "C" int knn_index_list_within_each_host(knn_index *idx, int m, const floa
 // ---- the whole shard about its own rows (include/knn_mi355x.h 2i): the kNN graph and the radius graph, synchronous ---------------
 extern "C" int knn_index_self_topk_host(knn_index *idx, int K, float max_dist2, int *indices_host, float *dist2_host, int *counts_host)
 {
-    if (!(max_dist2 >= 0.0f))
-        return fail(KNN_EINVAL, "knn_index_self_topk_host: max_dist2 must be >= 0 and not NaN");
-    if (K < 1 || K > KNN_TOPK_MAX)
-        return fail(KNN_EINVAL, "knn_index_self_topk_host: K outside 1 .. 64");
-    if (!indices_host)
-        return fail(KNN_EINVAL, "knn_index_self_topk_host: null indices");
-    if (!idx)
-        return fail(KNN_EINVAL, "knn_index_self_topk_host: null index");
+    // (the rows are the whole shard's: the entry states none, and one row cannot break the m * K rule)
+    const TopkEntry t = {"knn_index_self_topk_host", kSelf, 0, 1, K, nullptr, 0, max_dist2};
+    KNN_TRY(topk_check(t, {{!indices_host, "null indices"}}, idx));
     std::lock_guard<std::recursive_mutex> lock(idx->mu);
     if (idx->n == 0)
         return KNN_OK;
@@ -3116,63 +3077,47 @@ static int self_list_host_run(knn_index *idx, const char *who, bool routed, cons
     const int n = (int)idx->n;
     const int step = KNN_TOPK_CHUNK;   // rows per call
     const unsigned fl = KNN_QUERY_INIT_KEYS | flags;
-    std::vector<u64> offs((size_t)n + 1, 0ull);
-    std::vector<u64> keys;
     Staging stage(idx->device);
-    if (n > 0) {
-        unsigned *c_dev = nullptr, *fill_dev = nullptr;
-        u64 *off_dev = nullptr, *keys_dev = nullptr;
-        float *rad_dev = nullptr;
-        const size_t cbytes = (size_t)n * sizeof(unsigned), obytes = ((size_t)n + 1) * sizeof(u64);
-        hipError_t e = stage.get(&c_dev, cbytes);
-        if (e == hipSuccess)
-            e = stage.get(&fill_dev, cbytes);
-        if (e == hipSuccess)
-            e = stage.get(&off_dev, obytes);
-        if (e == hipSuccess && radii_host)
-            e = stage.get(&rad_dev, (size_t)n * sizeof(float));
+    if (n == 0)   // (an empty shard: the one offset 0, one element of room)
+        return lists_to_host(who, std::vector<u64>(1, 0ull), std::vector<u64>(), offsets_host, indices_out, dist2_out);
+    unsigned *c_dev = nullptr, *fill_dev = nullptr;
+    u64 *off_dev = nullptr;
+    float *rad_dev = nullptr;
+    const size_t cbytes = (size_t)n * sizeof(unsigned), obytes = ((size_t)n + 1) * sizeof(u64);
+    hipError_t e = stage.get(&c_dev, cbytes);
+    if (e == hipSuccess)
+        e = stage.get(&fill_dev, cbytes);
+    if (e == hipSuccess)
+        e = stage.get(&off_dev, obytes);
+    if (e == hipSuccess && radii_host)
+        e = stage.get(&rad_dev, (size_t)n * sizeof(float));
+    if (e != hipSuccess)
+        return fail_in(KNN_EHIP, who, "staging counts", hipGetErrorString(e));
+    if (radii_host) {
+        e = hipMemcpy(rad_dev, radii_host, (size_t)n * sizeof(float), hipMemcpyHostToDevice);
         if (e != hipSuccess)
-            return fail_in(KNN_EHIP, who, "staging counts", hipGetErrorString(e));
-        if (radii_host) {
-            e = hipMemcpy(rad_dev, radii_host, (size_t)n * sizeof(float), hipMemcpyHostToDevice);
-            if (e != hipSuccess)
-                return fail_in(KNN_EHIP, who, "H2D radii", hipGetErrorString(e));
-        }
-        // count -> offsets, then the one synchronisation: the total sizes the keys
-        int rv = KNN_OK;
-        for (int r0 = 0; r0 < n && rv == KNN_OK; r0 += step)
-            rv = routed ? knn_index_self_count_within_routed(idx, 0, r0, std::min(step, n - r0), rad_dev ? rad_dev + r0 : nullptr, max_dist2,
-                                                             c_dev + r0, nullptr, fl)
-                        : knn_index_self_count_within(idx, 0, r0, std::min(step, n - r0), max_dist2, c_dev + r0, nullptr, fl);
-        if (rv == KNN_OK)
-            rv = knn_counts_to_offsets(idx->device, c_dev, n, off_dev, nullptr);
-        if (rv != KNN_OK)
+            return fail_in(KNN_EHIP, who, "H2D radii", hipGetErrorString(e));
+    }
+    // (the offsets are absolute: every block of rows stores into the one keys array)
+    return lists_host_round(
+        idx, who, stage, n, c_dev, fill_dev, off_dev, offsets_host, indices_out, dist2_out,
+        [&] {
+            int rv = KNN_OK;
+            for (int r0 = 0; r0 < n && rv == KNN_OK; r0 += step)
+                rv = routed ? knn_index_self_count_within_routed(idx, 0, r0, std::min(step, n - r0), rad_dev ? rad_dev + r0 : nullptr, max_dist2,
+                                                                 c_dev + r0, nullptr, fl)
+                            : knn_index_self_count_within(idx, 0, r0, std::min(step, n - r0), max_dist2, c_dev + r0, nullptr, fl);
             return rv;
-        e = hipMemcpy(offs.data(), off_dev, obytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess)
-            return fail_in(KNN_EHIP, who, "D2H offsets", hipGetErrorString(e));
-        const u64 total = offs[(size_t)n];
-        keys.resize((size_t)total);
-        if (total) {   // list -> sort (the offsets are absolute: every block of rows stores into the one keys array)
-            e = stage.get(&keys_dev, (size_t)total * sizeof(u64));
-            if (e != hipSuccess)
-                return fail_in(KNN_EHIP, who, "staging keys", hipGetErrorString(e));
+        },
+        [&](u64 *keys_dev) {
+            int rv = KNN_OK;
             for (int r0 = 0; r0 < n && rv == KNN_OK; r0 += step)
                 rv = routed ? knn_index_self_list_within_routed(idx, 0, r0, std::min(step, n - r0), rad_dev ? rad_dev + r0 : nullptr,
                                                                 max_dist2, off_dev + r0, fill_dev + r0, keys_dev, nullptr, fl)
                             : knn_index_self_list_within(idx, 0, r0, std::min(step, n - r0), max_dist2, off_dev + r0, fill_dev + r0,
                                                          keys_dev, nullptr, fl);
-            if (rv == KNN_OK)
-                rv = knn_keys_sort_segments(idx->device, n, off_dev, fill_dev, keys_dev, nullptr);
-            if (rv != KNN_OK)
-                return rv;
-            e = hipMemcpy(keys.data(), keys_dev, (size_t)total * sizeof(u64), hipMemcpyDeviceToHost);
-            if (e != hipSuccess)
-                return fail_in(KNN_EHIP, who, "D2H keys", hipGetErrorString(e));
-        }
-    }
-    // (not declared waited: the slot's buffers go back after the device-wide wait `stage` then makes itself, as the other host calls)
-    return lists_to_host(who, offs, keys, offsets_host, indices_out, dist2_out);
+            return rv;
+        });
 }
 
 extern "C" int knn_index_self_list_within_host(knn_index *idx, float max_dist2, long long *offsets_host, int **indices_out,
@@ -3271,17 +3216,18 @@ extern "C" int knn_index_list_within_masked_host(knn_index *idx, int m, const fl
 {
     if (!idx || m < 1 || !queries_host || !mask_host || !offsets_host || !indices_out || !(max_dist2 >= 0.0f))
         return fail(KNN_EINVAL, "knn_index_list_within_masked_host: bad arguments (m >= 1, max_dist2 >= 0 and not NaN)");
+    const char *const who = "knn_index_list_within_masked_host";
     *indices_out = nullptr;
     if (dist2_out)
         *dist2_out = nullptr;
     std::lock_guard<std::recursive_mutex> lock(idx->mu);
     DeviceGuard guard(idx->device);
     if (!guard.ok)
-        return fail(KNN_EHIP, "knn_index_list_within_masked_host: hipSetDevice failed");
+        return fail_in(KNN_EHIP, who, "hipSetDevice failed");
     Staging stage(idx->device);
     float *q_dev = nullptr;
     unsigned *c_dev = nullptr, *fill_dev = nullptr, *mask_dev = nullptr;
-    u64 *off_dev = nullptr, *keys_dev = nullptr;
+    u64 *off_dev = nullptr;
     const size_t qbytes = (size_t)m * (size_t)idx->k * sizeof(float), cbytes = (size_t)m * sizeof(unsigned);
     const size_t obytes = ((size_t)m + 1) * sizeof(u64);
     const size_t mbytes = std::max<size_t>((size_t)((idx->n + 31) / 32), 1) * sizeof(unsigned);   // (an empty shard: one word, unread)
@@ -3299,86 +3245,23 @@ extern "C" int knn_index_list_within_masked_host(knn_index *idx, int m, const fl
     if (e == hipSuccess && idx->n > 0)
         e = hipMemcpy(mask_dev, mask_host, mbytes, hipMemcpyHostToDevice);
     if (e != hipSuccess)
-        return fail(KNN_EHIP, "knn_index_list_within_masked_host: staging queries and mask", hipGetErrorString(e));
-    // masked count -> offsets, then the one synchronisation: the total sizes the keys
-    int rc = knn_index_count_within_masked(idx, 0, m, q_dev, max_dist2, mask_dev, c_dev, nullptr, KNN_QUERY_INIT_KEYS);
-    if (rc == KNN_OK)
-        rc = knn_counts_to_offsets(idx->device, c_dev, m, off_dev, nullptr);
-    if (rc != KNN_OK)
-        return rc;
-    std::vector<u64> offs((size_t)m + 1);
-    e = hipMemcpy(offs.data(), off_dev, obytes, hipMemcpyDeviceToHost);
-    if (e != hipSuccess)
-        return fail(KNN_EHIP, "knn_index_list_within_masked_host: D2H offsets", hipGetErrorString(e));
-    const u64 total = offs[(size_t)m];
-    std::vector<u64> keys((size_t)total);
-    if (total) {   // masked list -> sort
-        e = stage.get(&keys_dev, (size_t)total * sizeof(u64));
-        if (e != hipSuccess)
-            return fail(KNN_EHIP, "knn_index_list_within_masked_host: staging keys", hipGetErrorString(e));
-        rc = knn_index_list_within_masked(idx, 0, m, q_dev, max_dist2, mask_dev, off_dev, fill_dev, keys_dev, nullptr, KNN_QUERY_INIT_KEYS);
-        if (rc == KNN_OK)
-            rc = knn_keys_sort_segments(idx->device, m, off_dev, fill_dev, keys_dev, nullptr);
-        if (rc != KNN_OK)
-            return rc;
-        e = hipMemcpy(keys.data(), keys_dev, (size_t)total * sizeof(u64), hipMemcpyDeviceToHost);
-        if (e != hipSuccess)
-            return fail(KNN_EHIP, "knn_index_list_within_masked_host: D2H keys", hipGetErrorString(e));
-    }
-    // (not declared waited: the slot's buffers go back after the device-wide wait `stage` then makes itself, as the other host calls)
-    return lists_to_host("knn_index_list_within_masked_host", offs, keys, offsets_host, indices_out, dist2_out);
+        return fail_in(KNN_EHIP, who, "staging queries and mask", hipGetErrorString(e));
+    return lists_host_round(
+        idx, who, stage, m, c_dev, fill_dev, off_dev, offsets_host, indices_out, dist2_out,
+        [&] { return knn_index_count_within_masked(idx, 0, m, q_dev, max_dist2, mask_dev, c_dev, nullptr, KNN_QUERY_INIT_KEYS); },
+        [&](u64 *keys_dev) {
+            return knn_index_list_within_masked(idx, 0, m, q_dev, max_dist2, mask_dev, off_dev, fill_dev, keys_dev, nullptr, KNN_QUERY_INIT_KEYS);
+        });
 }
 
 extern "C" int knn_index_query_topk_large_masked_host(knn_index *idx, int m, int K, const float *queries_host, float max_dist2,
                                                       const unsigned *mask_host, int *indices_host, float *dist2_host, int *counts_host)
 {
-    if (!(max_dist2 >= 0.0f))
-        return fail(KNN_EINVAL, "knn_index_query_topk_large_masked_host: max_dist2 must be >= 0 and not NaN");
-    if (m < 1)
-        return fail(KNN_EINVAL, "knn_index_query_topk_large_masked_host: m < 1");
-    if (K < 1 || K > KNN_TOPK_LARGE_MAX)
-        return fail(KNN_EINVAL, "knn_index_query_topk_large_masked_host: K outside 1 .. 4096");
-    if ((long long)m * K > INT_MAX)
-        return fail(KNN_EINVAL, "knn_index_query_topk_large_masked_host: m * K above INT_MAX");
-    if (!queries_host || !mask_host || !indices_host)
-        return fail(KNN_EINVAL, "knn_index_query_topk_large_masked_host: null queries, mask or indices");
-    if (!idx)
-        return fail(KNN_EINVAL, "knn_index_query_topk_large_masked_host: null index");
-    std::lock_guard<std::recursive_mutex> lock(idx->mu);
-    DeviceGuard guard(idx->device);
-    if (!guard.ok)
-        return fail(KNN_EHIP, "knn_index_query_topk_large_masked_host: hipSetDevice failed");
-    const size_t mk = (size_t)m * (size_t)K;
-    std::vector<u64> keys(mk);
-    {
-        Staging stage(idx->device);
-        float *q_dev = nullptr;
-        u64 *keys_dev = nullptr;
-        unsigned *mask_dev = nullptr;
-        const size_t qbytes = (size_t)m * (size_t)idx->k * sizeof(float);
-        const size_t mbytes = std::max<size_t>((size_t)((idx->n + 31) / 32), 1) * sizeof(unsigned);   // (an empty shard: one word, unread)
-        hipError_t e = stage.get(&q_dev, qbytes);
-        if (e == hipSuccess)
-            e = stage.get(&keys_dev, mk * sizeof(u64));
-        if (e == hipSuccess)
-            e = stage.get(&mask_dev, mbytes);
-        if (e == hipSuccess)
-            e = hipMemcpy(q_dev, queries_host, qbytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess && idx->n > 0)
-            e = hipMemcpy(mask_dev, mask_host, mbytes, hipMemcpyHostToDevice);
-        if (e != hipSuccess)
-            return fail(KNN_EHIP, "knn_index_query_topk_large_masked_host: staging queries and mask", hipGetErrorString(e));
-        const int rc = knn_index_query_topk_large_masked(idx, 0, m, K, q_dev, max_dist2, mask_dev, keys_dev, nullptr, nullptr,
-                                                         KNN_QUERY_INIT_KEYS);
-        if (rc != KNN_OK)
-            return rc;
-        e = hipMemcpy(keys.data(), keys_dev, mk * sizeof(u64), hipMemcpyDeviceToHost);
-        if (e != hipSuccess)
-            return fail(KNN_EHIP, "knn_index_query_topk_large_masked_host: D2H keys", hipGetErrorString(e));
-        // (not declared waited: the buffers go back after the device-wide wait `stage` then makes itself, as the top-K's)
-    }
-    unpack_topk(keys.data(), m, K, indices_host, dist2_host, counts_host);
-    return KNN_OK;
+    const TopkEntry t = {"knn_index_query_topk_large_masked_host", kLarge | kMasked, 0, m, K, queries_host, 0, max_dist2, mask_host};
+    KNN_TRY(topk_check(t, {{!queries_host || !mask_host || !indices_host, "null queries, mask or indices"}}, idx));
+    return topk_host_run(idx, t, indices_host, dist2_host, counts_host, [&](const float *q_dev, const unsigned *mask_dev, u64 *keys_dev) {
+        return knn_index_query_topk_large_masked(idx, 0, m, K, q_dev, max_dist2, mask_dev, keys_dev, nullptr, nullptr, KNN_QUERY_INIT_KEYS);
+    });
 }
 
 namespace {

@@ -13,6 +13,10 @@ Each (index, m, K): a plain call and a call with a finite radius (the median 1-N
 its keys and once folding into them.  The cells index then answers one 1-NN call (two batches) and one count call with
 KNN_QUERY_COUNT_CELLS at that radius (two passes) of the same m = 1100 queries: with its top-K passes, all three drivers of the
 cell-pruned scan.  Each call's way (knn_index_last_stats()[0]) is printed as one JSON line.
+  one-way  k 3, n 2000 (no layout): knn_index_query_topk_large and _large_masked (m, K) = (20, 100), _masked (20, 5) and
+           knn_index_self_topk on its exact branch (rows 7 .. 26, K 5), each once writing its keys and once folding into them; then
+           one call of each of their three host calls and of the list host calls — knn_index_list_within_host, _masked_host,
+           knn_index_self_list_within_host and _routed_host (a radius per row) — at a radius of a few hits per row
 
   topk_launches.py --compare A.csv B.csv
 reads two such kernel traces and prints the sequences of (kernel, grid, block) of the library's kernels and whether they are
@@ -76,6 +80,48 @@ def calls():
             ix.close()
     for o in options:
         pkg.set_option(o, 0)
+    one_way_calls(pkg, np, torch, dev)
+
+
+def one_way_calls(pkg, np, torch, dev):
+    """The one-way top-K entries and the staged host calls (the docstring's last block)."""
+    k, n, m, first, r2 = 3, 2000, 20, 7, 0.007
+    rng = np.random.default_rng(n + k)
+    R = rng.random((n, k), dtype=np.float32)
+    Q = R[first:first + m].copy()
+    ix = pkg.KnnIndex(k, R)
+    try:
+        q = torch.from_numpy(Q.reshape(-1)).to(dev)
+        words = np.full(pkg.mask_words(n), 0xFFFFFFFF, dtype=np.uint32)
+        mask = torch.from_numpy(words.view(np.int32)).to(dev)
+        for entry, K in (("query_topk_large", 100), ("query_topk_masked", 5), ("query_topk_large_masked", 100), ("self_topk", 5)):
+            keys = torch.empty(m * K, dtype=torch.int64, device=dev)
+            for init in (True, False):
+                if entry == "query_topk_large":
+                    ix.query_topk_large(m, K, q.data_ptr(), keys.data_ptr(), init_keys=init)
+                elif entry == "query_topk_masked":
+                    ix.query_topk_masked(m, K, q.data_ptr(), mask.data_ptr(), keys.data_ptr(), init_keys=init)
+                elif entry == "query_topk_large_masked":
+                    ix.query_topk_large_masked(m, K, q.data_ptr(), mask.data_ptr(), keys.data_ptr(), init_keys=init)
+                else:
+                    ix.self_topk(first, m, K, keys.data_ptr(), init_keys=init)
+                torch.cuda.synchronize()
+                print(json.dumps(dict(index="one-way", call=entry, m=m, K=K, init=init, way=ix.last_stats()[0])), flush=True)
+        radii = (np.float32(r2) * (np.float32(0.5) + np.float32(0.5) * rng.random(n, dtype=np.float32))).astype(np.float32)
+        host_calls = (
+            ("query_topk_large_host", lambda: ix.query_topk_large_host(Q, 100, max_dist2=r2)),
+            ("query_topk_masked_host", lambda: ix.query_topk_masked_host(Q, 5, words, max_dist2=r2)),
+            ("query_topk_large_masked_host", lambda: ix.query_topk_large_masked_host(Q, 100, words, max_dist2=r2)),
+            ("list_within_host", lambda: ix.list_within_host(Q, r2)),
+            ("list_within_masked_host", lambda: ix.list_within_masked_host(Q, r2, words)),
+            ("self_list_within_host", lambda: ix.self_list_within_host(r2)),
+            ("self_list_within_routed_host", lambda: ix.self_list_within_routed_host(r2, max_dist2=radii)),
+        )
+        for name, call in host_calls:
+            call()
+            print(json.dumps(dict(index="one-way", call=name, way=ix.last_stats()[0])), flush=True)
+    finally:
+        ix.close()
 
 
 def sequence(path):
