@@ -580,6 +580,11 @@ int knn_index_self_list_within_host(knn_index *idx, float max_dist2, long long *
  * and after it: three disjoint ranges, ascending, whose union is [i0, i1). */
 int knn_debug_self_plan(const long long in[6], long long out[8]);
 int knn_debug_self_ranges(long long i0, long long i1, long long w0, long long w1, long long out[6]);
+/* knn_debug_slice_chunks: the chunks every exact slice scan (2b-2m: top-K, count, list, select, masked, self, cluster sweep) walks
+ * its queries in, and each chunk's cut of the shard's rows.  in = {queries, the shard's rows, CUs, K, rule}; rule 0: the count
+ * scan's slices (K ignored), 1: the top-K scan's for 1 <= K <= 64, 2: a select pass's (K ignored).  out[i] = {first query, queries
+ * (<= 65536), slices, rows of a slice, grid.x, grid.y} for chunk i < *chunks; cap: the rows of out, EINVAL when too few. */
+int knn_debug_slice_chunks(const long long in[5], int cap, long long (*out)[6], int *chunks);
 
 /* ------------------------------------------------------------------------
  * 2j. A radius per query: the counts and lists of 2d, 2e and 2i with ONE RADIUS FOR EVERY QUERY, read from a device array — ball

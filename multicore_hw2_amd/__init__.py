@@ -23,7 +23,7 @@ __all__ = ["lib", "lib_path", "cudaCallback", "KnnIndex", "KnnGeom", "KnnError",
            "list_within_masked_c", "query_topk_large_masked_c", "list_within_masked_host_c", "query_topk_large_masked_host_c",
            "debug_masked_lists_plan",
            "self_topk_c", "self_count_within_c", "self_list_within_c", "self_topk_host_c", "self_list_within_host_c",
-           "debug_self_plan", "debug_self_ranges",
+           "debug_self_plan", "debug_self_ranges", "debug_slice_chunks", "SLICE_CHUNK",
            "count_within_each_c", "list_within_each_c", "self_count_within_each_c", "self_list_within_each_c",
            "count_within_each_host_c", "list_within_each_host_c", "keys_column_dist2_c", "keys_column_dist2", "debug_each_radius",
            "self_count_within_routed_c", "self_list_within_routed_c", "self_list_within_routed_host_c", "debug_self_routed_plan",
@@ -55,7 +55,7 @@ EXPORTED_SYMBOLS = [
     "knn_index_list_within_masked", "knn_index_list_within_masked_host", "knn_index_query_topk_large_masked",
     "knn_index_query_topk_large_masked_host", "knn_debug_masked_lists_plan",
     "knn_index_self_topk", "knn_index_self_count_within", "knn_index_self_list_within", "knn_index_self_topk_host",
-    "knn_index_self_list_within_host", "knn_debug_self_plan", "knn_debug_self_ranges",
+    "knn_index_self_list_within_host", "knn_debug_self_plan", "knn_debug_self_ranges", "knn_debug_slice_chunks",
     "knn_index_count_within_each", "knn_index_list_within_each", "knn_index_self_count_within_each",
     "knn_index_self_list_within_each", "knn_keys_column_dist2", "knn_index_count_within_each_host",
     "knn_index_list_within_each_host", "knn_debug_each_radius",
@@ -718,6 +718,24 @@ def debug_self_ranges(i0, i1, w0, w1):
     f.argtypes = [ctypes.c_longlong] * 4 + [ctypes.POINTER(ctypes.c_longlong)]
     _check(f(int(i0), int(i1), int(w0), int(w1), out))
     return dict(zip(SELF_RANGES, list(out)))
+
+
+SLICE_CHUNK = ("c0", "mc", "slices", "per", "grid_x", "grid_y")
+SLICE_RULES = {"count": 0, "topk": 1, "select": 2}
+
+
+def debug_slice_chunks(m, n, num_cu, K=0, rule="count"):
+    """knn_debug_slice_chunks: the chunks of <= 65536 queries the exact slice scans walk m queries in, and each chunk's cut of n rows
+    under a slice rule ("count", "topk" with K, "select"): a list of dicts with the names in SLICE_CHUNK.  Host arithmetic; works
+    without a GPU."""
+    cap = (int(m) + 65535) // 65536 if m > 0 else 1
+    out = ((ctypes.c_longlong * 6) * cap)()
+    chunks = ctypes.c_int(0)
+    vin = (ctypes.c_longlong * 5)(int(m), int(n), int(num_cu), int(K), SLICE_RULES[rule])
+    f = lib().knn_debug_slice_chunks
+    f.argtypes = [ctypes.POINTER(ctypes.c_longlong), ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
+    _check(f(vin, cap, ctypes.cast(out, ctypes.c_void_p), ctypes.byref(chunks)))
+    return [dict(zip(SLICE_CHUNK, list(out[i]))) for i in range(chunks.value)]
 
 
 def count_within_each_c():

@@ -9,6 +9,7 @@
 #include "../../include/knn_mi355x.h"
 #include "knn_common.h"
 #include "knn_radix_pick.h"
+#include "knn_slice_launch.h"
 #include "knn_mask_split.h"
 #include "knn_self_window.h"
 #include "knn_each_radius.h"
@@ -923,7 +924,7 @@ QueryRoute knn_query_route(const QueryRouteInputs &in)
 CountPlan knn_count_route(const CountRouteInputs &in)
 {
     CountPlan p;
-    p.slices = knn_count_slices(std::min(in.m, KNN_TOPK_CHUNK), in.n, in.num_cu);
+    p.slices = knn_slice_plan(in.m, in.n, in.num_cu, KnnCountSlices{}).slices;
     const int path = in.path;
     if (in.has_grid && in.flag_grid && (path == 0 || path == 3)) {
         // rmax: the radius-bounded top-K's rule at K = 1, the 2^15-cell budget included (chosen, not measured)
@@ -2239,6 +2240,29 @@ int knn_debug_self_ranges(long long i0, long long i1, long long w0, long long w1
     if (!out)
         return fail(KNN_EINVAL, "knn_debug_self_ranges: null out");
     knn_self_ranges(i0, i1, w0, w1, out);
+    return KNN_OK;
+}
+
+int knn_debug_slice_chunks(const long long in[5], int cap, long long (*out)[6], int *chunks)
+{
+    if (!in || !out || !chunks || cap < 1 || in[0] < 1 || in[0] > INT_MAX || in[1] < 1 || in[1] > (1ll << 32) || in[2] < 1 ||
+        in[2] > INT_MAX || in[4] < 0 || in[4] > 2 || (in[4] == 1 && (in[3] < 1 || in[3] > KNN_TOPK_MAX)) ||
+        knn_divup(in[0], KNN_TOPK_CHUNK) > cap)
+        return fail(KNN_EINVAL, "knn_debug_slice_chunks: bad arguments (1 <= queries <= INT_MAX, 1 <= rows <= 2^32, CUs >= 1, rule 0, "
+                                "1 with 1 <= K <= 64, or 2, cap >= the chunks)");
+    int count = 0;
+    const auto put = [&](const SliceChunk &ch) {
+        const long long v[6] = {ch.c0, ch.mc, ch.slices, ch.per, ch.grid.x, ch.grid.y};
+        memcpy(out[count++], v, sizeof v);
+        return hipSuccess;
+    };
+    if (in[4] == 1)
+        (void)knn_slice_chunks(in[0], in[1], (int)in[2], KnnTopkSlices{(int)in[3]}, put);
+    else if (in[4] == 2)
+        (void)knn_slice_chunks(in[0], in[1], (int)in[2], KnnSelectSlices{}, put);
+    else
+        (void)knn_slice_chunks(in[0], in[1], (int)in[2], KnnCountSlices{}, put);
+    *chunks = count;
     return KNN_OK;
 }
 

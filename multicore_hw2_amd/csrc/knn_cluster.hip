@@ -31,6 +31,7 @@
 // row's slot (-1) is read by its own thread alone, before it writes it.
 #include "knn_self_scan.h"
 #include "knn_cluster_uf.h"
+#include "knn_slice_launch.h"
 
 #define KNN_CLUSTER_BLOCK 256
 
@@ -142,9 +143,9 @@ ClusterPlan knn_cluster_plan(long long n, int num_cu, bool own_mask)
     ClusterPlan p;
     if (n <= 0)
         return p;
-    const int chunk_m = n < KNN_TOPK_CHUNK ? (int)n : KNN_TOPK_CHUNK;
-    p.chunks = knn_divup(n, KNN_TOPK_CHUNK);
-    p.slices = knn_count_slices(chunk_m, n, num_cu);
+    const SlicePlan sp = knn_slice_plan(n, n, num_cu, KnnCountSlices{});   // (the sweep's "queries" are the shard's rows)
+    p.chunks = sp.chunks;
+    p.slices = sp.slices;
     // exact: the counts' memset is no kernel; per chunk the self count and the link sweep; core and flatten
     p.launches_exact = 2ll * p.chunks + 2;
     // grid: grid count, its commit, the gated self count per chunk; core; grid link, the gated link sweep per chunk; flatten
@@ -174,11 +175,10 @@ hipError_t knn_cluster_link_launch(const ClusterCall &c, const unsigned *gate)
     if (!cluster_call_ok(c))
         return hipErrorInvalidValue;
     hipStream_t s = c.stream;
-    for (long long c0 = 0; c0 < c.n; c0 += KNN_TOPK_CHUNK) {
-        const int mc = c.n - c0 < KNN_TOPK_CHUNK ? (int)(c.n - c0) : KNN_TOPK_CHUNK;
-        const long long slices = knn_count_slices(mc, c.n, c.num_cu);
-        const long long per = (c.n + slices - 1) / slices;
-        const dim3 grid((unsigned)slices, (unsigned)knn_divup(mc, KNN_WAVE)), block(KNN_WAVE);
+    return knn_slice_chunks(c.n, c.n, c.num_cu, KnnCountSlices{}, [&](const SliceChunk &ch) {
+        const int mc = ch.mc;
+        const long long c0 = ch.c0, per = ch.per;
+        const dim3 grid = ch.grid, block(KNN_WAVE);
 #define KNN_CLUSTER_LINK(KCV)                                                                                                        \
     if (gate)                                                                                                                        \
         hipLaunchKernelGGL(knn_cluster_link_gated_kernel<KCV>, grid, block, 0, s, c.r, c.k, c0, mc, c.n, per, c.max_dist2, c.parent, \
@@ -186,23 +186,10 @@ hipError_t knn_cluster_link_launch(const ClusterCall &c, const unsigned *gate)
     else                                                                                                                             \
         hipLaunchKernelGGL(knn_cluster_link_kernel<KCV>, grid, block, 0, s, c.r, c.k, c0, mc, c.n, per, c.max_dist2, c.parent,       \
                            (const unsigned *)c.core, c.best)
-        switch ((c.k + 15) / 16) {
-        case 1: KNN_CLUSTER_LINK(1); break;
-        case 2: KNN_CLUSTER_LINK(2); break;
-        case 3: KNN_CLUSTER_LINK(3); break;
-        case 4: KNN_CLUSTER_LINK(4); break;
-        case 5: KNN_CLUSTER_LINK(5); break;
-        case 6: KNN_CLUSTER_LINK(6); break;
-        case 7: KNN_CLUSTER_LINK(7); break;
-        case 8: KNN_CLUSTER_LINK(8); break;
-        default: KNN_CLUSTER_LINK(0); break;
-        }
+        KNN_KC_SWITCH(c.k, KNN_CLUSTER_LINK)
 #undef KNN_CLUSTER_LINK
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess)
-            return e;
-    }
-    return hipSuccess;
+        return hipGetLastError();
+    });
 }
 
 hipError_t knn_cluster_flatten_launch(const ClusterCall &c)

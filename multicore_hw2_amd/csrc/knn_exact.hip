@@ -21,7 +21,7 @@
 // This is not a translation of the reference's one-block-per-query kernels (core.cu:808-855):
 // no SoA transpose pass, no per-block result array, no host second-level reduce.
 #include "knn_exact_dev.h"
-#include "knn_masked_dev.h"   // masked_dist2: v0's distance of one row, the each-forms' row lines
+#include "knn_slice_launch.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -906,7 +906,7 @@ __global__ __launch_bounds__(KNN_WAVE) void knn_exact_topk_kernel(const float *_
     const float *__restrict__ r = R + (size_t)i0 * k;
     const float *__restrict__ qp = Q + (size_t)qa * k;
     for (long long i = i0; i < i1; ++i, r += k) {
-        float acc = 0.0f;
+        float acc = 0.0f;   // (lane_row_dist2's arithmetic, knn_exact_dev.h, in this kernel's own text: a call schedules the prologue differently)
         if (KC > 0) {
 #pragma unroll
             for (int c = 0; c < (KC > 0 ? KC : 1); ++c) {
@@ -1035,7 +1035,9 @@ constexpr size_t kTopkPartBytes = (size_t)128 << 20;   // most bytes of the scan
 // kTopkPartBytes (at least one), and ~32 waves per CU for K <= 16 (the scalar row loads need the occupancy: K 8 at C3's shape
 // 68 -> 22 ms) but ~8 for larger K (every slice fills its K-list from scratch and the fold reads every slice's list: K 64
 // 241 ms at 8, 334 at 32).
-long long topk_slices(int mc, int K, long long n, int num_cu)
+}  // namespace
+
+long long knn_topk_slices(int mc, int K, long long n, int num_cu)
 {
     const unsigned qg = (unsigned)knn_divup(mc, KNN_WAVE);
     long long slices = (long long)num_cu * (K <= 16 ? 32 : 8) / qg;
@@ -1052,9 +1054,6 @@ long long topk_slices(int mc, int K, long long n, int num_cu)
     const long long per = (n + slices - 1) / slices;
     return (n + per - 1) / per;
 }
-}  // namespace
-
-long long knn_topk_slices(int mc, int K, long long n, int num_cu) { return topk_slices(mc, K, n, num_cu); }
 
 hipError_t knn_topk_select_launch(const u64 *lists, int nl, int m, int K, u64 *keys, int init, hipStream_t s)
 {
@@ -1069,8 +1068,8 @@ size_t knn_topk_part_bytes(int m, int K, long long n, int num_cu)
 {
     if (n <= 0 || m <= 0)
         return 0;
-    const int mc = m < KNN_TOPK_CHUNK ? m : KNN_TOPK_CHUNK;
-    return (size_t)topk_slices(mc, K, n, num_cu) * (size_t)mc * (size_t)K * sizeof(u64);
+    const SliceChunk first = knn_slice_chunk(0, m, n, num_cu, KnnTopkSlices{K});
+    return KnnTopkSlices{K}.part_bytes(first.slices, first.mc);
 }
 
 hipError_t knn_exact_topk_launch(const TopkCall &c, const unsigned *gate, bool limit)
@@ -1086,16 +1085,14 @@ hipError_t knn_exact_topk_launch(const TopkCall &c, const unsigned *gate, bool l
             return knn_keys_fill_launch(c.keys, (int)((long long)c.m * K), s);
         return hipSuccess;
     }
-    for (int c0 = 0; c0 < c.m; c0 += KNN_TOPK_CHUNK) {
-        const int mc = c.m - c0 < KNN_TOPK_CHUNK ? c.m - c0 : KNN_TOPK_CHUNK;
-        const unsigned qg = (unsigned)knn_divup(mc, KNN_WAVE);
-        const long long slices = topk_slices(mc, K, c.n, c.num_cu);
-        if ((size_t)slices * (size_t)mc * (size_t)K * sizeof(u64) > c.part_bytes)
+    return knn_slice_chunks(c.m, c.n, c.num_cu, KnnTopkSlices{K}, [&](const SliceChunk &ch) {
+        const int mc = ch.mc;
+        const long long per = ch.per;
+        if (KnnTopkSlices{K}.part_bytes(ch.slices, mc) > c.part_bytes)
             return hipErrorInvalidValue;
-        const long long per = (c.n + slices - 1) / slices;
-        const dim3 grid((unsigned)slices, qg), block(KNN_WAVE);
-        const size_t lds = (size_t)K * KNN_WAVE * sizeof(u64);
-        const float *qc = c.q + (size_t)c0 * c.k;
+        const dim3 grid = ch.grid, block(KNN_WAVE);
+        const size_t lds = KnnTopkSlices{K}.lds_bytes();
+        const float *qc = c.q + (size_t)ch.c0 * c.k;
 #define KNN_TOPK_SCAN(KCV)                                                                                                       \
     if (within)                                                                                                                  \
         hipLaunchKernelGGL((knn_exact_topk_kernel<KCV, true>), grid, block, lds, s, qc, c.r, c.k, mc, c.n, K, per, c.base, c.gids,  \
@@ -1103,28 +1100,15 @@ hipError_t knn_exact_topk_launch(const TopkCall &c, const unsigned *gate, bool l
     else                                                                                                                         \
         hipLaunchKernelGGL((knn_exact_topk_kernel<KCV>), grid, block, lds, s, qc, c.r, c.k, mc, c.n, K, per, c.base, c.gids, c.part, \
                            gate, lim)
-        switch ((c.k + 15) / 16) {
-        case 1: KNN_TOPK_SCAN(1); break;
-        case 2: KNN_TOPK_SCAN(2); break;
-        case 3: KNN_TOPK_SCAN(3); break;
-        case 4: KNN_TOPK_SCAN(4); break;
-        case 5: KNN_TOPK_SCAN(5); break;
-        case 6: KNN_TOPK_SCAN(6); break;
-        case 7: KNN_TOPK_SCAN(7); break;
-        case 8: KNN_TOPK_SCAN(8); break;
-        default: KNN_TOPK_SCAN(0); break;
-        }
+        KNN_KC_SWITCH(c.k, KNN_TOPK_SCAN)
 #undef KNN_TOPK_SCAN
-        hipError_t e = hipGetLastError();
+        const hipError_t e = hipGetLastError();
         if (e != hipSuccess)
             return e;
-        hipLaunchKernelGGL(knn_topk_select_kernel, dim3((unsigned)mc), dim3(KNN_WAVE), 0, s, (const u64 *)c.part, (int)slices, mc,
-                           K, c.keys + (size_t)c0 * K, c.init, gate);
-        e = hipGetLastError();
-        if (e != hipSuccess)
-            return e;
-    }
-    return hipSuccess;
+        hipLaunchKernelGGL(knn_topk_select_kernel, dim3((unsigned)mc), dim3(KNN_WAVE), 0, s, (const u64 *)c.part, (int)ch.slices, mc,
+                           K, c.keys + (size_t)ch.c0 * K, c.init, gate);
+        return hipGetLastError();
+    });
 }
 
 hipError_t knn_topk_merge_launch(int m, int K, const u64 *a, u64 *b, hipStream_t s)
@@ -1424,7 +1408,7 @@ __global__ __launch_bounds__(KNN_WAVE) void knn_exact_count_kernel(const float *
     const float *__restrict__ r = R + (size_t)i0 * k;
     const float *__restrict__ qp = Q + (size_t)qa * k;
     for (long long i = i0; i < i1; ++i, r += k) {
-        float acc = 0.0f;
+        float acc = 0.0f;   // (lane_row_dist2's arithmetic, knn_exact_dev.h, in this kernel's own text)
         if (KC > 0) {
 #pragma unroll
             for (int c = 0; c < (KC > 0 ? KC : 1); ++c) {
@@ -1519,44 +1503,7 @@ long long knn_count_slices(int mc, long long n, int num_cu)
     return (n + per - 1) / per;
 }
 
-// (a call with a radius per query — c.radii — takes the each-forms: the scans at the end of this file, the cell-pruned way's
-// re-rank in knn_each.hip)
-static hipError_t exact_count_each_launch(const CountCall &c, const unsigned *gate);
-static hipError_t exact_list_each_launch(const ListCall &c, const unsigned *gate);
-
-hipError_t knn_exact_count_launch(const CountCall &c, const unsigned *gate)
-{
-    if (c.m <= 0 || c.n <= 0)
-        return hipSuccess;
-    if (c.radii)
-        return exact_count_each_launch(c, gate);
-    hipStream_t s = c.stream;
-    for (int c0 = 0; c0 < c.m; c0 += KNN_TOPK_CHUNK) {
-        const int mc = c.m - c0 < KNN_TOPK_CHUNK ? c.m - c0 : KNN_TOPK_CHUNK;
-        const long long slices = knn_count_slices(mc, c.n, c.num_cu);
-        const long long per = (c.n + slices - 1) / slices;
-        const dim3 grid((unsigned)slices, (unsigned)knn_divup(mc, KNN_WAVE)), block(KNN_WAVE);
-        const float *qc = c.q + (size_t)c0 * c.k;
-#define KNN_COUNT_SCAN(KCV) \
-    hipLaunchKernelGGL(knn_exact_count_kernel<KCV>, grid, block, 0, s, qc, c.r, c.k, mc, c.n, per, c.max_dist2, c.counts + c0, gate)
-        switch ((c.k + 15) / 16) {
-        case 1: KNN_COUNT_SCAN(1); break;
-        case 2: KNN_COUNT_SCAN(2); break;
-        case 3: KNN_COUNT_SCAN(3); break;
-        case 4: KNN_COUNT_SCAN(4); break;
-        case 5: KNN_COUNT_SCAN(5); break;
-        case 6: KNN_COUNT_SCAN(6); break;
-        case 7: KNN_COUNT_SCAN(7); break;
-        case 8: KNN_COUNT_SCAN(8); break;
-        default: KNN_COUNT_SCAN(0); break;
-        }
-#undef KNN_COUNT_SCAN
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess)
-            return e;
-    }
-    return hipSuccess;
-}
+// (knn_exact_count_launch and knn_exact_list_launch: at the end of this file, behind the each-forms of their kernels)
 
 hipError_t knn_count_commit_launch(int m, const unsigned *scratch, unsigned *counts, const unsigned *giveup, hipStream_t s)
 {
@@ -1628,7 +1575,7 @@ __global__ __launch_bounds__(KNN_WAVE) void knn_exact_list_kernel(const float *_
     const float *__restrict__ r = R + (size_t)i0 * k;
     const float *__restrict__ qp = Q + (size_t)qa * k;
     for (long long i = i0; i < i1; ++i, r += k) {
-        float acc = 0.0f;
+        float acc = 0.0f;   // (lane_row_dist2's arithmetic, knn_exact_dev.h, in this kernel's own text)
         if (KC > 0) {
 #pragma unroll
             for (int c = 0; c < (KC > 0 ? KC : 1); ++c) {
@@ -1743,41 +1690,6 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_keys_sort_segments_kernel(const
     }
 }
 
-hipError_t knn_exact_list_launch(const ListCall &c, const unsigned *gate)
-{
-    if (c.m <= 0 || c.n <= 0)
-        return hipSuccess;
-    if (c.radii)
-        return exact_list_each_launch(c, gate);
-    hipStream_t s = c.stream;
-    for (int c0 = 0; c0 < c.m; c0 += KNN_TOPK_CHUNK) {
-        const int mc = c.m - c0 < KNN_TOPK_CHUNK ? c.m - c0 : KNN_TOPK_CHUNK;
-        const long long slices = knn_count_slices(mc, c.n, c.num_cu);
-        const long long per = (c.n + slices - 1) / slices;
-        const dim3 grid((unsigned)slices, (unsigned)knn_divup(mc, KNN_WAVE)), block(KNN_WAVE);
-        const float *qc = c.q + (size_t)c0 * c.k;
-#define KNN_LIST_SCAN(KCV)                                                                                                        \
-    hipLaunchKernelGGL(knn_exact_list_kernel<KCV>, grid, block, 0, s, qc, c.r, c.k, mc, c.n, per, c.max_dist2, c.base, c.gids, \
-                       c.offsets + c0, c.fill + c0, c.keys, gate)
-        switch ((c.k + 15) / 16) {
-        case 1: KNN_LIST_SCAN(1); break;
-        case 2: KNN_LIST_SCAN(2); break;
-        case 3: KNN_LIST_SCAN(3); break;
-        case 4: KNN_LIST_SCAN(4); break;
-        case 5: KNN_LIST_SCAN(5); break;
-        case 6: KNN_LIST_SCAN(6); break;
-        case 7: KNN_LIST_SCAN(7); break;
-        case 8: KNN_LIST_SCAN(8); break;
-        default: KNN_LIST_SCAN(0); break;
-        }
-#undef KNN_LIST_SCAN
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess)
-            return e;
-    }
-    return hipSuccess;
-}
-
 hipError_t knn_list_commit_launch(int m, const unsigned *cursor, unsigned *fill, const unsigned *giveup, hipStream_t s)
 {
     if (m <= 0)
@@ -1830,10 +1742,10 @@ hipError_t knn_keys_sort_segments_launch(int m, const u64 *offsets, const unsign
 // A radius per query (include/knn_mi355x.h 2j; DESIGN §4.6 "A radius per query"): the each-forms of the count and list kernels.
 // A row is a hit for query j when its v0 distance E is finite, E <= radii[j] and E <= cap — two fp32 compares, equality inside; a
 // NaN or negative radius fails the first for every row.  The kernels are their scalar twins with the radius read per query;
-// the launchers hand a call that carries radii (CountCall::radii, ListCall::radii; max_dist2 is then the cap) to the ones below.
+// the launchers behind them launch these for a call that carries radii (CountCall::radii, ListCall::radii; max_dist2 is then the cap).
 // ------------------------------------------------------------------------------------------
-// knn_exact_count_each_kernel<KC> — knn_exact_count_kernel<KC>'s skeleton (masked_dist2 holds its row lines): the lanes ARE the
-// queries, so the lane loads its own radius once and the compare reads a VGPR where the twin reads an SGPR.  gate as there.
+// knn_exact_count_each_kernel<KC> — knn_exact_count_kernel<KC>'s skeleton (lane_row_dist2, knn_exact_dev.h, holds its row lines):
+// the lanes ARE the queries, so the lane loads its own radius once and the compare reads a VGPR where the twin reads an SGPR.  gate as there.
 template <int KC>
 __global__ __launch_bounds__(KNN_WAVE) void knn_exact_count_each_kernel(const float *__restrict__ Q, const float *__restrict__ R, int k,
                                                                        int m, long long n, long long rows_per_slice,
@@ -1858,7 +1770,7 @@ __global__ __launch_bounds__(KNN_WAVE) void knn_exact_count_each_kernel(const fl
     const long long i1 = min(n, i0 + rows_per_slice);
     const float *__restrict__ r = R + (size_t)i0 * k;
     for (long long i = i0; i < i1; ++i, r += k) {
-        const float acc = masked_dist2<KC>(qv, qp, r, k);
+        const float acc = lane_row_dist2<KC>(qv, qp, r, k);
         cnt += acc < INFINITY && acc <= rad && acc <= cap ? 1u : 0u;   // (NaN — the distance or the radius — fails)
     }
     if (q < m && cnt != 0u)
@@ -1893,66 +1805,55 @@ __global__ __launch_bounds__(KNN_WAVE) void knn_exact_list_each_kernel(const flo
     const long long i1 = min(n, i0 + rows_per_slice);
     const float *__restrict__ r = R + (size_t)i0 * k;
     for (long long i = i0; i < i1; ++i, r += k) {
-        const float acc = masked_dist2<KC>(qv, qp, r, k);
+        const float acc = lane_row_dist2<KC>(qv, qp, r, k);
         if (q < m && acc < INFINITY && acc <= rad && acc <= cap)   // (NaN — the distance or the radius — fails)
             list_put(&fill[q], keys, off, room, pack_key(acc, gids ? gids[i] : (unsigned)(base + i)));
     }
 }
 
-#define KNN_EACH_SWITCH(k, LAUNCH) \
-    switch (((k) + 15) / 16) {     \
-    case 1: LAUNCH(1); break;      \
-    case 2: LAUNCH(2); break;      \
-    case 3: LAUNCH(3); break;      \
-    case 4: LAUNCH(4); break;      \
-    case 5: LAUNCH(5); break;      \
-    case 6: LAUNCH(6); break;      \
-    case 7: LAUNCH(7); break;      \
-    case 8: LAUNCH(8); break;      \
-    default: LAUNCH(0); break;     \
-    }
-
-// knn_exact_count_launch for a call with radii: its slices and chunks; the radii advance with the queries, chunk by chunk.
-static hipError_t exact_count_each_launch(const CountCall &c, const unsigned *gate)
+// The count scan and the list scan: the queries in chunks, the rows in the count rule's slices.  A call with radii takes the each
+// kernel, its radii advancing with the queries chunk by chunk; gate: both forms carry it.
+hipError_t knn_exact_count_launch(const CountCall &c, const unsigned *gate)
 {
+    if (c.m <= 0 || c.n <= 0)
+        return hipSuccess;
     hipStream_t s = c.stream;
-    for (int c0 = 0; c0 < c.m; c0 += KNN_TOPK_CHUNK) {
-        const int mc = c.m - c0 < KNN_TOPK_CHUNK ? c.m - c0 : KNN_TOPK_CHUNK;
-        const long long slices = knn_count_slices(mc, c.n, c.num_cu);
-        const long long per = (c.n + slices - 1) / slices;
-        const dim3 grid((unsigned)slices, (unsigned)knn_divup(mc, KNN_WAVE)), block(KNN_WAVE);
+    return knn_slice_chunks(c.m, c.n, c.num_cu, KnnCountSlices{}, [&](const SliceChunk &ch) {
+        const int mc = ch.mc;
+        const long long c0 = ch.c0, per = ch.per;
+        const dim3 grid = ch.grid, block(KNN_WAVE);
         const float *qc = c.q + (size_t)c0 * c.k;
-#define KNN_COUNT_EACH_SCAN(KCV)                                                                                                  \
-    hipLaunchKernelGGL(knn_exact_count_each_kernel<KCV>, grid, block, 0, s, qc, c.r, c.k, mc, c.n, per, c.radii + c0, c.max_dist2, \
-                       c.counts + c0, gate)
-        KNN_EACH_SWITCH(c.k, KNN_COUNT_EACH_SCAN)
-#undef KNN_COUNT_EACH_SCAN
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess)
-            return e;
-    }
-    return hipSuccess;
+#define KNN_COUNT_SCAN(KCV)                                                                                                           \
+    if (c.radii)                                                                                                                      \
+        hipLaunchKernelGGL(knn_exact_count_each_kernel<KCV>, grid, block, 0, s, qc, c.r, c.k, mc, c.n, per, c.radii + c0, c.max_dist2, \
+                           c.counts + c0, gate);                                                                                      \
+    else                                                                                                                              \
+        hipLaunchKernelGGL(knn_exact_count_kernel<KCV>, grid, block, 0, s, qc, c.r, c.k, mc, c.n, per, c.max_dist2, c.counts + c0, gate)
+        KNN_KC_SWITCH(c.k, KNN_COUNT_SCAN)
+#undef KNN_COUNT_SCAN
+        return hipGetLastError();
+    });
 }
 
-// knn_exact_list_launch for a call with radii.
-static hipError_t exact_list_each_launch(const ListCall &c, const unsigned *gate)
+hipError_t knn_exact_list_launch(const ListCall &c, const unsigned *gate)
 {
+    if (c.m <= 0 || c.n <= 0)
+        return hipSuccess;
     hipStream_t s = c.stream;
-    for (int c0 = 0; c0 < c.m; c0 += KNN_TOPK_CHUNK) {
-        const int mc = c.m - c0 < KNN_TOPK_CHUNK ? c.m - c0 : KNN_TOPK_CHUNK;
-        const long long slices = knn_count_slices(mc, c.n, c.num_cu);
-        const long long per = (c.n + slices - 1) / slices;
-        const dim3 grid((unsigned)slices, (unsigned)knn_divup(mc, KNN_WAVE)), block(KNN_WAVE);
+    return knn_slice_chunks(c.m, c.n, c.num_cu, KnnCountSlices{}, [&](const SliceChunk &ch) {
+        const int mc = ch.mc;
+        const long long c0 = ch.c0, per = ch.per;
+        const dim3 grid = ch.grid, block(KNN_WAVE);
         const float *qc = c.q + (size_t)c0 * c.k;
-#define KNN_LIST_EACH_SCAN(KCV)                                                                                                  \
-    hipLaunchKernelGGL(knn_exact_list_each_kernel<KCV>, grid, block, 0, s, qc, c.r, c.k, mc, c.n, per, c.radii + c0, c.max_dist2, \
-                       c.base, c.gids, c.offsets + c0, c.fill + c0, c.keys, gate)
-        KNN_EACH_SWITCH(c.k, KNN_LIST_EACH_SCAN)
-#undef KNN_LIST_EACH_SCAN
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess)
-            return e;
-    }
-    return hipSuccess;
+#define KNN_LIST_SCAN(KCV)                                                                                                           \
+    if (c.radii)                                                                                                                     \
+        hipLaunchKernelGGL(knn_exact_list_each_kernel<KCV>, grid, block, 0, s, qc, c.r, c.k, mc, c.n, per, c.radii + c0, c.max_dist2, \
+                           c.base, c.gids, c.offsets + c0, c.fill + c0, c.keys, gate);                                               \
+    else                                                                                                                             \
+        hipLaunchKernelGGL(knn_exact_list_kernel<KCV>, grid, block, 0, s, qc, c.r, c.k, mc, c.n, per, c.max_dist2, c.base, c.gids,    \
+                           c.offsets + c0, c.fill + c0, c.keys, gate)
+        KNN_KC_SWITCH(c.k, KNN_LIST_SCAN)
+#undef KNN_LIST_SCAN
+        return hipGetLastError();
+    });
 }
-#undef KNN_EACH_SWITCH

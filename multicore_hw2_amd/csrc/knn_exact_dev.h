@@ -34,6 +34,51 @@ __device__ __forceinline__ u64 wave_min_u64(u64 v)
     return v;
 }
 
+// v0's distance of one row at the wave-uniform address r to the lane's query: the row lines of every exact slice scan — one wave
+// per block, lanes = queries, the lane's coordinates in qv (KC > 0: 16 * KC registers, zero beyond k) or read through qp (KC 0) —
+// and so the arithmetic their bit-exactness rests on.  knn_exact_topk_kernel, knn_exact_count_kernel and knn_exact_list_kernel
+// (knn_exact.hip) hold the same lines in their own text; every other scan calls this.
+template <int KC>
+__device__ __forceinline__ float lane_row_dist2(const float (&qv)[KC > 0 ? 16 * KC : 1], const float *__restrict__ qp,
+                                                const float *__restrict__ r, int k)
+{
+#pragma clang fp contract(off)
+    float acc = 0.0f;
+    if (KC > 0) {
+#pragma unroll
+        for (int c = 0; c < (KC > 0 ? KC : 1); ++c) {
+            const int rem = k - 16 * c;   // wave-uniform
+            if (rem >= 16) {
+                float rv[16];
+#pragma unroll
+                for (int j = 0; j < 16; ++j)
+                    rv[j] = r[16 * c + j];   // wave-uniform address -> scalar loads
+#pragma unroll
+                for (int j = 0; j < 16; ++j) {
+                    const float diff = qv[16 * c + j] - rv[j];
+                    const float sq = diff * diff;
+                    acc = acc + sq;
+                }
+            } else if (rem > 0) {
+#pragma unroll
+                for (int j = 0; j < 15; ++j)
+                    if (j < rem) {
+                        const float diff = qv[16 * c + j] - r[16 * c + j];
+                        const float sq = diff * diff;
+                        acc = acc + sq;
+                    }
+            }
+        }
+    } else {
+        for (int d = 0; d < k; ++d) {
+            const float diff = qp[d] - r[d];
+            const float sq = diff * diff;
+            acc = acc + sq;
+        }
+    }
+    return acc;
+}
+
 // The first cnt keys of a[] ascending, by one block of KNN_BLOCK threads (knn_keys_sort_segments_kernel describes the network;
 // knn_topk_large_sort_kernel, knn_select.hip, sorts its lists with it too).  a: LDS or global memory of the block's own.
 __device__ __forceinline__ void sort_network(u64 *a, unsigned cnt)

@@ -18,6 +18,7 @@
 // granule counts, the prefix (a gated twin of knn_counts_to_offsets_kernel around the same block body), the scan — returns at once
 // unless *gate != 0, so the query path never synchronises with the host.  gate null: the launches of 2g, unchanged.
 #include "knn_masked_dev.h"
+#include "knn_slice_launch.h"
 
 // counts[g] <- the admitted rows of granule g: one mask word per thread (bits at and beyond n dropped), a granule per 32 lanes.
 __global__ __launch_bounds__(KNN_BLOCK) void knn_mask_granule_counts_kernel(const unsigned *__restrict__ mask, long long n, long long G,
@@ -89,7 +90,7 @@ __global__ __launch_bounds__(KNN_WAVE) void knn_masked_topk_kernel(const float *
     long long r0, r1;
     masked_slice(mask, n, P, G, r0, r1);
     masked_walk(mask, P, G, r0, r1, [&](long long i) {
-        const float acc = masked_dist2<KC>(qv, qp, R + (size_t)i * k, k);
+        const float acc = lane_row_dist2<KC>(qv, qp, R + (size_t)i * k, k);
         const u64 key = pack_key(acc, (unsigned)i);
         if (key < kth) {
             int p = K - 1;
@@ -141,7 +142,7 @@ __global__ __launch_bounds__(KNN_WAVE) void knn_masked_count_kernel(const float 
     long long r0, r1;
     masked_slice(mask, n, P, G, r0, r1);
     masked_walk(mask, P, G, r0, r1, [&](long long i) {
-        const float acc = masked_dist2<KC>(qv, qp, R + (size_t)i * k, k);
+        const float acc = lane_row_dist2<KC>(qv, qp, R + (size_t)i * k, k);
         cnt += acc < INFINITY && acc <= max_dist2 ? 1u : 0u;   // (NaN fails both compares)
     });
     if (q < m && cnt != 0u)
@@ -153,22 +154,19 @@ MaskedPlan knn_masked_plan(int k, int m, int K, long long n, int num_cu, bool in
     MaskedPlan p;
     if (m <= 0)
         return p;
-    p.chunk_m = m < KNN_TOPK_CHUNK ? m : KNN_TOPK_CHUNK;
-    p.chunks = knn_divup(m, KNN_TOPK_CHUNK);
+    const SlicePlan sp = knn_slice_plan(m, K, n, num_cu);   // (the unmasked scan's chunks, slices, LDS and per-slice lists)
+    p.chunk_m = sp.chunk_m;
+    p.chunks = sp.chunks;
     if (n <= 0) {   // an empty shard: an init top-K fills the keys, everything else launches nothing
         p.launches = K > 0 && init ? 1 : 0;
         return p;
     }
     p.granules = (n + KNN_MASK_GRANULE_ROWS - 1) / KNN_MASK_GRANULE_ROWS;
-    p.slices = K > 0 ? knn_topk_slices(p.chunk_m, K, n, num_cu) : knn_count_slices(p.chunk_m, n, num_cu);
-    p.lds_bytes = K > 0 ? (size_t)K * KNN_WAVE * sizeof(u64) : 0;
+    p.slices = sp.slices;
+    p.lds_bytes = sp.lds_bytes;
     p.counts_off = (size_t)(p.granules + 1) * sizeof(u64);
     p.mask_bytes = p.counts_off + (((size_t)p.granules * sizeof(unsigned) + 7) & ~(size_t)7);
-    if (K > 0) {   // knn_topk_part_bytes sizes by the first chunk; the last, of fewer queries, may cut the rows finer
-        const int ml = m - (p.chunks - 1) * KNN_TOPK_CHUNK;
-        const size_t last = (size_t)knn_topk_slices(ml, K, n, num_cu) * (size_t)ml * (size_t)K * sizeof(u64);
-        p.part_bytes = std::max(knn_topk_part_bytes(m, K, n, num_cu), last);
-    }
+    p.part_bytes = sp.part_bytes;
     p.launches = 2 + (long long)p.chunks * (K > 0 ? 2 : 1);
     return p;
 }
@@ -212,36 +210,25 @@ hipError_t knn_masked_topk_launch(const TopkCall &c, const MaskedPlan &p, const 
     if (c.ev0 && (e = hipEventRecord(c.ev0, s)) != hipSuccess)
         return e;
     const u64 lim = c.limit_key();
-    for (int c0 = 0; c0 < c.m; c0 += KNN_TOPK_CHUNK) {
-        const int mc = c.m - c0 < KNN_TOPK_CHUNK ? c.m - c0 : KNN_TOPK_CHUNK;
-        const long long slices = knn_topk_slices(mc, K, c.n, c.num_cu);
-        if ((size_t)slices * (size_t)mc * (size_t)K * sizeof(u64) > c.part_bytes)
+    e = knn_slice_chunks(c.m, c.n, c.num_cu, KnnTopkSlices{K}, [&](const SliceChunk &ch) {
+        const int mc = ch.mc;
+        if (KnnTopkSlices{K}.part_bytes(ch.slices, mc) > c.part_bytes)
             return hipErrorInvalidValue;
-        const dim3 grid((unsigned)slices, (unsigned)knn_divup(mc, KNN_WAVE)), block(KNN_WAVE);
-        const size_t lds = (size_t)K * KNN_WAVE * sizeof(u64);
-        const float *qc = c.q + (size_t)c0 * c.k;
+        const dim3 grid = ch.grid, block(KNN_WAVE);
+        const size_t lds = KnnTopkSlices{K}.lds_bytes();
+        const float *qc = c.q + (size_t)ch.c0 * c.k;
 #define KNN_MASKED_TOPK(KCV)                                                                                                    \
     hipLaunchKernelGGL(knn_masked_topk_kernel<KCV>, grid, block, lds, s, qc, c.r, c.k, mc, c.n, K, mask, (const u64 *)scratch, \
                        (int)p.granules, c.base, c.gids, c.part, lim)
-        switch ((c.k + 15) / 16) {
-        case 1: KNN_MASKED_TOPK(1); break;
-        case 2: KNN_MASKED_TOPK(2); break;
-        case 3: KNN_MASKED_TOPK(3); break;
-        case 4: KNN_MASKED_TOPK(4); break;
-        case 5: KNN_MASKED_TOPK(5); break;
-        case 6: KNN_MASKED_TOPK(6); break;
-        case 7: KNN_MASKED_TOPK(7); break;
-        case 8: KNN_MASKED_TOPK(8); break;
-        default: KNN_MASKED_TOPK(0); break;
-        }
+        KNN_KC_SWITCH(c.k, KNN_MASKED_TOPK)
 #undef KNN_MASKED_TOPK
-        e = hipGetLastError();
-        if (e != hipSuccess)
-            return e;
-        e = knn_topk_select_launch(c.part, (int)slices, mc, K, c.keys + (size_t)c0 * K, c.init, s);
-        if (e != hipSuccess)
-            return e;
-    }
+        const hipError_t el = hipGetLastError();
+        if (el != hipSuccess)
+            return el;
+        return knn_topk_select_launch(c.part, (int)ch.slices, mc, K, c.keys + (size_t)ch.c0 * K, c.init, s);
+    });
+    if (e != hipSuccess)
+        return e;
     if (c.ev1 && (e = hipEventRecord(c.ev1, s)) != hipSuccess)
         return e;
     return hipSuccess;
@@ -257,30 +244,19 @@ hipError_t knn_masked_count_launch(const CountCall &c, const MaskedPlan &p, cons
         return e;
     if (!gate && c.ev0 && (e = hipEventRecord(c.ev0, s)) != hipSuccess)
         return e;
-    for (int c0 = 0; c0 < c.m; c0 += KNN_TOPK_CHUNK) {
-        const int mc = c.m - c0 < KNN_TOPK_CHUNK ? c.m - c0 : KNN_TOPK_CHUNK;
-        const long long slices = knn_count_slices(mc, c.n, c.num_cu);
-        const dim3 grid((unsigned)slices, (unsigned)knn_divup(mc, KNN_WAVE)), block(KNN_WAVE);
-        const float *qc = c.q + (size_t)c0 * c.k;
+    e = knn_slice_chunks(c.m, c.n, c.num_cu, KnnCountSlices{}, [&](const SliceChunk &ch) {
+        const int mc = ch.mc;
+        const dim3 grid = ch.grid, block(KNN_WAVE);
+        const float *qc = c.q + (size_t)ch.c0 * c.k;
 #define KNN_MASKED_COUNT(KCV)                                                                                                   \
     hipLaunchKernelGGL(knn_masked_count_kernel<KCV>, grid, block, 0, s, qc, c.r, c.k, mc, c.n, mask, (const u64 *)scratch,     \
-                       (int)p.granules, c.max_dist2, c.counts + c0, gate)
-        switch ((c.k + 15) / 16) {
-        case 1: KNN_MASKED_COUNT(1); break;
-        case 2: KNN_MASKED_COUNT(2); break;
-        case 3: KNN_MASKED_COUNT(3); break;
-        case 4: KNN_MASKED_COUNT(4); break;
-        case 5: KNN_MASKED_COUNT(5); break;
-        case 6: KNN_MASKED_COUNT(6); break;
-        case 7: KNN_MASKED_COUNT(7); break;
-        case 8: KNN_MASKED_COUNT(8); break;
-        default: KNN_MASKED_COUNT(0); break;
-        }
+                       (int)p.granules, c.max_dist2, c.counts + ch.c0, gate)
+        KNN_KC_SWITCH(c.k, KNN_MASKED_COUNT)
 #undef KNN_MASKED_COUNT
-        e = hipGetLastError();
-        if (e != hipSuccess)
-            return e;
-    }
+        return hipGetLastError();
+    });
+    if (e != hipSuccess)
+        return e;
     if (!gate && c.ev1 && (e = hipEventRecord(c.ev1, s)) != hipSuccess)
         return e;
     return hipSuccess;

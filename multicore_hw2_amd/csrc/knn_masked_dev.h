@@ -1,6 +1,7 @@
 // knn_masked_dev.h — device code the scans over a subset of the rows share (knn_masked.hip: masked top-K and count;
 // knn_masked_lists.hip: masked lists and masked top-K beyond 64; DESIGN §4.6 "Over a subset of the rows"): the block's (or the
-// wave's) slice by admitted rows, the walk over the set bits of a slice's mask words, and v0's distance of one admitted row.
+// wave's) slice by admitted rows, and the walk over the set bits of a slice's mask words (v0's distance of an admitted row is the
+// exact scans' own: lane_row_dist2, knn_exact_dev.h).
 // The mask words, the bit positions and the row addresses are wave-uniform everywhere here: scalar loads, scalar arithmetic.
 #pragma once
 
@@ -109,46 +110,4 @@ __device__ __forceinline__ void masked_walk(const unsigned *__restrict__ mask, c
             }
         }
     }
-}
-
-// v0's distance of one row at the wave-uniform address r to the lane's query: knn_exact_topk_kernel's lines.
-template <int KC>
-__device__ __forceinline__ float masked_dist2(const float (&qv)[KC > 0 ? 16 * KC : 1], const float *__restrict__ qp,
-                                              const float *__restrict__ r, int k)
-{
-#pragma clang fp contract(off)
-    float acc = 0.0f;
-    if (KC > 0) {
-#pragma unroll
-        for (int c = 0; c < (KC > 0 ? KC : 1); ++c) {
-            const int rem = k - 16 * c;   // wave-uniform
-            if (rem >= 16) {
-                float rv[16];
-#pragma unroll
-                for (int j = 0; j < 16; ++j)
-                    rv[j] = r[16 * c + j];   // wave-uniform address -> scalar loads
-#pragma unroll
-                for (int j = 0; j < 16; ++j) {
-                    const float diff = qv[16 * c + j] - rv[j];
-                    const float sq = diff * diff;
-                    acc = acc + sq;
-                }
-            } else if (rem > 0) {
-#pragma unroll
-                for (int j = 0; j < 15; ++j)
-                    if (j < rem) {
-                        const float diff = qv[16 * c + j] - r[16 * c + j];
-                        const float sq = diff * diff;
-                        acc = acc + sq;
-                    }
-            }
-        }
-    } else {
-        for (int d = 0; d < k; ++d) {
-            const float diff = qp[d] - r[d];
-            const float sq = diff * diff;
-            acc = acc + sq;
-        }
-    }
-    return acc;
 }

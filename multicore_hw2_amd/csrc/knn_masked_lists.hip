@@ -7,10 +7,12 @@
 //   knn_masked_list_kernel<KC>   knn_exact_list_kernel<KC> (knn_exact.hip): the second pass of masked count -> offsets -> list;
 //   knn_masked_hist_kernel<KC>   knn_select_hist_kernel<KC> (knn_select.hip): one pass of the radix select;
 //   knn_masked_fill_kernel<KC>   knn_select_fill_kernel<KC>: the rows with key <= T into the query's K places.
-// A masked select is a select over the admitted rows: the histograms count admitted candidates only, so the pick
-// (knn_select_pick_kernel), the sort and the fold behind them are the unmasked call's own, through their launchers.
+// A masked select is a select over the admitted rows: the histograms count admitted candidates only, so the round — memset, pick
+// (knn_select_pick_kernel), sort, fold — is the unmasked call's own (knn_select_round, knn_slice_launch.h), handed the two masked
+// scans.  Chunks, slices and the KC forms: knn_slice_launch.h, as for every exact slice scan.
 #include "knn_masked_dev.h"
 #include "knn_radix_pick.h"
+#include "knn_slice_launch.h"
 
 // knn_masked_list_kernel<KC> — knn_exact_list_kernel<KC> over the admitted rows of the block's slice: one wave per block, lanes =
 // queries, a hit reserves and stores through list_put.  The walk gives the LOCAL row i; the key carries gids[i] or base + i.
@@ -40,7 +42,7 @@ __global__ __launch_bounds__(KNN_WAVE) void knn_masked_list_kernel(const float *
     long long r0, r1;
     masked_slice(mask, n, P, G, r0, r1);
     masked_walk(mask, P, G, r0, r1, [&](long long i) {
-        const float acc = masked_dist2<KC>(qv, qp, R + (size_t)i * k, k);
+        const float acc = lane_row_dist2<KC>(qv, qp, R + (size_t)i * k, k);
         if (q < m && acc < INFINITY && acc <= max_dist2)   // (NaN fails both compares)
             list_put(&fill[q], keys, off, room, pack_key(acc, gids ? gids[i] : (unsigned)(base + i)));
     });
@@ -81,7 +83,7 @@ __global__ __launch_bounds__(KNN_SELECT_BLOCK) void knn_masked_hist_kernel(const
     long long r0, r1;
     masked_wave_slice(mask, n, P, G, KNN_SELECT_WAVES, wave, r0, r1);
     masked_walk(mask, P, G, r0, r1, [&](long long i) {
-        const float acc = masked_dist2<KC>(qv, qp, R + (size_t)i * k, k);
+        const float acc = lane_row_dist2<KC>(qv, qp, R + (size_t)i * k, k);
         if (live && acc < INFINITY && acc <= max_dist2) {   // (NaN fails both compares)
             const u64 key = pack_key(acc, gids ? gids[i] : (unsigned)(base + i));
             if (knn_radix_match(key, pre, pass))
@@ -120,7 +122,7 @@ __global__ __launch_bounds__(KNN_WAVE) void knn_masked_fill_kernel(const float *
     long long r0, r1;
     masked_slice(mask, n, P, G, r0, r1);
     masked_walk(mask, P, G, r0, r1, [&](long long i) {
-        const float acc = masked_dist2<KC>(qv, qp, R + (size_t)i * k, k);
+        const float acc = lane_row_dist2<KC>(qv, qp, R + (size_t)i * k, k);
         if (q < m && acc < INFINITY && acc <= max_dist2) {   // (NaN fails both compares)
             const u64 key = pack_key(acc, gids ? gids[i] : (unsigned)(base + i));
             if (key <= t) {
@@ -157,19 +159,6 @@ MaskedListsPlan knn_masked_lists_plan(int k, int m, int K, long long n, int num_
     return p;
 }
 
-#define KNN_MASKED_FORMS(CALL)   \
-    switch ((c.k + 15) / 16) {   \
-    case 1: CALL(1); break;      \
-    case 2: CALL(2); break;      \
-    case 3: CALL(3); break;      \
-    case 4: CALL(4); break;      \
-    case 5: CALL(5); break;      \
-    case 6: CALL(6); break;      \
-    case 7: CALL(7); break;      \
-    case 8: CALL(8); break;      \
-    default: CALL(0); break;     \
-    }
-
 hipError_t knn_masked_list_launch(const ListCall &c, const MaskedListsPlan &p, const unsigned *mask, u64 *scratch, const unsigned *gate)
 {
     hipStream_t s = c.stream;
@@ -180,20 +169,20 @@ hipError_t knn_masked_list_launch(const ListCall &c, const MaskedListsPlan &p, c
         return e;
     if (!gate && c.ev0 && (e = hipEventRecord(c.ev0, s)) != hipSuccess)
         return e;
-    for (int c0 = 0; c0 < c.m; c0 += KNN_TOPK_CHUNK) {
-        const int mc = c.m - c0 < KNN_TOPK_CHUNK ? c.m - c0 : KNN_TOPK_CHUNK;
-        const long long slices = knn_count_slices(mc, c.n, c.num_cu);
-        const dim3 grid((unsigned)slices, (unsigned)knn_divup(mc, KNN_WAVE)), block(KNN_WAVE);
+    e = knn_slice_chunks(c.m, c.n, c.num_cu, KnnCountSlices{}, [&](const SliceChunk &ch) {
+        const int mc = ch.mc;
+        const long long c0 = ch.c0;
+        const dim3 grid = ch.grid, block(KNN_WAVE);
         const float *qc = c.q + (size_t)c0 * c.k;
 #define KNN_MASKED_LIST(KCV)                                                                                                   \
     hipLaunchKernelGGL(knn_masked_list_kernel<KCV>, grid, block, 0, s, qc, c.r, c.k, mc, c.n, mask, (const u64 *)scratch,     \
                        (int)p.cut.granules, c.max_dist2, c.base, c.gids, c.offsets + c0, c.fill + c0, c.keys, gate)
-        KNN_MASKED_FORMS(KNN_MASKED_LIST)
+        KNN_KC_SWITCH(c.k, KNN_MASKED_LIST)
 #undef KNN_MASKED_LIST
-        e = hipGetLastError();
-        if (e != hipSuccess)
-            return e;
-    }
+        return hipGetLastError();
+    });
+    if (e != hipSuccess)
+        return e;
     if (!gate && c.ev1 && (e = hipEventRecord(c.ev1, s)) != hipSuccess)
         return e;
     return hipSuccess;
@@ -213,55 +202,24 @@ hipError_t knn_masked_large_launch(const TopkCall &c, const MaskedListsPlan &p, 
     hipError_t e = knn_masked_prefix_launch(p.cut, c.n, mask, scratch, s);
     if (e != hipSuccess)
         return e;
-    for (int c0 = 0; c0 < c.m; c0 += KNN_TOPK_CHUNK) {
-        const int mc = c.m - c0 < KNN_TOPK_CHUNK ? c.m - c0 : KNN_TOPK_CHUNK;
-        const float *qc = c.q + (size_t)c0 * c.k;
-        u64 *keys = c.keys + (size_t)c0 * c.K;
-        u64 *list = c.init ? keys : (u64 *)(st + sp.list_off);
-        const long long mcp = (long long)knn_divup(mc, KNN_WAVE) * KNN_WAVE;
-        const dim3 grid_hist((unsigned)knn_select_slices(mc, c.n, c.num_cu), (unsigned)knn_divup(mc, KNN_WAVE));
-        const dim3 grid_fill((unsigned)knn_count_slices(mc, c.n, c.num_cu), (unsigned)knn_divup(mc, KNN_WAVE));
-        e = hipMemsetAsync(st, 0, sp.state_bytes, s);
-        if (e != hipSuccess)
-            return e;
-        if (c.ev0 && c0 == 0)
-            (void)hipEventRecord(c.ev0, s);
-        const unsigned *gates = (const unsigned *)(st + sp.gate_off);
-        for (int pass = 0; pass < KNN_RADIX_PASSES; ++pass) {
+    return knn_select_round(
+        c, sp, tie_word,
+        [&](const SliceChunk &ch, const float *qc, int pass, const unsigned *pass_gate) {
+            const int mc = ch.mc;
+            const long long mcp = (long long)ch.grid.y * KNN_WAVE;
 #define KNN_MASKED_HIST(KCV)                                                                                                        \
-    hipLaunchKernelGGL(knn_masked_hist_kernel<KCV>, grid_hist, dim3(KNN_SELECT_BLOCK), 0, s, qc, c.r, c.k, mc, c.n, mask, P, G, \
+    hipLaunchKernelGGL(knn_masked_hist_kernel<KCV>, ch.grid, dim3(KNN_SELECT_BLOCK), 0, s, qc, c.r, c.k, mc, c.n, mask, P, G,      \
                        c.max_dist2, c.base, c.gids, pass, (const u64 *)(st + sp.prefix_off), (const unsigned *)(st + sp.need_off), \
-                       (unsigned *)(st + sp.hist_off), mcp, pass == 0 ? (const unsigned *)nullptr : gates + pass)
-            KNN_MASKED_FORMS(KNN_MASKED_HIST)
+                       (unsigned *)(st + sp.hist_off), mcp, pass_gate)
+            KNN_KC_SWITCH(c.k, KNN_MASKED_HIST)
 #undef KNN_MASKED_HIST
-            e = hipGetLastError();
-            if (e != hipSuccess)
-                return e;
-            e = knn_select_pick_launch(sp, c.part, mc, pass, c.K, s);
-            if (e != hipSuccess)
-                return e;
-        }
-#define KNN_MASKED_FILL(KCV)                                                                                                    \
-    hipLaunchKernelGGL(knn_masked_fill_kernel<KCV>, grid_fill, dim3(KNN_WAVE), 0, s, qc, c.r, c.k, mc, c.n, mask, P, G,    \
+        },
+        [&](const SliceChunk &ch, const float *qc, u64 *list) {
+            const int mc = ch.mc;
+#define KNN_MASKED_FILL(KCV)                                                                                                \
+    hipLaunchKernelGGL(knn_masked_fill_kernel<KCV>, ch.grid, dim3(KNN_WAVE), 0, s, qc, c.r, c.k, mc, c.n, mask, P, G,      \
                        c.max_dist2, c.base, c.gids, (const u64 *)(st + sp.prefix_off), (unsigned *)(st + sp.cursor_off), c.K, list)
-        KNN_MASKED_FORMS(KNN_MASKED_FILL)
+            KNN_KC_SWITCH(c.k, KNN_MASKED_FILL)
 #undef KNN_MASKED_FILL
-        e = hipGetLastError();
-        if (e != hipSuccess)
-            return e;
-        if (c.ev1 && c0 + mc == c.m)
-            (void)hipEventRecord(c.ev1, s);
-        e = knn_topk_large_sort_launch(sp, c.part, mc, c.K, list, s);
-        if (e != hipSuccess)
-            return e;
-        if (!c.init) {
-            e = knn_topk_merge_large_launch(mc, c.K, list, keys, s);
-            if (e != hipSuccess)
-                return e;
-        }
-    }
-    if (tie_word)
-        *tie_word = (const unsigned *)(st + sp.gate_off) + KNN_RADIX_DIST_PASSES;
-    return hipSuccess;
+        });
 }
-#undef KNN_MASKED_FORMS

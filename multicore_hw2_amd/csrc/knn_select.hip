@@ -11,50 +11,11 @@
 //
 // Every scan is knn_exact_count_kernel<KC>'s loop (knn_exact.hip): lanes = queries, coordinates in VGPRs, rows as wave-uniform
 // scalar loads, v0's arithmetic under fp contract(off); a candidate is a row whose distance E is finite and E <= max_dist2.
+// The sequence of launches per chunk of queries is knn_select_round's (knn_slice_launch.h), shared with the select over a subset
+// of the rows (knn_masked_lists.hip); this file hands it its two scans and keeps the pieces that do not look at rows.
 #include "knn_exact_dev.h"
 #include "knn_radix_pick.h"
-
-// v0's distance of one row to the lane's query — the body of knn_exact_count_kernel's row loop.  r: wave-uniform.
-template <int KC>
-__device__ __forceinline__ float select_row_dist(const float (&qv)[KC > 0 ? 16 * KC : 1], const float *__restrict__ qp,
-                                                 const float *__restrict__ r, int k)
-{
-#pragma clang fp contract(off)
-    float acc = 0.0f;
-    if (KC > 0) {
-#pragma unroll
-        for (int c = 0; c < (KC > 0 ? KC : 1); ++c) {
-            const int rem = k - 16 * c;   // wave-uniform
-            if (rem >= 16) {
-                float rv[16];
-#pragma unroll
-                for (int j = 0; j < 16; ++j)
-                    rv[j] = r[16 * c + j];   // wave-uniform address -> scalar loads
-#pragma unroll
-                for (int j = 0; j < 16; ++j) {
-                    const float diff = qv[16 * c + j] - rv[j];
-                    const float sq = diff * diff;
-                    acc = acc + sq;
-                }
-            } else if (rem > 0) {
-#pragma unroll
-                for (int j = 0; j < 15; ++j)
-                    if (j < rem) {
-                        const float diff = qv[16 * c + j] - r[16 * c + j];
-                        const float sq = diff * diff;
-                        acc = acc + sq;
-                    }
-            }
-        }
-    } else {
-        for (int d = 0; d < k; ++d) {
-            const float diff = qp[d] - r[d];
-            const float sq = diff * diff;
-            acc = acc + sq;
-        }
-    }
-    return acc;
-}
+#include "knn_slice_launch.h"
 
 // One pass of the select: grid (slices, waves of queries), KNN_SELECT_WAVES waves per block.  The block's waves hold the SAME 64
 // queries and split the slice's rows; a candidate whose key lies under its query's prefix adds one to hist[digit][lane] in LDS —
@@ -96,7 +57,7 @@ __global__ __launch_bounds__(KNN_SELECT_BLOCK) void knn_select_hist_kernel(const
     const float *__restrict__ r = R + (size_t)i0 * k;
     const float *__restrict__ qp = Q + (size_t)qa * k;
     for (long long i = i0; i < i1; ++i, r += k) {
-        const float acc = select_row_dist<KC>(qv, qp, r, k);
+        const float acc = lane_row_dist2<KC>(qv, qp, r, k);
         if (live && acc < INFINITY && acc <= max_dist2) {   // (NaN fails both compares)
             const u64 key = pack_key(acc, gids ? gids[i] : (unsigned)(base + i));
             if (knn_radix_match(key, pre, pass))
@@ -160,7 +121,7 @@ __global__ __launch_bounds__(KNN_WAVE) void knn_select_fill_kernel(const float *
     const float *__restrict__ r = R + (size_t)i0 * k;
     const float *__restrict__ qp = Q + (size_t)qa * k;
     for (long long i = i0; i < i1; ++i, r += k) {
-        const float acc = select_row_dist<KC>(qv, qp, r, k);
+        const float acc = lane_row_dist2<KC>(qv, qp, r, k);
         if (q < m && acc < INFINITY && acc <= max_dist2) {   // (NaN fails both compares)
             const u64 key = pack_key(acc, gids ? gids[i] : (unsigned)(base + i));
             if (key <= t) {
@@ -229,11 +190,9 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_topk_merge_large_kernel(int K, 
     }
 }
 
-namespace {
-
 // Slices of one select pass over a chunk of mc queries: two 64 KiB blocks are resident per CU, twice that many are launched
 // (the tail of a pass is then a quarter of a block's work), a slice holds at least 128 rows per wave.
-long long select_slices(int mc, long long n, int num_cu)
+long long knn_select_slices(int mc, long long n, int num_cu)
 {
     const long long qg = knn_divup(mc, KNN_WAVE);
     long long slices = (long long)num_cu * 4 / qg;
@@ -248,41 +207,19 @@ long long select_slices(int mc, long long n, int num_cu)
     return (n + per - 1) / per;
 }
 
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-template <int KC>
-void launch_hist(const TopkCall &c, const float *qc, int mc, long long slices, int pass, const TopkLargePlan &p, unsigned char *st)
-{
-    const long long per = (c.n + slices - 1) / slices;
-    const unsigned *gates = (const unsigned *)(st + p.gate_off);
-    hipLaunchKernelGGL(knn_select_hist_kernel<KC>, dim3((unsigned)slices, (unsigned)knn_divup(mc, KNN_WAVE)), dim3(KNN_SELECT_BLOCK), 0,
-                       c.stream, qc, c.r, c.k, mc, c.n, per, c.max_dist2, c.base, c.gids, pass, (const u64 *)(st + p.prefix_off),
-                       (const unsigned *)(st + p.need_off), (unsigned *)(st + p.hist_off), (long long)knn_divup(mc, KNN_WAVE) * KNN_WAVE,
-                       pass == 0 ? nullptr : gates + pass);
-}
-
-template <int KC>
-void launch_fill(const TopkCall &c, const float *qc, int mc, const TopkLargePlan &p, unsigned char *st, u64 *list)
-{
-    const long long slices = knn_count_slices(mc, c.n, c.num_cu);
-    const long long per = (c.n + slices - 1) / slices;
-    hipLaunchKernelGGL(knn_select_fill_kernel<KC>, dim3((unsigned)slices, (unsigned)knn_divup(mc, KNN_WAVE)), dim3(KNN_WAVE), 0, c.stream,
-                       qc, c.r, c.k, mc, c.n, per, c.max_dist2, c.base, c.gids, (const u64 *)(st + p.prefix_off),
-                       (unsigned *)(st + p.cursor_off), c.K, list);
-}
-
-}  // namespace
+static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 TopkLargePlan knn_topk_large_plan(int k, int m, int K, long long n, int num_cu, bool init)
 {
     TopkLargePlan p;
-    p.chunks = knn_divup(m, KNN_TOPK_CHUNK);
-    p.chunk_m = m < KNN_TOPK_CHUNK ? m : KNN_TOPK_CHUNK;
-    p.mcp = (long long)knn_divup(p.chunk_m, KNN_WAVE) * KNN_WAVE;
-    p.slices = select_slices(p.chunk_m, n, num_cu);
+    const SlicePlan sp = knn_slice_plan(m, n, num_cu, KnnSelectSlices{});
+    p.chunks = sp.chunks;
+    p.chunk_m = sp.chunk_m;
+    p.mcp = sp.groups * KNN_WAVE;
+    p.slices = sp.slices;
     p.dist_passes = KNN_RADIX_DIST_PASSES;
     p.index_passes = KNN_RADIX_PASSES - KNN_RADIX_DIST_PASSES;
-    p.lds_bytes = KNN_SELECT_HIST_WORDS * sizeof(unsigned);
+    p.lds_bytes = sp.lds_bytes;
     const size_t mcp = (size_t)p.mcp;
     p.hist_off = 0;
     p.prefix_off = align256(p.hist_off + (size_t)KNN_RADIX_BINS * mcp * sizeof(unsigned));
@@ -306,66 +243,29 @@ hipError_t knn_topk_large_launch(const TopkCall &c, const TopkLargePlan &p, cons
         return hipErrorInvalidValue;
     hipStream_t s = c.stream;
     unsigned char *st = (unsigned char *)c.part;
-    for (int c0 = 0; c0 < c.m; c0 += KNN_TOPK_CHUNK) {
-        const int mc = c.m - c0 < KNN_TOPK_CHUNK ? c.m - c0 : KNN_TOPK_CHUNK;
-        const float *qc = c.q + (size_t)c0 * c.k;
-        u64 *keys = c.keys + (size_t)c0 * c.K;
-        u64 *list = c.init ? keys : (u64 *)(st + p.list_off);
-        const long long slices = select_slices(mc, c.n, c.num_cu);
-        const long long mcp = (long long)knn_divup(mc, KNN_WAVE) * KNN_WAVE;
-        hipError_t e = hipMemsetAsync(st, 0, p.state_bytes, s);
-        if (e != hipSuccess)
-            return e;
-        if (c.ev0 && c0 == 0)
-            (void)hipEventRecord(c.ev0, s);
-#define KNN_SELECT_FORMS(CALL)   \
-    switch ((c.k + 15) / 16) {   \
-    case 1: CALL(1); break;      \
-    case 2: CALL(2); break;      \
-    case 3: CALL(3); break;      \
-    case 4: CALL(4); break;      \
-    case 5: CALL(5); break;      \
-    case 6: CALL(6); break;      \
-    case 7: CALL(7); break;      \
-    case 8: CALL(8); break;      \
-    default: CALL(0); break;     \
-    }
-        for (int pass = 0; pass < KNN_RADIX_PASSES; ++pass) {
-#define KNN_SELECT_HIST(KCV) launch_hist<KCV>(c, qc, mc, slices, pass, p, st)
-            KNN_SELECT_FORMS(KNN_SELECT_HIST)
+    return knn_select_round(
+        c, p, tie_word,
+        [&](const SliceChunk &ch, const float *qc, int pass, const unsigned *pass_gate) {
+            const int mc = ch.mc;
+            const long long mcp = (long long)ch.grid.y * KNN_WAVE;
+#define KNN_SELECT_HIST(KCV)                                                                                                       \
+    hipLaunchKernelGGL(knn_select_hist_kernel<KCV>, ch.grid, dim3(KNN_SELECT_BLOCK), 0, s, qc, c.r, c.k, mc, c.n, ch.per,         \
+                       c.max_dist2, c.base, c.gids, pass, (const u64 *)(st + p.prefix_off), (const unsigned *)(st + p.need_off), \
+                       (unsigned *)(st + p.hist_off), mcp, pass_gate)
+            KNN_KC_SWITCH(c.k, KNN_SELECT_HIST)
 #undef KNN_SELECT_HIST
-            hipLaunchKernelGGL(knn_select_pick_kernel, dim3((unsigned)knn_divup(mc, KNN_BLOCK)), dim3(KNN_BLOCK), 0, s,
-                               (unsigned *)(st + p.hist_off), mcp, mc, pass, c.K, (u64 *)(st + p.prefix_off),
-                               (unsigned *)(st + p.need_off), (unsigned *)(st + p.gate_off));
-            e = hipGetLastError();
-            if (e != hipSuccess)
-                return e;
-        }
-#define KNN_SELECT_FILL(KCV) launch_fill<KCV>(c, qc, mc, p, st, list)
-        KNN_SELECT_FORMS(KNN_SELECT_FILL)
+        },
+        [&](const SliceChunk &ch, const float *qc, u64 *list) {
+            const int mc = ch.mc;
+#define KNN_SELECT_FILL(KCV)                                                                                                 \
+    hipLaunchKernelGGL(knn_select_fill_kernel<KCV>, ch.grid, dim3(KNN_WAVE), 0, s, qc, c.r, c.k, mc, c.n, ch.per, c.max_dist2, \
+                       c.base, c.gids, (const u64 *)(st + p.prefix_off), (unsigned *)(st + p.cursor_off), c.K, list)
+            KNN_KC_SWITCH(c.k, KNN_SELECT_FILL)
 #undef KNN_SELECT_FILL
-#undef KNN_SELECT_FORMS
-        if (c.ev1 && c0 + mc == c.m)
-            (void)hipEventRecord(c.ev1, s);
-        hipLaunchKernelGGL(knn_topk_large_sort_kernel, dim3((unsigned)mc), dim3(KNN_BLOCK), 0, s, (const unsigned *)(st + p.cursor_off),
-                           c.K, list);
-        e = hipGetLastError();
-        if (e != hipSuccess)
-            return e;
-        if (!c.init) {
-            e = knn_topk_merge_large_launch(mc, c.K, list, keys, s);
-            if (e != hipSuccess)
-                return e;
-        }
-    }
-    if (tie_word)
-        *tie_word = (const unsigned *)(st + p.gate_off) + KNN_RADIX_DIST_PASSES;
-    return hipSuccess;
+        });
 }
 
 // The select's pieces that do not look at rows, for the select over a subset of the rows (knn_masked_lists.hip).
-long long knn_select_slices(int mc, long long n, int num_cu) { return select_slices(mc, n, num_cu); }
-
 hipError_t knn_select_pick_launch(const TopkLargePlan &p, u64 *scratch, int mc, int pass, int K, hipStream_t s)
 {
     if (!scratch || mc <= 0 || mc > p.mcp || pass < 0 || pass >= KNN_RADIX_PASSES || K < 1 || K > KNN_TOPK_LARGE_MAX)

@@ -4,7 +4,7 @@
 // Query j of a call is LOCAL row first + j of the shard, and that row is no candidate for it: the K nearest OTHER rows, the other
 // rows within a radius.  The three scans are the skeletons of knn_exact_topk_kernel<KC, LIM>, knn_exact_count_kernel<KC> and
 // knn_exact_list_kernel<KC> (knn_exact.hip) — one wave per block, lanes = queries, rows as wave-uniform scalar loads, v0's
-// arithmetic (masked_dist2, knn_masked_dev.h) — with two changes.  A lane's coordinates come straight from the resident rows,
+// arithmetic (lane_row_dist2, knn_exact_dev.h) — with two changes.  A lane's coordinates come straight from the resident rows,
 // R + (first + q) * k: no queries pointer, nothing uploaded or gathered.  And the block cuts its slice around the only rows that can
 // be some lane's own — the window [w0, w0 + 64), w0 = first + 64 * blockIdx.y (knn_self_window.h) — into the rows before it, inside
 // it and after it, and runs one row-loop body over the three: only the window's form compares the (wave-uniform) row with the
@@ -18,6 +18,7 @@
 // knn_self_count_gated_kernel and knn_self_list_gated_kernel are the count and list scans behind a device gate: the exact answer of
 // the routed self calls (include/knn_mi355x.h 2k) when the grid gave up or a cell-pruned pass fell back.
 #include "knn_self_scan.h"   // self_rows, self_scan, self_scan_one: the row loops (shared with knn_cluster.hip)
+#include "knn_slice_launch.h"
 
 // knn_self_topk_kernel<KC, LIM> — knn_exact_topk_kernel<KC, LIM> for the m queries that are the rows first .. first + m - 1.  LIM as
 // there: the call has a radius, the K-th key a row is compared with is min(column[K - 1], lim); the plain form never reads `lim`
@@ -328,35 +329,19 @@ SelfPlan knn_self_plan(int /*k*/, int m, int K, long long n, int num_cu, bool in
     SelfPlan p;
     if (m <= 0 || n <= 0)
         return p;
-    p.chunk_m = m < KNN_TOPK_CHUNK ? m : KNN_TOPK_CHUNK;
-    p.chunks = knn_divup(m, KNN_TOPK_CHUNK);
-    p.slices = K > 0 ? knn_topk_slices(p.chunk_m, K, n, num_cu) : knn_count_slices(p.chunk_m, n, num_cu);
-    p.groups = knn_divup(p.chunk_m, KNN_WAVE);
-    p.lds_bytes = K > 0 ? (size_t)K * KNN_WAVE * sizeof(u64) : 0;
-    if (K > 0) {   // knn_topk_part_bytes sizes by the first chunk; the last, of fewer queries, may cut the rows finer
-        const int ml = m - (p.chunks - 1) * KNN_TOPK_CHUNK;
-        const size_t last = (size_t)knn_topk_slices(ml, K, n, num_cu) * (size_t)ml * (size_t)K * sizeof(u64);
-        p.part_bytes = std::max(knn_topk_part_bytes(m, K, n, num_cu), last);
-        // the through way: the plain call's lists [m][K + 1], and behind them — a folding call — the K that stay [m][K]
-        if (K + 1 <= KNN_TOPK_MAX)
-            p.through_bytes = (size_t)m * (size_t)(K + 1) * sizeof(u64) + (init ? 0 : (size_t)m * (size_t)K * sizeof(u64));
-    }
+    const SlicePlan sp = knn_slice_plan(m, K, n, num_cu);   // (the plain exact scan's chunks, slices, LDS and per-slice lists)
+    p.chunk_m = sp.chunk_m;
+    p.chunks = sp.chunks;
+    p.slices = sp.slices;
+    p.groups = sp.groups;
+    p.lds_bytes = sp.lds_bytes;
+    p.part_bytes = sp.part_bytes;
+    // the through way: the plain call's lists [m][K + 1], and behind them — a folding call — the K that stay [m][K]
+    if (K > 0 && K + 1 <= KNN_TOPK_MAX)
+        p.through_bytes = (size_t)m * (size_t)(K + 1) * sizeof(u64) + (init ? 0 : (size_t)m * (size_t)K * sizeof(u64));
     p.launches = (long long)p.chunks * (K > 0 ? 2 : 1);
     return p;
 }
-
-#define KNN_SELF_SWITCH(k, LAUNCH) \
-    switch (((k) + 15) / 16) {     \
-    case 1: LAUNCH(1); break;      \
-    case 2: LAUNCH(2); break;      \
-    case 3: LAUNCH(3); break;      \
-    case 4: LAUNCH(4); break;      \
-    case 5: LAUNCH(5); break;      \
-    case 6: LAUNCH(6); break;      \
-    case 7: LAUNCH(7); break;      \
-    case 8: LAUNCH(8); break;      \
-    default: LAUNCH(0); break;     \
-    }
 
 hipError_t knn_self_topk_launch(const TopkCall &c, long long row_first)
 {
@@ -369,16 +354,15 @@ hipError_t knn_self_topk_launch(const TopkCall &c, long long row_first)
         return e;
     const u64 lim = c.limit_key();
     const bool within = lim < kKeyInit;
-    for (int c0 = 0; c0 < c.m; c0 += KNN_TOPK_CHUNK) {
-        const int mc = c.m - c0 < KNN_TOPK_CHUNK ? c.m - c0 : KNN_TOPK_CHUNK;
-        const long long slices = knn_topk_slices(mc, K, c.n, c.num_cu);
-        if ((size_t)slices * (size_t)mc * (size_t)K * sizeof(u64) > c.part_bytes)
+    e = knn_slice_chunks(c.m, c.n, c.num_cu, KnnTopkSlices{K}, [&](const SliceChunk &ch) {
+        const int mc = ch.mc;
+        const long long c0 = ch.c0, per = ch.per;
+        if (KnnTopkSlices{K}.part_bytes(ch.slices, mc) > c.part_bytes)
             return hipErrorInvalidValue;
-        const long long per = (c.n + slices - 1) / slices;
         if (per > 0xFFFFFFFFll)   // (the kernels count a slice's rows in 32 bits)
             return hipErrorInvalidValue;
-        const dim3 grid((unsigned)slices, (unsigned)knn_divup(mc, KNN_WAVE)), block(KNN_WAVE);
-        const size_t lds = (size_t)K * KNN_WAVE * sizeof(u64);
+        const dim3 grid = ch.grid, block(KNN_WAVE);
+        const size_t lds = KnnTopkSlices{K}.lds_bytes();
 #define KNN_SELF_TOPK(KCV)                                                                                                          \
     if (within)                                                                                                                     \
         hipLaunchKernelGGL((knn_self_topk_kernel<KCV, true>), grid, block, lds, s, c.r, c.k, row_first + c0, mc, c.n, K, per, c.base, \
@@ -386,15 +370,15 @@ hipError_t knn_self_topk_launch(const TopkCall &c, long long row_first)
     else                                                                                                                            \
         hipLaunchKernelGGL((knn_self_topk_kernel<KCV, false>), grid, block, lds, s, c.r, c.k, row_first + c0, mc, c.n, K, per, c.base, \
                            c.gids, c.part, lim)
-        KNN_SELF_SWITCH(c.k, KNN_SELF_TOPK)
+        KNN_KC_SWITCH(c.k, KNN_SELF_TOPK)
 #undef KNN_SELF_TOPK
-        e = hipGetLastError();
-        if (e != hipSuccess)
-            return e;
-        e = knn_topk_select_launch(c.part, (int)slices, mc, K, c.keys + (size_t)c0 * K, c.init, s);
-        if (e != hipSuccess)
-            return e;
-    }
+        const hipError_t el = hipGetLastError();
+        if (el != hipSuccess)
+            return el;
+        return knn_topk_select_launch(c.part, (int)ch.slices, mc, K, c.keys + (size_t)c0 * K, c.init, s);
+    });
+    if (e != hipSuccess)
+        return e;
     if (c.ev1 && (e = hipEventRecord(c.ev1, s)) != hipSuccess)
         return e;
     return hipSuccess;
@@ -408,13 +392,12 @@ hipError_t knn_self_count_launch(const CountCall &c, long long row_first, const 
     hipError_t e;
     if (!gate && c.ev0 && (e = hipEventRecord(c.ev0, s)) != hipSuccess)   // (a gated scan is not its way's dominant kernel)
         return e;
-    for (int c0 = 0; c0 < c.m; c0 += KNN_TOPK_CHUNK) {
-        const int mc = c.m - c0 < KNN_TOPK_CHUNK ? c.m - c0 : KNN_TOPK_CHUNK;
-        const long long slices = knn_count_slices(mc, c.n, c.num_cu);
-        const long long per = (c.n + slices - 1) / slices;
+    e = knn_slice_chunks(c.m, c.n, c.num_cu, KnnCountSlices{}, [&](const SliceChunk &ch) {
+        const int mc = ch.mc;
+        const long long c0 = ch.c0, per = ch.per;
         if (per > 0xFFFFFFFFll)   // (the kernels count a slice's rows in 32 bits)
             return hipErrorInvalidValue;
-        const dim3 grid((unsigned)slices, (unsigned)knn_divup(mc, KNN_WAVE)), block(KNN_WAVE);
+        const dim3 grid = ch.grid, block(KNN_WAVE);
 #define KNN_SELF_COUNT(KCV)                                                                                                          \
     if (gate)      /* the gated twin: scalar form and radii alike */                                                                 \
         hipLaunchKernelGGL(knn_self_count_gated_kernel<KCV>, grid, block, 0, s, c.r, c.k, row_first + c0, mc, c.n, per,               \
@@ -424,12 +407,12 @@ hipError_t knn_self_count_launch(const CountCall &c, long long row_first, const 
                            c.max_dist2, c.counts + c0);                                                                              \
     else                                                                                                                             \
         hipLaunchKernelGGL(knn_self_count_kernel<KCV>, grid, block, 0, s, c.r, c.k, row_first + c0, mc, c.n, per, c.max_dist2, c.counts + c0)
-        KNN_SELF_SWITCH(c.k, KNN_SELF_COUNT)
+        KNN_KC_SWITCH(c.k, KNN_SELF_COUNT)
 #undef KNN_SELF_COUNT
-        e = hipGetLastError();
-        if (e != hipSuccess)
-            return e;
-    }
+        return hipGetLastError();
+    });
+    if (e != hipSuccess)
+        return e;
     if (!gate && c.ev1 && (e = hipEventRecord(c.ev1, s)) != hipSuccess)
         return e;
     return hipSuccess;
@@ -443,13 +426,12 @@ hipError_t knn_self_list_launch(const ListCall &c, long long row_first, const un
     hipError_t e;
     if (!gate && c.ev0 && (e = hipEventRecord(c.ev0, s)) != hipSuccess)   // (a gated scan is not its way's dominant kernel)
         return e;
-    for (int c0 = 0; c0 < c.m; c0 += KNN_TOPK_CHUNK) {
-        const int mc = c.m - c0 < KNN_TOPK_CHUNK ? c.m - c0 : KNN_TOPK_CHUNK;
-        const long long slices = knn_count_slices(mc, c.n, c.num_cu);
-        const long long per = (c.n + slices - 1) / slices;
+    e = knn_slice_chunks(c.m, c.n, c.num_cu, KnnCountSlices{}, [&](const SliceChunk &ch) {
+        const int mc = ch.mc;
+        const long long c0 = ch.c0, per = ch.per;
         if (per > 0xFFFFFFFFll)   // (the kernels count a slice's rows in 32 bits)
             return hipErrorInvalidValue;
-        const dim3 grid((unsigned)slices, (unsigned)knn_divup(mc, KNN_WAVE)), block(KNN_WAVE);
+        const dim3 grid = ch.grid, block(KNN_WAVE);
 #define KNN_SELF_LIST(KCV)                                                                                                              \
     if (gate)      /* the gated twin: scalar form and radii alike */                                                                    \
         hipLaunchKernelGGL(knn_self_list_gated_kernel<KCV>, grid, block, 0, s, c.r, c.k, row_first + c0, mc, c.n, per,                   \
@@ -460,12 +442,12 @@ hipError_t knn_self_list_launch(const ListCall &c, long long row_first, const un
     else                                                                                                                                \
         hipLaunchKernelGGL(knn_self_list_kernel<KCV>, grid, block, 0, s, c.r, c.k, row_first + c0, mc, c.n, per, c.max_dist2, c.base, c.gids, \
                            c.offsets + c0, c.fill + c0, c.keys)
-        KNN_SELF_SWITCH(c.k, KNN_SELF_LIST)
+        KNN_KC_SWITCH(c.k, KNN_SELF_LIST)
 #undef KNN_SELF_LIST
-        e = hipGetLastError();
-        if (e != hipSuccess)
-            return e;
-    }
+        return hipGetLastError();
+    });
+    if (e != hipSuccess)
+        return e;
     if (!gate && c.ev1 && (e = hipEventRecord(c.ev1, s)) != hipSuccess)
         return e;
     return hipSuccess;

@@ -1,10 +1,10 @@
 // knn_self_scan.h — the row loops of the exact self-scans (knn_self.hip: top-K, count, list and their forms; knn_cluster.hip: the
 // link sweep of knn_index_self_cluster_within).  One wave per block, lanes = queries that are rows of the shard, rows as
-// wave-uniform scalar loads, v0's arithmetic (masked_dist2, knn_masked_dev.h); the block cuts its slice around the only rows that
+// wave-uniform scalar loads, v0's arithmetic (lane_row_dist2, knn_exact_dev.h); the block cuts its slice around the only rows that
 // can be some lane's own (knn_self_window.h).  knn_self.hip's head describes the kernels built on them.
 #pragma once
 
-#include "knn_masked_dev.h"
+#include "knn_exact_dev.h"
 #include "knn_self_window.h"
 
 // hit(acc, row) for the next `count` rows but — WIN — the lane's own: the one row-loop body of the three scans.  r: the first of
@@ -15,7 +15,7 @@ __device__ __forceinline__ void self_rows(const float (&qv)[KC > 0 ? 16 * KC : 1
                                           const float *__restrict__ &r, int k, unsigned &row, unsigned count, unsigned own, Hit &&hit)
 {
     for (unsigned c = 0; c < count; ++c, ++row, r += k) {
-        const float acc = masked_dist2<KC>(qv, qp, r, k);
+        const float acc = lane_row_dist2<KC>(qv, qp, r, k);
         if (!WIN || row != own)
             hit(acc, row);
     }
@@ -64,7 +64,7 @@ __device__ __forceinline__ void self_scan_one(const float (&qv)[KC > 0 ? 16 * KC
         const bool win = t == 1;
         const unsigned count = t == 0 ? n0 : t == 1 ? n1 : n2;
         for (unsigned c = 0; c < count; ++c, ++row, r += k) {
-            const float acc = masked_dist2<KC>(qv, qp, r, k);
+            const float acc = lane_row_dist2<KC>(qv, qp, r, k);
             hit(acc, row, !(win && row == own));
         }
     }

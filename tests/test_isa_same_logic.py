@@ -75,6 +75,16 @@ def test_order_and_label_numbers_do_not_count(isa_same):
     assert isa_same.kernels(old)[A] != isa_same.kernels(old)[B]
 
 
+def test_label_comment_column_does_not_count(isa_same):
+    """The printer pads a block label's comment to a fixed column: a function number with one more digit leaves one blank fewer."""
+    old = listing(kernel(A, 9), kernel(B, 99))
+    new = listing(kernel(A, 10).replace(".LBB10_1:  ", ".LBB10_1: "), kernel(B, 100).replace(".LBB100_1:  ", ".LBB100_1: "))
+    assert ".LBB10_1:   " in new and ".LBB10_1:" + " " * 31 + ";" in new and ".LBB9_1:" + " " * 32 + ";" in old
+    assert isa_same.compare(old, new) == (True, 2, [], [], [])
+    # (blanks elsewhere still count: an instruction's operands are not a label's comment)
+    assert isa_same.compare(old, listing(kernel(A, 9).replace("v0, v0, v1", "v0,  v0, v1"), kernel(B, 99))) == (False, 2, [A], [], [])
+
+
 def test_one_changed_operand_names_its_kernel(isa_same):
     old = listing(kernel(A, 0), kernel(B, 1))
     assert isa_same.compare(old, listing(kernel(A, 0), kernel(B, 1, operand="v3"))) == (False, 2, [B], [], [])

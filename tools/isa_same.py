@@ -7,7 +7,9 @@ the same set of kernel symbols, and for every kernel the same text from its entr
 .amdhsa_kernel ... .end_amdhsa_kernel block (the code, then registers, LDS, scratch and kernel-argument sizes).  The order of the
 kernels in a file follows the order in which the host code names them, and the compiler numbers its labels by that order
 (.LBB<function>_<block>, .Lfunc_end<function>), so the function number is taken out of every such label and of every mention of
-one before the texts are compared; nothing else is.  Text only: the tool knows no instruction.
+one before the texts are compared.  The printer sets a block label's comment at a fixed column, so the blanks between the two
+follow the label's length — one fewer where the function number gains a digit; that run of blanks is made one.  Nothing else is
+taken out.  Text only: the tool knows no instruction.
 
 Prints one verdict line, above it the names of kernels that differ or are in one listing only; exit status 1 on any difference."""
 import re
@@ -18,6 +20,7 @@ _END = re.compile(r"^\.Lfunc_end\d+:")
 _KERNEL = re.compile(r"^\s*\.amdhsa_kernel\s+(\S+)")
 _BLOCK = re.compile(r"(\.L|\b)BB\d+_(\d+)")                        # .LBB3_7 and, in comments, BB3_7
 _FUNC = re.compile(r"\.Lfunc_(begin|end)\d+")
+_PAD = re.compile(r"^(\.LBB_\d+:)[ \t]+;", re.M)                   # a block label (number taken out) and its comment
 
 
 def kernels(text):
@@ -36,7 +39,7 @@ def kernels(text):
                 if kernel != name or name in out:
                     raise ValueError("kernel %s: descriptor of %s, or listed twice" % (name, kernel))
                 body = "\n".join(l.rstrip() for l in lines)
-                out[name] = _FUNC.sub(r".Lfunc_\1", _BLOCK.sub(r"\1BB_\2", body))
+                out[name] = _PAD.sub(r"\1 ;", _FUNC.sub(r".Lfunc_\1", _BLOCK.sub(r"\1BB_\2", body)))
             name = None
             continue
         lines.append(line)
