@@ -781,8 +781,9 @@ int knn_index_list_within_masked_routed(knn_index *idx, int slot, int m, const f
  * knn_debug_cluster_unite: the kernels' own find / unite lines (knn_cluster_uf.h) with the host's atomics, one unite per pair, in
  * order, on parent [n] (on entry parent[x] <= x, e.g. parent[x] = x; pairs of rows 0 .. n - 1).
  *
- * Not built: the cell-pruned way; clusters across shards (merging the ranks' components); a radius per row; compact numbering on
- * the device; a mask of admitted rows; evaluating a pair once for both rows (each sweep still meets a pair from either side). */
+ * Not built: clusters across shards (merging the ranks' components); a radius per row; compact numbering on the device; a mask of
+ * admitted rows; evaluating a pair once for both rows (each sweep still meets a pair from either side).  (The cell-pruned way:
+ * 2n.) */
 #define KNN_CLUSTER_NOISE (-1)
 int knn_index_self_cluster_within(knn_index *idx, int slot, float max_dist2, int min_pts, int *labels_dev /*[n_local]*/,
                                   unsigned *core_dev /*[(n_local+31)/32] or NULL*/, void *stream, unsigned flags);
@@ -790,6 +791,67 @@ int knn_index_self_cluster_within_host(knn_index *idx, float max_dist2, int min_
                                        unsigned char *core_host /*[n_local] or NULL*/, long long info[4] /*NULL ok*/);
 int knn_debug_cluster_plan(const long long in[], long long out[]);   /* host arithmetic only */
 int knn_debug_cluster_unite(int *parent, long long n, const int *pairs /*[npairs][2]*/, long long npairs);
+
+/* ------------------------------------------------------------------------
+ * 2n. Clusters on the routed ways: 2m's call with the cell-pruned scan as a third way, on request.  2m's two ways leave a k = 8 .. 32
+ * shard in a cell-sorted layout with an O(n^2) clustering call; here its degree step and its link sweep both run in passes of 1024
+ * own rows on the cell-pruned scan (KNN_QUERY_COUNT_CELLS), as 2k's routed count does.  2m's call stays as it is.
+ *
+ * The answer is 2m's, word for word: degree, symmetry, core, core labels (the smallest core local row of the component), border
+ * rows (the label of the core row with the smallest packed key: E's bits, local row), noise, labels as LOCAL rows on every index,
+ * core_dev in 2g's format, min_pts == 1 the connected components.  It depends neither on the way nor on thread timing: for every
+ * input the labels and the core mask equal 2m's bit for bit.
+ *
+ * Flags: KNN_QUERY_COUNT_GRID and KNN_QUERY_COUNT_CELLS; anything else, KNN_QUERY_INIT_KEYS included, is KNN_EINVAL.  The way is the
+ * one knn_index_self_count_within_routed takes for the shard's rows at cap = max_dist2 under the same flags and options
+ * (knn_count_route, its precedence for a call that carries both flags included; knn_debug_count_plan describes it), and both the
+ * degree step and the link sweep take it.  Without a flag, or with the grid flag alone, the call launches exactly what 2m's call
+ * launches.  The cell-pruned way (4) needs all of: a finite max_dist2, a one-frame cell-sorted layout (fp16 rows without per-cell
+ * frames, or 8-bit rows in bin frames), k <= 32, at least 5 rows, "path" 0 or 2, "cells" not 2.  A cell-range shard takes it as the
+ * routed count does; its labels stay local rows.
+ *
+ * The link sweep on way 4, per pass of <= 1024 own rows first .. first + m - 1: the count pass's front unchanged (prep, match,
+ * record-only scan, Q = R + first * k), then the link re-rank of the records and the link kernel of the layout's out-of-box rows.
+ * A hit is a pair (own = first + query, row) with E finite, E <= max_dist2 and row != own; both core and row < own: unite(row,
+ * own); own not core and row core: (E's bits, row) is folded into own's border key.  A pass unites exactly the pairs whose LARGER
+ * row it owns and sets exactly its own rows' border keys, so it is self-contained: a pass that raises FALLBACK (a row nothing
+ * bounds — far outside the box, or with a non-finite coordinate —, an over-full record list) is swept whole by the gated exact
+ * link kernel over its own window, over whatever the record kernels left (unite and the key's minimum are idempotent: nothing is
+ * committed), and touches no other pass.  knn_index_last_stats: [0] = 1 / 3 / 4; on way 4 [1], [2], [3] are 2d's for the LAST pass
+ * that ran (the link sweep's last).  Scratch: 2m's (8 bytes per row, and the mask's words when core_dev is NULL) and the routed
+ * count's 4 bytes per row, the slot's, grown on demand.
+ *
+ * Argument errors: 2m's rules in 2m's order, each text prefixed by the function's name — max_dist2 < 0 or NaN, an unknown flag
+ * ("unknown flag (KNN_QUERY_COUNT_GRID, KNN_QUERY_COUNT_CELLS)"), a slot outside 0 .. 7, min_pts < 1, a null labels pointer, a null
+ * index, n_local > INT_MAX; the host form (2m's renumbering and info) skips the slot rule.  An empty shard succeeds and writes
+ * nothing.
+ *
+ * Measured (MI355X, uniform rows, min_pts 5, the radius the median 10th-neighbour distance; profiles/cluster_cells_timing.txt):
+ * medians of 5 calls, the whole call (degree step + link sweep with core and flatten), way 4 against way 1 of the same index —
+ *   k 16, n 2^18:   55.048 ms (27.048 + 28.000) against  158.259 ms (  68.390 +   89.869)
+ *   k 16, n 2^20:  182.707 ms (89.209 + 93.498) against 2746.771 ms (1140.563 + 1606.208)
+ *   k  8, n 2^20:  104.167 ms (50.174 + 53.993) against 3230.807 ms (1275.537 + 1955.270)
+ * way 4 was faster at every shape (2.87 x, 15.03 x, 31.02 x); labels and core masks equal; no pass fell back.  The link sweep keeps
+ * the degree step's ratio (link 3.21 x, 17.18 x, 36.21 x against degree 2.53 x, 12.79 x, 25.42 x).  Dense blobs were not measured.
+ *
+ * Test hooks, host arithmetic only.  knn_debug_cluster_routed_plan: in = knn_debug_count_plan's sixteen inputs with m = the shard's
+ * rows (<= INT_MAX), then 1 if core_dev is given; out = {the way (1 / 3 / 4), passes and the first pass's rows (way 4), kernel
+ * launches of the whole call on that way — ways 1 and 3: knn_debug_cluster_plan's; way 4: per pass of the degree step prep, match,
+ * scan, the count re-rank of the slices and of the overflow area, commit, the gated self-scan (7), core, per pass of the link sweep
+ * the same front, the link re-rank of the slices and of the overflow area, the gated twin (6), flatten —, the same when the layout
+ * has out-of-box rows (one more launch per pass in each sweep), bytes of the slot's cluster scratch, bytes of its count scratch on
+ * this way, chunks of the exact link sweep}.  knn_debug_cluster_pair: the link kernels' own decision lines (knn_cluster_pair.h)
+ * for one hit — *action = 0 nothing, 1 unite, 2 border key — from (own core, row core, row, own).
+ *
+ * Not built: a default policy (way 4 stays on request until someone decides from profiles/cluster_cells_timing.txt); skipping the
+ * degree step when min_pts is 1; one pass front for both sweeps (the core bits need every degree first); clusters across shards, a
+ * radius per row, a mask of admitted rows, per-cell-framed layouts, compact numbering on the device, evaluating a pair once. */
+int knn_index_self_cluster_within_routed(knn_index *idx, int slot, float max_dist2, int min_pts, int *labels_dev /*[n_local]*/,
+                                         unsigned *core_dev /*[(n_local+31)/32] or NULL*/, void *stream, unsigned flags);
+int knn_index_self_cluster_within_routed_host(knn_index *idx, float max_dist2, int min_pts, unsigned flags, int *labels_host /*[n_local]*/,
+                                              unsigned char *core_host /*[n_local] or NULL*/, long long info[4] /*NULL ok*/);
+int knn_debug_cluster_routed_plan(const long long in[], long long out[]);   /* host arithmetic only */
+int knn_debug_cluster_pair(int own_core, int row_core, long long row, long long own, int *action);
 
 /* Tuning / test hooks.  Known names:
  *   "path"    0 = auto, 1 = exact VALU kernels only, 2 = force the MFMA filter

@@ -29,6 +29,7 @@ __all__ = ["lib", "lib_path", "cudaCallback", "KnnIndex", "KnnGeom", "KnnError",
            "self_count_within_routed_c", "self_list_within_routed_c", "self_list_within_routed_host_c", "debug_self_routed_plan",
            "count_within_masked_routed_c", "list_within_masked_routed_c",
            "self_cluster_within_c", "self_cluster_within_host_c", "debug_cluster_plan", "debug_cluster_unite", "CLUSTER_NOISE",
+           "self_cluster_within_routed_c", "self_cluster_within_routed_host_c", "debug_cluster_routed_plan", "debug_cluster_pair",
            "debug_match_tests"]
 
 KEY_INIT = 0x7F80000000000000
@@ -63,6 +64,8 @@ EXPORTED_SYMBOLS = [
     "knn_debug_self_routed_plan",
     "knn_index_count_within_masked_routed", "knn_index_list_within_masked_routed",
     "knn_index_self_cluster_within", "knn_index_self_cluster_within_host", "knn_debug_cluster_plan", "knn_debug_cluster_unite",
+    "knn_index_self_cluster_within_routed", "knn_index_self_cluster_within_routed_host", "knn_debug_cluster_routed_plan",
+    "knn_debug_cluster_pair",
     "knn_debug_cells_fetch", "knn_debug_match_tests",
 ]
 TOPK_LARGE_MAX = 4096   # KNN_TOPK_LARGE_MAX
@@ -845,6 +848,47 @@ def debug_cluster_unite(parent, pairs):
     return parent
 
 
+def self_cluster_within_routed_c():
+    """knn_index_self_cluster_within_routed with its argument types (set here, not in lib(), as count_within_c)."""
+    f = lib().knn_index_self_cluster_within_routed
+    f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                  ctypes.c_uint]
+    return f
+
+
+def self_cluster_within_routed_host_c():
+    f = lib().knn_index_self_cluster_within_routed_host
+    f.argtypes = [ctypes.c_void_p, ctypes.c_float, ctypes.c_int, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p,
+                  ctypes.POINTER(ctypes.c_longlong)]
+    return f
+
+
+CLUSTER_ROUTED_PLAN = ("way", "passes", "pass_m", "launches", "launches_outliers", "scratch_bytes", "count_bytes", "chunks")
+PAIR_ACTIONS = ("nothing", "unite", "border")
+
+
+def debug_cluster_routed_plan(core_given=1, **inputs):
+    """knn_debug_cluster_routed_plan: which way answers a self_cluster_within_routed call and what the whole call launches, for the
+    inputs named in COUNT_PLAN_INPUTS (m: the shard's rows, equal to n) and core_given (the caller passes core_dev); the outputs
+    are named in CLUSTER_ROUTED_PLAN.  Host arithmetic; works without a GPU."""
+    vin = (ctypes.c_longlong * (len(COUNT_PLAN_INPUTS) + 1))(*([int(inputs[n]) for n in COUNT_PLAN_INPUTS] + [int(core_given)]))
+    out = (ctypes.c_longlong * len(CLUSTER_ROUTED_PLAN))()
+    f = lib().knn_debug_cluster_routed_plan
+    f.argtypes = [ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)]
+    _check(f(vin, out))
+    return dict(zip(CLUSTER_ROUTED_PLAN, list(out)))
+
+
+def debug_cluster_pair(own_core, row_core, row, own):
+    """knn_debug_cluster_pair: what the cell-pruned way's link kernels do with the hit (own, row) — one of PAIR_ACTIONS —, by their
+    own lines (knn_cluster_pair.h) compiled for the host.  Works without a GPU."""
+    action = ctypes.c_int(-1)
+    f = lib().knn_debug_cluster_pair
+    f.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.POINTER(ctypes.c_int)]
+    _check(f(int(own_core), int(row_core), int(row), int(own), ctypes.byref(action)))
+    return PAIR_ACTIONS[action.value]
+
+
 def self_list_within_routed_host_c():
     f = lib().knn_index_self_list_within_routed_host
     f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_uint, ctypes.c_void_p,
@@ -1452,6 +1496,27 @@ class KnnIndex:
         info = (ctypes.c_longlong * 4)()
         _check(self_cluster_within_host_c()(self._h, float(max_dist2), int(min_pts), (QUERY_COUNT_GRID if grid else 0) | int(flags),
                                             labels.ctypes.data_as(ctypes.c_void_p), core.ctypes.data_as(ctypes.c_void_p), info))
+        return labels, core.astype(bool), dict(zip(("clusters", "core", "border", "noise"), list(info)))
+
+    def self_cluster_within_routed(self, max_dist2, min_pts, labels_dev, core_dev=None, slot=0, stream=0, grid=False, cells=False,
+                                   flags=0):
+        """Async (knn_index_self_cluster_within_routed): self_cluster_within's answer, bit for bit, on the way the routed self count
+        takes for the shard's rows at cap = max_dist2 — grid asks for the grid index (QUERY_COUNT_GRID), cells for the cell-pruned
+        scan (QUERY_COUNT_CELLS), without either the exact self-scan.  flags: further flag bits as they are (every one raises)."""
+        _check(self_cluster_within_routed_c()(self._h, int(slot), float(max_dist2), int(min_pts), ctypes.c_void_p(int(labels_dev)),
+                                              ctypes.c_void_p(int(core_dev)) if core_dev is not None else None,
+                                              ctypes.c_void_p(stream),
+                                              (QUERY_COUNT_GRID if grid else 0) | (QUERY_COUNT_CELLS if cells else 0) | int(flags)))
+
+    def self_cluster_within_routed_host(self, max_dist2, min_pts, grid=False, cells=False, flags=0):
+        """Synchronous (knn_index_self_cluster_within_routed_host): self_cluster_within_host's (labels, core, info) on the routed ways."""
+        n = int(self.n)
+        labels = np.empty(n, dtype=np.int32)
+        core = np.zeros(n, dtype=np.uint8)
+        info = (ctypes.c_longlong * 4)()
+        _check(self_cluster_within_routed_host_c()(self._h, float(max_dist2), int(min_pts),
+                                                   (QUERY_COUNT_GRID if grid else 0) | (QUERY_COUNT_CELLS if cells else 0) | int(flags),
+                                                   labels.ctypes.data_as(ctypes.c_void_p), core.ctypes.data_as(ctypes.c_void_p), info))
         return labels, core.astype(bool), dict(zip(("clusters", "core", "border", "noise"), list(info)))
 
     def self_list_within_routed_host(self, cap, max_dist2=None, grid=False, cells=False, flags=0):

@@ -14,6 +14,7 @@
 #include "knn_self_window.h"
 #include "knn_each_radius.h"
 #include "knn_cluster_uf.h"
+#include "knn_cluster_pair.h"
 
 #include <limits.h>
 #include <math.h>
@@ -2093,11 +2094,22 @@ static int cluster_check(const char *who, float max_dist2, unsigned flags)
     return KNN_OK;
 }
 
-int knn_index_self_cluster_within(knn_index *idx, int slot, float max_dist2, int min_pts, int *labels_dev, unsigned *core_dev,
-                                  void *stream, unsigned flags)
+// 2n's flag rule: the two flags of the routed count, and no INIT_KEYS — the call always writes its labels.
+constexpr unsigned kClusterRoutedFlags = KNN_QUERY_COUNT_GRID | KNN_QUERY_COUNT_CELLS;
+static int cluster_routed_check(const char *who, float max_dist2, unsigned flags)
 {
-    const char *const who = "knn_index_self_cluster_within";
-    KNN_TRY(cluster_check(who, max_dist2, flags));
+    if (!(max_dist2 >= 0.0f))
+        return fail_in(KNN_EINVAL, who, "max_dist2 must be >= 0 and not NaN");
+    if ((flags & ~kClusterRoutedFlags) != 0u)
+        return fail_in(KNN_EINVAL, who, "unknown flag (KNN_QUERY_COUNT_GRID, KNN_QUERY_COUNT_CELLS)");
+    return KNN_OK;
+}
+
+// A device cluster call behind its radius and flag rules (2m's or 2n's, which decide the flags that can reach this): the rest of
+// the ladder, then degrees -> core -> the link sweep of the degree step's way -> flatten.
+static int cluster_run(const char *who, knn_index *idx, int slot, float max_dist2, int min_pts, int *labels_dev, unsigned *core_dev,
+                       void *stream, unsigned flags)
+{
     if (slot < 0 || slot >= KNN_SLOTS)
         return fail_in(KNN_EINVAL, who, "slot outside 0 .. 7");
     if (min_pts < 1)
@@ -2143,11 +2155,68 @@ int knn_index_self_cluster_within(knn_index *idx, int slot, float max_dist2, int
         HIP_TRY(knn_grid_cluster_link(idx->grid, cp.rmax, slot, c, &gate));
         idx->grid_topk_gate = gate;   // (the degree batch's walks are the same walks: both words say the same)
         HIP_TRY(knn_cluster_link_launch(c, gate));
+    } else if (idx->stats[0] == (long long)QueryWay::Cells) {   // (2n alone: 2m's flag rule admits no KNN_QUERY_COUNT_CELLS)
+        const CellTopkPlan tp = knn_cells_count_plan(route_inputs(idx, n, 1, 0u).t);
+        if (!tp.use)
+            return fail_in(KNN_EHIP, who, "the cell-pruned scan has no pass shape for this layout");
+        HIP_TRY(knn_filter_cluster_link_cells(idx->filter, tp, slot, c));
     } else {
         HIP_TRY(knn_cluster_link_launch(c, nullptr));
     }
     // 3. forest -> labels
     HIP_TRY(knn_cluster_flatten_launch(c));
+    return KNN_OK;
+}
+
+int knn_index_self_cluster_within(knn_index *idx, int slot, float max_dist2, int min_pts, int *labels_dev, unsigned *core_dev,
+                                  void *stream, unsigned flags)
+{
+    const char *const who = "knn_index_self_cluster_within";
+    KNN_TRY(cluster_check(who, max_dist2, flags));
+    return cluster_run(who, idx, slot, max_dist2, min_pts, labels_dev, core_dev, stream, flags);
+}
+
+// ---- 2n. Clusters on the routed ways: 2m's answer, the cell-pruned way on request (knn_cluster_routed.hip) -------------------------
+int knn_index_self_cluster_within_routed(knn_index *idx, int slot, float max_dist2, int min_pts, int *labels_dev, unsigned *core_dev,
+                                         void *stream, unsigned flags)
+{
+    const char *const who = "knn_index_self_cluster_within_routed";
+    KNN_TRY(cluster_routed_check(who, max_dist2, flags));
+    return cluster_run(who, idx, slot, max_dist2, min_pts, labels_dev, core_dev, stream, flags);
+}
+
+int knn_debug_cluster_pair(int own_core, int row_core, long long row, long long own, int *action)
+{
+    if ((own_core != 0 && own_core != 1) || (row_core != 0 && row_core != 1) || row < 0 || own < 0 || row > INT_MAX || own > INT_MAX || !action)
+        return fail(KNN_EINVAL, "knn_debug_cluster_pair: bad arguments (core bits 0 or 1, 0 <= row, own <= INT_MAX, no null action)");
+    *action = knn_cluster_pair(own_core != 0, row_core != 0, row, own);   // the kernels' own lines (knn_cluster_pair.h)
+    return KNN_OK;
+}
+
+int knn_debug_cluster_routed_plan(const long long in[], long long out[])
+{
+    // in = knn_debug_count_plan's sixteen with m = the shard's rows, then 1 if the caller passes core_dev
+    const char *const bad = "knn_debug_cluster_routed_plan: bad arguments (knn_debug_count_plan's with m = the shard's rows <= INT_MAX, "
+                            "core_dev given 0 or 1)";
+    if (!in || !out || in[1] != in[2] || in[2] > INT_MAX || (in[16] != 0 && in[16] != 1))
+        return fail(KNN_EINVAL, bad);
+    long long cnt[8];
+    if (knn_debug_count_plan(in, cnt) != KNN_OK)
+        return fail(KNN_EINVAL, bad);
+    const long long way = cnt[0], n = in[2];
+    const ClusterPlan p = knn_cluster_plan(n, (int)in[14], in[16] == 0);
+    long long launches = way == 3 ? p.launches_grid : p.launches_exact, with_outliers = launches;
+    if (way == 4) {
+        // per pass of the degree step: prep, match, record-only scan, count re-rank of the slices and of the overflow area, commit,
+        // the gated self-scan (a pass's rows are one chunk) = 7; per pass of the link sweep: the same front, the link re-rank of the
+        // slices and of the overflow area, the gated twin = 6; core and flatten.  A layout with out-of-box rows: one more in each.
+        const long long gated = knn_divup(std::min<long long>(n, KNN_CELL_BATCH), KNN_TOPK_CHUNK);
+        launches = cnt[1] * (11 + 2 * gated) + 2;
+        with_outliers = launches + 2 * cnt[1];
+    }
+    const long long v[8] = {way, cnt[1], cnt[2], launches, with_outliers, (long long)p.scratch_bytes,
+                            way == 1 ? 0 : (long long)p.count_bytes, p.chunks};
+    memcpy(out, v, sizeof v);
     return KNN_OK;
 }
 
@@ -3176,11 +3245,11 @@ extern "C" int knn_index_self_list_within_routed_host(knn_index *idx, const floa
 
 // The clusters of the whole shard on the host: the device call on the default stream, then the renumbering — clusters 0 .. C - 1 in
 // ascending order of their representative row (the smallest core row: the label the device call gives) — and the tallies.
-extern "C" int knn_index_self_cluster_within_host(knn_index *idx, float max_dist2, int min_pts, unsigned flags, int *labels_host,
-                                                  unsigned char *core_host, long long info[4])
+// (behind the entry's radius and flag rules; device_call: the entry's device twin)
+typedef int (*ClusterDeviceCall)(knn_index *, int, float, int, int *, unsigned *, void *, unsigned);
+static int cluster_host_run(const char *who, ClusterDeviceCall device_call, knn_index *idx, float max_dist2, int min_pts, unsigned flags,
+                            int *labels_host, unsigned char *core_host, long long info[4])
 {
-    const char *const who = "knn_index_self_cluster_within_host";
-    KNN_TRY(cluster_check(who, max_dist2, flags));
     if (min_pts < 1)
         return fail_in(KNN_EINVAL, who, "min_pts < 1");
     if (!labels_host)
@@ -3204,7 +3273,7 @@ extern "C" int knn_index_self_cluster_within_host(knn_index *idx, float max_dist
             e = stage.get(&core_dev, words * sizeof(unsigned));
         if (e != hipSuccess)
             return fail_in(KNN_EHIP, who, "staging labels", hipGetErrorString(e));
-        const int rv = knn_index_self_cluster_within(idx, 0, max_dist2, min_pts, labels_dev, core_dev, nullptr, flags);
+        const int rv = device_call(idx, 0, max_dist2, min_pts, labels_dev, core_dev, nullptr, flags);
         if (rv != KNN_OK)
             return rv;
         std::vector<unsigned> core(words);
@@ -3233,6 +3302,22 @@ extern "C" int knn_index_self_cluster_within_host(knn_index *idx, float max_dist
     if (info)
         memcpy(info, tally, sizeof tally);
     return KNN_OK;
+}
+
+extern "C" int knn_index_self_cluster_within_host(knn_index *idx, float max_dist2, int min_pts, unsigned flags, int *labels_host,
+                                                  unsigned char *core_host, long long info[4])
+{
+    const char *const who = "knn_index_self_cluster_within_host";
+    KNN_TRY(cluster_check(who, max_dist2, flags));
+    return cluster_host_run(who, knn_index_self_cluster_within, idx, max_dist2, min_pts, flags, labels_host, core_host, info);
+}
+
+extern "C" int knn_index_self_cluster_within_routed_host(knn_index *idx, float max_dist2, int min_pts, unsigned flags, int *labels_host,
+                                                         unsigned char *core_host, long long info[4])
+{
+    const char *const who = "knn_index_self_cluster_within_routed_host";
+    KNN_TRY(cluster_routed_check(who, max_dist2, flags));
+    return cluster_host_run(who, knn_index_self_cluster_within_routed, idx, max_dist2, min_pts, flags, labels_host, core_host, info);
 }
 
 extern "C" int knn_index_list_within_masked_host(knn_index *idx, int m, const float *queries_host, float max_dist2,

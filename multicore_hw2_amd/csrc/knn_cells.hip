@@ -3217,6 +3217,28 @@ hipError_t knn_cells_query_count(FilterState &st, FilterWorkspace &w, const Cell
     return knn_gated_count_launch(call, w.ctl_cur + KNN_CTL_FALLBACK);
 }
 
+// One pass of <= KNN_CELL_BATCH own rows of a cluster call's link sweep (knn_index_self_cluster_within_routed with
+// KNN_QUERY_COUNT_CELLS; DESIGN §4.6 "Clusters on the cell-pruned way"): the count pass unchanged up to its finish — count prep ->
+// match -> record-only scan, Q = R + first * k —, then the link re-rank of the slices and of the shared overflow area -> out-of-box
+// rows (knn_cluster_routed.hip; nothing to commit) -> the exact link sweep of the pass's window, gated on FALLBACK.
+hipError_t knn_cells_cluster_link(FilterState &st, FilterWorkspace &w, const CellTopkPlan &tp, bool timed, const ClusterPass &pass)
+{
+    const CellIndex &c = *st.cells;
+    const CellQueryPlan &p = tp.batch;
+    const ClusterCall &call = pass.c;
+    const int m = pass.m;
+    if (!tp.use || m < 1 || m > tp.pass_m || tp.scan.self || tp.scan.ctr || c.centred || p.prep_ctr || !(call.max_dist2 < INFINITY) ||
+        call.n != st.n || call.k != st.k || pass.first < 0 || pass.first + m > call.n)
+        return hipErrorInvalidValue;
+    const SeedLayer no_layer = {nullptr, 0u, 0u, 0u, 0ull, {0u}};
+    CellBatch b{st, c, w, p, m, call.r + (size_t)pass.first * call.k, call.r, 0ll, nullptr, nullptr, CellFinal{nullptr, nullptr, 0}, no_layer,
+                call.stream, 1, call.max_dist2};
+    FTRY(cells_pass_front(w, b, cells_records_kernel(tp.scan), CellPrepForm::Count, timed));
+    FTRY(knn_cluster_link_records_finish(pass, cells_pass_records(st, w)));
+    // gated: the exact sweep of the window answers a pass that raised FALLBACK, over whatever the record kernels left
+    return knn_cluster_link_window_launch(call, pass.first, m, w.ctl_cur + KNN_CTL_FALLBACK);
+}
+
 // One pass of <= KNN_CELL_BATCH queries of a list call (knn_index_list_within with KNN_QUERY_COUNT_CELLS; DESIGN §4.6 "Lists within
 // a radius"): the count pass unchanged up to its finish — count prep -> match -> record-only scan —, then the list re-rank of the
 // slices and of the shared overflow area -> out-of-box rows, all reserving in call.scratch (on entry a copy of call.fill) and

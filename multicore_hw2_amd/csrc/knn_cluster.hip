@@ -192,6 +192,25 @@ hipError_t knn_cluster_link_launch(const ClusterCall &c, const unsigned *gate)
     });
 }
 
+// The gated twin for a pass of the cell-pruned way (knn_cluster_routed.hip): the same kernel over the window's chunks.
+hipError_t knn_cluster_link_window_launch(const ClusterCall &c, long long first, int m, const unsigned *gate)
+{
+    if (!cluster_call_ok(c) || !gate || first < 0 || m < 1 || first + m > c.n)
+        return hipErrorInvalidValue;
+    hipStream_t s = c.stream;
+    return knn_slice_chunks(m, c.n, c.num_cu, KnnCountSlices{}, [&](const SliceChunk &ch) {
+        const int mc = ch.mc;
+        const long long c0 = first + ch.c0, per = ch.per;
+        const dim3 grid = ch.grid, block(KNN_WAVE);
+#define KNN_CLUSTER_LINK(KCV)                                                                                                    \
+    hipLaunchKernelGGL(knn_cluster_link_gated_kernel<KCV>, grid, block, 0, s, c.r, c.k, c0, mc, c.n, per, c.max_dist2, c.parent, \
+                       (const unsigned *)c.core, c.best, gate)
+        KNN_KC_SWITCH(c.k, KNN_CLUSTER_LINK)
+#undef KNN_CLUSTER_LINK
+        return hipGetLastError();
+    });
+}
+
 hipError_t knn_cluster_flatten_launch(const ClusterCall &c)
 {
     if (!cluster_call_ok(c))

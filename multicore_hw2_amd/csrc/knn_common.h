@@ -984,6 +984,22 @@ hipError_t knn_cluster_link_launch(const ClusterCall &c, const unsigned *gate);
 hipError_t knn_grid_cluster_link(const GridState *gs, int rmax, int slot, const ClusterCall &c, const unsigned **gate_out);
 // parent -> labels: a core row's root, a border row's (c.best[i] holds a key) nearest core row's root, -1 for every other row.
 hipError_t knn_cluster_flatten_launch(const ClusterCall &c);
+// The link sweep on the cell-pruned way (include/knn_mi355x.h 2n; knn_cluster_routed.hip): one pass of <= KNN_CELL_BATCH own rows.
+struct ClusterPass {
+    ClusterCall c;
+    long long first = 0;   // the pass's first own row
+    int m = 0;             // its rows
+};
+// The exact sweep of the window of own rows first .. first + m - 1 against all c.n rows, gated (gate != nullptr): what
+// knn_cluster_link_launch does for the shard's rows, for a pass's.
+hipError_t knn_cluster_link_window_launch(const ClusterCall &c, long long first, int m, const unsigned *gate);
+// A pass behind its record-only scan: the link re-rank of the slices and of the shared overflow area, the out-of-box rows; no commit.
+hipError_t knn_cluster_link_records_finish(const ClusterPass &p, const TopkRecords &rs);
+// One pass: the count pass's front unchanged (Q = R + first * k) -> knn_cluster_link_records_finish -> the gated exact twin on the
+// pass's window.  tp: knn_cells_count_plan's pass shapes.
+hipError_t knn_cells_cluster_link(FilterState &st, FilterWorkspace &w, const CellTopkPlan &tp, bool timed, const ClusterPass &p);
+// The link sweep of the whole shard in passes of KNN_CELL_BATCH own rows (knn_cells_cluster_link).
+hipError_t knn_filter_cluster_link_cells(FilterState &st, const CellTopkPlan &tp, int slot, const ClusterCall &c);
 
 // ---- RCCL exchange step (knn_rccl.cpp; librccl is dlopen'ed at first use) -------------------
 #ifdef __cplusplus

@@ -2719,6 +2719,18 @@ hipError_t knn_filter_query_count_cells(FilterState &st, const CellTopkPlan &tp,
     return cell_passes(st, w, c.ev0, c.ev1, c.m, [&](int q0, int mb, bool first) { return knn_cells_query_count(st, w, tp, first, c.pass(q0, mb)); });
 }
 
+// The link sweep of a cluster call on the cell-pruned scan: every KNN_CELL_BATCH own rows a pass of their own (no events: the
+// call's dominant kernel was the degree step's).
+hipError_t knn_filter_cluster_link_cells(FilterState &st, const CellTopkPlan &tp, int slot, const ClusterCall &c)
+{
+    if (!st.cells || !tp.use || c.n < 1 || c.n > 0x7FFFFFFFll)
+        return hipErrorInvalidValue;
+    FilterWorkspace &w = st.ws[slot];
+    return cell_passes(st, w, nullptr, nullptr, (int)c.n, [&](int q0, int mb, bool first) {
+        return knn_cells_cluster_link(st, w, tp, first, ClusterPass{c, (long long)q0, mb});
+    });
+}
+
 hipError_t knn_filter_query_list_cells(FilterState &st, const CellTopkPlan &tp, int slot, const ListCall &c)
 {
     if (!st.cells || !tp.use || !c.scratch)
