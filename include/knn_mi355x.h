@@ -853,6 +853,92 @@ int knn_index_self_cluster_within_routed_host(knn_index *idx, float max_dist2, i
 int knn_debug_cluster_routed_plan(const long long in[], long long out[]);   /* host arithmetic only */
 int knn_debug_cluster_pair(int own_core, int row_core, long long row, long long own, int *action);
 
+/* ------------------------------------------------------------------------
+ * 2o. Minimum spanning forest of the shard's own rows (single linkage).  2m and 2n answer for ONE radius, fixed before the call;
+ * the minimum spanning tree holds all radii at once: the single-linkage dendrogram, the friends-of-friends groups at every linking
+ * length from one run, the backbone of HDBSCAN, the usual Euclidean-MST uses on point clouds.  The adjacency is never stored:
+ * Borůvka rounds on the index, each a scan whose hit path is "the nearest row of ANOTHER component", a pick per component and a
+ * hook (a lock-free union-find in the labels array itself, 2m's).
+ *
+ * The definition; the answer depends neither on the way nor on thread timing.
+ *   Graph.  Vertices are the shard's LOCAL rows.  Rows i < j are joined when their v0 distance E(i, j) is finite and <= max_dist2
+ *     — 2i's candidate rule word for word: fp32, accumulated in dimension order, no FMA, an fp32 compare with equality inside, -0
+ *     counts as 0, +INF means no radius (the complete graph of the rows with finite coordinates).  E(i, j) == E(j, i) bit for bit
+ *     (2m, "Symmetry").  A row with a non-finite coordinate has no edge.
+ *   Edge order.  Edges are ordered by the triple (E's bits as unsigned, i, j), i < j, lexicographically: a strict total order, so
+ *     the minimum spanning forest of the graph is UNIQUE — the set Kruskal accepts when it takes the edges in that order.  The call
+ *     returns exactly that set: n_local - C edges, C the connected components of the graph.
+ *   Labels.  labels_dev[i] = the smallest local row of i's component; for a finite radius, bit for bit, the labels of
+ *     knn_index_self_cluster_within at min_pts 1.
+ *   Labels and edge ends are LOCAL rows on every index, as in 2m.  n_local <= INT_MAX.
+ *
+ * The device call is asynchronous on `stream`, with no host round trip inside it.  Edge e, e < count_dev[0], is edge_keys_dev[e] =
+ * (E's bits << 32 | i) and edge_hi_dev[e] = j, i < j; the order of the edges is unspecified.  count_dev[0] = the number of edges,
+ * count_dev[1] = the number of rounds that added at least one.  Nothing is ever stored at or beyond entry n_local (a forest has at
+ * most n_local - 1 edges: the reserve-and-test is a guard, not an overflow contract).  labels_dev is also the call's working
+ * memory, as in 2m: its contents are the answer only once the call's work on `stream` is done.
+ *
+ * The rounds.  ROUNDS(n) = max(1, ceil(log2 n)); the call queues all of them, and every kernel of round t > 0 is gated on a device
+ * word that round t - 1 raises when it adds an edge, so a run that finishes early costs empty launches only.  One round: flatten
+ * (labels[i] = root(i), frozen until the hook); scan (per row the smallest key (E's bits, row) of a row of another component within
+ * the radius — for a fixed row that is also its smallest edge —; a row that finds none is done for good, components only grow);
+ * pick (per component the smallest offered edge: an atomic min of (E's bits << 32 | lo) on the root's slot, then of hi among the
+ * rows that match it); hook (every root with a pick appends its edge through one cursor and unites its ends; when the component at
+ * the other end picked the SAME edge only the one that holds `lo` appends, so every forest edge is stored exactly once).  Behind
+ * the last round one more flatten, gated on the word that round raised: a hook re-parents only the larger root, and when even the
+ * LAST queued round added an edge (rows paired at every level) no later round would bring the labels back to depth 1.
+ *
+ * Flags: KNN_QUERY_COUNT_GRID alone; every other flag, KNN_QUERY_INIT_KEYS and KNN_QUERY_COUNT_CELLS included, is KNN_EINVAL.  The way
+ * is the one knn_index_self_count_within_routed takes for the shard's rows at cap = max_dist2 under the flag and options: the grid
+ * way on a grid index (k <= 4) with the flag and option "path" 0 or 3, the exact self-scan everywhere else.  On the grid way a
+ * row's walk ends by the radius clause or by the 1-NN walk's clause on the best key so far; a row that passes the ring limit raises
+ * the round's give-up word, and that round's exact scan then runs over the whole shard (the candidate's atomic min is idempotent:
+ * nothing is committed).  An infinite radius with the flag is legal and simply ends on the exact scan.  knn_index_last_stats
+ * reports [0] = 1 or 3, [1] = 0, [2] = 1 when a grid round gave up (the last round that ran), [3] = 0.  Scratch, the slot's, grown
+ * on demand: 20 bytes and one bit per row, and 2 ROUNDS(n) + 2 words.
+ *
+ * Argument errors are KNN_EINVAL, each with its own knn_last_error text prefixed by the function's name, checked in this order —
+ * the first that fails speaks, nothing is launched —: max_dist2 < 0 or NaN, an unknown flag, a slot outside 0 .. 7, a null labels,
+ * edge-keys, edge-hi or count pointer, a null index, n_local > INT_MAX.  An empty shard succeeds and writes count_dev = {0, 0}.
+ *
+ * knn_index_self_forest_within_host: synchronous, the device call on the default stream, copied back, the edges SORTED ascending
+ * by (E, i, j) — the order single linkage merges in — into lo_host, hi_host and dist2_host (NULL ok), n_local entries each of which
+ * the first info[0] are written; labels_host [n_local] (NULL ok).  info (NULL ok) = {edges, components, rounds run, 1 if a grid
+ * round gave up}.  Errors, in this order: max_dist2, an unknown flag, a null lo or hi pointer, a null index, n_local > INT_MAX.
+ *
+ * Measured (MI355X, uniform rows, the radius the median 10th-neighbour distance; profiles/forest_timing.txt): medians of 5 calls, the
+ * whole call, against what a caller did before it — knn_index_self_list_within_routed_host under the same flag plus Kruskal over
+ * the CSR on the host (a numpy sort and a Python union-find in tools/forest_timing.py; in brackets scipy's minimum_spanning_tree
+ * in its place) —
+ *   k  3, n 2^20, the grid way:    14.433 ms against 3375.6 ms (list 67.8 + Kruskal 3307.7; scipy 946.9); 10 of 20 rounds added
+ *                                  edges; 21.1 MB of scratch and 16.8 MB of outputs beside an 89.7 MB CSR
+ *   k 16, n 2^16, the exact way:   30.640 ms against  163.5 ms (list 14.8 + Kruskal  148.8; scipy 128.9); 6 of 16 rounds
+ *   k 16, n 2^16, exact, +INF:     35.940 ms; no route before (a list call needs a radius)
+ * the sorted edge weights equal both routes' bit for bit.  The exact way at n 2^20, clustered rows, k 3 at +INF: not measured.
+ *
+ * Test hooks, host code only.  knn_debug_forest_plan: in = {k, the shard's rows, CUs, 1 if the grid way answers (k <= 4)}; out =
+ * {ROUNDS, chunks of 65536 rows of one round's exact scan, slices of its first chunk, kernel launches of the whole call on the exact
+ * way (per round: flatten, the scan's chunks, two offers, emit, hook; then the last flatten), the same on the grid way (one more per
+ * round: the grid scan; the exact scan's chunks are then gated on its give-up word), bytes of the slot's scratch, the way (1 / 3), the launches on this
+ * way}.  knn_debug_forest_round: ONE round's flatten, pick and hook by the kernels' own lines (knn_forest_pick.h,
+ * knn_cluster_uf.h) with the host's atomics, on parent [n] (on entry parent[x] <= x, e.g. parent[x] = x) and a candidate array
+ * cand [n] the caller made from the roots of `parent` (KNN_KEY_INIT: none); edges are appended at count[0], count[1] is raised when
+ * the round added one, *added = the edges this round added.  On ENTRY *added = the number of host threads that share every step's
+ * rows (below 2: the calling thread alone; at most 16), a join between two steps.  A call whose candidates are all KNN_KEY_INIT
+ * is the flatten alone — the device call's last step: parent[x] = root(x) for every x.
+ *
+ * Not built: the cell-pruned way (way 4) for k = 8 .. 32; forests across shards; mutual-reachability weights (HDBSCAN's core
+ * distances); the dendrogram or a cut of it on the device; a mask of admitted rows; a radius per row. */
+int knn_index_self_forest_within(knn_index *idx, int slot, float max_dist2, int *labels_dev /*[n_local]*/,
+                                 unsigned long long *edge_keys_dev /*[n_local]*/, unsigned *edge_hi_dev /*[n_local]*/,
+                                 unsigned *count_dev /*[2]*/, void *stream, unsigned flags);
+int knn_index_self_forest_within_host(knn_index *idx, float max_dist2, unsigned flags, int *labels_host /*[n_local] or NULL*/,
+                                      int *lo_host, int *hi_host /*[n_local] each*/, float *dist2_host /*[n_local] or NULL*/,
+                                      long long info[4] /*NULL ok*/);
+int knn_debug_forest_plan(const long long in[], long long out[]);   /* host arithmetic only */
+int knn_debug_forest_round(long long n, int *parent, const unsigned long long *cand, unsigned long long *edge_keys, unsigned *edge_hi,
+                           unsigned *count, int *added);
+
 /* Tuning / test hooks.  Known names:
  *   "path"    0 = auto, 1 = exact VALU kernels only, 2 = force the MFMA filter
  *             (+ exact re-rank) where its preconditions hold, 3 = the uniform-grid spatial index

@@ -30,6 +30,7 @@ __all__ = ["lib", "lib_path", "cudaCallback", "KnnIndex", "KnnGeom", "KnnError",
            "count_within_masked_routed_c", "list_within_masked_routed_c",
            "self_cluster_within_c", "self_cluster_within_host_c", "debug_cluster_plan", "debug_cluster_unite", "CLUSTER_NOISE",
            "self_cluster_within_routed_c", "self_cluster_within_routed_host_c", "debug_cluster_routed_plan", "debug_cluster_pair",
+           "self_forest_within_c", "self_forest_within_host_c", "debug_forest_plan", "debug_forest_round", "forest_rounds",
            "debug_match_tests"]
 
 KEY_INIT = 0x7F80000000000000
@@ -66,6 +67,7 @@ EXPORTED_SYMBOLS = [
     "knn_index_self_cluster_within", "knn_index_self_cluster_within_host", "knn_debug_cluster_plan", "knn_debug_cluster_unite",
     "knn_index_self_cluster_within_routed", "knn_index_self_cluster_within_routed_host", "knn_debug_cluster_routed_plan",
     "knn_debug_cluster_pair",
+    "knn_index_self_forest_within", "knn_index_self_forest_within_host", "knn_debug_forest_plan", "knn_debug_forest_round",
     "knn_debug_cells_fetch", "knn_debug_match_tests",
 ]
 TOPK_LARGE_MAX = 4096   # KNN_TOPK_LARGE_MAX
@@ -889,6 +891,64 @@ def debug_cluster_pair(own_core, row_core, row, own):
     return PAIR_ACTIONS[action.value]
 
 
+def self_forest_within_c():
+    """knn_index_self_forest_within with its argument types (set here, not in lib(), as count_within_c)."""
+    f = lib().knn_index_self_forest_within
+    f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                  ctypes.c_void_p, ctypes.c_uint]
+    return f
+
+
+def self_forest_within_host_c():
+    f = lib().knn_index_self_forest_within_host
+    f.argtypes = [ctypes.c_void_p, ctypes.c_float, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                  ctypes.POINTER(ctypes.c_longlong)]
+    return f
+
+
+FOREST_PLAN_INPUTS = ("k", "n", "num_cu", "grid")
+FOREST_PLAN = ("rounds", "chunks", "slices", "launches_exact", "launches_grid", "scratch_bytes", "way", "launches")
+
+
+def forest_rounds(n):
+    """ROUNDS(n) = max(1, ceil(log2 n)): the Borůvka rounds a self_forest_within call on n rows queues."""
+    return max(1, (int(n) - 1).bit_length())
+
+
+def debug_forest_plan(**inputs):
+    """knn_debug_forest_plan: what a self_forest_within call on a shard of n rows launches and the slot scratch it needs, for the
+    inputs named in FOREST_PLAN_INPUTS (grid: the grid way answers, k <= 4).  Host arithmetic; works without a GPU."""
+    vin = (ctypes.c_longlong * len(FOREST_PLAN_INPUTS))(*[int(inputs[n]) for n in FOREST_PLAN_INPUTS])
+    out = (ctypes.c_longlong * len(FOREST_PLAN))()
+    f = lib().knn_debug_forest_plan
+    f.argtypes = [ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)]
+    _check(f(vin, out))
+    return dict(zip(FOREST_PLAN, list(out)))
+
+
+def debug_forest_round(parent, cand, edge_keys, edge_hi, count, threads=1):
+    """knn_debug_forest_round: one Borůvka round's flatten, pick and hook by the kernels' own lines (knn_forest_pick.h,
+    knn_cluster_uf.h) with the host's atomics.  parent: int32 [n], changed IN PLACE (parent[x] <= x on entry); cand: uint64 [n],
+    row i's key (distance bits << 32 | row) of the nearest row of another component, KEY_INIT for none; edge_keys uint64 [n],
+    edge_hi uint32 [n] and count uint32 [2] receive the edges at count[0] on (count[1]: rounds that added one).  threads: host
+    threads that share every step's rows.  Returns the edges this round added.  Works without a GPU."""
+    for name, a, dt in (("parent", parent, np.int32), ("cand", cand, np.uint64), ("edge_keys", edge_keys, np.uint64),
+                        ("edge_hi", edge_hi, np.uint32), ("count", count, np.uint32)):
+        if not (isinstance(a, np.ndarray) and a.dtype == dt and a.flags.c_contiguous and a.ndim == 1):
+            raise ValueError("%s must be a contiguous one-dimensional %s array" % (name, np.dtype(dt).name))
+    n = parent.size
+    if cand.size != n or edge_keys.size < n or edge_hi.size < n or count.size != 2:
+        raise ValueError("cand [n], edge_keys and edge_hi [>= n], count [2]")
+    added = ctypes.c_int(int(threads))
+    f = lib().knn_debug_forest_round
+    f.argtypes = [ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                  ctypes.POINTER(ctypes.c_int)]
+    _check(f(n, parent.ctypes.data_as(ctypes.c_void_p), cand.ctypes.data_as(ctypes.c_void_p),
+             edge_keys.ctypes.data_as(ctypes.c_void_p), edge_hi.ctypes.data_as(ctypes.c_void_p),
+             count.ctypes.data_as(ctypes.c_void_p), ctypes.byref(added)))
+    return added.value
+
+
 def self_list_within_routed_host_c():
     f = lib().knn_index_self_list_within_routed_host
     f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_uint, ctypes.c_void_p,
@@ -1518,6 +1578,34 @@ class KnnIndex:
                                                    (QUERY_COUNT_GRID if grid else 0) | (QUERY_COUNT_CELLS if cells else 0) | int(flags),
                                                    labels.ctypes.data_as(ctypes.c_void_p), core.ctypes.data_as(ctypes.c_void_p), info))
         return labels, core.astype(bool), dict(zip(("clusters", "core", "border", "noise"), list(info)))
+
+    def self_forest_within(self, max_dist2, labels_dev, edge_keys_dev, edge_hi_dev, count_dev, stream=0, slot=0, grid=False, flags=0):
+        """Async (knn_index_self_forest_within): the minimum spanning forest of this shard's rows on the radius graph (max_dist2
+        may be inf: the spanning tree).  labels_dev: int32 [n], the smallest LOCAL row of every row's component; edge e <
+        count_dev[0] is edge_keys_dev[e] = (distance bits << 32 | i), edge_hi_dev[e] = j, i < j, in no particular order
+        (uint64 [n], uint32 [n]); count_dev: uint32 [2] = edges, rounds that added one.  grid asks for the grid index
+        (QUERY_COUNT_GRID); without it the exact self-scan.  flags: further flag bits as they are (every one of them raises)."""
+        _check(self_forest_within_c()(self._h, int(slot), float(max_dist2), ctypes.c_void_p(int(labels_dev)),
+                                      ctypes.c_void_p(int(edge_keys_dev)), ctypes.c_void_p(int(edge_hi_dev)),
+                                      ctypes.c_void_p(int(count_dev)), ctypes.c_void_p(stream),
+                                      (QUERY_COUNT_GRID if grid else 0) | int(flags)))
+
+    def self_forest_within_host(self, max_dist2, grid=False, flags=0, want_labels=True, want_dist2=True):
+        """Synchronous (knn_index_self_forest_within_host): (labels int32 [n] or None, lo int32 [edges], hi int32 [edges], dist2
+        float32 [edges] or None, info dict(edges, components, rounds, gave_up)), the edges sorted ascending by (distance, lo, hi):
+        the order single linkage merges in."""
+        n = int(self.n)
+        labels = np.empty(n, dtype=np.int32) if want_labels else None
+        lo = np.empty(n, dtype=np.int32)
+        hi = np.empty(n, dtype=np.int32)
+        dist2 = np.empty(n, dtype=np.float32) if want_dist2 else None
+        info = (ctypes.c_longlong * 4)()
+        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
+        _check(self_forest_within_host_c()(self._h, float(max_dist2), (QUERY_COUNT_GRID if grid else 0) | int(flags), ptr(labels),
+                                           ptr(lo), ptr(hi), ptr(dist2), info))
+        e = int(info[0])
+        return (labels, lo[:e].copy(), hi[:e].copy(), dist2[:e].copy() if want_dist2 else None,
+                dict(zip(("edges", "components", "rounds", "gave_up"), list(info))))
 
     def self_list_within_routed_host(self, cap, max_dist2=None, grid=False, cells=False, flags=0):
         """Synchronous radius graph of this shard on the routed self calls (knn_index_self_list_within_routed_host), in

@@ -15,6 +15,7 @@
 #include "knn_each_radius.h"
 #include "knn_cluster_uf.h"
 #include "knn_cluster_pair.h"
+#include "knn_forest_pick.h"
 
 #include <limits.h>
 #include <math.h>
@@ -345,6 +346,8 @@ struct knn_index {
         size_t self_bytes = 0;
         u64 *cluster = nullptr;    // knn_index_self_cluster_within: what knn_cluster_plan says (best [n_local], the core mask when the caller keeps none)
         size_t cluster_bytes = 0;
+        u64 *forest = nullptr;     // knn_index_self_forest_within: what knn_forest_plan says (candidates, picks, done bits, gate words)
+        size_t forest_bytes = 0;
     } topk[KNN_SLOTS];
     // Calls on one index from several host threads are serialised (enqueueing a batch is ~20 us of host work; the GPU
     // work of different slots still overlaps): the workspaces' lazily grown buffers, the event list, the statistics and
@@ -832,6 +835,7 @@ void knn_index_destroy(knn_index *idx)
             (void)knn_dev_free(t.mask);
             (void)knn_dev_free(t.self);
             (void)knn_dev_free(t.cluster);
+            (void)knn_dev_free(t.forest);
         }
         knn_dev_free_end_synced();
         for (auto &ev : idx->events) {
@@ -2251,6 +2255,138 @@ int knn_debug_cluster_unite(int *parent, long long n, const int *pairs, long lon
     return KNN_OK;
 }
 
+// ---- 2o. Minimum spanning forest of the radius graph (include/knn_mi355x.h 2o; knn_forest.hip, knn_grid.hip) ----------
+// (one message per rule, in the header's order; tests/test_forest_logic.py tells them apart without a GPU)
+constexpr unsigned kForestFlags = KNN_QUERY_COUNT_GRID;   // the one flag the forest calls admit
+static int forest_check(const char *who, float max_dist2, unsigned flags)
+{
+    if (!(max_dist2 >= 0.0f))
+        return fail_in(KNN_EINVAL, who, "max_dist2 must be >= 0 and not NaN");
+    if ((flags & ~kForestFlags) != 0u)
+        return fail_in(KNN_EINVAL, who, "unknown flag (KNN_QUERY_COUNT_GRID alone is admitted: the call always writes its outputs, and "
+                                        "the cell-pruned way is not built for it)");
+    return KNN_OK;
+}
+
+int knn_index_self_forest_within(knn_index *idx, int slot, float max_dist2, int *labels_dev, unsigned long long *edge_keys_dev,
+                                 unsigned *edge_hi_dev, unsigned *count_dev, void *stream, unsigned flags)
+{
+    const char *const who = "knn_index_self_forest_within";
+    KNN_TRY(forest_check(who, max_dist2, flags));
+    if (slot < 0 || slot >= KNN_SLOTS)
+        return fail_in(KNN_EINVAL, who, "slot outside 0 .. 7");
+    if (!labels_dev || !edge_keys_dev || !edge_hi_dev || !count_dev)
+        return fail_in(KNN_EINVAL, who, "null labels, edge keys, edge hi or count");
+    if (!idx)
+        return fail_in(KNN_EINVAL, who, "null index");
+    std::lock_guard<std::recursive_mutex> lock(idx->mu);
+    if (idx->n > INT_MAX)
+        return fail_in(KNN_EINVAL, who, "more than INT_MAX rows (labels and edge ends are int row numbers)");
+    DeviceGuard guard(idx->device);
+    if (!guard.ok)
+        return fail_in(KNN_EHIP, who, "hipSetDevice failed");
+    begin_call(idx, slot);
+    if (idx->n == 0) {   // an empty shard has no row and no edge
+        HIP_TRY(hipMemsetAsync(count_dev, 0, 2 * sizeof(unsigned), (hipStream_t)stream));
+        return KNN_OK;
+    }
+    const int n = (int)idx->n;
+    const ForestPlan plan = knn_forest_plan(idx->n, idx->num_cu);
+    knn_index::TopkSlot &ts = idx->topk[slot];
+    KNN_TRY(slot_buffer_grow(ts.forest, ts.forest_bytes, plan.scratch_bytes));   // the slot's scratch, grown before the first launch
+    ForestCall c;
+    c.k = idx->k;
+    c.n = idx->n;
+    c.r = idx->refs;
+    c.max_dist2 = max_dist2 == 0.0f ? 0.0f : max_dist2;   // (-0 counts as 0)
+    c.num_cu = idx->num_cu;
+    c.stream = (hipStream_t)stream;
+    c.labels = labels_dev;
+    c.edge_keys = edge_keys_dev;
+    c.edge_hi = edge_hi_dev;
+    c.count = count_dev;
+    knn_forest_layout(c, plan, ts.forest);
+    // the way the routed self count takes for the shard's rows at this cap under the call's flag
+    const CountPlan cp = count_plan_of(idx, route_inputs(idx, n, 1, 0u), n, c.max_dist2, flags);
+    const bool grid = cp.way == QueryWay::Grid;
+    idx->stats[0] = (long long)(grid ? QueryWay::Grid : QueryWay::Exact);
+    HIP_TRY(knn_forest_begin_launch(c, plan));
+    for (int t = 0; t < c.rounds; ++t) {
+        HIP_TRY(knn_forest_flatten_launch(c, t));
+        if (grid) {   // the walk, then the exact scan gated on the round's give-up word as well
+            HIP_TRY(knn_grid_forest_scan(idx->grid, cp.rmax, c, t));
+            HIP_TRY(knn_forest_scan_launch(c, t, c.giveup(t)));
+        } else {
+            HIP_TRY(knn_forest_scan_launch(c, t, nullptr));
+        }
+        HIP_TRY(knn_forest_pick_launch(c, t));
+    }
+    HIP_TRY(knn_forest_labels_launch(c));   // (the last round's hook left a forest: one more flatten when it added an edge)
+    if (grid)
+        idx->grid_topk_gate = c.stat();   // (the give-up word of the last round that ran)
+    return KNN_OK;
+}
+
+int knn_debug_forest_plan(const long long in[], long long out[])
+{
+    // in = {k, the shard's rows, CUs, 1 if the grid way answers}
+    if (!in || !out || in[0] < 1 || in[0] > INT_MAX || in[1] < 0 || in[1] > INT_MAX || in[2] < 1 || in[2] > INT_MAX ||
+        (in[3] != 0 && in[3] != 1) || (in[3] != 0 && in[0] > 4))
+        return fail(KNN_EINVAL, "knn_debug_forest_plan: bad arguments (k >= 1, 0 <= rows <= INT_MAX, CUs >= 1, grid way 0 or 1 and only "
+                                "with k <= 4)");
+    const ForestPlan p = knn_forest_plan(in[1], (int)in[2]);
+    const bool grid = in[3] != 0 && in[1] > 0;
+    const long long v[8] = {p.rounds, p.chunks, p.slices, p.launches_exact, p.launches_grid, (long long)p.scratch_bytes, grid ? 3 : 1,
+                            grid ? p.launches_grid : p.launches_exact};
+    memcpy(out, v, sizeof v);
+    return KNN_OK;
+}
+
+int knn_debug_forest_round(long long n, int *parent, const unsigned long long *cand, unsigned long long *edge_keys, unsigned *edge_hi,
+                           unsigned *count, int *added)
+{
+    if (n < 0 || n > INT_MAX || !count || !added || (n > 0 && (!parent || !cand || !edge_keys || !edge_hi)))
+        return fail(KNN_EINVAL, "knn_debug_forest_round: bad arguments (0 <= n <= INT_MAX, no null array)");
+    for (long long i = 0; i < n; ++i)
+        if (parent[i] < 0 || parent[i] > i)
+            return fail(KNN_EINVAL, "knn_debug_forest_round: parent[x] <= x does not hold on entry (start from parent[x] = x)");
+    for (long long i = 0; i < n; ++i)
+        if (cand[i] != KNN_FOREST_NONE && ((long long)(unsigned)cand[i] >= n || (long long)(unsigned)cand[i] == i))
+            return fail(KNN_EINVAL, "knn_debug_forest_round: a candidate names the row itself or a row outside 0 .. n - 1");
+    const int threads = std::min(16, std::max(1, *added));
+    // every step over all rows, row i on thread i % threads, a join between two steps (the launches' order on the stream)
+    const auto step = [&](const std::function<void(long long)> &row) {
+        if (threads == 1) {
+            for (long long i = 0; i < n; ++i)
+                row(i);
+            return;
+        }
+        std::vector<std::thread> pool;
+        for (int t = 0; t < threads; ++t)
+            pool.emplace_back([&, t] {
+                for (long long i = t; i < n; i += threads)
+                    row(i);
+            });
+        for (std::thread &th : pool)
+            th.join();
+    };
+    // the kernels' own lines (knn_forest_pick.h, knn_cluster_uf.h) with the host's atomics
+    std::vector<unsigned long long> pick1((size_t)n);
+    std::vector<unsigned> pick2((size_t)n);
+    const unsigned before = count[0];
+    unsigned raised = 0u;
+    step([&](long long i) {   // flatten
+        knn_forest_flatten<KnnPickHost>(parent, i);
+        knn_forest_clear(pick1.data(), pick2.data(), i);
+    });
+    step([&](long long i) { knn_forest_offer1<KnnPickHost>(parent, cand, pick1.data(), i); });
+    step([&](long long i) { knn_forest_offer2<KnnPickHost>(parent, cand, pick1.data(), pick2.data(), i); });
+    step([&](long long i) { (void)knn_forest_emit<KnnPickHost>(parent, pick1.data(), pick2.data(), i, n, edge_keys, edge_hi, count, &raised); });
+    step([&](long long i) { knn_forest_hook<KnnPickHost>(parent, pick1.data(), pick2.data(), i); });
+    *added = (int)(count[0] - before);
+    return KNN_OK;
+}
+
 int knn_debug_self_routed_plan(const long long in[16], long long out[8])
 {
     // knn_debug_count_plan's inputs with m = the call's rows, which lie inside the shard; its outputs, [6] from the self-scan's plan
@@ -3318,6 +3454,81 @@ extern "C" int knn_index_self_cluster_within_routed_host(knn_index *idx, float m
     const char *const who = "knn_index_self_cluster_within_routed_host";
     KNN_TRY(cluster_routed_check(who, max_dist2, flags));
     return cluster_host_run(who, knn_index_self_cluster_within_routed, idx, max_dist2, min_pts, flags, labels_host, core_host, info);
+}
+
+// The forest of the whole shard on the host: the device call on the default stream (every round queued), copied back, the edges
+// SORTED ascending by (E's bits, i, j) — the order single linkage merges in.
+extern "C" int knn_index_self_forest_within_host(knn_index *idx, float max_dist2, unsigned flags, int *labels_host, int *lo_host,
+                                                 int *hi_host, float *dist2_host, long long info[4])
+{
+    const char *const who = "knn_index_self_forest_within_host";
+    KNN_TRY(forest_check(who, max_dist2, flags));
+    if (!lo_host || !hi_host)
+        return fail_in(KNN_EINVAL, who, "null lo or hi");
+    if (!idx)
+        return fail_in(KNN_EINVAL, who, "null index");
+    std::lock_guard<std::recursive_mutex> lock(idx->mu);
+    if (idx->n > INT_MAX)
+        return fail_in(KNN_EINVAL, who, "more than INT_MAX rows (labels and edge ends are int row numbers)");
+    DeviceGuard guard(idx->device);
+    if (!guard.ok)
+        return fail_in(KNN_EHIP, who, "hipSetDevice failed");
+    const size_t n = (size_t)idx->n;
+    long long tally[4] = {0, 0, 0, 0};
+    if (n > 0) {
+        Staging stage(idx->device);
+        int *labels_dev = nullptr;
+        u64 *keys_dev = nullptr;
+        unsigned *his_dev = nullptr, *count_dev = nullptr;
+        hipError_t e = stage.get(&labels_dev, n * sizeof(int));
+        if (e == hipSuccess)
+            e = stage.get(&keys_dev, n * sizeof(u64));
+        if (e == hipSuccess)
+            e = stage.get(&his_dev, n * sizeof(unsigned));
+        if (e == hipSuccess)
+            e = stage.get(&count_dev, 2 * sizeof(unsigned));
+        if (e != hipSuccess)
+            return fail_in(KNN_EHIP, who, "staging the forest", hipGetErrorString(e));
+        const int rv = knn_index_self_forest_within(idx, 0, max_dist2, labels_dev, keys_dev, his_dev, count_dev, nullptr, flags);
+        if (rv != KNN_OK)
+            return rv;
+        unsigned count[2] = {0u, 0u};
+        e = hipMemcpy(count, count_dev, sizeof count, hipMemcpyDeviceToHost);
+        const size_t edges = std::min<size_t>(count[0], n);
+        std::vector<u64> keys(edges);
+        std::vector<unsigned> his(edges);
+        if (e == hipSuccess && edges > 0)
+            e = hipMemcpy(keys.data(), keys_dev, edges * sizeof(u64), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && edges > 0)
+            e = hipMemcpy(his.data(), his_dev, edges * sizeof(unsigned), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && labels_host)
+            e = hipMemcpy(labels_host, labels_dev, n * sizeof(int), hipMemcpyDeviceToHost);
+        if (e != hipSuccess)
+            return fail_in(KNN_EHIP, who, "D2H forest", hipGetErrorString(e));
+        std::vector<size_t> order(edges);
+        for (size_t t = 0; t < edges; ++t)
+            order[t] = t;
+        std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return keys[a] != keys[b] ? keys[a] < keys[b] : his[a] < his[b]; });
+        for (size_t t = 0; t < edges; ++t) {
+            const u64 key = keys[order[t]];
+            lo_host[t] = (int)(unsigned)key;
+            hi_host[t] = (int)his[order[t]];
+            if (dist2_host) {
+                const unsigned bits = (unsigned)(key >> 32);
+                memcpy(&dist2_host[t], &bits, sizeof bits);
+            }
+        }
+        long long stats[4] = {0, 0, 0, 0};
+        KNN_TRY(knn_index_last_stats(idx, stats));
+        tally[0] = (long long)edges;
+        tally[1] = (long long)(n - edges);
+        tally[2] = std::min<long long>(knn_forest_rounds(idx->n), (long long)count[1] + 1);   // (the first round that adds nothing ends the run)
+        tally[3] = stats[2];
+        // (not declared waited: the buffers go back after the device-wide wait `stage` then makes itself, as the other host calls)
+    }
+    if (info)
+        memcpy(info, tally, sizeof tally);
+    return KNN_OK;
 }
 
 extern "C" int knn_index_list_within_masked_host(knn_index *idx, int m, const float *queries_host, float max_dist2,

@@ -1001,6 +1001,69 @@ hipError_t knn_cells_cluster_link(FilterState &st, FilterWorkspace &w, const Cel
 // The link sweep of the whole shard in passes of KNN_CELL_BATCH own rows (knn_cells_cluster_link).
 hipError_t knn_filter_cluster_link_cells(FilterState &st, const CellTopkPlan &tp, int slot, const ClusterCall &c);
 
+// ---- minimum spanning forest of the radius graph (knn_forest.hip, knn_forest_pick.h, knn_grid.hip; DESIGN §4.6 "Minimum spanning
+// forest") ------------------------------------------------------------------------------------------------------------------------
+// ROUNDS(n) = max(1, ceil(log2 n)): the unfinished components at least halve in every Borůvka round.
+inline int knn_forest_rounds(long long n)
+{
+    int t = 0;
+    while (t < 62 && (1ll << t) < n)
+        ++t;
+    return t < 1 ? 1 : t;
+}
+// One knn_index_self_forest_within call, as the launches below take it.  labels is the caller's array: the union-find forest
+// (labels[i] = a row <= i of i's component) during the call, depth 1 — the answer — behind knn_forest_labels_launch.
+struct ForestCall {
+    int k = 0;
+    long long n = 0;               // the shard's rows, 1 .. INT_MAX
+    const float *r = nullptr;      // device [n][k]
+    float max_dist2 = INFINITY;    // the radius, squared (>= 0, never -0; +INF: every pair with a finite distance)
+    int num_cu = 0;
+    hipStream_t stream = nullptr;
+    int rounds = 0;                // knn_forest_rounds(n): all of them are queued
+    int *labels = nullptr;         // device [n]
+    u64 *edge_keys = nullptr;      // device [n]: E's bits << 32 | i
+    unsigned *edge_hi = nullptr;   // device [n]: j
+    unsigned *count = nullptr;     // device [2]: edges; rounds that added one
+    // the slot's scratch (knn_forest_layout):
+    u64 *cand = nullptr;           // [n] the round's candidate keys
+    u64 *pick1 = nullptr;          // [n] a root's smallest (E's bits << 32 | lo)
+    unsigned *pick2 = nullptr;     // [n] the smallest hi among the offers that match it
+    unsigned *done = nullptr;      // [(n + 31) / 32] bit i: row i found no candidate in some round
+    unsigned *words = nullptr;     // [2 * rounds + 2]: the gates of rounds 0 .. rounds, the rounds' give-up words, the statistics word
+    // round t's kernels run when *gate(t) != 0; round t - 1's emit raises it (round 0: no gate)
+    const unsigned *gate(int t) const { return t > 0 ? words + t : nullptr; }
+    unsigned *raise(int t) const { return words + t + 1; }                   // what round t's emit raises
+    unsigned *giveup(int t) const { return words + rounds + 1 + t; }         // round t's grid scan: some row passed rmax rings
+    unsigned *stat() const { return words + 2 * rounds + 1; }               // the give-up word of the last round that ran
+};
+// Everything a call launches and the slot scratch it needs (host arithmetic only; knn_debug_forest_plan shows it).
+struct ForestPlan {
+    int rounds = 0;
+    int chunks = 0;                  // launches of one round's exact scan: chunks of <= KNN_TOPK_CHUNK rows
+    long long slices = 0;            // blocks along the shard's rows of the first chunk's scan (knn_count_slices)
+    long long launches_exact = 0;    // kernel launches of the whole call on the exact way: per round flatten, the scan's chunks, two offers, emit, hook; the last flatten
+    long long launches_grid = 0;     // ... on the grid way: per round the grid scan as well, the exact scan gated on its give-up word
+    size_t cand_off = 0, pick1_off = 0, pick2_off = 0, done_off = 0, words_off = 0;
+    size_t zero_bytes = 0;           // done bits and words: zeroed at the start of every call
+    size_t scratch_bytes = 0;
+};
+ForestPlan knn_forest_plan(long long n, int num_cu);
+void knn_forest_layout(ForestCall &c, const ForestPlan &p, void *scratch);
+// count <- {0, 0}; the done bits and the words <- 0.  (Two memsets, no kernel.)
+hipError_t knn_forest_begin_launch(const ForestCall &c, const ForestPlan &p);
+// Round t's flatten: labels[i] <- i (t == 0) or root(i); cand, pick1, pick2 <- empty; the statistics word <- 0.
+hipError_t knn_forest_flatten_launch(const ForestCall &c, int t);
+// Round t's exact scan: cand[i] <- min(cand[i], the smallest key of a row of another component within the radius).  also: a
+// second gate (the round's give-up word behind the grid scan), null on the exact way.
+hipError_t knn_forest_scan_launch(const ForestCall &c, int t, const unsigned *also);
+// Round t's scan on the grid (knn_grid.hip): one wave per row walks its rings.  rmax: CountPlan::rmax at the call's radius.
+hipError_t knn_grid_forest_scan(const GridState *gs, int rmax, const ForestCall &c, int t);
+// Round t's pick and hook: offer 1 (which also marks the rows without a candidate done), offer 2, emit, hook.
+hipError_t knn_forest_pick_launch(const ForestCall &c, int t);
+// Behind the last round: labels[i] <- root(i) when that round added an edge (else they are depth 1 already).  Labels alone.
+hipError_t knn_forest_labels_launch(const ForestCall &c);
+
 // ---- RCCL exchange step (knn_rccl.cpp; librccl is dlopen'ed at first use) -------------------
 #ifdef __cplusplus
 #include <string>

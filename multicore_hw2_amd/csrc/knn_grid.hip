@@ -700,6 +700,112 @@ __global__ __launch_bounds__(GRID_BLOCK) void knn_grid_cluster_link_kernel(const
     }
 }
 
+// ---- the scan step of knn_index_self_forest_within on the grid (include/knn_mi355x.h 2o; knn_forest.hip describes the round) ----
+// The link kernel's SELF walk once more — one wave per local row qi, lanes take the cells of a ring — with the Borůvka hit path: a
+// row i = orig[p] != qi with E finite, E <= cap and labels[i] != labels[qi] (the labels are frozen: this kernel only reads them)
+// folds the key (E's bits, i) into the lane's minimum; the wave reduces it ring by ring and lane 0 stores cand[qi] once, when some
+// lane folded a key.  A walk ends by the radius clause OR by the 1-NN kernel's clause on the best key so far — every unseen row
+// is farther than the nearest foreign row found —, so a row whose nearest foreign row is close does not walk out to the radius.
+// A row that is done (it had no candidate in an earlier round: components only grow) walks nothing.  A wave that passes rmax rings
+// raises the round's give-up word (and the call's statistics word) and stores what it has: the gated exact scan of the round
+// folds every candidate again with an atomic min, which is idempotent.  gate: the round's word (null: round 0).
+template <int KD>
+__global__ __launch_bounds__(GRID_BLOCK) void knn_grid_forest_scan_kernel(const float *__restrict__ Q, int m, GridGeom gg,
+                                                                          const unsigned *__restrict__ start,
+                                                                          const f4g *__restrict__ pts, const unsigned *__restrict__ orig,
+                                                                          const int *__restrict__ labels,
+                                                                          const unsigned *__restrict__ done_bits, u64 *__restrict__ cand,
+                                                                          int rmax, const unsigned *__restrict__ gate,
+                                                                          unsigned *__restrict__ giveup, unsigned *__restrict__ stat,
+                                                                          float cap)
+{
+#pragma clang fp contract(off)
+    if (gate && *gate == 0u)
+        return;
+    const int lane = threadIdx.x & 63;
+    const int qi = blockIdx.x * (GRID_BLOCK / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (qi >= m)
+        return;
+    const unsigned own = (unsigned)qi;
+    if (((done_bits[own >> 5] >> (own & 31u)) & 1u) != 0u)   // wave-uniform
+        return;
+    float q[4] = {0.f, 0.f, 0.f, 0.f};
+    bool finite = true;
+#pragma unroll
+    for (int d = 0; d < KD; ++d) {
+        q[d] = Q[(size_t)qi * KD + d];
+        finite = finite && fabsf(q[d]) < INFINITY;
+    }
+    if (!finite)   // no row can be a hit (and nothing to give up on)
+        return;
+    const int mine = labels[own];
+    u64 best = kKeyInit;
+    int c[4];
+    (void)grid_cell_of(gg, q, c);
+    int gmax = 1;
+#pragma unroll
+    for (int d = 0; d < KD; ++d)
+        gmax = gg.g[d] > gmax ? gg.g[d] : gmax;
+    bool done = false;
+    bool first_ring = true;   // (rings 0 and 1 together, as the 1-NN kernel)
+    for (int r = gmax > 1 ? 1 : 0; r < gmax && r <= rmax; ++r) {
+        const int side = 2 * r + 1;
+        int total = 1;
+#pragma unroll
+        for (int d = 0; d < KD; ++d)
+            total *= side;
+        u64 near = kKeyInit;
+        for (int idx = lane; idx < total; idx += KNN_WAVE) {
+            unsigned cell;
+            if (!grid_ring_cell<KD>(gg, c, r, side, idx, first_ring, &cell))
+                continue;
+            const unsigned p0 = start[cell], p1 = start[cell + 1];
+            for (unsigned p = p0; p < p1; ++p) {
+                const f4g x = pts[p];
+                float acc = 0.0f;
+#pragma unroll
+                for (int d = 0; d < KD; ++d) {
+                    const float diff = q[d] - x[d];   // v0: search - reference, squared, summed in order
+                    const float sq = diff * diff;
+                    acc = acc + sq;
+                }
+                if (acc < INFINITY && acc <= cap) {
+                    const unsigned row = orig[p];
+                    if (row != own && labels[row] != mine) {
+                        const u64 key = ((u64)__float_as_uint(acc) << 32) | (u64)row;
+                        near = key < near ? key : near;
+                    }
+                }
+            }
+        }
+        first_ring = false;
+        near = grid_wave_min(near);
+        best = near < best ? near : best;
+        bool covers_all;
+        const double lb = grid_face_bound<KD>(gg, c, q, r, &covers_all);
+        if (covers_all) {
+            done = true;
+            break;
+        }
+        if (lb > 0.0) {
+            const double reach = lb * lb * (1.0 - 1e-6);
+            const float bd = __uint_as_float((unsigned)(best >> 32));   // (+INF while no key is in)
+            if ((double)cap < reach || (double)bd < reach) {   // no unseen row is within the radius, or none can beat or tie the best
+                done = true;
+                break;
+            }
+        }
+    }
+    if (lane == 0) {
+        if (best != kKeyInit)
+            cand[qi] = best;
+        if (!done && gmax > rmax + 1) {
+            *giveup = 1u;      // benign race: every writer stores 1
+            *stat = 1u;
+        }
+    }
+}
+
 // ---- host -------------------------------------------------------------------------------------------
 #define GTRY(call)                     \
     do {                                 \
@@ -1105,6 +1211,32 @@ hipError_t knn_grid_cluster_link(const GridState *gs, int rmax, int slot, const 
     }
 #undef GRID_CLUSTER_LINK
     return grid_batch_end(b, s, nullptr, gate_out);
+}
+
+// The scan step of round `round` of a forest call on the grid way, asynchronous on c.stream: one batch of c.n queries — the shard's
+// rows in local order — through knn_grid_forest_scan_kernel.  The give-up word is the round's own (ForestCall::giveup), not the
+// slot's alternating pair: a round that its gate keeps shut must leave no word behind for the next batch.  The caller queues the
+// exact scan of the round gated on that word.
+hipError_t knn_grid_forest_scan(const GridState *gs, int rmax, const ForestCall &c, int round)
+{
+    if (!gs || !gs->usable || c.n <= 0 || c.n > 0x7FFFFFFFll || c.k != gs->geom.k || !c.r || !c.labels || !c.cand || !c.done || !c.words ||
+        rmax < 0 || round < 0 || round >= c.rounds)
+        return hipErrorInvalidValue;
+    hipStream_t s = c.stream;
+    const int m = (int)c.n;
+    const dim3 grid((unsigned)((m + GRID_BLOCK / 64 - 1) / (GRID_BLOCK / 64))), block(GRID_BLOCK);
+#define GRID_FOREST_SCAN(KDV)                                                                                                        \
+    hipLaunchKernelGGL(knn_grid_forest_scan_kernel<KDV>, grid, block, 0, s, c.r, m, gs->geom, gs->start, gs->pts, gs->orig,          \
+                       (const int *)c.labels, (const unsigned *)c.done, c.cand, rmax, c.gate(round), c.giveup(round), c.stat(),      \
+                       c.max_dist2)
+    switch (gs->geom.k) {
+    case 1: GRID_FOREST_SCAN(1); break;
+    case 2: GRID_FOREST_SCAN(2); break;
+    case 3: GRID_FOREST_SCAN(3); break;
+    default: GRID_FOREST_SCAN(4); break;
+    }
+#undef GRID_FOREST_SCAN
+    return hipGetLastError();
 }
 
 long long knn_grid_radius_rings(const GridState *gs, float max_dist2)
