@@ -1,6 +1,6 @@
 // knn_cluster.hip — density clustering of the shard's own rows on the radius graph (include/knn_mi355x.h 2m; DESIGN §4.6
 // "Clusters of the radius graph"): knn_index_self_cluster_within behind its degree step.  (The grid way's link kernel lives
-// beside the walk it shares in knn_grid.hip; the union-find itself in knn_cluster_uf.h.)
+// in knn_grid.hip, on grid_walk, the ring walk of that file's kernels; the union-find itself in knn_cluster_uf.h.)
 //
 // The call is three steps on one stream, no host round trip between them, all in the caller's labels array:
 //   1. degrees    the routed self count (2k) over the whole shard writes deg(i) into labels[i]; knn_cluster_core_kernel turns that

@@ -1,6 +1,6 @@
 // knn_forest.hip — the minimum spanning forest of the shard's own rows on the radius graph (include/knn_mi355x.h 2o; DESIGN §4.6
-// "Minimum spanning forest"): the rounds of knn_index_self_forest_within.  (The grid way's scan kernel lives beside the walk it
-// shares in knn_grid.hip; the pick and the hook's decision lines in knn_forest_pick.h; the union-find in knn_cluster_uf.h.)
+// "Minimum spanning forest"): the rounds of knn_index_self_forest_within.  (The grid way's scan kernel lives in knn_grid.hip, on
+// grid_walk, the ring walk of that file's kernels; the pick and the hook's decision lines in knn_forest_pick.h; the union-find in knn_cluster_uf.h.)
 //
 // Borůvka, ROUNDS(n) = max(1, ceil(log2 n)) rounds, all queued on one stream with no host round trip.  Every kernel of round
 // t > 0 starts with "*gate == 0 -> return" on the word round t - 1's emit raises when it stores an edge: a forest that is

@@ -276,6 +276,83 @@ __device__ __forceinline__ double grid_face_bound(const GridGeom &gg, const int 
     return lb;
 }
 
+// Query qi's K coordinates into q (the rest 0); false when one of them is not finite: every distance is then NaN or +INF and no
+// row can be an answer.
+template <int K>
+__device__ __forceinline__ bool grid_query_load(const float *__restrict__ Q, int qi, float q[4])
+{
+    bool finite = true;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+        q[d] = d < K ? Q[(size_t)qi * K + d] : 0.f;
+        finite = finite && fabsf(q[d]) < INFINITY;
+    }
+    return finite;
+}
+
+// The ring walk of one wave for the finite query q, shared by the 1-NN, radius, link and forest kernels (the top-K kernels'
+// lanes share cells and walk under a ballot: knn_grid_topk_body.inc).  Ring r's positions of the (2r+1)^K block go to the lanes 64
+// at a time; the first pass takes rings 0 and 1 together (the whole 3^K block): with ~3 rows per cell the own cell alone almost
+// never satisfies a stop rule, and every ring is a chain of dependent loads (cell bounds -> rows).  The forms differ in three
+// places, their functors:
+//   row(acc, p)   for every row position p of a taken cell, acc = its v0 distance (core.cu:44-49: search - reference, squared,
+//                 summed in order); every test on acc is the form's own;
+//   ring_end()    after the cells of EVERY ring, the one that ends the walk included, before the bound is made: the forms that
+//                 keep a wave minimum reduce it here, and what a form keeps per ring is its own to reset here;
+//   stop(reach)   the form's stop clause, asked when the block of rings 0..r is not the whole grid and lb > 0: every unseen
+//                 row's computed distance is strictly above reach = lb^2 (1 - 1e-6) (grid_face_bound); true ends the walk.
+// A query far outside the box, or in an empty region, would walk O(r^K) cells per ring: past rmax rings the walk ends
+// unfinished.  Returns whether the wave must raise the give-up word that un-gates the exact scan queued behind the kernel:
+// unfinished, and the grid has rings beyond rmax.  Wave-uniform: the query, its cell, r and what stop() says decide it.
+template <int K, class Row, class RingEnd, class Stop>
+__device__ __forceinline__ bool grid_walk(const GridGeom &gg, const unsigned *__restrict__ start, const f4g *__restrict__ pts,
+                                          const float q[4], int lane, int rmax, Row row, RingEnd ring_end, Stop stop)
+{
+#pragma clang fp contract(off)
+    int c[4];
+    (void)grid_cell_of(gg, q, c);
+    int gmax = 1;
+#pragma unroll
+    for (int d = 0; d < K; ++d)
+        gmax = gg.g[d] > gmax ? gg.g[d] : gmax;
+    bool done = false;
+    bool first = true;
+    for (int r = gmax > 1 ? 1 : 0; r < gmax && r <= rmax; ++r) {
+        // the cells of ring r: positions of the (2r+1)^K block whose largest |offset| is exactly r
+        const int side = 2 * r + 1;
+        int total = 1;
+#pragma unroll
+        for (int d = 0; d < K; ++d)
+            total *= side;
+        for (int idx = lane; idx < total; idx += KNN_WAVE) {
+            unsigned cell;
+            if (!grid_ring_cell<K>(gg, c, r, side, idx, first, &cell))
+                continue;
+            const unsigned p0 = start[cell], p1 = start[cell + 1];
+            for (unsigned p = p0; p < p1; ++p) {
+                const f4g x = pts[p];
+                float acc = 0.0f;
+#pragma unroll
+                for (int d = 0; d < K; ++d) {
+                    const float diff = q[d] - x[d];   // v0: search - reference, squared, summed in order
+                    const float sq = diff * diff;
+                    acc = acc + sq;
+                }
+                row(acc, p);
+            }
+        }
+        first = false;
+        ring_end();
+        bool covers_all;
+        const double lb = grid_face_bound<K>(gg, c, q, r, &covers_all);
+        if (covers_all || (lb > 0.0 && stop(lb * lb * (1.0 - 1e-6)))) {
+            done = true;
+            break;
+        }
+    }
+    return !done && gmax > rmax + 1;
+}
+
 template <int K>
 __global__ __launch_bounds__(GRID_BLOCK) void knn_grid_query_kernel(const float *__restrict__ Q, int m, GridGeom gg,
                                                                     const unsigned *__restrict__ start,
@@ -294,79 +371,30 @@ __global__ __launch_bounds__(GRID_BLOCK) void knn_grid_query_kernel(const float 
     const int qi = blockIdx.x * (GRID_BLOCK / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (qi >= m)
         return;
-    float q[4] = {0.f, 0.f, 0.f, 0.f};
-    bool finite = true;
-#pragma unroll
-    for (int d = 0; d < K; ++d) {
-        q[d] = Q[(size_t)qi * K + d];
-        finite = finite && fabsf(q[d]) < INFINITY;
-    }
-    if (!finite)
+    float q[4];
+    if (!grid_query_load<K>(Q, qi, q))
         return;   // every distance is NaN or +INF: v0 keeps (+INF, index 0) = the key's initial value
-    int c[4];
-    (void)grid_cell_of(gg, q, c);
-    int gmax = 1;
-#pragma unroll
-    for (int d = 0; d < K; ++d)
-        gmax = gg.g[d] > gmax ? gg.g[d] : gmax;
-
-    u64 best = kKeyInit;
-    bool done = false;
-    // (a query far outside the box, or in an empty region, would walk O(r^K) cells per ring: past rmax rings
-    // it gives up and raises the flag that un-gates the brute-force scan queued behind this kernel)
-    // The first pass takes rings 0 and 1 together (the whole 3^K block): with ~3 rows per cell the own cell alone
-    // almost never satisfies the stop rule, and every ring is a chain of dependent loads (cell bounds -> rows).
-    bool first = true;
-    for (int r = gmax > 1 ? 1 : 0; r < gmax && r <= rmax; ++r) {
-        // the cells of ring r: positions of the (2r+1)^K block whose largest |offset| is exactly r
-        const int side = 2 * r + 1;
-        int total = 1;
-#pragma unroll
-        for (int d = 0; d < K; ++d)
-            total *= side;
-        u64 mine = kKeyInit;
-        for (int idx = lane; idx < total; idx += KNN_WAVE) {
-            unsigned cell;
-            if (!grid_ring_cell<K>(gg, c, r, side, idx, first, &cell))
-                continue;
-            const unsigned p0 = start[cell], p1 = start[cell + 1];
-            for (unsigned p = p0; p < p1; ++p) {
-                const f4g x = pts[p];
-                float acc = 0.0f;
-#pragma unroll
-                for (int d = 0; d < K; ++d) {
-                    const float diff = q[d] - x[d];   // v0: search - reference, squared, summed in order
-                    const float sq = diff * diff;
-                    acc = acc + sq;
-                }
-                if (acc < INFINITY) {                 // NaN / +INF never beat +INF (v0's strict >)
-                    const u64 key = ((u64)__float_as_uint(acc) << 32) | (u64)(unsigned)(base + orig[p]);
-                    mine = key < mine ? key : mine;
-                }
+    u64 best = kKeyInit, mine = kKeyInit;   // the wave's minimum so far; the lane's of the ring at hand
+    const bool gave_up = grid_walk<K>(
+        gg, start, pts, q, lane, rmax,
+        [&](float acc, unsigned p) {
+            if (acc < INFINITY) {   // NaN / +INF never beat +INF (v0's strict >)
+                const u64 key = ((u64)__float_as_uint(acc) << 32) | (u64)(unsigned)(base + orig[p]);
+                mine = key < mine ? key : mine;
             }
-        }
-        first = false;
-        mine = grid_wave_min(mine);
-        best = mine < best ? mine : best;
-        // stop rule (grid_face_bound): every unseen row is at least lb away
-        bool covers_all;
-        const double lb = grid_face_bound<K>(gg, c, q, r, &covers_all);
-        if (covers_all) {
-            done = true;
-            break;
-        }
-        if (lb > 0.0) {
-            const float bd = __uint_as_float((unsigned)(best >> 32));
-            if ((double)bd < lb * lb * (1.0 - 1e-6)) {
-                done = true;
-                break;
-            }
-        }
-    }
+        },
+        [&] {
+            mine = grid_wave_min(mine);
+            best = mine < best ? mine : best;
+            mine = kKeyInit;
+        },
+        [&](double reach) {   // no unseen row can beat or tie the best
+            return (double)__uint_as_float((unsigned)(best >> 32)) < reach;
+        });
     if (lane == 0) {
         if (best < kKeyInit)   // a real row's key: folding it in is right whether or not the search finished
             __hip_atomic_fetch_min(&keys[qi], best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (!done && gmax > rmax + 1)
+        if (gave_up)
             *giveup = 1u;      // benign race: every writer stores 1
     }
 }
@@ -433,8 +461,9 @@ __global__ __launch_bounds__(GRID_BLOCK) void knn_grid_within_kernel(const float
 
 // ---- counts and lists within a radius (KNN_QUERY_COUNT_GRID) ---------------------------------------
 // Eight entry points of one walk, knn_grid_radius_body.inc (the description is there): each fixes the switches LIST, EACH, SELF and MASKED
-// and names, as null or zero constants, the arguments it does not take.  (A body file and not a function template, as the top-K
-// kernels above: every form keeps its argument list, its name and its code.)
+// and names, as null or zero constants, the arguments it does not take.  (A body file and not a function template over
+// grid_walk: as a function template the same text compiled to 2 to 6 VGPRs more in every kernel of KD 2..4, with the first face
+// of grid_face_bound held as a select: profiles/grid_walk_refactor.txt has the figures and what is supposed about the cause.)
 #define GRID_RADIUS_NO_LIST /* a count form reserves and stores nothing */   \
     constexpr long long base = 0;                                            \
     constexpr const u64 *offsets = nullptr;                                  \
@@ -594,9 +623,8 @@ __global__ __launch_bounds__(GRID_BLOCK) void knn_grid_masked_list_kernel(const 
 #undef GRID_RADIUS_NO_MASK
 
 // ---- the link sweep of knn_index_self_cluster_within on the grid (include/knn_mi355x.h 2m; knn_cluster.hip describes the call) ----
-// knn_grid_radius_body.inc's walk with SELF at the scalar radius — one wave per query (local row qi), lanes take the cells of a
-// ring, the same stop clause, ring limit and give-up word — written out here as a sibling and not as a fifth switch of the body
-// file: the eight kernels made from that file keep their code.  A hit is a row i = orig[p] != qi with E finite and E <= cap; the
+// knn_grid_radius_body.inc's walk with SELF at the scalar radius — one wave per query (local row qi) on grid_walk, the same stop
+// clause, ring limit and give-up word.  A hit is a row i = orig[p] != qi with E finite and E <= cap; the
 // hit path is knn_cluster_link_kernel's: both rows core and i < qi — the lane unites (knn_cluster_uf.h; every lane has its own
 // cached root, a member of row qi's set); row qi not core and i core — the key (E's bits, i) goes into the lane's minimum, the
 // wave reduces it with shuffles and lane 0 issues one atomic min on best[qi], only when some lane folded a key.
@@ -618,90 +646,42 @@ __global__ __launch_bounds__(GRID_BLOCK) void knn_grid_cluster_link_kernel(const
     const int qi = blockIdx.x * (GRID_BLOCK / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (qi >= m)
         return;
-    float q[4] = {0.f, 0.f, 0.f, 0.f};
-    bool finite = true;
-#pragma unroll
-    for (int d = 0; d < KD; ++d) {
-        q[d] = Q[(size_t)qi * KD + d];
-        finite = finite && fabsf(q[d]) < INFINITY;
-    }
-    if (!finite)   // no row can be a hit (and nothing to give up on)
+    float q[4];
+    if (!grid_query_load<KD>(Q, qi, q))   // no row can be a hit (and nothing to give up on)
         return;
     const unsigned own = (unsigned)qi;
     const bool jcore = ((core[own >> 5] >> (own & 31u)) & 1u) != 0u;   // wave-uniform
     int croot = qi;
     u64 near = kKeyInit;
-    int c[4];
-    (void)grid_cell_of(gg, q, c);
-    int gmax = 1;
-#pragma unroll
-    for (int d = 0; d < KD; ++d)
-        gmax = gg.g[d] > gmax ? gg.g[d] : gmax;
-    bool done = false;
-    bool first_ring = true;   // (rings 0 and 1 together, as the 1-NN kernel)
-    for (int r = gmax > 1 ? 1 : 0; r < gmax && r <= rmax; ++r) {
-        const int side = 2 * r + 1;
-        int total = 1;
-#pragma unroll
-        for (int d = 0; d < KD; ++d)
-            total *= side;
-        for (int idx = lane; idx < total; idx += KNN_WAVE) {
-            unsigned cell;
-            if (!grid_ring_cell<KD>(gg, c, r, side, idx, first_ring, &cell))
-                continue;
-            const unsigned p0 = start[cell], p1 = start[cell + 1];
-            for (unsigned p = p0; p < p1; ++p) {
-                const f4g x = pts[p];
-                float acc = 0.0f;
-#pragma unroll
-                for (int d = 0; d < KD; ++d) {
-                    const float diff = q[d] - x[d];   // v0: search - reference, squared, summed in order
-                    const float sq = diff * diff;
-                    acc = acc + sq;
-                }
-                if (acc < INFINITY && acc <= cap) {
-                    const unsigned row = orig[p];
-                    if (row != own && ((core[row >> 5] >> (row & 31u)) & 1u) != 0u) {
-                        if (jcore) {
-                            if (row < own && KnnUfDevice::load(&parent[row]) != croot)
-                                croot = knn_uf_unite<KnnUfDevice>(parent, (int)row, croot);
-                        } else {
-                            const u64 key = ((u64)__float_as_uint(acc) << 32) | (u64)row;
-                            near = key < near ? key : near;
-                        }
+    const bool gave_up = grid_walk<KD>(
+        gg, start, pts, q, lane, rmax,
+        [&](float acc, unsigned p) {
+            if (acc < INFINITY && acc <= cap) {
+                const unsigned row = orig[p];
+                if (row != own && ((core[row >> 5] >> (row & 31u)) & 1u) != 0u) {
+                    if (jcore) {
+                        if (row < own && KnnUfDevice::load(&parent[row]) != croot)
+                            croot = knn_uf_unite<KnnUfDevice>(parent, (int)row, croot);
+                    } else {
+                        const u64 key = ((u64)__float_as_uint(acc) << 32) | (u64)row;
+                        near = key < near ? key : near;
                     }
                 }
             }
-        }
-        first_ring = false;
-        bool covers_all;
-        const double lb = grid_face_bound<KD>(gg, c, q, r, &covers_all);
-        if (covers_all) {
-            done = true;
-            break;
-        }
-        if (lb > 0.0 && (double)cap < lb * lb * (1.0 - 1e-6)) {   // no unseen row is within the radius
-            done = true;
-            break;
-        }
-    }
-    if (!jcore) {   // (wave-uniform)
-#pragma unroll
-        for (int step = 32; step > 0; step >>= 1) {
-            const u64 o = __shfl_xor(near, step, KNN_WAVE);
-            near = o < near ? o : near;
-        }
-    }
+        },
+        [] {}, [&](double reach) { return (double)cap < reach; });   // no unseen row is within the radius
+    if (!jcore)   // (wave-uniform)
+        near = grid_wave_min(near);
     if (lane == 0) {
         if (near != kKeyInit)
             __hip_atomic_fetch_min(&best[qi], near, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (!done && gmax > rmax + 1)
+        if (gave_up)
             *giveup = 1u;      // benign race: every writer stores 1
     }
 }
 
 // ---- the scan step of knn_index_self_forest_within on the grid (include/knn_mi355x.h 2o; knn_forest.hip describes the round) ----
-// The link kernel's SELF walk once more — one wave per local row qi, lanes take the cells of a ring — with the Borůvka hit path: a
+// The link kernel's SELF walk — one wave per local row qi on grid_walk — with the Borůvka hit path: a
 // row i = orig[p] != qi with E finite, E <= cap and labels[i] != labels[qi] (the labels are frozen: this kernel only reads them)
 // folds the key (E's bits, i) into the lane's minimum; the wave reduces it ring by ring and lane 0 stores cand[qi] once, when some
 // lane folded a key.  A walk ends by the radius clause OR by the 1-NN kernel's clause on the best key so far — every unseen row
@@ -729,77 +709,34 @@ __global__ __launch_bounds__(GRID_BLOCK) void knn_grid_forest_scan_kernel(const 
     const unsigned own = (unsigned)qi;
     if (((done_bits[own >> 5] >> (own & 31u)) & 1u) != 0u)   // wave-uniform
         return;
-    float q[4] = {0.f, 0.f, 0.f, 0.f};
-    bool finite = true;
-#pragma unroll
-    for (int d = 0; d < KD; ++d) {
-        q[d] = Q[(size_t)qi * KD + d];
-        finite = finite && fabsf(q[d]) < INFINITY;
-    }
-    if (!finite)   // no row can be a hit (and nothing to give up on)
+    float q[4];
+    if (!grid_query_load<KD>(Q, qi, q))   // no row can be a hit (and nothing to give up on)
         return;
     const int mine = labels[own];
-    u64 best = kKeyInit;
-    int c[4];
-    (void)grid_cell_of(gg, q, c);
-    int gmax = 1;
-#pragma unroll
-    for (int d = 0; d < KD; ++d)
-        gmax = gg.g[d] > gmax ? gg.g[d] : gmax;
-    bool done = false;
-    bool first_ring = true;   // (rings 0 and 1 together, as the 1-NN kernel)
-    for (int r = gmax > 1 ? 1 : 0; r < gmax && r <= rmax; ++r) {
-        const int side = 2 * r + 1;
-        int total = 1;
-#pragma unroll
-        for (int d = 0; d < KD; ++d)
-            total *= side;
-        u64 near = kKeyInit;
-        for (int idx = lane; idx < total; idx += KNN_WAVE) {
-            unsigned cell;
-            if (!grid_ring_cell<KD>(gg, c, r, side, idx, first_ring, &cell))
-                continue;
-            const unsigned p0 = start[cell], p1 = start[cell + 1];
-            for (unsigned p = p0; p < p1; ++p) {
-                const f4g x = pts[p];
-                float acc = 0.0f;
-#pragma unroll
-                for (int d = 0; d < KD; ++d) {
-                    const float diff = q[d] - x[d];   // v0: search - reference, squared, summed in order
-                    const float sq = diff * diff;
-                    acc = acc + sq;
-                }
-                if (acc < INFINITY && acc <= cap) {
-                    const unsigned row = orig[p];
-                    if (row != own && labels[row] != mine) {
-                        const u64 key = ((u64)__float_as_uint(acc) << 32) | (u64)row;
-                        near = key < near ? key : near;
-                    }
+    u64 best = kKeyInit, near = kKeyInit;   // the wave's minimum so far; the lane's of the ring at hand
+    const bool gave_up = grid_walk<KD>(
+        gg, start, pts, q, lane, rmax,
+        [&](float acc, unsigned p) {
+            if (acc < INFINITY && acc <= cap) {
+                const unsigned row = orig[p];
+                if (row != own && labels[row] != mine) {
+                    const u64 key = ((u64)__float_as_uint(acc) << 32) | (u64)row;
+                    near = key < near ? key : near;
                 }
             }
-        }
-        first_ring = false;
-        near = grid_wave_min(near);
-        best = near < best ? near : best;
-        bool covers_all;
-        const double lb = grid_face_bound<KD>(gg, c, q, r, &covers_all);
-        if (covers_all) {
-            done = true;
-            break;
-        }
-        if (lb > 0.0) {
-            const double reach = lb * lb * (1.0 - 1e-6);
-            const float bd = __uint_as_float((unsigned)(best >> 32));   // (+INF while no key is in)
-            if ((double)cap < reach || (double)bd < reach) {   // no unseen row is within the radius, or none can beat or tie the best
-                done = true;
-                break;
-            }
-        }
-    }
+        },
+        [&] {
+            near = grid_wave_min(near);
+            best = near < best ? near : best;
+            near = kKeyInit;
+        },
+        [&](double reach) {   // no unseen row is within the radius, or none can beat or tie the best (+INF while no key is in)
+            return (double)cap < reach || (double)__uint_as_float((unsigned)(best >> 32)) < reach;
+        });
     if (lane == 0) {
         if (best != kKeyInit)
             cand[qi] = best;
-        if (!done && gmax > rmax + 1) {
+        if (gave_up) {
             *giveup = 1u;      // benign race: every writer stores 1
             *stat = 1u;
         }
@@ -813,6 +750,16 @@ __global__ __launch_bounds__(GRID_BLOCK) void knn_grid_forest_scan_kernel(const 
         if (e_ != hipSuccess)            \
             return e_;                   \
     } while (0)
+
+// The kernel form for k dimensions (1 .. 4: knn_grid_build takes no other).  LAUNCH(KD) is a statement (or an if / else chain of
+// launches) that names a kernel's <KD> instance.
+#define GRID_KD_SWITCH(k, LAUNCH)  \
+    switch (k) {                   \
+    case 1: LAUNCH(1); break;      \
+    case 2: LAUNCH(2); break;      \
+    case 3: LAUNCH(3); break;      \
+    default: LAUNCH(4); break;     \
+    }
 
 struct GridState {
     bool usable = false;
@@ -990,12 +937,11 @@ hipError_t knn_grid_query(const GridState *gs, int slot, int m, const float *q, 
     const int k = gs->geom.k;
     const int rmax = grid_rmax_1nn(k);
     const dim3 grid((unsigned)((m + GRID_BLOCK / 64 - 1) / (GRID_BLOCK / 64))), block(GRID_BLOCK);
-    switch (k) {
-    case 1: hipLaunchKernelGGL(knn_grid_query_kernel<1>, grid, block, 0, s, q, m, gs->geom, gs->start, gs->pts, gs->orig, base, keys, rmax, giveup, giveup_next); break;
-    case 2: hipLaunchKernelGGL(knn_grid_query_kernel<2>, grid, block, 0, s, q, m, gs->geom, gs->start, gs->pts, gs->orig, base, keys, rmax, giveup, giveup_next); break;
-    case 3: hipLaunchKernelGGL(knn_grid_query_kernel<3>, grid, block, 0, s, q, m, gs->geom, gs->start, gs->pts, gs->orig, base, keys, rmax, giveup, giveup_next); break;
-    default: hipLaunchKernelGGL(knn_grid_query_kernel<4>, grid, block, 0, s, q, m, gs->geom, gs->start, gs->pts, gs->orig, base, keys, rmax, giveup, giveup_next); break;
-    }
+#define GRID_QUERY(KDV)                                                                                                              \
+    hipLaunchKernelGGL(knn_grid_query_kernel<KDV>, grid, block, 0, s, q, m, gs->geom, gs->start, gs->pts, gs->orig, base, keys, rmax, \
+                       giveup, giveup_next)
+    GRID_KD_SWITCH(k, GRID_QUERY)
+#undef GRID_QUERY
     *gate_out = giveup;
     return hipGetLastError();
 }
@@ -1086,12 +1032,7 @@ hipError_t knn_grid_query_topk(const GridState *gs, const GridTopkPlan &plan, in
     else                                                                                                                             \
         hipLaunchKernelGGL(knn_grid_topk_kernel<KDV>, b.grid, b.block, 0, s, c.q, c.m, c.K, gs->geom, gs->start, gs->pts, gs->orig,  \
                            c.base, lists, plan.rmax, b.giveup, b.giveup_next)
-    switch (gs->geom.k) {
-    case 1: GRID_TOPK(1); break;
-    case 2: GRID_TOPK(2); break;
-    case 3: GRID_TOPK(3); break;
-    default: GRID_TOPK(4); break;
-    }
+    GRID_KD_SWITCH(gs->geom.k, GRID_TOPK)
 #undef GRID_TOPK
     GTRY(grid_batch_end(b, s, c.ev1, gate_out));
     GTRY(knn_exact_topk_launch(c.writing(lists), b.giveup, true));
@@ -1129,12 +1070,7 @@ hipError_t knn_grid_query_count(const GridState *gs, int rmax, int slot, const C
     else                                                                                                                             \
         hipLaunchKernelGGL(knn_grid_count_kernel<KDV>, b.grid, b.block, 0, s, c.q, c.m, gs->geom, gs->start, gs->pts, c.scratch,     \
                            rmax, b.giveup, b.giveup_next, c.max_dist2)
-    switch (gs->geom.k) {
-    case 1: GRID_COUNT(1); break;
-    case 2: GRID_COUNT(2); break;
-    case 3: GRID_COUNT(3); break;
-    default: GRID_COUNT(4); break;
-    }
+    GRID_KD_SWITCH(gs->geom.k, GRID_COUNT)
 #undef GRID_COUNT
 #undef GRID_COUNT_SELF
     GTRY(grid_batch_end(b, s, c.ev1, gate_out));
@@ -1175,12 +1111,7 @@ hipError_t knn_grid_query_list(const GridState *gs, int rmax, int slot, const Li
     else                                                                                                                             \
         hipLaunchKernelGGL(knn_grid_list_kernel<KDV>, b.grid, b.block, 0, s, c.q, c.m, gs->geom, gs->start, gs->pts, gs->orig,       \
                            c.base, c.offsets, c.scratch, c.keys, rmax, b.giveup, b.giveup_next, c.max_dist2)
-    switch (gs->geom.k) {
-    case 1: GRID_LIST(1); break;
-    case 2: GRID_LIST(2); break;
-    case 3: GRID_LIST(3); break;
-    default: GRID_LIST(4); break;
-    }
+    GRID_KD_SWITCH(gs->geom.k, GRID_LIST)
 #undef GRID_LIST
 #undef GRID_LIST_SELF
     GTRY(grid_batch_end(b, s, c.ev1, gate_out));
@@ -1203,12 +1134,7 @@ hipError_t knn_grid_cluster_link(const GridState *gs, int rmax, int slot, const 
 #define GRID_CLUSTER_LINK(KDV)                                                                                                       \
     hipLaunchKernelGGL(knn_grid_cluster_link_kernel<KDV>, b.grid, b.block, 0, s, c.r, m, gs->geom, gs->start, gs->pts, gs->orig,     \
                        c.parent, (const unsigned *)c.core, c.best, rmax, b.giveup, b.giveup_next, c.max_dist2)
-    switch (gs->geom.k) {
-    case 1: GRID_CLUSTER_LINK(1); break;
-    case 2: GRID_CLUSTER_LINK(2); break;
-    case 3: GRID_CLUSTER_LINK(3); break;
-    default: GRID_CLUSTER_LINK(4); break;
-    }
+    GRID_KD_SWITCH(gs->geom.k, GRID_CLUSTER_LINK)
 #undef GRID_CLUSTER_LINK
     return grid_batch_end(b, s, nullptr, gate_out);
 }
@@ -1229,12 +1155,7 @@ hipError_t knn_grid_forest_scan(const GridState *gs, int rmax, const ForestCall 
     hipLaunchKernelGGL(knn_grid_forest_scan_kernel<KDV>, grid, block, 0, s, c.r, m, gs->geom, gs->start, gs->pts, gs->orig,          \
                        (const int *)c.labels, (const unsigned *)c.done, c.cand, rmax, c.gate(round), c.giveup(round), c.stat(),      \
                        c.max_dist2)
-    switch (gs->geom.k) {
-    case 1: GRID_FOREST_SCAN(1); break;
-    case 2: GRID_FOREST_SCAN(2); break;
-    case 3: GRID_FOREST_SCAN(3); break;
-    default: GRID_FOREST_SCAN(4); break;
-    }
+    GRID_KD_SWITCH(gs->geom.k, GRID_FOREST_SCAN)
 #undef GRID_FOREST_SCAN
     return hipGetLastError();
 }

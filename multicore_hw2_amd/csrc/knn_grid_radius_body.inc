@@ -8,7 +8,7 @@
 // — and provide KD, the arguments Q, m, gg, start, pts, rmax, giveup, giveup_next by their names, and every one of orig, first,
 // base, out, offsets, cursor, keys, radii, cap, mask: as its argument, or as a constant null / zero stand-in where the form has none.
 //
-// One wave per query, the 1-NN kernel's walk: lanes take the cells of ring r, and a row is a hit when its v0 distance E is finite,
+// One wave per query on grid_walk (knn_grid.hip): lanes take the cells of ring r, and a row is a hit when its v0 distance E is finite,
 // E <= rad and E <= cap (fp32 compares, equality inside; the scalar forms' rad is cap, so theirs is one compare).  One wave per
 // query, so radii[qi] is wave-uniform as the scalar radius is.
 // Stop rule, after ring r: the block of rings 0..r is the whole grid, or bound < lb^2 (1 - 1e-6) — the radius clause of
@@ -43,13 +43,8 @@
     const int qi = blockIdx.x * (GRID_BLOCK / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (qi >= m)
         return;
-    float q[4] = {0.f, 0.f, 0.f, 0.f};
-    bool finite = true;
-#pragma unroll
-    for (int d = 0; d < KD; ++d) {
-        q[d] = Q[(size_t)qi * KD + d];
-        finite = finite && fabsf(q[d]) < INFINITY;
-    }
+    float q[4];
+    const bool finite = grid_query_load<KD>(Q, qi, q);
     const float rad = EACH ? radii[qi] : cap;
     if (!finite || (EACH && !knn_each_has(rad))) {   // no row can be a hit (and nothing to give up on)
         if (!LIST && lane == 0)
@@ -58,72 +53,35 @@
     }
     const float bound = EACH ? knn_each_bound(rad, cap) : cap;
     const unsigned own = first + (unsigned)qi;
-    int c[4];
-    (void)grid_cell_of(gg, q, c);
-    int gmax = 1;
-#pragma unroll
-    for (int d = 0; d < KD; ++d)
-        gmax = gg.g[d] > gmax ? gg.g[d] : gmax;
     const u64 off = LIST ? offsets[qi] : 0ull, end = LIST ? offsets[qi + 1] : 0ull;
     const u64 room64 = end > off ? end - off : 0ull;
     const unsigned room = room64 < 0xFFFFFFFFull ? (unsigned)room64 : 0xFFFFFFFFu;   // (the cursor is 32-bit)
 
     unsigned cnt = 0u;
-    bool done = false;
-    bool first_ring = true;   // (rings 0 and 1 together, as the 1-NN kernel)
-    for (int r = gmax > 1 ? 1 : 0; r < gmax && r <= rmax; ++r) {
-        const int side = 2 * r + 1;
-        int total = 1;
-#pragma unroll
-        for (int d = 0; d < KD; ++d)
-            total *= side;
-        for (int idx = lane; idx < total; idx += KNN_WAVE) {
-            unsigned cell;
-            if (!grid_ring_cell<KD>(gg, c, r, side, idx, first_ring, &cell))
-                continue;
-            const unsigned p0 = start[cell], p1 = start[cell + 1];
-            for (unsigned p = p0; p < p1; ++p) {
-                const f4g x = pts[p];
-                float acc = 0.0f;
-#pragma unroll
-                for (int d = 0; d < KD; ++d) {
-                    const float diff = q[d] - x[d];   // v0: search - reference, squared, summed in order
-                    const float sq = diff * diff;
-                    acc = acc + sq;
-                }
-                if (acc < INFINITY && acc <= rad && acc <= cap) {
-                    if (!LIST && MASKED) {
-                        const unsigned row = orig[p];
-                        cnt += (mask[row >> 5] >> (row & 31u)) & 1u;
-                    } else if (!LIST) {
-                        cnt += !SELF || orig[p] != own ? 1u : 0u;
-                    } else if (SELF || MASKED) {
-                        const unsigned row = orig[p];
-                        if (SELF ? row != own : ((mask[row >> 5] >> (row & 31u)) & 1u) != 0u) {
-                            const unsigned place = atomicAdd(&cursor[qi], 1u);
-                            if (place < room)
-                                keys[off + place] = ((u64)__float_as_uint(acc) << 32) | (u64)(unsigned)(base + (long long)row);
-                        }
-                    } else {
+    const bool gave_up = grid_walk<KD>(
+        gg, start, pts, q, lane, rmax,
+        [&](float acc, unsigned p) {
+            if (acc < INFINITY && acc <= rad && acc <= cap) {
+                if (!LIST && MASKED) {
+                    const unsigned row = orig[p];
+                    cnt += (mask[row >> 5] >> (row & 31u)) & 1u;
+                } else if (!LIST) {
+                    cnt += !SELF || orig[p] != own ? 1u : 0u;
+                } else if (SELF || MASKED) {
+                    const unsigned row = orig[p];
+                    if (SELF ? row != own : ((mask[row >> 5] >> (row & 31u)) & 1u) != 0u) {
                         const unsigned place = atomicAdd(&cursor[qi], 1u);
                         if (place < room)
-                            keys[off + place] = ((u64)__float_as_uint(acc) << 32) | (u64)(unsigned)(base + (long long)orig[p]);
+                            keys[off + place] = ((u64)__float_as_uint(acc) << 32) | (u64)(unsigned)(base + (long long)row);
                     }
+                } else {
+                    const unsigned place = atomicAdd(&cursor[qi], 1u);
+                    if (place < room)
+                        keys[off + place] = ((u64)__float_as_uint(acc) << 32) | (u64)(unsigned)(base + (long long)orig[p]);
                 }
             }
-        }
-        first_ring = false;
-        bool covers_all;
-        const double lb = grid_face_bound<KD>(gg, c, q, r, &covers_all);
-        if (covers_all) {
-            done = true;
-            break;
-        }
-        if (lb > 0.0 && (double)bound < lb * lb * (1.0 - 1e-6)) {   // no unseen row is within the query's bound
-            done = true;
-            break;
-        }
-    }
+        },
+        [] {}, [&](double reach) { return (double)bound < reach; });   // no unseen row is within the query's bound
     if (!LIST) {
 #pragma unroll
         for (int step = 32; step > 0; step >>= 1)
@@ -132,6 +90,6 @@
     if (lane == 0) {
         if (!LIST)
             out[qi] = cnt;
-        if (!done && gmax > rmax + 1)
+        if (gave_up)
             *giveup = 1u;      // benign race: every writer stores 1
     }

@@ -1,6 +1,8 @@
 """knn_index_self_forest_within on the uniform-grid index (KNN_QUERY_COUNT_GRID) on the GPU: the scan kernel at KD 2 and 4
-(tests/cluster_rows.uniform_planted), a radius that spans ten rings (cluster_rows.column: a walk ends on the radius clause or on
-the nearest foreign row, whichever comes first, and most components hang on single links), and +INF with the flag, where rows
+(tests/cluster_rows.uniform_planted) and at KD 1 and 3 (tests/test_within_grid_gpu.rows_and_queries: half the rows uniform, half in
+a cluster, at a radius that leaves isolated rows, small components and one large one), a radius that spans ten rings
+(cluster_rows.column: a walk ends on the radius clause or on the nearest foreign row, whichever comes first, and most components
+hang on single links), and +INF with the flag, where rows
 deep inside a component pass the ring limit, the round's exact scan answers and knn_index_last_stats [2] says so.  Bar: sorted
 edges and labels equal tests/forest_oracle.py's and the exact way's on the same index; for the infinite radius (n = 20000: no
 oracle) the exact way's alone."""
@@ -12,6 +14,7 @@ import multicore_hw2_amd as pkg
 from tests import cluster_rows as cr
 from tests import forest_oracle as fo
 from tests.forest_helper import assert_forest, run_forest
+from tests.test_within_grid_gpu import rows_and_queries
 
 pytestmark = pytest.mark.gpu
 BASE = 5
@@ -25,8 +28,8 @@ def _options():
     pkg.set_option("path", 0)
 
 
-def both_ways(ix, R, cap, gave_up=0):
-    w = fo.forest(R, R.shape[1], cap)
+def both_ways(ix, R, cap, gave_up=0, want=None):
+    w = want if want is not None else fo.forest(R, R.shape[1], cap)
     labels, table, count, st = run_forest(ix, cap, grid=True)
     print(f"grid: {len(table)} edges, {np.unique(labels).size} components, {count[1]} rounds of {fo.rounds_of(len(R))}, stats {st}")
     assert st == [3, 0, gave_up, 0], st
@@ -57,6 +60,21 @@ def test_the_grid_scan_kernel_at_two_and_four_dimensions(k):
         np.testing.assert_array_equal(forced, labels)
     finally:
         pkg.set_option("path", 0)
+        ix.close()
+
+
+@pytest.mark.parametrize("k, r", [(1, 2.0 ** -13), (3, 2.0 ** -6)])
+def test_the_grid_scan_kernel_at_one_and_three_dimensions(k, r):
+    R, _ = rows_and_queries(k, 16384 + 7, 8, 6400 + k)            # the smallest shard that gets a grid index, and a few rows
+    want = fo.forest(R, k, r * r)
+    sizes = np.bincount(want["labels"])                           # on the CPU, before the GPU is touched
+    print(f"k={k}: {(sizes == 1).sum()} isolated rows, {((sizes >= 3) & (sizes < 64)).sum()} components of 3 .. 63 rows, "
+          f"the largest of {sizes.max()}")
+    assert (sizes == 1).sum() >= 32 and ((sizes >= 3) & (sizes < 64)).sum() >= 32 and sizes.max() > 4096
+    ix = pkg.KnnIndex(k, R, base_index=BASE)
+    try:
+        both_ways(ix, R, r * r, want=want)
+    finally:
         ix.close()
 
 

@@ -31,7 +31,7 @@ def kind_max(r, kind):
     return float(r[eo.KINDS.index(kind)::len(eo.KINDS)].max())
 
 
-@pytest.mark.parametrize("k", [3, 1])
+@pytest.mark.parametrize("k", [3, 1, 2, 4])
 def test_scalar_and_per_row_radii_are_exact_on_the_grid_and_never_list_the_own_row(k):
     R = np.random.default_rng(8100 + k).random((N, k), dtype=np.float32)
     src, twin, outside = plant_duplicates(R, FIRST)
